@@ -2,7 +2,7 @@
  *
  * TEST INFRASTRUCTURE ONLY (CPU oracle).
  *
- * Restates (all under /root/reference/prover/src):
+ * Restates (all under the reference's prover/src):
  *   Column::eval_table             cross_table_lookup.rs:313-333 (next-row terms count as 0 on the last row)
  *   Filter::eval_table             cross_table_lookup.rs:106-117
  *   get_helper_cols                cross_table_lookup.rs:709-797 (dummy 1 before inversion, zeroed afterwards; filters must be 0/1)

@@ -3,7 +3,7 @@
  * TEST INFRASTRUCTURE ONLY (the CPU oracle).  Nothing under zkm_amd/ may include this.
  *
  * The arithmetic lives in the un-vendored dependency plonky2_field 0.1.1 (zkMIPS/plonky2 @ zkm_dev,
- * rev f1e28a6d, /root/reference/prover/examples/Cargo.lock:3233-3283); the reference only calls it
+ * rev f1e28a6d, the reference's prover/examples/Cargo.lock:3233-3283); the reference only calls it
  * (e.g. prover/src/prover.rs:595, 690-696).  Results are mathematically determined, so any correct
  * implementation is bit-exact after canonicalisation.  Every value here is kept canonical (< p).
  * Domain constants (generator, 2^32-th root, non-residue 7) are the published Goldilocks parameters

@@ -3,7 +3,7 @@
  * TEST INFRASTRUCTURE ONLY (CPU oracle / CPU baseline).
  *
  * The reference calls tiny-keccak 2.0.2 `keccakf` (crates.io dependency, not in the tree) through
- * /root/reference/prover/src/cpu/kernel/keccak_util.rs:6-31; this file restates the published
+ * the reference's prover/src/cpu/kernel/keccak_util.rs:6-31; this file restates the published
  * Keccak-f[1600] permutation (FIPS 202 §3.2-3.3: theta, rho, pi, chi, iota; 24 rounds).  Pinned by the
  * in-tree known-answer test keccak_util.rs:39-59 (tests/golden/keccakf_kat.json) and by the standard
  * Keccak-256 digests.  Sponge padding as keccak_sponge_stark.rs:334-341.

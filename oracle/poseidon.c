@@ -2,7 +2,7 @@
  *
  * TEST INFRASTRUCTURE ONLY (CPU oracle / CPU baseline).
  *
- * Permutation: restates the in-tree copy at /root/reference/prover/src/poseidon/poseidon_stark.rs
+ * Permutation: restates the in-tree copy at the reference's prover/src/poseidon/poseidon_stark.rs
  *   poseidon_with_witness :51-64, full_rounds :65-77, partial_rounds :79-95, constant_layer :164-169,
  *   sbox_monomial :239-251, mds_layer :310-331 / mds_row_shf :333-345, mds_partial_layer_init :392-404,
  *   mds_partial_layer_fast :463-487, parameter tables constants.rs:11-870.

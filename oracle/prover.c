@@ -2,7 +2,7 @@
  *
  * TEST INFRASTRUCTURE ONLY (CPU oracle / CPU baseline).
  *
- * Follows, in this order of authority (all under /root/reference/prover/src):
+ * Follows, in this order of authority (all under the reference's prover/src):
  *   prover.rs:441-641   prove_single_table (stage order, transcript order)
  *   prover.rs:645-789   compute_quotient_polys (step / next_step, Z_H, Lagrange first/last, chunking :560-575)
  *   stark.rs:91-148     fri_instance (three batches: zeta, g*zeta, 1)

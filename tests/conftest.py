@@ -3,9 +3,6 @@ import sys
 
 import pytest
 
-# the launcher's job: read by the HIP runtime at the first HIP call of the process
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)

@@ -4,7 +4,7 @@
 Sources (data only -- inputs and expected outputs):
   * poseidon_kat.json : the two upstream plonky2 Goldilocks-Poseidon test vectors.
   * keccakf_kat.json  : the Keccak-f[1600] input/output u64 states held by the reference's own test
-                        /root/reference/prover/src/cpu/kernel/keccak_util.rs:42-49 (parsed from there when the
+                        the reference's prover/src/cpu/kernel/keccak_util.rs:42-49 (parsed from there when the
                         reference is readable), plus the standard Keccak-256 digests of b"" and b"abc".
 """
 import json
@@ -12,7 +12,7 @@ import os
 import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference/prover/src/cpu/kernel/keccak_util.rs"
+REF = os.path.join(os.environ.get("ZKM_REFERENCE_ROOT", "reference"), "prover/src/cpu/kernel/keccak_util.rs")   # ZKM_REFERENCE_ROOT: a checkout of the reference
 
 poseidon = {
     "source": "plonky2 poseidon_goldilocks test_vectors (SURVEY.md App. B.1)",

@@ -154,7 +154,7 @@ def test_bench_sharding_path_two_rank_gloo(tmp_path, nctx, backend, stack):
 
 def test_bench_started_as_a_plain_process_relaunches_itself_under_torchrun(tmp_path, monkeypatch):
     """`python bench.py --gpus N` -- the driver's N = 1 command with N swapped -- used to exit with a hint.  Started without
-    a launcher's environment it now replaces itself by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
+    a launcher's environment it now runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
     127.0.0.1 --master-port <free> bench.py ...` (zkm_amd.dist.self_launch): both ranks run, rank 0 prints the one JSON line.  A process
     that HAS a launcher's environment and the wrong world is an error, not a relaunch."""
     script = tmp_path / "bench_worker.py"
@@ -320,3 +320,68 @@ def test_cpu_baseline_is_measured_in_the_run(tmp_path):
     """) % ROOT
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout + r.stderr
+
+
+DUMP_WORKER = textwrap.dedent("""
+    # bench.py --gpus 1 with a stub Context: the timed step count, ms_per_step and --dump-outputs (the last timed step's proof)
+    import sys, time, types
+    sys.path.insert(0, %r)
+    import numpy as np, torch
+    import zkm_amd
+    proved = []
+    class Buf:
+        def __init__(self, seed): self.seed = seed
+        def upload(self, a): return self
+        def free(self): pass
+    class StubContext:
+        def __init__(self, device): pass
+        def poseidon_trace(self, seed, n, log_n): return Buf(seed)
+        def alloc(self, words): return Buf(None)
+        def prove_single_table(self, trace, log_n, aux, nh):
+            proved.append(trace.seed); time.sleep(0.005)
+            return np.arange(7, dtype=np.uint64) * np.uint64(0x100000001) + np.uint64(trace.seed << 40)
+        def prove_single_tables(self, traces, log_n, aux, nh):
+            return [self.prove_single_table(t, log_n, aux, nh) for t in traces]
+        def set_tuning(self, key, value): pass
+        def profile(self, on): pass
+        def profile_reset(self): pass
+        def profile_records(self): return {"merkle_leaves": (1, 1.0)}
+        def close(self): pass
+    zkm_amd.Context = StubContext
+    torch.cuda.is_available = lambda: True
+    torch.cuda.set_device = lambda d: None
+    torch.cuda.synchronize = lambda: proved.append("sync")
+    torch.cuda.device_count = lambda: 1
+    torch.cuda.current_device = lambda: 0
+    torch.cuda.mem_get_info = lambda d=None: (200 << 30, 288 << 30)
+    torch.cuda.get_device_properties = lambda d: types.SimpleNamespace(multi_processor_count=256)
+    sys.argv = [__file__, "--gpus", "1", "--steps", "6", "--warmup", "1", "--log-n", "10", "--no-cpu-baseline", "--no-extras",
+                "--stack", %r, "--dump-outputs", %r]
+    import runpy
+    runpy.run_path(%r, run_name="__main__")
+    i0 = proved.index("sync"); i1 = proved.index("sync", i0 + 1)
+    assert sorted(proved[i0 + 1:i1]) == list(range(100, 106)), proved       # --steps 6: six timed proofs, seeds 100..105
+    print("WORKER OK")
+""")
+
+
+@pytest.mark.parametrize("stack", [1, 4])
+def test_bench_dump_outputs_writes_the_last_timed_proof(tmp_path, stack):
+    """--dump-outputs DIR: the proof of the last timed step (segment steps - 1, seed 100 + steps - 1) as exact float64 32-bit halves; the
+    line's ms_per_step is the timed region over --steps."""
+    out = tmp_path / "dump"
+    script = tmp_path / "dump_worker.py"
+    script.write_text(DUMP_WORKER % (ROOT, str(stack), str(out), os.path.join(ROOT, "bench.py")))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "TORCHELASTIC_RUN_ID")}
+    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "WORKER OK" in r.stdout
+    import json
+    import numpy as np
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert j["steps"] == 6 and j["timed_segments"] == 6 and abs(j["value"] * j["ms_per_step"] / 1e3 - 1) < 1e-6
+    lo, hi = np.load(out / "proof_lo32.npy"), np.load(out / "proof_hi32.npy")
+    assert lo.dtype == np.float64 and hi.dtype == np.float64 and sorted(os.listdir(out)) == ["proof_hi32.npy", "proof_lo32.npy"]
+    want = np.arange(7, dtype=np.uint64) * np.uint64(0x100000001) + np.uint64(105 << 40)
+    got = lo.astype(np.uint64) | (hi.astype(np.uint64) << np.uint64(32))
+    assert (got == want).all()

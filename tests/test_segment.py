@@ -250,7 +250,7 @@ def test_pure_c_caller_proves_the_segment_image(ctx, zkm, oracle, tmp_path):
     path = tmp_path / "segment.zkmtrace"
     img.tofile(path)
     out = tmp_path / "proofs.bin"
-    r = subprocess.run([exe, str(path), str(out)], capture_output=True, text=True, timeout=300, env=dict(os.environ, GPU_MAX_HW_QUEUES="16"))
+    r = subprocess.run([exe, str(path), str(out)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     got = np.fromfile(out, dtype=np.uint64)
     want, chal, offs = ctx.prove_segment_image(img)

@@ -246,7 +246,7 @@ def multi_process_rate(procs, nctx, reps=8, tuning=""):
     process with k contexts and nothing else in it (the in-process `concurrent` figures share bench.py's process with its four
     headline contexts and torch)."""
     import subprocess
-    env = dict(os.environ, GPU_MAX_HW_QUEUES=str(max(2, 16 // procs)), ZKM_SEG_TUNING=tuning)   # ~16 hardware queues on the GPU in total
+    env = dict(os.environ, ZKM_SEG_TUNING=tuning)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "bench_segment_procs.py"), str(procs), str(nctx), str(reps)],
                        capture_output=True, text=True, timeout=300, env=env)
     if r.returncode != 0:
@@ -278,7 +278,7 @@ def lockstep_rates(device, shapes=((4, 8), (8, 8)), reps=3, sleeping_shape=(8, 8
     kernel's measured issue rate).  (16 x 8 reaches 111.7 segments/s = 0.95 of the budget in a process of its own and 100.7 as a child of
     bench.py -- sixteen polling threads are the box's whole 16-CPU quota -- so it is not one of the default shapes.)"""
     import subprocess
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", ZKM_BENCH_DEVICE=str(device))
+    env = dict(os.environ, ZKM_BENCH_DEVICE=str(device))
     specs = ["%d,%d,throughput_profile=1,reps=%d" % (g, k, reps) for g, k in shapes]
     # ... and one shape once more with SLEEPING host waits (blocking-sync device flag + block_after_us 0): the rate next to the host
     # CPUs it keeps busy (`host_cpus_busy`; polling: one per context)

@@ -16,11 +16,14 @@ pairs = [
     (f"{tag}_cfg/configs_with_counters.json", f"{tag}_configs_4_5.json"), (f"{tag}_cfg/fri_pmc.json", "fri_2_22_pmc.json"),
     (f"{tag}_cfg/sponge_pmc.json", "keccak_sponge_2_20_pmc.json"), (f"{tag}_cfg/fri_kernel_stats.csv", f"{tag}_fri_2_22_kernel_stats.csv"),
     (f"{tag}_cfg/sponge_kernel_stats.csv", f"{tag}_keccak_sponge_2_20_kernel_stats.csv"),
-    (f"{tag}_lockstep_kernel_stats.csv", f"{tag}_lockstep_kernel_stats.csv"), (f"{tag}_lockstep_valu.txt", f"{tag}_lockstep_valu.txt"),
-    ("lockstep_valu_latest.json", "lockstep_valu_latest.json"),
 ]
+# what tools/gpu_lockstep_prof.sh wrote under prof_out/
+L = os.path.join(ROOT, "prof_out")
+pairs += [(os.path.join(L, f"{tag}_lockstep_kernel_stats.csv"), f"{tag}_lockstep_kernel_stats.csv"),
+          (os.path.join(L, f"{tag}_lockstep_valu.txt"), f"{tag}_lockstep_valu.txt"),
+          (os.path.join(L, "lockstep_valu_latest.json"), "lockstep_valu_latest.json")]
 for src, dst in pairs:
-    s = os.path.join(G, src)
+    s = os.path.join(G, src)            # (an absolute src stays as it is)
     if os.path.isfile(s):
         shutil.copyfile(s, os.path.join(P, dst))
         print("copied", src, "->", "profiles/" + dst)

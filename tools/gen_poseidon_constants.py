@@ -27,7 +27,7 @@ N_PARTIAL = 22
 N_ROUNDS = 2 * HALF_FULL + N_PARTIAL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/prover/src/poseidon/constants.rs"
+REF = os.path.join(os.environ.get("ZKM_REFERENCE_ROOT", "reference"), "prover/src/poseidon/constants.rs")   # ZKM_REFERENCE_ROOT: a checkout of the reference
 OUTS = [os.path.join(ROOT, "zkm_amd", "csrc", "poseidon_constants.inc"),
         os.path.join(ROOT, "oracle", "poseidon_constants.inc")]
 

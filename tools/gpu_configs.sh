@@ -6,7 +6,6 @@ TAG=${1:-r04_e}
 R=$PWD
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-export GPU_MAX_HW_QUEUES=16
 python tools/bench_configs.py all > $O/configs.json 2> $O/configs.err; tail -c 600 $O/configs.json
 cd /tmp && export TMPDIR=/tmp
 for W in fri sponge; do

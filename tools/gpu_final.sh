@@ -5,13 +5,12 @@
 TAG=${1:-r05_z}
 O=gpurun_out/$TAG
 mkdir -p $O
-export GPU_MAX_HW_QUEUES=16
 timeout 1700 python -m pytest tests -m gpu -q -x --durations=6 > $O/pytest.log 2>&1; tail -10 $O/pytest.log
 bash tools/collect_pmc.sh $TAG > $O/collect.log 2>&1; tail -24 $O/collect.log
 cp gpurun_out/prof_$TAG/pmc_latest.json profiles/pmc_latest.json      # (on the GPU box: the bench line below quotes the traffic of THIS code)
 bash tools/gpu_configs.sh ${TAG}_cfg > $O/configs.log 2>&1; tail -30 $O/configs.log
 bash tools/gpu_lockstep_prof.sh $TAG 16 > $O/lockstep_prof.log 2>&1; tail -12 $O/lockstep_prof.log
-cp gpurun_out/lockstep_valu_latest.json profiles/lockstep_valu_latest.json
+cp prof_out/lockstep_valu_latest.json profiles/lockstep_valu_latest.json
 T0=$SECONDS; python bench.py > $O/bench.json 2> $O/bench.err; echo "bench.py wall $((SECONDS - T0)) s"; tail -c 300 $O/bench.err
 python tools/bench_segment.py 16 > $O/seg16.json 2> $O/seg16.err
 rm -rf gpurun_out/prof_$TAG/trace

@@ -4,7 +4,6 @@ call in lock-step (zkm_prove_single_tables) from G contexts: proofs per second. 
 import os, sys, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np  # noqa: E402
 import zkm_amd  # noqa: E402
 log_n = 20

@@ -8,7 +8,6 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import zkm_amd  # noqa: E402
 from tools.bench_segment import tiled_segment  # noqa: E402
 

@@ -8,7 +8,6 @@ SEGMENTS=${2:-64}
 PORT=${3:-29500}
 cd "$(dirname "$0")/.."
 export HSA_ENABLE_IPC_MODE_LEGACY=${HSA_ENABLE_IPC_MODE_LEGACY:-0}      # RCCL on this driver stack: dmabuf IPC
-export GPU_MAX_HW_QUEUES=${GPU_MAX_HW_QUEUES:-16}                      # streams of a process spread over 16 hardware queues
 if [ "$N" -le 1 ]; then
     exec python bench.py --gpus 1 --segments "$SEGMENTS" --steps "$SEGMENTS" --warmup 1 --no-extras
 fi

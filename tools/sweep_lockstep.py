@@ -8,7 +8,6 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 from tools.bench_segment import lockstep_segment_rate  # noqa: E402
 
 for spec in sys.argv[1:]:

@@ -480,18 +480,9 @@ const zkm_table_lookup* zkm_table_lookups(int table_id, size_t* n) {
     return nullptr;
 }
 
-// The HIP runtime spreads the streams of a process over GPU_MAX_HW_QUEUES hardware queues (default 4); streams that share one queue
-// run their kernels one after the other.  A process proving small segments with k contexts has k x ZKM_COMMIT_LANES streams (+ copy streams) whose
-// kernels are short and meant to overlap: with 8 contexts, 43 segments/s at 4 queues, 50 at 8, 57 at 16, 47 at 32
-// (profiles/r03_hw_queues.txt; the 2^20-row proofs do not care).  The variable is read when the runtime initialises, i.e. at the first
-// HIP call of the PROCESS: it belongs to the launcher (bench.py, tools/run_config3.sh, the Rust host's main()) -- a
-// shared library does not edit the environment of the process that loads it.  zkm_ctx_create reports an unset variable once, on stderr.
-static void zkm_hw_queues_hint() {
-    static std::atomic<bool> said{false};
-    if (getenv("GPU_MAX_HW_QUEUES") || getenv("ZKM_QUIET") || said.exchange(true)) return;
-    fprintf(stderr, "zkm-hip: GPU_MAX_HW_QUEUES is not set (runtime default: 4 hardware queues); small-segment throughput with several "
-                    "contexts is ~25 %% higher with GPU_MAX_HW_QUEUES=16 exported before the first HIP call (see INTEGRATION.md)\n");
-}
+// The HIP runtime spreads the streams of a process over its hardware queues (GPU_MAX_HW_QUEUES, default 4, read at the first HIP call of
+// the PROCESS); streams that share one queue run their kernels one after the other.  The setting belongs to whoever launches the
+// process: a shared library does not edit the environment of the process that loads it, and the library leaves the default alone.
 
 extern "C" {
 
@@ -513,7 +504,6 @@ int zkm_ctx_create(int device, zkm_ctx** out, char** err) {
         if (sscanf(part, "%d/%d", &k, &n) == 2) { c->cu_part_k = k; c->cu_part_n = n; }
     }
     ZKM_HIP_CHECK(zkm_stream_create(&c->stream, c->num_cus, c->cu_part_k, c->cu_part_n));
-    zkm_hw_queues_hint();
     g_live_contexts.fetch_add(1, std::memory_order_relaxed);
     *out = c;
     ZKM_API_END(err)

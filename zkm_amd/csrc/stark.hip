@@ -1,6 +1,6 @@
 // stark.hip -- prove_single_table on the GPU: quotient (K7-K9), openings (K10), FRI (K11-K14), queries.
 //
-// Host orchestration restates /root/reference/prover/src/prover.rs:441-641 (stage and transcript order);
+// Host orchestration restates the reference's prover/src/prover.rs:441-641 (stage and transcript order);
 // the kernels replace the rayon loops of compute_quotient_polys (:700-782), StarkOpeningSet::new
 // (proof.rs:299-334) and plonky2's PolynomialBatch::prove_openings / fri_proof.
 // The Challenger stays on the host (a few hundred field elements per table); only caps, openings,

@@ -33,8 +33,8 @@ def self_launch_command(nproc, argv, port=None):
 
 
 def self_launch(nproc, argv):
-    """`python bench.py --gpus N` started as a PLAIN process (no RANK / WORLD_SIZE in the environment): replace this process by the
-    torchrun launch of the same command line -- the multi-GPU job must be startable the way the single-GPU one is.  A
+    """`python bench.py --gpus N` started as a PLAIN process (no RANK / WORLD_SIZE in the environment): run the torchrun launch of the
+    same command line as a child process and exit with its status -- the multi-GPU job must be startable the way the single-GPU one is.  A
     process that already has a launcher's environment and the wrong world size is an error, not a relaunch (it would recurse)."""
     import sys
     if any(k in os.environ for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "TORCHELASTIC_RUN_ID")):
@@ -46,7 +46,8 @@ def self_launch(nproc, argv):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     print("zkm_amd.dist: relaunching as %d ranks: %s" % (nproc, " ".join(cmd)), file=sys.stderr, flush=True)
     sys.stdout.flush()
-    os.execv(cmd[0], cmd)
+    import subprocess
+    raise SystemExit(subprocess.call(cmd))
 
 
 def check_gpus(world, local_rank, share_gpu=False):
