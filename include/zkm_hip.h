@@ -239,6 +239,26 @@ int zkm_sha_compress_sponge_trace(zkm_ctx* ctx, const uint32_t* hx, const uint32
 #define ZKM_LOGIC_COLS 69
 int zkm_logic_trace(zkm_ctx* ctx, const uint32_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, char** err);
 
+/* ------------------------------------------------------------------ N3: MemoryStark witness
+ * MemoryStark::generate_trace (memory/memory_stark.rs:135-248) on the segment's raw memory operations: sort by (context, segment,
+ * virt, timestamp) keeping push order among equal keys, fill_gaps (dummy filter-0 reads bridging virt gaps and timestamp gaps above
+ * max_rc = next_pow2(nops) - 1), pad_memory_ops (filter-0 read copies of the last operation pushed), the R0 write rule of into_row,
+ * first-change flags, RANGE_CHECK, COUNTER and FREQUENCIES.  13 columns x 2^log_n rows, column-major, canonical; column order of
+ * memory/columns.rs (FILTER, TIMESTAMP, IS_READ, CONTEXT, SEGMENT, VIRTUAL, VALUE, three first-change flags, RANGE_CHECK,
+ * COUNTER, FREQUENCIES).  Word for word the CPU oracle's zko_memory_trace.
+ *   ops                nops x 6 words {context, segment, virt, timestamp, is_read (nonzero: read), value (truncated to 32 bits)},
+ *                      host or device; every op has filter 1 (MemoryOp::new)
+ *   out_dev            device pointer, or NULL: sizing only -- log_n is ignored and only *natural_rows_out is computed
+ *   natural_rows_out   next_pow2(nops + dummy rows), the reference's table height (may be NULL)
+ * Fails (nonzero, message in *err; the contents of out_dev are then unspecified) if nops is 0 or 2^32 or more, log_n is above
+ * ZKM_MEMORY_MAX_LOG_N, a key word is not below p, the dummy rows overflow (2^62 rows or more), the table needs more than 2^log_n
+ * rows (*natural_rows_out is still written), or a context / segment gap gives a range check of 2^log_n or more.  Synchronous on the
+ * context's stream. */
+#define ZKM_MEMORY_COLS 13
+#define ZKM_MEMORY_MAX_LOG_N 28
+int zkm_memory_trace(zkm_ctx* ctx, const uint64_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, size_t* natural_rows_out,
+                     char** err);
+
 /* ------------------------------------------------------------------ Fiat-Shamir (host)
  * plonky2 Challenger<F, PoseidonHash> (uses at prover.rs:182-190, 466, 524-527, 588-591, 610). */
 typedef struct {

@@ -1,0 +1,521 @@
+// memory_trace.hip -- MemoryStark witness from the raw memory operations (memory_stark.rs:135-248, oracle/ctl.c zko_memory_trace).
+//
+// The reference sorts the operations by (context, segment, virt, timestamp), appends the dummy reads of fill_gaps, pads with copies
+// of the last operation pushed, sorts again and then builds the rows.  Here:
+//   (1) k_mem_widths     OR of every key field (and a check that each is below p): the significant bits of the key;
+//   (2) k_mem_pack       the four fields packed into the fewest 64-bit words (timestamp lowest), plus the original index;
+//   (3) radix passes     a stable LSD sort of (key words, index), 8 bits a pass over the significant bits only: upsweep (per-tile
+//                        digit histograms), per-digit scan over the tiles, downsweep (in-tile stable rank from wave64 ballot
+//                        match masks, scatter).  Every hand-off between workgroups is a kernel boundary;
+//   (4) k_mem_gaps       the number of dummy rows after each sorted operation in closed form (fill_gaps :175-204), and the last
+//                        operation that has any;
+//   (5) scan             exclusive saturating scan of 1 + dummies: each operation's first row; the total is the table's height;
+//   (6) k_mem_rows       one thread per output row: the second sort is not needed, since every dummy lies strictly between its
+//                        pair's keys; the pad rows (copies of the last operation pushed, :206-224) go right behind that row;
+//   (7) k_mem_neighbours first-change flags, RANGE_CHECK, COUNTER and the FREQUENCIES histogram (:83-166).
+// Only the key widths and the row count come back to the host before the output is written.
+#include <algorithm>
+#include <memory>
+
+#include "zkm_internal.h"
+
+namespace {
+
+constexpr int MT_THREADS = 256;
+constexpr int MT_WAVES = MT_THREADS / 64;
+constexpr int MT_ITEMS = 8;                          // keys per lane and tile
+constexpr int MT_TILE = MT_THREADS * MT_ITEMS;       // 2048 keys per tile
+constexpr int MT_RADIX = 256;                        // 8-bit digits
+constexpr uint64_t MT_SAT = 1ull << 62;              // row counts saturate here (one timestamp gap can ask for 2^40 dummies)
+constexpr int MT_HIST_LDS = 2048;                    // FREQUENCIES bins kept in LDS (range checks are mostly small)
+constexpr unsigned MT_MAX_LOG_N = ZKM_MEMORY_MAX_LOG_N;
+
+struct mem_op {
+    uint64_t ctx, seg, virt, ts, is_read, value;
+};
+__device__ __forceinline__ mem_op load_op(const uint64_t* __restrict__ ops, uint32_t i) {
+    const uint64_t* o = ops + (size_t)6 * i;
+    return mem_op{o[0], o[1], o[2], o[3], o[4], o[5]};
+}
+
+// bit layout of the packed key: field f (0 context, 1 segment, 2 virt, 3 timestamp) at bits [shift[f], shift[f] + width[f])
+struct key_layout {
+    unsigned width[4], shift[4], nwords, bits;
+};
+
+__device__ __forceinline__ uint64_t sat_add(uint64_t a, uint64_t b) {   // a, b <= MT_SAT
+    uint64_t s = a + b;
+    return s > MT_SAT ? MT_SAT : s;
+}
+
+struct add_u32 { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; } };
+struct add_sat { __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return sat_add(a, b); } };
+
+// inclusive scan over the block (identity 0); *total = the block's sum.  sh: MT_WAVES words of LDS.  Every thread must call it.
+template <class T, class Op>
+__device__ __forceinline__ T block_incl_scan(T v, T* sh, Op op, T* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        T u = __shfl_up(v, o);
+        if (lane >= o) v = op(u, v);
+    }
+    if (lane == 63) sh[w] = v;
+    __syncthreads();
+    T pre = 0, all = 0;
+#pragma unroll
+    for (int q = 0; q < MT_WAVES; q++) {
+        if (q < w) pre = op(pre, sh[q]);
+        all = op(all, sh[q]);
+    }
+    __syncthreads();
+    *total = all;
+    return op(pre, v);
+}
+
+// ---- (1) key widths
+__global__ __launch_bounds__(MT_THREADS) void k_mem_widths(const uint64_t* __restrict__ ops, size_t nops, unsigned long long* acc) {
+    uint64_t o[4] = {0, 0, 0, 0}, bad = 0;
+    for (size_t i = (size_t)blockIdx.x * MT_THREADS + threadIdx.x; i < nops; i += (size_t)gridDim.x * MT_THREADS) {
+#pragma unroll
+        for (int f = 0; f < 4; f++) {
+            uint64_t v = ops[6 * i + f];
+            o[f] |= v;
+            bad |= v >= GL_P;
+        }
+    }
+#pragma unroll
+    for (int s = 32; s; s >>= 1) {
+#pragma unroll
+        for (int f = 0; f < 4; f++) o[f] |= __shfl_xor(o[f], s);
+        bad |= __shfl_xor(bad, s);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int f = 0; f < 4; f++)
+            if (o[f]) atomicOr(&acc[f], (unsigned long long)o[f]);
+        if (bad) atomicOr(&acc[4], 1ull);
+    }
+}
+
+// ---- (2) pack: keys[q * nops + i] = word q of op i's key, idx[i] = i
+__global__ __launch_bounds__(MT_THREADS) void k_mem_pack(const uint64_t* __restrict__ ops, uint32_t nops, key_layout L,
+                                                          uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+    size_t i = (size_t)blockIdx.x * MT_THREADS + threadIdx.x;
+    if (i >= nops) return;
+    uint64_t w[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int f = 0; f < 4; f++) {
+        if (!L.width[f]) continue;
+        const uint64_t v = ops[6 * i + f];
+        const unsigned word = L.shift[f] >> 6, b = L.shift[f] & 63;
+#pragma unroll
+        for (unsigned q = 0; q < 4; q++) {   // (constant indices: w stays in registers)
+            if (q == word) w[q] |= v << b;
+            if (q == word + 1 && b && b + L.width[f] > 64) w[q] |= v >> (64 - b);
+        }
+    }
+#pragma unroll
+    for (unsigned q = 0; q < 4; q++)
+        if (q < L.nwords) keys[(size_t)q * nops + i] = w[q];
+    idx[i] = (uint32_t)i;
+}
+
+// ---- (3) radix sort, one 8-bit digit at bit `bit` of the key
+// tile t = keys [t * MT_TILE, (t + 1) * MT_TILE); hist[d * ntiles + t] = keys of tile t with digit d
+__global__ __launch_bounds__(MT_THREADS) void k_radix_upsweep(const uint64_t* __restrict__ keys, uint32_t nops, unsigned bit,
+                                                               uint32_t* __restrict__ hist, uint32_t ntiles) {
+    __shared__ uint32_t h[MT_RADIX];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const uint64_t* kw = keys + (size_t)(bit >> 6) * nops;
+    const unsigned sh = bit & 63;
+    const size_t base = (size_t)blockIdx.x * MT_TILE;
+#pragma unroll
+    for (int it = 0; it < MT_ITEMS; it++) {
+        size_t i = base + (size_t)it * MT_THREADS + threadIdx.x;
+        if (i < nops) atomicAdd(&h[(kw[i] >> sh) & (MT_RADIX - 1)], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// one block per digit: hist row d becomes its exclusive scan over the tiles, tot[d] the digit's total
+__global__ __launch_bounds__(MT_THREADS) void k_radix_scan(uint32_t* __restrict__ hist, uint32_t ntiles, uint32_t* __restrict__ tot) {
+    __shared__ uint32_t sh[MT_WAVES];
+    uint32_t* row = hist + (size_t)blockIdx.x * ntiles;
+    uint32_t carry = 0;
+    for (uint32_t c = 0; c < ntiles; c += MT_THREADS) {
+        const uint32_t t = c + threadIdx.x;
+        const uint32_t v = t < ntiles ? row[t] : 0;
+        uint32_t all;
+        const uint32_t incl = block_incl_scan(v, sh, add_u32(), &all);
+        if (t < ntiles) row[t] = carry + incl - v;
+        carry += all;
+    }
+    if (threadIdx.x == 0) tot[blockIdx.x] = carry;
+}
+
+// Stable scatter.  Wave w of the block owns the contiguous run [tile + w 64 MT_ITEMS, + 64 MT_ITEMS) and walks it 64 keys at a time
+// in input order; a key's rank among equal digits of its wave = the wave's running count of that digit + the equal-digit lanes below
+// it (ballot match mask).  The waves' counts are then turned into exclusive offsets in wave order, on top of the digit's global base.
+__global__ __launch_bounds__(MT_THREADS) void k_radix_downsweep(const uint64_t* __restrict__ kin, const uint32_t* __restrict__ iin,
+                                                                 uint64_t* __restrict__ kout, uint32_t* __restrict__ iout, uint32_t nops,
+                                                                 unsigned nwords, unsigned bit, const uint32_t* __restrict__ hist,
+                                                                 const uint32_t* __restrict__ tot, uint32_t ntiles) {
+    __shared__ uint32_t cnt[MT_WAVES][MT_RADIX];
+    __shared__ uint32_t dbase[MT_RADIX];
+    __shared__ uint32_t sh[MT_WAVES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < MT_WAVES; q++) cnt[q][threadIdx.x] = 0;
+    {
+        const uint32_t t = tot[threadIdx.x];
+        uint32_t all;
+        const uint32_t incl = block_incl_scan(t, sh, add_u32(), &all);
+        dbase[threadIdx.x] = incl - t + hist[(size_t)threadIdx.x * ntiles + blockIdx.x];
+    }
+    __syncthreads();
+    const uint64_t* kw = kin + (size_t)(bit >> 6) * nops;
+    const unsigned shift = bit & 63;
+    const size_t run = (size_t)blockIdx.x * MT_TILE + (size_t)w * 64 * MT_ITEMS;
+    const uint64_t below = (1ull << lane) - 1;
+    uint32_t dig[MT_ITEMS], rank[MT_ITEMS];
+#pragma unroll
+    for (int it = 0; it < MT_ITEMS; it++) {
+        const size_t i = run + (size_t)it * 64 + lane;
+        const bool valid = i < nops;
+        const uint32_t d = valid ? (uint32_t)(kw[i] >> shift) & (MT_RADIX - 1) : 0;
+        uint64_t m = __ballot(valid);
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            const bool on = (d >> b) & 1;
+            const uint64_t bb = __ballot(on);
+            m &= on ? bb : ~bb;
+        }
+        const uint32_t pre = cnt[w][d];
+        __builtin_amdgcn_wave_barrier();
+        dig[it] = d;
+        rank[it] = pre + (uint32_t)__popcll(m & below);
+        if (valid && 63 - __clzll(m) == lane) cnt[w][d] = pre + (uint32_t)__popcll(m);   // the group's highest lane publishes
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    {
+        uint32_t off = dbase[threadIdx.x];
+#pragma unroll
+        for (int q = 0; q < MT_WAVES; q++) {
+            const uint32_t c = cnt[q][threadIdx.x];
+            cnt[q][threadIdx.x] = off;
+            off += c;
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < MT_ITEMS; it++) {
+        const size_t i = run + (size_t)it * 64 + lane;
+        if (i >= nops) continue;
+        const uint32_t dst = cnt[w][dig[it]] + rank[it];
+        iout[dst] = iin[i];
+        for (unsigned q = 0; q < nwords; q++) kout[(size_t)q * nops + dst] = kin[(size_t)q * nops + i];
+    }
+}
+
+// ---- (4) dummy rows after sorted op i (fill_gaps, memory_stark.rs:175-204; max_rc = M = next_pow2(nops) - 1):
+//   same context and segment, virt differs by d:  while d - 1 > M { virt += M + 1 }  ->  (d - 1) / (M + 1) dummies
+//   same address, timestamps differ by dt:         while dt > M { ts += M }          ->  dt > M ? (dt - 1) / M : 0
+__device__ __forceinline__ uint64_t gap_dummies(const mem_op& a, const mem_op& b, uint64_t M) {
+    if (a.ctx != b.ctx || a.seg != b.seg) return 0;
+    if (a.virt != b.virt) return (b.virt - a.virt - 1) / (M + 1);
+    const uint64_t dt = b.ts - a.ts;
+    return dt > M ? (dt - 1) / M : 0;
+}
+
+// cnt[i] = 1 + dummies after sorted op i (saturated); *last = 1 + the last sorted op with dummies (atomicMax; 0: none)
+__global__ __launch_bounds__(MT_THREADS) void k_mem_gaps(const uint64_t* __restrict__ ops, const uint32_t* __restrict__ idx, uint32_t nops,
+                                                          uint64_t M, uint64_t* __restrict__ cnt, unsigned* __restrict__ last) {
+    const size_t i = (size_t)blockIdx.x * MT_THREADS + threadIdx.x;
+    if (i >= nops) return;
+    uint64_t k = 0;
+    if (i + 1 < nops) k = gap_dummies(load_op(ops, idx[i]), load_op(ops, idx[i + 1]), M);
+    cnt[i] = k >= MT_SAT ? MT_SAT : k + 1;
+    if (k) atomicMax(last, (unsigned)(i + 1));
+}
+
+// ---- (5) exclusive saturating scan of v[0, len) in place: per-tile sums, a one-block scan of those, then the tiles
+__global__ __launch_bounds__(MT_THREADS) void k_scan_tiles(const uint64_t* __restrict__ v, size_t len, uint64_t* __restrict__ part) {
+    __shared__ uint64_t sh[MT_WAVES];
+    const size_t base = (size_t)blockIdx.x * MT_TILE + (size_t)threadIdx.x * MT_ITEMS;
+    uint64_t s = 0;
+#pragma unroll
+    for (int it = 0; it < MT_ITEMS; it++)
+        if (base + it < len) s = sat_add(s, v[base + it]);
+    uint64_t all;
+    block_incl_scan(s, sh, add_sat(), &all);
+    if (threadIdx.x == 0) part[blockIdx.x] = all;
+}
+__global__ __launch_bounds__(MT_THREADS) void k_scan_parts(uint64_t* __restrict__ part, size_t nparts) {
+    __shared__ uint64_t sh[MT_WAVES];
+    uint64_t carry = 0;
+    for (size_t c = 0; c < nparts; c += MT_THREADS) {
+        const size_t t = c + threadIdx.x;
+        const uint64_t x = t < nparts ? part[t] : 0;
+        uint64_t all;
+        const uint64_t incl = block_incl_scan(x, sh, add_sat(), &all);
+        if (t < nparts) part[t] = sat_add(carry, incl >= MT_SAT ? MT_SAT : incl - x);   // exact unless the table is rejected
+        carry = sat_add(carry, all);
+    }
+}
+__global__ __launch_bounds__(MT_THREADS) void k_scan_apply(uint64_t* __restrict__ v, size_t len, const uint64_t* __restrict__ part) {
+    __shared__ uint64_t sh[MT_WAVES];
+    const size_t base = (size_t)blockIdx.x * MT_TILE + (size_t)threadIdx.x * MT_ITEMS;
+    uint64_t x[MT_ITEMS], s = 0;
+#pragma unroll
+    for (int it = 0; it < MT_ITEMS; it++) {
+        x[it] = base + it < len ? v[base + it] : 0;
+        s = sat_add(s, x[it]);
+    }
+    uint64_t all;
+    const uint64_t incl = block_incl_scan(s, sh, add_sat(), &all);
+    // exclusive prefix of this thread: the block's inclusive scan minus its own sum (exact when nothing saturated; otherwise both are
+    // MT_SAT and the caller rejects the table anyway)
+    uint64_t run = sat_add(part[blockIdx.x], incl >= MT_SAT ? MT_SAT : incl - s);
+#pragma unroll
+    for (int it = 0; it < MT_ITEMS; it++) {
+        if (base + it < len) v[base + it] = run;
+        run = sat_add(run, x[it]);
+    }
+}
+
+// ---- (6) rows.  start[i] = first row of sorted op i (rows of the padding-free table), start[nops] = that table's height `count`.
+// The padding (n - count copies of the last op pushed) goes right behind that op's row q - 1, q = start[last] (or count).
+struct rows_args {
+    const uint64_t* ops;
+    const uint32_t* idx;
+    const uint64_t* start;
+    const unsigned* last;
+    uint32_t nops;
+    uint64_t M, pad;
+    size_t n;
+};
+__device__ __forceinline__ uint64_t pre_row(uint64_t r, uint64_t q, uint64_t pad) { return r < q ? r : r < q + pad ? q - 1 : r - pad; }
+// the last i in [lo, hi] with start[i] <= p (start is strictly increasing, start[lo] <= p)
+__device__ __forceinline__ uint32_t find_op(const uint64_t* __restrict__ start, uint64_t p, uint32_t lo, uint32_t hi) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (start[mid] <= p) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+__global__ __launch_bounds__(MT_THREADS) void k_mem_rows(rows_args A, gl_t* __restrict__ out) {
+    __shared__ uint32_t range[2];
+    const size_t n = A.n;
+    const unsigned lst = *A.last;
+    const uint64_t q = A.start[lst ? lst : A.nops];
+    const size_t r0 = (size_t)blockIdx.x * MT_THREADS, r = r0 + threadIdx.x;
+    const size_t rl = r0 + MT_THREADS - 1 < n ? r0 + MT_THREADS - 1 : n - 1;
+    if (threadIdx.x == 0) range[0] = find_op(A.start, pre_row(r0, q, A.pad), 0, A.nops - 1);
+    if (threadIdx.x == 1) range[1] = find_op(A.start, pre_row(rl, q, A.pad), 0, A.nops - 1);
+    __syncthreads();
+    if (r >= n) return;
+    const bool is_pad = r >= q && r < q + A.pad;
+    const uint64_t p = pre_row(r, q, A.pad);
+    const uint32_t i = find_op(A.start, p, range[0], range[1]);
+    const uint64_t j = p - A.start[i];
+    mem_op o = load_op(A.ops, A.idx[i]);
+    uint64_t filter = 1, is_read = o.is_read != 0;
+    if (j && i + 1 < A.nops) {
+        const mem_op b = load_op(A.ops, A.idx[i + 1]);
+        if (o.virt != b.virt) {   // (same context and segment: only such pairs have dummies)
+            o.virt += j * (A.M + 1);
+            o.ts = 0;
+            o.value = 0;
+        } else {
+            o.ts += j * A.M;
+        }
+        filter = 0;
+        is_read = 1;
+    }
+    uint64_t value = (uint32_t)o.value;
+    if (is_pad) {
+        filter = 0;
+        is_read = 1;
+    } else if (!is_read && o.ctx == 0 && o.seg == 4 && o.virt == 0) {
+        value = 0;   // into_row (:68-76): a write to register 0 is stored as 0
+    }
+    out[0 * n + r] = filter;
+    out[1 * n + r] = o.ts;
+    out[2 * n + r] = is_read;
+    out[3 * n + r] = o.ctx;
+    out[4 * n + r] = o.seg;
+    out[5 * n + r] = o.virt;
+    out[6 * n + r] = value;
+}
+
+// ---- (7) generate_first_change_flags_and_rc (:83-130), COUNTER and FREQUENCIES (:161-166); column 12 zeroed by the caller
+__global__ __launch_bounds__(MT_THREADS) void k_mem_neighbours(gl_t* __restrict__ out, size_t n, int* __restrict__ bad) {
+    __shared__ uint32_t h[MT_HIST_LDS];
+    for (int b = threadIdx.x; b < MT_HIST_LDS; b += MT_THREADS) h[b] = 0;
+    __syncthreads();
+    unsigned long long* freq = (unsigned long long*)(out + 12 * n);
+    for (size_t r = (size_t)blockIdx.x * MT_THREADS + threadIdx.x; r < n; r += (size_t)gridDim.x * MT_THREADS) {
+        uint64_t cfc = 0, sfc = 0, vfc = 0, rc = 0;
+        if (r + 1 < n) {
+            const uint64_t c0 = out[3 * n + r], c1 = out[3 * n + r + 1];
+            const uint64_t s0 = out[4 * n + r], s1 = out[4 * n + r + 1];
+            const uint64_t v0 = out[5 * n + r], v1 = out[5 * n + r + 1];
+            cfc = c0 != c1;
+            sfc = !cfc && s0 != s1;
+            vfc = !cfc && !sfc && v0 != v1;
+            // (rows are sorted and every key word is below p: the field differences are the integer ones)
+            rc = cfc ? c1 - c0 - 1 : sfc ? s1 - s0 - 1 : vfc ? v1 - v0 - 1 : out[1 * n + r + 1] - out[1 * n + r];
+        }
+        out[7 * n + r] = cfc;
+        out[8 * n + r] = sfc;
+        out[9 * n + r] = vfc;
+        out[10 * n + r] = rc;
+        out[11 * n + r] = r;
+        if (rc >= n) *bad = 1;
+        else if (rc < MT_HIST_LDS) atomicAdd(&h[rc], 1u);
+        else atomicAdd(&freq[rc], 1ull);
+    }
+    __syncthreads();
+    for (int b = threadIdx.x; b < MT_HIST_LDS && (size_t)b < n; b += MT_THREADS)
+        if (h[b]) atomicAdd(&freq[b], (unsigned long long)h[b]);
+}
+
+unsigned bit_width(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+size_t next_pow2(size_t v) {
+    size_t p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+size_t blocks_for(size_t items, size_t per) { return (items + per - 1) / per; }
+
+int fail(char** err, const std::string& msg) {
+    if (err) {
+        *err = (char*)malloc(msg.size() + 1);
+        if (*err) memcpy(*err, msg.c_str(), msg.size() + 1);
+    }
+    return 1;
+}
+
+}  // namespace
+
+extern "C" int zkm_memory_trace(zkm_ctx* c, const uint64_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, size_t* natural_rows_out,
+                                char** err) {
+    try {
+        ZKM_HIP_CHECK(hipSetDevice(c->device));
+        if (nops == 0) throw std::runtime_error("zkm_memory_trace: No memory ops?");
+        if (nops >= ((size_t)1 << 32)) throw std::runtime_error("zkm_memory_trace: 2^32 or more memory ops");
+        if (out_dev) {
+            if (log_n > MT_MAX_LOG_N)
+                throw std::runtime_error("zkm_memory_trace: log_n " + std::to_string(log_n) + " above the cap " + std::to_string(MT_MAX_LOG_N));
+            if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_memory_trace: out must be a device pointer");
+        }
+        const uint32_t m = (uint32_t)nops;
+        std::unique_ptr<zkm_scratch> host_copy;
+        const uint64_t* d_ops = ops;
+        if (!zkm_is_device_ptr(ops)) {
+            host_copy.reset(new zkm_scratch(c, nops * 48));
+            ZKM_HIP_CHECK(hipMemcpyAsync(host_copy->p, ops, nops * 48, hipMemcpyHostToDevice, c->stream));
+            d_ops = host_copy->as<uint64_t>();
+        }
+        // small: [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies, [6] range-check flag
+        zkm_scratch small(c, 64);
+        unsigned long long* d_acc = small.as<unsigned long long>();
+        unsigned* d_last = (unsigned*)(d_acc + 5);
+        int* d_bad = (int*)(d_acc + 6);
+        ZKM_HIP_CHECK(hipMemsetAsync(small.p, 0, 64, c->stream));
+        {
+            zkm_prof_scope ps(c, "memory_trace/widths");
+            hipLaunchKernelGGL(k_mem_widths, dim3(std::min<size_t>(blocks_for(nops, MT_THREADS), 1024)), dim3(MT_THREADS), 0, c->stream,
+                               d_ops, nops, d_acc);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        uint64_t acc[5];
+        c->download(acc, d_acc, sizeof(acc));
+        if (acc[4]) throw std::runtime_error("zkm_memory_trace: a context, segment, virt or timestamp word is not below p");
+        // key layout: timestamp lowest, then virt, segment, context
+        key_layout L{};
+        unsigned sh = 0;
+        for (int f = 3; f >= 0; f--) {
+            L.width[f] = bit_width(acc[f]);
+            L.shift[f] = sh;
+            sh += L.width[f];
+        }
+        L.bits = sh;
+        L.nwords = sh ? (sh + 63) / 64 : 1;
+        const size_t K = L.nwords, ntiles = blocks_for(nops, MT_TILE);
+        zkm_scratch keys_a(c, K * nops * 8), keys_b(c, K * nops * 8), idx_a(c, nops * 4), idx_b(c, nops * 4);
+        uint64_t *kin = keys_a.as<uint64_t>(), *kout = keys_b.as<uint64_t>();
+        uint32_t *iin = idx_a.as<uint32_t>(), *iout = idx_b.as<uint32_t>();
+        {
+            zkm_prof_scope ps(c, "memory_trace/pack");
+            hipLaunchKernelGGL(k_mem_pack, dim3(blocks_for(nops, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, d_ops, m, L, kin, iin);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        if (nops > 1 && L.bits) {
+            zkm_scratch hist(c, (size_t)MT_RADIX * ntiles * 4), tot(c, MT_RADIX * 4);
+            zkm_prof_scope ps(c, "memory_trace/sort");
+            for (unsigned bit = 0; bit < L.bits; bit += 8) {
+                hipLaunchKernelGGL(k_radix_upsweep, dim3(ntiles), dim3(MT_THREADS), 0, c->stream, kin, m, bit, hist.as<uint32_t>(), (uint32_t)ntiles);
+                hipLaunchKernelGGL(k_radix_scan, dim3(MT_RADIX), dim3(MT_THREADS), 0, c->stream, hist.as<uint32_t>(), (uint32_t)ntiles,
+                                   tot.as<uint32_t>());
+                hipLaunchKernelGGL(k_radix_downsweep, dim3(ntiles), dim3(MT_THREADS), 0, c->stream, kin, iin, kout, iout, m, L.nwords, bit,
+                                   hist.as<uint32_t>(), tot.as<uint32_t>(), (uint32_t)ntiles);
+                ZKM_HIP_CHECK(hipGetLastError());
+                std::swap(kin, kout);
+                std::swap(iin, iout);
+            }
+        }
+        // gaps and their scan: start[i] = first row of sorted op i, start[nops] = rows before padding
+        const uint64_t M = next_pow2(nops) - 1;
+        zkm_scratch start(c, (nops + 1) * 8);
+        uint64_t* d_start = start.as<uint64_t>();
+        const size_t len = nops + 1, nparts = blocks_for(len, MT_TILE);
+        zkm_scratch part(c, nparts * 8);
+        {
+            zkm_prof_scope ps(c, "memory_trace/gaps");
+            ZKM_HIP_CHECK(hipMemsetAsync(d_start + nops, 0, 8, c->stream));
+            hipLaunchKernelGGL(k_mem_gaps, dim3(blocks_for(nops, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, d_ops, iin, m, M, d_start, d_last);
+            hipLaunchKernelGGL(k_scan_tiles, dim3(nparts), dim3(MT_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
+            hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(MT_THREADS), 0, c->stream, part.as<uint64_t>(), nparts);
+            hipLaunchKernelGGL(k_scan_apply, dim3(nparts), dim3(MT_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        uint64_t count = 0;
+        c->download(&count, d_start + nops, 8);
+        if (count >= MT_SAT) {
+            if (natural_rows_out) *natural_rows_out = (size_t)MT_SAT;
+            throw std::runtime_error("zkm_memory_trace: the dummy rows of fill_gaps do not fit (2^62 rows or more)");
+        }
+        const size_t natural = next_pow2(count);
+        if (natural_rows_out) *natural_rows_out = natural;
+        if (!out_dev) return 0;
+        const size_t n = (size_t)1 << log_n;
+        if (natural > n)
+            throw std::runtime_error("zkm_memory_trace: the table needs " + std::to_string(natural) + " rows, more than 2^" + std::to_string(log_n));
+        {
+            zkm_prof_scope ps(c, "memory_trace/rows");
+            rows_args A{d_ops, iin, d_start, d_last, m, M, n - count, n};
+            hipLaunchKernelGGL(k_mem_rows, dim3(blocks_for(n, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, A, out_dev);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        {
+            zkm_prof_scope ps(c, "memory_trace/neighbours");
+            ZKM_HIP_CHECK(hipMemsetAsync(out_dev + 12 * n, 0, n * 8, c->stream));
+            hipLaunchKernelGGL(k_mem_neighbours, dim3(std::min<size_t>(blocks_for(n, MT_THREADS), 1024)), dim3(MT_THREADS), 0, c->stream,
+                               out_dev, n, d_bad);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        int bad = 0;
+        c->download(&bad, d_bad, sizeof(bad));
+        if (bad) throw std::runtime_error("zkm_memory_trace: a range check is 2^log_n or more (a context or segment gap)");
+    } catch (const std::exception& e) {
+        (void)hipStreamSynchronize(c->stream);
+        return fail(err, e.what());
+    }
+    return 0;
+}

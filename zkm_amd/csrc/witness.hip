@@ -2,7 +2,7 @@
 //
 // Every kernel writes the table column-major (the flattened Vec<PolynomialValues<F>> of util.rs:37-46) with consecutive
 // threads on consecutive rows, so each column store is a contiguous 512 B run per wavefront.  References are given at
-// each kernel.  The Memory table's rows come sorted from the CPU-side generator (as in the reference) and have no kernel.
+// each kernel.  The Memory table, whose rows need a sort, has its own file (memory_trace.hip).
 #include "poseidon_dev.h"
 #include "hash_constants_dev.h"
 #include "zkm_internal.h"
