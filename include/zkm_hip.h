@@ -6,6 +6,11 @@
  * `extern "C"` block a patched plonky2 / zkm-prover would bind.  Error convention follows the reference's
  * only existing FFI (recursion/src/snark/snarks.rs:7-20, 39-59): int status (0 = ok) + optional
  * malloc'd message in *err that the caller releases with free().
+ * What holds for every export: no C++ exception and no crash from a null handle crosses the boundary.  A
+ * null zkm_ctx / zkm_batch / zkm_staged / zkm_pool is status 1 (with "<function>: null argument" where
+ * there is an err), a no-op for destroy / free, 0 or NULL for size- and pointer-returning functions;
+ * zkm_staged_ready keeps 1 / 0 / -1 and zkm_pool_device -1.  A failed call releases what it allocated,
+ * and a failed prove call leaves the caller's challenger untouched.
  *
  * Data conventions
  *   - field element: canonical uint64_t (< p = 2^64 - 2^32 + 1); F2 = F[X]/(X^2-7) as [c0, c1].

@@ -35,6 +35,11 @@ def gpu_trace(ctx, oracle, ops, log_n=None, device=False):
     return got.reshape(13, -1), natural
 
 
+def _transient(ctx):
+    """Live bytes of the context that are not resident tables (twiddles and the like): a failed call must leave them as it found them."""
+    return ctx.memory()[0] - ctx.resident_bytes()
+
+
 def raw_call(ctx, ops, nops, log_n, out):
     """zkm_memory_trace through ctypes: (status, natural_rows_out, message)."""
     natural = C.c_size_t(12345)
@@ -195,8 +200,10 @@ def test_failures_leave_the_context_usable(ctx, zkm, oracle):
         # a context gap and a segment gap whose range check is >= 2^log_n (the oracle rejects them too)
         for gap in ([(0, 1, 0, 1, 0, 5), (100, 1, 0, 1, 0, 6)], [(2, 0, 0, 1, 0, 5), (2, 4, 0, 1, 0, 6)]):
             g = np.array(gap, dtype=np.uint64)
+            before = _transient(ctx)
             with pytest.raises(zkm.ZkmError, match="range check"):
                 ctx.memory_trace(g, 1)
+            assert _transient(ctx) == before   # (the check fails after the whole table is built: every block went back)
             with pytest.raises(RuntimeError):
                 oracle.memory_trace(g, 1)
             still_works()

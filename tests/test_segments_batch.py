@@ -27,6 +27,11 @@ def _segment(variant, heights=None):
     return traces, log_n
 
 
+def _transient(ctx):
+    """Live bytes of the context that are not resident tables (twiddles and the like): a failed call must leave them as it found them."""
+    return ctx.memory()[0] - ctx.resident_bytes()
+
+
 @pytest.mark.gpu
 def test_lockstep_segments_equal_single_segment_proofs_and_oracle(ctx, zkm, oracle):
     """Four segments of the base heights (one group of four per table): lock-step == one at a time == oracle."""
@@ -163,8 +168,10 @@ def test_a_bad_segment_of_a_group_is_named(ctx, zkm):
     bad_tr = [t.copy() for t in segs[1][0]]
     w = T.WIDTH[T.TABLE_ENUM_ORDER[10]]
     bad_tr[10].reshape(w, -1)[0][0] = 2
+    before = _transient(ctx)
     with pytest.raises(zkm.ZkmError, match=r"segment 1, table 10: Non-binary filter"):
         ctx.prove_segments([segs[0], (bad_tr, segs[1][1], segs[1][2]), segs[2]])
+    assert _transient(ctx) == before
     got = ctx.prove_segments(segs)
     for v in range(3):
         assert (got[v][0] == want[v][0]).all()

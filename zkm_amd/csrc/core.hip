@@ -8,25 +8,6 @@
 #include "poseidon_dev.h"
 #include "zkm_internal.h"
 
-// ------------------------------------------------------------------ error plumbing
-static int fail(char** err, const std::string& msg) {
-    if (err) {
-        *err = (char*)malloc(msg.size() + 1);
-        if (*err) memcpy(*err, msg.c_str(), msg.size() + 1);
-    }
-    return 1;
-}
-#define ZKM_API_BEGIN try {
-#define ZKM_API_END(err)                 \
-    }                                    \
-    catch (const std::exception& e) {    \
-        return fail(err, e.what());      \
-    }                                    \
-    catch (...) {                        \
-        return fail(err, "unknown error"); \
-    }                                    \
-    return 0;
-
 // ------------------------------------------------------------------ ctx
 // The allocator of a context is used by ONE thread at a time (its owner, or the lane thread of run_on_lanes) -- except for the
 // out-of-memory path, which reaches into the caches of the parent and sibling contexts: every allocator therefore has a mutex, held
@@ -489,24 +470,25 @@ extern "C" {
 const char* zkm_version(void) { return "zkm-hip 0.1 (gfx950)"; }
 
 int zkm_ctx_create(int device, zkm_ctx** out, char** err) {
-    ZKM_API_BEGIN
-    int n = 0;
-    ZKM_HIP_CHECK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) throw std::runtime_error("zkm_ctx_create: no such HIP device " + std::to_string(device));
-    ZKM_HIP_CHECK(hipSetDevice(device));
-    zkm_ctx* c = new zkm_ctx();
-    c->device = device;
-    hipDeviceProp_t prop;
-    ZKM_HIP_CHECK(hipGetDeviceProperties(&prop, device));
-    c->num_cus = prop.multiProcessorCount;
-    if (const char* part = getenv("ZKM_CU_MASK_PART")) {
-        int k = -1, n = 0;
-        if (sscanf(part, "%d/%d", &k, &n) == 2) { c->cu_part_k = k; c->cu_part_n = n; }
-    }
-    ZKM_HIP_CHECK(zkm_stream_create(&c->stream, c->num_cus, c->cu_part_k, c->cu_part_n));
-    g_live_contexts.fetch_add(1, std::memory_order_relaxed);
-    *out = c;
-    ZKM_API_END(err)
+    return zkm_api("zkm_ctx_create", err, [&] {
+        if (!out) throw std::runtime_error("zkm_ctx_create: null argument");
+        int n = 0;
+        ZKM_HIP_CHECK(hipGetDeviceCount(&n));
+        if (device < 0 || device >= n) throw std::runtime_error("zkm_ctx_create: no such HIP device " + std::to_string(device));
+        ZKM_HIP_CHECK(hipSetDevice(device));
+        std::unique_ptr<zkm_ctx> c(new zkm_ctx());
+        c->device = device;
+        hipDeviceProp_t prop;
+        ZKM_HIP_CHECK(hipGetDeviceProperties(&prop, device));
+        c->num_cus = prop.multiProcessorCount;
+        if (const char* part = getenv("ZKM_CU_MASK_PART")) {
+            int k = -1, n = 0;
+            if (sscanf(part, "%d/%d", &k, &n) == 2) { c->cu_part_k = k; c->cu_part_n = n; }
+        }
+        ZKM_HIP_CHECK(zkm_stream_create(&c->stream, c->num_cus, c->cu_part_k, c->cu_part_n));
+        g_live_contexts.fetch_add(1, std::memory_order_relaxed);
+        *out = c.release();
+    });
 }
 
 void zkm_ctx_destroy(zkm_ctx* c) {
@@ -531,127 +513,115 @@ void zkm_ctx_destroy(zkm_ctx* c) {
 }
 
 int zkm_ctx_set_tuning(zkm_ctx* c, const char* key, uint64_t value, char** err) {
-    ZKM_API_BEGIN
-    if (!c || !key) throw std::runtime_error("zkm_ctx_set_tuning: null argument");
-    const std::string k(key);
-    auto set = [&](zkm_ctx* x) {
-        if (k == "ingest_chunk_cols") x->ingest_chunk_cols = (size_t)value;
-        else if (k == "keccak_parts_max_points") x->keccak_parts_max_points = (size_t)value;
-        else if (k == "fri_fused_division_min") x->fri_fused_division_min = (size_t)value;
-        else if (k == "wide_max_hashes") x->wide_max_hashes = (size_t)value;
-        else if (k == "leaf_mfma") x->leaf_mfma = value ? 1 : 0;
-        else if (k == "quad_max_hashes") x->quad_max_hashes = (size_t)value;
-        else if (k == "block_after_us") x->block_after_us = value;
-        else if (k == "small_ntt") x->small_ntt = value ? 1 : 0;
-        else if (k == "tree_tail") x->tree_tail = value ? 1 : 0;
-        else if (k == "pow_round_log") x->pow_round_log = value < 8 ? 8 : (value > 22 ? 22 : (unsigned)value);
-        else if (k == "fri_scan_combine") x->fri_scan_combine = value ? 1 : 0;
-        else if (k == "aux_pipeline") x->aux_pipeline = value ? 1 : 0;
-        else if (k == "commit_lanes") x->commit_lanes = value < 1 ? 1 : (value > 8 ? 8 : (size_t)value);
-        else if (k == "segments_memory_budget") x->segments_memory_budget = (size_t)value;
-        else if (k == "max_stack") x->max_stack = value < 1 ? 1 : (value > ZKM_MAX_SEG ? ZKM_MAX_SEG : (size_t)value);
-        else if (k == "throughput_profile") {
-            // MANY contexts on one GPU proving small segments (profiles/r04_throughput_profile.txt): one stream per context -- the runtime
-            // has ~16 hardware queues, and streams that share one run behind each other's long kernels -- and the latency forms of the
-            // permutation only where a launch is tiny (with a dozen independent chains in flight the issue slots they cost are somebody
-            // else's work).  0 restores the defaults of a context that has the GPU (nearly) to itself.
-            x->commit_lanes = value ? 1 : ZKM_COMMIT_LANES;
-            x->wide_max_hashes = value ? 256 : 1024;
-            x->quad_max_hashes = value ? 4096 : 32768;
-            x->pow_round_log = value ? 16 : 17;                 // (half-filled SIMDs are somebody else's slots here: 76.3 vs 75.4 segments/s)
-        }
-        else if (k == "debug_fail_allocs") {
-            // test hook, not a tuning: only a process that asks for the hooks (ZKM_ENABLE_TEST_HOOKS=1 in its environment) may set it
-            const char* hooks = getenv("ZKM_ENABLE_TEST_HOOKS");
-            if (!hooks || strcmp(hooks, "1") != 0) throw std::runtime_error("zkm_ctx_set_tuning: unknown key '" + k + "'");
-            if (x == c) x->debug_fail_allocs.store((int)value);
-        }
-        else throw std::runtime_error("zkm_ctx_set_tuning: unknown key '" + k + "'");
-    };
-    set(c);
-    for (zkm_ctx* l : c->lanes) set(l);
-    ZKM_API_END(err)
+    return zkm_api("zkm_ctx_set_tuning", err, [&] {
+        if (!c || !key) throw std::runtime_error("zkm_ctx_set_tuning: null argument");
+        const std::string k(key);
+        auto set = [&](zkm_ctx* x) {
+            if (k == "ingest_chunk_cols") x->ingest_chunk_cols = (size_t)value;
+            else if (k == "keccak_parts_max_points") x->keccak_parts_max_points = (size_t)value;
+            else if (k == "fri_fused_division_min") x->fri_fused_division_min = (size_t)value;
+            else if (k == "wide_max_hashes") x->wide_max_hashes = (size_t)value;
+            else if (k == "leaf_mfma") x->leaf_mfma = value ? 1 : 0;
+            else if (k == "quad_max_hashes") x->quad_max_hashes = (size_t)value;
+            else if (k == "block_after_us") x->block_after_us = value;
+            else if (k == "small_ntt") x->small_ntt = value ? 1 : 0;
+            else if (k == "tree_tail") x->tree_tail = value ? 1 : 0;
+            else if (k == "pow_round_log") x->pow_round_log = value < 8 ? 8 : (value > 22 ? 22 : (unsigned)value);
+            else if (k == "fri_scan_combine") x->fri_scan_combine = value ? 1 : 0;
+            else if (k == "aux_pipeline") x->aux_pipeline = value ? 1 : 0;
+            else if (k == "commit_lanes") x->commit_lanes = value < 1 ? 1 : (value > 8 ? 8 : (size_t)value);
+            else if (k == "segments_memory_budget") x->segments_memory_budget = (size_t)value;
+            else if (k == "max_stack") x->max_stack = value < 1 ? 1 : (value > ZKM_MAX_SEG ? ZKM_MAX_SEG : (size_t)value);
+            else if (k == "throughput_profile") {
+                // MANY contexts on one GPU proving small segments (profiles/r04_throughput_profile.txt): one stream per context -- the runtime
+                // has ~16 hardware queues, and streams that share one run behind each other's long kernels -- and the latency forms of the
+                // permutation only where a launch is tiny (with a dozen independent chains in flight the issue slots they cost are somebody
+                // else's work).  0 restores the defaults of a context that has the GPU (nearly) to itself.
+                x->commit_lanes = value ? 1 : ZKM_COMMIT_LANES;
+                x->wide_max_hashes = value ? 256 : 1024;
+                x->quad_max_hashes = value ? 4096 : 32768;
+                x->pow_round_log = value ? 16 : 17;                 // (half-filled SIMDs are somebody else's slots here: 76.3 vs 75.4 segments/s)
+            }
+            else if (k == "debug_fail_allocs") {
+                // test hook, not a tuning: only a process that asks for the hooks (ZKM_ENABLE_TEST_HOOKS=1 in its environment) may set it
+                const char* hooks = getenv("ZKM_ENABLE_TEST_HOOKS");
+                if (!hooks || strcmp(hooks, "1") != 0) throw std::runtime_error("zkm_ctx_set_tuning: unknown key '" + k + "'");
+                if (x == c) x->debug_fail_allocs.store((int)value);
+            }
+            else throw std::runtime_error("zkm_ctx_set_tuning: unknown key '" + k + "'");
+        };
+        set(c);
+        for (zkm_ctx* l : c->lanes) set(l);
+    });
 }
 
 int zkm_ctx_synchronize(zkm_ctx* c, char** err) {
-    ZKM_API_BEGIN
-    c->sync();
-    ZKM_API_END(err)
+    return zkm_api("zkm_ctx_synchronize", c, err, [&] { c->sync(); });
 }
-void* zkm_ctx_stream(zkm_ctx* c) { return (void*)c->stream; }
+void* zkm_ctx_stream(zkm_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 void zkm_ctx_memory(const zkm_ctx* c, size_t* live_bytes, size_t* cached_bytes) {
     size_t live = 0, cached = 0;
-    for (auto& kv : c->live_blocks) live += kv.second;
-    for (auto& kv : c->free_blocks) cached += kv.first;
-    for (const zkm_ctx* l : c->lanes) {
-        size_t a = 0, b = 0;
-        zkm_ctx_memory(l, &a, &b);
-        live += a;
-        cached += b;
+    if (c) {
+        for (auto& kv : c->live_blocks) live += kv.second;
+        for (auto& kv : c->free_blocks) cached += kv.first;
+        for (const zkm_ctx* l : c->lanes) {
+            size_t a = 0, b = 0;
+            zkm_ctx_memory(l, &a, &b);
+            live += a;
+            cached += b;
+        }
     }
     if (live_bytes) *live_bytes = live;
     if (cached_bytes) *cached_bytes = cached;
 }
 
 size_t zkm_ctx_resident_bytes(const zkm_ctx* c) {
+    if (!c) return 0;
     size_t r = c->resident_bytes;
     for (const zkm_ctx* l : c->lanes) r += zkm_ctx_resident_bytes(l);
     return r;
 }
 
 void zkm_ctx_trim(zkm_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    c->trim();
+    (void)zkm_api("zkm_ctx_trim", c, nullptr, [&] { c->trim(); });
 }
 
 // Pinned host memory for the witness generator's buffers: hipMemcpyAsync from pageable memory is staged by the runtime and
 // blocks the host; from pinned memory the chunked upload of zkm_batch_build overlaps with compute.
 int zkm_host_alloc(zkm_ctx* c, size_t bytes, void** out, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));
-    ZKM_HIP_CHECK(hipHostMalloc(out, bytes ? bytes : 8, hipHostMallocDefault));
-    ZKM_API_END(err)
+    return zkm_api("zkm_host_alloc", c, err, [&] { ZKM_HIP_CHECK(hipHostMalloc(out, bytes ? bytes : 8, hipHostMallocDefault)); });
 }
 int zkm_host_free(zkm_ctx* c, void* p) {
-    (void)hipSetDevice(c->device);
-    return hipHostFree(p) == hipSuccess ? 0 : 1;
+    return zkm_api("zkm_host_free", c, nullptr, [&] { ZKM_HIP_CHECK(hipHostFree(p)); });
 }
 int zkm_host_register(zkm_ctx* c, void* p, size_t bytes, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));
-    ZKM_HIP_CHECK(hipHostRegister(p, bytes, hipHostRegisterDefault));
-    ZKM_API_END(err)
+    return zkm_api("zkm_host_register", c, err, [&] { ZKM_HIP_CHECK(hipHostRegister(p, bytes, hipHostRegisterDefault)); });
 }
 int zkm_host_unregister(zkm_ctx* c, void* p) {
-    (void)hipSetDevice(c->device);
-    return hipHostUnregister(p) == hipSuccess ? 0 : 1;
+    return zkm_api("zkm_host_unregister", c, nullptr, [&] { ZKM_HIP_CHECK(hipHostUnregister(p)); });
 }
 
+// (the current device is per host thread; contexts are driven from worker threads: every entry point selects its context's device)
 int zkm_dev_alloc(zkm_ctx* c, size_t bytes, void** out, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));
-    *out = c->alloc(bytes);
-    ZKM_API_END(err)
+    return zkm_api("zkm_dev_alloc", c, err, [&] { *out = c->alloc(bytes); });
 }
 int zkm_dev_free(zkm_ctx* c, void* p) {
+    if (!c) return 1;
     c->release(p);
     return 0;
 }
 int zkm_dev_upload(zkm_ctx* c, void* dst, const void* src, size_t bytes, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));   // (the current device is per host thread; contexts are driven from worker threads)
-    ZKM_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    c->sync();
-    ZKM_API_END(err)
+    return zkm_api("zkm_dev_upload", c, err, [&] {
+        ZKM_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+        c->sync();
+    });
 }
 int zkm_dev_download(zkm_ctx* c, void* dst, const void* src, size_t bytes, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));
-    ZKM_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    c->sync();
-    ZKM_API_END(err)
+    return zkm_api("zkm_dev_download", c, err, [&] {
+        ZKM_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+    });
 }
 
 // ------------------------------------------------------------------ staged traces: the upload of the NEXT proof behind the CURRENT one
@@ -718,12 +688,14 @@ static void stage_abort(zkm_staged* s) {
     delete s;
 }
 
+// a staged upload under way: stage_abort releases it if the call fails before the handle is handed out
+using staged_owner = std::unique_ptr<zkm_staged, void (*)(zkm_staged*)>;
+
 int zkm_trace_stage(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, int canonical, zkm_staged** out, char** err) {
-    ZKM_API_BEGIN
-    if (!c || !values || !out || !ncols || log_n > 30) throw std::runtime_error("zkm_trace_stage: bad argument");
-    const size_t n = (size_t)1 << log_n;
-    zkm_staged* s = stage_begin(c, ncols * n, canonical);
-    try {
+    return zkm_api("zkm_trace_stage", c, err, [&] {
+        if (!values || !out || !ncols || log_n > 30) throw std::runtime_error("zkm_trace_stage: bad argument");
+        const size_t n = (size_t)1 << log_n;
+        staged_owner s(stage_begin(c, ncols * n, canonical), stage_abort);
         // pieces of >= 64 MB (8 columns at 2^20 rows; a short table is ONE copy): the two streams take alternate pieces; small pieces let
         // the other contexts' copies interleave (4 contexts at 2^20 rows: 16.3 proofs/s against 15.6 with 268 MB pieces), tiny ones are
         // all call overhead (a 2431-column table of 2^10 rows in 8-column pieces was 304 copies of 64 KB)
@@ -733,51 +705,41 @@ int zkm_trace_stage(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned l
             const size_t nc = std::min(piece, ncols - c0);
             ZKM_HIP_CHECK(hipMemcpyAsync(s->dev + c0 * n, values + c0 * n, nc * n * sizeof(gl_t), hipMemcpyHostToDevice, (k & 1) ? c->copy_stream2 : c->copy_stream));
         }
-        stage_end(s);
-    } catch (...) {
-        stage_abort(s);
-        throw;
-    }
-    *out = s;
-    ZKM_API_END(err)
+        stage_end(s.get());
+        *out = s.release();
+    });
 }
 int zkm_trace_stage_columns(zkm_ctx* c, const uint64_t* const* columns, size_t ncols, unsigned log_n, int canonical, zkm_staged** out, char** err) {
-    ZKM_API_BEGIN
-    if (!c || !columns || !out || !ncols || log_n > 30) throw std::runtime_error("zkm_trace_stage_columns: bad argument");
-    for (size_t i = 0; i < ncols; i++)
-        if (!columns[i]) throw std::runtime_error("zkm_trace_stage_columns: null column pointer");
-    const size_t n = (size_t)1 << log_n;
-    zkm_staged* s = stage_begin(c, ncols * n, canonical);
-    try {
+    return zkm_api("zkm_trace_stage_columns", c, err, [&] {
+        if (!columns || !out || !ncols || log_n > 30) throw std::runtime_error("zkm_trace_stage_columns: bad argument");
+        for (size_t i = 0; i < ncols; i++)
+            if (!columns[i]) throw std::runtime_error("zkm_trace_stage_columns: null column pointer");
+        const size_t n = (size_t)1 << log_n;
+        staged_owner s(stage_begin(c, ncols * n, canonical), stage_abort);
         for (size_t i = 0; i < ncols; i++)
             ZKM_HIP_CHECK(hipMemcpyAsync(s->dev + i * n, columns[i], n * sizeof(gl_t), hipMemcpyHostToDevice, ((i / 8) & 1) ? c->copy_stream2 : c->copy_stream));
-        stage_end(s);
-    } catch (...) {
-        stage_abort(s);
-        throw;
-    }
-    *out = s;
-    ZKM_API_END(err)
+        stage_end(s.get());
+        *out = s.release();
+    });
 }
 // All twelve tables of ONE segment in one call (Table::all() order, zkm_table_width columns x 2^log_n[t] words each): one block, one pair
 // of events -- a lock-step call of K segments is K stage calls instead of 12 K (96 calls per 8-segment call cost its host thread 9 ms of
 // the 600 the call takes).  Exactly one of traces / columns is non-null.
 static int stage_segment(const char* what, zkm_ctx* c, const uint64_t* const* traces, const uint64_t* const* const* columns, const unsigned* log_n,
                          int canonical, zkm_staged** out, char** err) {
-    ZKM_API_BEGIN
-    if (!c || (!traces && !columns) || !log_n || !out) throw std::runtime_error(std::string(what) + ": null argument");
-    static const int order[12] = {ZKM_TABLE_ARITHMETIC, ZKM_TABLE_CPU, ZKM_TABLE_POSEIDON, ZKM_TABLE_POSEIDON_SPONGE, ZKM_TABLE_KECCAK,
-                                  ZKM_TABLE_KECCAK_SPONGE, ZKM_TABLE_SHA_EXTEND, ZKM_TABLE_SHA_EXTEND_SPONGE, ZKM_TABLE_SHA_COMPRESS,
-                                  ZKM_TABLE_SHA_COMPRESS_SPONGE, ZKM_TABLE_LOGIC, ZKM_TABLE_MEMORY};   // Table::all(), all_stark.rs:117-134
-    size_t off[13], W[12];
-    off[0] = 0;
-    for (int t = 0; t < 12; t++) {
-        if (log_n[t] > 30 || (traces && !traces[t]) || (columns && !columns[t])) throw std::runtime_error(std::string(what) + ": bad table");
-        W[t] = zkm_table_width(order[t]);
-        off[t + 1] = off[t] + (W[t] << log_n[t]);
-    }
-    zkm_staged* s = stage_begin(c, off[12], canonical);
-    try {
+    return zkm_api(what, c, err, [&] {
+        if ((!traces && !columns) || !log_n || !out) throw std::runtime_error(std::string(what) + ": null argument");
+        static const int order[12] = {ZKM_TABLE_ARITHMETIC, ZKM_TABLE_CPU, ZKM_TABLE_POSEIDON, ZKM_TABLE_POSEIDON_SPONGE, ZKM_TABLE_KECCAK,
+                                      ZKM_TABLE_KECCAK_SPONGE, ZKM_TABLE_SHA_EXTEND, ZKM_TABLE_SHA_EXTEND_SPONGE, ZKM_TABLE_SHA_COMPRESS,
+                                      ZKM_TABLE_SHA_COMPRESS_SPONGE, ZKM_TABLE_LOGIC, ZKM_TABLE_MEMORY};   // Table::all(), all_stark.rs:117-134
+        size_t off[13], W[12];
+        off[0] = 0;
+        for (int t = 0; t < 12; t++) {
+            if (log_n[t] > 30 || (traces && !traces[t]) || (columns && !columns[t])) throw std::runtime_error(std::string(what) + ": bad table");
+            W[t] = zkm_table_width(order[t]);
+            off[t + 1] = off[t] + (W[t] << log_n[t]);
+        }
+        staged_owner s(stage_begin(c, off[12], canonical), stage_abort);
         s->segment = true;
         for (int t = 0; t <= 12; t++) s->off[t] = off[t];
         size_t k = 0, bytes_on[2] = {0, 0};
@@ -793,13 +755,9 @@ static int stage_segment(const char* what, zkm_ctx* c, const uint64_t* const* tr
                 bytes_on[k] += nc * n * sizeof(gl_t);
             }
         }
-        stage_end(s);
-    } catch (...) {
-        stage_abort(s);
-        throw;
-    }
-    *out = s;
-    ZKM_API_END(err)
+        stage_end(s.get());
+        *out = s.release();
+    });
 }
 int zkm_segment_stage(zkm_ctx* c, const uint64_t* const* traces, const unsigned* log_n, int canonical, zkm_staged** out, char** err) {
     return stage_segment("zkm_segment_stage", c, traces, nullptr, log_n, canonical, out, err);
@@ -821,16 +779,13 @@ int zkm_staged_segment_ptrs(zkm_staged* s, const uint64_t** ptrs_out) {
 const uint64_t* zkm_staged_ptr(zkm_staged* s) {
     if (!s) return nullptr;
     zkm_ctx* c = s->ctx;
-    if (!s->joined) {
-        (void)hipSetDevice(c->device);
-        if (hipStreamWaitEvent(c->stream, s->done[0], 0) != hipSuccess || hipStreamWaitEvent(c->stream, s->done[1], 0) != hipSuccess) return nullptr;
-        try {
+    if (!s->joined && zkm_api("zkm_staged_ptr", c, nullptr, [&] {
+            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, s->done[0], 0));
+            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, s->done[1], 0));
             if (!s->canonical) zkm_launch_canon(c, s->dev, s->words);
-        } catch (...) {
-            return nullptr;
-        }
-        s->joined = true;
-    }
+            s->joined = true;
+        }))
+        return nullptr;
     return s->dev;
 }
 // host-side: has the upload finished (1), is it still in flight (0)?  `wait` != 0 blocks until it has.
@@ -857,24 +812,27 @@ void zkm_staged_free(zkm_staged* s) {
     (void)hipEventSynchronize(s->done[0]);
     (void)hipEventSynchronize(s->done[1]);
     c->release(s->dev);
-    c->event_pool.push_back(s->done[0]);
-    c->event_pool.push_back(s->done[1]);
+    (void)zkm_api("zkm_staged_free", nullptr, [&] { c->event_pool.insert(c->event_pool.end(), s->done, s->done + 2); });
     delete s;
     g_staged_live.fetch_sub(1, std::memory_order_relaxed);
 }
 
 // ------------------------------------------------------------------ profiling
 void zkm_profile_enable(zkm_ctx* c, int on) {
+    if (!c) return;
     c->profiling = on != 0;
     for (zkm_ctx* l : c->lanes) l->profiling = c->profiling;
 }
-void zkm_profile_reset(zkm_ctx* c) {
+static void profile_reset(zkm_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     for (auto& r : c->prof) { c->event_pool.push_back(r.start); c->event_pool.push_back(r.stop); }
     c->prof.clear();
     c->prof_agg.clear();
     c->prof_agg_valid = false;
-    for (zkm_ctx* l : c->lanes) zkm_profile_reset(l);
+    for (zkm_ctx* l : c->lanes) profile_reset(l);
+}
+void zkm_profile_reset(zkm_ctx* c) {
+    (void)zkm_api("zkm_profile_reset", c, nullptr, [&] { profile_reset(c); });
 }
 // (records of the commit lanes are reported with the context's: launches that ran side by side on different lanes each count
 // their own duration, so a sum over kernels can exceed the wall time of a segment)
@@ -899,16 +857,17 @@ static void prof_aggregate(zkm_ctx* c) {
     c->prof_agg_valid = !lane_records;   // (lane records may still grow without invalidating this context's flag)
 }
 size_t zkm_profile_count(zkm_ctx* c) {
-    prof_aggregate(c);
-    return c->prof_agg.size();
+    return zkm_api("zkm_profile_count", c, nullptr, [&] { prof_aggregate(c); }) ? 0 : c->prof_agg.size();
 }
 int zkm_profile_get(zkm_ctx* c, size_t i, const char** name, uint64_t* launches, double* total_ms) {
-    prof_aggregate(c);
-    if (i >= c->prof_agg.size()) return 1;
-    *name = c->prof_agg[i].name;
-    *launches = c->prof_agg[i].launches;
-    *total_ms = c->prof_agg[i].ms;
-    return 0;
+    return zkm_api("zkm_profile_get", c, nullptr, [&] {
+        prof_aggregate(c);
+        if (i >= c->prof_agg.size()) return 1;
+        *name = c->prof_agg[i].name;
+        *launches = c->prof_agg[i].launches;
+        *total_ms = c->prof_agg[i].ms;
+        return 0;
+    });
 }
 
 // ------------------------------------------------------------------ Fiat-Shamir (host)
@@ -1132,10 +1091,10 @@ __global__ __launch_bounds__(256) void k_gather_lde_rows(const gl_t* __restrict_
     out[idx] = lde[col * N + row];
 }
 
-static zkm_batch* batch_new(zkm_ctx* c, size_t ncols, unsigned log_n, unsigned rate_bits, unsigned cap_height) {
+static zkm_batch_ptr batch_new(zkm_ctx* c, size_t ncols, unsigned log_n, unsigned rate_bits, unsigned cap_height) {
     if (ncols == 0) throw std::runtime_error("empty polynomial batch");
     if (cap_height > log_n + rate_bits) throw std::runtime_error("cap_height exceeds LDE size");
-    zkm_batch* b = new zkm_batch();
+    zkm_batch_ptr b(new zkm_batch());
     b->ctx = c; b->ncols = ncols; b->log_n = log_n; b->rate_bits = rate_bits; b->cap_height = cap_height;
     return b;
 }
@@ -1143,63 +1102,37 @@ static zkm_batch* batch_new(zkm_ctx* c, size_t ncols, unsigned log_n, unsigned r
 // from_values keeping the uploaded values in dev_values (see zkm_batch_build); throws
 zkm_batch* zkm_batch_commit_values_keep(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, unsigned rate_bits,
                                         unsigned cap_height, gl_t* dev_values, const uint64_t* const* columns) {
-    zkm_batch* b = batch_new(c, ncols, log_n, rate_bits, cap_height);
-    try {
-        zkm_batch_build(b, values, true, dev_values, columns);
-    } catch (...) {
-        zkm_batch_free(b);
-        throw;
-    }
-    return b;
+    zkm_batch_ptr b = batch_new(c, ncols, log_n, rate_bits, cap_height);
+    zkm_batch_build(b.get(), values, true, dev_values, columns);
+    return b.release();
 }
 
 extern "C" {
 
 int zkm_batch_commit_values(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, unsigned rate_bits,
                             unsigned cap_height, zkm_batch** out, char** err) {
-    zkm_batch* b = nullptr;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
-        b = batch_new(c, ncols, log_n, rate_bits, cap_height);
-        zkm_batch_build(b, values, true);
-        *out = b;
-    } catch (const std::exception& e) {
-        zkm_batch_free(b);
-        return fail(err, e.what());
-    }
-    return 0;
+    return zkm_api("zkm_batch_commit_values", c, err, [&] {
+        zkm_batch_ptr b = batch_new(c, ncols, log_n, rate_bits, cap_height);
+        zkm_batch_build(b.get(), values, true);
+        *out = b.release();
+    });
 }
 int zkm_batch_commit_columns(zkm_ctx* c, const uint64_t* const* columns, size_t ncols, unsigned log_n, int columns_are_values,
                              unsigned rate_bits, unsigned cap_height, zkm_batch** out, char** err) {
-    zkm_batch* b = nullptr;
-    try {
-        if (!c || !columns || !out) throw std::runtime_error("zkm_batch_commit_columns: null argument");
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
-        b = batch_new(c, ncols, log_n, rate_bits, cap_height);
-        zkm_batch_build(b, nullptr, columns_are_values != 0, nullptr, columns);
-        *out = b;
-    } catch (const std::exception& e) {
-        zkm_batch_free(b);
-        return fail(err, e.what());
-    } catch (...) {
-        zkm_batch_free(b);
-        return fail(err, "zkm_batch_commit_columns: unknown error");
-    }
-    return 0;
+    return zkm_api("zkm_batch_commit_columns", c, err, [&] {
+        if (!columns || !out) throw std::runtime_error("zkm_batch_commit_columns: null argument");
+        zkm_batch_ptr b = batch_new(c, ncols, log_n, rate_bits, cap_height);
+        zkm_batch_build(b.get(), nullptr, columns_are_values != 0, nullptr, columns);
+        *out = b.release();
+    });
 }
 int zkm_batch_commit_coeffs(zkm_ctx* c, const uint64_t* coeffs, size_t ncols, unsigned log_n, unsigned rate_bits,
                             unsigned cap_height, zkm_batch** out, char** err) {
-    zkm_batch* b = nullptr;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
-        b = batch_new(c, ncols, log_n, rate_bits, cap_height);
-        zkm_batch_build(b, coeffs, false);
-        *out = b;
-    } catch (const std::exception& e) {
-        zkm_batch_free(b);
-        return fail(err, e.what());
-    }
-    return 0;
+    return zkm_api("zkm_batch_commit_coeffs", c, err, [&] {
+        zkm_batch_ptr b = batch_new(c, ncols, log_n, rate_bits, cap_height);
+        zkm_batch_build(b.get(), coeffs, false);
+        *out = b.release();
+    });
 }
 void zkm_batch_free(zkm_batch* b) {
     if (!b) return;
@@ -1210,17 +1143,18 @@ void zkm_batch_free(zkm_batch* b) {
     b->ctx->release(b->digests);
     delete b;
 }
+// (the accessors have no message: a null batch, an index out of range or a failed copy is status 1)
 int zkm_batch_cap(const zkm_batch* b, uint64_t* out) {
+    if (!b) return 1;
     memcpy(out, b->cap.data(), b->cap.size() * sizeof(uint64_t));
     return 0;
 }
 int zkm_batch_coeffs(const zkm_batch* b, uint64_t* out) {
     // .polynomials in NATURAL order, whatever layout the batch keeps them in
-    zkm_ctx* c = b->ctx;
-    const size_t bytes = b->ncols * b->n() * sizeof(gl_t);
-    const bool dev = zkm_is_device_ptr(out);
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    zkm_ctx* c = b ? b->ctx : nullptr;
+    return zkm_api("zkm_batch_coeffs", c, nullptr, [&] {
+        const size_t bytes = b->ncols * b->n() * sizeof(gl_t);
+        const bool dev = zkm_is_device_ptr(out);
         if (!b->coeff_s1) {
             ZKM_HIP_CHECK(hipMemcpyAsync(out, b->coeffs, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
         } else {
@@ -1231,13 +1165,10 @@ int zkm_batch_coeffs(const zkm_batch* b, uint64_t* out) {
             c->sync();   // (the scratch goes back to the allocator on return)
         }
         c->sync();
-    } catch (...) {
-        return 1;
-    }
-    return 0;
+    });
 }
 int zkm_batch_leaf(const zkm_batch* b, size_t leaf, uint64_t* out) {
-    if (leaf >= b->N()) return 1;
+    if (!b || leaf >= b->N()) return 1;
     // one strided gather: ncols words at stride N
     if (hipMemcpy2DAsync(out, sizeof(gl_t), b->lde + leaf, b->N() * sizeof(gl_t), sizeof(gl_t), b->ncols, hipMemcpyDeviceToHost,
                          b->ctx->stream) != hipSuccess)
@@ -1245,19 +1176,19 @@ int zkm_batch_leaf(const zkm_batch* b, size_t leaf, uint64_t* out) {
     return hipStreamSynchronize(b->ctx->stream) == hipSuccess ? 0 : 1;
 }
 int zkm_batch_lde_row(const zkm_batch* b, size_t natural_index, uint64_t* out) {
-    if (natural_index >= b->N()) return 1;
+    if (!b || natural_index >= b->N()) return 1;
     return zkm_batch_leaf(b, bitrev32((uint32_t)natural_index, b->lde_bits()), out);
 }
 int zkm_batch_lde_rows(const zkm_batch* b, size_t index_start, size_t step, size_t count, uint64_t* out) {
     // get_lde_values_packed(index_start, step) for `count` consecutive indices (prover.rs:687, 723-748): row i of the output is
     // get_lde_values(index_start + i, step) = leaves[reverse_bits((index_start + i) * step)], ncols words; out host or device
+    if (!b) return 1;
     if (!count) return 0;
     if (step == 0) return 1;
     const size_t last_ok = (b->N() - 1) / step;                     // largest index whose (index * step) is a row of the LDE
     if (index_start > last_ok || count - 1 > last_ok - index_start) return 1;   // (no wrap-around for hostile arguments)
     zkm_ctx* c = b->ctx;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_batch_lde_rows", c, nullptr, [&] {
         bool dev = zkm_is_device_ptr(out);
         zkm_scratch tmp(c, dev ? 8 : count * b->ncols * sizeof(gl_t));
         gl_t* d = dev ? out : tmp.as<gl_t>();
@@ -1267,13 +1198,10 @@ int zkm_batch_lde_rows(const zkm_batch* b, size_t index_start, size_t step, size
         ZKM_HIP_CHECK(hipGetLastError());
         if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(out, d, total * sizeof(gl_t), hipMemcpyDeviceToHost, c->stream));
         c->sync();
-    } catch (...) {
-        return 1;
-    }
-    return 0;
+    });
 }
 int zkm_batch_merkle_path(const zkm_batch* b, size_t leaf, uint64_t* sib) {
-    if (leaf >= b->N()) return 1;
+    if (!b || leaf >= b->N()) return 1;
     for (unsigned l = 0; l < b->top(); l++)
         if (hipMemcpyAsync(sib + 4 * l, b->digests + b->level_off[l] + 4 * ((leaf >> l) ^ 1), 32, hipMemcpyDeviceToHost,
                            b->ctx->stream) != hipSuccess)
@@ -1281,7 +1209,7 @@ int zkm_batch_merkle_path(const zkm_batch* b, size_t leaf, uint64_t* sib) {
     return hipStreamSynchronize(b->ctx->stream) == hipSuccess ? 0 : 1;
 }
 int zkm_batch_digest_layer(const zkm_batch* b, unsigned level, uint64_t* out) {
-    if (level > b->top()) return 1;
+    if (!b || level > b->top()) return 1;
     size_t words = (size_t)4 << (b->lde_bits() - level);
     if (hipMemcpyAsync(out, b->digests + b->level_off[level], words * sizeof(gl_t), hipMemcpyDeviceToHost, b->ctx->stream) != hipSuccess)
         return 1;
@@ -1290,70 +1218,65 @@ int zkm_batch_digest_layer(const zkm_batch* b, unsigned level, uint64_t* out) {
 
 // ------------------------------------------------------------------ NTT / hashes / trace
 int zkm_ntt(zkm_ctx* c, uint64_t* cols, size_t ncols, unsigned log_n, int inverse, uint64_t coset_shift, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));
-    if (log_n > 30) throw std::runtime_error("zkm_ntt: log_n too large");
-    if (coset_shift >= GL_P) throw std::runtime_error("zkm_ntt: coset_shift not canonical");
-    size_t n = (size_t)1 << log_n, bytes = ncols * n * sizeof(gl_t);
-    if (bytes == 0) return 0;
-    bool dev = zkm_is_device_ptr(cols);
-    gl_t* scratch = (gl_t*)c->alloc(bytes);
-    gl_t* work = dev ? cols : (gl_t*)c->alloc(bytes);
-    // transform from scratch (copy of the input) into `work`
-    ZKM_HIP_CHECK(hipMemcpyAsync(scratch, cols, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    zkm_ntt_natural(c, scratch, work, ncols, n, n, log_n, inverse != 0, coset_shift);
-    if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(cols, work, bytes, hipMemcpyDeviceToHost, c->stream));
-    c->sync();
-    c->release(scratch);
-    if (!dev) c->release(work);
-    ZKM_API_END(err)
+    return zkm_api("zkm_ntt", c, err, [&] {
+        if (log_n > 30) throw std::runtime_error("zkm_ntt: log_n too large");
+        if (coset_shift >= GL_P) throw std::runtime_error("zkm_ntt: coset_shift not canonical");
+        size_t n = (size_t)1 << log_n, bytes = ncols * n * sizeof(gl_t);
+        if (bytes == 0) return;
+        bool dev = zkm_is_device_ptr(cols);
+        zkm_scratch_list tmp(c);
+        gl_t* scratch = tmp.alloc<gl_t>(bytes);
+        gl_t* work = dev ? (gl_t*)cols : tmp.alloc<gl_t>(bytes);
+        // transform from scratch (copy of the input) into `work`
+        ZKM_HIP_CHECK(hipMemcpyAsync(scratch, cols, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+        zkm_ntt_natural(c, scratch, work, ncols, n, n, log_n, inverse != 0, coset_shift);
+        if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(cols, work, bytes, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+    });
 }
 
+// k permutations of `width`-word states in place (host or device)
+static int permute_batch(const char* what, zkm_ctx* c, uint64_t* states, size_t k, size_t width, char** err,
+                         void (*launch)(zkm_ctx*, uint64_t*, size_t)) {
+    return zkm_api(what, c, err, [&] {
+        size_t bytes = k * width * sizeof(uint64_t);
+        if (!bytes) return;
+        bool dev = zkm_is_device_ptr(states);
+        zkm_scratch_list tmp(c);
+        uint64_t* d = dev ? states : tmp.alloc<uint64_t>(bytes);
+        if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(d, states, bytes, hipMemcpyHostToDevice, c->stream));
+        launch(c, d, k);
+        if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(states, d, bytes, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+    });
+}
 int zkm_poseidon_permute_batch(zkm_ctx* c, uint64_t* states, size_t k, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));
-    size_t bytes = k * 12 * sizeof(uint64_t);
-    if (!bytes) return 0;
-    bool dev = zkm_is_device_ptr(states);
-    gl_t* d = dev ? states : (gl_t*)c->alloc(bytes);
-    if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(d, states, bytes, hipMemcpyHostToDevice, c->stream));
-    zkm_launch_poseidon_permute(c, d, k);
-    if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(states, d, bytes, hipMemcpyDeviceToHost, c->stream));
-    c->sync();
-    if (!dev) c->release(d);
-    ZKM_API_END(err)
+    return permute_batch("zkm_poseidon_permute_batch", c, states, k, 12, err, zkm_launch_poseidon_permute);
 }
-
 int zkm_keccakf_batch(zkm_ctx* c, uint64_t* states, size_t k, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));
-    size_t bytes = k * 25 * sizeof(uint64_t);
-    if (!bytes) return 0;
-    bool dev = zkm_is_device_ptr(states);
-    uint64_t* d = dev ? states : (uint64_t*)c->alloc(bytes);
-    if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(d, states, bytes, hipMemcpyHostToDevice, c->stream));
-    zkm_launch_keccakf(c, d, k);
-    if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(states, d, bytes, hipMemcpyDeviceToHost, c->stream));
-    c->sync();
-    if (!dev) c->release(d);
-    ZKM_API_END(err)
+    return permute_batch("zkm_keccakf_batch", c, states, k, 25, err, zkm_launch_keccakf);
 }
 
 int zkm_poseidon_trace(zkm_ctx* c, uint64_t seed, size_t num_perms, unsigned log_n, uint64_t* out_dev, char** err) {
-    ZKM_API_BEGIN
-    ZKM_HIP_CHECK(hipSetDevice(c->device));
-    if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_poseidon_trace: out must be a device pointer");
-    zkm_launch_poseidon_trace(c, seed, nullptr, nullptr, num_perms, log_n, out_dev);
-    c->sync();
-    ZKM_API_END(err)
+    return zkm_api("zkm_poseidon_trace", c, err, [&] {
+        if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_poseidon_trace: out must be a device pointer");
+        zkm_launch_poseidon_trace(c, seed, nullptr, nullptr, num_perms, log_n, out_dev);
+        c->sync();
+    });
+}
+
+// host -> device staging of small argument arrays for the witness entry points (device pointers are used where they lie)
+static const void* stage_arg(zkm_scratch_list& tmp, const void* p, size_t bytes) {
+    if (!bytes || zkm_is_device_ptr(p)) return p;
+    void* d = tmp.alloc(bytes);
+    ZKM_HIP_CHECK(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, tmp.c->stream));
+    return d;
 }
 
 // shared host side of the two sponge witness generators: rows per operation = len / rate + 1
 static int sponge_trace(zkm_ctx* c, const char* what, size_t rate, bool poseidon, const uint8_t* inputs, const uint64_t* input_off,
                         const uint64_t* meta, size_t nops, unsigned log_n, uint64_t* out_dev, size_t* rows_used_out, char** err) {
-    std::vector<void*> tmp;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api(what, c, err, [&] {
         if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error(std::string(what) + ": out must be a device pointer");
         size_t n = (size_t)1 << log_n;
         std::vector<uint64_t> row_off(nops + 1, 0);
@@ -1362,21 +1285,11 @@ static int sponge_trace(zkm_ctx* c, const char* what, size_t rate, bool poseidon
             row_off[i + 1] = row_off[i] + (input_off[i + 1] - input_off[i]) / rate + 1;
         }
         if (row_off[nops] > n) throw std::runtime_error(std::string(what) + ": operations need more rows than 2^log_n");
-        size_t nbytes = nops ? input_off[nops] : 0;
-        bool idev = zkm_is_device_ptr(inputs);
-        const uint8_t* d_in = inputs;
-        if (!idev && nbytes) {
-            void* p = c->alloc(nbytes);
-            tmp.push_back(p);
-            ZKM_HIP_CHECK(hipMemcpyAsync(p, inputs, nbytes, hipMemcpyHostToDevice, c->stream));
-            d_in = (const uint8_t*)p;
-        }
-        uint64_t* d_off = (uint64_t*)c->alloc((nops + 1) * 8);
-        tmp.push_back(d_off);
-        uint64_t* d_meta = (uint64_t*)c->alloc((nops ? nops : 1) * 32);
-        tmp.push_back(d_meta);
-        uint64_t* d_row = (uint64_t*)c->alloc((nops + 1) * 8);
-        tmp.push_back(d_row);
+        zkm_scratch_list tmp(c);
+        const uint8_t* d_in = (const uint8_t*)stage_arg(tmp, inputs, nops ? input_off[nops] : 0);
+        uint64_t* d_off = tmp.alloc<uint64_t>((nops + 1) * 8);
+        uint64_t* d_meta = tmp.alloc<uint64_t>((nops ? nops : 1) * 32);
+        uint64_t* d_row = tmp.alloc<uint64_t>((nops + 1) * 8);
         ZKM_HIP_CHECK(hipMemcpyAsync(d_off, input_off, (nops + 1) * 8, hipMemcpyHostToDevice, c->stream));
         if (nops) ZKM_HIP_CHECK(hipMemcpyAsync(d_meta, meta, nops * 32, hipMemcpyHostToDevice, c->stream));
         ZKM_HIP_CHECK(hipMemcpyAsync(d_row, row_off.data(), (nops + 1) * 8, hipMemcpyHostToDevice, c->stream));
@@ -1384,13 +1297,7 @@ static int sponge_trace(zkm_ctx* c, const char* what, size_t rate, bool poseidon
         else zkm_launch_keccak_sponge_trace(c, d_in, d_off, d_meta, d_row, nops, (size_t)row_off[nops], log_n, out_dev);
         c->sync();
         if (rows_used_out) *rows_used_out = row_off[nops];
-        for (void* p : tmp) c->release(p);
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 int zkm_keccak_sponge_trace(zkm_ctx* c, const uint8_t* inputs, const uint64_t* input_off, const uint64_t* meta, size_t nops,
@@ -1405,30 +1312,16 @@ int zkm_poseidon_sponge_trace(zkm_ctx* c, const uint8_t* inputs, const uint64_t*
 
 int zkm_poseidon_trace_inputs(zkm_ctx* c, const uint64_t* inputs, const uint64_t* timestamps, size_t num_perms, unsigned log_n,
                               uint64_t* out_dev, char** err) {
-    std::vector<void*> tmp;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_poseidon_trace_inputs", c, err, [&] {
         if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_poseidon_trace_inputs: out must be a device pointer");
         if (num_perms > ((size_t)1 << log_n)) throw std::runtime_error("zkm_poseidon_trace_inputs: more permutations than 2^log_n rows");
         if (num_perms && (!inputs || !timestamps)) throw std::runtime_error("zkm_poseidon_trace_inputs: inputs and timestamps are required");
-        auto to_dev = [&](const uint64_t* p, size_t words) -> const uint64_t* {
-            if (!words || zkm_is_device_ptr(p)) return p;
-            void* d = c->alloc(words * 8);
-            tmp.push_back(d);
-            ZKM_HIP_CHECK(hipMemcpyAsync(d, p, words * 8, hipMemcpyHostToDevice, c->stream));
-            return (const uint64_t*)d;
-        };
-        const uint64_t* d_in = to_dev(inputs, num_perms * 12);
-        const uint64_t* d_ts = to_dev(timestamps, num_perms);
+        zkm_scratch_list tmp(c);
+        const uint64_t* d_in = (const uint64_t*)stage_arg(tmp, inputs, num_perms * 12 * 8);
+        const uint64_t* d_ts = (const uint64_t*)stage_arg(tmp, timestamps, num_perms * 8);
         zkm_launch_poseidon_trace(c, 0, num_perms ? d_in : nullptr, num_perms ? d_ts : nullptr, num_perms, log_n, out_dev);
         c->sync();
-        for (void* p : tmp) c->release(p);
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 size_t zkm_num_lookup_columns(int table_id, const zkm_stark_config* cfg) {
@@ -1456,78 +1349,48 @@ size_t zkm_table_width(int table_id) {
     }
 }
 
-// host -> device staging of small argument arrays for the witness entry points
-static const void* stage_arg(zkm_ctx* c, std::vector<void*>& tmp, const void* p, size_t bytes) {
-    if (!bytes || zkm_is_device_ptr(p)) return p;
-    void* d = c->alloc(bytes);
-    tmp.push_back(d);
-    ZKM_HIP_CHECK(hipMemcpyAsync(d, p, bytes, hipMemcpyHostToDevice, c->stream));
-    return d;
-}
-
 int zkm_sha_extend_trace(zkm_ctx* c, const uint8_t* inputs, const uint64_t* timestamps, size_t nrows, unsigned log_n, uint64_t* out_dev,
                          char** err) {
-    std::vector<void*> tmp;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_sha_extend_trace", c, err, [&] {
         if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_sha_extend_trace: out must be a device pointer");
         size_t n = (size_t)1 << log_n;
         if (nrows > n) throw std::runtime_error("zkm_sha_extend_trace: more rows than 2^log_n");
-        const uint8_t* d_in = (const uint8_t*)stage_arg(c, tmp, inputs, nrows * 16);
-        const uint64_t* d_ts = (const uint64_t*)stage_arg(c, tmp, timestamps, nrows * 8);
+        zkm_scratch_list tmp(c);
+        const uint8_t* d_in = (const uint8_t*)stage_arg(tmp, inputs, nrows * 16);
+        const uint64_t* d_ts = (const uint64_t*)stage_arg(tmp, timestamps, nrows * 8);
         zkm_launch_sha_extend_trace(c, d_in, d_ts, nrows, n, out_dev);
         c->sync();
-        for (void* p : tmp) c->release(p);
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 int zkm_sha_extend_sponge_trace(zkm_ctx* c, const uint32_t* w16, const uint64_t* meta, size_t nblocks, unsigned log_n, uint64_t* out_dev,
                                 char** err) {
-    std::vector<void*> tmp;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_sha_extend_sponge_trace", c, err, [&] {
         if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_sha_extend_sponge_trace: out must be a device pointer");
         size_t n = (size_t)1 << log_n;
         if (48 * nblocks > n) throw std::runtime_error("zkm_sha_extend_sponge_trace: message schedules need more rows than 2^log_n (48 each)");
-        const uint32_t* d_w = (const uint32_t*)stage_arg(c, tmp, w16, nblocks * 64);
-        const uint64_t* d_meta = (const uint64_t*)stage_arg(c, tmp, meta, nblocks * 32);
+        zkm_scratch_list tmp(c);
+        const uint32_t* d_w = (const uint32_t*)stage_arg(tmp, w16, nblocks * 64);
+        const uint64_t* d_meta = (const uint64_t*)stage_arg(tmp, meta, nblocks * 32);
         zkm_launch_sha_extend_sponge_trace(c, d_w, d_meta, nblocks, n, out_dev);
         c->sync();
-        for (void* p : tmp) c->release(p);
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 static int sha_compress_trace(zkm_ctx* c, bool sponge, const uint32_t* hx, const uint32_t* w, const uint64_t* meta, size_t ncomp,
                               unsigned log_n, uint64_t* out_dev, char** err) {
-    std::vector<void*> tmp;
     const char* what = sponge ? "zkm_sha_compress_sponge_trace" : "zkm_sha_compress_trace";
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api(what, c, err, [&] {
         if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error(std::string(what) + ": out must be a device pointer");
         size_t n = (size_t)1 << log_n;
         if ((sponge ? 1 : 65) * ncomp > n) throw std::runtime_error(std::string(what) + ": compressions need more rows than 2^log_n");
-        const uint32_t* d_hx = (const uint32_t*)stage_arg(c, tmp, hx, ncomp * 32);
-        const uint32_t* d_w = (const uint32_t*)stage_arg(c, tmp, w, ncomp * 256);
-        const uint64_t* d_meta = (const uint64_t*)stage_arg(c, tmp, meta, ncomp * 64);
+        zkm_scratch_list tmp(c);
+        const uint32_t* d_hx = (const uint32_t*)stage_arg(tmp, hx, ncomp * 32);
+        const uint32_t* d_w = (const uint32_t*)stage_arg(tmp, w, ncomp * 256);
+        const uint64_t* d_meta = (const uint64_t*)stage_arg(tmp, meta, ncomp * 64);
         zkm_launch_sha_compress_trace(c, sponge, d_hx, d_w, d_meta, ncomp, n, out_dev);
         c->sync();
-        for (void* p : tmp) c->release(p);
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 int zkm_sha_compress_trace(zkm_ctx* c, const uint32_t* hx, const uint32_t* w, const uint64_t* meta, size_t ncomp, unsigned log_n,
                            uint64_t* out_dev, char** err) {
@@ -1540,62 +1403,33 @@ int zkm_sha_compress_sponge_trace(zkm_ctx* c, const uint32_t* hx, const uint32_t
 
 int zkm_keccak_trace(zkm_ctx* c, const uint64_t* inputs, const uint64_t* timestamps, size_t nperms, unsigned log_n, uint64_t* out_dev,
                      char** err) {
-    std::vector<void*> tmp;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_keccak_trace", c, err, [&] {
         if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_keccak_trace: out must be a device pointer");
         size_t n = (size_t)1 << log_n;
         if (nperms * 24 > n) throw std::runtime_error("zkm_keccak_trace: permutations need more rows than 2^log_n (24 each)");
-        auto to_dev = [&](const uint64_t* p, size_t words) -> const uint64_t* {
-            if (!words || zkm_is_device_ptr(p)) return p;
-            void* d = c->alloc(words * 8);
-            tmp.push_back(d);
-            ZKM_HIP_CHECK(hipMemcpyAsync(d, p, words * 8, hipMemcpyHostToDevice, c->stream));
-            return (const uint64_t*)d;
-        };
-        const uint64_t* d_in = to_dev(inputs, nperms * 25);
-        const uint64_t* d_ts = to_dev(timestamps, nperms);
+        zkm_scratch_list tmp(c);
+        const uint64_t* d_in = (const uint64_t*)stage_arg(tmp, inputs, nperms * 25 * 8);
+        const uint64_t* d_ts = (const uint64_t*)stage_arg(tmp, timestamps, nperms * 8);
         zkm_launch_keccak_trace(c, d_in, d_ts, nperms, n, out_dev);
         c->sync();
-        for (void* p : tmp) c->release(p);
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 int zkm_logic_trace(zkm_ctx* c, const uint32_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, char** err) {
-    std::vector<void*> tmp;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_logic_trace", c, err, [&] {
         if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_logic_trace: out must be a device pointer");
         size_t n = (size_t)1 << log_n;
         if (nops > n) throw std::runtime_error("zkm_logic_trace: more operations than 2^log_n rows");
-        const uint32_t* d_ops = ops;
-        if (nops && !zkm_is_device_ptr(ops)) {
-            void* p = c->alloc(nops * 12);
-            tmp.push_back(p);
-            ZKM_HIP_CHECK(hipMemcpyAsync(p, ops, nops * 12, hipMemcpyHostToDevice, c->stream));
-            d_ops = (const uint32_t*)p;
-        }
-        int* d_bad = (int*)c->alloc(sizeof(int));
-        tmp.push_back(d_bad);
+        zkm_scratch_list tmp(c);
+        const uint32_t* d_ops = (const uint32_t*)stage_arg(tmp, ops, nops * 12);
+        int* d_bad = tmp.alloc<int>(sizeof(int));
         ZKM_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
         zkm_launch_logic_trace(c, d_ops, nops, n, out_dev, d_bad);
         int bad = 0;
         ZKM_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         c->sync();
-        for (void* p : tmp) c->release(p);
-        tmp.clear();
         if (bad) throw std::runtime_error("zkm_logic_trace: op code out of range (0 and, 1 or, 2 xor, 3 nor)");
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 }  // extern "C"

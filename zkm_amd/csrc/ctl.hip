@@ -389,45 +389,25 @@ static std::vector<table_zs> derive_zs(size_t ntables, const zkm_cross_table_loo
     return out;
 }
 
-static int fail(char** err, const std::string& msg) {
-    if (err) {
-        *err = (char*)malloc(msg.size() + 1);
-        if (*err) memcpy(*err, msg.c_str(), msg.size() + 1);
-    }
-    return 1;
-}
-
 extern "C" {
 
 int zkm_ctl_data(zkm_ctx* c, const zkm_ctl_table* table, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs,
                  const uint64_t* trace, size_t ncols, unsigned log_n, uint64_t* aux_out, char** err) {
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_ctl_data", c, err, [&] {
         size_t n = (size_t)1 << log_n;
         ctl_dev_owner own;
         own.upload(c, table, zs, colset_ids, nzs, false, ncols);
         for (size_t i = 0; i < (table ? table->nterms : 0); i++)
             if (table->term_col[i] >= ncols) throw std::runtime_error("CTL description: trace column index out of range");
         bool tdev = zkm_is_device_ptr(trace), adev = zkm_is_device_ptr(aux_out);
-        gl_t* d_trace = tdev ? const_cast<gl_t*>(trace) : (gl_t*)c->alloc(ncols * n * 8);
+        zkm_scratch_list tmp(c);
+        gl_t* d_trace = tdev ? const_cast<gl_t*>(trace) : tmp.alloc<gl_t>(ncols * n * 8);
         if (!tdev) ZKM_HIP_CHECK(hipMemcpyAsync(d_trace, trace, ncols * n * 8, hipMemcpyHostToDevice, c->stream));
-        gl_t* d_aux = adev ? aux_out : (gl_t*)c->alloc(own.naux * n * 8);
-        try {
-            zkm_ctl_data_device(c, own, d_trace, log_n, d_aux, 1, 0, 0);
-            if (!adev) ZKM_HIP_CHECK(hipMemcpyAsync(aux_out, d_aux, own.naux * n * 8, hipMemcpyDeviceToHost, c->stream));
-            c->sync();
-        } catch (...) {
-            (void)hipStreamSynchronize(c->stream);
-            if (!tdev) c->release(d_trace);
-            if (!adev) c->release(d_aux);
-            throw;
-        }
-        if (!tdev) c->release(d_trace);
-        if (!adev) c->release(d_aux);
-    } catch (const std::exception& e) {
-        return fail(err, e.what());
-    }
-    return 0;
+        gl_t* d_aux = adev ? aux_out : tmp.alloc<gl_t>(own.naux * n * 8);
+        zkm_ctl_data_device(c, own, d_trace, log_n, d_aux, 1, 0, 0);
+        if (!adev) ZKM_HIP_CHECK(hipMemcpyAsync(aux_out, d_aux, own.naux * n * 8, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+    });
 }
 
 }  // extern "C"
@@ -437,43 +417,32 @@ int zkm_ctl_data(zkm_ctx* c, const zkm_ctl_table* table, const zkm_ctl_z* zs, co
 static void lookup_helper_columns_device(zkm_ctx* c, const zkm_ctl_table* table, const uint32_t* colset_ids, size_t nlookup, uint32_t table_col,
                                          uint32_t freq_col, const uint64_t* challenges, const gl_t* d_trace, size_t n, gl_t* d_out,
                                          size_t trace_ncols = 0, size_t nseg = 1, size_t trace_seg = 0, size_t out_seg = 0) {
-    std::vector<void*> tmp;
     size_t nh = (nlookup + 1) / 2;
     std::vector<zkm_ctl_z> zl(nseg);
     for (size_t sg = 0; sg < nseg; sg++) zl[sg] = zkm_ctl_z{(uint32_t)nlookup, 0, (uint32_t)nh, 0, 1, challenges[sg]};  // GrandProductChallenge{beta: 1, gamma: challenge}
     ctl_dev_owner own;
     own.upload(c, table, zl.data(), colset_ids, 1, /*lookup_mode=*/true, trace_ncols, nseg);
     const unsigned z = (unsigned)nseg;
-    try {
-        gl_t* d_hsum = (gl_t*)c->alloc(nseg * n * 8);
-        tmp.push_back(d_hsum);
-        gl_t* d_x = (gl_t*)c->alloc(nseg * n * 8);
-        tmp.push_back(d_x);
-        int* d_bad = (int*)c->alloc(ZKM_MAX_SEG * sizeof(int));
-        tmp.push_back(d_bad);
-        ZKM_HIP_CHECK(hipMemsetAsync(d_bad, 0, ZKM_MAX_SEG * sizeof(int), c->stream));
-        {
-            zkm_prof_scope ps(c, "lookup_terms");
-            hipLaunchKernelGGL(k_ctl_terms, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, own.d, 0u, d_trace, n, d_out, d_hsum, d_bad, trace_seg,
-                               out_seg);
-            hipLaunchKernelGGL(k_lookup_x, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, own.d, table_col, freq_col, d_trace, n, d_hsum, d_x,
-                               trace_seg);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        suffix_sum(c, d_x, n, n, 1, d_hsum, n, nseg, n, n);
-        hipLaunchKernelGGL(k_prefix_from_suffix, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, d_hsum, n, d_out + nh * n, out_seg);
+    zkm_scratch_list tmp(c);
+    gl_t* d_hsum = tmp.alloc<gl_t>(nseg * n * 8);
+    gl_t* d_x = tmp.alloc<gl_t>(nseg * n * 8);
+    int* d_bad = tmp.alloc<int>(ZKM_MAX_SEG * sizeof(int));
+    ZKM_HIP_CHECK(hipMemsetAsync(d_bad, 0, ZKM_MAX_SEG * sizeof(int), c->stream));
+    {
+        zkm_prof_scope ps(c, "lookup_terms");
+        hipLaunchKernelGGL(k_ctl_terms, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, own.d, 0u, d_trace, n, d_out, d_hsum, d_bad, trace_seg,
+                           out_seg);
+        hipLaunchKernelGGL(k_lookup_x, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, own.d, table_col, freq_col, d_trace, n, d_hsum, d_x,
+                           trace_seg);
         ZKM_HIP_CHECK(hipGetLastError());
-        int bad[ZKM_MAX_SEG];
-        c->download(bad, d_bad, ZKM_MAX_SEG * sizeof(int));
-        for (void* p : tmp) c->release(p);
-        tmp.clear();
-        for (size_t sg = 0; sg < nseg; sg++)
-            if (bad[sg]) throw zkm_segment_error(sg, "Non-binary filter?");
-    } catch (...) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        throw;
     }
+    suffix_sum(c, d_x, n, n, 1, d_hsum, n, nseg, n, n);
+    hipLaunchKernelGGL(k_prefix_from_suffix, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, d_hsum, n, d_out + nh * n, out_seg);
+    ZKM_HIP_CHECK(hipGetLastError());
+    int bad[ZKM_MAX_SEG];
+    c->download(bad, d_bad, ZKM_MAX_SEG * sizeof(int));
+    for (size_t sg = 0; sg < nseg; sg++)
+        if (bad[sg]) throw zkm_segment_error(sg, "Non-binary filter?");
 }
 
 // A table's own logUp lookups (Stark::lookups()): every use in the reference is Column::single columns without filters
@@ -513,9 +482,7 @@ extern "C" {
 int zkm_lookup_helper_columns(zkm_ctx* c, const zkm_ctl_table* table, const uint32_t* colset_ids, size_t nlookup, uint32_t table_col,
                               uint32_t freq_col, uint64_t challenge, const uint64_t* trace, size_t ncols, unsigned log_n,
                               uint64_t* out, char** err) {
-    std::vector<void*> tmp;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_lookup_helper_columns", c, err, [&] {
         if (!table || nlookup == 0) throw std::runtime_error("zkm_lookup_helper_columns: empty lookup");
         if (table_col >= table->ncolumns || freq_col >= table->ncolumns) throw std::runtime_error("lookup: column index out of range");
         if (challenge >= GL_P) throw std::runtime_error("lookup: non-canonical challenge");
@@ -526,21 +493,14 @@ int zkm_lookup_helper_columns(zkm_ctx* c, const zkm_ctl_table* table, const uint
             if (colset_ids[i] < table->ncolsets && table->colsets[colset_ids[i]].ncols != 1)
                 throw std::runtime_error("lookup: every looking entry must be a single-column set");
         bool tdev = zkm_is_device_ptr(trace), odev = zkm_is_device_ptr(out);
-        gl_t* d_trace = tdev ? const_cast<gl_t*>(trace) : (gl_t*)c->alloc(ncols * n * 8);
-        if (!tdev) { tmp.push_back(d_trace); ZKM_HIP_CHECK(hipMemcpyAsync(d_trace, trace, ncols * n * 8, hipMemcpyHostToDevice, c->stream)); }
-        gl_t* d_out = odev ? out : (gl_t*)c->alloc((nh + 1) * n * 8);
-        if (!odev) tmp.push_back(d_out);
+        zkm_scratch_list tmp(c);
+        gl_t* d_trace = tdev ? const_cast<gl_t*>(trace) : tmp.alloc<gl_t>(ncols * n * 8);
+        if (!tdev) ZKM_HIP_CHECK(hipMemcpyAsync(d_trace, trace, ncols * n * 8, hipMemcpyHostToDevice, c->stream));
+        gl_t* d_out = odev ? out : tmp.alloc<gl_t>((nh + 1) * n * 8);
         lookup_helper_columns_device(c, table, colset_ids, nlookup, table_col, freq_col, &challenge, d_trace, n, d_out, ncols);
         if (!odev) ZKM_HIP_CHECK(hipMemcpyAsync(out, d_out, (nh + 1) * n * 8, hipMemcpyDeviceToHost, c->stream));
         c->sync();
-        for (void* p : tmp) c->release(p);
-        tmp.clear();
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* p : tmp) c->release(p);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 // ---- the AllStark description shipped with the library (all_stark_ctl.inc, generated from zkm_amd/tables.py)
@@ -557,33 +517,37 @@ const zkm_ctl_table* zkm_all_stark_ctl_table(int table_id) {
 }
 int zkm_prove_segment(zkm_ctx* c, const zkm_stark_config* cfg, const uint64_t* const* traces, const unsigned* log_n,
                       const uint64_t* pub, size_t npub, uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
-    if (!traces || !log_n) return fail(err, "zkm_prove_segment: null argument");
-    zkm_table_input tables[12];
-    for (int t = 0; t < 12; t++) tables[t] = zkm_table_input{AS_TABLE_IDS[t], traces[t], AS_TABLE_WIDTH[t], log_n[t], &AS_CTL_TABLES[t], nullptr};
-    size_t offs[13];
-    size_t total = zkm_all_proof_words(cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, offs);
-    if (!total) return fail(err, "zkm_prove_segment: unsupported configuration or table size");
-    if (offsets_out) memcpy(offsets_out, offs, sizeof offs);
-    if (!proofs) return 0;  // sizing pass
-    if (!c || !challenges) return fail(err, "zkm_prove_segment: null argument");
-    return zkm_prove_with_traces(c, cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, pub, npub, proofs, challenges, err);
+    return zkm_api("zkm_prove_segment", err, [&] {
+        if (!traces || !log_n) throw std::runtime_error("zkm_prove_segment: null argument");
+        zkm_table_input tables[12];
+        for (int t = 0; t < 12; t++) tables[t] = zkm_table_input{AS_TABLE_IDS[t], traces[t], AS_TABLE_WIDTH[t], log_n[t], &AS_CTL_TABLES[t], nullptr};
+        size_t offs[13];
+        size_t total = zkm_all_proof_words(cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, offs);
+        if (!total) throw std::runtime_error("zkm_prove_segment: unsupported configuration or table size");
+        if (offsets_out) memcpy(offsets_out, offs, sizeof offs);
+        if (!proofs) return 0;  // sizing pass
+        if (!c || !challenges) throw std::runtime_error("zkm_prove_segment: null argument");
+        return zkm_prove_with_traces(c, cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, pub, npub, proofs, challenges, err);
+    });
 }
 
 int zkm_prove_segment_columns(zkm_ctx* c, const zkm_stark_config* cfg, const uint64_t* const* const* columns, const unsigned* log_n,
                               const uint64_t* pub, size_t npub, uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
-    if (!columns || !log_n) return fail(err, "zkm_prove_segment_columns: null argument");
-    zkm_table_input tables[12];
-    for (int t = 0; t < 12; t++) {
-        if (!columns[t]) return fail(err, "zkm_prove_segment_columns: null table");
-        tables[t] = zkm_table_input{AS_TABLE_IDS[t], nullptr, AS_TABLE_WIDTH[t], log_n[t], &AS_CTL_TABLES[t], columns[t]};
-    }
-    size_t offs[13];
-    size_t total = zkm_all_proof_words(cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, offs);
-    if (!total) return fail(err, "zkm_prove_segment_columns: unsupported configuration or table size");
-    if (offsets_out) memcpy(offsets_out, offs, sizeof offs);
-    if (!proofs) return 0;  // sizing pass
-    if (!c || !challenges) return fail(err, "zkm_prove_segment_columns: null argument");
-    return zkm_prove_with_traces(c, cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, pub, npub, proofs, challenges, err);
+    return zkm_api("zkm_prove_segment_columns", err, [&] {
+        if (!columns || !log_n) throw std::runtime_error("zkm_prove_segment_columns: null argument");
+        zkm_table_input tables[12];
+        for (int t = 0; t < 12; t++) {
+            if (!columns[t]) throw std::runtime_error("zkm_prove_segment_columns: null table");
+            tables[t] = zkm_table_input{AS_TABLE_IDS[t], nullptr, AS_TABLE_WIDTH[t], log_n[t], &AS_CTL_TABLES[t], columns[t]};
+        }
+        size_t offs[13];
+        size_t total = zkm_all_proof_words(cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, offs);
+        if (!total) throw std::runtime_error("zkm_prove_segment_columns: unsupported configuration or table size");
+        if (offsets_out) memcpy(offsets_out, offs, sizeof offs);
+        if (!proofs) return 0;  // sizing pass
+        if (!c || !challenges) throw std::runtime_error("zkm_prove_segment_columns: null argument");
+        return zkm_prove_with_traces(c, cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, pub, npub, proofs, challenges, err);
+    });
 }
 
 int zkm_table_enum_index(int table_id) {
@@ -597,21 +561,19 @@ int zkm_table_enum_index(int table_id) {
 
 size_t zkm_all_proof_words(const zkm_stark_config* cfg, const zkm_table_input* tables, size_t ntables,
                            const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t* offs) {
-    try {
+    size_t total = 0;
+    const int rc = zkm_api("zkm_all_proof_words", nullptr, [&] {
         auto tz = derive_zs(ntables, ctls, sides, nctls, cfg->num_challenges, nullptr);
-        size_t total = 0;
         for (size_t t = 0; t < ntables; t++) {
             if (offs) offs[t] = total;
             size_t w = zkm_proof_words(cfg, tables[t].log_n, tables[t].ncols, zkm_num_lookup_columns(tables[t].table_id, cfg) + tz[t].naux,
                                        tz[t].zs.size());
-            if (!w) return 0;  // unsupported configuration / table height
+            if (!w) { total = 0; return; }  // unsupported configuration / table height
             total += w;
         }
         if (offs) offs[ntables] = total;
-        return total;
-    } catch (...) {
-        return 0;
-    }
+    });
+    return rc ? 0 : total;
 }
 
 }  // extern "C"
@@ -1183,16 +1145,11 @@ extern "C" {
 int zkm_prove_with_traces(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_table_input* tables, size_t ntables,
                           const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, const uint64_t* pub,
                           size_t npub, uint64_t* proofs, uint64_t* challenges, char** err) {
-    try {
-        if (!c || !cfg || (!tables && ntables)) throw std::runtime_error("zkm_prove_with_traces: null argument");
+    return zkm_api("zkm_prove_with_traces", c, err, [&] {
+        if (!cfg || (!tables && ntables)) throw std::runtime_error("zkm_prove_with_traces: null argument");
         seg_io io{tables, pub, npub, proofs, challenges};
         prove_segments_impl(c, cfg, 1, &io, ntables, ctls, sides, nctls);
-    } catch (const std::exception& e) {
-        return fail(err, e.what());
-    } catch (...) {
-        return fail(err, "zkm_prove_with_traces: unknown error");
-    }
-    return 0;
+    });
 }
 
 // traces[s][t] (one block per table) or columns[s][t][i] (one pointer per column) -- exactly one of the two is non-null
@@ -1200,8 +1157,8 @@ int zkm_prove_with_traces(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_tab
 int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const uint64_t* const* const* traces,
                              const uint64_t* const* const* const* columns, const unsigned* const* log_n, const uint64_t* const* pub,
                              const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges, char** err, size_t seg_base) {
-    try {
-        if (!c || !cfg || (!traces && !columns) || !log_n || !proofs || !challenges) throw std::runtime_error(std::string(what) + ": null argument");
+    return zkm_api(what, c, err, [&] {
+        if (!cfg || (!traces && !columns) || !log_n || !proofs || !challenges) throw std::runtime_error(std::string(what) + ": null argument");
         std::vector<std::vector<zkm_table_input>> tables(nseg, std::vector<zkm_table_input>(12));
         std::vector<seg_io> io(nseg);
         for (size_t s = 0; s < nseg; s++) {
@@ -1216,12 +1173,7 @@ int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_confi
             if (io[s].npub && !io[s].pub) throw std::runtime_error(std::string(what) + ": null public values");
         }
         prove_segments_waves(c, cfg, nseg, io.data(), 12, AS_CTLS, AS_SIDES, AS_NCTLS, seg_base);
-    } catch (const std::exception& e) {
-        return fail(err, e.what());
-    } catch (...) {
-        return fail(err, std::string(what) + ": unknown error");
-    }
-    return 0;
+    });
 }
 
 int zkm_prove_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const uint64_t* const* const* traces, const unsigned* const* log_n,

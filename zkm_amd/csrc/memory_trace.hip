@@ -15,7 +15,6 @@
 //   (7) k_mem_neighbours first-change flags, RANGE_CHECK, COUNTER and the FREQUENCIES histogram (:83-166).
 // Only the key widths and the row count come back to the host before the output is written.
 #include <algorithm>
-#include <memory>
 
 #include "zkm_internal.h"
 
@@ -393,20 +392,11 @@ size_t next_pow2(size_t v) {
 }
 size_t blocks_for(size_t items, size_t per) { return (items + per - 1) / per; }
 
-int fail(char** err, const std::string& msg) {
-    if (err) {
-        *err = (char*)malloc(msg.size() + 1);
-        if (*err) memcpy(*err, msg.c_str(), msg.size() + 1);
-    }
-    return 1;
-}
-
 }  // namespace
 
 extern "C" int zkm_memory_trace(zkm_ctx* c, const uint64_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, size_t* natural_rows_out,
                                 char** err) {
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_memory_trace", c, err, [&] {
         if (nops == 0) throw std::runtime_error("zkm_memory_trace: No memory ops?");
         if (nops >= ((size_t)1 << 32)) throw std::runtime_error("zkm_memory_trace: 2^32 or more memory ops");
         if (out_dev) {
@@ -415,12 +405,11 @@ extern "C" int zkm_memory_trace(zkm_ctx* c, const uint64_t* ops, size_t nops, un
             if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_memory_trace: out must be a device pointer");
         }
         const uint32_t m = (uint32_t)nops;
-        std::unique_ptr<zkm_scratch> host_copy;
+        zkm_scratch_list host_copy(c);
         const uint64_t* d_ops = ops;
         if (!zkm_is_device_ptr(ops)) {
-            host_copy.reset(new zkm_scratch(c, nops * 48));
-            ZKM_HIP_CHECK(hipMemcpyAsync(host_copy->p, ops, nops * 48, hipMemcpyHostToDevice, c->stream));
-            d_ops = host_copy->as<uint64_t>();
+            d_ops = host_copy.alloc<uint64_t>(nops * 48);
+            ZKM_HIP_CHECK(hipMemcpyAsync((void*)d_ops, ops, nops * 48, hipMemcpyHostToDevice, c->stream));
         }
         // small: [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies, [6] range-check flag
         zkm_scratch small(c, 64);
@@ -493,7 +482,7 @@ extern "C" int zkm_memory_trace(zkm_ctx* c, const uint64_t* ops, size_t nops, un
         }
         const size_t natural = next_pow2(count);
         if (natural_rows_out) *natural_rows_out = natural;
-        if (!out_dev) return 0;
+        if (!out_dev) return;
         const size_t n = (size_t)1 << log_n;
         if (natural > n)
             throw std::runtime_error("zkm_memory_trace: the table needs " + std::to_string(natural) + " rows, more than 2^" + std::to_string(log_n));
@@ -513,9 +502,5 @@ extern "C" int zkm_memory_trace(zkm_ctx* c, const uint64_t* ops, size_t nops, un
         int bad = 0;
         c->download(&bad, d_bad, sizeof(bad));
         if (bad) throw std::runtime_error("zkm_memory_trace: a range check is 2^log_n or more (a context or segment gap)");
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }

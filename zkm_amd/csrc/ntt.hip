@@ -83,8 +83,7 @@ __global__ void k_field_selftest(const uint64_t* __restrict__ a, const uint64_t*
     out[5 * n + i] = gl_mul(x, y);
 }
 extern "C" int zkm_field_selftest(zkm_ctx* c, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out, char** err) {
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_field_selftest", c, err, [&] {
         zkm_scratch da(c, n * 8), db(c, n * 8), dout(c, 7 * n * 8);
         ZKM_HIP_CHECK(hipMemcpyAsync(da.p, a, n * 8, hipMemcpyHostToDevice, c->stream));
         ZKM_HIP_CHECK(hipMemcpyAsync(db.p, b, n * 8, hipMemcpyHostToDevice, c->stream));
@@ -93,11 +92,7 @@ extern "C" int zkm_field_selftest(zkm_ctx* c, const uint64_t* a, const uint64_t*
         zkm_launch_mul_selftest_branchfree(c, da.as<uint64_t>(), db.as<uint64_t>(), n, dout.as<uint64_t>() + 6 * n);
         ZKM_HIP_CHECK(hipMemcpyAsync(out, dout.p, 7 * n * 8, hipMemcpyDeviceToHost, c->stream));
         c->sync();
-    } catch (const std::exception& e) {
-        if (err) *err = strdup(e.what());
-        return 1;
-    }
-    return 0;
+    });
 }
 
 // ------------------------------------------------------------------ multi-stage LDS pass kernel

@@ -21,14 +21,6 @@ struct zkm_pool {
     std::vector<size_t> last_worker, last_group;   // of the last call: who proved segment s, in which group
 };
 
-static int pool_fail(char** err, const std::string& msg) {
-    if (err) {
-        *err = (char*)malloc(msg.size() + 1);
-        if (*err) memcpy(*err, msg.c_str(), msg.size() + 1);
-    }
-    return 1;
-}
-
 // The groups of one call: consecutive runs of at most `stack` segments, the same number of groups for every worker (the fewest that
 // keeps a group within `stack`), sizes as even as the count allows -- 20 segments, 2 workers, stack 4 -> 4, 4, 3, 3, 3, 3
 // (zkm_amd/dist.py chunk_segments is the same rule; tests/test_pool.py holds them against each other).
@@ -48,17 +40,18 @@ static std::vector<std::pair<size_t, size_t>> pool_groups(size_t nseg, size_t wo
     return g;
 }
 
-static int pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack,
-                      const uint64_t* const* const* traces, const uint64_t* const* const* const* columns, const unsigned* const* log_n,
-                      const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges, char** err) {
-    if (!p || !cfg || (!traces && !columns) || !log_n || !proofs || !challenges) return pool_fail(err, std::string(what) + ": null argument");
+// (throws: the entry points below run it inside the error boundary)
+static void pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack,
+                       const uint64_t* const* const* traces, const uint64_t* const* const* const* columns, const unsigned* const* log_n,
+                       const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges) {
+    if (!p || !cfg || (!traces && !columns) || !log_n || !proofs || !challenges) throw std::runtime_error(std::string(what) + ": null argument");
     if (max_stack == 0) max_stack = 8;
-    if (max_stack > ZKM_MAX_SEG) return pool_fail(err, std::string(what) + ": max_stack beyond " + std::to_string(ZKM_MAX_SEG));
+    if (max_stack > ZKM_MAX_SEG) throw std::runtime_error(std::string(what) + ": max_stack beyond " + std::to_string(ZKM_MAX_SEG));
     const size_t W = p->ctxs.size();
     const auto groups = pool_groups(nseg, W, max_stack);
     p->last_worker.assign(nseg, ~(size_t)0);
     p->last_group.assign(nseg, ~(size_t)0);
-    if (groups.empty()) return 0;
+    if (groups.empty()) return;
     std::mutex mu;
     size_t next = 0;
     std::string first_error;
@@ -72,19 +65,9 @@ static int pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cfg
                 g = next++;
             }
             const size_t s0 = groups[g].first, k = groups[g].second;
-            char* e = nullptr;
-            int rc = 1;
-            try {
-                rc = zkm_prove_segments_entry(what, p->ctxs[w], cfg, k, traces ? traces + s0 : nullptr, columns ? columns + s0 : nullptr, log_n + s0,
-                                              pub ? pub + s0 : nullptr, npub ? npub + s0 : nullptr, proofs + s0, challenges + s0, &e, s0);
-            } catch (const std::exception& x) {    // (the entry catches everything itself: belt and braces, a worker thread must not unwind)
-                rc = 1;
-                const std::string m = x.what();
-                e = (char*)malloc(m.size() + 1);
-                if (e) memcpy(e, m.c_str(), m.size() + 1);
-            } catch (...) {
-                rc = 1;
-            }
+            char* e = nullptr;   // (the entry point is noexcept: nothing unwinds out of a worker thread)
+            const int rc = zkm_prove_segments_entry(what, p->ctxs[w], cfg, k, traces ? traces + s0 : nullptr, columns ? columns + s0 : nullptr,
+                                                    log_n + s0, pub ? pub + s0 : nullptr, npub ? npub + s0 : nullptr, proofs + s0, challenges + s0, &e, s0);
             std::lock_guard<std::mutex> lk(mu);
             if (rc != 0) {
                 if (!failed)
@@ -107,43 +90,39 @@ static int pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cfg
     }
     worker(0);
     for (auto& t : th) t.join();
-    if (failed) return pool_fail(err, first_error);
-    return 0;
+    if (failed) throw std::runtime_error(first_error);
 }
 
 extern "C" {
 
 int zkm_pool_create(const int* devices, size_t ndevices, size_t contexts_per_device, zkm_pool** out, char** err) {
-    if (!out) return pool_fail(err, "zkm_pool_create: null argument");
-    *out = nullptr;
-    if (!devices || ndevices == 0 || contexts_per_device == 0) return pool_fail(err, "zkm_pool_create: at least one device and one context per device");
-    if (ndevices > 64 || contexts_per_device > 64) return pool_fail(err, "zkm_pool_create: at most 64 devices x 64 contexts");
-    for (size_t i = 0; i < ndevices; i++)
-        for (size_t j = 0; j < i; j++)
-            if (devices[i] == devices[j]) return pool_fail(err, "zkm_pool_create: device " + std::to_string(devices[i]) + " listed twice");
-    zkm_pool* p = nullptr;
-    try {
-        p = new zkm_pool();
-    } catch (...) {
-        return pool_fail(err, "zkm_pool_create: out of memory");
-    }
-    // worker order: device-major round robin (worker w -> device w % ndevices), so the first `ndevices` groups of a call land on
-    // different devices even when the call has fewer groups than workers
-    for (size_t k = 0; k < contexts_per_device; k++)
-        for (size_t d = 0; d < ndevices; d++) {
-            zkm_ctx* c = nullptr;
-            char* e = nullptr;
-            if (zkm_ctx_create(devices[d], &c, &e) != 0) {
-                const std::string msg = "zkm_pool_create: context " + std::to_string(k) + " on device " + std::to_string(devices[d]) + ": " + (e ? e : "failed");
-                free(e);
-                zkm_pool_destroy(p);
-                return pool_fail(err, msg);
+    return zkm_api("zkm_pool_create", err, [&] {
+        if (!out) throw std::runtime_error("zkm_pool_create: null argument");
+        *out = nullptr;
+        if (!devices || ndevices == 0 || contexts_per_device == 0) throw std::runtime_error("zkm_pool_create: at least one device and one context per device");
+        if (ndevices > 64 || contexts_per_device > 64) throw std::runtime_error("zkm_pool_create: at most 64 devices x 64 contexts");
+        for (size_t i = 0; i < ndevices; i++)
+            for (size_t j = 0; j < i; j++)
+                if (devices[i] == devices[j]) throw std::runtime_error("zkm_pool_create: device " + std::to_string(devices[i]) + " listed twice");
+        std::unique_ptr<zkm_pool, void (*)(zkm_pool*)> p(new zkm_pool(), zkm_pool_destroy);
+        p->ctxs.reserve(ndevices * contexts_per_device);    // (a context, once created, is in the pool: push_back cannot throw)
+        p->devices.reserve(ndevices * contexts_per_device);
+        // worker order: device-major round robin (worker w -> device w % ndevices), so the first `ndevices` groups of a call land on
+        // different devices even when the call has fewer groups than workers
+        for (size_t k = 0; k < contexts_per_device; k++)
+            for (size_t d = 0; d < ndevices; d++) {
+                zkm_ctx* c = nullptr;
+                char* e = nullptr;
+                if (zkm_ctx_create(devices[d], &c, &e) != 0) {
+                    const std::string msg = "zkm_pool_create: context " + std::to_string(k) + " on device " + std::to_string(devices[d]) + ": " + (e ? e : "failed");
+                    free(e);
+                    throw std::runtime_error(msg);
+                }
+                p->ctxs.push_back(c);
+                p->devices.push_back(devices[d]);
             }
-            p->ctxs.push_back(c);
-            p->devices.push_back(devices[d]);
-        }
-    *out = p;
-    return 0;
+        *out = p.release();
+    });
 }
 
 void zkm_pool_destroy(zkm_pool* p) {
@@ -157,24 +136,26 @@ zkm_ctx* zkm_pool_context(zkm_pool* p, size_t w) { return (p && w < p->ctxs.size
 int zkm_pool_device(const zkm_pool* p, size_t w) { return (p && w < p->devices.size()) ? p->devices[w] : -1; }
 
 int zkm_pool_set_tuning(zkm_pool* p, const char* key, uint64_t value, char** err) {
-    if (!p) return pool_fail(err, "zkm_pool_set_tuning: null argument");
-    for (zkm_ctx* c : p->ctxs) {
-        const int rc = zkm_ctx_set_tuning(c, key, value, err);
-        if (rc != 0) return rc;
-    }
-    return 0;
+    return zkm_api("zkm_pool_set_tuning", err, [&] {
+        if (!p) throw std::runtime_error("zkm_pool_set_tuning: null argument");
+        for (zkm_ctx* c : p->ctxs)
+            if (const int rc = zkm_ctx_set_tuning(c, key, value, err)) return rc;
+        return 0;
+    });
 }
 
 int zkm_pool_prove_segments(zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack, const uint64_t* const* const* traces,
                             const unsigned* const* log_n, const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs,
                             uint64_t* const* challenges, char** err) {
-    return pool_prove("zkm_pool_prove_segments", p, cfg, nseg, max_stack, traces, nullptr, log_n, pub, npub, proofs, challenges, err);
+    return zkm_api("zkm_pool_prove_segments", err,
+                   [&] { pool_prove("zkm_pool_prove_segments", p, cfg, nseg, max_stack, traces, nullptr, log_n, pub, npub, proofs, challenges); });
 }
 
 int zkm_pool_prove_segments_columns(zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack,
                                     const uint64_t* const* const* const* columns, const unsigned* const* log_n, const uint64_t* const* pub,
                                     const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges, char** err) {
-    return pool_prove("zkm_pool_prove_segments_columns", p, cfg, nseg, max_stack, nullptr, columns, log_n, pub, npub, proofs, challenges, err);
+    return zkm_api("zkm_pool_prove_segments_columns", err,
+                   [&] { pool_prove("zkm_pool_prove_segments_columns", p, cfg, nseg, max_stack, nullptr, columns, log_n, pub, npub, proofs, challenges); });
 }
 
 size_t zkm_pool_plan(size_t nseg, size_t workers, size_t max_stack, size_t* group_sizes_out, size_t capacity) {

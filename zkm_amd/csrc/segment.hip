@@ -15,10 +15,6 @@ constexpr uint64_t SEGMENT_MAGIC = 0x45434152544d4b5aULL;  // "ZKMTRACE" little-
 constexpr uint64_t SEGMENT_VERSION = 1;
 constexpr size_t HEADER_WORDS = 8, TABLE_WORDS = 8;
 
-int fail_msg(char** err, const std::string& m) {
-    if (err) *err = strdup(m.c_str());
-    return 1;
-}
 size_t u32_words(size_t n) { return (n + 1) / 2; }
 size_t desc_words(const zkm_ctl_table* t) {
     if (!t) return 0;
@@ -93,112 +89,115 @@ size_t zkm_segment_image_words(const zkm_table_input* tables, size_t ntables, co
 
 int zkm_segment_image_write(const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
                             size_t nctls, const uint64_t* pub, size_t npub, uint64_t* img, char** err) {
-    if (!img || (ntables && !tables) || (nctls && (!ctls || !sides))) return fail_msg(err, "zkm_segment_image_write: null argument");
-    size_t nsides = 0;
-    for (size_t i = 0; i < nctls; i++) {
-        if (ctls[i].looking_off != nsides) return fail_msg(err, "zkm_segment_image_write: looking sides must be stored in lookup order");
-        nsides += ctls[i].nlooking;
-    }
-    for (size_t t = 0; t < ntables; t++) {
-        if (!tables[t].trace && !tables[t].columns) return fail_msg(err, "zkm_segment_image_write: table without a trace");
-        if (!tables[t].columns && zkm_is_device_ptr(tables[t].trace)) return fail_msg(err, "zkm_segment_image_write: traces must be host pointers");
-        for (size_t i = 0; tables[t].columns && i < tables[t].ncols; i++)
-            if (!tables[t].columns[i] || zkm_is_device_ptr(tables[t].columns[i]))
-                return fail_msg(err, "zkm_segment_image_write: columns must be host pointers");
-    }
-    img[0] = SEGMENT_MAGIC; img[1] = SEGMENT_VERSION; img[2] = ntables; img[3] = npub; img[4] = nctls; img[5] = nsides; img[6] = img[7] = 0;
-    size_t o = HEADER_WORDS;
-    if (npub) memcpy(img + o, pub, npub * 8);
-    o += npub;
-    uint64_t* th = img + o;
-    o += TABLE_WORDS * ntables;
-    for (size_t t = 0; t < ntables; t++) {
-        const zkm_ctl_table* c = tables[t].ctl;
-        uint64_t* h = th + TABLE_WORDS * t;
-        h[0] = (uint64_t)tables[t].table_id; h[1] = tables[t].ncols; h[2] = tables[t].log_n; h[3] = 0;
-        h[4] = c ? c->ncolumns : 0; h[5] = c ? c->nterms : 0; h[6] = c ? c->ncolsets : 0; h[7] = c ? c->nfilter_idx : 0;
-        if (!c) continue;
-        memcpy(img + o, c->columns, c->ncolumns * sizeof(zkm_column)); o += 3 * c->ncolumns;
-        img[o + u32_words(c->nterms) - (c->nterms ? 1 : 0)] = 0;
-        memcpy(img + o, c->term_col, c->nterms * 4); o += u32_words(c->nterms);
-        memcpy(img + o, c->term_coeff, c->nterms * 8); o += c->nterms;
-        memcpy(img + o, c->colsets, c->ncolsets * sizeof(zkm_colset)); o += 4 * c->ncolsets;
-        if (c->nfilter_idx) img[o + u32_words(c->nfilter_idx) - 1] = 0;
-        memcpy(img + o, c->filter_idx, c->nfilter_idx * 4); o += u32_words(c->nfilter_idx);
-    }
-    memcpy(img + o, ctls, nctls * sizeof(zkm_cross_table_lookup)); o += 2 * nctls;
-    memcpy(img + o, sides, nsides * sizeof(zkm_ctl_side)); o += nsides;
-    for (size_t t = 0; t < ntables; t++) {
-        size_t words = tables[t].ncols << tables[t].log_n;
-        th[TABLE_WORDS * t + 3] = o;
-        if (tables[t].columns)
-            for (size_t i = 0; i < tables[t].ncols; i++) memcpy(img + o + (i << tables[t].log_n), tables[t].columns[i], (size_t)8 << tables[t].log_n);
-        else
-            memcpy(img + o, tables[t].trace, words * 8);
-        o += words;
-    }
-    return 0;
+    return zkm_api("zkm_segment_image_write", err, [&] {
+        if (!img || (ntables && !tables) || (nctls && (!ctls || !sides))) throw std::runtime_error("zkm_segment_image_write: null argument");
+        size_t nsides = 0;
+        for (size_t i = 0; i < nctls; i++) {
+            if (ctls[i].looking_off != nsides) throw std::runtime_error("zkm_segment_image_write: looking sides must be stored in lookup order");
+            nsides += ctls[i].nlooking;
+        }
+        for (size_t t = 0; t < ntables; t++) {
+            if (!tables[t].trace && !tables[t].columns) throw std::runtime_error("zkm_segment_image_write: table without a trace");
+            if (!tables[t].columns && zkm_is_device_ptr(tables[t].trace)) throw std::runtime_error("zkm_segment_image_write: traces must be host pointers");
+            for (size_t i = 0; tables[t].columns && i < tables[t].ncols; i++)
+                if (!tables[t].columns[i] || zkm_is_device_ptr(tables[t].columns[i]))
+                    throw std::runtime_error("zkm_segment_image_write: columns must be host pointers");
+        }
+        img[0] = SEGMENT_MAGIC; img[1] = SEGMENT_VERSION; img[2] = ntables; img[3] = npub; img[4] = nctls; img[5] = nsides; img[6] = img[7] = 0;
+        size_t o = HEADER_WORDS;
+        if (npub) memcpy(img + o, pub, npub * 8);
+        o += npub;
+        uint64_t* th = img + o;
+        o += TABLE_WORDS * ntables;
+        for (size_t t = 0; t < ntables; t++) {
+            const zkm_ctl_table* c = tables[t].ctl;
+            uint64_t* h = th + TABLE_WORDS * t;
+            h[0] = (uint64_t)tables[t].table_id; h[1] = tables[t].ncols; h[2] = tables[t].log_n; h[3] = 0;
+            h[4] = c ? c->ncolumns : 0; h[5] = c ? c->nterms : 0; h[6] = c ? c->ncolsets : 0; h[7] = c ? c->nfilter_idx : 0;
+            if (!c) continue;
+            memcpy(img + o, c->columns, c->ncolumns * sizeof(zkm_column)); o += 3 * c->ncolumns;
+            img[o + u32_words(c->nterms) - (c->nterms ? 1 : 0)] = 0;
+            memcpy(img + o, c->term_col, c->nterms * 4); o += u32_words(c->nterms);
+            memcpy(img + o, c->term_coeff, c->nterms * 8); o += c->nterms;
+            memcpy(img + o, c->colsets, c->ncolsets * sizeof(zkm_colset)); o += 4 * c->ncolsets;
+            if (c->nfilter_idx) img[o + u32_words(c->nfilter_idx) - 1] = 0;
+            memcpy(img + o, c->filter_idx, c->nfilter_idx * 4); o += u32_words(c->nfilter_idx);
+        }
+        memcpy(img + o, ctls, nctls * sizeof(zkm_cross_table_lookup)); o += 2 * nctls;
+        memcpy(img + o, sides, nsides * sizeof(zkm_ctl_side)); o += nsides;
+        for (size_t t = 0; t < ntables; t++) {
+            size_t words = tables[t].ncols << tables[t].log_n;
+            th[TABLE_WORDS * t + 3] = o;
+            if (tables[t].columns)
+                for (size_t i = 0; i < tables[t].ncols; i++) memcpy(img + o + (i << tables[t].log_n), tables[t].columns[i], (size_t)8 << tables[t].log_n);
+            else
+                memcpy(img + o, tables[t].trace, words * 8);
+            o += words;
+        }
+    });
 }
 
 int zkm_prove_segment_image(zkm_ctx* c, const zkm_stark_config* cfg, const uint64_t* img, size_t image_words, uint64_t* proofs,
                             size_t* proof_words_out, size_t* offsets_out, uint64_t* challenges, char** err) {
-    if (!img || image_words < HEADER_WORDS || img[0] != SEGMENT_MAGIC) return fail_msg(err, "zkm_prove_segment_image: not a ZKMTRACE image");
-    if (img[1] != SEGMENT_VERSION) return fail_msg(err, "zkm_prove_segment_image: unsupported image version");
-    // Every size below comes from the image: all checks are subtractions against the words that remain (no sums of untrusted
-    // 64-bit fields, which could wrap), and every field is bounded before it is multiplied or used as a shift count.
-    const uint64_t ntables = img[2], npub = img[3], nctls = img[4], nsides = img[5];
-    size_t o = HEADER_WORDS;
-    auto take = [&](uint64_t words, size_t per) -> bool {  // reserve words * per image words at o; false if they do not fit
-        if (per && words > (image_words - o) / per) return false;
-        o += (size_t)words * per;
-        return true;
-    };
-    if (ntables > 4096 || nctls > 65536) return fail_msg(err, "zkm_prove_segment_image: truncated header");
-    const uint64_t* pub = img + o;
-    if (!take(npub, 1)) return fail_msg(err, "zkm_prove_segment_image: truncated header");
-    const uint64_t* th = img + o;
-    if (!take(ntables, TABLE_WORDS)) return fail_msg(err, "zkm_prove_segment_image: truncated header");
-    std::vector<zkm_ctl_table> descs(ntables);
-    std::vector<zkm_table_input> tables(ntables);
-    for (size_t t = 0; t < ntables; t++) {
-        const uint64_t* h = th + TABLE_WORDS * t;
-        zkm_ctl_table& d = descs[t];
-        const char* trunc = "zkm_prove_segment_image: truncated table description";
-        // (u32 arrays are stored two per word: counts are bounded by twice the remaining words before u32_words() rounds them)
-        if (h[1] == 0 || h[1] > (1u << 20) || h[2] > 40) return fail_msg(err, "zkm_prove_segment_image: table width / height out of range");
-        if (h[5] > 2 * (uint64_t)(image_words - o) || h[7] > 2 * (uint64_t)(image_words - o)) return fail_msg(err, trunc);
-        d.ncolumns = h[4]; d.nterms = h[5]; d.ncolsets = h[6]; d.nfilter_idx = h[7];
-        d.columns = (const zkm_column*)(img + o);
-        if (!take(h[4], 3)) return fail_msg(err, trunc);
-        d.term_col = (const uint32_t*)(img + o);
-        if (!take(u32_words(d.nterms), 1)) return fail_msg(err, trunc);
-        d.term_coeff = img + o;
-        if (!take(h[5], 1)) return fail_msg(err, trunc);
-        d.colsets = (const zkm_colset*)(img + o);
-        if (!take(h[6], 4)) return fail_msg(err, trunc);
-        d.filter_idx = (const uint32_t*)(img + o);
-        if (!take(u32_words(d.nfilter_idx), 1)) return fail_msg(err, trunc);
-        tables[t].table_id = (int)h[0]; tables[t].ncols = h[1]; tables[t].log_n = (unsigned)h[2]; tables[t].ctl = &d;
-        // ncols <= 2^20 and log_n <= 40: the product cannot wrap
-        const uint64_t words = h[1] << h[2];
-        if (h[3] > image_words || words > image_words - h[3]) return fail_msg(err, "zkm_prove_segment_image: trace data out of bounds");
-        tables[t].trace = img + h[3];
-        tables[t].columns = nullptr;
-    }
-    const zkm_cross_table_lookup* ctls = (const zkm_cross_table_lookup*)(img + o);
-    if (!take(nctls, 2)) return fail_msg(err, "zkm_prove_segment_image: truncated lookup description");
-    const zkm_ctl_side* sides = (const zkm_ctl_side*)(img + o);
-    if (!take(nsides, 1)) return fail_msg(err, "zkm_prove_segment_image: truncated lookup description");
-    for (size_t i = 0; i < nctls; i++)
-        if (ctls[i].looking_off > nsides || ctls[i].nlooking > nsides - ctls[i].looking_off)
-            return fail_msg(err, "zkm_prove_segment_image: looking sides out of range");
-    std::vector<size_t> offs(ntables + 1, 0);
-    size_t total = zkm_all_proof_words(cfg, tables.data(), ntables, ctls, sides, nctls, offs.data());
-    if (!total && ntables) return fail_msg(err, "zkm_prove_segment_image: malformed cross-table lookups");
-    if (proof_words_out) *proof_words_out = total;
-    if (offsets_out) memcpy(offsets_out, offs.data(), (ntables + 1) * sizeof(size_t));
-    if (!proofs) return 0;
-    return zkm_prove_with_traces(c, cfg, tables.data(), ntables, ctls, sides, nctls, pub, npub, proofs, challenges, err);
+    return zkm_api("zkm_prove_segment_image", err, [&] {
+        if (!img || image_words < HEADER_WORDS || img[0] != SEGMENT_MAGIC) throw std::runtime_error("zkm_prove_segment_image: not a ZKMTRACE image");
+        if (img[1] != SEGMENT_VERSION) throw std::runtime_error("zkm_prove_segment_image: unsupported image version");
+        // Every size below comes from the image: all checks are subtractions against the words that remain (no sums of untrusted
+        // 64-bit fields, which could wrap), and every field is bounded before it is multiplied or used as a shift count.
+        const uint64_t ntables = img[2], npub = img[3], nctls = img[4], nsides = img[5];
+        size_t o = HEADER_WORDS;
+        auto take = [&](uint64_t words, size_t per) -> bool {  // reserve words * per image words at o; false if they do not fit
+            if (per && words > (image_words - o) / per) return false;
+            o += (size_t)words * per;
+            return true;
+        };
+        if (ntables > 4096 || nctls > 65536) throw std::runtime_error("zkm_prove_segment_image: truncated header");
+        const uint64_t* pub = img + o;
+        if (!take(npub, 1)) throw std::runtime_error("zkm_prove_segment_image: truncated header");
+        const uint64_t* th = img + o;
+        if (!take(ntables, TABLE_WORDS)) throw std::runtime_error("zkm_prove_segment_image: truncated header");
+        std::vector<zkm_ctl_table> descs(ntables);
+        std::vector<zkm_table_input> tables(ntables);
+        for (size_t t = 0; t < ntables; t++) {
+            const uint64_t* h = th + TABLE_WORDS * t;
+            zkm_ctl_table& d = descs[t];
+            const char* trunc = "zkm_prove_segment_image: truncated table description";
+            // (u32 arrays are stored two per word: counts are bounded by twice the remaining words before u32_words() rounds them)
+            if (h[1] == 0 || h[1] > (1u << 20) || h[2] > 40) throw std::runtime_error("zkm_prove_segment_image: table width / height out of range");
+            if (h[5] > 2 * (uint64_t)(image_words - o) || h[7] > 2 * (uint64_t)(image_words - o)) throw std::runtime_error(trunc);
+            d.ncolumns = h[4]; d.nterms = h[5]; d.ncolsets = h[6]; d.nfilter_idx = h[7];
+            d.columns = (const zkm_column*)(img + o);
+            if (!take(h[4], 3)) throw std::runtime_error(trunc);
+            d.term_col = (const uint32_t*)(img + o);
+            if (!take(u32_words(d.nterms), 1)) throw std::runtime_error(trunc);
+            d.term_coeff = img + o;
+            if (!take(h[5], 1)) throw std::runtime_error(trunc);
+            d.colsets = (const zkm_colset*)(img + o);
+            if (!take(h[6], 4)) throw std::runtime_error(trunc);
+            d.filter_idx = (const uint32_t*)(img + o);
+            if (!take(u32_words(d.nfilter_idx), 1)) throw std::runtime_error(trunc);
+            tables[t].table_id = (int)h[0]; tables[t].ncols = h[1]; tables[t].log_n = (unsigned)h[2]; tables[t].ctl = &d;
+            // ncols <= 2^20 and log_n <= 40: the product cannot wrap
+            const uint64_t words = h[1] << h[2];
+            if (h[3] > image_words || words > image_words - h[3]) throw std::runtime_error("zkm_prove_segment_image: trace data out of bounds");
+            tables[t].trace = img + h[3];
+            tables[t].columns = nullptr;
+        }
+        const zkm_cross_table_lookup* ctls = (const zkm_cross_table_lookup*)(img + o);
+        if (!take(nctls, 2)) throw std::runtime_error("zkm_prove_segment_image: truncated lookup description");
+        const zkm_ctl_side* sides = (const zkm_ctl_side*)(img + o);
+        if (!take(nsides, 1)) throw std::runtime_error("zkm_prove_segment_image: truncated lookup description");
+        for (size_t i = 0; i < nctls; i++)
+            if (ctls[i].looking_off > nsides || ctls[i].nlooking > nsides - ctls[i].looking_off)
+                throw std::runtime_error("zkm_prove_segment_image: looking sides out of range");
+        std::vector<size_t> offs(ntables + 1, 0);
+        size_t total = zkm_all_proof_words(cfg, tables.data(), ntables, ctls, sides, nctls, offs.data());
+        if (!total && ntables) throw std::runtime_error("zkm_prove_segment_image: malformed cross-table lookups");
+        if (proof_words_out) *proof_words_out = total;
+        if (offsets_out) memcpy(offsets_out, offs.data(), (ntables + 1) * sizeof(size_t));
+        if (!proofs) return 0;
+        return zkm_prove_with_traces(c, cfg, tables.data(), ntables, ctls, sides, nctls, pub, npub, proofs, challenges, err);
+    });
 }
 
 }  // extern "C"

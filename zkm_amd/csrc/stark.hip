@@ -1221,173 +1221,157 @@ static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, 
     const unsigned lde_bits = log_n + cfg->rate_bits;
     const size_t N = (size_t)1 << lde_bits;
     std::vector<fri_layer> layers(L);
-    std::vector<void*> scratch;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(c->stream);
-        for (auto& l : layers) { c->release(l.values); c->release(l.digests); }
-        for (void* p : scratch) c->release(p);
-    };
-    try {
-        gl_t* d_fin = (gl_t*)c->alloc(nseg * 2 * n * sizeof(gl_t));  // final poly coefficients [segment][2][n]
-        scratch.push_back(d_fin);
-        divide_accumulate_all(c, comps, comp_seg, n, d_fin, d_fin + n);
+    zkm_scratch_list scratch(c);   // (the layers' blocks too)
+    gl_t* d_fin = scratch.alloc<gl_t>(nseg * 2 * n * sizeof(gl_t));  // final poly coefficients [segment][2][n]
+    divide_accumulate_all(c, comps, comp_seg, n, d_fin, d_fin + n);
 
-        // commit phase: coefficients stay in d_fin (length clen, implicitly zero-padded x4)
-        size_t clen = n;
-        unsigned clog = log_n;
-        gl_t shift = GL_GENERATOR;
-        unsigned arity = 1u << cfg->arity_bits;
-        gl_t* d_coef = d_fin;       // [segment][2][clen]: c0 array, then c1
-        std::vector<uint64_t> capbuf(nseg * C4);
-        for (unsigned l = 0; l < L; l++) {
-            fri_layer& fl = layers[l];
-            fl.len = clen << cfg->rate_bits;
-            fl.values = (gl_t*)c->alloc(nseg * 2 * fl.len * sizeof(gl_t));
-            // values = coset_fft(shift) of the zero-padded coefficients, bit-reversed: two base-field columns per proof
-            // (the coefficient arrays are contiguous: [c0 | c1] per proof, column stride clen)
-            zkm_lde_bitrev(c, d_coef, fl.values, 2 * nseg, clog, cfg->rate_bits, shift);
-            fl.log_leaves = clog + cfg->rate_bits - cfg->arity_bits;
-            size_t dwords = zkm_merkle_layout(fl.log_leaves, cfg->cap_height, fl.level_off);
-            fl.dig_words = dwords;
-            fl.digests = (gl_t*)c->alloc(nseg * dwords * sizeof(gl_t));
-            zkm_launch_merkle_leaves_ext(c, fl.values, fl.values + fl.len, (size_t)1 << fl.log_leaves, arity, fl.digests, nseg, 2 * fl.len, dwords);
-            zkm_merkle_build_inner_cap(c, fl.digests, fl.level_off, fl.log_leaves, cfg->cap_height, capbuf.data(), nseg, dwords);
-            seg_gl2 betas{};
-            for (size_t sg = 0; sg < nseg; sg++) {
-                uint64_t* capo = caps_out[sg] + l * C4;
-                memcpy(capo, capbuf.data() + sg * C4, C4 * sizeof(uint64_t));
-                zkm_challenger_observe(chs[sg], capo, C4);
-                gl2_t beta = challenger_get_ext(chs[sg]);
-                betas.v[2 * sg] = beta.c0; betas.v[2 * sg + 1] = beta.c1;
-            }
-            size_t nout = clen >> cfg->arity_bits;
-            gl_t* d_new = (gl_t*)c->alloc(nseg * 2 * nout * sizeof(gl_t));
-            scratch.push_back(d_new);
-            {
-                zkm_prof_scope ps(c, "fri_fold");
-                const size_t lds = 2 * 64 * ((size_t)arity + 1) * sizeof(gl_t);
-                if (lds > 64 * 1024) {
-                    static std::atomic<uint64_t> lds_ok{0};
-                    const uint64_t bit = (uint64_t)1 << (c->device & 63);
-                    if (!(lds_ok.load(std::memory_order_acquire) & bit)) {
-                        ZKM_HIP_CHECK(hipFuncSetAttribute((const void*)k_fri_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                        lds_ok.fetch_or(bit, std::memory_order_release);
-                    }
+    // commit phase: coefficients stay in d_fin (length clen, implicitly zero-padded x4)
+    size_t clen = n;
+    unsigned clog = log_n;
+    gl_t shift = GL_GENERATOR;
+    unsigned arity = 1u << cfg->arity_bits;
+    gl_t* d_coef = d_fin;       // [segment][2][clen]: c0 array, then c1
+    std::vector<uint64_t> capbuf(nseg * C4);
+    for (unsigned l = 0; l < L; l++) {
+        fri_layer& fl = layers[l];
+        fl.len = clen << cfg->rate_bits;
+        fl.values = scratch.alloc<gl_t>(nseg * 2 * fl.len * sizeof(gl_t));
+        // values = coset_fft(shift) of the zero-padded coefficients, bit-reversed: two base-field columns per proof
+        // (the coefficient arrays are contiguous: [c0 | c1] per proof, column stride clen)
+        zkm_lde_bitrev(c, d_coef, fl.values, 2 * nseg, clog, cfg->rate_bits, shift);
+        fl.log_leaves = clog + cfg->rate_bits - cfg->arity_bits;
+        size_t dwords = zkm_merkle_layout(fl.log_leaves, cfg->cap_height, fl.level_off);
+        fl.dig_words = dwords;
+        fl.digests = scratch.alloc<gl_t>(nseg * dwords * sizeof(gl_t));
+        zkm_launch_merkle_leaves_ext(c, fl.values, fl.values + fl.len, (size_t)1 << fl.log_leaves, arity, fl.digests, nseg, 2 * fl.len, dwords);
+        zkm_merkle_build_inner_cap(c, fl.digests, fl.level_off, fl.log_leaves, cfg->cap_height, capbuf.data(), nseg, dwords);
+        seg_gl2 betas{};
+        for (size_t sg = 0; sg < nseg; sg++) {
+            uint64_t* capo = caps_out[sg] + l * C4;
+            memcpy(capo, capbuf.data() + sg * C4, C4 * sizeof(uint64_t));
+            zkm_challenger_observe(chs[sg], capo, C4);
+            gl2_t beta = challenger_get_ext(chs[sg]);
+            betas.v[2 * sg] = beta.c0; betas.v[2 * sg + 1] = beta.c1;
+        }
+        size_t nout = clen >> cfg->arity_bits;
+        gl_t* d_new = scratch.alloc<gl_t>(nseg * 2 * nout * sizeof(gl_t));
+        {
+            zkm_prof_scope ps(c, "fri_fold");
+            const size_t lds = 2 * 64 * ((size_t)arity + 1) * sizeof(gl_t);
+            if (lds > 64 * 1024) {
+                static std::atomic<uint64_t> lds_ok{0};
+                const uint64_t bit = (uint64_t)1 << (c->device & 63);
+                if (!(lds_ok.load(std::memory_order_acquire) & bit)) {
+                    ZKM_HIP_CHECK(hipFuncSetAttribute((const void*)k_fri_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                    lds_ok.fetch_or(bit, std::memory_order_release);
                 }
-                hipLaunchKernelGGL(k_fri_fold, dim3((unsigned)((nout + 63) / 64), 1, z), dim3(64), lds, c->stream, d_coef, d_coef + clen, nout, arity, betas,
-                                   d_new, d_new + nout);
-                ZKM_HIP_CHECK(hipGetLastError());
             }
-            d_coef = d_new;
-            clen = nout;
-            clog -= cfg->arity_bits;
-            shift = gl_pow(shift, arity);
+            hipLaunchKernelGGL(k_fri_fold, dim3((unsigned)((nout + 63) / 64), 1, z), dim3(64), lds, c->stream, d_coef, d_coef + clen, nout, arity, betas,
+                               d_new, d_new + nout);
+            ZKM_HIP_CHECK(hipGetLastError());
         }
-        if (clen != F) throw std::runtime_error("internal: final polynomial length mismatch");
-        {
-            std::vector<gl_t> f(nseg * 2 * clen);
-            c->download(f.data(), d_coef, nseg * 2 * clen * 8);
-            for (size_t sg = 0; sg < nseg; sg++) {
-                uint64_t* fp = final_out[sg];
-                const gl_t* fs = f.data() + sg * 2 * clen;
-                for (size_t i = 0; i < clen; i++) { fp[2 * i] = fs[i]; fp[2 * i + 1] = fs[clen + i]; }
-                zkm_challenger_observe(chs[sg], fp, 2 * clen);
-            }
-        }
-
-        // proof of work (App. A.9), smallest witness of every proof
-        {
-            std::vector<pow_state> sts(nseg);
-            seg_u32 pos{}, done{};
-            for (size_t sg = 0; sg < nseg; sg++) {
-                memcpy(sts[sg].s, chs[sg]->state, sizeof sts[sg].s);
-                for (uint32_t i = 0; i < chs[sg]->n_in; i++) sts[sg].s[i] = chs[sg]->in_buf[i];
-                pos.v[sg] = chs[sg]->n_in;
-            }
-            pow_state* d_sts = (pow_state*)c->alloc(nseg * sizeof(pow_state));
-            scratch.push_back(d_sts);
-            c->upload(d_sts, sts.data(), nseg * sizeof(pow_state));
-            unsigned long long* d_best = c->pow_best();      // ZKM_MAX_SEG words, all ones between searches (the kernel leaves them that way)
-            std::vector<unsigned long long> best(nseg, ~0ULL), got(nseg);
-            // 2^pow_round_log candidates per round and proof (17 for a proof alone: two waves per SIMD -- a wave alone issues at half the
-            // SIMD's rate, so the round is barely longer than with one, and it holds the hit with probability 0.86 instead of 0.63 at 16
-            // bits; the searches of a stack share the machine: the round of each shrinks with their number, down to 2^12, so that the
-            // stack's round is still one launch-filling set of waves and few candidates are tried beyond the round of a proof's first hit),
-            // up to 2^6 rounds per launch (a launch without a hit: probability e^-128 for a proof alone)
-            unsigned round_log = c->pow_round_log;
-            for (size_t k = 1; k < nseg && round_log > 12; k <<= 1) round_log--;
-            const uint64_t stride = (uint64_t)1 << round_log, span = stride << 6;
-            size_t open = nseg;
-            for (uint64_t base = 0; open; base += span) {
-                if (base > ((uint64_t)1 << 40)) throw std::runtime_error("Proof of work failed. This is highly unlikely!");
-                uint64_t *host_slot, *flag;
-                unsigned* counter;
-                const uint64_t seq = c->xfer_begin(8 * nseg, &host_slot, &flag, &counter);
-                {
-                    zkm_prof_scope ps(c, "fri_pow_search");
-                    hipLaunchKernelGGL(k_pow_search, dim3(stride / 256, z), dim3(256), 0, c->stream, d_sts, pos, done, cfg->pow_bits, base, base + span,
-                                       d_best, counter, host_slot, flag, seq);
-                    ZKM_HIP_CHECK(hipGetLastError());
-                }
-                c->xfer_finish(seq, got.data(), 8 * nseg);
-                for (size_t sg = 0; sg < nseg; sg++)
-                    if (!done.v[sg] && got[sg] != ~0ULL) { best[sg] = got[sg]; done.v[sg] = 1; open--; }
-            }
-            for (size_t sg = 0; sg < nseg; sg++) {
-                uint64_t w = best[sg];
-                *pow_out[sg] = w;
-                zkm_challenger_observe(chs[sg], &w, 1);
-                uint64_t resp = zkm_challenger_get(chs[sg]);
-                if ((resp >> (64 - cfg->pow_bits)) != 0) throw std::runtime_error("internal: proof-of-work response check failed");
-            }
-        }
-
-        // query rounds
-        {
-            if (nq > ZKM_FRI_MAX_QUERIES || lde_bits > 32) throw std::runtime_error("FRI: at most 128 query rounds on domains of at most 2^32 points");
-            std::vector<uint32_t> qs(nseg * nq);
-            for (size_t sg = 0; sg < nseg; sg++)
-                for (size_t q = 0; q < nq; q++) qs[sg * nq + q] = (uint32_t)(zkm_challenger_get(chs[sg]) % N);
-            uint32_t* d_qs = (uint32_t*)c->alloc(qs.size() * sizeof(uint32_t));
-            scratch.push_back(d_qs);
-            c->upload(d_qs, qs.data(), qs.size() * sizeof(uint32_t));
-            gather_args ga{};
-            ga.noracles = (uint32_t)noracles;
-            for (size_t k = 0; k < noracles; k++) {
-                if (orc[k]->lde_bits() != lde_bits || orc[k]->nseg != nseg) throw std::runtime_error("internal: oracle of another domain size in the query gather");
-                ga.o[k].lde = orc[k]->lde; ga.o[k].digests = orc[k]->digests; ga.o[k].ncols = (uint32_t)orc[k]->ncols;
-                ga.o[k].nsib = lde_bits - cfg->cap_height;
-                ga.lde_seg[k] = orc[k]->lde_seg(); ga.dig_seg[k] = orc[k]->dig_words;
-            }
-            for (unsigned l = 0; l < L; l++) {
-                ga.l[l].c0 = layers[l].values; ga.l[l].c1 = layers[l].values + layers[l].len; ga.l[l].digests = layers[l].digests;
-                ga.l[l].nsib = layers[l].log_leaves - cfg->cap_height;
-                ga.l[l].log_leaves = layers[l].log_leaves;
-                ga.val_seg[l] = 2 * layers[l].len; ga.ldig_seg[l] = layers[l].dig_words;
-            }
-            ga.nlayers = L; ga.arity_bits = cfg->arity_bits; ga.lde_bits = lde_bits; ga.query_words = query_words;
-            const size_t qwords = nq * query_words;
-            gl_t* d_q = (gl_t*)c->alloc(nseg * qwords * 8);
-            scratch.push_back(d_q);
-            {
-                zkm_prof_scope ps(c, "fri_gather_queries");
-                hipLaunchKernelGGL(k_gather_queries, dim3(nq, z), dim3(256), 0, c->stream, ga, d_qs, d_q);
-                ZKM_HIP_CHECK(hipGetLastError());
-            }
-            if (nseg == 1) {
-                c->download(queries_out[0], d_q, qwords * 8);
-            } else {
-                std::vector<gl_t> all(nseg * qwords);
-                c->download(all.data(), d_q, nseg * qwords * 8);
-                for (size_t sg = 0; sg < nseg; sg++) memcpy(queries_out[sg], all.data() + sg * qwords, qwords * 8);
-            }
-        }
-
-    } catch (...) {
-        cleanup();
-        throw;
+        d_coef = d_new;
+        clen = nout;
+        clog -= cfg->arity_bits;
+        shift = gl_pow(shift, arity);
     }
-    cleanup();
+    if (clen != F) throw std::runtime_error("internal: final polynomial length mismatch");
+    {
+        std::vector<gl_t> f(nseg * 2 * clen);
+        c->download(f.data(), d_coef, nseg * 2 * clen * 8);
+        for (size_t sg = 0; sg < nseg; sg++) {
+            uint64_t* fp = final_out[sg];
+            const gl_t* fs = f.data() + sg * 2 * clen;
+            for (size_t i = 0; i < clen; i++) { fp[2 * i] = fs[i]; fp[2 * i + 1] = fs[clen + i]; }
+            zkm_challenger_observe(chs[sg], fp, 2 * clen);
+        }
+    }
+
+    // proof of work (App. A.9), smallest witness of every proof
+    {
+        std::vector<pow_state> sts(nseg);
+        seg_u32 pos{}, done{};
+        for (size_t sg = 0; sg < nseg; sg++) {
+            memcpy(sts[sg].s, chs[sg]->state, sizeof sts[sg].s);
+            for (uint32_t i = 0; i < chs[sg]->n_in; i++) sts[sg].s[i] = chs[sg]->in_buf[i];
+            pos.v[sg] = chs[sg]->n_in;
+        }
+        pow_state* d_sts = scratch.alloc<pow_state>(nseg * sizeof(pow_state));
+        c->upload(d_sts, sts.data(), nseg * sizeof(pow_state));
+        unsigned long long* d_best = c->pow_best();      // ZKM_MAX_SEG words, all ones between searches (the kernel leaves them that way)
+        std::vector<unsigned long long> best(nseg, ~0ULL), got(nseg);
+        // 2^pow_round_log candidates per round and proof (17 for a proof alone: two waves per SIMD -- a wave alone issues at half the
+        // SIMD's rate, so the round is barely longer than with one, and it holds the hit with probability 0.86 instead of 0.63 at 16
+        // bits; the searches of a stack share the machine: the round of each shrinks with their number, down to 2^12, so that the
+        // stack's round is still one launch-filling set of waves and few candidates are tried beyond the round of a proof's first hit),
+        // up to 2^6 rounds per launch (a launch without a hit: probability e^-128 for a proof alone)
+        unsigned round_log = c->pow_round_log;
+        for (size_t k = 1; k < nseg && round_log > 12; k <<= 1) round_log--;
+        const uint64_t stride = (uint64_t)1 << round_log, span = stride << 6;
+        size_t open = nseg;
+        for (uint64_t base = 0; open; base += span) {
+            if (base > ((uint64_t)1 << 40)) throw std::runtime_error("Proof of work failed. This is highly unlikely!");
+            uint64_t *host_slot, *flag;
+            unsigned* counter;
+            const uint64_t seq = c->xfer_begin(8 * nseg, &host_slot, &flag, &counter);
+            {
+                zkm_prof_scope ps(c, "fri_pow_search");
+                hipLaunchKernelGGL(k_pow_search, dim3(stride / 256, z), dim3(256), 0, c->stream, d_sts, pos, done, cfg->pow_bits, base, base + span,
+                                   d_best, counter, host_slot, flag, seq);
+                ZKM_HIP_CHECK(hipGetLastError());
+            }
+            c->xfer_finish(seq, got.data(), 8 * nseg);
+            for (size_t sg = 0; sg < nseg; sg++)
+                if (!done.v[sg] && got[sg] != ~0ULL) { best[sg] = got[sg]; done.v[sg] = 1; open--; }
+        }
+        for (size_t sg = 0; sg < nseg; sg++) {
+            uint64_t w = best[sg];
+            *pow_out[sg] = w;
+            zkm_challenger_observe(chs[sg], &w, 1);
+            uint64_t resp = zkm_challenger_get(chs[sg]);
+            if ((resp >> (64 - cfg->pow_bits)) != 0) throw std::runtime_error("internal: proof-of-work response check failed");
+        }
+    }
+
+    // query rounds
+    {
+        if (nq > ZKM_FRI_MAX_QUERIES || lde_bits > 32) throw std::runtime_error("FRI: at most 128 query rounds on domains of at most 2^32 points");
+        std::vector<uint32_t> qs(nseg * nq);
+        for (size_t sg = 0; sg < nseg; sg++)
+            for (size_t q = 0; q < nq; q++) qs[sg * nq + q] = (uint32_t)(zkm_challenger_get(chs[sg]) % N);
+        uint32_t* d_qs = scratch.alloc<uint32_t>(qs.size() * sizeof(uint32_t));
+        c->upload(d_qs, qs.data(), qs.size() * sizeof(uint32_t));
+        gather_args ga{};
+        ga.noracles = (uint32_t)noracles;
+        for (size_t k = 0; k < noracles; k++) {
+            if (orc[k]->lde_bits() != lde_bits || orc[k]->nseg != nseg) throw std::runtime_error("internal: oracle of another domain size in the query gather");
+            ga.o[k].lde = orc[k]->lde; ga.o[k].digests = orc[k]->digests; ga.o[k].ncols = (uint32_t)orc[k]->ncols;
+            ga.o[k].nsib = lde_bits - cfg->cap_height;
+            ga.lde_seg[k] = orc[k]->lde_seg(); ga.dig_seg[k] = orc[k]->dig_words;
+        }
+        for (unsigned l = 0; l < L; l++) {
+            ga.l[l].c0 = layers[l].values; ga.l[l].c1 = layers[l].values + layers[l].len; ga.l[l].digests = layers[l].digests;
+            ga.l[l].nsib = layers[l].log_leaves - cfg->cap_height;
+            ga.l[l].log_leaves = layers[l].log_leaves;
+            ga.val_seg[l] = 2 * layers[l].len; ga.ldig_seg[l] = layers[l].dig_words;
+        }
+        ga.nlayers = L; ga.arity_bits = cfg->arity_bits; ga.lde_bits = lde_bits; ga.query_words = query_words;
+        const size_t qwords = nq * query_words;
+        gl_t* d_q = scratch.alloc<gl_t>(nseg * qwords * 8);
+        {
+            zkm_prof_scope ps(c, "fri_gather_queries");
+            hipLaunchKernelGGL(k_gather_queries, dim3(nq, z), dim3(256), 0, c->stream, ga, d_qs, d_q);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        if (nseg == 1) {
+            c->download(queries_out[0], d_q, qwords * 8);
+        } else {
+            std::vector<gl_t> all(nseg * qwords);
+            c->download(all.data(), d_q, nseg * qwords * 8);
+            for (size_t sg = 0; sg < nseg; sg++) memcpy(queries_out[sg], all.data() + sg * qwords, qwords * 8);
+        }
+    }
+
 }
 
 // prove_single_table for a STACK of nseg = chs.size() independent proofs of the same table at the same height (one proof: vectors of
@@ -1441,209 +1425,188 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
         proof[7] = y.L; proof[8] = y.F; proof[9] = y.nq; proof[10] = cfg->rate_bits; proof[11] = cfg->arity_bits;
     }
 
-    zkm_batch* own_trace = nullptr;
-    zkm_batch *ab = nullptr, *qb = nullptr;
-    std::vector<void*> scratch;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(c->stream);
-        zkm_batch_free(own_trace);
-        zkm_batch_free(ab);
-        zkm_batch_free(qb);
-        for (void* p : scratch) c->release(p);
-    };
-    try {
-        const zkm_batch* tb = trace_batch;
-        if (!tb) {
-            own_trace = new zkm_batch();
-            own_trace->ctx = c; own_trace->ncols = W; own_trace->log_n = log_n; own_trace->rate_bits = cfg->rate_bits;
-            own_trace->cap_height = cfg->cap_height;
-            zkm_prof_scope st(c, "stage/compute trace commitment");  // prover.rs:146-163 (done by the caller in the reference)
-            zkm_batch_build(own_trace, trace, true);
-            tb = own_trace;
-        }
-        if (tb->ncols != W || tb->log_n != log_n || tb->rate_bits != cfg->rate_bits || tb->cap_height != cfg->cap_height || tb->nseg != nseg)
-            throw std::runtime_error("trace commitment does not match the table shape / config");
+    zkm_scratch_list scratch(c);
+    zkm_batch_ptr own_trace, ab, qb;   // (freed before the scratch goes back: zkm_batch_free waits for the stream)
+    const zkm_batch* tb = trace_batch;
+    if (!tb) {
+        own_trace.reset(new zkm_batch());
+        own_trace->ctx = c; own_trace->ncols = W; own_trace->log_n = log_n; own_trace->rate_bits = cfg->rate_bits;
+        own_trace->cap_height = cfg->cap_height;
+        zkm_prof_scope st(c, "stage/compute trace commitment");  // prover.rs:146-163 (done by the caller in the reference)
+        zkm_batch_build(own_trace.get(), trace, true);
+        tb = own_trace.get();
+    }
+    if (tb->ncols != W || tb->log_n != log_n || tb->rate_bits != cfg->rate_bits || tb->cap_height != cfg->cap_height || tb->nseg != nseg)
+        throw std::runtime_error("trace commitment does not match the table shape / config");
 
-        const size_t C4 = y.C * 4;
-        for (size_t sg = 0; sg < nseg; sg++) {
-            zkm_challenger_compact(chs[sg], proofs[sg] + y.o_init);  // :466
-            memcpy(proofs[sg] + y.o_caps, tb->cap.data() + sg * C4, C4 * 8);
-        }
-        const zkm_batch *abp = aux_batch_in, *qbp = quot_batch_in;
-        if (aux_given) {
-            if (abp->ncols != A || abp->log_n != log_n || abp->rate_bits != cfg->rate_bits || abp->cap_height != cfg->cap_height || abp->nseg != nseg)
-                throw std::runtime_error("auxiliary commitment does not match the table shape / config");
-        } else if (!openings_only) {
-            // auxiliary commitment :511-522
-            ab = new zkm_batch();
-            ab->ctx = c; ab->ncols = A; ab->log_n = log_n; ab->rate_bits = cfg->rate_bits; ab->cap_height = cfg->cap_height;
-            if (NL) {
-                // "compute lookup helper columns" :475-493, then the CTL columns behind them
-                auto st = std::make_unique<zkm_prof_scope>(c, "stage/compute lookup helper columns");
-                gl_t* d_all = (gl_t*)c->alloc(A * n * sizeof(gl_t));
-                scratch.push_back(d_all);
-                const gl_t* d_trace = trace;
-                if (!zkm_is_device_ptr(trace)) {
-                    gl_t* d = (gl_t*)c->alloc(W * n * sizeof(gl_t));
-                    scratch.push_back(d);
-                    c->upload(d, trace, W * n * sizeof(gl_t));
-                    zkm_launch_canon(c, d, W * n);   // (host words may be any representative; the lookup kernels want canonical ones)
-                    d_trace = d;
-                }
-                zkm_table_lookup_columns_device(c, table_id, lookup_challenges, cfg->num_challenges, d_trace, n, d_all);
-                ZKM_HIP_CHECK(hipMemcpyAsync(d_all + NL * n, aux, A_ctl * n * sizeof(gl_t), hipMemcpyDefault, c->stream));
-                st.reset();
-                zkm_prof_scope st2(c, "stage/compute auxiliary polynomials commitment");  // :511-522
-                zkm_batch_build(ab, d_all, true);
-            } else {
-                zkm_prof_scope st2(c, "stage/compute auxiliary polynomials commitment");
-                zkm_batch_build(ab, aux, true);
+    const size_t C4 = y.C * 4;
+    for (size_t sg = 0; sg < nseg; sg++) {
+        zkm_challenger_compact(chs[sg], proofs[sg] + y.o_init);  // :466
+        memcpy(proofs[sg] + y.o_caps, tb->cap.data() + sg * C4, C4 * 8);
+    }
+    const zkm_batch *abp = aux_batch_in, *qbp = quot_batch_in;
+    if (aux_given) {
+        if (abp->ncols != A || abp->log_n != log_n || abp->rate_bits != cfg->rate_bits || abp->cap_height != cfg->cap_height || abp->nseg != nseg)
+            throw std::runtime_error("auxiliary commitment does not match the table shape / config");
+    } else if (!openings_only) {
+        // auxiliary commitment :511-522
+        ab.reset(new zkm_batch());
+        ab->ctx = c; ab->ncols = A; ab->log_n = log_n; ab->rate_bits = cfg->rate_bits; ab->cap_height = cfg->cap_height;
+        if (NL) {
+            // "compute lookup helper columns" :475-493, then the CTL columns behind them
+            auto st = std::make_unique<zkm_prof_scope>(c, "stage/compute lookup helper columns");
+            gl_t* d_all = scratch.alloc<gl_t>(A * n * sizeof(gl_t));
+            const gl_t* d_trace = trace;
+            if (!zkm_is_device_ptr(trace)) {
+                gl_t* d = scratch.alloc<gl_t>(W * n * sizeof(gl_t));
+                c->upload(d, trace, W * n * sizeof(gl_t));
+                zkm_launch_canon(c, d, W * n);   // (host words may be any representative; the lookup kernels want canonical ones)
+                d_trace = d;
             }
-            abp = ab;
-        }
-        if (!openings_only) {
-            std::vector<gl_t> alphas(nseg * cfg->num_challenges);
-            for (size_t sg = 0; sg < nseg; sg++) {
-                uint64_t* caps = proofs[sg] + y.o_caps;
-                memcpy(caps + C4, abp->cap.data() + sg * C4, C4 * 8);
-                zkm_challenger_observe(chs[sg], caps + C4, C4);  // :525
-                for (unsigned i = 0; i < cfg->num_challenges; i++) alphas[sg * cfg->num_challenges + i] = zkm_challenger_get(chs[sg]);  // :527
-            }
-
-            // quotient :543-587
-            gl_t* d_quot = (gl_t*)c->alloc(nseg * cfg->num_challenges * 2 * n * sizeof(gl_t));
-            scratch.push_back(d_quot);
-            {
-                zkm_prof_scope st(c, "stage/compute quotient polys");  // :543-559
-                quotient_device(c, table_id, tb, abp, own, lookup_challenges, alphas.data(), cfg->num_challenges, d_quot);
-            }
-            qb = new zkm_batch();
-            qb->ctx = c; qb->ncols = y.Q; qb->nseg = nseg; qb->log_n = log_n; qb->rate_bits = cfg->rate_bits; qb->cap_height = cfg->cap_height;
-            {
-                zkm_prof_scope st(c, "stage/compute quotient commitment");  // :576-587
-                zkm_batch_build(qb, d_quot, false);  // chunks [q0_lo, q0_hi, q1_lo, q1_hi] == d_quot viewed as Q columns of n, proof after proof
-            }
-            for (size_t sg = 0; sg < nseg; sg++) {
-                uint64_t* caps = proofs[sg] + y.o_caps;
-                memcpy(caps + 2 * C4, qb->cap.data() + sg * C4, C4 * 8);
-                zkm_challenger_observe(chs[sg], caps + 2 * C4, C4);  // :589
-            }
-            qbp = qb;
+            zkm_table_lookup_columns_device(c, table_id, lookup_challenges, cfg->num_challenges, d_trace, n, d_all);
+            ZKM_HIP_CHECK(hipMemcpyAsync(d_all + NL * n, aux, A_ctl * n * sizeof(gl_t), hipMemcpyDefault, c->stream));
+            st.reset();
+            zkm_prof_scope st2(c, "stage/compute auxiliary polynomials commitment");  // :511-522
+            zkm_batch_build(ab.get(), d_all, true);
         } else {
-            for (const zkm_batch* b : {abp, qbp})
-                if (!b || b->log_n != log_n || b->rate_bits != cfg->rate_bits || b->cap_height != cfg->cap_height || b->nseg != nseg)
-                    throw std::runtime_error("zkm_prove_openings: commitments do not match the table shape / config");
-            if (abp->ncols != A || qbp->ncols != y.Q) throw std::runtime_error("zkm_prove_openings: unexpected number of polynomials");
-            for (size_t sg = 0; sg < nseg; sg++) {
-                uint64_t* caps = proofs[sg] + y.o_caps;
-                memcpy(caps + C4, abp->cap.data() + sg * C4, C4 * 8);
-                memcpy(caps + 2 * C4, qbp->cap.data() + sg * C4, C4 * 8);
-            }
+            zkm_prof_scope st2(c, "stage/compute auxiliary polynomials commitment");
+            zkm_batch_build(ab.get(), aux, true);
         }
-
-        std::vector<gl2_t> zeta(nseg), zeta_next(nseg);
-        gl_t g = gl_root_of_unity(log_n);
+        abp = ab.get();
+    }
+    if (!openings_only) {
+        std::vector<gl_t> alphas(nseg * cfg->num_challenges);
         for (size_t sg = 0; sg < nseg; sg++) {
-            zeta[sg] = challenger_get_ext(chs[sg]);  // :591
-            if (gl2_eq(gl2_exp_pow2(zeta[sg], log_n), gl2_t{1, 0})) throw std::runtime_error("Opening point is in the subgroup.");  // :596-599
-            zeta_next[sg] = gl2_scalar_mul(zeta[sg], g);
+            uint64_t* caps = proofs[sg] + y.o_caps;
+            memcpy(caps + C4, abp->cap.data() + sg * C4, C4 * 8);
+            zkm_challenger_observe(chs[sg], caps + C4, C4);  // :525
+            for (unsigned i = 0; i < cfg->num_challenges; i++) alphas[sg * cfg->num_challenges + i] = zkm_challenger_get(chs[sg]);  // :527
         }
 
-        // openings proof.rs:299-334
+        // quotient :543-587
+        gl_t* d_quot = scratch.alloc<gl_t>(nseg * cfg->num_challenges * 2 * n * sizeof(gl_t));
         {
-            zkm_prof_scope st(c, "stage/openings (StarkOpeningSet::new)");  // proof.rs:299-334, between two timed! scopes in the reference
-            auto ev = eval_batches(c, {tb, abp, qbp}, zeta.data(), zeta_next.data());
-            for (size_t sg = 0; sg < nseg; sg++) {
-                uint64_t* op = proofs[sg] + y.o_open;
-                uint64_t *o_local = op, *o_next = op + 2 * W, *o_aux = op + 4 * W, *o_auxn = o_aux + 2 * A, *o_ctl = o_auxn + 2 * A, *o_quot = o_ctl + Z;
-                const auto &tv = ev[sg][0], &av = ev[sg][1], &qv = ev[sg][2];
-                for (size_t i = 0; i < W; i++) {
-                    o_local[2 * i] = tv[i].at_z0.c0; o_local[2 * i + 1] = tv[i].at_z0.c1;
-                    o_next[2 * i] = tv[i].at_z1.c0; o_next[2 * i + 1] = tv[i].at_z1.c1;
-                }
-                for (size_t i = 0; i < A; i++) {
-                    o_aux[2 * i] = av[i].at_z0.c0; o_aux[2 * i + 1] = av[i].at_z0.c1;
-                    o_auxn[2 * i] = av[i].at_z1.c0; o_auxn[2 * i + 1] = av[i].at_z1.c1;
-                    if (i >= total_helpers) o_ctl[i - total_helpers] = av[i].at_one;
-                }
-                for (size_t i = 0; i < y.Q; i++) { o_quot[2 * i] = qv[i].at_z0.c0; o_quot[2 * i + 1] = qv[i].at_z0.c1; }
-            }
+            zkm_prof_scope st(c, "stage/compute quotient polys");  // :543-559
+            quotient_device(c, table_id, tb, abp, own, lookup_challenges, alphas.data(), cfg->num_challenges, d_quot);
         }
-        // ---- prove_openings (App. A.8)
-        zkm_prof_scope st_fri(c, "stage/compute openings proof");  // prover.rs:618-628
-        const size_t np0 = W + A + y.Q, np1 = W + A, np2 = Z, apow_seg = 2 * (np0 + 1);
-        std::vector<gl_t> apow(nseg * apow_seg);
+        qb.reset(new zkm_batch());
+        qb->ctx = c; qb->ncols = y.Q; qb->nseg = nseg; qb->log_n = log_n; qb->rate_bits = cfg->rate_bits; qb->cap_height = cfg->cap_height;
+        {
+            zkm_prof_scope st(c, "stage/compute quotient commitment");  // :576-587
+            zkm_batch_build(qb.get(), d_quot, false);  // chunks [q0_lo, q0_hi, q1_lo, q1_hi] == d_quot viewed as Q columns of n, proof after proof
+        }
         for (size_t sg = 0; sg < nseg; sg++) {
-            zkm_challenger* ch = chs[sg];
+            uint64_t* caps = proofs[sg] + y.o_caps;
+            memcpy(caps + 2 * C4, qb->cap.data() + sg * C4, C4 * 8);
+            zkm_challenger_observe(chs[sg], caps + 2 * C4, C4);  // :589
+        }
+        qbp = qb.get();
+    } else {
+        for (const zkm_batch* b : {abp, qbp})
+            if (!b || b->log_n != log_n || b->rate_bits != cfg->rate_bits || b->cap_height != cfg->cap_height || b->nseg != nseg)
+                throw std::runtime_error("zkm_prove_openings: commitments do not match the table shape / config");
+        if (abp->ncols != A || qbp->ncols != y.Q) throw std::runtime_error("zkm_prove_openings: unexpected number of polynomials");
+        for (size_t sg = 0; sg < nseg; sg++) {
+            uint64_t* caps = proofs[sg] + y.o_caps;
+            memcpy(caps + C4, abp->cap.data() + sg * C4, C4 * 8);
+            memcpy(caps + 2 * C4, qbp->cap.data() + sg * C4, C4 * 8);
+        }
+    }
+
+    std::vector<gl2_t> zeta(nseg), zeta_next(nseg);
+    gl_t g = gl_root_of_unity(log_n);
+    for (size_t sg = 0; sg < nseg; sg++) {
+        zeta[sg] = challenger_get_ext(chs[sg]);  // :591
+        if (gl2_eq(gl2_exp_pow2(zeta[sg], log_n), gl2_t{1, 0})) throw std::runtime_error("Opening point is in the subgroup.");  // :596-599
+        zeta_next[sg] = gl2_scalar_mul(zeta[sg], g);
+    }
+
+    // openings proof.rs:299-334
+    {
+        zkm_prof_scope st(c, "stage/openings (StarkOpeningSet::new)");  // proof.rs:299-334, between two timed! scopes in the reference
+        auto ev = eval_batches(c, {tb, abp, qbp}, zeta.data(), zeta_next.data());
+        for (size_t sg = 0; sg < nseg; sg++) {
             uint64_t* op = proofs[sg] + y.o_open;
             uint64_t *o_local = op, *o_next = op + 2 * W, *o_aux = op + 4 * W, *o_auxn = o_aux + 2 * A, *o_ctl = o_auxn + 2 * A, *o_quot = o_ctl + Z;
-            // observe_openings(to_fri_openings) proof.rs:336-367
-            zkm_challenger_observe(ch, o_local, 2 * W);
-            zkm_challenger_observe(ch, o_aux, 2 * A);
-            zkm_challenger_observe(ch, o_quot, 2 * y.Q);
-            zkm_challenger_observe(ch, o_next, 2 * W);
-            zkm_challenger_observe(ch, o_auxn, 2 * A);
-            for (size_t i = 0; i < Z; i++) { uint64_t e[2] = {o_ctl[i], 0}; zkm_challenger_observe(ch, e, 2); }
-            gl2_t alpha = challenger_get_ext(ch);
-            gl2_t p{1, 0};
-            gl_t* ap = apow.data() + sg * apow_seg;
-            for (size_t j = 0; j <= np0; j++) { ap[2 * j] = p.c0; ap[2 * j + 1] = p.c1; p = gl2_mul(p, alpha); }
-        }
-        gl_t* d_apow = (gl_t*)c->alloc(apow.size() * sizeof(gl_t));
-        scratch.push_back(d_apow);
-        c->upload(d_apow, apow.data(), apow.size() * sizeof(gl_t));
-        gl_t* d_comp = (gl_t*)c->alloc(nseg * 6 * n * sizeof(gl_t));
-        scratch.push_back(d_comp);
-        if (tb->coeff_s1 != abp->coeff_s1 || tb->coeff_s1 != qbp->coeff_s1) throw std::runtime_error("internal: coefficient layouts of the three oracles differ");
-        {
-            zkm_prof_scope ps(c, "fri_combine");
-            const size_t npoly = W + A + y.Q;
-            const unsigned z = (unsigned)nseg;
-            // slices of >= 32 polynomials while the launch stays below ~2^17 threads (two waves per SIMD)
-            size_t slices = npoly / 32 < 1 ? 1 : npoly / 32;
-            while (slices > 1 && slices * n * nseg > ((size_t)1 << 17)) slices >>= 1;
-            if (slices >= 4) {
-                const size_t per = (npoly + slices - 1) / slices;
-                slices = (npoly + per - 1) / per;
-                gl_t* d_part = (gl_t*)c->alloc(nseg * slices * 6 * n * sizeof(gl_t));
-                scratch.push_back(d_part);
-                hipLaunchKernelGGL(k_fri_combine_slice, dim3((n + 255) / 256, (unsigned)slices, z), dim3(256), 0, c->stream, tb->coeffs, W, abp->coeffs, A,
-                                   qbp->coeffs, y.Q, total_helpers, d_apow, n, per, d_part, apow_seg);
-                hipLaunchKernelGGL(k_fri_combine_sum, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, d_part, (unsigned)slices, n, d_comp);
-            } else {
-                hipLaunchKernelGGL(k_fri_combine, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, tb->coeffs, W, abp->coeffs, A, qbp->coeffs, y.Q,
-                                   total_helpers, d_apow, n, d_comp, apow_seg);
+            const auto &tv = ev[sg][0], &av = ev[sg][1], &qv = ev[sg][2];
+            for (size_t i = 0; i < W; i++) {
+                o_local[2 * i] = tv[i].at_z0.c0; o_local[2 * i + 1] = tv[i].at_z0.c1;
+                o_next[2 * i] = tv[i].at_z1.c0; o_next[2 * i + 1] = tv[i].at_z1.c1;
             }
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        if (tb->coeff_s1) {
-            // the combination is position-wise, so the six composite arrays come out in the batches' coefficient layout; the division by
-            // (X - point) walks exponents in order
-            gl_t* d_nat = (gl_t*)c->alloc(nseg * 6 * n * sizeof(gl_t));
-            scratch.push_back(d_nat);
-            zkm_coeff_layout_convert(c, d_comp, n, d_nat, n, 6 * nseg, log_n, /*to_natural=*/true);
-            d_comp = d_nat;
-        }
-        // divide by (X - point), accumulate, commit phase, proof of work, query rounds: shared with zkm_fri_prove
-        {
-            std::vector<std::vector<fri_composite>> comps(nseg);
-            std::vector<uint64_t*> caps_o(nseg), final_o(nseg), pow_o(nseg), queries_o(nseg);
-            for (size_t sg = 0; sg < nseg; sg++) {
-                const gl_t* ap = apow.data() + sg * apow_seg;
-                comps[sg] = {{d_comp, d_comp + n, zeta[sg], gl2_t{ap[2 * np0], ap[2 * np0 + 1]}},
-                             {d_comp + 2 * n, d_comp + 3 * n, zeta_next[sg], gl2_t{ap[2 * np1], ap[2 * np1 + 1]}},
-                             {d_comp + 4 * n, d_comp + 5 * n, gl2_t{1, 0}, gl2_t{ap[2 * np2], ap[2 * np2 + 1]}}};
-                caps_o[sg] = proofs[sg] + y.o_fri_caps; final_o[sg] = proofs[sg] + y.o_final; pow_o[sg] = proofs[sg] + y.o_pow;
-                queries_o[sg] = proofs[sg] + y.o_queries;
+            for (size_t i = 0; i < A; i++) {
+                o_aux[2 * i] = av[i].at_z0.c0; o_aux[2 * i + 1] = av[i].at_z0.c1;
+                o_auxn[2 * i] = av[i].at_z1.c0; o_auxn[2 * i + 1] = av[i].at_z1.c1;
+                if (i >= total_helpers) o_ctl[i - total_helpers] = av[i].at_one;
             }
-            const zkm_batch* orc[3] = {tb, abp, qbp};
-            fri_finish(c, cfg, log_n, comps, 6 * n, orc, 3, chs, y.L, y.F, y.nq, y.query_words, caps_o, final_o, pow_o, queries_o);
+            for (size_t i = 0; i < y.Q; i++) { o_quot[2 * i] = qv[i].at_z0.c0; o_quot[2 * i + 1] = qv[i].at_z0.c1; }
         }
-    } catch (...) {
-        cleanup();
-        throw;
     }
-    cleanup();
+    // ---- prove_openings (App. A.8)
+    zkm_prof_scope st_fri(c, "stage/compute openings proof");  // prover.rs:618-628
+    const size_t np0 = W + A + y.Q, np1 = W + A, np2 = Z, apow_seg = 2 * (np0 + 1);
+    std::vector<gl_t> apow(nseg * apow_seg);
+    for (size_t sg = 0; sg < nseg; sg++) {
+        zkm_challenger* ch = chs[sg];
+        uint64_t* op = proofs[sg] + y.o_open;
+        uint64_t *o_local = op, *o_next = op + 2 * W, *o_aux = op + 4 * W, *o_auxn = o_aux + 2 * A, *o_ctl = o_auxn + 2 * A, *o_quot = o_ctl + Z;
+        // observe_openings(to_fri_openings) proof.rs:336-367
+        zkm_challenger_observe(ch, o_local, 2 * W);
+        zkm_challenger_observe(ch, o_aux, 2 * A);
+        zkm_challenger_observe(ch, o_quot, 2 * y.Q);
+        zkm_challenger_observe(ch, o_next, 2 * W);
+        zkm_challenger_observe(ch, o_auxn, 2 * A);
+        for (size_t i = 0; i < Z; i++) { uint64_t e[2] = {o_ctl[i], 0}; zkm_challenger_observe(ch, e, 2); }
+        gl2_t alpha = challenger_get_ext(ch);
+        gl2_t p{1, 0};
+        gl_t* ap = apow.data() + sg * apow_seg;
+        for (size_t j = 0; j <= np0; j++) { ap[2 * j] = p.c0; ap[2 * j + 1] = p.c1; p = gl2_mul(p, alpha); }
+    }
+    gl_t* d_apow = scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
+    c->upload(d_apow, apow.data(), apow.size() * sizeof(gl_t));
+    gl_t* d_comp = scratch.alloc<gl_t>(nseg * 6 * n * sizeof(gl_t));
+    if (tb->coeff_s1 != abp->coeff_s1 || tb->coeff_s1 != qbp->coeff_s1) throw std::runtime_error("internal: coefficient layouts of the three oracles differ");
+    {
+        zkm_prof_scope ps(c, "fri_combine");
+        const size_t npoly = W + A + y.Q;
+        const unsigned z = (unsigned)nseg;
+        // slices of >= 32 polynomials while the launch stays below ~2^17 threads (two waves per SIMD)
+        size_t slices = npoly / 32 < 1 ? 1 : npoly / 32;
+        while (slices > 1 && slices * n * nseg > ((size_t)1 << 17)) slices >>= 1;
+        if (slices >= 4) {
+            const size_t per = (npoly + slices - 1) / slices;
+            slices = (npoly + per - 1) / per;
+            gl_t* d_part = scratch.alloc<gl_t>(nseg * slices * 6 * n * sizeof(gl_t));
+            hipLaunchKernelGGL(k_fri_combine_slice, dim3((n + 255) / 256, (unsigned)slices, z), dim3(256), 0, c->stream, tb->coeffs, W, abp->coeffs, A,
+                               qbp->coeffs, y.Q, total_helpers, d_apow, n, per, d_part, apow_seg);
+            hipLaunchKernelGGL(k_fri_combine_sum, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, d_part, (unsigned)slices, n, d_comp);
+        } else {
+            hipLaunchKernelGGL(k_fri_combine, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, tb->coeffs, W, abp->coeffs, A, qbp->coeffs, y.Q,
+                               total_helpers, d_apow, n, d_comp, apow_seg);
+        }
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+    if (tb->coeff_s1) {
+        // the combination is position-wise, so the six composite arrays come out in the batches' coefficient layout; the division by
+        // (X - point) walks exponents in order
+        gl_t* d_nat = scratch.alloc<gl_t>(nseg * 6 * n * sizeof(gl_t));
+        zkm_coeff_layout_convert(c, d_comp, n, d_nat, n, 6 * nseg, log_n, /*to_natural=*/true);
+        d_comp = d_nat;
+    }
+    // divide by (X - point), accumulate, commit phase, proof of work, query rounds: shared with zkm_fri_prove
+    {
+        std::vector<std::vector<fri_composite>> comps(nseg);
+        std::vector<uint64_t*> caps_o(nseg), final_o(nseg), pow_o(nseg), queries_o(nseg);
+        for (size_t sg = 0; sg < nseg; sg++) {
+            const gl_t* ap = apow.data() + sg * apow_seg;
+            comps[sg] = {{d_comp, d_comp + n, zeta[sg], gl2_t{ap[2 * np0], ap[2 * np0 + 1]}},
+                         {d_comp + 2 * n, d_comp + 3 * n, zeta_next[sg], gl2_t{ap[2 * np1], ap[2 * np1 + 1]}},
+                         {d_comp + 4 * n, d_comp + 5 * n, gl2_t{1, 0}, gl2_t{ap[2 * np2], ap[2 * np2 + 1]}}};
+            caps_o[sg] = proofs[sg] + y.o_fri_caps; final_o[sg] = proofs[sg] + y.o_final; pow_o[sg] = proofs[sg] + y.o_pow;
+            queries_o[sg] = proofs[sg] + y.o_queries;
+        }
+        const zkm_batch* orc[3] = {tb, abp, qbp};
+        fri_finish(c, cfg, log_n, comps, 6 * n, orc, 3, chs, y.L, y.F, y.nq, y.query_words, caps_o, final_o, pow_o, queries_o);
+    }
 }
 
 // prove_single_table on existing (stacked) trace AND auxiliary commitments (zkm_prove_with_traces builds the auxiliary commitments of all
@@ -1658,13 +1621,8 @@ void zkm_prove_single_table_aux(zkm_ctx* c, int table_id, const zkm_stark_config
 }
 
 // ------------------------------------------------------------------ C ABI
-static int fail(char** err, const std::string& msg) {
-    if (err) {
-        *err = (char*)malloc(msg.size() + 1);
-        if (*err) memcpy(*err, msg.c_str(), msg.size() + 1);
-    }
-    return 1;
-}
+// (a prove entry point advances the transcript on a copy and hands it back only when the whole proof exists: a failed call leaves the
+// caller's challenger where it was -- the reference's prove_openings cannot fail half way; a C ABI call can)
 
 // ---- PolynomialBatch::prove_openings for an arbitrary FriInstanceInfo (plonky2 fri/oracle.rs; instance of the STARKs: stark.rs:91-148)
 // composite of one batch: sum_j alpha^j p_j, polynomials named by pointer (any oracle, any column)
@@ -1718,25 +1676,17 @@ void zkm_launch_mul_selftest_branchfree(zkm_ctx* c, const uint64_t* a, const uin
 extern "C" {
 
 size_t zkm_fri_proof_words(const zkm_stark_config* cfg, unsigned log_n, const size_t* oracle_cols, size_t noracles) {
-    try {
-        fri_blob_layout y;
-        fri_blob_make(y, cfg, log_n, oracle_cols, noracles);
-        return y.total;
-    } catch (...) {
-        return 0;
-    }
+    fri_blob_layout y;
+    return zkm_api("zkm_fri_proof_words", nullptr, [&] { fri_blob_make(y, cfg, log_n, oracle_cols, noracles); }) ? 0 : y.total;
 }
 
 int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles, const zkm_fri_batch* batches,
                   size_t nbatches, zkm_challenger* ch_io, uint64_t* proof, char** err) {
-    std::vector<void*> scratch;
-    if (!c || !cfg || !oracles || !batches || !nbatches || !ch_io || !proof) return fail(err, "zkm_fri_prove: null argument");
-    // The transcript is advanced on a copy and handed back only when the whole proof exists: a failed call leaves the caller's
-    // challenger where it was (the reference's prove_openings cannot fail half way; a C ABI call can).
-    zkm_challenger local = *ch_io;
-    zkm_challenger* const ch = &local;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_fri_prove", c, err, [&] {
+        if (!cfg || !oracles || !batches || !nbatches || !ch_io || !proof) throw std::runtime_error("zkm_fri_prove: null argument");
+        zkm_challenger local = *ch_io;
+        zkm_challenger* const ch = &local;
+        zkm_scratch_list scratch(c);
         if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error("zkm_fri_prove: 1..8 oracles");
         const unsigned log_n = oracles[0]->log_n;
         size_t cols[ZKM_FRI_MAX_ORACLES];
@@ -1769,19 +1719,16 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
             gl2_t pw{1, 0};
             for (size_t j = 0; j <= maxp; j++) { apow[2 * j] = pw.c0; apow[2 * j + 1] = pw.c1; pw = gl2_mul(pw, alpha); }
         }
-        gl_t* d_apow = (gl_t*)c->alloc(apow.size() * sizeof(gl_t));
-        scratch.push_back(d_apow);
+        gl_t* d_apow = scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
         c->upload(d_apow, apow.data(), apow.size() * sizeof(gl_t));
-        gl_t* d_comp = (gl_t*)c->alloc(2 * nbatches * n * sizeof(gl_t));
-        scratch.push_back(d_comp);
+        gl_t* d_comp = scratch.alloc<gl_t>(2 * nbatches * n * sizeof(gl_t));
         std::vector<const gl_t*> ptrs;
         std::vector<size_t> first(nbatches);
         for (size_t b = 0; b < nbatches; b++) {
             first[b] = ptrs.size();
             for (size_t j = 0; j < batches[b].npolys; j++) ptrs.push_back(oracles[batches[b].polys[j].oracle]->coeffs + (size_t)batches[b].polys[j].poly * n);
         }
-        const gl_t** d_ptrs = (const gl_t**)c->alloc(ptrs.size() * sizeof(gl_t*));
-        scratch.push_back((void*)d_ptrs);
+        const gl_t** d_ptrs = scratch.alloc<const gl_t*>(ptrs.size() * sizeof(gl_t*));
         c->upload((void*)d_ptrs, ptrs.data(), ptrs.size() * sizeof(gl_t*));
         std::vector<std::vector<fri_composite>> comps_v(1);
         std::vector<fri_composite>& comps = comps_v[0];
@@ -1795,8 +1742,7 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
                              gl2_t{apow[2 * np], apow[2 * np + 1]}});
         }
         if (oracles[0]->coeff_s1) {   // (the layout is a function of the height: the same for every oracle; see prove_single_table)
-            gl_t* d_nat = (gl_t*)c->alloc(2 * nbatches * n * sizeof(gl_t));
-            scratch.push_back(d_nat);
+            gl_t* d_nat = scratch.alloc<gl_t>(2 * nbatches * n * sizeof(gl_t));
             zkm_coeff_layout_convert(c, d_comp, n, d_nat, n, 2 * nbatches, log_n, /*to_natural=*/true);
             for (auto& k : comps) { k.c0 = d_nat + (k.c0 - d_comp); k.c1 = d_nat + (k.c1 - d_comp); }
         }
@@ -1805,18 +1751,8 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
             if (oracles[k]->nseg != 1) throw std::runtime_error("zkm_fri_prove: stacked batches are internal");
         fri_finish(c, cfg, log_n, comps_v, 0, oracles, noracles, {ch}, y.L, y.F, cfg->num_queries, y.query_words, {proof + y.o_caps}, {proof + y.o_final},
                    {proof + y.o_pow}, {proof + y.o_queries});
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* q : scratch) c->release(q);
-        return fail(err, e.what());
-    } catch (...) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* q : scratch) c->release(q);
-        return fail(err, "zkm_fri_prove: unknown error");
-    }
-    for (void* q : scratch) c->release(q);
-    *ch_io = local;
-    return 0;
+        *ch_io = local;
+    });
 }
 
 }  // extern "C"
@@ -1824,13 +1760,8 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
 extern "C" {
 
 size_t zkm_proof_words(const zkm_stark_config* cfg, unsigned log_n, size_t ncols, size_t naux, size_t nctl_zs) {
-    try {  // 0 = unsupported configuration (the prove entry points report which field)
-        proof_layout y;
-        make_layout(y, cfg, log_n, ncols, naux, nctl_zs);
-        return y.total;
-    } catch (...) {
-        return 0;
-    }
+    proof_layout y;   // (0 = unsupported configuration: the prove entry points report which field)
+    return zkm_api("zkm_proof_words", nullptr, [&] { make_layout(y, cfg, log_n, ncols, naux, nctl_zs); }) ? 0 : y.total;
 }
 
 // CtlZData of the benchmark's fake CTL shape: helper columns, no column sets (poseidon_stark.rs:786-799)
@@ -1847,52 +1778,36 @@ int zkm_prove_single_table_ctl(zkm_ctx* c, int table_id, const zkm_stark_config*
                                const zkm_batch* trace_batch, const uint64_t* aux, size_t naux, const zkm_ctl_table* table,
                                const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs, const uint64_t* lookup_challenges,
                                zkm_challenger* challenger, uint64_t* proof_out, char** err) {
-    if (!c || !cfg || !challenger || !proof_out) return fail(err, "zkm_prove_single_table: null argument");
-    zkm_challenger local = *challenger;   // (handed back on success only: a failed call leaves the caller's transcript untouched)
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_prove_single_table", c, err, [&] {
+        if (!cfg || !challenger || !proof_out) throw std::runtime_error("zkm_prove_single_table: null argument");
         if (!trace && !trace_batch) throw std::runtime_error("zkm_prove_single_table: need trace values or a trace commitment");
+        zkm_challenger local = *challenger;
         prove_single_table(c, table_id, cfg, trace, ncols, log_n, trace_batch, aux, naux, table, zs, colset_ids, nzs, lookup_challenges,
                            {&local}, {proof_out});
-    } catch (const std::exception& e) {
-        return fail(err, e.what());
-    } catch (...) {
-        return fail(err, "zkm_prove_single_table: unknown error");
-    }
-    *challenger = local;
-    return 0;
+        *challenger = local;
+    });
 }
 
 int zkm_prove_openings(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* trace_batch, const zkm_batch* aux_batch,
                        const zkm_batch* quot_batch, size_t nctl_zs, zkm_challenger* challenger, uint64_t* proof_out, char** err) {
-    if (!c || !cfg || !challenger || !proof_out) return fail(err, "zkm_prove_openings: null argument");
-    zkm_challenger local = *challenger;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_prove_openings", c, err, [&] {
+        if (!cfg || !challenger || !proof_out) throw std::runtime_error("zkm_prove_openings: null argument");
         if (!trace_batch || !aux_batch || !quot_batch) throw std::runtime_error("zkm_prove_openings: three commitments are required");
+        zkm_challenger local = *challenger;
         prove_single_table(c, -1, cfg, nullptr, trace_batch->ncols, trace_batch->log_n, trace_batch, nullptr, aux_batch->ncols, nullptr,
                            nullptr, nullptr, nctl_zs, nullptr, {&local}, {proof_out}, aux_batch, quot_batch);
-    } catch (const std::exception& e) {
-        return fail(err, e.what());
-    } catch (...) {
-        return fail(err, "zkm_prove_openings: unknown error");
-    }
-    *challenger = local;
-    return 0;
+        *challenger = local;
+    });
 }
 
 int zkm_prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, const uint64_t* trace, size_t ncols, unsigned log_n,
                            const zkm_batch* trace_batch, const uint64_t* aux, size_t naux, const uint32_t* num_helpers, size_t nctl_zs,
                            zkm_challenger* challenger, uint64_t* proof_out, char** err) {
-    try {
+    return zkm_api("zkm_prove_single_table", err, [&] {
         auto zs = fake_zs(num_helpers, nctl_zs);
         return zkm_prove_single_table_ctl(c, table_id, cfg, trace, ncols, log_n, trace_batch, aux, naux, nullptr, zs.data(), nullptr,
                                           nctl_zs, nullptr, challenger, proof_out, err);
-    } catch (const std::exception& e) {
-        return fail(err, e.what());
-    } catch (...) {
-        return fail(err, "zkm_prove_single_table: unknown error");
-    }
+    });
 }
 
 // K proofs of the same table at the same height in LOCK-STEP (the benchmark shape: CtlData given as auxiliary columns, no column sets):
@@ -1901,18 +1816,16 @@ int zkm_prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config* cfg
 int zkm_prove_single_tables(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, size_t nproofs, const uint64_t* const* traces, size_t ncols,
                             unsigned log_n, const uint64_t* const* aux, size_t naux, const uint32_t* num_helpers, size_t nctl_zs,
                             zkm_challenger* const* challengers, uint64_t* const* proofs_out, char** err) {
-    if (!c || !cfg || !traces || !aux || !challengers || !proofs_out) return fail(err, "zkm_prove_single_tables: null argument");
-    if (nproofs == 0) return 0;
-    zkm_batch *tb = nullptr, *ab = nullptr;
-    std::vector<zkm_challenger> local(nproofs);
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_prove_single_tables", c, err, [&] {
+        if (!cfg || !traces || !aux || !challengers || !proofs_out) throw std::runtime_error("zkm_prove_single_tables: null argument");
+        if (nproofs == 0) return;
         if (nproofs > ZKM_MAX_SEG) throw std::runtime_error("zkm_prove_single_tables: at most 32 proofs per call");
         validate_config(cfg, log_n);
         if (zkm_num_lookup_columns(table_id, cfg)) throw std::runtime_error("zkm_prove_single_tables: a table with lookups of its own needs zkm_prove_segments");
         auto zs1 = fake_zs(num_helpers, nctl_zs);
         std::vector<zkm_ctl_z> zs;
         for (size_t k = 0; k < nproofs; k++) zs.insert(zs.end(), zs1.begin(), zs1.end());
+        std::vector<zkm_challenger> local(nproofs);
         std::vector<zkm_challenger*> chs(nproofs);
         std::vector<uint64_t*> proofs(nproofs);
         for (size_t k = 0; k < nproofs; k++) {
@@ -1922,17 +1835,13 @@ int zkm_prove_single_tables(zkm_ctx* c, int table_id, const zkm_stark_config* cf
             proofs[k] = proofs_out[k];
         }
         auto stacked = [&](size_t cols, const uint64_t* const* srcs) {
-            zkm_batch* b = new zkm_batch();
+            zkm_batch_ptr b(new zkm_batch());
             b->ctx = c; b->ncols = cols; b->nseg = nproofs; b->log_n = log_n; b->rate_bits = cfg->rate_bits; b->cap_height = cfg->cap_height;
-            try {
-                if (nproofs == 1) zkm_batch_build(b, srcs[0], true);
-                else zkm_batch_build(b, nullptr, true, nullptr, nullptr, srcs);   // (device matrices are transformed where they lie)
-            } catch (...) {
-                zkm_batch_free(b);
-                throw;
-            }
+            if (nproofs == 1) zkm_batch_build(b.get(), srcs[0], true);
+            else zkm_batch_build(b.get(), nullptr, true, nullptr, nullptr, srcs);   // (device matrices are transformed where they lie)
             return b;
         };
+        zkm_batch_ptr tb, ab;
         {
             zkm_prof_scope st(c, "stage/compute trace commitment");
             tb = stacked(ncols, traces);
@@ -1941,27 +1850,16 @@ int zkm_prove_single_tables(zkm_ctx* c, int table_id, const zkm_stark_config* cf
             zkm_prof_scope st(c, "stage/compute auxiliary polynomials commitment");
             ab = stacked(naux, aux);
         }
-        prove_single_table(c, table_id, cfg, nullptr, ncols, log_n, tb, nullptr, naux, nullptr, zs.data(), nullptr, nctl_zs, nullptr, chs, proofs, ab,
-                           nullptr);
-    } catch (const std::exception& e) {
-        zkm_batch_free(tb);
-        zkm_batch_free(ab);
-        return fail(err, e.what());
-    } catch (...) {
-        zkm_batch_free(tb);
-        zkm_batch_free(ab);
-        return fail(err, "zkm_prove_single_tables: unknown error");
-    }
-    zkm_batch_free(tb);
-    zkm_batch_free(ab);
-    for (size_t k = 0; k < nproofs; k++) *challengers[k] = local[k];
-    return 0;
+        prove_single_table(c, table_id, cfg, nullptr, ncols, log_n, tb.get(), nullptr, naux, nullptr, zs.data(), nullptr, nctl_zs, nullptr, chs, proofs,
+                           ab.get(), nullptr);
+        for (size_t k = 0; k < nproofs; k++) *challengers[k] = local[k];
+    });
 }
 
 int zkm_quotient(zkm_ctx* c, int table_id, const zkm_batch* trace, const zkm_batch* aux, const uint32_t* num_helpers, size_t nctl_zs,
                  const uint64_t* alphas, size_t nalphas, uint64_t* out_coeffs, char** err) {
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_quotient", c, err, [&] {
+        if (!trace || !aux) throw std::runtime_error("zkm_quotient: null argument");
         auto zs = fake_zs(num_helpers, nctl_zs);
         ctl_dev_owner own;
         own.upload(c, nullptr, zs.data(), nullptr, nctl_zs);
@@ -1973,10 +1871,7 @@ int zkm_quotient(zkm_ctx* c, int table_id, const zkm_batch* trace, const zkm_bat
         if (!dev) {
             c->download(out_coeffs, d, words * 8);
         }
-    } catch (const std::exception& e) {
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 // first row (of n) at which any of the nalphas accumulators is nonzero, into *first (left untouched if none): one pass
@@ -1991,10 +1886,8 @@ __global__ __launch_bounds__(256) void k_first_nonzero_row(const gl_t* __restric
 int zkm_check_constraints(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, const uint64_t* trace, size_t ncols, unsigned log_n,
                           const uint64_t* aux, size_t naux, const zkm_ctl_table* table, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs,
                           const uint64_t* lookup_challenges, const uint64_t* alphas, size_t nalphas, uint64_t* first_failing_row, char** err) {
-    std::vector<void*> tmp;
-    if (!c || !cfg || !trace || !aux || !alphas || !first_failing_row) return fail(err, "zkm_check_constraints: null argument");
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_check_constraints", c, err, [&] {
+        if (!cfg || !trace || !aux || !alphas || !first_failing_row) throw std::runtime_error("zkm_check_constraints: null argument");
         validate_config(cfg, log_n);
         if (table_id < 0 || table_id >= 12) throw std::runtime_error("zkm_check_constraints: unknown table id");
         // a table with lookups of its own (Memory, Arithmetic) takes its challenges from the caller: none given is an error here, not a
@@ -2007,9 +1900,9 @@ int zkm_check_constraints(zkm_ctx* c, int table_id, const zkm_stark_config* cfg,
         // the values stand where the quotient kernels expect an LDE: "batches" of rate 0 over device copies of the caller's columns
         zkm_batch tb, ab;
         tb.ctx = ab.ctx = c; tb.ncols = ncols; ab.ncols = naux; tb.log_n = ab.log_n = log_n; tb.rate_bits = ab.rate_bits = 0;
+        zkm_scratch_list tmp(c);
         auto on_device = [&](const uint64_t* p, size_t words) -> gl_t* {
-            gl_t* d = (gl_t*)c->alloc(words * sizeof(gl_t));
-            tmp.push_back(d);
+            gl_t* d = tmp.alloc<gl_t>(words * sizeof(gl_t));
             ZKM_HIP_CHECK(hipMemcpyAsync(d, p, words * sizeof(gl_t), hipMemcpyDefault, c->stream));
             zkm_launch_canon(c, d, words);
             return d;
@@ -2018,48 +1911,32 @@ int zkm_check_constraints(zkm_ctx* c, int table_id, const zkm_stark_config* cfg,
         ab.lde = on_device(aux, naux * n);
         ctl_dev_owner own;
         own.upload(c, table, zs, colset_ids, nzs, false, ncols);
-        gl_t* d_acc = (gl_t*)c->alloc(nalphas * n * sizeof(gl_t));
-        tmp.push_back(d_acc);
+        gl_t* d_acc = tmp.alloc<gl_t>(nalphas * n * sizeof(gl_t));
         quotient_device(c, table_id, &tb, &ab, own, lookup_challenges, alphas, nalphas, d_acc, /*check=*/true);
-        unsigned long long* d_first = (unsigned long long*)c->alloc(8);
-        tmp.push_back(d_first);
+        unsigned long long* d_first = tmp.alloc<unsigned long long>(8);
         ZKM_HIP_CHECK(hipMemsetAsync(d_first, 0xff, 8, c->stream));
         hipLaunchKernelGGL(k_first_nonzero_row, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_acc, n, (unsigned)nalphas, d_first);
         ZKM_HIP_CHECK(hipGetLastError());
         unsigned long long first = ~0ULL;
         c->download(&first, d_first, 8);
-        for (void* q : tmp) c->release(q);
-        tmp.clear();
         *first_failing_row = first;
         if (first != ~0ULL) {
             static const char* const names[] = {"PoseidonStark", "LogicStark", "KeccakSpongeStark", "KeccakStark", "MemoryStark", "PoseidonSpongeStark",
                                                 "ShaExtendStark", "ShaExtendSpongeStark", "ShaCompressStark", "ShaCompressSpongeStark", "ArithmeticStark",
                                                 "CpuStark"};
-            return fail(err, std::string("Constraint failed in ") + names[table_id] + " (first failing row " + std::to_string(first) + ")");   // prover.rs:903-908
+            throw std::runtime_error(std::string("Constraint failed in ") + names[table_id] + " (first failing row " + std::to_string(first) + ")");   // prover.rs:903-908
         }
-    } catch (const std::exception& e) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* q : tmp) c->release(q);
-        return fail(err, e.what());
-    } catch (...) {
-        (void)hipStreamSynchronize(c->stream);
-        for (void* q : tmp) c->release(q);
-        return fail(err, "zkm_check_constraints: unknown error");
-    }
-    return 0;
+    });
 }
 
 int zkm_eval_openings(zkm_ctx* c, const zkm_batch* b, const uint64_t zeta[2], uint64_t* out, char** err) {
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
+    return zkm_api("zkm_eval_openings", c, err, [&] {
+        if (!b || !zeta || !out) throw std::runtime_error("zkm_eval_openings: null argument");
         gl2_t z{zeta[0], zeta[1]};
         if (b->nseg != 1) throw std::runtime_error("zkm_eval_openings: stacked batches are internal");
         auto v = eval_batches(c, {b}, &z, &z)[0][0];
         for (size_t i = 0; i < b->ncols; i++) { out[2 * i] = v[i].at_z0.c0; out[2 * i + 1] = v[i].at_z0.c1; }
-    } catch (const std::exception& e) {
-        return fail(err, e.what());
-    }
-    return 0;
+    });
 }
 
 }  // extern "C"

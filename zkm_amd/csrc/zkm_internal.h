@@ -6,9 +6,12 @@
 #include <string.h>
 
 #include <atomic>
+#include <exception>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 #include <stdexcept>
 #include <string>
 #include <initializer_list>
@@ -152,14 +155,62 @@ struct zkm_ctx {
 };
 
 
-// RAII owner of one scratch block from the context's allocator (released on every exit path)
-struct zkm_scratch {
+// ---- the C ABI's error boundary (include/zkm_hip.h "Error convention"): the one writer of *err, and the one place an exception becomes
+// a status.  zkm_api runs an entry point's body: 0 when it returns (or the int it returns, for a body that delegates to another entry
+// point), 1 and the message when it throws.  The context form rejects a null context and makes the context's device current.
+inline int zkm_fail(char** err, const char* msg, const char* suffix = "") noexcept {
+    if (err) {
+        const size_t a = strlen(msg), b = strlen(suffix);
+        *err = (char*)malloc(a + b + 1);
+        if (*err) { memcpy(*err, msg, a); memcpy(*err + a, suffix, b + 1); }
+    }
+    return 1;
+}
+template <class F> int zkm_api(const char* what, char** err, F&& body) noexcept {
+    try {
+        if constexpr (std::is_void_v<decltype(body())>) {
+            body();
+            return 0;
+        } else {
+            return body();
+        }
+    } catch (const std::exception& e) {
+        return zkm_fail(err, e.what());
+    } catch (...) {
+        return zkm_fail(err, what, ": unknown error");
+    }
+}
+template <class F> int zkm_api(const char* what, const zkm_ctx* c, char** err, F&& body) noexcept {
+    return zkm_api(what, err, [&] {
+        if (!c) throw std::runtime_error(std::string(what) + ": null argument");
+        ZKM_HIP_CHECK(hipSetDevice(c->device));
+        return body();
+    });
+}
+
+// RAII owner of scratch blocks from the context's allocator, released on every exit path.  Blocks released while an exception unwinds
+// may still be in use by work queued on the context's stream: the owner waits for the stream first (a normal exit adds no wait).
+struct zkm_scratch_list {
     zkm_ctx* c;
+    std::vector<void*> ps;
+    const int unwinding = std::uncaught_exceptions();
+    explicit zkm_scratch_list(zkm_ctx* ctx) : c(ctx) {}
+    zkm_scratch_list(const zkm_scratch_list&) = delete;
+    zkm_scratch_list& operator=(const zkm_scratch_list&) = delete;
+    ~zkm_scratch_list() {
+        if (std::uncaught_exceptions() > unwinding) (void)hipStreamSynchronize(c->stream);
+        for (void* p : ps) c->release(p);
+    }
+    template <class T = void> T* alloc(size_t bytes) {
+        ps.reserve(ps.size() + 1);   // (push_back cannot throw once the block exists)
+        ps.push_back(c->alloc(bytes));
+        return (T*)ps.back();
+    }
+};
+// ... of one block
+struct zkm_scratch : zkm_scratch_list {
     void* p;
-    zkm_scratch(zkm_ctx* ctx, size_t bytes) : c(ctx), p(ctx->alloc(bytes)) {}
-    zkm_scratch(const zkm_scratch&) = delete;
-    zkm_scratch& operator=(const zkm_scratch&) = delete;
-    ~zkm_scratch() { c->release(p); }
+    zkm_scratch(zkm_ctx* ctx, size_t bytes) : zkm_scratch_list(ctx), p(alloc(bytes)) {}
     template <class T> T* as() const { return (T*)p; }
 };
 
@@ -203,6 +254,12 @@ struct zkm_batch {
     unsigned lde_bits() const { return log_n + rate_bits; }
     unsigned top() const { return lde_bits() - cap_height; }
 };
+
+// owner of a batch until it is handed out (zkm_batch_free: waits for the streams, releases the blocks)
+struct zkm_batch_deleter {
+    void operator()(zkm_batch* b) const { zkm_batch_free(b); }
+};
+using zkm_batch_ptr = std::unique_ptr<zkm_batch, zkm_batch_deleter>;
 
 inline bool zkm_is_device_ptr(const void* p) {
     hipPointerAttribute_t a;
