@@ -515,8 +515,11 @@ int zkm_prove_segments_columns(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t
  * being proven -- the witness generator runs ahead of the prover -- stages it instead: zkm_trace_stage[_columns] queues the upload of
  * an ncols x 2^log_n host matrix on the context's two copy streams (alternate pieces of >= 64 MB: 8 columns at 2^20 rows, a short table in one copy) into a block of the context's
  * allocator and RETURNS AT ONCE; zkm_staged_ptr gives the device matrix to pass as `trace` / `traces[k]` of a later prove call ON THE
- * SAME CONTEXT, ordered behind the upload on the context's compute stream (a device-side wait; NULL on a runtime error).  That call
- * runs the device-resident path at full speed while the copy engines bring in the trace after it.
+ * SAME CONTEXT, ordered behind the upload on the context's compute stream (a device-side wait; NULL on a runtime error).  A prove
+ * call orders EVERY stream it uses (the context's compute and copy streams, its commit lanes' compute and copy streams) behind what was
+ * queued on the context's compute stream before the call -- these waits, the canonicalising pass below, anything the caller wrote on
+ * zkm_ctx_stream -- with device-side waits: no stream of the call reads a staged matrix before it has landed.  That call runs the
+ * device-resident path at full speed while the copy engines bring in the trace after it.
  *   canonical   nonzero: the caller vouches that every word is < p; 0: the staged copy is canonicalised once when first consumed
  *   host memory pinned (zkm_host_alloc, or a Vec under zkm_host_register): the copies are asynchronous.  Pageable memory works and
  *               makes zkm_trace_stage itself take the time of the upload (the runtime stages it through its own pinned buffer).

@@ -9,6 +9,7 @@ missing or no GPU is present, every compute entry point raises.
 import ctypes as C
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -288,10 +289,24 @@ class DeviceBuffer:
 
 class StagedTrace:
     """zkm_staged: a host matrix on its way into HBM behind the context's current work (include/zkm_hip.h "staged traces").  Pass it
-    wherever a prove call of the SAME context takes a trace; free() after that call has returned."""
+    wherever a prove call of the SAME context takes a trace; free() after that call has returned.  A handle that is dropped, leaves a
+    `with` block or outlives Context.close() is freed then (free() after close() is a no-op: the context freed it)."""
 
     def __init__(self, ctx, handle, words):
         self.ctx, self.h, self.words = ctx, handle, words
+        ctx._staged.add(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
     @property
     def ptr(self):
@@ -314,9 +329,12 @@ class StagedTrace:
         return bool(r)
 
     def free(self):
+        """Waits for the upload and returns the block (see include/zkm_hip.h); the host matrix may go after this."""
         if self.h:
-            self.ctx.L.zkm_staged_free(self.h)
-            self.h = None
+            h, self.h = self.h, None
+            self.ctx._staged.discard(self)
+            if self.ctx.h:
+                self.ctx.L.zkm_staged_free(h)
 
 
 def _data_ptr(x):
@@ -448,9 +466,12 @@ class Context:
         err = C.c_char_p()
         _check(self.L.zkm_ctx_create(device, C.byref(h), C.byref(err)), err)
         self.h = h
+        self._staged = weakref.WeakSet()     # outstanding StagedTraces: freed by close() before the context goes
 
     def close(self):
         if self.h:
+            for st in list(getattr(self, "_staged", ())):    # (first: their uploads may read pinned arrays freed below)
+                st.free()
             for p in list(getattr(self, "_pinned", {}).values()):
                 self.L.zkm_host_free(self.h, p)
             self._pinned = {}

@@ -598,18 +598,47 @@ static double commit_cost_estimate(const zkm_ctx* c, size_t ncols, unsigned log_
     return (double)((ncols + 7) / 8) * step + rows * (double)ncols * 2.5e-11 + 2e-4;    // + transforms (~25 ps per LDE word) + launches
 }
 
+// What the caller queued on the context's compute stream before a prove call -- zkm_staged_ptr's waits for a staged upload, the
+// canonicalising pass of a staged copy, anything written on zkm_ctx_stream -- comes before every read of the call's inputs on ANY stream
+// of the call (include/zkm_hip.h "staged traces"), not on the context's stream alone: one event recorded there where lanes are
+// dispatched, waited for on the device by each worker's compute and copy streams before their first operation.  Back to the context's
+// pool when the lanes have been joined (the waits are queued by then).
+struct call_entry {
+    zkm_ctx* c;
+    hipEvent_t e;
+    explicit call_entry(zkm_ctx* ctx) : c(ctx), e(ctx->get_event()) {
+        const hipError_t r = hipEventRecord(e, c->stream);
+        if (r != hipSuccess) {
+            c->event_pool.push_back(e);
+            ZKM_HIP_CHECK(r);
+        }
+    }
+    call_entry(const call_entry&) = delete;
+    call_entry& operator=(const call_entry&) = delete;
+    ~call_entry() { c->event_pool.push_back(e); }
+    void order(hipStream_t st) const {
+        if (st && st != c->stream) ZKM_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
+    }
+    void order(const zkm_ctx* w) const {
+        order(w->stream);
+        order(w->copy_stream);
+    }
+};
+
 // Independent per-table jobs on the context and its commit lanes (one host thread each).  `big` tables run first, on the context
 // itself; the others are assigned to the workers AHEAD of time, longest first onto the least loaded worker (cost[t] = estimated
 // seconds) -- not pulled from a queue: a worker that gets the same tables on every call finds every block it needs in its own
 // exact-size allocator cache from the second segment on (a dynamic queue kept hitting hipMalloc for ten or more calls: 37 -- 53 ms
 // per 2^16-cycle segment depending on who had grabbed what), and the memory the lanes cache stays that of ONE assignment.
-struct no_prep { void operator()(zkm_ctx*, const std::vector<size_t>&) const {} };
-// prep(worker context, the jobs that worker will run, in order): called once on the worker's thread before its first job
+struct no_prep { void operator()(zkm_ctx*, const std::vector<size_t>&, const call_entry&) const {} };
+// prep(worker context, the jobs that worker will run, in order, the call's entry): called once on the worker's thread before its first
+// job, after the worker's streams have been ordered behind the entry (a copy stream prep creates must be ordered by prep)
 template <class F, class P = no_prep>
 static void run_on_lanes(zkm_ctx* c, const std::vector<size_t>& big, const std::vector<size_t>& small, const std::vector<double>& cost,
                          F&& fn, P&& prep = P()) {
     const size_t nlanes = small.size() >= 2 ? std::min<size_t>(std::max<size_t>(1, c->commit_lanes), small.size()) - 1 : 0;
     c->ensure_lanes(nlanes);
+    const call_entry entry(c);
     std::vector<std::vector<size_t>> mine(nlanes + 1);
     {
         std::vector<double> load(nlanes + 1, 0.0);
@@ -629,11 +658,12 @@ static void run_on_lanes(zkm_ctx* c, const std::vector<size_t>& big, const std::
     auto work = [&](zkm_ctx* w, size_t slot, bool take_big) {
         try {
             ZKM_HIP_CHECK(hipSetDevice(c->device));
+            entry.order(w);
             {
                 std::vector<size_t> jobs;
                 if (take_big) jobs = big;
                 jobs.insert(jobs.end(), mine[slot].begin(), mine[slot].end());
-                prep(w, jobs);
+                prep(w, jobs, entry);
             }
             if (take_big)
                 for (size_t t : big) {
@@ -883,7 +913,7 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
                     for (size_t k = 0; k < G; k++) srcs[k] = io[g.segs[k]].tables[g.t].trace;
                     zkm_batch_build(b, nullptr, true, g.d_traces, nullptr, srcs.data());
                 }
-            }, [&](zkm_ctx* w, const std::vector<size_t>& jobs) {
+            }, [&](zkm_ctx* w, const std::vector<size_t>& jobs, const call_entry& entry) {
                 // Host-resident traces of the worker's stacks (the deployed input: generate_traces leaves them in host memory) go up on
                 // the worker's COPY stream, all of them queued now, each followed by an event: the transforms and hashing of a group
                 // overlap the uploads of the groups behind it (0.3 GB per 2^16-cycle segment over PCIe).  Pinned (zkm_host_alloc /
@@ -895,8 +925,11 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
                     if (!w->copy_stream) {
                         hipStream_t cs = nullptr;
                         ZKM_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-                        std::lock_guard<std::mutex> lk(w->alloc_mu);
-                        w->copy_stream = cs;
+                        {
+                            std::lock_guard<std::mutex> lk(w->alloc_mu);
+                            w->copy_stream = cs;
+                        }
+                        entry.order(cs);   // (a column may be a staged device matrix: the gather reads it after its upload)
                     }
                     g.d_traces = (gl_t*)w->alloc(G * W * n * sizeof(gl_t));
                     g.d_owner = w;
@@ -1042,6 +1075,7 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
             c->ensure_lanes(bg_lanes);
             bg.ready.assign(njobs, 0);
             bg.errs.assign(bg_lanes, nullptr);
+            const call_entry entry(c);     // (a lane may not have been a worker of the commitments: it reads staged traces too)
             struct stop_and_join {     // (an exception on this thread unwinds what the lanes refer to: they are stopped and joined first)
                 background& b;
                 ~stop_and_join() {
@@ -1054,6 +1088,7 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
                     zkm_ctx* w = c->lanes[k];
                     try {
                         ZKM_HIP_CHECK(hipSetDevice(c->device));
+                        entry.order(w);
                         for (size_t j = 1 + k; j < njobs; j += bg_lanes) {
                             if (bg.failed.load()) break;
                             aux_job(w, j);
