@@ -96,7 +96,7 @@ BENCH_WORKER = textwrap.dedent("""
     NCTX = %d
     STACK = %d
     sys.argv = [__file__, "--gpus", "2", "--segments", "7", "--warmup", "1", "--log-n", "10", "--no-cpu-baseline", "--no-extras",
-                "--contexts", str(NCTX), "--stack", str(STACK)]
+                "--contexts", str(NCTX), "--stack", str(STACK)] + %r
     import runpy
     runpy.run_path(%r, run_name="__main__")
     rank = int(__import__("os").environ["RANK"])
@@ -123,11 +123,12 @@ import pytest  # noqa: E402
 
 
 @pytest.mark.parametrize("nctx,backend,stack", [(1, "gloo", 1), (2, "gloo", 1), (2, "nccl", 1), (2, "gloo", 2), (1, "gloo", 4)])
-def test_bench_sharding_path_two_rank_gloo(tmp_path, nctx, backend, stack):
-    """backend "nccl": what the driver's multi-GPU run asks for.  There is no GPU here, so RCCL cannot come up -- the probe child of
+def test_bench_full_run_sharding_path_two_rank_gloo(tmp_path, nctx, backend, stack):
+    """bench.py --full on two ranks: the headline keys and the one-context profiled pass (single_context) in rank 0's line.
+    backend "nccl": what the driver's multi-GPU run asks for.  There is no GPU here, so RCCL cannot come up -- the probe child of
     every rank fails, the ranks agree on that over the gloo control group, and the job must finish on gloo and say so."""
     script = tmp_path / "bench_worker.py"
-    script.write_text(BENCH_WORKER % (ROOT, backend, nctx, stack, os.path.join(ROOT, "bench.py")))
+    script.write_text(BENCH_WORKER % (ROOT, backend, nctx, stack, ["--full"], os.path.join(ROOT, "bench.py")))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(29517 + nctx + (10 if backend == "nccl" else 0) + 20 * stack), str(script)],
@@ -158,7 +159,7 @@ def test_bench_started_as_a_plain_process_relaunches_itself_under_torchrun(tmp_p
     127.0.0.1 --master-port <free> bench.py ...` (zkm_amd.dist.self_launch): both ranks run, rank 0 prints the one JSON line.  A process
     that HAS a launcher's environment and the wrong world is an error, not a relaunch."""
     script = tmp_path / "bench_worker.py"
-    script.write_text(BENCH_WORKER % (ROOT, "gloo", 1, 1, os.path.join(ROOT, "bench.py")))
+    script.write_text(BENCH_WORKER % (ROOT, "gloo", 1, 1, [], os.path.join(ROOT, "bench.py")))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
     env["ZKM_BENCH_ENTRY"] = str(script)      # (the stub-context wrapper is the script to relaunch; runpy hides it from bench.py's sys.argv[0])
     r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300, env=env)
@@ -356,11 +357,12 @@ DUMP_WORKER = textwrap.dedent("""
     torch.cuda.mem_get_info = lambda d=None: (200 << 30, 288 << 30)
     torch.cuda.get_device_properties = lambda d: types.SimpleNamespace(multi_processor_count=256)
     sys.argv = [__file__, "--gpus", "1", "--steps", "6", "--warmup", "1", "--log-n", "10", "--no-cpu-baseline", "--no-extras",
-                "--stack", %r, "--dump-outputs", %r]
+                "--stack", %r, "--dump-outputs", %r] + %r
     import runpy
     runpy.run_path(%r, run_name="__main__")
     i0 = proved.index("sync"); i1 = proved.index("sync", i0 + 1)
     assert sorted(proved[i0 + 1:i1]) == list(range(100, 106)), proved       # --steps 6: six timed proofs, seeds 100..105
+    print("AFTER THE CLOCK", proved[i1 + 1:])
     print("WORKER OK")
 """)
 
@@ -371,7 +373,7 @@ def test_bench_dump_outputs_writes_the_last_timed_proof(tmp_path, stack):
     line's ms_per_step is the timed region over --steps."""
     out = tmp_path / "dump"
     script = tmp_path / "dump_worker.py"
-    script.write_text(DUMP_WORKER % (ROOT, str(stack), str(out), os.path.join(ROOT, "bench.py")))
+    script.write_text(DUMP_WORKER % (ROOT, str(stack), str(out), [], os.path.join(ROOT, "bench.py")))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "TORCHELASTIC_RUN_ID")}
     r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -385,3 +387,32 @@ def test_bench_dump_outputs_writes_the_last_timed_proof(tmp_path, stack):
     want = np.arange(7, dtype=np.uint64) * np.uint64(0x100000001) + np.uint64(105 << 40)
     got = lo.astype(np.uint64) | (hi.astype(np.uint64) << np.uint64(32))
     assert (got == want).all()
+
+
+FULL_ONLY_KEYS = ("roofline", "roofline_whole_proof", "roofline_ntt", "single_context", "stage_ms", "kernel_ms_per_proof", "timed_proofs_verified")
+
+
+@pytest.mark.parametrize("full", [False, True])
+def test_plain_bench_run_does_only_the_headline(tmp_path, full):
+    """A plain run sets up, warms up, times the steps, dumps and prints the line: after the clock it proves nothing and the line holds
+    no per-kernel figures.  --full adds the one-context profiled pass (three proofs after the clock) and its keys; the contract keys
+    and the proof size are the same either way."""
+    out = tmp_path / "dump"
+    script = tmp_path / "dump_worker.py"
+    script.write_text(DUMP_WORKER % (ROOT, "4", str(out), ["--full"] if full else [], os.path.join(ROOT, "bench.py")))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "TORCHELASTIC_RUN_ID")}
+    r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stdout + r.stderr
+    import json
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    after = [l for l in r.stdout.splitlines() if l.startswith("AFTER THE CLOCK")][0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in j, k
+    assert j["metric"] == "segment_proofs_per_sec" and j["unit"] == "proofs/s" and j["higher_is_better"] is True and j["steps"] == 6
+    assert j["config"]["proof_words"] == 7 and j["full"] is full
+    if full:
+        assert all(k in j for k in FULL_ONLY_KEYS), sorted(j)
+        assert j["single_context"]["steps"] == 3 and after == "AFTER THE CLOCK ['sync', 100, 101, 102, 'sync']", after
+    else:
+        assert not any(k in j for k in FULL_ONLY_KEYS), sorted(j)
+        assert after == "AFTER THE CLOCK []", after
