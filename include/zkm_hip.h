@@ -264,6 +264,34 @@ int zkm_logic_trace(zkm_ctx* ctx, const uint32_t* ops, size_t nops, unsigned log
 int zkm_memory_trace(zkm_ctx* ctx, const uint64_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, size_t* natural_rows_out,
                      char** err);
 
+/* ------------------------------------------------------------------ N3: ArithmeticStark witness
+ * ArithmeticStark::generate_trace (arithmetic/arithmetic_stark.rs:155-185) with generate_range_checks (:127-153) on the segment's
+ * arithmetic operations: each operation's rows (binary_op_to_rows, arithmetic/mod.rs:237-313; two rows for DIV, DIVU, SRL, SRLV, SRA
+ * and SRAV, one for the rest) in push order, zero rows behind them, RANGE_COUNTER (column 44) = min(row, 2^16 - 1) and RC_FREQUENCIES
+ * (column 45) += the count of each value over the 18 shared columns 26..43 of all 2^log_n rows, padding included.  54 columns x
+ * 2^log_n rows, column-major, canonical; column order of arithmetic/columns.rs.
+ *   ops                nops x 3 uint32 words {op, input0, input1} as Operation::binary(operator, input0, input1) receives them, host
+ *                      or device; op = the operator's row filter, IS_ADD = 0 .. IS_MTLO = 25 (mod.rs:135-164).  result0 / result1
+ *                      are computed on the device (BinaryOperator::result, mod.rs:48-133).  nops = 0 is valid: an all-padding table
+ *   out_dev            device pointer, or NULL: sizing only -- log_n is ignored and only *natural_rows_out is computed
+ *   natural_rows_out   max(2^16, next_pow2(rows)), the reference's table height (may be NULL)
+ * Fails (nonzero, message in *err; the contents of out_dev are then unspecified) if nops is 2^31 or more, log_n is below 16 or above
+ * ZKM_ARITHMETIC_MAX_LOG_N, the rows do not fit in 2^log_n (*natural_rows_out is still written), or an operation is outside the
+ * reference's domain:
+ *   op > 25;
+ *   DIV or DIVU with input1 = 0, or DIV of 0x80000000 by 0xFFFFFFFF (result() panics on both, mod.rs:123-127);
+ *   ADDI, ADDIU, SLTI or SLTIU with an input1 that is not a sign-extended 16-bit immediate (the emulator sign-extends,
+ *   witness/operation.rs:390; for any other input1 the row of addcy.rs / slt.rs and result0, mod.rs:52-60 / 94-109, disagree);
+ *   SLL, SRL, SRA or SRAV with a shift amount above 31 (result() gives 0 there, mod.rs:63-69, and sra.rs:52-73 shifts by the full
+ *   amount; SLLV and SRLV mask it, mod.rs:72-73, and accept any);
+ *   a shared-column value of 2^16 or more (the assert of generate_range_checks, arithmetic_stark.rs:144-149).
+ * LUI accepts any input0.  A failure leaves the context usable and its transient memory as it was.  Synchronous on the context's
+ * stream. */
+#define ZKM_ARITHMETIC_COLS 54
+#define ZKM_ARITHMETIC_MAX_LOG_N 28
+int zkm_arithmetic_trace(zkm_ctx* ctx, const uint32_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, size_t* natural_rows_out,
+                         char** err);
+
 /* ------------------------------------------------------------------ Fiat-Shamir (host)
  * plonky2 Challenger<F, PoseidonHash> (uses at prover.rs:182-190, 466, 524-527, 588-591, 610). */
 typedef struct {
@@ -296,7 +324,7 @@ void zkm_standard_config(zkm_stark_config* cfg);
  *   SHA_COMPRESS   sha_compress/sha_compress_stark.rs:402-606         224 columns
  *   SHA_COMPRESS_SPONGE sha_compress_sponge/sha_compress_sponge_stark.rs:233-268  127 columns
  *   ARITHMETIC     arithmetic/arithmetic_stark.rs:214-240 and its nine operation modules, 54 columns, plus the 18-column range-check lookup
- *                  :269-276 (at least 2^16 rows); rows come from the CPU-side witness generator (no witness kernel) */
+ *                  :269-276 (at least 2^16 rows); rows from zkm_arithmetic_trace or the CPU-side witness generator */
 #define ZKM_TABLE_POSEIDON 0
 #define ZKM_TABLE_LOGIC 1
 #define ZKM_TABLE_KECCAK_SPONGE 2

@@ -68,6 +68,8 @@ pub const ZKM_TABLE_SHA_EXTEND: c_int = 6; pub const ZKM_TABLE_SHA_EXTEND_SPONGE
 pub const ZKM_TABLE_SHA_COMPRESS_SPONGE: c_int = 9; pub const ZKM_TABLE_ARITHMETIC: c_int = 10; pub const ZKM_TABLE_CPU: c_int = 11;
 // width of the MemoryStark table zkm_memory_trace writes (memory/columns.rs)
 pub const ZKM_MEMORY_COLS: usize = 13;
+// width of the ArithmeticStark table zkm_arithmetic_trace writes (arithmetic/columns.rs)
+pub const ZKM_ARITHMETIC_COLS: usize = 54;
 
 #[link(name = "zkmhip")]
 extern "C" {
@@ -128,6 +130,8 @@ extern "C" {
     pub fn zkm_logic_trace(ctx: *mut zkm_ctx, ops: *const u32, nops: usize, log_n: c_uint, out_dev: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_memory_trace(ctx: *mut zkm_ctx, ops: *const u64, nops: usize, log_n: c_uint, out_dev: *mut u64, natural_rows_out: *mut usize,
                             err: *mut *mut c_char) -> c_int;
+    pub fn zkm_arithmetic_trace(ctx: *mut zkm_ctx, ops: *const u32, nops: usize, log_n: c_uint, out_dev: *mut u64,
+                                natural_rows_out: *mut usize, err: *mut *mut c_char) -> c_int;
     // Fiat-Shamir
     pub fn zkm_challenger_init(ch: *mut zkm_challenger);
     pub fn zkm_challenger_observe(ch: *mut zkm_challenger, elems: *const u64, n: usize);

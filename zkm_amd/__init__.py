@@ -22,6 +22,7 @@ POSEIDON_COLS = 262
 KECCAK_SPONGE_COLS = 470
 LOGIC_COLS = 69
 MEMORY_COLS = 13
+ARITHMETIC_COLS = 54
 KECCAK_COLS = 2431
 POSEIDON_SPONGE_COLS = 110
 TABLE_POSEIDON, TABLE_LOGIC, TABLE_KECCAK_SPONGE, TABLE_KECCAK, TABLE_MEMORY, TABLE_POSEIDON_SPONGE = 0, 1, 2, 3, 4, 5
@@ -33,7 +34,7 @@ EXPORTS = [
     "zkm_host_register", "zkm_host_unregister", "zkm_all_stark_ctls", "zkm_all_stark_ctl_table", "zkm_prove_segment", "zkm_prove_segments", "zkm_prove_segments_columns", "zkm_prove_segment_columns", "zkm_ctx_synchronize", "zkm_ctx_stream", "zkm_dev_alloc", "zkm_dev_free",
     "zkm_dev_upload", "zkm_dev_download", "zkm_ntt", "zkm_field_selftest", "zkm_batch_commit_values", "zkm_batch_commit_coeffs", "zkm_batch_commit_columns", "zkm_batch_free",
     "zkm_batch_cap", "zkm_batch_coeffs", "zkm_batch_lde_row", "zkm_batch_lde_rows", "zkm_batch_leaf", "zkm_batch_merkle_path",
-    "zkm_batch_digest_layer", "zkm_poseidon_permute_batch", "zkm_keccakf_batch", "zkm_poseidon_trace", "zkm_keccak_sponge_trace", "zkm_keccak_trace", "zkm_logic_trace", "zkm_memory_trace",
+    "zkm_batch_digest_layer", "zkm_poseidon_permute_batch", "zkm_keccakf_batch", "zkm_poseidon_trace", "zkm_keccak_sponge_trace", "zkm_keccak_trace", "zkm_logic_trace", "zkm_memory_trace", "zkm_arithmetic_trace",
     "zkm_poseidon_sponge_trace", "zkm_poseidon_trace_inputs", "zkm_sha_extend_trace", "zkm_sha_extend_sponge_trace",
     "zkm_sha_compress_trace", "zkm_sha_compress_sponge_trace",
     "zkm_table_width", "zkm_num_lookup_columns", "zkm_challenger_init",
@@ -197,6 +198,7 @@ def load():
         "zkm_table_enum_index": (C.c_int, [C.c_int]),
         "zkm_logic_trace": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, cp, err]),
         "zkm_memory_trace": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
+        "zkm_arithmetic_trace": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
         "zkm_table_width": (C.c_size_t, [C.c_int]),
         "zkm_challenger_init": (None, [C.POINTER(Challenger)]),
         "zkm_challenger_observe": (None, [C.POINTER(Challenger), u64p, C.c_size_t]),
@@ -686,6 +688,30 @@ class Context:
         mine = out is None
         out = out or self.alloc(MEMORY_COLS << log_n)
         rc = self.L.zkm_memory_trace(self.h, _data_ptr(ops), nops, log_n, _data_ptr(out), C.byref(natural), C.byref(err))
+        if rc != 0 and mine:
+            out.free()
+        _check(rc, err)
+        return out, natural.value
+
+    def arithmetic_trace(self, ops, log_n=None, out=None, nops=None):
+        """ArithmeticStark::generate_trace on the GPU (arithmetic_stark.rs:155-185) from the raw operations.  ops: nops x 3 uint32
+        (op = row filter IS_ADD 0 .. IS_MTLO 25, input0, input1), an ndarray or a DeviceBuffer holding them packed (ceil(3 nops / 2)
+        words; nops=None takes that many from its size).  log_n=None: the reference's height (a sizing call first).  Returns
+        (DeviceBuffer of 54 x 2^log_n words, natural rows = max(2^16, next_pow2(rows)))."""
+        if isinstance(ops, DeviceBuffer):
+            nops = ops.words * 2 // 3 if nops is None else nops
+        else:
+            ops = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1, 3)
+            nops = len(ops)
+        src = _data_ptr(ops) if isinstance(ops, DeviceBuffer) else ops.ctypes.data_as(C.c_void_p)
+        natural = C.c_size_t()
+        err = C.c_char_p()
+        if log_n is None:
+            _check(self.L.zkm_arithmetic_trace(self.h, src, nops, 0, None, C.byref(natural), C.byref(err)), err)
+            log_n = natural.value.bit_length() - 1
+        mine = out is None
+        out = out or self.alloc(ARITHMETIC_COLS << log_n)
+        rc = self.L.zkm_arithmetic_trace(self.h, src, nops, log_n, _data_ptr(out), C.byref(natural), C.byref(err))
         if rc != 0 and mine:
             out.free()
         _check(rc, err)

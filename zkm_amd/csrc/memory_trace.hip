@@ -16,16 +16,17 @@
 // Only the key widths and the row count come back to the host before the output is written.
 #include <algorithm>
 
+#include "scan_dev.h"
 #include "zkm_internal.h"
 
 namespace {
 
-constexpr int MT_THREADS = 256;
-constexpr int MT_WAVES = MT_THREADS / 64;
-constexpr int MT_ITEMS = 8;                          // keys per lane and tile
-constexpr int MT_TILE = MT_THREADS * MT_ITEMS;       // 2048 keys per tile
+constexpr int MT_THREADS = SCAN_THREADS;
+constexpr int MT_WAVES = SCAN_WAVES;
+constexpr int MT_ITEMS = SCAN_ITEMS;                 // keys per lane and tile
+constexpr int MT_TILE = SCAN_TILE;                   // 2048 keys per tile
 constexpr int MT_RADIX = 256;                        // 8-bit digits
-constexpr uint64_t MT_SAT = 1ull << 62;              // row counts saturate here (one timestamp gap can ask for 2^40 dummies)
+constexpr uint64_t MT_SAT = SCAN_SAT;                // row counts saturate here (one timestamp gap can ask for 2^40 dummies)
 constexpr int MT_HIST_LDS = 2048;                    // FREQUENCIES bins kept in LDS (range checks are mostly small)
 constexpr unsigned MT_MAX_LOG_N = ZKM_MEMORY_MAX_LOG_N;
 
@@ -41,36 +42,6 @@ __device__ __forceinline__ mem_op load_op(const uint64_t* __restrict__ ops, uint
 struct key_layout {
     unsigned width[4], shift[4], nwords, bits;
 };
-
-__device__ __forceinline__ uint64_t sat_add(uint64_t a, uint64_t b) {   // a, b <= MT_SAT
-    uint64_t s = a + b;
-    return s > MT_SAT ? MT_SAT : s;
-}
-
-struct add_u32 { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; } };
-struct add_sat { __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return sat_add(a, b); } };
-
-// inclusive scan over the block (identity 0); *total = the block's sum.  sh: MT_WAVES words of LDS.  Every thread must call it.
-template <class T, class Op>
-__device__ __forceinline__ T block_incl_scan(T v, T* sh, Op op, T* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        T u = __shfl_up(v, o);
-        if (lane >= o) v = op(u, v);
-    }
-    if (lane == 63) sh[w] = v;
-    __syncthreads();
-    T pre = 0, all = 0;
-#pragma unroll
-    for (int q = 0; q < MT_WAVES; q++) {
-        if (q < w) pre = op(pre, sh[q]);
-        all = op(all, sh[q]);
-    }
-    __syncthreads();
-    *total = all;
-    return op(pre, v);
-}
 
 // ---- (1) key widths
 __global__ __launch_bounds__(MT_THREADS) void k_mem_widths(const uint64_t* __restrict__ ops, size_t nops, unsigned long long* acc) {
@@ -241,50 +212,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_mem_gaps(const uint64_t* __restr
     if (k) atomicMax(last, (unsigned)(i + 1));
 }
 
-// ---- (5) exclusive saturating scan of v[0, len) in place: per-tile sums, a one-block scan of those, then the tiles
-__global__ __launch_bounds__(MT_THREADS) void k_scan_tiles(const uint64_t* __restrict__ v, size_t len, uint64_t* __restrict__ part) {
-    __shared__ uint64_t sh[MT_WAVES];
-    const size_t base = (size_t)blockIdx.x * MT_TILE + (size_t)threadIdx.x * MT_ITEMS;
-    uint64_t s = 0;
-#pragma unroll
-    for (int it = 0; it < MT_ITEMS; it++)
-        if (base + it < len) s = sat_add(s, v[base + it]);
-    uint64_t all;
-    block_incl_scan(s, sh, add_sat(), &all);
-    if (threadIdx.x == 0) part[blockIdx.x] = all;
-}
-__global__ __launch_bounds__(MT_THREADS) void k_scan_parts(uint64_t* __restrict__ part, size_t nparts) {
-    __shared__ uint64_t sh[MT_WAVES];
-    uint64_t carry = 0;
-    for (size_t c = 0; c < nparts; c += MT_THREADS) {
-        const size_t t = c + threadIdx.x;
-        const uint64_t x = t < nparts ? part[t] : 0;
-        uint64_t all;
-        const uint64_t incl = block_incl_scan(x, sh, add_sat(), &all);
-        if (t < nparts) part[t] = sat_add(carry, incl >= MT_SAT ? MT_SAT : incl - x);   // exact unless the table is rejected
-        carry = sat_add(carry, all);
-    }
-}
-__global__ __launch_bounds__(MT_THREADS) void k_scan_apply(uint64_t* __restrict__ v, size_t len, const uint64_t* __restrict__ part) {
-    __shared__ uint64_t sh[MT_WAVES];
-    const size_t base = (size_t)blockIdx.x * MT_TILE + (size_t)threadIdx.x * MT_ITEMS;
-    uint64_t x[MT_ITEMS], s = 0;
-#pragma unroll
-    for (int it = 0; it < MT_ITEMS; it++) {
-        x[it] = base + it < len ? v[base + it] : 0;
-        s = sat_add(s, x[it]);
-    }
-    uint64_t all;
-    const uint64_t incl = block_incl_scan(s, sh, add_sat(), &all);
-    // exclusive prefix of this thread: the block's inclusive scan minus its own sum (exact when nothing saturated; otherwise both are
-    // MT_SAT and the caller rejects the table anyway)
-    uint64_t run = sat_add(part[blockIdx.x], incl >= MT_SAT ? MT_SAT : incl - s);
-#pragma unroll
-    for (int it = 0; it < MT_ITEMS; it++) {
-        if (base + it < len) v[base + it] = run;
-        run = sat_add(run, x[it]);
-    }
-}
+// ---- (5) exclusive saturating scan: k_scan_tiles / k_scan_parts / k_scan_apply (scan_dev.h)
 
 // ---- (6) rows.  start[i] = first row of sorted op i (rows of the padding-free table), start[nops] = that table's height `count`.
 // The padding (n - count copies of the last op pushed) goes right behind that op's row q - 1, q = start[last] (or count).
