@@ -96,6 +96,17 @@ void zkm_ctx::drop_copy_streams() {
     for (hipStream_t st : {a, b})
         if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
 }
+// (published under the allocator's lock: a relative's out-of-memory path reads it from its own thread, trim_self)
+hipStream_t zkm_ctx::ensure_copy_stream(int k) {
+    hipStream_t& cs = k ? copy_stream2 : copy_stream;
+    if (!cs) {
+        hipStream_t st = nullptr;
+        ZKM_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        std::lock_guard<std::mutex> g(alloc_mu);
+        cs = st;
+    }
+    return cs;
+}
 void zkm_ctx::trim() {   // public: between calls (zkm_ctx_trim)
     trim_self();
     shrink_down();
@@ -643,31 +654,22 @@ struct zkm_staged {
 
 static zkm_staged* stage_begin(zkm_ctx* c, size_t words, int canonical) {
     ZKM_HIP_CHECK(hipSetDevice(c->device));
-    for (hipStream_t* cs : {&c->copy_stream, &c->copy_stream2})
-        if (!*cs) {
-            hipStream_t st = nullptr;
-            ZKM_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-            std::lock_guard<std::mutex> g(c->alloc_mu);      // (published under the allocator's lock, like zkm_batch_build's)
-            *cs = st;
-        }
+    c->ensure_copy_stream(0);
+    c->ensure_copy_stream(1);
+    zkm_scratch dev(c, words * sizeof(gl_t));
+    {
+        // the block may be one a finished call of this context released: whatever the compute stream still has queued on it comes first
+        const zkm_event e(c);
+        e.record(c->stream);
+        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
+        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
+    }
     zkm_staged* s = new zkm_staged();
     s->ctx = c; s->words = words; s->joined = false; s->canonical = canonical != 0;
     s->done[0] = s->done[1] = nullptr;
     s->segment = false;
     for (size_t& o : s->off) o = 0;
-    try {
-        s->dev = (gl_t*)c->alloc(words * sizeof(gl_t));
-        // the block may be one a finished call of this context released: whatever the compute stream still has queued on it comes first
-        hipEvent_t e = c->get_event();
-        ZKM_HIP_CHECK(hipEventRecord(e, c->stream));
-        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e, 0));
-        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e, 0));
-        c->event_pool.push_back(e);
-    } catch (...) {
-        if (s->dev) c->release(s->dev);
-        delete s;
-        throw;
-    }
+    s->dev = (gl_t*)dev.take();
     g_staged_live.fetch_add(1, std::memory_order_relaxed);
     return s;
 }
@@ -992,50 +994,40 @@ void zkm_batch_build(zkm_batch* b, const uint64_t* src, bool src_is_values, gl_t
         // split into chunks of CH columns on the copy stream; the compute stream transforms (iNTT, LDE) and ABSORBS chunk k
         // (leaf sponge, hash.hip k_merkle_leaves_chunk) while chunk k + 1 .. are in flight, so PCIe time hides behind hashing.
         // Each chunk is staged in the LDE region of its own columns (or lands in dev_values), so there is no buffer to recycle.
-        if (!c->copy_stream) {   // (published under the allocator's lock: a relative's out-of-memory path reads it from its own thread)
-            hipStream_t cs = nullptr;
-            ZKM_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-            std::lock_guard<std::mutex> g(c->alloc_mu);
-            c->copy_stream = cs;
-        }
+        c->ensure_copy_stream();
         const size_t nchunks = (ncols + CH - 1) / CH;
-        std::vector<hipEvent_t> ev;
-        ev.reserve(nchunks + 1);
         zkm_scratch state(c, 12 * N * sizeof(gl_t));
-        // Every exit path -- also a HIP error in the middle of the loop -- drains BOTH streams before the sponge state, the events
-        // and (in the callers' unwinding) the batch's buffers go back to the allocator: uploads may still be in flight into them, and
-        // the caller may free the host source as soon as this returns.
-        auto drain = [&]() {
-            (void)hipStreamSynchronize(c->copy_stream);
-            (void)hipStreamSynchronize(c->stream);
-            for (auto e : ev) c->event_pool.push_back(e);
-            ev.clear();
-        };
-        try {
-            ev.push_back(c->get_event());
-            ZKM_HIP_CHECK(hipEventRecord(ev[0], c->stream));           // the LDE buffer may still be in use by queued work of a freed batch
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, ev[0], 0));
-            for (size_t k = 0; k < nchunks; k++) {
-                size_t c0 = k * CH, nc = std::min(CH, ncols - c0);
-                gl_t* dst = dev_values ? dev_values + c0 * n : b->lde + c0 * N;
-                copy_cols(dst, c0, nc, hipMemcpyHostToDevice, c->copy_stream);
-                ev.push_back(c->get_event());
-                ZKM_HIP_CHECK(hipEventRecord(ev.back(), c->copy_stream));
+        std::vector<zkm_event> ev;
+        ev.reserve(nchunks + 1);
+        // Every exit path -- also a HIP error in the middle of the loop -- drains BOTH streams before the events, the sponge state and
+        // (in the callers' unwinding) the batch's buffers go back: uploads may still be in flight into them, and the caller may free the
+        // host source as soon as this returns.
+        struct drain {
+            zkm_ctx* c;
+            ~drain() {
+                (void)hipStreamSynchronize(c->copy_stream);
+                (void)hipStreamSynchronize(c->stream);
             }
-            for (size_t k = 0; k < nchunks; k++) {
-                size_t c0 = k * CH, nc = std::min(CH, ncols - c0);
-                gl_t* vals = dev_values ? dev_values + c0 * n : b->lde + c0 * N;
-                ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, ev[k + 1], 0));
-                if (dev_values) zkm_launch_canon(c, vals, nc * n);
-                inverse_transform(vals, c0, nc);
-                zkm_lde_bitrev(c, b->coeffs + c0 * n, b->lde + c0 * N, nc, b->log_n, b->rate_bits, GL_GENERATOR, s1);
-                zkm_launch_merkle_leaves_chunk(c, b->lde + c0 * N, N, nc, N, state.as<gl_t>(), k == 0, k + 1 == nchunks, b->digests);
-            }
-        } catch (...) {
-            drain();
-            throw;
+        } const drained{c};
+        ev.emplace_back(c);
+        ev[0].record(c->stream);           // the LDE buffer may still be in use by queued work of a freed batch
+        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, ev[0].e, 0));
+        for (size_t k = 0; k < nchunks; k++) {
+            size_t c0 = k * CH, nc = std::min(CH, ncols - c0);
+            gl_t* dst = dev_values ? dev_values + c0 * n : b->lde + c0 * N;
+            copy_cols(dst, c0, nc, hipMemcpyHostToDevice, c->copy_stream);
+            ev.emplace_back(c);
+            ev.back().record(c->copy_stream);
         }
-        drain();
+        for (size_t k = 0; k < nchunks; k++) {
+            size_t c0 = k * CH, nc = std::min(CH, ncols - c0);
+            gl_t* vals = dev_values ? dev_values + c0 * n : b->lde + c0 * N;
+            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, ev[k + 1].e, 0));
+            if (dev_values) zkm_launch_canon(c, vals, nc * n);
+            inverse_transform(vals, c0, nc);
+            zkm_lde_bitrev(c, b->coeffs + c0 * n, b->lde + c0 * N, nc, b->log_n, b->rate_bits, GL_GENERATOR, s1);
+            zkm_launch_merkle_leaves_chunk(c, b->lde + c0 * N, N, nc, N, state.as<gl_t>(), k == 0, k + 1 == nchunks, b->digests);
+        }
         leaves_done = true;
     } else if (src_is_values && dev) {
         // device-resident values are only read (first NTT pass); the not-yet-used LDE buffer holds the intermediate passes
@@ -1091,18 +1083,18 @@ __global__ __launch_bounds__(256) void k_gather_lde_rows(const gl_t* __restrict_
     out[idx] = lde[col * N + row];
 }
 
-static zkm_batch_ptr batch_new(zkm_ctx* c, size_t ncols, unsigned log_n, unsigned rate_bits, unsigned cap_height) {
+zkm_batch_ptr zkm_batch_new(zkm_ctx* c, size_t ncols, size_t nseg, unsigned log_n, unsigned rate_bits, unsigned cap_height) {
     if (ncols == 0) throw std::runtime_error("empty polynomial batch");
     if (cap_height > log_n + rate_bits) throw std::runtime_error("cap_height exceeds LDE size");
     zkm_batch_ptr b(new zkm_batch());
-    b->ctx = c; b->ncols = ncols; b->log_n = log_n; b->rate_bits = rate_bits; b->cap_height = cap_height;
+    b->ctx = c; b->ncols = ncols; b->nseg = nseg; b->log_n = log_n; b->rate_bits = rate_bits; b->cap_height = cap_height;
     return b;
 }
 
 // from_values keeping the uploaded values in dev_values (see zkm_batch_build); throws
 zkm_batch* zkm_batch_commit_values_keep(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, unsigned rate_bits,
                                         unsigned cap_height, gl_t* dev_values, const uint64_t* const* columns) {
-    zkm_batch_ptr b = batch_new(c, ncols, log_n, rate_bits, cap_height);
+    zkm_batch_ptr b = zkm_batch_new(c, ncols, 1, log_n, rate_bits, cap_height);
     zkm_batch_build(b.get(), values, true, dev_values, columns);
     return b.release();
 }
@@ -1112,7 +1104,7 @@ extern "C" {
 int zkm_batch_commit_values(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, unsigned rate_bits,
                             unsigned cap_height, zkm_batch** out, char** err) {
     return zkm_api("zkm_batch_commit_values", c, err, [&] {
-        zkm_batch_ptr b = batch_new(c, ncols, log_n, rate_bits, cap_height);
+        zkm_batch_ptr b = zkm_batch_new(c, ncols, 1, log_n, rate_bits, cap_height);
         zkm_batch_build(b.get(), values, true);
         *out = b.release();
     });
@@ -1121,7 +1113,7 @@ int zkm_batch_commit_columns(zkm_ctx* c, const uint64_t* const* columns, size_t 
                              unsigned rate_bits, unsigned cap_height, zkm_batch** out, char** err) {
     return zkm_api("zkm_batch_commit_columns", c, err, [&] {
         if (!columns || !out) throw std::runtime_error("zkm_batch_commit_columns: null argument");
-        zkm_batch_ptr b = batch_new(c, ncols, log_n, rate_bits, cap_height);
+        zkm_batch_ptr b = zkm_batch_new(c, ncols, 1, log_n, rate_bits, cap_height);
         zkm_batch_build(b.get(), nullptr, columns_are_values != 0, nullptr, columns);
         *out = b.release();
     });
@@ -1129,7 +1121,7 @@ int zkm_batch_commit_columns(zkm_ctx* c, const uint64_t* const* columns, size_t 
 int zkm_batch_commit_coeffs(zkm_ctx* c, const uint64_t* coeffs, size_t ncols, unsigned log_n, unsigned rate_bits,
                             unsigned cap_height, zkm_batch** out, char** err) {
     return zkm_api("zkm_batch_commit_coeffs", c, err, [&] {
-        zkm_batch_ptr b = batch_new(c, ncols, log_n, rate_bits, cap_height);
+        zkm_batch_ptr b = zkm_batch_new(c, ncols, 1, log_n, rate_bits, cap_height);
         zkm_batch_build(b.get(), coeffs, false);
         *out = b.release();
     });

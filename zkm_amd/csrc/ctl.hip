@@ -19,7 +19,6 @@
 // ------------------------------------------------------------------ descriptor upload + validation
 void ctl_dev_owner::upload(zkm_ctx* ctx, const zkm_ctl_table* t, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs, bool lookup_mode,
                            size_t trace_ncols, size_t nseg) {
-    c = ctx;
     if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("CTL description: bad segment count");
     // (a stacked description: zs holds nseg lists of nzs entries that differ in their challenges only -- segment s of a launch reads list s)
     for (size_t sg = 1; sg < nseg; sg++)
@@ -73,10 +72,10 @@ void ctl_dev_owner::upload(zkm_ctx* ctx, const zkm_ctl_table* t, const zkm_ctl_z
     if (nzs) memcpy(&h[o_zs], zs, nseg * nzs * sizeof(zkm_ctl_z));
     if (t->nfilter_idx) memcpy(&h[o_fi], t->filter_idx, t->nfilter_idx * 4);
     if (nids) memcpy(&h[o_ids], colset_ids, nids * 4);
-    blob = c->alloc(total);
+    blob = zkm_scratch(ctx, total);
     h_zs.assign(zs, zs + nzs);
-    c->upload(blob, h.data(), total);   // (staged through the context's pinned ring or by the runtime: `h` may go)
-    char* b = (char*)blob;
+    ctx->upload(blob.p, h.data(), total);   // (staged through the context's pinned ring or by the runtime: `h` may go)
+    char* b = blob.as<char>();
     d.columns = (const zkm_column*)(b + o_cols);
     d.term_coeff = (const uint64_t*)(b + o_coeff);
     d.colsets = (const zkm_colset*)(b + o_sets);
@@ -89,10 +88,7 @@ void ctl_dev_owner::upload(zkm_ctx* ctx, const zkm_ctl_table* t, const zkm_ctl_z
     naux = th + nzs;
 }
 ctl_dev_owner::~ctl_dev_owner() {
-    if (c && blob) {
-        (void)hipStreamSynchronize(c->stream);
-        c->release(blob);
-    }
+    if (blob.p) (void)hipStreamSynchronize(blob.c->stream);
 }
 
 // ------------------------------------------------------------------ K6 kernels
@@ -251,11 +247,10 @@ static void suffix_sum(zkm_ctx* c, const gl_t* a, size_t a_stride, size_t n, siz
     const unsigned z = (unsigned)nstack;
     struct level { const gl_t* t; size_t stride, m, seg; };
     std::vector<level> lv{{a, a_stride, n, a_seg}};
-    std::vector<void*> tmp;
+    zkm_scratch_list tmp(c);
     while (lv.back().m > 64) {
         size_t nseg = (lv.back().m + 63) / 64;
-        gl_t* t = (gl_t*)c->alloc(nstack * nb * nseg * sizeof(gl_t));
-        tmp.push_back(t);
+        gl_t* t = tmp.alloc<gl_t>(nstack * nb * nseg * sizeof(gl_t));
         hipLaunchKernelGGL(k_sum_totals, dim3((unsigned)((nseg + 63) / 64), (unsigned)nb, z), dim3(64), 0, c->stream, lv.back().t, lv.back().stride,
                            lv.back().m, t, lv.back().seg);
         lv.push_back({t, nseg, nseg, nb * nseg});
@@ -266,14 +261,12 @@ static void suffix_sum(zkm_ctx* c, const gl_t* a, size_t a_stride, size_t n, siz
         const gl_t* upper = l + 1 < lv.size() ? S[l + 1] : nullptr;
         size_t nupper = l + 1 < lv.size() ? lv[l + 1].m : 0;
         if (l == 0) S[l] = out;
-        else { S[l] = (gl_t*)c->alloc(nstack * nb * lv[l].m * sizeof(gl_t)); tmp.push_back(S[l]); }
+        else S[l] = tmp.alloc<gl_t>(nstack * nb * lv[l].m * sizeof(gl_t));
         hipLaunchKernelGGL(k_sum_scan, dim3((unsigned)((nseg + 63) / 64), (unsigned)nb, z), dim3(64), 0, c->stream, lv[l].t, lv[l].stride, lv[l].m,
                            upper, nupper, S[l], l == 0 ? out_stride : lv[l].m, lv[l].seg, l == 0 ? out_seg : nb * lv[l].m);
     }
     ZKM_HIP_CHECK(hipGetLastError());
-    // no host sync: the temporaries go back to the caching allocator, whose blocks are only ever reused by later work on this stream
-    for (void* q : tmp) c->release(q);
-}
+}   // (no host sync: `tmp` goes back to the caching allocator, whose blocks are only ever reused by later work on this stream)
 
 // logUp: x[i] = hsum[i] - frequencies[i] / (challenge + table[i])   (lookup.rs:100-116)
 // (segment blockIdx.z of a stack: its challenge is the gamma of its CtlZData list's only entry)
@@ -306,8 +299,9 @@ void zkm_ctl_data_device(zkm_ctx* c, const ctl_dev_owner& own, const gl_t* d_tra
     const std::vector<zkm_ctl_z>& zs = own.h_zs;             // (host copy kept by upload(): no round trip for the launch planning)
     const size_t nzs = zs.size();
     const unsigned z = (unsigned)nseg;
-    gl_t* const d_hsum_all = (gl_t*)c->alloc(nseg * (nzs ? nzs : 1) * n * sizeof(gl_t));   // the per-row sums of every Z, scanned together below
-    int* d_bad = (int*)c->alloc(ZKM_MAX_SEG * sizeof(int));     // one flag per segment of the stack
+    zkm_scratch hsum_all(c, nseg * (nzs ? nzs : 1) * n * sizeof(gl_t)), bad_flags(c, ZKM_MAX_SEG * sizeof(int));
+    gl_t* const d_hsum_all = hsum_all.as<gl_t>();   // the per-row sums of every Z, scanned together below
+    int* d_bad = bad_flags.as<int>();                // one flag per segment of the stack
     ZKM_HIP_CHECK(hipMemsetAsync(d_bad, 0, ZKM_MAX_SEG * sizeof(int), c->stream));
     // Zs with many helper columns on a short table spread their column sets over blockIdx.y (few workgroups per launch otherwise);
     // every other run of consecutive Zs is ONE launch (blockIdx.y = Z)
@@ -338,8 +332,8 @@ void zkm_ctl_data_device(zkm_ctx* c, const ctl_dev_owner& own, const gl_t* d_tra
     }
     int bad[ZKM_MAX_SEG];
     c->download(bad, d_bad, ZKM_MAX_SEG * sizeof(int));
-    c->release(d_hsum_all);
-    c->release(d_bad);
+    hsum_all.reset();
+    bad_flags.reset();
     for (size_t sg = 0; sg < nseg; sg++)
         if (bad[sg]) throw zkm_segment_error(sg, "Non-binary filter?");
 }
@@ -605,19 +599,10 @@ static double commit_cost_estimate(const zkm_ctx* c, size_t ncols, unsigned log_
 // pool when the lanes have been joined (the waits are queued by then).
 struct call_entry {
     zkm_ctx* c;
-    hipEvent_t e;
-    explicit call_entry(zkm_ctx* ctx) : c(ctx), e(ctx->get_event()) {
-        const hipError_t r = hipEventRecord(e, c->stream);
-        if (r != hipSuccess) {
-            c->event_pool.push_back(e);
-            ZKM_HIP_CHECK(r);
-        }
-    }
-    call_entry(const call_entry&) = delete;
-    call_entry& operator=(const call_entry&) = delete;
-    ~call_entry() { c->event_pool.push_back(e); }
+    zkm_event e;
+    explicit call_entry(zkm_ctx* ctx) : c(ctx), e(ctx) { e.record(c->stream); }
     void order(hipStream_t st) const {
-        if (st && st != c->stream) ZKM_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
+        if (st && st != c->stream) ZKM_HIP_CHECK(hipStreamWaitEvent(st, e.e, 0));
     }
     void order(const zkm_ctx* w) const {
         order(w->stream);
@@ -687,6 +672,67 @@ static void run_on_lanes(zkm_ctx* c, const std::vector<size_t>& big, const std::
         if (e) std::rethrow_exception(e);
 }
 
+// The other schedule, for a segment of short tables (no table fills the GPU on its own): the table proofs are ONE chain of
+// latency-bound steps on the context's stream, and the job a proof needs (its table's auxiliary commitment) is not needed before that
+// table's turn.  `nlanes` lanes build jobs 1 .. njobs - 1 behind the proofs -- lane k takes 1 + k, 1 + k + nlanes, ..., the same deal on
+// every call, so that each lane finds its blocks in its own allocator cache -- while the calling thread builds job 0 and then consumes
+// the jobs in order, each as soon as it has been built: build(worker context, job), consume(job).  The error contract is run_on_lanes':
+// the first exception stops the lanes, they are joined, and it is rethrown on the caller.
+template <class B, class U>
+static void run_behind(zkm_ctx* c, size_t nlanes, size_t njobs, B&& build, U&& consume) {
+    c->ensure_lanes(nlanes);
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<char> ready(njobs, 0);
+    std::vector<std::exception_ptr> errs(nlanes);
+    std::atomic<bool> failed{false};
+    const call_entry entry(c);     // (a lane may not have been a worker of the commitments: it reads staged traces too)
+    std::vector<std::thread> threads;
+    struct stop_and_join {         // (an exception on this thread unwinds what the lanes refer to: they are stopped and joined first)
+        std::vector<std::thread>& threads;
+        std::atomic<bool>& failed;
+        ~stop_and_join() {
+            if (!threads.empty()) failed.store(true);
+            for (auto& th : threads) th.join();
+        }
+    } guard{threads, failed};
+    for (size_t k = 0; k < nlanes; k++)
+        threads.emplace_back([&, k]() {
+            zkm_ctx* w = c->lanes[k];
+            try {
+                ZKM_HIP_CHECK(hipSetDevice(c->device));
+                entry.order(w);
+                for (size_t j = 1 + k; j < njobs; j += nlanes) {
+                    if (failed.load()) break;
+                    build(w, j);
+                    std::lock_guard<std::mutex> g(mu);
+                    ready[j] = 1;
+                    cv.notify_all();
+                }
+            } catch (...) {
+                errs[k] = std::current_exception();
+                failed.store(true);
+            }
+            std::lock_guard<std::mutex> g(mu);      // (whatever happened: nobody waits for this lane any more)
+            for (size_t j = 1 + k; j < njobs; j += nlanes) ready[j] = 1;
+            cv.notify_all();
+        });
+    build(c, 0);
+    for (size_t j = 0; j < njobs; j++) {
+        if (j) {
+            zkm_prof_scope st(c, "stage/wait for auxiliary polynomials commitment");
+            std::unique_lock<std::mutex> g(mu);
+            cv.wait(g, [&] { return ready[j] != 0; });
+        }
+        if (failed.load()) break;
+        consume(j);
+    }
+    for (auto& th : threads) th.join();
+    threads.clear();
+    for (auto& e : errs)
+        if (e) std::rethrow_exception(e);
+}
+
 // ------------------------------------------------------------------ prove_with_traces for K segments in lock-step
 // The segments of one call share the table list (ids, widths, column-set descriptions) and the cross-table lookups; heights may differ.
 // For every table the segments are partitioned by height into GROUPS of at most ZKM_MAX_SEG: a group's trace, auxiliary and quotient
@@ -705,68 +751,61 @@ struct table_group {
     size_t t = 0;                    // table
     std::vector<size_t> segs;        // its segments (call order)
     unsigned log_n = 0;
-    zkm_batch* commit = nullptr;
-    zkm_batch* aux = nullptr;
-    gl_t* d_traces = nullptr;        // stacked device copy of the trace values (segs.size() x ncols x n), or null: read in place
-    zkm_ctx* d_owner = nullptr;      // ... from the allocator of the context (commit lane) that made it
+    zkm_batch_ptr commit, aux;
+    zkm_scratch traces;              // stacked device copy of the trace values (segs.size() x ncols x n) from the allocator of the context
+                                     // (commit lane) that made it, or empty: read in place
     bool host = false, keep = false;
-    hipEvent_t uploaded = nullptr;   // host-resident traces of a stack: recorded on the worker's copy stream behind their upload
-    zkm_ctx* uploaded_on = nullptr;
+    zkm_event uploaded;              // host-resident traces of a stack: recorded on the worker's copy stream behind their upload
 };
 
-// (seg_base: position of io[0] in the caller's call -- the waves of an oversized call; only error messages use it)
-static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const seg_io* io, size_t ntables,
-                                const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t seg_base = 0) {
-    std::vector<table_group> groups;
-    auto drop_traces = [&]() {
-        (void)hipStreamSynchronize(c->stream);
-        for (table_group& g : groups) {
-            if (g.d_traces) (g.d_owner ? g.d_owner : c)->release(g.d_traces);
-            g.d_traces = nullptr;
-        }
-    };
-    auto drop_all = [&]() {
+// One call, phase by phase (prove_segments_impl).  The groups own what the call holds; on every exit path, normal or exceptional, the
+// destructor drains the streams of the call -- the context's compute and copy streams and each lane's -- before the groups release it.
+struct lockstep_call {
+    zkm_ctx* const c;
+    const zkm_stark_config* const cfg;
+    const size_t nseg;
+    const seg_io* const io;
+    const size_t ntables;
+    const zkm_cross_table_lookup* const ctls;
+    const zkm_ctl_side* const sides;
+    const size_t nctls;
+    const size_t seg_base;                        // position of io[0] in the caller's call (the waves of an oversized call; error messages only)
+    const zkm_table_input* T0 = nullptr;          // segment 0's table list (the others agree: plan)
+    std::vector<std::vector<size_t>> offs;        // per segment: word offset of each table's proof
+    std::vector<table_zs> tz0;                    // the structure of every table's CtlZData list (no challenges)
+    std::vector<table_group> groups;              // numbered table by table: job order is proof order
+    std::vector<std::vector<size_t>> where, pos;  // group of (table, segment), and the segment's position in it
+    std::vector<size_t> big, small;               // groups committed on the context itself / dealt to the lanes
+    std::vector<zkm_challenger> ch;               // per segment
+    std::vector<std::vector<zkm_ctl_z>> gzs;      // per group: its segments' CtlZData lists one after the other
+    std::vector<std::vector<uint64_t>> glookup;   // ... and their lookup challenges
+
+    ~lockstep_call() {
         (void)hipStreamSynchronize(c->stream);
         if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
         for (zkm_ctx* l : c->lanes) {
             (void)hipStreamSynchronize(l->stream);
             if (l->copy_stream) (void)hipStreamSynchronize(l->copy_stream);
         }
-        for (table_group& g : groups)
-            if (g.uploaded) {
-                g.uploaded_on->event_pool.push_back(g.uploaded);
-                g.uploaded = nullptr;
-            }
-        for (table_group& g : groups) {
-            zkm_batch_free(g.commit);
-            zkm_batch_free(g.aux);
-            g.commit = g.aux = nullptr;
-        }
-        drop_traces();
-    };
-    struct background {            // lanes building auxiliary commitments behind the table proofs (below)
-        std::mutex mu;
-        std::condition_variable cv;
-        std::vector<char> ready;
-        std::vector<std::exception_ptr> errs;
-        std::vector<std::thread> threads;
-        std::atomic<bool> failed{false};
-        void join() {
-            for (auto& th : threads)
-                if (th.joinable()) th.join();
-            threads.clear();
-        }
-    } bg;
-    try {
-        ZKM_HIP_CHECK(hipSetDevice(c->device));
-        if (nseg == 0) return;
-        // The allocator's free lists are exact-size, and the sizes of a call's blocks are those of its stacks: a call of another
-        // height would leave the blocks of BOTH heights cached (8 segments per call: 14.5 GB per context -- twice that after one
-        // call of 7).  The cache is returned to the device when the number of segments per call changes (a few hipFree / hipMalloc
-        // on the next call; calls of one height -- the steady state -- never get here).
-        // TWO heights may stay cached side by side: the waves of one oversized call have floor and ceil(nseg / nwaves) segments, and a
-        // caller that cuts k segments into calls (bench.py: 20 steps = 4, 4, 3, 3, 3, 3) alternates between two heights as well -- with
-        // one remembered height every such call trimmed and re-hipMalloc'ed its blocks.  A third height trims.
+    }
+    const zkm_table_input& input(const table_group& g, size_t k = 0) const { return io[g.segs[k]].tables[g.t]; }
+    // "segment S, table T: " for member k of group g, or (k = npos) for all of its members -- "segments a,b, table T: " when there are
+    // several.  S, a, b are positions in the caller's call.
+    std::string label(const table_group& g, size_t k = std::string::npos) const {
+        std::string who;
+        for (size_t i = 0; i < g.segs.size(); i++)
+            if (k == std::string::npos || i == k) who += (who.empty() ? "" : ",") + std::to_string(seg_base + g.segs[i]);
+        return (k == std::string::npos && g.segs.size() > 1 ? "segments " : "segment ") + who + ", table " + std::to_string(g.t) + ": ";
+    }
+
+    // The allocator's free lists are exact-size, and the sizes of a call's blocks are those of its stacks: a call of another
+    // height would leave the blocks of BOTH heights cached (8 segments per call: 14.5 GB per context -- twice that after one
+    // call of 7).  The cache is returned to the device when the number of segments per call changes (a few hipFree / hipMalloc
+    // on the next call; calls of one height -- the steady state -- never get here).
+    // TWO heights may stay cached side by side: the waves of one oversized call have floor and ceil(nseg / nwaves) segments, and a
+    // caller that cuts k segments into calls (bench.py: 20 steps = 4, 4, 3, 3, 3, 3) alternates between two heights as well -- with
+    // one remembered height every such call trimmed and re-hipMalloc'ed its blocks.  A third height trims.
+    void note_stack_height() {
         if (nseg != c->last_stack && nseg != c->prev_stack) {
             if (c->last_stack && c->prev_stack) {
                 c->trim();
@@ -777,7 +816,12 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
             c->prev_stack = c->last_stack;
         }
         c->last_stack = nseg;
-        const zkm_table_input* T0 = io[0].tables;
+    }
+
+    // validation, proof offsets, and the groups: per table, segments of equal height, at most max_stack (and 65535 stacked columns: a
+    // grid dimension of the transforms)
+    void plan() {
+        T0 = io[0].tables;
         for (size_t s = 0; s < nseg; s++) {
             if (!io[s].tables || !io[s].proofs || !io[s].challenges) throw std::runtime_error("zkm_prove_with_traces: null argument");
             for (size_t t = 0; t < ntables; t++) {
@@ -803,15 +847,14 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
                 throw std::runtime_error("zkm_prove_with_traces: the twelve tables must be given in the reference's Table enum order "
                                          "(all_stark.rs:96-110; see zkm_table_enum_index)");
         }
-        std::vector<std::vector<size_t>> offs(nseg, std::vector<size_t>(ntables + 1));
+        offs.assign(nseg, std::vector<size_t>(ntables + 1));
         for (size_t s = 0; s < nseg; s++)
             if (!zkm_all_proof_words(cfg, io[s].tables, ntables, ctls, sides, nctls, offs[s].data()) && ntables)
                 throw std::runtime_error("zkm_prove_with_traces: malformed cross-table lookups");
-        // the structure of every table's CtlZData list (no challenges yet): the number of auxiliary columns bounds the stack height
-        const auto tz0 = derive_zs(ntables, ctls, sides, nctls, cfg->num_challenges, nullptr);
-        // groups: per table, segments of equal height, at most max_stack (and 65535 stacked columns: a grid dimension of the transforms)
-        std::vector<std::vector<size_t>> where(ntables, std::vector<size_t>(nseg));     // group of (table, segment)
-        std::vector<std::vector<size_t>> pos(ntables, std::vector<size_t>(nseg));       // ... and the segment's position in it
+        // (the number of auxiliary columns bounds the stack height)
+        tz0 = derive_zs(ntables, ctls, sides, nctls, cfg->num_challenges, nullptr);
+        where.assign(ntables, std::vector<size_t>(nseg));
+        pos.assign(ntables, std::vector<size_t>(nseg));
         for (size_t t = 0; t < ntables; t++) {
             const size_t widest = std::max<size_t>(T0[t].ncols, tz0[t].naux + zkm_num_lookup_columns(T0[t].table_id, cfg));
             size_t cap = std::min<size_t>(std::max<size_t>(1, c->max_stack), ZKM_MAX_SEG);
@@ -832,129 +875,117 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
                 groups.push_back(std::move(g));
             }
         }
+    }
+
+    // "compute all trace commitments" prover.rs:144-167.  Host-resident traces are uploaded once, with their commitment, and the device
+    // copy is reused for the table's CTL / lookup columns -- as long as the copies kept this way stay within a quarter of the memory that
+    // is free now (all twelve commitments -- coefficients + 4x LDE + digests -- are alive at the same time, and a full-size Keccak table
+    // alone is 20 GB of values).  A trace beyond that budget is dropped after its commitment and uploaded again when its table is
+    // proven.  (A group of several segments always keeps its stacked copy: its kernels read ONE block.)
+    void commit_traces() {
         const size_t njobs = groups.size();
-        // "compute all trace commitments" prover.rs:144-167
-        std::vector<zkm_challenger> ch(nseg);
-        for (auto& x : ch) zkm_challenger_init(&x);
-        // Host-resident traces are uploaded once, with their commitment, and the device copy is reused for the table's CTL / lookup
-        // columns -- as long as the copies kept this way stay within a quarter of the memory that is free now (all twelve commitments
-        // -- coefficients + 4x LDE + digests -- are alive at the same time, and a full-size Keccak table alone is 20 GB of values).
-        // A trace beyond that budget is dropped after its commitment and uploaded again when its table is proven.  (A group of several
-        // segments always keeps its stacked copy: its kernels read ONE block.)
         size_t kept = 0, keep_limit = 0;
         bool have_limit = false;                       // (hipMemGetInfo is a driver round trip: only asked when a trace is host-resident)
-        std::vector<size_t> big, small;
-        {
-            zkm_prof_scope st(c, "stage/compute all trace commitments");
-            // The commitments do not depend on each other -- only the transcript does, and it starts after them (prover.rs:144-167 is a
-            // plain loop; :182-185 observes the caps in table order): run_on_lanes.
-            for (size_t j = 0; j < njobs; j++) {
-                table_group& g = groups[j];
-                const zkm_table_input& a = io[g.segs[0]].tables[g.t];
-                const size_t bytes = (a.ncols << g.log_n) * sizeof(gl_t) * g.segs.size();
-                g.host = false;
-                for (size_t s : g.segs) {
-                    const zkm_table_input& b = io[s].tables[g.t];
-                    g.host = g.host || b.columns || !zkm_is_device_ptr(b.trace);   // (column pointers are gathered into one device block)
-                }
-                if (g.segs.size() > 1) {
-                    g.keep = true;
-                } else {
-                    if (g.host && !have_limit) {
-                        size_t free_b = 0, total_b = 0;
-                        ZKM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-                        // (a quarter of what is free NOW -- shared with every other context of this process working on the same GPU, each of
-                        // which asks the same question on its own: divided by their number)
-                        keep_limit = free_b / 4 / (size_t)std::max(1, zkm_live_contexts());
-                        have_limit = true;
-                    }
-                    g.keep = g.host && kept + bytes <= keep_limit;
-                    if (g.keep) kept += bytes;
-                }
-                ((bytes << cfg->rate_bits) > ((size_t)1 << 30) ? big : small).push_back(j);
+        zkm_prof_scope st(c, "stage/compute all trace commitments");
+        // The commitments do not depend on each other -- only the transcript does, and it starts after them (prover.rs:144-167 is a
+        // plain loop; :182-185 observes the caps in table order): run_on_lanes.
+        for (size_t j = 0; j < njobs; j++) {
+            table_group& g = groups[j];
+            const size_t bytes = (input(g).ncols << g.log_n) * sizeof(gl_t) * g.segs.size();
+            g.host = false;
+            for (size_t k = 0; k < g.segs.size(); k++) {
+                const zkm_table_input& b = input(g, k);
+                g.host = g.host || b.columns || !zkm_is_device_ptr(b.trace);   // (column pointers are gathered into one device block)
             }
-            auto words = [&](size_t j) { return (T0[groups[j].t].ncols << groups[j].log_n) * groups[j].segs.size(); };
-            std::sort(small.begin(), small.end(), [&](size_t a, size_t b) { return words(a) > words(b); });
-            std::vector<double> cost(njobs, 0.0);
-            for (size_t j = 0; j < njobs; j++)
-                cost[j] = commit_cost_estimate(c, T0[groups[j].t].ncols, groups[j].log_n, cfg->rate_bits, groups[j].segs.size());
-            run_on_lanes(c, big, small, cost, [&](zkm_ctx* w, size_t j) {
-                table_group& g = groups[j];
-                const size_t W = T0[g.t].ncols, n = (size_t)1 << g.log_n, G = g.segs.size();
-                if (g.keep && !g.d_traces) {
-                    g.d_traces = (gl_t*)w->alloc(G * W * n * sizeof(gl_t));
-                    g.d_owner = w;
+            if (g.segs.size() > 1) {
+                g.keep = true;
+            } else {
+                if (g.host && !have_limit) {
+                    size_t free_b = 0, total_b = 0;
+                    ZKM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+                    // (a quarter of what is free NOW -- shared with every other context of this process working on the same GPU, each of
+                    // which asks the same question on its own: divided by their number)
+                    keep_limit = free_b / 4 / (size_t)std::max(1, zkm_live_contexts());
+                    have_limit = true;
                 }
-                if (G == 1) {
-                    const zkm_table_input& a = io[g.segs[0]].tables[g.t];
-                    g.commit = zkm_batch_commit_values_keep(w, a.trace, W, g.log_n, cfg->rate_bits, cfg->cap_height, g.d_traces, a.columns);
-                    return;
-                }
-                zkm_batch* b = new zkm_batch();
-                b->ctx = w; b->ncols = W; b->nseg = G; b->log_n = g.log_n; b->rate_bits = cfg->rate_bits; b->cap_height = cfg->cap_height;
-                g.commit = b;      // (owned from here on: freed on every exit path)
-                if (g.uploaded) {  // its traces came up on the copy stream while the worker's earlier groups were transformed and hashed
-                    ZKM_HIP_CHECK(hipStreamWaitEvent(w->stream, g.uploaded, 0));
-                    zkm_launch_canon(w, g.d_traces, G * W * n);
-                    zkm_batch_build(b, g.d_traces, true);
-                    return;
-                }
-                bool any_cols = false;
-                for (size_t s : g.segs) any_cols = any_cols || io[s].tables[g.t].columns;
-                if (any_cols) {    // one pointer per column of every segment
-                    std::vector<const uint64_t*> cols(G * W);
-                    for (size_t k = 0; k < G; k++) {
-                        const zkm_table_input& a = io[g.segs[k]].tables[g.t];
-                        for (size_t i = 0; i < W; i++) cols[k * W + i] = a.columns ? a.columns[i] : a.trace + i * n;
-                    }
-                    zkm_batch_build(b, nullptr, true, g.d_traces, cols.data());
-                } else {
-                    std::vector<const uint64_t*> srcs(G);
-                    for (size_t k = 0; k < G; k++) srcs[k] = io[g.segs[k]].tables[g.t].trace;
-                    zkm_batch_build(b, nullptr, true, g.d_traces, nullptr, srcs.data());
-                }
-            }, [&](zkm_ctx* w, const std::vector<size_t>& jobs, const call_entry& entry) {
-                // Host-resident traces of the worker's stacks (the deployed input: generate_traces leaves them in host memory) go up on
-                // the worker's COPY stream, all of them queued now, each followed by an event: the transforms and hashing of a group
-                // overlap the uploads of the groups behind it (0.3 GB per 2^16-cycle segment over PCIe).  Pinned (zkm_host_alloc /
-                // zkm_host_register) sources make the copies asynchronous; pageable ones are staged by the runtime inside the call.
-                for (size_t j : jobs) {
-                    table_group& g = groups[j];
-                    if (!(g.host && g.keep && g.segs.size() > 1)) continue;
-                    const size_t W = T0[g.t].ncols, n = (size_t)1 << g.log_n, G = g.segs.size();
-                    if (!w->copy_stream) {
-                        hipStream_t cs = nullptr;
-                        ZKM_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-                        {
-                            std::lock_guard<std::mutex> lk(w->alloc_mu);
-                            w->copy_stream = cs;
-                        }
-                        entry.order(cs);   // (a column may be a staged device matrix: the gather reads it after its upload)
-                    }
-                    g.d_traces = (gl_t*)w->alloc(G * W * n * sizeof(gl_t));
-                    g.d_owner = w;
-                    for (size_t k = 0; k < G; k++) {
-                        const zkm_table_input& a = io[g.segs[k]].tables[g.t];
-                        gl_t* dst = g.d_traces + k * W * n;
-                        if (a.columns)
-                            for (size_t i = 0; i < W; i++)
-                                ZKM_HIP_CHECK(hipMemcpyAsync(dst + i * n, a.columns[i], n * sizeof(gl_t), hipMemcpyDefault, w->copy_stream));
-                        else
-                            ZKM_HIP_CHECK(hipMemcpyAsync(dst, a.trace, W * n * sizeof(gl_t), hipMemcpyDefault, w->copy_stream));
-                    }
-                    g.uploaded = w->get_event();
-                    g.uploaded_on = w;
-                    ZKM_HIP_CHECK(hipEventRecord(g.uploaded, w->copy_stream));
-                }
-            });
-            for (table_group& g : groups)      // (every upload has been waited for by its group's commitment: the events go back)
-                if (g.uploaded) {
-                    g.uploaded_on->event_pool.push_back(g.uploaded);
-                    g.uploaded = nullptr;
-                }
+                g.keep = g.host && kept + bytes <= keep_limit;
+                if (g.keep) kept += bytes;
+            }
+            ((bytes << cfg->rate_bits) > ((size_t)1 << 30) ? big : small).push_back(j);
         }
+        auto words = [&](size_t j) { return (T0[groups[j].t].ncols << groups[j].log_n) * groups[j].segs.size(); };
+        std::sort(small.begin(), small.end(), [&](size_t a, size_t b) { return words(a) > words(b); });
+        std::vector<double> cost(njobs, 0.0);
+        for (size_t j = 0; j < njobs; j++)
+            cost[j] = commit_cost_estimate(c, T0[groups[j].t].ncols, groups[j].log_n, cfg->rate_bits, groups[j].segs.size());
+        run_on_lanes(c, big, small, cost, [&](zkm_ctx* w, size_t j) { commit_group(w, j); },
+                     [&](zkm_ctx* w, const std::vector<size_t>& jobs, const call_entry& entry) { upload_stacks(w, jobs, entry); });
+        for (table_group& g : groups) g.uploaded.reset();   // (every upload has been waited for by its group's commitment)
+    }
+    // Host-resident traces of the worker's stacks (the deployed input: generate_traces leaves them in host memory) go up on the worker's
+    // COPY stream, all of them queued now, each followed by an event: the transforms and hashing of a group overlap the uploads of the
+    // groups behind it (0.3 GB per 2^16-cycle segment over PCIe).  Pinned (zkm_host_alloc / zkm_host_register) sources make the copies
+    // asynchronous; pageable ones are staged by the runtime inside the call.
+    void upload_stacks(zkm_ctx* w, const std::vector<size_t>& jobs, const call_entry& entry) {
+        for (size_t j : jobs) {
+            table_group& g = groups[j];
+            if (!(g.host && g.keep && g.segs.size() > 1)) continue;
+            const size_t W = T0[g.t].ncols, n = (size_t)1 << g.log_n, G = g.segs.size();
+            if (!w->copy_stream) entry.order(w->ensure_copy_stream());   // (a column may be a staged device matrix: the gather reads it after its upload)
+            g.traces = zkm_scratch(w, G * W * n * sizeof(gl_t));
+            for (size_t k = 0; k < G; k++) {
+                const zkm_table_input& a = input(g, k);
+                gl_t* dst = g.traces.as<gl_t>() + k * W * n;
+                if (a.columns)
+                    for (size_t i = 0; i < W; i++)
+                        ZKM_HIP_CHECK(hipMemcpyAsync(dst + i * n, a.columns[i], n * sizeof(gl_t), hipMemcpyDefault, w->copy_stream));
+                else
+                    ZKM_HIP_CHECK(hipMemcpyAsync(dst, a.trace, W * n * sizeof(gl_t), hipMemcpyDefault, w->copy_stream));
+            }
+            g.uploaded = zkm_event(w);
+            g.uploaded.record(w->copy_stream);
+        }
+    }
+    void commit_group(zkm_ctx* w, size_t j) {
+        table_group& g = groups[j];
+        const size_t W = T0[g.t].ncols, n = (size_t)1 << g.log_n, G = g.segs.size();
+        if (g.keep && !g.traces.p) g.traces = zkm_scratch(w, G * W * n * sizeof(gl_t));
+        gl_t* const d_traces = g.traces.as<gl_t>();
+        if (G == 1) {
+            const zkm_table_input& a = input(g);
+            g.commit.reset(zkm_batch_commit_values_keep(w, a.trace, W, g.log_n, cfg->rate_bits, cfg->cap_height, d_traces, a.columns));
+            return;
+        }
+        g.commit = zkm_batch_new(w, W, G, g.log_n, cfg->rate_bits, cfg->cap_height);
+        if (g.uploaded.e) {  // its traces came up on the copy stream while the worker's earlier groups were transformed and hashed
+            ZKM_HIP_CHECK(hipStreamWaitEvent(w->stream, g.uploaded.e, 0));
+            zkm_launch_canon(w, d_traces, G * W * n);
+            zkm_batch_build(g.commit.get(), d_traces, true);
+            return;
+        }
+        bool any_cols = false;
+        for (size_t k = 0; k < G; k++) any_cols = any_cols || input(g, k).columns;
+        if (any_cols) {    // one pointer per column of every segment
+            std::vector<const uint64_t*> cols(G * W);
+            for (size_t k = 0; k < G; k++) {
+                const zkm_table_input& a = input(g, k);
+                for (size_t i = 0; i < W; i++) cols[k * W + i] = a.columns ? a.columns[i] : a.trace + i * n;
+            }
+            zkm_batch_build(g.commit.get(), nullptr, true, d_traces, cols.data());
+        } else {
+            std::vector<const uint64_t*> srcs(G);
+            for (size_t k = 0; k < G; k++) srcs[k] = input(g, k).trace;
+            zkm_batch_build(g.commit.get(), nullptr, true, d_traces, nullptr, srcs.data());
+        }
+    }
+
+    // all trace caps in table order, the public values, the CTL challenges (prover.rs:182-190); then per group its segments' CtlZData
+    // lists one after the other (same structure, own challenges), and the betas of the CTL challenges as lookup challenges (:468-474)
+    void draw_ctl_challenges() {
         const size_t C4 = (size_t)4 << cfg->cap_height;
         const unsigned nch = cfg->num_challenges;
+        ch.resize(nseg);
+        for (auto& x : ch) zkm_challenger_init(&x);
         for (size_t s = 0; s < nseg; s++) {
             for (size_t t = 0; t < ntables; t++)   // :182-185
                 zkm_challenger_observe(&ch[s], groups[where[t][s]].commit->cap.data() + pos[t][s] * C4, C4);
@@ -966,19 +997,100 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
         }
         std::vector<std::vector<table_zs>> tz(nseg);
         for (size_t s = 0; s < nseg; s++) tz[s] = derive_zs(ntables, ctls, sides, nctls, nch, io[s].challenges);
-        // per group: its segments' CtlZData lists one after the other (same structure, own challenges), and the betas of the CTL
-        // challenges as lookup challenges (prover.rs:468-474)
-        std::vector<std::vector<zkm_ctl_z>> gzs(njobs);
-        std::vector<std::vector<uint64_t>> glookup(njobs);
-        for (size_t j = 0; j < njobs; j++)
+        gzs.assign(groups.size(), {});
+        glookup.assign(groups.size(), {});
+        for (size_t j = 0; j < groups.size(); j++)
             for (size_t s : groups[j].segs) {
                 const table_zs& z = tz[s][groups[j].t];
                 gzs[j].insert(gzs[j].end(), z.zs.begin(), z.zs.end());
                 for (unsigned k = 0; k < nch; k++) glookup[j].push_back(io[s].challenges[2 * k]);
             }
-        // "compute CTL data" :191-200 and each table's "compute auxiliary polynomials commitment" :511-522 (with its "compute lookup helper
-        // columns" :475-493) depend on the CTL challenges only, not on the transcript of the table proofs: all tables' auxiliary
-        // commitments are built now, side by side (run_on_lanes).  The transcript then observes them in table order, below.
+    }
+
+    // "compute CTL data" :191-200 and the table's "compute auxiliary polynomials commitment" :511-522 (with its "compute lookup helper
+    // columns" :475-493) for group j on worker w
+    void build_aux(zkm_ctx* w, size_t j) {
+        table_group& g = groups[j];
+        const size_t t = g.t, G = g.segs.size();
+        if (tz0[t].naux == 0) return;   // ("No CTL?" -- reported by prove_single_table in table order, prover.rs:509)
+        const size_t n = (size_t)1 << g.log_n, W = T0[t].ncols;
+        const size_t NL = zkm_num_lookup_columns(T0[t].table_id, cfg), A = NL + tz0[t].naux;
+        const unsigned nch = cfg->num_challenges;
+        ctl_dev_owner own;
+        own.upload(w, T0[t].ctl, gzs[j].data(), tz0[t].ids.data(), tz0[t].zs.size(), false, W, G);
+        const zkm_table_input& a0 = input(g);
+        const gl_t* d_trace = g.traces.p ? g.traces.as<gl_t>() : a0.trace;
+        zkm_scratch again(w, (!g.traces.p && g.host) ? W * n * sizeof(gl_t) : 8);
+        if (!g.traces.p && g.host) {   // (one segment, over the keep budget: second upload)
+            gl_t* d = again.as<gl_t>();
+            if (a0.columns)
+                for (size_t i = 0; i < W; i++) ZKM_HIP_CHECK(hipMemcpyAsync(d + i * n, a0.columns[i], n * sizeof(gl_t), hipMemcpyDefault, w->stream));
+            else
+                ZKM_HIP_CHECK(hipMemcpyAsync(d, a0.trace, W * n * sizeof(gl_t), hipMemcpyHostToDevice, w->stream));
+            zkm_launch_canon(w, d, W * n);   // (as zkm_batch_build does for the copies it keeps)
+            d_trace = d;
+        }
+        zkm_scratch d_all(w, G * A * n * sizeof(gl_t));   // per segment [lookup helper columns | CTL helper columns and Zs], prover.rs:497-508
+        try {
+            {
+                zkm_prof_scope st(w, "stage/compute CTL data");
+                zkm_ctl_data_device(w, own, d_trace, g.log_n, d_all.as<gl_t>() + NL * n, G, W * n, A * n);
+            }
+            if (NL) {
+                zkm_prof_scope st(w, "stage/compute lookup helper columns");
+                zkm_table_lookup_columns_device(w, T0[t].table_id, glookup[j].data(), nch, d_trace, n, d_all.as<gl_t>(), G, W * n, A * n);
+            }
+        } catch (const zkm_segment_error& e) {   // (a stack names the position in the group: the caller wants ITS segment and the table)
+            if (nseg == 1 && seg_base == 0) throw std::runtime_error(e.what());
+            throw std::runtime_error(label(g, e.seg) + e.what());
+        }
+        zkm_prof_scope st(w, "stage/compute auxiliary polynomials commitment");
+        g.aux = zkm_batch_new(w, A, G, g.log_n, cfg->rate_bits, cfg->cap_height);
+        zkm_batch_build(g.aux.get(), d_all.as<uint64_t>(), true);
+        w->sync();             // d_all / `again` go back to the lane's allocator when this returns
+        // the device copy of the traces has served its purpose (commitment, CTL data, lookup columns): back to its owner's allocator
+        // NOW, not after the last table proof (nothing reads it any more and w's stream is drained)
+        g.traces.reset();
+    }
+
+    // "compute all proofs given commitments" :234-438 for group j: tables in order, one transcript per segment
+    void prove_group(size_t j) {
+        table_group& g = groups[j];
+        const size_t t = g.t;
+        try {
+            if (!g.aux) throw std::runtime_error("No CTL? aux column count does not match the CTL description");  // prover.rs:509
+            std::vector<zkm_challenger> local(g.segs.size());
+            std::vector<zkm_challenger*> chs(g.segs.size());
+            std::vector<uint64_t*> proofs(g.segs.size());
+            for (size_t k = 0; k < g.segs.size(); k++) {
+                local[k] = ch[g.segs[k]];
+                chs[k] = &local[k];
+                proofs[k] = io[g.segs[k]].proofs + offs[g.segs[k]][t];
+            }
+            zkm_prove_single_table_aux(c, T0[t].table_id, cfg, T0[t].ncols, g.log_n, g.commit.get(), g.aux.get(), tz0[t].naux, T0[t].ctl,
+                                       gzs[j].data(), tz0[t].ids.data(), tz0[t].zs.size(), glookup[j].data(), chs, proofs);
+            for (size_t k = 0; k < g.segs.size(); k++) ch[g.segs[k]] = local[k];
+        } catch (const zkm_segment_error& e) {
+            throw std::runtime_error(label(g, e.seg) + e.what());
+        } catch (const std::exception& e) {
+            if (nseg == 1 && seg_base == 0) throw std::runtime_error("table " + std::to_string(t) + ": " + e.what());
+            // a stacked group fails as a whole: name its members (positions in the caller's call) next to the table
+            throw std::runtime_error(label(g) + e.what());
+        }
+    }
+
+    // The auxiliary commitments depend on the CTL challenges only, not on the transcript of the table proofs; the transcript observes
+    // them in table order, inside each table's proof.
+    void prove_tables() {
+        const size_t njobs = groups.size();
+        auto build = [&](zkm_ctx* w, size_t j) { build_aux(w, j); };
+        const size_t bg_lanes =
+            (big.empty() && c->aux_pipeline && njobs >= 3) ? std::min<size_t>(std::max<size_t>(1, c->commit_lanes), njobs - 1) - 1 : 0;
+        if (bg_lanes) {        // a segment of short tables: the lanes build later tables' auxiliary commitments behind the proofs
+            run_behind(c, bg_lanes, njobs, build, [&](size_t j) { prove_group(j); });
+            return;
+        }
+        // all tables' auxiliary commitments first, side by side (run_on_lanes), then the proofs
         std::vector<double> aux_cost(njobs, 0.0);          // CTL data + lookup columns read the trace once; then an `naux`-column commitment
         for (size_t j = 0; j < njobs; j++) {
             const size_t t = groups[j].t;
@@ -986,146 +1098,24 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
                                                groups[j].segs.size()) +
                           (double)((T0[t].ncols << groups[j].log_n) * groups[j].segs.size()) * 1e-10;
         }
-        auto aux_job = [&](zkm_ctx* w, size_t j) {
-            table_group& g = groups[j];
-            const size_t t = g.t, G = g.segs.size();
-            if (tz0[t].naux == 0) return;   // ("No CTL?" -- reported by prove_single_table in table order, prover.rs:509)
-            const size_t n = (size_t)1 << g.log_n, W = T0[t].ncols;
-            const size_t NL = zkm_num_lookup_columns(T0[t].table_id, cfg), A = NL + tz0[t].naux;
-            ctl_dev_owner own;
-            own.upload(w, T0[t].ctl, gzs[j].data(), tz0[t].ids.data(), tz0[t].zs.size(), false, W, G);
-            const zkm_table_input& a0 = io[g.segs[0]].tables[t];
-            const gl_t* d_trace = g.d_traces ? g.d_traces : a0.trace;
-            zkm_scratch again(w, (!g.d_traces && g.host) ? W * n * sizeof(gl_t) : 8);
-            if (!g.d_traces && g.host) {   // (one segment, over the keep budget: second upload)
-                gl_t* d = again.as<gl_t>();
-                if (a0.columns)
-                    for (size_t i = 0; i < W; i++) ZKM_HIP_CHECK(hipMemcpyAsync(d + i * n, a0.columns[i], n * sizeof(gl_t), hipMemcpyDefault, w->stream));
-                else
-                    ZKM_HIP_CHECK(hipMemcpyAsync(d, a0.trace, W * n * sizeof(gl_t), hipMemcpyHostToDevice, w->stream));
-                zkm_launch_canon(w, d, W * n);   // (as zkm_batch_build does for the copies it keeps)
-                d_trace = d;
-            }
-            zkm_scratch d_all(w, G * A * n * sizeof(gl_t));   // per segment [lookup helper columns | CTL helper columns and Zs], prover.rs:497-508
-            try {
-                {
-                    zkm_prof_scope st(w, "stage/compute CTL data");
-                    zkm_ctl_data_device(w, own, d_trace, g.log_n, d_all.as<gl_t>() + NL * n, G, W * n, A * n);
-                }
-                if (NL) {
-                    zkm_prof_scope st(w, "stage/compute lookup helper columns");
-                    zkm_table_lookup_columns_device(w, T0[t].table_id, glookup[j].data(), nch, d_trace, n, d_all.as<gl_t>(), G, W * n, A * n);
-                }
-            } catch (const zkm_segment_error& e) {   // (a stack names the position in the group: the caller wants ITS segment and the table)
-                if (nseg == 1 && seg_base == 0) throw std::runtime_error(e.what());
-                throw std::runtime_error("segment " + std::to_string(seg_base + g.segs[e.seg]) + ", table " + std::to_string(t) + ": " + e.what());
-            }
-            zkm_prof_scope st(w, "stage/compute auxiliary polynomials commitment");
-            zkm_batch* ab = new zkm_batch();
-            ab->ctx = w; ab->ncols = A; ab->nseg = G; ab->log_n = g.log_n; ab->rate_bits = cfg->rate_bits; ab->cap_height = cfg->cap_height;
-            g.aux = ab;            // (owned from here on: freed with the others on every exit path)
-            zkm_batch_build(ab, d_all.as<uint64_t>(), true);
-            w->sync();             // d_all / `again` go back to the lane's allocator when this returns
-            // the device copy of the traces has served its purpose (commitment, CTL data, lookup columns): back to its owner's allocator
-            // NOW, not after the last table proof (nothing reads it any more and w's stream is drained)
-            if (g.d_traces) {
-                (g.d_owner ? g.d_owner : c)->release(g.d_traces);
-                g.d_traces = nullptr;
-            }
-        };
-        auto prove_group = [&](size_t j) {   // "compute all proofs given commitments" :234-438: tables in order, one transcript per segment
-            table_group& g = groups[j];
-            const size_t t = g.t;
-            try {
-                if (!g.aux) throw std::runtime_error("No CTL? aux column count does not match the CTL description");  // prover.rs:509
-                std::vector<zkm_challenger> local(g.segs.size());
-                std::vector<zkm_challenger*> chs(g.segs.size());
-                std::vector<uint64_t*> proofs(g.segs.size());
-                for (size_t k = 0; k < g.segs.size(); k++) {
-                    local[k] = ch[g.segs[k]];
-                    chs[k] = &local[k];
-                    proofs[k] = io[g.segs[k]].proofs + offs[g.segs[k]][t];
-                }
-                zkm_prove_single_table_aux(c, T0[t].table_id, cfg, T0[t].ncols, g.log_n, g.commit, g.aux, tz0[t].naux, T0[t].ctl, gzs[j].data(),
-                                           tz0[t].ids.data(), tz0[t].zs.size(), glookup[j].data(), chs, proofs);
-                for (size_t k = 0; k < g.segs.size(); k++) ch[g.segs[k]] = local[k];
-            } catch (const zkm_segment_error& e) {
-                throw std::runtime_error("segment " + std::to_string(seg_base + g.segs[e.seg]) + ", table " + std::to_string(t) + ": " + e.what());
-            } catch (const std::exception& e) {
-                if (nseg == 1 && seg_base == 0) throw std::runtime_error("table " + std::to_string(t) + ": " + e.what());
-                // a stacked group fails as a whole: name its members (positions in the caller's call) next to the table
-                std::string who = g.segs.size() == 1 ? "segment " : "segments ";
-                for (size_t k = 0; k < g.segs.size(); k++) who += (k ? "," : "") + std::to_string(seg_base + g.segs[k]);
-                throw std::runtime_error(who + ", table " + std::to_string(t) + ": " + e.what());
-            }
-        };
-        // (groups are numbered table by table: job order is proof order)
-        const size_t bg_lanes =
-            (big.empty() && c->aux_pipeline && njobs >= 3) ? std::min<size_t>(std::max<size_t>(1, c->commit_lanes), njobs - 1) - 1 : 0;
-        if (bg_lanes == 0) {
-            run_on_lanes(c, big, small, aux_cost, aux_job);
-            drop_traces();         // the device copies of the traces have served their purpose (commitment, CTL data, lookup columns)
-            for (size_t j = 0; j < njobs; j++) prove_group(j);
-        } else {
-            // A segment of short tables (no table fills the GPU on its own): the table proofs are ONE chain of latency-bound steps on
-            // the context's stream, and the auxiliary commitment of a LATER table is not needed before that table's turn -- the lanes
-            // build them behind the proofs of the earlier tables (dealt to the lanes in proof order, the same deal every segment, so
-            // that each lane finds its blocks in its own allocator cache; the context builds table 0's and starts proving).  The
-            // transcript is what it was: every cap is observed inside its table's proof, in table order.
-            c->ensure_lanes(bg_lanes);
-            bg.ready.assign(njobs, 0);
-            bg.errs.assign(bg_lanes, nullptr);
-            const call_entry entry(c);     // (a lane may not have been a worker of the commitments: it reads staged traces too)
-            struct stop_and_join {     // (an exception on this thread unwinds what the lanes refer to: they are stopped and joined first)
-                background& b;
-                ~stop_and_join() {
-                    if (!b.threads.empty()) b.failed.store(true);
-                    b.join();
-                }
-            } guard{bg};
-            for (size_t k = 0; k < bg_lanes; k++)
-                bg.threads.emplace_back([&, k]() {
-                    zkm_ctx* w = c->lanes[k];
-                    try {
-                        ZKM_HIP_CHECK(hipSetDevice(c->device));
-                        entry.order(w);
-                        for (size_t j = 1 + k; j < njobs; j += bg_lanes) {
-                            if (bg.failed.load()) break;
-                            aux_job(w, j);
-                            std::lock_guard<std::mutex> g(bg.mu);
-                            bg.ready[j] = 1;
-                            bg.cv.notify_all();
-                        }
-                    } catch (...) {
-                        bg.errs[k] = std::current_exception();
-                        bg.failed.store(true);
-                    }
-                    std::lock_guard<std::mutex> g(bg.mu);      // (whatever happened: nobody waits for this lane any more)
-                    for (size_t j = 1 + k; j < njobs; j += bg_lanes) bg.ready[j] = 1;
-                    bg.cv.notify_all();
-                });
-            aux_job(c, 0);
-            for (size_t j = 0; j < njobs; j++) {
-                if (j) {
-                    zkm_prof_scope st(c, "stage/wait for auxiliary polynomials commitment");
-                    std::unique_lock<std::mutex> g(bg.mu);
-                    bg.cv.wait(g, [&] { return bg.ready[j] != 0; });
-                }
-                if (bg.failed.load()) break;
-                prove_group(j);
-            }
-            bg.join();
-            for (auto& e : bg.errs)
-                if (e) std::rethrow_exception(e);
-            drop_traces();
-        }
-    } catch (...) {
-        bg.failed.store(true);
-        bg.join();
-        drop_all();
-        throw;
+        run_on_lanes(c, big, small, aux_cost, build);
+        (void)hipStreamSynchronize(c->stream);   // the device copies of the traces have served their purpose (commitment, CTL data, lookup columns)
+        for (table_group& g : groups) g.traces.reset();
+        for (size_t j = 0; j < njobs; j++) prove_group(j);
     }
-    drop_all();
+};
+
+// (seg_base: position of io[0] in the caller's call -- the waves of an oversized call; only error messages use it)
+static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const seg_io* io, size_t ntables,
+                                const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t seg_base = 0) {
+    lockstep_call call{c, cfg, nseg, io, ntables, ctls, sides, nctls, seg_base};
+    ZKM_HIP_CHECK(hipSetDevice(c->device));
+    if (nseg == 0) return;
+    call.note_stack_height();
+    call.plan();
+    call.commit_traces();
+    call.draw_ctl_challenges();
+    call.prove_tables();
 }
 
 // A call may hold more segments than fit in HBM together (every commitment of every segment of a lock-step call is alive until its

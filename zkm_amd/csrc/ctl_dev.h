@@ -53,8 +53,7 @@ __device__ __forceinline__ gl_t ctl_combine(const ctl_dev& d, const zkm_colset& 
 
 // host-side owner of the device copy of a description
 struct ctl_dev_owner {
-    zkm_ctx* c = nullptr;
-    void* blob = nullptr;
+    zkm_scratch blob;
     std::vector<zkm_ctl_z> h_zs;  // host copy of the CtlZData list (launch planning)
     ctl_dev d{};
     size_t naux = 0;

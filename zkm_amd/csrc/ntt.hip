@@ -555,13 +555,11 @@ __global__ __launch_bounds__(1024) void k_ntt_small(ntt_small_args p) {
     }
 }
 static bool ntt_small_ok(unsigned log_n) { return log_n >= 9 && log_n <= 13; }
-template <typename K>
-static void ntt_allow_big_lds(zkm_ctx* c, K kernel, std::atomic<uint64_t>& done);
 static void launch_ntt_small(zkm_ctx* c, const ntt_small_args& a, size_t ncols, unsigned ncoset, const char* name) {
     static std::atomic<uint64_t> lds_ok{0};
     const unsigned n = 1u << a.log_n;
     zkm_prof_scope ps(c, name);
-    if (2 * (size_t)n * sizeof(gl_t) > 64 * 1024) ntt_allow_big_lds(c, k_ntt_small, lds_ok);
+    if (2 * (size_t)n * sizeof(gl_t) > 64 * 1024) ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_ntt_small, lds_ok));
     hipLaunchKernelGGL(k_ntt_small, dim3((unsigned)ncols, ncoset), dim3(n >> 3), 2 * (size_t)n * sizeof(gl_t), c->stream, a);
     ZKM_HIP_CHECK(hipGetLastError());
 }
@@ -590,20 +588,10 @@ static ntt_plan make_plan(unsigned L) {
     return pl;
 }
 
-// hipFuncSetAttribute is per device: remember which devices have the dynamic-LDS limit of a kernel raised (one bit per device; a
-// process may hold contexts on several GPUs, and several host threads may get here at once -- setting it twice is harmless)
-template <typename K>
-static void ntt_allow_big_lds(zkm_ctx* c, K kernel, std::atomic<uint64_t>& done) {
-    const uint64_t bit = (uint64_t)1 << (c->device & 63);
-    if (done.load(std::memory_order_acquire) & bit) return;
-    ZKM_HIP_CHECK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    done.fetch_or(bit, std::memory_order_release);
-}
-
 template <int S, bool IN_A, bool OUT_A, int PRE, int POST, bool ZP = false, bool PF = true>
 static void launch_pass_t(zkm_ctx* c, const ntt_pass_args& a, size_t ntiles) {
     static std::atomic<uint64_t> lds_ok{0};
-    ntt_allow_big_lds(c, k_ntt_pass<S, IN_A, OUT_A, PRE, POST, ZP, PF>, lds_ok);
+    ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_ntt_pass<S, IN_A, OUT_A, PRE, POST, ZP, PF>, lds_ok));
     int T = 1 << a.log_T;
     size_t shmem = ((size_t)1 << S) * a.tp * sizeof(gl_t);
     dim3 grid((unsigned)(ntiles * (a.ncoset > 1 ? a.ncoset : 1)), (a.ncols + a.cpb - 1) / a.cpb), block((unsigned)(((1 << S) >> 3) * T));
@@ -1012,7 +1000,7 @@ template <bool INV, bool PERM>
 static void launch_blk12(zkm_ctx* c, const ntt_big_args& a) {
     static std::atomic<uint64_t> lds_ok{0};
     const size_t shmem = (8 * 576 + 7 * 64 + 7 * 8) * sizeof(gl_t);
-    ntt_allow_big_lds(c, k_ntt_blk12<INV, PERM>, lds_ok);
+    ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_ntt_blk12<INV, PERM>, lds_ok));
     uint32_t total = a.ncols * a.blocks_per_col;
     uint32_t grid = total < (uint32_t)c->num_cus * 12 ? total : (uint32_t)c->num_cus * 12;
     hipLaunchKernelGGL((k_ntt_blk12<INV, PERM>), dim3(grid), dim3(512), shmem, c->stream, a);
@@ -1022,7 +1010,7 @@ template <int SA>
 static void launch_big_t(zkm_ctx* c, const ntt_big_args& a) {
     static std::atomic<uint64_t> lds_ok{0};
     size_t shmem = ((size_t)1 << SA) * 65 * sizeof(gl_t);
-    ntt_allow_big_lds(c, k_ntt_big<SA>, lds_ok);
+    ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_ntt_big<SA>, lds_ok));
     uint32_t total = a.ncols * a.blocks_per_col;
     uint32_t grid = total < (uint32_t)c->num_cus * 8 ? total : (uint32_t)c->num_cus * 8;
     hipLaunchKernelGGL((k_ntt_big<SA>), dim3(grid), dim3((1u << SA) * 8), shmem, c->stream, a);
@@ -1277,7 +1265,7 @@ __global__ __launch_bounds__(512, 4) void k_lde_upper(lde_upper_args p) {
 template <int S, bool RUNS = false>
 static void launch_lde_upper_t(zkm_ctx* c, const lde_upper_args& a) {
     static std::atomic<uint64_t> lds_ok{0};
-    ntt_allow_big_lds(c, k_lde_upper<S, RUNS>, lds_ok);
+    ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_lde_upper<S, RUNS>, lds_ok));
     const size_t shmem = 2 * (4096 + (4096 >> S)) * sizeof(gl_t);             // two images of the 2^S x 2^(12-S) tile (+ one pad word per column)
     const uint32_t ntiles = (1u << a.S2) >> (12 - S);
     dim3 grid(ntiles * 4, (a.ncols + a.cpb - 1) / a.cpb);

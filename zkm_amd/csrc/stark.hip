@@ -353,7 +353,8 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
     alpha_args d_alphas{};
     for (size_t sg = 0; sg < nseg; sg++)
         for (size_t a = 0; a < nalphas && a < 2; a++) d_alphas.v[2 * sg + a] = alphas_host[sg * nalphas + a];
-    gl_t* d_vals = (gl_t*)c->alloc(nseg * nalphas * size * sizeof(gl_t));
+    zkm_scratch vals(c, nseg * nalphas * size * sizeof(gl_t));
+    gl_t* const d_vals = vals.as<gl_t>();
     {
         static const char* const names[] = {"quotient_poseidon", "quotient_logic", "quotient_keccak_sponge", "quotient_keccak", "quotient_memory", "quotient_poseidon_sponge", "quotient_sha_extend", "quotient_sha_extend_sponge", "quotient_sha_compress",
                                             "quotient_sha_compress_sponge", "quotient_arithmetic", "quotient_cpu"};
@@ -450,8 +451,9 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
                 hipLaunchKernelGGL((k_quotient_ctl<2>), grid, block, 0, c->stream, trace->lde, aux->lde, lde_bits, ctl, NL, d_alphas, wpow, gn, zh0, zh1,
                                    last, w_n, n_inv, d_vals, trace_seg, aux_seg);
         } else {
-            ctl_chunk* d_plan = (ctl_chunk*)c->alloc(plan.size() * sizeof(ctl_chunk));
-            gl_t* d_tmp = (gl_t*)c->alloc(nseg * plan.size() * nalphas * size * sizeof(gl_t));
+            zkm_scratch_list tmp(c);
+            ctl_chunk* d_plan = tmp.alloc<ctl_chunk>(plan.size() * sizeof(ctl_chunk));
+            gl_t* d_tmp = tmp.alloc<gl_t>(nseg * plan.size() * nalphas * size * sizeof(gl_t));
             c->upload(d_plan, plan.data(), plan.size() * sizeof(ctl_chunk));
             dim3 grid2((unsigned)((size + 255) / 256), (unsigned)plan.size(), z);
             if (nalphas == 1) {
@@ -466,20 +468,16 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
             ZKM_HIP_CHECK(hipGetLastError());
             // (no host sync: upload() has copied `plan` into the pinned ring -- or waited itself if it was too large for it -- and the
             // blocks released here are only reused by later work on this stream)
-            c->release(d_plan);
-            c->release(d_tmp);
         }
         ZKM_HIP_CHECK(hipGetLastError());
     }
     if (check) {
         ZKM_HIP_CHECK(hipMemcpyAsync(d_out, d_vals, nseg * nalphas * size * sizeof(gl_t), hipMemcpyDeviceToDevice, c->stream));
-        c->release(d_vals);
         return;
     }
     // coset_ifft(g) of each challenge's evaluations (prover.rs:784-788)
     zkm_ntt_natural(c, d_vals, d_out, nseg * nalphas, size, size, log_q, true, GL_GENERATOR);
-    c->release(d_vals);  // stream-ordered reuse: no host sync needed
-}
+}   // (`vals` goes back: stream-ordered reuse, no host sync needed)
 
 // ------------------------------------------------------------------ K10: openings
 // partial[col][chunk] = sum_{k in chunk} c_k z^(k - chunk_start) for z in {zeta, g*zeta}, plus the plain sum (evaluation
@@ -1125,7 +1123,7 @@ static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_
     const size_t L = m.size();
     std::vector<seg_batches> lv(L);
     std::vector<gl_t*> tot(L, nullptr), suf(L, nullptr);   // tot[l]: [segment][nb][2][m[l]] totals feeding level l (l >= 1); suf[l]: suffix values of level l
-    std::vector<void*> tmp;
+    zkm_scratch_list tmp(c);
     // points and weights of every level and segment: zw[l][s][b] = (z_b^(FRI_SEG^l), w_b), w_b = product of the shifts of the batches after b
     const size_t per_level = nseg * nb * 2;
     std::vector<gl2_t> zw(L * per_level);
@@ -1141,16 +1139,14 @@ static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_
             wacc = gl2_mul(wacc, comps[sg][b].shift);
         }
     }
-    gl2_t* d_zw = (gl2_t*)c->alloc(zw.size() * sizeof(gl2_t));
-    tmp.push_back(d_zw);
+    gl2_t* d_zw = tmp.alloc<gl2_t>(zw.size() * sizeof(gl2_t));
     c->upload(d_zw, zw.data(), zw.size() * sizeof(gl2_t));
     for (unsigned b = 0; b < nb; b++) { lv[0].a0[b] = comps[0][b].c0; lv[0].a1[b] = comps[0][b].c1; }
     lv[0].nb = nb;
     lv[0].a_seg = comp_seg;
     lv[0].zw = d_zw;
     for (size_t l = 1; l < L; l++) {
-        tot[l] = (gl_t*)c->alloc(nseg * 2 * nb * m[l] * sizeof(gl_t));
-        tmp.push_back(tot[l]);
+        tot[l] = tmp.alloc<gl_t>(nseg * 2 * nb * m[l] * sizeof(gl_t));
         hipLaunchKernelGGL(k_seg_totals, dim3((unsigned)((m[l] + 63) / 64), nb, z), dim3(64), 0, c->stream, lv[l - 1], m[l - 1], tot[l]);
         lv[l] = lv[0];
         for (unsigned b = 0; b < nb; b++) {
@@ -1167,14 +1163,8 @@ static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_
         const size_t nupper = l + 1 < L ? m[l + 1] : 0;
         if (l == 0 && n >= c->fri_fused_division_min) {
             const size_t lds = 4 * 64 * SEG_ROW * sizeof(gl_t);
-            if (lds > 64 * 1024) {                                  // (only a build with longer segments needs the raised limit -- ADVICE r04)
-                static std::atomic<uint64_t> lds_ok{0};             // (hipFuncSetAttribute is per device; setting it twice is harmless)
-                const uint64_t bit = (uint64_t)1 << (c->device & 63);
-                if (!(lds_ok.load(std::memory_order_acquire) & bit)) {
-                    ZKM_HIP_CHECK(hipFuncSetAttribute((const void*)k_seg_scan_final, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    lds_ok.fetch_or(bit, std::memory_order_release);
-                }
-            }
+            static std::atomic<uint64_t> lds_ok{0};                 // (only a build with longer segments needs the raised limit -- ADVICE r04)
+            if (lds > 64 * 1024) ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_seg_scan_final, lds_ok));
             hipLaunchKernelGGL(k_seg_scan_final, dim3((unsigned)((nsegm + 63) / 64), 1, z), dim3(64), lds, c->stream, lv[0], n, upper, nupper, f0, f1);
             break;
         }
@@ -1182,27 +1172,18 @@ static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_
             // two tiles per batch: 9,216 B per batch with segments of 8 -- eight batches (FRI_MAX_BATCHES) are 73,728 B, over the 64 KB a
             // launch gets without asking; the limit is raised once per device like k_fri_fold's
             const size_t lds = (size_t)2 * nb * 64 * SEG_ROW * sizeof(gl_t);
-            if (lds > 64 * 1024) {
-                static std::atomic<uint64_t> sc_lds_ok{0};
-                const uint64_t bit = (uint64_t)1 << (c->device & 63);
-                if (!(sc_lds_ok.load(std::memory_order_acquire) & bit)) {
-                    ZKM_HIP_CHECK(hipFuncSetAttribute((const void*)k_seg_scan_combine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    sc_lds_ok.fetch_or(bit, std::memory_order_release);
-                }
-            }
+            static std::atomic<uint64_t> sc_lds_ok{0};
+            if (lds > 64 * 1024) ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_seg_scan_combine, sc_lds_ok));
             hipLaunchKernelGGL(k_seg_scan_combine, dim3((unsigned)((nsegm + 63) / 64), 1, z), dim3(64 * nb), lds, c->stream, lv[0], n, upper, nupper, f0,
                                f1);
             break;
         }
-        suf[l] = (gl_t*)c->alloc(nseg * 2 * nb * m[l] * sizeof(gl_t));
-        tmp.push_back(suf[l]);
+        suf[l] = tmp.alloc<gl_t>(nseg * 2 * nb * m[l] * sizeof(gl_t));
         hipLaunchKernelGGL(k_seg_scan, dim3((unsigned)((nsegm + 63) / 64), nb, z), dim3(64), 0, c->stream, lv[l], m[l], upper, nupper, suf[l]);
         if (l == 0) hipLaunchKernelGGL(k_seg_combine, dim3((unsigned)((n + 255) / 256), 1, z), dim3(256), 0, c->stream, lv[0], n, suf[0], f0, f1);
     }
     ZKM_HIP_CHECK(hipGetLastError());
-    // no host sync: released blocks are only reused by later work on this stream
-    for (void* q : tmp) c->release(q);
-}
+}   // (`tmp` goes back without a host sync: released blocks are only reused by later work on this stream)
 
 // Everything of a FRI proof after the alpha-combination, for a STACK of independent proofs of the same shape (one proof: vectors of
 // length 1): comps[s] = proof s's composites (pointers: proof 0's; proof s's are s * comp_seg words further), orc = the stacked initial
@@ -1258,14 +1239,8 @@ static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, 
         {
             zkm_prof_scope ps(c, "fri_fold");
             const size_t lds = 2 * 64 * ((size_t)arity + 1) * sizeof(gl_t);
-            if (lds > 64 * 1024) {
-                static std::atomic<uint64_t> lds_ok{0};
-                const uint64_t bit = (uint64_t)1 << (c->device & 63);
-                if (!(lds_ok.load(std::memory_order_acquire) & bit)) {
-                    ZKM_HIP_CHECK(hipFuncSetAttribute((const void*)k_fri_fold, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                    lds_ok.fetch_or(bit, std::memory_order_release);
-                }
-            }
+            static std::atomic<uint64_t> lds_ok{0};
+            if (lds > 64 * 1024) ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_fri_fold, lds_ok));
             hipLaunchKernelGGL(k_fri_fold, dim3((unsigned)((nout + 63) / 64), 1, z), dim3(64), lds, c->stream, d_coef, d_coef + clen, nout, arity, betas,
                                d_new, d_new + nout);
             ZKM_HIP_CHECK(hipGetLastError());
@@ -1429,9 +1404,7 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
     zkm_batch_ptr own_trace, ab, qb;   // (freed before the scratch goes back: zkm_batch_free waits for the stream)
     const zkm_batch* tb = trace_batch;
     if (!tb) {
-        own_trace.reset(new zkm_batch());
-        own_trace->ctx = c; own_trace->ncols = W; own_trace->log_n = log_n; own_trace->rate_bits = cfg->rate_bits;
-        own_trace->cap_height = cfg->cap_height;
+        own_trace = zkm_batch_new(c, W, 1, log_n, cfg->rate_bits, cfg->cap_height);
         zkm_prof_scope st(c, "stage/compute trace commitment");  // prover.rs:146-163 (done by the caller in the reference)
         zkm_batch_build(own_trace.get(), trace, true);
         tb = own_trace.get();
@@ -1450,8 +1423,7 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
             throw std::runtime_error("auxiliary commitment does not match the table shape / config");
     } else if (!openings_only) {
         // auxiliary commitment :511-522
-        ab.reset(new zkm_batch());
-        ab->ctx = c; ab->ncols = A; ab->log_n = log_n; ab->rate_bits = cfg->rate_bits; ab->cap_height = cfg->cap_height;
+        ab = zkm_batch_new(c, A, 1, log_n, cfg->rate_bits, cfg->cap_height);
         if (NL) {
             // "compute lookup helper columns" :475-493, then the CTL columns behind them
             auto st = std::make_unique<zkm_prof_scope>(c, "stage/compute lookup helper columns");
@@ -1489,8 +1461,7 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
             zkm_prof_scope st(c, "stage/compute quotient polys");  // :543-559
             quotient_device(c, table_id, tb, abp, own, lookup_challenges, alphas.data(), cfg->num_challenges, d_quot);
         }
-        qb.reset(new zkm_batch());
-        qb->ctx = c; qb->ncols = y.Q; qb->nseg = nseg; qb->log_n = log_n; qb->rate_bits = cfg->rate_bits; qb->cap_height = cfg->cap_height;
+        qb = zkm_batch_new(c, y.Q, nseg, log_n, cfg->rate_bits, cfg->cap_height);
         {
             zkm_prof_scope st(c, "stage/compute quotient commitment");  // :576-587
             zkm_batch_build(qb.get(), d_quot, false);  // chunks [q0_lo, q0_hi, q1_lo, q1_hi] == d_quot viewed as Q columns of n, proof after proof
@@ -1835,8 +1806,7 @@ int zkm_prove_single_tables(zkm_ctx* c, int table_id, const zkm_stark_config* cf
             proofs[k] = proofs_out[k];
         }
         auto stacked = [&](size_t cols, const uint64_t* const* srcs) {
-            zkm_batch_ptr b(new zkm_batch());
-            b->ctx = c; b->ncols = cols; b->nseg = nproofs; b->log_n = log_n; b->rate_bits = cfg->rate_bits; b->cap_height = cfg->cap_height;
+            zkm_batch_ptr b = zkm_batch_new(c, cols, nproofs, log_n, cfg->rate_bits, cfg->cap_height);
             if (nproofs == 1) zkm_batch_build(b.get(), srcs[0], true);
             else zkm_batch_build(b.get(), nullptr, true, nullptr, nullptr, srcs);   // (device matrices are transformed where they lie)
             return b;

@@ -116,6 +116,7 @@ struct zkm_ctx {
     void trim_self();  // hipFree every cached (not live) block of THIS allocator (any thread: used by a relative's out-of-memory retry)
     void trim();       // ... and of the lanes; only between calls
     void drop_copy_streams();   // trim(): the idle upload streams give their hardware queues back
+    hipStream_t ensure_copy_stream(int k = 0);   // upload stream k (0: copy_stream, 1: copy_stream2), created on first use
     void shrink_down();   // the pinned download area back to its base size (trim(): between calls, owner's thread)
     void ensure_twiddles(unsigned log_n);
     const gl_t* pow_table(uint64_t shift, unsigned log_n);  // lo: 2^ceil(log_n/2) entries, then hi
@@ -207,12 +208,74 @@ struct zkm_scratch_list {
         return (T*)ps.back();
     }
 };
-// ... of one block
-struct zkm_scratch : zkm_scratch_list {
-    void* p;
-    zkm_scratch(zkm_ctx* ctx, size_t bytes) : zkm_scratch_list(ctx), p(alloc(bytes)) {}
+// ... of one block, movable: it goes back to the allocator that made it (a block of commit lane w to w's, whichever thread drops it),
+// on the same terms -- reset() or the destructor; take() hands the block out of the owner.
+struct zkm_scratch {
+    zkm_ctx* c = nullptr;
+    void* p = nullptr;
+    int unwinding = std::uncaught_exceptions();
+    zkm_scratch() = default;
+    zkm_scratch(zkm_ctx* ctx, size_t bytes) : c(ctx), p(ctx->alloc(bytes)) {}
+    zkm_scratch(zkm_scratch&& o) noexcept : c(o.c), p(o.take()) {}
+    zkm_scratch& operator=(zkm_scratch&& o) noexcept {
+        reset();
+        c = o.c;
+        p = o.take();
+        return *this;
+    }
+    ~zkm_scratch() { reset(); }
+    void reset() noexcept {
+        if (!p) return;
+        if (std::uncaught_exceptions() > unwinding) (void)hipStreamSynchronize(c->stream);
+        c->release(take());
+    }
+    void* take() noexcept {
+        void* q = p;
+        p = nullptr;
+        return q;
+    }
     template <class T> T* as() const { return (T*)p; }
 };
+
+// Owner of one pooled event (zkm_ctx::get_event), movable: it goes back to the pool of the context that issued it.  The pools are not
+// thread-safe: the owner of a commit lane's event is destroyed on the thread that drives that lane, or on the caller's thread after the
+// lanes have been joined -- never while the lane's thread may still take events from the same pool.
+struct zkm_event {
+    zkm_ctx* c = nullptr;
+    hipEvent_t e = nullptr;
+    zkm_event() = default;
+    explicit zkm_event(zkm_ctx* ctx) : c(ctx), e(ctx->get_event()) {}
+    zkm_event(zkm_event&& o) noexcept : c(o.c), e(o.e) { o.e = nullptr; }
+    zkm_event& operator=(zkm_event&& o) noexcept {
+        reset();
+        c = o.c;
+        e = o.e;
+        o.e = nullptr;
+        return *this;
+    }
+    ~zkm_event() { reset(); }
+    void reset() noexcept {
+        if (e) c->event_pool.push_back(e);
+        e = nullptr;
+    }
+    void record(hipStream_t st) const { ZKM_HIP_CHECK(hipEventRecord(e, st)); }
+};
+
+// hipFuncSetAttribute is per device: `done` remembers the devices on which `kernel`'s dynamic-LDS limit has been raised (one bit per
+// device; a process may hold contexts on several GPUs, and several host threads may get here at once -- setting it twice is harmless).
+// The limit goes to a fixed maximum, never to what the current launch needs: a later, larger launch finds it raised.  Returns the
+// runtime's answer: a caller with a smaller launch to fall back on checks it, the others wrap the call in ZKM_HIP_CHECK.
+inline hipError_t zkm_allow_big_lds(const zkm_ctx* c, const void* kernel, std::atomic<uint64_t>& done, int limit = 160 * 1024) noexcept {
+    const uint64_t bit = (uint64_t)1 << (c->device & 63);
+    if (done.load(std::memory_order_acquire) & bit) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return e;
+    }
+    done.fetch_or(bit, std::memory_order_release);
+    return hipSuccess;
+}
 
 // RAII profiling scope around one kernel launch (or a small group).  Names starting with "stage/" are the reference's timed!
 // scopes (prover.rs:146-153, 193, 204, 479, 513, 545, 578, 620): event pairs at the stage boundaries, reported beside the kernel
@@ -260,6 +323,8 @@ struct zkm_batch_deleter {
     void operator()(zkm_batch* b) const { zkm_batch_free(b); }
 };
 using zkm_batch_ptr = std::unique_ptr<zkm_batch, zkm_batch_deleter>;
+// an empty batch of this shape (zkm_batch_build fills it in); core.hip
+zkm_batch_ptr zkm_batch_new(zkm_ctx* c, size_t ncols, size_t nseg, unsigned log_n, unsigned rate_bits, unsigned cap_height);
 
 inline bool zkm_is_device_ptr(const void* p) {
     hipPointerAttribute_t a;
