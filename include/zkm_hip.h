@@ -569,6 +569,58 @@ const uint64_t* zkm_staged_ptr(zkm_staged* staged);
 int zkm_staged_ready(zkm_staged* staged, int wait);
 void zkm_staged_free(zkm_staged* staged);
 
+/* ------------------------------------------------------------------ N3: a whole segment from its raw operations
+ * Traces::into_tables (witness/traces.rs:230-320) on the device: the reference's Traces, one group of fields per field of it in its
+ * order.  Every list keeps the layout of the entry point named beside it; pointers are host (pageable or pinned) or device memory,
+ * except the two sponge offset arrays, which must be host memory.  A count may be 0 (its pointers may then be NULL): the table is
+ * padding only, min_rows high.
+ *   cpu_rows    Vec<CpuColumnsView<F>> as it is: ncpu_rows x ZKM_CPU_COLS words, row-major; ncpu_rows a power of two, at most 2^28
+ *               (simulate_cpu pads to one, generation/mod.rs:170-185).  Words may be non-canonical: column c of row r of the table is
+ *               cpu_rows[r * ZKM_CPU_COLS + c] mod p.
+ *   every other list   as its zkm_*_trace entry point; sha_extend_sponge_* are complete 48-round schedules (w16, meta), sha_compress_* and
+ *               sha_compress_sponge_* one {hx, w, meta} per compression. */
+typedef struct {
+    const uint64_t* cpu_rows; size_t ncpu_rows;
+    const uint32_t* arithmetic_ops; size_t narithmetic;                                      /* zkm_arithmetic_trace */
+    const uint32_t* logic_ops; size_t nlogic;                                                /* zkm_logic_trace */
+    const uint64_t* memory_ops; size_t nmemory;                                              /* zkm_memory_trace */
+    const uint64_t* poseidon_inputs; const uint64_t* poseidon_timestamps; size_t nposeidon;  /* zkm_poseidon_trace_inputs */
+    const uint8_t* poseidon_sponge_inputs; const uint64_t* poseidon_sponge_off; const uint64_t* poseidon_sponge_meta;
+    size_t nposeidon_sponge;                                                                 /* zkm_poseidon_sponge_trace */
+    const uint64_t* keccak_inputs; const uint64_t* keccak_timestamps; size_t nkeccak;        /* zkm_keccak_trace */
+    const uint8_t* keccak_sponge_inputs; const uint64_t* keccak_sponge_off; const uint64_t* keccak_sponge_meta;
+    size_t nkeccak_sponge;                                                                   /* zkm_keccak_sponge_trace */
+    const uint8_t* sha_extend_inputs; const uint64_t* sha_extend_timestamps; size_t nsha_extend;   /* zkm_sha_extend_trace (rows) */
+    const uint32_t* sha_extend_sponge_w16; const uint64_t* sha_extend_sponge_meta; size_t nsha_extend_sponge;   /* zkm_sha_extend_sponge_trace */
+    const uint32_t* sha_compress_hx; const uint32_t* sha_compress_w; const uint64_t* sha_compress_meta; size_t nsha_compress;   /* zkm_sha_compress_trace */
+    const uint32_t* sha_compress_sponge_hx; const uint32_t* sha_compress_sponge_w; const uint64_t* sha_compress_sponge_meta;
+    size_t nsha_compress_sponge;                                                             /* zkm_sha_compress_sponge_trace */
+} zkm_segment_ops;
+
+/* zkm_segment_tables: the twelve tables of the segment (Table::all() order) in ONE block of the context's allocator.
+ *   log_n_out[12]   the reference's heights, min_rows = max(2^cfg->cap_height, 64) (traces.rs:246-247, MIN_TRACE_LEN all_stark.rs:115):
+ *                   Arithmetic max(2^16, next_pow2(rows)); Cpu ncpu_rows; Poseidon pow2(max(nposeidon, min_rows)); PoseidonSponge
+ *                   pow2(max(sum(len / 32 + 1), min_rows)); Keccak pow2(max(24 nkeccak, min_rows)); KeccakSponge pow2(max(sum(len / 136 + 1),
+ *                   min_rows)); ShaExtend pow2(max(nsha_extend, min_rows)); ShaExtendSponge pow2(max(48 nsha_extend_sponge, min_rows));
+ *                   ShaCompress pow2(max(65 nsha_compress, min_rows)); ShaCompressSponge pow2(max(nsha_compress_sponge, min_rows)); Logic
+ *                   pow2(max(nlogic, min_rows)); Memory zkm_memory_trace's natural height.  Each table is word for word what its entry
+ *                   point writes at that height (the Poseidon padding row is the permutation of zero).
+ *   out             a segment-shaped zkm_staged (zkm_staged_segment_ptrs / _ready / _free; traces[s] of zkm_prove_segments).  The call
+ *                   returns once the tables are complete: the handle is never an upload in flight.  NULL: sizing only -- log_n_out is
+ *                   filled (the device still finds the Memory and Arithmetic heights) and nothing is allocated.
+ * Fails (nonzero, a message naming the table) on every refusal of the per-table entry points, on CPU rows that are not a power of two
+ * or more than 2^28, a NULL pointer with a nonzero count, zero memory operations, and a table of more than 2^28 rows.  A failure leaves
+ * the context usable and its live memory as it was.  At most three host waits: the Memory key widths with the Arithmetic row count and
+ * flags, the Memory row count, the writers' validation flags.  CPU rows in host memory are copied in row pieces on the context's copy
+ * streams (asynchronous from pinned memory) while the other tables are generated. */
+int zkm_segment_tables(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out,
+                       char** err);
+/* zkm_segment_tables, zkm_prove_segment on the block, the block freed: into_tables + prove_with_traces (generation/mod.rs:25-76) in
+ * one call.  Outputs as zkm_prove_segment; proofs_out = NULL sizes them (proof_offsets_out[13]) -- unlike zkm_prove_segment's sizing
+ * pass this one needs the context, for the Memory and Arithmetic heights. */
+int zkm_prove_segment_ops(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_segment_ops* ops, const uint64_t* public_values, size_t npublic,
+                          uint64_t* proofs_out, size_t* proof_offsets_out, uint64_t* ctl_challenges_out, char** err);
+
 /* ------------------------------------------------------------------ one process, many GPUs: a pool of contexts
  * The reference drives all segments of a program from ONE process (prover/examples/utils/src/utils.rs:57-68 prove_single_seg_common,
  * :105-133 prove_multi_seg_common: a loop of prove_with_traces calls); segments are independent proofs, so N GPUs take them

@@ -60,6 +60,25 @@ pub struct zkm_table_input { pub table_id: c_int, pub trace: *const u64, pub nco
 pub struct zkm_fri_poly { pub oracle: u32, pub poly: u32 }
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct zkm_fri_batch { pub point: [u64; 2], pub polys: *const zkm_fri_poly, pub npolys: usize }
+/// a segment's raw operations for zkm_segment_tables / zkm_prove_segment_ops: one group per field of the reference's Traces, in its
+/// order (witness/traces.rs:47-62); segment_hip.rs packs a Traces<F> into it
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct zkm_segment_ops {
+    pub cpu_rows: *const u64, pub ncpu_rows: usize,
+    pub arithmetic_ops: *const u32, pub narithmetic: usize,
+    pub logic_ops: *const u32, pub nlogic: usize,
+    pub memory_ops: *const u64, pub nmemory: usize,
+    pub poseidon_inputs: *const u64, pub poseidon_timestamps: *const u64, pub nposeidon: usize,
+    pub poseidon_sponge_inputs: *const u8, pub poseidon_sponge_off: *const u64, pub poseidon_sponge_meta: *const u64, pub nposeidon_sponge: usize,
+    pub keccak_inputs: *const u64, pub keccak_timestamps: *const u64, pub nkeccak: usize,
+    pub keccak_sponge_inputs: *const u8, pub keccak_sponge_off: *const u64, pub keccak_sponge_meta: *const u64, pub nkeccak_sponge: usize,
+    pub sha_extend_inputs: *const u8, pub sha_extend_timestamps: *const u64, pub nsha_extend: usize,
+    pub sha_extend_sponge_w16: *const u32, pub sha_extend_sponge_meta: *const u64, pub nsha_extend_sponge: usize,
+    pub sha_compress_hx: *const u32, pub sha_compress_w: *const u32, pub sha_compress_meta: *const u64, pub nsha_compress: usize,
+    pub sha_compress_sponge_hx: *const u32, pub sha_compress_sponge_w: *const u32, pub sha_compress_sponge_meta: *const u64,
+    pub nsha_compress_sponge: usize,
+}
+pub type ZkmSegmentOps = zkm_segment_ops;
 
 // ZKM_TABLE_* ids (NOT the reference's Table enum order: see zkm_table_enum_index)
 pub const ZKM_TABLE_POSEIDON: c_int = 0; pub const ZKM_TABLE_LOGIC: c_int = 1; pub const ZKM_TABLE_KECCAK_SPONGE: c_int = 2;
@@ -191,6 +210,12 @@ extern "C" {
     pub fn zkm_staged_ptr(staged: *mut zkm_staged) -> *const u64;
     pub fn zkm_staged_ready(staged: *mut zkm_staged, wait: c_int) -> c_int;
     pub fn zkm_staged_free(staged: *mut zkm_staged);
+    // a whole segment from its raw operations: the twelve tables in one device block (Traces::into_tables), or proven at once
+    pub fn zkm_segment_tables(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, ops: *const zkm_segment_ops, log_n_out: *mut c_uint,
+                              out: *mut *mut zkm_staged, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_prove_segment_ops(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, ops: *const zkm_segment_ops, public_values: *const u64,
+                                 npublic: usize, proofs_out: *mut u64, proof_offsets_out: *mut usize, ctl_challenges_out: *mut u64,
+                                 err: *mut *mut c_char) -> c_int;
     // one process, many GPUs: contexts_per_device contexts on each device, one worker thread per context, groups of <= max_stack segments
     pub fn zkm_pool_create(devices: *const c_int, ndevices: usize, contexts_per_device: usize, out: *mut *mut zkm_pool, err: *mut *mut c_char) -> c_int;
     pub fn zkm_pool_destroy(pool: *mut zkm_pool);

@@ -76,6 +76,21 @@ int main(void) {
     BEGIN(zkm_fri_batch);
     FIELD(zkm_fri_batch, point); FIELD(zkm_fri_batch, polys); FIELD(zkm_fri_batch, npolys);
     END();
+    BEGIN(zkm_segment_ops);
+    FIELD(zkm_segment_ops, cpu_rows); FIELD(zkm_segment_ops, ncpu_rows); FIELD(zkm_segment_ops, arithmetic_ops);
+    FIELD(zkm_segment_ops, narithmetic); FIELD(zkm_segment_ops, logic_ops); FIELD(zkm_segment_ops, nlogic);
+    FIELD(zkm_segment_ops, memory_ops); FIELD(zkm_segment_ops, nmemory); FIELD(zkm_segment_ops, poseidon_inputs);
+    FIELD(zkm_segment_ops, poseidon_timestamps); FIELD(zkm_segment_ops, nposeidon); FIELD(zkm_segment_ops, poseidon_sponge_inputs);
+    FIELD(zkm_segment_ops, poseidon_sponge_off); FIELD(zkm_segment_ops, poseidon_sponge_meta); FIELD(zkm_segment_ops, nposeidon_sponge);
+    FIELD(zkm_segment_ops, keccak_inputs); FIELD(zkm_segment_ops, keccak_timestamps); FIELD(zkm_segment_ops, nkeccak);
+    FIELD(zkm_segment_ops, keccak_sponge_inputs); FIELD(zkm_segment_ops, keccak_sponge_off); FIELD(zkm_segment_ops, keccak_sponge_meta);
+    FIELD(zkm_segment_ops, nkeccak_sponge); FIELD(zkm_segment_ops, sha_extend_inputs); FIELD(zkm_segment_ops, sha_extend_timestamps);
+    FIELD(zkm_segment_ops, nsha_extend); FIELD(zkm_segment_ops, sha_extend_sponge_w16); FIELD(zkm_segment_ops, sha_extend_sponge_meta);
+    FIELD(zkm_segment_ops, nsha_extend_sponge); FIELD(zkm_segment_ops, sha_compress_hx); FIELD(zkm_segment_ops, sha_compress_w);
+    FIELD(zkm_segment_ops, sha_compress_meta); FIELD(zkm_segment_ops, nsha_compress); FIELD(zkm_segment_ops, sha_compress_sponge_hx);
+    FIELD(zkm_segment_ops, sha_compress_sponge_w); FIELD(zkm_segment_ops, sha_compress_sponge_meta);
+    FIELD(zkm_segment_ops, nsha_compress_sponge);
+    END();
     printf("\n}\n");
     return 0;
 }

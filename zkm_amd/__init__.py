@@ -46,6 +46,7 @@ EXPORTS = [
     "zkm_trace_stage", "zkm_trace_stage_columns", "zkm_segment_stage", "zkm_segment_stage_columns", "zkm_staged_segment_ptrs", "zkm_staged_ptr", "zkm_staged_ready", "zkm_staged_free",
     "zkm_pool_create", "zkm_pool_destroy", "zkm_pool_workers", "zkm_pool_context", "zkm_pool_device", "zkm_pool_set_tuning",
     "zkm_pool_prove_segments", "zkm_pool_prove_segments_columns", "zkm_pool_plan", "zkm_pool_last_assignment",
+    "zkm_segment_tables", "zkm_prove_segment_ops",
 ]
 
 
@@ -100,6 +101,29 @@ class FriBatch(C.Structure):
     _fields_ = [("point", C.c_uint64 * 2), ("polys", C.c_void_p), ("npolys", C.c_size_t)]
 
 
+# zkm_segment_ops (include/zkm_hip.h): per group of fields, the data pointers (with the bytes of one item of each) and the count
+SEGMENT_OPS_GROUPS = [
+    ("cpu_rows", [("cpu_rows", 259 * 8)], "ncpu_rows"),
+    ("arithmetic", [("arithmetic_ops", 12)], "narithmetic"),
+    ("logic", [("logic_ops", 12)], "nlogic"),
+    ("memory", [("memory_ops", 48)], "nmemory"),
+    ("poseidon", [("poseidon_inputs", 96), ("poseidon_timestamps", 8)], "nposeidon"),
+    ("poseidon_sponge", [("poseidon_sponge_inputs", 0), ("poseidon_sponge_off", 0), ("poseidon_sponge_meta", 32)], "nposeidon_sponge"),
+    ("keccak", [("keccak_inputs", 200), ("keccak_timestamps", 8)], "nkeccak"),
+    ("keccak_sponge", [("keccak_sponge_inputs", 0), ("keccak_sponge_off", 0), ("keccak_sponge_meta", 32)], "nkeccak_sponge"),
+    ("sha_extend", [("sha_extend_inputs", 16), ("sha_extend_timestamps", 8)], "nsha_extend"),
+    ("sha_extend_sponge", [("sha_extend_sponge_w16", 64), ("sha_extend_sponge_meta", 32)], "nsha_extend_sponge"),
+    ("sha_compress", [("sha_compress_hx", 32), ("sha_compress_w", 256), ("sha_compress_meta", 64)], "nsha_compress"),
+    ("sha_compress_sponge", [("sha_compress_sponge_hx", 32), ("sha_compress_sponge_w", 256), ("sha_compress_sponge_meta", 64)],
+     "nsha_compress_sponge"),
+]
+
+
+class SegmentOpsStruct(C.Structure):
+    """zkm_segment_ops: a segment's raw operations, one group per field of the reference's Traces (witness/traces.rs:47-62)."""
+    _fields_ = [f for _, ptrs, count in SEGMENT_OPS_GROUPS for f in [(name, C.c_void_p) for name, _ in ptrs] + [(count, C.c_size_t)]]
+
+
 def abi_mirrors():
     """Every struct of include/zkm_hip.h -> its Python mirror (a ctypes Structure or a numpy dtype); tests/test_abi.py compares
     size and field offsets of each with what the C compiler says (tools/abi_layout.c)."""
@@ -108,7 +132,7 @@ def abi_mirrors():
             "zkm_proof_query_layout": ProofQueryLayout, "zkm_column": ctl.COLUMN_DT, "zkm_colset": ctl.COLSET_DT,
             "zkm_ctl_table": ctl.CtlTableStruct, "zkm_ctl_z": ctl.CTLZ_DT, "zkm_ctl_side": ctl.SIDE_DT,
             "zkm_cross_table_lookup": ctl.CTL_DT, "zkm_table_input": ctl.TableInputStruct, "zkm_fri_poly": FriPoly,
-            "zkm_fri_batch": FriBatch}
+            "zkm_fri_batch": FriBatch, "zkm_segment_ops": SegmentOpsStruct}
 
 
 _lib = None
@@ -191,6 +215,9 @@ def load():
         "zkm_staged_ptr": (cp, [cp]),
         "zkm_staged_ready": (C.c_int, [cp, C.c_int]),
         "zkm_staged_free": (None, [cp]),
+        "zkm_segment_tables": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(SegmentOpsStruct), C.POINTER(C.c_uint), cpp, err]),
+        "zkm_prove_segment_ops": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(SegmentOpsStruct), u64p, C.c_size_t, u64p,
+                                            C.POINTER(C.c_size_t), u64p, err]),
         "zkm_host_alloc": (C.c_int, [cp, C.c_size_t, cpp, err]),
         "zkm_host_free": (C.c_int, [cp, cp]),
         "zkm_host_register": (C.c_int, [cp, cp, C.c_size_t, err]),
@@ -350,6 +377,89 @@ def _data_ptr(x):
     if hasattr(x, "data_ptr"):
         return C.c_void_p(x.data_ptr())
     raise TypeError("unsupported buffer type %r" % type(x))
+
+
+class SegmentOps:
+    """A segment's raw operations -- the reference's Traces (witness/traces.rs:47-62) -- for Context.segment_tables / prove_segment_ops.
+    Every list has the layout of its per-table entry point (include/zkm_hip.h zkm_segment_ops) and is a numpy array (pageable, or a
+    view of Context.pinned_array memory) or a DeviceBuffer; the sponge offsets stay numpy.  Groups given as tuples:
+      poseidon            (inputs n x 12 u64, timestamps n u64)
+      poseidon_sponge     (inputs u8, off n + 1 u64, meta n x 4 u64)               keccak_sponge   the same
+      keccak              (inputs n x 25 u64, timestamps n u64)
+      sha_extend          (inputs n x 16 u8, timestamps n u64)                     sha_extend_sponge   (w16 n x 16 u32, meta n x 4 u64)
+      sha_compress        (hx n x 8 u32, w n x 64 u32, meta n x 8 u64)            sha_compress_sponge the same
+    cpu_rows: ncpu_rows x 259 u64, row-major (any shape); arithmetic / logic: n x 3 u32; memory: n x 6 u64.  Counts come from the sizes
+    (a DeviceBuffer holds ceil(bytes / 8) words)."""
+
+    DTYPES = {"cpu_rows": np.uint64, "arithmetic_ops": np.uint32, "logic_ops": np.uint32, "memory_ops": np.uint64, "poseidon_inputs": np.uint64,
+              "poseidon_timestamps": np.uint64, "poseidon_sponge_inputs": np.uint8, "poseidon_sponge_off": np.uint64,
+              "poseidon_sponge_meta": np.uint64, "keccak_inputs": np.uint64, "keccak_timestamps": np.uint64, "keccak_sponge_inputs": np.uint8,
+              "keccak_sponge_off": np.uint64, "keccak_sponge_meta": np.uint64, "sha_extend_inputs": np.uint8, "sha_extend_timestamps": np.uint64,
+              "sha_extend_sponge_w16": np.uint32, "sha_extend_sponge_meta": np.uint64, "sha_compress_hx": np.uint32, "sha_compress_w": np.uint32,
+              "sha_compress_meta": np.uint64, "sha_compress_sponge_hx": np.uint32, "sha_compress_sponge_w": np.uint32,
+              "sha_compress_sponge_meta": np.uint64}
+
+    def __init__(self, cpu_rows, memory_ops, arithmetic_ops=None, logic_ops=None, poseidon=None, poseidon_sponge=None, keccak=None,
+                 keccak_sponge=None, sha_extend=None, sha_extend_sponge=None, sha_compress=None, sha_compress_sponge=None):
+        given = {"cpu_rows": (cpu_rows,), "memory": (memory_ops,), "arithmetic": (arithmetic_ops,), "logic": (logic_ops,),
+                 "poseidon": poseidon, "poseidon_sponge": poseidon_sponge, "keccak": keccak, "keccak_sponge": keccak_sponge,
+                 "sha_extend": sha_extend, "sha_extend_sponge": sha_extend_sponge, "sha_compress": sha_compress,
+                 "sha_compress_sponge": sha_compress_sponge}
+        self.lists, self.counts = {}, {}
+        for group, ptrs, count in SEGMENT_OPS_GROUPS:
+            vals = given[group] if given[group] is not None else (None,) * len(ptrs)
+            assert len(vals) == len(ptrs), group
+            n = 0
+            for (name, item), v in zip(ptrs, vals):
+                if v is None:
+                    continue
+                if not isinstance(v, DeviceBuffer):
+                    v = np.ascontiguousarray(v, dtype=self.DTYPES[name]).reshape(-1)
+                self.lists[name] = v
+                if name.endswith("_off"):               # a sponge group: counted by its offsets
+                    n = v.size - 1
+                elif name == ptrs[0][0] and item:       # any other group: by its first list
+                    n = (v.words * 8 if isinstance(v, DeviceBuffer) else v.nbytes) // item
+            self.counts[count] = n
+
+    def to_device(self, ctx):
+        """The same operations with every list (the sponge offsets excepted) copied into DeviceBuffers of ctx."""
+        return self._copy(lambda a: ctx.alloc((a.nbytes + 7) // 8).upload(_as_words(a)))
+
+    def to_pinned(self, ctx):
+        """The same operations with every list copied into page-locked host memory (Context.pinned_array)."""
+        def pin(a):
+            p = ctx.pinned_array((a.nbytes + 7) // 8)
+            p.view(np.uint8)[:a.nbytes] = a.view(np.uint8)
+            return p.view(a.dtype)[:a.size]
+        return self._copy(pin)
+
+    def _copy(self, fn):
+        out = SegmentOps.__new__(SegmentOps)
+        out.lists = {k: (v if k.endswith("_off") or isinstance(v, DeviceBuffer) else fn(v)) for k, v in self.lists.items()}
+        out.counts = dict(self.counts)
+        return out
+
+    def free(self):
+        """Free the DeviceBuffers (to_device's copies)."""
+        for v in self.lists.values():
+            if isinstance(v, DeviceBuffer):
+                v.free()
+
+    def struct(self):
+        st = SegmentOpsStruct()
+        for name, v in self.lists.items():
+            setattr(st, name, v.ptr if isinstance(v, DeviceBuffer) else v.ctypes.data)
+        for count, n in self.counts.items():
+            setattr(st, count, n)
+        return st
+
+
+def _as_words(a):
+    """The bytes of a numpy array as uint64 words (zero-padded to a multiple of 8)."""
+    b = np.zeros(((a.nbytes + 7) // 8) * 8, dtype=np.uint8)
+    b[:a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+    return b.view(np.uint64)
 
 
 class _marshal_segments:
@@ -777,6 +887,38 @@ class Context:
         st = StagedTrace(self, h, 0)
         st._keep = keep
         return st
+
+    def segment_tables(self, ops, cfg=None):
+        """zkm_segment_tables: Traces::into_tables (witness/traces.rs:230-320) on the device.  ops: a SegmentOps.  Returns (staged,
+        log_ns): a StagedTrace whose .tables() are the twelve device matrices (Table::all() order) -- traces[s] of prove_segments -- and
+        the reference's heights, as the library computes them."""
+        cfg = cfg or self.standard_config()
+        st, lg, h, err = ops.struct(), (C.c_uint * 12)(), C.c_void_p(), C.c_char_p()
+        _check(self.L.zkm_segment_tables(self.h, C.byref(cfg), C.byref(st), lg, C.byref(h), C.byref(err)), err)
+        staged = StagedTrace(self, h, 0)
+        return staged, list(lg)
+
+    def segment_heights(self, ops, cfg=None):
+        """zkm_segment_tables' sizing mode: the twelve log heights only, nothing allocated."""
+        cfg = cfg or self.standard_config()
+        st, lg, err = ops.struct(), (C.c_uint * 12)(), C.c_char_p()
+        _check(self.L.zkm_segment_tables(self.h, C.byref(cfg), C.byref(st), lg, None, C.byref(err)), err)
+        return list(lg)
+
+    def prove_segment_ops(self, ops, public_values=(), cfg=None):
+        """zkm_prove_segment_ops: the segment's tables built on the device from its raw operations and proven (into_tables +
+        prove_with_traces).  Returns (proofs, ctl_challenges, offsets) as prove_segment does."""
+        cfg = cfg or self.standard_config()
+        st, err = ops.struct(), C.c_char_p()
+        pub = np.ascontiguousarray(public_values, dtype=np.uint64)
+        offs = (C.c_size_t * 13)()
+        _check(self.L.zkm_prove_segment_ops(self.h, C.byref(cfg), C.byref(st), pub.ctypes.data_as(u64p), pub.size, None, offs, None, C.byref(err)),
+               err)
+        proofs = np.zeros(offs[12], dtype=np.uint64)
+        chal = np.zeros(2 * cfg.num_challenges, dtype=np.uint64)
+        _check(self.L.zkm_prove_segment_ops(self.h, C.byref(cfg), C.byref(st), pub.ctypes.data_as(u64p), pub.size, proofs.ctypes.data_as(u64p),
+                                            offs, chal.ctypes.data_as(u64p), C.byref(err)), err)
+        return proofs, chal, list(offs)
 
     def prove_single_table(self, trace, log_n, aux, num_helpers, challenger=None, cfg=None, ncols=POSEIDON_COLS,
                            trace_batch=None, naux=None, table_id=TABLE_POSEIDON):

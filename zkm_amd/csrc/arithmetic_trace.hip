@@ -419,6 +419,69 @@ size_t blocks_for(size_t items, size_t per) { return (items + per - 1) / per; }
 
 }  // namespace
 
+// ---- host phases (zkm_internal.h zkm_arith_job): zkm_arithmetic_trace runs them back to back, segment_ops.hip beside the Memory
+// witness's
+void zkm_arithmetic_count(zkm_arith_job& j) {
+    zkm_ctx* c = j.c;
+    const size_t nops = j.nops;
+    if (nops >= ((size_t)1 << 31)) throw std::runtime_error(std::string(j.what) + ": 2^31 or more arithmetic ops");
+    if (nops && !j.d_ops) throw std::runtime_error(std::string(j.what) + ": null ops");
+    // start[0, nops] the scan (start[nops] = rows), start[nops + 1] the failure flags
+    j.start = zkm_scratch(c, (nops + 2) * 8);
+    uint64_t* d_start = j.start.as<uint64_t>();
+    unsigned* d_flags = (unsigned*)(d_start + nops + 1);
+    ZKM_HIP_CHECK(hipMemsetAsync(d_start + nops, 0, 16, c->stream));
+    if (nops) {
+        const size_t len = nops + 1, nparts = blocks_for(len, SCAN_TILE);
+        zkm_scratch part(c, nparts * 8);
+        zkm_prof_scope ps(c, "arithmetic_trace/count");
+        hipLaunchKernelGGL(k_arith_count, dim3(blocks_for(nops, AT_THREADS)), dim3(AT_THREADS), 0, c->stream, j.d_ops, (uint32_t)nops, d_start,
+                           d_flags);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(nparts), dim3(SCAN_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
+        hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(SCAN_THREADS), 0, c->stream, part.as<uint64_t>(), nparts);
+        hipLaunchKernelGGL(k_scan_apply, dim3(nparts), dim3(SCAN_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+}
+
+size_t zkm_arithmetic_height(zkm_arith_job& j, const uint64_t got[2], size_t* natural_rows_out) {
+    const std::string w(j.what);
+    const unsigned flags = (unsigned)got[1];
+    if (flags & BAD_OP) throw std::runtime_error(w + ": an op code is above 25 (IS_MTLO)");
+    if (flags & BAD_DIV_ZERO) throw std::runtime_error(w + ": DIV or DIVU by zero");
+    if (flags & BAD_DIV_OVERFLOW) throw std::runtime_error(w + ": DIV of 0x80000000 by 0xFFFFFFFF overflows");
+    if (flags & BAD_IMM) throw std::runtime_error(w + ": ADDI, ADDIU, SLTI or SLTIU with an input1 that is not a sign-extended 16-bit immediate");
+    if (flags & BAD_SHIFT) throw std::runtime_error(w + ": SLL, SRL, SRA or SRAV with a shift amount above 31");
+    j.rows = got[0];
+    const size_t natural = std::max<size_t>(RANGE_MAX, next_pow2(j.rows));
+    if (natural_rows_out) *natural_rows_out = natural;
+    return natural;
+}
+
+void zkm_arithmetic_write(zkm_arith_job& j, unsigned log_n, gl_t* out_dev, unsigned* d_bad) {
+    zkm_ctx* c = j.c;
+    const size_t n = (size_t)1 << log_n, nops = j.nops, rows = j.rows;
+    // hist[0, 2^16) the RC_FREQUENCIES bins (hist[2^16]: zero, where the wrapper keeps its range-check flag)
+    j.hist = zkm_scratch(c, (RANGE_MAX + 1) * 8);
+    unsigned long long* d_hist = j.hist.as<unsigned long long>();
+    ZKM_HIP_CHECK(hipMemsetAsync(d_hist, 0, (RANGE_MAX + 1) * 8, c->stream));
+    if (!d_bad) d_bad = (unsigned*)(d_hist + RANGE_MAX);
+    {
+        zkm_prof_scope ps(c, "arithmetic_trace/rows");
+        rows_args A{j.d_ops, j.start.as<uint64_t>(), (uint32_t)nops, rows, n, d_hist, d_bad};
+        const size_t work = std::max<size_t>(nops, n - rows);
+        const size_t grid = std::min<size_t>(blocks_for(work, AR_THREADS), (size_t)std::max(c->num_cus, 1));
+        hipLaunchKernelGGL(k_arith_rows, dim3(grid), dim3(AR_THREADS), 0, c->stream, A, out_dev);
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+    {
+        zkm_prof_scope ps(c, "arithmetic_trace/freq");
+        hipLaunchKernelGGL(k_arith_freq, dim3(RANGE_MAX / AT_THREADS), dim3(AT_THREADS), 0, c->stream, d_hist, (uint64_t)NSHARED * (n - rows),
+                           n, out_dev);
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+}
+
 extern "C" int zkm_arithmetic_trace(zkm_ctx* c, const uint32_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev,
                                     size_t* natural_rows_out, char** err) {
     return zkm_api("zkm_arithmetic_trace", c, err, [&] {
@@ -430,64 +493,24 @@ extern "C" int zkm_arithmetic_trace(zkm_ctx* c, const uint32_t* ops, size_t nops
                                          std::to_string(AT_MAX_LOG_N) + "] (the range-check table needs 2^16 rows)");
             if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_arithmetic_trace: out must be a device pointer");
         }
-        const uint32_t m = (uint32_t)nops;
         zkm_scratch_list host_copy(c);
         const uint32_t* d_ops = ops;
         if (nops && !zkm_is_device_ptr(ops)) {
             d_ops = host_copy.alloc<uint32_t>(nops * 12);
             ZKM_HIP_CHECK(hipMemcpyAsync((void*)d_ops, ops, nops * 12, hipMemcpyHostToDevice, c->stream));
         }
-        // start[0, nops] the scan (start[nops] = rows), start[nops + 1] the failure flags
-        zkm_scratch start(c, (nops + 2) * 8);
-        uint64_t* d_start = start.as<uint64_t>();
-        unsigned* d_flags = (unsigned*)(d_start + nops + 1);
-        ZKM_HIP_CHECK(hipMemsetAsync(d_start + nops, 0, 16, c->stream));
-        if (nops) {
-            const size_t len = nops + 1, nparts = blocks_for(len, SCAN_TILE);
-            zkm_scratch part(c, nparts * 8);
-            zkm_prof_scope ps(c, "arithmetic_trace/count");
-            hipLaunchKernelGGL(k_arith_count, dim3(blocks_for(nops, AT_THREADS)), dim3(AT_THREADS), 0, c->stream, d_ops, m, d_start, d_flags);
-            hipLaunchKernelGGL(k_scan_tiles, dim3(nparts), dim3(SCAN_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
-            hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(SCAN_THREADS), 0, c->stream, part.as<uint64_t>(), nparts);
-            hipLaunchKernelGGL(k_scan_apply, dim3(nparts), dim3(SCAN_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
+        zkm_arith_job j(c, "zkm_arithmetic_trace", d_ops, nops);
+        zkm_arithmetic_count(j);
         uint64_t got[2];
-        c->download(got, d_start + nops, 16);
-        const uint64_t rows = got[0];
-        const unsigned flags = (unsigned)got[1];
-        if (flags & BAD_OP) throw std::runtime_error("zkm_arithmetic_trace: an op code is above 25 (IS_MTLO)");
-        if (flags & BAD_DIV_ZERO) throw std::runtime_error("zkm_arithmetic_trace: DIV or DIVU by zero");
-        if (flags & BAD_DIV_OVERFLOW) throw std::runtime_error("zkm_arithmetic_trace: DIV of 0x80000000 by 0xFFFFFFFF overflows");
-        if (flags & BAD_IMM)
-            throw std::runtime_error("zkm_arithmetic_trace: ADDI, ADDIU, SLTI or SLTIU with an input1 that is not a sign-extended 16-bit immediate");
-        if (flags & BAD_SHIFT) throw std::runtime_error("zkm_arithmetic_trace: SLL, SRL, SRA or SRAV with a shift amount above 31");
-        const size_t natural = std::max<size_t>(RANGE_MAX, next_pow2(rows));
-        if (natural_rows_out) *natural_rows_out = natural;
+        c->download(got, j.counts(), 16);
+        const size_t natural = zkm_arithmetic_height(j, got, natural_rows_out);
         if (!out_dev) return;
         const size_t n = (size_t)1 << log_n;
         if (natural > n)
             throw std::runtime_error("zkm_arithmetic_trace: the table needs " + std::to_string(natural) + " rows, more than 2^" + std::to_string(log_n));
-        // hist[0, 2^16) the RC_FREQUENCIES bins, hist[2^16] the range-check flag
-        zkm_scratch hist(c, (RANGE_MAX + 1) * 8);
-        unsigned long long* d_hist = hist.as<unsigned long long>();
-        ZKM_HIP_CHECK(hipMemsetAsync(d_hist, 0, (RANGE_MAX + 1) * 8, c->stream));
-        {
-            zkm_prof_scope ps(c, "arithmetic_trace/rows");
-            rows_args A{d_ops, d_start, m, rows, n, d_hist, (unsigned*)(d_hist + RANGE_MAX)};
-            const size_t work = std::max<size_t>(nops, n - rows);
-            const size_t grid = std::min<size_t>(blocks_for(work, AR_THREADS), (size_t)std::max(c->num_cus, 1));
-            hipLaunchKernelGGL(k_arith_rows, dim3(grid), dim3(AR_THREADS), 0, c->stream, A, out_dev);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        {
-            zkm_prof_scope ps(c, "arithmetic_trace/freq");
-            hipLaunchKernelGGL(k_arith_freq, dim3(RANGE_MAX / AT_THREADS), dim3(AT_THREADS), 0, c->stream, d_hist, (uint64_t)NSHARED * (n - rows),
-                               n, out_dev);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
+        zkm_arithmetic_write(j, log_n, out_dev, nullptr);
         uint64_t bad = 0;
-        c->download(&bad, d_hist + RANGE_MAX, 8);
+        c->download(&bad, j.hist.as<unsigned long long>() + RANGE_MAX, 8);
         if (bad) throw std::runtime_error("zkm_arithmetic_trace: a shared-column value is 2^16 or more");
     });
 }

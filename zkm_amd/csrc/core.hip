@@ -650,6 +650,7 @@ struct zkm_staged {
     bool joined, canonical;
     size_t off[13];     // a staged SEGMENT: word offset of table t (Table::all() order) in the block, off[12] = words; one matrix: unused
     bool segment;
+    bool counted;       // an upload counted in g_staged_live (a segment built on the device by zkm_segment_tables is not)
 };
 
 static zkm_staged* stage_begin(zkm_ctx* c, size_t words, int canonical) {
@@ -668,6 +669,7 @@ static zkm_staged* stage_begin(zkm_ctx* c, size_t words, int canonical) {
     s->ctx = c; s->words = words; s->joined = false; s->canonical = canonical != 0;
     s->done[0] = s->done[1] = nullptr;
     s->segment = false;
+    s->counted = true;
     for (size_t& o : s->off) o = 0;
     s->dev = (gl_t*)dev.take();
     g_staged_live.fetch_add(1, std::memory_order_relaxed);
@@ -815,8 +817,25 @@ void zkm_staged_free(zkm_staged* s) {
     (void)hipEventSynchronize(s->done[1]);
     c->release(s->dev);
     (void)zkm_api("zkm_staged_free", nullptr, [&] { c->event_pool.insert(c->event_pool.end(), s->done, s->done + 2); });
+    const bool counted = s->counted;
     delete s;
-    g_staged_live.fetch_sub(1, std::memory_order_relaxed);
+    if (counted) g_staged_live.fetch_sub(1, std::memory_order_relaxed);
+}
+
+// A segment whose tables were WRITTEN on the device by work already queued on the context's compute stream (segment_ops.hip): the block
+// becomes a segment-shaped handle that zkm_staged_segment_ptrs / _ready / _free take as they take an upload.  Both events are recorded
+// on the compute stream; the block is canonical and needs no join.  Not an upload, so not counted in g_staged_live.
+zkm_staged* zkm_staged_from_segment(zkm_ctx* c, void* block, const size_t off[13]) {
+    zkm_event e0(c), e1(c);
+    e0.record(c->stream);
+    e1.record(c->stream);
+    zkm_staged* s = new zkm_staged();
+    s->ctx = c; s->dev = (gl_t*)block; s->words = off[12]; s->joined = true; s->canonical = true;
+    s->segment = true; s->counted = false;
+    for (int t = 0; t <= 12; t++) s->off[t] = off[t];
+    s->done[0] = e0.e; s->done[1] = e1.e;
+    e0.e = e1.e = nullptr;
+    return s;
 }
 
 // ------------------------------------------------------------------ profiling

@@ -322,6 +322,111 @@ size_t blocks_for(size_t items, size_t per) { return (items + per - 1) / per; }
 
 }  // namespace
 
+// ---- host phases (zkm_internal.h zkm_memory_job): zkm_memory_trace runs them back to back, segment_ops.hip interleaves them with
+// the other tables' so that one host wait serves several tables
+void zkm_memory_widths(zkm_memory_job& j) {
+    zkm_ctx* c = j.c;
+    if (j.nops == 0) throw std::runtime_error(std::string(j.what) + ": No memory ops?");
+    if (j.nops >= ((size_t)1 << 32)) throw std::runtime_error(std::string(j.what) + ": 2^32 or more memory ops");
+    // small: [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies, [6] range-check flag
+    j.small = zkm_scratch(c, 64);
+    j.d_acc = j.small.as<unsigned long long>();
+    ZKM_HIP_CHECK(hipMemsetAsync(j.small.p, 0, 64, c->stream));
+    zkm_prof_scope ps(c, "memory_trace/widths");
+    hipLaunchKernelGGL(k_mem_widths, dim3(std::min<size_t>(blocks_for(j.nops, MT_THREADS), 1024)), dim3(MT_THREADS), 0, c->stream,
+                       j.d_ops, j.nops, j.d_acc);
+    ZKM_HIP_CHECK(hipGetLastError());
+}
+
+void zkm_memory_sort(zkm_memory_job& j, const uint64_t acc[5]) {
+    zkm_ctx* c = j.c;
+    const size_t nops = j.nops;
+    const uint32_t m = (uint32_t)nops;
+    if (acc[4]) throw std::runtime_error(std::string(j.what) + ": a context, segment, virt or timestamp word is not below p");
+    // key layout: timestamp lowest, then virt, segment, context
+    key_layout L{};
+    unsigned sh = 0;
+    for (int f = 3; f >= 0; f--) {
+        L.width[f] = bit_width(acc[f]);
+        L.shift[f] = sh;
+        sh += L.width[f];
+    }
+    L.bits = sh;
+    L.nwords = sh ? (sh + 63) / 64 : 1;
+    const size_t K = L.nwords, ntiles = blocks_for(nops, MT_TILE);
+    j.keys_a = zkm_scratch(c, K * nops * 8);
+    j.keys_b = zkm_scratch(c, K * nops * 8);
+    j.idx_a = zkm_scratch(c, nops * 4);
+    j.idx_b = zkm_scratch(c, nops * 4);
+    uint64_t *kin = j.keys_a.as<uint64_t>(), *kout = j.keys_b.as<uint64_t>();
+    uint32_t *iin = j.idx_a.as<uint32_t>(), *iout = j.idx_b.as<uint32_t>();
+    {
+        zkm_prof_scope ps(c, "memory_trace/pack");
+        hipLaunchKernelGGL(k_mem_pack, dim3(blocks_for(nops, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, j.d_ops, m, L, kin, iin);
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+    if (nops > 1 && L.bits) {
+        zkm_scratch hist(c, (size_t)MT_RADIX * ntiles * 4), tot(c, MT_RADIX * 4);
+        zkm_prof_scope ps(c, "memory_trace/sort");
+        for (unsigned bit = 0; bit < L.bits; bit += 8) {
+            hipLaunchKernelGGL(k_radix_upsweep, dim3(ntiles), dim3(MT_THREADS), 0, c->stream, kin, m, bit, hist.as<uint32_t>(), (uint32_t)ntiles);
+            hipLaunchKernelGGL(k_radix_scan, dim3(MT_RADIX), dim3(MT_THREADS), 0, c->stream, hist.as<uint32_t>(), (uint32_t)ntiles,
+                               tot.as<uint32_t>());
+            hipLaunchKernelGGL(k_radix_downsweep, dim3(ntiles), dim3(MT_THREADS), 0, c->stream, kin, iin, kout, iout, m, L.nwords, bit,
+                               hist.as<uint32_t>(), tot.as<uint32_t>(), (uint32_t)ntiles);
+            ZKM_HIP_CHECK(hipGetLastError());
+            std::swap(kin, kout);
+            std::swap(iin, iout);
+        }
+    }
+    j.idx = iin;
+    // gaps and their scan: start[i] = first row of sorted op i, start[nops] = rows before padding
+    j.M = next_pow2(nops) - 1;
+    j.start = zkm_scratch(c, (nops + 1) * 8);
+    uint64_t* d_start = j.start.as<uint64_t>();
+    const size_t len = nops + 1, nparts = blocks_for(len, MT_TILE);
+    zkm_scratch part(c, nparts * 8);
+    {
+        zkm_prof_scope ps(c, "memory_trace/gaps");
+        ZKM_HIP_CHECK(hipMemsetAsync(d_start + nops, 0, 8, c->stream));
+        hipLaunchKernelGGL(k_mem_gaps, dim3(blocks_for(nops, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, j.d_ops, iin, m, j.M, d_start,
+                           (unsigned*)(j.d_acc + 5));
+        hipLaunchKernelGGL(k_scan_tiles, dim3(nparts), dim3(MT_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
+        hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(MT_THREADS), 0, c->stream, part.as<uint64_t>(), nparts);
+        hipLaunchKernelGGL(k_scan_apply, dim3(nparts), dim3(MT_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+}
+
+size_t zkm_memory_height(zkm_memory_job& j, uint64_t count, size_t* natural_rows_out) {
+    if (count >= MT_SAT) {
+        if (natural_rows_out) *natural_rows_out = (size_t)MT_SAT;
+        throw std::runtime_error(std::string(j.what) + ": the dummy rows of fill_gaps do not fit (2^62 rows or more)");
+    }
+    j.count = count;
+    const size_t natural = next_pow2(count);
+    if (natural_rows_out) *natural_rows_out = natural;
+    return natural;
+}
+
+void zkm_memory_write(zkm_memory_job& j, unsigned log_n, gl_t* out_dev, int* d_bad) {
+    zkm_ctx* c = j.c;
+    const size_t n = (size_t)1 << log_n;
+    {
+        zkm_prof_scope ps(c, "memory_trace/rows");
+        rows_args A{j.d_ops, j.idx, j.start.as<uint64_t>(), (const unsigned*)(j.d_acc + 5), (uint32_t)j.nops, j.M, n - j.count, n};
+        hipLaunchKernelGGL(k_mem_rows, dim3(blocks_for(n, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, A, out_dev);
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+    {
+        zkm_prof_scope ps(c, "memory_trace/neighbours");
+        ZKM_HIP_CHECK(hipMemsetAsync(out_dev + 12 * n, 0, n * 8, c->stream));
+        hipLaunchKernelGGL(k_mem_neighbours, dim3(std::min<size_t>(blocks_for(n, MT_THREADS), 1024)), dim3(MT_THREADS), 0, c->stream,
+                           out_dev, n, d_bad);
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+}
+
 extern "C" int zkm_memory_trace(zkm_ctx* c, const uint64_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, size_t* natural_rows_out,
                                 char** err) {
     return zkm_api("zkm_memory_trace", c, err, [&] {
@@ -332,101 +437,26 @@ extern "C" int zkm_memory_trace(zkm_ctx* c, const uint64_t* ops, size_t nops, un
                 throw std::runtime_error("zkm_memory_trace: log_n " + std::to_string(log_n) + " above the cap " + std::to_string(MT_MAX_LOG_N));
             if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_memory_trace: out must be a device pointer");
         }
-        const uint32_t m = (uint32_t)nops;
         zkm_scratch_list host_copy(c);
         const uint64_t* d_ops = ops;
         if (!zkm_is_device_ptr(ops)) {
             d_ops = host_copy.alloc<uint64_t>(nops * 48);
             ZKM_HIP_CHECK(hipMemcpyAsync((void*)d_ops, ops, nops * 48, hipMemcpyHostToDevice, c->stream));
         }
-        // small: [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies, [6] range-check flag
-        zkm_scratch small(c, 64);
-        unsigned long long* d_acc = small.as<unsigned long long>();
-        unsigned* d_last = (unsigned*)(d_acc + 5);
-        int* d_bad = (int*)(d_acc + 6);
-        ZKM_HIP_CHECK(hipMemsetAsync(small.p, 0, 64, c->stream));
-        {
-            zkm_prof_scope ps(c, "memory_trace/widths");
-            hipLaunchKernelGGL(k_mem_widths, dim3(std::min<size_t>(blocks_for(nops, MT_THREADS), 1024)), dim3(MT_THREADS), 0, c->stream,
-                               d_ops, nops, d_acc);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
+        zkm_memory_job j(c, "zkm_memory_trace", d_ops, nops);
+        zkm_memory_widths(j);
         uint64_t acc[5];
-        c->download(acc, d_acc, sizeof(acc));
-        if (acc[4]) throw std::runtime_error("zkm_memory_trace: a context, segment, virt or timestamp word is not below p");
-        // key layout: timestamp lowest, then virt, segment, context
-        key_layout L{};
-        unsigned sh = 0;
-        for (int f = 3; f >= 0; f--) {
-            L.width[f] = bit_width(acc[f]);
-            L.shift[f] = sh;
-            sh += L.width[f];
-        }
-        L.bits = sh;
-        L.nwords = sh ? (sh + 63) / 64 : 1;
-        const size_t K = L.nwords, ntiles = blocks_for(nops, MT_TILE);
-        zkm_scratch keys_a(c, K * nops * 8), keys_b(c, K * nops * 8), idx_a(c, nops * 4), idx_b(c, nops * 4);
-        uint64_t *kin = keys_a.as<uint64_t>(), *kout = keys_b.as<uint64_t>();
-        uint32_t *iin = idx_a.as<uint32_t>(), *iout = idx_b.as<uint32_t>();
-        {
-            zkm_prof_scope ps(c, "memory_trace/pack");
-            hipLaunchKernelGGL(k_mem_pack, dim3(blocks_for(nops, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, d_ops, m, L, kin, iin);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        if (nops > 1 && L.bits) {
-            zkm_scratch hist(c, (size_t)MT_RADIX * ntiles * 4), tot(c, MT_RADIX * 4);
-            zkm_prof_scope ps(c, "memory_trace/sort");
-            for (unsigned bit = 0; bit < L.bits; bit += 8) {
-                hipLaunchKernelGGL(k_radix_upsweep, dim3(ntiles), dim3(MT_THREADS), 0, c->stream, kin, m, bit, hist.as<uint32_t>(), (uint32_t)ntiles);
-                hipLaunchKernelGGL(k_radix_scan, dim3(MT_RADIX), dim3(MT_THREADS), 0, c->stream, hist.as<uint32_t>(), (uint32_t)ntiles,
-                                   tot.as<uint32_t>());
-                hipLaunchKernelGGL(k_radix_downsweep, dim3(ntiles), dim3(MT_THREADS), 0, c->stream, kin, iin, kout, iout, m, L.nwords, bit,
-                                   hist.as<uint32_t>(), tot.as<uint32_t>(), (uint32_t)ntiles);
-                ZKM_HIP_CHECK(hipGetLastError());
-                std::swap(kin, kout);
-                std::swap(iin, iout);
-            }
-        }
-        // gaps and their scan: start[i] = first row of sorted op i, start[nops] = rows before padding
-        const uint64_t M = next_pow2(nops) - 1;
-        zkm_scratch start(c, (nops + 1) * 8);
-        uint64_t* d_start = start.as<uint64_t>();
-        const size_t len = nops + 1, nparts = blocks_for(len, MT_TILE);
-        zkm_scratch part(c, nparts * 8);
-        {
-            zkm_prof_scope ps(c, "memory_trace/gaps");
-            ZKM_HIP_CHECK(hipMemsetAsync(d_start + nops, 0, 8, c->stream));
-            hipLaunchKernelGGL(k_mem_gaps, dim3(blocks_for(nops, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, d_ops, iin, m, M, d_start, d_last);
-            hipLaunchKernelGGL(k_scan_tiles, dim3(nparts), dim3(MT_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
-            hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(MT_THREADS), 0, c->stream, part.as<uint64_t>(), nparts);
-            hipLaunchKernelGGL(k_scan_apply, dim3(nparts), dim3(MT_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
+        c->download(acc, j.d_acc, sizeof(acc));
+        zkm_memory_sort(j, acc);
         uint64_t count = 0;
-        c->download(&count, d_start + nops, 8);
-        if (count >= MT_SAT) {
-            if (natural_rows_out) *natural_rows_out = (size_t)MT_SAT;
-            throw std::runtime_error("zkm_memory_trace: the dummy rows of fill_gaps do not fit (2^62 rows or more)");
-        }
-        const size_t natural = next_pow2(count);
-        if (natural_rows_out) *natural_rows_out = natural;
+        c->download(&count, j.start.as<uint64_t>() + nops, 8);
+        const size_t natural = zkm_memory_height(j, count, natural_rows_out);
         if (!out_dev) return;
         const size_t n = (size_t)1 << log_n;
         if (natural > n)
             throw std::runtime_error("zkm_memory_trace: the table needs " + std::to_string(natural) + " rows, more than 2^" + std::to_string(log_n));
-        {
-            zkm_prof_scope ps(c, "memory_trace/rows");
-            rows_args A{d_ops, iin, d_start, d_last, m, M, n - count, n};
-            hipLaunchKernelGGL(k_mem_rows, dim3(blocks_for(n, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, A, out_dev);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        {
-            zkm_prof_scope ps(c, "memory_trace/neighbours");
-            ZKM_HIP_CHECK(hipMemsetAsync(out_dev + 12 * n, 0, n * 8, c->stream));
-            hipLaunchKernelGGL(k_mem_neighbours, dim3(std::min<size_t>(blocks_for(n, MT_THREADS), 1024)), dim3(MT_THREADS), 0, c->stream,
-                               out_dev, n, d_bad);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
+        int* d_bad = (int*)(j.d_acc + 6);
+        zkm_memory_write(j, log_n, out_dev, d_bad);
         int bad = 0;
         c->download(&bad, d_bad, sizeof(bad));
         if (bad) throw std::runtime_error("zkm_memory_trace: a range check is 2^log_n or more (a context or segment gap)");

@@ -425,6 +425,43 @@ void zkm_launch_sha_compress_trace(zkm_ctx* c, bool sponge, const uint32_t* d_hx
 void zkm_launch_keccak_trace(zkm_ctx* c, const uint64_t* d_inputs, const uint64_t* d_ts, size_t nperms, size_t n, gl_t* out);
 void zkm_launch_logic_trace(zkm_ctx* c, const uint32_t* d_ops, size_t nops, size_t n, gl_t* out, int* d_bad);
 
+// ---- the two witnesses whose heights need the device, in phases: zkm_memory_trace / zkm_arithmetic_trace run each one's phases back
+// to back with a host wait between them; segment_ops.hip runs the phases of both side by side, so that one wait serves both.  A phase
+// throws with `what` in front of its message; the job owns its scratch blocks until it goes.
+// memory_trace.hip: widths (queues the OR of the key fields into d_acc[0..5)) -> the host reads d_acc -> sort (sort, gaps, scan: the row
+// count before padding lands at start[nops]) -> the host reads it -> height -> write (rows and neighbours; *d_bad set on a range check
+// of 2^log_n or more)
+struct zkm_memory_job {
+    zkm_ctx* c;
+    const char* what;
+    const uint64_t* d_ops;       // nops x 6 words, device
+    size_t nops;
+    zkm_scratch small, keys_a, keys_b, idx_a, idx_b, start;
+    unsigned long long* d_acc = nullptr;   // in `small`: [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies, [6] free
+    const uint32_t* idx = nullptr;         // sorted order
+    uint64_t M = 0, count = 0;
+    zkm_memory_job(zkm_ctx* ctx, const char* w, const uint64_t* ops, size_t n) : c(ctx), what(w), d_ops(ops), nops(n) {}
+};
+void zkm_memory_widths(zkm_memory_job& j);
+void zkm_memory_sort(zkm_memory_job& j, const uint64_t acc[5]);
+size_t zkm_memory_height(zkm_memory_job& j, uint64_t count, size_t* natural_rows_out);   // next_pow2(count); throws if it saturated
+void zkm_memory_write(zkm_memory_job& j, unsigned log_n, gl_t* out_dev, int* d_bad);
+// arithmetic_trace.hip: count (validation flags and the scan of the row counts: rows at start[nops], flags at start[nops + 1]) -> the
+// host reads both -> height -> write (rows, RC_FREQUENCIES; *d_bad set on a shared-column value of 2^16 or more)
+struct zkm_arith_job {
+    zkm_ctx* c;
+    const char* what;
+    const uint32_t* d_ops;       // nops x 3 words, device (may be null when nops = 0)
+    size_t nops;
+    zkm_scratch start, hist;
+    uint64_t rows = 0;
+    zkm_arith_job(zkm_ctx* ctx, const char* w, const uint32_t* ops, size_t n) : c(ctx), what(w), d_ops(ops), nops(n) {}
+    uint64_t* counts() const { return start.as<uint64_t>() + nops; }   // {rows, flags}: the two words the host reads
+};
+void zkm_arithmetic_count(zkm_arith_job& j);
+size_t zkm_arithmetic_height(zkm_arith_job& j, const uint64_t got[2], size_t* natural_rows_out);   // max(2^16, next_pow2(rows)); throws on a flag
+void zkm_arithmetic_write(zkm_arith_job& j, unsigned log_n, gl_t* out_dev, unsigned* d_bad);
+
 // ctl.hip: the body of zkm_prove_segments[_columns] (exactly one of traces / columns non-null); seg_base = position of segment 0 in the
 // caller's larger call (csrc/pool.hip deals groups of one pool call to its workers) -- used in error messages only
 extern "C" int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const uint64_t* const* const* traces,
