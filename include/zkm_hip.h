@@ -621,6 +621,49 @@ int zkm_segment_tables(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_segm
 int zkm_prove_segment_ops(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_segment_ops* ops, const uint64_t* public_values, size_t npublic,
                           uint64_t* proofs_out, size_t* proof_offsets_out, uint64_t* ctl_challenges_out, char** err);
 
+/* K segments' tables in one call: K x Traces::into_tables with the segment as a grid dimension -- every generation kernel is launched
+ * ONCE for all K (heights may differ: the grid is the largest segment's), and the call has the THREE host waits of zkm_segment_tables
+ * whatever K (one download each of all K key widths and Arithmetic counts, all K Memory row counts, all K validation flag triples).
+ *   ops         nseg zkm_segment_ops, each as zkm_segment_tables takes it (any mix of pageable, pinned and device memory, or the
+ *               pointers of zkm_staged_ops_get); more than 32 segments are built in consecutive groups
+ *   log_n_out   log_n_out[12 * s + t]: height of table t (Table::all() order) of segment s
+ *   out         out[s]: a segment-shaped zkm_staged each (one block per segment: free each on its own), word for word what
+ *               zkm_segment_tables gives for that segment alone.  NULL: sizing only.
+ * Every refusal of zkm_segment_tables applies per segment; the message names the segment's position in the call before the table
+ * ("zkm_segments_tables: segment 1: Logic: ...").  nseg = 0 and NULL ops are refused.  A failure leaves the context usable, its live
+ * memory as it was, and no handle behind. */
+int zkm_segments_tables(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops, unsigned* log_n_out,
+                        zkm_staged** out, char** err);
+/* zkm_segments_tables, zkm_prove_segments on the blocks (lock-step: one launch per stage for all of them), the blocks freed: K x
+ * (into_tables + prove_with_traces) in one call.  public_values / npublic / proofs_out / ctl_challenges_out as zkm_prove_segments;
+ * every blob and every challenge is word for word what zkm_prove_segment_ops returns for that segment alone.
+ *   proof_offsets_out   proof_offsets_out[13 * s + i] as zkm_prove_segment_ops gives them for segment s (may be NULL when proving)
+ *   proofs_out = NULL   sizing: only the heights are found (two host waits per 32 segments) and proof_offsets_out is filled
+ * More than 32 segments, or more than the context's "segments_memory_budget" holds -- estimated as for zkm_prove_segments, plus the
+ * built tables and the staging block -- are built and proven in consecutive, equally sized waves; the words do not depend on the
+ * waves.  Refusals and failures as zkm_segments_tables and zkm_prove_segments (positions are those in the call). */
+int zkm_prove_segments_ops(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops,
+                           const uint64_t* const* public_values, const size_t* npublic, uint64_t* const* proofs_out, size_t* proof_offsets_out,
+                           uint64_t* const* ctl_challenges_out, char** err);
+
+/* Staged operations: the NEXT call's lists behind the CURRENT proofs (the counterpart of zkm_segment_stage for operations).  Every
+ * byte count of a segment's lists is known on the host, so zkm_segment_ops_stage queues the uploads -- one block of the context's
+ * allocator for the CPU rows and every list, alternate pieces on the context's two copy streams, behind what the compute stream has
+ * queued -- and RETURNS AT ONCE.  The checks that need no device (NULL pointers, the CPU row count, the sponge offsets, zero memory
+ * operations) run here and refuse here.
+ *   zkm_staged_ops_get     the same segment with device pointers, for zkm_segment[s]_tables / zkm_prove_segment[s]_ops ON THE SAME
+ *                          CONTEXT (another context is refused): that call is ordered behind the upload on the device -- the compute
+ *                          stream waits for the copies, every other stream of the call waits for the compute stream -- with no host
+ *                          wait.  The two sponge offset arrays, which the builder reads on the host, point at the handle's own copy.
+ *   zkm_staged_ops_ready   1: the uploads have landed -- every list of the caller, offsets included, may be reused; 0: in flight;
+ *                          -1: a runtime error.  wait != 0 blocks until they have.
+ *   zkm_staged_ops_free    after the call that consumed the handle has returned (waits for the uploads, releases the block). */
+typedef struct zkm_staged_ops zkm_staged_ops;
+int zkm_segment_ops_stage(zkm_ctx* ctx, const zkm_segment_ops* ops, zkm_staged_ops** out, char** err);
+int zkm_staged_ops_get(zkm_staged_ops* staged, zkm_segment_ops* ops_out);
+int zkm_staged_ops_ready(zkm_staged_ops* staged, int wait);
+void zkm_staged_ops_free(zkm_staged_ops* staged);
+
 /* ------------------------------------------------------------------ one process, many GPUs: a pool of contexts
  * The reference drives all segments of a program from ONE process (prover/examples/utils/src/utils.rs:57-68 prove_single_seg_common,
  * :105-133 prove_multi_seg_common: a loop of prove_with_traces calls); segments are independent proofs, so N GPUs take them
@@ -650,6 +693,12 @@ int zkm_pool_prove_segments_columns(zkm_pool* pool, const zkm_stark_config* cfg,
                                     const uint64_t* const* const* const* columns, const unsigned* const* log_n,
                                     const uint64_t* const* public_values, const size_t* npublic, uint64_t* const* proofs_out,
                                     uint64_t* const* ctl_challenges_out, char** err);
+/* The pool takes operations: the same groups, each ONE zkm_prove_segments_ops call on its worker's context (tables built and proven
+ * there).  ops / proof_offsets_out as zkm_prove_segments_ops; the lists must be host memory unless the pool has one device.
+ * proofs_out = NULL sizes (the groups spread over the workers as in a proving call).  zkm_pool_last_assignment works after it. */
+int zkm_pool_prove_segments_ops(zkm_pool* pool, const zkm_stark_config* cfg, size_t nseg, size_t max_stack, const zkm_segment_ops* ops,
+                                const uint64_t* const* public_values, const size_t* npublic, uint64_t* const* proofs_out,
+                                size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
 /* The groups a pool call of nseg segments is cut into for `workers` workers (a pure function: no pool, no GPU): returns their number and
  * writes the first min(capacity, number) sizes, in segment order.  20 segments, 2 workers, max_stack 4 -> 4, 4, 3, 3, 3, 3. */
 size_t zkm_pool_plan(size_t nseg, size_t workers, size_t max_stack, size_t* group_sizes_out, size_t capacity);

@@ -1,5 +1,7 @@
 //! segment_hip.rs -- a whole segment's tables (Traces::into_tables, witness/traces.rs:230-320) built by libzkmhip.so from the
-//! segment's raw operations (zkm_segment_tables / zkm_prove_segment_ops, include/zkm_hip.h), and its proof in one call.
+//! segment's raw operations (zkm_segment_tables / zkm_prove_segment_ops, include/zkm_hip.h), and its proof in one call; K segments
+//! built in one set of launches and proven in lock-step (zkm_prove_segments_ops), their lists staged behind the proofs in flight
+//! (StagedOps), and a pool's workers taking operations (prove_segments_ops_pool_hip).
 //!
 //! Goes into the zkm-prover crate as `prover/src/segment_hip.rs`, beside `prove_hip.rs`, `memory_hip.rs` and `arithmetic_hip.rs`;
 //! `generate_traces` -> `into_tables` -> `prove_with_traces` (generation/mod.rs:25-76) becomes `prove_segment_ops_hip` when the `hip`
@@ -8,7 +10,7 @@
 //!     impl Operation { pub(crate) fn hip_words(&self) -> [u32; 3] { [self.operator as u32, self.input0, self.input1] } }
 //!
 //! (Op is And, Or, Xor, Nor in that order: the op codes 0 .. 3 of zkm_logic_trace.)  The reference items used here are checked by
-//! tests/test_rust_segment_names.py.  NOT COMPILED in the build image (no cargo / rustc there).
+//! tests/test_rust_segment_names.py and tests/test_rust_segments_ops_names.py.  NOT COMPILED in the build image (no cargo / rustc there).
 use anyhow::{ensure, Result};
 use plonky2::field::types::PrimeField64;
 use plonky2::hip::sys::*;
@@ -208,4 +210,89 @@ pub fn prove_segment_ops_hip<F: PrimeField64>(ctx: *mut zkm_ctx, traces: &Traces
     check(unsafe { zkm_prove_segment_ops(ctx, config, &ops, public_values.as_ptr(), public_values.len(), proofs.as_mut_ptr(),
                                          offs.as_mut_ptr(), challenges.as_mut_ptr(), &mut err) }, err)?;
     Ok((proofs, offs, challenges))
+}
+
+/// One (proof blobs, offsets, CTL challenges) per segment, as `prove_segment_ops_hip` returns them.
+pub type SegmentProofs = Vec<(Vec<u64>, [usize; 13], Vec<u64>)>;
+
+/// The two calls of a K-segment entry point -- sizing, then proving into buffers of those sizes -- behind one closure:
+/// `call(public_values, npublic, proofs_out, proof_offsets_out, ctl_challenges_out, err)`.
+fn size_then_prove(nseg: usize, public_values: &[&[u64]], num_challenges: usize,
+                   call: impl Fn(*const *const u64, *const usize, *const *mut u64, *mut usize, *const *mut u64, *mut *mut std::os::raw::c_char) -> i32)
+                   -> Result<SegmentProofs> {
+    ensure!(public_values.len() == nseg, "{} public value lists for {} segments", public_values.len(), nseg);
+    let pub_ptrs: Vec<*const u64> = public_values.iter().map(|p| p.as_ptr()).collect();
+    let pub_lens: Vec<usize> = public_values.iter().map(|p| p.len()).collect();
+    let mut offs = vec![0usize; 13 * nseg];
+    let mut err = std::ptr::null_mut();
+    check(call(pub_ptrs.as_ptr(), pub_lens.as_ptr(), std::ptr::null(), offs.as_mut_ptr(), std::ptr::null(), &mut err), err)?;
+    let mut proofs: Vec<Vec<u64>> = (0..nseg).map(|s| vec![0u64; offs[13 * s + 12]]).collect();
+    let mut challenges: Vec<Vec<u64>> = (0..nseg).map(|_| vec![0u64; 2 * num_challenges]).collect();
+    let proof_ptrs: Vec<*mut u64> = proofs.iter_mut().map(|p| p.as_mut_ptr()).collect();
+    let chal_ptrs: Vec<*mut u64> = challenges.iter_mut().map(|c| c.as_mut_ptr()).collect();
+    check(call(pub_ptrs.as_ptr(), pub_lens.as_ptr(), proof_ptrs.as_ptr(), offs.as_mut_ptr(), chal_ptrs.as_ptr(), &mut err), err)?;
+    Ok(proofs.into_iter().zip(challenges).enumerate().map(|(s, (p, c))| {
+        let mut seg_offs = [0usize; 13];
+        seg_offs.copy_from_slice(&offs[13 * s..13 * s + 13]);
+        (p, seg_offs, c)
+    }).collect())
+}
+
+/// K x (`into_tables` + `prove_with_traces`) in one call: every generation kernel is launched once for all K segments, the call has
+/// three host waits whatever K, and the proofs advance in lock-step.  Each result is word for word `prove_segment_ops_hip`'s.
+pub fn prove_segments_ops_hip<F: PrimeField64>(ctx: *mut zkm_ctx, segments: &[Traces<F>], config: &zkm_stark_config, public_values: &[&[u64]])
+                                               -> Result<SegmentProofs> {
+    let hosts = segments.iter().map(segment_ops_host).collect::<Result<Vec<_>>>()?;
+    let ops: Vec<zkm_segment_ops> = hosts.iter().map(|h| h.ops()).collect();
+    prove_segments_ops_raw(ctx, &ops, config, public_values)
+}
+
+/// ... on zkm_segment_ops the caller holds: host lists, or the device lists of `StagedOps::ops` (same context), mixed.
+pub fn prove_segments_ops_raw(ctx: *mut zkm_ctx, ops: &[zkm_segment_ops], config: &zkm_stark_config, public_values: &[&[u64]])
+                              -> Result<SegmentProofs> {
+    size_then_prove(ops.len(), public_values, config.num_challenges as usize, |pv, npv, proofs, offs, chal, err| unsafe {
+        zkm_prove_segments_ops(ctx, config, ops.len(), ops.as_ptr(), pv, npv, proofs, offs, chal, err)
+    })
+}
+
+/// A segment's lists on their way into HBM behind the context's current work (zkm_segment_ops_stage): stage the next call's segments
+/// while the current call proves, hand `ops()` to `prove_segments_ops_raw` on the same context, drop after that call has returned.
+/// `host` may be dropped or reused once `ready(true)` has returned: the handle keeps its own copy of the two sponge offset arrays.
+pub struct StagedOps(*mut zkm_staged_ops);
+impl StagedOps {
+    pub fn new(ctx: *mut zkm_ctx, host: &SegmentOpsHost) -> Result<Self> {
+        let ops = host.ops();
+        let mut staged = std::ptr::null_mut();
+        let mut err = std::ptr::null_mut();
+        check(unsafe { zkm_segment_ops_stage(ctx, &ops, &mut staged, &mut err) }, err)?;
+        Ok(Self(staged))
+    }
+    /// The same segment with device pointers, ordered behind the upload on the device (no host wait).
+    pub fn ops(&self) -> Result<zkm_segment_ops> {
+        let mut ops = std::mem::MaybeUninit::<zkm_segment_ops>::zeroed();
+        ensure!(unsafe { zkm_staged_ops_get(self.0, ops.as_mut_ptr()) } == 0, "zkm_staged_ops_get failed");
+        Ok(unsafe { ops.assume_init() })
+    }
+    /// Have the uploads landed?  `wait` blocks until they have.
+    pub fn ready(&self, wait: bool) -> Result<bool> {
+        let r = unsafe { zkm_staged_ops_ready(self.0, wait as i32) };
+        ensure!(r >= 0, "zkm_staged_ops_ready: runtime error");
+        Ok(r == 1)
+    }
+}
+impl Drop for StagedOps {
+    fn drop(&mut self) {
+        unsafe { zkm_staged_ops_free(self.0) };
+    }
+}
+
+/// All segments of a program over the pool's contexts, from their raw operations: the groups of `prove_segments_multi_hip`, each ONE
+/// zkm_prove_segments_ops call on its worker's context.  `pool` is the `*mut zkm_pool` of a `HipPool` (prove_hip.rs).
+pub fn prove_segments_ops_pool_hip<F: PrimeField64>(pool: *mut zkm_pool, segments: &[Traces<F>], config: &zkm_stark_config, max_stack: usize,
+                                                    public_values: &[&[u64]]) -> Result<SegmentProofs> {
+    let hosts = segments.iter().map(segment_ops_host).collect::<Result<Vec<_>>>()?;
+    let ops: Vec<zkm_segment_ops> = hosts.iter().map(|h| h.ops()).collect();
+    size_then_prove(ops.len(), public_values, config.num_challenges as usize, |pv, npv, proofs, offs, chal, err| unsafe {
+        zkm_pool_prove_segments_ops(pool, config, ops.len(), max_stack, ops.as_ptr(), pv, npv, proofs, offs, chal, err)
+    })
 }

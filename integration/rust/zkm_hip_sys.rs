@@ -14,6 +14,7 @@ use std::os::raw::{c_char, c_double, c_int, c_uint, c_void};
 #[repr(C)] pub struct zkm_batch { _p: [u8; 0] }
 #[repr(C)] pub struct zkm_pool { _p: [u8; 0] }
 #[repr(C)] pub struct zkm_staged { _p: [u8; 0] }
+pub enum zkm_staged_ops {}   // opaque: only ever behind a pointer
 
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct zkm_challenger { pub state: [u64; 12], pub in_buf: [u64; 8], pub out_buf: [u64; 8], pub n_in: u32, pub n_out: u32 }
@@ -216,6 +217,17 @@ extern "C" {
     pub fn zkm_prove_segment_ops(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, ops: *const zkm_segment_ops, public_values: *const u64,
                                  npublic: usize, proofs_out: *mut u64, proof_offsets_out: *mut usize, ctl_challenges_out: *mut u64,
                                  err: *mut *mut c_char) -> c_int;
+    // K segments from their raw operations: every generation kernel launched once for all K, three host waits, lock-step proofs
+    pub fn zkm_segments_tables(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, ops: *const zkm_segment_ops, log_n_out: *mut c_uint,
+                               out: *mut *mut zkm_staged, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_prove_segments_ops(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, ops: *const zkm_segment_ops,
+                                  public_values: *const *const u64, npublic: *const usize, proofs_out: *const *mut u64,
+                                  proof_offsets_out: *mut usize, ctl_challenges_out: *const *mut u64, err: *mut *mut c_char) -> c_int;
+    // staged operations: the next call's lists uploaded behind the current proofs
+    pub fn zkm_segment_ops_stage(ctx: *mut zkm_ctx, ops: *const zkm_segment_ops, out: *mut *mut zkm_staged_ops, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_staged_ops_get(staged: *mut zkm_staged_ops, ops_out: *mut zkm_segment_ops) -> c_int;
+    pub fn zkm_staged_ops_ready(staged: *mut zkm_staged_ops, wait: c_int) -> c_int;
+    pub fn zkm_staged_ops_free(staged: *mut zkm_staged_ops);
     // one process, many GPUs: contexts_per_device contexts on each device, one worker thread per context, groups of <= max_stack segments
     pub fn zkm_pool_create(devices: *const c_int, ndevices: usize, contexts_per_device: usize, out: *mut *mut zkm_pool, err: *mut *mut c_char) -> c_int;
     pub fn zkm_pool_destroy(pool: *mut zkm_pool);
@@ -231,6 +243,10 @@ extern "C" {
                                            columns: *const *const *const *const u64, log_n: *const *const c_uint,
                                            public_values: *const *const u64, npublic: *const usize, proofs_out: *const *mut u64,
                                            ctl_challenges_out: *const *mut u64, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_pool_prove_segments_ops(pool: *mut zkm_pool, cfg: *const zkm_stark_config, nseg: usize, max_stack: usize,
+                                       ops: *const zkm_segment_ops, public_values: *const *const u64, npublic: *const usize,
+                                       proofs_out: *const *mut u64, proof_offsets_out: *mut usize, ctl_challenges_out: *const *mut u64,
+                                       err: *mut *mut c_char) -> c_int;
     pub fn zkm_pool_plan(nseg: usize, workers: usize, max_stack: usize, group_sizes_out: *mut usize, capacity: usize) -> usize;
     pub fn zkm_pool_last_assignment(pool: *const zkm_pool, segment: usize, worker_out: *mut usize, group_out: *mut usize) -> c_int;
     pub fn zkm_prove_single_tables(ctx: *mut zkm_ctx, table_id: c_int, cfg: *const zkm_stark_config, nproofs: usize, traces: *const *const u64,

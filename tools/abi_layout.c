@@ -16,8 +16,30 @@
                  first_struct = 0, first_field = 1
 #define END() printf("]}")
 
+/* The K-segment entry points held to the argument types their callers (ctypes, Rust, C) rely on: a changed prototype fails this
+ * file's build.  The assignments sit inside sizeof -- type-checked, never evaluated -- so the file still links without the library. */
+static void check_segments_ops_prototypes(void) {
+    int (*tables)(zkm_ctx*, const zkm_stark_config*, size_t, const zkm_segment_ops*, unsigned*, zkm_staged**, char**) = 0;
+    int (*prove)(zkm_ctx*, const zkm_stark_config*, size_t, const zkm_segment_ops*, const uint64_t* const*, const size_t*, uint64_t* const*,
+                 size_t*, uint64_t* const*, char**) = 0;
+    int (*pool)(zkm_pool*, const zkm_stark_config*, size_t, size_t, const zkm_segment_ops*, const uint64_t* const*, const size_t*,
+                uint64_t* const*, size_t*, uint64_t* const*, char**) = 0;
+    int (*stage)(zkm_ctx*, const zkm_segment_ops*, zkm_staged_ops**, char**) = 0;
+    int (*get)(zkm_staged_ops*, zkm_segment_ops*) = 0;
+    int (*ready)(zkm_staged_ops*, int) = 0;
+    void (*release)(zkm_staged_ops*) = 0;
+    (void)sizeof(tables = zkm_segments_tables);
+    (void)sizeof(prove = zkm_prove_segments_ops);
+    (void)sizeof(pool = zkm_pool_prove_segments_ops);
+    (void)sizeof(stage = zkm_segment_ops_stage);
+    (void)sizeof(get = zkm_staged_ops_get);
+    (void)sizeof(ready = zkm_staged_ops_ready);
+    (void)sizeof(release = zkm_staged_ops_free);
+}
+
 int main(void) {
     int first_struct = 1, first_field = 1;
+    check_segments_ops_prototypes();
     printf("{");
     BEGIN(zkm_challenger);
     FIELD(zkm_challenger, state); FIELD(zkm_challenger, in_buf); FIELD(zkm_challenger, out_buf); FIELD(zkm_challenger, n_in);

@@ -1,6 +1,6 @@
 /* tools/c_smoke.c -- the C ABI used from plain C99, no Python anywhere: read a ZKMTRACE segment image from a file, prove it with
  * zkm_prove_segment_image (and, for a twelve-table image, twice more in one zkm_prove_segments call and three times through a zkm_pool of
- * two workers), write the proof blobs to a file.  The reference-side caller of this boundary is Rust over FFI
+ * two workers; then two tiny segments from their raw operations in one zkm_prove_segments_ops call), write the proof blobs to a file.  The reference-side caller of this boundary is Rust over FFI
  * (its only existing FFI has this very shape: recursion/src/snark/snarks.rs:7-20, 39-59 -- int status, char** message
  * freed by the caller); this file is the proof that include/zkm_hip.h is usable as it stands by a C compiler in pedantic mode.
  *
@@ -16,6 +16,49 @@
 #include <string.h>
 
 #include "zkm_hip.h"
+
+/* Two tiny segments from their RAW OPERATIONS in one zkm_prove_segments_ops call (tables built in one set of launches, proofs in
+ * lock-step): 64 and 128 zero CPU rows, three memory operations each, every other list empty.  Each blob must equal
+ * zkm_prove_segment_ops' for that segment alone.  Returns NULL on success, else what went wrong (*err: the library's message). */
+static const char* segments_ops_smoke(zkm_ctx* ctx, const zkm_stark_config* cfg, char** err) {
+    static const uint64_t mem[2][18] = {{0, 2, 5, 1, 0, 7, 0, 2, 5, 2, 1, 7, 0, 2, 9, 3, 0, 11}, {0, 1, 4, 1, 0, 3, 0, 1, 4, 5, 1, 3, 0, 3, 8, 2, 0, 9}};
+    static const uint64_t pub0[2] = {1, 2}, pub1[1] = {3};
+    const uint64_t* pubs[2];
+    size_t npubs[2] = {2, 1}, offs[26], one_offs[13], s;
+    zkm_segment_ops ops[2];
+    uint64_t *cpu, *proofs[2] = {NULL, NULL}, *one = NULL, *chal[2], chal_words[2][8], one_chal[8];
+    const char* bad = NULL;
+    pubs[0] = pub0;
+    pubs[1] = pub1;
+    cpu = (uint64_t*)calloc((size_t)128 * ZKM_CPU_COLS, 8);
+    if (!cpu) return "out of host memory";
+    memset(ops, 0, sizeof ops);
+    for (s = 0; s < 2; s++) {
+        ops[s].cpu_rows = cpu;
+        ops[s].ncpu_rows = (size_t)64 << s;
+        ops[s].memory_ops = mem[s];
+        ops[s].nmemory = 3;
+        chal[s] = chal_words[s];
+    }
+    if (zkm_prove_segments_ops(ctx, cfg, 2, ops, pubs, npubs, NULL, offs, NULL, err)) bad = "zkm_prove_segments_ops (sizing)";
+    for (s = 0; s < 2 && !bad; s++)
+        if (!(proofs[s] = (uint64_t*)malloc(offs[13 * s + 12] * 8))) bad = "out of host memory";
+    if (!bad && zkm_prove_segments_ops(ctx, cfg, 2, ops, pubs, npubs, proofs, offs, chal, err)) bad = "zkm_prove_segments_ops";
+    for (s = 0; s < 2 && !bad; s++) {
+        if (zkm_prove_segment_ops(ctx, cfg, &ops[s], pubs[s], npubs[s], NULL, one_offs, NULL, err)) bad = "zkm_prove_segment_ops (sizing)";
+        else if (memcmp(one_offs, offs + 13 * s, sizeof one_offs) != 0) bad = "the offsets of the two-segment call differ from the one-segment call's";
+        else if (!(one = (uint64_t*)malloc(one_offs[12] * 8))) bad = "out of host memory";
+        else if (zkm_prove_segment_ops(ctx, cfg, &ops[s], pubs[s], npubs[s], one, one_offs, one_chal, err)) bad = "zkm_prove_segment_ops";
+        else if (memcmp(one, proofs[s], one_offs[12] * 8) != 0 || memcmp(one_chal, chal[s], 4 * 8) != 0)
+            bad = "a proof of the two-segment call differs from the one-segment call's";
+        free(one);
+        one = NULL;
+    }
+    free(proofs[0]);
+    free(proofs[1]);
+    free(cpu);
+    return bad;
+}
 
 static int die(const char* what, char* err) {
     fprintf(stderr, "c_smoke: %s: %s\n", what, err ? err : "(no message)");
@@ -116,6 +159,11 @@ int main(int argc, char** argv) {
             zkm_pool_destroy(pool);
             for (k = 0; k < 3; k++) free(p_proofs[k]);
         }
+    }
+    {
+        const char* bad = segments_ops_smoke(ctx, &cfg, &err);
+        if (bad) return die(bad, err);
+        printf("segments_ops ok: 2 segments from raw operations, each blob == zkm_prove_segment_ops' alone\n");
     }
     zkm_ctx_destroy(ctx);
 

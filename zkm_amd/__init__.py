@@ -47,6 +47,8 @@ EXPORTS = [
     "zkm_pool_create", "zkm_pool_destroy", "zkm_pool_workers", "zkm_pool_context", "zkm_pool_device", "zkm_pool_set_tuning",
     "zkm_pool_prove_segments", "zkm_pool_prove_segments_columns", "zkm_pool_plan", "zkm_pool_last_assignment",
     "zkm_segment_tables", "zkm_prove_segment_ops",
+    "zkm_segments_tables", "zkm_prove_segments_ops", "zkm_pool_prove_segments_ops",
+    "zkm_segment_ops_stage", "zkm_staged_ops_get", "zkm_staged_ops_ready", "zkm_staged_ops_free",
 ]
 
 
@@ -218,6 +220,16 @@ def load():
         "zkm_segment_tables": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(SegmentOpsStruct), C.POINTER(C.c_uint), cpp, err]),
         "zkm_prove_segment_ops": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(SegmentOpsStruct), u64p, C.c_size_t, u64p,
                                             C.POINTER(C.c_size_t), u64p, err]),
+        "zkm_segments_tables": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(SegmentOpsStruct), C.POINTER(C.c_uint), cpp, err]),
+        "zkm_prove_segments_ops": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(SegmentOpsStruct), C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), err]),
+        "zkm_pool_prove_segments_ops": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.c_size_t, C.POINTER(SegmentOpsStruct),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_void_p), err]),
+        "zkm_segment_ops_stage": (C.c_int, [cp, C.POINTER(SegmentOpsStruct), cpp, err]),
+        "zkm_staged_ops_get": (C.c_int, [cp, C.POINTER(SegmentOpsStruct)]),
+        "zkm_staged_ops_ready": (C.c_int, [cp, C.c_int]),
+        "zkm_staged_ops_free": (None, [cp]),
         "zkm_host_alloc": (C.c_int, [cp, C.c_size_t, cpp, err]),
         "zkm_host_free": (C.c_int, [cp, cp]),
         "zkm_host_register": (C.c_int, [cp, cp, C.c_size_t, err]),
@@ -447,12 +459,87 @@ class SegmentOps:
                 v.free()
 
     def struct(self):
+        if getattr(self, "_staged_struct", None) is not None:    # StagedOps.ops(): device pointers the library handed out
+            return self._staged_struct
         st = SegmentOpsStruct()
         for name, v in self.lists.items():
             setattr(st, name, v.ptr if isinstance(v, DeviceBuffer) else v.ctypes.data)
         for count, n in self.counts.items():
             setattr(st, count, n)
         return st
+
+
+class StagedOps:
+    """zkm_staged_ops: a segment's raw operations on their way into HBM behind the context's current work (include/zkm_hip.h "Staged
+    operations").  ops() is the same segment with device pointers, for segment[s]_tables / prove_segment[s]_ops of the SAME context;
+    free() after that call has returned.  Freed like a StagedTrace when dropped, at the end of a `with` block or by Context.close()."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
+        ctx._staged.add(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def ops(self):
+        """A SegmentOps of device pointers, ordered behind the upload on the device (no host wait)."""
+        st = SegmentOpsStruct()
+        if not self.h or self.ctx.L.zkm_staged_ops_get(self.h, C.byref(st)) != 0:
+            raise ZkmError("zkm_staged_ops_get: freed handle, or the upload could not be ordered before the compute stream")
+        out = SegmentOps.__new__(SegmentOps)
+        out.lists, out.counts, out._staged_struct, out._owner = {}, {}, st, self
+        return out
+
+    def ready(self, wait=False):
+        r = self.ctx.L.zkm_staged_ops_ready(self.h, 1 if wait else 0)
+        if r < 0:
+            raise ZkmError("zkm_staged_ops_ready: runtime error")
+        return bool(r)
+
+    def free(self):
+        """Waits for the upload and returns the block."""
+        if self.h:
+            h, self.h = self.h, None
+            self.ctx._staged.discard(self)
+            if self.ctx.h:
+                self.ctx.L.zkm_staged_ops_free(h)
+
+
+class _marshal_ops:
+    """The argument arrays of zkm_[pool_]prove_segments_ops for a list of SegmentOps and one array of public values per segment."""
+
+    def __init__(self, ops_list, public_values, cfg):
+        K = len(ops_list)
+        self.keep = list(ops_list)
+        self.st = (SegmentOpsStruct * max(K, 1))(*[o.struct() for o in ops_list])
+        pv = list(public_values) if public_values is not None else [()] * K
+        assert len(pv) == K, "one array of public values per segment"
+        self.pubs = [np.ascontiguousarray(p, dtype=np.uint64) for p in pv]
+        self.pv = (C.c_void_p * max(K, 1))(*[p.ctypes.data for p in self.pubs])
+        self.npv = (C.c_size_t * max(K, 1))(*[p.size for p in self.pubs])
+        self.offs = (C.c_size_t * (13 * max(K, 1)))()
+        self.K, self.cfg = K, cfg
+
+    def alloc(self):
+        """After the sizing call: the output buffers."""
+        K = self.K
+        self.sizes = [list(self.offs[13 * s:13 * s + 13]) for s in range(K)]
+        self.proofs = [np.zeros(o[12], dtype=np.uint64) for o in self.sizes]
+        self.chals = [np.zeros(2 * self.cfg.num_challenges, dtype=np.uint64) for _ in range(K)]
+        self.po = (C.c_void_p * max(K, 1))(*[p.ctypes.data for p in self.proofs])
+        self.co = (C.c_void_p * max(K, 1))(*[p.ctypes.data for p in self.chals])
+
+    def results(self):
+        return [(self.proofs[i], self.chals[i], self.sizes[i]) for i in range(self.K)]
 
 
 def _as_words(a):
@@ -559,6 +646,16 @@ class Pool:
         err = C.c_char_p()
         fn = self.L.zkm_pool_prove_segments_columns if m.by_columns else self.L.zkm_pool_prove_segments
         _check(fn(self.h, C.byref(cfg), len(segments), max_stack, m.tr, m.lg, m.pv, m.npv, m.po, m.co, C.byref(err)), err)
+        return m.results()
+
+    def prove_segments_ops(self, ops_list, public_values=None, max_stack=0, cfg=None):
+        """zkm_pool_prove_segments_ops: one SegmentOps per segment (HOST lists unless the pool has one device), one array of public values
+        per segment.  Each group is built and proven on its worker's context.  Returns (proofs, ctl_challenges, offsets) per segment."""
+        cfg = cfg or self.standard_config()
+        m, err = _marshal_ops(ops_list, public_values, cfg), C.c_char_p()
+        _check(self.L.zkm_pool_prove_segments_ops(self.h, C.byref(cfg), m.K, max_stack, m.st, m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
+        m.alloc()
+        _check(self.L.zkm_pool_prove_segments_ops(self.h, C.byref(cfg), m.K, max_stack, m.st, m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
         return m.results()
 
     def last_assignment(self, segment):
@@ -904,6 +1001,57 @@ class Context:
         st, lg, err = ops.struct(), (C.c_uint * 12)(), C.c_char_p()
         _check(self.L.zkm_segment_tables(self.h, C.byref(cfg), C.byref(st), lg, None, C.byref(err)), err)
         return list(lg)
+
+    def segments_tables(self, ops_list, cfg=None):
+        """zkm_segments_tables: the tables of K segments, every generation kernel launched once for all of them and three host waits for
+        the call.  ops_list: SegmentOps (host lists, device lists, StagedOps.ops(), mixed).  Returns [(staged, log_ns)] as
+        segment_tables gives them, one per segment; each staged is freed on its own."""
+        cfg = cfg or self.standard_config()
+        K = len(ops_list)
+        st = (SegmentOpsStruct * max(K, 1))(*[o.struct() for o in ops_list])
+        lg, hs, err = (C.c_uint * (12 * max(K, 1)))(), (C.c_void_p * max(K, 1))(), C.c_char_p()
+        _check(self.L.zkm_segments_tables(self.h, C.byref(cfg), K, st, lg, hs, C.byref(err)), err)
+        return [(StagedTrace(self, C.c_void_p(hs[s]), 0), list(lg[12 * s:12 * s + 12])) for s in range(K)]
+
+    def segments_heights(self, ops_list, cfg=None):
+        """zkm_segments_tables' sizing mode: the twelve log heights of each segment, nothing allocated."""
+        cfg = cfg or self.standard_config()
+        K = len(ops_list)
+        st = (SegmentOpsStruct * max(K, 1))(*[o.struct() for o in ops_list])
+        lg, err = (C.c_uint * (12 * max(K, 1)))(), C.c_char_p()
+        _check(self.L.zkm_segments_tables(self.h, C.byref(cfg), K, st, lg, None, C.byref(err)), err)
+        return [list(lg[12 * s:12 * s + 12]) for s in range(K)]
+
+    def prove_segments_ops(self, ops_list, public_values=None, cfg=None, sizes=None):
+        """zkm_prove_segments_ops: K segments built from their raw operations in one set of launches and proven in lock-step.
+        public_values: one array per segment.  Returns [(proofs, ctl_challenges, offsets)] as prove_segment_ops gives them.
+        sizes: the offsets an earlier call returned for segments of the same heights -- the sizing call (which finds the heights on the
+        device) is then skipped."""
+        cfg = cfg or self.standard_config()
+        m, err = _marshal_ops(ops_list, public_values, cfg), C.c_char_p()
+        if sizes is None:
+            _check(self.L.zkm_prove_segments_ops(self.h, C.byref(cfg), m.K, m.st, m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
+        else:
+            m.offs[:] = [x for o in sizes for x in o]
+        m.alloc()
+        _check(self.L.zkm_prove_segments_ops(self.h, C.byref(cfg), m.K, m.st, m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
+        return m.results()
+
+    def prove_segments_ops_sizes(self, ops_list, public_values=None, cfg=None):
+        """The sizing call of zkm_prove_segments_ops alone: the thirteen proof offsets of each segment."""
+        cfg = cfg or self.standard_config()
+        m, err = _marshal_ops(ops_list, public_values, cfg), C.c_char_p()
+        _check(self.L.zkm_prove_segments_ops(self.h, C.byref(cfg), m.K, m.st, m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
+        return [list(m.offs[13 * s:13 * s + 13]) for s in range(m.K)]
+
+    def stage_segment_ops(self, ops):
+        """zkm_segment_ops_stage: queue the upload of a segment's lists behind the context's current work and return at once.  The
+        lists (ideally Context.pinned_array memory) must stay as they are until .ready() says so."""
+        st, h, err = ops.struct(), C.c_void_p(), C.c_char_p()
+        _check(self.L.zkm_segment_ops_stage(self.h, C.byref(st), C.byref(h), C.byref(err)), err)
+        staged = StagedOps(self, h)
+        staged._keep = ops
+        return staged
 
     def prove_segment_ops(self, ops, public_values=(), cfg=None):
         """zkm_prove_segment_ops: the segment's tables built on the device from its raw operations and proven (into_tables +

@@ -12,7 +12,9 @@
 //                      could pass 2^16 - 1;
 //   (4) k_arith_freq   RC_FREQUENCIES rows 0 .. 2^16 - 1 from that histogram (the rows below write the column's other rows).
 // Only the row count and the flags come back to the host before the output is written.
+// Every kernel serves K segments in one launch (zkm_seg_args: its segment's descriptor from blockIdx.z); a lone table is K = 1.
 #include <algorithm>
+#include <vector>
 
 #include "scan_dev.h"
 #include "zkm_internal.h"
@@ -54,8 +56,18 @@ __device__ __forceinline__ bool two_rows(uint32_t op) {
 }
 
 // ---- (1) flags and row counts
-__global__ __launch_bounds__(AT_THREADS) void k_arith_count(const uint32_t* __restrict__ ops, uint32_t nops, uint64_t* __restrict__ cnt,
-                                                             unsigned* __restrict__ flags) {
+struct count_seg {
+    const uint32_t* ops;
+    uint64_t* cnt;
+    unsigned* flags;
+    uint32_t nops;
+};
+__global__ __launch_bounds__(AT_THREADS) void k_arith_count(zkm_seg_args<count_seg> S) {
+    const count_seg& A = S.v[blockIdx.z];
+    const uint32_t* __restrict__ ops = A.ops;
+    uint64_t* __restrict__ cnt = A.cnt;
+    unsigned* __restrict__ flags = A.flags;
+    const uint32_t nops = A.nops;
     const size_t i = (size_t)blockIdx.x * AT_THREADS + threadIdx.x;
     uint32_t bad = 0;
     if (i < nops) {
@@ -299,6 +311,7 @@ struct rows_args {
     size_t n;
     unsigned long long* hist;   // 2^16 bins (RC_FREQUENCIES before the padding zeros)
     unsigned* bad;              // a shared value of 2^16 or more
+    gl_t* out;
 };
 
 // every column of row r; RC_FREQUENCIES rows below 2^16 belong to k_arith_freq.  One address register pair walks the columns (the
@@ -353,10 +366,14 @@ __device__ __forceinline__ void flush(uint32_t* h, unsigned long long* hist) {
     }
 }
 
-__global__ __launch_bounds__(AR_THREADS) void k_arith_rows(rows_args A, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(AR_THREADS) void k_arith_rows(zkm_seg_args<rows_args> S) {
     __shared__ uint32_t h[AR_HIST_WORDS];
     __shared__ uint32_t added;
     __shared__ uint64_t sext[32][16];
+    const rows_args& A = S.v[blockIdx.z];
+    gl_t* __restrict__ out = A.out;
+    // (a workgroup with neither operations nor zero rows of its segment leaves before it clears 128 KiB of counters)
+    if ((size_t)blockIdx.x * AR_THREADS >= A.nops && A.rows + (size_t)blockIdx.x * AR_THREADS >= A.n) return;
     for (int w = threadIdx.x; w < AR_HIST_WORDS; w += AR_THREADS) h[w] = 0;
     sign_extend_table(sext);
     if (threadIdx.x == 0) added = 0;
@@ -404,10 +421,16 @@ __global__ __launch_bounds__(AR_THREADS) void k_arith_rows(rows_args A, gl_t* __
 }
 
 // ---- (4) RC_FREQUENCIES rows 0 .. 2^16 - 1 (n >= 2^16)
-__global__ __launch_bounds__(AT_THREADS) void k_arith_freq(const unsigned long long* __restrict__ hist, uint64_t pad_zeros, size_t n,
-                                                            gl_t* __restrict__ out) {
+struct freq_seg {
+    const unsigned long long* hist;
+    uint64_t pad_zeros;
+    size_t n;
+    gl_t* out;
+};
+__global__ __launch_bounds__(AT_THREADS) void k_arith_freq(zkm_seg_args<freq_seg> S) {
+    const freq_seg& A = S.v[blockIdx.z];
     const uint32_t v = blockIdx.x * AT_THREADS + threadIdx.x;
-    if (v < RANGE_MAX) out[COL_RC_FREQ * n + v] = hist[v] + (v == 0 ? pad_zeros : 0);
+    if (v < RANGE_MAX) A.out[COL_RC_FREQ * A.n + v] = A.hist[v] + (v == 0 ? A.pad_zeros : 0);
 }
 
 size_t next_pow2(size_t v) {
@@ -419,29 +442,34 @@ size_t blocks_for(size_t items, size_t per) { return (items + per - 1) / per; }
 
 }  // namespace
 
-// ---- host phases (zkm_internal.h zkm_arith_job): zkm_arithmetic_trace runs them back to back, segment_ops.hip beside the Memory
-// witness's
-void zkm_arithmetic_count(zkm_arith_job& j) {
-    zkm_ctx* c = j.c;
-    const size_t nops = j.nops;
-    if (nops >= ((size_t)1 << 31)) throw std::runtime_error(std::string(j.what) + ": 2^31 or more arithmetic ops");
-    if (nops && !j.d_ops) throw std::runtime_error(std::string(j.what) + ": null ops");
-    // start[0, nops] the scan (start[nops] = rows), start[nops + 1] the failure flags
-    j.start = zkm_scratch(c, (nops + 2) * 8);
-    uint64_t* d_start = j.start.as<uint64_t>();
-    unsigned* d_flags = (unsigned*)(d_start + nops + 1);
-    ZKM_HIP_CHECK(hipMemsetAsync(d_start + nops, 0, 16, c->stream));
-    if (nops) {
-        const size_t len = nops + 1, nparts = blocks_for(len, SCAN_TILE);
-        zkm_scratch part(c, nparts * 8);
-        zkm_prof_scope ps(c, "arithmetic_trace/count");
-        hipLaunchKernelGGL(k_arith_count, dim3(blocks_for(nops, AT_THREADS)), dim3(AT_THREADS), 0, c->stream, j.d_ops, (uint32_t)nops, d_start,
-                           d_flags);
-        hipLaunchKernelGGL(k_scan_tiles, dim3(nparts), dim3(SCAN_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
-        hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(SCAN_THREADS), 0, c->stream, part.as<uint64_t>(), nparts);
-        hipLaunchKernelGGL(k_scan_apply, dim3(nparts), dim3(SCAN_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
-        ZKM_HIP_CHECK(hipGetLastError());
+// ---- host phases (zkm_internal.h zkm_arith_job): zkm_arithmetic_trace runs them back to back for one table, segment_ops.hip for the
+// K segments of a call beside the Memory witness's
+void zkm_arithmetic_count(zkm_arith_job* j, size_t nseg) {
+    zkm_ctx* c = j->c;
+    count_seg cs[ZKM_MAX_SEG];
+    scan_seg sc[ZKM_MAX_SEG];
+    std::vector<zkm_scratch> part;
+    size_t live = 0, max_ops = 0;   // (a segment without operations takes no part: its counts stay zero)
+    for (size_t s = 0; s < nseg; s++) {
+        const size_t nops = j[s].nops;
+        if (nops >= ((size_t)1 << 31)) throw std::runtime_error(std::string(j[s].what) + ": 2^31 or more arithmetic ops");
+        if (nops && !j[s].d_ops) throw std::runtime_error(std::string(j[s].what) + ": null ops");
+        // start[0, nops] the scan (start[nops] = rows, also counts()[0]); counts()[1] the failure flags (start[nops + 1] unless the caller
+        // gave the two words a home, which it zeroes)
+        j[s].start = zkm_scratch(c, (nops + 2) * 8);
+        uint64_t* d_start = j[s].start.as<uint64_t>();
+        ZKM_HIP_CHECK(hipMemsetAsync(d_start + nops, 0, 16, c->stream));
+        if (!nops) continue;
+        part.emplace_back(c, blocks_for(nops + 1, SCAN_TILE) * 8);
+        cs[live] = count_seg{j[s].d_ops, d_start, (unsigned*)(j[s].counts() + 1), (uint32_t)nops};
+        sc[live] = scan_seg{d_start, nops + 1, part.back().as<uint64_t>(), j[s].d_counts};
+        max_ops = std::max(max_ops, nops);
+        live++;
     }
+    if (!live) return;
+    zkm_prof_scope ps(c, "arithmetic_trace/count");
+    zkm_launch_segs(c->stream, k_arith_count, cs, live, blocks_for(max_ops, AT_THREADS), AT_THREADS);
+    scan_launch(c->stream, sc, live);
 }
 
 size_t zkm_arithmetic_height(zkm_arith_job& j, const uint64_t got[2], size_t* natural_rows_out) {
@@ -458,27 +486,30 @@ size_t zkm_arithmetic_height(zkm_arith_job& j, const uint64_t got[2], size_t* na
     return natural;
 }
 
-void zkm_arithmetic_write(zkm_arith_job& j, unsigned log_n, gl_t* out_dev, unsigned* d_bad) {
-    zkm_ctx* c = j.c;
-    const size_t n = (size_t)1 << log_n, nops = j.nops, rows = j.rows;
-    // hist[0, 2^16) the RC_FREQUENCIES bins (hist[2^16]: zero, where the wrapper keeps its range-check flag)
-    j.hist = zkm_scratch(c, (RANGE_MAX + 1) * 8);
-    unsigned long long* d_hist = j.hist.as<unsigned long long>();
-    ZKM_HIP_CHECK(hipMemsetAsync(d_hist, 0, (RANGE_MAX + 1) * 8, c->stream));
-    if (!d_bad) d_bad = (unsigned*)(d_hist + RANGE_MAX);
+void zkm_arithmetic_write(zkm_arith_job* j, size_t nseg, const unsigned* log_n, gl_t* const* out_dev, unsigned* const* d_bad) {
+    zkm_ctx* c = j->c;
+    rows_args ra[ZKM_MAX_SEG];
+    freq_seg fs[ZKM_MAX_SEG];
+    size_t grid = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        const size_t n = (size_t)1 << log_n[s], nops = j[s].nops, rows = j[s].rows;
+        // hist[0, 2^16) the RC_FREQUENCIES bins (hist[2^16]: zero, where the wrapper keeps its range-check flag)
+        j[s].hist = zkm_scratch(c, (RANGE_MAX + 1) * 8);
+        unsigned long long* d_hist = j[s].hist.as<unsigned long long>();
+        ZKM_HIP_CHECK(hipMemsetAsync(d_hist, 0, (RANGE_MAX + 1) * 8, c->stream));
+        ra[s] = rows_args{j[s].d_ops, j[s].start.as<uint64_t>(), (uint32_t)nops, rows, n, d_hist,
+                          d_bad && d_bad[s] ? d_bad[s] : (unsigned*)(d_hist + RANGE_MAX), out_dev[s]};
+        fs[s] = freq_seg{d_hist, (uint64_t)NSHARED * (n - rows), n, out_dev[s]};
+        const size_t work = std::max<size_t>(nops, n - rows);
+        grid = std::max(grid, std::min<size_t>(blocks_for(work, AR_THREADS), (size_t)std::max(c->num_cus, 1)));
+    }
     {
         zkm_prof_scope ps(c, "arithmetic_trace/rows");
-        rows_args A{j.d_ops, j.start.as<uint64_t>(), (uint32_t)nops, rows, n, d_hist, d_bad};
-        const size_t work = std::max<size_t>(nops, n - rows);
-        const size_t grid = std::min<size_t>(blocks_for(work, AR_THREADS), (size_t)std::max(c->num_cus, 1));
-        hipLaunchKernelGGL(k_arith_rows, dim3(grid), dim3(AR_THREADS), 0, c->stream, A, out_dev);
-        ZKM_HIP_CHECK(hipGetLastError());
+        zkm_launch_segs(c->stream, k_arith_rows, ra, nseg, grid, AR_THREADS);
     }
     {
         zkm_prof_scope ps(c, "arithmetic_trace/freq");
-        hipLaunchKernelGGL(k_arith_freq, dim3(RANGE_MAX / AT_THREADS), dim3(AT_THREADS), 0, c->stream, d_hist, (uint64_t)NSHARED * (n - rows),
-                           n, out_dev);
-        ZKM_HIP_CHECK(hipGetLastError());
+        zkm_launch_segs(c->stream, k_arith_freq, fs, nseg, RANGE_MAX / AT_THREADS, AT_THREADS);
     }
 }
 
@@ -500,7 +531,7 @@ extern "C" int zkm_arithmetic_trace(zkm_ctx* c, const uint32_t* ops, size_t nops
             ZKM_HIP_CHECK(hipMemcpyAsync((void*)d_ops, ops, nops * 12, hipMemcpyHostToDevice, c->stream));
         }
         zkm_arith_job j(c, "zkm_arithmetic_trace", d_ops, nops);
-        zkm_arithmetic_count(j);
+        zkm_arithmetic_count(&j, 1);
         uint64_t got[2];
         c->download(got, j.counts(), 16);
         const size_t natural = zkm_arithmetic_height(j, got, natural_rows_out);
@@ -508,7 +539,8 @@ extern "C" int zkm_arithmetic_trace(zkm_ctx* c, const uint32_t* ops, size_t nops
         const size_t n = (size_t)1 << log_n;
         if (natural > n)
             throw std::runtime_error("zkm_arithmetic_trace: the table needs " + std::to_string(natural) + " rows, more than 2^" + std::to_string(log_n));
-        zkm_arithmetic_write(j, log_n, out_dev, nullptr);
+        gl_t* const out = out_dev;
+        zkm_arithmetic_write(&j, 1, &log_n, &out, nullptr);
         uint64_t bad = 0;
         c->download(&bad, j.hist.as<unsigned long long>() + RANGE_MAX, 8);
         if (bad) throw std::runtime_error("zkm_arithmetic_trace: a shared-column value is 2^16 or more");

@@ -1118,6 +1118,19 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
     call.prove_tables();
 }
 
+// estimated bytes one segment holds while its wave is proven: per table the trace values, coefficients, 4x LDE and digests of the trace,
+// auxiliary and quotient batches
+template <class TZ>
+static double segment_footprint(const zkm_stark_config* cfg, const zkm_table_input* tables, size_t ntables, const TZ& tz0) {
+    double words = 0;
+    for (size_t t = 0; t < ntables && tables; t++) {
+        const double n = (double)((size_t)1 << std::min<unsigned>(tables[t].log_n, 40)), W = (double)tables[t].ncols;
+        const double A = (double)(tz0[t].naux + zkm_num_lookup_columns(tables[t].table_id, cfg)), Q = 2.0 * cfg->num_challenges;
+        words += W * n + (W + A + Q) * n * (1.0 + (double)(1u << cfg->rate_bits)) + 3.0 * 8.0 * n * (double)(1u << cfg->rate_bits);
+    }
+    return words * 8.0;
+}
+
 // A call may hold more segments than fit in HBM together (every commitment of every segment of a lock-step call is alive until its
 // table has been proven): the segments are proven in consecutive WAVES whose estimated footprint -- per table the trace values,
 // coefficients, 4x LDE and digests of the trace, auxiliary and quotient batches -- stays within 80 % of the blocks its allocator has
@@ -1140,15 +1153,7 @@ static void prove_segments_waves(zkm_ctx* c, const zkm_stark_config* cfg, size_t
     // sizes: 12 x 8 fell from 107 to 72 segments/s.)
     const double budget = c->segments_memory_budget ? (double)c->segments_memory_budget : 0.8 * ((double)cached + (double)free_b);
     const auto tz0 = derive_zs(ntables, ctls, sides, nctls, cfg->num_challenges, nullptr);
-    auto footprint = [&](const seg_io& s) {
-        double words = 0;
-        for (size_t t = 0; t < ntables && s.tables; t++) {
-            const double n = (double)((size_t)1 << std::min<unsigned>(s.tables[t].log_n, 40)), W = (double)s.tables[t].ncols;
-            const double A = (double)(tz0[t].naux + zkm_num_lookup_columns(s.tables[t].table_id, cfg)), Q = 2.0 * cfg->num_challenges;
-            words += W * n + (W + A + Q) * n * (1.0 + (double)(1u << cfg->rate_bits)) + 3.0 * 8.0 * n * (double)(1u << cfg->rate_bits);
-        }
-        return words * 8.0;
-    };
+    auto footprint = [&](const seg_io& s) { return segment_footprint(cfg, s.tables, ntables, tz0); };
     double total = 0;
     for (size_t s = 0; s < nseg; s++) total += footprint(io[s]);
     // even waves: nseg mod nwaves of them hold ceil(nseg / nwaves) segments, the others floor -- two stack heights at most, which is
@@ -1163,6 +1168,14 @@ static void prove_segments_waves(zkm_ctx* c, const zkm_stark_config* cfg, size_t
         prove_segments_impl(c, cfg, k, io + s0, ntables, ctls, sides, nctls, seg_base + s0);   // (errors name positions in the CALL, not in the wave)
         s0 += k;
     }
+}
+
+// zkm_internal.h: the same estimate for a whole segment known by its heights alone (Table::all() order) -- segment_ops.hip sizes the
+// waves of a call before the tables exist
+double zkm_segment_footprint(const zkm_stark_config* cfg, const unsigned log_n[12]) {
+    zkm_table_input tables[12];
+    for (int t = 0; t < 12; t++) tables[t] = zkm_table_input{AS_TABLE_IDS[t], nullptr, AS_TABLE_WIDTH[t], log_n[t], &AS_CTL_TABLES[t], nullptr};
+    return segment_footprint(cfg, tables, 12, derive_zs(12, AS_CTLS, AS_SIDES, AS_NCTLS, cfg->num_challenges, nullptr));
 }
 
 extern "C" {

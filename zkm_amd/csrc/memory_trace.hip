@@ -14,7 +14,9 @@
 //                        pair's keys; the pad rows (copies of the last operation pushed, :206-224) go right behind that row;
 //   (7) k_mem_neighbours first-change flags, RANGE_CHECK, COUNTER and the FREQUENCIES histogram (:83-166).
 // Only the key widths and the row count come back to the host before the output is written.
+// Every kernel serves K segments in one launch (zkm_seg_args: its segment's descriptor from blockIdx.z); a lone table is K = 1.
 #include <algorithm>
+#include <vector>
 
 #include "scan_dev.h"
 #include "zkm_internal.h"
@@ -44,7 +46,16 @@ struct key_layout {
 };
 
 // ---- (1) key widths
-__global__ __launch_bounds__(MT_THREADS) void k_mem_widths(const uint64_t* __restrict__ ops, size_t nops, unsigned long long* acc) {
+struct widths_seg {
+    const uint64_t* ops;
+    size_t nops;
+    unsigned long long* acc;
+};
+__global__ __launch_bounds__(MT_THREADS) void k_mem_widths(zkm_seg_args<widths_seg> S) {
+    const widths_seg& A = S.v[blockIdx.z];
+    const uint64_t* __restrict__ ops = A.ops;
+    const size_t nops = A.nops;
+    unsigned long long* acc = A.acc;
     uint64_t o[4] = {0, 0, 0, 0}, bad = 0;
     for (size_t i = (size_t)blockIdx.x * MT_THREADS + threadIdx.x; i < nops; i += (size_t)gridDim.x * MT_THREADS) {
 #pragma unroll
@@ -69,8 +80,20 @@ __global__ __launch_bounds__(MT_THREADS) void k_mem_widths(const uint64_t* __res
 }
 
 // ---- (2) pack: keys[q * nops + i] = word q of op i's key, idx[i] = i
-__global__ __launch_bounds__(MT_THREADS) void k_mem_pack(const uint64_t* __restrict__ ops, uint32_t nops, key_layout L,
-                                                          uint64_t* __restrict__ keys, uint32_t* __restrict__ idx) {
+struct pack_seg {
+    const uint64_t* ops;
+    uint64_t* keys;
+    uint32_t* idx;
+    uint32_t nops;
+    key_layout L;
+};
+__global__ __launch_bounds__(MT_THREADS) void k_mem_pack(zkm_seg_args<pack_seg> S) {
+    const pack_seg& A = S.v[blockIdx.z];
+    const uint64_t* __restrict__ ops = A.ops;
+    uint64_t* __restrict__ keys = A.keys;
+    uint32_t* __restrict__ idx = A.idx;
+    const uint32_t nops = A.nops;
+    const key_layout& L = A.L;
     size_t i = (size_t)blockIdx.x * MT_THREADS + threadIdx.x;
     if (i >= nops) return;
     uint64_t w[4] = {0, 0, 0, 0};
@@ -92,27 +115,46 @@ __global__ __launch_bounds__(MT_THREADS) void k_mem_pack(const uint64_t* __restr
 }
 
 // ---- (3) radix sort, one 8-bit digit at bit `bit` of the key
-// tile t = keys [t * MT_TILE, (t + 1) * MT_TILE); hist[d * ntiles + t] = keys of tile t with digit d
-__global__ __launch_bounds__(MT_THREADS) void k_radix_upsweep(const uint64_t* __restrict__ keys, uint32_t nops, unsigned bit,
-                                                               uint32_t* __restrict__ hist, uint32_t ntiles) {
+// tile t = keys [t * MT_TILE, (t + 1) * MT_TILE); hist[d * ntiles + t] = keys of tile t with digit d.  The passes of a launch run to the
+// widest segment's bit count: a digit at or above a segment's own key words is zero without a read (the sort is stable, so such a
+// pass copies the segment in order and keeps its ping-pong parity with the others).
+struct radix_seg {
+    uint64_t *kin, *kout;    // keys and indices: this pass reads kin / iin and writes kout / iout
+    uint32_t *iin, *iout;
+    uint32_t *hist, *tot;    // 256 x ntiles tile counts, 256 digit totals
+    uint32_t nops, ntiles;
+    unsigned nwords;
+};
+__device__ __forceinline__ uint32_t digit_of(const uint64_t* __restrict__ kw, size_t i, unsigned sh, bool live) {
+    return live ? (uint32_t)(kw[i] >> sh) & (MT_RADIX - 1) : 0;
+}
+__global__ __launch_bounds__(MT_THREADS) void k_radix_upsweep(zkm_seg_args<radix_seg> S, unsigned bit) {
     __shared__ uint32_t h[MT_RADIX];
+    const radix_seg& A = S.v[blockIdx.z];
+    if (blockIdx.x >= A.ntiles) return;
+    const uint32_t nops = A.nops;
     h[threadIdx.x] = 0;
     __syncthreads();
-    const uint64_t* kw = keys + (size_t)(bit >> 6) * nops;
+    const bool live = (bit >> 6) < A.nwords;
+    const uint64_t* kw = A.kin + (size_t)(bit >> 6) * nops;
     const unsigned sh = bit & 63;
     const size_t base = (size_t)blockIdx.x * MT_TILE;
 #pragma unroll
     for (int it = 0; it < MT_ITEMS; it++) {
         size_t i = base + (size_t)it * MT_THREADS + threadIdx.x;
-        if (i < nops) atomicAdd(&h[(kw[i] >> sh) & (MT_RADIX - 1)], 1u);
+        if (i < nops) atomicAdd(&h[digit_of(kw, i, sh, live)], 1u);
     }
     __syncthreads();
-    hist[(size_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
+    A.hist[(size_t)threadIdx.x * A.ntiles + blockIdx.x] = h[threadIdx.x];
 }
 
 // one block per digit: hist row d becomes its exclusive scan over the tiles, tot[d] the digit's total
-__global__ __launch_bounds__(MT_THREADS) void k_radix_scan(uint32_t* __restrict__ hist, uint32_t ntiles, uint32_t* __restrict__ tot) {
+__global__ __launch_bounds__(MT_THREADS) void k_radix_scan(zkm_seg_args<radix_seg> S) {
     __shared__ uint32_t sh[MT_WAVES];
+    const radix_seg& A = S.v[blockIdx.z];
+    uint32_t* __restrict__ hist = A.hist;
+    uint32_t* __restrict__ tot = A.tot;
+    const uint32_t ntiles = A.ntiles;
     uint32_t* row = hist + (size_t)blockIdx.x * ntiles;
     uint32_t carry = 0;
     for (uint32_t c = 0; c < ntiles; c += MT_THREADS) {
@@ -129,13 +171,21 @@ __global__ __launch_bounds__(MT_THREADS) void k_radix_scan(uint32_t* __restrict_
 // Stable scatter.  Wave w of the block owns the contiguous run [tile + w 64 MT_ITEMS, + 64 MT_ITEMS) and walks it 64 keys at a time
 // in input order; a key's rank among equal digits of its wave = the wave's running count of that digit + the equal-digit lanes below
 // it (ballot match mask).  The waves' counts are then turned into exclusive offsets in wave order, on top of the digit's global base.
-__global__ __launch_bounds__(MT_THREADS) void k_radix_downsweep(const uint64_t* __restrict__ kin, const uint32_t* __restrict__ iin,
-                                                                 uint64_t* __restrict__ kout, uint32_t* __restrict__ iout, uint32_t nops,
-                                                                 unsigned nwords, unsigned bit, const uint32_t* __restrict__ hist,
-                                                                 const uint32_t* __restrict__ tot, uint32_t ntiles) {
+__global__ __launch_bounds__(MT_THREADS) void k_radix_downsweep(zkm_seg_args<radix_seg> S, unsigned bit) {
     __shared__ uint32_t cnt[MT_WAVES][MT_RADIX];
     __shared__ uint32_t dbase[MT_RADIX];
     __shared__ uint32_t sh[MT_WAVES];
+    const radix_seg& A = S.v[blockIdx.z];
+    if (blockIdx.x >= A.ntiles) return;
+    const uint64_t* __restrict__ kin = A.kin;
+    const uint32_t* __restrict__ iin = A.iin;
+    uint64_t* __restrict__ kout = A.kout;
+    uint32_t* __restrict__ iout = A.iout;
+    const uint32_t* __restrict__ hist = A.hist;
+    const uint32_t* __restrict__ tot = A.tot;
+    const uint32_t nops = A.nops, ntiles = A.ntiles;
+    const unsigned nwords = A.nwords;
+    const bool live = (bit >> 6) < nwords;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int q = 0; q < MT_WAVES; q++) cnt[q][threadIdx.x] = 0;
@@ -155,7 +205,7 @@ __global__ __launch_bounds__(MT_THREADS) void k_radix_downsweep(const uint64_t* 
     for (int it = 0; it < MT_ITEMS; it++) {
         const size_t i = run + (size_t)it * 64 + lane;
         const bool valid = i < nops;
-        const uint32_t d = valid ? (uint32_t)(kw[i] >> shift) & (MT_RADIX - 1) : 0;
+        const uint32_t d = digit_of(kw, i, shift, valid && live);
         uint64_t m = __ballot(valid);
 #pragma unroll
         for (int b = 0; b < 8; b++) {
@@ -202,14 +252,27 @@ __device__ __forceinline__ uint64_t gap_dummies(const mem_op& a, const mem_op& b
 }
 
 // cnt[i] = 1 + dummies after sorted op i (saturated); *last = 1 + the last sorted op with dummies (atomicMax; 0: none)
-__global__ __launch_bounds__(MT_THREADS) void k_mem_gaps(const uint64_t* __restrict__ ops, const uint32_t* __restrict__ idx, uint32_t nops,
-                                                          uint64_t M, uint64_t* __restrict__ cnt, unsigned* __restrict__ last) {
+struct gaps_seg {
+    const uint64_t* ops;
+    const uint32_t* idx;
+    uint64_t* cnt;
+    unsigned* last;
+    uint64_t M;
+    uint32_t nops;
+};
+__global__ __launch_bounds__(MT_THREADS) void k_mem_gaps(zkm_seg_args<gaps_seg> S) {
+    const gaps_seg& A = S.v[blockIdx.z];
+    const uint64_t* __restrict__ ops = A.ops;
+    const uint32_t* __restrict__ idx = A.idx;
+    uint64_t* __restrict__ cnt = A.cnt;
+    const uint32_t nops = A.nops;
+    const uint64_t M = A.M;
     const size_t i = (size_t)blockIdx.x * MT_THREADS + threadIdx.x;
     if (i >= nops) return;
     uint64_t k = 0;
     if (i + 1 < nops) k = gap_dummies(load_op(ops, idx[i]), load_op(ops, idx[i + 1]), M);
     cnt[i] = k >= MT_SAT ? MT_SAT : k + 1;
-    if (k) atomicMax(last, (unsigned)(i + 1));
+    if (k) atomicMax(A.last, (unsigned)(i + 1));
 }
 
 // ---- (5) exclusive saturating scan: k_scan_tiles / k_scan_parts / k_scan_apply (scan_dev.h)
@@ -224,6 +287,7 @@ struct rows_args {
     uint32_t nops;
     uint64_t M, pad;
     size_t n;
+    gl_t* out;
 };
 __device__ __forceinline__ uint64_t pre_row(uint64_t r, uint64_t q, uint64_t pad) { return r < q ? r : r < q + pad ? q - 1 : r - pad; }
 // the last i in [lo, hi] with start[i] <= p (start is strictly increasing, start[lo] <= p)
@@ -235,9 +299,12 @@ __device__ __forceinline__ uint32_t find_op(const uint64_t* __restrict__ start, 
     }
     return lo;
 }
-__global__ __launch_bounds__(MT_THREADS) void k_mem_rows(rows_args A, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(MT_THREADS) void k_mem_rows(zkm_seg_args<rows_args> S) {
     __shared__ uint32_t range[2];
+    const rows_args& A = S.v[blockIdx.z];
     const size_t n = A.n;
+    if ((size_t)blockIdx.x * MT_THREADS >= n) return;
+    gl_t* __restrict__ out = A.out;
     const unsigned lst = *A.last;
     const uint64_t q = A.start[lst ? lst : A.nops];
     const size_t r0 = (size_t)blockIdx.x * MT_THREADS, r = r0 + threadIdx.x;
@@ -281,8 +348,18 @@ __global__ __launch_bounds__(MT_THREADS) void k_mem_rows(rows_args A, gl_t* __re
 }
 
 // ---- (7) generate_first_change_flags_and_rc (:83-130), COUNTER and FREQUENCIES (:161-166); column 12 zeroed by the caller
-__global__ __launch_bounds__(MT_THREADS) void k_mem_neighbours(gl_t* __restrict__ out, size_t n, int* __restrict__ bad) {
+struct neighbours_seg {
+    gl_t* out;
+    size_t n;
+    int* bad;
+};
+__global__ __launch_bounds__(MT_THREADS) void k_mem_neighbours(zkm_seg_args<neighbours_seg> S) {
     __shared__ uint32_t h[MT_HIST_LDS];
+    const neighbours_seg& A = S.v[blockIdx.z];
+    gl_t* __restrict__ out = A.out;
+    const size_t n = A.n;
+    int* __restrict__ bad = A.bad;
+    if ((size_t)blockIdx.x * MT_THREADS >= n) return;
     for (int b = threadIdx.x; b < MT_HIST_LDS; b += MT_THREADS) h[b] = 0;
     __syncthreads();
     unsigned long long* freq = (unsigned long long*)(out + 12 * n);
@@ -322,80 +399,101 @@ size_t blocks_for(size_t items, size_t per) { return (items + per - 1) / per; }
 
 }  // namespace
 
-// ---- host phases (zkm_internal.h zkm_memory_job): zkm_memory_trace runs them back to back, segment_ops.hip interleaves them with
-// the other tables' so that one host wait serves several tables
-void zkm_memory_widths(zkm_memory_job& j) {
-    zkm_ctx* c = j.c;
-    if (j.nops == 0) throw std::runtime_error(std::string(j.what) + ": No memory ops?");
-    if (j.nops >= ((size_t)1 << 32)) throw std::runtime_error(std::string(j.what) + ": 2^32 or more memory ops");
-    // small: [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies, [6] range-check flag
-    j.small = zkm_scratch(c, 64);
-    j.d_acc = j.small.as<unsigned long long>();
-    ZKM_HIP_CHECK(hipMemsetAsync(j.small.p, 0, 64, c->stream));
+// ---- host phases (zkm_internal.h zkm_memory_job): zkm_memory_trace runs them back to back for one table, segment_ops.hip runs them
+// for the K segments of a call and interleaves them with the other tables' so that one host wait serves several tables
+void zkm_memory_widths(zkm_memory_job* j, size_t nseg) {
+    zkm_ctx* c = j->c;
+    widths_seg ws[ZKM_MAX_SEG];
+    size_t grid = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        if (j[s].nops == 0) throw std::runtime_error(std::string(j[s].what) + ": No memory ops?");
+        if (j[s].nops >= ((size_t)1 << 32)) throw std::runtime_error(std::string(j[s].what) + ": 2^32 or more memory ops");
+        if (!j[s].d_acc) {
+            // small: [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies, [6] range-check flag, [7] the row count
+            j[s].small = zkm_scratch(c, 64);
+            j[s].d_acc = j[s].small.as<unsigned long long>();
+            j[s].d_count = j[s].small.as<uint64_t>() + 7;
+            ZKM_HIP_CHECK(hipMemsetAsync(j[s].small.p, 0, 64, c->stream));
+        }
+        ws[s] = widths_seg{j[s].d_ops, j[s].nops, j[s].d_acc};
+        grid = std::max(grid, std::min<size_t>(blocks_for(j[s].nops, MT_THREADS), 1024));
+    }
     zkm_prof_scope ps(c, "memory_trace/widths");
-    hipLaunchKernelGGL(k_mem_widths, dim3(std::min<size_t>(blocks_for(j.nops, MT_THREADS), 1024)), dim3(MT_THREADS), 0, c->stream,
-                       j.d_ops, j.nops, j.d_acc);
-    ZKM_HIP_CHECK(hipGetLastError());
+    zkm_launch_segs(c->stream, k_mem_widths, ws, nseg, grid, MT_THREADS);
 }
 
-void zkm_memory_sort(zkm_memory_job& j, const uint64_t acc[5]) {
-    zkm_ctx* c = j.c;
-    const size_t nops = j.nops;
-    const uint32_t m = (uint32_t)nops;
-    if (acc[4]) throw std::runtime_error(std::string(j.what) + ": a context, segment, virt or timestamp word is not below p");
-    // key layout: timestamp lowest, then virt, segment, context
-    key_layout L{};
-    unsigned sh = 0;
-    for (int f = 3; f >= 0; f--) {
-        L.width[f] = bit_width(acc[f]);
-        L.shift[f] = sh;
-        sh += L.width[f];
+void zkm_memory_sort(zkm_memory_job* j, size_t nseg, const uint64_t* acc_all, size_t acc_stride) {
+    zkm_ctx* c = j->c;
+    pack_seg pk[ZKM_MAX_SEG];
+    radix_seg rx[ZKM_MAX_SEG];
+    gaps_seg gp[ZKM_MAX_SEG];
+    scan_seg sc[ZKM_MAX_SEG];
+    size_t max_ops = 0;
+    unsigned max_bits = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        const uint64_t* acc = acc_all + s * acc_stride;
+        const size_t nops = j[s].nops;
+        if (acc[4]) throw std::runtime_error(std::string(j[s].what) + ": a context, segment, virt or timestamp word is not below p");
+        // key layout: timestamp lowest, then virt, segment, context
+        key_layout L{};
+        unsigned sh = 0;
+        for (int f = 3; f >= 0; f--) {
+            L.width[f] = bit_width(acc[f]);
+            L.shift[f] = sh;
+            sh += L.width[f];
+        }
+        L.bits = sh;
+        L.nwords = sh ? (sh + 63) / 64 : 1;
+        const size_t K = L.nwords;
+        j[s].keys_a = zkm_scratch(c, K * nops * 8);
+        j[s].keys_b = zkm_scratch(c, K * nops * 8);
+        j[s].idx_a = zkm_scratch(c, nops * 4);
+        j[s].idx_b = zkm_scratch(c, nops * 4);
+        pk[s] = pack_seg{j[s].d_ops, j[s].keys_a.as<uint64_t>(), j[s].idx_a.as<uint32_t>(), (uint32_t)nops, L};
+        rx[s] = radix_seg{j[s].keys_a.as<uint64_t>(), j[s].keys_b.as<uint64_t>(), j[s].idx_a.as<uint32_t>(), j[s].idx_b.as<uint32_t>(),
+                          nullptr, nullptr, (uint32_t)nops, (uint32_t)blocks_for(nops, MT_TILE), L.nwords};
+        max_ops = std::max(max_ops, nops);
+        if (nops > 1) max_bits = std::max(max_bits, L.bits);
     }
-    L.bits = sh;
-    L.nwords = sh ? (sh + 63) / 64 : 1;
-    const size_t K = L.nwords, ntiles = blocks_for(nops, MT_TILE);
-    j.keys_a = zkm_scratch(c, K * nops * 8);
-    j.keys_b = zkm_scratch(c, K * nops * 8);
-    j.idx_a = zkm_scratch(c, nops * 4);
-    j.idx_b = zkm_scratch(c, nops * 4);
-    uint64_t *kin = j.keys_a.as<uint64_t>(), *kout = j.keys_b.as<uint64_t>();
-    uint32_t *iin = j.idx_a.as<uint32_t>(), *iout = j.idx_b.as<uint32_t>();
     {
         zkm_prof_scope ps(c, "memory_trace/pack");
-        hipLaunchKernelGGL(k_mem_pack, dim3(blocks_for(nops, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, j.d_ops, m, L, kin, iin);
-        ZKM_HIP_CHECK(hipGetLastError());
+        zkm_launch_segs(c->stream, k_mem_pack, pk, nseg, blocks_for(max_ops, MT_THREADS), MT_THREADS);
     }
-    if (nops > 1 && L.bits) {
-        zkm_scratch hist(c, (size_t)MT_RADIX * ntiles * 4), tot(c, MT_RADIX * 4);
+    if (max_bits) {
+        std::vector<zkm_scratch> hist;   // per segment: the tile counts, then the digit totals
+        for (size_t s = 0; s < nseg; s++) {
+            hist.emplace_back(c, ((size_t)MT_RADIX * rx[s].ntiles + MT_RADIX) * 4);
+            rx[s].hist = hist.back().as<uint32_t>();
+            rx[s].tot = rx[s].hist + (size_t)MT_RADIX * rx[s].ntiles;
+        }
+        const size_t ntiles = blocks_for(max_ops, MT_TILE);
         zkm_prof_scope ps(c, "memory_trace/sort");
-        for (unsigned bit = 0; bit < L.bits; bit += 8) {
-            hipLaunchKernelGGL(k_radix_upsweep, dim3(ntiles), dim3(MT_THREADS), 0, c->stream, kin, m, bit, hist.as<uint32_t>(), (uint32_t)ntiles);
-            hipLaunchKernelGGL(k_radix_scan, dim3(MT_RADIX), dim3(MT_THREADS), 0, c->stream, hist.as<uint32_t>(), (uint32_t)ntiles,
-                               tot.as<uint32_t>());
-            hipLaunchKernelGGL(k_radix_downsweep, dim3(ntiles), dim3(MT_THREADS), 0, c->stream, kin, iin, kout, iout, m, L.nwords, bit,
-                               hist.as<uint32_t>(), tot.as<uint32_t>(), (uint32_t)ntiles);
-            ZKM_HIP_CHECK(hipGetLastError());
-            std::swap(kin, kout);
-            std::swap(iin, iout);
+        for (unsigned bit = 0; bit < max_bits; bit += 8) {
+            zkm_launch_segs(c->stream, k_radix_upsweep, rx, nseg, ntiles, MT_THREADS, bit);
+            zkm_launch_segs(c->stream, k_radix_scan, rx, nseg, MT_RADIX, MT_THREADS);
+            zkm_launch_segs(c->stream, k_radix_downsweep, rx, nseg, ntiles, MT_THREADS, bit);
+            for (size_t s = 0; s < nseg; s++) {
+                std::swap(rx[s].kin, rx[s].kout);
+                std::swap(rx[s].iin, rx[s].iout);
+            }
         }
     }
-    j.idx = iin;
-    // gaps and their scan: start[i] = first row of sorted op i, start[nops] = rows before padding
-    j.M = next_pow2(nops) - 1;
-    j.start = zkm_scratch(c, (nops + 1) * 8);
-    uint64_t* d_start = j.start.as<uint64_t>();
-    const size_t len = nops + 1, nparts = blocks_for(len, MT_TILE);
-    zkm_scratch part(c, nparts * 8);
-    {
-        zkm_prof_scope ps(c, "memory_trace/gaps");
+    // gaps and their scan: start[i] = first row of sorted op i, start[nops] = rows before padding (and *d_count)
+    std::vector<zkm_scratch> part;
+    for (size_t s = 0; s < nseg; s++) {
+        const size_t nops = j[s].nops;
+        j[s].idx = rx[s].iin;
+        j[s].M = next_pow2(nops) - 1;
+        j[s].start = zkm_scratch(c, (nops + 1) * 8);
+        uint64_t* d_start = j[s].start.as<uint64_t>();
+        part.emplace_back(c, blocks_for(nops + 1, MT_TILE) * 8);
         ZKM_HIP_CHECK(hipMemsetAsync(d_start + nops, 0, 8, c->stream));
-        hipLaunchKernelGGL(k_mem_gaps, dim3(blocks_for(nops, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, j.d_ops, iin, m, j.M, d_start,
-                           (unsigned*)(j.d_acc + 5));
-        hipLaunchKernelGGL(k_scan_tiles, dim3(nparts), dim3(MT_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
-        hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(MT_THREADS), 0, c->stream, part.as<uint64_t>(), nparts);
-        hipLaunchKernelGGL(k_scan_apply, dim3(nparts), dim3(MT_THREADS), 0, c->stream, d_start, len, part.as<uint64_t>());
-        ZKM_HIP_CHECK(hipGetLastError());
+        gp[s] = gaps_seg{j[s].d_ops, j[s].idx, d_start, (unsigned*)(j[s].d_acc + 5), j[s].M, (uint32_t)nops};
+        sc[s] = scan_seg{d_start, nops + 1, part.back().as<uint64_t>(), j[s].d_count};
     }
+    zkm_prof_scope ps(c, "memory_trace/gaps");
+    zkm_launch_segs(c->stream, k_mem_gaps, gp, nseg, blocks_for(max_ops, MT_THREADS), MT_THREADS);
+    scan_launch(c->stream, sc, nseg);
 }
 
 size_t zkm_memory_height(zkm_memory_job& j, uint64_t count, size_t* natural_rows_out) {
@@ -409,21 +507,26 @@ size_t zkm_memory_height(zkm_memory_job& j, uint64_t count, size_t* natural_rows
     return natural;
 }
 
-void zkm_memory_write(zkm_memory_job& j, unsigned log_n, gl_t* out_dev, int* d_bad) {
-    zkm_ctx* c = j.c;
-    const size_t n = (size_t)1 << log_n;
+void zkm_memory_write(zkm_memory_job* j, size_t nseg, const unsigned* log_n, gl_t* const* out_dev, int* const* d_bad) {
+    zkm_ctx* c = j->c;
+    rows_args ra[ZKM_MAX_SEG];
+    neighbours_seg nb[ZKM_MAX_SEG];
+    size_t max_n = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        const size_t n = (size_t)1 << log_n[s];
+        ra[s] = rows_args{j[s].d_ops, j[s].idx, j[s].start.as<uint64_t>(), (const unsigned*)(j[s].d_acc + 5), (uint32_t)j[s].nops, j[s].M,
+                          n - j[s].count, n, out_dev[s]};
+        nb[s] = neighbours_seg{out_dev[s], n, d_bad[s]};
+        max_n = std::max(max_n, n);
+        ZKM_HIP_CHECK(hipMemsetAsync(out_dev[s] + 12 * n, 0, n * 8, c->stream));
+    }
     {
         zkm_prof_scope ps(c, "memory_trace/rows");
-        rows_args A{j.d_ops, j.idx, j.start.as<uint64_t>(), (const unsigned*)(j.d_acc + 5), (uint32_t)j.nops, j.M, n - j.count, n};
-        hipLaunchKernelGGL(k_mem_rows, dim3(blocks_for(n, MT_THREADS)), dim3(MT_THREADS), 0, c->stream, A, out_dev);
-        ZKM_HIP_CHECK(hipGetLastError());
+        zkm_launch_segs(c->stream, k_mem_rows, ra, nseg, blocks_for(max_n, MT_THREADS), MT_THREADS);
     }
     {
         zkm_prof_scope ps(c, "memory_trace/neighbours");
-        ZKM_HIP_CHECK(hipMemsetAsync(out_dev + 12 * n, 0, n * 8, c->stream));
-        hipLaunchKernelGGL(k_mem_neighbours, dim3(std::min<size_t>(blocks_for(n, MT_THREADS), 1024)), dim3(MT_THREADS), 0, c->stream,
-                           out_dev, n, d_bad);
-        ZKM_HIP_CHECK(hipGetLastError());
+        zkm_launch_segs(c->stream, k_mem_neighbours, nb, nseg, std::min<size_t>(blocks_for(max_n, MT_THREADS), 1024), MT_THREADS);
     }
 }
 
@@ -444,19 +547,20 @@ extern "C" int zkm_memory_trace(zkm_ctx* c, const uint64_t* ops, size_t nops, un
             ZKM_HIP_CHECK(hipMemcpyAsync((void*)d_ops, ops, nops * 48, hipMemcpyHostToDevice, c->stream));
         }
         zkm_memory_job j(c, "zkm_memory_trace", d_ops, nops);
-        zkm_memory_widths(j);
+        zkm_memory_widths(&j, 1);
         uint64_t acc[5];
         c->download(acc, j.d_acc, sizeof(acc));
-        zkm_memory_sort(j, acc);
+        zkm_memory_sort(&j, 1, acc, 0);
         uint64_t count = 0;
-        c->download(&count, j.start.as<uint64_t>() + nops, 8);
+        c->download(&count, j.d_count, 8);
         const size_t natural = zkm_memory_height(j, count, natural_rows_out);
         if (!out_dev) return;
         const size_t n = (size_t)1 << log_n;
         if (natural > n)
             throw std::runtime_error("zkm_memory_trace: the table needs " + std::to_string(natural) + " rows, more than 2^" + std::to_string(log_n));
         int* d_bad = (int*)(j.d_acc + 6);
-        zkm_memory_write(j, log_n, out_dev, d_bad);
+        gl_t* const out = out_dev;
+        zkm_memory_write(&j, 1, &log_n, &out, &d_bad);
         int bad = 0;
         c->download(&bad, d_bad, sizeof(bad));
         if (bad) throw std::runtime_error("zkm_memory_trace: a range check is 2^log_n or more (a context or segment gap)");

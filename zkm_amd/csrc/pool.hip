@@ -41,10 +41,9 @@ static std::vector<std::pair<size_t, size_t>> pool_groups(size_t nseg, size_t wo
 }
 
 // (throws: the entry points below run it inside the error boundary)
-static void pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack,
-                       const uint64_t* const* const* traces, const uint64_t* const* const* const* columns, const unsigned* const* log_n,
-                       const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges) {
-    if (!p || !cfg || (!traces && !columns) || !log_n || !proofs || !challenges) throw std::runtime_error(std::string(what) + ": null argument");
+// run_group(context, first segment, count, err): ONE call of the entry point that proves the group on that worker's context
+template <class G>
+static void pool_run(const char* what, zkm_pool* p, size_t nseg, size_t max_stack, G&& run_group) {
     if (max_stack == 0) max_stack = 8;
     if (max_stack > ZKM_MAX_SEG) throw std::runtime_error(std::string(what) + ": max_stack beyond " + std::to_string(ZKM_MAX_SEG));
     const size_t W = p->ctxs.size();
@@ -66,8 +65,7 @@ static void pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cf
             }
             const size_t s0 = groups[g].first, k = groups[g].second;
             char* e = nullptr;   // (the entry point is noexcept: nothing unwinds out of a worker thread)
-            const int rc = zkm_prove_segments_entry(what, p->ctxs[w], cfg, k, traces ? traces + s0 : nullptr, columns ? columns + s0 : nullptr,
-                                                    log_n + s0, pub ? pub + s0 : nullptr, npub ? npub + s0 : nullptr, proofs + s0, challenges + s0, &e, s0);
+            const int rc = run_group(p->ctxs[w], s0, k, &e);
             std::lock_guard<std::mutex> lk(mu);
             if (rc != 0) {
                 if (!failed)
@@ -91,6 +89,16 @@ static void pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cf
     worker(0);
     for (auto& t : th) t.join();
     if (failed) throw std::runtime_error(first_error);
+}
+
+static void pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack,
+                       const uint64_t* const* const* traces, const uint64_t* const* const* const* columns, const unsigned* const* log_n,
+                       const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges) {
+    if (!p || !cfg || (!traces && !columns) || !log_n || !proofs || !challenges) throw std::runtime_error(std::string(what) + ": null argument");
+    pool_run(what, p, nseg, max_stack, [&](zkm_ctx* c, size_t s0, size_t k, char** e) {
+        return zkm_prove_segments_entry(what, c, cfg, k, traces ? traces + s0 : nullptr, columns ? columns + s0 : nullptr, log_n + s0,
+                                        pub ? pub + s0 : nullptr, npub ? npub + s0 : nullptr, proofs + s0, challenges + s0, e, s0);
+    });
 }
 
 extern "C" {
@@ -156,6 +164,22 @@ int zkm_pool_prove_segments_columns(zkm_pool* p, const zkm_stark_config* cfg, si
                                     const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges, char** err) {
     return zkm_api("zkm_pool_prove_segments_columns", err,
                    [&] { pool_prove("zkm_pool_prove_segments_columns", p, cfg, nseg, max_stack, nullptr, columns, log_n, pub, npub, proofs, challenges); });
+}
+
+// the groups as above, each ONE zkm_prove_segments_ops call (tables built and proven on the worker's context); proofs == NULL sizes
+int zkm_pool_prove_segments_ops(zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack, const zkm_segment_ops* ops,
+                                const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, size_t* offsets_out,
+                                uint64_t* const* challenges, char** err) {
+    const char* what = "zkm_pool_prove_segments_ops";
+    return zkm_api(what, err, [&] {
+        if (!p || !cfg || !ops || (proofs ? !challenges : !offsets_out)) throw std::runtime_error(std::string(what) + ": null argument");
+        if (nseg == 0) throw std::runtime_error(std::string(what) + ": no segments");
+        pool_run(what, p, nseg, max_stack, [&](zkm_ctx* c, size_t s0, size_t k, char** e) {
+            return zkm_prove_segments_ops_entry(what, c, cfg, k, ops + s0, pub ? pub + s0 : nullptr, npub ? npub + s0 : nullptr,
+                                                proofs ? proofs + s0 : nullptr, offsets_out ? offsets_out + 13 * s0 : nullptr,
+                                                challenges ? challenges + s0 : nullptr, e, s0);
+        });
+    });
 }
 
 size_t zkm_pool_plan(size_t nseg, size_t workers, size_t max_stack, size_t* group_sizes_out, size_t capacity) {

@@ -1,8 +1,11 @@
 // scan_dev.h -- block-wide inclusive scan and a three-launch exclusive saturating scan of uint64 counts (memory_trace.hip: rows per
-// sorted memory op; arithmetic_trace.hip: rows per arithmetic op).  Kernels with internal linkage: each including file has its own copy.
+// sorted memory op; arithmetic_trace.hip: rows per arithmetic op), K independent scans a launch (zkm_seg_args: the scan from
+// blockIdx.z).  Kernels with internal linkage: each including file has its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "zkm_internal.h"
 
 namespace {
 
@@ -42,20 +45,32 @@ __device__ __forceinline__ T block_incl_scan(T v, T* sh, Op op, T* total) {
     return op(pre, v);
 }
 
-// exclusive saturating scan of v[0, len) in place: per-tile sums, a one-block scan of those, then the tiles
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_tiles(const uint64_t* __restrict__ v, size_t len, uint64_t* __restrict__ part) {
+// exclusive saturating scan of v[0, len) in place: per-tile sums, a one-block scan of those, then the tiles.  part: one word per tile;
+// total (optional): a second home for v[len - 1] after the scan -- the sum, when the caller put a zero behind its counts
+struct scan_seg {
+    uint64_t* v;
+    size_t len;
+    uint64_t *part, *total;
+    GL_HD size_t nparts() const { return (len + SCAN_TILE - 1) / SCAN_TILE; }
+};
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_tiles(zkm_seg_args<scan_seg> S) {
     __shared__ uint64_t sh[SCAN_WAVES];
+    const scan_seg& A = S.v[blockIdx.z];
     const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
+    if ((size_t)blockIdx.x * SCAN_TILE >= A.len) return;
     uint64_t s = 0;
 #pragma unroll
     for (int it = 0; it < SCAN_ITEMS; it++)
-        if (base + it < len) s = sat_add(s, v[base + it]);
+        if (base + it < A.len) s = sat_add(s, A.v[base + it]);
     uint64_t all;
     block_incl_scan(s, sh, add_sat(), &all);
-    if (threadIdx.x == 0) part[blockIdx.x] = all;
+    if (threadIdx.x == 0) A.part[blockIdx.x] = all;
 }
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_parts(uint64_t* __restrict__ part, size_t nparts) {
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_parts(zkm_seg_args<scan_seg> S) {
     __shared__ uint64_t sh[SCAN_WAVES];
+    const scan_seg& A = S.v[blockIdx.z];
+    uint64_t* __restrict__ part = A.part;
+    const size_t nparts = A.nparts();
     uint64_t carry = 0;
     for (size_t c = 0; c < nparts; c += SCAN_THREADS) {
         const size_t t = c + threadIdx.x;
@@ -66,8 +81,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_parts(uint64_t* __restric
         carry = sat_add(carry, all);
     }
 }
-__global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(uint64_t* __restrict__ v, size_t len, const uint64_t* __restrict__ part) {
+__global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(zkm_seg_args<scan_seg> S) {
     __shared__ uint64_t sh[SCAN_WAVES];
+    const scan_seg& A = S.v[blockIdx.z];
+    const size_t len = A.len;
+    if ((size_t)blockIdx.x * SCAN_TILE >= len) return;
+    uint64_t* __restrict__ v = A.v;
     const size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
     uint64_t x[SCAN_ITEMS], s = 0;
 #pragma unroll
@@ -79,12 +98,21 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(uint64_t* __restric
     const uint64_t incl = block_incl_scan(s, sh, add_sat(), &all);
     // exclusive prefix of this thread: the block's inclusive scan minus its own sum (exact when nothing saturated; otherwise both are
     // SCAN_SAT and the caller rejects the table anyway)
-    uint64_t run = sat_add(part[blockIdx.x], incl >= SCAN_SAT ? SCAN_SAT : incl - s);
+    uint64_t run = sat_add(A.part[blockIdx.x], incl >= SCAN_SAT ? SCAN_SAT : incl - s);
 #pragma unroll
     for (int it = 0; it < SCAN_ITEMS; it++) {
         if (base + it < len) v[base + it] = run;
+        if (base + it + 1 == len && A.total) *A.total = run;
         run = sat_add(run, x[it]);
     }
+}
+// the three launches for nseg scans (every len >= 1) on `stream`
+inline void scan_launch(hipStream_t stream, const scan_seg* segs, size_t nseg) {
+    size_t grid = 0;
+    for (size_t s = 0; s < nseg; s++) grid = std::max(grid, segs[s].nparts());
+    zkm_launch_segs(stream, k_scan_tiles, segs, nseg, grid, SCAN_THREADS);
+    zkm_launch_segs(stream, k_scan_parts, segs, nseg, 1, SCAN_THREADS);
+    zkm_launch_segs(stream, k_scan_apply, segs, nseg, grid, SCAN_THREADS);
 }
 
 }  // namespace

@@ -1,22 +1,29 @@
-// segment_ops.hip -- a whole segment's twelve tables built on the device from its raw operations (the reference's Traces::into_tables,
-// witness/traces.rs:230-320), and the proof of that segment in one call.
+// segment_ops.hip -- whole segments' twelve tables built on the device from their raw operations (the reference's Traces::into_tables,
+// witness/traces.rs:230-320), and the proofs of those segments in the same call.
 //
-//   zkm_segment_tables      every height (Table::all() order), ONE output block from the context's allocator, every table written
-//                           into it, handed out as a segment-shaped zkm_staged;
-//   zkm_prove_segment_ops   zkm_segment_tables, zkm_prove_segment on the block, the block freed.
+//   zkm_segments_tables      K segments: every height (Table::all() order), ONE output block per segment from the context's allocator,
+//                            every table written into it, each handed out as a segment-shaped zkm_staged;
+//   zkm_prove_segments_ops   zkm_segments_tables, zkm_prove_segments on the blocks (lock-step), the blocks freed; in waves when the
+//                            call holds more than ZKM_MAX_SEG segments or more than the memory budget;
+//   zkm_segment_tables, zkm_prove_segment_ops   the one-segment forms (the same builder, K = 1; zkm_prove_segment proves);
+//   zkm_segment_ops_stage    a segment's lists uploaded behind the work in flight, for a later call of the above.
 //
-// The one new kernel, k_cpu_rows_to_cols, turns the emulator's CPU rows (Vec<CpuColumnsView<F>>: 259 words a row, row-major) into the
+// The one kernel here, k_cpu_rows_to_cols, turns the emulator's CPU rows (Vec<CpuColumnsView<F>>: 259 words a row, row-major) into the
 // column-major table of trace_rows_to_poly_values (util.rs:37-46), canonical.  Every other table comes from its existing launcher;
-// the Memory and Arithmetic witnesses run in phases (zkm_internal.h zkm_memory_job / zkm_arith_job) so that they share host waits.
+// every launcher serves the K segments of a wave with ONE launch per kernel (the segment is blockIdx.z), and the Memory and
+// Arithmetic witnesses run in phases (zkm_internal.h zkm_memory_job / zkm_arith_job) so that they share host waits.
 //
-// Host waits per call, each ONE download of a few words (zkm_ctx::download):
-//   (1) the Memory key widths, with the Arithmetic row count and validation flags;
-//   (2) the Memory row count after the sort and the gap scan: every height is then known, and the output block is allocated;
-//   (3) the validation flags of every writer (Logic op codes, Memory range checks, Arithmetic shared-column values), one device array.
-// Sizing mode (out == NULL) ends after (2).  Inputs in host memory go through one staging block; CPU rows in host memory are copied in
+// Host waits per wave, whatever K, each ONE download of the wave's sync words (16 per segment, zkm_ctx::download):
+//   (1) the Memory key widths, with the Arithmetic row counts and validation flags;
+//   (2) the Memory row counts after the sort and the gap scan: every height is then known, and the output blocks are allocated;
+//   (3) the validation flags of every writer (Logic op codes, Memory range checks, Arithmetic shared-column values), a triple a segment.
+// Sizing mode ends after (2).  Inputs in host memory go through one staging block for the wave; CPU rows in host memory are copied in
 // row pieces on the context's two copy streams, each piece transposed on the compute stream behind its own copy, so that the largest
 // transfer overlaps the other tables' generation.
 #include <algorithm>
+#include <cmath>
+#include <map>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -36,12 +43,20 @@ constexpr unsigned SEG_MAX_LOG_N = 28;     // every table, as ZKM_MEMORY_MAX_LOG
 // store instruction is two runs of 256 B down two columns.  The tile needs no padding: a row is 518 dwords, so lane l of a ds_read_b64
 // down a column reads bank (518 l + 2 c) mod 64 = (6 l + 2 c) mod 64, a different pair of banks for each of the 32 lanes of a group.
 // 66,304 B of LDS: two workgroups per CU.  Words >= p are reduced on the way (GoldilocksField words may be non-canonical).
-__global__ __launch_bounds__(TR_THREADS) void k_cpu_rows_to_cols(const uint64_t* __restrict__ rows, size_t nrows, size_t row0, size_t n,
-                                                                  gl_t* __restrict__ out) {
+// One launch serves K segments (zkm_seg_args): rows [0, nrows) at `rows` become rows [row0, row0 + nrows) of the n-row table at `out`.
+struct cpu_seg {
+    const uint64_t* rows;
+    size_t nrows, row0, n;
+    gl_t* out;
+};
+__global__ __launch_bounds__(TR_THREADS) void k_cpu_rows_to_cols(zkm_seg_args<cpu_seg> S) {
     __shared__ __attribute__((aligned(16))) uint64_t t[TR_ROWS * CPU_W];
+    const cpu_seg& A = S.v[blockIdx.z];
+    const size_t nrows = A.nrows, n = A.n;
     const size_t pr = (size_t)blockIdx.x * TR_ROWS;
+    if (pr >= nrows) return;
     const unsigned here = (unsigned)(nrows - pr < (size_t)TR_ROWS ? nrows - pr : TR_ROWS);
-    const uint64_t* src = rows + pr * CPU_W;
+    const uint64_t* src = A.rows + pr * CPU_W;
     const unsigned nw = here * CPU_W;
     if (here == TR_ROWS && (((uintptr_t)src) & 15) == 0) {
         // a full tile: every load in flight before the first LDS store (17 x 16 B per lane)
@@ -67,7 +82,7 @@ __global__ __launch_bounds__(TR_THREADS) void k_cpu_rows_to_cols(const uint64_t*
     __syncthreads();
     const unsigned lane = threadIdx.x & 63, r = lane & 31;
     if (r >= here) return;
-    gl_t* o = out + row0 + pr + r;
+    gl_t* o = A.out + A.row0 + pr + r;
 #pragma unroll 4
     for (unsigned c = 2 * (threadIdx.x >> 6) + (lane >> 5); c < (unsigned)CPU_W; c += 2 * (TR_THREADS / 64)) {
         const uint64_t v = t[r * CPU_W + c];
@@ -75,11 +90,11 @@ __global__ __launch_bounds__(TR_THREADS) void k_cpu_rows_to_cols(const uint64_t*
     }
 }
 
-void launch_cpu_rows_to_cols(zkm_ctx* c, const uint64_t* rows, size_t nrows, size_t row0, size_t n, gl_t* out) {
+void launch_cpu_rows_to_cols(zkm_ctx* c, const cpu_seg* segs, size_t nseg) {
+    size_t max_rows = 0;
+    for (size_t s = 0; s < nseg; s++) max_rows = std::max(max_rows, segs[s].nrows);
     zkm_prof_scope ps(c, "segment_ops/cpu_rows_to_cols");
-    hipLaunchKernelGGL(k_cpu_rows_to_cols, dim3((unsigned)((nrows + TR_ROWS - 1) / TR_ROWS)), dim3(TR_THREADS), 0, c->stream, rows, nrows, row0,
-                       n, out);
-    ZKM_HIP_CHECK(hipGetLastError());
+    zkm_launch_segs(c->stream, k_cpu_rows_to_cols, segs, nseg, (max_rows + TR_ROWS - 1) / TR_ROWS, TR_THREADS);
 }
 
 // Table::all() (all_stark.rs:117-134) and the reference's names of the tables, for messages
@@ -103,20 +118,83 @@ struct copy_join {
     }
 };
 
-// the output of one build: the block (empty in sizing mode) and the word offset of each table in it
+// the output of one build: the block (empty in sizing mode), the word offset of each table in it, and the heights
 struct segment_block {
     zkm_scratch block;
     size_t off[13] = {};
+    unsigned lg[NTAB] = {};
 };
 
-struct builder {
-    const char* what;
-    zkm_ctx* c;
-    const zkm_segment_ops& o;
-    unsigned lg[NTAB] = {};
+// ---- lists staged ahead of a call (zkm_segment_ops_stage): the block of each handle alive in this process and the context it belongs
+// to.  A build handed such a block's pointers on another context is refused -- nothing would order that context behind the upload.
+std::mutex g_staged_mu;
+std::map<const void*, const zkm_ctx*> g_staged_ops;   // block -> its context
+const zkm_ctx* staged_ops_context(const void* p) {
+    std::lock_guard<std::mutex> lk(g_staged_mu);
+    const auto it = g_staged_ops.find(p);
+    return it == g_staged_ops.end() ? nullptr : it->second;
+}
 
-    [[noreturn]] void refuse(int t, const std::string& msg) const { throw std::runtime_error(std::string(what) + ": " + NAME[t] + ": " + msg); }
-    std::string name(int t) const { return std::string(what) + ": " + NAME[t]; }
+// one list of a zkm_segment_ops: the address of its pointer field (fields differ in type: read and written as bytes) and its size
+struct list_ref {
+    void* field;
+    size_t bytes;
+    bool sizing;   // read before the heights are known (Arithmetic, Memory)
+    const void* get() const {
+        const void* p;
+        memcpy(&p, field, sizeof p);
+        return p;
+    }
+    void set(const void* p) const { memcpy(field, &p, sizeof p); }
+};
+// every list of `o` except the CPU rows and the two sponge offset arrays (which stay host memory)
+std::vector<list_ref> lists_of(zkm_segment_ops& o, size_t ps_bytes, size_t ks_bytes) {
+    return {{&o.arithmetic_ops, o.narithmetic * 12, true},
+            {&o.memory_ops, o.nmemory * 48, true},
+            {&o.logic_ops, o.nlogic * 12, false},
+            {&o.poseidon_inputs, o.nposeidon * 96, false},
+            {&o.poseidon_timestamps, o.nposeidon * 8, false},
+            {&o.poseidon_sponge_inputs, ps_bytes, false},
+            {&o.poseidon_sponge_meta, o.nposeidon_sponge * 32, false},
+            {&o.keccak_inputs, o.nkeccak * 200, false},
+            {&o.keccak_timestamps, o.nkeccak * 8, false},
+            {&o.keccak_sponge_inputs, ks_bytes, false},
+            {&o.keccak_sponge_meta, o.nkeccak_sponge * 32, false},
+            {&o.sha_extend_inputs, o.nsha_extend * 16, false},
+            {&o.sha_extend_timestamps, o.nsha_extend * 8, false},
+            {&o.sha_extend_sponge_w16, o.nsha_extend_sponge * 64, false},
+            {&o.sha_extend_sponge_meta, o.nsha_extend_sponge * 32, false},
+            {&o.sha_compress_hx, o.nsha_compress * 32, false},
+            {&o.sha_compress_w, o.nsha_compress * 256, false},
+            {&o.sha_compress_meta, o.nsha_compress * 64, false},
+            {&o.sha_compress_sponge_hx, o.nsha_compress_sponge * 32, false},
+            {&o.sha_compress_sponge_w, o.nsha_compress_sponge * 256, false},
+            {&o.sha_compress_sponge_meta, o.nsha_compress_sponge * 64, false}};
+}
+
+// One segment of a wave.  The phases below are driven for the K builders of a wave side by side (build_wave), so that every launch and
+// every host wait serves all of them.
+struct builder {
+    std::string what;             // "<entry point>", or "<entry point>: segment <position in the call>" in a call of several
+    zkm_ctx* c;
+    const zkm_segment_ops* o;     // the caller's lists
+    zkm_segment_ops d{};          // ... and where the device reads them: the caller's device pointers, or places in the staging block
+    unsigned lg[NTAB] = {};
+    std::vector<uint64_t> ps_row, ks_row;   // first row of each sponge operation
+    size_t ps_rows = 0, ks_rows = 0, ps_bytes = 0, ks_bytes = 0;
+    const void *d_pso = nullptr, *d_psr = nullptr, *d_kso = nullptr, *d_ksr = nullptr;   // device copies of the offsets and the row offsets
+    std::string me_what, ar_what;
+    // staging
+    struct upload { list_ref dst; const void* src; size_t off; };
+    std::vector<upload> ups;
+    bool cpu_host = false;
+    size_t cpu_off = 0, piece_rows = 0;
+    std::vector<zkm_event> piece_done;
+
+    builder(const char* entry, zkm_ctx* ctx, const zkm_segment_ops* ops, size_t pos, bool label)
+        : what(label ? std::string(entry) + ": segment " + std::to_string(pos) : std::string(entry)), c(ctx), o(ops) {}
+
+    [[noreturn]] void refuse(int t, const std::string& msg) const { throw std::runtime_error(what + ": " + NAME[t] + ": " + msg); }
     // a height of max(rows, min_rows) rounded up to a power of two; rows = count x per, refused above 2^SEG_MAX_LOG_N
     unsigned height(int t, size_t count, size_t per, size_t min_rows) const {
         const size_t cap = (size_t)1 << SEG_MAX_LOG_N;
@@ -144,11 +222,9 @@ struct builder {
         return row_off[nops];
     }
 
-    segment_block run(const zkm_stark_config* cfg, bool write) {
-        if (!cfg) throw std::runtime_error(std::string(what) + ": null argument");
-        if (cfg->cap_height > SEG_MAX_LOG_N) throw std::runtime_error(std::string(what) + ": cap_height out of range");
-        const size_t min_rows = std::max<size_t>((size_t)1 << cfg->cap_height, 64);   // max(num_cap_elements, MIN_TRACE_LEN), traces.rs:246-247
-        // ---- every check that needs no device
+    // ---- phase: every check that needs no device (zkm_segment_ops_stage runs it too)
+    void check_host() {
+        const zkm_segment_ops& o = *this->o;
         need(CPU, o.ncpu_rows, {o.cpu_rows});
         need(AR, o.narithmetic, {o.arithmetic_ops});
         need(LO, o.nlogic, {o.logic_ops});
@@ -166,13 +242,20 @@ struct builder {
         if (o.nmemory == 0) refuse(ME, "No memory ops?");
         if (o.nmemory >= ((size_t)1 << 32)) refuse(ME, "2^32 or more memory ops");
         if (o.narithmetic >= ((size_t)1 << 31)) refuse(AR, "2^31 or more arithmetic ops");
-        std::vector<uint64_t> ps_row, ks_row;
-        const size_t ps_rows = sponge_rows(PS, o.poseidon_sponge_off, o.nposeidon_sponge, 32, ps_row);
-        const size_t ks_rows = sponge_rows(KS, o.keccak_sponge_off, o.nkeccak_sponge, 136, ks_row);
-        const size_t ps_bytes = o.nposeidon_sponge ? o.poseidon_sponge_off[o.nposeidon_sponge] : 0;
-        const size_t ks_bytes = o.nkeccak_sponge ? o.keccak_sponge_off[o.nkeccak_sponge] : 0;
+        ps_rows = sponge_rows(PS, o.poseidon_sponge_off, o.nposeidon_sponge, 32, ps_row);
+        ks_rows = sponge_rows(KS, o.keccak_sponge_off, o.nkeccak_sponge, 136, ks_row);
+        ps_bytes = o.nposeidon_sponge ? o.poseidon_sponge_off[o.nposeidon_sponge] : 0;
+        ks_bytes = o.nkeccak_sponge ? o.keccak_sponge_off[o.nkeccak_sponge] : 0;
         need(PS, ps_bytes, {o.poseidon_sponge_inputs});
         need(KS, ks_bytes, {o.keccak_sponge_inputs});
+        const zkm_ctx* owner = staged_ops_context(o.cpu_rows);
+        if (owner && owner != c) refuse(CPU, "the lists were staged on another context");
+    }
+    // ---- phase: the heights the host knows (Arithmetic and Memory: the least they can be, for the memory estimate of a wave)
+    void heights(const zkm_stark_config* cfg) {
+        const zkm_segment_ops& o = *this->o;
+        const size_t min_rows = std::max<size_t>((size_t)1 << cfg->cap_height, 64);   // max(num_cap_elements, MIN_TRACE_LEN), traces.rs:246-247
+        lg[AR] = height(AR, o.narithmetic, 1, (size_t)1 << 16);
         lg[CPU] = log2_of(o.ncpu_rows);
         lg[PO] = height(PO, o.nposeidon, 1, min_rows);
         lg[PS] = height(PS, ps_rows, 1, min_rows);
@@ -183,154 +266,331 @@ struct builder {
         lg[SC] = height(SC, o.nsha_compress, 65, min_rows);
         lg[SCS] = height(SCS, o.nsha_compress_sponge, 1, min_rows);
         lg[LO] = height(LO, o.nlogic, 1, min_rows);
-
-        // ---- the staging block: [0, 64) the writers' flags, then the CPU rows (host rows only), then every input list in host memory
-        struct upload { const void* src; size_t bytes; const void** dev; };
-        std::vector<upload> ups;
-        const void *d_ar = o.arithmetic_ops, *d_me = o.memory_ops, *d_lo = o.logic_ops, *d_poi = o.poseidon_inputs, *d_pot = o.poseidon_timestamps,
-                   *d_psi = o.poseidon_sponge_inputs, *d_pso = o.poseidon_sponge_off, *d_psm = o.poseidon_sponge_meta,
-                   *d_psr = ps_row.data(), *d_kki = o.keccak_inputs, *d_kkt = o.keccak_timestamps, *d_ksi = o.keccak_sponge_inputs,
-                   *d_kso = o.keccak_sponge_off, *d_ksm = o.keccak_sponge_meta, *d_ksr = ks_row.data(), *d_sei = o.sha_extend_inputs,
-                   *d_set = o.sha_extend_timestamps, *d_sew = o.sha_extend_sponge_w16, *d_sem = o.sha_extend_sponge_meta,
-                   *d_sch = o.sha_compress_hx, *d_scw = o.sha_compress_w, *d_scm = o.sha_compress_meta, *d_ssh = o.sha_compress_sponge_hx,
-                   *d_ssw = o.sha_compress_sponge_w, *d_ssm = o.sha_compress_sponge_meta;
-        auto add = [&](const void** p, size_t bytes, bool host_only) {
-            if (bytes && (host_only || !zkm_is_device_ptr(*p))) ups.push_back(upload{*p, bytes, p});
+        lg[ME] = height(ME, o.nmemory, 1, 1);
+    }
+    // ---- phase: the segment's part of the staging block, from byte `base`: the CPU rows (host rows only), then every list in host memory.
+    // Returns the bytes it takes.
+    size_t plan(bool write, size_t base) {
+        const zkm_segment_ops& o = *this->o;
+        d = o;
+        d_pso = d_psr = d_kso = d_ksr = nullptr;
+        ups.clear();
+        cpu_host = write && !zkm_is_device_ptr(o.cpu_rows);
+        cpu_off = base;
+        size_t at = base + align_up(cpu_host ? o.ncpu_rows * CPU_W * 8 : 0);
+        auto add = [&](const list_ref& l, const void* src) {
+            if (!l.bytes || (!write && !l.sizing)) return;
+            ups.push_back(upload{l, src, at});
+            at += align_up(l.bytes);
         };
-        add(&d_ar, o.narithmetic * 12, false);
-        add(&d_me, o.nmemory * 48, false);
-        const size_t nsizing = ups.size();
-        if (write) {
-            add(&d_lo, o.nlogic * 12, false);
-            add(&d_poi, o.nposeidon * 96, false);
-            add(&d_pot, o.nposeidon * 8, false);
-            add(&d_psi, ps_bytes, false);
-            add(&d_pso, o.nposeidon_sponge ? (o.nposeidon_sponge + 1) * 8 : 0, true);
-            add(&d_psm, o.nposeidon_sponge * 32, false);
-            add(&d_psr, o.nposeidon_sponge ? (o.nposeidon_sponge + 1) * 8 : 0, true);
-            add(&d_kki, o.nkeccak * 200, false);
-            add(&d_kkt, o.nkeccak * 8, false);
-            add(&d_ksi, ks_bytes, false);
-            add(&d_kso, o.nkeccak_sponge ? (o.nkeccak_sponge + 1) * 8 : 0, true);
-            add(&d_ksm, o.nkeccak_sponge * 32, false);
-            add(&d_ksr, o.nkeccak_sponge ? (o.nkeccak_sponge + 1) * 8 : 0, true);
-            add(&d_sei, o.nsha_extend * 16, false);
-            add(&d_set, o.nsha_extend * 8, false);
-            add(&d_sew, o.nsha_extend_sponge * 64, false);
-            add(&d_sem, o.nsha_extend_sponge * 32, false);
-            add(&d_sch, o.nsha_compress * 32, false);
-            add(&d_scw, o.nsha_compress * 256, false);
-            add(&d_scm, o.nsha_compress * 64, false);
-            add(&d_ssh, o.nsha_compress_sponge * 32, false);
-            add(&d_ssw, o.nsha_compress_sponge * 256, false);
-            add(&d_ssm, o.nsha_compress_sponge * 64, false);
+        for (const list_ref& l : lists_of(d, ps_bytes, ks_bytes))
+            if (!zkm_is_device_ptr(l.get())) add(l, l.get());
+        const size_t nps = o.nposeidon_sponge ? (o.nposeidon_sponge + 1) * 8 : 0, nks = o.nkeccak_sponge ? (o.nkeccak_sponge + 1) * 8 : 0;
+        add(list_ref{&d_pso, nps, false}, o.poseidon_sponge_off);
+        add(list_ref{&d_psr, nps, false}, ps_row.data());
+        add(list_ref{&d_kso, nks, false}, o.keccak_sponge_off);
+        add(list_ref{&d_ksr, nks, false}, ks_row.data());
+        return at - base;
+    }
+    // ---- phase: the copies of the CPU rows in pieces of >= 8192 rows (17 MB), at most 16 of them, on alternate copy streams (`turn` runs
+    // on through the segments of a wave), an event behind each
+    void copy_cpu_rows(char* sb, size_t& turn) {
+        const zkm_segment_ops& o = *this->o;
+        piece_rows = o.ncpu_rows;
+        if (!cpu_host) return;
+        d.cpu_rows = (const uint64_t*)(sb + cpu_off);
+        piece_rows = std::min<size_t>(o.ncpu_rows, std::max<size_t>(8192, o.ncpu_rows / 16));
+        for (size_t r0 = 0; r0 < o.ncpu_rows; r0 += piece_rows, turn++) {
+            hipStream_t st = (turn & 1) ? c->copy_stream2 : c->copy_stream;
+            ZKM_HIP_CHECK(hipMemcpyAsync((void*)(d.cpu_rows + r0 * CPU_W), o.cpu_rows + r0 * CPU_W, piece_rows * CPU_W * 8, hipMemcpyHostToDevice, st));
+            piece_done.emplace_back(c);
+            piece_done.back().record(st);
         }
-        const bool cpu_host = write && !zkm_is_device_ptr(o.cpu_rows);
-        const size_t cpu_bytes = cpu_host ? o.ncpu_rows * CPU_W * 8 : 0;
-        size_t stage_bytes = 64 + align_up(cpu_bytes);
-        std::vector<size_t> up_off(ups.size());
-        for (size_t i = 0; i < ups.size(); i++) {
-            up_off[i] = stage_bytes;
-            stage_bytes += align_up(ups[i].bytes);
+    }
+    // ---- phase: the uploads of the lists on the compute stream (sizing: the two that the heights need; then the others)
+    void put(char* sb, bool sizing) {
+        for (const upload& u : ups) {
+            if (u.dst.sizing != sizing) continue;
+            ZKM_HIP_CHECK(hipMemcpyAsync(sb + u.off, u.src, u.dst.bytes, hipMemcpyHostToDevice, c->stream));
+            u.dst.set(sb + u.off);
         }
-        zkm_scratch stage(c, stage_bytes);
-        char* sb = stage.as<char>();
-        unsigned* d_flags = (unsigned*)sb;   // [0] Logic op code, [1] Memory range check, [2] Arithmetic shared-column value
-        std::vector<zkm_event> piece_done;
-        copy_join join;
-        const uint64_t* cpu_src = o.cpu_rows;
-        size_t piece_rows = o.ncpu_rows;
-        if (cpu_host) {
-            // pieces of >= 8192 rows (17 MB), at most 16 of them; alternate copy streams, each behind what the compute stream has queued
-            c->ensure_copy_stream(0);
-            c->ensure_copy_stream(1);
-            const zkm_event e(c);
-            e.record(c->stream);
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
-            join.c = c;
-            cpu_src = (const uint64_t*)(sb + 64);
-            piece_rows = std::min<size_t>(o.ncpu_rows, std::max<size_t>(8192, o.ncpu_rows / 16));
-            for (size_t r0 = 0, k = 0; r0 < o.ncpu_rows; r0 += piece_rows, k++) {
-                hipStream_t st = (k & 1) ? c->copy_stream2 : c->copy_stream;
-                ZKM_HIP_CHECK(hipMemcpyAsync((void*)(cpu_src + r0 * CPU_W), o.cpu_rows + r0 * CPU_W, piece_rows * CPU_W * 8, hipMemcpyHostToDevice, st));
-                piece_done.emplace_back(c);
-                piece_done.back().record(st);
+    }
+    size_t n(int t) const { return (size_t)1 << lg[t]; }
+};
+
+constexpr size_t SYNC_WORDS = 16;   // per segment: [0, 5) Memory key widths and >= p flag, [5] Memory last op with dummies, [6] Memory row count,
+                                    // [7] Arithmetic rows, [8] Arithmetic flags, [9, 11) three 32-bit validation flags (Logic, Memory, Arithmetic)
+
+// K <= ZKM_MAX_SEG checked builders of one context, phase by phase: one staging block, three host waits, one launch per kernel.
+// write = false: sizing only (the heights; the blocks stay empty).
+std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool write) {
+    // ---- the staging block: the sync words of every segment, then each segment's part
+    size_t stage_bytes = align_up(K * SYNC_WORDS * 8);
+    for (size_t s = 0; s < K; s++) stage_bytes += b[s].plan(write, stage_bytes);
+    zkm_scratch stage(c, stage_bytes);
+    char* sb = stage.as<char>();
+    uint64_t* d_sync = (uint64_t*)sb;
+    std::vector<uint64_t> sync(K * SYNC_WORDS);
+    copy_join join;
+    bool any_host_rows = false;
+    for (size_t s = 0; s < K; s++) any_host_rows = any_host_rows || b[s].cpu_host;
+    if (any_host_rows) {
+        // the copy streams start behind what the compute stream has queued (the block may be one that a finished call released)
+        c->ensure_copy_stream(0);
+        c->ensure_copy_stream(1);
+        const zkm_event e(c);
+        e.record(c->stream);
+        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
+        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
+        join.c = c;
+    }
+    size_t turn = 0;
+    for (size_t s = 0; s < K; s++) b[s].copy_cpu_rows(sb, turn);
+    ZKM_HIP_CHECK(hipMemsetAsync(d_sync, 0, K * SYNC_WORDS * 8, c->stream));
+    for (size_t s = 0; s < K; s++) b[s].put(sb, true);
+
+    // ---- Memory and Arithmetic sizing phases; waits (1) and (2)
+    std::vector<zkm_memory_job> mj;
+    std::vector<zkm_arith_job> aj;
+    mj.reserve(K);
+    aj.reserve(K);
+    for (size_t s = 0; s < K; s++) {
+        b[s].me_what = b[s].what + ": " + NAME[ME];
+        b[s].ar_what = b[s].what + ": " + NAME[AR];
+        mj.emplace_back(c, b[s].me_what.c_str(), b[s].d.memory_ops, b[s].o->nmemory);
+        aj.emplace_back(c, b[s].ar_what.c_str(), b[s].d.arithmetic_ops, b[s].o->narithmetic);
+        mj[s].d_acc = (unsigned long long*)(d_sync + s * SYNC_WORDS);
+        mj[s].d_count = d_sync + s * SYNC_WORDS + 6;
+        aj[s].d_counts = d_sync + s * SYNC_WORDS + 7;
+    }
+    zkm_memory_widths(mj.data(), K);
+    zkm_arithmetic_count(aj.data(), K);
+    c->download(sync.data(), d_sync, K * SYNC_WORDS * 8);                                                               // wait (1)
+    std::vector<segment_block> out(K);
+    const size_t cap = (size_t)1 << SEG_MAX_LOG_N;
+    for (size_t s = 0; s < K; s++) {
+        const size_t ar_n = zkm_arithmetic_height(aj[s], &sync[s * SYNC_WORDS + 7], nullptr);
+        if (ar_n > cap) b[s].refuse(AR, "the table needs " + std::to_string(ar_n) + " rows, more than 2^" + std::to_string(SEG_MAX_LOG_N));
+        b[s].lg[AR] = log2_of(ar_n);
+    }
+    zkm_memory_sort(mj.data(), K, sync.data(), SYNC_WORDS);
+    c->download(sync.data(), d_sync, K * SYNC_WORDS * 8);                                                               // wait (2)
+    for (size_t s = 0; s < K; s++) {
+        const size_t me_n = zkm_memory_height(mj[s], sync[s * SYNC_WORDS + 6], nullptr);
+        if (me_n > cap) b[s].refuse(ME, "the table needs " + std::to_string(me_n) + " rows, more than 2^" + std::to_string(SEG_MAX_LOG_N));
+        b[s].lg[ME] = log2_of(me_n);
+        for (int t = 0; t < NTAB; t++) {
+            out[s].lg[t] = b[s].lg[t];
+            out[s].off[t + 1] = out[s].off[t] + (zkm_table_width(TABLE_ID[t]) << b[s].lg[t]);
+        }
+    }
+    if (!write) return out;
+
+    // ---- one output block per segment (each handle is freed on its own) and every writer, a launch per kernel for the wave; wait (3)
+    for (size_t s = 0; s < K; s++) {
+        b[s].put(sb, false);
+        out[s].block = zkm_scratch(c, out[s].off[12] * sizeof(gl_t));
+    }
+    auto T = [&](size_t s, int t) { return out[s].block.as<gl_t>() + out[s].off[t]; };
+    auto flag = [&](size_t s, int k) { return (unsigned*)(d_sync + s * SYNC_WORDS + 9) + k; };   // 0 Logic, 1 Memory, 2 Arithmetic
+    {
+        unsigned lg[ZKM_MAX_SEG];
+        gl_t* o[ZKM_MAX_SEG];
+        unsigned* bad[ZKM_MAX_SEG];
+        for (size_t s = 0; s < K; s++) { lg[s] = b[s].lg[AR]; o[s] = T(s, AR); bad[s] = flag(s, 2); }
+        zkm_arithmetic_write(aj.data(), K, lg, o, bad);
+    }
+    // the data-parallel writers: the descriptor of table t for segment s
+    auto writers = [&](int t, auto&& seg) {
+        zkm_writer_seg w[ZKM_MAX_SEG];
+        for (size_t s = 0; s < K; s++) {
+            w[s] = seg(b[s], *b[s].o);
+            w[s].n = b[s].n(t);
+            w[s].out = T(s, t);
+        }
+        zkm_launch_writers(c, TABLE_ID[t], w, K);
+    };
+    using B = const builder&;
+    using O = const zkm_segment_ops&;
+    // (a Poseidon table without permutations is seed 0 with no inputs: every row is the padding row)
+    writers(PO, [](B b, O o) { return zkm_writer_seg{{o.nposeidon ? b.d.poseidon_inputs : nullptr, o.nposeidon ? b.d.poseidon_timestamps : nullptr}, o.nposeidon}; });
+    writers(PS, [](B b, O o) { return zkm_writer_seg{{b.d.poseidon_sponge_inputs, b.d_pso, b.d.poseidon_sponge_meta, b.d_psr}, o.nposeidon_sponge}; });
+    writers(KK, [](B b, O o) { return zkm_writer_seg{{b.d.keccak_inputs, b.d.keccak_timestamps}, o.nkeccak}; });
+    writers(KS, [](B b, O o) { return zkm_writer_seg{{b.d.keccak_sponge_inputs, b.d_kso, b.d.keccak_sponge_meta, b.d_ksr}, o.nkeccak_sponge, 0, b.ks_rows}; });
+    writers(SE, [](B b, O o) { return zkm_writer_seg{{b.d.sha_extend_inputs, b.d.sha_extend_timestamps}, o.nsha_extend}; });
+    writers(SES, [](B b, O o) { return zkm_writer_seg{{b.d.sha_extend_sponge_w16, b.d.sha_extend_sponge_meta}, o.nsha_extend_sponge}; });
+    writers(SC, [](B b, O o) { return zkm_writer_seg{{b.d.sha_compress_hx, b.d.sha_compress_w, b.d.sha_compress_meta}, o.nsha_compress}; });
+    writers(SCS, [](B b, O o) {
+        return zkm_writer_seg{{b.d.sha_compress_sponge_hx, b.d.sha_compress_sponge_w, b.d.sha_compress_sponge_meta}, o.nsha_compress_sponge};
+    });
+    {
+        zkm_writer_seg w[ZKM_MAX_SEG];
+        for (size_t s = 0; s < K; s++) w[s] = zkm_writer_seg{{b[s].d.logic_ops}, b[s].o->nlogic, b[s].n(LO), 0, T(s, LO), (int*)flag(s, 0)};
+        zkm_launch_writers(c, ZKM_TABLE_LOGIC, w, K);
+    }
+    {
+        unsigned lg[ZKM_MAX_SEG];
+        gl_t* o[ZKM_MAX_SEG];
+        int* bad[ZKM_MAX_SEG];
+        for (size_t s = 0; s < K; s++) { lg[s] = b[s].lg[ME]; o[s] = T(s, ME); bad[s] = (int*)flag(s, 1); }
+        zkm_memory_write(mj.data(), K, lg, o, bad);
+    }
+    // the CPU table: device-resident rows of every segment in one launch; host rows piece by piece, each behind its own copy (last: the
+    // copies overlap everything above)
+    {
+        cpu_seg cs[ZKM_MAX_SEG];
+        size_t nd = 0;
+        for (size_t s = 0; s < K; s++)
+            if (!b[s].cpu_host) cs[nd++] = cpu_seg{b[s].d.cpu_rows, b[s].o->ncpu_rows, 0, b[s].n(CPU), T(s, CPU)};
+        if (nd) launch_cpu_rows_to_cols(c, cs, nd);
+        for (size_t s = 0; s < K; s++) {
+            if (!b[s].cpu_host) continue;
+            for (size_t r0 = 0, k = 0; r0 < b[s].o->ncpu_rows; r0 += b[s].piece_rows, k++) {
+                ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, b[s].piece_done[k].e, 0));
+                const cpu_seg piece{b[s].d.cpu_rows + r0 * CPU_W, b[s].piece_rows, r0, b[s].n(CPU), T(s, CPU)};
+                launch_cpu_rows_to_cols(c, &piece, 1);
             }
         }
-        ZKM_HIP_CHECK(hipMemsetAsync(d_flags, 0, 64, c->stream));
-        auto put = [&](size_t i) {
-            ZKM_HIP_CHECK(hipMemcpyAsync(sb + up_off[i], ups[i].src, ups[i].bytes, hipMemcpyHostToDevice, c->stream));
-            *ups[i].dev = sb + up_off[i];
-        };
-        for (size_t i = 0; i < nsizing; i++) put(i);
-
-        // ---- Memory and Arithmetic sizing phases; waits (1) and (2)
-        const std::string me_what = name(ME), ar_what = name(AR);
-        zkm_memory_job mj(c, me_what.c_str(), (const uint64_t*)d_me, o.nmemory);
-        zkm_arith_job aj(c, ar_what.c_str(), (const uint32_t*)d_ar, o.narithmetic);
-        zkm_memory_widths(mj);
-        zkm_arithmetic_count(aj);
-        uint64_t acc[5], got[2];
-        c->download({{acc, mj.d_acc, sizeof acc}, {got, aj.counts(), sizeof got}});                               // wait (1)
-        const size_t ar_n = zkm_arithmetic_height(aj, got, nullptr);
-        zkm_memory_sort(mj, acc);
-        uint64_t count = 0;
-        c->download(&count, mj.start.as<uint64_t>() + o.nmemory, 8);                                                    // wait (2)
-        const size_t me_n = zkm_memory_height(mj, count, nullptr);
-        if (me_n > ((size_t)1 << SEG_MAX_LOG_N)) refuse(ME, "the table needs " + std::to_string(me_n) + " rows, more than 2^" + std::to_string(SEG_MAX_LOG_N));
-        if (ar_n > ((size_t)1 << SEG_MAX_LOG_N)) refuse(AR, "the table needs " + std::to_string(ar_n) + " rows, more than 2^" + std::to_string(SEG_MAX_LOG_N));
-        lg[AR] = log2_of(ar_n);
-        lg[ME] = log2_of(me_n);
-        segment_block out;
-        for (int t = 0; t < NTAB; t++) out.off[t + 1] = out.off[t] + (zkm_table_width(TABLE_ID[t]) << lg[t]);
-        if (!write) return out;
-
-        // ---- the one output block and every writer; wait (3)
-        for (size_t i = nsizing; i < ups.size(); i++) put(i);
-        out.block = zkm_scratch(c, out.off[12] * sizeof(gl_t));
-        gl_t* base = out.block.as<gl_t>();
-        auto T = [&](int t) { return base + out.off[t]; };
-        auto N = [&](int t) { return (size_t)1 << lg[t]; };
-        zkm_arithmetic_write(aj, lg[AR], T(AR), d_flags + 2);
-        zkm_launch_poseidon_trace(c, 0, o.nposeidon ? (const uint64_t*)d_poi : nullptr, o.nposeidon ? (const uint64_t*)d_pot : nullptr, o.nposeidon,
-                                  lg[PO], T(PO));
-        zkm_launch_poseidon_sponge_trace(c, (const uint8_t*)d_psi, (const uint64_t*)d_pso, (const uint64_t*)d_psm, (const uint64_t*)d_psr,
-                                         o.nposeidon_sponge, lg[PS], T(PS));
-        zkm_launch_keccak_trace(c, (const uint64_t*)d_kki, (const uint64_t*)d_kkt, o.nkeccak, N(KK), T(KK));
-        zkm_launch_keccak_sponge_trace(c, (const uint8_t*)d_ksi, (const uint64_t*)d_kso, (const uint64_t*)d_ksm, (const uint64_t*)d_ksr,
-                                       o.nkeccak_sponge, ks_rows, lg[KS], T(KS));
-        zkm_launch_sha_extend_trace(c, (const uint8_t*)d_sei, (const uint64_t*)d_set, o.nsha_extend, N(SE), T(SE));
-        zkm_launch_sha_extend_sponge_trace(c, (const uint32_t*)d_sew, (const uint64_t*)d_sem, o.nsha_extend_sponge, N(SES), T(SES));
-        zkm_launch_sha_compress_trace(c, false, (const uint32_t*)d_sch, (const uint32_t*)d_scw, (const uint64_t*)d_scm, o.nsha_compress, N(SC),
-                                      T(SC));
-        zkm_launch_sha_compress_trace(c, true, (const uint32_t*)d_ssh, (const uint32_t*)d_ssw, (const uint64_t*)d_ssm, o.nsha_compress_sponge,
-                                      N(SCS), T(SCS));
-        zkm_launch_logic_trace(c, (const uint32_t*)d_lo, o.nlogic, N(LO), T(LO), (int*)d_flags);
-        zkm_memory_write(mj, lg[ME], T(ME), (int*)d_flags + 1);
-        for (size_t r0 = 0, k = 0; r0 < o.ncpu_rows; r0 += piece_rows, k++) {   // (last: the copies overlap everything above)
-            if (cpu_host) ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, piece_done[k].e, 0));
-            launch_cpu_rows_to_cols(c, cpu_src + r0 * CPU_W, piece_rows, r0, N(CPU), T(CPU));
-        }
-        unsigned flags[3];
-        c->download(flags, d_flags, sizeof flags);                                                                       // wait (3)
-        if (flags[0]) refuse(LO, "op code out of range (0 and, 1 or, 2 xor, 3 nor)");
-        if (flags[1]) refuse(ME, "a range check is 2^log_n or more (a context or segment gap)");
-        if (flags[2]) refuse(AR, "a shared-column value is 2^16 or more");
-        return out;
     }
-};
+    c->download(sync.data(), d_sync, K * SYNC_WORDS * 8);                                                               // wait (3)
+    for (size_t s = 0; s < K; s++) {
+        const unsigned* f = (const unsigned*)&sync[s * SYNC_WORDS + 9];
+        if (f[0]) b[s].refuse(LO, "op code out of range (0 and, 1 or, 2 xor, 3 nor)");
+        if (f[1]) b[s].refuse(ME, "a range check is 2^log_n or more (a context or segment gap)");
+        if (f[2]) b[s].refuse(AR, "a shared-column value is 2^16 or more");
+    }
+    return out;
+}
+
+// the builders of a call: argument checks, every host check of every segment, the host-known heights.  A call of one segment through
+// the one-segment entry points names no position (label = false).
+std::vector<builder> make_builders(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segment_ops* ops, size_t nseg, size_t seg_base,
+                                   bool label) {
+    if (!cfg || !ops) throw std::runtime_error(std::string(what) + ": null argument");
+    if (nseg == 0) throw std::runtime_error(std::string(what) + ": no segments");
+    if (cfg->cap_height > SEG_MAX_LOG_N) throw std::runtime_error(std::string(what) + ": cap_height out of range");
+    std::vector<builder> b;
+    b.reserve(nseg);
+    for (size_t s = 0; s < nseg; s++) {
+        b.emplace_back(what, c, ops + s, seg_base + s, label);
+        b.back().check_host();
+        b.back().heights(cfg);
+    }
+    return b;
+}
+
+// a call of nseg segments in at least `nwaves` waves of at most ZKM_MAX_SEG: even sizes (two stack heights at most, as the prover's own waves)
+std::vector<size_t> even_waves(size_t nseg, size_t nwaves) {
+    nwaves = std::min(nseg, std::max<size_t>(nwaves, (nseg + ZKM_MAX_SEG - 1) / ZKM_MAX_SEG));
+    std::vector<size_t> k(nwaves, nseg / nwaves);
+    for (size_t w = 0; w < nseg % nwaves; w++) k[w]++;
+    return k;
+}
 
 }  // namespace
 
+struct zkm_staged_ops {
+    zkm_ctx* ctx = nullptr;
+    zkm_scratch block;                   // the CPU rows and every list
+    zkm_segment_ops dev{};               // the segment with device pointers; the two offset arrays point at the copies below
+    std::vector<uint64_t> ps_off, ks_off;
+    zkm_event done[2];                   // the end of the uploads on the two copy streams
+    bool joined = false;                 // the compute stream waits for both (first zkm_staged_ops_get)
+    ~zkm_staged_ops() {
+        if (!block.p) return;
+        std::lock_guard<std::mutex> lk(g_staged_mu);
+        g_staged_ops.erase(block.p);
+    }
+};
+
 extern "C" {
+
+int zkm_segments_tables(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out,
+                        char** err) {
+    return zkm_api("zkm_segments_tables", c, err, [&] {
+        if (!log_n_out) throw std::runtime_error("zkm_segments_tables: null argument");
+        std::vector<builder> b = make_builders("zkm_segments_tables", c, cfg, ops, nseg, 0, true);
+        std::vector<segment_block> blocks;   // (a failure in a later wave releases the earlier waves' blocks: no handle is left behind)
+        size_t s0 = 0;
+        for (const size_t k : even_waves(nseg, 1)) {
+            for (segment_block& sb : build_wave(c, b.data() + s0, k, out != nullptr)) blocks.push_back(std::move(sb));
+            s0 += k;
+        }
+        for (size_t s = 0; s < nseg; s++)
+            for (int t = 0; t < NTAB; t++) log_n_out[NTAB * s + t] = blocks[s].lg[t];
+        if (!out) return;
+        std::vector<zkm_staged*> handles;
+        try {
+            for (size_t s = 0; s < nseg; s++) {
+                handles.push_back(zkm_staged_from_segment(c, blocks[s].block.p, blocks[s].off));
+                blocks[s].block.take();
+            }
+        } catch (...) {
+            for (zkm_staged* h : handles) zkm_staged_free(h);
+            throw;
+        }
+        std::copy(handles.begin(), handles.end(), out);
+    });
+}
+
+int zkm_prove_segments_ops_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops,
+                                 const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, size_t* offsets_out,
+                                 uint64_t* const* challenges, char** err, size_t seg_base) {
+    return zkm_api(what, c, err, [&]() -> int {
+        if (proofs && !challenges) throw std::runtime_error(std::string(what) + ": null argument");
+        if (!proofs && !offsets_out) throw std::runtime_error(std::string(what) + ": null argument");
+        std::vector<builder> b = make_builders(what, c, cfg, ops, nseg, seg_base, true);
+        // ---- the waves: what a segment holds while it is proven (the prover's estimate at the heights the host knows), its tables and
+        // its part of the staging block, against the budget of zkm_prove_segments
+        size_t nwaves = 1;
+        if (proofs && nseg > 1) {
+            size_t free_b = 0, total_b = 0, live = 0, cached = 0;
+            ZKM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            zkm_ctx_memory(c, &live, &cached);
+            const double budget = c->segments_memory_budget ? (double)c->segments_memory_budget : 0.8 * ((double)cached + (double)free_b);
+            double total = 0;
+            for (size_t s = 0; s < nseg; s++) {
+                double tables = 0;
+                for (int t = 0; t < NTAB; t++) tables += 8.0 * (double)(zkm_table_width(TABLE_ID[t]) << b[s].lg[t]);
+                total += zkm_segment_footprint(cfg, b[s].lg) + tables + (double)b[s].plan(true, 0);
+            }
+            nwaves = (size_t)std::min<double>((double)nseg, std::max(1.0, std::ceil(total / std::max(budget, 1.0))));
+        }
+        size_t s0 = 0;
+        for (const size_t k : even_waves(nseg, nwaves)) {
+            std::vector<segment_block> blocks = build_wave(c, b.data() + s0, k, proofs != nullptr);
+            const uint64_t* traces[ZKM_MAX_SEG][NTAB] = {};
+            const uint64_t* const* tr[ZKM_MAX_SEG];
+            const unsigned* lg[ZKM_MAX_SEG];
+            for (size_t s = 0; s < k; s++) {
+                for (int t = 0; t < NTAB && proofs; t++) traces[s][t] = blocks[s].block.as<const uint64_t>() + blocks[s].off[t];
+                tr[s] = traces[s];
+                lg[s] = blocks[s].lg;
+                if (offsets_out)
+                    if (const int rc = zkm_prove_segment(nullptr, cfg, traces[s], lg[s], nullptr, 0, nullptr, offsets_out + 13 * (s0 + s), nullptr, err))
+                        return rc;
+            }
+            if (proofs)
+                if (const int rc = zkm_prove_segments_entry(what, c, cfg, k, tr, nullptr, lg, pub ? pub + s0 : nullptr, npub ? npub + s0 : nullptr,
+                                                            proofs + s0, challenges + s0, err, seg_base + s0))
+                    return rc;
+            s0 += k;
+        }
+        return 0;
+    });
+}
+
+int zkm_prove_segments_ops(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops, const uint64_t* const* pub,
+                           const size_t* npub, uint64_t* const* proofs, size_t* offsets_out, uint64_t* const* challenges, char** err) {
+    return zkm_prove_segments_ops_entry("zkm_prove_segments_ops", c, cfg, nseg, ops, pub, npub, proofs, offsets_out, challenges, err, 0);
+}
 
 int zkm_segment_tables(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out, char** err) {
     return zkm_api("zkm_segment_tables", c, err, [&] {
         if (!ops || !log_n_out) throw std::runtime_error("zkm_segment_tables: null argument");
-        builder b{"zkm_segment_tables", c, *ops};
-        segment_block sb = b.run(cfg, out != nullptr);
-        for (int t = 0; t < NTAB; t++) log_n_out[t] = b.lg[t];
+        std::vector<builder> b = make_builders("zkm_segment_tables", c, cfg, ops, 1, 0, false);
+        segment_block sb = std::move(build_wave(c, b.data(), 1, out != nullptr)[0]);
+        for (int t = 0; t < NTAB; t++) log_n_out[t] = sb.lg[t];
         if (!out) return;
         *out = zkm_staged_from_segment(c, sb.block.p, sb.off);
         sb.block.take();
@@ -341,12 +601,109 @@ int zkm_prove_segment_ops(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_seg
                           uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
     return zkm_api("zkm_prove_segment_ops", c, err, [&] {
         if (!ops) throw std::runtime_error("zkm_prove_segment_ops: null argument");
-        builder b{"zkm_prove_segment_ops", c, *ops};
-        segment_block sb = b.run(cfg, proofs != nullptr);
+        std::vector<builder> b = make_builders("zkm_prove_segment_ops", c, cfg, ops, 1, 0, false);
+        segment_block sb = std::move(build_wave(c, b.data(), 1, proofs != nullptr)[0]);
         const uint64_t* traces[NTAB] = {};
         for (int t = 0; t < NTAB; t++) traces[t] = proofs ? sb.block.as<const uint64_t>() + sb.off[t] : nullptr;
-        return zkm_prove_segment(proofs ? c : nullptr, cfg, traces, b.lg, pub, npub, proofs, offsets_out, challenges, err);
+        return zkm_prove_segment(proofs ? c : nullptr, cfg, traces, sb.lg, pub, npub, proofs, offsets_out, challenges, err);
     });
+}
+
+// ---- staged operations: the next call's lists behind the current proofs.  Every byte count is known on the host, so the uploads are
+// queued on the two copy streams (behind what the compute stream has queued: the block may be one a finished call released) and the
+// call returns; zkm_staged_ops_get orders the compute stream behind them with a device-side wait.
+int zkm_segment_ops_stage(zkm_ctx* c, const zkm_segment_ops* ops, zkm_staged_ops** out, char** err) {
+    return zkm_api("zkm_segment_ops_stage", c, err, [&] {
+        if (!ops || !out) throw std::runtime_error("zkm_segment_ops_stage: null argument");
+        builder b("zkm_segment_ops_stage", c, ops, 0, false);
+        b.check_host();
+        std::unique_ptr<zkm_staged_ops> h(new zkm_staged_ops());
+        h->ctx = c;
+        h->dev = *ops;
+        if (ops->nposeidon_sponge) h->ps_off.assign(ops->poseidon_sponge_off, ops->poseidon_sponge_off + ops->nposeidon_sponge + 1);
+        if (ops->nkeccak_sponge) h->ks_off.assign(ops->keccak_sponge_off, ops->keccak_sponge_off + ops->nkeccak_sponge + 1);
+        h->dev.poseidon_sponge_off = h->ps_off.data();
+        h->dev.keccak_sponge_off = h->ks_off.data();
+        const size_t cpu_bytes = ops->ncpu_rows * CPU_W * 8;
+        std::vector<list_ref> lists = lists_of(h->dev, b.ps_bytes, b.ks_bytes);
+        size_t bytes = align_up(cpu_bytes);
+        for (const list_ref& l : lists) bytes += align_up(l.bytes);
+        h->block = zkm_scratch(c, bytes);
+        char* base = h->block.as<char>();
+        c->ensure_copy_stream(0);
+        c->ensure_copy_stream(1);
+        {
+            const zkm_event e(c);
+            e.record(c->stream);
+            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
+            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
+        }
+        copy_join join;   // (a copy that fails to queue: the ones before it land before the block goes back)
+        join.c = c;
+        // alternate streams: the CPU rows in pieces of >= 16 MB, every other list in one copy (device-resident lists are copied too: the
+        // handle owns all it hands out)
+        size_t turn = 0, at = 0;
+        auto copy = [&](void* dst, const void* src, size_t n) {
+            ZKM_HIP_CHECK(hipMemcpyAsync(dst, src, n, hipMemcpyDefault, (turn++ & 1) ? c->copy_stream2 : c->copy_stream));
+        };
+        const size_t piece = std::max<size_t>((size_t)16 << 20, cpu_bytes / 16);
+        for (size_t o0 = 0; o0 < cpu_bytes; o0 += piece) copy(base + o0, (const char*)ops->cpu_rows + o0, std::min(piece, cpu_bytes - o0));
+        h->dev.cpu_rows = (const uint64_t*)base;
+        at = align_up(cpu_bytes);
+        for (const list_ref& l : lists) {
+            if (!l.bytes) continue;
+            copy(base + at, l.get(), l.bytes);
+            l.set(base + at);
+            at += align_up(l.bytes);
+        }
+        h->done[0] = zkm_event(c);
+        h->done[1] = zkm_event(c);
+        h->done[0].record(c->copy_stream);
+        h->done[1].record(c->copy_stream2);
+        join.c = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(g_staged_mu);
+            g_staged_ops[h->block.p] = c;
+        }
+        *out = h.release();
+    });
+}
+
+int zkm_staged_ops_get(zkm_staged_ops* h, zkm_segment_ops* ops_out) {
+    if (!h || !ops_out) return 1;
+    zkm_ctx* c = h->ctx;
+    if (!h->joined && zkm_api("zkm_staged_ops_get", c, nullptr, [&] {
+            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, h->done[0].e, 0));
+            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, h->done[1].e, 0));
+            h->joined = true;
+        }))
+        return 1;
+    *ops_out = h->dev;
+    return 0;
+}
+
+int zkm_staged_ops_ready(zkm_staged_ops* h, int wait) {
+    if (!h) return 1;
+    (void)hipSetDevice(h->ctx->device);
+    for (const zkm_event& e : h->done) {
+        if (wait) {
+            if (hipEventSynchronize(e.e) != hipSuccess) return -1;
+        } else {
+            const hipError_t q = hipEventQuery(e.e);
+            if (q == hipErrorNotReady) return 0;
+            if (q != hipSuccess) return -1;
+        }
+    }
+    return 1;
+}
+
+void zkm_staged_ops_free(zkm_staged_ops* h) {
+    if (!h) return;
+    (void)hipSetDevice(h->ctx->device);
+    // the block goes back to an allocator whose blocks are reused by later work of the compute stream only: the uploads must have landed
+    (void)hipEventSynchronize(h->done[0].e);
+    (void)hipEventSynchronize(h->done[1].e);
+    delete h;
 }
 
 }  // extern "C"

@@ -3,6 +3,12 @@
 // Every kernel writes the table column-major (the flattened Vec<PolynomialValues<F>> of util.rs:37-46) with consecutive
 // threads on consecutive rows, so each column store is a contiguous 512 B run per wavefront.  References are given at
 // each kernel.  The Memory table, whose rows need a sort, has its own file (memory_trace.hip).
+//
+// Every kernel serves K segments in one launch: its segment's zkm_writer_seg (zkm_internal.h) comes from kernel-argument slot
+// blockIdx.z, the grid's x extent is the largest segment's, and the `r >= n` that ends a thread beyond its table ends the workgroups
+// beyond a smaller segment's extent too.  zkm_launch_writers is the one launcher; the zkm_launch_*_trace helpers are its K = 1 case.
+#include <vector>
+
 #include "poseidon_dev.h"
 #include "hash_constants_dev.h"
 #include "zkm_internal.h"
@@ -32,9 +38,14 @@ __device__ __forceinline__ uint64_t sponge_block_word(const uint8_t* __restrict_
     return w;
 }
 
-__global__ __launch_bounds__(128) void k_keccak_sponge_states(const uint8_t* __restrict__ inputs, const uint64_t* __restrict__ off,
-                                                              const uint64_t* __restrict__ row_off, size_t nops,
-                                                              uint64_t* __restrict__ row_state, uint32_t* __restrict__ row_op) {
+__global__ __launch_bounds__(128) void k_keccak_sponge_states(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint8_t* __restrict__ inputs = (const uint8_t*)A.in[0];
+    const uint64_t* __restrict__ off = (const uint64_t*)A.in[1];
+    const uint64_t* __restrict__ row_off = (const uint64_t*)A.in[3];
+    const size_t nops = A.k;
+    uint64_t* __restrict__ row_state = (uint64_t*)A.tmp[0];
+    uint32_t* __restrict__ row_op = (uint32_t*)A.tmp[1];
     const size_t op = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (op >= nops) return;
     const uint8_t* msg = inputs + off[op];
@@ -59,10 +70,16 @@ __global__ __launch_bounds__(128) void k_keccak_sponge_states(const uint8_t* __r
     }
 }
 
-__global__ __launch_bounds__(256) void k_keccak_sponge_rows(const uint8_t* __restrict__ inputs, const uint64_t* __restrict__ off,
-                                                            const uint64_t* __restrict__ meta, const uint64_t* __restrict__ row_off,
-                                                            const uint64_t* __restrict__ row_state, const uint32_t* __restrict__ row_op,
-                                                            size_t rows_used, size_t n, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_keccak_sponge_rows(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint8_t* __restrict__ inputs = (const uint8_t*)A.in[0];
+    const uint64_t* __restrict__ off = (const uint64_t*)A.in[1];
+    const uint64_t* __restrict__ meta = (const uint64_t*)A.in[2];
+    const uint64_t* __restrict__ row_off = (const uint64_t*)A.in[3];
+    const uint64_t* __restrict__ row_state = (const uint64_t*)A.tmp[0];
+    const uint32_t* __restrict__ row_op = (const uint32_t*)A.tmp[1];
+    const size_t rows_used = A.aux, n = A.n;
+    gl_t* __restrict__ out = A.out;
     const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     gl_t* o = out + r;
@@ -120,14 +137,8 @@ __global__ __launch_bounds__(256) void k_keccak_sponge_rows(const uint8_t* __res
 
 void zkm_launch_keccak_sponge_trace(zkm_ctx* c, const uint8_t* d_inputs, const uint64_t* d_off, const uint64_t* d_meta,
                                     const uint64_t* d_row_off, size_t nops, size_t rows_used, unsigned log_n, gl_t* out) {
-    const size_t n = (size_t)1 << log_n;
-    zkm_scratch row_state(c, (rows_used ? rows_used : 1) * 25 * sizeof(uint64_t)), row_op(c, (rows_used ? rows_used : 1) * sizeof(uint32_t));
-    zkm_prof_scope ps(c, "keccak_sponge_trace");
-    if (nops) hipLaunchKernelGGL(k_keccak_sponge_states, dim3((nops + 127) / 128), dim3(128), 0, c->stream, d_inputs, d_off, d_row_off, nops,
-                                 row_state.as<uint64_t>(), row_op.as<uint32_t>());
-    hipLaunchKernelGGL(k_keccak_sponge_rows, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_inputs, d_off, d_meta, d_row_off,
-                       row_state.as<uint64_t>(), row_op.as<uint32_t>(), rows_used, n, out);
-    ZKM_HIP_CHECK(hipGetLastError());
+    const zkm_writer_seg a{{d_inputs, d_off, d_meta, d_row_off}, nops, (size_t)1 << log_n, rows_used, out};
+    zkm_launch_writers(c, ZKM_TABLE_KECCAK_SPONGE, &a, 1);
 }
 
 
@@ -141,8 +152,13 @@ __device__ __forceinline__ uint64_t splitmix_at(uint64_t seed, uint64_t k) {
 
 // One row per lane; every column store is a contiguous wave access (column-major output).
 // Column map: poseidon/columns.rs:3-54 (FILTER 0, in 1..12, out 13..24, TIMESTAMP 25, full0 26.., partial 122.., full1 166..)
-__global__ __launch_bounds__(256) void k_poseidon_trace(uint64_t seed, const uint64_t* __restrict__ inputs, const uint64_t* __restrict__ ts,
-                                                        size_t num_perms, size_t n, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_poseidon_trace(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint64_t seed = A.aux;
+    const uint64_t* __restrict__ inputs = (const uint64_t*)A.in[0];
+    const uint64_t* __restrict__ ts = (const uint64_t*)A.in[1];
+    const size_t num_perms = A.k, n = A.n;
+    gl_t* __restrict__ out = A.out;
     size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     bool real = r < num_perms;
@@ -210,16 +226,18 @@ __global__ __launch_bounds__(256) void k_poseidon_trace(uint64_t seed, const uin
 
 void zkm_launch_poseidon_trace(zkm_ctx* c, uint64_t seed, const uint64_t* inputs, const uint64_t* ts, size_t num_perms, unsigned log_n,
                                gl_t* out) {
-    size_t n = (size_t)1 << log_n;
-    zkm_prof_scope ps(c, "poseidon_trace");
-    hipLaunchKernelGGL(k_poseidon_trace, dim3((n + 255) / 256), dim3(256), 0, c->stream, seed, inputs, ts, num_perms, n, out);
-    ZKM_HIP_CHECK(hipGetLastError());
+    const zkm_writer_seg a{{inputs, ts}, num_perms, (size_t)1 << log_n, seed, out};
+    zkm_launch_writers(c, ZKM_TABLE_POSEIDON, &a, 1);
 }
 
 // ------------------------------------------------------------------ LogicStark witness (logic.rs:122-183)
 // One thread per row; stores are coalesced per column (column-major).
-__global__ __launch_bounds__(256) void k_logic_trace(const uint32_t* __restrict__ ops, size_t nops, size_t n, gl_t* __restrict__ out,
-                                                     int* __restrict__ bad) {
+__global__ __launch_bounds__(256) void k_logic_trace(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint32_t* __restrict__ ops = (const uint32_t*)A.in[0];
+    const size_t nops = A.k, n = A.n;
+    gl_t* __restrict__ out = A.out;
+    int* __restrict__ bad = A.bad;
     size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     uint32_t op = 4, a = 0, b = 0, res = 0;
@@ -241,17 +259,20 @@ __global__ __launch_bounds__(256) void k_logic_trace(const uint32_t* __restrict_
 }
 
 void zkm_launch_logic_trace(zkm_ctx* c, const uint32_t* d_ops, size_t nops, size_t n, gl_t* out, int* d_bad) {
-    zkm_prof_scope ps(c, "logic_trace");
-    hipLaunchKernelGGL(k_logic_trace, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_ops, nops, n, out, d_bad);
-    ZKM_HIP_CHECK(hipGetLastError());
+    const zkm_writer_seg a{{d_ops}, nops, n, 0, out, d_bad};
+    zkm_launch_writers(c, ZKM_TABLE_LOGIC, &a, 1);
 }
 
 // ------------------------------------------------------------------ KeccakStark witness (keccak/keccak_stark.rs:62-226)
 // One thread per trace row (permutation p, round r): replays r rounds from the input (at most 23 cheap rounds; the row's
 // 2431 stores dominate), then emits the round's registers.  Consecutive threads own consecutive rows, so every
 // column store is a contiguous 512-byte run per wavefront.  State index: a[x + 5y] = A(x, y).
-__global__ __launch_bounds__(256) void k_keccak_trace(const uint64_t* __restrict__ inputs, const uint64_t* __restrict__ ts, size_t nperms,
-                                                      size_t n, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_keccak_trace(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint64_t* __restrict__ inputs = (const uint64_t*)A.in[0];
+    const uint64_t* __restrict__ ts = (const uint64_t*)A.in[1];
+    const size_t nperms = A.k, n = A.n;
+    gl_t* __restrict__ out = A.out;
     size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n) return;
     gl_t* o = out + row;
@@ -311,17 +332,21 @@ __global__ __launch_bounds__(256) void k_keccak_trace(const uint64_t* __restrict
 }
 
 void zkm_launch_keccak_trace(zkm_ctx* c, const uint64_t* d_inputs, const uint64_t* d_ts, size_t nperms, size_t n, gl_t* out) {
-    zkm_prof_scope ps(c, "keccak_trace");
-    hipLaunchKernelGGL(k_keccak_trace, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_inputs, d_ts, nperms, n, out);
-    ZKM_HIP_CHECK(hipGetLastError());
+    const zkm_writer_seg a{{d_inputs, d_ts}, nperms, n, 0, out};
+    zkm_launch_writers(c, ZKM_TABLE_KECCAK, &a, 1);
 }
 
 // ------------------------------------------------------------------ PoseidonSpongeStark witness (poseidon_sponge_stark.rs:186-381)
 // One lane per sponge operation, as k_keccak_sponge_trace; column map poseidon_sponge/columns.rs:17-66.  The output buffer is
 // zero-filled first; only non-zero cells are stored.
-__global__ __launch_bounds__(128) void k_poseidon_sponge_trace(const uint8_t* __restrict__ inputs, const uint64_t* __restrict__ off,
-                                                               const uint64_t* __restrict__ meta, const uint64_t* __restrict__ row_off,
-                                                               size_t nops, size_t n, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(128) void k_poseidon_sponge_trace(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint8_t* __restrict__ inputs = (const uint8_t*)A.in[0];
+    const uint64_t* __restrict__ off = (const uint64_t*)A.in[1];
+    const uint64_t* __restrict__ meta = (const uint64_t*)A.in[2];
+    const uint64_t* __restrict__ row_off = (const uint64_t*)A.in[3];
+    const size_t nops = A.k, n = A.n;
+    gl_t* __restrict__ out = A.out;
     size_t op = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (op >= nops) return;
     const uint8_t* msg = inputs + off[op];
@@ -378,12 +403,8 @@ __global__ __launch_bounds__(128) void k_poseidon_sponge_trace(const uint8_t* __
 
 void zkm_launch_poseidon_sponge_trace(zkm_ctx* c, const uint8_t* d_inputs, const uint64_t* d_off, const uint64_t* d_meta,
                                       const uint64_t* d_row_off, size_t nops, unsigned log_n, gl_t* out) {
-    size_t n = (size_t)1 << log_n;
-    ZKM_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)ZKM_POSEIDON_SPONGE_COLS * n * sizeof(gl_t), c->stream));
-    if (!nops) return;
-    zkm_prof_scope ps(c, "poseidon_sponge_trace");
-    hipLaunchKernelGGL(k_poseidon_sponge_trace, dim3((nops + 127) / 128), dim3(128), 0, c->stream, d_inputs, d_off, d_meta, d_row_off, nops, n, out);
-    ZKM_HIP_CHECK(hipGetLastError());
+    const zkm_writer_seg a{{d_inputs, d_off, d_meta, d_row_off}, nops, (size_t)1 << log_n, 0, out};
+    zkm_launch_writers(c, ZKM_TABLE_POSEIDON_SPONGE, &a, 1);
 }
 
 // ------------------------------------------------------------------ SHA-256 message-schedule witnesses
@@ -400,8 +421,12 @@ __device__ __forceinline__ void put_rot_dev(gl_t* o, size_t n, int col, uint32_t
     o[(size_t)(col + 4) * n] = shift;
     o[(size_t)(col + 5) * n] = carry;
 }
-__global__ __launch_bounds__(256) void k_sha_extend_trace(const uint8_t* __restrict__ inputs, const uint64_t* __restrict__ ts, size_t k,
-                                                          size_t n, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_sha_extend_trace(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint8_t* __restrict__ inputs = (const uint8_t*)A.in[0];
+    const uint64_t* __restrict__ ts = (const uint64_t*)A.in[1];
+    const size_t k = A.k, n = A.n;
+    gl_t* __restrict__ out = A.out;
     size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     gl_t* o = out + r;
@@ -438,8 +463,12 @@ __global__ __launch_bounds__(256) void k_sha_extend_trace(const uint8_t* __restr
 }
 
 // row = 48 e + round; the thread recomputes the schedule of its block up to its round (at most 48 cheap steps)
-__global__ __launch_bounds__(256) void k_sha_extend_sponge_trace(const uint32_t* __restrict__ w16, const uint64_t* __restrict__ meta, size_t k,
-                                                                 size_t n, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_sha_extend_sponge_trace(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint32_t* __restrict__ w16 = (const uint32_t*)A.in[0];
+    const uint64_t* __restrict__ meta = (const uint64_t*)A.in[1];
+    const size_t k = A.k, n = A.n;
+    gl_t* __restrict__ out = A.out;
     size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n) return;
     gl_t* o = out + row;
@@ -478,14 +507,12 @@ __global__ __launch_bounds__(256) void k_sha_extend_sponge_trace(const uint32_t*
 }
 
 void zkm_launch_sha_extend_trace(zkm_ctx* c, const uint8_t* d_inputs, const uint64_t* d_ts, size_t k, size_t n, gl_t* out) {
-    zkm_prof_scope ps(c, "sha_extend_trace");
-    hipLaunchKernelGGL(k_sha_extend_trace, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_inputs, d_ts, k, n, out);
-    ZKM_HIP_CHECK(hipGetLastError());
+    const zkm_writer_seg a{{d_inputs, d_ts}, k, n, 0, out};
+    zkm_launch_writers(c, ZKM_TABLE_SHA_EXTEND, &a, 1);
 }
 void zkm_launch_sha_extend_sponge_trace(zkm_ctx* c, const uint32_t* d_w16, const uint64_t* d_meta, size_t k, size_t n, gl_t* out) {
-    zkm_prof_scope ps(c, "sha_extend_sponge_trace");
-    hipLaunchKernelGGL(k_sha_extend_sponge_trace, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_w16, d_meta, k, n, out);
-    ZKM_HIP_CHECK(hipGetLastError());
+    const zkm_writer_seg a{{d_w16, d_meta}, k, n, 0, out};
+    zkm_launch_writers(c, ZKM_TABLE_SHA_EXTEND_SPONGE, &a, 1);
 }
 
 // ------------------------------------------------------------------ SHA-256 compression witnesses
@@ -504,8 +531,13 @@ __device__ __forceinline__ void put_wadd_dev(gl_t* o, size_t n, int col, uint64_
 #pragma unroll
     for (uint32_t c = 0; c < NC; c++) o[(size_t)(col + 4 + c) * n] = (uint32_t)(wide >> 32) == c;
 }
-__global__ __launch_bounds__(256) void k_sha_compress_trace(const uint32_t* __restrict__ hx, const uint32_t* __restrict__ w,
-                                                            const uint64_t* __restrict__ meta, size_t k, size_t n, gl_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_sha_compress_trace(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint32_t* __restrict__ hx = (const uint32_t*)A.in[0];
+    const uint32_t* __restrict__ w = (const uint32_t*)A.in[1];
+    const uint64_t* __restrict__ meta = (const uint64_t*)A.in[2];
+    const size_t k = A.k, n = A.n;
+    gl_t* __restrict__ out = A.out;
     size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (row >= n) return;
     gl_t* o = out + row;
@@ -546,9 +578,13 @@ __global__ __launch_bounds__(256) void k_sha_compress_trace(const uint32_t* __re
     o[(size_t)149 * n] = meta[8 * e_ + 4] + 4 * (uint64_t)rd;
     for (int i = 0; i < 65; i++) o[(size_t)(159 + i) * n] = i == rd;
 }
-__global__ __launch_bounds__(256) void k_sha_compress_sponge_trace(const uint32_t* __restrict__ hx, const uint32_t* __restrict__ w,
-                                                                   const uint64_t* __restrict__ meta, size_t k, size_t n,
-                                                                   gl_t* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_sha_compress_sponge_trace(zkm_seg_args<zkm_writer_seg> S) {
+    const zkm_writer_seg& A = S.v[blockIdx.z];
+    const uint32_t* __restrict__ hx = (const uint32_t*)A.in[0];
+    const uint32_t* __restrict__ w = (const uint32_t*)A.in[1];
+    const uint64_t* __restrict__ meta = (const uint64_t*)A.in[2];
+    const size_t k = A.k, n = A.n;
+    gl_t* __restrict__ out = A.out;
     size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n) return;
     gl_t* o = out + r;
@@ -577,8 +613,53 @@ __global__ __launch_bounds__(256) void k_sha_compress_sponge_trace(const uint32_
 }
 void zkm_launch_sha_compress_trace(zkm_ctx* c, bool sponge, const uint32_t* d_hx, const uint32_t* d_w, const uint64_t* d_meta, size_t k,
                                    size_t n, gl_t* out) {
-    zkm_prof_scope ps(c, sponge ? "sha_compress_sponge_trace" : "sha_compress_trace");
-    if (sponge) hipLaunchKernelGGL(k_sha_compress_sponge_trace, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_hx, d_w, d_meta, k, n, out);
-    else hipLaunchKernelGGL(k_sha_compress_trace, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_hx, d_w, d_meta, k, n, out);
-    ZKM_HIP_CHECK(hipGetLastError());
+    const zkm_writer_seg a{{d_hx, d_w, d_meta}, k, n, 0, out};
+    zkm_launch_writers(c, sponge ? ZKM_TABLE_SHA_COMPRESS_SPONGE : ZKM_TABLE_SHA_COMPRESS, &a, 1);
+}
+
+// ------------------------------------------------------------------ the launcher of every writer above, nseg <= ZKM_MAX_SEG segments
+// One thread per row of the table (per operation for the two chained sponge kernels): the grid covers the largest segment.
+void zkm_launch_writers(zkm_ctx* c, int table_id, const zkm_writer_seg* segs, size_t nseg) {
+    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_launch_writers: segment count out of range");
+    size_t max_n = 0, max_k = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        max_n = std::max(max_n, segs[s].n);
+        max_k = std::max(max_k, segs[s].k);
+    }
+    const size_t rows256 = (max_n + 255) / 256, ops128 = (max_k + 127) / 128;
+    auto go = [&](const char* scope, void (*kernel)(zkm_seg_args<zkm_writer_seg>), const zkm_writer_seg* a, size_t grid, unsigned threads) {
+        zkm_prof_scope ps(c, scope);
+        zkm_launch_segs(c->stream, kernel, a, nseg, grid, threads);
+    };
+    switch (table_id) {
+    case ZKM_TABLE_POSEIDON: return go("poseidon_trace", k_poseidon_trace, segs, rows256, 256);
+    case ZKM_TABLE_KECCAK: return go("keccak_trace", k_keccak_trace, segs, rows256, 256);
+    case ZKM_TABLE_SHA_EXTEND: return go("sha_extend_trace", k_sha_extend_trace, segs, rows256, 256);
+    case ZKM_TABLE_SHA_EXTEND_SPONGE: return go("sha_extend_sponge_trace", k_sha_extend_sponge_trace, segs, rows256, 256);
+    case ZKM_TABLE_SHA_COMPRESS: return go("sha_compress_trace", k_sha_compress_trace, segs, rows256, 256);
+    case ZKM_TABLE_SHA_COMPRESS_SPONGE: return go("sha_compress_sponge_trace", k_sha_compress_sponge_trace, segs, rows256, 256);
+    case ZKM_TABLE_LOGIC: return go("logic_trace", k_logic_trace, segs, rows256, 256);
+    case ZKM_TABLE_POSEIDON_SPONGE:
+        // the table is zero-filled first; only non-zero cells are stored
+        for (size_t s = 0; s < nseg; s++)
+            ZKM_HIP_CHECK(hipMemsetAsync(segs[s].out, 0, (size_t)ZKM_POSEIDON_SPONGE_COLS * segs[s].n * sizeof(gl_t), c->stream));
+        if (max_k) go("poseidon_sponge_trace", k_poseidon_sponge_trace, segs, ops128, 128);
+        return;
+    case ZKM_TABLE_KECCAK_SPONGE: {
+        // per segment: the sponge state before each row in use (25 words) and the row's operation
+        std::vector<zkm_scratch> tmp;
+        std::vector<zkm_writer_seg> a(segs, segs + nseg);
+        for (size_t s = 0; s < nseg; s++) {
+            const size_t rows = a[s].aux ? a[s].aux : 1;
+            tmp.emplace_back(c, rows * 25 * sizeof(uint64_t) + rows * sizeof(uint32_t));
+            a[s].tmp[0] = tmp.back().p;
+            a[s].tmp[1] = tmp.back().as<uint64_t>() + rows * 25;
+        }
+        zkm_prof_scope ps(c, "keccak_sponge_trace");
+        zkm_launch_segs(c->stream, k_keccak_sponge_states, a.data(), nseg, ops128, 128);
+        zkm_launch_segs(c->stream, k_keccak_sponge_rows, a.data(), nseg, rows256, 256);
+        return;
+    }
+    default: throw std::runtime_error("zkm_launch_writers: no data-parallel writer for table " + std::to_string(table_id));
+    }
 }

@@ -5,6 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <exception>
 #include <map>
@@ -51,6 +52,11 @@ struct seg_gl2 { gl_t v[2 * ZKM_MAX_SEG]; };     // two per segment (an F2 eleme
 #ifndef ZKM_LEAF_MFMA_DEFAULT
 #define ZKM_LEAF_MFMA_DEFAULT 1
 #endif
+
+// K segments served by ONE launch (the witness generators; the prover's kernels use the same idiom, zkm_batch): descriptor s sits in
+// kernel-argument slot s, the kernel takes its segment from blockIdx.z -- a uniform read, so the descriptor lives in scalar registers --
+// and the grid's x extent is the largest segment's; workgroups beyond a segment's own extent leave at once.
+template <class A> struct zkm_seg_args { A v[ZKM_MAX_SEG]; };
 
 struct zkm_twiddles {
     gl_t* fwd = nullptr;  // per-stage tables concatenated: entry (1<<s) + j = w_{2^(s+1)}^j, j < 2^s
@@ -336,6 +342,17 @@ inline bool zkm_is_device_ptr(const void* p) {
     return a.type == hipMemoryTypeDevice;
 }
 
+template <class A, class... X>
+void zkm_launch_segs(hipStream_t stream, void (*kernel)(zkm_seg_args<A>, X...), const A* segs, size_t nseg, size_t grid_x, unsigned threads, X... x) {
+    static_assert(sizeof(zkm_seg_args<A>) + sizeof...(X) * 8 <= 3840, "the descriptors travel as kernel arguments (4 KiB)");
+    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_launch_segs: segment count out of range");
+    if (!grid_x) return;
+    zkm_seg_args<A> S{};
+    std::copy(segs, segs + nseg, S.v);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid_x, 1, (unsigned)nseg), dim3(threads), 0, stream, S, x...);
+    ZKM_HIP_CHECK(hipGetLastError());
+}
+
 // ---- hash.hip
 void zkm_launch_poseidon_permute(zkm_ctx*, gl_t* states, size_t k);
 void zkm_launch_mul_selftest_branchfree(zkm_ctx*, const uint64_t* a, const uint64_t* b, size_t n, uint64_t* out);  // stark.hip
@@ -418,6 +435,17 @@ struct zkm_table_lookup { uint32_t ncols; const uint32_t* cols; uint32_t table_c
 const zkm_table_lookup* zkm_table_lookups(int table_id, size_t* n);
 void zkm_table_lookup_columns_device(zkm_ctx* c, int table_id, const uint64_t* challenges, size_t nch, const gl_t* d_trace, size_t n,
                                      gl_t* d_out, size_t nseg = 1, size_t trace_seg = 0, size_t out_seg = 0);
+// ---- witness.hip: the data-parallel writers, K segments a launch.  One descriptor serves every table: `in` are the table's input lists
+// in the order of its zkm_launch_*_trace below, k the operations, n the table's rows, aux the Poseidon seed or the KeccakSponge rows in
+// use, bad the Logic flag; tmp is the KeccakSponge scratch (filled in by the launcher).
+struct zkm_writer_seg {
+    const void* in[4];
+    size_t k, n, aux;
+    gl_t* out;
+    int* bad;
+    void* tmp[2];
+};
+void zkm_launch_writers(zkm_ctx* c, int table_id, const zkm_writer_seg* segs, size_t nseg);
 void zkm_launch_sha_extend_trace(zkm_ctx* c, const uint8_t* d_inputs, const uint64_t* d_ts, size_t k, size_t n, gl_t* out);
 void zkm_launch_sha_extend_sponge_trace(zkm_ctx* c, const uint32_t* d_w16, const uint64_t* d_meta, size_t k, size_t n, gl_t* out);
 void zkm_launch_sha_compress_trace(zkm_ctx* c, bool sponge, const uint32_t* d_hx, const uint32_t* d_w, const uint64_t* d_meta, size_t k,
@@ -437,15 +465,19 @@ struct zkm_memory_job {
     const uint64_t* d_ops;       // nops x 6 words, device
     size_t nops;
     zkm_scratch small, keys_a, keys_b, idx_a, idx_b, start;
-    unsigned long long* d_acc = nullptr;   // in `small`: [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies, [6] free
+    // [0, 5) OR of the key fields and the >= p flag, [5] last op with dummies; d_count: where the row count lands beside start[nops].
+    // Null: in `small` ([6] free), which widths then allocates; a caller of several jobs points them into one block, for one download.
+    unsigned long long* d_acc = nullptr;
+    uint64_t* d_count = nullptr;
     const uint32_t* idx = nullptr;         // sorted order
     uint64_t M = 0, count = 0;
     zkm_memory_job(zkm_ctx* ctx, const char* w, const uint64_t* ops, size_t n) : c(ctx), what(w), d_ops(ops), nops(n) {}
 };
-void zkm_memory_widths(zkm_memory_job& j);
-void zkm_memory_sort(zkm_memory_job& j, const uint64_t acc[5]);
+// (the launching phases take nseg <= ZKM_MAX_SEG jobs of one context and serve them with ONE launch per kernel)
+void zkm_memory_widths(zkm_memory_job* j, size_t nseg);
+void zkm_memory_sort(zkm_memory_job* j, size_t nseg, const uint64_t* acc, size_t acc_stride);   // job s: acc[s * acc_stride + (0..5)]
 size_t zkm_memory_height(zkm_memory_job& j, uint64_t count, size_t* natural_rows_out);   // next_pow2(count); throws if it saturated
-void zkm_memory_write(zkm_memory_job& j, unsigned log_n, gl_t* out_dev, int* d_bad);
+void zkm_memory_write(zkm_memory_job* j, size_t nseg, const unsigned* log_n, gl_t* const* out_dev, int* const* d_bad);
 // arithmetic_trace.hip: count (validation flags and the scan of the row counts: rows at start[nops], flags at start[nops + 1]) -> the
 // host reads both -> height -> write (rows, RC_FREQUENCIES; *d_bad set on a shared-column value of 2^16 or more)
 struct zkm_arith_job {
@@ -456,14 +488,20 @@ struct zkm_arith_job {
     zkm_scratch start, hist;
     uint64_t rows = 0;
     zkm_arith_job(zkm_ctx* ctx, const char* w, const uint32_t* ops, size_t n) : c(ctx), what(w), d_ops(ops), nops(n) {}
-    uint64_t* counts() const { return start.as<uint64_t>() + nops; }   // {rows, flags}: the two words the host reads
+    uint64_t* d_counts = nullptr;   // {rows, flags}: the two words the host reads.  Null: start[nops], start[nops + 1]
+    uint64_t* counts() const { return d_counts ? d_counts : start.as<uint64_t>() + nops; }
 };
-void zkm_arithmetic_count(zkm_arith_job& j);
+void zkm_arithmetic_count(zkm_arith_job* j, size_t nseg);
 size_t zkm_arithmetic_height(zkm_arith_job& j, const uint64_t got[2], size_t* natural_rows_out);   // max(2^16, next_pow2(rows)); throws on a flag
-void zkm_arithmetic_write(zkm_arith_job& j, unsigned log_n, gl_t* out_dev, unsigned* d_bad);
+void zkm_arithmetic_write(zkm_arith_job* j, size_t nseg, const unsigned* log_n, gl_t* const* out_dev, unsigned* const* d_bad);
 
 // ctl.hip: the body of zkm_prove_segments[_columns] (exactly one of traces / columns non-null); seg_base = position of segment 0 in the
 // caller's larger call (csrc/pool.hip deals groups of one pool call to its workers) -- used in error messages only
 extern "C" int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const uint64_t* const* const* traces,
                                         const uint64_t* const* const* const* columns, const unsigned* const* log_n, const uint64_t* const* pub,
                                         const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges, char** err, size_t seg_base);
+double zkm_segment_footprint(const zkm_stark_config* cfg, const unsigned log_n[12]);   // ctl.hip: estimated bytes of one segment in a proving wave
+// segment_ops.hip: the body of zkm_prove_segments_ops, seg_base as above (the pool's workers)
+extern "C" int zkm_prove_segments_ops_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops,
+                                            const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, size_t* offsets_out,
+                                            uint64_t* const* challenges, char** err, size_t seg_base);
