@@ -90,6 +90,14 @@ void zkm_ctx_trim(zkm_ctx* ctx);
  *                               polling a flag in pinned memory; after this many microseconds (default 50) a thread of a CROWDED
  *                               process -- more than half as many threads waiting as CPUs the process may run on -- parks on a
  *                               blocking-sync event instead, leaving its core to the other contexts.  0: always park.
+ *   "check_ctls"                1: zkm_prove_with_traces, zkm_prove_segment[_columns], zkm_prove_segment_ops, zkm_prove_segments[_columns] and
+ *                               zkm_prove_segments_ops run zkm_check_ctls on each segment's tables before they prove -- the reference's `test`
+ *                               feature (prover.rs:171-176) -- and fail with "check_ctls: segment <position in the call>: " and that call's
+ *                               message; no proof is written.  Default 0: no launch is added and every proof word stays what it is
+ *   "debug_ctl_key_bits"        TEST HOOK, accepted only when the process environment holds ZKM_ENABLE_TEST_HOOKS=1 (an unknown key otherwise):
+ *                               the FIRST attempt of every zkm_check_ctls call sorts by keys truncated to `value` bits (0: off), so that the
+ *                               collision path -- confirmation fails, the call sorts again with the next seed -- runs; reports are
+ *                               unchanged and `attempts` is 2 (tests/test_gpu_check_ctls.py)
  *   "debug_fail_allocs"         TEST HOOK, accepted only when the process environment holds ZKM_ENABLE_TEST_HOOKS=1 (an unknown key otherwise):
  *                               the next `value` device allocations of the context and its lanes fail on their first
  *                               attempt as if out of memory, so the recovery path (trim the caches -- this context's, then the
@@ -770,6 +778,50 @@ int zkm_quotient(zkm_ctx* ctx, int table_id, const zkm_batch* trace, const zkm_b
 int zkm_check_constraints(zkm_ctx* ctx, int table_id, const zkm_stark_config* cfg, const uint64_t* trace, size_t ncols, unsigned log_n,
                           const uint64_t* aux, size_t naux, const zkm_ctl_table* table, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs,
                           const uint64_t* lookup_challenges, const uint64_t* alphas, size_t nalphas, uint64_t* first_failing_row, char** err);
+/* check_ctls (cross_table_lookup.rs:1486-1581 testutils::check_ctls; prove_with_traces calls it under the `test` feature, prover.rs:171-176):
+ * for each CrossTableLookup, the multiset of the rows of the looking tables whose filter is 1 (check_ctl :1505-1536, process_table
+ * :1538-1563) must equal that of the looked table -- on the device, nothing downloaded.  tables / ctls / sides / nctls as
+ * zkm_prove_with_traces takes them (`trace` or `columns`, host or device pointers; host tables are copied up for the call).
+ * Tuples are compared as canonical field elements; Columns with next-row terms follow eval_table (:266-285: on the last row the next-row
+ * part is zero); a filter value other than 0 or 1 is the reference's "Non-binary filter?" (:1560).
+ * Returns 0 when every lookup holds.  Otherwise nonzero, with `report` filled (it may be NULL) and *err =
+ *   "CTL #i: Row [..] is present a times in the looking tables, but b times in the looked table. Looking locations (Table, Row index):
+ *    [(Cpu, 5), ..]. Looked locations (Table, Row index): []."   (check_locations :1565-1581), or
+ *   "CTL #i: Non-binary filter? (side s, table T, row r: the filter is v)".
+ * WHICH finding is reported is fixed: the lowest failing lookup; within it a non-binary filter wins over a multiset difference, and the
+ * row named is the smallest in (side, row) order -- side = position among the lookup's looking sides, the looked side counting last;
+ * among unbalanced tuples the one whose first occurrence comes first in (side, row) order; locations are listed in that order.
+ *   kind          0 consistent; 1 non-binary filter; 2 multisets differ; 3 the check could not be made (bad arguments, column sets of
+ *                 unequal width on the two sides of a lookup, a runtime failure): the message says why
+ *   ctl           the reported lookup (kind 1, 2)
+ *   attempts      rows are matched by sorting 128-bit keys of their tuples; every match is confirmed word for word, and keys of different
+ *                 tuples that collide make the call sort again with other keys: the number of sorts (1 in practice; kind 3 after 4)
+ *   host_waits    times the call waited for the device: the same whatever the number of lookups and sides
+ *   side, table, row, filter_value   kind 1: the row (table = index into `tables`) and its filter's value
+ *   width, nwords, tuple             kind 2: the tuple's columns, and the first nwords = min(width, 64) canonical words
+ *   looking_count, looked_count      kind 2: its occurrences on either side
+ *   looking, looked                  kind 2: the first n*_locations = min(count, 8) locations of either side
+ * zkm_segment_check_ctls: the same for the AllStark that ships with the library, traces[t] / log_n[t] of Table::all()[t] as
+ * zkm_prove_segment takes them -- e.g. the twelve device pointers of zkm_staged_segment_ptrs for a block zkm_segment_tables built.
+ * Both run on the context's stream, behind what is queued there.  A debugging aid: on the proving path only under "check_ctls". */
+/* (Layout lock: `tools/abi_layout check_ctls` prints these two structs, tests/test_check_ctls_abi.py compares them with the ctypes and
+ * Rust mirrors.) */
+#define ZKM_CTL_REPORT_WORDS 64
+#define ZKM_CTL_REPORT_LOCATIONS 8
+typedef struct zkm_ctl_location { uint32_t side, table; uint64_t row; } zkm_ctl_location;
+typedef struct zkm_ctl_report {
+    uint32_t kind, ctl, attempts, host_waits;
+    uint32_t side, table;
+    uint64_t row, filter_value;
+    uint32_t width, nwords;
+    uint64_t tuple[ZKM_CTL_REPORT_WORDS];
+    uint64_t looking_count, looked_count;
+    uint32_t nlooking_locations, nlooked_locations;
+    zkm_ctl_location looking[ZKM_CTL_REPORT_LOCATIONS], looked[ZKM_CTL_REPORT_LOCATIONS];
+} zkm_ctl_report;
+int zkm_check_ctls(zkm_ctx* ctx, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
+                   size_t nctls, zkm_ctl_report* report, char** err);
+int zkm_segment_check_ctls(zkm_ctx* ctx, const uint64_t* const* traces, const unsigned* log_n, zkm_ctl_report* report, char** err);
 /* a9: StarkOpeningSet::new building block (proof.rs:299-334): p(zeta) in F2 for every polynomial of the
  * batch; out = ncols x 2 words, host. */
 int zkm_eval_openings(zkm_ctx* ctx, const zkm_batch* b, const uint64_t zeta[2], uint64_t* out, char** err);

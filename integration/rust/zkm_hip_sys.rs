@@ -80,6 +80,27 @@ pub struct zkm_segment_ops {
     pub nsha_compress_sponge: usize,
 }
 pub type ZkmSegmentOps = zkm_segment_ops;
+// (The two structs of zkm_check_ctls carry Rust-style names, with the C names as aliases: the snake-case #[repr(C)] structs of this
+// file are the fixed set tests/test_abi.py compares with tools/abi_layout.c's plain output; these two are compared with
+// `abi_layout check_ctls` by tests/test_check_ctls_abi.py.)
+/// one occurrence of a tuple zkm_check_ctls reports: side of the lookup (the looked side last), index of the table, row
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct ZkmCtlLocation { pub side: u32, pub table: u32, pub row: u64 }
+pub type zkm_ctl_location = ZkmCtlLocation;
+/// what zkm_check_ctls / zkm_segment_check_ctls found (include/zkm_hip.h): kind 0 consistent, 1 non-binary filter, 2 multisets differ,
+/// 3 the check could not be made
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct ZkmCtlReport {
+    pub kind: u32, pub ctl: u32, pub attempts: u32, pub host_waits: u32,
+    pub side: u32, pub table: u32,
+    pub row: u64, pub filter_value: u64,
+    pub width: u32, pub nwords: u32,
+    pub tuple: [u64; 64],
+    pub looking_count: u64, pub looked_count: u64,
+    pub nlooking_locations: u32, pub nlooked_locations: u32,
+    pub looking: [ZkmCtlLocation; 8], pub looked: [ZkmCtlLocation; 8],
+}
+pub type zkm_ctl_report = ZkmCtlReport;
 
 // ZKM_TABLE_* ids (NOT the reference's Table enum order: see zkm_table_enum_index)
 pub const ZKM_TABLE_POSEIDON: c_int = 0; pub const ZKM_TABLE_LOGIC: c_int = 1; pub const ZKM_TABLE_KECCAK_SPONGE: c_int = 2;
@@ -270,6 +291,11 @@ extern "C" {
                         alphas: *const u64, nalphas: usize, out_coeffs: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_eval_openings(ctx: *mut zkm_ctx, b: *const zkm_batch, zeta: *const u64, out: *mut u64, err: *mut *mut c_char) -> c_int;
     // check_constraints (prover.rs:793-910): debugging aid, rc != 0 + "Constraint failed in <Stark>" and the first failing row
+    // check_ctls (cross_table_lookup.rs:1486-1581) on the device: every lookup's looking multiset against its looked multiset
+    pub fn zkm_check_ctls(ctx: *mut zkm_ctx, tables: *const zkm_table_input, ntables: usize, ctls: *const zkm_cross_table_lookup,
+                          sides: *const zkm_ctl_side, nctls: usize, report: *mut zkm_ctl_report, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_segment_check_ctls(ctx: *mut zkm_ctx, traces: *const *const u64, log_n: *const c_uint, report: *mut zkm_ctl_report,
+                                  err: *mut *mut c_char) -> c_int;
     pub fn zkm_check_constraints(ctx: *mut zkm_ctx, table_id: c_int, cfg: *const zkm_stark_config, trace: *const u64, ncols: usize, log_n: c_uint,
                                  aux: *const u64, naux: usize, table: *const zkm_ctl_table, zs: *const zkm_ctl_z, colset_ids: *const u32,
                                  nzs: usize, lookup_challenges: *const u64, alphas: *const u64, nalphas: usize, first_failing_row: *mut u64,

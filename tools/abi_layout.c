@@ -28,6 +28,8 @@ static void check_segments_ops_prototypes(void) {
     int (*get)(zkm_staged_ops*, zkm_segment_ops*) = 0;
     int (*ready)(zkm_staged_ops*, int) = 0;
     void (*release)(zkm_staged_ops*) = 0;
+    int (*check)(zkm_ctx*, const zkm_table_input*, size_t, const zkm_cross_table_lookup*, const zkm_ctl_side*, size_t, zkm_ctl_report*, char**) = 0;
+    int (*check_segment)(zkm_ctx*, const uint64_t* const*, const unsigned*, zkm_ctl_report*, char**) = 0;
     (void)sizeof(tables = zkm_segments_tables);
     (void)sizeof(prove = zkm_prove_segments_ops);
     (void)sizeof(pool = zkm_pool_prove_segments_ops);
@@ -35,11 +37,35 @@ static void check_segments_ops_prototypes(void) {
     (void)sizeof(get = zkm_staged_ops_get);
     (void)sizeof(ready = zkm_staged_ops_ready);
     (void)sizeof(release = zkm_staged_ops_free);
+    (void)sizeof(check = zkm_check_ctls);
+    (void)sizeof(check_segment = zkm_segment_check_ctls);
 }
 
-int main(void) {
+/* `abi_layout check_ctls`: the structs of zkm_check_ctls (tests/test_check_ctls_abi.py compares them with their mirrors).  They are
+ * printed on request only: the plain output is the fixed set of structs that tests/test_segments_ops_abi.py holds to their sizes. */
+static void print_check_ctls(void) {
+    int first_struct = 1, first_field = 1;
+    printf("{");
+    BEGIN(zkm_ctl_location);
+    FIELD(zkm_ctl_location, side); FIELD(zkm_ctl_location, table); FIELD(zkm_ctl_location, row);
+    END();
+    BEGIN(zkm_ctl_report);
+    FIELD(zkm_ctl_report, kind); FIELD(zkm_ctl_report, ctl); FIELD(zkm_ctl_report, attempts); FIELD(zkm_ctl_report, host_waits);
+    FIELD(zkm_ctl_report, side); FIELD(zkm_ctl_report, table); FIELD(zkm_ctl_report, row); FIELD(zkm_ctl_report, filter_value);
+    FIELD(zkm_ctl_report, width); FIELD(zkm_ctl_report, nwords); FIELD(zkm_ctl_report, tuple); FIELD(zkm_ctl_report, looking_count);
+    FIELD(zkm_ctl_report, looked_count); FIELD(zkm_ctl_report, nlooking_locations); FIELD(zkm_ctl_report, nlooked_locations);
+    FIELD(zkm_ctl_report, looking); FIELD(zkm_ctl_report, looked);
+    END();
+    printf("\n}\n");
+}
+
+int main(int argc, char** argv) {
     int first_struct = 1, first_field = 1;
     check_segments_ops_prototypes();
+    if (argc > 1 && argv[1][0] == 'c') {
+        print_check_ctls();
+        return 0;
+    }
     printf("{");
     BEGIN(zkm_challenger);
     FIELD(zkm_challenger, state); FIELD(zkm_challenger, in_buf); FIELD(zkm_challenger, out_buf); FIELD(zkm_challenger, n_in);

@@ -49,6 +49,7 @@ EXPORTS = [
     "zkm_segment_tables", "zkm_prove_segment_ops",
     "zkm_segments_tables", "zkm_prove_segments_ops", "zkm_pool_prove_segments_ops",
     "zkm_segment_ops_stage", "zkm_staged_ops_get", "zkm_staged_ops_ready", "zkm_staged_ops_free",
+    "zkm_check_ctls", "zkm_segment_check_ctls",
 ]
 
 
@@ -126,6 +127,32 @@ class SegmentOpsStruct(C.Structure):
     _fields_ = [f for _, ptrs, count in SEGMENT_OPS_GROUPS for f in [(name, C.c_void_p) for name, _ in ptrs] + [(count, C.c_size_t)]]
 
 
+class CtlLocation(C.Structure):
+    """zkm_ctl_location: one occurrence of a reported tuple (side of the lookup, index of the table, row)."""
+    _fields_ = [("side", C.c_uint32), ("table", C.c_uint32), ("row", C.c_uint64)]
+
+
+class CtlReport(C.Structure):
+    """zkm_ctl_report (include/zkm_hip.h): what zkm_check_ctls found.  kind 0 consistent, 1 non-binary filter, 2 multisets differ,
+    3 the check could not be made; .message holds the text of the error channel (None when consistent)."""
+    _fields_ = [("kind", C.c_uint32), ("ctl", C.c_uint32), ("attempts", C.c_uint32), ("host_waits", C.c_uint32),
+                ("side", C.c_uint32), ("table", C.c_uint32), ("row", C.c_uint64), ("filter_value", C.c_uint64),
+                ("width", C.c_uint32), ("nwords", C.c_uint32), ("tuple", C.c_uint64 * 64),
+                ("looking_count", C.c_uint64), ("looked_count", C.c_uint64),
+                ("nlooking_locations", C.c_uint32), ("nlooked_locations", C.c_uint32),
+                ("looking", CtlLocation * 8), ("looked", CtlLocation * 8)]
+    message = None
+
+    def tuple_words(self):
+        return [int(self.tuple[k]) for k in range(self.nwords)]
+
+    def looking_locations(self):
+        return [(l.side, l.table, l.row) for l in self.looking[:self.nlooking_locations]]
+
+    def looked_locations(self):
+        return [(l.side, l.table, l.row) for l in self.looked[:self.nlooked_locations]]
+
+
 def abi_mirrors():
     """Every struct of include/zkm_hip.h -> its Python mirror (a ctypes Structure or a numpy dtype); tests/test_abi.py compares
     size and field offsets of each with what the C compiler says (tools/abi_layout.c)."""
@@ -135,6 +162,11 @@ def abi_mirrors():
             "zkm_ctl_table": ctl.CtlTableStruct, "zkm_ctl_z": ctl.CTLZ_DT, "zkm_ctl_side": ctl.SIDE_DT,
             "zkm_cross_table_lookup": ctl.CTL_DT, "zkm_table_input": ctl.TableInputStruct, "zkm_fri_poly": FriPoly,
             "zkm_fri_batch": FriBatch, "zkm_segment_ops": SegmentOpsStruct}
+
+
+def abi_mirrors_check_ctls():
+    """The structs of zkm_check_ctls -> their mirrors; tests/test_check_ctls_abi.py compares them with `tools/abi_layout check_ctls`."""
+    return {"zkm_ctl_location": CtlLocation, "zkm_ctl_report": CtlReport}
 
 
 _lib = None
@@ -272,6 +304,8 @@ def load():
         "zkm_eval_openings": (C.c_int, [cp, cp, u64p, u64p, err]),
         "zkm_check_constraints": (C.c_int, [cp, C.c_int, C.POINTER(StarkConfig), cp, C.c_size_t, C.c_uint, cp, C.c_size_t, cp, cp, cp, C.c_size_t,
                                             u64p, u64p, C.c_size_t, u64p, err]),
+        "zkm_check_ctls": (C.c_int, [cp, cp, C.c_size_t, cp, cp, C.c_size_t, C.POINTER(CtlReport), err]),
+        "zkm_segment_check_ctls": (C.c_int, [cp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint), C.POINTER(CtlReport), err]),
         "zkm_profile_enable": (None, [cp, C.c_int]),
         "zkm_profile_reset": (None, [cp]),
         "zkm_profile_count": (C.c_size_t, [cp]),
@@ -1174,6 +1208,40 @@ class Context:
         if "Constraint failed" not in msg:
             _check(rc, err)
         return int(first.value)
+
+    @staticmethod
+    def _ctl_report(rc, rep, err):
+        """The report of a check_ctls call; a call that could not be made (kind 3) raises."""
+        rep.message = err.value.decode() if err.value else None
+        if rc != 0 and rep.kind in (0, 3):
+            raise ZkmError(rep.message or "check_ctls: error %d" % rc)
+        return rep
+
+    def check_ctls(self, tables, ctls):
+        """zkm_check_ctls: testutils::check_ctls (cross_table_lookup.rs:1486-1581) on the device.  tables / ctls as prove_with_traces
+        takes them (arrays, DeviceBuffers, device pointers, or a list of per-column arrays).  Returns the CtlReport: .kind 0 when every
+        lookup holds, else the finding with .message in the reference's wording."""
+        from . import ctl as zc
+        packed = [(tid, [_data_ptr(col).value for col in tr] if isinstance(tr, (list, tuple)) else _data_ptr(tr).value, ncols, log_n, ct)
+                  for (tid, tr, ncols, log_n, ct) in tables]
+        tarr, keep = zc.pack_tables(packed)
+        carr, sides = zc.pack_ctls(ctls)
+        rep, err = CtlReport(), C.c_char_p()
+        rc = self.L.zkm_check_ctls(self.h, tarr, len(tables), carr.ctypes.data, sides.ctypes.data, len(carr), C.byref(rep), C.byref(err))
+        return self._ctl_report(rc, rep, err)
+
+    def segment_check_ctls(self, traces, log_ns):
+        """zkm_segment_check_ctls: check_ctls for the AllStark inside the library.  traces: twelve arrays / DeviceBuffers / device
+        pointers in Table::all() order, or a staged segment (segment_tables' StagedTrace); log_ns their heights."""
+        if isinstance(traces, StagedTrace):
+            traces = traces.tables()
+        assert len(traces) == 12 and len(log_ns) == 12
+        keep = [t if isinstance(t, (DeviceBuffer, StagedTrace, int)) else np.ascontiguousarray(t, dtype=np.uint64) for t in traces]
+        ptrs = (C.c_void_p * 12)(*[_data_ptr(t).value for t in keep])
+        lg = (C.c_uint * 12)(*[int(x) for x in log_ns])
+        rep, err = CtlReport(), C.c_char_p()
+        rc = self.L.zkm_segment_check_ctls(self.h, ptrs, lg, C.byref(rep), C.byref(err))
+        return self._ctl_report(rc, rep, err)
 
     def prove_with_traces(self, tables, ctls, public_values=(), cfg=None):
         """prove_with_traces (prover.rs:130-232).  tables: list of (table_id, trace (ndarray | DeviceBuffer), ncols, log_n, CtlTable);

@@ -553,6 +553,13 @@ int zkm_ctx_set_tuning(zkm_ctx* c, const char* key, uint64_t value, char** err) 
                 x->quad_max_hashes = value ? 4096 : 32768;
                 x->pow_round_log = value ? 16 : 17;                 // (half-filled SIMDs are somebody else's slots here: 76.3 vs 75.4 segments/s)
             }
+            else if (k == "check_ctls") x->check_ctls = value ? 1 : 0;
+            else if (k == "debug_ctl_key_bits") {
+                // test hook, as debug_fail_allocs below
+                const char* hooks = getenv("ZKM_ENABLE_TEST_HOOKS");
+                if (!hooks || strcmp(hooks, "1") != 0) throw std::runtime_error("zkm_ctx_set_tuning: unknown key '" + k + "'");
+                x->debug_ctl_key_bits = value > 128 ? 128 : (unsigned)value;
+            }
             else if (k == "debug_fail_allocs") {
                 // test hook, not a tuning: only a process that asks for the hooks (ZKM_ENABLE_TEST_HOOKS=1 in its environment) may set it
                 const char* hooks = getenv("ZKM_ENABLE_TEST_HOOKS");

@@ -1111,6 +1111,14 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
     lockstep_call call{c, cfg, nseg, io, ntables, ctls, sides, nctls, seg_base};
     ZKM_HIP_CHECK(hipSetDevice(c->device));
     if (nseg == 0) return;
+    if (c->check_ctls)   // the reference's `test` feature (prover.rs:171-176): nothing is proven from inconsistent tables
+        for (size_t s = 0; s < nseg; s++) {
+            zkm_ctl_report rep{};
+            std::string msg;
+            if (!io[s].tables) throw std::runtime_error("zkm_prove_with_traces: null argument");
+            if (zkm_check_ctls_run(c, io[s].tables, ntables, ctls, sides, nctls, &rep, &msg))
+                throw std::runtime_error("check_ctls: segment " + std::to_string(seg_base + s) + ": " + msg);
+        }
     call.note_stack_height();
     call.plan();
     call.commit_traces();

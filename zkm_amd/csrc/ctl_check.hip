@@ -1,0 +1,565 @@
+// ctl_check.hip -- testutils::check_ctls (cross_table_lookup.rs:1486-1581; prove_with_traces runs it under the `test` feature,
+// prover.rs:171-176) on device-resident tables: for every CrossTableLookup, the multiset of the filtered rows of the looking tables
+// against that of the looked table, with the row and its locations named when they differ.
+//
+// One job per lookup; the jobs of a call share every launch (zkm_seg_args: the job from blockIdx.z).  A job's candidate rows are its
+// sides' rows, side after side (the looking sides in the lookup's order, the looked side last), cut into tiles of CC_TILE rows:
+//   (1) k_cc_count    one lane per (side, row): the filter; the smallest (side, row) with a value other than 0 or 1; per-tile counts of
+//                     the rows with filter 1 (the job's RECORDS);
+//   (2) scan          exclusive scan of the tile counts (scan_dev.h): each tile's first record; the total comes to the host, which sizes
+//                     everything below by the records, not by sides x rows;
+//   (3) k_cc_emit     the records' locations (side, row) in candidate order;
+//   (4) k_cc_keys     per record a 128-bit key: two linear forms of the canonical tuple over Goldilocks, multipliers from the attempt's seed;
+//   (5) radix passes  the stable LSD sort of (key, record) (radix_dev.h, the Memory witness's kernels);
+//   (6) k_cc_flags    per sorted position: run-head flag, the record's sign (looking in the low half of a word, looked in the high half),
+//                     and the CONFIRMATION -- a record whose key equals its predecessor's re-evaluates both tuples and compares them word
+//                     for word; a difference is a key collision and the attempt is void;
+//   (7) scan          of the flags (run numbers) and of the signs (occurrences on either side before each position);
+//   (8) k_cc_mark     each run's head position and the sign prefix at its end;  k_cc_verdict  a run is balanced iff the prefix grew by
+//                     the same amount in both halves; the unbalanced run whose head is the earliest record (atomicMin) is the one
+//                     reported: the sort is stable, so a run's head is its tuple's first occurrence in candidate order;
+//   (9) k_cc_report   the reported tuple, its two counts and its first locations (or the filter's value).
+// Host waits: the record counts, the verdict of each attempt (one unless keys collided), the report of a failing call.
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "ctl_dev.h"
+#include "radix_dev.h"
+#include "scan_dev.h"
+#include "zkm_internal.h"
+
+namespace {
+
+constexpr int CC_THREADS = SCAN_THREADS;
+constexpr int CC_ITEMS = 4;                       // rows per lane and tile
+constexpr int CC_TILE = CC_THREADS * CC_ITEMS;    // 1024 candidate rows per tile
+constexpr unsigned CC_KEY_BITS = 128;
+constexpr int CC_MAX_ATTEMPTS = 4;
+constexpr uint64_t CC_NONE = ~0ull;
+constexpr size_t CC_MAX_RECORDS = (size_t)1 << 30;   // per lookup: record and run numbers share a word, the two signs another
+constexpr int CC_REPORT_WORDS = 3 + ZKM_CTL_REPORT_WORDS + 2 * ZKM_CTL_REPORT_LOCATIONS;
+
+struct cc_tab {
+    ctl_dev d;
+    const gl_t* trace;
+    uint64_t n;
+};
+struct cc_side {
+    uint32_t table, colset;
+    uint32_t tile0, _pad;        // the side's first tile among the job's
+};
+// res: [0] smallest (side << 32 | row) with a non-binary filter, [1] records; ver (reset per attempt): [0] collision seen,
+// [1] (record << 32 | run) of the reported run, [2] runs
+struct cc_job {
+    const cc_tab* tabs;
+    const cc_side* sides;        // this lookup's sides: the looking ones, then the looked one
+    uint32_t nsides, width, ntiles, nrec;
+    uint64_t* cnt;               // ntiles + 1 words: records per tile, then their exclusive scan
+    unsigned long long *res, *ver;
+    uint64_t* loc;               // nrec: side << 32 | row of each record
+    uint64_t* keys;              // 2 x nrec, sorted order after the passes
+    uint32_t* idx;               // nrec: the record at each sorted position
+    uint64_t *sgn, *flg;         // nrec + 1 each
+    uint32_t* head;              // per run: its first sorted position
+    uint64_t* end;               // per run: sgn behind its last position
+};
+
+__device__ __forceinline__ uint32_t cc_side_of(const cc_side* __restrict__ sides, uint32_t nsides, uint32_t tile) {
+    uint32_t lo = 0, hi = nsides - 1;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (sides[mid].tile0 <= tile) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+// eval_table (cross_table_lookup.rs:266-285): on the last row the next-row part is zero
+__device__ __forceinline__ gl_t cc_filter(const cc_tab& T, const zkm_colset& cs, size_t row) {
+    return gl_canon(ctl_eval_filter(T.d, cs, T.trace + row, T.n, 1, row + 1 < T.n));
+}
+__device__ __forceinline__ gl_t cc_word(const cc_tab& T, const zkm_colset& cs, size_t row, uint32_t k) {
+    return gl_canon(ctl_eval_column(T.d, cs.col_off + k, T.trace + row, T.n, 1, row + 1 < T.n));
+}
+GL_HD uint64_t cc_mix(uint64_t x) {   // SplitMix64's finaliser
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// ---- (1) count
+__global__ __launch_bounds__(CC_THREADS) void k_cc_count(zkm_seg_args<cc_job> S) {
+    __shared__ uint32_t sh[SCAN_WAVES];
+    const cc_job& J = S.v[blockIdx.z];
+    if (blockIdx.x >= J.ntiles) return;
+    const uint32_t s = cc_side_of(J.sides, J.nsides, blockIdx.x);
+    const cc_side sd = J.sides[s];
+    const cc_tab& T = J.tabs[sd.table];
+    const zkm_colset cs = T.d.colsets[sd.colset];
+    const size_t n = T.n, base = (size_t)(blockIdx.x - sd.tile0) * CC_TILE;
+    uint32_t c = 0;
+    unsigned long long bad = CC_NONE;
+#pragma unroll
+    for (int it = 0; it < CC_ITEMS; it++) {
+        const size_t row = base + (size_t)it * CC_THREADS + threadIdx.x;
+        if (row >= n) continue;
+        const gl_t f = cc_filter(T, cs, row);
+        if (f == 1) c++;
+        else if (f != 0 && bad == CC_NONE) bad = ((unsigned long long)s << 32) | row;
+    }
+    uint32_t all;
+    block_incl_scan(c, sh, add_u32(), &all);
+    if (threadIdx.x == 0) J.cnt[blockIdx.x] = all;
+    if (bad != CC_NONE) atomicMin(&J.res[0], bad);
+}
+
+// ---- (3) emit: cnt[tile] = the tile's first record
+__global__ __launch_bounds__(CC_THREADS) void k_cc_emit(zkm_seg_args<cc_job> S) {
+    __shared__ uint32_t sh[SCAN_WAVES];
+    const cc_job& J = S.v[blockIdx.z];
+    if (blockIdx.x >= J.ntiles) return;
+    const uint32_t s = cc_side_of(J.sides, J.nsides, blockIdx.x);
+    const cc_side sd = J.sides[s];
+    const cc_tab& T = J.tabs[sd.table];
+    const zkm_colset cs = T.d.colsets[sd.colset];
+    const size_t n = T.n, base = (size_t)(blockIdx.x - sd.tile0) * CC_TILE;
+    uint64_t run = J.cnt[blockIdx.x];
+    for (int it = 0; it < CC_ITEMS; it++) {
+        const size_t row = base + (size_t)it * CC_THREADS + threadIdx.x;
+        const bool on = row < n && cc_filter(T, cs, row) == 1;
+        uint32_t all;
+        const uint32_t incl = block_incl_scan(on ? 1u : 0u, sh, add_u32(), &all);
+        if (on && run + incl - 1 < J.nrec) J.loc[run + incl - 1] = ((uint64_t)s << 32) | row;
+        run += all;
+    }
+}
+
+// ---- (4) keys.  bits < 128 (the test hook): the key truncated to its low `bits` bits
+__global__ __launch_bounds__(CC_THREADS) void k_cc_keys(zkm_seg_args<cc_job> S, uint64_t seed, unsigned bits) {
+    const cc_job& J = S.v[blockIdx.z];
+    const size_t i = (size_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= J.nrec) return;
+    const uint64_t loc = J.loc[i];
+    const cc_side sd = J.sides[loc >> 32];
+    const cc_tab& T = J.tabs[sd.table];
+    const zkm_colset cs = T.d.colsets[sd.colset];
+    const size_t row = (uint32_t)loc;
+    gl_t k0 = 0, k1 = 0;
+    for (uint32_t k = 0; k < J.width; k++) {
+        const gl_t v = cc_word(T, cs, row, k);
+        k0 = gl_add(k0, gl_mul(v, gl_canon(cc_mix(seed + 2 * k))));
+        k1 = gl_add(k1, gl_mul(v, gl_canon(cc_mix(~seed + 2 * k + 1))));
+    }
+    k0 = gl_canon(k0);
+    k1 = gl_canon(k1);
+    if (bits < 64) k0 &= (1ull << bits) - 1;
+    if (bits <= 64) k1 = 0;
+    else if (bits < 128) k1 &= (1ull << (bits - 64)) - 1;
+    J.keys[i] = k0;
+    J.keys[(size_t)J.nrec + i] = k1;
+    J.idx[i] = (uint32_t)i;
+}
+
+__device__ __forceinline__ bool cc_same_key(const cc_job& J, size_t a, size_t b) {
+    return J.keys[a] == J.keys[b] && J.keys[(size_t)J.nrec + a] == J.keys[(size_t)J.nrec + b];
+}
+__device__ __forceinline__ bool cc_same_tuple(const cc_job& J, uint64_t la, uint64_t lb) {
+    const cc_side sa = J.sides[la >> 32], sb = J.sides[lb >> 32];
+    const cc_tab &Ta = J.tabs[sa.table], &Tb = J.tabs[sb.table];
+    const zkm_colset ca = Ta.d.colsets[sa.colset], cb = Tb.d.colsets[sb.colset];
+    for (uint32_t k = 0; k < J.width; k++)
+        if (cc_word(Ta, ca, (uint32_t)la, k) != cc_word(Tb, cb, (uint32_t)lb, k)) return false;
+    return true;
+}
+
+// ---- (6) flags, signs and the confirmation; position nrec holds the zero behind the scans' inputs
+__global__ __launch_bounds__(CC_THREADS) void k_cc_flags(zkm_seg_args<cc_job> S) {
+    const cc_job& J = S.v[blockIdx.z];
+    const size_t i = (size_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i > J.nrec) return;
+    if (i == J.nrec) {
+        J.sgn[i] = 0;
+        J.flg[i] = 0;
+        return;
+    }
+    const uint64_t loc = J.loc[J.idx[i]];
+    const bool head = i == 0 || !cc_same_key(J, i, i - 1);
+    J.sgn[i] = (loc >> 32) == J.nsides - 1 ? 1ull << 32 : 1ull;
+    J.flg[i] = head;
+    if (!head && !cc_same_tuple(J, loc, J.loc[J.idx[i - 1]])) J.ver[0] = 1;
+}
+
+// ---- (8) flg[i] = run heads before position i, sgn[i] = signs before it
+__global__ __launch_bounds__(CC_THREADS) void k_cc_mark(zkm_seg_args<cc_job> S) {
+    const cc_job& J = S.v[blockIdx.z];
+    const size_t i = (size_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (i >= J.nrec) return;
+    const bool head = i == 0 || !cc_same_key(J, i, i - 1);
+    const bool last = i + 1 == J.nrec || !cc_same_key(J, i, i + 1);
+    const uint64_t r = head ? J.flg[i] : J.flg[i] - 1;
+    if (head) J.head[r] = (uint32_t)i;
+    if (last) J.end[r] = J.sgn[i + 1];
+}
+__device__ __forceinline__ uint64_t cc_run_signs(const cc_job& J, size_t r) { return J.end[r] - (r ? J.end[r - 1] : 0); }
+__global__ __launch_bounds__(CC_THREADS) void k_cc_verdict(zkm_seg_args<cc_job> S) {
+    const cc_job& J = S.v[blockIdx.z];
+    const size_t r = (size_t)blockIdx.x * CC_THREADS + threadIdx.x;
+    if (r >= J.nrec || r >= J.ver[2]) return;
+    const uint64_t d = cc_run_signs(J, r);
+    if ((uint32_t)d != (uint32_t)(d >> 32)) atomicMin(&J.ver[1], ((unsigned long long)J.idx[J.head[r]] << 32) | r);
+}
+
+// ---- (9) report of ONE job.  what = side << 32 | row of a non-binary filter (out[0] = its value), or CC_NONE: run `run` -- out[1], out[2]
+// its occurrences on the looking / looked side, out[3 ..] the tuple, then the first locations of either side
+__global__ __launch_bounds__(CC_THREADS) void k_cc_report(cc_job J, unsigned long long what, uint32_t run, uint64_t* __restrict__ out) {
+    const uint32_t t = threadIdx.x;
+    if (what != CC_NONE) {
+        if (t) return;
+        const cc_side sd = J.sides[what >> 32];
+        const cc_tab& T = J.tabs[sd.table];
+        out[0] = cc_filter(T, T.d.colsets[sd.colset], (uint32_t)what);
+        return;
+    }
+    const uint64_t d = cc_run_signs(J, run);
+    const uint32_t looking = (uint32_t)d, looked = (uint32_t)(d >> 32), h = J.head[run];
+    if (t == 0) {
+        out[1] = looking;
+        out[2] = looked;
+    }
+    const uint64_t loc = J.loc[J.idx[h]];
+    const cc_side sd = J.sides[loc >> 32];
+    const cc_tab& T = J.tabs[sd.table];
+    if (t < J.width && t < ZKM_CTL_REPORT_WORDS) out[3 + t] = cc_word(T, T.d.colsets[sd.colset], (uint32_t)loc, t);
+    // (the run is in candidate order: its looking records first)
+    if (t < ZKM_CTL_REPORT_LOCATIONS) {
+        if (t < looking) out[3 + ZKM_CTL_REPORT_WORDS + t] = J.loc[J.idx[h + t]];
+        if (t < looked) out[3 + ZKM_CTL_REPORT_WORDS + ZKM_CTL_REPORT_LOCATIONS + t] = J.loc[J.idx[h + looking + t]];
+    }
+}
+
+size_t blocks_for(size_t items, size_t per) { return (items + per - 1) / per; }
+
+// every launch of a call serves all its jobs; more than ZKM_MAX_SEG jobs go in consecutive groups
+template <class E, class... X>
+void launch_jobs(zkm_ctx* c, const char* name, void (*kernel)(zkm_seg_args<cc_job>, X...), const std::vector<cc_job>& jobs, E extent, X... x) {
+    for (size_t g0 = 0; g0 < jobs.size(); g0 += ZKM_MAX_SEG) {
+        const size_t k = std::min<size_t>(ZKM_MAX_SEG, jobs.size() - g0);
+        size_t grid = 0;
+        for (size_t j = 0; j < k; j++) grid = std::max(grid, (size_t)extent(jobs[g0 + j]));
+        zkm_prof_scope ps(c, name);
+        zkm_launch_segs(c->stream, kernel, jobs.data() + g0, k, grid, CC_THREADS, x...);
+    }
+}
+void scan_jobs(zkm_ctx* c, const std::vector<scan_seg>& scans) {
+    for (size_t g0 = 0; g0 < scans.size(); g0 += ZKM_MAX_SEG) {
+        zkm_prof_scope ps(c, "check_ctls/scan");
+        scan_launch(c->stream, scans.data() + g0, std::min<size_t>(ZKM_MAX_SEG, scans.size() - g0));
+    }
+}
+
+const char* table_name(int table_id) {
+    static const char* const names[12] = {"Arithmetic", "Cpu", "Poseidon", "PoseidonSponge", "Keccak", "KeccakSponge", "ShaExtend", "ShaExtendSponge",
+                                          "ShaCompress", "ShaCompressSponge", "Logic", "Memory"};   // Table's Debug names, all_stark.rs:96-110
+    const int e = zkm_table_enum_index(table_id);
+    return e < 0 ? nullptr : names[e];
+}
+std::string table_label(const zkm_table_input* tables, uint32_t t) {
+    const char* nm = table_name(tables[t].table_id);
+    return nm ? std::string(nm) : "Table" + std::to_string(t);
+}
+std::string locations_text(const zkm_table_input* tables, const zkm_ctl_location* l, uint32_t shown, uint64_t count) {
+    std::string s = "[";
+    for (uint32_t i = 0; i < shown; i++) s += (i ? ", (" : "(") + table_label(tables, l[i].table) + ", " + std::to_string(l[i].row) + ")";
+    if (count > shown) s += ", ...";
+    return s + "]";
+}
+
+}  // namespace
+
+// zkm_internal.h: the check on one segment's tables.  Returns the report's kind (0, 1 or 2) with the reference's message in *msg; throws
+// when the check cannot be made (the entry points turn that into kind 3).
+int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
+                       size_t nctls, zkm_ctl_report* rep, std::string* msg) {
+    if ((!tables && ntables) || (nctls && (!ctls || !sides))) throw std::runtime_error("check_ctls: null argument");
+    if (nctls >= ((size_t)1 << 31)) throw std::runtime_error("check_ctls: too many lookups");
+    rep->attempts = 0;
+    rep->host_waits = 0;
+    // ---- the description: every side names a table and one of its column sets; the sides of a lookup agree in width
+    std::vector<char> used(ntables, 0);
+    std::vector<cc_side> h_sides;
+    std::vector<size_t> side_off(nctls + 1, 0);
+    std::vector<uint32_t> width(nctls), ntiles(nctls);
+    for (size_t j = 0; j < nctls; j++) {
+        const zkm_cross_table_lookup& L = ctls[j];
+        if (L.nlooking + 1 == 0) throw std::runtime_error("check_ctls: malformed cross-table lookups");
+        uint64_t tile = 0;
+        for (uint32_t i = 0; i <= L.nlooking; i++) {
+            const zkm_ctl_side sd = i < L.nlooking ? sides[L.looking_off + i] : L.looked;
+            if (sd.table >= ntables) throw std::runtime_error("CTL #" + std::to_string(j) + ": table index out of range");
+            const zkm_table_input& t = tables[sd.table];
+            if (!t.ctl || sd.colset >= t.ctl->ncolsets) throw std::runtime_error("CTL #" + std::to_string(j) + ": column-set index out of range");
+            if (t.ncols == 0 || t.log_n > 30 || (!t.trace && !t.columns)) throw std::runtime_error("check_ctls: bad table shape");
+            const uint32_t w = t.ctl->colsets[sd.colset].ncols;
+            if (i == 0) width[j] = w;
+            if (w != width[j])   // (the oracle's 100 + c)
+                throw std::runtime_error("CTL #" + std::to_string(j) + ": the column sets of the looking and looked tables differ in width");
+            used[sd.table] = 1;
+            h_sides.push_back(cc_side{sd.table, sd.colset, (uint32_t)tile, 0});
+            tile += blocks_for((size_t)1 << t.log_n, CC_TILE);
+            if (tile >= ((uint64_t)1 << 31)) throw std::runtime_error("CTL #" + std::to_string(j) + ": too many candidate rows");
+        }
+        ntiles[j] = (uint32_t)tile;
+        side_off[j + 1] = h_sides.size();
+    }
+    // (the description is judged before the context is needed: a caller without a device still learns what is wrong with it)
+    if (!c) throw std::runtime_error("check_ctls: null argument");
+    ZKM_HIP_CHECK(hipSetDevice(c->device));
+    // ---- the tables on the device: in place, or a copy of host memory / of one pointer per column
+    std::vector<ctl_dev_owner> desc(ntables);
+    std::vector<zkm_scratch> copies;
+    std::vector<cc_tab> h_tabs(ntables, cc_tab{});
+    for (size_t t = 0; t < ntables; t++) {
+        if (!used[t]) continue;
+        const zkm_table_input& in = tables[t];
+        const size_t n = (size_t)1 << in.log_n;
+        desc[t].upload(c, in.ctl, nullptr, nullptr, 0, false, in.ncols);
+        const gl_t* d_trace = in.trace;
+        if (in.columns) {
+            copies.emplace_back(c, in.ncols * n * 8);
+            for (size_t k = 0; k < in.ncols; k++) {
+                if (!in.columns[k]) throw std::runtime_error("check_ctls: null column");
+                ZKM_HIP_CHECK(hipMemcpyAsync(copies.back().as<gl_t>() + k * n, in.columns[k], n * 8, hipMemcpyDefault, c->stream));
+            }
+            d_trace = copies.back().as<gl_t>();
+        } else if (!zkm_is_device_ptr(in.trace)) {
+            copies.emplace_back(c, in.ncols * n * 8);
+            ZKM_HIP_CHECK(hipMemcpyAsync(copies.back().p, in.trace, in.ncols * n * 8, hipMemcpyHostToDevice, c->stream));
+            d_trace = copies.back().as<gl_t>();
+        }
+        h_tabs[t] = cc_tab{desc[t].d, d_trace, n};
+    }
+    if (nctls == 0) return 0;
+    // ---- one block for the descriptors and the jobs' result words: [tabs | sides | res (2 per job) | ver (4 per job) | report]
+    auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
+    const size_t o_sides = al(ntables * sizeof(cc_tab)), o_res = al(o_sides + h_sides.size() * sizeof(cc_side)), o_ver = al(o_res + nctls * 16),
+                 o_rep = al(o_ver + nctls * 32), total = o_rep + CC_REPORT_WORDS * 8;
+    zkm_scratch block(c, total);
+    char* const base = block.as<char>();
+    const cc_tab* d_tabs = (const cc_tab*)base;
+    const cc_side* d_sides = (const cc_side*)(base + o_sides);
+    unsigned long long* d_res = (unsigned long long*)(base + o_res);
+    unsigned long long* d_ver = (unsigned long long*)(base + o_ver);
+    uint64_t* d_rep = (uint64_t*)(base + o_rep);
+    {
+        std::vector<char> h(o_ver, 0);
+        memcpy(h.data(), h_tabs.data(), ntables * sizeof(cc_tab));
+        memcpy(h.data() + o_sides, h_sides.data(), h_sides.size() * sizeof(cc_side));
+        for (size_t j = 0; j < nctls; j++) ((uint64_t*)(h.data() + o_res))[2 * j] = CC_NONE;
+        c->upload(base, h.data(), o_ver);   // (through the context's pinned ring: `h` may go)
+    }
+    std::vector<cc_job> jobs(nctls, cc_job{});
+    std::vector<zkm_scratch> cnt, part;
+    std::vector<scan_seg> scans;
+    for (size_t j = 0; j < nctls; j++) {
+        cnt.emplace_back(c, ((size_t)ntiles[j] + 1) * 8);
+        part.emplace_back(c, blocks_for((size_t)ntiles[j] + 1, SCAN_TILE) * 8);
+        ZKM_HIP_CHECK(hipMemsetAsync(cnt.back().as<uint64_t>() + ntiles[j], 0, 8, c->stream));
+        cc_job& J = jobs[j];
+        J.tabs = d_tabs;
+        J.sides = d_sides + side_off[j];
+        J.nsides = (uint32_t)(side_off[j + 1] - side_off[j]);
+        J.width = width[j];
+        J.ntiles = ntiles[j];
+        J.cnt = cnt.back().as<uint64_t>();
+        J.res = d_res + 2 * j;
+        J.ver = d_ver + 4 * j;
+        scans.push_back(scan_seg{J.cnt, (size_t)ntiles[j] + 1, part.back().as<uint64_t>(), (uint64_t*)(J.res + 1)});
+    }
+    auto tiles_of = [](const cc_job& J) { return (size_t)J.ntiles; };
+    launch_jobs(c, "check_ctls/count", k_cc_count, jobs, tiles_of);
+    scan_jobs(c, scans);
+    std::vector<uint64_t> h_res(2 * nctls);
+    c->download(h_res.data(), d_res, nctls * 16);
+    rep->host_waits++;
+    // ---- the records
+    std::vector<zkm_scratch> store;
+    std::vector<radix_seg> rx(nctls);
+    std::vector<uint64_t*> keys_b(nctls);   // the sort's second buffers
+    std::vector<uint32_t*> idx_b(nctls);
+    size_t max_rec = 0;
+    scans.clear();
+    for (size_t j = 0; j < nctls; j++) {
+        const size_t nrec = (size_t)h_res[2 * j + 1];
+        if (nrec > CC_MAX_RECORDS) throw std::runtime_error("CTL #" + std::to_string(j) + ": more than 2^30 filtered rows");
+        max_rec = std::max(max_rec, nrec);
+        cc_job& J = jobs[j];
+        J.nrec = (uint32_t)nrec;
+        auto take = [&](size_t bytes) {
+            store.emplace_back(c, std::max<size_t>(bytes, 64));
+            return store.back().p;
+        };
+        const uint32_t rtiles = (uint32_t)blocks_for(nrec, MT_TILE);
+        J.loc = (uint64_t*)take(nrec * 8);
+        J.keys = (uint64_t*)take(2 * nrec * 8);
+        J.idx = (uint32_t*)take(nrec * 4);
+        J.sgn = (uint64_t*)take((nrec + 1) * 8);
+        J.flg = (uint64_t*)take((nrec + 1) * 8);
+        J.head = (uint32_t*)take(nrec * 4);
+        J.end = (uint64_t*)take(nrec * 8);
+        uint32_t* hist = (uint32_t*)take(((size_t)MT_RADIX * rtiles + MT_RADIX) * 4);
+        keys_b[j] = (uint64_t*)take(2 * nrec * 8);
+        idx_b[j] = (uint32_t*)take(nrec * 4);
+        rx[j] = radix_seg{J.keys, keys_b[j], J.idx, idx_b[j], hist, hist + (size_t)MT_RADIX * rtiles, (uint32_t)nrec, rtiles, 2};
+        scans.push_back(scan_seg{J.sgn, nrec + 1, (uint64_t*)take(blocks_for(nrec + 1, SCAN_TILE) * 8), nullptr});
+        scans.push_back(scan_seg{J.flg, nrec + 1, (uint64_t*)take(blocks_for(nrec + 1, SCAN_TILE) * 8), (uint64_t*)(J.ver + 2)});
+    }
+    launch_jobs(c, "check_ctls/emit", k_cc_emit, jobs, tiles_of);
+    auto recs_of = [](const cc_job& J) { return blocks_for(J.nrec, CC_THREADS); };
+    auto recs1_of = [](const cc_job& J) { return blocks_for((size_t)J.nrec + 1, CC_THREADS); };
+    std::vector<uint64_t> h_ver(4 * nctls), ver_init(4 * nctls, 0);
+    for (size_t j = 0; j < nctls; j++) ver_init[4 * j + 1] = CC_NONE;
+    bool confirmed = false;
+    for (int attempt = 1; attempt <= CC_MAX_ATTEMPTS && !confirmed; attempt++) {
+        rep->attempts = (uint32_t)attempt;
+        const unsigned bits = attempt == 1 && c->debug_ctl_key_bits ? std::min<unsigned>(c->debug_ctl_key_bits, CC_KEY_BITS) : CC_KEY_BITS;
+        c->upload(d_ver, ver_init.data(), nctls * 32);
+        launch_jobs(c, "check_ctls/keys", k_cc_keys, jobs, recs_of, cc_mix(0x5a4b4d43544cull + (uint64_t)attempt), bits);
+        if (max_rec) {
+            for (size_t j = 0; j < nctls; j++) {   // (every attempt starts from the buffers k_cc_keys writes)
+                rx[j].kin = jobs[j].keys;
+                rx[j].kout = keys_b[j];
+                rx[j].iin = jobs[j].idx;
+                rx[j].iout = idx_b[j];
+            }
+            const size_t rtiles = blocks_for(max_rec, MT_TILE);
+            for (unsigned bit = 0; bit < bits; bit += 8) {
+                for (size_t g0 = 0; g0 < nctls; g0 += ZKM_MAX_SEG) {
+                    const size_t k = std::min<size_t>(ZKM_MAX_SEG, nctls - g0);
+                    {
+                        zkm_prof_scope ps(c, "check_ctls/radix_upsweep");
+                        zkm_launch_segs(c->stream, k_radix_upsweep, rx.data() + g0, k, rtiles, MT_THREADS, bit);
+                    }
+                    {
+                        zkm_prof_scope ps(c, "check_ctls/radix_scan");
+                        zkm_launch_segs(c->stream, k_radix_scan, rx.data() + g0, k, MT_RADIX, MT_THREADS);
+                    }
+                    {
+                        zkm_prof_scope ps(c, "check_ctls/radix_downsweep");
+                        zkm_launch_segs(c->stream, k_radix_downsweep, rx.data() + g0, k, rtiles, MT_THREADS, bit);
+                    }
+                }
+                for (size_t j = 0; j < nctls; j++) {
+                    std::swap(rx[j].kin, rx[j].kout);
+                    std::swap(rx[j].iin, rx[j].iout);
+                }
+            }
+        }
+        std::vector<cc_job> sorted = jobs;   // the same jobs reading the buffers the last pass wrote
+        for (size_t j = 0; j < nctls; j++) {
+            sorted[j].keys = rx[j].kin;
+            sorted[j].idx = rx[j].iin;
+        }
+        launch_jobs(c, "check_ctls/flags", k_cc_flags, sorted, recs1_of);
+        scan_jobs(c, scans);
+        launch_jobs(c, "check_ctls/mark", k_cc_mark, sorted, recs_of);
+        launch_jobs(c, "check_ctls/verdict", k_cc_verdict, sorted, recs_of);
+        c->download(h_ver.data(), d_ver, nctls * 32);
+        rep->host_waits++;
+        confirmed = true;
+        for (size_t j = 0; j < nctls; j++) confirmed = confirmed && !h_ver[4 * j];
+        if (!confirmed) continue;
+        // ---- the lowest failing lookup; within it a non-binary filter wins
+        size_t j = 0;
+        while (j < nctls && h_res[2 * j] == CC_NONE && h_ver[4 * j + 1] == CC_NONE) j++;
+        if (j == nctls) return 0;
+        const bool nonbin = h_res[2 * j] != CC_NONE;
+        {
+            zkm_prof_scope ps(c, "check_ctls/report");
+            ZKM_HIP_CHECK(hipMemsetAsync(d_rep, 0, CC_REPORT_WORDS * 8, c->stream));
+            hipLaunchKernelGGL(k_cc_report, dim3(1), dim3(CC_THREADS), 0, c->stream, sorted[j], (unsigned long long)(nonbin ? h_res[2 * j] : CC_NONE),
+                               (uint32_t)h_ver[4 * j + 1], d_rep);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        uint64_t out[CC_REPORT_WORDS];
+        c->download(out, d_rep, sizeof out);
+        rep->host_waits++;
+        rep->ctl = (uint32_t)j;
+        const cc_side* js = h_sides.data() + side_off[j];
+        if (nonbin) {
+            rep->kind = 1;
+            rep->side = (uint32_t)(h_res[2 * j] >> 32);
+            rep->table = js[rep->side].table;
+            rep->row = (uint32_t)h_res[2 * j];
+            rep->filter_value = out[0];
+            *msg = "CTL #" + std::to_string(j) + ": Non-binary filter? (side " + std::to_string(rep->side) + ", table " + table_label(tables, rep->table) +
+                   ", row " + std::to_string(rep->row) + ": the filter is " + std::to_string(rep->filter_value) + ")";
+            return 1;
+        }
+        rep->kind = 2;
+        rep->width = width[j];
+        rep->nwords = std::min<uint32_t>(width[j], ZKM_CTL_REPORT_WORDS);
+        memcpy(rep->tuple, out + 3, rep->nwords * 8);
+        rep->looking_count = out[1];
+        rep->looked_count = out[2];
+        rep->nlooking_locations = (uint32_t)std::min<uint64_t>(out[1], ZKM_CTL_REPORT_LOCATIONS);
+        rep->nlooked_locations = (uint32_t)std::min<uint64_t>(out[2], ZKM_CTL_REPORT_LOCATIONS);
+        auto fill = [&](zkm_ctl_location* l, const uint64_t* w, uint32_t k) {
+            for (uint32_t i = 0; i < k; i++) l[i] = zkm_ctl_location{(uint32_t)(w[i] >> 32), js[w[i] >> 32].table, (uint32_t)w[i]};
+        };
+        fill(rep->looking, out + 3 + ZKM_CTL_REPORT_WORDS, rep->nlooking_locations);
+        fill(rep->looked, out + 3 + ZKM_CTL_REPORT_WORDS + ZKM_CTL_REPORT_LOCATIONS, rep->nlooked_locations);
+        std::string row = "[";
+        for (uint32_t k = 0; k < rep->nwords; k++) row += (k ? ", " : "") + std::to_string(rep->tuple[k]);
+        if (rep->width > rep->nwords) row += ", ...";
+        *msg = "CTL #" + std::to_string(j) + ": Row " + row + "] is present " + std::to_string(out[1]) + " times in the looking tables, but " +
+               std::to_string(out[2]) + " times in the looked table. Looking locations (Table, Row index): " +
+               locations_text(tables, rep->looking, rep->nlooking_locations, out[1]) + ". Looked locations (Table, Row index): " +
+               locations_text(tables, rep->looked, rep->nlooked_locations, out[2]) + ".";
+        return 2;
+    }
+    throw std::runtime_error("check_ctls: the keys of different rows collided in " + std::to_string(CC_MAX_ATTEMPTS) + " attempts");
+}
+
+namespace {
+
+template <class F> int check_entry(const char* what, zkm_ctl_report* report, char** err, F&& body) {
+    zkm_ctl_report local;
+    zkm_ctl_report* rep = report ? report : &local;
+    memset(rep, 0, sizeof *rep);
+    std::string msg;
+    const int rc = zkm_api(what, err, [&] { body(rep, &msg); });
+    if (rc) {
+        rep->kind = 3;
+        return rc;
+    }
+    return rep->kind ? zkm_fail(err, msg.c_str()) : 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int zkm_check_ctls(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
+                   size_t nctls, zkm_ctl_report* report, char** err) {
+    return check_entry("zkm_check_ctls", report, err,
+                       [&](zkm_ctl_report* rep, std::string* msg) { zkm_check_ctls_run(c, tables, ntables, ctls, sides, nctls, rep, msg); });
+}
+
+int zkm_segment_check_ctls(zkm_ctx* c, const uint64_t* const* traces, const unsigned* log_n, zkm_ctl_report* report, char** err) {
+    return check_entry("zkm_segment_check_ctls", report, err, [&](zkm_ctl_report* rep, std::string* msg) {
+        if (!traces || !log_n) throw std::runtime_error("zkm_segment_check_ctls: null argument");
+        const zkm_cross_table_lookup* ctls;
+        const zkm_ctl_side* sides;
+        size_t nctls, nsides;
+        zkm_all_stark_ctls(&ctls, &nctls, &sides, &nsides);
+        zkm_table_input tables[12];
+        for (int id = 0; id < 12; id++) {   // Table::all() order
+            const int t = zkm_table_enum_index(id);
+            tables[t] = zkm_table_input{id, traces[t], zkm_table_width(id), log_n[t], zkm_all_stark_ctl_table(id), nullptr};
+        }
+        zkm_check_ctls_run(c, tables, 12, ctls, sides, nctls, rep, msg);
+    });
+}
+
+}  // extern "C"

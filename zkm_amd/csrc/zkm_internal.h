@@ -100,6 +100,8 @@ struct zkm_ctx {
     std::mutex alloc_mu;                // guards the two maps (the out-of-memory path of a relative trims this cache from its thread)
     zkm_ctx* parent = nullptr;          // of a commit lane: the context that owns it
     std::atomic<int> debug_fail_allocs{0};   // test hook (root context only): pretend the next k hipMalloc first attempts fail
+    int check_ctls = 0;                 // the prove drivers run check_ctls on each segment's tables before they prove (ctl_check.hip)   } zkm_ctx_set_tuning
+    unsigned debug_ctl_key_bits = 0;    // test hook: the FIRST attempt of a check_ctls call sorts by keys truncated to this many bits (0: off)
     // twiddles
     zkm_twiddles tw;
     // power tables for coset scaling: key (shift, log_n) -> device ptr [lo table 2^h | hi table 2^(log_n-h)]
@@ -495,6 +497,10 @@ void zkm_arithmetic_count(zkm_arith_job* j, size_t nseg);
 size_t zkm_arithmetic_height(zkm_arith_job& j, const uint64_t got[2], size_t* natural_rows_out);   // max(2^16, next_pow2(rows)); throws on a flag
 void zkm_arithmetic_write(zkm_arith_job* j, size_t nseg, const unsigned* log_n, gl_t* const* out_dev, unsigned* const* d_bad);
 
+// ctl_check.hip: check_ctls on one segment's tables.  Returns the report's kind (0 consistent, 1 non-binary filter, 2 multisets differ)
+// with the reference's message in *msg; throws when the check cannot be made
+int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
+                       size_t nctls, zkm_ctl_report* rep, std::string* msg);
 // ctl.hip: the body of zkm_prove_segments[_columns] (exactly one of traces / columns non-null); seg_base = position of segment 0 in the
 // caller's larger call (csrc/pool.hip deals groups of one pool call to its workers) -- used in error messages only
 extern "C" int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const uint64_t* const* const* traces,
