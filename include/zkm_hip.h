@@ -94,6 +94,17 @@ void zkm_ctx_trim(zkm_ctx* ctx);
  *                               zkm_prove_segments_ops run zkm_check_ctls on each segment's tables before they prove -- the reference's `test`
  *                               feature (prover.rs:171-176) -- and fail with "check_ctls: segment <position in the call>: " and that call's
  *                               message; no proof is written.  Default 0: no launch is added and every proof word stays what it is
+ *   "verify"                    1: the same prove calls verify what they have written (zkm_verify_proofs on every segment's blobs) before they
+ *                               return, as prove_root does (fixed_recursive_verifier.rs:777, 853); on a rejection the call fails with
+ *                               "verify: segment <position in the call>: " and that call's message, and no proof word is handed out -- of any
+ *                               segment of a zkm_prove_segments[_columns] call, all of which are verified in one set of launches after the
+ *                               last has been proven.  (zkm_prove_segments_ops builds and proves a call of more than 32 segments, or
+ *                               of more than the memory budget holds, in consecutive waves, and a pool deals groups to its workers: there
+ *                               each wave / group is verified and handed out on its own.)
+ *                               Default 0: no launch is added and every proof word stays what it is
+ *   "debug_verify_flip"         TEST HOOK, accepted only when the process environment holds ZKM_ENABLE_TEST_HOOKS=1 (an unknown key otherwise):
+ *                               under "verify", word `value` (0: off) of the blobs of segment 1 of the call (segment 0 of a call of one) is
+ *                               increased by one mod p between proving and verifying (tests/test_gpu_verify.py)
  *   "debug_ctl_key_bits"        TEST HOOK, accepted only when the process environment holds ZKM_ENABLE_TEST_HOOKS=1 (an unknown key otherwise):
  *                               the FIRST attempt of every zkm_check_ctls call sorts by keys truncated to `value` bits (0: off), so that the
  *                               collision path -- confirmation fails, the call sorts again with the next seed -- runs; reports are
@@ -822,6 +833,65 @@ typedef struct zkm_ctl_report {
 int zkm_check_ctls(zkm_ctx* ctx, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
                    size_t nctls, zkm_ctl_report* report, char** err);
 int zkm_segment_check_ctls(zkm_ctx* ctx, const uint64_t* const* traces, const unsigned* log_n, zkm_ctl_report* report, char** err);
+/* ------------------------------------------------------------------ verify_proof on the device
+ * verify_proof (verifier.rs:27-176) with verify_stark_proof_with_challenges (:178-292) per table and verify_cross_table_lookups, for the
+ * proof blobs this library writes, from the blobs alone -- what prove_root / prove_root_with_assumption run on every segment proof
+ * before it enters the recursion (fixed_recursive_verifier.rs:777, 853).  The transcript is replayed on the host (every word of it is
+ * in the blob); the constraints at zeta, the Merkle paths and the FRI arithmetic of all tables of all segments run in one set of
+ * launches, and one download brings the verdicts back.  A rejected proof is a normal result: nothing is asserted on the device.
+ *   code        ZKM_VERIFY_*: the check that failed, in the reference's order of checks
+ *                 OK; SHAPE (magic, header against cfg and the table -- validate_proof_shape :294-342 -- the FRI proof's shape,
+ *                 proof_words too short, a field word >= p: found on the host, such a blob never reaches a kernel); TRANSCRIPT_STATE (the
+ *                 recorded init_challenger_state is not where the transcript stands); CTL_CHALLENGES (the claimed challenges are not the
+ *                 transcript's); QUOTIENT ("Mismatch between evaluation and opening of quotient polynomial" :248-264); POW; INITIAL_MERKLE;
+ *                 FRI_EVAL; FRI_MERKLE; FINAL_POLY; CTL_SUM (verify_cross_table_lookups); FAILED (the check could not be made: bad
+ *                 arguments, a runtime failure)
+ *   table       index into `tables` / Table::all()        challenge   the constraint challenge (QUOTIENT) or CTL challenge (CTL_SUM)
+ *   query, tree (initial oracle 0 trace, 1 auxiliary, 2 quotient), layer      where in the query phase
+ *   ctl         the lookup (CTL_SUM)                       host_waits  times the call waited for the device (counted where the context waits):
+ *                                                          1 whatever the segments; 0 for a segment refused on the host
+ * WHICH finding is reported is fixed: CTL_CHALLENGES first; then the lowest table, and within it TRANSCRIPT_STATE, QUOTIENT (lowest
+ * challenge), POW, then the lowest query and inside it trace tree, auxiliary tree, quotient tree, per layer evaluation before Merkle
+ * path, the final polynomial; CTL_SUM (lowest lookup, lowest challenge) only when every table passes.  A blob with a SHAPE finding in
+ * any table is reported as SHAPE at that table and nothing of its segment is launched.
+ * (Layout lock: `tools/abi_layout verify` prints the struct, tests/test_verify_abi.py compares it with the ctypes and Rust mirrors.) */
+#define ZKM_VERIFY_OK 0
+#define ZKM_VERIFY_SHAPE 1
+#define ZKM_VERIFY_TRANSCRIPT_STATE 2
+#define ZKM_VERIFY_CTL_CHALLENGES 3
+#define ZKM_VERIFY_QUOTIENT 4
+#define ZKM_VERIFY_POW 5
+#define ZKM_VERIFY_INITIAL_MERKLE 6
+#define ZKM_VERIFY_FRI_EVAL 7
+#define ZKM_VERIFY_FRI_MERKLE 8
+#define ZKM_VERIFY_FINAL_POLY 9
+#define ZKM_VERIFY_CTL_SUM 10
+#define ZKM_VERIFY_FAILED 11
+typedef struct zkm_verify_report {
+    uint32_t code, table, challenge, query, tree, layer, ctl, host_waits;
+} zkm_verify_report;
+/* The general form, the mirror of zkm_prove_with_traces: tables / ctls / sides / nctls / public values as that call takes them (`trace` and
+ * `columns` of a table are ignored; its log_n must be the blob's), proofs = the per-table blobs concatenated as it writes them,
+ * proof_words their total, ctl_challenges = the claimed challenges (2 * num_challenges words) or NULL.  Returns 0 when the proof is
+ * accepted; nonzero otherwise with *err naming table and check; `report` (may be NULL) is filled either way. */
+int zkm_verify_proofs(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_table_input* tables, size_t ntables,
+                      const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, const uint64_t* public_values,
+                      size_t npublic, const uint64_t* proofs, size_t proof_words, const uint64_t* ctl_challenges, zkm_verify_report* report,
+                      char** err);
+/* verify_proof for nseg segments proven with the AllStark that ships with the library (zkm_all_stark_ctls): proofs[s] = the twelve
+ * blobs of segment s in Table::all() order as zkm_prove_segment* writes them, in HOST memory (the transcript is replayed there; a
+ * device pointer is FAILED), proof_words[s] their total.  The heights are read from the blobs (recover_degree_bits, proof.rs:205-212), so segments of different heights share a call.  public_values / npublic /
+ * ctl_challenges may be NULL, and so may each ctl_challenges[s]; reports = nseg entries (may be NULL).  Returns 0 when every proof is
+ * accepted; nonzero otherwise, *err naming the first rejected segment, its table (the reference's name) and the check. */
+int zkm_verify_segments(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const uint64_t* const* proofs, const size_t* proof_words,
+                        const uint64_t* const* public_values, const size_t* npublic, const uint64_t* const* ctl_challenges,
+                        zkm_verify_report* reports, char** err);
+/* The mirror of zkm_prove_single_table (the benchmark's fake CtlData shape): verify_stark_proof_with_challenges (verifier.rs:178-292)
+ * on one blob, `challenger` in/out like the prove call (left untouched unless the proof is accepted).  naux counts the CTL columns. */
+int zkm_verify_single_table(zkm_ctx* ctx, int table_id, const zkm_stark_config* cfg, const uint64_t* proof, size_t proof_words, size_t ncols,
+                            size_t naux, const uint32_t* num_helpers, size_t nctl_zs, zkm_challenger* challenger, zkm_verify_report* report,
+                            char** err);
+
 /* a9: StarkOpeningSet::new building block (proof.rs:299-334): p(zeta) in F2 for every polynomial of the
  * batch; out = ncols x 2 words, host. */
 int zkm_eval_openings(zkm_ctx* ctx, const zkm_batch* b, const uint64_t zeta[2], uint64_t* out, char** err);

@@ -101,6 +101,17 @@ pub struct ZkmCtlReport {
     pub looking: [ZkmCtlLocation; 8], pub looked: [ZkmCtlLocation; 8],
 }
 pub type zkm_ctl_report = ZkmCtlReport;
+/// the verdict of zkm_verify_* on one proof (include/zkm_hip.h; compared with `abi_layout verify` by tests/test_verify_abi.py):
+/// code = ZKM_VERIFY_*, the check that failed, in the reference's order of checks
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct ZkmVerifyReport {
+    pub code: u32, pub table: u32, pub challenge: u32, pub query: u32, pub tree: u32, pub layer: u32, pub ctl: u32, pub host_waits: u32,
+}
+pub type zkm_verify_report = ZkmVerifyReport;
+pub const ZKM_VERIFY_OK: u32 = 0; pub const ZKM_VERIFY_SHAPE: u32 = 1; pub const ZKM_VERIFY_TRANSCRIPT_STATE: u32 = 2;
+pub const ZKM_VERIFY_CTL_CHALLENGES: u32 = 3; pub const ZKM_VERIFY_QUOTIENT: u32 = 4; pub const ZKM_VERIFY_POW: u32 = 5;
+pub const ZKM_VERIFY_INITIAL_MERKLE: u32 = 6; pub const ZKM_VERIFY_FRI_EVAL: u32 = 7; pub const ZKM_VERIFY_FRI_MERKLE: u32 = 8;
+pub const ZKM_VERIFY_FINAL_POLY: u32 = 9; pub const ZKM_VERIFY_CTL_SUM: u32 = 10; pub const ZKM_VERIFY_FAILED: u32 = 11;
 
 // ZKM_TABLE_* ids (NOT the reference's Table enum order: see zkm_table_enum_index)
 pub const ZKM_TABLE_POSEIDON: c_int = 0; pub const ZKM_TABLE_LOGIC: c_int = 1; pub const ZKM_TABLE_KECCAK_SPONGE: c_int = 2;
@@ -296,6 +307,17 @@ extern "C" {
                           sides: *const zkm_ctl_side, nctls: usize, report: *mut zkm_ctl_report, err: *mut *mut c_char) -> c_int;
     pub fn zkm_segment_check_ctls(ctx: *mut zkm_ctx, traces: *const *const u64, log_n: *const c_uint, report: *mut zkm_ctl_report,
                                   err: *mut *mut c_char) -> c_int;
+    // verify_proof (verifier.rs:27-176) on the device: the general form, K AllStark segments, and the mirror of zkm_prove_single_table
+    pub fn zkm_verify_proofs(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, tables: *const zkm_table_input, ntables: usize,
+                             ctls: *const zkm_cross_table_lookup, sides: *const zkm_ctl_side, nctls: usize, public_values: *const u64,
+                             npublic: usize, proofs: *const u64, proof_words: usize, ctl_challenges: *const u64, report: *mut zkm_verify_report,
+                             err: *mut *mut c_char) -> c_int;
+    pub fn zkm_verify_segments(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, proofs: *const *const u64, proof_words: *const usize,
+                               public_values: *const *const u64, npublic: *const usize, ctl_challenges: *const *const u64,
+                               reports: *mut zkm_verify_report, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_verify_single_table(ctx: *mut zkm_ctx, table_id: c_int, cfg: *const zkm_stark_config, proof: *const u64, proof_words: usize,
+                                   ncols: usize, naux: usize, num_helpers: *const u32, nctl_zs: usize, challenger: *mut zkm_challenger,
+                                   report: *mut zkm_verify_report, err: *mut *mut c_char) -> c_int;
     pub fn zkm_check_constraints(ctx: *mut zkm_ctx, table_id: c_int, cfg: *const zkm_stark_config, trace: *const u64, ncols: usize, log_n: c_uint,
                                  aux: *const u64, naux: usize, table: *const zkm_ctl_table, zs: *const zkm_ctl_z, colset_ids: *const u32,
                                  nzs: usize, lookup_challenges: *const u64, alphas: *const u64, nalphas: usize, first_failing_row: *mut u64,

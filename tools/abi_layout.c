@@ -59,11 +59,29 @@ static void print_check_ctls(void) {
     printf("\n}\n");
 }
 
+/* `abi_layout verify`: the struct of zkm_verify_* (tests/test_verify_abi.py compares it with its mirrors); on request only, as above. */
+static void print_verify(void) {
+    int first_struct = 1, first_field = 1;
+    int (*segments)(zkm_ctx*, const zkm_stark_config*, size_t, const uint64_t* const*, const size_t*, const uint64_t* const*, const size_t*,
+                    const uint64_t* const*, zkm_verify_report*, char**) = 0;
+    (void)sizeof(segments = zkm_verify_segments);
+    printf("{");
+    BEGIN(zkm_verify_report);
+    FIELD(zkm_verify_report, code); FIELD(zkm_verify_report, table); FIELD(zkm_verify_report, challenge); FIELD(zkm_verify_report, query);
+    FIELD(zkm_verify_report, tree); FIELD(zkm_verify_report, layer); FIELD(zkm_verify_report, ctl); FIELD(zkm_verify_report, host_waits);
+    END();
+    printf("\n}\n");
+}
+
 int main(int argc, char** argv) {
     int first_struct = 1, first_field = 1;
     check_segments_ops_prototypes();
     if (argc > 1 && argv[1][0] == 'c') {
         print_check_ctls();
+        return 0;
+    }
+    if (argc > 1 && argv[1][0] == 'v') {
+        print_verify();
         return 0;
     }
     printf("{");

@@ -50,6 +50,7 @@ EXPORTS = [
     "zkm_segments_tables", "zkm_prove_segments_ops", "zkm_pool_prove_segments_ops",
     "zkm_segment_ops_stage", "zkm_staged_ops_get", "zkm_staged_ops_ready", "zkm_staged_ops_free",
     "zkm_check_ctls", "zkm_segment_check_ctls",
+    "zkm_verify_proofs", "zkm_verify_segments", "zkm_verify_single_table",
 ]
 
 
@@ -151,6 +152,31 @@ class CtlReport(C.Structure):
 
     def looked_locations(self):
         return [(l.side, l.table, l.row) for l in self.looked[:self.nlooked_locations]]
+
+
+VERIFY_CODES = ("OK", "SHAPE", "TRANSCRIPT_STATE", "CTL_CHALLENGES", "QUOTIENT", "POW", "INITIAL_MERKLE", "FRI_EVAL", "FRI_MERKLE", "FINAL_POLY",
+                "CTL_SUM", "FAILED")
+(VERIFY_OK, VERIFY_SHAPE, VERIFY_TRANSCRIPT_STATE, VERIFY_CTL_CHALLENGES, VERIFY_QUOTIENT, VERIFY_POW, VERIFY_INITIAL_MERKLE, VERIFY_FRI_EVAL,
+ VERIFY_FRI_MERKLE, VERIFY_FINAL_POLY, VERIFY_CTL_SUM, VERIFY_FAILED) = range(12)
+
+
+class VerifyReport(C.Structure):
+    """zkm_verify_report (include/zkm_hip.h): the verdict of zkm_verify_* on one proof.  code = VERIFY_* (the check that failed, 0 when
+    the proof is accepted); .message holds the text of the error channel for the first rejected proof of a call (None otherwise)."""
+    _fields_ = [(n, C.c_uint32) for n in ("code", "table", "challenge", "query", "tree", "layer", "ctl", "host_waits")]
+    message = None
+
+    @property
+    def name(self):
+        return VERIFY_CODES[self.code] if self.code < len(VERIFY_CODES) else "?%d" % self.code
+
+    def key(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_)
+
+
+def abi_mirrors_verify():
+    """The struct of zkm_verify_* -> its mirror; tests/test_verify_abi.py compares it with `tools/abi_layout verify`."""
+    return {"zkm_verify_report": VerifyReport}
 
 
 def abi_mirrors():
@@ -306,6 +332,12 @@ def load():
                                             u64p, u64p, C.c_size_t, u64p, err]),
         "zkm_check_ctls": (C.c_int, [cp, cp, C.c_size_t, cp, cp, C.c_size_t, C.POINTER(CtlReport), err]),
         "zkm_segment_check_ctls": (C.c_int, [cp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint), C.POINTER(CtlReport), err]),
+        "zkm_verify_proofs": (C.c_int, [cp, C.POINTER(StarkConfig), cp, C.c_size_t, cp, cp, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, u64p,
+                                        C.POINTER(VerifyReport), err]),
+        "zkm_verify_segments": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(VerifyReport), err]),
+        "zkm_verify_single_table": (C.c_int, [cp, C.c_int, C.POINTER(StarkConfig), u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32),
+                                              C.c_size_t, C.POINTER(Challenger), C.POINTER(VerifyReport), err]),
         "zkm_profile_enable": (None, [cp, C.c_int]),
         "zkm_profile_reset": (None, [cp]),
         "zkm_profile_count": (C.c_size_t, [cp]),
@@ -1242,6 +1274,66 @@ class Context:
         rep, err = CtlReport(), C.c_char_p()
         rc = self.L.zkm_segment_check_ctls(self.h, ptrs, lg, C.byref(rep), C.byref(err))
         return self._ctl_report(rc, rep, err)
+
+    @staticmethod
+    def _verify_reports(rc, reps, err):
+        """The reports of a verify call; a call that could not be made (FAILED) raises.  The message belongs to the first rejection."""
+        msg = err.value.decode() if err.value else None
+        if rc != 0 and (not reps or all(r.code in (VERIFY_OK, VERIFY_FAILED) for r in reps)):
+            raise ZkmError(msg or "verify: error %d" % rc)
+        for r in reps:
+            if r.code != VERIFY_OK:
+                r.message = msg
+                break
+        return reps
+
+    def verify_segments(self, proofs, public_values=None, ctl_challenges=None, cfg=None):
+        """zkm_verify_segments: verify_proof (verifier.rs:27-176) on the device for K segments proven with the built-in AllStark.
+        proofs: one uint64 array per segment (the twelve blobs as prove_segment* returns them); public_values / ctl_challenges: one
+        array per segment, or None (a ctl_challenges entry may be None too).  Returns one VerifyReport per segment."""
+        cfg = cfg or self.standard_config()
+        K = len(proofs)
+        keep = [np.ascontiguousarray(p, dtype=np.uint64) for p in proofs]
+        pp = (C.c_void_p * K)(*[k.ctypes.data for k in keep])
+        pw = (C.c_size_t * K)(*[k.size for k in keep])
+        pubs = [np.ascontiguousarray(v, dtype=np.uint64) for v in public_values] if public_values is not None else None
+        pv = (C.c_void_p * K)(*[v.ctypes.data if v.size else None for v in pubs]) if pubs is not None else None
+        npv = (C.c_size_t * K)(*[v.size for v in pubs]) if pubs is not None else None
+        chs = [None if v is None else np.ascontiguousarray(v, dtype=np.uint64) for v in ctl_challenges] if ctl_challenges is not None else None
+        cc = (C.c_void_p * K)(*[None if v is None else v.ctypes.data for v in chs]) if chs is not None else None
+        reps, err = (VerifyReport * K)(), C.c_char_p()
+        rc = self.L.zkm_verify_segments(self.h, C.byref(cfg), K, pp, pw, pv, npv, cc, reps, C.byref(err))
+        return self._verify_reports(rc, list(reps), err)
+
+    def verify_proofs(self, tables, ctls, proofs, public_values=(), ctl_challenges=None, cfg=None):
+        """zkm_verify_proofs: the general form, the mirror of prove_with_traces -- tables / ctls as that call takes them (a table's trace
+        may be None: it is ignored), proofs = its concatenated blobs.  Returns the VerifyReport."""
+        from . import ctl as zc
+        cfg = cfg or self.standard_config()
+        tarr, keep = zc.pack_tables([(tid, None, ncols, log_n, ct) for (tid, _tr, ncols, log_n, ct) in tables])
+        carr, sides = zc.pack_ctls(ctls)
+        proofs = np.ascontiguousarray(proofs, dtype=np.uint64)
+        pub = np.ascontiguousarray(public_values, dtype=np.uint64)
+        ch = None if ctl_challenges is None else np.ascontiguousarray(ctl_challenges, dtype=np.uint64)
+        rep, err = VerifyReport(), C.c_char_p()
+        rc = self.L.zkm_verify_proofs(self.h, C.byref(cfg), tarr, len(tables), carr.ctypes.data, sides.ctypes.data, len(carr),
+                                      pub.ctypes.data_as(u64p), pub.size, proofs.ctypes.data_as(u64p), proofs.size,
+                                      None if ch is None else ch.ctypes.data_as(u64p), C.byref(rep), C.byref(err))
+        return self._verify_reports(rc, [rep], err)[0]
+
+    def verify_single_table(self, proof, num_helpers, challenger=None, cfg=None, ncols=POSEIDON_COLS, table_id=TABLE_POSEIDON, naux=None):
+        """zkm_verify_single_table: the mirror of prove_single_table (the benchmark's fake CtlData shape).  challenger: in/out like
+        the prove call (advanced only when the proof is accepted).  Returns the VerifyReport."""
+        cfg = cfg or self.standard_config()
+        ch = challenger if challenger is not None else Challenger()
+        if naux is None:
+            naux = sum(int(h) + 1 for h in num_helpers)
+        nh = (C.c_uint32 * len(num_helpers))(*num_helpers)
+        proof = np.ascontiguousarray(proof, dtype=np.uint64)
+        rep, err = VerifyReport(), C.c_char_p()
+        rc = self.L.zkm_verify_single_table(self.h, table_id, C.byref(cfg), proof.ctypes.data_as(u64p), proof.size, ncols, naux, nh,
+                                            len(num_helpers), C.byref(ch), C.byref(rep), C.byref(err))
+        return self._verify_reports(rc, [rep], err)[0]
 
     def prove_with_traces(self, tables, ctls, public_values=(), cfg=None):
         """prove_with_traces (prover.rs:130-232).  tables: list of (table_id, trace (ndarray | DeviceBuffer), ncols, log_n, CtlTable);

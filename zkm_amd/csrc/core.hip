@@ -232,6 +232,7 @@ void zkm_ctx::ensure_down(size_t bytes) {
     size_t cap = down_cap ? down_cap : XFER_DOWN;
     while (cap < bytes) cap <<= 1;
     if (h_down) {
+        host_waits++;
         ZKM_HIP_CHECK(hipStreamSynchronize(stream));
         (void)hipHostFree(h_down);
         h_down = nullptr;
@@ -283,6 +284,7 @@ static inline uint64_t now_ns() {
 }
 void zkm_ctx::wait_flag(const uint64_t* flag, uint64_t seq) {
     struct waiter { waiter() { g_waiting.fetch_add(1, std::memory_order_relaxed); } ~waiter() { g_waiting.fetch_sub(1, std::memory_order_relaxed); } } w;
+    host_waits++;
     const uint64_t t0 = now_ns(), spin_ns = (parent ? parent : this)->block_after_us * 1000ull;
     for (uint64_t spins = 1;; spins++) {
         if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) return;
@@ -554,6 +556,13 @@ int zkm_ctx_set_tuning(zkm_ctx* c, const char* key, uint64_t value, char** err) 
                 x->pow_round_log = value ? 16 : 17;                 // (half-filled SIMDs are somebody else's slots here: 76.3 vs 75.4 segments/s)
             }
             else if (k == "check_ctls") x->check_ctls = value ? 1 : 0;
+            else if (k == "verify") x->verify = value ? 1 : 0;
+            else if (k == "debug_verify_flip") {
+                // test hook, as debug_fail_allocs below
+                const char* hooks = getenv("ZKM_ENABLE_TEST_HOOKS");
+                if (!hooks || strcmp(hooks, "1") != 0) throw std::runtime_error("zkm_ctx_set_tuning: unknown key '" + k + "'");
+                x->debug_verify_flip = value;
+            }
             else if (k == "debug_ctl_key_bits") {
                 // test hook, as debug_fail_allocs below
                 const char* hooks = getenv("ZKM_ENABLE_TEST_HOOKS");

@@ -17,8 +17,8 @@
 #include "all_stark_ctl.inc"
 
 // ------------------------------------------------------------------ descriptor upload + validation
-void ctl_dev_owner::upload(zkm_ctx* ctx, const zkm_ctl_table* t, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs, bool lookup_mode,
-                           size_t trace_ncols, size_t nseg) {
+ctl_dev_packed ctl_dev_pack(const zkm_ctl_table* t, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs, bool lookup_mode, size_t trace_ncols,
+                            size_t nseg, std::vector<char>& out) {
     if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("CTL description: bad segment count");
     // (a stacked description: zs holds nseg lists of nzs entries that differ in their challenges only -- segment s of a launch reads list s)
     for (size_t sg = 1; sg < nseg; sg++)
@@ -65,27 +65,38 @@ void ctl_dev_owner::upload(zkm_ctx* ctx, const zkm_ctl_table* t, const zkm_ctl_z
     size_t o_cols = 0, o_coeff = al(o_cols + t->ncolumns * sizeof(zkm_column)), o_sets = al(o_coeff + t->nterms * 8);
     size_t o_zs = al(o_sets + t->ncolsets * sizeof(zkm_colset)), o_tc = al(o_zs + nseg * nzs * sizeof(zkm_ctl_z));
     size_t o_fi = al(o_tc + t->nterms * 4), o_ids = al(o_fi + t->nfilter_idx * 4), total = al(o_ids + nids * 4) + 16;
-    std::vector<char> h(total, 0);
+    const size_t base = (out.size() + 15) & ~(size_t)15;
+    out.resize(base + total, 0);
+    char* h = out.data() + base;
     if (t->ncolumns) memcpy(&h[o_cols], t->columns, t->ncolumns * sizeof(zkm_column));
     if (t->nterms) { memcpy(&h[o_coeff], t->term_coeff, t->nterms * 8); memcpy(&h[o_tc], t->term_col, t->nterms * 4); }
     if (t->ncolsets) memcpy(&h[o_sets], t->colsets, t->ncolsets * sizeof(zkm_colset));
     if (nzs) memcpy(&h[o_zs], zs, nseg * nzs * sizeof(zkm_ctl_z));
     if (t->nfilter_idx) memcpy(&h[o_fi], t->filter_idx, t->nfilter_idx * 4);
     if (nids) memcpy(&h[o_ids], colset_ids, nids * 4);
-    blob = zkm_scratch(ctx, total);
+    ctl_dev_packed p{};
+    const char* b = (const char*)base;   // (offsets for now: ctl_dev_rebase)
+    p.d.columns = (const zkm_column*)(b + o_cols);
+    p.d.term_coeff = (const uint64_t*)(b + o_coeff);
+    p.d.colsets = (const zkm_colset*)(b + o_sets);
+    p.d.zs = (const zkm_ctl_z*)(b + o_zs);
+    p.d.term_col = (const uint32_t*)(b + o_tc);
+    p.d.filter_idx = (const uint32_t*)(b + o_fi);
+    p.d.colset_ids = (const uint32_t*)(b + o_ids);
+    p.d.nzs = (uint32_t)nzs;
+    p.d.total_helpers = (uint32_t)th;
+    p.naux = th + nzs;
+    return p;
+}
+void ctl_dev_owner::upload(zkm_ctx* ctx, const zkm_ctl_table* t, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs, bool lookup_mode,
+                           size_t trace_ncols, size_t nseg) {
+    std::vector<char> h;
+    const ctl_dev_packed p = ctl_dev_pack(t, zs, colset_ids, nzs, lookup_mode, trace_ncols, nseg, h);
+    blob = zkm_scratch(ctx, h.size());
     h_zs.assign(zs, zs + nzs);
-    ctx->upload(blob.p, h.data(), total);   // (staged through the context's pinned ring or by the runtime: `h` may go)
-    char* b = blob.as<char>();
-    d.columns = (const zkm_column*)(b + o_cols);
-    d.term_coeff = (const uint64_t*)(b + o_coeff);
-    d.colsets = (const zkm_colset*)(b + o_sets);
-    d.zs = (const zkm_ctl_z*)(b + o_zs);
-    d.term_col = (const uint32_t*)(b + o_tc);
-    d.filter_idx = (const uint32_t*)(b + o_fi);
-    d.colset_ids = (const uint32_t*)(b + o_ids);
-    d.nzs = (uint32_t)nzs;
-    d.total_helpers = (uint32_t)th;
-    naux = th + nzs;
+    ctx->upload(blob.p, h.data(), h.size());   // (staged through the context's pinned ring or by the runtime: `h` may go)
+    d = ctl_dev_rebase(p.d, blob.as<char>());
+    naux = p.naux;
 }
 ctl_dev_owner::~ctl_dev_owner() {
     if (blob.p) (void)hipStreamSynchronize(blob.c->stream);
@@ -339,11 +350,7 @@ void zkm_ctl_data_device(zkm_ctx* c, const ctl_dev_owner& own, const gl_t* d_tra
 }
 
 // ------------------------------------------------------------------ per-table CtlZData lists (cross_table_lookup_data order)
-struct table_zs {
-    std::vector<zkm_ctl_z> zs;
-    std::vector<uint32_t> ids;
-    size_t naux = 0;
-};
+// (struct table_zs: zkm_internal.h -- the verifier derives the same lists from the transcript it replays)
 static std::vector<table_zs> derive_zs(size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls,
                                        size_t nch, const uint64_t* challenges) {
     std::vector<table_zs> out(ntables);
@@ -381,6 +388,11 @@ static std::vector<table_zs> derive_zs(size_t ntables, const zkm_cross_table_loo
         }
     }
     return out;
+}
+
+std::vector<table_zs> zkm_derive_zs(size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t nch,
+                                    const uint64_t* challenges) {
+    return derive_zs(ntables, ctls, sides, nctls, nch, challenges);
 }
 
 extern "C" {
@@ -505,6 +517,11 @@ int zkm_all_stark_ctls(const zkm_cross_table_lookup** ctls_out, size_t* nctls_ou
     if (nsides_out) *nsides_out = AS_NSIDES;
     return 0;
 }
+}  // extern "C"
+void zkm_all_stark_table_inputs(zkm_table_input out[12]) {
+    for (int t = 0; t < 12; t++) out[t] = zkm_table_input{AS_TABLE_IDS[t], nullptr, AS_TABLE_WIDTH[t], 0, &AS_CTL_TABLES[t], nullptr};
+}
+extern "C" {
 const zkm_ctl_table* zkm_all_stark_ctl_table(int table_id) {
     int e = zkm_table_enum_index(table_id);
     return e < 0 ? nullptr : &AS_CTL_TABLES[e];
@@ -1126,6 +1143,50 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
     call.prove_tables();
 }
 
+static void prove_segments_waves(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const seg_io* io, size_t ntables,
+                                 const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t seg_base);
+
+// The body of every prove driver: the whole call (`waves`: cut into waves by the memory budget) or, under "verify"
+// (zkm_ctx_set_tuning), the same into buffers of the call's own, then verify_proof on ALL its segments in one set of launches as
+// prove_root does on each (fixed_recursive_verifier.rs:777, 853), and only then the words handed out -- of no segment of the call, in
+// whichever wave it was proven, when one is rejected
+static void prove_segments_checked(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const seg_io* io, size_t ntables,
+                                   const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t seg_base, bool waves) {
+    auto prove = [&](const seg_io* x) {
+        if (waves) prove_segments_waves(c, cfg, nseg, x, ntables, ctls, sides, nctls, seg_base);
+        else prove_segments_impl(c, cfg, nseg, x, ntables, ctls, sides, nctls, seg_base);
+    };
+    if (!c->verify || nseg == 0) return prove(io);
+    std::vector<seg_io> held(io, io + nseg);
+    std::vector<std::vector<uint64_t>> proofs(nseg), challenges(nseg);
+    for (size_t s = 0; s < nseg; s++) {
+        if (!io[s].tables || !io[s].proofs || !io[s].challenges) throw std::runtime_error("zkm_prove_with_traces: null argument");
+        proofs[s].assign(zkm_all_proof_words(cfg, io[s].tables, ntables, ctls, sides, nctls, nullptr), 0);
+        challenges[s].assign(2 * (size_t)cfg->num_challenges, 0);
+        held[s].proofs = proofs[s].data();
+        held[s].challenges = challenges[s].data();
+    }
+    prove(held.data());
+    if (c->debug_verify_flip) {   // test hook: one word changes between proving and verifying
+        std::vector<uint64_t>& p = proofs[nseg > 1 ? 1 : 0];
+        if (c->debug_verify_flip < p.size()) p[c->debug_verify_flip] = p[c->debug_verify_flip] + 1 == GL_P ? 0 : p[c->debug_verify_flip] + 1;
+    }
+    std::vector<const zkm_table_input*> tabs(nseg);
+    std::vector<const uint64_t*> pubs(nseg), pp(nseg), cc(nseg);
+    std::vector<size_t> npubs(nseg), words(nseg);
+    for (size_t s = 0; s < nseg; s++) {
+        tabs[s] = io[s].tables; pubs[s] = io[s].pub; npubs[s] = io[s].npub;
+        pp[s] = proofs[s].data(); words[s] = proofs[s].size(); cc[s] = challenges[s].data();
+    }
+    std::string msg;
+    const size_t bad = zkm_verify_run(c, cfg, nseg, tabs.data(), ntables, ctls, sides, nctls, pubs.data(), npubs.data(), pp.data(), words.data(), cc.data(), &msg);
+    if (bad < nseg) throw std::runtime_error("verify: segment " + std::to_string(seg_base + bad) + ": " + msg);
+    for (size_t s = 0; s < nseg; s++) {
+        memcpy(io[s].proofs, proofs[s].data(), proofs[s].size() * sizeof(uint64_t));
+        memcpy(io[s].challenges, challenges[s].data(), challenges[s].size() * sizeof(uint64_t));
+    }
+}
+
 // estimated bytes one segment holds while its wave is proven: per table the trace values, coefficients, 4x LDE and digests of the trace,
 // auxiliary and quotient batches
 template <class TZ>
@@ -1145,7 +1206,7 @@ static double segment_footprint(const zkm_stark_config* cfg, const zkm_table_inp
 // cached plus the memory that is free right now.  One segment always goes (a single
 // segment that does not fit fails in the allocator, as it always did).
 static void prove_segments_waves(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const seg_io* io, size_t ntables,
-                                 const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t seg_base = 0) {
+                                 const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t seg_base) {
     if (nseg <= 1) {
         prove_segments_impl(c, cfg, nseg, io, ntables, ctls, sides, nctls, seg_base);
         return;
@@ -1194,7 +1255,7 @@ int zkm_prove_with_traces(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_tab
     return zkm_api("zkm_prove_with_traces", c, err, [&] {
         if (!cfg || (!tables && ntables)) throw std::runtime_error("zkm_prove_with_traces: null argument");
         seg_io io{tables, pub, npub, proofs, challenges};
-        prove_segments_impl(c, cfg, 1, &io, ntables, ctls, sides, nctls);
+        prove_segments_checked(c, cfg, 1, &io, ntables, ctls, sides, nctls, 0, false);
     });
 }
 
@@ -1218,7 +1279,7 @@ int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_confi
             io[s] = seg_io{tables[s].data(), pub ? pub[s] : nullptr, npub ? npub[s] : 0, proofs[s], challenges[s]};
             if (io[s].npub && !io[s].pub) throw std::runtime_error(std::string(what) + ": null public values");
         }
-        prove_segments_waves(c, cfg, nseg, io.data(), 12, AS_CTLS, AS_SIDES, AS_NCTLS, seg_base);
+        prove_segments_checked(c, cfg, nseg, io.data(), 12, AS_CTLS, AS_SIDES, AS_NCTLS, seg_base, true);
     });
 }
 

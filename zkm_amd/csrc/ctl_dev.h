@@ -51,6 +51,23 @@ __device__ __forceinline__ gl_t ctl_combine(const ctl_dev& d, const zkm_colset& 
     return gl_add(acc, gamma);
 }
 
+// A description validated and laid out as one block of bytes, appended to `out` at a 16-byte boundary; the pointers of .d are OFFSETS
+// from the start of `out` until ctl_dev_rebase gives them the address `out` was copied to (ctl.hip).  The owner below uploads one
+// description on its own; the verifier packs all of a call's descriptions into the one block it sends up.
+struct ctl_dev_packed { ctl_dev d; size_t naux; };
+ctl_dev_packed ctl_dev_pack(const zkm_ctl_table* t, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs, bool lookup_mode, size_t trace_ncols,
+                            size_t nseg, std::vector<char>& out);
+inline ctl_dev ctl_dev_rebase(ctl_dev d, const char* base) {
+    d.columns = (const zkm_column*)(base + (uintptr_t)d.columns);
+    d.term_col = (const uint32_t*)(base + (uintptr_t)d.term_col);
+    d.term_coeff = (const uint64_t*)(base + (uintptr_t)d.term_coeff);
+    d.colsets = (const zkm_colset*)(base + (uintptr_t)d.colsets);
+    d.filter_idx = (const uint32_t*)(base + (uintptr_t)d.filter_idx);
+    d.zs = (const zkm_ctl_z*)(base + (uintptr_t)d.zs);
+    d.colset_ids = (const uint32_t*)(base + (uintptr_t)d.colset_ids);
+    return d;
+}
+
 // host-side owner of the device copy of a description
 struct ctl_dev_owner {
     zkm_scratch blob;

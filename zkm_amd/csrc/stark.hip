@@ -12,11 +12,7 @@
 #include "ctl_dev.h"
 
 // ------------------------------------------------------------------ proof layout (include/zkm_hip.h)
-struct proof_layout {
-    unsigned log_n, lde_bits, L, cap;
-    size_t W, A, Q, Z, F, C, nq;
-    size_t o_init, o_caps, o_open, o_fri_caps, o_final, o_pow, o_queries, query_words, total;
-};
+// (struct proof_layout: zkm_internal.h -- the verifier reads the same layout)
 
 // FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits) (config.rs:25)
 static unsigned fri_num_layers(const zkm_stark_config* c, unsigned degree_bits) {
@@ -64,6 +60,8 @@ static void make_layout(proof_layout& y, const zkm_stark_config* c, unsigned log
     y.query_words = q;
     y.total = o + q * y.nq;
 }
+
+void zkm_proof_layout_make(proof_layout& y, const zkm_stark_config* cfg, unsigned log_n, size_t W, size_t A, size_t Z) { make_layout(y, cfg, log_n, W, A, Z); }
 
 // ------------------------------------------------------------------ K7: quotient evaluation
 // Table constraints live in constraints_dev.h; constraint order = alpha-power order (constraint_consumer.rs:57-62): table
@@ -304,6 +302,30 @@ __global__ __launch_bounds__(256) void k_quotient_ctl_sum(const gl_t* __restrict
     }
 }
 
+// the table's own lookups as the constraint kernels take them (lookup_dev, and the nseg x nalphas lookup challenges in kernel-argument
+// form); returns the number of lookup columns in front of the CTL columns
+static uint32_t table_lookup_args(int table_id, size_t nalphas, const uint64_t* lookup_challenges, size_t nseg, lookup_dev& lookups,
+                                  seg_gl2& lookup_ch) {
+    uint32_t NL = 0;
+    size_t nl = 0;
+    const zkm_table_lookup* defs = zkm_table_lookups(table_id, &nl);
+    if (nl && !lookup_challenges) throw std::runtime_error("zkm_quotient: this table has lookups; lookup challenges are required");
+    if (nl > 2) throw std::runtime_error("zkm_quotient: too many lookups");
+    lookups.nlookups = (uint32_t)nl;
+    lookups.nch = (uint32_t)nalphas;
+    uint32_t off = 0;
+    for (size_t l = 0; l < nl; l++) {
+        if (off + defs[l].ncols > 24) throw std::runtime_error("zkm_quotient: too many lookup columns");
+        lookups.lk[l] = {defs[l].ncols, off, defs[l].table_col, defs[l].freq_col};
+        for (uint32_t i = 0; i < defs[l].ncols; i++) lookups.cols[off + i] = defs[l].cols[i];
+        off += defs[l].ncols;
+        NL += ((defs[l].ncols + 1) / 2 + 1) * (uint32_t)nalphas;
+    }
+    for (size_t sg = 0; nl && sg < nseg; sg++)
+        for (size_t i = 0; i < nalphas; i++) lookup_ch.v[2 * sg + i] = lookup_challenges[sg * nalphas + i];
+    return NL;
+}
+
 // quotient polys: d_out = nalphas x 2n natural-order coefficients (device) -- per segment of the stack (trace / aux: stacked batches of
 // the same nseg; alphas_host: nseg x nalphas; lookup_challenges: nseg x nalphas; own: a description with nseg lists of CtlZData)
 // check = true (zkm_check_constraints): trace / aux describe the VALUES (lde = ncols x n values, rate_bits 0) and d_out receives the
@@ -312,28 +334,10 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
                             const uint64_t* lookup_challenges, const gl_t* alphas_host, size_t nalphas, gl_t* d_out, bool check = false) {
     lookup_dev lookups{};
     seg_gl2 lookup_ch{};
-    uint32_t NL = 0;
     const size_t nseg = trace->nseg;
     if (aux->nseg != nseg || nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_quotient: batches of different stacks");
     const unsigned z = (unsigned)nseg;
-    {
-        size_t nl = 0;
-        const zkm_table_lookup* defs = zkm_table_lookups(table_id, &nl);
-        if (nl && !lookup_challenges) throw std::runtime_error("zkm_quotient: this table has lookups; lookup challenges are required");
-        if (nl > 2) throw std::runtime_error("zkm_quotient: too many lookups");
-        lookups.nlookups = (uint32_t)nl;
-        lookups.nch = (uint32_t)nalphas;
-        uint32_t off = 0;
-        for (size_t l = 0; l < nl; l++) {
-            if (off + defs[l].ncols > 24) throw std::runtime_error("zkm_quotient: too many lookup columns");
-            lookups.lk[l] = {defs[l].ncols, off, defs[l].table_col, defs[l].freq_col};
-            for (uint32_t i = 0; i < defs[l].ncols; i++) lookups.cols[off + i] = defs[l].cols[i];
-            off += defs[l].ncols;
-            NL += ((defs[l].ncols + 1) / 2 + 1) * (uint32_t)nalphas;
-        }
-        for (size_t sg = 0; nl && sg < nseg; sg++)
-            for (size_t i = 0; i < nalphas; i++) lookup_ch.v[2 * sg + i] = lookup_challenges[sg * nalphas + i];
-    }
+    const uint32_t NL = table_lookup_args(table_id, nalphas, lookup_challenges, nseg, lookups, lookup_ch);
     if (zkm_table_width(table_id) == 0 || trace->ncols != zkm_table_width(table_id))
         throw std::runtime_error("zkm_quotient: unknown table id, or the trace width does not match the table");
     if (trace->rate_bits != (check ? 0u : 2u) || aux->rate_bits != trace->rate_bits || trace->log_n != aux->log_n)
@@ -478,6 +482,82 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
     // coset_ifft(g) of each challenge's evaluations (prover.rs:784-788)
     zkm_ntt_natural(c, d_vals, d_out, nseg * nalphas, size, size, log_q, true, GL_GENERATOR);
 }   // (`vals` goes back: stream-ordered reuse, no host sync needed)
+
+// ------------------------------------------------------------------ the verifier's constraint check at zeta (verifier.rs:205-264)
+// The functions above evaluate the constraints over the base field; the verifier needs them at the opened values v = v0 + v1 X in
+// F2 = F[X] / (X^2 - 7).  Every constraint is a polynomial with base-field coefficients (the constraint, CTL and lookup challenges are
+// base-field) of degree <= 3 in the opened values, so c(v0 + t v1) is a polynomial of degree <= 3 in t: it is evaluated at the
+// BASE-FIELD rows v0 + t v1 for t = 0 .. 4 with the same code k_quotient runs, interpolated, and t replaced by X on the host
+// (verify.hip).  The Lagrange / last-row multipliers are F2 values too, and not linear in t: the accumulator is linear in
+// (1, z_last, l_first, l_last), so four consumer settings -- (0,0,0), (1,0,0), (0,1,0), (0,0,1) -- separate the plain, transition,
+// first-row and last-row classes, and the true multipliers are applied after the interpolation.  Thread 4 t + setting of workgroup z
+// handles point t of (segment, table) entry z; the rows are a two-row buffer per point: column c at [2 c] (local) and [2 c + 1] (next).
+struct seg_off { uint64_t v[ZKM_MAX_SEG]; };
+template <int TABLE>
+__global__ __launch_bounds__(64) void k_verify_line(const gl_t* __restrict__ rows, seg_off rows_off, gl_t* __restrict__ acc, seg_off acc_off, uint32_t W,
+                                                    uint32_t A, uint32_t NL, lookup_dev lookups, alpha_args alphas_v, seg_gl2 lookup_ch, ctl_dev ctl) {
+    const unsigned tid = threadIdx.x;
+    if (tid >= ZKM_VERIFY_LINE_THREADS) return;
+    const unsigned t = tid >> 2, setting = tid & 3;
+    const gl_t* const tl = rows + rows_off.v[blockIdx.z] + (size_t)t * 2 * (W + A);
+    const gl_t* const aux = tl + 2 * (size_t)W;
+    consumer_t<2> k;
+#pragma unroll
+    for (int a = 0; a < 2; a++) { k.alpha[a] = alphas_v.v[2 * blockIdx.z + a]; k.acc[a] = 0; }
+    k.z_last = setting == 1 ? 1 : 0;
+    k.l_first = setting == 2 ? 1 : 0;
+    k.l_last = setting == 3 ? 1 : 0;
+    eval_table_constraints<TABLE, 2>(tl, 2, 1, k);
+    if constexpr (TABLE == ZKM_TABLE_MEMORY || TABLE == ZKM_TABLE_ARITHMETIC)
+        eval_lookup_constraints<2>(lookups, lookup_ch.v + 2 * blockIdx.z, tl, 2, aux, 0, 1, k);
+    ctl.zs += (size_t)blockIdx.z * ctl.nzs;
+    eval_ctl_constraints<2>(ctl, tl, 2, 1, aux + 2 * (size_t)NL, 0, 1, k);
+    gl_t* const o = acc + acc_off.v[blockIdx.z] + 2 * tid;
+    o[0] = k.acc[0];
+    o[1] = k.acc[1];
+}
+
+void zkm_verify_line_constraints(zkm_ctx* c, int table_id, size_t nalphas, const ctl_dev& own, size_t naux, const uint64_t* lookup_challenges,
+                                 const gl_t* alphas, const gl_t* d_rows, const uint64_t* rows_off, gl_t* d_acc, const uint64_t* acc_off,
+                                 size_t W, size_t A, size_t nseg) {
+    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("verify: segment count of a constraint launch out of range");
+    if (nalphas < 1 || nalphas > 2) throw std::runtime_error("verify: 1 or 2 challenges supported");
+    if (table_id < 0 || table_id > ZKM_TABLE_CPU || zkm_table_width(table_id) != W) throw std::runtime_error("verify: unknown table id, or the width does not match the table");
+    lookup_dev lookups{};
+    seg_gl2 lookup_ch{};
+    const uint32_t NL = table_lookup_args(table_id, nalphas, lookup_challenges, nseg, lookups, lookup_ch);
+    if (naux + NL != A) throw std::runtime_error("verify: aux column count does not match the CTL description");
+    alpha_args d_alphas{};   // (one challenge: the second accumulator runs with alpha 0 and is ignored)
+    seg_off ro{}, ao{};
+    for (size_t sg = 0; sg < nseg; sg++) {
+        for (size_t a = 0; a < nalphas; a++) d_alphas.v[2 * sg + a] = alphas[sg * nalphas + a];
+        ro.v[sg] = rows_off[sg];
+        ao.v[sg] = acc_off[sg];
+    }
+    static const char* const names[] = {"verify/line_poseidon", "verify/line_logic", "verify/line_keccak_sponge", "verify/line_keccak", "verify/line_memory",
+                                        "verify/line_poseidon_sponge", "verify/line_sha_extend", "verify/line_sha_extend_sponge", "verify/line_sha_compress",
+                                        "verify/line_sha_compress_sponge", "verify/line_arithmetic", "verify/line_cpu"};
+    zkm_prof_scope ps(c, names[table_id]);
+    const dim3 grid(1, 1, (unsigned)nseg), block(64);
+#define ZKM_LAUNCH_LINE(T) \
+    hipLaunchKernelGGL((k_verify_line<T>), grid, block, 0, c->stream, d_rows, ro, d_acc, ao, (uint32_t)W, (uint32_t)A, NL, lookups, d_alphas, lookup_ch, own)
+    switch (table_id) {
+        case ZKM_TABLE_POSEIDON: ZKM_LAUNCH_LINE(ZKM_TABLE_POSEIDON); break;
+        case ZKM_TABLE_LOGIC: ZKM_LAUNCH_LINE(ZKM_TABLE_LOGIC); break;
+        case ZKM_TABLE_KECCAK_SPONGE: ZKM_LAUNCH_LINE(ZKM_TABLE_KECCAK_SPONGE); break;
+        case ZKM_TABLE_KECCAK: ZKM_LAUNCH_LINE(ZKM_TABLE_KECCAK); break;
+        case ZKM_TABLE_MEMORY: ZKM_LAUNCH_LINE(ZKM_TABLE_MEMORY); break;
+        case ZKM_TABLE_POSEIDON_SPONGE: ZKM_LAUNCH_LINE(ZKM_TABLE_POSEIDON_SPONGE); break;
+        case ZKM_TABLE_SHA_EXTEND: ZKM_LAUNCH_LINE(ZKM_TABLE_SHA_EXTEND); break;
+        case ZKM_TABLE_SHA_EXTEND_SPONGE: ZKM_LAUNCH_LINE(ZKM_TABLE_SHA_EXTEND_SPONGE); break;
+        case ZKM_TABLE_SHA_COMPRESS: ZKM_LAUNCH_LINE(ZKM_TABLE_SHA_COMPRESS); break;
+        case ZKM_TABLE_SHA_COMPRESS_SPONGE: ZKM_LAUNCH_LINE(ZKM_TABLE_SHA_COMPRESS_SPONGE); break;
+        case ZKM_TABLE_ARITHMETIC: ZKM_LAUNCH_LINE(ZKM_TABLE_ARITHMETIC); break;
+        default: ZKM_LAUNCH_LINE(ZKM_TABLE_CPU); break;
+    }
+#undef ZKM_LAUNCH_LINE
+    ZKM_HIP_CHECK(hipGetLastError());
+}
 
 // ------------------------------------------------------------------ K10: openings
 // partial[col][chunk] = sum_{k in chunk} c_k z^(k - chunk_start) for z in {zeta, g*zeta}, plus the plain sum (evaluation

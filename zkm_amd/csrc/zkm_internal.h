@@ -102,6 +102,8 @@ struct zkm_ctx {
     std::atomic<int> debug_fail_allocs{0};   // test hook (root context only): pretend the next k hipMalloc first attempts fail
     int check_ctls = 0;                 // the prove drivers run check_ctls on each segment's tables before they prove (ctl_check.hip)   } zkm_ctx_set_tuning
     unsigned debug_ctl_key_bits = 0;    // test hook: the FIRST attempt of a check_ctls call sorts by keys truncated to this many bits (0: off)
+    int verify = 0;                     // the prove drivers verify every segment's blobs before they hand them out (verify.hip)   } zkm_ctx_set_tuning
+    uint64_t debug_verify_flip = 0;     // test hook: under `verify`, this word of one segment's blobs is changed before it is verified (0: off)
     // twiddles
     zkm_twiddles tw;
     // power tables for coset scaling: key (shift, log_n) -> device ptr [lo table 2^h | hi table 2^(log_n-h)]
@@ -160,7 +162,8 @@ struct zkm_ctx {
     hipEvent_t get_event();
     size_t prof_begin(const char* name);   // returns the record's index (scopes nest: a stage scope holds kernel scopes)
     void prof_end(size_t idx);
-    void sync() { ZKM_HIP_CHECK(hipStreamSynchronize(stream)); up_off = 0; }
+    uint64_t host_waits = 0;            // times a thread waited for this context's stream (sync, wait_flag, ensure_down): callers that report their waits read the difference
+    void sync() { host_waits++; ZKM_HIP_CHECK(hipStreamSynchronize(stream)); up_off = 0; }
 };
 
 
@@ -501,6 +504,49 @@ void zkm_arithmetic_write(zkm_arith_job* j, size_t nseg, const unsigned* log_n, 
 // with the reference's message in *msg; throws when the check cannot be made
 int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
                        size_t nctls, zkm_ctl_report* rep, std::string* msg);
+// ---- the verifier (verify.hip; the constraint evaluation on the line through the opening lives beside k_quotient in stark.hip)
+// word offsets of the fields of a proof blob (include/zkm_hip.h); stark.hip fills it in for a validated configuration (throws otherwise)
+struct proof_layout {
+    unsigned log_n, lde_bits, L, cap;
+    size_t W, A, Q, Z, F, C, nq;
+    size_t o_init, o_caps, o_open, o_fri_caps, o_final, o_pow, o_queries, query_words, total;
+};
+void zkm_proof_layout_make(proof_layout& y, const zkm_stark_config* cfg, unsigned log_n, size_t W, size_t A, size_t Z);
+// per-table CtlZData lists in cross_table_lookup_data order (ctl.hip): the prover's derivation, which the verifier replays
+struct table_zs {
+    std::vector<zkm_ctl_z> zs;
+    std::vector<uint32_t> ids;
+    size_t naux = 0;
+};
+std::vector<table_zs> zkm_derive_zs(size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t nch,
+                                    const uint64_t* challenges);
+void zkm_all_stark_table_inputs(zkm_table_input out[12]);   // ctl.hip: the twelve tables of the built-in AllStark (no traces, log_n 0)
+// One (segment, table) of a verify call as the kernels see it: where its blob lies in the call's device block, the blob's validated
+// shape, and what the transcript replay gave.  Every offset was computed on the host from the validated header.
+#define ZKM_VERIFY_LINE_POINTS 5      // constraints are evaluated on the rows v0 + t v1, t = 0 .. 4 (degree <= 3, one point to spare)
+#define ZKM_VERIFY_LINE_THREADS (4 * ZKM_VERIFY_LINE_POINTS)
+struct zkm_verify_table {
+    uint64_t blob;                    // word offset of the blob
+    uint64_t rows;                    // word offset of its line rows: [t][column][local, next], trace columns then auxiliary columns
+    uint32_t log_n, lde_bits, W, A, Q, Z, L, F, nq, cap_height, arity_bits, slots;   // slots: verdict words per query = 4 + 2 L
+    uint32_t o_caps, o_open, o_fri_caps, o_final, o_queries, query_words;
+    uint32_t xs, verdicts;            // first of its nq query indices / of its nq * slots verdict words
+    gl_t zeta[2], zeta_next[2], fri_alpha[2], apow_wa[2], apow_z[2], red_open[3][2], betas[16][2];
+};
+// stark.hip: all constraints of `table_id` on the line rows of nseg <= ZKM_MAX_SEG (segment, table) entries, ONE launch; entry s reads
+// d_rows + rows_off[s] and writes its 20 x 2 accumulators (thread = 4 t + setting, then challenge) to d_acc + acc_off[s].  `own` holds
+// nseg lists of CtlZData (device pointers) for `naux` CTL columns; alphas / lookup_challenges: nseg x nalphas
+struct ctl_dev;
+void zkm_verify_line_constraints(zkm_ctx* c, int table_id, size_t nalphas, const ctl_dev& own, size_t naux, const uint64_t* lookup_challenges,
+                                 const gl_t* alphas, const gl_t* d_rows, const uint64_t* rows_off, gl_t* d_acc, const uint64_t* acc_off,
+                                 size_t W, size_t A, size_t nseg);
+// verify.hip: verify_proof on nseg segments' blobs in ONE set of launches (the body of zkm_verify_segments; the prove drivers call it
+// under "verify"): tables[s] = segment s's table list, proofs[s] / proof_words[s] its blobs, challenges[s] the claimed CTL challenges.
+// Returns the index of the first rejected segment (its report's message in *msg) or nseg when all are accepted; throws when the check
+// cannot be made
+size_t zkm_verify_run(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_table_input* const* tables, size_t ntables,
+                      const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, const uint64_t* const* pub, const size_t* npub,
+                      const uint64_t* const* proofs, const size_t* proof_words, const uint64_t* const* challenges, std::string* msg);
 // ctl.hip: the body of zkm_prove_segments[_columns] (exactly one of traces / columns non-null); seg_base = position of segment 0 in the
 // caller's larger call (csrc/pool.hip deals groups of one pool call to its workers) -- used in error messages only
 extern "C" int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const uint64_t* const* const* traces,
