@@ -54,221 +54,364 @@ void zkm_launch_poseidon_permute(zkm_ctx* c, gl_t* states, size_t k) {
     ZKM_HIP_CHECK(hipGetLastError());
 }
 
-// ------------------------------------------------------------------ Merkle leaves (column-major rows)
-// (every leaf / tree kernel: blockIdx.z = segment of a stacked batch, zkm_internal.h -- its matrix starts lde_seg words, its digest
-// block dig_seg words after the previous segment's)
-// MFMA = true: the MDS layers of the full rounds run on the matrix core (poseidon_mfma_dev.h).  MFMA ignores EXEC, so that form keeps
-// the lanes past the last row alive on the last row's data and only masks their store.
-template <bool MFMA>
-__device__ __forceinline__ void merkle_leaves_body(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride, gl_t* __restrict__ digests,
-                                                   size_t lde_seg, size_t dig_seg) {
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = j < nrows;
-    if (!MFMA && !live) return;
-    if (!live) j = nrows - 1;
-    lde += (size_t)blockIdx.z * lde_seg;
-    digests += (size_t)blockIdx.z * dig_seg;
-    typename std::conditional<MFMA, poseidon_mds_mfma, poseidon_mds_valu>::type mds;
-    if constexpr (MFMA) {
-        mds.A = poseidon_mfma_operand();
-#if ZKM_MFMA_PARK
-        __shared__ uint32_t park[24 * ZKM_MFMA_PARK_STRIDE];
-        mds.park = park + threadIdx.x;
-#endif
+// ------------------------------------------------------------------ leaf sources
+// A source answers "word m of the leaf, and how many words a leaf has" once seek(k) has put it on leaf k of the block's segment (every
+// leaf / tree kernel: blockIdx.z = segment of a stacked batch, zkm_internal.h -- its matrix starts `seg` words, its digest block
+// dig_seg words after the previous segment's).  WHOLE: the word count is a multiple of 8 (no ragged last chunk, and never the short
+// leaf of hash_or_noop).
+// Column-major matrix row: lde[m * col_stride + k] -- a wave's load of one column is contiguous.
+struct leaf_cols {
+    static constexpr bool WHOLE = false;
+    const gl_t* lde;
+    size_t ncols, col_stride, seg;
+    __device__ __forceinline__ void seek(size_t k) { lde += (size_t)blockIdx.z * seg; lde += k; }
+    __device__ __forceinline__ size_t words() const { return ncols; }
+    __device__ __forceinline__ uint64_t word(size_t m) const { return lde[m * col_stride]; }
+};
+// FRI layer: leaf k = arity consecutive F2 values (bit-reversed order), flattened c0,c1,c0,c1.. -- word m of leaf k is component m & 1
+// of value k * arity + (m >> 1).  2 * arity words, arity a multiple of 4 -> whole chunks of 8 words = 4 pairs.
+struct leaf_f2 {
+    static constexpr bool WHOLE = true;
+    const gl_t* c0;
+    const gl_t* c1;
+    unsigned arity;
+    size_t seg;
+    __device__ __forceinline__ void seek(size_t k) {
+        c0 += (size_t)blockIdx.z * seg; c1 += (size_t)blockIdx.z * seg;
+        c0 += k * arity; c1 += k * arity;
     }
-    uint64_t s[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = 0;
-    if (ncols <= 4) {  // hash_or_noop: copy
-        for (size_t c = 0; c < ncols; c++) s[c] = lde[c * col_stride + j];
-    } else {
-        const gl_t* p = lde + j;
-        size_t c = 0;
-        // ONE copy of the round code: the ragged last chunk (it overwrites the words that exist) goes through the same call site.  (Round 5's
-        // 126-register layer needed a second, multiply-add copy for it; at 93 registers it does not, and two copies buy nothing: 39.25
-        // against 39.33 ms, measured.)  Another whole chunk follows: it replaces words 0..7 and only the capacity words are carried over;
-        // before a ragged chunk (it keeps words rem..7) the whole state is needed, at the end the digest.
-        for (; c < ncols; c += 8) {
-            const size_t rem = ncols - c;          // (uniform)
-            if (rem >= 8) {
-                uint64_t v[8];
-#pragma unroll
-                for (int i = 0; i < 8; i++) v[i] = p[(c + i) * col_stride];
-#pragma unroll
-                for (int i = 0; i < 8; i++) s[i] = v[i];
-            } else {
-#pragma unroll
-                for (int i = 0; i < 8; i++)
-                    if ((size_t)i < rem) s[i] = p[(c + i) * col_stride];
-            }
-            poseidon_permute_out_t(s, c + 16 <= ncols ? POSEIDON_OUT_CAPACITY : (c + 8 >= ncols ? POSEIDON_OUT_DIGEST : POSEIDON_OUT_ALL), mds);
+    __device__ __forceinline__ unsigned words() const { return 2 * arity; }
+    __device__ __forceinline__ uint64_t word(unsigned m) const {
+        const gl_t *a = c0, *b = c1;                      // (both read before the choice: a select of two values, not of two fields)
+        return ((m & 1) ? b : a)[m >> 1];
+    }
+};
+
+// ------------------------------------------------------------------ sponge forms
+// One Poseidon state spread over 1, 4 or 16 lanes.  The state -- state_t, this lane's words of it -- is a local array of the routine
+// that runs the sponge (as a member of the form the compiler keeps it in memory; as a local array it stays in registers across the
+// absorb loop); a form is what a lane needs to work on it:
+//   LANES                     lanes per hash
+//   take(n)                   the item of an n-item launch this lane works on (item, live); false: the lane has nothing to do and leaves
+//   clear(s)                  the empty sponge
+//   load<RAGGED>(s, src, c, n) overwrite-mode absorb of words [c, c + 8) of the leaf the source is on; RAGGED: only the words below n exist
+//                             and only those are overwritten
+//   permute(s, out)           one permutation; out = what the caller reads of the result (POSEIDON_OUT_*, a hint)
+//   compress(s, nodes, k, on) two_to_one of node pair k of a level (the eight words at nodes + 8 k) -- the latency forms
+//   store_digest(s, d, k, on) digest k of a level
+// In the latency forms `on` / `live` are uniform over the hash's lanes, and every lane of the wave takes part in every permutation
+// (shuffles / DPP).
+
+// One lane per hash.  MDS = poseidon_mds_mfma: the MDS layers of the full rounds run on the matrix core (poseidon_mfma_dev.h).  MFMA
+// ignores EXEC, so that form keeps the lanes past the last item alive on the last item's data and only masks their store.
+template <class MDS>
+struct sponge_lane {
+    static constexpr unsigned LANES = 1;
+    static constexpr bool MFMA = std::is_same<MDS, poseidon_mds_mfma>::value;
+    typedef uint64_t state_t[12];
+    MDS mds;
+    size_t item;
+    bool live;
+    __device__ __forceinline__ sponge_lane() {
+        if constexpr (MFMA) {
+            mds.A = poseidon_mfma_operand();
+#if ZKM_MFMA_PARK
+            __shared__ uint32_t park[24 * ZKM_MFMA_PARK_STRIDE];
+            mds.park = park + threadIdx.x;
+#endif
         }
     }
-    if (!live) return;
-    uint64_t* d = digests + 4 * j;
-    *reinterpret_cast<ulonglong2*>(d) = make_ulonglong2(s[0], s[1]);
-    *reinterpret_cast<ulonglong2*>(d + 2) = make_ulonglong2(s[2], s[3]);
+    __device__ __forceinline__ bool take(size_t n) {
+        item = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+        live = item < n;
+        if (!MFMA && !live) return false;
+        if (!live) item = n - 1;
+        return true;
+    }
+    __device__ __forceinline__ void clear(state_t& s) const {
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = 0;
+    }
+    template <bool RAGGED, class Src, class I>
+    __device__ __forceinline__ void load(state_t& s, const Src& src, I c, I n) const {
+        if (!RAGGED) {
+            uint64_t v[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) v[i] = src.word(c + i);
+#pragma unroll
+            for (int i = 0; i < 8; i++) s[i] = v[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 8; i++)
+                if ((I)i < n - c) s[i] = src.word(c + i);
+        }
+    }
+    __device__ __forceinline__ void permute(state_t& s, int out) const { poseidon_permute_out_t(s, out, mds); }
+    template <class Src>
+    __device__ __forceinline__ void copy(state_t& s, const Src& src) const {
+        for (size_t c = 0; c < src.words(); c++) s[c] = src.word(c);
+    }
+    template <class K>
+    __device__ __forceinline__ void store_digest(const state_t& s, uint64_t* digests, K k, bool on) const {
+        if (!on) return;
+        uint64_t* d = digests + 4 * k;
+        *reinterpret_cast<ulonglong2*>(d) = make_ulonglong2(s[0], s[1]);
+        *reinterpret_cast<ulonglong2*>(d + 2) = make_ulonglong2(s[2], s[3]);
+    }
+    // the whole state of every item parked in HBM between two launches: state[i * n + item], lane-contiguous
+    __device__ __forceinline__ void load_state(state_t& s, const gl_t* __restrict__ state, size_t n) const {
+#pragma unroll
+        for (int i = 0; i < 12; i++) s[i] = state[(size_t)i * n + item];
+    }
+    __device__ __forceinline__ void store_state(const state_t& s, gl_t* __restrict__ state, size_t n) const {
+        if (!live) return;
+#pragma unroll
+        for (int i = 0; i < 12; i++) state[(size_t)i * n + item] = s[i];
+    }
+};
+
+using sponge_lane_valu = sponge_lane<poseidon_mds_valu>;
+using sponge_lane_mfma = sponge_lane<poseidon_mds_mfma>;
+
+// A quad of lanes per hash (poseidon_lat_dev.h): lane q holds the state words q, q + 4, q + 8, and fetches words c + q and c + 4 + q of
+// its leaf for the absorb step at word c.
+struct sponge_quad {
+    static constexpr unsigned LANES = 4;
+    typedef uint64_t state_t[3];
+    const poseidon_quad Q;
+    const unsigned q;
+    size_t item;
+    bool live;
+    // (every thread of the workgroup builds its form at the same place: the table load ends with a workgroup barrier)
+    __device__ __forceinline__ sponge_quad() : Q(threadIdx.x, table()), q(threadIdx.x & 3) {}
+    static __device__ __forceinline__ const uint32_t* table() {
+        __shared__ __attribute__((aligned(16))) uint32_t qtab[ZKM_QUAD_TAB_WORDS];
+        quad_tab_load(qtab);
+        return qtab;
+    }
+    __device__ __forceinline__ bool take(size_t n) {
+        item = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+        live = item < n;
+        return true;
+    }
+    __device__ __forceinline__ void clear(state_t& s) const { s[0] = s[1] = s[2] = 0; }
+    template <bool RAGGED, class Src, class I>
+    __device__ __forceinline__ void load(state_t& s, const Src& src, I c, I n) const {
+        if (live && (!RAGGED || c + q < n)) s[0] = src.word(c + q);
+        if (live && (!RAGGED || c + 4 + q < n)) s[1] = src.word(c + 4 + q);
+    }
+    __device__ __forceinline__ void permute(state_t& s, int) const { poseidon_permute_quad(s, Q); }
+    template <class K>
+    __device__ __forceinline__ void compress(state_t& s, const uint64_t* nodes, K k, bool on) const {
+        s[0] = on ? nodes[8 * k + q] : 0;
+        s[1] = on ? nodes[8 * k + 4 + q] : 0;
+        s[2] = 0;
+        permute(s, POSEIDON_OUT_DIGEST);
+    }
+    template <class K>
+    __device__ __forceinline__ void store_digest(const state_t& s, uint64_t* digests, K k, bool on) const {
+        if (on) digests[4 * k + q] = s[0];
+    }
+};
+
+// A 16-lane row per hash (poseidon_permute_wide): lanes 0..11 of the row hold the twelve state words, lanes 0..7 fetch the next eight
+// words of their leaf.
+struct sponge_wide {
+    static constexpr unsigned LANES = 16;
+    typedef uint64_t state_t[1];
+    const unsigned lane, idx;
+    size_t item;
+    bool live;
+    __device__ __forceinline__ sponge_wide() : lane(threadIdx.x & 63), idx(lane & 15) {}
+    __device__ __forceinline__ bool take(size_t n) {
+        item = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+        live = item < n;
+        return true;
+    }
+    __device__ __forceinline__ void clear(state_t& s) const { s[0] = 0; }
+    template <bool RAGGED, class Src, class I>
+    __device__ __forceinline__ void load(state_t& s, const Src& src, I c, I n) const {
+        if (live && idx < 8 && (!RAGGED || c + idx < n)) s[0] = src.word(c + idx);
+    }
+    __device__ __forceinline__ void permute(state_t& s, int) const { s[0] = poseidon_permute_wide(s[0], lane); }
+    template <class K>
+    __device__ __forceinline__ void compress(state_t& s, const uint64_t* nodes, K k, bool on) const {
+        s[0] = (on && idx < 8) ? nodes[8 * k + idx] : 0;
+        permute(s, POSEIDON_OUT_DIGEST);
+    }
+    template <class K>
+    __device__ __forceinline__ void store_digest(const state_t& s, uint64_t* digests, K k, bool on) const {
+        if (on && idx < 4) digests[4 * k + idx] = s[0];
+    }
+};
+
+// ------------------------------------------------------------------ Merkle leaves
+// Leaf digests of an n-leaf launch: hash_or_noop of every leaf of the source, bit-exact in every form.
+// CHUNK: leaf hashing in column chunks (pipelined host ingest, core.hip zkm_batch_build): the sponge absorbs eight columns per
+// permutation in column order, so a chunk of columns [c0, c0 + nc) -- c0 a multiple of 8 -- can be absorbed as soon as its LDE
+// exists, with the 12-word sponge state of every row parked in HBM between chunks.  first: the state starts at zero; last: the digest
+// is written instead of the state.  Same permutation sequence as the whole matrix at once, so digests are identical.
+template <class Form, class Src, bool CHUNK = false>
+__device__ __forceinline__ void merkle_leaves_body(Src src, size_t n, gl_t* __restrict__ digests, size_t dig_seg, gl_t* __restrict__ state = nullptr,
+                                                   int first = 1, int last = 1) {
+    Form f;
+    if (!f.take(n)) return;
+    src.seek(f.item);
+    digests += (size_t)blockIdx.z * dig_seg;
+    typename Form::state_t s;
+    if constexpr (CHUNK) {
+        if (first) f.clear(s);
+        else f.load_state(s, state, n);
+    } else {
+        f.clear(s);
+    }
+    const auto nw = src.words();
+    // hash_or_noop: a leaf of <= 4 words is copied, not hashed (the latency forms are only launched for leaves that are hashed; a
+    // chunk is part of a longer leaf)
+    constexpr bool NOOP = Form::LANES == 1 && !CHUNK && !Src::WHOLE;
+    if (NOOP && nw <= 4) {
+        if constexpr (NOOP) f.copy(s, src);               // (only the one-lane form has copy(): the inner test keeps it from being asked of the others)
+    } else {
+        // What the next step needs of a permutation's result: another whole chunk replaces words 0..7 and only the capacity words are carried
+        // over; before a ragged chunk (it keeps words rem..7) the whole state is needed, at the end the digest -- or, where the state is
+        // parked between chunks, the whole, canonical state: the last permutation of such a launch keeps all twelve words.
+        // Whole-matrix kernels: ONE copy of the round code, the ragged last chunk goes through the same call site.  (Round 5's 126-register
+        // layer needed a second, multiply-add copy for it; at 93 registers it does not, and two copies buy nothing: 39.25 against 39.33 ms,
+        // measured.)
+        decltype(src.words()) c = 0;
+        for (; CHUNK ? c + 8 <= nw : c < nw; c += 8) {
+            // (only the one-lane form has a path of its own for a whole chunk: eight loads that do not look at the count -- uniform)
+            if (Src::WHOLE || CHUNK || (Form::LANES == 1 && nw - c >= 8)) f.template load<false>(s, src, c, nw);
+            else f.template load<true>(s, src, c, nw);
+            f.permute(s, c + 16 <= nw ? POSEIDON_OUT_CAPACITY : ((Src::WHOLE || c + 8 >= nw) && !CHUNK ? POSEIDON_OUT_DIGEST : POSEIDON_OUT_ALL));
+        }
+        // CHUNK: the ragged chunk (only legal in the last launch of a row) has a permutation of its own, a second copy of the round code on
+        // the multiply-add form.  The single call site of the whole-matrix kernels has not been timed on the staged path, so the chunk
+        // kernels keep this shape.
+        if constexpr (CHUNK) {
+            if (c < nw) {
+                f.template load<true>(s, src, c, nw);
+                sponge_lane_valu().permute(s, POSEIDON_OUT_ALL);
+            }
+        }
+    }
+    if constexpr (CHUNK) {
+        if (!last) {
+            f.store_state(s, state, n);
+            return;
+        }
+    }
+    f.store_digest(s, digests, f.item, f.live);
 }
+
+#define ZKM_LEAF_MFMA_ATTR __attribute__((amdgpu_waves_per_eu(ZKM_LEAF_MFMA_WAVES, ZKM_LEAF_MFMA_WAVES)))
 
 __global__ __launch_bounds__(256) void k_merkle_leaves(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride,
                                                        gl_t* __restrict__ digests, size_t lde_seg, size_t dig_seg) {
-    merkle_leaves_body<false>(lde, nrows, ncols, col_stride, digests, lde_seg, dig_seg);
+    merkle_leaves_body<sponge_lane_valu>(leaf_cols{lde, ncols, col_stride, lde_seg}, nrows, digests, dig_seg);
 }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZKM_LEAF_MFMA_WAVES, ZKM_LEAF_MFMA_WAVES)))
-void k_merkle_leaves_mfma(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride, gl_t* __restrict__ digests, size_t lde_seg,
-                          size_t dig_seg) {
-    merkle_leaves_body<true>(lde, nrows, ncols, col_stride, digests, lde_seg, dig_seg);
+__global__ __launch_bounds__(256) ZKM_LEAF_MFMA_ATTR void k_merkle_leaves_mfma(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride,
+                                                                              gl_t* __restrict__ digests, size_t lde_seg, size_t dig_seg) {
+    merkle_leaves_body<sponge_lane_mfma>(leaf_cols{lde, ncols, col_stride, lde_seg}, nrows, digests, dig_seg);
+}
+// (a quad of lanes per leaf: launches of at most zkm_ctx::quad_max_hashes leaves, merkle_pick_form)
+__global__ __launch_bounds__(256) void k_merkle_leaves_quad(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride,
+                                                            gl_t* __restrict__ digests, size_t lde_seg, size_t dig_seg) {
+    ZKM_RAISE_PRIO();
+    merkle_leaves_body<sponge_quad>(leaf_cols{lde, ncols, col_stride, lde_seg}, nrows, digests, dig_seg);
+}
+// (a 16-lane row per leaf: launches of at most zkm_ctx::wide_max_hashes leaves, merkle_pick_form)
+__global__ __launch_bounds__(256) void k_merkle_leaves_wide(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride,
+                                                            gl_t* __restrict__ digests, size_t lde_seg, size_t dig_seg) {
+    ZKM_RAISE_PRIO();
+    merkle_leaves_body<sponge_wide>(leaf_cols{lde, ncols, col_stride, lde_seg}, nrows, digests, dig_seg);
 }
 
-__global__ void k_merkle_leaves_quad(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride, gl_t* __restrict__ digests,
-                                     size_t lde_seg, size_t dig_seg);
-__global__ void k_merkle_leaves_wide(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride, gl_t* __restrict__ digests,
-                                     size_t lde_seg, size_t dig_seg);
+__global__ __launch_bounds__(256) void k_merkle_leaves_chunk(const gl_t* __restrict__ lde, size_t nrows, size_t nc, size_t col_stride,
+                                                             gl_t* __restrict__ state, int first, int last, gl_t* __restrict__ digests) {
+    merkle_leaves_body<sponge_lane_valu, leaf_cols, true>(leaf_cols{lde, nc, col_stride, 0}, nrows, digests, 0, state, first, last);
+}
+__global__ __launch_bounds__(256) ZKM_LEAF_MFMA_ATTR void k_merkle_leaves_chunk_mfma(const gl_t* __restrict__ lde, size_t nrows, size_t nc, size_t col_stride,
+                                                                                    gl_t* __restrict__ state, int first, int last, gl_t* __restrict__ digests) {
+    merkle_leaves_body<sponge_lane_mfma, leaf_cols, true>(leaf_cols{lde, nc, col_stride, 0}, nrows, digests, 0, state, first, last);
+}
+
+__global__ __launch_bounds__(256) void k_merkle_leaves_ext(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1,
+                                                           size_t nleaves, unsigned arity, gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
+    merkle_leaves_body<sponge_lane_valu>(leaf_f2{c0, c1, arity, val_seg}, nleaves, digests, dig_seg);
+}
+__global__ __launch_bounds__(256) ZKM_LEAF_MFMA_ATTR void k_merkle_leaves_ext_mfma(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1, size_t nleaves,
+                                                                                  unsigned arity, gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
+    merkle_leaves_body<sponge_lane_mfma>(leaf_f2{c0, c1, arity, val_seg}, nleaves, digests, dig_seg);
+}
+__global__ __launch_bounds__(256) void k_merkle_leaves_ext_quad(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1, size_t nleaves,
+                                                                unsigned arity, gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
+    ZKM_RAISE_PRIO();
+    merkle_leaves_body<sponge_quad>(leaf_f2{c0, c1, arity, val_seg}, nleaves, digests, dig_seg);
+}
+__global__ __launch_bounds__(256) void k_merkle_leaves_ext_wide(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1, size_t nleaves,
+                                                                unsigned arity, gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
+    ZKM_RAISE_PRIO();
+    merkle_leaves_body<sponge_wide>(leaf_f2{c0, c1, arity, val_seg}, nleaves, digests, dig_seg);
+}
+
+// The form of the permutation for a launch of `hashes` hashes (the segments of a stacked batch fill the machine together):
+//   wide: the smallest launches -- 16 lanes per hash, the lowest latency per step of a chain of dependent permutations;
+//   quad: short, wide matrices (Keccak: 2431 columns x a few thousand rows), small FRI layers, the levels near the top of a tree: one
+//         lane per hash leaves the machine empty and pays one permutation's full latency per step; four lanes per hash cut that latency
+//         to a third and fill 4x the lanes;
+//   lane / lane_mfma: one lane per hash, the throughput form; mfma_ok: the launch has a matrix-core kernel (zkm_ctx::leaf_mfma decides).
+// wide_max_hashes = quad_max_hashes = 0: one lane per hash always.
+// wide_max_hashes = 1024.  One absorb step takes ~13 us in the 16-lane form while every SIMD holds at most one such wave (4096 hashes),
+// ~21 us with two (8192), ~41 us with four (16384); the four-lane form takes over there.  Up to 4096 the 16-lane form is the fastest for a
+// context alone, but it spends 4.2x the issue slots of the one-lane form, and with four or more contexts on the GPU those slots are
+// somebody else's work (2^16-cycle segments, 1 / 4 / 8 contexts: 24.5 / 52.5 / 51.8 segments/s at 4096, 25.5 / 56.9 / 59.0 at 1024 --
+// profiles/r03_hw_queues.txt).
+// quad_max_hashes = 32768.  One absorb step takes ~16 us in the quad form while a SIMD holds at most one such wave (16384 hashes = 1024
+// waves; ~21 us with two, 32768), against ~39 us for the one-lane form on a wave that has its SIMD to itself; it costs 1.45x the
+// instructions per hash since its partial rounds are fused (poseidon_lat_dev.h).
+enum merkle_form { MERKLE_LANE, MERKLE_LANE_MFMA, MERKLE_QUAD, MERKLE_WIDE };
+static merkle_form merkle_pick_form(const zkm_ctx* c, size_t hashes, bool mfma_ok) {
+    if (hashes <= c->wide_max_hashes) return MERKLE_WIDE;
+    if (hashes <= c->quad_max_hashes) return MERKLE_QUAD;
+    return mfma_ok && c->leaf_mfma ? MERKLE_LANE_MFMA : MERKLE_LANE;
+}
+// grid of a leaf launch in form f: 256-thread workgroups, one z-slice per segment
+static dim3 leaf_grid(merkle_form f, size_t n, size_t nseg = 1) {
+    static const unsigned lanes[] = {1, 1, 4, 16};
+    return dim3((unsigned)((n * lanes[f] + 255) / 256), 1, (unsigned)nseg);
+}
 
 void zkm_launch_merkle_leaves(zkm_ctx* c, const gl_t* lde, size_t nrows, size_t ncols, size_t col_stride, gl_t* digests, size_t nseg,
                               size_t lde_seg, size_t dig_seg) {
     // rows of <= 4 elements are copied, not hashed (hash_or_noop): profile them under their own name
     zkm_prof_scope ps(c, ncols <= 4 ? "merkle_leaves_copy" : "merkle_leaves");
     if (nseg == 0 || nseg > 65535) throw std::runtime_error("merkle_leaves: bad segment count");
-    const size_t hashes = nrows * nseg;    // the launch's hashes decide the form of the permutation: the segments of a stacked batch fill the machine together
-    const unsigned z = (unsigned)nseg;
-    if (ncols > 4 && hashes <= c->wide_max_hashes)
-        // the shortest matrices: 16 lanes per leaf, the lowest latency per absorb step
-        hipLaunchKernelGGL(k_merkle_leaves_wide, dim3((nrows * 16 + 255) / 256, 1, z), dim3(256), 0, c->stream, lde, nrows, ncols, col_stride, digests,
-                           lde_seg, dig_seg);
-    else if (ncols > 4 && hashes <= c->quad_max_hashes)
-        // short, wide matrices (Keccak: 2431 columns x a few thousand rows): one lane per leaf leaves the machine empty and pays one
-        // permutation's full latency per 8 columns; four lanes per leaf cut that latency to a third and fill 4x the lanes
-        hipLaunchKernelGGL(k_merkle_leaves_quad, dim3((nrows * 4 + 255) / 256, 1, z), dim3(256), 0, c->stream, lde, nrows, ncols, col_stride, digests,
-                           lde_seg, dig_seg);
-    else if (c->leaf_mfma && ncols > 4)
-        hipLaunchKernelGGL(k_merkle_leaves_mfma, dim3((nrows + 255) / 256, 1, z), dim3(256), 0, c->stream, lde, nrows, ncols, col_stride, digests,
-                           lde_seg, dig_seg);
-    else
-        hipLaunchKernelGGL(k_merkle_leaves, dim3((nrows + 255) / 256, 1, z), dim3(256), 0, c->stream, lde, nrows, ncols, col_stride, digests,
-                           lde_seg, dig_seg);
+    static constexpr decltype(&k_merkle_leaves) kernel[] = {k_merkle_leaves, k_merkle_leaves_mfma, k_merkle_leaves_quad, k_merkle_leaves_wide};   // by merkle_form
+    const merkle_form f = ncols > 4 ? merkle_pick_form(c, nrows * nseg, true) : MERKLE_LANE;
+    hipLaunchKernelGGL(kernel[f], leaf_grid(f, nrows, nseg), dim3(256), 0, c->stream, lde, nrows, ncols, col_stride, digests, lde_seg, dig_seg);
     ZKM_HIP_CHECK(hipGetLastError());
-}
-
-// Leaf hashing in column chunks (pipelined host ingest, core.hip zkm_batch_build): the sponge absorbs eight columns per
-// permutation in column order, so a chunk of columns [c0, c0 + nc) -- c0 a multiple of 8 -- can be absorbed as soon as its LDE
-// exists, with the 12-word sponge state of every row parked in HBM between chunks (state[i * nrows + j], lane-contiguous).
-// first: the state starts at zero; last: the digest is written instead of the state.  Same permutation sequence as
-// k_merkle_leaves, so digests are identical.
-template <bool MFMA>
-__device__ __forceinline__ void merkle_leaves_chunk_body(const gl_t* __restrict__ lde, size_t nrows, size_t nc, size_t col_stride,
-                                                         gl_t* __restrict__ state, int first, int last, gl_t* __restrict__ digests) {
-    size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = j < nrows;
-    if (!MFMA && !live) return;
-    if (!live) j = nrows - 1;          // (MFMA ignores EXEC: lanes past the last row hash the last row and store nothing)
-    typename std::conditional<MFMA, poseidon_mds_mfma, poseidon_mds_valu>::type mds;
-    if constexpr (MFMA) {
-        mds.A = poseidon_mfma_operand();
-#if ZKM_MFMA_PARK
-        __shared__ uint32_t park[24 * ZKM_MFMA_PARK_STRIDE];
-        mds.park = park + threadIdx.x;
-#endif
-    }
-    uint64_t s[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = first ? 0 : state[(size_t)i * nrows + j];
-    const gl_t* p = lde + j;
-    size_t c = 0;
-    for (; c + 8 <= nc; c += 8) {
-        uint64_t v[8];
-#pragma unroll
-        for (int i = 0; i < 8; i++) v[i] = p[(c + i) * col_stride];
-#pragma unroll
-        for (int i = 0; i < 8; i++) s[i] = v[i];
-        // (the state parked between chunks is the whole, canonical state: the last permutation of a launch keeps all twelve words)
-        poseidon_permute_out_t(s, c + 16 <= nc ? POSEIDON_OUT_CAPACITY : POSEIDON_OUT_ALL, mds);
-    }
-    if (c < nc) {  // ragged tail: only legal in the last chunk
-        size_t rem = nc - c;
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-            if ((size_t)i < rem) s[i] = p[(c + i) * col_stride];
-        poseidon_permute_out_t(s, POSEIDON_OUT_ALL, poseidon_mds_valu{});   // (the ragged chunk's one permutation: the second copy of the round code stays on the multiply-add form, as in k_merkle_leaves_mfma)
-    }
-    if (!live) return;
-    if (last) {
-        uint64_t* d = digests + 4 * j;
-        *reinterpret_cast<ulonglong2*>(d) = make_ulonglong2(s[0], s[1]);
-        *reinterpret_cast<ulonglong2*>(d + 2) = make_ulonglong2(s[2], s[3]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < 12; i++) state[(size_t)i * nrows + j] = s[i];
-    }
-}
-__global__ __launch_bounds__(256) void k_merkle_leaves_chunk(const gl_t* __restrict__ lde, size_t nrows, size_t nc, size_t col_stride,
-                                                             gl_t* __restrict__ state, int first, int last, gl_t* __restrict__ digests) {
-    merkle_leaves_chunk_body<false>(lde, nrows, nc, col_stride, state, first, last, digests);
-}
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZKM_LEAF_MFMA_WAVES, ZKM_LEAF_MFMA_WAVES)))
-void k_merkle_leaves_chunk_mfma(const gl_t* __restrict__ lde, size_t nrows, size_t nc, size_t col_stride, gl_t* __restrict__ state, int first, int last,
-                                gl_t* __restrict__ digests) {
-    merkle_leaves_chunk_body<true>(lde, nrows, nc, col_stride, state, first, last, digests);
 }
 
 void zkm_launch_merkle_leaves_chunk(zkm_ctx* c, const gl_t* lde, size_t nrows, size_t nc, size_t col_stride, gl_t* state, bool first,
                                     bool last, gl_t* digests) {
     if (!last && nc % 8) throw std::runtime_error("merkle_leaves_chunk: only the last chunk may hold a ragged group of columns");
     zkm_prof_scope ps(c, "merkle_leaves");
-    if (c->leaf_mfma)
-        hipLaunchKernelGGL(k_merkle_leaves_chunk_mfma, dim3((nrows + 255) / 256), dim3(256), 0, c->stream, lde, nrows, nc, col_stride, state,
-                           first ? 1 : 0, last ? 1 : 0, digests);
-    else
-        hipLaunchKernelGGL(k_merkle_leaves_chunk, dim3((nrows + 255) / 256), dim3(256), 0, c->stream, lde, nrows, nc, col_stride, state,
-                           first ? 1 : 0, last ? 1 : 0, digests);
+    hipLaunchKernelGGL(c->leaf_mfma ? k_merkle_leaves_chunk_mfma : k_merkle_leaves_chunk, leaf_grid(MERKLE_LANE, nrows), dim3(256), 0, c->stream, lde, nrows,
+                       nc, col_stride, state, first ? 1 : 0, last ? 1 : 0, digests);
     ZKM_HIP_CHECK(hipGetLastError());
 }
 
-// leaves of a FRI layer: leaf k = arity consecutive F2 values (bit-reversed order), flattened c0,c1,c0,c1..
-// (MFMA: the matrix-core MDS layer of the leaf kernel -- MFMA ignores EXEC: lanes past the last leaf hash the last leaf and do not store)
-template <bool MFMA>
-__device__ __forceinline__ void merkle_leaves_ext_body(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1, size_t nleaves, unsigned arity,
-                                                       gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
-    size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = k < nleaves;
-    if (!MFMA && !live) return;
-    if (!live) k = nleaves - 1;
-    c0 += (size_t)blockIdx.z * val_seg; c1 += (size_t)blockIdx.z * val_seg; digests += (size_t)blockIdx.z * dig_seg;
-    typename std::conditional<MFMA, poseidon_mds_mfma, poseidon_mds_valu>::type mds;
-    if constexpr (MFMA) {
-        mds.A = poseidon_mfma_operand();
-#if ZKM_MFMA_PARK
-        __shared__ uint32_t park[24 * ZKM_MFMA_PARK_STRIDE];
-        mds.park = park + threadIdx.x;
-#endif
-    }
-    uint64_t s[12];
-#pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = 0;
-    const gl_t* a = c0 + k * arity;
-    const gl_t* b = c1 + k * arity;
-    // 2*arity words, arity a multiple of 4 -> whole chunks of 8 words = 4 pairs
-    for (unsigned e = 0; e < arity; e += 4) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            s[2 * i] = a[e + i];
-            s[2 * i + 1] = b[e + i];
-        }
-        poseidon_permute_out_t(s, e + 4 < arity ? POSEIDON_OUT_CAPACITY : POSEIDON_OUT_DIGEST, mds);
-    }
-    if (!live) return;
-    uint64_t* d = digests + 4 * k;
-    *reinterpret_cast<ulonglong2*>(d) = make_ulonglong2(s[0], s[1]);
-    *reinterpret_cast<ulonglong2*>(d + 2) = make_ulonglong2(s[2], s[3]);
-}
-__global__ __launch_bounds__(256) void k_merkle_leaves_ext(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1,
-                                                           size_t nleaves, unsigned arity, gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
-    merkle_leaves_ext_body<false>(c0, c1, nleaves, arity, digests, val_seg, dig_seg);
-}
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ZKM_LEAF_MFMA_WAVES, ZKM_LEAF_MFMA_WAVES)))
-void k_merkle_leaves_ext_mfma(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1, size_t nleaves, unsigned arity, gl_t* __restrict__ digests,
-                              size_t val_seg, size_t dig_seg) {
-    merkle_leaves_ext_body<true>(c0, c1, nleaves, arity, digests, val_seg, dig_seg);
+void zkm_launch_merkle_leaves_ext(zkm_ctx* c, const gl_t* c0, const gl_t* c1, size_t nleaves, unsigned arity, gl_t* digests, size_t nseg,
+                                  size_t val_seg, size_t dig_seg) {
+    if (arity % 4 || 2 * arity <= 4) throw std::runtime_error("merkle_leaves_ext: unsupported arity");
+    if (nseg == 0 || nseg > 65535) throw std::runtime_error("merkle_leaves_ext: bad segment count");
+    zkm_prof_scope ps(c, "merkle_leaves_ext");
+    // (the leaf kernel's matrix-core layer here: layer 0 of a 2^22-row FRI proof 1.70 -> 1.62 ms)
+    static constexpr decltype(&k_merkle_leaves_ext) kernel[] = {k_merkle_leaves_ext, k_merkle_leaves_ext_mfma, k_merkle_leaves_ext_quad, k_merkle_leaves_ext_wide};   // by merkle_form
+    const merkle_form f = merkle_pick_form(c, nleaves * nseg, true);
+    hipLaunchKernelGGL(kernel[f], leaf_grid(f, nleaves, nseg), dim3(256), 0, c->stream, c0, c1, nleaves, arity, digests, val_seg, dig_seg);
+    ZKM_HIP_CHECK(hipGetLastError());
 }
 
 // ------------------------------------------------------------------ Merkle inner levels, fused (K5)
@@ -321,108 +464,51 @@ __global__ __launch_bounds__(256) void k_merkle_fused(merkle_fused_args p) {
         if (tid >= (width >> 1)) return;
     }
 }
-// Small levels, fused: a workgroup (256 threads = 16 hash slots of 16 lanes) owns a subtree with 2^J children (J <= 6) and climbs
-// its J levels through LDS -- ceil(2^(J-k) / 16) rounds of wide permutations at level k -- instead of one launch per level: the top
-// of a tree is a chain of dependent permutations (one wide permutation ~10 us), and every launch boundary added its gap to it.
+
+// Small levels: a workgroup owns a subtree with 2^J children and climbs its J levels through LDS instead of one launch per level: the
+// top of a tree is a chain of dependent permutations (one wide permutation ~10 us), and every launch boundary added its gap to it.
+// The np parents of ONE level of the subtree from their children in LDS (`in`, AoS as in HBM), in ceil(np / slots) rounds of the form's
+// permutations -- slots = threads / LANES hash slots per workgroup, 64 / LANES of them per wave.  A parent goes to LDS (`out`) for the
+// level above, to HBM (`g`: Merkle paths read every level) and, where the caller has one, to a third place (`also`).  The caller puts
+// the workgroup barrier between levels.
+// false: this wave has no node at this level, so none above either -- a kernel with nothing else to do lets it leave (the barrier only
+// counts survivors).
+template <class Form>
+__device__ __forceinline__ bool merkle_climb_level(const Form& f, unsigned slots, unsigned np, const uint64_t* in, uint64_t* out, gl_t* g, uint64_t* also = nullptr) {
+    const unsigned slot = threadIdx.x / Form::LANES, wave_slot0 = (threadIdx.x >> 6) * (64 / Form::LANES);
+    if (wave_slot0 >= np) return false;
+    for (unsigned h0 = 0; h0 < np; h0 += slots) {
+        if (h0 + wave_slot0 >= np) continue;              // (a wave with no live slot in this round skips it -- uniform over the wave)
+        const unsigned h = h0 + slot;
+        const bool on = h < np;                           // uniform over the hash's lanes; every lane of a working wave permutes
+        typename Form::state_t s;
+        f.compress(s, in, h, on);
+        f.store_digest(s, out, h, on);
+        f.store_digest(s, g, h, on);
+        if (also) f.store_digest(s, also, h, on);
+    }
+    return true;
+}
+
+// 16 lanes per hash: 256 threads = 16 hash slots, J <= 6 -- ceil(2^(J-k) / 16) rounds of wide permutations at level k.
 struct merkle_fused_wide_args {
     const gl_t* children;   // level l: nsub * 2^J digests
     gl_t* parents[6];       // levels l + 1 .. l + J
     uint32_t J;             // levels in this launch (1 .. 6)
     size_t dig_seg;
 };
-
-__global__ __launch_bounds__(256) void k_merkle_fused_wide(merkle_fused_wide_args p) {
-    ZKM_RAISE_PRIO();
-    __shared__ uint64_t sh[2][64 * 4];                    // digests of the current level of this subtree (AoS, as in HBM)
-    const unsigned tid = threadIdx.x, lane = tid & 63, idx = lane & 15, slot = tid >> 4;
-    const unsigned C = 1u << p.J;
-    const size_t seg_off = (size_t)blockIdx.z * p.dig_seg;
-    {
-        const gl_t* src = p.children + seg_off + (size_t)blockIdx.x * C * 4;
-        for (unsigned w = tid; w < C * 4; w += 256) sh[0][w] = src[w];
-    }
-    __syncthreads();
-    for (unsigned lvl = 0; lvl < p.J; lvl++) {
-        const unsigned np = C >> (lvl + 1);               // parents of this level in the subtree
-        const uint64_t* in = sh[lvl & 1];
-        uint64_t* out = sh[(lvl + 1) & 1];
-        gl_t* g = p.parents[lvl] + seg_off + (size_t)blockIdx.x * np * 4;
-        if ((slot & ~3u) >= np) return;                  // this wave has no node here or above: leave (the barrier only counts survivors)
-        for (unsigned h0 = 0; h0 < np; h0 += 16) {
-            // (a wave holds four slots; one with no live slot in this round skips it -- uniform over the wave)
-            if (h0 + (slot & ~3u) >= np) continue;
-            const unsigned h = h0 + slot;
-            const bool live = h < np;                     // uniform over the 16-lane row; every lane of the wave shuffles
-            uint64_t x = (live && idx < 8) ? in[8 * h + idx] : 0;
-            x = poseidon_permute_wide(x, lane);
-            if (live && idx < 4) {
-                out[4 * h + idx] = x;
-                g[4 * h + idx] = x;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// Column-major leaves, one leaf per 16-lane row (see poseidon_permute_wide): lanes 0..7 of the row fetch the next eight columns of
-// their leaf (overwrite-mode absorb: a ragged tail overwrites only the words that exist), all 12 lanes permute.  Bit-exact with
-// k_merkle_leaves.  Used when the matrix has at most zkm_ctx::wide_max_hashes rows.
-__global__ __launch_bounds__(256) void k_merkle_leaves_wide(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride,
-                                                            gl_t* __restrict__ digests, size_t lde_seg, size_t dig_seg) {
-    ZKM_RAISE_PRIO();
-    lde += (size_t)blockIdx.z * lde_seg;
-    digests += (size_t)blockIdx.z * dig_seg;
-    const unsigned lane = threadIdx.x & 63, idx = lane & 15;
-    const size_t leaf = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-    const bool live = leaf < nrows;  // uniform over the 16-lane row; every lane of the wave takes part in the shuffles
-    uint64_t x = 0;
-    for (size_t c = 0; c < ncols; c += 8) {
-        if (live && idx < 8 && c + idx < ncols) x = lde[(c + idx) * col_stride + leaf];
-        x = poseidon_permute_wide(x, lane);
-    }
-    if (live && idx < 4) digests[4 * leaf + idx] = x;
-}
-// Rows up to which a leaf gets a 16-lane row (k_merkle_leaves_wide).  One absorb step takes ~13 us in the 16-lane form while every SIMD
-// holds at most one such wave (4096 rows), ~21 us with two (8192), ~41 us with four (16384); the four-lane form takes over there.
-// zkm_ctx::wide_max_hashes = 1024: up to 4096 the 16-lane form is the fastest for a context alone, but it spends 4.2x the issue slots
-// of the one-lane form, and with four or more contexts on the GPU those slots are somebody else's work (2^16-cycle segments, 1 / 4 / 8
-// contexts: 24.5 / 52.5 / 51.8 segments/s at 4096, 25.5 / 56.9 / 59.0 at 1024 -- profiles/r03_hw_queues.txt).
-
-
-// FRI layer leaves, one hash per 16-lane row (small layers): word m of leaf k is component m & 1 of value k * arity + (m >> 1).
-__global__ __launch_bounds__(256) void k_merkle_leaves_ext_wide(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1, size_t nleaves,
-                                                                unsigned arity, gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
-    ZKM_RAISE_PRIO();
-    c0 += (size_t)blockIdx.z * val_seg; c1 += (size_t)blockIdx.z * val_seg; digests += (size_t)blockIdx.z * dig_seg;
-    const unsigned lane = threadIdx.x & 63, idx = lane & 15;
-    const size_t k = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-    const bool live = k < nleaves;
-    const gl_t* col = (idx & 1) ? c1 : c0;
-    uint64_t x = 0;
-    for (unsigned m = 0; m < 2 * arity; m += 8) {
-        if (live && idx < 8) x = col[k * arity + ((m + idx) >> 1)];
-        x = poseidon_permute_wide(x, lane);
-    }
-    if (live && idx < 4) digests[4 * k + idx] = x;
-}
-
-// Small levels, fused: a workgroup (256 threads = 64 hash slots of 4 lanes) owns a subtree with 2^J children (J <= 7) and climbs its J
-// levels through LDS -- ceil(2^(J-k-1) / 64) rounds of quad permutations at level k -- instead of one launch per level: the top of a
-// tree is a chain of dependent permutations, and every launch boundary added its gap to it.
+// four lanes per hash: 256 threads = 64 hash slots, J <= 7 -- ceil(2^(J-k-1) / 64) rounds of quad permutations at level k.
 struct merkle_fused_quad_args {
     const gl_t* children;   // level l: nsub * 2^J digests
     gl_t* parents[7];       // levels l + 1 .. l + J
     uint32_t J;             // levels in this launch (1 .. 7)
     size_t dig_seg;
 };
-
-__global__ __launch_bounds__(256) void k_merkle_fused_quad(merkle_fused_quad_args p) {
-    ZKM_RAISE_PRIO();
-    __shared__ uint64_t sh[2][128 * 4];                   // digests of the current level of this subtree (AoS, as in HBM)
-    const unsigned tid = threadIdx.x, q = tid & 3, slot = tid >> 2, wave_slot0 = (tid >> 6) << 4;
-    __shared__ __attribute__((aligned(16))) uint32_t qtab[ZKM_QUAD_TAB_WORDS];
-    quad_tab_load(qtab);
-    const poseidon_quad Q(tid, qtab);
+template <class Form, unsigned MAXC, class Args>
+__device__ __forceinline__ void merkle_fused_body(const Args& p) {
+    __shared__ uint64_t sh[2][MAXC * 4];                  // digests of the current level of this subtree (AoS, as in HBM)
+    const unsigned tid = threadIdx.x;
+    Form f;
     const unsigned C = 1u << p.J;
     const size_t seg_off = (size_t)blockIdx.z * p.dig_seg;
     {
@@ -432,95 +518,18 @@ __global__ __launch_bounds__(256) void k_merkle_fused_quad(merkle_fused_quad_arg
     __syncthreads();
     for (unsigned lvl = 0; lvl < p.J; lvl++) {
         const unsigned np = C >> (lvl + 1);               // parents of this level in the subtree
-        const uint64_t* in = sh[lvl & 1];
-        uint64_t* out = sh[(lvl + 1) & 1];
-        gl_t* g = p.parents[lvl] + seg_off + (size_t)blockIdx.x * np * 4;
-        if (wave_slot0 >= np) return;                     // this wave has no node here or above: leave (the barrier only counts survivors)
-        for (unsigned h0 = 0; h0 < np; h0 += 64) {
-            if (h0 + wave_slot0 >= np) continue;          // (a wave holds sixteen slots; uniform over the wave)
-            const unsigned h = h0 + slot;
-            const bool live = h < np;                     // uniform over the quad; every lane of the wave takes part in the DPP moves
-            uint64_t s[3] = {live ? in[8 * h + q] : 0, live ? in[8 * h + 4 + q] : 0, 0};
-            poseidon_permute_quad(s, Q);
-            if (live) {
-                out[4 * h + q] = s[0];
-                g[4 * h + q] = s[0];
-            }
-        }
+        if (!merkle_climb_level(f, 256 / Form::LANES, np, sh[lvl & 1], sh[(lvl + 1) & 1], p.parents[lvl] + seg_off + (size_t)blockIdx.x * np * 4))
+            return;                                       // this wave has no node here or above: leave
         __syncthreads();
     }
 }
-
-// Column-major leaves, one leaf per quad: lane q fetches columns c + q and c + 4 + q of its leaf for the absorb step at column c
-// (overwrite-mode absorb: a ragged tail overwrites only the words that exist).  Bit-exact with k_merkle_leaves.  Used when the matrix
-// has at most zkm_ctx::quad_max_hashes rows.
-__global__ __launch_bounds__(256) void k_merkle_leaves_quad(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride,
-                                                            gl_t* __restrict__ digests, size_t lde_seg, size_t dig_seg) {
+__global__ __launch_bounds__(256) void k_merkle_fused_wide(merkle_fused_wide_args p) {
     ZKM_RAISE_PRIO();
-    lde += (size_t)blockIdx.z * lde_seg;
-    digests += (size_t)blockIdx.z * dig_seg;
-    const unsigned q = threadIdx.x & 3;
-    const size_t leaf = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-    const bool live = leaf < nrows;  // uniform over the quad; every lane of the wave takes part in the DPP moves
-    __shared__ __attribute__((aligned(16))) uint32_t qtab[ZKM_QUAD_TAB_WORDS];
-    quad_tab_load(qtab);
-    const poseidon_quad Q(threadIdx.x, qtab);
-    uint64_t s[3] = {0, 0, 0};
-    for (size_t c = 0; c < ncols; c += 8) {
-        if (live && c + q < ncols) s[0] = lde[(c + q) * col_stride + leaf];
-        if (live && c + 4 + q < ncols) s[1] = lde[(c + 4 + q) * col_stride + leaf];
-        poseidon_permute_quad(s, Q);
-    }
-    if (live) digests[4 * leaf + q] = s[0];
+    merkle_fused_body<sponge_wide, 64>(p);
 }
-// Rows up to which a leaf gets a quad of lanes.  One absorb step takes ~16 us in the quad form while a SIMD holds at most one such wave
-// (16384 rows = 1024 waves; ~21 us with two, 32768 rows), against ~39 us for the one-lane form on a wave that has its SIMD to itself;
-// it costs 1.45x the instructions per hash since its partial rounds are fused (poseidon_lat_dev.h; 1.9x and 24 us before that).
-// (zkm_ctx::quad_max_hashes = 32768)
-
-// FRI layer leaves, one hash per quad (small layers): word m of leaf k is component m & 1 of value k * arity + (m >> 1).
-__global__ __launch_bounds__(256) void k_merkle_leaves_ext_quad(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1, size_t nleaves,
-                                                                unsigned arity, gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
+__global__ __launch_bounds__(256) void k_merkle_fused_quad(merkle_fused_quad_args p) {
     ZKM_RAISE_PRIO();
-    c0 += (size_t)blockIdx.z * val_seg; c1 += (size_t)blockIdx.z * val_seg; digests += (size_t)blockIdx.z * dig_seg;
-    const unsigned q = threadIdx.x & 3;
-    const size_t k = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
-    const bool live = k < nleaves;
-    __shared__ __attribute__((aligned(16))) uint32_t qtab[ZKM_QUAD_TAB_WORDS];
-    quad_tab_load(qtab);
-    const poseidon_quad Q(threadIdx.x, qtab);
-    const gl_t* col = (q & 1) ? c1 : c0;                  // words q and q + 4 have the parity of q
-    uint64_t s[3] = {0, 0, 0};
-    for (unsigned m = 0; m < 2 * arity; m += 8) {
-        if (live) {
-            s[0] = col[k * arity + ((m + q) >> 1)];
-            s[1] = col[k * arity + ((m + 4 + q) >> 1)];
-        }
-        poseidon_permute_quad(s, Q);
-    }
-    if (live) digests[4 * k + q] = s[0];
-}
-
-void zkm_launch_merkle_leaves_ext(zkm_ctx* c, const gl_t* c0, const gl_t* c1, size_t nleaves, unsigned arity, gl_t* digests, size_t nseg,
-                                  size_t val_seg, size_t dig_seg) {
-    if (arity % 4 || 2 * arity <= 4) throw std::runtime_error("merkle_leaves_ext: unsupported arity");
-    if (nseg == 0 || nseg > 65535) throw std::runtime_error("merkle_leaves_ext: bad segment count");
-    zkm_prof_scope ps(c, "merkle_leaves_ext");
-    const size_t hashes = nleaves * nseg;
-    const unsigned z = (unsigned)nseg;
-    if (hashes <= c->wide_max_hashes)    // the smallest layers: one hash per 16-lane row
-        hipLaunchKernelGGL(k_merkle_leaves_ext_wide, dim3((nleaves * 16 + 255) / 256, 1, z), dim3(256), 0, c->stream, c0, c1, nleaves, arity, digests,
-                           val_seg, dig_seg);
-    else if (hashes <= c->quad_max_hashes)   // small layers: one hash per quad of lanes
-        hipLaunchKernelGGL(k_merkle_leaves_ext_quad, dim3((nleaves * 4 + 255) / 256, 1, z), dim3(256), 0, c->stream, c0, c1, nleaves, arity, digests,
-                           val_seg, dig_seg);
-    else if (c->leaf_mfma)     // (the leaf kernel's matrix-core layer: layer 0 of a 2^22-row FRI proof 1.70 -> 1.62 ms)
-        hipLaunchKernelGGL(k_merkle_leaves_ext_mfma, dim3((nleaves + 255) / 256, 1, z), dim3(256), 0, c->stream, c0, c1, nleaves, arity, digests, val_seg,
-                           dig_seg);
-    else
-        hipLaunchKernelGGL(k_merkle_leaves_ext, dim3((nleaves + 255) / 256, 1, z), dim3(256), 0, c->stream, c0, c1, nleaves, arity, digests, val_seg,
-                           dig_seg);
-    ZKM_HIP_CHECK(hipGetLastError());
+    merkle_fused_body<sponge_quad, 128>(p);
 }
 
 // ---- a whole small tree in ONE launch, cap delivered to the host by the same launch (VERDICT r03 missing #4)
@@ -542,7 +551,7 @@ struct merkle_tail_args {
 __global__ __launch_bounds__(256) void k_merkle_tail(merkle_tail_args p) {
     ZKM_RAISE_PRIO();
     extern __shared__ __attribute__((aligned(16))) uint64_t tail_lds[];
-    const unsigned tid = threadIdx.x, lane = tid & 63, C = 1u << p.J;
+    const unsigned tid = threadIdx.x, C = 1u << p.J;
     uint64_t* const buf0 = tail_lds;             // C digests
     uint64_t* const buf1 = tail_lds + 4 * C;     // C / 2 digests
     const size_t seg_off = (size_t)blockIdx.z * p.dig_seg;
@@ -552,43 +561,17 @@ __global__ __launch_bounds__(256) void k_merkle_tail(merkle_tail_args p) {
         for (unsigned w = tid; w < C * 4; w += blockDim.x) buf0[w] = src[w];
     }
     __syncthreads();
-    __shared__ __attribute__((aligned(16))) uint32_t qtab[ZKM_QUAD_TAB_WORDS];
-    quad_tab_load(qtab);
-    const poseidon_quad Q(tid, qtab);
+    sponge_quad fq;
+    sponge_wide fw;
     for (unsigned lvl = 0; lvl < p.J; lvl++) {
         const unsigned np = C >> (lvl + 1);
         const uint64_t* in = (lvl & 1) ? buf1 : buf0;
         uint64_t* out = (lvl & 1) ? buf0 : buf1;
         gl_t* g = p.parents[lvl] + seg_off + (size_t)blockIdx.x * np * 4;
-        if (np > p.wide_np_max) {                                  // a quad of lanes per hash: blockDim / 4 hashes per round
-            const unsigned q = tid & 3, slot = tid >> 2, wave_slot0 = (tid >> 6) << 4;
-            for (unsigned h0 = 0; h0 < np; h0 += blockDim.x >> 2) {
-                if (h0 + wave_slot0 >= np) continue;               // (uniform over the wave: every lane of a working wave permutes)
-                const unsigned h = h0 + slot;
-                const bool live = h < np;
-                uint64_t st[3] = {live ? in[8 * h + q] : 0, live ? in[8 * h + 4 + q] : 0, 0};
-                poseidon_permute_quad(st, Q);
-                if (live) {
-                    out[4 * h + q] = st[0];
-                    g[4 * h + q] = st[0];
-                    if (np == 1) host_cap[q] = st[0];
-                }
-            }
-        } else {                                                   // 16 lanes per hash: blockDim / 16 hashes per round
-            const unsigned idx = lane & 15, slot = tid >> 4, wave_slot0 = (tid >> 6) << 2;
-            for (unsigned h0 = 0; h0 < np; h0 += blockDim.x >> 4) {
-                if (h0 + wave_slot0 >= np) continue;
-                const unsigned h = h0 + slot;
-                const bool live = h < np;
-                uint64_t x = (live && idx < 8) ? in[8 * h + idx] : 0;
-                x = poseidon_permute_wide(x, lane);
-                if (live && idx < 4) {
-                    out[4 * h + idx] = x;
-                    g[4 * h + idx] = x;
-                    if (np == 1) host_cap[idx] = x;
-                }
-            }
-        }
+        uint64_t* const also = np == 1 ? host_cap : nullptr;      // the top of the subtree is this workgroup's cap entry
+        // (every wave stays to the end: the ticket below follows a barrier of the whole workgroup)
+        if (np > p.wide_np_max) merkle_climb_level(fq, blockDim.x >> 2, np, in, out, g, also);
+        else merkle_climb_level(fw, blockDim.x >> 4, np, in, out, g, also);
         __syncthreads();
     }
     // every workgroup's cap words are in host memory before its ticket is; the holder of the last ticket publishes
@@ -609,8 +592,8 @@ bool zkm_merkle_tail(zkm_ctx* c, gl_t* digests, const std::vector<size_t>& level
                      unsigned l0, size_t nseg, size_t dig_seg) {
     const unsigned J = log_leaves - l0 - cap_height;
     if (!c->tree_tail || J == 0 || J > 11 || cap_height > 6) return false;
-    // (a first level the tuning gives to the one-lane form -- more parents than both latency thresholds -- stays with the level kernels)
-    if (((size_t)1 << (log_leaves - l0 - 1)) > c->quad_max_hashes && ((size_t)1 << (log_leaves - l0 - 1)) > c->wide_max_hashes) return false;
+    // (a first level the tuning gives to the one-lane form stays with the level kernels)
+    if (merkle_pick_form(c, (size_t)1 << (log_leaves - l0 - 1), false) == MERKLE_LANE) return false;
     // LDS: two level buffers of C and C / 2 digests (6 KB at the usual J = 7, 96 KB at J = 11) next to the static table of the quad form.
     // Only a launch beyond the default 64 KB needs the raised limit; a part that cannot grant it keeps the level kernels.
     const size_t tail_lds = (((size_t)1 << J) * 4 + ((size_t)1 << J) * 2) * sizeof(uint64_t);
@@ -635,7 +618,7 @@ bool zkm_merkle_tail(zkm_ctx* c, gl_t* digests, const std::vector<size_t>& level
     if (threads < 64) threads = 64;
     {
         zkm_prof_scope ps(c, "merkle_compress");
-        hipLaunchKernelGGL(k_merkle_tail, dim3(1u << cap_height, 1, (unsigned)nseg), dim3(threads), (C * 4 + C * 2) * sizeof(uint64_t), c->stream, a);
+        hipLaunchKernelGGL(k_merkle_tail, dim3(1u << cap_height, 1, (unsigned)nseg), dim3(threads), tail_lds, c->stream, a);
         ZKM_HIP_CHECK(hipGetLastError());
     }
     c->xfer_finish(seq, cap_out, capw * 8);
@@ -671,7 +654,9 @@ void zkm_merkle_build_inner(zkm_ctx* c, gl_t* digests, const std::vector<size_t>
         const unsigned log_p1 = log_leaves - l - 1;       // log2(#parents) of the first level made
         const unsigned rem = top - l;
         const size_t p1 = (size_t)1 << log_p1, h1 = p1 * nseg;   // (h1: hashes of the launch's first level over all stacked trees)
-        if (h1 > c->quad_max_hashes && h1 > c->wide_max_hashes && log_p1 >= 8) {   // (the one-lane kernel works on blocks of 256 parents)
+        merkle_form form = merkle_pick_form(c, h1, false);   // (no matrix core here: see below)
+        if (form == MERKLE_LANE && log_p1 < 8) form = MERKLE_QUAD;   // (the one-lane kernel works on blocks of 256 parents)
+        if (form == MERKLE_LANE) {
             merkle_fused_args a{};
             a.dig_seg = dig_seg;
             a.children = digests + level_off[l];
@@ -681,7 +666,7 @@ void zkm_merkle_build_inner(zkm_ctx* c, gl_t* digests, const std::vector<size_t>
             // workgroups per CU -- merkle_compress 1.59 -> 1.72 ms per 262 x 2^20 commitment, lock-step segments 108 -> 106/s: not adopted)
             hipLaunchKernelGGL(k_merkle_fused, dim3((unsigned)(((size_t)1 << log_p1) / 256), 1, z), dim3(256), 0, c->stream, a);
             l += a.levels;
-        } else if (h1 <= c->wide_max_hashes) {
+        } else if (form == MERKLE_WIDE) {
             merkle_fused_wide_args a{};
             a.dig_seg = dig_seg;
             a.children = digests + level_off[l];
@@ -696,7 +681,7 @@ void zkm_merkle_build_inner(zkm_ctx* c, gl_t* digests, const std::vector<size_t>
             a.dig_seg = dig_seg;
             a.children = digests + level_off[l];
             unsigned J = 1;                                  // the levels that are still too large for the 16-lane form (default: 2^14 and 2^13 parents)
-            while (J < rem && J < 7 && J <= log_p1 && (h1 >> J) > c->wide_max_hashes) J++;
+            while (J < rem && J < 7 && J <= log_p1 && merkle_pick_form(c, h1 >> J, false) != MERKLE_WIDE) J++;
             a.J = J;
             for (unsigned k = 0; k < J; k++) a.parents[k] = digests + level_off[l + 1 + k];
             hipLaunchKernelGGL(k_merkle_fused_quad, dim3((unsigned)(((size_t)2 << log_p1) >> J), 1, z), dim3(256), 0, c->stream, a);
