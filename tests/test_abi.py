@@ -1,6 +1,7 @@
 """CPU suite: the C-ABI library loads and exports every symbol include/zkm_hip.h declares; host-side
 transcript code (no GPU needed) agrees with the oracle."""
 import ctypes as C
+import itertools
 import os
 import re
 
@@ -71,7 +72,21 @@ def test_host_permutation_edge_states_match_oracle(zkm, oracle):
         assert zkm.challenger_get(a) == oracle.challenge(b)
 
 
+def fri_num_layers(log_n, rate_bits, cap_height, arity_bits, final_poly_bits):
+    """FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits) (plonky2 fri/reduction_strategies.rs): reduce by
+    arity_bits while the degree is above final_poly_bits and the next layer's tree still reaches down to its cap."""
+    layers, d = 0, log_n
+    while d > final_poly_bits and d + rate_bits - arity_bits >= cap_height:
+        assert d >= arity_bits
+        d -= arity_bits
+        layers += 1
+    return layers
+
+
 def test_proof_layout_sizes_agree(zkm, oracle):
+    """Three statements of the blob's size agree on a grid of configurations, heights and table shapes: zkm_proof_words (from the
+    configuration), the oracle's proof_words, and zkm_proof_get_layout on a header written here.  The public layout's fields tile the
+    blob in the order and with the sizes include/zkm_hip.h states, and so do the fields of a query round."""
     cfg_o = oracle.standard_config()
     cfg = zkm.StarkConfig()
     zkm.load().zkm_standard_config(C.byref(cfg))
@@ -80,6 +95,39 @@ def test_proof_layout_sizes_agree(zkm, oracle):
     lib = zkm.load()
     for log_n in (5, 7, 12, 16, 20, 22):
         assert lib.zkm_proof_words(C.byref(cfg), log_n, 262, 4, 2) == oracle.proof_words(cfg_o, log_n, 262, 4, 2)
+    magic = int.from_bytes(b"FOORPMKZ", "little")          # "ZKMPROOF" read as a big-endian word
+    cases = 0
+    for cap, arity_bits, nq, nch in itertools.product((0, 2, 4), (2, 3, 4), (1, 37), (1, 2)):
+        for c in (cfg, cfg_o):
+            c.cap_height, c.arity_bits, c.num_queries, c.num_challenges, c.final_poly_bits = cap, arity_bits, nq, nch, 5
+        rate = cfg.rate_bits
+        for log_n, (W, A, Z) in itertools.product((2, 5, 6, 9, 10, 13, 16, 22), ((262, 4, 2), (9, 3, 1), (2431, 61, 20))):
+            L = fri_num_layers(log_n, rate, cap, arity_bits, 5)
+            F, Q, C4, lde_bits = 1 << (log_n - L * arity_bits), 2 * nch, 4 << cap, log_n + rate
+            header = np.array([magic, log_n, W, A, Q, Z, cap, L, F, nq, rate, arity_bits, 0, 0, 0, 0], dtype=np.uint64)
+            lay, q = zkm.proof_layout(header)
+            words = lib.zkm_proof_words(C.byref(cfg), log_n, W, A, Z)
+            assert words != 0 and words == oracle.proof_words(cfg_o, log_n, W, A, Z) == lay.total_words, (cap, arity_bits, nq, nch, log_n, W)
+            at = 16
+            for name, size in (("init_challenger_state", 12), ("trace_cap", C4), ("aux_cap", C4), ("quotient_cap", C4), ("local_values", 2 * W),
+                               ("next_values", 2 * W), ("aux_polys", 2 * A), ("aux_polys_next", 2 * A), ("ctl_zs_first", Z),
+                               ("quotient_polys_open", 2 * Q), ("commit_phase_merkle_caps", L * C4), ("final_poly", 2 * F), ("pow_witness", 1),
+                               ("query_round_proofs", nq * lay.query_round_words)):
+                assert getattr(lay, name) == at, (name, cap, arity_bits, nq, nch, log_n, W)
+                at += size
+            assert at == lay.total_words
+            at = 0
+            assert q.initial_siblings == lde_bits - cap
+            for k, cols in enumerate((W, A, Q)):
+                assert (q.oracle_evals[k], q.oracle_cols[k], q.oracle_siblings[k]) == (at, cols, at + cols)
+                at += cols + 4 * (lde_bits - cap)
+            for i in range(L):
+                count = lde_bits - arity_bits * (i + 1) - cap
+                assert (q.layer_evals[i], q.layer_siblings[i], q.layer_siblings_count[i]) == (at, at + (2 << arity_bits), count)
+                at += (2 << arity_bits) + 4 * count
+            assert at == lay.query_round_words
+            cases += 1
+    assert cases == 864
 
 
 def test_all_stark_ctl_inc_is_current():

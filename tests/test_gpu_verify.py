@@ -130,23 +130,38 @@ def ch_key(ch):
     return (list(ch.state), list(ch.in_buf[:ch.n_in]), list(ch.out_buf[:ch.n_out]))
 
 
-def test_single_table_proof_and_the_challenger_it_leaves(ctx, zkm, oracle):
-    log_n = 12
+@pytest.mark.parametrize("log_n", [5, 6, 12])
+def test_single_table_proof_and_the_challenger_it_leaves(ctx, zkm, oracle, log_n):
+    """Under the standard configuration the three heights are the three shapes of a query round: 5 has no FRI layer (and a final
+    polynomial of 32 coefficients), 6 one layer whose tree is already at its cap (no siblings; 4 coefficients), 12 two layers."""
     n = 1 << log_n
     trace = ctx.poseidon_trace(seed=11, num_perms=n - 5, log_n=log_n)
     aux = np.zeros(4 * n, dtype=np.uint64)
     proof = ctx.prove_single_table(trace, log_n, aux, [1, 1])
     trace.free()
+    lay, q = ctx_layout(proof)
+    assert (lay.fri_layers, lay.final_poly_len) == {5: (0, 32), 6: (1, 4), 12: (2, 16)}[log_n]
+    assert log_n != 6 or q.layer_siblings_count[0] == 0
     from oracle.oracle_py import Challenger as OCh
     och, dch = OCh(), zkm.Challenger()
     assert oracle.verify(proof, 4, [1, 1], challenger=och) == 0
     rep = ctx.verify_single_table(proof, [1, 1], challenger=dch)
     judged(rep, 0)
     assert ch_key(och) == ch_key(dch)                    # the transcript stands where the oracle's stands
-    for i in (16 + 12, ctx_layout(proof)[0].local_values + 7, proof.size - 1):
+    # one word of every kind of field, at positions taken from the blob's own layout
+    kinds = {"trace cap word", "local value", "ctl_zs_first word", "quotient opening", "final polynomial word", "pow witness", "FRI cap word",
+             "last word of the last query"}
+    cases = [c for c in tamper_cases(proof, [0, proof.size], 0) if c[0] in kinds] + [("first word of the first query", lay.query_round_proofs, 0, None)]
+    assert len(cases) == 8 + (1 if lay.fri_layers else 0)
+    for name, i, query, layer in cases:
         bad = bumped(proof, i)
         dch2 = zkm.Challenger()
-        judged(ctx.verify_single_table(bad, [1, 1], challenger=dch2), oracle.verify(bad, 4, [1, 1]))
+        code = oracle.verify(bad, 4, [1, 1])
+        print("%-32s" % name, end=" ")
+        rep = ctx.verify_single_table(bad, [1, 1], challenger=dch2)
+        assert code != 0
+        if judged(rep, code)[0] in ("INITIAL_MERKLE", "FRI_EVAL", "FRI_MERKLE") and query is not None:
+            assert rep.query == query
         assert bytes(dch2) == bytes(zkm.Challenger())    # a rejection leaves the caller's challenger alone
 
 

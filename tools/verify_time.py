@@ -5,7 +5,8 @@ oracle's verify_all (the restated sequential verifier, `kind: port`) on the same
 blob per thread -- and against what it follows: zkm_prove_segments of the same 8 segments, and the same call with "verify" at 1.
 Wall clock around calls that end synchronised (a verify call ends in its one download), every shape warmed first, at least a second
 of timed work per figure.  Writes profiles/verify_time.json and prints it.  --one: a single warmed verify call of 8 and nothing else
-(the run to put under a kernel trace)."""
+(the run to put under a kernel trace); --one-prove: the same for the prove call of 8.  --ab: only the figures two builds are compared
+by -- verify of 8, verify of 1, prove of 8 -- printed, nothing written."""
 import json
 import os
 import sys
@@ -47,8 +48,18 @@ def main():
     def verify(k):
         reps = ctx.verify_segments(proofs[:k], [PUB] * k, chals[:k])
         assert all(r.code == 0 and r.host_waits == 1 for r in reps)
+
+    def prove():
+        ctx.prove_segments(segments)
+        ctx.synchronize()
     if "--one" in sys.argv:
         verify(K), verify(K)
+        return
+    if "--one-prove" in sys.argv:
+        prove(), prove()
+        return
+    if "--ab" in sys.argv:
+        print(json.dumps({"verify_segments_8": timed(lambda: verify(K)), "verify_segments_1": timed(lambda: verify(1)), "prove_segments_8": timed(prove)}))
         return
     threads = max(1, min(16, os.cpu_count() or 1, cpu_quota() or 16))
     oracle.set_threads(1)
@@ -56,10 +67,6 @@ def main():
     def cpu():
         with ThreadPoolExecutor(threads) as pool:       # (ctypes releases the GIL for the call)
             assert list(pool.map(lambda i: oracle.verify_all(tables, ctls, proofs[i], chals[i], PUB), range(K))) == [0] * K
-
-    def prove():
-        ctx.prove_segments(segments)
-        ctx.synchronize()
     res = {"segment": {"log_n": lg, "proof_words": int(proofs[0].size)}, "segments": K,
            "verify_segments_8": timed(lambda: verify(K)), "verify_segments_1": timed(lambda: verify(1)),
            "oracle_verify_all_8": dict(timed(cpu), kind="port", threads=threads), "prove_segments_8": timed(prove)}

@@ -1002,16 +1002,9 @@ struct lockstep_call {
         const size_t C4 = (size_t)4 << cfg->cap_height;
         const unsigned nch = cfg->num_challenges;
         ch.resize(nseg);
-        for (auto& x : ch) zkm_challenger_init(&x);
-        for (size_t s = 0; s < nseg; s++) {
-            for (size_t t = 0; t < ntables; t++)   // :182-185
-                zkm_challenger_observe(&ch[s], groups[where[t][s]].commit->cap.data() + pos[t][s] * C4, C4);
-            zkm_challenger_observe(&ch[s], io[s].pub, io[s].npub);  // :187 observe_public_values
-            for (unsigned k = 0; k < nch; k++) {  // :190, beta then gamma (cross_table_lookup.rs:560-566)
-                io[s].challenges[2 * k] = zkm_challenger_get(&ch[s]);
-                io[s].challenges[2 * k + 1] = zkm_challenger_get(&ch[s]);
-            }
-        }
+        for (size_t s = 0; s < nseg; s++)
+            zkm_transcript_seed(&ch[s], ntables, [&](size_t t) { return groups[where[t][s]].commit->cap.data() + pos[t][s] * C4; }, C4, io[s].pub,
+                                io[s].npub, nch, io[s].challenges);
         std::vector<std::vector<table_zs>> tz(nseg);
         for (size_t s = 0; s < nseg; s++) tz[s] = derive_zs(ntables, ctls, sides, nctls, nch, io[s].challenges);
         gzs.assign(groups.size(), {});

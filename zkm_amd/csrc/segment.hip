@@ -27,51 +27,43 @@ extern "C" {
 int zkm_proof_get_layout(const uint64_t* p, zkm_proof_layout* y) {
     if (!p || !y || p[0] != ZKM_PROOF_MAGIC) return 1;
     memset(y, 0, sizeof *y);
-    y->degree_bits = p[1]; y->trace_cols = p[2]; y->aux_cols = p[3]; y->quotient_polys = p[4]; y->ctl_zs = p[5]; y->cap_height = p[6];
-    y->fri_layers = p[7]; y->final_poly_len = p[8]; y->num_queries = p[9]; y->rate_bits = p[10]; y->arity_bits = p[11];
-    if (y->fri_layers > 16 || y->cap_height > 32 || y->degree_bits > 40) return 1;
-    const size_t W = y->trace_cols, A = y->aux_cols, Q = y->quotient_polys, Z = y->ctl_zs, C = (size_t)1 << y->cap_height;
-    size_t o = 16;
-    y->init_challenger_state = o; o += 12;
-    y->trace_cap = o; o += C * 4;
-    y->aux_cap = o; o += C * 4;
-    y->quotient_cap = o; o += C * 4;
-    y->local_values = o; o += 2 * W;
-    y->next_values = o; o += 2 * W;
-    y->aux_polys = o; o += 2 * A;
-    y->aux_polys_next = o; o += 2 * A;
-    y->ctl_zs_first = o; o += Z;
-    y->quotient_polys_open = o; o += 2 * Q;
-    y->commit_phase_merkle_caps = o; o += y->fri_layers * C * 4;
-    y->final_poly = o; o += 2 * y->final_poly_len;
-    y->pow_witness = o; o += 1;
-    y->query_round_proofs = o;
-    zkm_proof_query_layout q;
-    if (zkm_proof_get_query_layout(p, &q)) return 1;
-    const unsigned L = (unsigned)y->fri_layers;
-    y->query_round_words = L ? q.layer_siblings[L - 1] + 4 * q.layer_siblings_count[L - 1] : q.oracle_siblings[2] + 4 * q.initial_siblings;
-    y->total_words = o + y->query_round_words * y->num_queries;
+    const zkm_blob_desc d = zkm_blob_header_read(p);
+    y->degree_bits = d.log_n; y->trace_cols = d.W; y->aux_cols = d.A; y->quotient_polys = d.Q; y->ctl_zs = d.Z; y->cap_height = d.cap_height;
+    y->fri_layers = d.L; y->final_poly_len = d.F; y->num_queries = d.nq; y->rate_bits = d.rate_bits; y->arity_bits = d.arity_bits;
+    if (d.L > ZKM_FRI_HEADER_LAYERS || d.cap_height > 32 || d.log_n > 40) return 1;
+    const auto o = d.openings((size_t)0);
+    y->init_challenger_state = d.o_init();
+    y->trace_cap = d.o_cap(0); y->aux_cap = d.o_cap(1); y->quotient_cap = d.o_cap(2);
+    y->local_values = o.local; y->next_values = o.next;
+    y->aux_polys = o.aux; y->aux_polys_next = o.aux_next;
+    y->ctl_zs_first = o.ctl_zs_first;
+    y->quotient_polys_open = o.quotient;
+    const zkm_fri_part f = d.fri();
+    y->commit_phase_merkle_caps = f.o_cap(0);
+    y->final_poly = f.o_final();
+    y->pow_witness = f.o_pow();
+    y->query_round_proofs = f.o_queries();
+    if (!f.round.fits()) return 1;
+    y->query_round_words = f.round.words();
+    y->total_words = f.total();
     return 0;
 }
 
 int zkm_proof_get_query_layout(const uint64_t* p, zkm_proof_query_layout* q) {
-    if (!p || !q || p[0] != ZKM_PROOF_MAGIC || p[7] > 16) return 1;
+    if (!p || !q || p[0] != ZKM_PROOF_MAGIC || p[7] > ZKM_FRI_HEADER_LAYERS) return 1;
     memset(q, 0, sizeof *q);
-    const size_t cols[3] = {(size_t)p[2], (size_t)p[3], (size_t)p[4]};
-    const size_t lde_bits = p[1] + p[10], cap = p[6], arity_bits = p[11], L = p[7];
-    if (lde_bits < cap) return 1;
-    q->initial_siblings = lde_bits - cap;
-    size_t o = 0;
+    const zkm_query_round r = zkm_blob_header_read(p).round();
+    if (!r.fits()) return 1;
+    q->initial_siblings = r.initial_siblings();
     for (int k = 0; k < 3; k++) {
-        q->oracle_cols[k] = cols[k];
-        q->oracle_evals[k] = o; o += cols[k];
-        q->oracle_siblings[k] = o; o += 4 * q->initial_siblings;
+        q->oracle_cols[k] = r.cols[k];
+        q->oracle_evals[k] = r.oracle_evals(k);
+        q->oracle_siblings[k] = r.oracle_siblings(k);
     }
-    for (size_t i = 0; i < L; i++) {
-        if (lde_bits < arity_bits * (i + 1) + cap) return 1;
-        q->layer_evals[i] = o; o += 2 * ((size_t)1 << arity_bits);
-        q->layer_siblings_count[i] = lde_bits - arity_bits * (i + 1) - cap;
-        q->layer_siblings[i] = o; o += 4 * q->layer_siblings_count[i];
+    for (size_t i = 0; i < r.L; i++) {
+        q->layer_evals[i] = r.layer_evals(i);
+        q->layer_siblings_count[i] = r.layer_sibling_count(i);
+        q->layer_siblings[i] = r.layer_siblings(i);
     }
     return 0;
 }

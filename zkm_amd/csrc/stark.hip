@@ -11,9 +11,7 @@
 #include "constraints_dev.h"
 #include "ctl_dev.h"
 
-// ------------------------------------------------------------------ proof layout (include/zkm_hip.h)
-// (struct proof_layout: zkm_internal.h -- the verifier reads the same layout)
-
+// ------------------------------------------------------------------ proof blob: its description for a configuration (proof_blob.h)
 // FriReductionStrategy::ConstantArityBits(arity_bits, final_poly_bits) (config.rs:25)
 static unsigned fri_num_layers(const zkm_stark_config* c, unsigned degree_bits) {
     unsigned l = 0, d = degree_bits;
@@ -22,8 +20,8 @@ static unsigned fri_num_layers(const zkm_stark_config* c, unsigned degree_bits) 
     return l;
 }
 
-// Every field of the caller's config is checked once, here, before any allocation or transcript mutation (make_layout is the first
-// thing every prove entry point and zkm_proof_words call).  The quotient kernels carry at most two alpha accumulators
+// Every field of the caller's config is checked once, here, before any allocation or transcript mutation (zkm_blob_describe is the
+// first thing every prove entry point and zkm_proof_words call).  The quotient kernels carry at most two alpha accumulators
 // (StarkConfig::num_challenges = 2 in standard_fast_config, config.rs:17-30).
 static void validate_config(const zkm_stark_config* c, unsigned log_n) {
     if (!c) throw std::runtime_error("stark config: null");
@@ -37,31 +35,12 @@ static void validate_config(const zkm_stark_config* c, unsigned log_n) {
     if (c->final_poly_bits > 32) throw std::runtime_error("stark config: final_poly_bits out of range");
 }
 
-static void make_layout(proof_layout& y, const zkm_stark_config* c, unsigned log_n, size_t W, size_t A, size_t Z) {
+zkm_blob_desc zkm_blob_describe(const zkm_stark_config* c, unsigned log_n, size_t W, size_t A, size_t Z) {
     validate_config(c, log_n);
-    y.log_n = log_n; y.lde_bits = log_n + c->rate_bits; y.cap = c->cap_height;
-    y.W = W; y.A = A; y.Q = (size_t)c->num_challenges * 2; y.Z = Z;
-    y.L = fri_num_layers(c, log_n);
-    y.F = (size_t)1 << (log_n - y.L * c->arity_bits);
-    y.C = (size_t)1 << c->cap_height;
-    y.nq = c->num_queries;
-    size_t o = 16;
-    y.o_init = o; o += 12;
-    y.o_caps = o; o += 3 * y.C * 4;
-    y.o_open = o; o += 4 * W + 4 * A + Z + 2 * y.Q;
-    y.o_fri_caps = o; o += y.L * y.C * 4;
-    y.o_final = o; o += 2 * y.F;
-    y.o_pow = o; o += 1;
-    y.o_queries = o;
-    size_t sib0 = (size_t)(y.lde_bits - y.cap) * 4;
-    size_t q = (W + sib0) + (A + sib0) + (y.Q + sib0);
-    for (unsigned i = 0; i < y.L; i++)
-        q += 2 * ((size_t)1 << c->arity_bits) + (size_t)(y.lde_bits - c->arity_bits * (i + 1) - y.cap) * 4;
-    y.query_words = q;
-    y.total = o + q * y.nq;
+    const unsigned L = fri_num_layers(c, log_n);
+    return zkm_blob_desc{log_n, W, A, (size_t)c->num_challenges * 2, Z, c->cap_height, L, (size_t)1 << (log_n - L * c->arity_bits), c->num_queries,
+                         c->rate_bits, c->arity_bits};
 }
-
-void zkm_proof_layout_make(proof_layout& y, const zkm_stark_config* cfg, unsigned log_n, size_t W, size_t A, size_t Z) { make_layout(y, cfg, log_n, W, A, Z); }
 
 // ------------------------------------------------------------------ K7: quotient evaluation
 // Table constraints live in constraints_dev.h; constraint order = alpha-power order (constraint_consumer.rs:57-62): table
@@ -1116,61 +1095,50 @@ __global__ __launch_bounds__(256) void k_pow_search(const pow_state* __restrict_
 // Everything the gather needs travels in the kernel-argument segment (no descriptor / index uploads per table): level l of a tree
 // with 2^log_leaves leaf digests starts at word 4 (2^(log_leaves + 1) - 2^(log_leaves - l + 1)) of its digest array
 // (zkm_merkle_layout), and the query indices are at most ZKM_FRI_MAX_QUERIES words.
-struct gather_oracle { const gl_t* lde; const gl_t* digests; uint32_t ncols, nsib; };
-struct gather_layer { const gl_t *c0, *c1, *digests; uint32_t nsib, log_leaves; };
-#define ZKM_FRI_MAX_ORACLES 8
+// (stacked proofs, blockIdx.y = segment s: its matrix / values and its digests start s * lde_seg / val_seg and s * dig_seg words further)
+struct gather_oracle { const gl_t *lde, *digests; size_t lde_seg, dig_seg; };
+struct gather_layer { const gl_t *c0, *c1, *digests; size_t val_seg, dig_seg; };
 #define ZKM_FRI_MAX_QUERIES 128
 struct gather_args {
     gather_oracle o[ZKM_FRI_MAX_ORACLES];
-    gather_layer l[8];
-    uint32_t noracles, nlayers, arity_bits, lde_bits;
-    uint64_t query_words;
-    // stacked proofs (blockIdx.y = segment): oracle k's matrix / digests of segment s start lde_seg[k] / dig_seg[k] words after segment
-    // s - 1's, layer l's values / digests val_seg[l] / ldig_seg[l] words
-    size_t lde_seg[ZKM_FRI_MAX_ORACLES], dig_seg[ZKM_FRI_MAX_ORACLES], val_seg[8], ldig_seg[8];
+    gather_layer l[ZKM_FRI_GATHER_LAYERS];
+    zkm_query_round round;   // where each piece goes
 };
-struct gather_queries { uint32_t x[ZKM_FRI_MAX_QUERIES]; };   // x < 2^lde_bits <= 2^32
 __device__ __forceinline__ size_t merkle_level_offset(unsigned log_leaves, unsigned lvl) {
     return (((size_t)2 << log_leaves) - ((size_t)2 << (log_leaves - lvl))) * 4;
 }
 __global__ void k_gather_queries(gather_args g, const uint32_t* __restrict__ qs /* [segment][queries] */, gl_t* __restrict__ out) {
+    const zkm_query_round& R = g.round;
     const size_t sg = blockIdx.y;
     uint64_t x = qs[sg * gridDim.x + blockIdx.x];
-    const uint64_t N = (uint64_t)1 << g.lde_bits;
-    gl_t* o = out + (sg * gridDim.x + blockIdx.x) * g.query_words;
-    for (uint32_t k = 0; k < g.noracles; k++) {
-        const gather_oracle& r = g.o[k];
-        const gl_t* lde = r.lde + sg * g.lde_seg[k];
-        const gl_t* dig = r.digests + sg * g.dig_seg[k];
-        for (uint32_t c = threadIdx.x; c < r.ncols; c += blockDim.x) o[c] = lde[(size_t)c * N + x];
-        o += r.ncols;
-        for (uint32_t e = threadIdx.x; e < r.nsib * 4; e += blockDim.x) {
+    const uint32_t lde_bits = (uint32_t)R.lde_bits, arity_bits = (uint32_t)R.arity_bits;
+    const uint64_t N = (uint64_t)1 << lde_bits;
+    gl_t* round = out + (sg * gridDim.x + blockIdx.x) * R.words();
+    for (uint32_t k = 0; k < (uint32_t)R.noracles; k++) {
+        const gl_t *lde = g.o[k].lde + sg * g.o[k].lde_seg, *dig = g.o[k].digests + sg * g.o[k].dig_seg;
+        gl_t *ev = round + R.oracle_evals(k), *sib = round + R.oracle_siblings(k);
+        for (uint32_t c = threadIdx.x; c < (uint32_t)R.cols[k]; c += blockDim.x) ev[c] = lde[(size_t)c * N + x];
+        for (uint32_t e = threadIdx.x; e < (uint32_t)R.initial_siblings() * 4; e += blockDim.x) {
             uint32_t lvl = e >> 2;
-            o[e] = dig[merkle_level_offset(g.lde_bits, lvl) + 4 * ((x >> lvl) ^ 1) + (e & 3)];
+            sib[e] = dig[merkle_level_offset(lde_bits, lvl) + 4 * ((x >> lvl) ^ 1) + (e & 3)];
         }
-        o += r.nsib * 4;
     }
-    uint32_t arity = 1u << g.arity_bits;
-    for (uint32_t l = 0; l < g.nlayers; l++) {
+    uint32_t arity = 1u << arity_bits;
+    for (uint32_t l = 0; l < (uint32_t)R.L; l++) {
         const gather_layer& r = g.l[l];
-        const gl_t *c0 = r.c0 + sg * g.val_seg[l], *c1 = r.c1 + sg * g.val_seg[l], *dig = r.digests + sg * g.ldig_seg[l];
-        x >>= g.arity_bits;
-        for (uint32_t e = threadIdx.x; e < 2 * arity; e += blockDim.x) o[e] = (e & 1) ? c1[x * arity + (e >> 1)] : c0[x * arity + (e >> 1)];
-        o += 2 * arity;
-        for (uint32_t e = threadIdx.x; e < r.nsib * 4; e += blockDim.x) {
+        const gl_t *c0 = r.c0 + sg * r.val_seg, *c1 = r.c1 + sg * r.val_seg, *dig = r.digests + sg * r.dig_seg;
+        const uint32_t nsib = (uint32_t)R.layer_sibling_count(l);
+        gl_t *ev = round + R.layer_evals(l), *sib = round + R.layer_siblings(l);
+        x >>= arity_bits;
+        for (uint32_t e = threadIdx.x; e < 2 * arity; e += blockDim.x) ev[e] = (e & 1) ? c1[x * arity + (e >> 1)] : c0[x * arity + (e >> 1)];
+        for (uint32_t e = threadIdx.x; e < nsib * 4; e += blockDim.x) {
             uint32_t lvl = e >> 2;
-            o[e] = dig[merkle_level_offset(r.log_leaves, lvl) + 4 * ((x >> lvl) ^ 1) + (e & 3)];
+            sib[e] = dig[merkle_level_offset(nsib + (uint32_t)R.cap_height, lvl) + 4 * ((x >> lvl) ^ 1) + (e & 3)];
         }
-        o += r.nsib * 4;
     }
 }
 
 // ------------------------------------------------------------------ host helpers
-static gl2_t challenger_get_ext(zkm_challenger* ch) {
-    gl_t a = zkm_challenger_get(ch), b = zkm_challenger_get(ch);
-    return gl2_t{a, b};
-}
-
 struct fri_layer {
     gl_t* values = nullptr;   // [segment][2][len] bit-reversed
     gl_t* digests = nullptr;  // [segment][dig_words]
@@ -1267,20 +1235,20 @@ static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_
 
 // Everything of a FRI proof after the alpha-combination, for a STACK of independent proofs of the same shape (one proof: vectors of
 // length 1): comps[s] = proof s's composites (pointers: proof 0's; proof s's are s * comp_seg words further), orc = the stacked initial
-// oracles, chs[s] = proof s's transcript, caps_out[s] etc. its output fields.  Every stage is ONE launch (or group of launches) for all
+// oracles, chs[s] = proof s's transcript, blobs[s] its blob, whose FRI fields lie where `part` says.  Every stage is ONE launch (or group of launches) for all
 // proofs, and every transcript round trip brings the words of all of them down together.
 static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, const std::vector<std::vector<fri_composite>>& comps, size_t comp_seg,
-                       const zkm_batch* const* orc, size_t noracles, const std::vector<zkm_challenger*>& chs, unsigned L, size_t F, size_t nq,
-                       size_t query_words, const std::vector<uint64_t*>& caps_out, const std::vector<uint64_t*>& final_out,
-                       const std::vector<uint64_t*>& pow_out, const std::vector<uint64_t*>& queries_out) {
-    if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error("FRI: 1..8 initial oracles");
-    if (L > 8) throw std::runtime_error("too many FRI layers");
+                       const zkm_batch* const* orc, size_t noracles, const std::vector<zkm_challenger*>& chs, const zkm_fri_part& part,
+                       const std::vector<uint64_t*>& blobs) {
+    const zkm_query_round& round = part.round;
+    if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES || round.noracles != noracles) throw std::runtime_error("FRI: 1..8 initial oracles");
+    const unsigned L = (unsigned)round.L;
+    if (L > ZKM_FRI_GATHER_LAYERS) throw std::runtime_error("too many FRI layers");
     const size_t nseg = comps.size();
-    if (nseg == 0 || nseg > ZKM_MAX_SEG || chs.size() != nseg) throw std::runtime_error("FRI: bad stack size");
+    if (nseg == 0 || nseg > ZKM_MAX_SEG || chs.size() != nseg || blobs.size() != nseg) throw std::runtime_error("FRI: bad stack size");
     const unsigned z = (unsigned)nseg;
-    const size_t n = (size_t)1 << log_n, C4 = (size_t)4 << cfg->cap_height;
+    const size_t n = (size_t)1 << log_n, C4 = part.cap_words, nq = part.nq;
     const unsigned lde_bits = log_n + cfg->rate_bits;
-    const size_t N = (size_t)1 << lde_bits;
     std::vector<fri_layer> layers(L);
     zkm_scratch_list scratch(c);   // (the layers' blocks too)
     gl_t* d_fin = scratch.alloc<gl_t>(nseg * 2 * n * sizeof(gl_t));  // final poly coefficients [segment][2][n]
@@ -1308,10 +1276,9 @@ static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, 
         zkm_merkle_build_inner_cap(c, fl.digests, fl.level_off, fl.log_leaves, cfg->cap_height, capbuf.data(), nseg, dwords);
         seg_gl2 betas{};
         for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t* capo = caps_out[sg] + l * C4;
+            uint64_t* capo = blobs[sg] + part.o_cap(l);
             memcpy(capo, capbuf.data() + sg * C4, C4 * sizeof(uint64_t));
-            zkm_challenger_observe(chs[sg], capo, C4);
-            gl2_t beta = challenger_get_ext(chs[sg]);
+            gl2_t beta = zkm_transcript_fri_beta(chs[sg], capo, C4);
             betas.v[2 * sg] = beta.c0; betas.v[2 * sg + 1] = beta.c1;
         }
         size_t nout = clen >> cfg->arity_bits;
@@ -1330,15 +1297,15 @@ static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, 
         clog -= cfg->arity_bits;
         shift = gl_pow(shift, arity);
     }
-    if (clen != F) throw std::runtime_error("internal: final polynomial length mismatch");
+    if (clen != part.F) throw std::runtime_error("internal: final polynomial length mismatch");
     {
         std::vector<gl_t> f(nseg * 2 * clen);
         c->download(f.data(), d_coef, nseg * 2 * clen * 8);
         for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t* fp = final_out[sg];
+            uint64_t* fp = blobs[sg] + part.o_final();
             const gl_t* fs = f.data() + sg * 2 * clen;
             for (size_t i = 0; i < clen; i++) { fp[2 * i] = fs[i]; fp[2 * i + 1] = fs[clen + i]; }
-            zkm_challenger_observe(chs[sg], fp, 2 * clen);
+            zkm_transcript_final_poly(chs[sg], fp, clen);
         }
     }
 
@@ -1380,11 +1347,8 @@ static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, 
                 if (!done.v[sg] && got[sg] != ~0ULL) { best[sg] = got[sg]; done.v[sg] = 1; open--; }
         }
         for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t w = best[sg];
-            *pow_out[sg] = w;
-            zkm_challenger_observe(chs[sg], &w, 1);
-            uint64_t resp = zkm_challenger_get(chs[sg]);
-            if ((resp >> (64 - cfg->pow_bits)) != 0) throw std::runtime_error("internal: proof-of-work response check failed");
+            blobs[sg][part.o_pow()] = best[sg];
+            if (!zkm_transcript_pow(chs[sg], best[sg], cfg->pow_bits)) throw std::runtime_error("internal: proof-of-work response check failed");
         }
     }
 
@@ -1392,26 +1356,19 @@ static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, 
     {
         if (nq > ZKM_FRI_MAX_QUERIES || lde_bits > 32) throw std::runtime_error("FRI: at most 128 query rounds on domains of at most 2^32 points");
         std::vector<uint32_t> qs(nseg * nq);
-        for (size_t sg = 0; sg < nseg; sg++)
-            for (size_t q = 0; q < nq; q++) qs[sg * nq + q] = (uint32_t)(zkm_challenger_get(chs[sg]) % N);
+        for (size_t sg = 0; sg < nseg; sg++) zkm_transcript_query_indices(chs[sg], nq, lde_bits, qs.data() + sg * nq);
         uint32_t* d_qs = scratch.alloc<uint32_t>(qs.size() * sizeof(uint32_t));
         c->upload(d_qs, qs.data(), qs.size() * sizeof(uint32_t));
         gather_args ga{};
-        ga.noracles = (uint32_t)noracles;
+        ga.round = round;
         for (size_t k = 0; k < noracles; k++) {
-            if (orc[k]->lde_bits() != lde_bits || orc[k]->nseg != nseg) throw std::runtime_error("internal: oracle of another domain size in the query gather");
-            ga.o[k].lde = orc[k]->lde; ga.o[k].digests = orc[k]->digests; ga.o[k].ncols = (uint32_t)orc[k]->ncols;
-            ga.o[k].nsib = lde_bits - cfg->cap_height;
-            ga.lde_seg[k] = orc[k]->lde_seg(); ga.dig_seg[k] = orc[k]->dig_words;
+            if (orc[k]->lde_bits() != lde_bits || orc[k]->nseg != nseg || orc[k]->ncols != round.cols[k])
+                throw std::runtime_error("internal: oracle of another shape in the query gather");
+            ga.o[k] = {orc[k]->lde, orc[k]->digests, orc[k]->lde_seg(), orc[k]->dig_words};
         }
-        for (unsigned l = 0; l < L; l++) {
-            ga.l[l].c0 = layers[l].values; ga.l[l].c1 = layers[l].values + layers[l].len; ga.l[l].digests = layers[l].digests;
-            ga.l[l].nsib = layers[l].log_leaves - cfg->cap_height;
-            ga.l[l].log_leaves = layers[l].log_leaves;
-            ga.val_seg[l] = 2 * layers[l].len; ga.ldig_seg[l] = layers[l].dig_words;
-        }
-        ga.nlayers = L; ga.arity_bits = cfg->arity_bits; ga.lde_bits = lde_bits; ga.query_words = query_words;
-        const size_t qwords = nq * query_words;
+        for (unsigned l = 0; l < L; l++)
+            ga.l[l] = {layers[l].values, layers[l].values + layers[l].len, layers[l].digests, 2 * layers[l].len, layers[l].dig_words};
+        const size_t qwords = nq * round.words();
         gl_t* d_q = scratch.alloc<gl_t>(nseg * qwords * 8);
         {
             zkm_prof_scope ps(c, "fri_gather_queries");
@@ -1419,11 +1376,11 @@ static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, 
             ZKM_HIP_CHECK(hipGetLastError());
         }
         if (nseg == 1) {
-            c->download(queries_out[0], d_q, qwords * 8);
+            c->download(blobs[0] + part.o_queries(), d_q, qwords * 8);
         } else {
             std::vector<gl_t> all(nseg * qwords);
             c->download(all.data(), d_q, nseg * qwords * 8);
-            for (size_t sg = 0; sg < nseg; sg++) memcpy(queries_out[sg], all.data() + sg * qwords, qwords * 8);
+            for (size_t sg = 0; sg < nseg; sg++) memcpy(blobs[sg] + part.o_queries(), all.data() + sg * qwords, qwords * 8);
         }
     }
 
@@ -1446,16 +1403,15 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
     const size_t nseg = chs.size();
     if (nseg == 0 || nseg > ZKM_MAX_SEG || proofs.size() != nseg) throw std::runtime_error("prove_single_table: bad stack size");
     if (nseg > 1 && !(aux_given && trace_batch)) throw std::runtime_error("internal: a stack of proofs needs its stacked commitments");
-    validate_config(cfg, log_n);  // before zkm_num_lookup_columns reads it; make_layout checks again
+    validate_config(cfg, log_n);  // before zkm_num_lookup_columns reads it; zkm_blob_describe checks again
     // the table's own lookup helper columns come first among the auxiliary polynomials (prover.rs:467-508)
     const size_t NL = openings_only ? 0 : zkm_num_lookup_columns(table_id, cfg);
     if (NL && !lookup_challenges) throw std::runtime_error("this table has lookups: lookup challenges are required");
     if (NL && !trace && !aux_given) throw std::runtime_error("this table has lookups: the trace values are required to build their helper columns");
     if (!NL) lookup_challenges = nullptr;
     const size_t A = NL + A_ctl;
-    proof_layout y;
-    make_layout(y, cfg, log_n, W, A, Z);
-    if (y.L > 8) throw std::runtime_error("too many FRI layers");
+    const zkm_blob_desc y = zkm_blob_describe(cfg, log_n, W, A, Z);
+    if (y.L > ZKM_FRI_GATHER_LAYERS) throw std::runtime_error("too many FRI layers");
     size_t n = (size_t)1 << log_n;
     if (openings_only) {
         if (Z > A) throw std::runtime_error("zkm_prove_openings: more CTL Zs than auxiliary polynomials");
@@ -1475,9 +1431,8 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
     // (the query rounds -- nine tenths of the blob, 2 MB for the Keccak table -- are written in full by the download at the end of
     // fri_finish: zeroing them here was 0.2 ms of host time per segment in front of the table's first launch)
     for (uint64_t* proof : proofs) {
-        memset(proof, 0, y.o_queries * sizeof(uint64_t));
-        proof[0] = ZKM_PROOF_MAGIC; proof[1] = log_n; proof[2] = W; proof[3] = A; proof[4] = y.Q; proof[5] = Z; proof[6] = y.cap;
-        proof[7] = y.L; proof[8] = y.F; proof[9] = y.nq; proof[10] = cfg->rate_bits; proof[11] = cfg->arity_bits;
+        memset(proof, 0, y.fri().o_queries() * sizeof(uint64_t));
+        zkm_blob_header_write(proof, y);
     }
 
     zkm_scratch_list scratch(c);
@@ -1492,10 +1447,11 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
     if (tb->ncols != W || tb->log_n != log_n || tb->rate_bits != cfg->rate_bits || tb->cap_height != cfg->cap_height || tb->nseg != nseg)
         throw std::runtime_error("trace commitment does not match the table shape / config");
 
-    const size_t C4 = y.C * 4;
+    const size_t C4 = y.cap_words();
+    auto put_cap = [&](size_t sg, unsigned tree, const zkm_batch* b) { memcpy(proofs[sg] + y.o_cap(tree), b->cap.data() + sg * C4, C4 * 8); };
     for (size_t sg = 0; sg < nseg; sg++) {
-        zkm_challenger_compact(chs[sg], proofs[sg] + y.o_init);  // :466
-        memcpy(proofs[sg] + y.o_caps, tb->cap.data() + sg * C4, C4 * 8);
+        zkm_challenger_compact(chs[sg], proofs[sg] + y.o_init());  // :466
+        put_cap(sg, 0, tb);
     }
     const zkm_batch *abp = aux_batch_in, *qbp = quot_batch_in;
     if (aux_given) {
@@ -1529,10 +1485,8 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
     if (!openings_only) {
         std::vector<gl_t> alphas(nseg * cfg->num_challenges);
         for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t* caps = proofs[sg] + y.o_caps;
-            memcpy(caps + C4, abp->cap.data() + sg * C4, C4 * 8);
-            zkm_challenger_observe(chs[sg], caps + C4, C4);  // :525
-            for (unsigned i = 0; i < cfg->num_challenges; i++) alphas[sg * cfg->num_challenges + i] = zkm_challenger_get(chs[sg]);  // :527
+            put_cap(sg, 1, abp);
+            zkm_transcript_alphas(chs[sg], y, proofs[sg], cfg->num_challenges, alphas.data() + sg * cfg->num_challenges);
         }
 
         // quotient :543-587
@@ -1546,28 +1500,20 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
             zkm_prof_scope st(c, "stage/compute quotient commitment");  // :576-587
             zkm_batch_build(qb.get(), d_quot, false);  // chunks [q0_lo, q0_hi, q1_lo, q1_hi] == d_quot viewed as Q columns of n, proof after proof
         }
-        for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t* caps = proofs[sg] + y.o_caps;
-            memcpy(caps + 2 * C4, qb->cap.data() + sg * C4, C4 * 8);
-            zkm_challenger_observe(chs[sg], caps + 2 * C4, C4);  // :589
-        }
         qbp = qb.get();
     } else {
         for (const zkm_batch* b : {abp, qbp})
             if (!b || b->log_n != log_n || b->rate_bits != cfg->rate_bits || b->cap_height != cfg->cap_height || b->nseg != nseg)
                 throw std::runtime_error("zkm_prove_openings: commitments do not match the table shape / config");
         if (abp->ncols != A || qbp->ncols != y.Q) throw std::runtime_error("zkm_prove_openings: unexpected number of polynomials");
-        for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t* caps = proofs[sg] + y.o_caps;
-            memcpy(caps + C4, abp->cap.data() + sg * C4, C4 * 8);
-            memcpy(caps + 2 * C4, qbp->cap.data() + sg * C4, C4 * 8);
-        }
+        for (size_t sg = 0; sg < nseg; sg++) put_cap(sg, 1, abp);
     }
 
     std::vector<gl2_t> zeta(nseg), zeta_next(nseg);
     gl_t g = gl_root_of_unity(log_n);
     for (size_t sg = 0; sg < nseg; sg++) {
-        zeta[sg] = challenger_get_ext(chs[sg]);  // :591
+        put_cap(sg, 2, qbp);   // (openings-only: the transcript goes from the compacted state straight to zeta)
+        zeta[sg] = openings_only ? zkm_challenger_get_ext(chs[sg]) : zkm_transcript_zeta(chs[sg], y, proofs[sg]);
         if (gl2_eq(gl2_exp_pow2(zeta[sg], log_n), gl2_t{1, 0})) throw std::runtime_error("Opening point is in the subgroup.");  // :596-599
         zeta_next[sg] = gl2_scalar_mul(zeta[sg], g);
     }
@@ -1577,19 +1523,18 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
         zkm_prof_scope st(c, "stage/openings (StarkOpeningSet::new)");  // proof.rs:299-334, between two timed! scopes in the reference
         auto ev = eval_batches(c, {tb, abp, qbp}, zeta.data(), zeta_next.data());
         for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t* op = proofs[sg] + y.o_open;
-            uint64_t *o_local = op, *o_next = op + 2 * W, *o_aux = op + 4 * W, *o_auxn = o_aux + 2 * A, *o_ctl = o_auxn + 2 * A, *o_quot = o_ctl + Z;
+            const auto o = y.openings(proofs[sg]);
             const auto &tv = ev[sg][0], &av = ev[sg][1], &qv = ev[sg][2];
             for (size_t i = 0; i < W; i++) {
-                o_local[2 * i] = tv[i].at_z0.c0; o_local[2 * i + 1] = tv[i].at_z0.c1;
-                o_next[2 * i] = tv[i].at_z1.c0; o_next[2 * i + 1] = tv[i].at_z1.c1;
+                o.local[2 * i] = tv[i].at_z0.c0; o.local[2 * i + 1] = tv[i].at_z0.c1;
+                o.next[2 * i] = tv[i].at_z1.c0; o.next[2 * i + 1] = tv[i].at_z1.c1;
             }
             for (size_t i = 0; i < A; i++) {
-                o_aux[2 * i] = av[i].at_z0.c0; o_aux[2 * i + 1] = av[i].at_z0.c1;
-                o_auxn[2 * i] = av[i].at_z1.c0; o_auxn[2 * i + 1] = av[i].at_z1.c1;
-                if (i >= total_helpers) o_ctl[i - total_helpers] = av[i].at_one;
+                o.aux[2 * i] = av[i].at_z0.c0; o.aux[2 * i + 1] = av[i].at_z0.c1;
+                o.aux_next[2 * i] = av[i].at_z1.c0; o.aux_next[2 * i + 1] = av[i].at_z1.c1;
+                if (i >= total_helpers) o.ctl_zs_first[i - total_helpers] = av[i].at_one;
             }
-            for (size_t i = 0; i < y.Q; i++) { o_quot[2 * i] = qv[i].at_z0.c0; o_quot[2 * i + 1] = qv[i].at_z0.c1; }
+            for (size_t i = 0; i < y.Q; i++) { o.quotient[2 * i] = qv[i].at_z0.c0; o.quotient[2 * i + 1] = qv[i].at_z0.c1; }
         }
     }
     // ---- prove_openings (App. A.8)
@@ -1597,17 +1542,7 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
     const size_t np0 = W + A + y.Q, np1 = W + A, np2 = Z, apow_seg = 2 * (np0 + 1);
     std::vector<gl_t> apow(nseg * apow_seg);
     for (size_t sg = 0; sg < nseg; sg++) {
-        zkm_challenger* ch = chs[sg];
-        uint64_t* op = proofs[sg] + y.o_open;
-        uint64_t *o_local = op, *o_next = op + 2 * W, *o_aux = op + 4 * W, *o_auxn = o_aux + 2 * A, *o_ctl = o_auxn + 2 * A, *o_quot = o_ctl + Z;
-        // observe_openings(to_fri_openings) proof.rs:336-367
-        zkm_challenger_observe(ch, o_local, 2 * W);
-        zkm_challenger_observe(ch, o_aux, 2 * A);
-        zkm_challenger_observe(ch, o_quot, 2 * y.Q);
-        zkm_challenger_observe(ch, o_next, 2 * W);
-        zkm_challenger_observe(ch, o_auxn, 2 * A);
-        for (size_t i = 0; i < Z; i++) { uint64_t e[2] = {o_ctl[i], 0}; zkm_challenger_observe(ch, e, 2); }
-        gl2_t alpha = challenger_get_ext(ch);
+        gl2_t alpha = zkm_transcript_fri_alpha(chs[sg], y, proofs[sg]);
         gl2_t p{1, 0};
         gl_t* ap = apow.data() + sg * apow_seg;
         for (size_t j = 0; j <= np0; j++) { ap[2 * j] = p.c0; ap[2 * j + 1] = p.c1; p = gl2_mul(p, alpha); }
@@ -1646,17 +1581,14 @@ static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config*
     // divide by (X - point), accumulate, commit phase, proof of work, query rounds: shared with zkm_fri_prove
     {
         std::vector<std::vector<fri_composite>> comps(nseg);
-        std::vector<uint64_t*> caps_o(nseg), final_o(nseg), pow_o(nseg), queries_o(nseg);
         for (size_t sg = 0; sg < nseg; sg++) {
             const gl_t* ap = apow.data() + sg * apow_seg;
             comps[sg] = {{d_comp, d_comp + n, zeta[sg], gl2_t{ap[2 * np0], ap[2 * np0 + 1]}},
                          {d_comp + 2 * n, d_comp + 3 * n, zeta_next[sg], gl2_t{ap[2 * np1], ap[2 * np1 + 1]}},
                          {d_comp + 4 * n, d_comp + 5 * n, gl2_t{1, 0}, gl2_t{ap[2 * np2], ap[2 * np2 + 1]}}};
-            caps_o[sg] = proofs[sg] + y.o_fri_caps; final_o[sg] = proofs[sg] + y.o_final; pow_o[sg] = proofs[sg] + y.o_pow;
-            queries_o[sg] = proofs[sg] + y.o_queries;
         }
         const zkm_batch* orc[3] = {tb, abp, qbp};
-        fri_finish(c, cfg, log_n, comps, 6 * n, orc, 3, chs, y.L, y.F, y.nq, y.query_words, caps_o, final_o, pow_o, queries_o);
+        fri_finish(c, cfg, log_n, comps, 6 * n, orc, 3, chs, y.fri(), proofs);
     }
 }
 
@@ -1691,27 +1623,15 @@ __global__ __launch_bounds__(256) void k_fri_combine_generic(const gl_t* const* 
     c1[i] = a1;
 }
 
-struct fri_blob_layout {
-    unsigned L;
-    size_t F, C4, o_caps, o_final, o_pow, o_queries, query_words, total;
-};
-static void fri_blob_make(fri_blob_layout& y, const zkm_stark_config* cfg, unsigned log_n, const size_t* cols, size_t noracles) {
+// the FRI-only blob of zkm_fri_prove: 24 header words (its own magic, the oracles' column counts from word 16), then the FRI part
+static zkm_fri_part fri_blob_describe(const zkm_stark_config* cfg, unsigned log_n, const size_t* cols, size_t noracles) {
     validate_config(cfg, log_n);
     if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error("zkm_fri_prove: 1..8 oracles");
-    y.L = fri_num_layers(cfg, log_n);
-    y.F = (size_t)1 << (log_n - y.L * cfg->arity_bits);
-    y.C4 = (size_t)4 << cfg->cap_height;
-    const unsigned lde_bits = log_n + cfg->rate_bits;
-    size_t o = 24;
-    y.o_caps = o; o += y.L * y.C4;
-    y.o_final = o; o += 2 * y.F;
-    y.o_pow = o; o += 1;
-    y.o_queries = o;
-    size_t q = 0;
-    for (size_t k = 0; k < noracles; k++) q += cols[k] + (size_t)(lde_bits - cfg->cap_height) * 4;
-    for (unsigned i = 0; i < y.L; i++) q += 2 * ((size_t)1 << cfg->arity_bits) + (size_t)(lde_bits - cfg->arity_bits * (i + 1) - cfg->cap_height) * 4;
-    y.query_words = q;
-    y.total = o + q * cfg->num_queries;
+    const unsigned L = fri_num_layers(cfg, log_n);
+    zkm_fri_part y{24, (size_t)4 << cfg->cap_height, (size_t)1 << (log_n - L * cfg->arity_bits), cfg->num_queries,
+                   zkm_query_round{{}, noracles, L, log_n + cfg->rate_bits, cfg->cap_height, cfg->arity_bits}};
+    std::copy(cols, cols + noracles, y.round.cols);
+    return y;
 }
 
 // parity / debug: a b mod p through THIS translation unit's gl_mul_loose (GL_REDUCE_BRANCHFREE), for zkm_field_selftest
@@ -1727,8 +1647,8 @@ void zkm_launch_mul_selftest_branchfree(zkm_ctx* c, const uint64_t* a, const uin
 extern "C" {
 
 size_t zkm_fri_proof_words(const zkm_stark_config* cfg, unsigned log_n, const size_t* oracle_cols, size_t noracles) {
-    fri_blob_layout y;
-    return zkm_api("zkm_fri_proof_words", nullptr, [&] { fri_blob_make(y, cfg, log_n, oracle_cols, noracles); }) ? 0 : y.total;
+    zkm_fri_part y{};   // (0 = unsupported configuration)
+    return zkm_api("zkm_fri_proof_words", nullptr, [&] { y = fri_blob_describe(cfg, log_n, oracle_cols, noracles); }) ? 0 : y.total();
 }
 
 int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles, const zkm_fri_batch* batches,
@@ -1747,8 +1667,7 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
                 throw std::runtime_error("zkm_fri_prove: oracles must share degree, rate and cap height with the config");
             cols[k] = oracles[k]->ncols;
         }
-        fri_blob_layout y;
-        fri_blob_make(y, cfg, log_n, cols, noracles);
+        const zkm_fri_part y = fri_blob_describe(cfg, log_n, cols, noracles);
         const size_t n = (size_t)1 << log_n;
         size_t maxp = 0;
         for (size_t b = 0; b < nbatches; b++) {
@@ -1759,12 +1678,12 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
                     throw std::runtime_error("zkm_fri_prove: polynomial index out of range");
             maxp = std::max(maxp, batches[b].npolys);
         }
-        memset(proof, 0, y.total * sizeof(uint64_t));
-        proof[0] = ZKM_FRI_PROOF_MAGIC; proof[1] = log_n; proof[2] = noracles; proof[3] = cfg->cap_height; proof[4] = y.L; proof[5] = y.F;
+        memset(proof, 0, y.total() * sizeof(uint64_t));
+        proof[0] = ZKM_FRI_PROOF_MAGIC; proof[1] = log_n; proof[2] = noracles; proof[3] = cfg->cap_height; proof[4] = y.round.L; proof[5] = y.F;
         proof[6] = cfg->num_queries; proof[7] = cfg->rate_bits; proof[8] = cfg->arity_bits;
         for (size_t k = 0; k < noracles; k++) proof[16 + k] = cols[k];
 
-        gl2_t alpha = challenger_get_ext(ch);
+        gl2_t alpha = zkm_challenger_get_ext(ch);
         std::vector<gl_t> apow(2 * (maxp + 1));
         {
             gl2_t pw{1, 0};
@@ -1800,8 +1719,7 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
         ZKM_HIP_CHECK(hipStreamSynchronize(c->stream));  // host vectors (ptrs, apow) are consumed
         for (size_t k = 0; k < noracles; k++)
             if (oracles[k]->nseg != 1) throw std::runtime_error("zkm_fri_prove: stacked batches are internal");
-        fri_finish(c, cfg, log_n, comps_v, 0, oracles, noracles, {ch}, y.L, y.F, cfg->num_queries, y.query_words, {proof + y.o_caps}, {proof + y.o_final},
-                   {proof + y.o_pow}, {proof + y.o_queries});
+        fri_finish(c, cfg, log_n, comps_v, 0, oracles, noracles, {ch}, y, {proof});
         *ch_io = local;
     });
 }
@@ -1811,8 +1729,8 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
 extern "C" {
 
 size_t zkm_proof_words(const zkm_stark_config* cfg, unsigned log_n, size_t ncols, size_t naux, size_t nctl_zs) {
-    proof_layout y;   // (0 = unsupported configuration: the prove entry points report which field)
-    return zkm_api("zkm_proof_words", nullptr, [&] { make_layout(y, cfg, log_n, ncols, naux, nctl_zs); }) ? 0 : y.total;
+    zkm_blob_desc y{};   // (0 = unsupported configuration: the prove entry points report which field)
+    return zkm_api("zkm_proof_words", nullptr, [&] { y = zkm_blob_describe(cfg, log_n, ncols, naux, nctl_zs); }) ? 0 : y.total();
 }
 
 // CtlZData of the benchmark's fake CTL shape: helper columns, no column sets (poseidon_stark.rs:786-799)

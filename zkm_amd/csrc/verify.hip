@@ -17,6 +17,7 @@
 //   verify/reduce         first finding per (segment, table) in the fixed order
 // behind ONE upload (the parameter block with every CTL description, then the blobs) and before ONE download: the constraint
 // accumulators and the reduced verdicts.  The quotient comparison is finished on the host.
+#include <iterator>
 #include <memory>
 
 #include "ctl_dev.h"
@@ -27,11 +28,11 @@ namespace {
 // ------------------------------------------------------------------ kernels
 __global__ __launch_bounds__(256) void k_verify_rows(const zkm_verify_table* __restrict__ tabs, const gl_t* __restrict__ blobs, gl_t* __restrict__ rows) {
     const zkm_verify_table& T = tabs[blockIdx.y];
-    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x, W = T.W, A = T.A;
+    const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x, W = (uint32_t)T.d.W, A = (uint32_t)T.d.A;
     if (c >= W + A) return;
-    const gl_t* op = blobs + T.blob + T.o_open;
-    const gl_t* l = c < W ? op + 2 * (size_t)c : op + 4 * (size_t)W + 2 * (size_t)(c - W);
-    const gl_t* n = l + 2 * (size_t)(c < W ? W : A);
+    const auto o = T.d.openings(blobs + T.blob);
+    const gl_t* l = c < W ? o.local + 2 * (size_t)c : o.aux + 2 * (size_t)(c - W);
+    const gl_t* n = c < W ? o.next + 2 * (size_t)c : o.aux_next + 2 * (size_t)(c - W);
     gl_t l0 = l[0], n0 = n[0];
     const gl_t l1 = l[1], n1 = n[1];
     gl_t* out = rows + T.rows + 2 * (size_t)c;
@@ -53,30 +54,29 @@ struct chain_t {
 };
 __device__ __forceinline__ bool chain_setup(const zkm_verify_table& T, const gl_t* __restrict__ blobs, const uint32_t* __restrict__ xs, uint32_t idx,
                                             chain_t& ch) {
-    if (idx >= T.nq * (3 + T.L)) return false;
-    const uint32_t tree = idx / T.nq, q = idx - tree * T.nq;
+    const uint32_t nq = (uint32_t)T.d.nq;
+    if (idx >= nq * (3 + (uint32_t)T.d.L)) return false;
+    const uint32_t tree = idx / nq, q = idx - tree * nq;
     const uint32_t x = xs[T.xs + q];
     const gl_t* blob = blobs + T.blob;
-    const gl_t* qr = blob + T.o_queries + (size_t)q * T.query_words;
-    const uint32_t sib0 = T.lde_bits - T.cap_height, C4 = 4u << T.cap_height;
+    const zkm_fri_part P = T.d.fri();
+    const zkm_query_round& R = P.round;
+    const gl_t* qr = blob + P.o_query(q);
     uint32_t slot;
     if (tree < 3) {
-        const uint32_t before = tree == 0 ? 0 : tree == 1 ? T.W + 4 * sib0 : T.W + T.A + 8 * sib0;
-        ch.len = tree == 0 ? T.W : tree == 1 ? T.A : T.Q;
-        ch.leaf = qr + before;
-        ch.nsib = sib0;
+        ch.len = (uint32_t)(tree == 0 ? R.cols[0] : tree == 1 ? R.cols[1] : R.cols[2]);
+        ch.leaf = qr + (tree == 0 ? R.oracle_evals(0) : tree == 1 ? R.oracle_evals(1) : R.oracle_evals(2));
+        ch.nsib = (uint32_t)R.initial_siblings();
         ch.index = x;
-        ch.cap = blob + T.o_caps + (size_t)tree * C4;
+        ch.cap = blob + T.d.o_cap(tree);
         slot = tree;
     } else {
-        const uint32_t l = tree - 3, arity2 = 2u << T.arity_bits;
-        uint32_t off = T.W + T.A + T.Q + 12 * sib0;
-        for (uint32_t i = 0; i < l; i++) off += arity2 + 4 * (T.lde_bits - T.arity_bits * (i + 1) - T.cap_height);
-        ch.len = arity2;
-        ch.leaf = qr + off;
-        ch.nsib = T.lde_bits - T.arity_bits * (l + 1) - T.cap_height;
-        ch.index = x >> (T.arity_bits * (l + 1));
-        ch.cap = blob + T.o_fri_caps + (size_t)l * C4;
+        const uint32_t l = tree - 3;
+        ch.len = (uint32_t)R.layer_values();
+        ch.leaf = qr + R.layer_evals(l);
+        ch.nsib = (uint32_t)R.layer_sibling_count(l);
+        ch.index = x >> ((uint32_t)R.arity_bits * (l + 1));
+        ch.cap = blob + P.o_cap(l);
         slot = 4 + 2 * l;
     }
     ch.sib = ch.leaf + ch.len;
@@ -89,7 +89,7 @@ __device__ __forceinline__ bool chain_setup(const zkm_verify_table& T, const gl_
 __global__ __launch_bounds__(256) void k_verify_chains_quad(const zkm_verify_table* __restrict__ tabs, const gl_t* __restrict__ blobs,
                                                             const uint32_t* __restrict__ xs, uint32_t* __restrict__ verdicts) {
     const zkm_verify_table& T = tabs[blockIdx.y];
-    if (blockIdx.x * 64u >= T.nq * (3 + T.L)) return;   // (uniform over the workgroup)
+    if (blockIdx.x * 64u >= (uint32_t)T.d.nq * (3 + (uint32_t)T.d.L)) return;   // (uniform over the workgroup)
     __shared__ __attribute__((aligned(16))) uint32_t qtab[ZKM_QUAD_TAB_WORDS];
     quad_tab_load(qtab);
     const poseidon_quad Q(threadIdx.x, qtab);
@@ -194,12 +194,16 @@ __global__ __launch_bounds__(64) void k_verify_fri(const zkm_verify_table* __res
                                                    const uint32_t* __restrict__ xs, uint32_t* __restrict__ verdicts) {
     const zkm_verify_table& T = tabs[blockIdx.y];
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= T.nq) return;
+    const zkm_blob_desc& d = T.d;
+    if (q >= (uint32_t)d.nq) return;
     uint32_t x = xs[T.xs + q];
     const gl_t* blob = blobs + T.blob;
-    const gl_t* qr = blob + T.o_queries + (size_t)q * T.query_words;
-    const uint32_t W = T.W, A = T.A, NQ = T.Q, Z = T.Z, sib0 = T.lde_bits - T.cap_height, arity = 1u << T.arity_bits;
-    const gl_t *ev0 = qr, *ev1 = ev0 + W + 4 * (size_t)sib0, *ev2 = ev1 + A + 4 * (size_t)sib0;
+    const zkm_fri_part P = d.fri();
+    const zkm_query_round& R = P.round;
+    const gl_t* qr = blob + P.o_query(q);
+    const uint32_t W = (uint32_t)d.W, A = (uint32_t)d.A, NQ = (uint32_t)d.Q, Z = (uint32_t)d.Z, L = (uint32_t)d.L;
+    const uint32_t lde_bits = (uint32_t)d.lde_bits(), arity_bits = (uint32_t)d.arity_bits, arity = 1u << arity_bits;
+    const gl_t *ev0 = qr + R.oracle_evals(0), *ev1 = qr + R.oracle_evals(1), *ev2 = qr + R.oracle_evals(2);
     uint32_t* v = verdicts + T.verdicts + q * T.slots;
     const gl2_t fa = ld2(T.fri_alpha), apow_wa = ld2(T.apow_wa);
     // fri_combine_initial: the batch at zeta is the trace, auxiliary and quotient columns, the batch at g zeta the first two, the
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(64) void k_verify_fri(const zkm_verify_table* __res
     for (uint32_t c = NQ; c-- > 0;) redq = horner_base(redq, fa, ev2[c]);
     for (uint32_t c = A; c-- > A - Z;) redz = horner_base(redz, fa, ev1[c]);
     const gl2_t red0 = gl2_add(red1, gl2_mul(apow_wa, redq));
-    gl_t sub_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(T.lde_bits), bitrev32(x, T.lde_bits)));
+    gl_t sub_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(lde_bits), bitrev32(x, lde_bits)));
     auto over = [&](gl2_t red, const gl_t* opened, gl2_t point) {
         gl2_t den{gl_sub(sub_x, point.c0), gl_neg(point.c1)};
         return gl2_mul(gl2_sub(red, ld2(opened)), gl2_inv(den));
@@ -219,19 +223,18 @@ __global__ __launch_bounds__(64) void k_verify_fri(const zkm_verify_table* __res
     sum = gl2_add(gl2_mul(sum, apow_wa), over(red1, T.red_open[1], ld2(T.zeta_next)));
     sum = gl2_add(gl2_mul(sum, ld2(T.apow_z)), over(redz, T.red_open[2], gl2_t{1, 0}));
     gl2_t old_eval = sum;
-    const gl_t* o = ev2 + NQ + 4 * (size_t)sib0;
-    for (uint32_t l = 0; l < T.L; l++) {
+    for (uint32_t l = 0; l < L; l++) {
+        const gl_t* o = qr + R.layer_evals(l);
         const uint32_t within = x & (arity - 1);
         v[3 + 2 * l] = gl2_eq(ld2(o + 2 * (size_t)within), old_eval) ? 0u : 1u;
-        old_eval = compute_evaluation(sub_x, within, T.arity_bits, o, ld2(T.betas[l]));
-        o += 2 * (size_t)arity + 4 * (size_t)(T.lde_bits - T.arity_bits * (l + 1) - T.cap_height);
-        sub_x = gl_exp_pow2(sub_x, T.arity_bits);
-        x >>= T.arity_bits;
+        old_eval = compute_evaluation(sub_x, within, arity_bits, o, ld2(T.betas[l]));
+        sub_x = gl_exp_pow2(sub_x, arity_bits);
+        x >>= arity_bits;
     }
-    const gl_t* fp = blob + T.o_final;
+    const gl_t* fp = blob + P.o_final();
     gl2_t fe{0, 0};
-    for (uint32_t i = T.F; i-- > 0;) fe = gl2_add(gl2_scalar_mul(fe, sub_x), ld2(fp + 2 * (size_t)i));
-    v[3 + 2 * T.L] = gl2_eq(fe, old_eval) ? 0u : 1u;
+    for (uint32_t i = (uint32_t)d.F; i-- > 0;) fe = gl2_add(gl2_scalar_mul(fe, sub_x), ld2(fp + 2 * (size_t)i));
+    v[3 + 2 * L] = gl2_eq(fe, old_eval) ? 0u : 1u;
 }
 
 // first finding of a (segment, table): the lowest query, and inside it the lowest slot -- trace, auxiliary, quotient tree, per layer
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(256) void k_verify_reduce(const zkm_verify_table* _
     __shared__ uint32_t best;
     if (threadIdx.x == 0) best = ~0u;
     __syncthreads();
-    const uint32_t n = T.nq * T.slots;
+    const uint32_t n = (uint32_t)T.d.nq * T.slots;
     uint32_t mine = ~0u;
     for (uint32_t i = threadIdx.x; i < n && mine == ~0u; i += blockDim.x)
         if (verdicts[T.verdicts + i]) mine = i;
@@ -261,13 +264,9 @@ std::string table_label(const zkm_table_input* tables, size_t t) {
     return "table " + std::to_string(t) + " (" + (e < 0 ? "Table" + std::to_string(tables[t].table_id) : std::string(names[e])) + ")";
 }
 
-gl2_t challenger_get_ext(zkm_challenger* ch) {
-    const gl_t a = zkm_challenger_get(ch), b = zkm_challenger_get(ch);
-    return gl2_t{a, b};
-}
-gl2_t reduce_ext(const std::vector<gl2_t>& v, gl2_t alpha) {   // sum_j alpha^j v_j
-    gl2_t acc{0, 0};
-    for (size_t i = v.size(); i-- > 0;) acc = gl2_add(gl2_mul(acc, alpha), v[i]);
+// acc alpha^k + sum_j alpha^j v_j over k values v_j: F2 pairs (stride 2) or base-field words (stride 1)
+gl2_t reduce_more(gl2_t acc, gl2_t alpha, const uint64_t* v, size_t k, size_t stride) {
+    for (size_t i = k; i-- > 0;) acc = gl2_add(gl2_mul(acc, alpha), gl2_t{v[stride * i], stride == 2 ? v[2 * i + 1] : 0});
     return acc;
 }
 // f(t), t = 0 .. 4, of a polynomial of degree <= 3 with base-field coefficients -> its value at t = X in F[X] / (X^2 - 7); false when
@@ -293,7 +292,7 @@ struct verify_input {
     const uint64_t* claimed;         // CTL challenges, or null
 };
 struct table_state {
-    proof_layout y{};
+    zkm_blob_desc y{};
     size_t off = 0;                  // of the blob in the segment's proofs
     gl_t alphas[2] = {0, 0};
     gl2_t zeta{0, 0};
@@ -333,22 +332,24 @@ bool check_shapes(const zkm_stark_config* cfg, const verify_input& in, size_t nt
         const size_t W = in.tables[t].ncols, A = zkm_num_lookup_columns(in.tables[t].table_id, cfg) + tz0[t].naux, Z = tz0[t].zs.size();
         table_state& ts = S.ts[t];
         try {
-            zkm_proof_layout_make(ts.y, cfg, log_n, W, A, Z);
+            ts.y = zkm_blob_describe(cfg, log_n, W, A, Z);
         } catch (const std::exception& e) {
             return bad(e.what());
         }
-        const proof_layout& y = ts.y;
-        const uint64_t want[10] = {W, A, y.Q, Z, y.cap, y.L, y.F, y.nq, cfg->rate_bits, cfg->arity_bits};
-        for (int i = 0; i < 10; i++)
-            if (p[2 + i] != want[i]) return bad("header word " + std::to_string(2 + i) + " does not match the configuration and the table");
+        const zkm_blob_desc& y = ts.y;
+        uint64_t want[16];
+        zkm_blob_header_write(want, y);
+        for (int i = 2; i < 12; i++)
+            if (p[i] != want[i]) return bad("header word " + std::to_string(i) + " does not match the configuration and the table");
         for (int i = 12; i < 16; i++)
-            if (p[i] != 0) return bad("reserved header word not zero");
-        if (y.L > 16 || y.lde_bits > 31 || y.total >= ((uint64_t)1 << 32)) return bad("unsupported FRI shape");
-        if (in.words - off < y.total) return bad("proof_words too short");
-        for (size_t i = 16; i < y.total; i++)
+            if (p[i] != want[i]) return bad("reserved header word not zero");
+        const size_t total = y.total();
+        if (y.L > ZKM_FRI_HEADER_LAYERS || y.lde_bits() > 31 || total >= ((uint64_t)1 << 32)) return bad("unsupported FRI shape");
+        if (in.words - off < total) return bad("proof_words too short");
+        for (size_t i = 16; i < total; i++)
             if (p[i] >= GL_P) return bad("word " + std::to_string(i) + " is not a canonical field element");
         ts.off = off;
-        off += y.total;
+        off += total;
     }
     return true;
 }
@@ -358,79 +359,51 @@ bool check_shapes(const zkm_stark_config* cfg, const verify_input& in, size_t nt
 void replay_table(const zkm_stark_config* cfg, const verify_input& in, size_t t, seg_state& S, zkm_verify_table& T,
                   std::vector<uint32_t>& xs) {
     table_state& ts = S.ts[t];
-    const proof_layout& y = ts.y;
+    const zkm_blob_desc& y = ts.y;
     const uint64_t* proof = in.proofs + ts.off;
     zkm_challenger* ch = &S.ch;
-    const size_t W = y.W, A = y.A, Z = y.Z, C4 = y.C * 4;
     uint64_t st0[12];
     zkm_challenger_compact(ch, st0);   // proof.rs:199: the prover recorded the compacted state
-    ts.state_ok = memcmp(st0, proof + y.o_init, sizeof st0) == 0;
-    const uint64_t* caps = proof + y.o_caps;
-    zkm_challenger_observe(ch, caps + C4, C4);
-    for (unsigned i = 0; i < cfg->num_challenges; i++) ts.alphas[i] = zkm_challenger_get(ch);
-    zkm_challenger_observe(ch, caps + 2 * C4, C4);
-    ts.zeta = challenger_get_ext(ch);
-    const uint64_t *o_local = proof + y.o_open, *o_next = o_local + 2 * W, *o_aux = o_local + 4 * W, *o_auxn = o_aux + 2 * A, *o_ctl = o_auxn + 2 * A,
-                   *o_quot = o_ctl + Z;
-    zkm_challenger_observe(ch, o_local, 2 * W);   // observe_openings(to_fri_openings) proof.rs:336-367
-    zkm_challenger_observe(ch, o_aux, 2 * A);
-    zkm_challenger_observe(ch, o_quot, 2 * y.Q);
-    zkm_challenger_observe(ch, o_next, 2 * W);
-    zkm_challenger_observe(ch, o_auxn, 2 * A);
-    for (size_t i = 0; i < Z; i++) { const uint64_t e[2] = {o_ctl[i], 0}; zkm_challenger_observe(ch, e, 2); }
-    const gl2_t fri_alpha = challenger_get_ext(ch);
-    gl2_t betas[16];
-    for (unsigned l = 0; l < y.L; l++) {
-        zkm_challenger_observe(ch, proof + y.o_fri_caps + l * C4, C4);
-        betas[l] = challenger_get_ext(ch);
-    }
-    zkm_challenger_observe(ch, proof + y.o_final, 2 * y.F);
-    zkm_challenger_observe(ch, proof + y.o_pow, 1);
-    const uint64_t pow_resp = zkm_challenger_get(ch);
-    ts.pow_ok = (pow_resp >> (64 - cfg->pow_bits)) == 0;   // fri_verify_proof_of_work
-    const size_t N = (size_t)1 << y.lde_bits;
+    ts.state_ok = memcmp(st0, proof + y.o_init(), sizeof st0) == 0;
+    zkm_transcript_alphas(ch, y, proof, cfg->num_challenges, ts.alphas);
+    ts.zeta = zkm_transcript_zeta(ch, y, proof);
+    auto put = [](gl_t* dst, gl2_t v) { dst[0] = v.c0; dst[1] = v.c1; };
+    const gl2_t fri_alpha = zkm_transcript_fri_alpha(ch, y, proof);
+    const zkm_fri_part f = y.fri();
+    for (unsigned l = 0; l < y.L; l++) put(T.betas[l], zkm_transcript_fri_beta(ch, proof + f.o_cap(l), f.cap_words));
+    zkm_transcript_final_poly(ch, proof + f.o_final(), f.F);
+    ts.pow_ok = zkm_transcript_pow(ch, proof[f.o_pow()], cfg->pow_bits);
     T.xs = (uint32_t)xs.size();
-    for (size_t q = 0; q < y.nq; q++) xs.push_back((uint32_t)(zkm_challenger_get(ch) % N));
+    zkm_transcript_query_indices(ch, y.nq, (unsigned)y.lde_bits(), std::back_inserter(xs));
 
-    T.log_n = y.log_n; T.lde_bits = y.lde_bits; T.W = (uint32_t)W; T.A = (uint32_t)A; T.Q = (uint32_t)y.Q; T.Z = (uint32_t)Z; T.L = y.L;
-    T.F = (uint32_t)y.F; T.nq = (uint32_t)y.nq; T.cap_height = y.cap; T.arity_bits = cfg->arity_bits; T.slots = 4 + 2 * y.L;
-    T.o_caps = (uint32_t)y.o_caps; T.o_open = (uint32_t)y.o_open; T.o_fri_caps = (uint32_t)y.o_fri_caps; T.o_final = (uint32_t)y.o_final;
-    T.o_queries = (uint32_t)y.o_queries; T.query_words = (uint32_t)y.query_words;
+    T.d = y;
+    T.slots = 4 + 2 * (uint32_t)y.L;
     const gl_t g = gl_root_of_unity(y.log_n);
     const gl2_t zeta_next = gl2_scalar_mul(ts.zeta, g);
-    auto put = [](gl_t* dst, gl2_t v) { dst[0] = v.c0; dst[1] = v.c1; };
     put(T.zeta, ts.zeta);
     put(T.zeta_next, zeta_next);
     put(T.fri_alpha, fri_alpha);
-    put(T.apow_wa, gl2_pow(fri_alpha, W + A));
-    put(T.apow_z, gl2_pow(fri_alpha, Z));
-    for (unsigned l = 0; l < y.L; l++) put(T.betas[l], betas[l]);
-    // the reduced openings of the three batches (fri/verifier.rs PrecomputedReducedOpenings)
-    std::vector<gl2_t> b;
-    for (size_t c = 0; c < W; c++) b.push_back(gl2_t{o_local[2 * c], o_local[2 * c + 1]});
-    for (size_t c = 0; c < A; c++) b.push_back(gl2_t{o_aux[2 * c], o_aux[2 * c + 1]});
-    for (size_t c = 0; c < y.Q; c++) b.push_back(gl2_t{o_quot[2 * c], o_quot[2 * c + 1]});
-    put(T.red_open[0], reduce_ext(b, fri_alpha));
-    b.clear();
-    for (size_t c = 0; c < W; c++) b.push_back(gl2_t{o_next[2 * c], o_next[2 * c + 1]});
-    for (size_t c = 0; c < A; c++) b.push_back(gl2_t{o_auxn[2 * c], o_auxn[2 * c + 1]});
-    put(T.red_open[1], reduce_ext(b, fri_alpha));
-    b.clear();
-    for (size_t c = 0; c < Z; c++) b.push_back(gl2_t{o_ctl[c], 0});
-    put(T.red_open[2], reduce_ext(b, fri_alpha));
+    put(T.apow_wa, gl2_pow(fri_alpha, y.W + y.A));
+    put(T.apow_z, gl2_pow(fri_alpha, y.Z));
+    // the reduced openings of the three batches (fri/verifier.rs PrecomputedReducedOpenings), each from its last value to its first
+    const auto o = y.openings(proof);
+    const gl2_t zero{0, 0}, at_zeta = reduce_more(reduce_more(zero, fri_alpha, o.quotient, y.Q, 2), fri_alpha, o.aux, y.A, 2);
+    put(T.red_open[0], reduce_more(at_zeta, fri_alpha, o.local, y.W, 2));
+    put(T.red_open[1], reduce_more(reduce_more(zero, fri_alpha, o.aux_next, y.A, 2), fri_alpha, o.next, y.W, 2));
+    put(T.red_open[2], reduce_more(zero, fri_alpha, o.ctl_zs_first, y.Z, 1));
 }
 
 // the quotient comparison (verifier.rs:205-264) from the line accumulators of one table: acc[4 t + setting][challenge]
 // returns the first challenge whose identity fails, or -1
 int quotient_check(const zkm_stark_config* cfg, const table_state& ts, const uint64_t* proof, const gl_t* acc) {
-    const proof_layout& y = ts.y;
+    const zkm_blob_desc& y = ts.y;
     const gl_t g = gl_root_of_unity(y.log_n);
     const gl2_t zeta = ts.zeta, one{1, 0};
     const gl2_t zeta_n = gl2_exp_pow2(zeta, y.log_n), z_h = gl2_sub(zeta_n, one);
     const gl_t nn = (gl_t)(((uint64_t)1 << y.log_n) % GL_P);   // eval_l_0_and_l_last verifier.rs:344-354
     const gl2_t d0 = gl2_scalar_mul(gl2_sub(zeta, one), nn), d1 = gl2_scalar_mul(gl2_sub(gl2_scalar_mul(zeta, g), one), nn);
     const gl2_t z_last = gl2_sub(zeta, gl2_t{gl_inv(g), 0}), l_first = gl2_mul(z_h, gl2_inv(d0)), l_last = gl2_mul(z_h, gl2_inv(d1));
-    const uint64_t* o_quot = proof + y.o_open + 4 * y.W + 4 * y.A + y.Z;
+    const uint64_t* o_quot = y.openings(proof).quotient;
     for (unsigned a = 0; a < cfg->num_challenges; a++) {
         gl2_t cls[4];
         for (int setting = 0; setting < 4; setting++) {
@@ -453,8 +426,7 @@ void check_ctl_sums(const zkm_stark_config* cfg, const verify_input& in, size_t 
                     size_t nctls, seg_state& S) {
     std::vector<size_t> cursor(ntables, 0);
     auto first = [&](size_t t) {
-        const proof_layout& y = S.ts[t].y;
-        return in.proofs[S.ts[t].off + y.o_open + 4 * y.W + 4 * y.A + cursor[t]++];
+        return S.ts[t].y.openings(in.proofs + S.ts[t].off).ctl_zs_first[cursor[t]++];
     };
     for (size_t c = 0; c < nctls; c++) {
         const zkm_ctl_side* lk = sides + ctls[c].looking_off;
@@ -489,8 +461,7 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
     if (nseg * ntables > 65535) throw std::runtime_error("verify: at most 65535 (segment, table) pairs per call");
     if (cfg->num_challenges < 1 || cfg->num_challenges > 2) throw std::runtime_error("stark config: num_challenges must be 1 or 2");
     {   // a configuration the library does not support is a bad argument (FAILED), not a property of a blob
-        proof_layout probe;
-        zkm_proof_layout_make(probe, cfg, 32, 1, 1, 1);
+        (void)zkm_blob_describe(cfg, 32, 1, 1, 1);
     }
     const unsigned nch = cfg->num_challenges;
     const std::vector<table_zs> tz0 = fixed ? *fixed : zkm_derive_zs(ntables, ctls, sides, nctls, nch, nullptr);
@@ -515,11 +486,8 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
             S.ch = *start;
             S.tz = *fixed;
         } else {
-            // AllProof::get_challenges get_challenges.rs:124-148: all trace caps, the public values, beta and gamma per challenge
-            zkm_challenger_init(&S.ch);
-            for (size_t t = 0; t < ntables; t++) zkm_challenger_observe(&S.ch, in[s].proofs + S.ts[t].off + S.ts[t].y.o_caps, S.ts[t].y.C * 4);
-            zkm_challenger_observe(&S.ch, in[s].pub, in[s].npub);
-            for (unsigned k = 0; k < 2 * nch; k++) S.challenges[k] = zkm_challenger_get(&S.ch);
+            zkm_transcript_seed(&S.ch, ntables, [&](size_t t) { return in[s].proofs + S.ts[t].off + S.ts[t].y.o_cap(0); }, S.ts[0].y.cap_words(),
+                                in[s].pub, in[s].npub, nch, S.challenges);
             if (in[s].claimed && memcmp(S.challenges, in[s].claimed, sizeof(uint64_t) * 2 * nch) != 0) {
                 reject(S, ZKM_VERIFY_CTL_CHALLENGES, 0, "the claimed CTL challenges are not the ones the transcript yields");
                 continue;
@@ -546,11 +514,11 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
             T.blob = blob_words + S.ts[t].off;
             T.rows = row_words;
             T.verdicts = (uint32_t)nverdicts;
-            row_words += (size_t)ZKM_VERIFY_LINE_POINTS * 2 * (T.W + T.A);
-            nverdicts += (size_t)T.nq * T.slots;
-            nchains += (size_t)T.nq * (3 + T.L);
+            row_words += (size_t)ZKM_VERIFY_LINE_POINTS * 2 * (T.d.W + T.d.A);
+            nverdicts += (size_t)T.d.nq * T.slots;
+            nchains += (size_t)T.d.nq * (3 + T.d.L);
         }
-        blob_words += S.ts[ntables - 1].off + S.ts[ntables - 1].y.total;
+        blob_words += S.ts[ntables - 1].off + S.ts[ntables - 1].y.total();
     }
     if (nverdicts >= ((uint64_t)1 << 32) || xs.size() >= ((uint64_t)1 << 32)) throw std::runtime_error("verify: too many queries in one call");
     const uint64_t waits_before = c->host_waits;
@@ -601,16 +569,16 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
         ZKM_HIP_CHECK(hipMemcpyAsync(up.p, params.data(), params.size(), hipMemcpyHostToDevice, c->stream));
         size_t at = 0;
         for (size_t s : launched) {
-            const size_t words = segs[s].ts[ntables - 1].off + segs[s].ts[ntables - 1].y.total;
+            const size_t words = segs[s].ts[ntables - 1].off + segs[s].ts[ntables - 1].y.total();
             ZKM_HIP_CHECK(hipMemcpyAsync(d_blobs + at, in[s].proofs, words * 8, hipMemcpyHostToDevice, c->stream));
             at += words;
         }
     }
     uint32_t most_cols = 0, most_chains = 0, most_q = 0;
     for (const zkm_verify_table& T : tabs) {
-        most_cols = std::max(most_cols, T.W + T.A);
-        most_chains = std::max(most_chains, T.nq * (3 + T.L));
-        most_q = std::max(most_q, T.nq);
+        most_cols = std::max(most_cols, (uint32_t)(T.d.W + T.d.A));
+        most_chains = std::max(most_chains, (uint32_t)(T.d.nq * (3 + T.d.L)));
+        most_q = std::max(most_q, (uint32_t)T.d.nq);
     }
     {
         zkm_prof_scope ps(c, "verify/line_rows");
@@ -620,7 +588,7 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
     for (const line_launch& ll : lines) {
         const zkm_verify_table& T0 = tabs[ll.acc_off[0] / (2 * ZKM_VERIFY_LINE_THREADS)];
         zkm_verify_line_constraints(c, in[0].tables[ll.t].table_id, nch, ctl_dev_rebase(ll.ctl.d, up.as<char>()), ll.ctl.naux, ll.lookup_ch.data(),
-                                    ll.alphas.data(), d_rows.as<gl_t>(), ll.rows_off.data(), d_acc, ll.acc_off.data(), T0.W, T0.A, ll.G);
+                                    ll.alphas.data(), d_rows.as<gl_t>(), ll.rows_off.data(), d_acc, ll.acc_off.data(), T0.d.W, T0.d.A, ll.G);
     }
     // the hash chains do not depend on each other or on the arithmetic; a call of few chains costs the longest chain's latency (the
     // Keccak table's leaf: 304 permutations), so it takes the four-lane form of the permutation; one that fills the machine one lane
@@ -680,7 +648,7 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
             if (slot < 3) {
                 reject(S, ZKM_VERIFY_INITIAL_MERKLE, t, at + "Invalid Merkle proof. (initial oracle " + std::to_string(slot) + ")");
                 S.rep.tree = slot;
-            } else if (slot == 3 + 2 * T.L) {
+            } else if (slot == 3 + 2 * (uint32_t)T.d.L) {
                 reject(S, ZKM_VERIFY_FINAL_POLY, t, at + "Final polynomial evaluation is invalid.");
             } else {
                 S.rep.layer = (slot - 3) / 2;

@@ -20,6 +20,7 @@
 
 #include "../../include/zkm_hip.h"
 #include "gl_dev.h"
+#include "proof_blob.h"
 
 #define ZKM_HIP_CHECK(expr)                                                                                  \
     do {                                                                                                     \
@@ -505,13 +506,6 @@ void zkm_arithmetic_write(zkm_arith_job* j, size_t nseg, const unsigned* log_n, 
 int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
                        size_t nctls, zkm_ctl_report* rep, std::string* msg);
 // ---- the verifier (verify.hip; the constraint evaluation on the line through the opening lives beside k_quotient in stark.hip)
-// word offsets of the fields of a proof blob (include/zkm_hip.h); stark.hip fills it in for a validated configuration (throws otherwise)
-struct proof_layout {
-    unsigned log_n, lde_bits, L, cap;
-    size_t W, A, Q, Z, F, C, nq;
-    size_t o_init, o_caps, o_open, o_fri_caps, o_final, o_pow, o_queries, query_words, total;
-};
-void zkm_proof_layout_make(proof_layout& y, const zkm_stark_config* cfg, unsigned log_n, size_t W, size_t A, size_t Z);
 // per-table CtlZData lists in cross_table_lookup_data order (ctl.hip): the prover's derivation, which the verifier replays
 struct table_zs {
     std::vector<zkm_ctl_z> zs;
@@ -522,16 +516,15 @@ std::vector<table_zs> zkm_derive_zs(size_t ntables, const zkm_cross_table_lookup
                                     const uint64_t* challenges);
 void zkm_all_stark_table_inputs(zkm_table_input out[12]);   // ctl.hip: the twelve tables of the built-in AllStark (no traces, log_n 0)
 // One (segment, table) of a verify call as the kernels see it: where its blob lies in the call's device block, the blob's validated
-// shape, and what the transcript replay gave.  Every offset was computed on the host from the validated header.
+// description (proof_blob.h: every offset follows from it), and what the transcript replay gave.
 #define ZKM_VERIFY_LINE_POINTS 5      // constraints are evaluated on the rows v0 + t v1, t = 0 .. 4 (degree <= 3, one point to spare)
 #define ZKM_VERIFY_LINE_THREADS (4 * ZKM_VERIFY_LINE_POINTS)
 struct zkm_verify_table {
     uint64_t blob;                    // word offset of the blob
     uint64_t rows;                    // word offset of its line rows: [t][column][local, next], trace columns then auxiliary columns
-    uint32_t log_n, lde_bits, W, A, Q, Z, L, F, nq, cap_height, arity_bits, slots;   // slots: verdict words per query = 4 + 2 L
-    uint32_t o_caps, o_open, o_fri_caps, o_final, o_queries, query_words;
-    uint32_t xs, verdicts;            // first of its nq query indices / of its nq * slots verdict words
-    gl_t zeta[2], zeta_next[2], fri_alpha[2], apow_wa[2], apow_z[2], red_open[3][2], betas[16][2];
+    zkm_blob_desc d;
+    uint32_t slots, xs, verdicts;     // verdict words per query = 4 + 2 L; first of its nq query indices / of its nq * slots verdict words
+    gl_t zeta[2], zeta_next[2], fri_alpha[2], apow_wa[2], apow_z[2], red_open[3][2], betas[ZKM_FRI_HEADER_LAYERS][2];
 };
 // stark.hip: all constraints of `table_id` on the line rows of nseg <= ZKM_MAX_SEG (segment, table) entries, ONE launch; entry s reads
 // d_rows + rows_off[s] and writes its 20 x 2 accumulators (thread = 4 t + setting, then challenge) to d_acc + acc_off[s].  `own` holds
