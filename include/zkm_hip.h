@@ -181,6 +181,49 @@ int zkm_batch_digest_layer(const zkm_batch* b, unsigned level, uint64_t* out);
 int zkm_poseidon_permute_batch(zkm_ctx* ctx, uint64_t* states, size_t k, char** err);
 int zkm_keccakf_batch(zkm_ctx* ctx, uint64_t* states, size_t k, char** err);
 
+/* Parity / debug: ONE piece of the device's Poseidon permutation per call, on words the caller chooses (any uint64: the device code
+ * promises "loose" inputs everywhere).  The device has four forms of the permutation -- one lane per hash on the vector ALU, one lane per
+ * hash with the full-round MDS layers on the matrix core, one hash per quad of lanes, one hash per 16-lane row -- and leaf hashing only
+ * ever feeds them the LDE of field data; this entry point places a chosen state in front of each form, of a single linear layer or fused
+ * partial-round group, and of the folds they end in.  `in` and `out` are host memory; a state is 12 words; outputs are the raw words the
+ * device code produced (loose unless stated), nothing is canonicalised by the probe.
+ *   probe                                  arg                   in -> out
+ *   PERMUTE_LANE, PERMUTE_LANE_MFMA,       ZKM_POSEIDON_OUT_*    n states -> n states through the form's permutation.  OUT_ALL: twelve canonical words.
+ *   PERMUTE_QUAD, PERMUTE_WIDE                                   OUT_CAPACITY: words 8..11, loose; words 0..7 are garbage.  OUT_DIGEST: words 0..3,
+ *                                                                canonical; words 4..11 are garbage.  The quad and 16-lane forms ignore arg and
+ *                                                                return twelve canonical words.
+ *   MDS_VALU, MDS_MFMA, MDS_QUAD           next: 1, 2, 3, 27,    n states -> n states: M s + the constants of round `next` (30: none) -- the layer
+ *                                          28, 29 or 30          of a full round on the vector ALU, on the matrix core, in the quad form
+ *   MDS_ROWS                               0 / 1                 n states -> n states: the last layer of OUT_DIGEST (0: rows 0..3 of M s) / of
+ *                                                                OUT_CAPACITY (1: rows 8..11); the other rows are unspecified
+ *   GROUP3, GROUP3_QUAD                    g = 0..6              n states -> n states: fused group g -- the linear layers of rounds 3g+3 .. 3g+5
+ *                                                                with their constants and the word-0 s-boxes of rounds 3g+4, 3g+5
+ *   GROUP2                                 0                     n states -> n states: the tail group (linear layers of rounds 24, 25)
+ *   FOLD                                   0                     n pairs (al, ah), both < 2^59 -> n words al + 2^32 ah
+ *   FOLD_TY                                0                     n pairs (T, Y), T < 2^57, Y < 2^27 in the low half of its word -> n words T + 2^48 Y
+ *   SBOX7, SBOX_DELTA, ADD_RC0             0                     n states -> n states, word by word: x^7;  x^7 - x;  x + constant of round 0
+ * (all mod p).  An unknown probe, an arg outside its column, n = 0 or n > 2^20 is an error: nothing is launched. */
+#define ZKM_POSEIDON_OUT_ALL 0
+#define ZKM_POSEIDON_OUT_CAPACITY 1
+#define ZKM_POSEIDON_OUT_DIGEST 2
+#define ZKM_POSEIDON_PROBE_PERMUTE_LANE 0
+#define ZKM_POSEIDON_PROBE_PERMUTE_LANE_MFMA 1
+#define ZKM_POSEIDON_PROBE_PERMUTE_QUAD 2
+#define ZKM_POSEIDON_PROBE_PERMUTE_WIDE 3
+#define ZKM_POSEIDON_PROBE_MDS_VALU 4
+#define ZKM_POSEIDON_PROBE_MDS_MFMA 5
+#define ZKM_POSEIDON_PROBE_MDS_QUAD 6
+#define ZKM_POSEIDON_PROBE_MDS_ROWS 7
+#define ZKM_POSEIDON_PROBE_GROUP3 8
+#define ZKM_POSEIDON_PROBE_GROUP3_QUAD 9
+#define ZKM_POSEIDON_PROBE_GROUP2 10
+#define ZKM_POSEIDON_PROBE_FOLD 11
+#define ZKM_POSEIDON_PROBE_FOLD_TY 12
+#define ZKM_POSEIDON_PROBE_SBOX7 13
+#define ZKM_POSEIDON_PROBE_SBOX_DELTA 14
+#define ZKM_POSEIDON_PROBE_ADD_RC0 15
+int zkm_poseidon_selftest(zkm_ctx* ctx, uint32_t probe, uint32_t arg, const uint64_t* in, size_t n, uint64_t* out, char** err);
+
 /* ------------------------------------------------------------------ a13: PoseidonStark witness
  * PoseidonStark::generate_trace (poseidon_stark.rs:104-160): 262 columns x 2^log_n rows, column-major,
  * from `num_perms` seeded 12-element inputs (SplitMix64(seed); timestamp 0, FILTER 1) padded with the

@@ -114,6 +114,14 @@ pub const ZKM_VERIFY_INITIAL_MERKLE: u32 = 6; pub const ZKM_VERIFY_FRI_EVAL: u32
 pub const ZKM_VERIFY_FINAL_POLY: u32 = 9; pub const ZKM_VERIFY_CTL_SUM: u32 = 10; pub const ZKM_VERIFY_FAILED: u32 = 11;
 
 // ZKM_TABLE_* ids (NOT the reference's Table enum order: see zkm_table_enum_index)
+// zkm_poseidon_selftest: output modes of a permutation probe, and the probes
+pub const ZKM_POSEIDON_OUT_ALL: u32 = 0; pub const ZKM_POSEIDON_OUT_CAPACITY: u32 = 1; pub const ZKM_POSEIDON_OUT_DIGEST: u32 = 2;
+pub const ZKM_POSEIDON_PROBE_PERMUTE_LANE: u32 = 0; pub const ZKM_POSEIDON_PROBE_PERMUTE_LANE_MFMA: u32 = 1; pub const ZKM_POSEIDON_PROBE_PERMUTE_QUAD: u32 = 2;
+pub const ZKM_POSEIDON_PROBE_PERMUTE_WIDE: u32 = 3; pub const ZKM_POSEIDON_PROBE_MDS_VALU: u32 = 4; pub const ZKM_POSEIDON_PROBE_MDS_MFMA: u32 = 5;
+pub const ZKM_POSEIDON_PROBE_MDS_QUAD: u32 = 6; pub const ZKM_POSEIDON_PROBE_MDS_ROWS: u32 = 7; pub const ZKM_POSEIDON_PROBE_GROUP3: u32 = 8;
+pub const ZKM_POSEIDON_PROBE_GROUP3_QUAD: u32 = 9; pub const ZKM_POSEIDON_PROBE_GROUP2: u32 = 10; pub const ZKM_POSEIDON_PROBE_FOLD: u32 = 11;
+pub const ZKM_POSEIDON_PROBE_FOLD_TY: u32 = 12; pub const ZKM_POSEIDON_PROBE_SBOX7: u32 = 13; pub const ZKM_POSEIDON_PROBE_SBOX_DELTA: u32 = 14;
+pub const ZKM_POSEIDON_PROBE_ADD_RC0: u32 = 15;
 pub const ZKM_TABLE_POSEIDON: c_int = 0; pub const ZKM_TABLE_LOGIC: c_int = 1; pub const ZKM_TABLE_KECCAK_SPONGE: c_int = 2;
 pub const ZKM_TABLE_KECCAK: c_int = 3; pub const ZKM_TABLE_MEMORY: c_int = 4; pub const ZKM_TABLE_POSEIDON_SPONGE: c_int = 5;
 pub const ZKM_TABLE_SHA_EXTEND: c_int = 6; pub const ZKM_TABLE_SHA_EXTEND_SPONGE: c_int = 7; pub const ZKM_TABLE_SHA_COMPRESS: c_int = 8;
@@ -162,6 +170,8 @@ extern "C" {
     // hash primitives, witness kernels
     pub fn zkm_poseidon_permute_batch(ctx: *mut zkm_ctx, states: *mut u64, k: usize, err: *mut *mut c_char) -> c_int;
     pub fn zkm_keccakf_batch(ctx: *mut zkm_ctx, states: *mut u64, k: usize, err: *mut *mut c_char) -> c_int;
+    /// parity / debug: one piece of the device's Poseidon permutation on chosen words (probe: ZKM_POSEIDON_PROBE_*, arg: see the header)
+    pub fn zkm_poseidon_selftest(ctx: *mut zkm_ctx, probe: u32, arg: u32, input: *const u64, n: usize, out: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_poseidon_trace(ctx: *mut zkm_ctx, seed: u64, num_perms: usize, log_n: c_uint, out_dev: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_poseidon_trace_inputs(ctx: *mut zkm_ctx, inputs: *const u64, timestamps: *const u64, num_perms: usize, log_n: c_uint,
                                      out_dev: *mut u64, err: *mut *mut c_char) -> c_int;

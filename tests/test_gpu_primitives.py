@@ -5,6 +5,8 @@ import os
 import numpy as np
 import pytest
 
+from . import poseidon_model
+
 pytestmark = pytest.mark.gpu
 P = 0xFFFFFFFF00000001
 G = 14293326489335486720
@@ -33,6 +35,15 @@ def test_poseidon_permute_batch(ctx, oracle):
         st[12 * (20 + i) + (i % 12)] = e
     got = ctx.poseidon_permute_batch(st.copy())
     assert (got == oracle.poseidon_permute_batch(st)).all()
+    # words >= p ("in: any uint64 words") in every position, among canonical words and as whole states: against the textbook permutation
+    # in Python integers (the oracle's binding is documented for field elements)
+    loose = [e for e in poseidon_model.EDGE if e >= P]
+    assert len(set(loose)) == 4                               # p, p + 1, 2^64 - 2, 2^64 - 1 (also listed as p + 0xFFFFFFFE)
+    states = [[e if i == pos else int(f) for i, f in enumerate(rng.integers(0, P, 12, dtype=np.uint64))] for e in loose for pos in range(12)]
+    states += [[e] * 12 for e in loose]
+    got = ctx.poseidon_permute_batch(np.array(states, dtype=np.uint64).reshape(-1)).reshape(-1, 12)
+    for row, s in zip(got, states):
+        assert [int(x) for x in row] == poseidon_model.permute(s), [hex(x) for x in s]
 
 
 def test_poseidon_permute_device_resident(ctx, oracle):

@@ -27,6 +27,11 @@ KECCAK_COLS = 2431
 POSEIDON_SPONGE_COLS = 110
 TABLE_POSEIDON, TABLE_LOGIC, TABLE_KECCAK_SPONGE, TABLE_KECCAK, TABLE_MEMORY, TABLE_POSEIDON_SPONGE = 0, 1, 2, 3, 4, 5
 TABLE_SHA_EXTEND, TABLE_SHA_EXTEND_SPONGE, TABLE_SHA_COMPRESS, TABLE_SHA_COMPRESS_SPONGE, TABLE_ARITHMETIC, TABLE_CPU = 6, 7, 8, 9, 10, 11
+# zkm_poseidon_selftest: ZKM_POSEIDON_OUT_* and ZKM_POSEIDON_PROBE_* of include/zkm_hip.h
+POSEIDON_OUT_ALL, POSEIDON_OUT_CAPACITY, POSEIDON_OUT_DIGEST = 0, 1, 2
+POSEIDON_PROBE = {name: i for i, name in enumerate((
+    "PERMUTE_LANE", "PERMUTE_LANE_MFMA", "PERMUTE_QUAD", "PERMUTE_WIDE", "MDS_VALU", "MDS_MFMA", "MDS_QUAD", "MDS_ROWS", "GROUP3", "GROUP3_QUAD",
+    "GROUP2", "FOLD", "FOLD_TY", "SBOX7", "SBOX_DELTA", "ADD_RC0"))}
 u64p = C.POINTER(C.c_uint64)
 
 EXPORTS = [
@@ -34,7 +39,7 @@ EXPORTS = [
     "zkm_host_register", "zkm_host_unregister", "zkm_all_stark_ctls", "zkm_all_stark_ctl_table", "zkm_prove_segment", "zkm_prove_segments", "zkm_prove_segments_columns", "zkm_prove_segment_columns", "zkm_ctx_synchronize", "zkm_ctx_stream", "zkm_dev_alloc", "zkm_dev_free",
     "zkm_dev_upload", "zkm_dev_download", "zkm_ntt", "zkm_field_selftest", "zkm_batch_commit_values", "zkm_batch_commit_coeffs", "zkm_batch_commit_columns", "zkm_batch_free",
     "zkm_batch_cap", "zkm_batch_coeffs", "zkm_batch_lde_row", "zkm_batch_lde_rows", "zkm_batch_leaf", "zkm_batch_merkle_path",
-    "zkm_batch_digest_layer", "zkm_poseidon_permute_batch", "zkm_keccakf_batch", "zkm_poseidon_trace", "zkm_keccak_sponge_trace", "zkm_keccak_trace", "zkm_logic_trace", "zkm_memory_trace", "zkm_arithmetic_trace",
+    "zkm_batch_digest_layer", "zkm_poseidon_permute_batch", "zkm_keccakf_batch", "zkm_poseidon_selftest", "zkm_poseidon_trace", "zkm_keccak_sponge_trace", "zkm_keccak_trace", "zkm_logic_trace", "zkm_memory_trace", "zkm_arithmetic_trace",
     "zkm_poseidon_sponge_trace", "zkm_poseidon_trace_inputs", "zkm_sha_extend_trace", "zkm_sha_extend_sponge_trace",
     "zkm_sha_compress_trace", "zkm_sha_compress_sponge_trace",
     "zkm_table_width", "zkm_num_lookup_columns", "zkm_challenger_init",
@@ -232,6 +237,7 @@ def load():
         "zkm_batch_digest_layer": (C.c_int, [cp, C.c_uint, u64p]),
         "zkm_poseidon_permute_batch": (C.c_int, [cp, cp, C.c_size_t, err]),
         "zkm_keccakf_batch": (C.c_int, [cp, cp, C.c_size_t, err]),
+        "zkm_poseidon_selftest": (C.c_int, [cp, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u64p, err]),
         "zkm_poseidon_trace": (C.c_int, [cp, C.c_uint64, C.c_size_t, C.c_uint, cp, err]),
         "zkm_keccak_sponge_trace": (C.c_int, [cp, cp, u64p, u64p, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
         "zkm_poseidon_sponge_trace": (C.c_int, [cp, cp, u64p, u64p, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
@@ -819,6 +825,22 @@ class Context:
         err = C.c_char_p()
         _check(self.L.zkm_field_selftest(self.h, a.ctypes.data_as(u64p), b.ctypes.data_as(u64p), a.size, out.ctypes.data_as(u64p), C.byref(err)), err)
         return out.reshape(7, -1)
+
+    def poseidon_selftest(self, probe, arg, words):
+        """One piece of the device's Poseidon permutation on chosen words (zkm_poseidon_selftest; probe: POSEIDON_PROBE[name] or its number).
+        `words`: n states of 12 words -- n pairs for FOLD / FOLD_TY -- of any uint64.  Returns the raw words the device produced:
+        an (n, 12) array, or n words for the folds."""
+        probe = POSEIDON_PROBE[probe] if isinstance(probe, str) else int(probe)
+        words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+        pairs = probe in (POSEIDON_PROBE["FOLD"], POSEIDON_PROBE["FOLD_TY"])
+        per = 2 if pairs else 12
+        if words.size % per:
+            raise ValueError("poseidon_selftest: %d words are not a whole number of %s" % (words.size, "pairs" if pairs else "states"))
+        n = words.size // per
+        out = np.zeros(n if pairs else 12 * n, dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.L.zkm_poseidon_selftest(self.h, probe, int(arg), words.ctypes.data_as(u64p), n, out.ctypes.data_as(u64p), C.byref(err)), err)
+        return out if pairs else out.reshape(-1, 12)
 
     def poseidon_permute_batch(self, states):
         k = (states.size if isinstance(states, np.ndarray) else states.words) // 12

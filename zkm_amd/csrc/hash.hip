@@ -765,3 +765,158 @@ void zkm_launch_keccakf(zkm_ctx* c, uint64_t* states, size_t k) {
     hipLaunchKernelGGL(k_keccakf, dim3((k + 255) / 256), dim3(256), 0, c->stream, states, k);
     ZKM_HIP_CHECK(hipGetLastError());
 }
+
+// ------------------------------------------------------------------ Poseidon self test (parity / debug)
+// zkm_poseidon_selftest: one piece of the device permutation per launch, on words the caller chooses -- the four forms of the whole
+// permutation, a single linear layer or fused group of each form, the two folds, the s-box and the first constant add.  Leaf hashing
+// only ever feeds these the LDE of field data, which never holds a state of all-ones halves or of extreme byte planes and a word >= p
+// once in 2^32; the range claims in the comments of poseidon_dev.h / poseidon_mfma_dev.h / gl_dev.h are about exactly those inputs.
+// Every kernel calls the product's code (the sponge forms above and the routines of the three Poseidon headers) and stores raw words:
+// nothing is canonicalised here.  One item per hash slot of the form, 256 threads per workgroup; a lane past the last item works on
+// the last item's data and only its store is masked (MFMA ignores EXEC, the latency forms shuffle).
+enum {
+    PROBE_PERMUTE_LANE = ZKM_POSEIDON_PROBE_PERMUTE_LANE, PROBE_PERMUTE_LANE_MFMA = ZKM_POSEIDON_PROBE_PERMUTE_LANE_MFMA,
+    PROBE_PERMUTE_QUAD = ZKM_POSEIDON_PROBE_PERMUTE_QUAD, PROBE_PERMUTE_WIDE = ZKM_POSEIDON_PROBE_PERMUTE_WIDE,
+    PROBE_MDS_VALU = ZKM_POSEIDON_PROBE_MDS_VALU, PROBE_MDS_MFMA = ZKM_POSEIDON_PROBE_MDS_MFMA, PROBE_MDS_QUAD = ZKM_POSEIDON_PROBE_MDS_QUAD,
+    PROBE_MDS_ROWS = ZKM_POSEIDON_PROBE_MDS_ROWS, PROBE_GROUP3 = ZKM_POSEIDON_PROBE_GROUP3, PROBE_GROUP3_QUAD = ZKM_POSEIDON_PROBE_GROUP3_QUAD,
+    PROBE_GROUP2 = ZKM_POSEIDON_PROBE_GROUP2, PROBE_FOLD = ZKM_POSEIDON_PROBE_FOLD, PROBE_FOLD_TY = ZKM_POSEIDON_PROBE_FOLD_TY,
+    PROBE_SBOX7 = ZKM_POSEIDON_PROBE_SBOX7, PROBE_SBOX_DELTA = ZKM_POSEIDON_PROBE_SBOX_DELTA, PROBE_ADD_RC0 = ZKM_POSEIDON_PROBE_ADD_RC0
+};
+static_assert(POSEIDON_OUT_ALL == ZKM_POSEIDON_OUT_ALL && POSEIDON_OUT_CAPACITY == ZKM_POSEIDON_OUT_CAPACITY && POSEIDON_OUT_DIGEST == ZKM_POSEIDON_OUT_DIGEST,
+              "include/zkm_hip.h names the output modes of poseidon_dev.h");
+
+// one lane per hash: the whole permutation, a full-round layer, the 4-row last layers, the fused groups (arg: wave-uniform)
+template <class Form, int PROBE>
+__device__ __forceinline__ void poseidon_probe_lane_body(const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out, unsigned arg) {
+    Form f;
+    if (!f.take(n)) return;
+    typename Form::state_t s;
+#pragma unroll
+    for (int i = 0; i < 12; i++) s[i] = in[f.item * 12 + i];
+    if constexpr (PROBE == PROBE_PERMUTE_LANE || PROBE == PROBE_PERMUTE_LANE_MFMA) {
+        f.permute(s, (int)arg);
+    } else if constexpr (PROBE == PROBE_MDS_VALU || PROBE == PROBE_MDS_MFMA) {
+        f.mds.layer(s, (int)arg);
+    } else if constexpr (PROBE == PROBE_MDS_ROWS) {
+        if (arg == 0) poseidon_mds_add<false, 0, 4>(s, nullptr);
+        else poseidon_mds_add<false, 8, 12>(s, nullptr);
+    } else if constexpr (PROBE == PROBE_GROUP3) {
+        poseidon_partial_group<3>(s, PC::ZKM_POSEIDON_FUSED_C1[arg], PC::ZKM_POSEIDON_FUSED_C2[arg], PC::ZKM_POSEIDON_FUSED_C3[arg]);
+    } else {
+        static_assert(PROBE == PROBE_GROUP2, "not a one-lane probe");
+        poseidon_partial_group<2>(s, PC::ZKM_POSEIDON_FUSED_C1[7], 0, PC::ZKM_POSEIDON_FUSED_C3[7]);
+    }
+    if (!f.live) return;
+#pragma unroll
+    for (int i = 0; i < 12; i++) out[f.item * 12 + i] = s[i];
+}
+template <int PROBE>
+__global__ __launch_bounds__(256) void k_poseidon_probe_lane(const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out, unsigned arg) {
+    poseidon_probe_lane_body<sponge_lane_valu, PROBE>(in, n, out, arg);
+}
+template <int PROBE>
+__global__ __launch_bounds__(256) ZKM_LEAF_MFMA_ATTR void k_poseidon_probe_lane_mfma(const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out, unsigned arg) {
+    poseidon_probe_lane_body<sponge_lane_mfma, PROBE>(in, n, out, arg);
+}
+
+// a quad of lanes per hash: lane q holds the words q, q + 4, q + 8 of its state
+template <int PROBE>
+__global__ __launch_bounds__(256) void k_poseidon_probe_quad(const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out, unsigned arg) {
+    sponge_quad f;
+    f.take(n);
+    const size_t item = f.live ? f.item : n - 1;
+    sponge_quad::state_t s;
+#pragma unroll
+    for (int a = 0; a < 3; a++) s[a] = in[item * 12 + f.q + 4 * a];
+    if constexpr (PROBE == PROBE_PERMUTE_QUAD) {
+        f.permute(s, (int)arg);
+    } else if constexpr (PROBE == PROBE_MDS_QUAD) {
+        quad_mds(s, f.Q, arg < 30 ? PC::ZKM_POSEIDON_RC + arg * 12 + f.q : nullptr);
+    } else {
+        static_assert(PROBE == PROBE_GROUP3_QUAD, "not a quad probe");
+        quad_group3(s, f.Q, PC::ZKM_POSEIDON_FUSED_C1[arg], PC::ZKM_POSEIDON_FUSED_C2[arg], PC::ZKM_POSEIDON_FUSED_C3[arg] + f.q);
+    }
+    if (!f.live) return;
+#pragma unroll
+    for (int a = 0; a < 3; a++) out[item * 12 + f.q + 4 * a] = s[a];
+}
+
+// a 16-lane row per hash: lanes 0..11 of the row hold the twelve words
+__global__ __launch_bounds__(256) void k_poseidon_probe_wide(const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out, unsigned arg) {
+    sponge_wide f;
+    f.take(n);
+    const size_t item = f.live ? f.item : n - 1;
+    sponge_wide::state_t s;
+    s[0] = f.idx < 12 ? in[item * 12 + f.idx] : 0;
+    f.permute(s, (int)arg);
+    if (f.live && f.idx < 12) out[item * 12 + f.idx] = s[0];
+}
+
+// word-wise probes: n pairs -> n words (the folds), n states -> n states (s-box, s-box delta, the first constant add)
+template <int PROBE>
+__global__ __launch_bounds__(256) void k_poseidon_probe_words(const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (PROBE == PROBE_FOLD) {
+        out[i] = poseidon_fold(in[2 * i], in[2 * i + 1]);
+    } else if constexpr (PROBE == PROBE_FOLD_TY) {
+#if defined(__HIP_DEVICE_COMPILE__)      // (the matrix-core layer's fold has no host form)
+        out[i] = poseidon_fold_ty(in[2 * i], (uint32_t)in[2 * i + 1]);
+#endif
+    } else {
+        const uint64_t* rc0 = PC::ZKM_POSEIDON_RC;
+#pragma unroll
+        for (int w = 0; w < 12; w++) {
+            const uint64_t x = in[i * 12 + w];
+            out[i * 12 + w] = PROBE == PROBE_SBOX7 ? poseidon_sbox7(x) : PROBE == PROBE_SBOX_DELTA ? poseidon_sbox_delta(x) : gl_add_lc(x, rc0[w]);
+        }
+    }
+}
+
+extern "C" int zkm_poseidon_selftest(zkm_ctx* c, uint32_t probe, uint32_t arg, const uint64_t* in, size_t n, uint64_t* out, char** err) {
+    return zkm_api("zkm_poseidon_selftest", c, err, [&] {
+        typedef void (*probe_kernel)(const uint64_t*, size_t, uint64_t*, unsigned);
+        probe_kernel kernel = nullptr;
+        unsigned lanes = 1;               // lanes per item
+        bool arg_ok = arg == 0;
+        const bool is_out = arg == POSEIDON_OUT_ALL || arg == POSEIDON_OUT_CAPACITY || arg == POSEIDON_OUT_DIGEST;
+        const bool is_next = arg == 1 || arg == 2 || arg == 3 || arg == 27 || arg == 28 || arg == 29 || arg == 30;   // the values the permutation uses
+        switch (probe) {
+            case PROBE_PERMUTE_LANE: kernel = k_poseidon_probe_lane<PROBE_PERMUTE_LANE>; arg_ok = is_out; break;
+            case PROBE_PERMUTE_LANE_MFMA: kernel = k_poseidon_probe_lane_mfma<PROBE_PERMUTE_LANE_MFMA>; arg_ok = is_out; break;
+            case PROBE_PERMUTE_QUAD: kernel = k_poseidon_probe_quad<PROBE_PERMUTE_QUAD>; arg_ok = is_out; lanes = 4; break;
+            case PROBE_PERMUTE_WIDE: kernel = k_poseidon_probe_wide; arg_ok = is_out; lanes = 16; break;
+            case PROBE_MDS_VALU: kernel = k_poseidon_probe_lane<PROBE_MDS_VALU>; arg_ok = is_next; break;
+            case PROBE_MDS_MFMA: kernel = k_poseidon_probe_lane_mfma<PROBE_MDS_MFMA>; arg_ok = is_next; break;
+            case PROBE_MDS_QUAD: kernel = k_poseidon_probe_quad<PROBE_MDS_QUAD>; arg_ok = is_next; lanes = 4; break;
+            case PROBE_MDS_ROWS: kernel = k_poseidon_probe_lane<PROBE_MDS_ROWS>; arg_ok = arg <= 1; break;
+            case PROBE_GROUP3: kernel = k_poseidon_probe_lane<PROBE_GROUP3>; arg_ok = arg < 7; break;
+            case PROBE_GROUP3_QUAD: kernel = k_poseidon_probe_quad<PROBE_GROUP3_QUAD>; arg_ok = arg < 7; lanes = 4; break;
+            case PROBE_GROUP2: kernel = k_poseidon_probe_lane<PROBE_GROUP2>; break;
+            case PROBE_FOLD: case PROBE_FOLD_TY: case PROBE_SBOX7: case PROBE_SBOX_DELTA: case PROBE_ADD_RC0: break;
+            default: throw std::runtime_error("zkm_poseidon_selftest: unknown probe");
+        }
+        if (!arg_ok) throw std::runtime_error("zkm_poseidon_selftest: bad arg for this probe");
+        if (!in || !out) throw std::runtime_error("zkm_poseidon_selftest: null argument");
+        if (n == 0 || n > ((size_t)1 << 20)) throw std::runtime_error("zkm_poseidon_selftest: n must be 1 .. 2^20");
+        const bool pairs = probe == PROBE_FOLD || probe == PROBE_FOLD_TY;
+        const size_t in_words = pairs ? 2 * n : 12 * n, out_words = pairs ? n : 12 * n;
+        zkm_scratch din(c, in_words * 8), dout(c, out_words * 8);
+        ZKM_HIP_CHECK(hipMemcpyAsync(din.p, in, in_words * 8, hipMemcpyHostToDevice, c->stream));
+        // (rows / words a probe leaves unspecified read as zero, not as what the block held before)
+        ZKM_HIP_CHECK(hipMemsetAsync(dout.p, 0, out_words * 8, c->stream));
+        const dim3 grid((unsigned)((n * lanes + 255) / 256)), block(256);
+        if (kernel) {
+            hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, din.as<uint64_t>(), n, dout.as<uint64_t>(), arg);
+        } else {
+            void (*words)(const uint64_t*, size_t, uint64_t*) =
+                probe == PROBE_FOLD ? k_poseidon_probe_words<PROBE_FOLD> : probe == PROBE_FOLD_TY ? k_poseidon_probe_words<PROBE_FOLD_TY> :
+                probe == PROBE_SBOX7 ? k_poseidon_probe_words<PROBE_SBOX7> : probe == PROBE_SBOX_DELTA ? k_poseidon_probe_words<PROBE_SBOX_DELTA> :
+                                                                                                        k_poseidon_probe_words<PROBE_ADD_RC0>;
+            hipLaunchKernelGGL(words, grid, block, 0, c->stream, din.as<uint64_t>(), n, dout.as<uint64_t>());
+        }
+        ZKM_HIP_CHECK(hipGetLastError());
+        ZKM_HIP_CHECK(hipMemcpyAsync(out, dout.p, out_words * 8, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+    });
+}
