@@ -36,6 +36,9 @@ typedef struct zkm_batch zkm_batch;
 int zkm_ctx_create(int device, zkm_ctx** out, char** err);
 void zkm_ctx_destroy(zkm_ctx* ctx);
 int zkm_ctx_synchronize(zkm_ctx* ctx, char** err);
+/* times a host thread has waited for this context's stream since it was created (the calls that promise a number of waits are
+ * checked by the difference around them) */
+uint64_t zkm_ctx_host_waits(const zkm_ctx* ctx);
 /* the hipStream_t every kernel of this context is launched on (for event timing by the host) */
 void* zkm_ctx_stream(zkm_ctx* ctx);
 /* Device memory held by the context's caching allocator: bytes in live allocations (DeviceBuffers, batches, scratch of a call in
@@ -102,6 +105,11 @@ void zkm_ctx_trim(zkm_ctx* ctx);
  *                               of more than the memory budget holds, in consecutive waves, and a pool deals groups to its workers: there
  *                               each wave / group is verified and handed out on its own.)
  *                               Default 0: no launch is added and every proof word stays what it is
+ *   "boot_chain_quad"           1: the sponge chains of the zkm_*_boot calls run their permutation across a quad of lanes (sixteen chains a
+ *                               wave) instead of a 16-lane row (four a wave); the words are the same.  Default 0: the row form --
+ *                               a chain of 129 permutations took 1.43 ms in the row form and 2.11 ms in the quad form on an MI355X, at
+ *                               16, 64 and 256 pages alike (profiles/boot_time.json).  A measurement aid: tools/boot_time.py sets it to
+ *                               time both, nothing else should
  *   "debug_verify_flip"         TEST HOOK, accepted only when the process environment holds ZKM_ENABLE_TEST_HOOKS=1 (an unknown key otherwise):
  *                               under "verify", word `value` (0: off) of the blobs of segment 1 of the call (segment 0 of a call of one) is
  *                               increased by one mod p between proving and verifying (tests/test_gpu_verify.py)
@@ -725,6 +733,56 @@ int zkm_segment_ops_stage(zkm_ctx* ctx, const zkm_segment_ops* ops, zkm_staged_o
 int zkm_staged_ops_get(zkm_staged_ops* staged, zkm_segment_ops* ops_out);
 int zkm_staged_ops_ready(zkm_staged_ops* staged, int wait);
 void zkm_staged_ops_free(zkm_staged_ops* staged);
+
+/* ------------------------------------------------------------------ a segment's bootstrap kernel from its image
+ * generate_bootstrap_kernel (prover/src/cpu/bootstrap_kernel.rs:26-306, the first thing generate_traces does) on the device: the rows
+ * that write the segment's memory image into (context 0, Segment::Code) eight words a row, the Poseidon sponge over each 4 KiB page
+ * with the check of its digest against the image's hash words (the root page against pre_hash_root), and the image id over the root
+ * and the entry pc.  Everything it pushes into Traces is a function of the image, so the caller hands over 8 bytes a word instead of
+ * the CPU rows, memory operations, Poseidon inputs and sponge operations made from them (about 530 KB a page).  Bootstrap only: the
+ * reference's exit kernel has no caller and is not built.
+ *   addrs / values   the image as nwords pairs in BTreeMap order: addrs strictly ascending multiples of 4; host or device memory
+ *   npages           addresses with addr & 0xFFF == 0 (checked on the device); each is hashed as a page, absent words reading as 0
+ *   check            nonzero: the three assert_eq of the reference (page hash, root hash, image id) refuse the call
+ * With R = ceil(nwords / 8) and P = npages the bootstrap gives R + P + 3 CPU rows, nwords + 4096 P + 45 memory operations, 129 P + 2
+ * Poseidon inputs and P + 1 sponge operations of 129 P + 2 rows (zkm_boot_counts; pure, any pointer may be NULL), all of them BEFORE
+ * what simulate_cpu pushes. */
+typedef struct zkm_boot_image {
+    const uint32_t* addrs; const uint32_t* values; size_t nwords;
+    size_t npages;
+    uint32_t entry, check;
+    uint8_t pre_hash_root[32], pre_image_id[32];
+} zkm_boot_image;
+void zkm_boot_counts(const zkm_boot_image* image, size_t* cpu_rows, size_t* memory_ops, size_t* poseidon_inputs, size_t* sponge_ops,
+                     size_t* sponge_rows);
+/* zkm_segment[s]_tables / zkm_prove_segment[s]_ops with the bootstrap built from `image` (one per segment) in front of `ops`:
+ *   ops   what simulate_cpu pushed only; its CPU rows carry clocks from R + P + 3 on and are transposed behind the bootstrap's rows, its
+ *         Poseidon inputs, sponge operations and memory operations follow the bootstrap's.  (R + P + 3) + ops->ncpu_rows must be a power
+ *         of two; nmemory may be 0.  The device pointers of zkm_staged_ops_get are accepted as ops; images themselves are not staged,
+ *         and the pool takes none.
+ * Heights are those of into_tables on the joined lists; "check_ctls", "verify", waves, memory budget and sizing mode as in the calls
+ * without an image, and so are the three host waits whatever K: the sponge chains run on a second stream beside the Memory, Arithmetic
+ * and Logic tables, and the digest checks ride on the third wait (sizing mode therefore makes the first two kinds of refusal only).
+ * Refused (nonzero; the message names the segment's position in calls of several, the table "Cpu" and the address):
+ *   an address that is not a multiple of 4 above the one before it; npages that is not the image's count; a page whose hash words at
+ *   0x80000000 + ((addr >> 12) << 5) are not all in the image; with `check`, a page hash, root hash or image id mismatch; a row count
+ *   that is not a power of two.
+ * A refusal leaves the context usable and its live memory as it was. */
+int zkm_segment_tables_boot(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_boot_image* image, const zkm_segment_ops* ops, unsigned* log_n_out,
+                            zkm_staged** out, char** err);
+int zkm_segments_tables_boot(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_segment_ops* ops,
+                             unsigned* log_n_out, zkm_staged** out, char** err);
+int zkm_prove_segment_ops_boot(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_boot_image* image, const zkm_segment_ops* ops,
+                               const uint64_t* public_values, size_t npublic, uint64_t* proofs_out, size_t* proof_offsets_out,
+                               uint64_t* ctl_challenges_out, char** err);
+int zkm_prove_segments_ops_boot(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_segment_ops* ops,
+                                const uint64_t* const* public_values, const size_t* npublic, uint64_t* const* proofs_out,
+                                size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
+/* The bootstrap's kernels alone (tests and tools): device outputs sized by zkm_boot_counts -- cpu_rows_out cpu_rows x ZKM_CPU_COLS words
+ * row-major, memory_ops_out memory_ops x 6 words (zkm_memory_trace's layout), poseidon_inputs_out n x 12 with poseidon_ts_out n,
+ * digests_out sponge_ops x 4.  Refusals as above.  Two host waits. */
+int zkm_boot_witness(zkm_ctx* ctx, const zkm_boot_image* image, uint64_t* cpu_rows_out, uint64_t* memory_ops_out, uint64_t* poseidon_inputs_out,
+                     uint64_t* poseidon_ts_out, uint64_t* digests_out, char** err);
 
 /* ------------------------------------------------------------------ one process, many GPUs: a pool of contexts
  * The reference drives all segments of a program from ONE process (prover/examples/utils/src/utils.rs:57-68 prove_single_seg_common,

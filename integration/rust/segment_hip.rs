@@ -9,8 +9,12 @@
 //!
 //!     impl Operation { pub(crate) fn hip_words(&self) -> [u32; 3] { [self.operator as u32, self.input0, self.input1] } }
 //!
+//! With `boot_image_from_segment` (boot_hip.rs) the bootstrap kernel (cpu/bootstrap_kernel.rs:26-306) is not generated on the host at all: the zkm_*_boot
+//! calls build its rows from the segment's image, and `generate_traces` then pushes only what `simulate_cpu` does (bootstrap only: the
+//! reference's exit kernel has no caller).
+//!
 //! (Op is And, Or, Xor, Nor in that order: the op codes 0 .. 3 of zkm_logic_trace.)  The reference items used here are checked by
-//! tests/test_rust_segment_names.py and tests/test_rust_segments_ops_names.py.  NOT COMPILED in the build image (no cargo / rustc there).
+//! tests/test_rust_segment_names.py, tests/test_rust_segments_ops_names.py and tests/test_rust_boot_names.py.  NOT COMPILED in the build image (no cargo / rustc there).
 use anyhow::{ensure, Result};
 use plonky2::field::types::PrimeField64;
 use plonky2::hip::sys::*;
@@ -217,7 +221,7 @@ pub type SegmentProofs = Vec<(Vec<u64>, [usize; 13], Vec<u64>)>;
 
 /// The two calls of a K-segment entry point -- sizing, then proving into buffers of those sizes -- behind one closure:
 /// `call(public_values, npublic, proofs_out, proof_offsets_out, ctl_challenges_out, err)`.
-fn size_then_prove(nseg: usize, public_values: &[&[u64]], num_challenges: usize,
+pub(crate) fn size_then_prove(nseg: usize, public_values: &[&[u64]], num_challenges: usize,
                    call: impl Fn(*const *const u64, *const usize, *const *mut u64, *mut usize, *const *mut u64, *mut *mut std::os::raw::c_char) -> i32)
                    -> Result<SegmentProofs> {
     ensure!(public_values.len() == nseg, "{} public value lists for {} segments", public_values.len(), nseg);

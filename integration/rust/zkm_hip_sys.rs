@@ -108,6 +108,14 @@ pub struct ZkmVerifyReport {
     pub code: u32, pub table: u32, pub challenge: u32, pub query: u32, pub tree: u32, pub layer: u32, pub ctl: u32, pub host_waits: u32,
 }
 pub type zkm_verify_report = ZkmVerifyReport;
+/// a segment's memory image for the zkm_*_boot calls (include/zkm_hip.h; compared with `abi_layout boot` by tests/test_boot_abi.py):
+/// the bootstrap kernel's part of Traces is built from it on the device
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct ZkmBootImage {
+    pub addrs: *const u32, pub values: *const u32, pub nwords: usize, pub npages: usize, pub entry: u32, pub check: u32,
+    pub pre_hash_root: [u8; 32], pub pre_image_id: [u8; 32],
+}
+pub type zkm_boot_image = ZkmBootImage;
 pub const ZKM_VERIFY_OK: u32 = 0; pub const ZKM_VERIFY_SHAPE: u32 = 1; pub const ZKM_VERIFY_TRANSCRIPT_STATE: u32 = 2;
 pub const ZKM_VERIFY_CTL_CHALLENGES: u32 = 3; pub const ZKM_VERIFY_QUOTIENT: u32 = 4; pub const ZKM_VERIFY_POW: u32 = 5;
 pub const ZKM_VERIFY_INITIAL_MERKLE: u32 = 6; pub const ZKM_VERIFY_FRI_EVAL: u32 = 7; pub const ZKM_VERIFY_FRI_MERKLE: u32 = 8;
@@ -265,6 +273,23 @@ extern "C" {
     pub fn zkm_prove_segments_ops(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, ops: *const zkm_segment_ops,
                                   public_values: *const *const u64, npublic: *const usize, proofs_out: *const *mut u64,
                                   proof_offsets_out: *mut usize, ctl_challenges_out: *const *mut u64, err: *mut *mut c_char) -> c_int;
+    // the same calls with each segment's bootstrap kernel built from its image in front of the caller's lists
+    pub fn zkm_boot_counts(image: *const zkm_boot_image, cpu_rows: *mut usize, memory_ops: *mut usize, poseidon_inputs: *mut usize,
+                           sponge_ops: *mut usize, sponge_rows: *mut usize);
+    pub fn zkm_segment_tables_boot(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, image: *const zkm_boot_image, ops: *const zkm_segment_ops,
+                                   log_n_out: *mut c_uint, out: *mut *mut zkm_staged, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_segments_tables_boot(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, images: *const zkm_boot_image,
+                                    ops: *const zkm_segment_ops, log_n_out: *mut c_uint, out: *mut *mut zkm_staged, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_prove_segment_ops_boot(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, image: *const zkm_boot_image, ops: *const zkm_segment_ops,
+                                      public_values: *const u64, npublic: usize, proofs_out: *mut u64, proof_offsets_out: *mut usize,
+                                      ctl_challenges_out: *mut u64, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_prove_segments_ops_boot(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, images: *const zkm_boot_image,
+                                       ops: *const zkm_segment_ops, public_values: *const *const u64, npublic: *const usize,
+                                       proofs_out: *const *mut u64, proof_offsets_out: *mut usize, ctl_challenges_out: *const *mut u64,
+                                       err: *mut *mut c_char) -> c_int;
+    pub fn zkm_boot_witness(ctx: *mut zkm_ctx, image: *const zkm_boot_image, cpu_rows_out: *mut u64, memory_ops_out: *mut u64,
+                            poseidon_inputs_out: *mut u64, poseidon_ts_out: *mut u64, digests_out: *mut u64, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_ctx_host_waits(ctx: *const zkm_ctx) -> u64;
     // staged operations: the next call's lists uploaded behind the current proofs
     pub fn zkm_segment_ops_stage(ctx: *mut zkm_ctx, ops: *const zkm_segment_ops, out: *mut *mut zkm_staged_ops, err: *mut *mut c_char) -> c_int;
     pub fn zkm_staged_ops_get(staged: *mut zkm_staged_ops, ops_out: *mut zkm_segment_ops) -> c_int;

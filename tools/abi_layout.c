@@ -73,9 +73,31 @@ static void print_verify(void) {
     printf("\n}\n");
 }
 
+/* `abi_layout boot`: the struct of the zkm_*_boot calls (tests/test_boot_abi.py compares it with its mirrors); on request only, as above. */
+static void print_boot(void) {
+    int first_struct = 1, first_field = 1;
+    int (*tables)(zkm_ctx*, const zkm_stark_config*, size_t, const zkm_boot_image*, const zkm_segment_ops*, unsigned*, zkm_staged**, char**) = 0;
+    int (*prove)(zkm_ctx*, const zkm_stark_config*, size_t, const zkm_boot_image*, const zkm_segment_ops*, const uint64_t* const*, const size_t*,
+                 uint64_t* const*, size_t*, uint64_t* const*, char**) = 0;
+    int (*witness)(zkm_ctx*, const zkm_boot_image*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, char**) = 0;
+    (void)sizeof(tables = zkm_segments_tables_boot);
+    (void)sizeof(prove = zkm_prove_segments_ops_boot);
+    (void)sizeof(witness = zkm_boot_witness);
+    printf("{");
+    BEGIN(zkm_boot_image);
+    FIELD(zkm_boot_image, addrs); FIELD(zkm_boot_image, values); FIELD(zkm_boot_image, nwords); FIELD(zkm_boot_image, npages);
+    FIELD(zkm_boot_image, entry); FIELD(zkm_boot_image, check); FIELD(zkm_boot_image, pre_hash_root); FIELD(zkm_boot_image, pre_image_id);
+    END();
+    printf("\n}\n");
+}
+
 int main(int argc, char** argv) {
     int first_struct = 1, first_field = 1;
     check_segments_ops_prototypes();
+    if (argc > 1 && argv[1][0] == 'b') {
+        print_boot();
+        return 0;
+    }
     if (argc > 1 && argv[1][0] == 'c') {
         print_check_ctls();
         return 0;

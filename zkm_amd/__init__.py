@@ -55,6 +55,8 @@ EXPORTS = [
     "zkm_segments_tables", "zkm_prove_segments_ops", "zkm_pool_prove_segments_ops",
     "zkm_segment_ops_stage", "zkm_staged_ops_get", "zkm_staged_ops_ready", "zkm_staged_ops_free",
     "zkm_check_ctls", "zkm_segment_check_ctls",
+    "zkm_ctx_host_waits", "zkm_boot_counts", "zkm_boot_witness", "zkm_segment_tables_boot", "zkm_segments_tables_boot", "zkm_prove_segment_ops_boot",
+    "zkm_prove_segments_ops_boot",
     "zkm_verify_proofs", "zkm_verify_segments", "zkm_verify_single_table",
 ]
 
@@ -131,6 +133,17 @@ SEGMENT_OPS_GROUPS = [
 class SegmentOpsStruct(C.Structure):
     """zkm_segment_ops: a segment's raw operations, one group per field of the reference's Traces (witness/traces.rs:47-62)."""
     _fields_ = [f for _, ptrs, count in SEGMENT_OPS_GROUPS for f in [(name, C.c_void_p) for name, _ in ptrs] + [(count, C.c_size_t)]]
+
+
+class BootImageStruct(C.Structure):
+    """zkm_boot_image: a segment's memory image with its root, image id and entry pc (include/zkm_hip.h)."""
+    _fields_ = [("addrs", C.c_void_p), ("values", C.c_void_p), ("nwords", C.c_size_t), ("npages", C.c_size_t), ("entry", C.c_uint32),
+                ("check", C.c_uint32), ("pre_hash_root", C.c_uint8 * 32), ("pre_image_id", C.c_uint8 * 32)]
+
+
+def abi_mirrors_boot():
+    """The struct of the zkm_*_boot calls -> its mirror; tests/test_boot_abi.py compares it with `tools/abi_layout boot`."""
+    return {"zkm_boot_image": BootImageStruct}
 
 
 class CtlLocation(C.Structure):
@@ -291,6 +304,18 @@ def load():
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                   C.POINTER(C.c_void_p), err]),
         "zkm_segment_ops_stage": (C.c_int, [cp, C.POINTER(SegmentOpsStruct), cpp, err]),
+        "zkm_ctx_host_waits": (C.c_uint64, [cp]),
+        "zkm_boot_counts": (None, [C.POINTER(BootImageStruct)] + [C.POINTER(C.c_size_t)] * 5),
+        "zkm_boot_witness": (C.c_int, [cp, C.POINTER(BootImageStruct), cp, cp, cp, cp, cp, err]),
+        "zkm_segment_tables_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct),
+                                              C.POINTER(C.c_uint), cpp, err]),
+        "zkm_segments_tables_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct),
+                                               C.POINTER(C.c_uint), cpp, err]),
+        "zkm_prove_segment_ops_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct), u64p,
+                                                 C.c_size_t, u64p, C.POINTER(C.c_size_t), u64p, err]),
+        "zkm_prove_segments_ops_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct),
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_void_p), err]),
         "zkm_staged_ops_get": (C.c_int, [cp, C.POINTER(SegmentOpsStruct)]),
         "zkm_staged_ops_ready": (C.c_int, [cp, C.c_int]),
         "zkm_staged_ops_free": (None, [cp]),
@@ -541,6 +566,43 @@ class SegmentOps:
         return st
 
 
+class BootImage:
+    """A segment's memory image for the *_boot calls (include/zkm_hip.h zkm_boot_image): the bootstrap kernel's CPU rows, memory
+    operations, Poseidon inputs and sponge rows are built from it on the device.  addrs / values: uint32 numpy arrays (or DeviceBuffers
+    with nwords given) in ascending address order; root / image_id: 32 bytes each; npages: the page-aligned addresses, counted here
+    when the addresses are a numpy array.  check: refuse a page hash, root hash or image id that does not match."""
+
+    def __init__(self, addrs, values, root, image_id, entry, check=True, npages=None, nwords=None):
+        host = not isinstance(addrs, DeviceBuffer)
+        self.addrs = np.ascontiguousarray(addrs, dtype=np.uint32).reshape(-1) if host else addrs
+        self.values = values if isinstance(values, DeviceBuffer) else np.ascontiguousarray(values, dtype=np.uint32).reshape(-1)
+        self.nwords = int(self.addrs.size if host else nwords)
+        self.npages = int(np.count_nonzero((self.addrs & 0xFFF) == 0)) if npages is None else int(npages)
+        self.root, self.image_id, self.entry, self.check = bytes(root), bytes(image_id), int(entry), bool(check)
+        assert len(self.root) == 32 and len(self.image_id) == 32
+
+    @classmethod
+    def from_dict(cls, image, root, image_id, entry, **kw):
+        """image: {addr: value} (the reference's BTreeMap<u32, u32>)."""
+        addrs = sorted(image)
+        return cls(np.array(addrs, dtype=np.uint32), np.array([image[a] for a in addrs], dtype=np.uint32), root, image_id, entry, **kw)
+
+    def struct(self):
+        st = BootImageStruct()
+        st.addrs = self.addrs.ptr if isinstance(self.addrs, DeviceBuffer) else self.addrs.ctypes.data
+        st.values = self.values.ptr if isinstance(self.values, DeviceBuffer) else self.values.ctypes.data
+        st.nwords, st.npages, st.entry, st.check = self.nwords, self.npages, self.entry, int(self.check)
+        st.pre_hash_root[:] = self.root
+        st.pre_image_id[:] = self.image_id
+        return st
+
+    def counts(self):
+        """zkm_boot_counts: (cpu_rows, memory_ops, poseidon_inputs, sponge_ops, sponge_rows) of the bootstrap."""
+        out = [C.c_size_t() for _ in range(5)]
+        load().zkm_boot_counts(C.byref(self.struct()), *[C.byref(x) for x in out])
+        return tuple(int(x.value) for x in out)
+
+
 class StagedOps:
     """zkm_staged_ops: a segment's raw operations on their way into HBM behind the context's current work (include/zkm_hip.h "Staged
     operations").  ops() is the same segment with device pointers, for segment[s]_tables / prove_segment[s]_ops of the SAME context;
@@ -589,9 +651,12 @@ class StagedOps:
 class _marshal_ops:
     """The argument arrays of zkm_[pool_]prove_segments_ops for a list of SegmentOps and one array of public values per segment."""
 
-    def __init__(self, ops_list, public_values, cfg):
+    def __init__(self, ops_list, public_values, cfg, images=None):
         K = len(ops_list)
         self.keep = list(ops_list)
+        if images is not None:
+            assert len(images) == K, "one image per segment"
+            self.im = (BootImageStruct * max(K, 1))(*[i.struct() for i in images])
         self.st = (SegmentOpsStruct * max(K, 1))(*[o.struct() for o in ops_list])
         pv = list(public_values) if public_values is not None else [()] * K
         assert len(pv) == K, "one array of public values per segment"
@@ -770,6 +835,10 @@ class Context:
         live, cached = C.c_size_t(), C.c_size_t()
         self.L.zkm_ctx_memory(self.h, C.byref(live), C.byref(cached))
         return live.value, cached.value
+
+    def host_waits(self):
+        """zkm_ctx_host_waits: how often a host thread has waited for this context's stream so far."""
+        return int(self.L.zkm_ctx_host_waits(self.h))
 
     def resident_bytes(self):
         """Of the live bytes: tables kept for reuse (twiddles, power tables; the commit lanes' included)."""
@@ -1131,6 +1200,63 @@ class Context:
         m, err = _marshal_ops(ops_list, public_values, cfg), C.c_char_p()
         _check(self.L.zkm_prove_segments_ops(self.h, C.byref(cfg), m.K, m.st, m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
         return [list(m.offs[13 * s:13 * s + 13]) for s in range(m.K)]
+
+    # ---- the same calls with each segment's bootstrap kernel built from its image (include/zkm_hip.h "a segment's bootstrap kernel")
+    def boot_witness(self, image):
+        """zkm_boot_witness: the bootstrap's kernels alone.  Returns numpy (cpu_rows nboot x 259, memory_ops n x 6, poseidon_inputs
+        n x 12, poseidon_timestamps n, digests (npages + 1) x 4)."""
+        rows, mem, po, _, _ = image.counts()
+        bufs = [self.alloc(max(n, 1)) for n in (rows * 259, mem * 6, po * 12, po, (image.npages + 1) * 4)]
+        try:
+            st, err = image.struct(), C.c_char_p()
+            _check(self.L.zkm_boot_witness(self.h, C.byref(st), *[C.c_void_p(b.ptr) for b in bufs], C.byref(err)), err)
+            shapes = ((rows, 259), (mem, 6), (po, 12), (po,), (image.npages + 1, 4))
+            return tuple(b.download()[:int(np.prod(sh))].reshape(sh) for b, sh in zip(bufs, shapes))
+        finally:
+            for b in bufs:
+                b.free()
+
+    def segment_tables_boot(self, image, ops, cfg=None, sizing=False):
+        """zkm_segment_tables_boot: segment_tables with the bootstrap of `image` (a BootImage) in front of ops.  Returns (staged,
+        log_ns); sizing=True: the log heights only."""
+        cfg = cfg or self.standard_config()
+        im, st, lg, h, err = image.struct(), ops.struct(), (C.c_uint * 12)(), C.c_void_p(), C.c_char_p()
+        _check(self.L.zkm_segment_tables_boot(self.h, C.byref(cfg), C.byref(im), C.byref(st), lg, None if sizing else C.byref(h), C.byref(err)), err)
+        return list(lg) if sizing else (StagedTrace(self, h, 0), list(lg))
+
+    def segments_tables_boot(self, images, ops_list, cfg=None):
+        """zkm_segments_tables_boot: K segments in one call.  Returns [(staged, log_ns)], each staged freed on its own."""
+        cfg = cfg or self.standard_config()
+        K = len(ops_list)
+        assert len(images) == K, "one image per segment"
+        im = (BootImageStruct * max(K, 1))(*[i.struct() for i in images])
+        st = (SegmentOpsStruct * max(K, 1))(*[o.struct() for o in ops_list])
+        lg, hs, err = (C.c_uint * (12 * max(K, 1)))(), (C.c_void_p * max(K, 1))(), C.c_char_p()
+        _check(self.L.zkm_segments_tables_boot(self.h, C.byref(cfg), K, im, st, lg, hs, C.byref(err)), err)
+        return [(StagedTrace(self, C.c_void_p(hs[s]), 0), list(lg[12 * s:12 * s + 12])) for s in range(K)]
+
+    def prove_segment_ops_boot(self, image, ops, public_values=(), cfg=None):
+        """zkm_prove_segment_ops_boot: prove_segment_ops with the bootstrap of `image` in front of ops."""
+        cfg = cfg or self.standard_config()
+        im, st, err = image.struct(), ops.struct(), C.c_char_p()
+        pub = np.ascontiguousarray(public_values, dtype=np.uint64)
+        offs = (C.c_size_t * 13)()
+        _check(self.L.zkm_prove_segment_ops_boot(self.h, C.byref(cfg), C.byref(im), C.byref(st), pub.ctypes.data_as(u64p), pub.size, None, offs,
+                                                 None, C.byref(err)), err)
+        proofs = np.zeros(offs[12], dtype=np.uint64)
+        chal = np.zeros(2 * cfg.num_challenges, dtype=np.uint64)
+        _check(self.L.zkm_prove_segment_ops_boot(self.h, C.byref(cfg), C.byref(im), C.byref(st), pub.ctypes.data_as(u64p), pub.size,
+                                                 proofs.ctypes.data_as(u64p), offs, chal.ctypes.data_as(u64p), C.byref(err)), err)
+        return proofs, chal, list(offs)
+
+    def prove_segments_ops_boot(self, images, ops_list, public_values=None, cfg=None):
+        """zkm_prove_segments_ops_boot: K segments, each with its bootstrap, built in one set of launches and proven in lock-step."""
+        cfg = cfg or self.standard_config()
+        m, err = _marshal_ops(ops_list, public_values, cfg, images), C.c_char_p()
+        _check(self.L.zkm_prove_segments_ops_boot(self.h, C.byref(cfg), m.K, m.im, m.st, m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
+        m.alloc()
+        _check(self.L.zkm_prove_segments_ops_boot(self.h, C.byref(cfg), m.K, m.im, m.st, m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
+        return m.results()
 
     def stage_segment_ops(self, ops):
         """zkm_segment_ops_stage: queue the upload of a segment's lists behind the context's current work and return at once.  The

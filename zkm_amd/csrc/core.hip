@@ -83,30 +83,33 @@ void zkm_ctx::shrink_down() {
     down_cap = 0;
     ensure_down(XFER_DOWN);
 }
-// The upload streams go as well (created again on first use): an idle stream still holds one of the runtime's hardware queues, and a GPU
-// whose queues are oversubscribed by idle contexts runs everybody's launches slower -- bench.py's small-segment extra, a fresh process,
-// fell from 105 to 95 segments/s next to four parked contexts with two copy streams each (round 6).
+// The upload streams and the side stream go as well (created again on first use): an idle stream still holds one of the runtime's
+// hardware queues, and a GPU whose queues are oversubscribed by idle contexts runs everybody's launches slower -- bench.py's
+// small-segment extra, a fresh process, fell from 105 to 95 segments/s next to four parked contexts with two copy streams each (round 6).
 void zkm_ctx::drop_copy_streams() {
-    hipStream_t a, b;
+    hipStream_t a, b, d;
     {
         std::lock_guard<std::mutex> g(alloc_mu);
-        a = copy_stream; b = copy_stream2;
-        copy_stream = copy_stream2 = nullptr;
+        a = copy_stream; b = copy_stream2; d = side_stream;
+        copy_stream = copy_stream2 = side_stream = nullptr;
     }
-    for (hipStream_t st : {a, b})
+    for (hipStream_t st : {a, b, d})
         if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
 }
 // (published under the allocator's lock: a relative's out-of-memory path reads it from its own thread, trim_self)
-hipStream_t zkm_ctx::ensure_copy_stream(int k) {
-    hipStream_t& cs = k ? copy_stream2 : copy_stream;
+static hipStream_t ensure_stream(zkm_ctx* c, hipStream_t& cs) {
     if (!cs) {
         hipStream_t st = nullptr;
         ZKM_HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        std::lock_guard<std::mutex> g(alloc_mu);
+        std::lock_guard<std::mutex> g(c->alloc_mu);
         cs = st;
     }
     return cs;
 }
+hipStream_t zkm_ctx::ensure_copy_stream(int k) { return ensure_stream(this, k ? copy_stream2 : copy_stream); }
+// The second compute stream: kernels only (the bootstrap's sponge chains), never an upload.  Only the *_boot calls create it, so a
+// process that never builds a bootstrap holds no queue for it; trim() gives it back with the upload streams.
+hipStream_t zkm_ctx::ensure_side_stream() { return ensure_stream(this, side_stream); }
 void zkm_ctx::trim() {   // public: between calls (zkm_ctx_trim)
     trim_self();
     shrink_down();
@@ -513,6 +516,7 @@ void zkm_ctx_destroy(zkm_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     if (c->copy_stream2) { (void)hipStreamSynchronize(c->copy_stream2); (void)hipStreamDestroy(c->copy_stream2); }
+    if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
     for (auto& kv : c->free_blocks) (void)hipFree(kv.second);
     for (auto& kv : c->live_blocks) (void)hipFree(kv.first);
     for (auto& r : c->prof) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
@@ -557,6 +561,7 @@ int zkm_ctx_set_tuning(zkm_ctx* c, const char* key, uint64_t value, char** err) 
             }
             else if (k == "check_ctls") x->check_ctls = value ? 1 : 0;
             else if (k == "verify") x->verify = value ? 1 : 0;
+            else if (k == "boot_chain_quad") x->boot_chain_quad = value ? 1 : 0;
             else if (k == "debug_verify_flip") {
                 // test hook, as debug_fail_allocs below
                 const char* hooks = getenv("ZKM_ENABLE_TEST_HOOKS");
@@ -581,6 +586,8 @@ int zkm_ctx_set_tuning(zkm_ctx* c, const char* key, uint64_t value, char** err) 
         for (zkm_ctx* l : c->lanes) set(l);
     });
 }
+
+uint64_t zkm_ctx_host_waits(const zkm_ctx* c) { return c ? c->host_waits : 0; }
 
 int zkm_ctx_synchronize(zkm_ctx* c, char** err) {
     return zkm_api("zkm_ctx_synchronize", c, err, [&] { c->sync(); });

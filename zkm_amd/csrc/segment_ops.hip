@@ -6,7 +6,11 @@
 //   zkm_prove_segments_ops   zkm_segments_tables, zkm_prove_segments on the blocks (lock-step), the blocks freed; in waves when the
 //                            call holds more than ZKM_MAX_SEG segments or more than the memory budget;
 //   zkm_segment_tables, zkm_prove_segment_ops   the one-segment forms (the same builder, K = 1; zkm_prove_segment proves);
-//   zkm_segment_ops_stage    a segment's lists uploaded behind the work in flight, for a later call of the above.
+//   zkm_segment_ops_stage    a segment's lists uploaded behind the work in flight, for a later call of the above;
+//   zkm_*_boot               the same calls with each segment's bootstrap kernel built from its image (bootstrap.hip) in front of the
+//                            caller's lists: the boot's rows are the first of the CPU, Poseidon and PoseidonSponge tables and its
+//                            memory operations the first of the joined list.  Its sponge chains run on the context's side stream
+//                            beside the Memory, Arithmetic and Logic tables; its flags ride on waits (1) and (3).
 //
 // The one kernel here, k_cpu_rows_to_cols, turns the emulator's CPU rows (Vec<CpuColumnsView<F>>: 259 words a row, row-major) into the
 // column-major table of trace_rows_to_poly_values (util.rs:37-46), canonical.  Every other table comes from its existing launcher;
@@ -178,6 +182,8 @@ struct builder {
     std::string what;             // "<entry point>", or "<entry point>: segment <position in the call>" in a call of several
     zkm_ctx* c;
     const zkm_segment_ops* o;     // the caller's lists
+    const zkm_boot_image* im;     // the image whose bootstrap goes in front of them, or null
+    zkm_boot_counts_t bn{};       // ... and what it adds to each list (zeros without an image)
     zkm_segment_ops d{};          // ... and where the device reads them: the caller's device pointers, or places in the staging block
     unsigned lg[NTAB] = {};
     std::vector<uint64_t> ps_row, ks_row;   // first row of each sponge operation
@@ -185,14 +191,17 @@ struct builder {
     const void *d_pso = nullptr, *d_psr = nullptr, *d_kso = nullptr, *d_ksr = nullptr;   // device copies of the offsets and the row offsets
     std::string me_what, ar_what;
     // staging
-    struct upload { list_ref dst; const void* src; size_t off; };
+    struct upload { list_ref dst; const void* src; size_t off, skip; };   // skip: bytes of the bootstrap's part in front (joined lists)
     std::vector<upload> ups;
     bool cpu_host = false;
     size_t cpu_off = 0, piece_rows = 0;
     std::vector<zkm_event> piece_done;
 
-    builder(const char* entry, zkm_ctx* ctx, const zkm_segment_ops* ops, size_t pos, bool label)
-        : what(label ? std::string(entry) + ": segment " + std::to_string(pos) : std::string(entry)), c(ctx), o(ops) {}
+    builder(const char* entry, zkm_ctx* ctx, const zkm_segment_ops* ops, size_t pos, bool label, const zkm_boot_image* image = nullptr)
+        : what(label ? std::string(entry) + ": segment " + std::to_string(pos) : std::string(entry)), c(ctx), o(ops), im(image) {}
+    size_t nmemory() const { return bn.memory_ops + o->nmemory; }
+    size_t nposeidon() const { return bn.poseidon + o->nposeidon; }
+    size_t ncpu_rows() const { return bn.cpu_rows + o->ncpu_rows; }
 
     [[noreturn]] void refuse(int t, const std::string& msg) const { throw std::runtime_error(what + ": " + NAME[t] + ": " + msg); }
     // a height of max(rows, min_rows) rounded up to a power of two; rows = count x per, refused above 2^SEG_MAX_LOG_N
@@ -237,12 +246,22 @@ struct builder {
         need(SES, o.nsha_extend_sponge, {o.sha_extend_sponge_w16, o.sha_extend_sponge_meta});
         need(SC, o.nsha_compress, {o.sha_compress_hx, o.sha_compress_w, o.sha_compress_meta});
         need(SCS, o.nsha_compress_sponge, {o.sha_compress_sponge_hx, o.sha_compress_sponge_w, o.sha_compress_sponge_meta});
-        if (o.ncpu_rows == 0 || (o.ncpu_rows & (o.ncpu_rows - 1)) || o.ncpu_rows > ((size_t)1 << SEG_MAX_LOG_N))
-            refuse(CPU, std::to_string(o.ncpu_rows) + " rows: not a power of two of at most 2^" + std::to_string(SEG_MAX_LOG_N));
-        if (o.nmemory == 0) refuse(ME, "No memory ops?");
-        if (o.nmemory >= ((size_t)1 << 32)) refuse(ME, "2^32 or more memory ops");
+        if (im) {
+            try {
+                bn = zkm_boot_job(c, im).n;
+            } catch (const std::exception& e) {
+                refuse(CPU, std::string("bootstrap image: ") + e.what());
+            }
+        }
+        const size_t rows = ncpu_rows();
+        if (o.ncpu_rows == 0 || (rows & (rows - 1)) || rows > ((size_t)1 << SEG_MAX_LOG_N))
+            refuse(CPU, std::to_string(rows) + " rows" + (im ? " (" + std::to_string(bn.cpu_rows) + " of the bootstrap)" : std::string()) +
+                            ": not a power of two of at most 2^" + std::to_string(SEG_MAX_LOG_N));
+        if (nmemory() == 0) refuse(ME, "No memory ops?");
+        if (nmemory() >= ((size_t)1 << 32)) refuse(ME, "2^32 or more memory ops");
         if (o.narithmetic >= ((size_t)1 << 31)) refuse(AR, "2^31 or more arithmetic ops");
-        ps_rows = sponge_rows(PS, o.poseidon_sponge_off, o.nposeidon_sponge, 32, ps_row);
+        ps_rows = sponge_rows(PS, o.poseidon_sponge_off, o.nposeidon_sponge, 32, ps_row) + bn.poseidon;
+        for (uint64_t& r : ps_row) r += bn.poseidon;      // the bootstrap's sponge rows come first
         ks_rows = sponge_rows(KS, o.keccak_sponge_off, o.nkeccak_sponge, 136, ks_row);
         ps_bytes = o.nposeidon_sponge ? o.poseidon_sponge_off[o.nposeidon_sponge] : 0;
         ks_bytes = o.nkeccak_sponge ? o.keccak_sponge_off[o.nkeccak_sponge] : 0;
@@ -256,8 +275,8 @@ struct builder {
         const zkm_segment_ops& o = *this->o;
         const size_t min_rows = std::max<size_t>((size_t)1 << cfg->cap_height, 64);   // max(num_cap_elements, MIN_TRACE_LEN), traces.rs:246-247
         lg[AR] = height(AR, o.narithmetic, 1, (size_t)1 << 16);
-        lg[CPU] = log2_of(o.ncpu_rows);
-        lg[PO] = height(PO, o.nposeidon, 1, min_rows);
+        lg[CPU] = log2_of(ncpu_rows());
+        lg[PO] = height(PO, nposeidon(), 1, min_rows);
         lg[PS] = height(PS, ps_rows, 1, min_rows);
         lg[KK] = height(KK, o.nkeccak, 24, min_rows);
         lg[KS] = height(KS, ks_rows, 1, min_rows);
@@ -266,7 +285,7 @@ struct builder {
         lg[SC] = height(SC, o.nsha_compress, 65, min_rows);
         lg[SCS] = height(SCS, o.nsha_compress_sponge, 1, min_rows);
         lg[LO] = height(LO, o.nlogic, 1, min_rows);
-        lg[ME] = height(ME, o.nmemory, 1, 1);
+        lg[ME] = height(ME, nmemory(), 1, 1);
     }
     // ---- phase: the segment's part of the staging block, from byte `base`: the CPU rows (host rows only), then every list in host memory.
     // Returns the bytes it takes.
@@ -278,13 +297,18 @@ struct builder {
         cpu_host = write && !zkm_is_device_ptr(o.cpu_rows);
         cpu_off = base;
         size_t at = base + align_up(cpu_host ? o.ncpu_rows * CPU_W * 8 : 0);
-        auto add = [&](const list_ref& l, const void* src) {
-            if (!l.bytes || (!write && !l.sizing)) return;
-            ups.push_back(upload{l, src, at});
-            at += align_up(l.bytes);
+        auto add = [&](const list_ref& l, const void* src, size_t skip = 0) {
+            if (!(l.bytes + skip) || (!write && !l.sizing)) return;
+            ups.push_back(upload{l, src, at, skip});
+            at += align_up(l.bytes + skip);
         };
-        for (const list_ref& l : lists_of(d, ps_bytes, ks_bytes))
-            if (!zkm_is_device_ptr(l.get())) add(l, l.get());
+        // the lists the bootstrap writes the head of are joined in the staging block, wherever the caller's part lies
+        for (const list_ref& l : lists_of(d, ps_bytes, ks_bytes)) {
+            const size_t skip = l.field == (void*)&d.memory_ops ? bn.memory_ops * 48
+                                : l.field == (void*)&d.poseidon_inputs ? bn.poseidon * 96
+                                : l.field == (void*)&d.poseidon_timestamps ? bn.poseidon * 8 : 0;
+            if (skip || !zkm_is_device_ptr(l.get())) add(l, l.get(), skip);
+        }
         const size_t nps = o.nposeidon_sponge ? (o.nposeidon_sponge + 1) * 8 : 0, nks = o.nkeccak_sponge ? (o.nkeccak_sponge + 1) * 8 : 0;
         add(list_ref{&d_pso, nps, false}, o.poseidon_sponge_off);
         add(list_ref{&d_psr, nps, false}, ps_row.data());
@@ -302,7 +326,8 @@ struct builder {
         piece_rows = std::min<size_t>(o.ncpu_rows, std::max<size_t>(8192, o.ncpu_rows / 16));
         for (size_t r0 = 0; r0 < o.ncpu_rows; r0 += piece_rows, turn++) {
             hipStream_t st = (turn & 1) ? c->copy_stream2 : c->copy_stream;
-            ZKM_HIP_CHECK(hipMemcpyAsync((void*)(d.cpu_rows + r0 * CPU_W), o.cpu_rows + r0 * CPU_W, piece_rows * CPU_W * 8, hipMemcpyHostToDevice, st));
+            const size_t here = std::min(piece_rows, o.ncpu_rows - r0);   // (behind a bootstrap the caller's rows are no power of two)
+            ZKM_HIP_CHECK(hipMemcpyAsync((void*)(d.cpu_rows + r0 * CPU_W), o.cpu_rows + r0 * CPU_W, here * CPU_W * 8, hipMemcpyHostToDevice, st));
             piece_done.emplace_back(c);
             piece_done.back().record(st);
         }
@@ -311,21 +336,38 @@ struct builder {
     void put(char* sb, bool sizing) {
         for (const upload& u : ups) {
             if (u.dst.sizing != sizing) continue;
-            ZKM_HIP_CHECK(hipMemcpyAsync(sb + u.off, u.src, u.dst.bytes, hipMemcpyHostToDevice, c->stream));
+            if (u.dst.bytes) ZKM_HIP_CHECK(hipMemcpyAsync(sb + u.off + u.skip, u.src, u.dst.bytes, u.skip ? hipMemcpyDefault : hipMemcpyHostToDevice, c->stream));
             u.dst.set(sb + u.off);
         }
+    }
+    // where a joined list will lie (put sets the same pointer when it queues the caller's part)
+    void point_joined(char* sb) {
+        for (const upload& u : ups)
+            if (u.skip) u.dst.set(sb + u.off);
     }
     size_t n(int t) const { return (size_t)1 << lg[t]; }
 };
 
 constexpr size_t SYNC_WORDS = 16;   // per segment: [0, 5) Memory key widths and >= p flag, [5] Memory last op with dummies, [6] Memory row count,
-                                    // [7] Arithmetic rows, [8] Arithmetic flags, [9, 11) three 32-bit validation flags (Logic, Memory, Arithmetic)
+                                    // [7] Arithmetic rows, [8] Arithmetic flags, [9, 11) three 32-bit validation flags (Logic, Memory, Arithmetic),
+                                    // [11, 15) the bootstrap's flags (zkm_boot_seg::flags)
+
+// a failure while the sponge chains run on the side stream: they end before their blocks go back to the allocator
+struct side_join {
+    hipStream_t st = nullptr;
+    ~side_join() {
+        if (st) (void)hipStreamSynchronize(st);
+    }
+};
 
 // K <= ZKM_MAX_SEG checked builders of one context, phase by phase: one staging block, three host waits, one launch per kernel.
 // write = false: sizing only (the heights; the blocks stay empty).
 std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool write) {
     // ---- the staging block: the sync words of every segment, then each segment's part
-    size_t stage_bytes = align_up(K * SYNC_WORDS * 8);
+    size_t stage_bytes = align_up(K * SYNC_WORDS * 8), nboot = 0;
+    for (size_t s = 0; s < K; s++) nboot += b[s].im != nullptr;
+    const size_t desc_off = stage_bytes;     // the bootstraps' descriptors: one set for the early phase and the chains, one for the late phase
+    stage_bytes += align_up(2 * nboot * sizeof(zkm_boot_seg));
     for (size_t s = 0; s < K; s++) stage_bytes += b[s].plan(write, stage_bytes);
     zkm_scratch stage(c, stage_bytes);
     char* sb = stage.as<char>();
@@ -348,6 +390,35 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     for (size_t s = 0; s < K; s++) b[s].copy_cpu_rows(sb, turn);
     ZKM_HIP_CHECK(hipMemsetAsync(d_sync, 0, K * SYNC_WORDS * 8, c->stream));
     for (size_t s = 0; s < K; s++) b[s].put(sb, true);
+    // ---- the bootstraps: every memory operation of theirs (Memory is sized on the joined list), then the sponge chains on the side
+    // stream, joined before the writers that need the states
+    std::vector<zkm_boot_job> bj;
+    zkm_boot_seg* d_desc = (zkm_boot_seg*)(sb + desc_off);
+    side_join side;
+    zkm_event chains_done;
+    bj.reserve(K);
+    for (size_t s = 0; s < K; s++) {
+        bj.emplace_back(c, b[s].im);
+        if (!b[s].im) continue;
+        b[s].point_joined(sb);
+        bj[s].prepare();
+        bj[s].d.flags = (unsigned long long*)(d_sync + s * SYNC_WORDS + 11);
+        bj[s].d.mem = (uint64_t*)b[s].d.memory_ops;
+        bj[s].d.po_in = write ? (uint64_t*)b[s].d.poseidon_inputs : nullptr;
+    }
+    zkm_boot_early(c, bj.data(), K, d_desc);
+    if (nboot && write) {
+        // (a profiled context keeps the chains on the compute stream: the scopes are event pairs on that stream, so "bootstrap/chain_*"
+        // measures the chains only there, and the call then costs the serial sum -- tools/boot_time.py reads the overlap from the difference)
+        const hipStream_t st = c->profiling ? c->stream : c->ensure_side_stream();
+        const zkm_event e(c);
+        e.record(c->stream);
+        ZKM_HIP_CHECK(hipStreamWaitEvent(st, e.e, 0));
+        side.st = st;
+        zkm_boot_chain(c, bj.data(), K, d_desc, st);
+        chains_done = zkm_event(c);
+        chains_done.record(st);
+    }
 
     // ---- Memory and Arithmetic sizing phases; waits (1) and (2)
     std::vector<zkm_memory_job> mj;
@@ -357,7 +428,7 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     for (size_t s = 0; s < K; s++) {
         b[s].me_what = b[s].what + ": " + NAME[ME];
         b[s].ar_what = b[s].what + ": " + NAME[AR];
-        mj.emplace_back(c, b[s].me_what.c_str(), b[s].d.memory_ops, b[s].o->nmemory);
+        mj.emplace_back(c, b[s].me_what.c_str(), b[s].d.memory_ops, b[s].nmemory());
         aj.emplace_back(c, b[s].ar_what.c_str(), b[s].d.arithmetic_ops, b[s].o->narithmetic);
         mj[s].d_acc = (unsigned long long*)(d_sync + s * SYNC_WORDS);
         mj[s].d_count = d_sync + s * SYNC_WORDS + 6;
@@ -368,6 +439,9 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     c->download(sync.data(), d_sync, K * SYNC_WORDS * 8);                                                               // wait (1)
     std::vector<segment_block> out(K);
     const size_t cap = (size_t)1 << SEG_MAX_LOG_N;
+    for (size_t s = 0; s < K; s++)
+        if (b[s].im)
+            if (const std::string m = zkm_boot_refusal_early(bj[s], &sync[s * SYNC_WORDS + 11]); !m.empty()) b[s].refuse(CPU, m);
     for (size_t s = 0; s < K; s++) {
         const size_t ar_n = zkm_arithmetic_height(aj[s], &sync[s * SYNC_WORDS + 7], nullptr);
         if (ar_n > cap) b[s].refuse(AR, "the table needs " + std::to_string(ar_n) + " rows, more than 2^" + std::to_string(SEG_MAX_LOG_N));
@@ -413,8 +487,25 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     using B = const builder&;
     using O = const zkm_segment_ops&;
     // (a Poseidon table without permutations is seed 0 with no inputs: every row is the padding row)
-    writers(PO, [](B b, O o) { return zkm_writer_seg{{o.nposeidon ? b.d.poseidon_inputs : nullptr, o.nposeidon ? b.d.poseidon_timestamps : nullptr}, o.nposeidon}; });
+    // (PoseidonSponge first: its writer zero-fills the table, the bootstrap's rows go in behind it; the bootstrap's timestamps in front of
+    // the Poseidon writer)
     writers(PS, [](B b, O o) { return zkm_writer_seg{{b.d.poseidon_sponge_inputs, b.d_pso, b.d.poseidon_sponge_meta, b.d_psr}, o.nposeidon_sponge}; });
+    if (nboot) {
+        for (size_t s = 0; s < K; s++) {
+            if (!b[s].im) continue;
+            bj[s].d.po_ts = (uint64_t*)b[s].d.poseidon_timestamps;
+            bj[s].d.cpu = T(s, CPU);
+            bj[s].d.cpu_rs = 1;
+            bj[s].d.cpu_cs = b[s].n(CPU);
+            bj[s].d.ps = T(s, PS);
+            bj[s].d.ps_rs = 1;
+            bj[s].d.ps_cs = b[s].n(PS);
+        }
+        ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, chains_done.e, 0));
+        side.st = nullptr;                      // (from here on the compute stream is behind the chains)
+        zkm_boot_late(c, bj.data(), K, d_desc + nboot);
+    }
+    writers(PO, [](B b, O) { return zkm_writer_seg{{b.nposeidon() ? b.d.poseidon_inputs : nullptr, b.nposeidon() ? b.d.poseidon_timestamps : nullptr}, b.nposeidon()}; });
     writers(KK, [](B b, O o) { return zkm_writer_seg{{b.d.keccak_inputs, b.d.keccak_timestamps}, o.nkeccak}; });
     writers(KS, [](B b, O o) { return zkm_writer_seg{{b.d.keccak_sponge_inputs, b.d_kso, b.d.keccak_sponge_meta, b.d_ksr}, o.nkeccak_sponge, 0, b.ks_rows}; });
     writers(SE, [](B b, O o) { return zkm_writer_seg{{b.d.sha_extend_inputs, b.d.sha_extend_timestamps}, o.nsha_extend}; });
@@ -441,13 +532,14 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
         cpu_seg cs[ZKM_MAX_SEG];
         size_t nd = 0;
         for (size_t s = 0; s < K; s++)
-            if (!b[s].cpu_host) cs[nd++] = cpu_seg{b[s].d.cpu_rows, b[s].o->ncpu_rows, 0, b[s].n(CPU), T(s, CPU)};
+            if (!b[s].cpu_host) cs[nd++] = cpu_seg{b[s].d.cpu_rows, b[s].o->ncpu_rows, b[s].bn.cpu_rows, b[s].n(CPU), T(s, CPU)};
         if (nd) launch_cpu_rows_to_cols(c, cs, nd);
         for (size_t s = 0; s < K; s++) {
             if (!b[s].cpu_host) continue;
             for (size_t r0 = 0, k = 0; r0 < b[s].o->ncpu_rows; r0 += b[s].piece_rows, k++) {
                 ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, b[s].piece_done[k].e, 0));
-                const cpu_seg piece{b[s].d.cpu_rows + r0 * CPU_W, b[s].piece_rows, r0, b[s].n(CPU), T(s, CPU)};
+                const cpu_seg piece{b[s].d.cpu_rows + r0 * CPU_W, std::min(b[s].piece_rows, b[s].o->ncpu_rows - r0), b[s].bn.cpu_rows + r0, b[s].n(CPU),
+                                    T(s, CPU)};
                 launch_cpu_rows_to_cols(c, &piece, 1);
             }
         }
@@ -458,6 +550,8 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
         if (f[0]) b[s].refuse(LO, "op code out of range (0 and, 1 or, 2 xor, 3 nor)");
         if (f[1]) b[s].refuse(ME, "a range check is 2^log_n or more (a context or segment gap)");
         if (f[2]) b[s].refuse(AR, "a shared-column value is 2^16 or more");
+        if (b[s].im)
+            if (const std::string m = zkm_boot_refusal_late(bj[s], &sync[s * SYNC_WORDS + 11]); !m.empty()) b[s].refuse(CPU, m);
     }
     return out;
 }
@@ -465,14 +559,14 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
 // the builders of a call: argument checks, every host check of every segment, the host-known heights.  A call of one segment through
 // the one-segment entry points names no position (label = false).
 std::vector<builder> make_builders(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segment_ops* ops, size_t nseg, size_t seg_base,
-                                   bool label) {
+                                   bool label, const zkm_boot_image* images = nullptr) {
     if (!cfg || !ops) throw std::runtime_error(std::string(what) + ": null argument");
     if (nseg == 0) throw std::runtime_error(std::string(what) + ": no segments");
     if (cfg->cap_height > SEG_MAX_LOG_N) throw std::runtime_error(std::string(what) + ": cap_height out of range");
     std::vector<builder> b;
     b.reserve(nseg);
     for (size_t s = 0; s < nseg; s++) {
-        b.emplace_back(what, c, ops + s, seg_base + s, label);
+        b.emplace_back(what, c, ops + s, seg_base + s, label, images ? images + s : nullptr);
         b.back().check_host();
         b.back().heights(cfg);
     }
@@ -505,11 +599,12 @@ struct zkm_staged_ops {
 
 extern "C" {
 
-int zkm_segments_tables(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out,
-                        char** err) {
-    return zkm_api("zkm_segments_tables", c, err, [&] {
-        if (!log_n_out) throw std::runtime_error("zkm_segments_tables: null argument");
-        std::vector<builder> b = make_builders("zkm_segments_tables", c, cfg, ops, nseg, 0, true);
+// the body of zkm_segments_tables[_boot] (images: one per segment, or null)
+static int segments_tables(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
+                           const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out, char** err) {
+    return zkm_api(what, c, err, [&] {
+        if (!log_n_out) throw std::runtime_error(std::string(what) + ": null argument");
+        std::vector<builder> b = make_builders(what, c, cfg, ops, nseg, 0, true, images);
         std::vector<segment_block> blocks;   // (a failure in a later wave releases the earlier waves' blocks: no handle is left behind)
         size_t s0 = 0;
         for (const size_t k : even_waves(nseg, 1)) {
@@ -532,16 +627,26 @@ int zkm_segments_tables(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, co
         std::copy(handles.begin(), handles.end(), out);
     });
 }
+int zkm_segments_tables(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out,
+                        char** err) {
+    return segments_tables("zkm_segments_tables", c, cfg, nseg, nullptr, ops, log_n_out, out, err);
+}
+int zkm_segments_tables_boot(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_segment_ops* ops,
+                             unsigned* log_n_out, zkm_staged** out, char** err) {
+    if (!images) return zkm_fail(err, "zkm_segments_tables_boot: null argument");
+    return segments_tables("zkm_segments_tables_boot", c, cfg, nseg, images, ops, log_n_out, out, err);
+}
 
-int zkm_prove_segments_ops_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops,
-                                 const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, size_t* offsets_out,
-                                 uint64_t* const* challenges, char** err, size_t seg_base) {
+// the body of zkm_prove_segments_ops[_boot] and of the pool's workers (images: one per segment, or null)
+static int prove_segments_ops(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
+                              const zkm_segment_ops* ops, const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs,
+                              size_t* offsets_out, uint64_t* const* challenges, char** err, size_t seg_base) {
     return zkm_api(what, c, err, [&]() -> int {
         if (proofs && !challenges) throw std::runtime_error(std::string(what) + ": null argument");
         if (!proofs && !offsets_out) throw std::runtime_error(std::string(what) + ": null argument");
-        std::vector<builder> b = make_builders(what, c, cfg, ops, nseg, seg_base, true);
-        // ---- the waves: what a segment holds while it is proven (the prover's estimate at the heights the host knows), its tables and
-        // its part of the staging block, against the budget of zkm_prove_segments
+        std::vector<builder> b = make_builders(what, c, cfg, ops, nseg, seg_base, true, images);
+        // ---- the waves: what a segment holds while it is proven (the prover's estimate at the heights the host knows), its tables,
+        // its part of the staging block and its bootstrap's scratch, against the budget of zkm_prove_segments
         size_t nwaves = 1;
         if (proofs && nseg > 1) {
             size_t free_b = 0, total_b = 0, live = 0, cached = 0;
@@ -552,7 +657,7 @@ int zkm_prove_segments_ops_entry(const char* what, zkm_ctx* c, const zkm_stark_c
             for (size_t s = 0; s < nseg; s++) {
                 double tables = 0;
                 for (int t = 0; t < NTAB; t++) tables += 8.0 * (double)(zkm_table_width(TABLE_ID[t]) << b[s].lg[t]);
-                total += zkm_segment_footprint(cfg, b[s].lg) + tables + (double)b[s].plan(true, 0);
+                total += zkm_segment_footprint(cfg, b[s].lg) + tables + (double)b[s].plan(true, 0) + (double)zkm_boot_scratch_bytes(b[s].im);
             }
             nwaves = (size_t)std::min<double>((double)nseg, std::max(1.0, std::ceil(total / std::max(budget, 1.0))));
         }
@@ -580,15 +685,28 @@ int zkm_prove_segments_ops_entry(const char* what, zkm_ctx* c, const zkm_stark_c
     });
 }
 
+int zkm_prove_segments_ops_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops,
+                                 const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, size_t* offsets_out,
+                                 uint64_t* const* challenges, char** err, size_t seg_base) {
+    return prove_segments_ops(what, c, cfg, nseg, nullptr, ops, pub, npub, proofs, offsets_out, challenges, err, seg_base);
+}
 int zkm_prove_segments_ops(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops, const uint64_t* const* pub,
                            const size_t* npub, uint64_t* const* proofs, size_t* offsets_out, uint64_t* const* challenges, char** err) {
-    return zkm_prove_segments_ops_entry("zkm_prove_segments_ops", c, cfg, nseg, ops, pub, npub, proofs, offsets_out, challenges, err, 0);
+    return prove_segments_ops("zkm_prove_segments_ops", c, cfg, nseg, nullptr, ops, pub, npub, proofs, offsets_out, challenges, err, 0);
+}
+int zkm_prove_segments_ops_boot(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_segment_ops* ops,
+                                const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, size_t* offsets_out,
+                                uint64_t* const* challenges, char** err) {
+    if (!images) return zkm_fail(err, "zkm_prove_segments_ops_boot: null argument");
+    return prove_segments_ops("zkm_prove_segments_ops_boot", c, cfg, nseg, images, ops, pub, npub, proofs, offsets_out, challenges, err, 0);
 }
 
-int zkm_segment_tables(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out, char** err) {
-    return zkm_api("zkm_segment_tables", c, err, [&] {
-        if (!ops || !log_n_out) throw std::runtime_error("zkm_segment_tables: null argument");
-        std::vector<builder> b = make_builders("zkm_segment_tables", c, cfg, ops, 1, 0, false);
+// the body of zkm_segment_tables[_boot] (image: or null)
+static int segment_tables(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, const zkm_boot_image* image, const zkm_segment_ops* ops,
+                          unsigned* log_n_out, zkm_staged** out, char** err) {
+    return zkm_api(what, c, err, [&] {
+        if (!ops || !log_n_out) throw std::runtime_error(std::string(what) + ": null argument");
+        std::vector<builder> b = make_builders(what, c, cfg, ops, 1, 0, false, image);
         segment_block sb = std::move(build_wave(c, b.data(), 1, out != nullptr)[0]);
         for (int t = 0; t < NTAB; t++) log_n_out[t] = sb.lg[t];
         if (!out) return;
@@ -596,17 +714,35 @@ int zkm_segment_tables(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segmen
         sb.block.take();
     });
 }
+int zkm_segment_tables(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out, char** err) {
+    return segment_tables("zkm_segment_tables", c, cfg, nullptr, ops, log_n_out, out, err);
+}
+int zkm_segment_tables_boot(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_boot_image* image, const zkm_segment_ops* ops, unsigned* log_n_out,
+                            zkm_staged** out, char** err) {
+    if (!image) return zkm_fail(err, "zkm_segment_tables_boot: null argument");
+    return segment_tables("zkm_segment_tables_boot", c, cfg, image, ops, log_n_out, out, err);
+}
 
-int zkm_prove_segment_ops(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segment_ops* ops, const uint64_t* pub, size_t npub,
-                          uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
-    return zkm_api("zkm_prove_segment_ops", c, err, [&] {
-        if (!ops) throw std::runtime_error("zkm_prove_segment_ops: null argument");
-        std::vector<builder> b = make_builders("zkm_prove_segment_ops", c, cfg, ops, 1, 0, false);
+// the body of zkm_prove_segment_ops[_boot] (image: or null)
+static int prove_segment_ops(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, const zkm_boot_image* image, const zkm_segment_ops* ops,
+                             const uint64_t* pub, size_t npub, uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
+    return zkm_api(what, c, err, [&] {
+        if (!ops) throw std::runtime_error(std::string(what) + ": null argument");
+        std::vector<builder> b = make_builders(what, c, cfg, ops, 1, 0, false, image);
         segment_block sb = std::move(build_wave(c, b.data(), 1, proofs != nullptr)[0]);
         const uint64_t* traces[NTAB] = {};
         for (int t = 0; t < NTAB; t++) traces[t] = proofs ? sb.block.as<const uint64_t>() + sb.off[t] : nullptr;
         return zkm_prove_segment(proofs ? c : nullptr, cfg, traces, sb.lg, pub, npub, proofs, offsets_out, challenges, err);
     });
+}
+int zkm_prove_segment_ops(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segment_ops* ops, const uint64_t* pub, size_t npub,
+                          uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
+    return prove_segment_ops("zkm_prove_segment_ops", c, cfg, nullptr, ops, pub, npub, proofs, offsets_out, challenges, err);
+}
+int zkm_prove_segment_ops_boot(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_boot_image* image, const zkm_segment_ops* ops, const uint64_t* pub,
+                               size_t npub, uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
+    if (!image) return zkm_fail(err, "zkm_prove_segment_ops_boot: null argument");
+    return prove_segment_ops("zkm_prove_segment_ops_boot", c, cfg, image, ops, pub, npub, proofs, offsets_out, challenges, err);
 }
 
 // ---- staged operations: the next call's lists behind the current proofs.  Every byte count is known on the host, so the uploads are

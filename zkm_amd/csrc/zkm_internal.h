@@ -70,7 +70,9 @@ struct zkm_ctx {
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;  // host -> device ingest, overlapped with the compute stream (created on first use)
     hipStream_t copy_stream2 = nullptr; // second upload stream of staged traces (zkm_trace_stage: alternate pieces, two copy engines)
-    size_t ingest_chunk_cols = 32;      // columns per ingest chunk (0 = monolithic upload)           } zkm_ctx_set_tuning
+    hipStream_t side_stream = nullptr;  // the bootstrap's sponge chains beside the other tables' generation (created on first use)
+    int boot_chain_quad = 0;            // the chains' permutation across a quad of lanes instead of a 16-lane row (tools/boot_time.py times both)   } zkm_ctx_set_tuning
+    size_t ingest_chunk_cols = 32;     // columns per ingest chunk (0 = monolithic upload)           } zkm_ctx_set_tuning
     size_t keccak_parts_max_points = (size_t)1 << 15;   // k_quotient_keccak_parts up to this many points  }
     size_t fri_fused_division_min = ~(size_t)0;         // k_seg_scan_final from this many coefficients (default: never -- since the
                                                         // LDS-tiled kernels of round 4 the per-batch scans are faster at every size)  }
@@ -126,8 +128,9 @@ struct zkm_ctx {
     void release(void* p);
     void trim_self();  // hipFree every cached (not live) block of THIS allocator (any thread: used by a relative's out-of-memory retry)
     void trim();       // ... and of the lanes; only between calls
-    void drop_copy_streams();   // trim(): the idle upload streams give their hardware queues back
+    void drop_copy_streams();   // trim(): the idle upload streams and the side stream give their hardware queues back
     hipStream_t ensure_copy_stream(int k = 0);   // upload stream k (0: copy_stream, 1: copy_stream2), created on first use
+    hipStream_t ensure_side_stream();            // side_stream, created on first use
     void shrink_down();   // the pinned download area back to its base size (trim(): between calls, owner's thread)
     void ensure_twiddles(unsigned log_n);
     const gl_t* pow_table(uint64_t shift, unsigned log_n);  // lo: 2^ceil(log_n/2) entries, then hi
@@ -500,6 +503,39 @@ struct zkm_arith_job {
 void zkm_arithmetic_count(zkm_arith_job* j, size_t nseg);
 size_t zkm_arithmetic_height(zkm_arith_job& j, const uint64_t got[2], size_t* natural_rows_out);   // max(2^16, next_pow2(rows)); throws on a flag
 void zkm_arithmetic_write(zkm_arith_job* j, size_t nseg, const unsigned* log_n, gl_t* const* out_dev, unsigned* const* d_bad);
+
+// ---- bootstrap.hip: a segment's bootstrap-kernel witness from its image, in phases (the file's head lists them).  One descriptor per
+// segment, in device memory; a job owns the scratch block the descriptor points into.
+struct zkm_boot_seg {
+    const uint32_t *addrs, *values;              // the image, device
+    uint32_t nwords, npages, rows_image, check;  // rows_image = ceil(nwords / 8)
+    uint32_t id_words[9], want_root[8], want_id[8];   // check_image_id's nine words; the expected digests as LE words
+    uint64_t *post, *digests;                    // state after each permutation (as po_in); (npages + 1) x 4
+    uint32_t *pagew, *blk_count, *page_addr, *page_idx;   // (npages + 1) x 1024 message words; pages per 256 image words; the pages
+    unsigned long long* flags;                   // [0] order / alignment, [1] page count, [2] missing hash word, [3] digest mismatch
+    uint64_t *mem, *po_in, *po_ts;               // outputs: the boot's first memory operation / Poseidon input / timestamp
+    gl_t *cpu, *ps;                              // cell (row r, column k) of the CPU rows at cpu[r cpu_rs + k cpu_cs]; ps likewise, or null
+    size_t cpu_rs, cpu_cs, ps_rs, ps_cs;
+};
+struct zkm_boot_counts_t { size_t rows_image, cpu_rows, memory_ops, poseidon, sponge_ops; };   // poseidon: inputs = sponge rows
+void zkm_boot_sizes(const zkm_boot_image* im, zkm_boot_counts_t* n);
+size_t zkm_boot_scratch_bytes(const zkm_boot_image* im);   // what a job of this image holds beside the joined lists (0 for null)
+struct zkm_boot_job {
+    zkm_ctx* c;
+    const zkm_boot_image* im;                    // null: a segment without a bootstrap (every phase passes it over)
+    zkm_boot_counts_t n{};
+    zkm_scratch scratch;
+    zkm_boot_seg d{};
+    zkm_boot_job(zkm_ctx* ctx, const zkm_boot_image* image);   // the host checks: throws the bare message
+    void prepare();                              // scratch, the image's upload, `d` without flags and outputs (the caller sets those)
+};
+// (nseg <= ZKM_MAX_SEG jobs of one context, ONE launch per kernel; d_desc: room for nseg descriptors, a different one for late than
+// the one the chain may still be reading)
+void zkm_boot_early(zkm_ctx* c, zkm_boot_job* j, size_t nseg, zkm_boot_seg* d_desc);   // needs flags, mem
+void zkm_boot_chain(zkm_ctx* c, zkm_boot_job* j, size_t nseg, const zkm_boot_seg* d_desc, hipStream_t st);   // needs po_in; early's descriptors
+void zkm_boot_late(zkm_ctx* c, zkm_boot_job* j, size_t nseg, zkm_boot_seg* d_desc);    // needs po_ts, cpu, ps
+std::string zkm_boot_refusal_early(const zkm_boot_job& j, const uint64_t flags[4]);    // "" or the message (flags 0, 1: known after early)
+std::string zkm_boot_refusal_late(const zkm_boot_job& j, const uint64_t flags[4]);     // flags 2, 3: known after late
 
 // ctl_check.hip: check_ctls on one segment's tables.  Returns the report's kind (0 consistent, 1 non-binary filter, 2 multisets differ)
 // with the reference's message in *msg; throws when the check cannot be made
