@@ -191,6 +191,18 @@ def test_prove_segment_sizing_and_descriptors(zkm, oracle):
     assert lib.zkm_all_stark_ctls(None, C.byref(n), None, C.byref(ns)) == 0
     assert n.value == 15 and ns.value == sum(len(looking) for looking, _ in ctls)
     assert [lib.zkm_table_enum_index(t) for t in T.TABLE_ENUM_ORDER] == list(range(12)) and lib.zkm_table_enum_index(99) == -1
+    # the library's registry of the tables against the Python model's own copy: widths, order, own lookups
+    assert sorted(T.TABLE_ENUM_ORDER) == list(range(12))
+    for tid in range(12):
+        assert lib.zkm_table_width(tid) == T.WIDTH[tid], tid
+        # ((ncols + 1) / 2 + 1) helper and Z columns per challenge: Memory looks up 1 column, Arithmetic 18
+        want = {T.TABLE_MEMORY: 2, T.TABLE_ARITHMETIC: 10}.get(tid, 0) * cfg.num_challenges
+        assert lib.zkm_num_lookup_columns(tid, C.byref(cfg)) == want, tid
+    for tid in (-1, 12, 99):
+        assert lib.zkm_table_width(tid) == 0 and lib.zkm_table_enum_index(tid) == -1 and lib.zkm_num_lookup_columns(tid, C.byref(cfg)) == 0
+    for name, tid in (("POSEIDON", T.TABLE_POSEIDON), ("KECCAK_SPONGE", T.TABLE_KECCAK_SPONGE), ("LOGIC", T.TABLE_LOGIC), ("MEMORY", T.TABLE_MEMORY),
+                      ("ARITHMETIC", T.TABLE_ARITHMETIC), ("KECCAK", T.TABLE_KECCAK), ("POSEIDON_SPONGE", T.TABLE_POSEIDON_SPONGE)):
+        assert getattr(zkm, name + "_COLS") == lib.zkm_table_width(tid), name
     assert lib.zkm_all_stark_ctl_table(99) is None and lib.zkm_all_stark_ctl_table(T.TABLE_CPU) is not None
     lg[1] = 99  # a table height the library cannot size
     assert lib.zkm_prove_segment(None, C.byref(cfg), ptrs, lg, None, 0, None, offs, None, C.byref(err)) != 0

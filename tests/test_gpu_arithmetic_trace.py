@@ -267,6 +267,11 @@ def test_large_tables(ctx, zkm, log_ops):
     aux = np.concatenate(lk + [ctl_aux])
     assert ctx.check_constraints(trace, log_n, aux, t, zs, ids, [5, 7], ncols=54, table_id=T.TABLE_ARITHMETIC,
                                  lookup_challenges=betas) is None
+    # one challenge: the first challenge's lookup columns, then the CTL columns of its (beta, gamma)
+    zs1, ids1 = make_zs([([cs], 3, 5)])
+    aux1 = np.concatenate([lk[0], ctx.ctl_data(t, zs1, ids1, trace, 54, log_n)])
+    assert ctx.check_constraints(trace, log_n, aux1, t, zs1, ids1, [5], ncols=54, table_id=T.TABLE_ARITHMETIC,
+                                 lookup_challenges=betas[:1]) is None
 
 
 FLAG = {"addu": A.IS_ADDU, "subu": A.IS_SUBU, "addiu": A.IS_ADDIU, "sll": A.IS_SLL, "srl": A.IS_SRL, "sra": A.IS_SRA,

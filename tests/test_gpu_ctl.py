@@ -184,6 +184,31 @@ def test_check_constraints_entry_point(ctx, zkm, oracle):
     tr.free()
 
 
+@pytest.mark.parametrize("enum_index,snake", [(1, "cpu"), (2, "poseidon"), (3, "poseidon_sponge"), (4, "keccak"), (5, "keccak_sponge"), (6, "sha_extend"),
+                                              (7, "sha_extend_sponge"), (8, "sha_compress"), (9, "sha_compress_sponge"), (10, "logic")])
+def test_check_constraints_reaches_each_tables_own_constraints(ctx, enum_index, snake):
+    """The ten tables without lookups of their own, on the traces of the fixture segment (2^3 .. 2^10 rows): their constraints hold with
+    one and with two challenges, and the only quotient_* kernel that ran is the table's own.  (Memory and Arithmetic, with their
+    lookups: test_gpu_memory_trace.py, test_gpu_arithmetic_trace.py.)"""
+    import os
+    from zkm_amd import tables as T
+    seg = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "segment12.npz"))
+    tid, log_n = T.TABLE_ENUM_ORDER[enum_index], int(seg["log_n"][enum_index])
+    trace = seg["t%d" % enum_index]
+    aux = np.zeros(4 << log_n, dtype=np.uint64)          # the fake CTL shape, as above
+    ctx.profile(True)
+    try:
+        for alphas in ([0x1234567 % P], [0x1234567 % P, 0xFEDCBA9876543210 % P]):
+            ctx.profile_reset()
+            assert ctx.check_constraints(trace, log_n, aux, None, [1, 1], None, alphas, ncols=T.WIDTH[tid], table_id=tid) is None
+            ctx.synchronize()
+            ran = {k for k in ctx.profile_records() if k.startswith("quotient_") and k != "quotient_ctl"}
+            assert ran == {"quotient_" + snake}, ran
+    finally:
+        ctx.profile(False)
+        ctx.profile_reset()
+
+
 def test_check_constraints_on_a_table_with_lookups(ctx, zkm, oracle):
     """MemoryStark: its range-check lookup columns (memory_stark.rs:476-483: RANGE_CHECK looked up in COUNTER with FREQUENCIES) come
     first among the auxiliary columns, per challenge helper column then Z (prover.rs:475-508)."""

@@ -302,3 +302,7 @@ def test_2_20_table_range_check_lookup(ctx, zkm, oracle):
     lk = [ctx.lookup_helper_columns(lt, [looking], lt.single(11), lt.single(12), b, trace, 13, log_n) for b in betas]
     aux = np.concatenate(lk + [ctl_aux])
     assert ctx.check_constraints(trace, log_n, aux, t, zs, ids, [5, 7], ncols=13, table_id=T.TABLE_MEMORY, lookup_challenges=betas) is None
+    # one challenge: the first challenge's lookup columns, then the CTL columns of its (beta, gamma)
+    zs1, ids1 = make_zs([([cs], 3, 5)])
+    aux1 = np.concatenate([lk[0], ctx.ctl_data(t, zs1, ids1, trace, 13, log_n)])
+    assert ctx.check_constraints(trace, log_n, aux1, t, zs1, ids1, [5], ncols=13, table_id=T.TABLE_MEMORY, lookup_challenges=betas[:1]) is None

@@ -188,17 +188,24 @@ def test_refusals_name_the_table_and_leave_nothing_behind(ctx, zkm):
                 call()
             assert ctx.memory()[0] == live, table
             ctx.segment_tables(good)[0].free()
-    # a null pointer with a nonzero count, and more CPU rows than 2^28 (refused before any row is read)
-    for field, count, table in (("keccak_inputs", "nkeccak", "Keccak"), ("cpu_rows", "ncpu_rows", "Cpu")):
+    # a null pointer with a nonzero count, more CPU rows than 2^28 and, for every other table with a data-parallel writer, a count that
+    # by itself needs more than 2^28 rows (every one refused before a list is read: the pointers only have to be non-null)
+    somewhere = good.struct().cpu_rows
+    cases = [("Keccak: null pointer with a nonzero count", dict(keccak_inputs=None, nkeccak=3)), ("Cpu", dict(ncpu_rows=1 << 29))]
+    for table, group, rows_per_op in (("Poseidon", "poseidon", 1), ("Keccak", "keccak", 24), ("ShaExtend", "sha_extend", 1),
+                                      ("ShaExtendSponge", "sha_extend_sponge", 48), ("ShaCompress", "sha_compress", 65),
+                                      ("ShaCompressSponge", "sha_compress_sponge", 1), ("Logic", "logic", 1)):
+        lists, count = next((ptrs, count) for name, ptrs, count in zkm.SEGMENT_OPS_GROUPS if name == group)
+        fields = {name: somewhere for name, _ in lists}
+        fields[count] = (1 << 28) // rows_per_op + 1
+        cases.append((table + ": the operations need more than 2^28 rows", fields))
+    for text, fields in cases:
         st = good.struct()
-        if field == "cpu_rows":
-            setattr(st, count, 1 << 29)
-        else:
-            setattr(st, field, None)
-            setattr(st, count, 3)
+        for name, value in fields.items():
+            setattr(st, name, value)
         lg, h, err = (C.c_uint * 12)(), C.c_void_p(), C.c_char_p()
         cfg = ctx.standard_config()
         assert ctx.L.zkm_segment_tables(ctx.h, C.byref(cfg), C.byref(st), lg, C.byref(h), C.byref(err)) == 1
-        assert table in err.value.decode() and not h.value
+        assert text in err.value.decode() and not h.value
         assert ctx.memory()[0] == live
     ctx.segment_tables(good)[0].free()

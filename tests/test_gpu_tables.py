@@ -332,6 +332,52 @@ def test_sha_extend_trace_errors(ctx, zkm):
         ctx.sha_extend_trace(np.zeros((9, 16), dtype=np.uint8), np.zeros(9, dtype=np.uint64), 3)
 
 
+def writer_lists(name, k):
+    """k random operations of a uniform writer entry point, as the lists its Context method (and the oracle's) takes."""
+    rng = np.random.default_rng(k)
+    u32 = lambda *shape: rng.integers(0, 1 << 32, shape, dtype=np.uint64).astype(np.uint32)
+    small = lambda *shape: rng.integers(0, 1 << 30, shape, dtype=np.uint64)      # addresses, contexts, timestamps
+    if name == "poseidon_trace_inputs":
+        return rng.integers(0, 1 << 62, (k, 12), dtype=np.uint64), small(k)
+    if name == "keccak_trace":
+        return rng.integers(0, 1 << 64, (k, 25), dtype=np.uint64), small(k)
+    if name == "sha_extend_trace":
+        return rng.integers(0, 256, (k, 16), dtype=np.uint64).astype(np.uint8), small(k)
+    if name == "sha_extend_sponge_trace":
+        return u32(k, 16), small(k, 4)
+    if name in ("sha_compress_trace", "sha_compress_sponge_trace"):
+        return u32(k, 8), u32(k, 64), small(k, 8)
+    ops = u32(k, 3)
+    ops[:, 0] &= 3
+    return (ops,)
+
+
+# every uniform stand-alone writer entry point at the smallest height where its row bound bites: the most operations that fit, and the
+# entry point's whole refusal of one more
+@pytest.mark.parametrize("name,log_n,fits,refusal", [
+    ("poseidon_trace_inputs", 4, 16, "zkm_poseidon_trace_inputs: more permutations than 2^log_n rows"),
+    ("keccak_trace", 6, 2, "zkm_keccak_trace: permutations need more rows than 2^log_n (24 each)"),
+    ("sha_extend_trace", 6, 64, "zkm_sha_extend_trace: more rows than 2^log_n"),
+    ("sha_extend_sponge_trace", 6, 1, "zkm_sha_extend_sponge_trace: message schedules need more rows than 2^log_n (48 each)"),
+    ("sha_compress_trace", 7, 1, "zkm_sha_compress_trace: compressions need more rows than 2^log_n"),
+    ("sha_compress_sponge_trace", 3, 8, "zkm_sha_compress_sponge_trace: compressions need more rows than 2^log_n"),
+    ("logic_trace", 3, 8, "zkm_logic_trace: more operations than 2^log_n rows")])
+def test_writer_entry_points_at_their_row_bound(ctx, zkm, oracle, name, log_n, fits, refusal):
+    run, want = getattr(ctx, name), getattr(oracle, name)
+    for k in (fits, 0):                      # a full table word for word; no operations: the oracle's padding table
+        lists = writer_lists(name, k)
+        got, table = run(*lists, log_n), want(*lists, log_n)
+        assert (got.download() == (table[0] if isinstance(table, tuple) else table)).all(), k     # (some oracle calls add the rows in use)
+        got.free()
+    with pytest.raises(zkm.ZkmError) as e:
+        run(*writer_lists(name, fits + 1), log_n)
+    assert str(e.value) == refusal
+    host_out = np.zeros(8, dtype=np.uint64)
+    with pytest.raises(zkm.ZkmError) as e:
+        run(*writer_lists(name, fits), log_n, out=host_out.ctypes.data)
+    assert str(e.value) == refusal.split(":")[0] + ": out must be a device pointer"
+
+
 @pytest.mark.parametrize("ncomp", [1, 9])
 def test_sha_compress_path_is_bit_exact_and_verifies(ctx, oracle, ncomp):
     """Memory -> ShaCompressSponge -> ShaCompress -> Logic: SHA-256 compressions (all_stark.rs:298-324, 387-470, 511-525)."""

@@ -324,6 +324,9 @@ def test_launches_and_host_waits_do_not_depend_on_the_segments(ctx, proven):
         ctx.profile_reset()
     print(rec8)
     assert rec1 == rec8 and len(rec1) == 16 and all(v == 1 for v in rec1.values())    # rows, twelve tables, chains, queries, reduce
+    assert {k for k in rec1 if k.startswith("verify/line_")} == {"verify/line_rows"} | {"verify/line_" + name for name in (
+        "poseidon", "logic", "keccak_sponge", "keccak", "memory", "poseidon_sponge", "sha_extend", "sha_extend_sponge", "sha_compress",
+        "sha_compress_sponge", "arithmetic", "cpu")}
     assert all(r.host_waits == 1 and r.name == "OK" for r in reps1 + reps8)
     assert [bytes(r) for r in reps8] == [bytes(r) for r in again8] == [bytes(reps1[0])] * 8
     assert ctx.memory()[0] == before

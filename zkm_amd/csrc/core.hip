@@ -463,18 +463,11 @@ void zkm_ctx::prof_end(size_t idx) {
     if (idx < prof.size()) (void)hipEventRecord(prof[idx].stop, stream);
 }
 
-// Stark::lookups() of the tables with constraint kernels.  Memory: RANGE_CHECK (10) looked up in COUNTER (11) with
-// FREQUENCIES (12), memory_stark.rs:476-483.
-static const uint32_t MEMORY_LOOKUP_COLS[1] = {10};
-static const zkm_table_lookup MEMORY_LOOKUPS[1] = {{1, MEMORY_LOOKUP_COLS, 11, 12}};
-// Arithmetic: the 18 shared columns (26..43) looked up in RANGE_COUNTER (44) with RC_FREQUENCIES (45), arithmetic_stark.rs:269-276.
-static const uint32_t ARITH_LOOKUP_COLS[18] = {26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43};
-static const zkm_table_lookup ARITH_LOOKUPS[1] = {{18, ARITH_LOOKUP_COLS, 44, 45}};
+// Stark::lookups() of a table (tables.h)
 const zkm_table_lookup* zkm_table_lookups(int table_id, size_t* n) {
-    if (table_id == ZKM_TABLE_MEMORY) { *n = 1; return MEMORY_LOOKUPS; }
-    if (table_id == ZKM_TABLE_ARITHMETIC) { *n = 1; return ARITH_LOOKUPS; }
-    *n = 0;
-    return nullptr;
+    const zkm_table_row* t = zkm_table(table_id);
+    *n = t ? t->nlookups : 0;
+    return t ? t->lookups : nullptr;
 }
 
 // The HIP runtime spreads the streams of a process over its hardware queues (GPU_MAX_HW_QUEUES, default 4, read at the first HIP call of
@@ -671,7 +664,7 @@ struct zkm_staged {
     size_t words;
     hipEvent_t done[2];
     bool joined, canonical;
-    size_t off[13];     // a staged SEGMENT: word offset of table t (Table::all() order) in the block, off[12] = words; one matrix: unused
+    size_t off[ZKM_NUM_TABLES + 1];     // a staged SEGMENT: word offset of table t (Table::all() order) in the block, the last = words; one matrix: unused
     bool segment;
     bool counted;       // an upload counted in g_staged_live (a segment built on the device by zkm_segment_tables is not)
 };
@@ -756,21 +749,19 @@ static int stage_segment(const char* what, zkm_ctx* c, const uint64_t* const* tr
                          int canonical, zkm_staged** out, char** err) {
     return zkm_api(what, c, err, [&] {
         if ((!traces && !columns) || !log_n || !out) throw std::runtime_error(std::string(what) + ": null argument");
-        static const int order[12] = {ZKM_TABLE_ARITHMETIC, ZKM_TABLE_CPU, ZKM_TABLE_POSEIDON, ZKM_TABLE_POSEIDON_SPONGE, ZKM_TABLE_KECCAK,
-                                      ZKM_TABLE_KECCAK_SPONGE, ZKM_TABLE_SHA_EXTEND, ZKM_TABLE_SHA_EXTEND_SPONGE, ZKM_TABLE_SHA_COMPRESS,
-                                      ZKM_TABLE_SHA_COMPRESS_SPONGE, ZKM_TABLE_LOGIC, ZKM_TABLE_MEMORY};   // Table::all(), all_stark.rs:117-134
-        size_t off[13], W[12];
+        constexpr int NT = ZKM_NUM_TABLES;
+        size_t off[NT + 1], W[NT];
         off[0] = 0;
-        for (int t = 0; t < 12; t++) {
+        for (int t = 0; t < NT; t++) {
             if (log_n[t] > 30 || (traces && !traces[t]) || (columns && !columns[t])) throw std::runtime_error(std::string(what) + ": bad table");
-            W[t] = zkm_table_width(order[t]);
+            W[t] = zkm_table_at(t)->width;
             off[t + 1] = off[t] + (W[t] << log_n[t]);
         }
-        staged_owner s(stage_begin(c, off[12], canonical), stage_abort);
+        staged_owner s(stage_begin(c, off[NT], canonical), stage_abort);
         s->segment = true;
-        for (int t = 0; t <= 12; t++) s->off[t] = off[t];
+        for (int t = 0; t <= NT; t++) s->off[t] = off[t];
         size_t k = 0, bytes_on[2] = {0, 0};
-        for (int t = 0; t < 12; t++) {
+        for (int t = 0; t < NT; t++) {
             const size_t n = (size_t)1 << log_n[t];
             const size_t piece = std::max<size_t>(8, (((size_t)64 << 20) / (n * sizeof(gl_t)) + 7) / 8 * 8);
             for (size_t c0 = 0; c0 < W[t]; c0 += columns ? 1 : piece) {
@@ -797,7 +788,7 @@ int zkm_staged_segment_ptrs(zkm_staged* s, const uint64_t** ptrs_out) {
     if (!s || !s->segment || !ptrs_out) return 1;
     const uint64_t* base = zkm_staged_ptr(s);
     if (!base) return 1;
-    for (int t = 0; t < 12; t++) ptrs_out[t] = base + s->off[t];
+    for (int t = 0; t < ZKM_NUM_TABLES; t++) ptrs_out[t] = base + s->off[t];
     return 0;
 }
 
@@ -848,14 +839,14 @@ void zkm_staged_free(zkm_staged* s) {
 // A segment whose tables were WRITTEN on the device by work already queued on the context's compute stream (segment_ops.hip): the block
 // becomes a segment-shaped handle that zkm_staged_segment_ptrs / _ready / _free take as they take an upload.  Both events are recorded
 // on the compute stream; the block is canonical and needs no join.  Not an upload, so not counted in g_staged_live.
-zkm_staged* zkm_staged_from_segment(zkm_ctx* c, void* block, const size_t off[13]) {
+zkm_staged* zkm_staged_from_segment(zkm_ctx* c, void* block, const size_t off[ZKM_NUM_TABLES + 1]) {
     zkm_event e0(c), e1(c);
     e0.record(c->stream);
     e1.record(c->stream);
     zkm_staged* s = new zkm_staged();
-    s->ctx = c; s->dev = (gl_t*)block; s->words = off[12]; s->joined = true; s->canonical = true;
+    s->ctx = c; s->dev = (gl_t*)block; s->words = off[ZKM_NUM_TABLES]; s->joined = true; s->canonical = true;
     s->segment = true; s->counted = false;
-    for (int t = 0; t <= 12; t++) s->off[t] = off[t];
+    for (int t = 0; t <= ZKM_NUM_TABLES; t++) s->off[t] = off[t];
     s->done[0] = e0.e; s->done[1] = e1.e;
     e0.e = e1.e = nullptr;
     return s;
@@ -1294,7 +1285,8 @@ int zkm_keccakf_batch(zkm_ctx* c, uint64_t* states, size_t k, char** err) {
 int zkm_poseidon_trace(zkm_ctx* c, uint64_t seed, size_t num_perms, unsigned log_n, uint64_t* out_dev, char** err) {
     return zkm_api("zkm_poseidon_trace", c, err, [&] {
         if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_poseidon_trace: out must be a device pointer");
-        zkm_launch_poseidon_trace(c, seed, nullptr, nullptr, num_perms, log_n, out_dev);
+        const zkm_writer_seg a{{}, num_perms, (size_t)1 << log_n, seed, out_dev};
+        zkm_launch_writers(c, ZKM_TABLE_POSEIDON, &a, 1);
         c->sync();
     });
 }
@@ -1327,8 +1319,8 @@ static int sponge_trace(zkm_ctx* c, const char* what, size_t rate, bool poseidon
         ZKM_HIP_CHECK(hipMemcpyAsync(d_off, input_off, (nops + 1) * 8, hipMemcpyHostToDevice, c->stream));
         if (nops) ZKM_HIP_CHECK(hipMemcpyAsync(d_meta, meta, nops * 32, hipMemcpyHostToDevice, c->stream));
         ZKM_HIP_CHECK(hipMemcpyAsync(d_row, row_off.data(), (nops + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        if (poseidon) zkm_launch_poseidon_sponge_trace(c, d_in, d_off, d_meta, d_row, nops, log_n, out_dev);
-        else zkm_launch_keccak_sponge_trace(c, d_in, d_off, d_meta, d_row, nops, (size_t)row_off[nops], log_n, out_dev);
+        const zkm_writer_seg a{{d_in, d_off, d_meta, d_row}, nops, n, poseidon ? 0 : (size_t)row_off[nops], out_dev};   // (aux: the KeccakSponge rows in use)
+        zkm_launch_writers(c, poseidon ? ZKM_TABLE_POSEIDON_SPONGE : ZKM_TABLE_KECCAK_SPONGE, &a, 1);
         c->sync();
         if (rows_used_out) *rows_used_out = row_off[nops];
     });
@@ -1344,18 +1336,62 @@ int zkm_poseidon_sponge_trace(zkm_ctx* c, const uint8_t* inputs, const uint64_t*
     return sponge_trace(c, "zkm_poseidon_sponge_trace", 32, true, inputs, input_off, meta, nops, log_n, out_dev, rows_used_out, err);
 }
 
+// One body for the stand-alone entry points of the uniform data-parallel writers, driven by the table's description (tables.h
+// zkm_writer): `lists` in the description's order, host or device; the refusals are the description's phrases behind `what`.
+static int writer_trace(const char* what, zkm_ctx* c, int table_id, std::initializer_list<const void*> lists, size_t k, unsigned log_n,
+                        uint64_t* out_dev, char** err) {
+    return zkm_api(what, c, err, [&] {
+        const zkm_writer& w = zkm_table(table_id)->writer;
+        const std::string who = std::string(what) + ": ";
+        if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error(who + "out must be a device pointer");
+        const size_t n = (size_t)1 << log_n;
+        if (k > n / w.rows_per_op) throw std::runtime_error(who + w.too_many);
+        for (const void* p : lists)
+            if (w.required && k && !p) throw std::runtime_error(who + w.required);
+        zkm_scratch_list tmp(c);
+        zkm_writer_seg a{{}, k, n, 0, out_dev};
+        size_t i = 0;
+        for (const void* p : lists) {
+            a.in[i] = k ? stage_arg(tmp, p, k * w.list_bytes[i]) : nullptr;   // (a table without operations is all padding: no list is read)
+            i++;
+        }
+        int bad = 0;
+        if (w.bad) {
+            a.bad = tmp.alloc<int>(sizeof(int));
+            ZKM_HIP_CHECK(hipMemsetAsync(a.bad, 0, sizeof(int), c->stream));
+        }
+        zkm_launch_writers(c, table_id, &a, 1);
+        if (w.bad) ZKM_HIP_CHECK(hipMemcpyAsync(&bad, a.bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+        if (bad) throw std::runtime_error(who + w.bad);
+    });
+}
 int zkm_poseidon_trace_inputs(zkm_ctx* c, const uint64_t* inputs, const uint64_t* timestamps, size_t num_perms, unsigned log_n,
                               uint64_t* out_dev, char** err) {
-    return zkm_api("zkm_poseidon_trace_inputs", c, err, [&] {
-        if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_poseidon_trace_inputs: out must be a device pointer");
-        if (num_perms > ((size_t)1 << log_n)) throw std::runtime_error("zkm_poseidon_trace_inputs: more permutations than 2^log_n rows");
-        if (num_perms && (!inputs || !timestamps)) throw std::runtime_error("zkm_poseidon_trace_inputs: inputs and timestamps are required");
-        zkm_scratch_list tmp(c);
-        const uint64_t* d_in = (const uint64_t*)stage_arg(tmp, inputs, num_perms * 12 * 8);
-        const uint64_t* d_ts = (const uint64_t*)stage_arg(tmp, timestamps, num_perms * 8);
-        zkm_launch_poseidon_trace(c, 0, num_perms ? d_in : nullptr, num_perms ? d_ts : nullptr, num_perms, log_n, out_dev);
-        c->sync();
-    });
+    return writer_trace("zkm_poseidon_trace_inputs", c, ZKM_TABLE_POSEIDON, {inputs, timestamps}, num_perms, log_n, out_dev, err);
+}
+int zkm_keccak_trace(zkm_ctx* c, const uint64_t* inputs, const uint64_t* timestamps, size_t nperms, unsigned log_n, uint64_t* out_dev,
+                     char** err) {
+    return writer_trace("zkm_keccak_trace", c, ZKM_TABLE_KECCAK, {inputs, timestamps}, nperms, log_n, out_dev, err);
+}
+int zkm_sha_extend_trace(zkm_ctx* c, const uint8_t* inputs, const uint64_t* timestamps, size_t nrows, unsigned log_n, uint64_t* out_dev,
+                         char** err) {
+    return writer_trace("zkm_sha_extend_trace", c, ZKM_TABLE_SHA_EXTEND, {inputs, timestamps}, nrows, log_n, out_dev, err);
+}
+int zkm_sha_extend_sponge_trace(zkm_ctx* c, const uint32_t* w16, const uint64_t* meta, size_t nblocks, unsigned log_n, uint64_t* out_dev,
+                                char** err) {
+    return writer_trace("zkm_sha_extend_sponge_trace", c, ZKM_TABLE_SHA_EXTEND_SPONGE, {w16, meta}, nblocks, log_n, out_dev, err);
+}
+int zkm_sha_compress_trace(zkm_ctx* c, const uint32_t* hx, const uint32_t* w, const uint64_t* meta, size_t ncomp, unsigned log_n,
+                           uint64_t* out_dev, char** err) {
+    return writer_trace("zkm_sha_compress_trace", c, ZKM_TABLE_SHA_COMPRESS, {hx, w, meta}, ncomp, log_n, out_dev, err);
+}
+int zkm_sha_compress_sponge_trace(zkm_ctx* c, const uint32_t* hx, const uint32_t* w, const uint64_t* meta, size_t ncomp, unsigned log_n,
+                                  uint64_t* out_dev, char** err) {
+    return writer_trace("zkm_sha_compress_sponge_trace", c, ZKM_TABLE_SHA_COMPRESS_SPONGE, {hx, w, meta}, ncomp, log_n, out_dev, err);
+}
+int zkm_logic_trace(zkm_ctx* c, const uint32_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, char** err) {
+    return writer_trace("zkm_logic_trace", c, ZKM_TABLE_LOGIC, {ops}, nops, log_n, out_dev, err);
 }
 
 size_t zkm_num_lookup_columns(int table_id, const zkm_stark_config* cfg) {
@@ -1366,104 +1402,8 @@ size_t zkm_num_lookup_columns(int table_id, const zkm_stark_config* cfg) {
 }
 
 size_t zkm_table_width(int table_id) {
-    switch (table_id) {
-        case ZKM_TABLE_POSEIDON: return ZKM_POSEIDON_COLS;
-        case ZKM_TABLE_LOGIC: return ZKM_LOGIC_COLS;
-        case ZKM_TABLE_KECCAK_SPONGE: return ZKM_KECCAK_SPONGE_COLS;
-        case ZKM_TABLE_KECCAK: return ZKM_KECCAK_COLS;
-        case ZKM_TABLE_MEMORY: return ZKM_MEMORY_COLS;
-        case ZKM_TABLE_POSEIDON_SPONGE: return ZKM_POSEIDON_SPONGE_COLS;
-        case ZKM_TABLE_SHA_EXTEND: return ZKM_SHA_EXTEND_COLS;
-        case ZKM_TABLE_SHA_EXTEND_SPONGE: return ZKM_SHA_EXTEND_SPONGE_COLS;
-        case ZKM_TABLE_SHA_COMPRESS: return ZKM_SHA_COMPRESS_COLS;
-        case ZKM_TABLE_SHA_COMPRESS_SPONGE: return ZKM_SHA_COMPRESS_SPONGE_COLS;
-        case ZKM_TABLE_ARITHMETIC: return ZKM_ARITHMETIC_COLS;
-        case ZKM_TABLE_CPU: return ZKM_CPU_COLS;
-        default: return 0;
-    }
-}
-
-int zkm_sha_extend_trace(zkm_ctx* c, const uint8_t* inputs, const uint64_t* timestamps, size_t nrows, unsigned log_n, uint64_t* out_dev,
-                         char** err) {
-    return zkm_api("zkm_sha_extend_trace", c, err, [&] {
-        if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_sha_extend_trace: out must be a device pointer");
-        size_t n = (size_t)1 << log_n;
-        if (nrows > n) throw std::runtime_error("zkm_sha_extend_trace: more rows than 2^log_n");
-        zkm_scratch_list tmp(c);
-        const uint8_t* d_in = (const uint8_t*)stage_arg(tmp, inputs, nrows * 16);
-        const uint64_t* d_ts = (const uint64_t*)stage_arg(tmp, timestamps, nrows * 8);
-        zkm_launch_sha_extend_trace(c, d_in, d_ts, nrows, n, out_dev);
-        c->sync();
-    });
-}
-
-int zkm_sha_extend_sponge_trace(zkm_ctx* c, const uint32_t* w16, const uint64_t* meta, size_t nblocks, unsigned log_n, uint64_t* out_dev,
-                                char** err) {
-    return zkm_api("zkm_sha_extend_sponge_trace", c, err, [&] {
-        if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_sha_extend_sponge_trace: out must be a device pointer");
-        size_t n = (size_t)1 << log_n;
-        if (48 * nblocks > n) throw std::runtime_error("zkm_sha_extend_sponge_trace: message schedules need more rows than 2^log_n (48 each)");
-        zkm_scratch_list tmp(c);
-        const uint32_t* d_w = (const uint32_t*)stage_arg(tmp, w16, nblocks * 64);
-        const uint64_t* d_meta = (const uint64_t*)stage_arg(tmp, meta, nblocks * 32);
-        zkm_launch_sha_extend_sponge_trace(c, d_w, d_meta, nblocks, n, out_dev);
-        c->sync();
-    });
-}
-
-static int sha_compress_trace(zkm_ctx* c, bool sponge, const uint32_t* hx, const uint32_t* w, const uint64_t* meta, size_t ncomp,
-                              unsigned log_n, uint64_t* out_dev, char** err) {
-    const char* what = sponge ? "zkm_sha_compress_sponge_trace" : "zkm_sha_compress_trace";
-    return zkm_api(what, c, err, [&] {
-        if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error(std::string(what) + ": out must be a device pointer");
-        size_t n = (size_t)1 << log_n;
-        if ((sponge ? 1 : 65) * ncomp > n) throw std::runtime_error(std::string(what) + ": compressions need more rows than 2^log_n");
-        zkm_scratch_list tmp(c);
-        const uint32_t* d_hx = (const uint32_t*)stage_arg(tmp, hx, ncomp * 32);
-        const uint32_t* d_w = (const uint32_t*)stage_arg(tmp, w, ncomp * 256);
-        const uint64_t* d_meta = (const uint64_t*)stage_arg(tmp, meta, ncomp * 64);
-        zkm_launch_sha_compress_trace(c, sponge, d_hx, d_w, d_meta, ncomp, n, out_dev);
-        c->sync();
-    });
-}
-int zkm_sha_compress_trace(zkm_ctx* c, const uint32_t* hx, const uint32_t* w, const uint64_t* meta, size_t ncomp, unsigned log_n,
-                           uint64_t* out_dev, char** err) {
-    return sha_compress_trace(c, false, hx, w, meta, ncomp, log_n, out_dev, err);
-}
-int zkm_sha_compress_sponge_trace(zkm_ctx* c, const uint32_t* hx, const uint32_t* w, const uint64_t* meta, size_t ncomp, unsigned log_n,
-                                  uint64_t* out_dev, char** err) {
-    return sha_compress_trace(c, true, hx, w, meta, ncomp, log_n, out_dev, err);
-}
-
-int zkm_keccak_trace(zkm_ctx* c, const uint64_t* inputs, const uint64_t* timestamps, size_t nperms, unsigned log_n, uint64_t* out_dev,
-                     char** err) {
-    return zkm_api("zkm_keccak_trace", c, err, [&] {
-        if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_keccak_trace: out must be a device pointer");
-        size_t n = (size_t)1 << log_n;
-        if (nperms * 24 > n) throw std::runtime_error("zkm_keccak_trace: permutations need more rows than 2^log_n (24 each)");
-        zkm_scratch_list tmp(c);
-        const uint64_t* d_in = (const uint64_t*)stage_arg(tmp, inputs, nperms * 25 * 8);
-        const uint64_t* d_ts = (const uint64_t*)stage_arg(tmp, timestamps, nperms * 8);
-        zkm_launch_keccak_trace(c, d_in, d_ts, nperms, n, out_dev);
-        c->sync();
-    });
-}
-
-int zkm_logic_trace(zkm_ctx* c, const uint32_t* ops, size_t nops, unsigned log_n, uint64_t* out_dev, char** err) {
-    return zkm_api("zkm_logic_trace", c, err, [&] {
-        if (!zkm_is_device_ptr(out_dev)) throw std::runtime_error("zkm_logic_trace: out must be a device pointer");
-        size_t n = (size_t)1 << log_n;
-        if (nops > n) throw std::runtime_error("zkm_logic_trace: more operations than 2^log_n rows");
-        zkm_scratch_list tmp(c);
-        const uint32_t* d_ops = (const uint32_t*)stage_arg(tmp, ops, nops * 12);
-        int* d_bad = tmp.alloc<int>(sizeof(int));
-        ZKM_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(int), c->stream));
-        zkm_launch_logic_trace(c, d_ops, nops, n, out_dev, d_bad);
-        int bad = 0;
-        ZKM_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        c->sync();
-        if (bad) throw std::runtime_error("zkm_logic_trace: op code out of range (0 and, 1 or, 2 xor, 3 nor)");
-    });
+    const zkm_table_row* t = zkm_table(table_id);
+    return t ? t->width : 0;
 }
 
 }  // extern "C"

@@ -518,8 +518,12 @@ int zkm_all_stark_ctls(const zkm_cross_table_lookup** ctls_out, size_t* nctls_ou
     return 0;
 }
 }  // extern "C"
-void zkm_all_stark_table_inputs(zkm_table_input out[12]) {
-    for (int t = 0; t < 12; t++) out[t] = zkm_table_input{AS_TABLE_IDS[t], nullptr, AS_TABLE_WIDTH[t], 0, &AS_CTL_TABLES[t], nullptr};
+// table t (Table::all() order) of the built-in AllStark
+static zkm_table_input all_stark_table(int t, const uint64_t* trace, unsigned log_n, const uint64_t* const* columns = nullptr) {
+    return zkm_table_input{zkm_table_at(t)->id, trace, zkm_table_at(t)->width, log_n, &AS_CTL_TABLES[t], columns};
+}
+void zkm_all_stark_table_inputs(zkm_table_input out[ZKM_NUM_TABLES]) {
+    for (int t = 0; t < ZKM_NUM_TABLES; t++) out[t] = all_stark_table(t, nullptr, 0);
 }
 extern "C" {
 const zkm_ctl_table* zkm_all_stark_ctl_table(int table_id) {
@@ -530,15 +534,15 @@ int zkm_prove_segment(zkm_ctx* c, const zkm_stark_config* cfg, const uint64_t* c
                       const uint64_t* pub, size_t npub, uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
     return zkm_api("zkm_prove_segment", err, [&] {
         if (!traces || !log_n) throw std::runtime_error("zkm_prove_segment: null argument");
-        zkm_table_input tables[12];
-        for (int t = 0; t < 12; t++) tables[t] = zkm_table_input{AS_TABLE_IDS[t], traces[t], AS_TABLE_WIDTH[t], log_n[t], &AS_CTL_TABLES[t], nullptr};
-        size_t offs[13];
-        size_t total = zkm_all_proof_words(cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, offs);
+        zkm_table_input tables[ZKM_NUM_TABLES];
+        for (int t = 0; t < ZKM_NUM_TABLES; t++) tables[t] = all_stark_table(t, traces[t], log_n[t]);
+        size_t offs[ZKM_NUM_TABLES + 1];
+        size_t total = zkm_all_proof_words(cfg, tables, ZKM_NUM_TABLES, AS_CTLS, AS_SIDES, AS_NCTLS, offs);
         if (!total) throw std::runtime_error("zkm_prove_segment: unsupported configuration or table size");
         if (offsets_out) memcpy(offsets_out, offs, sizeof offs);
         if (!proofs) return 0;  // sizing pass
         if (!c || !challenges) throw std::runtime_error("zkm_prove_segment: null argument");
-        return zkm_prove_with_traces(c, cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, pub, npub, proofs, challenges, err);
+        return zkm_prove_with_traces(c, cfg, tables, ZKM_NUM_TABLES, AS_CTLS, AS_SIDES, AS_NCTLS, pub, npub, proofs, challenges, err);
     });
 }
 
@@ -546,29 +550,22 @@ int zkm_prove_segment_columns(zkm_ctx* c, const zkm_stark_config* cfg, const uin
                               const uint64_t* pub, size_t npub, uint64_t* proofs, size_t* offsets_out, uint64_t* challenges, char** err) {
     return zkm_api("zkm_prove_segment_columns", err, [&] {
         if (!columns || !log_n) throw std::runtime_error("zkm_prove_segment_columns: null argument");
-        zkm_table_input tables[12];
-        for (int t = 0; t < 12; t++) {
+        zkm_table_input tables[ZKM_NUM_TABLES];
+        for (int t = 0; t < ZKM_NUM_TABLES; t++) {
             if (!columns[t]) throw std::runtime_error("zkm_prove_segment_columns: null table");
-            tables[t] = zkm_table_input{AS_TABLE_IDS[t], nullptr, AS_TABLE_WIDTH[t], log_n[t], &AS_CTL_TABLES[t], columns[t]};
+            tables[t] = all_stark_table(t, nullptr, log_n[t], columns[t]);
         }
-        size_t offs[13];
-        size_t total = zkm_all_proof_words(cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, offs);
+        size_t offs[ZKM_NUM_TABLES + 1];
+        size_t total = zkm_all_proof_words(cfg, tables, ZKM_NUM_TABLES, AS_CTLS, AS_SIDES, AS_NCTLS, offs);
         if (!total) throw std::runtime_error("zkm_prove_segment_columns: unsupported configuration or table size");
         if (offsets_out) memcpy(offsets_out, offs, sizeof offs);
         if (!proofs) return 0;  // sizing pass
         if (!c || !challenges) throw std::runtime_error("zkm_prove_segment_columns: null argument");
-        return zkm_prove_with_traces(c, cfg, tables, 12, AS_CTLS, AS_SIDES, AS_NCTLS, pub, npub, proofs, challenges, err);
+        return zkm_prove_with_traces(c, cfg, tables, ZKM_NUM_TABLES, AS_CTLS, AS_SIDES, AS_NCTLS, pub, npub, proofs, challenges, err);
     });
 }
 
-int zkm_table_enum_index(int table_id) {
-    static const int order[12] = {ZKM_TABLE_ARITHMETIC, ZKM_TABLE_CPU, ZKM_TABLE_POSEIDON, ZKM_TABLE_POSEIDON_SPONGE, ZKM_TABLE_KECCAK,
-                                  ZKM_TABLE_KECCAK_SPONGE, ZKM_TABLE_SHA_EXTEND, ZKM_TABLE_SHA_EXTEND_SPONGE, ZKM_TABLE_SHA_COMPRESS,
-                                  ZKM_TABLE_SHA_COMPRESS_SPONGE, ZKM_TABLE_LOGIC, ZKM_TABLE_MEMORY};
-    for (int i = 0; i < 12; i++)
-        if (order[i] == table_id) return i;
-    return -1;
-}
+int zkm_table_enum_index(int table_id) { return zkm_table_index(table_id); }
 
 size_t zkm_all_proof_words(const zkm_stark_config* cfg, const zkm_table_input* tables, size_t ntables,
                            const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t* offs) {
@@ -849,16 +846,16 @@ struct lockstep_call {
                 if (!a.trace && !a.columns) throw std::runtime_error("zkm_prove_with_traces: table without a trace");
             }
         }
-        if (ntables == 12) {  // a whole AllStark segment: the transcript only matches the reference's in Table::all() order
+        if (ntables == ZKM_NUM_TABLES) {  // a whole AllStark segment: the transcript only matches the reference's in Table::all() order
             bool all = true, ordered = true;
-            for (size_t t = 0; t < 12; t++) {
+            for (size_t t = 0; t < ntables; t++) {
                 int e = zkm_table_enum_index(T0[t].table_id);
                 all = all && e >= 0;
                 ordered = ordered && e == (int)t;
             }
             bool distinct = all;
-            for (size_t a = 0; a < 12 && distinct; a++)
-                for (size_t b = a + 1; b < 12; b++)
+            for (size_t a = 0; a < ntables && distinct; a++)
+                for (size_t b = a + 1; b < ntables; b++)
                     if (T0[a].table_id == T0[b].table_id) distinct = false;
             if (distinct && !ordered)
                 throw std::runtime_error("zkm_prove_with_traces: the twelve tables must be given in the reference's Table enum order "
@@ -1234,10 +1231,10 @@ static void prove_segments_waves(zkm_ctx* c, const zkm_stark_config* cfg, size_t
 
 // zkm_internal.h: the same estimate for a whole segment known by its heights alone (Table::all() order) -- segment_ops.hip sizes the
 // waves of a call before the tables exist
-double zkm_segment_footprint(const zkm_stark_config* cfg, const unsigned log_n[12]) {
-    zkm_table_input tables[12];
-    for (int t = 0; t < 12; t++) tables[t] = zkm_table_input{AS_TABLE_IDS[t], nullptr, AS_TABLE_WIDTH[t], log_n[t], &AS_CTL_TABLES[t], nullptr};
-    return segment_footprint(cfg, tables, 12, derive_zs(12, AS_CTLS, AS_SIDES, AS_NCTLS, cfg->num_challenges, nullptr));
+double zkm_segment_footprint(const zkm_stark_config* cfg, const unsigned log_n[ZKM_NUM_TABLES]) {
+    zkm_table_input tables[ZKM_NUM_TABLES];
+    for (int t = 0; t < ZKM_NUM_TABLES; t++) tables[t] = all_stark_table(t, nullptr, log_n[t]);
+    return segment_footprint(cfg, tables, ZKM_NUM_TABLES, derive_zs(ZKM_NUM_TABLES, AS_CTLS, AS_SIDES, AS_NCTLS, cfg->num_challenges, nullptr));
 }
 
 extern "C" {
@@ -1259,20 +1256,19 @@ int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_confi
                              const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges, char** err, size_t seg_base) {
     return zkm_api(what, c, err, [&] {
         if (!cfg || (!traces && !columns) || !log_n || !proofs || !challenges) throw std::runtime_error(std::string(what) + ": null argument");
-        std::vector<std::vector<zkm_table_input>> tables(nseg, std::vector<zkm_table_input>(12));
+        std::vector<std::vector<zkm_table_input>> tables(nseg, std::vector<zkm_table_input>(ZKM_NUM_TABLES));
         std::vector<seg_io> io(nseg);
         for (size_t s = 0; s < nseg; s++) {
             if ((traces && !traces[s]) || (columns && !columns[s]) || !log_n[s] || !proofs[s] || !challenges[s])
                 throw std::runtime_error(std::string(what) + ": null segment");
-            for (int t = 0; t < 12; t++) {
+            for (int t = 0; t < ZKM_NUM_TABLES; t++) {
                 if (columns && !columns[s][t]) throw std::runtime_error(std::string(what) + ": null table");
-                tables[s][t] = zkm_table_input{AS_TABLE_IDS[t], traces ? traces[s][t] : nullptr, AS_TABLE_WIDTH[t], log_n[s][t], &AS_CTL_TABLES[t],
-                                               columns ? columns[s][t] : nullptr};
+                tables[s][t] = all_stark_table(t, traces ? traces[s][t] : nullptr, log_n[s][t], columns ? columns[s][t] : nullptr);
             }
             io[s] = seg_io{tables[s].data(), pub ? pub[s] : nullptr, npub ? npub[s] : 0, proofs[s], challenges[s]};
             if (io[s].npub && !io[s].pub) throw std::runtime_error(std::string(what) + ": null public values");
         }
-        prove_segments_checked(c, cfg, nseg, io.data(), 12, AS_CTLS, AS_SIDES, AS_NCTLS, seg_base, true);
+        prove_segments_checked(c, cfg, nseg, io.data(), ZKM_NUM_TABLES, AS_CTLS, AS_SIDES, AS_NCTLS, seg_base, true);
     });
 }
 

@@ -258,15 +258,9 @@ void scan_jobs(zkm_ctx* c, const std::vector<scan_seg>& scans) {
     }
 }
 
-const char* table_name(int table_id) {
-    static const char* const names[12] = {"Arithmetic", "Cpu", "Poseidon", "PoseidonSponge", "Keccak", "KeccakSponge", "ShaExtend", "ShaExtendSponge",
-                                          "ShaCompress", "ShaCompressSponge", "Logic", "Memory"};   // Table's Debug names, all_stark.rs:96-110
-    const int e = zkm_table_enum_index(table_id);
-    return e < 0 ? nullptr : names[e];
-}
 std::string table_label(const zkm_table_input* tables, uint32_t t) {
-    const char* nm = table_name(tables[t].table_id);
-    return nm ? std::string(nm) : "Table" + std::to_string(t);
+    const zkm_table_row* row = zkm_table(tables[t].table_id);
+    return row ? std::string(row->name) : "Table" + std::to_string(t);
 }
 std::string locations_text(const zkm_table_input* tables, const zkm_ctl_location* l, uint32_t shown, uint64_t count) {
     std::string s = "[";
@@ -553,12 +547,13 @@ int zkm_segment_check_ctls(zkm_ctx* c, const uint64_t* const* traces, const unsi
         const zkm_ctl_side* sides;
         size_t nctls, nsides;
         zkm_all_stark_ctls(&ctls, &nctls, &sides, &nsides);
-        zkm_table_input tables[12];
-        for (int id = 0; id < 12; id++) {   // Table::all() order
-            const int t = zkm_table_enum_index(id);
-            tables[t] = zkm_table_input{id, traces[t], zkm_table_width(id), log_n[t], zkm_all_stark_ctl_table(id), nullptr};
+        zkm_table_input tables[ZKM_NUM_TABLES];
+        zkm_all_stark_table_inputs(tables);   // Table::all() order
+        for (int t = 0; t < ZKM_NUM_TABLES; t++) {
+            tables[t].trace = traces[t];
+            tables[t].log_n = log_n[t];
         }
-        zkm_check_ctls_run(c, tables, 12, ctls, sides, nctls, rep, msg);
+        zkm_check_ctls_run(c, tables, ZKM_NUM_TABLES, ctls, sides, nctls, rep, msg);
     });
 }
 

@@ -176,7 +176,7 @@ int zkm_pool_prove_segments_ops(zkm_pool* p, const zkm_stark_config* cfg, size_t
         if (nseg == 0) throw std::runtime_error(std::string(what) + ": no segments");
         pool_run(what, p, nseg, max_stack, [&](zkm_ctx* c, size_t s0, size_t k, char** e) {
             return zkm_prove_segments_ops_entry(what, c, cfg, k, ops + s0, pub ? pub + s0 : nullptr, npub ? npub + s0 : nullptr,
-                                                proofs ? proofs + s0 : nullptr, offsets_out ? offsets_out + 13 * s0 : nullptr,
+                                                proofs ? proofs + s0 : nullptr, offsets_out ? offsets_out + (ZKM_NUM_TABLES + 1) * s0 : nullptr,
                                                 challenges ? challenges + s0 : nullptr, e, s0);
         });
     });

@@ -33,7 +33,7 @@
 
 #include "zkm_internal.h"
 
-extern "C" zkm_staged* zkm_staged_from_segment(zkm_ctx* c, void* block, const size_t off[13]);   // core.hip
+extern "C" zkm_staged* zkm_staged_from_segment(zkm_ctx* c, void* block, const size_t off[ZKM_NUM_TABLES + 1]);   // core.hip
 
 namespace {
 
@@ -101,13 +101,9 @@ void launch_cpu_rows_to_cols(zkm_ctx* c, const cpu_seg* segs, size_t nseg) {
     zkm_launch_segs(c->stream, k_cpu_rows_to_cols, segs, nseg, (max_rows + TR_ROWS - 1) / TR_ROWS, TR_THREADS);
 }
 
-// Table::all() (all_stark.rs:117-134) and the reference's names of the tables, for messages
+// names for positions in Table::all() (tables.h: zkm_table_at)
 enum { AR, CPU, PO, PS, KK, KS, SE, SES, SC, SCS, LO, ME, NTAB };
-const char* const NAME[NTAB] = {"Arithmetic", "Cpu", "Poseidon", "PoseidonSponge", "Keccak", "KeccakSponge", "ShaExtend", "ShaExtendSponge",
-                                "ShaCompress", "ShaCompressSponge", "Logic", "Memory"};
-const int TABLE_ID[NTAB] = {ZKM_TABLE_ARITHMETIC, ZKM_TABLE_CPU, ZKM_TABLE_POSEIDON, ZKM_TABLE_POSEIDON_SPONGE, ZKM_TABLE_KECCAK,
-                            ZKM_TABLE_KECCAK_SPONGE, ZKM_TABLE_SHA_EXTEND, ZKM_TABLE_SHA_EXTEND_SPONGE, ZKM_TABLE_SHA_COMPRESS,
-                            ZKM_TABLE_SHA_COMPRESS_SPONGE, ZKM_TABLE_LOGIC, ZKM_TABLE_MEMORY};
+static_assert(NTAB == ZKM_NUM_TABLES && zkm_table_at(ME)->id == ZKM_TABLE_MEMORY, "the positions are the registry's");
 
 unsigned log2_of(size_t pow2) { return pow2 ? 63 - __builtin_clzll(pow2) : 0; }
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -125,7 +121,7 @@ struct copy_join {
 // the output of one build: the block (empty in sizing mode), the word offset of each table in it, and the heights
 struct segment_block {
     zkm_scratch block;
-    size_t off[13] = {};
+    size_t off[NTAB + 1] = {};
     unsigned lg[NTAB] = {};
 };
 
@@ -151,29 +147,48 @@ struct list_ref {
     }
     void set(const void* p) const { memcpy(field, &p, sizeof p); }
 };
+// Where the lists of a data-parallel writer (tables.h zkm_writer, in its order) lie in a zkm_segment_ops: the count, the pointers and,
+// for a sponge, its host offsets.  In the order the lists take in a staging block.
+struct ops_fields {
+    int t;
+    size_t count, list[3], off;
+    size_t k(const zkm_segment_ops& o) const { return *(const size_t*)((const char*)&o + count); }
+    const void* ptr(const zkm_segment_ops& o, size_t field) const {
+        const void* p;
+        memcpy(&p, (const char*)&o + field, sizeof p);
+        return p;
+    }
+    // bytes of list i (a sponge's byte list: where its last operation ends -- the offsets are host memory, builder::sponge_rows checks it)
+    size_t bytes(const zkm_segment_ops& o, uint32_t i) const {
+        const uint32_t per = zkm_table_at(t)->writer.list_bytes[i];
+        return per ? k(o) * per : k(o) ? ((const uint64_t*)ptr(o, off))[k(o)] : 0;
+    }
+};
+#define F(m) offsetof(zkm_segment_ops, m)
+const ops_fields FIELDS[] = {
+    {LO, F(nlogic), {F(logic_ops)}},
+    {PO, F(nposeidon), {F(poseidon_inputs), F(poseidon_timestamps)}},
+    {PS, F(nposeidon_sponge), {F(poseidon_sponge_inputs), F(poseidon_sponge_meta)}, F(poseidon_sponge_off)},
+    {KK, F(nkeccak), {F(keccak_inputs), F(keccak_timestamps)}},
+    {KS, F(nkeccak_sponge), {F(keccak_sponge_inputs), F(keccak_sponge_meta)}, F(keccak_sponge_off)},
+    {SE, F(nsha_extend), {F(sha_extend_inputs), F(sha_extend_timestamps)}},
+    {SES, F(nsha_extend_sponge), {F(sha_extend_sponge_w16), F(sha_extend_sponge_meta)}},
+    {SC, F(nsha_compress), {F(sha_compress_hx), F(sha_compress_w), F(sha_compress_meta)}},
+    {SCS, F(nsha_compress_sponge), {F(sha_compress_sponge_hx), F(sha_compress_sponge_w), F(sha_compress_sponge_meta)}},
+};
+#undef F
+const ops_fields& fields_of(int t) {
+    for (const ops_fields& f : FIELDS)
+        if (f.t == t) return f;
+    throw std::runtime_error("segment_ops: no data-parallel writer for table " + std::string(zkm_table_at(t)->name));
+}
+
 // every list of `o` except the CPU rows and the two sponge offset arrays (which stay host memory)
-std::vector<list_ref> lists_of(zkm_segment_ops& o, size_t ps_bytes, size_t ks_bytes) {
-    return {{&o.arithmetic_ops, o.narithmetic * 12, true},
-            {&o.memory_ops, o.nmemory * 48, true},
-            {&o.logic_ops, o.nlogic * 12, false},
-            {&o.poseidon_inputs, o.nposeidon * 96, false},
-            {&o.poseidon_timestamps, o.nposeidon * 8, false},
-            {&o.poseidon_sponge_inputs, ps_bytes, false},
-            {&o.poseidon_sponge_meta, o.nposeidon_sponge * 32, false},
-            {&o.keccak_inputs, o.nkeccak * 200, false},
-            {&o.keccak_timestamps, o.nkeccak * 8, false},
-            {&o.keccak_sponge_inputs, ks_bytes, false},
-            {&o.keccak_sponge_meta, o.nkeccak_sponge * 32, false},
-            {&o.sha_extend_inputs, o.nsha_extend * 16, false},
-            {&o.sha_extend_timestamps, o.nsha_extend * 8, false},
-            {&o.sha_extend_sponge_w16, o.nsha_extend_sponge * 64, false},
-            {&o.sha_extend_sponge_meta, o.nsha_extend_sponge * 32, false},
-            {&o.sha_compress_hx, o.nsha_compress * 32, false},
-            {&o.sha_compress_w, o.nsha_compress * 256, false},
-            {&o.sha_compress_meta, o.nsha_compress * 64, false},
-            {&o.sha_compress_sponge_hx, o.nsha_compress_sponge * 32, false},
-            {&o.sha_compress_sponge_w, o.nsha_compress_sponge * 256, false},
-            {&o.sha_compress_sponge_meta, o.nsha_compress_sponge * 64, false}};
+std::vector<list_ref> lists_of(zkm_segment_ops& o) {
+    std::vector<list_ref> ls = {{&o.arithmetic_ops, o.narithmetic * 12, true}, {&o.memory_ops, o.nmemory * 48, true}};
+    for (const ops_fields& f : FIELDS)
+        for (uint32_t i = 0; i < zkm_table_at(f.t)->writer.nlists; i++) ls.push_back({(char*)&o + f.list[i], f.bytes(o, i), false});
+    return ls;
 }
 
 // One segment of a wave.  The phases below are driven for the K builders of a wave side by side (build_wave), so that every launch and
@@ -187,7 +202,7 @@ struct builder {
     zkm_segment_ops d{};          // ... and where the device reads them: the caller's device pointers, or places in the staging block
     unsigned lg[NTAB] = {};
     std::vector<uint64_t> ps_row, ks_row;   // first row of each sponge operation
-    size_t ps_rows = 0, ks_rows = 0, ps_bytes = 0, ks_bytes = 0;
+    size_t ps_rows = 0, ks_rows = 0;
     const void *d_pso = nullptr, *d_psr = nullptr, *d_kso = nullptr, *d_ksr = nullptr;   // device copies of the offsets and the row offsets
     std::string me_what, ar_what;
     // staging
@@ -203,7 +218,7 @@ struct builder {
     size_t nposeidon() const { return bn.poseidon + o->nposeidon; }
     size_t ncpu_rows() const { return bn.cpu_rows + o->ncpu_rows; }
 
-    [[noreturn]] void refuse(int t, const std::string& msg) const { throw std::runtime_error(what + ": " + NAME[t] + ": " + msg); }
+    [[noreturn]] void refuse(int t, const std::string& msg) const { throw std::runtime_error(what + ": " + zkm_table_at(t)->name + ": " + msg); }
     // a height of max(rows, min_rows) rounded up to a power of two; rows = count x per, refused above 2^SEG_MAX_LOG_N
     unsigned height(int t, size_t count, size_t per, size_t min_rows) const {
         const size_t cap = (size_t)1 << SEG_MAX_LOG_N;
@@ -236,16 +251,11 @@ struct builder {
         const zkm_segment_ops& o = *this->o;
         need(CPU, o.ncpu_rows, {o.cpu_rows});
         need(AR, o.narithmetic, {o.arithmetic_ops});
-        need(LO, o.nlogic, {o.logic_ops});
         need(ME, o.nmemory, {o.memory_ops});
-        need(PO, o.nposeidon, {o.poseidon_inputs, o.poseidon_timestamps});
-        need(PS, o.nposeidon_sponge, {o.poseidon_sponge_off, o.poseidon_sponge_meta});
-        need(KK, o.nkeccak, {o.keccak_inputs, o.keccak_timestamps});
-        need(KS, o.nkeccak_sponge, {o.keccak_sponge_off, o.keccak_sponge_meta});
-        need(SE, o.nsha_extend, {o.sha_extend_inputs, o.sha_extend_timestamps});
-        need(SES, o.nsha_extend_sponge, {o.sha_extend_sponge_w16, o.sha_extend_sponge_meta});
-        need(SC, o.nsha_compress, {o.sha_compress_hx, o.sha_compress_w, o.sha_compress_meta});
-        need(SCS, o.nsha_compress_sponge, {o.sha_compress_sponge_hx, o.sha_compress_sponge_w, o.sha_compress_sponge_meta});
+        for (const ops_fields& f : FIELDS) {   // (a sponge: the offsets here, the bytes once the offsets have been read)
+            const zkm_writer& w = zkm_table_at(f.t)->writer;
+            for (uint32_t i = 0; i < w.nlists; i++) need(f.t, f.k(o), {f.ptr(o, w.list_bytes[i] ? f.list[i] : f.off)});
+        }
         if (im) {
             try {
                 bn = zkm_boot_job(c, im).n;
@@ -263,10 +273,8 @@ struct builder {
         ps_rows = sponge_rows(PS, o.poseidon_sponge_off, o.nposeidon_sponge, 32, ps_row) + bn.poseidon;
         for (uint64_t& r : ps_row) r += bn.poseidon;      // the bootstrap's sponge rows come first
         ks_rows = sponge_rows(KS, o.keccak_sponge_off, o.nkeccak_sponge, 136, ks_row);
-        ps_bytes = o.nposeidon_sponge ? o.poseidon_sponge_off[o.nposeidon_sponge] : 0;
-        ks_bytes = o.nkeccak_sponge ? o.keccak_sponge_off[o.nkeccak_sponge] : 0;
-        need(PS, ps_bytes, {o.poseidon_sponge_inputs});
-        need(KS, ks_bytes, {o.keccak_sponge_inputs});
+        need(PS, fields_of(PS).bytes(o, 0), {o.poseidon_sponge_inputs});
+        need(KS, fields_of(KS).bytes(o, 0), {o.keccak_sponge_inputs});
         const zkm_ctx* owner = staged_ops_context(o.cpu_rows);
         if (owner && owner != c) refuse(CPU, "the lists were staged on another context");
     }
@@ -274,17 +282,13 @@ struct builder {
     void heights(const zkm_stark_config* cfg) {
         const zkm_segment_ops& o = *this->o;
         const size_t min_rows = std::max<size_t>((size_t)1 << cfg->cap_height, 64);   // max(num_cap_elements, MIN_TRACE_LEN), traces.rs:246-247
-        lg[AR] = height(AR, o.narithmetic, 1, (size_t)1 << 16);
-        lg[CPU] = log2_of(ncpu_rows());
+        for (const ops_fields& f : FIELDS) lg[f.t] = height(f.t, f.k(o), zkm_table_at(f.t)->writer.rows_per_op, min_rows);
+        // ... except where the rows are not the caller's count: the sponges' lengths, the bootstrap's permutations in front
         lg[PO] = height(PO, nposeidon(), 1, min_rows);
         lg[PS] = height(PS, ps_rows, 1, min_rows);
-        lg[KK] = height(KK, o.nkeccak, 24, min_rows);
         lg[KS] = height(KS, ks_rows, 1, min_rows);
-        lg[SE] = height(SE, o.nsha_extend, 1, min_rows);
-        lg[SES] = height(SES, o.nsha_extend_sponge, 48, min_rows);
-        lg[SC] = height(SC, o.nsha_compress, 65, min_rows);
-        lg[SCS] = height(SCS, o.nsha_compress_sponge, 1, min_rows);
-        lg[LO] = height(LO, o.nlogic, 1, min_rows);
+        lg[AR] = height(AR, o.narithmetic, 1, (size_t)1 << 16);
+        lg[CPU] = log2_of(ncpu_rows());
         lg[ME] = height(ME, nmemory(), 1, 1);
     }
     // ---- phase: the segment's part of the staging block, from byte `base`: the CPU rows (host rows only), then every list in host memory.
@@ -303,7 +307,7 @@ struct builder {
             at += align_up(l.bytes + skip);
         };
         // the lists the bootstrap writes the head of are joined in the staging block, wherever the caller's part lies
-        for (const list_ref& l : lists_of(d, ps_bytes, ks_bytes)) {
+        for (const list_ref& l : lists_of(d)) {
             const size_t skip = l.field == (void*)&d.memory_ops ? bn.memory_ops * 48
                                 : l.field == (void*)&d.poseidon_inputs ? bn.poseidon * 96
                                 : l.field == (void*)&d.poseidon_timestamps ? bn.poseidon * 8 : 0;
@@ -426,8 +430,8 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     mj.reserve(K);
     aj.reserve(K);
     for (size_t s = 0; s < K; s++) {
-        b[s].me_what = b[s].what + ": " + NAME[ME];
-        b[s].ar_what = b[s].what + ": " + NAME[AR];
+        b[s].me_what = b[s].what + ": " + zkm_table_at(ME)->name;
+        b[s].ar_what = b[s].what + ": " + zkm_table_at(AR)->name;
         mj.emplace_back(c, b[s].me_what.c_str(), b[s].d.memory_ops, b[s].nmemory());
         aj.emplace_back(c, b[s].ar_what.c_str(), b[s].d.arithmetic_ops, b[s].o->narithmetic);
         mj[s].d_acc = (unsigned long long*)(d_sync + s * SYNC_WORDS);
@@ -455,7 +459,7 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
         b[s].lg[ME] = log2_of(me_n);
         for (int t = 0; t < NTAB; t++) {
             out[s].lg[t] = b[s].lg[t];
-            out[s].off[t + 1] = out[s].off[t] + (zkm_table_width(TABLE_ID[t]) << b[s].lg[t]);
+            out[s].off[t + 1] = out[s].off[t] + (zkm_table_at(t)->width << b[s].lg[t]);
         }
     }
     if (!write) return out;
@@ -463,7 +467,7 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     // ---- one output block per segment (each handle is freed on its own) and every writer, a launch per kernel for the wave; wait (3)
     for (size_t s = 0; s < K; s++) {
         b[s].put(sb, false);
-        out[s].block = zkm_scratch(c, out[s].off[12] * sizeof(gl_t));
+        out[s].block = zkm_scratch(c, out[s].off[NTAB] * sizeof(gl_t));
     }
     auto T = [&](size_t s, int t) { return out[s].block.as<gl_t>() + out[s].off[t]; };
     auto flag = [&](size_t s, int k) { return (unsigned*)(d_sync + s * SYNC_WORDS + 9) + k; };   // 0 Logic, 1 Memory, 2 Arithmetic
@@ -474,22 +478,23 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
         for (size_t s = 0; s < K; s++) { lg[s] = b[s].lg[AR]; o[s] = T(s, AR); bad[s] = flag(s, 2); }
         zkm_arithmetic_write(aj.data(), K, lg, o, bad);
     }
-    // the data-parallel writers: the descriptor of table t for segment s
-    auto writers = [&](int t, auto&& seg) {
+    // the data-parallel writers: table t's descriptor for segment s from the table's description and its fields, then what only this
+    // table has (`more`)
+    auto writers = [&](int t, auto&& more) {
+        const ops_fields& f = fields_of(t);
+        const zkm_writer& d = zkm_table_at(t)->writer;
         zkm_writer_seg w[ZKM_MAX_SEG];
         for (size_t s = 0; s < K; s++) {
-            w[s] = seg(b[s], *b[s].o);
-            w[s].n = b[s].n(t);
-            w[s].out = T(s, t);
+            w[s] = zkm_writer_seg{{}, f.k(*b[s].o), b[s].n(t), 0, T(s, t)};
+            for (uint32_t i = 0; i < d.nlists; i++) w[s].in[d.variable ? 2 * i : i] = f.ptr(b[s].d, f.list[i]);
+            more(s, w[s]);
         }
-        zkm_launch_writers(c, TABLE_ID[t], w, K);
+        zkm_launch_writers(c, zkm_table_at(t)->id, w, K);
     };
-    using B = const builder&;
-    using O = const zkm_segment_ops&;
-    // (a Poseidon table without permutations is seed 0 with no inputs: every row is the padding row)
+    using W = zkm_writer_seg&;
     // (PoseidonSponge first: its writer zero-fills the table, the bootstrap's rows go in behind it; the bootstrap's timestamps in front of
     // the Poseidon writer)
-    writers(PS, [](B b, O o) { return zkm_writer_seg{{b.d.poseidon_sponge_inputs, b.d_pso, b.d.poseidon_sponge_meta, b.d_psr}, o.nposeidon_sponge}; });
+    writers(PS, [&](size_t s, W w) { w.in[1] = b[s].d_pso; w.in[3] = b[s].d_psr; });
     if (nboot) {
         for (size_t s = 0; s < K; s++) {
             if (!b[s].im) continue;
@@ -505,20 +510,15 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
         side.st = nullptr;                      // (from here on the compute stream is behind the chains)
         zkm_boot_late(c, bj.data(), K, d_desc + nboot);
     }
-    writers(PO, [](B b, O) { return zkm_writer_seg{{b.nposeidon() ? b.d.poseidon_inputs : nullptr, b.nposeidon() ? b.d.poseidon_timestamps : nullptr}, b.nposeidon()}; });
-    writers(KK, [](B b, O o) { return zkm_writer_seg{{b.d.keccak_inputs, b.d.keccak_timestamps}, o.nkeccak}; });
-    writers(KS, [](B b, O o) { return zkm_writer_seg{{b.d.keccak_sponge_inputs, b.d_kso, b.d.keccak_sponge_meta, b.d_ksr}, o.nkeccak_sponge, 0, b.ks_rows}; });
-    writers(SE, [](B b, O o) { return zkm_writer_seg{{b.d.sha_extend_inputs, b.d.sha_extend_timestamps}, o.nsha_extend}; });
-    writers(SES, [](B b, O o) { return zkm_writer_seg{{b.d.sha_extend_sponge_w16, b.d.sha_extend_sponge_meta}, o.nsha_extend_sponge}; });
-    writers(SC, [](B b, O o) { return zkm_writer_seg{{b.d.sha_compress_hx, b.d.sha_compress_w, b.d.sha_compress_meta}, o.nsha_compress}; });
-    writers(SCS, [](B b, O o) {
-        return zkm_writer_seg{{b.d.sha_compress_sponge_hx, b.d.sha_compress_sponge_w, b.d.sha_compress_sponge_meta}, o.nsha_compress_sponge};
+    // (the bootstrap's permutations come first; a Poseidon table without permutations is seed 0 with no inputs: every row is the padding row)
+    writers(PO, [&](size_t s, W w) {
+        w.k = b[s].nposeidon();
+        if (!w.k) w.in[0] = w.in[1] = nullptr;
     });
-    {
-        zkm_writer_seg w[ZKM_MAX_SEG];
-        for (size_t s = 0; s < K; s++) w[s] = zkm_writer_seg{{b[s].d.logic_ops}, b[s].o->nlogic, b[s].n(LO), 0, T(s, LO), (int*)flag(s, 0)};
-        zkm_launch_writers(c, ZKM_TABLE_LOGIC, w, K);
-    }
+    writers(KK, [](size_t, W) {});
+    writers(KS, [&](size_t s, W w) { w.in[1] = b[s].d_kso; w.in[3] = b[s].d_ksr; w.aux = b[s].ks_rows; });
+    for (const int t : {SE, SES, SC, SCS}) writers(t, [](size_t, W) {});
+    writers(LO, [&](size_t s, W w) { w.bad = (int*)flag(s, 0); });
     {
         unsigned lg[ZKM_MAX_SEG];
         gl_t* o[ZKM_MAX_SEG];
@@ -547,7 +547,7 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     c->download(sync.data(), d_sync, K * SYNC_WORDS * 8);                                                               // wait (3)
     for (size_t s = 0; s < K; s++) {
         const unsigned* f = (const unsigned*)&sync[s * SYNC_WORDS + 9];
-        if (f[0]) b[s].refuse(LO, "op code out of range (0 and, 1 or, 2 xor, 3 nor)");
+        if (f[0]) b[s].refuse(LO, zkm_table_at(LO)->writer.bad);
         if (f[1]) b[s].refuse(ME, "a range check is 2^log_n or more (a context or segment gap)");
         if (f[2]) b[s].refuse(AR, "a shared-column value is 2^16 or more");
         if (b[s].im)
@@ -656,7 +656,7 @@ static int prove_segments_ops(const char* what, zkm_ctx* c, const zkm_stark_conf
             double total = 0;
             for (size_t s = 0; s < nseg; s++) {
                 double tables = 0;
-                for (int t = 0; t < NTAB; t++) tables += 8.0 * (double)(zkm_table_width(TABLE_ID[t]) << b[s].lg[t]);
+                for (int t = 0; t < NTAB; t++) tables += 8.0 * (double)(zkm_table_at(t)->width << b[s].lg[t]);
                 total += zkm_segment_footprint(cfg, b[s].lg) + tables + (double)b[s].plan(true, 0) + (double)zkm_boot_scratch_bytes(b[s].im);
             }
             nwaves = (size_t)std::min<double>((double)nseg, std::max(1.0, std::ceil(total / std::max(budget, 1.0))));
@@ -672,7 +672,7 @@ static int prove_segments_ops(const char* what, zkm_ctx* c, const zkm_stark_conf
                 tr[s] = traces[s];
                 lg[s] = blocks[s].lg;
                 if (offsets_out)
-                    if (const int rc = zkm_prove_segment(nullptr, cfg, traces[s], lg[s], nullptr, 0, nullptr, offsets_out + 13 * (s0 + s), nullptr, err))
+                    if (const int rc = zkm_prove_segment(nullptr, cfg, traces[s], lg[s], nullptr, 0, nullptr, offsets_out + (NTAB + 1) * (s0 + s), nullptr, err))
                         return rc;
             }
             if (proofs)
@@ -761,7 +761,7 @@ int zkm_segment_ops_stage(zkm_ctx* c, const zkm_segment_ops* ops, zkm_staged_ops
         h->dev.poseidon_sponge_off = h->ps_off.data();
         h->dev.keccak_sponge_off = h->ks_off.data();
         const size_t cpu_bytes = ops->ncpu_rows * CPU_W * 8;
-        std::vector<list_ref> lists = lists_of(h->dev, b.ps_bytes, b.ks_bytes);
+        std::vector<list_ref> lists = lists_of(h->dev);
         size_t bytes = align_up(cpu_bytes);
         for (const list_ref& l : lists) bytes += align_up(l.bytes);
         h->block = zkm_scratch(c, bytes);

@@ -339,13 +339,8 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
     zkm_scratch vals(c, nseg * nalphas * size * sizeof(gl_t));
     gl_t* const d_vals = vals.as<gl_t>();
     {
-        static const char* const names[] = {"quotient_poseidon", "quotient_logic", "quotient_keccak_sponge", "quotient_keccak", "quotient_memory", "quotient_poseidon_sponge", "quotient_sha_extend", "quotient_sha_extend_sponge", "quotient_sha_compress",
-                                            "quotient_sha_compress_sponge", "quotient_arithmetic", "quotient_cpu"};
-        zkm_prof_scope ps(c, names[table_id]);
+        zkm_prof_scope ps(c, zkm_table(table_id)->quotient_scope);
         dim3 grid((size + 255) / 256, 1, z), block(256);
-#define ZKM_LAUNCH_QUOTIENT(T, NA)                                                                                              \
-    hipLaunchKernelGGL((k_quotient<T, NA>), grid, block, 0, c->stream, trace->lde, aux->lde, log_n, lde_bits, lookups, d_alphas, lookup_ch, wpow, gn, \
-                       last, w_n, n_inv, d_vals, trace_seg, aux_seg)
         if (table_id == ZKM_TABLE_KECCAK && size * nseg <= c->keccak_parts_max_points && !check) {
             // short table: 25 threads per point, then the sum of the parts (constraints_dev.h)
             const size_t per = nalphas * (KECCAK_NUM_CONSTRAINTS + 1);
@@ -370,33 +365,12 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
             hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)((nalphas * size + 255) / 256), 1, z), block, 0, c->stream, d_tmp.as<gl_t>(),
                                (unsigned)KECCAK_CONSTRAINT_PARTS, nalphas * size, d_vals);
         } else
-        switch (table_id * 2 + (int)nalphas - 1) {
-            case 0: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_POSEIDON, 1); break;
-            case 1: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_POSEIDON, 2); break;
-            case 2: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_LOGIC, 1); break;
-            case 3: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_LOGIC, 2); break;
-            case 4: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_KECCAK_SPONGE, 1); break;
-            case 5: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_KECCAK_SPONGE, 2); break;
-            case 6: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_KECCAK, 1); break;
-            case 7: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_KECCAK, 2); break;
-            case 8: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_MEMORY, 1); break;
-            case 9: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_MEMORY, 2); break;
-            case 10: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_POSEIDON_SPONGE, 1); break;
-            case 11: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_POSEIDON_SPONGE, 2); break;
-            case 12: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_SHA_EXTEND, 1); break;
-            case 13: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_SHA_EXTEND, 2); break;
-            case 14: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_SHA_EXTEND_SPONGE, 1); break;
-            case 15: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_SHA_EXTEND_SPONGE, 2); break;
-            case 16: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_SHA_COMPRESS, 1); break;
-            case 17: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_SHA_COMPRESS, 2); break;
-            case 18: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_SHA_COMPRESS_SPONGE, 1); break;
-            case 19: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_SHA_COMPRESS_SPONGE, 2); break;
-            case 20: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_ARITHMETIC, 1); break;
-            case 21: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_ARITHMETIC, 2); break;
-            case 22: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_CPU, 1); break;
-            default: ZKM_LAUNCH_QUOTIENT(ZKM_TABLE_CPU, 2); break;
-        }
-#undef ZKM_LAUNCH_QUOTIENT
+            zkm_with_table(table_id, [&](auto T) {
+                constexpr int TABLE = decltype(T)::value;
+                auto* const kernel = nalphas == 1 ? k_quotient<TABLE, 1> : k_quotient<TABLE, 2>;
+                hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, trace->lde, aux->lde, log_n, lde_bits, lookups, d_alphas, lookup_ch, wpow, gn, last,
+                                   w_n, n_inv, d_vals, trace_seg, aux_seg);
+            });
         ZKM_HIP_CHECK(hipGetLastError());
     }
     {
@@ -501,7 +475,7 @@ void zkm_verify_line_constraints(zkm_ctx* c, int table_id, size_t nalphas, const
                                  size_t W, size_t A, size_t nseg) {
     if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("verify: segment count of a constraint launch out of range");
     if (nalphas < 1 || nalphas > 2) throw std::runtime_error("verify: 1 or 2 challenges supported");
-    if (table_id < 0 || table_id > ZKM_TABLE_CPU || zkm_table_width(table_id) != W) throw std::runtime_error("verify: unknown table id, or the width does not match the table");
+    if (!zkm_table(table_id) || zkm_table_width(table_id) != W) throw std::runtime_error("verify: unknown table id, or the width does not match the table");
     lookup_dev lookups{};
     seg_gl2 lookup_ch{};
     const uint32_t NL = table_lookup_args(table_id, nalphas, lookup_challenges, nseg, lookups, lookup_ch);
@@ -513,28 +487,12 @@ void zkm_verify_line_constraints(zkm_ctx* c, int table_id, size_t nalphas, const
         ro.v[sg] = rows_off[sg];
         ao.v[sg] = acc_off[sg];
     }
-    static const char* const names[] = {"verify/line_poseidon", "verify/line_logic", "verify/line_keccak_sponge", "verify/line_keccak", "verify/line_memory",
-                                        "verify/line_poseidon_sponge", "verify/line_sha_extend", "verify/line_sha_extend_sponge", "verify/line_sha_compress",
-                                        "verify/line_sha_compress_sponge", "verify/line_arithmetic", "verify/line_cpu"};
-    zkm_prof_scope ps(c, names[table_id]);
+    zkm_prof_scope ps(c, zkm_table(table_id)->line_scope);
     const dim3 grid(1, 1, (unsigned)nseg), block(64);
-#define ZKM_LAUNCH_LINE(T) \
-    hipLaunchKernelGGL((k_verify_line<T>), grid, block, 0, c->stream, d_rows, ro, d_acc, ao, (uint32_t)W, (uint32_t)A, NL, lookups, d_alphas, lookup_ch, own)
-    switch (table_id) {
-        case ZKM_TABLE_POSEIDON: ZKM_LAUNCH_LINE(ZKM_TABLE_POSEIDON); break;
-        case ZKM_TABLE_LOGIC: ZKM_LAUNCH_LINE(ZKM_TABLE_LOGIC); break;
-        case ZKM_TABLE_KECCAK_SPONGE: ZKM_LAUNCH_LINE(ZKM_TABLE_KECCAK_SPONGE); break;
-        case ZKM_TABLE_KECCAK: ZKM_LAUNCH_LINE(ZKM_TABLE_KECCAK); break;
-        case ZKM_TABLE_MEMORY: ZKM_LAUNCH_LINE(ZKM_TABLE_MEMORY); break;
-        case ZKM_TABLE_POSEIDON_SPONGE: ZKM_LAUNCH_LINE(ZKM_TABLE_POSEIDON_SPONGE); break;
-        case ZKM_TABLE_SHA_EXTEND: ZKM_LAUNCH_LINE(ZKM_TABLE_SHA_EXTEND); break;
-        case ZKM_TABLE_SHA_EXTEND_SPONGE: ZKM_LAUNCH_LINE(ZKM_TABLE_SHA_EXTEND_SPONGE); break;
-        case ZKM_TABLE_SHA_COMPRESS: ZKM_LAUNCH_LINE(ZKM_TABLE_SHA_COMPRESS); break;
-        case ZKM_TABLE_SHA_COMPRESS_SPONGE: ZKM_LAUNCH_LINE(ZKM_TABLE_SHA_COMPRESS_SPONGE); break;
-        case ZKM_TABLE_ARITHMETIC: ZKM_LAUNCH_LINE(ZKM_TABLE_ARITHMETIC); break;
-        default: ZKM_LAUNCH_LINE(ZKM_TABLE_CPU); break;
-    }
-#undef ZKM_LAUNCH_LINE
+    zkm_with_table(table_id, [&](auto T) {
+        hipLaunchKernelGGL((k_verify_line<decltype(T)::value>), grid, block, 0, c->stream, d_rows, ro, d_acc, ao, (uint32_t)W, (uint32_t)A, NL, lookups, d_alphas, lookup_ch,
+                           own);
+    });
     ZKM_HIP_CHECK(hipGetLastError());
 }
 

@@ -258,10 +258,8 @@ __global__ __launch_bounds__(256) void k_verify_reduce(const zkm_verify_table* _
 const char* const CODE_NAMES[] = {"OK", "SHAPE", "TRANSCRIPT_STATE", "CTL_CHALLENGES", "QUOTIENT", "POW", "INITIAL_MERKLE", "FRI_EVAL", "FRI_MERKLE",
                                   "FINAL_POLY", "CTL_SUM", "FAILED"};
 std::string table_label(const zkm_table_input* tables, size_t t) {
-    static const char* const names[12] = {"Arithmetic", "Cpu", "Poseidon", "PoseidonSponge", "Keccak", "KeccakSponge", "ShaExtend", "ShaExtendSponge",
-                                          "ShaCompress", "ShaCompressSponge", "Logic", "Memory"};   // Table's Debug names, all_stark.rs:96-110
-    const int e = zkm_table_enum_index(tables[t].table_id);
-    return "table " + std::to_string(t) + " (" + (e < 0 ? "Table" + std::to_string(tables[t].table_id) : std::string(names[e])) + ")";
+    const zkm_table_row* row = zkm_table(tables[t].table_id);
+    return "table " + std::to_string(t) + " (" + (row ? std::string(row->name) : "Table" + std::to_string(tables[t].table_id)) + ")";
 }
 
 // acc alpha^k + sum_j alpha^j v_j over k values v_j: F2 pairs (stride 2) or base-field words (stride 1)
@@ -724,7 +722,7 @@ int zkm_verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, co
                         const uint64_t* const* pub, const size_t* npub, const uint64_t* const* ctl_challenges, zkm_verify_report* reports, char** err) {
     return guarded("zkm_verify_segments", c, reports, nseg, err, [&] {
         if (!cfg || !proofs || !proof_words || nseg == 0) throw std::runtime_error("zkm_verify_segments: null argument");
-        zkm_table_input tables[12];
+        zkm_table_input tables[ZKM_NUM_TABLES];
         zkm_all_stark_table_inputs(tables);
         const zkm_cross_table_lookup* ctls;
         const zkm_ctl_side* sides;
@@ -737,7 +735,7 @@ int zkm_verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, co
             if (in[s].npub && !in[s].pub) throw std::runtime_error("zkm_verify_segments: null public values");
         }
         std::vector<seg_state> segs;
-        verify_segments(c, cfg, nseg, in.data(), 12, ctls, sides, nctls, false, nullptr, nullptr, segs);
+        verify_segments(c, cfg, nseg, in.data(), ZKM_NUM_TABLES, ctls, sides, nctls, false, nullptr, nullptr, segs);
         return finish("zkm_verify_segments", segs, reports, err, true);
     });
 }

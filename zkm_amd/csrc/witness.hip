@@ -6,7 +6,7 @@
 //
 // Every kernel serves K segments in one launch: its segment's zkm_writer_seg (zkm_internal.h) comes from kernel-argument slot
 // blockIdx.z, the grid's x extent is the largest segment's, and the `r >= n` that ends a thread beyond its table ends the workgroups
-// beyond a smaller segment's extent too.  zkm_launch_writers is the one launcher; the zkm_launch_*_trace helpers are its K = 1 case.
+// beyond a smaller segment's extent too.  zkm_launch_writers is the one launcher.
 #include <vector>
 
 #include "poseidon_dev.h"
@@ -135,13 +135,6 @@ __global__ __launch_bounds__(256) void k_keccak_sponge_rows(zkm_seg_args<zkm_wri
     for (int i = 0; i < 32; i++) o[(size_t)(438 + i) * n] = (uint8_t)(st[i / 8] >> (8 * (i & 7)));
 }
 
-void zkm_launch_keccak_sponge_trace(zkm_ctx* c, const uint8_t* d_inputs, const uint64_t* d_off, const uint64_t* d_meta,
-                                    const uint64_t* d_row_off, size_t nops, size_t rows_used, unsigned log_n, gl_t* out) {
-    const zkm_writer_seg a{{d_inputs, d_off, d_meta, d_row_off}, nops, (size_t)1 << log_n, rows_used, out};
-    zkm_launch_writers(c, ZKM_TABLE_KECCAK_SPONGE, &a, 1);
-}
-
-
 // ------------------------------------------------------------------ PoseidonStark witness (a13)
 __device__ __forceinline__ uint64_t splitmix_at(uint64_t seed, uint64_t k) {
     uint64_t z = seed + k * 0x9E3779B97F4A7C15ULL;
@@ -224,12 +217,6 @@ __global__ __launch_bounds__(256) void k_poseidon_trace(zkm_seg_args<zkm_writer_
     for (int i = 0; i < 12; i++) o[(size_t)(13 + i) * n] = gl_canon(s[i]);
 }
 
-void zkm_launch_poseidon_trace(zkm_ctx* c, uint64_t seed, const uint64_t* inputs, const uint64_t* ts, size_t num_perms, unsigned log_n,
-                               gl_t* out) {
-    const zkm_writer_seg a{{inputs, ts}, num_perms, (size_t)1 << log_n, seed, out};
-    zkm_launch_writers(c, ZKM_TABLE_POSEIDON, &a, 1);
-}
-
 // ------------------------------------------------------------------ LogicStark witness (logic.rs:122-183)
 // One thread per row; stores are coalesced per column (column-major).
 __global__ __launch_bounds__(256) void k_logic_trace(zkm_seg_args<zkm_writer_seg> S) {
@@ -256,11 +243,6 @@ __global__ __launch_bounds__(256) void k_logic_trace(zkm_seg_args<zkm_writer_seg
         out[(size_t)(36 + i) * n + r] = (b >> i) & 1;
     }
     out[(size_t)68 * n + r] = res;
-}
-
-void zkm_launch_logic_trace(zkm_ctx* c, const uint32_t* d_ops, size_t nops, size_t n, gl_t* out, int* d_bad) {
-    const zkm_writer_seg a{{d_ops}, nops, n, 0, out, d_bad};
-    zkm_launch_writers(c, ZKM_TABLE_LOGIC, &a, 1);
 }
 
 // ------------------------------------------------------------------ KeccakStark witness (keccak/keccak_stark.rs:62-226)
@@ -331,11 +313,6 @@ __global__ __launch_bounds__(256) void k_keccak_trace(zkm_seg_args<zkm_writer_se
     o[(size_t)2430 * n] = appp >> 32;
 }
 
-void zkm_launch_keccak_trace(zkm_ctx* c, const uint64_t* d_inputs, const uint64_t* d_ts, size_t nperms, size_t n, gl_t* out) {
-    const zkm_writer_seg a{{d_inputs, d_ts}, nperms, n, 0, out};
-    zkm_launch_writers(c, ZKM_TABLE_KECCAK, &a, 1);
-}
-
 // ------------------------------------------------------------------ PoseidonSpongeStark witness (poseidon_sponge_stark.rs:186-381)
 // One lane per sponge operation, as k_keccak_sponge_trace; column map poseidon_sponge/columns.rs:17-66.  The output buffer is
 // zero-filled first; only non-zero cells are stored.
@@ -399,12 +376,6 @@ __global__ __launch_bounds__(128) void k_poseidon_sponge_trace(zkm_seg_args<zkm_
         if (!full) break;
         absorbed += 32;
     }
-}
-
-void zkm_launch_poseidon_sponge_trace(zkm_ctx* c, const uint8_t* d_inputs, const uint64_t* d_off, const uint64_t* d_meta,
-                                      const uint64_t* d_row_off, size_t nops, unsigned log_n, gl_t* out) {
-    const zkm_writer_seg a{{d_inputs, d_off, d_meta, d_row_off}, nops, (size_t)1 << log_n, 0, out};
-    zkm_launch_writers(c, ZKM_TABLE_POSEIDON_SPONGE, &a, 1);
 }
 
 // ------------------------------------------------------------------ SHA-256 message-schedule witnesses
@@ -506,15 +477,6 @@ __global__ __launch_bounds__(256) void k_sha_extend_sponge_trace(zkm_seg_args<zk
     o[(size_t)75 * n] = meta[4 * e + 3] + 20 * (uint64_t)rd;
 }
 
-void zkm_launch_sha_extend_trace(zkm_ctx* c, const uint8_t* d_inputs, const uint64_t* d_ts, size_t k, size_t n, gl_t* out) {
-    const zkm_writer_seg a{{d_inputs, d_ts}, k, n, 0, out};
-    zkm_launch_writers(c, ZKM_TABLE_SHA_EXTEND, &a, 1);
-}
-void zkm_launch_sha_extend_sponge_trace(zkm_ctx* c, const uint32_t* d_w16, const uint64_t* d_meta, size_t k, size_t n, gl_t* out) {
-    const zkm_writer_seg a{{d_w16, d_meta}, k, n, 0, out};
-    zkm_launch_writers(c, ZKM_TABLE_SHA_EXTEND_SPONGE, &a, 1);
-}
-
 // ------------------------------------------------------------------ SHA-256 compression witnesses
 // ShaCompressStark::generate_trace (sha_compress/sha_compress_stark.rs:227-400, rows as emitted by witness/util.rs:605-690: 65 per
 // compression) and ShaCompressSpongeStark::generate_trace (sha_compress_sponge_stark.rs:118-230).  One thread per row; the thread
@@ -611,11 +573,6 @@ __global__ __launch_bounds__(256) void k_sha_compress_sponge_trace(zkm_seg_args<
     o[(size_t)125 * n] = meta[8 * r + 6];
     o[(size_t)126 * n] = 1;
 }
-void zkm_launch_sha_compress_trace(zkm_ctx* c, bool sponge, const uint32_t* d_hx, const uint32_t* d_w, const uint64_t* d_meta, size_t k,
-                                   size_t n, gl_t* out) {
-    const zkm_writer_seg a{{d_hx, d_w, d_meta}, k, n, 0, out};
-    zkm_launch_writers(c, sponge ? ZKM_TABLE_SHA_COMPRESS_SPONGE : ZKM_TABLE_SHA_COMPRESS, &a, 1);
-}
 
 // ------------------------------------------------------------------ the launcher of every writer above, nseg <= ZKM_MAX_SEG segments
 // One thread per row of the table (per operation for the two chained sponge kernels): the grid covers the largest segment.
@@ -627,23 +584,24 @@ void zkm_launch_writers(zkm_ctx* c, int table_id, const zkm_writer_seg* segs, si
         max_k = std::max(max_k, segs[s].k);
     }
     const size_t rows256 = (max_n + 255) / 256, ops128 = (max_k + 127) / 128;
-    auto go = [&](const char* scope, void (*kernel)(zkm_seg_args<zkm_writer_seg>), const zkm_writer_seg* a, size_t grid, unsigned threads) {
-        zkm_prof_scope ps(c, scope);
+    const zkm_table_row* row = zkm_table(table_id);
+    auto go = [&](void (*kernel)(zkm_seg_args<zkm_writer_seg>), const zkm_writer_seg* a, size_t grid, unsigned threads) {
+        zkm_prof_scope ps(c, row->writer_scope);
         zkm_launch_segs(c->stream, kernel, a, nseg, grid, threads);
     };
     switch (table_id) {
-    case ZKM_TABLE_POSEIDON: return go("poseidon_trace", k_poseidon_trace, segs, rows256, 256);
-    case ZKM_TABLE_KECCAK: return go("keccak_trace", k_keccak_trace, segs, rows256, 256);
-    case ZKM_TABLE_SHA_EXTEND: return go("sha_extend_trace", k_sha_extend_trace, segs, rows256, 256);
-    case ZKM_TABLE_SHA_EXTEND_SPONGE: return go("sha_extend_sponge_trace", k_sha_extend_sponge_trace, segs, rows256, 256);
-    case ZKM_TABLE_SHA_COMPRESS: return go("sha_compress_trace", k_sha_compress_trace, segs, rows256, 256);
-    case ZKM_TABLE_SHA_COMPRESS_SPONGE: return go("sha_compress_sponge_trace", k_sha_compress_sponge_trace, segs, rows256, 256);
-    case ZKM_TABLE_LOGIC: return go("logic_trace", k_logic_trace, segs, rows256, 256);
+    case ZKM_TABLE_POSEIDON: return go(k_poseidon_trace, segs, rows256, 256);
+    case ZKM_TABLE_KECCAK: return go(k_keccak_trace, segs, rows256, 256);
+    case ZKM_TABLE_SHA_EXTEND: return go(k_sha_extend_trace, segs, rows256, 256);
+    case ZKM_TABLE_SHA_EXTEND_SPONGE: return go(k_sha_extend_sponge_trace, segs, rows256, 256);
+    case ZKM_TABLE_SHA_COMPRESS: return go(k_sha_compress_trace, segs, rows256, 256);
+    case ZKM_TABLE_SHA_COMPRESS_SPONGE: return go(k_sha_compress_sponge_trace, segs, rows256, 256);
+    case ZKM_TABLE_LOGIC: return go(k_logic_trace, segs, rows256, 256);
     case ZKM_TABLE_POSEIDON_SPONGE:
         // the table is zero-filled first; only non-zero cells are stored
         for (size_t s = 0; s < nseg; s++)
             ZKM_HIP_CHECK(hipMemsetAsync(segs[s].out, 0, (size_t)ZKM_POSEIDON_SPONGE_COLS * segs[s].n * sizeof(gl_t), c->stream));
-        if (max_k) go("poseidon_sponge_trace", k_poseidon_sponge_trace, segs, ops128, 128);
+        if (max_k) go(k_poseidon_sponge_trace, segs, ops128, 128);
         return;
     case ZKM_TABLE_KECCAK_SPONGE: {
         // per segment: the sponge state before each row in use (25 words) and the row's operation
@@ -655,7 +613,7 @@ void zkm_launch_writers(zkm_ctx* c, int table_id, const zkm_writer_seg* segs, si
             a[s].tmp[0] = tmp.back().p;
             a[s].tmp[1] = tmp.back().as<uint64_t>() + rows * 25;
         }
-        zkm_prof_scope ps(c, "keccak_sponge_trace");
+        zkm_prof_scope ps(c, row->writer_scope);
         zkm_launch_segs(c->stream, k_keccak_sponge_states, a.data(), nseg, ops128, 128);
         zkm_launch_segs(c->stream, k_keccak_sponge_rows, a.data(), nseg, rows256, 256);
         return;

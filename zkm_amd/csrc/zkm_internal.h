@@ -21,6 +21,7 @@
 #include "../../include/zkm_hip.h"
 #include "gl_dev.h"
 #include "proof_blob.h"
+#include "tables.h"
 
 #define ZKM_HIP_CHECK(expr)                                                                                  \
     do {                                                                                                     \
@@ -379,12 +380,6 @@ void zkm_ntt_natural_ex(zkm_ctx* c, const gl_t* in, size_t cs_in, gl_t* scratch,
 // (nseg > 1: segment s reads c0 / c1 + s * val_seg and writes digests + s * dig_seg)
 void zkm_launch_merkle_leaves_ext(zkm_ctx*, const gl_t* c0, const gl_t* c1, size_t nleaves, unsigned arity, gl_t* digests, size_t nseg = 1,
                                   size_t val_seg = 0, size_t dig_seg = 0);
-void zkm_launch_poseidon_trace(zkm_ctx*, uint64_t seed, const uint64_t* d_inputs, const uint64_t* d_ts, size_t num_perms, unsigned log_n,
-                               gl_t* out);
-void zkm_launch_poseidon_sponge_trace(zkm_ctx*, const uint8_t* d_inputs, const uint64_t* d_off, const uint64_t* d_meta,
-                                      const uint64_t* d_row_off, size_t nops, unsigned log_n, gl_t* out);
-void zkm_launch_keccak_sponge_trace(zkm_ctx*, const uint8_t* d_inputs, const uint64_t* d_off, const uint64_t* d_meta,
-                                    const uint64_t* d_row_off, size_t nops, size_t rows_used, unsigned log_n, gl_t* out);
 // build all digest layers above level 0; fills level_off and returns total words needed (call with digests==nullptr to size)
 size_t zkm_merkle_layout(unsigned log_leaves, unsigned cap_height, std::vector<size_t>& level_off);
 // (nseg trees of the same shape, dig_seg words apart: one launch per group of levels for all of them)
@@ -439,14 +434,14 @@ void zkm_launch_canon(zkm_ctx* c, gl_t* v, size_t total);   // v[i] = canonical 
 void zkm_host_poseidon_permute(uint64_t st[12]);
 void zkm_host_poseidon_permute_reference(uint64_t st[12]);   // poseidon_dev.h compiled for the host (cross-check)
 // ---- hash.hip (LogicStark witness)
-// ---- tables' own logUp lookups (core.hip: definitions; ctl.hip: helper columns)
-struct zkm_table_lookup { uint32_t ncols; const uint32_t* cols; uint32_t table_col, freq_col; };
+// ---- tables' own logUp lookups (tables.h: definitions; ctl.hip: helper columns)
 const zkm_table_lookup* zkm_table_lookups(int table_id, size_t* n);
 void zkm_table_lookup_columns_device(zkm_ctx* c, int table_id, const uint64_t* challenges, size_t nch, const gl_t* d_trace, size_t n,
                                      gl_t* d_out, size_t nseg = 1, size_t trace_seg = 0, size_t out_seg = 0);
 // ---- witness.hip: the data-parallel writers, K segments a launch.  One descriptor serves every table: `in` are the table's input lists
-// in the order of its zkm_launch_*_trace below, k the operations, n the table's rows, aux the Poseidon seed or the KeccakSponge rows in
-// use, bad the Logic flag; tmp is the KeccakSponge scratch (filled in by the launcher).
+// in the order of its description (tables.h zkm_writer; a sponge: the bytes, their offsets, the meta words, the first row of each
+// operation), k the operations, n the table's rows, aux the Poseidon seed or the KeccakSponge rows in use, bad the Logic flag; tmp is
+// the KeccakSponge scratch (filled in by the launcher).
 struct zkm_writer_seg {
     const void* in[4];
     size_t k, n, aux;
@@ -455,12 +450,6 @@ struct zkm_writer_seg {
     void* tmp[2];
 };
 void zkm_launch_writers(zkm_ctx* c, int table_id, const zkm_writer_seg* segs, size_t nseg);
-void zkm_launch_sha_extend_trace(zkm_ctx* c, const uint8_t* d_inputs, const uint64_t* d_ts, size_t k, size_t n, gl_t* out);
-void zkm_launch_sha_extend_sponge_trace(zkm_ctx* c, const uint32_t* d_w16, const uint64_t* d_meta, size_t k, size_t n, gl_t* out);
-void zkm_launch_sha_compress_trace(zkm_ctx* c, bool sponge, const uint32_t* d_hx, const uint32_t* d_w, const uint64_t* d_meta, size_t k,
-                                   size_t n, gl_t* out);
-void zkm_launch_keccak_trace(zkm_ctx* c, const uint64_t* d_inputs, const uint64_t* d_ts, size_t nperms, size_t n, gl_t* out);
-void zkm_launch_logic_trace(zkm_ctx* c, const uint32_t* d_ops, size_t nops, size_t n, gl_t* out, int* d_bad);
 
 // ---- the two witnesses whose heights need the device, in phases: zkm_memory_trace / zkm_arithmetic_trace run each one's phases back
 // to back with a host wait between them; segment_ops.hip runs the phases of both side by side, so that one wait serves both.  A phase
@@ -550,7 +539,7 @@ struct table_zs {
 };
 std::vector<table_zs> zkm_derive_zs(size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides, size_t nctls, size_t nch,
                                     const uint64_t* challenges);
-void zkm_all_stark_table_inputs(zkm_table_input out[12]);   // ctl.hip: the twelve tables of the built-in AllStark (no traces, log_n 0)
+void zkm_all_stark_table_inputs(zkm_table_input out[ZKM_NUM_TABLES]);   // ctl.hip: the twelve tables of the built-in AllStark (no traces, log_n 0)
 // One (segment, table) of a verify call as the kernels see it: where its blob lies in the call's device block, the blob's validated
 // description (proof_blob.h: every offset follows from it), and what the transcript replay gave.
 #define ZKM_VERIFY_LINE_POINTS 5      // constraints are evaluated on the rows v0 + t v1, t = 0 .. 4 (degree <= 3, one point to spare)
@@ -581,7 +570,7 @@ size_t zkm_verify_run(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, cons
 extern "C" int zkm_prove_segments_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const uint64_t* const* const* traces,
                                         const uint64_t* const* const* const* columns, const unsigned* const* log_n, const uint64_t* const* pub,
                                         const size_t* npub, uint64_t* const* proofs, uint64_t* const* challenges, char** err, size_t seg_base);
-double zkm_segment_footprint(const zkm_stark_config* cfg, const unsigned log_n[12]);   // ctl.hip: estimated bytes of one segment in a proving wave
+double zkm_segment_footprint(const zkm_stark_config* cfg, const unsigned log_n[ZKM_NUM_TABLES]);   // ctl.hip: estimated bytes of one segment in a proving wave
 // segment_ops.hip: the body of zkm_prove_segments_ops, seg_base as above (the pool's workers)
 extern "C" int zkm_prove_segments_ops_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops,
                                             const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, size_t* offsets_out,
