@@ -232,6 +232,14 @@ int zkm_keccakf_batch(zkm_ctx* ctx, uint64_t* states, size_t k, char** err);
 #define ZKM_POSEIDON_PROBE_ADD_RC0 15
 int zkm_poseidon_selftest(zkm_ctx* ctx, uint32_t probe, uint32_t arg, const uint64_t* in, size_t n, uint64_t* out, char** err);
 
+/* Parity / debug: the constraint consumer of the quotient kernels (the alpha-accumulation of vanishing_poly.rs:30-45,
+ * constraint_consumer.rs:57-62) on words the trace never holds.  n lanes each feed their own K terms -- terms[k * n + lane], ANY
+ * 64-bit words, also >= p -- to a consumer with the nalphas (1 or 2) challenges `alphas` (any words), `run` terms at a time (1 .. 8;
+ * the tail in one shorter run; 1 = the single-constraint path); out[a * n + lane] = sum_k terms[k] alphas[a]^(K-1-k) mod p, canonical.
+ * K = 0, n = 0, n > 2^20 or K * n > 2^26 is an error: nothing is launched. */
+int zkm_consumer_selftest(zkm_ctx* ctx, const uint64_t* alphas, size_t nalphas, const uint64_t* terms, size_t K, size_t n, uint32_t run,
+                          uint64_t* out, char** err);
+
 /* ------------------------------------------------------------------ a13: PoseidonStark witness
  * PoseidonStark::generate_trace (poseidon_stark.rs:104-160): 262 columns x 2^log_n rows, column-major,
  * from `num_perms` seeded 12-element inputs (SplitMix64(seed); timestamp 0, FILTER 1) padded with the

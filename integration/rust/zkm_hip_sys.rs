@@ -180,6 +180,7 @@ extern "C" {
     pub fn zkm_keccakf_batch(ctx: *mut zkm_ctx, states: *mut u64, k: usize, err: *mut *mut c_char) -> c_int;
     /// parity / debug: one piece of the device's Poseidon permutation on chosen words (probe: ZKM_POSEIDON_PROBE_*, arg: see the header)
     pub fn zkm_poseidon_selftest(ctx: *mut zkm_ctx, probe: u32, arg: u32, input: *const u64, n: usize, out: *mut u64, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_consumer_selftest(ctx: *mut zkm_ctx, alphas: *const u64, nalphas: usize, terms: *const u64, K: usize, n: usize, run: u32, out: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_poseidon_trace(ctx: *mut zkm_ctx, seed: u64, num_perms: usize, log_n: c_uint, out_dev: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_poseidon_trace_inputs(ctx: *mut zkm_ctx, inputs: *const u64, timestamps: *const u64, num_perms: usize, log_n: c_uint,
                                      out_dev: *mut u64, err: *mut *mut c_char) -> c_int;

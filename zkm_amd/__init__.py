@@ -39,7 +39,7 @@ EXPORTS = [
     "zkm_host_register", "zkm_host_unregister", "zkm_all_stark_ctls", "zkm_all_stark_ctl_table", "zkm_prove_segment", "zkm_prove_segments", "zkm_prove_segments_columns", "zkm_prove_segment_columns", "zkm_ctx_synchronize", "zkm_ctx_stream", "zkm_dev_alloc", "zkm_dev_free",
     "zkm_dev_upload", "zkm_dev_download", "zkm_ntt", "zkm_field_selftest", "zkm_batch_commit_values", "zkm_batch_commit_coeffs", "zkm_batch_commit_columns", "zkm_batch_free",
     "zkm_batch_cap", "zkm_batch_coeffs", "zkm_batch_lde_row", "zkm_batch_lde_rows", "zkm_batch_leaf", "zkm_batch_merkle_path",
-    "zkm_batch_digest_layer", "zkm_poseidon_permute_batch", "zkm_keccakf_batch", "zkm_poseidon_selftest", "zkm_poseidon_trace", "zkm_keccak_sponge_trace", "zkm_keccak_trace", "zkm_logic_trace", "zkm_memory_trace", "zkm_arithmetic_trace",
+    "zkm_batch_digest_layer", "zkm_poseidon_permute_batch", "zkm_keccakf_batch", "zkm_poseidon_selftest", "zkm_consumer_selftest", "zkm_poseidon_trace", "zkm_keccak_sponge_trace", "zkm_keccak_trace", "zkm_logic_trace", "zkm_memory_trace", "zkm_arithmetic_trace",
     "zkm_poseidon_sponge_trace", "zkm_poseidon_trace_inputs", "zkm_sha_extend_trace", "zkm_sha_extend_sponge_trace",
     "zkm_sha_compress_trace", "zkm_sha_compress_sponge_trace",
     "zkm_table_width", "zkm_num_lookup_columns", "zkm_challenger_init",
@@ -251,6 +251,7 @@ def load():
         "zkm_poseidon_permute_batch": (C.c_int, [cp, cp, C.c_size_t, err]),
         "zkm_keccakf_batch": (C.c_int, [cp, cp, C.c_size_t, err]),
         "zkm_poseidon_selftest": (C.c_int, [cp, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u64p, err]),
+        "zkm_consumer_selftest": (C.c_int, [cp, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_uint32, u64p, err]),
         "zkm_poseidon_trace": (C.c_int, [cp, C.c_uint64, C.c_size_t, C.c_uint, cp, err]),
         "zkm_keccak_sponge_trace": (C.c_int, [cp, cp, u64p, u64p, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
         "zkm_poseidon_sponge_trace": (C.c_int, [cp, cp, u64p, u64p, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
@@ -910,6 +911,21 @@ class Context:
         err = C.c_char_p()
         _check(self.L.zkm_poseidon_selftest(self.h, probe, int(arg), words.ctypes.data_as(u64p), n, out.ctypes.data_as(u64p), C.byref(err)), err)
         return out if pairs else out.reshape(-1, 12)
+
+    def consumer_selftest(self, alphas, terms, run=8):
+        """The quotient kernels' constraint consumer on chosen words (zkm_consumer_selftest): `terms` is a (K, n) array of any uint64
+        -- lane l takes terms[:, l] in order, `run` at a time -- and `alphas` 1 or 2 challenges (any uint64).  Returns the
+        (len(alphas), n) canonical accumulators sum_k terms[k] alpha^(K-1-k) mod p."""
+        alphas = np.ascontiguousarray(alphas, dtype=np.uint64).reshape(-1)
+        terms = np.ascontiguousarray(terms, dtype=np.uint64)
+        if terms.ndim != 2:
+            raise ValueError("consumer_selftest: terms must be a (K, n) array")
+        K, n = terms.shape
+        out = np.zeros(alphas.size * n, dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.L.zkm_consumer_selftest(self.h, alphas.ctypes.data_as(u64p), alphas.size, terms.ctypes.data_as(u64p), K, n, int(run),
+                                            out.ctypes.data_as(u64p), C.byref(err)), err)
+        return out.reshape(alphas.size, n)
 
     def poseidon_permute_batch(self, states):
         k = (states.size if isinstance(states, np.ndarray) else states.words) // 12

@@ -3,8 +3,9 @@
 // Each eval_<table>_constraints restates the table's eval_packed_generic in the reference, emitting constraints in the
 // SAME ORDER (the order defines the alpha powers, constraint_consumer.rs:57-62).  `lv` points at the thread's element of
 // column 0 of the trace LDE, columns are `cs` words apart, the next row's element of a column sits `dnext` words after the
-// local one.  All values canonical.  Used by k_quotient in stark.hip; the CPU oracle has the same functions in
-// oracle/constraints_tmpl.h (test infrastructure).
+// local one.  Trace cells are canonical; intermediate values and the constraint values handed to the consumer may be loose
+// (gl_dev.h), only the accumulators a kernel stores are canonical (consumer_t::value).  Used by k_quotient in stark.hip; the
+// CPU oracle has the same functions in oracle/constraints_tmpl.h (test infrastructure).
 #pragma once
 #include "poseidon_dev.h"
 #include "hash_constants_dev.h"
@@ -13,90 +14,161 @@
 // ------------------------------------------------------------------ constraint consumer, Poseidon table
 // Constraint order = alpha-power order (constraint_consumer.rs:57-62): table constraints
 // (poseidon_stark.rs:554-594), then CTL checks (cross_table_lookup.rs:1067-1118), vanishing_poly.rs:30-45.
-template <int NA>
-struct consumer_t {
-    gl_t alpha[NA], acc[NA];
-    gl_t z_last, l_first, l_last;
-    __device__ __forceinline__ void constraint(gl_t c) {
-#pragma unroll
-        for (int j = 0; j < NA; j++) acc[j] = gl_add(gl_mul(acc[j], alpha[j]), c);
+//
+// An unreduced sum of 64 x 64-bit products x * w with wave-uniform w (a power of alpha, kept in SGPRs): three 64-bit columns of
+// weights 2^0, 2^32, 2^64 take the four 32 x 32 partial products with one multiply-add each, and every multiply-add's carry-out is
+// counted (k0, k1, k2: weights 2^64, 2^96, 2^128).  The terms are independent of each other; one reduction serves them all.
+// Capacity: a term adds at most one carry to k0 and k2 and two to k1, and value() needs k2 + 1 < 2^32 - 1 and its 64-bit
+// temporaries t2, t3 < 2^64, i.e. fewer than 2^31 terms could ever lose a carry.  A run holds at most consumer_t::RUN + 1 = 9.
+struct gl_wide_sum {
+    uint64_t c0, c1, c2;
+    uint32_t k0, k1, k2;
+    // col = a * b + col, cnt += carry-out  (a: SGPR, b: VGPR)
+    static __device__ __forceinline__ void mad(uint64_t& col, uint32_t& cnt, uint32_t a, uint32_t b) {
+        asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc" : "+v"(col), "+v"(cnt) : "s"(a), "v"(b) : "vcc");
     }
-    __device__ __forceinline__ void transition(gl_t c) { constraint(gl_mul(c, z_last)); }
-    __device__ __forceinline__ void last_row(gl_t c) { constraint(gl_mul(c, l_last)); }
-    __device__ __forceinline__ void first_row(gl_t c) { constraint(gl_mul(c, l_first)); }
+    // the sum starts as  x * (wh:wl) + c : the first product into an empty column cannot carry
+    __device__ __forceinline__ void start(uint64_t c, uint64_t x, uint32_t wl, uint32_t wh) {
+        const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+        c0 = c; c1 = (uint64_t)xl * wh; c2 = (uint64_t)xh * wh;
+        k0 = k1 = k2 = 0;
+        mad(c0, k0, wl, xl);
+        mad(c1, k1, wl, xh);
+    }
+    __device__ __forceinline__ void add(uint64_t x, uint32_t wl, uint32_t wh) {
+        const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+        mad(c0, k0, wl, xl);
+        mad(c1, k1, wh, xl);
+        mad(c1, k1, wl, xh);
+        mad(c2, k2, wh, xh);
+    }
+    // -> loose.  32-bit words of the sum: w0 = c0_lo, w1 = c0_hi + c1_lo, w2 = c1_hi + c2_lo + k0, w3 = c2_hi + k1, w4 = k2 (each plus
+    // the carry of the word below); w4 2^128 == -w4 2^32 (2^128 == EPS^2 == -2^32), and w4 2^32 is canonical for w4 < 2^32 - 1.
+    __device__ __forceinline__ uint64_t value() const {
+        const uint64_t t1 = (c0 >> 32) + (uint32_t)c1;
+        const uint64_t t2 = (uint64_t)(uint32_t)c2 + (c1 >> 32) + k0 + (t1 >> 32);
+        const uint64_t t3 = (c2 >> 32) + k1 + (t2 >> 32);
+        const uint32_t w4 = k2 + (uint32_t)(t3 >> 32);
+        return gl_sub_lc(gl_reduce128((t1 << 32) | (uint32_t)c0, (t3 << 32) | (uint32_t)t2), (uint64_t)w4 << 32);
+    }
 };
 
+// acc[j] = sum_i c_i alpha_j^(K-1-i) (+ acc_in alpha_j^K), the Horner recurrence acc = acc alpha + c of the reference -- as a residue:
+// the accumulators and the constraint values handed in are LOOSE words, value(j) is the canonical word the recurrence on canonical
+// values gives, and it is what every kernel stores.  A run of B <= RUN constraints known together is taken at once,
+//     acc <- acc alpha^B + c_0 alpha^(B-1) + ... + c_(B-2) alpha + c_(B-1),
+// as B independent products against the powers of alpha (wave-uniform, in SGPRs) summed unreduced (gl_wide_sum) and reduced once;
+// a single constraint is the run of one, acc alpha + c in one multiply-add with one reduction.
 template <int NA>
-__device__ __forceinline__ void sbox_constraints(consumer_t<NA>& k, gl_t in, gl_t inter, gl_t out) {
-    k.constraint(gl_sub(gl_mul(gl_mul(in, in), in), inter));
-    k.constraint(gl_sub(gl_mul(gl_mul(in, inter), inter), out));
-}
-
-__device__ __forceinline__ void mds_canon(gl_t s[12]) {
-    poseidon_mds(s);
+struct consumer_t {
+    static constexpr int RUN = 8;
+    gl_t alpha[NA];
+    uint64_t acc[NA];
+    uint32_t wl[NA][RUN], wh[NA][RUN];  // halves of alpha^(i+1); unused ones cost nothing (the evaluators are inlined into their kernel)
+    gl_t z_last, l_first, l_last;
+    // `a` must be the same word in every lane of the wave (a challenge: a kernel argument)
+    __device__ __forceinline__ void set_alpha(int j, gl_t a) {
+        alpha[j] = a;
+        gl_t p = gl_canon(a);
 #pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = gl_canon(s[i]);
+        for (int i = 0; i < RUN; i++) {
+            wl[j][i] = __builtin_amdgcn_readfirstlane((uint32_t)p);
+            wh[j][i] = __builtin_amdgcn_readfirstlane((uint32_t)(p >> 32));
+            p = gl_mul(p, a);
+        }
+    }
+    __device__ __forceinline__ gl_t value(int j) const { return gl_canon(acc[j]); }
+    __device__ __forceinline__ void constraint(uint64_t c) {
+#pragma unroll
+        for (int j = 0; j < NA; j++) acc[j] = gl_mul_add_loose(acc[j], alpha[j], c);
+    }
+    template <int B>
+    __device__ __forceinline__ void constraints(const uint64_t (&c)[B]) {
+        static_assert(B >= 2 && B <= RUN, "consumer_t: a run has 2 .. RUN constraints");
+        gl_wide_sum w[NA];
+#pragma unroll
+        for (int j = 0; j < NA; j++) w[j].start(c[B - 1], acc[j], wl[j][B - 1], wh[j][B - 1]);
+#pragma unroll
+        for (int i = 0; i < B - 1; i++)
+#pragma unroll
+            for (int j = 0; j < NA; j++) w[j].add(c[i], wl[j][B - 2 - i], wh[j][B - 2 - i]);
+#pragma unroll
+        for (int j = 0; j < NA; j++) acc[j] = w[j].value();
+    }
+    __device__ __forceinline__ void transition(uint64_t c) { constraint(gl_mul_loose(c, z_last)); }
+    __device__ __forceinline__ void last_row(uint64_t c) { constraint(gl_mul_loose(c, l_last)); }
+    __device__ __forceinline__ void first_row(uint64_t c) { constraint(gl_mul_loose(c, l_first)); }
+};
+
+// the two checks of an s-box x -> x^7 with witness cells inter = x^3, out = x^7 (canonical), on a loose x: loose differences
+__device__ __forceinline__ void sbox_terms(uint64_t* c, uint64_t x, gl_t inter, gl_t out) {
+    c[0] = gl_sub_lc(gl_mul_loose(gl_mul_loose(x, x), x), inter);
+    c[1] = gl_sub_lc(gl_mul_loose(gl_mul_loose(x, inter), inter), out);
 }
 
-// lv(c) = trace LDE value of column c at this thread's row
+// PoseidonStark (poseidon_stark.rs:554-594).  lv(c) = trace LDE value of column c at this thread's row.  The state is loose and
+// already carries its round's constants (the layer before added them); the witness cells replace the s-box outputs.  The partial
+// rounds run in the sponge's fused textbook form (poseidon_dev.h, poseidon_partial_group_t) with delta_k = out_k - a_k[0] from
+// the witness: moving the linear maps past the lane-0 substitution never uses out = in^7, so this is the same polynomial in the
+// trace cells as the reference's sparse form on every row, valid or not.
+template <int NA>
+__device__ __forceinline__ void poseidon_full_round_checks(const gl_t* __restrict__ lv, size_t cs, int col0, uint64_t s[12], consumer_t<NA>& k) {
+#pragma unroll
+    for (int q = 0; q < 3; q++) {
+        uint64_t c[8];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int i = 4 * q + e;
+            const gl_t tmp = lv[(size_t)(col0 + 2 * i) * cs], out = lv[(size_t)(col0 + 2 * i + 1) * cs];
+            sbox_terms(&c[2 * e], s[i], tmp, out);
+            s[i] = out;
+        }
+        k.constraints(c);
+    }
+}
 template <int NA>
 __device__ void eval_poseidon_constraints(const gl_t* __restrict__ lv, size_t cs, consumer_t<NA>& k) {
-    gl_t s[12];
+    uint64_t s[12];
 #pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = lv[(size_t)(1 + i) * cs];
-    int rc = 0;
+    for (int i = 0; i < 12; i++) s[i] = gl_add_lc(lv[(size_t)(1 + i) * cs], PC::ZKM_POSEIDON_RC[i]);
 #pragma unroll 1
-    for (int r = 0; r < 4; r++, rc++) {
-#pragma unroll
-        for (int i = 0; i < 12; i++) {
-            gl_t x = gl_add(s[i], gl_canon(PC::ZKM_POSEIDON_RC[rc * 12 + i]));
-            gl_t tmp = lv[(size_t)(26 + 24 * r + 2 * i) * cs], out = lv[(size_t)(26 + 24 * r + 2 * i + 1) * cs];
-            sbox_constraints(k, x, tmp, out);
-            s[i] = out;
-        }
-        mds_canon(s);
+    for (int r = 0; r < 4; r++) {
+        poseidon_full_round_checks(lv, cs, 26 + 24 * r, s, k);
+        if (r < 3) poseidon_mds_add<true>(s, &PC::ZKM_POSEIDON_RC[(r + 1) * 12]);
     }
-#pragma unroll
-    for (int i = 0; i < 12; i++) s[i] = gl_add(s[i], PC::ZKM_POSEIDON_FAST_FIRST_RC[i]);
+    // partial round p (columns 122 + 2 p, 123 + 2 p) is round 4 + p; group g checks p = 3 g, 3 g + 1 inside and 3 g + 2 on its result
+    auto partial_check = [&](uint64_t* c, int p, uint64_t a) {
+        const gl_t inter = lv[(size_t)(122 + 2 * p) * cs], out = lv[(size_t)(123 + 2 * p) * cs];
+        sbox_terms(c, a, inter, out);
+        return out;
+    };
+#pragma unroll 1
+    for (int g = 0; g < 7; g++) {
+        uint64_t c[6];
+        poseidon_partial_group_t<3>(s, PC::ZKM_POSEIDON_FUSED_C1[g], PC::ZKM_POSEIDON_FUSED_C2[g], PC::ZKM_POSEIDON_FUSED_C3[g],
+                                    [&](int kk, uint64_t a) { return gl_sub(partial_check(&c[2 * kk], 3 * g + kk, a), gl_canon(a)); });
+        s[0] = partial_check(&c[4], 3 * g + 2, s[0]);
+        k.constraints(c);
+    }
     {
-        gl_t t[12];
-        t[0] = s[0];
-#pragma unroll
-        for (int c = 1; c < 12; c++) {
-            uint64_t acc = 0;
-#pragma unroll
-            for (int r = 1; r < 12; r++) acc = gl_add_loose(acc, gl_mul_loose(s[r], PC::ZKM_POSEIDON_FAST_INIT[r - 1][c - 1]));
-            t[c] = gl_canon(acc);
-        }
-#pragma unroll
-        for (int i = 0; i < 12; i++) s[i] = t[i];
+        uint64_t c[2];
+        poseidon_partial_group_t<2>(s, PC::ZKM_POSEIDON_FUSED_C1[7], 0, PC::ZKM_POSEIDON_FUSED_C3[7],
+                                    [&](int, uint64_t a) { return gl_sub(partial_check(c, 21, a), gl_canon(a)); });
+        k.constraints(c);
     }
 #pragma unroll 1
-    for (int r = 0; r < 22; r++) {
-        gl_t inter = lv[(size_t)(122 + 2 * r) * cs], out = lv[(size_t)(122 + 2 * r + 1) * cs];
-        sbox_constraints(k, s[0], inter, out);
-        gl_t s0 = r < 21 ? gl_add(out, PC::ZKM_POSEIDON_FAST_RC[r]) : out;
-        uint64_t d = gl_mul_loose(s0, 25);
-#pragma unroll
-        for (int i = 1; i < 12; i++) d = gl_add_loose(d, gl_mul_loose(s[i], PC::ZKM_POSEIDON_FAST_W_HATS[r][i - 1]));
-#pragma unroll
-        for (int i = 1; i < 12; i++) s[i] = gl_add(s[i], gl_mul(s0, PC::ZKM_POSEIDON_FAST_VS[r][i - 1]));
-        s[0] = gl_canon(d);
+    for (int r = 0; r < 4; r++) {
+        poseidon_full_round_checks(lv, cs, 166 + 24 * r, s, k);
+        poseidon_mds_add<true>(s, r < 3 ? &PC::ZKM_POSEIDON_RC[(27 + r) * 12] : PC::ZKM_POSEIDON_ZERO12);
     }
-    rc += 22;
-#pragma unroll 1
-    for (int r = 0; r < 4; r++, rc++) {
+    uint64_t c[8];
 #pragma unroll
-        for (int i = 0; i < 12; i++) {
-            gl_t x = gl_add(s[i], gl_canon(PC::ZKM_POSEIDON_RC[rc * 12 + i]));
-            gl_t tmp = lv[(size_t)(166 + 24 * r + 2 * i) * cs], out = lv[(size_t)(166 + 24 * r + 2 * i + 1) * cs];
-            sbox_constraints(k, x, tmp, out);
-            s[i] = out;
-        }
-        mds_canon(s);
-    }
+    for (int i = 0; i < 8; i++) c[i] = gl_sub_lc(s[i], lv[(size_t)(13 + i) * cs]);
+    k.constraints(c);
+    uint64_t d[4];
 #pragma unroll
-    for (int i = 0; i < 12; i++) k.constraint(gl_sub(s[i], lv[(size_t)(13 + i) * cs]));
+    for (int i = 0; i < 4; i++) d[i] = gl_sub_lc(s[8 + i], lv[(size_t)(21 + i) * cs]);
+    k.constraints(d);
 }
 
 // LogicStark (logic.rs:199-248; columns :25-50).  64 booleanity constraints then the result constraint.
@@ -109,13 +181,13 @@ __device__ void eval_logic_constraints(const gl_t* __restrict__ lv, size_t cs, c
 #pragma unroll 4
     for (int i = 0; i < 32; i++) {
         gl_t b = lv[(size_t)(4 + i) * cs];
-        k.constraint(gl_mul(b, gl_sub(b, 1)));
+        k.constraint(gl_mul_loose(b, gl_sub(b, 1)));
         x = gl_add(x, gl_mul(b, (gl_t)1 << i));
     }
 #pragma unroll 4
     for (int i = 0; i < 32; i++) {
         gl_t b = lv[(size_t)(36 + i) * cs];
-        k.constraint(gl_mul(b, gl_sub(b, 1)));
+        k.constraint(gl_mul_loose(b, gl_sub(b, 1)));
         y = gl_add(y, gl_mul(b, (gl_t)1 << i));
         x_land_y = gl_add(x_land_y, gl_mul(gl_mul(lv[(size_t)(4 + i) * cs], b), (gl_t)1 << i));
     }
@@ -130,48 +202,48 @@ __device__ void eval_keccak_sponge_constraints(const gl_t* __restrict__ lv, size
     enum { FULL = 0, CONTEXT = 1, SEGMENT = 2, TIMESTAMP = 37, LEN = 38, ABSORBED = 39, FINAL_LEN = 40, ORIG_RATE = 176,
            ORIG_CAP = 210, PARTIAL = 396, DIGEST = 438 };
     gl_t full = lv[FULL];
-    k.constraint(gl_mul(full, gl_sub(full, 1)));
+    k.constraint(gl_mul_loose(full, gl_sub(full, 1)));
     gl_t is_final = 0, next_final = 0;
 #pragma unroll 4
     for (int i = 0; i < 136; i++) {
         is_final = gl_add(is_final, lv[(size_t)(FINAL_LEN + i) * cs]);
         next_final = gl_add(next_final, nv[(size_t)(FINAL_LEN + i) * cs]);
     }
-    k.constraint(gl_mul(is_final, gl_sub(is_final, 1)));
+    k.constraint(gl_mul_loose(is_final, gl_sub(is_final, 1)));
 #pragma unroll 4
     for (int i = 0; i < 136; i++) {
         gl_t f = lv[(size_t)(FINAL_LEN + i) * cs];
-        k.constraint(gl_mul(f, gl_sub(f, 1)));
+        k.constraint(gl_mul_loose(f, gl_sub(f, 1)));
     }
-    k.constraint(gl_mul(is_final, full));
+    k.constraint(gl_mul_loose(is_final, full));
     gl_t absorbed = lv[(size_t)ABSORBED * cs];
     k.first_row(absorbed);
 #pragma unroll 2
     for (int i = 0; i < 50; i++) k.first_row(lv[(size_t)(ORIG_RATE + i) * cs]);  // original_rate then original_capacity
     // both scaled by (x - last) inside transition(): fold is_final / full into it once
     gl_t fin_t = gl_mul(is_final, k.z_last), full_t = gl_mul(full, k.z_last);
-    k.constraint(gl_mul(fin_t, nv[(size_t)ABSORBED * cs]));
+    k.constraint(gl_mul_loose(fin_t, nv[(size_t)ABSORBED * cs]));
 #pragma unroll 2
-    for (int i = 0; i < 50; i++) k.constraint(gl_mul(fin_t, nv[(size_t)(ORIG_RATE + i) * cs]));
-    k.constraint(gl_mul(full_t, gl_sub(lv[(size_t)CONTEXT * cs], nv[(size_t)CONTEXT * cs])));
-    k.constraint(gl_mul(full_t, gl_sub(lv[(size_t)SEGMENT * cs], nv[(size_t)SEGMENT * cs])));
-    k.constraint(gl_mul(full_t, gl_sub(lv[(size_t)TIMESTAMP * cs], nv[(size_t)TIMESTAMP * cs])));
+    for (int i = 0; i < 50; i++) k.constraint(gl_mul_loose(fin_t, nv[(size_t)(ORIG_RATE + i) * cs]));
+    k.constraint(gl_mul_loose(full_t, gl_sub(lv[(size_t)CONTEXT * cs], nv[(size_t)CONTEXT * cs])));
+    k.constraint(gl_mul_loose(full_t, gl_sub(lv[(size_t)SEGMENT * cs], nv[(size_t)SEGMENT * cs])));
+    k.constraint(gl_mul_loose(full_t, gl_sub(lv[(size_t)TIMESTAMP * cs], nv[(size_t)TIMESTAMP * cs])));
 #pragma unroll 2
     for (int l = 0; l < 8; l++) {
         gl_t cur = lv[(size_t)(DIGEST + 4 * l) * cs];
 #pragma unroll
         for (int i = 1; i < 4; i++) cur = gl_add(cur, gl_mul(lv[(size_t)(DIGEST + 4 * l + i) * cs], (gl_t)1 << (8 * i)));
-        k.constraint(gl_mul(full_t, gl_sub(nv[(size_t)(ORIG_RATE + l) * cs], cur)));
+        k.constraint(gl_mul_loose(full_t, gl_sub(nv[(size_t)(ORIG_RATE + l) * cs], cur)));
     }
 #pragma unroll 2
     for (int i = 0; i < 42; i++)  // rate u32s 8..33 then the 16 capacity u32s are contiguous in both views
-        k.constraint(gl_mul(full_t, gl_sub(nv[(size_t)(ORIG_RATE + 8 + i) * cs], lv[(size_t)(PARTIAL + i) * cs])));
-    k.constraint(gl_mul(full_t, gl_sub(gl_add(absorbed, 136), nv[(size_t)ABSORBED * cs])));
+        k.constraint(gl_mul_loose(full_t, gl_sub(nv[(size_t)(ORIG_RATE + 8 + i) * cs], lv[(size_t)(PARTIAL + i) * cs])));
+    k.constraint(gl_mul_loose(full_t, gl_sub(gl_add(absorbed, 136), nv[(size_t)ABSORBED * cs])));
     gl_t is_dummy = gl_sub(gl_sub(1, full), is_final);
-    k.transition(gl_mul(is_dummy, gl_add(nv[FULL], next_final)));
+    k.transition(gl_mul_loose(is_dummy, gl_add(nv[FULL], next_final)));
     gl_t offset = gl_sub(lv[(size_t)LEN * cs], absorbed);
 #pragma unroll 4
-    for (int i = 0; i < 136; i++) k.constraint(gl_mul(lv[(size_t)(FINAL_LEN + i) * cs], gl_sub(offset, (gl_t)i)));
+    for (int i = 0; i < 136; i++) k.constraint(gl_mul_loose(lv[(size_t)(FINAL_LEN + i) * cs], gl_sub(offset, (gl_t)i)));
 }
 
 // KeccakStark (keccak/keccak_stark.rs:256-413: 3 + 320 + 50 + 320 + 50 + 4 + 50 = 797 constraints over 2431 columns;
@@ -197,9 +269,9 @@ __device__ void eval_keccak_constraints(const gl_t* __restrict__ lv, size_t cs, 
 #define LV(c) lv[(size_t)(c) * cs]
 #define NV(c) nv[(size_t)(c) * cs]
     gl_t final_step = LV(23);
-    k.constraint(gl_mul(final_step, gl_sub(final_step, 1)));
+    k.constraint(gl_mul_loose(final_step, gl_sub(final_step, 1)));
     gl_t not_final = gl_sub(1, final_step);
-    k.constraint(gl_mul(not_final, final_step));
+    k.constraint(gl_mul_loose(not_final, final_step));
     // round flags: their sum, and the round-constant bit sum_r step_r * RC_r[z] for the 7 bit positions RC uses
     gl_t sum_flags = 0, rc0 = 0, rc1 = 0, rc3 = 0, rc7 = 0, rc15 = 0, rc31 = 0, rc63 = 0;
     {
@@ -217,7 +289,7 @@ __device__ void eval_keccak_constraints(const gl_t* __restrict__ lv, size_t cs, 
             if (RC[r] >> 63 & 1) rc63 = gl_add(rc63, f);
         }
     }
-    k.constraint(gl_mul(gl_mul(sum_flags, not_final), gl_sub(NV(TIMESTAMP), LV(TIMESTAMP))));
+    k.constraint(gl_mul_loose(gl_mul(sum_flags, not_final), gl_sub(NV(TIMESTAMP), LV(TIMESTAMP))));
     // C'[x, z] = xor(C[x, z], C[x - 1, z], C[x + 1, z - 1])
 #pragma unroll 1
     for (int x = 0; x < 5; x++)
@@ -248,7 +320,7 @@ __device__ void eval_keccak_constraints(const gl_t* __restrict__ lv, size_t cs, 
 #pragma unroll
             for (int i = 1; i < 5; i++) sum = gl_add(sum, LV(reg_ap(x, i, z)));
             gl_t diff = gl_sub(sum, LV(reg_cp(x, z)));
-            k.constraint(gl_mul(gl_mul(diff, gl_sub(diff, 2)), gl_sub(diff, 4)));
+            k.constraint(gl_mul_loose(gl_mul(diff, gl_sub(diff, 2)), gl_sub(diff, 4)));
         }
     // A''[x, y] = xor(B[x, y], andn(B[x + 1, y], B[x + 2, y])), B[x, y, z] = A'[(x + 3y) % 5, x, z - r] (columns.rs:91-105)
 #pragma unroll 1
@@ -296,7 +368,7 @@ __device__ void eval_keccak_constraints(const gl_t* __restrict__ lv, size_t cs, 
         for (int y = 0; y < 5; y++)
 #pragma unroll
             for (int half = 0; half < 2; half++)
-                k.constraint(gl_mul(not_last_t, gl_sub(LV(reg_appp(x, y) + half), NV(reg_a(x, y) + half))));
+                k.constraint(gl_mul_loose(not_last_t, gl_sub(LV(reg_appp(x, y) + half), NV(reg_a(x, y) + half))));
 #undef LV
 #undef NV
 }
@@ -331,8 +403,8 @@ __device__ void eval_keccak_constraints_part(const gl_t* __restrict__ lv, size_t
     const gl_t not_final = gl_sub(1, final_step);
     gl_t rc0 = 0, rc1 = 0, rc3 = 0, rc7 = 0, rc15 = 0, rc31 = 0, rc63 = 0;
     if (part == 0) {
-        k.constraint(gl_mul(final_step, gl_sub(final_step, 1)));
-        k.constraint(gl_mul(not_final, final_step));
+        k.constraint(gl_mul_loose(final_step, gl_sub(final_step, 1)));
+        k.constraint(gl_mul_loose(not_final, final_step));
         gl_t sum_flags = 0;
         constexpr const uint64_t (&RC)[24] = KECCAK_RC_DEV;
 #pragma unroll
@@ -347,7 +419,7 @@ __device__ void eval_keccak_constraints_part(const gl_t* __restrict__ lv, size_t
             if (RC[r] >> 31 & 1) rc31 = gl_add(rc31, f);
             if (RC[r] >> 63 & 1) rc63 = gl_add(rc63, f);
         }
-        k.constraint(gl_mul(gl_mul(sum_flags, not_final), gl_sub(NV(TIMESTAMP), LV(TIMESTAMP))));
+        k.constraint(gl_mul_loose(gl_mul(sum_flags, not_final), gl_sub(NV(TIMESTAMP), LV(TIMESTAMP))));
         pos = 3;
     }
     // C'[x, z], z0 <= z < z1: constraints 3 + 64 x + z
@@ -377,7 +449,7 @@ __device__ void eval_keccak_constraints_part(const gl_t* __restrict__ lv, size_t
 #pragma unroll
         for (int i = 1; i < 5; i++) sum = gl_add(sum, LV(reg_ap(x, i, z)));
         gl_t diff = gl_sub(sum, LV(reg_cp(x, z)));
-        k.constraint(gl_mul(gl_mul(diff, gl_sub(diff, 2)), gl_sub(diff, 4)));
+        k.constraint(gl_mul_loose(gl_mul(diff, gl_sub(diff, 2)), gl_sub(diff, 4)));
     }
     pos += z1 - z0;
     // A''[x, y]: constraints 693 + 2 (5 x + y) + half
@@ -426,7 +498,7 @@ __device__ void eval_keccak_constraints_part(const gl_t* __restrict__ lv, size_t
     {
         const gl_t not_last_t = gl_mul(not_final, k.z_last);
 #pragma unroll
-        for (int half = 0; half < 2; half++) k.constraint(gl_mul(not_last_t, gl_sub(LV(reg_appp(x, y) + half), NV(reg_a(x, y) + half))));
+        for (int half = 0; half < 2; half++) k.constraint(gl_mul_loose(not_last_t, gl_sub(LV(reg_appp(x, y) + half), NV(reg_a(x, y) + half))));
     }
     pos += 2;
     jump(KECCAK_NUM_CONSTRAINTS);
@@ -440,42 +512,42 @@ __device__ void eval_poseidon_sponge_constraints(const gl_t* __restrict__ lv, si
     const gl_t* __restrict__ nv = lv + dnext;
     enum { FULL = 0, CONTEXT = 1, SEGMENT = 2, TIMESTAMP = 11, LEN = 12, ABSORBED = 13, FINAL_LEN = 14, ORIG = 46, PARTIAL = 98, DIGEST = 106 };
     gl_t full = lv[FULL];
-    k.constraint(gl_mul(full, gl_sub(full, 1)));
+    k.constraint(gl_mul_loose(full, gl_sub(full, 1)));
     gl_t is_final = 0, next_final = 0;
 #pragma unroll 4
     for (int i = 0; i < 32; i++) {
         is_final = gl_add(is_final, lv[(size_t)(FINAL_LEN + i) * cs]);
         next_final = gl_add(next_final, nv[(size_t)(FINAL_LEN + i) * cs]);
     }
-    k.constraint(gl_mul(is_final, gl_sub(is_final, 1)));
+    k.constraint(gl_mul_loose(is_final, gl_sub(is_final, 1)));
 #pragma unroll 4
     for (int i = 0; i < 32; i++) {
         gl_t f = lv[(size_t)(FINAL_LEN + i) * cs];
-        k.constraint(gl_mul(f, gl_sub(f, 1)));
+        k.constraint(gl_mul_loose(f, gl_sub(f, 1)));
     }
-    k.constraint(gl_mul(is_final, full));
+    k.constraint(gl_mul_loose(is_final, full));
     gl_t absorbed = lv[(size_t)ABSORBED * cs];
     k.first_row(absorbed);
 #pragma unroll 2
     for (int i = 0; i < 12; i++) k.first_row(lv[(size_t)(ORIG + i) * cs]);  // original_rate then original_capacity
     gl_t fin_t = gl_mul(is_final, k.z_last), full_t = gl_mul(full, k.z_last);
-    k.constraint(gl_mul(fin_t, nv[(size_t)ABSORBED * cs]));
+    k.constraint(gl_mul_loose(fin_t, nv[(size_t)ABSORBED * cs]));
 #pragma unroll 2
-    for (int i = 0; i < 12; i++) k.constraint(gl_mul(fin_t, nv[(size_t)(ORIG + i) * cs]));
-    k.constraint(gl_mul(full_t, gl_sub(lv[(size_t)CONTEXT * cs], nv[(size_t)CONTEXT * cs])));
-    k.constraint(gl_mul(full_t, gl_sub(lv[(size_t)SEGMENT * cs], nv[(size_t)SEGMENT * cs])));
-    k.constraint(gl_mul(full_t, gl_sub(lv[(size_t)TIMESTAMP * cs], nv[(size_t)TIMESTAMP * cs])));
+    for (int i = 0; i < 12; i++) k.constraint(gl_mul_loose(fin_t, nv[(size_t)(ORIG + i) * cs]));
+    k.constraint(gl_mul_loose(full_t, gl_sub(lv[(size_t)CONTEXT * cs], nv[(size_t)CONTEXT * cs])));
+    k.constraint(gl_mul_loose(full_t, gl_sub(lv[(size_t)SEGMENT * cs], nv[(size_t)SEGMENT * cs])));
+    k.constraint(gl_mul_loose(full_t, gl_sub(lv[(size_t)TIMESTAMP * cs], nv[(size_t)TIMESTAMP * cs])));
 #pragma unroll 2
-    for (int i = 0; i < 4; i++) k.constraint(gl_mul(full_t, gl_sub(nv[(size_t)(ORIG + i) * cs], lv[(size_t)(DIGEST + i) * cs])));
+    for (int i = 0; i < 4; i++) k.constraint(gl_mul_loose(full_t, gl_sub(nv[(size_t)(ORIG + i) * cs], lv[(size_t)(DIGEST + i) * cs])));
 #pragma unroll 2
     for (int i = 0; i < 8; i++)  // rate words 4..7 then the 4 capacity words are contiguous in both views
-        k.constraint(gl_mul(full_t, gl_sub(nv[(size_t)(ORIG + 4 + i) * cs], lv[(size_t)(PARTIAL + i) * cs])));
-    k.constraint(gl_mul(full_t, gl_sub(gl_add(absorbed, 32), nv[(size_t)ABSORBED * cs])));
+        k.constraint(gl_mul_loose(full_t, gl_sub(nv[(size_t)(ORIG + 4 + i) * cs], lv[(size_t)(PARTIAL + i) * cs])));
+    k.constraint(gl_mul_loose(full_t, gl_sub(gl_add(absorbed, 32), nv[(size_t)ABSORBED * cs])));
     gl_t is_dummy = gl_sub(gl_sub(1, full), is_final);
-    k.transition(gl_mul(is_dummy, gl_add(nv[FULL], next_final)));
+    k.transition(gl_mul_loose(is_dummy, gl_add(nv[FULL], next_final)));
     gl_t offset = gl_sub(lv[(size_t)LEN * cs], absorbed);
 #pragma unroll 4
-    for (int i = 0; i < 32; i++) k.constraint(gl_mul(lv[(size_t)(FINAL_LEN + i) * cs], gl_sub(offset, (gl_t)i)));
+    for (int i = 0; i < 32; i++) k.constraint(gl_mul_loose(lv[(size_t)(FINAL_LEN + i) * cs], gl_sub(offset, (gl_t)i)));
 }
 
 // ShaExtendStark (sha_extend/sha_extend_stark.rs:238-317; rotate_right.rs:29-62, shift_right.rs:29-60, wrapping_add_4.rs:35-78)
@@ -501,17 +573,17 @@ __device__ void eval_sha_extend_constraints(const gl_t* __restrict__ lv, size_t 
     gl_t real = lv[77 * cs];
     const gl_t *a = lv + 36 * cs, *b = lv + 20 * cs, *c = lv + 28 * cs, *d = lv + 16 * cs, *cy = lv + 4 * cs;
     gl_t c0 = cy[0], c1 = cy[cs], c2 = cy[2 * cs], c3 = cy[3 * cs];
-    k.constraint(gl_mul(gl_mul(c0, gl_sub(1, c0)), real));
-    k.constraint(gl_mul(gl_mul(c1, gl_sub(1, c1)), real));
-    k.constraint(gl_mul(gl_mul(c2, gl_sub(1, c2)), real));
-    k.constraint(gl_mul(gl_mul(c3, gl_sub(1, c3)), real));
-    k.constraint(gl_mul(gl_sub(gl_add(gl_add(c0, c1), gl_add(c2, c3)), 1), real));
+    k.constraint(gl_mul_loose(gl_mul(c0, gl_sub(1, c0)), real));
+    k.constraint(gl_mul_loose(gl_mul(c1, gl_sub(1, c1)), real));
+    k.constraint(gl_mul_loose(gl_mul(c2, gl_sub(1, c2)), real));
+    k.constraint(gl_mul_loose(gl_mul(c3, gl_sub(1, c3)), real));
+    k.constraint(gl_mul_loose(gl_sub(gl_add(gl_add(c0, c1), gl_add(c2, c3)), 1), real));
     gl_t carry = gl_add(gl_add(c1, gl_add(c2, c2)), gl_mul(c3, 3));
     gl_t sum = 0;
 #pragma unroll
     for (int i = 3; i >= 0; i--)
         sum = gl_add(gl_mul(sum, 1u << 8), gl_add(gl_add(a[(size_t)i * cs], b[(size_t)i * cs]), gl_add(c[(size_t)i * cs], d[(size_t)i * cs])));
-    k.constraint(gl_mul(gl_sub(gl_sub(sum, gl_mul(carry, (gl_t)1 << 32)), sha_le4(lv, cs)), real));
+    k.constraint(gl_mul_loose(gl_sub(gl_sub(sum, gl_mul(carry, (gl_t)1 << 32)), sha_le4(lv, cs)), real));
 }
 
 // ShaExtendSpongeStark (sha_extend_sponge/sha_extend_sponge_stark.rs:220-330); NUM_CHANNELS = 10 (cpu/membus.rs:10-32)
@@ -522,24 +594,24 @@ __device__ void eval_sha_extend_sponge_constraints(const gl_t* __restrict__ lv, 
 #pragma unroll 4
     for (int i = 0; i < 48; i++) {
         gl_t f = lv[(size_t)i * cs];
-        k.constraint(gl_mul(f, gl_sub(f, 1)));
+        k.constraint(gl_mul_loose(f, gl_sub(f, 1)));
         sum = gl_add(sum, f);
         lidx = gl_add(lidx, gl_mul(f, (gl_t)i));
         nidx = gl_add(nidx, gl_mul(nv[(size_t)i * cs], (gl_t)i));
     }
     gl_t is_final = lv[(size_t)47 * cs];
-    k.constraint(gl_mul(is_final, gl_sub(is_final, 1)));
+    k.constraint(gl_mul_loose(is_final, gl_sub(is_final, 1)));
     gl_t g = gl_mul(sum, gl_sub(1, is_final));
-    k.constraint(gl_mul(g, gl_sub(gl_sub(nv[(size_t)75 * cs], lv[(size_t)75 * cs]), 20)));
-    k.constraint(gl_mul(g, gl_sub(gl_sub(nidx, lidx), 1)));
+    k.constraint(gl_mul_loose(g, gl_sub(gl_sub(nv[(size_t)75 * cs], lv[(size_t)75 * cs]), 20)));
+    k.constraint(gl_mul_loose(g, gl_sub(gl_sub(nidx, lidx), 1)));
 #pragma unroll
     for (int i = 0; i < 5; i++)  // the four input addresses, then the output address
-        k.constraint(gl_mul(g, gl_sub(gl_sub(nv[(size_t)(68 + i) * cs], lv[(size_t)(68 + i) * cs]), 4)));
+        k.constraint(gl_mul_loose(g, gl_sub(gl_sub(nv[(size_t)(68 + i) * cs], lv[(size_t)(68 + i) * cs]), 4)));
     gl_t a16 = lv[(size_t)70 * cs];
-    k.constraint(gl_mul(sum, gl_sub(gl_sub(lv[(size_t)68 * cs], a16), 4)));
-    k.constraint(gl_mul(sum, gl_sub(gl_sub(lv[(size_t)69 * cs], a16), 56)));
-    k.constraint(gl_mul(sum, gl_sub(gl_sub(lv[(size_t)71 * cs], a16), 36)));
-    k.constraint(gl_mul(sum, gl_sub(gl_sub(lv[(size_t)72 * cs], a16), 64)));
+    k.constraint(gl_mul_loose(sum, gl_sub(gl_sub(lv[(size_t)68 * cs], a16), 4)));
+    k.constraint(gl_mul_loose(sum, gl_sub(gl_sub(lv[(size_t)69 * cs], a16), 56)));
+    k.constraint(gl_mul_loose(sum, gl_sub(gl_sub(lv[(size_t)71 * cs], a16), 36)));
+    k.constraint(gl_mul_loose(sum, gl_sub(gl_sub(lv[(size_t)72 * cs], a16), 64)));
 }
 
 // ShaCompressStark (sha_compress/sha_compress_stark.rs:402-606) and ShaCompressSpongeStark (sha_compress_sponge_stark.rs:233-268)
@@ -551,11 +623,11 @@ __device__ __forceinline__ void sha_wadd_constraints(const gl_t* __restrict__ lv
 #pragma unroll
     for (int i = 0; i < NC; i++) {
         gl_t c = lv[(size_t)(op + 4 + i) * cs];
-        k.constraint(gl_mul(gate, gl_mul(c, gl_sub(1, c))));
+        k.constraint(gl_mul_loose(gate, gl_mul(c, gl_sub(1, c))));
         csum = gl_add(csum, c);
         if (i) carry = gl_add(carry, gl_mul(c, (gl_t)i));
     }
-    k.constraint(gl_mul(gate, gl_sub(csum, 1)));
+    k.constraint(gl_mul_loose(gate, gl_sub(csum, 1)));
     gl_t sum = 0;
 #pragma unroll
     for (int b = 3; b >= 0; b--) {
@@ -564,14 +636,14 @@ __device__ __forceinline__ void sha_wadd_constraints(const gl_t* __restrict__ lv
         for (int q = 1; q < NIN; q++) s = gl_add(s, lv[(size_t)(in[q] + b) * cs]);
         sum = gl_add(gl_mul(sum, 1u << 8), s);
     }
-    k.constraint(gl_mul(gate, gl_sub(gl_sub(sum, gl_mul(carry, (gl_t)1 << 32)), sha_le4(lv + (size_t)op * cs, cs))));
+    k.constraint(gl_mul_loose(gate, gl_sub(gl_sub(sum, gl_mul(carry, (gl_t)1 << 32)), sha_le4(lv + (size_t)op * cs, cs))));
 }
 template <int NA>
 __device__ void eval_sha_compress_constraints(const gl_t* __restrict__ lv, size_t cs, ptrdiff_t dnext, consumer_t<NA>& k) {
     const gl_t* __restrict__ nv = lv + dnext;
     enum { ROUND = 159, TIMESTAMP = 146, W_VIRT = 149 };
     gl_t is_final = lv[(size_t)(ROUND + 64) * cs];
-    k.constraint(gl_mul(is_final, gl_sub(is_final, 1)));
+    k.constraint(gl_mul_loose(is_final, gl_sub(is_final, 1)));
     gl_t sum = is_final, kb[4] = {0, 0, 0, 0};
 #pragma unroll 4
     for (int j = 0; j < 64; j++) {
@@ -581,10 +653,10 @@ __device__ void eval_sha_compress_constraints(const gl_t* __restrict__ lv, size_
 #pragma unroll
         for (int i = 0; i < 4; i++) kb[i] = gl_add(kb[i], gl_mul(f, (kc >> (8 * i)) & 0xFF));
     }
-    k.constraint(gl_mul(sum, gl_sub(sum, 1)));
+    k.constraint(gl_mul_loose(sum, gl_sub(sum, 1)));
     gl_t g = gl_mul(sum, gl_sub(1, is_final));
 #pragma unroll
-    for (int i = 0; i < 4; i++) k.constraint(gl_mul(g, gl_sub(lv[(size_t)(40 + i) * cs], kb[i])));
+    for (int i = 0; i < 4; i++) k.constraint(gl_mul_loose(g, gl_sub(lv[(size_t)(40 + i) * cs], kb[i])));
     sha_rot_constraints<NA>(lv + 16 * cs, lv + 92 * cs, cs, 6, false, k);
     sha_rot_constraints<NA>(lv + 16 * cs, lv + 98 * cs, cs, 11, false, k);
     sha_rot_constraints<NA>(lv + 16 * cs, lv + 104 * cs, cs, 25, false, k);
@@ -592,32 +664,32 @@ __device__ void eval_sha_compress_constraints(const gl_t* __restrict__ lv, size_
     sha_rot_constraints<NA>(lv, lv + 116 * cs, cs, 13, false, k);
     sha_rot_constraints<NA>(lv, lv + 122 * cs, cs, 22, false, k);
 #pragma unroll
-    for (int i = 0; i < 4; i++) k.constraint(gl_mul(sum, gl_sub(gl_add(lv[(size_t)(16 + i) * cs], lv[(size_t)(32 + i) * cs]), 255)));
+    for (int i = 0; i < 4; i++) k.constraint(gl_mul_loose(sum, gl_sub(gl_add(lv[(size_t)(16 + i) * cs], lv[(size_t)(32 + i) * cs]), 255)));
     { const int in[5] = {28, 48, 60, 40, 36}; sha_wadd_constraints<NA, 5, 5>(lv, cs, in, 150, sum, k); }  // temp1 = h + s_1 + ch + k_i + w_i
     { const int in[2] = {68, 88}; sha_wadd_constraints<NA, 2, 2>(lv, cs, in, 128, sum, k); }              // temp2 = s_0 + maj
     { const int in[2] = {12, 150}; sha_wadd_constraints<NA, 2, 2>(lv, cs, in, 134, sum, k); }             // d + temp1
     { const int in[2] = {150, 128}; sha_wadd_constraints<NA, 2, 2>(lv, cs, in, 140, sum, k); }            // temp1 + temp2
-    k.constraint(gl_mul(g, gl_sub(nv[(size_t)TIMESTAMP * cs], lv[(size_t)TIMESTAMP * cs])));
-    k.constraint(gl_mul(g, gl_sub(gl_sub(nv[(size_t)W_VIRT * cs], lv[(size_t)W_VIRT * cs]), 4)));
+    k.constraint(gl_mul_loose(g, gl_sub(nv[(size_t)TIMESTAMP * cs], lv[(size_t)TIMESTAMP * cs])));
+    k.constraint(gl_mul_loose(g, gl_sub(gl_sub(nv[(size_t)W_VIRT * cs], lv[(size_t)W_VIRT * cs]), 4)));
 #pragma unroll
-    for (int i = 0; i < 4; i++) k.constraint(gl_mul(g, gl_sub(lv[(size_t)(140 + i) * cs], nv[(size_t)i * cs])));
+    for (int i = 0; i < 4; i++) k.constraint(gl_mul_loose(g, gl_sub(lv[(size_t)(140 + i) * cs], nv[(size_t)i * cs])));
 #pragma unroll 1
     for (int w = 0; w < 3; w++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) k.constraint(gl_mul(g, gl_sub(lv[(size_t)(4 * w + i) * cs], nv[(size_t)(4 * (w + 1) + i) * cs])));
+        for (int i = 0; i < 4; i++) k.constraint(gl_mul_loose(g, gl_sub(lv[(size_t)(4 * w + i) * cs], nv[(size_t)(4 * (w + 1) + i) * cs])));
 #pragma unroll
-    for (int i = 0; i < 4; i++) k.constraint(gl_mul(g, gl_sub(lv[(size_t)(134 + i) * cs], nv[(size_t)(16 + i) * cs])));
+    for (int i = 0; i < 4; i++) k.constraint(gl_mul_loose(g, gl_sub(lv[(size_t)(134 + i) * cs], nv[(size_t)(16 + i) * cs])));
 #pragma unroll 1
     for (int w = 4; w < 7; w++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) k.constraint(gl_mul(g, gl_sub(lv[(size_t)(4 * w + i) * cs], nv[(size_t)(4 * (w + 1) + i) * cs])));
+        for (int i = 0; i < 4; i++) k.constraint(gl_mul_loose(g, gl_sub(lv[(size_t)(4 * w + i) * cs], nv[(size_t)(4 * (w + 1) + i) * cs])));
 }
 template <int NA>
 __device__ void eval_sha_compress_sponge_constraints(const gl_t* __restrict__ lv, size_t cs, consumer_t<NA>& k) {
     gl_t real = lv[(size_t)126 * cs];
-    k.constraint(gl_mul(real, gl_sub(real, 1)));
+    k.constraint(gl_mul_loose(real, gl_sub(real, 1)));
 #pragma unroll
-    for (int i = 0; i < 7; i++) k.constraint(gl_mul(real, gl_sub(gl_sub(lv[(size_t)(113 + i) * cs], lv[(size_t)(112 + i) * cs]), 4)));
+    for (int i = 0; i < 7; i++) k.constraint(gl_mul_loose(real, gl_sub(gl_sub(lv[(size_t)(113 + i) * cs], lv[(size_t)(112 + i) * cs]), 4)));
 #pragma unroll 1
     for (int i = 0; i < 8; i++) {
         const int in[2] = {4 * i, 32 + 4 * i};
@@ -631,25 +703,25 @@ __device__ void eval_memory_constraints(const gl_t* __restrict__ lv, size_t cs, 
     const gl_t* __restrict__ nv = lv + dnext;
     enum { FILTER = 0, TIMESTAMP = 1, IS_READ = 2, CONTEXT = 3, SEGMENT = 4, VIRTUAL = 5, VALUE = 6, CFC = 7, SFC = 8, VFC = 9, RANGE_CHECK = 10 };
     gl_t filter = lv[FILTER];
-    k.constraint(gl_mul(filter, gl_sub(filter, 1)));
+    k.constraint(gl_mul_loose(filter, gl_sub(filter, 1)));
     gl_t cfc = lv[CFC * cs], sfc = lv[SFC * cs], vfc = lv[VFC * cs];
     gl_t unchanged = gl_sub(gl_sub(gl_sub(1, cfc), sfc), vfc);
-    k.constraint(gl_mul(cfc, gl_sub(1, cfc)));
-    k.constraint(gl_mul(sfc, gl_sub(1, sfc)));
-    k.constraint(gl_mul(vfc, gl_sub(1, vfc)));
-    k.constraint(gl_mul(unchanged, gl_sub(1, unchanged)));
+    k.constraint(gl_mul_loose(cfc, gl_sub(1, cfc)));
+    k.constraint(gl_mul_loose(sfc, gl_sub(1, sfc)));
+    k.constraint(gl_mul_loose(vfc, gl_sub(1, vfc)));
+    k.constraint(gl_mul_loose(unchanged, gl_sub(1, unchanged)));
     gl_t dctx = gl_sub(nv[CONTEXT * cs], lv[CONTEXT * cs]), dseg = gl_sub(nv[SEGMENT * cs], lv[SEGMENT * cs]);
     gl_t dvirt = gl_sub(nv[VIRTUAL * cs], lv[VIRTUAL * cs]);
-    k.transition(gl_mul(sfc, dctx));
-    k.transition(gl_mul(vfc, dctx));
-    k.transition(gl_mul(vfc, dseg));
-    k.transition(gl_mul(unchanged, dctx));
-    k.transition(gl_mul(unchanged, dseg));
-    k.transition(gl_mul(unchanged, dvirt));
+    k.transition(gl_mul_loose(sfc, dctx));
+    k.transition(gl_mul_loose(vfc, dctx));
+    k.transition(gl_mul_loose(vfc, dseg));
+    k.transition(gl_mul_loose(unchanged, dctx));
+    k.transition(gl_mul_loose(unchanged, dseg));
+    k.transition(gl_mul_loose(unchanged, dvirt));
     gl_t computed = gl_add(gl_add(gl_mul(cfc, gl_sub(dctx, 1)), gl_mul(sfc, gl_sub(dseg, 1))),
                            gl_add(gl_mul(vfc, gl_sub(dvirt, 1)), gl_mul(unchanged, gl_sub(nv[TIMESTAMP * cs], lv[TIMESTAMP * cs]))));
     k.transition(gl_sub(lv[RANGE_CHECK * cs], computed));
-    k.transition(gl_mul(gl_mul(nv[IS_READ * cs], unchanged), gl_sub(nv[VALUE * cs], lv[VALUE * cs])));
+    k.transition(gl_mul_loose(gl_mul(nv[IS_READ * cs], unchanged), gl_sub(nv[VALUE * cs], lv[VALUE * cs])));
 }
 
 // A table's own logUp lookups (eval_packed_lookups_generic lookup.rs:138-198; helper-column checks eval_helper_columns
@@ -728,12 +800,12 @@ __device__ void addcy(consumer_t<NA>& k, gl_t filter, const gl_t (&x)[2], const 
         cy = gl_mul(t, INV_65536);
     }
     if (two_row) {
-        k.transition(gl_mul(filter, gl_sub(cy, given_cy[0])));
-        k.transition(gl_mul(filter, given_cy[1]));
+        k.transition(gl_mul_loose(filter, gl_sub(cy, given_cy[0])));
+        k.transition(gl_mul_loose(filter, given_cy[1]));
     } else {
-        k.constraint(gl_mul(gl_mul(filter, given_cy[0]), gl_sub(given_cy[0], 1)));
-        k.constraint(gl_mul(filter, gl_sub(cy, given_cy[0])));
-        k.constraint(gl_mul(filter, given_cy[1]));
+        k.constraint(gl_mul_loose(gl_mul(filter, given_cy[0]), gl_sub(given_cy[0], 1)));
+        k.constraint(gl_mul_loose(filter, gl_sub(cy, given_cy[0])));
+        k.constraint(gl_mul_loose(filter, given_cy[1]));
     }
 }
 // eval_packed_generic_mul mul.rs:109-135
@@ -745,8 +817,8 @@ __device__ void mul(const frame& f, gl_t filter, int l, int r, consumer_t<NA>& k
     gl_t l0 = f.L(l), l1 = f.L(l + 1), r0 = f.L(r), r1 = f.L(r + 1);
     gl_t c0 = gl_add(gl_sub(gl_mul(l0, r0), f.L(OUT)), gl_mul(aux[0], 65536));
     gl_t c1 = gl_sub(gl_sub(gl_add(gl_mul(l0, r1), gl_mul(l1, r0)), f.L(OUT + 1)), gl_sub(aux[0], gl_mul(aux[1], 65536)));
-    k.constraint(gl_mul(filter, c0));
-    k.constraint(gl_mul(filter, c1));
+    k.constraint(gl_mul_loose(filter, c0));
+    k.constraint(gl_mul_loose(filter, c1));
 }
 // eval_packed_generic_mult_helper mult.rs:236-262
 template <int NA>
@@ -765,20 +837,20 @@ __device__ void mult_helper(const frame& f, gl_t filter, const gl_t (&l)[4], con
 #pragma unroll
     for (int d = 1; d < 4; d++) cp[d] = gl_sub(cp[d], gl_sub(aux[d - 1], gl_mul(aux[d], 65536)));
 #pragma unroll
-    for (int d = 0; d < 4; d++) k.constraint(gl_mul(filter, cp[d]));
+    for (int d = 0; d < 4; d++) k.constraint(gl_mul_loose(filter, cp[d]));
 }
 // eval_packed_div_helper div.rs:509-541 (modular_constr_poly :325-380, check_reduced :300-323)
 template <int NA>
 __device__ void div_helper(const frame& f, consumer_t<NA>& k, gl_t filter, int num, int den, int quo, int rem) {
     k.last_row(filter);
     gl_t miz = f.N(NV_MOD_IS_ZERO);
-    k.transition(gl_mul(filter, gl_sub(gl_mul(miz, miz), miz)));
+    k.transition(gl_mul_loose(filter, gl_sub(gl_mul(miz, miz), miz)));
     gl_t modulus[2] = {f.L(den), f.L(den + 1)}, output[2] = {f.L(rem), f.L(rem + 1)};
-    k.transition(gl_mul(gl_mul(filter, gl_add(modulus[0], modulus[1])), miz));
+    k.transition(gl_mul_loose(gl_mul(filter, gl_add(modulus[0], modulus[1])), miz));
     modulus[0] = gl_add(modulus[0], miz);
     gl_t ddz = f.N(NV_DENOM_IS_ZERO);
     gl_t shr_div = gl_add(gl_add(gl_add(f.L(DIV), f.L(DIVU)), gl_add(f.L(SRL), f.L(SRLV))), gl_add(f.L(SRA), f.L(SRAV)));
-    k.transition(gl_mul(filter, gl_sub(gl_mul(miz, shr_div), ddz)));
+    k.transition(gl_mul_loose(filter, gl_sub(gl_mul(miz, shr_div), ddz)));
     output[0] = gl_add(output[0], ddz);
     {
         const gl_t less[2] = {gl_sub(1, gl_mul(miz, shr_div)), 0}, red[2] = {f.N(NV_RED), f.N(NV_RED + 1)};
@@ -798,20 +870,20 @@ __device__ void div_helper(const frame& f, consumer_t<NA>& k, gl_t filter, int n
     cp[0] = gl_sub(cp[0], f.L(num));
     cp[1] = gl_sub(cp[1], f.L(num + 1));
 #pragma unroll
-    for (int d = 0; d < 4; d++) k.transition(gl_mul(filter, cp[d]));
+    for (int d = 0; d < 4; d++) k.transition(gl_mul_loose(filter, cp[d]));
 }
 // check_abs of eval_packed_div div.rs:400-430
 template <int NA>
 __device__ gl_t check_abs(const frame& f, consumer_t<NA>& k, gl_t filter, int input, int abs_col, int sum_col, int neg_col, int borrow_col) {
     gl_t is_neg = f.N(neg_col);
-    k.transition(gl_mul(gl_mul(filter, is_neg), gl_sub(1, is_neg)));
-    k.transition(gl_mul(filter, gl_sub(gl_sub(gl_add(f.L(input + 1), 32768), f.N(sum_col)), gl_mul(is_neg, 65536))));
+    k.transition(gl_mul_loose(gl_mul(filter, is_neg), gl_sub(1, is_neg)));
+    k.transition(gl_mul_loose(filter, gl_sub(gl_sub(gl_add(f.L(input + 1), 32768), f.N(sum_col)), gl_mul(is_neg, 65536))));
     gl_t b = f.N(borrow_col);
-    k.transition(gl_mul(gl_mul(filter, b), gl_sub(1, b)));
+    k.transition(gl_mul_loose(gl_mul(filter, b), gl_sub(1, b)));
     const gl_t neg_in[2] = {gl_sub(gl_mul(b, 65536), f.L(input)), gl_sub(gl_sub(65536, f.L(input + 1)), b)};
 #pragma unroll
     for (int i = 0; i < 2; i++)
-        k.transition(gl_mul(filter, gl_sub(gl_add(gl_mul(is_neg, neg_in[i]), gl_mul(gl_sub(1, is_neg), f.L(input + i))), f.L(abs_col + i))));
+        k.transition(gl_mul_loose(filter, gl_sub(gl_add(gl_mul(is_neg, neg_in[i]), gl_mul(gl_sub(1, is_neg), f.L(input + i))), f.L(abs_col + i))));
     return is_neg;
 }
 }  // namespace arith
@@ -830,8 +902,8 @@ __device__ void eval_arithmetic_constraints(const gl_t* __restrict__ lv, size_t 
 #pragma unroll
         for (int s = 0; s < 2; s++) {
             gl_t is_neg = f.L(AUX_EXTRA + s), in_hi = f.L((s ? IN1 : IN0) + 1), sum = f.L(IN2 + s);
-            k.constraint(gl_mul(gl_mul(ff, is_neg), gl_sub(1, is_neg)));
-            k.constraint(gl_mul(ff, gl_sub(gl_sub(gl_add(in_hi, 32768), sum), gl_mul(is_neg, 65536))));
+            k.constraint(gl_mul_loose(gl_mul(ff, is_neg), gl_sub(1, is_neg)));
+            k.constraint(gl_mul_loose(ff, gl_sub(gl_sub(gl_add(in_hi, 32768), sum), gl_mul(is_neg, 65536))));
             gl_t pad = gl_mul(is_neg, 65535);
             if (s) { r[0] = f.L(IN1); r[1] = in_hi; r[2] = r[3] = pad; }
             else { l[0] = f.L(IN0); l[1] = in_hi; l[2] = l[3] = pad; }
@@ -854,15 +926,15 @@ __device__ void eval_arithmetic_constraints(const gl_t* __restrict__ lv, size_t 
 #pragma unroll
         for (int i = 0; i < 2; i++) {
             gl_t t = gl_sub(gl_add(gl_add(cy, in1[i]), aux[i]), in0[i]);
-            k.constraint(gl_mul(gl_mul(fl, t), gl_sub(65536, t)));
+            k.constraint(gl_mul_loose(gl_mul(fl, t), gl_sub(65536, t)));
             cy = gl_mul(t, INV_65536);
         }
-        k.constraint(gl_mul(gl_mul(fl, gc[0]), gl_sub(gc[0], 1)));
-        k.constraint(gl_mul(gl_mul(fl, gl_sub(cy, gc[0])), gl_sub(1, sign)));
-        k.constraint(gl_mul(gl_mul(fl, gc[1]), gl_sub(gl_sub(1, cy), gc[0])));
-        k.transition(gl_mul(fl, gl_sub(out[0], gc[0])));
-        k.constraint(gl_mul(gl_mul(fl, gc[1]), gl_sub(1, sign)));
-        k.transition(gl_mul(fl, out[1]));
+        k.constraint(gl_mul_loose(gl_mul(fl, gc[0]), gl_sub(gc[0], 1)));
+        k.constraint(gl_mul_loose(gl_mul(fl, gl_sub(cy, gc[0])), gl_sub(1, sign)));
+        k.constraint(gl_mul_loose(gl_mul(fl, gc[1]), gl_sub(gl_sub(1, cy), gc[0])));
+        k.transition(gl_mul_loose(fl, gl_sub(out[0], gc[0])));
+        k.constraint(gl_mul_loose(gl_mul(fl, gc[1]), gl_sub(1, sign)));
+        k.transition(gl_mul_loose(fl, out[1]));
     }
     mul(f, f.L(LUI), IN0, IN1, k);
     div_helper(f, k, f.L(DIVU), IN0, IN1, OUT, AUX0);
@@ -873,39 +945,39 @@ __device__ void eval_arithmetic_constraints(const gl_t* __restrict__ lv, size_t 
         gl_t nq = check_abs(f, k, ff, OUT, QUOT_ABS, NV_DENOM_IS_ZERO + 3, RC_FREQ + 1, RC_FREQ + 2);
         gl_t nr = check_abs(f, k, ff, AUX0, REM_ABS, NV_DENOM_IS_ZERO + 4, RC_FREQ + 3, RC_FREQ + 4);
         gl_t same = f.N(RC_FREQ + 5);
-        k.transition(gl_mul(ff, gl_sub(gl_sub(gl_add(n0, n1), gl_mul(gl_mul(n0, n1), 2)), same)));
-        k.transition(gl_mul(gl_mul(ff, gl_sub(nq, same)), gl_add(f.L(OUT), f.L(OUT + 1))));
-        k.transition(gl_mul(gl_mul(ff, gl_sub(nr, n0)), gl_add(f.L(AUX0), f.L(AUX0 + 1))));
+        k.transition(gl_mul_loose(ff, gl_sub(gl_sub(gl_add(n0, n1), gl_mul(gl_mul(n0, n1), 2)), same)));
+        k.transition(gl_mul_loose(gl_mul(ff, gl_sub(nq, same)), gl_add(f.L(OUT), f.L(OUT + 1))));
+        k.transition(gl_mul_loose(gl_mul(ff, gl_sub(nr, n0)), gl_add(f.L(AUX0), f.L(AUX0 + 1))));
         div_helper(f, k, ff, IN2, AUX2, QUOT_ABS, REM_ABS);
     }
     mul(f, gl_add(f.L(SLL), f.L(SLLV)), IN1, IN2, k);
     div_helper(f, k, gl_add(f.L(SRL), f.L(SRLV)), IN1, IN2, OUT, AUX0);
     {   // sra.rs:66-133
         gl_t ff = gl_add(f.L(SRA), f.L(SRAV)), shift = f.L(IN0);
-        k.transition(gl_mul(ff, f.L(IN0 + 1)));
+        k.transition(gl_mul_loose(ff, f.L(IN0 + 1)));
         gl_t is_neg = f.L(AUX2 + 3);
-        k.transition(gl_mul(gl_mul(ff, is_neg), gl_sub(1, is_neg)));
-        k.transition(gl_mul(ff, gl_sub(gl_sub(gl_add(f.L(IN1 + 1), 32768), f.L(AUX2 + 2)), gl_mul(is_neg, 65536))));
+        k.transition(gl_mul_loose(gl_mul(ff, is_neg), gl_sub(1, is_neg)));
+        k.transition(gl_mul_loose(ff, gl_sub(gl_sub(gl_add(f.L(IN1 + 1), 32768), f.L(AUX2 + 2)), gl_mul(is_neg, 65536))));
         gl_t shift_sq = f.N(AUX2 + 2);
-        k.transition(gl_mul(ff, gl_sub(shift_sq, gl_mul(shift, shift))));
+        k.transition(gl_mul_loose(ff, gl_sub(shift_sq, gl_mul(shift, shift))));
         gl_t acc = 0;
 #pragma unroll 1
         for (int i = 0; i < 16; i++) {
             gl_t w = i < 8 ? f.L(AUX_EXTRA + i) : f.N(AUX_EXTRA + i - 8);
             gl_t v = gl_add(gl_add(gl_mul(acc, shift_sq), gl_mul(shift, ZKM_ARITH_SIGN_EXTEND_POLY[31 - 2 * i])), ZKM_ARITH_SIGN_EXTEND_POLY[30 - 2 * i]);
-            k.transition(gl_mul(ff, gl_sub(v, w)));
+            k.transition(gl_mul_loose(ff, gl_sub(v, w)));
             acc = w;
         }
         gl_t acc_lo = f.N(AUX2), acc_hi = f.N(AUX2 + 1);
-        k.transition(gl_mul(ff, gl_sub(gl_add(gl_mul(acc_hi, 65536), acc_lo), acc)));
+        k.transition(gl_mul_loose(ff, gl_sub(gl_add(gl_mul(acc_hi, 65536), acc_lo), acc)));
         div_helper(f, k, ff, IN1, IN2, AUX2, AUX0);
-        k.transition(gl_mul(ff, gl_sub(gl_add(f.L(AUX2), gl_mul(acc_lo, is_neg)), f.L(OUT))));
-        k.transition(gl_mul(ff, gl_sub(gl_add(f.L(AUX2 + 1), gl_mul(acc_hi, is_neg)), f.L(OUT + 1))));
+        k.transition(gl_mul_loose(ff, gl_sub(gl_add(f.L(AUX2), gl_mul(acc_lo, is_neg)), f.L(OUT))));
+        k.transition(gl_mul_loose(ff, gl_sub(gl_add(f.L(AUX2 + 1), gl_mul(acc_hi, is_neg)), f.L(OUT + 1))));
     }
     {   // lo_hi.rs:23-36
         gl_t ff = gl_add(gl_add(f.L(MFHI), f.L(MTHI)), gl_add(f.L(MFLO), f.L(MTLO)));
-        k.constraint(gl_mul(ff, gl_sub(f.L(IN0), f.L(OUT))));
-        k.constraint(gl_mul(ff, gl_sub(f.L(IN0 + 1), f.L(OUT + 1))));
+        k.constraint(gl_mul_loose(ff, gl_sub(f.L(IN0), f.L(OUT))));
+        k.constraint(gl_mul_loose(ff, gl_sub(f.L(IN0 + 1), f.L(OUT + 1))));
     }
 }
 
@@ -944,15 +1016,15 @@ __device__ __forceinline__ gl_t word(gl_t b0, gl_t b1, gl_t b2, gl_t b3) {
 // memio.rs enforce_half_word :65-77 / enforce_byte :106-129
 template <int NA>
 __device__ __forceinline__ void half_word(consumer_t<NA>& k, gl_t op, gl_t rs1, gl_t mem, gl_t v1, gl_t v0) {
-    k.constraint(gl_mul(op, gl_add(gl_mul(gl_sub(rs1, 1), gl_sub(mem, v0)), gl_mul(rs1, gl_sub(mem, v1)))));
+    k.constraint(gl_mul_loose(op, gl_add(gl_mul(gl_sub(rs1, 1), gl_sub(mem, v0)), gl_mul(rs1, gl_sub(mem, v1)))));
 }
 struct byte_sel_t { gl_t rs0, rs1, aux, w00, w10, w01; };
 template <int NA>
 __device__ __forceinline__ void byte_sel(consumer_t<NA>& k, const byte_sel_t& s, gl_t op, gl_t mem, gl_t v00, gl_t v10, gl_t v01, gl_t v11) {
-    k.constraint(gl_mul(op, gl_sub(gl_mul(s.rs0, s.rs1), s.aux)));
+    k.constraint(gl_mul_loose(op, gl_sub(gl_mul(s.rs0, s.rs1), s.aux)));
     gl_t sum = gl_add(gl_add(gl_mul(gl_sub(mem, v00), s.w00), gl_mul(gl_sub(mem, v10), s.w10)),
                       gl_add(gl_mul(gl_sub(mem, v01), s.w01), gl_mul(gl_sub(mem, v11), s.aux)));
-    k.constraint(gl_mul(sum, op));
+    k.constraint(gl_mul_loose(sum, op));
 }
 }  // namespace cpu
 
@@ -965,24 +1037,24 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
         gl_t boot = lv(IS_BOOT), d = gl_sub(nv(IS_BOOT), boot);
         k.first_row(gl_sub(boot, 1));
         k.last_row(boot);
-        k.transition(gl_mul(d, gl_add(d, 1)));
+        k.transition(gl_mul_loose(d, gl_add(d, 1)));
 #pragma unroll 1
         for (int i = 0; i < 9; i++) {
             gl_t f = gl_mul(boot, lv.ch(i, USED));
-            k.constraint(gl_mul(f, lv.ch(i, CTX)));
-            k.constraint(gl_mul(f, lv.ch(i, SEG)));  // Segment::Code = 0
+            k.constraint(gl_mul_loose(f, lv.ch(i, CTX)));
+            k.constraint(gl_mul_loose(f, lv.ch(i, SEG)));  // Segment::Code = 0
         }
 #pragma unroll 1
-        for (int i = 0; i < 9; i++) k.transition(gl_mul(d, lv.ch(i, USED)));
+        for (int i = 0; i < 9; i++) k.transition(gl_mul_loose(d, lv.ch(i, USED)));
     }
     // ---- decode
     {
         gl_t km = lv(KERNEL);
-        k.constraint(gl_mul(km, gl_sub(km, 1)));
+        k.constraint(gl_mul_loose(km, gl_sub(km, 1)));
 #pragma unroll 1
         for (int i = 0; i < 6; i++) {
             gl_t b = lv(OPC + i);
-            k.constraint(gl_mul(b, gl_sub(b, 1)));
+            k.constraint(gl_mul_loose(b, gl_sub(b, 1)));
         }
         const int flags[15] = {EQ_ISZERO, KECCAK_GENERAL, JUMPS, BRANCH, PC_OP, GET_CONTEXT, SET_CONTEXT, EXIT_KERNEL,
                                LOGIC, BINARY, BINARY_IMM, SHIFT, SHIFT_IMM, M_OP_LOAD, M_OP_STORE};
@@ -990,10 +1062,10 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
 #pragma unroll
         for (int i = 0; i < 15; i++) {
             gl_t f = lv(flags[i]);
-            k.constraint(gl_mul(f, gl_sub(f, 1)));
+            k.constraint(gl_mul_loose(f, gl_sub(f, 1)));
             sum = gl_add(sum, f);
         }
-        k.constraint(gl_mul(sum, gl_sub(sum, 1)));
+        k.constraint(gl_mul_loose(sum, gl_sub(sum, 1)));
     }
     // shared instruction fields
     const gl_t rs_f = lv.le(RS, 5), rt_f = lv.le(RT, 5), rd_f = lv.le(RD, 5), sa_f = lv.le(SHAMT, 5), fn_f = lv.le(FUNC, 6);
@@ -1006,18 +1078,18 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
     {
         gl_t is_jump = lv(JUMPS), is_jumpi = lv(JUMPI), is_jd = lv(JUMPDIRECT);
         gl_t is_link = gl_mul(is_jump, lv(FUNC)), is_linki = gl_mul(is_jumpi, lv(OPC));
-        k.constraint(gl_mul(is_jump, gl_sub(npc_next, lv.ch(0, VAL))));
-        k.constraint(gl_mul(is_jump, gl_sub(rs_f, lv.ch(0, VIRT))));
+        k.constraint(gl_mul_loose(is_jump, gl_sub(npc_next, lv.ch(0, VAL))));
+        k.constraint(gl_mul_loose(is_jump, gl_sub(rs_f, lv.ch(0, VIRT))));
         gl_t index26 = gl_add(gl_add(imm16, gl_mul(rt_f, 1ULL << 16)), gl_mul(rs_f, 1ULL << 21));
         gl_t aux = lv.ch(2, VAL);
-        k.constraint(gl_mul(is_jumpi, gl_sub(npc_next, gl_add(aux, gl_mul(index26, 4)))));
-        k.constraint(gl_mul(is_jd, gl_sub(aux, off4)));
+        k.constraint(gl_mul_loose(is_jumpi, gl_sub(npc_next, gl_add(aux, gl_mul(index26, 4)))));
+        k.constraint(gl_mul_loose(is_jd, gl_sub(aux, off4)));
         gl_t dst = gl_add(gl_add(pc, 4), aux);
-        k.constraint(gl_mul(gl_mul(is_jd, gl_sub(npc_next, dst)), gl_sub(gl_add(npc_next, P32), dst)));
-        k.constraint(gl_mul(gl_add(gl_add(is_link, is_linki), is_jd), gl_sub(gl_add(pc, 8), lv.ch(1, VAL))));
+        k.constraint(gl_mul_loose(gl_mul(is_jd, gl_sub(npc_next, dst)), gl_sub(gl_add(npc_next, P32), dst)));
+        k.constraint(gl_mul_loose(gl_add(gl_add(is_link, is_linki), is_jd), gl_sub(gl_add(pc, 8), lv.ch(1, VAL))));
         gl_t link_reg = lv.ch(1, VIRT);
-        k.constraint(gl_mul(is_link, gl_sub(link_reg, rd_f)));
-        k.constraint(gl_mul(gl_add(is_linki, is_jd), gl_sub(link_reg, 31)));
+        k.constraint(gl_mul_loose(is_link, gl_sub(link_reg, rd_f)));
+        k.constraint(gl_mul_loose(gl_add(is_linki, is_jd), gl_sub(link_reg, 31)));
     }
     // ---- branch
     {
@@ -1026,54 +1098,54 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
         gl_t norm = gl_add(gl_add(is_eq, is_ne), gl_add(is_le, is_gt)), special = gl_add(is_ge, is_lt);
         gl_t src1 = lv.ch(0, VAL), src2 = lv.ch(1, VAL), aux1 = lv.ch(2, VAL), aux2 = lv.ch(3, VAL), aux3 = lv.ch(4, VAL), aux4 = lv.ch(5, VAL);
         gl_t nf = gl_sub(1, f);
-        k.constraint(gl_mul(sj, gl_sub(1, sj)));
-        k.constraint(gl_mul(sj, nf));
-        k.constraint(gl_mul(f, gl_sub(1, gl_add(norm, special))));
-        k.constraint(gl_mul(f, gl_sub(1, gl_add(gl_add(flt, fgt), feq))));
-        k.constraint(gl_mul(f, gl_sub(aux4, off4)));
+        k.constraint(gl_mul_loose(sj, gl_sub(1, sj)));
+        k.constraint(gl_mul_loose(sj, nf));
+        k.constraint(gl_mul_loose(f, gl_sub(1, gl_add(norm, special))));
+        k.constraint(gl_mul_loose(f, gl_sub(1, gl_add(gl_add(flt, fgt), feq))));
+        k.constraint(gl_mul_loose(f, gl_sub(aux4, off4)));
         gl_t dst = gl_add(gl_add(pc, 4), aux4);
-        k.constraint(gl_mul(gl_mul(sj, gl_sub(npc_next, dst)), gl_sub(gl_add(npc_next, P32), dst)));
-        k.constraint(gl_mul(gl_mul(f, gl_sub(1, sj)), gl_sub(npc_next, gl_add(pc, 8))));
+        k.constraint(gl_mul_loose(gl_mul(sj, gl_sub(npc_next, dst)), gl_sub(gl_add(npc_next, P32), dst)));
+        k.constraint(gl_mul_loose(gl_mul(f, gl_sub(1, sj)), gl_sub(npc_next, gl_add(pc, 8))));
         gl_t ca = gl_sub(gl_add(aux1, src2), src1), cb = gl_sub(gl_add(aux2, src1), src2);
         gl_t fca = gl_mul(f, ca), fcb = gl_mul(f, cb);
-        k.constraint(gl_mul(fca, gl_sub(ca, P32)));
-        k.constraint(gl_mul(fcb, gl_sub(cb, P32)));
-        k.constraint(gl_mul(gl_mul(f, aux1), gl_sub(gl_add(aux1, aux2), P32)));
-        k.constraint(gl_mul(gl_mul(f, aux3), gl_sub(1, aux3)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rs_f)));
+        k.constraint(gl_mul_loose(fca, gl_sub(ca, P32)));
+        k.constraint(gl_mul_loose(fcb, gl_sub(cb, P32)));
+        k.constraint(gl_mul_loose(gl_mul(f, aux1), gl_sub(gl_add(aux1, aux2), P32)));
+        k.constraint(gl_mul_loose(gl_mul(f, aux3), gl_sub(1, aux3)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rs_f)));
         gl_t rt_reg = lv.ch(1, VIRT);
-        k.constraint(gl_mul(norm, gl_sub(rt_reg, rt_f)));
-        k.constraint(gl_mul(gl_mul(special, rt_reg), gl_sub(1, rt_reg)));
-        k.constraint(gl_mul(fca, gl_sub(P32, ca)));
+        k.constraint(gl_mul_loose(norm, gl_sub(rt_reg, rt_f)));
+        k.constraint(gl_mul_loose(gl_mul(special, rt_reg), gl_sub(1, rt_reg)));
+        k.constraint(gl_mul_loose(fca, gl_sub(P32, ca)));
         gl_t lt = gl_mul(ca, INV_2_32);
-        k.constraint(gl_mul(flt, gl_sub(1, lt)));
-        k.constraint(gl_mul(fcb, gl_sub(P32, cb)));
+        k.constraint(gl_mul_loose(flt, gl_sub(1, lt)));
+        k.constraint(gl_mul_loose(fcb, gl_sub(P32, cb)));
         gl_t gt = gl_mul(cb, INV_2_32);
-        k.constraint(gl_mul(fgt, gl_sub(1, gt)));
+        k.constraint(gl_mul_loose(fgt, gl_sub(1, gt)));
         gl_t ne = gl_add(lt, gt);
-        k.constraint(gl_mul(feq, ne));
+        k.constraint(gl_mul_loose(feq, ne));
         // x xor aux3 = x + aux3 - 2 x aux3
         gl_t lt2 = gl_sub(gl_add(flt, aux3), gl_mul(gl_add(flt, flt), aux3));
         gl_t gt2 = gl_sub(gl_add(fgt, aux3), gl_mul(gl_add(fgt, fgt), aux3));
-        k.constraint(gl_mul(is_eq, nf));
-        k.constraint(gl_mul(is_eq, gl_sub(sj, gl_sub(1, ne))));
-        k.constraint(gl_mul(is_ne, nf));
-        k.constraint(gl_mul(is_ne, gl_sub(sj, ne)));
-        k.constraint(gl_mul(is_le, nf));
-        k.constraint(gl_mul(is_le, gl_sub(sj, gl_sub(1, gt2))));
-        k.constraint(gl_mul(is_ge, nf));
-        k.constraint(gl_mul(is_ge, gl_sub(sj, gl_sub(1, lt2))));
-        k.constraint(gl_mul(is_gt, nf));
-        k.constraint(gl_mul(is_gt, gl_sub(sj, gt2)));
-        k.constraint(gl_mul(is_lt, nf));
-        k.constraint(gl_mul(is_lt, gl_sub(sj, lt2)));
+        k.constraint(gl_mul_loose(is_eq, nf));
+        k.constraint(gl_mul_loose(is_eq, gl_sub(sj, gl_sub(1, ne))));
+        k.constraint(gl_mul_loose(is_ne, nf));
+        k.constraint(gl_mul_loose(is_ne, gl_sub(sj, ne)));
+        k.constraint(gl_mul_loose(is_le, nf));
+        k.constraint(gl_mul_loose(is_le, gl_sub(sj, gl_sub(1, gt2))));
+        k.constraint(gl_mul_loose(is_ge, nf));
+        k.constraint(gl_mul_loose(is_ge, gl_sub(sj, gl_sub(1, lt2))));
+        k.constraint(gl_mul_loose(is_gt, nf));
+        k.constraint(gl_mul_loose(is_gt, gl_sub(sj, gt2)));
+        k.constraint(gl_mul_loose(is_lt, nf));
+        k.constraint(gl_mul_loose(is_lt, gl_sub(sj, lt2)));
     }
     // ---- membus
     k.constraint(gl_sub(lv(CODE_CONTEXT), gl_mul(gl_sub(1, lv(KERNEL)), lv(CONTEXT))));
 #pragma unroll 1
     for (int i = 0; i < 9; i++) {
         gl_t u = lv.ch(i, USED);
-        k.constraint(gl_mul(u, gl_sub(u, 1)));
+        k.constraint(gl_mul_loose(u, gl_sub(u, 1)));
     }
     // ---- memio: io view = rs_le (GEN..), rt_le (GEN + 32..), mem_le (GEN + 64..), aux_rs0_mul_rs1 (GEN + 96)
     {
@@ -1097,23 +1169,23 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
 #pragma unroll 1
         for (int store = 0; store < 2; store++) {
             gl_t f = gl_mul(lv(store ? M_OP_STORE : M_OP_LOAD), lv(OPC + 5));
-            k.constraint(gl_mul(f, gl_sub(1, aux_filter)));
-            k.constraint(gl_mul(f, gl_sub(lv.ch(0, SEG), 4)));  // Segment::RegisterFile
-            k.constraint(gl_mul(f, gl_sub(lv.ch(1, SEG), 4)));
+            k.constraint(gl_mul_loose(f, gl_sub(1, aux_filter)));
+            k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, SEG), 4)));  // Segment::RegisterFile
+            k.constraint(gl_mul_loose(f, gl_sub(lv.ch(1, SEG), 4)));
             k.constraint(addr_check);
-            k.constraint(gl_mul(f, gl_sub(rt_word, rt)));
-            k.constraint(gl_mul(f, gl_sub(virt, lv.ch(2, VIRT))));
+            k.constraint(gl_mul_loose(f, gl_sub(rt_word, rt)));
+            k.constraint(gl_mul_loose(f, gl_sub(virt, lv.ch(2, VIRT))));
             if (!store) {
                 const gl_t lo16 = gl_add(M[0], gl_mul(M[1], 256)), hi16 = gl_add(M[2], gl_mul(M[3], 256));
                 half_word(k, lv(MEMIO + 0), rs1, mem, gl_add(lo16, gl_mul(m15, 0xFFFF0000ULL)), gl_add(hi16, gl_mul(m31, 0xFFFF0000ULL)));
                 byte_sel(k, s, lv(MEMIO + 1), mem, mem_word, word(R[0], M[0], M[1], M[2]), word(R[0], R[1], M[0], M[1]),
                          word(R[0], R[1], R[2], M[0]));
-                k.constraint(gl_mul(lv(MEMIO + 2), gl_sub(mem, mem_word)));
+                k.constraint(gl_mul_loose(lv(MEMIO + 2), gl_sub(mem, mem_word)));
                 byte_sel(k, s, lv(MEMIO + 3), mem, M[3], M[2], M[1], M[0]);
                 half_word(k, lv(MEMIO + 4), rs1, mem, lo16, hi16);
                 byte_sel(k, s, lv(MEMIO + 5), mem, word(M[3], R[1], R[2], R[3]), word(M[2], M[3], R[2], R[3]), word(M[1], M[2], M[3], R[3]),
                          mem_word);
-                k.constraint(gl_mul(lv(MEMIO + 11), gl_sub(mem, mem_word)));
+                k.constraint(gl_mul_loose(lv(MEMIO + 11), gl_sub(mem, mem_word)));
                 byte_sel(k, s, lv(MEMIO + 14), mem, gl_add(M[3], gl_mul(m31, 0xFFFFFF00ULL)), gl_add(M[2], gl_mul(m23, 0xFFFFFF00ULL)),
                          gl_add(M[1], gl_mul(m15, 0xFFFFFF00ULL)), gl_add(M[0], gl_mul(m7, 0xFFFFFF00ULL)));
             } else {
@@ -1122,14 +1194,14 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
                 half_word(k, lv(MEMIO + 7), rs1, mem, word(R[0], R[1], M[2], M[3]), word(M[0], M[1], R[0], R[1]));
                 byte_sel(k, s, lv(MEMIO + 8), mem, rt_word, word(R[1], R[2], R[3], M[3]), word(R[2], R[3], M[2], M[3]),
                          word(R[3], M[1], M[2], M[3]));
-                k.constraint(gl_mul(lv(MEMIO + 9), gl_sub(mem, rt_word)));
+                k.constraint(gl_mul_loose(lv(MEMIO + 9), gl_sub(mem, rt_word)));
                 byte_sel(k, s, lv(MEMIO + 10), mem, word(M[0], M[1], M[2], R[0]), word(M[0], M[1], R[0], R[1]), word(M[0], R[0], R[1], R[2]),
                          rt_word);
-                k.constraint(gl_mul(lv(MEMIO + 12), gl_sub(mem, rt_word)));
-                k.constraint(gl_mul(lv(MEMIO + 13), mem));
+                k.constraint(gl_mul_loose(lv(MEMIO + 12), gl_sub(mem, rt_word)));
+                k.constraint(gl_mul_loose(lv(MEMIO + 13), mem));
             }
-            k.constraint(gl_mul(f, lv.ch(6, USED)));
-            k.constraint(gl_mul(f, lv.ch(7, USED)));
+            k.constraint(gl_mul_loose(f, lv.ch(6, USED)));
+            k.constraint(gl_mul_loose(f, lv.ch(7, USED)));
         }
     }
     // ---- shift: variable then immediate; the power of two comes from the shift table through channel 3
@@ -1139,45 +1211,45 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
 #pragma unroll 1
         for (int imm = 0; imm < 2; imm++) {
             gl_t f = lv(imm ? SHIFT_IMM : SHIFT), disp = imm ? sa_f : lv.ch(0, VAL);
-            k.constraint(gl_mul(gl_mul(f, used3), rd1));
-            k.constraint(gl_mul(f, ctx3));
-            k.constraint(gl_mul(f, seg3));
-            k.constraint(gl_mul(f, gl_sub(virt3, disp)));
+            k.constraint(gl_mul_loose(gl_mul(f, used3), rd1));
+            k.constraint(gl_mul_loose(f, ctx3));
+            k.constraint(gl_mul_loose(f, seg3));
+            k.constraint(gl_mul_loose(f, gl_sub(virt3, disp)));
         }
     }
     // ---- count (CLZ / CLO)
     {
         gl_t fz = lv(CLZ), fo = lv(CLO), f = gl_add(fo, fz);
-        k.constraint(gl_mul(f, gl_sub(lv.le(OPC, 6), 0x1c)));
-        k.constraint(gl_mul(fz, gl_sub(fn_f, 0x20)));
-        k.constraint(gl_mul(fo, gl_sub(fn_f, 0x21)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rs_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(1, VIRT), rd_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.le(OPC, 6), 0x1c)));
+        k.constraint(gl_mul_loose(fz, gl_sub(fn_f, 0x20)));
+        k.constraint(gl_mul_loose(fo, gl_sub(fn_f, 0x21)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rs_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(1, VIRT), rd_f)));
         gl_t sum = 0;
 #pragma unroll 1
         for (int i = 0; i < 32; i++) {
             gl_t b = lv(GEN + i);
-            k.constraint(gl_mul(gl_mul(f, b), gl_sub(1, b)));
+            k.constraint(gl_mul_loose(gl_mul(f, b), gl_sub(1, b)));
             sum = gl_add(sum, gl_mul(b, (gl_t)1 << i));
         }
         gl_t rs = lv.ch(0, VAL), rd = lv.ch(1, VAL);
-        k.constraint(gl_mul(fz, gl_sub(rs, sum)));
-        k.constraint(gl_mul(fo, gl_sub(gl_sub(0xffffffffULL, rs), sum)));
+        k.constraint(gl_mul_loose(fz, gl_sub(rs, sum)));
+        k.constraint(gl_mul_loose(fo, gl_sub(gl_sub(0xffffffffULL, rs), sum)));
         gl_t partial = lv(GEN + 31);  // bits[i..] as an integer, Horner from the top
-        k.constraint(gl_mul(gl_mul(f, partial), rd));
+        k.constraint(gl_mul_loose(gl_mul(f, partial), rd));
 #pragma unroll 1
         for (int i = 30; i >= 0; i--) {
             partial = gl_add(gl_add(partial, partial), lv(GEN + i));
             const int j = 30 - i;
             gl_t is_eq = lv(GEN + 32 + j), inv = lv(GEN + 64 + j), diff = gl_sub(partial, 1), feq = gl_mul(f, is_eq);
-            k.constraint(gl_mul(feq, diff));
-            k.constraint(gl_mul(f, gl_sub(gl_add(gl_mul(diff, inv), is_eq), 1)));
-            k.constraint(gl_mul(feq, gl_sub(rd, (gl_t)(31 - i))));
+            k.constraint(gl_mul_loose(feq, diff));
+            k.constraint(gl_mul_loose(f, gl_sub(gl_add(gl_mul(diff, inv), is_eq), 1)));
+            k.constraint(gl_mul_loose(feq, gl_sub(rd, (gl_t)(31 - i))));
         }
         gl_t is_eq = lv(GEN + 32 + 31), inv = lv(GEN + 64 + 31), feq = gl_mul(f, is_eq);
-        k.constraint(gl_mul(feq, partial));
-        k.constraint(gl_mul(f, gl_sub(gl_add(gl_mul(partial, inv), is_eq), 1)));
-        k.constraint(gl_mul(feq, gl_sub(rd, 32)));
+        k.constraint(gl_mul_loose(feq, partial));
+        k.constraint(gl_mul_loose(f, gl_sub(gl_add(gl_mul(partial, inv), is_eq), 1)));
+        k.constraint(gl_mul_loose(feq, gl_sub(rd, 32)));
     }
     // ---- syscall: general = cond[12] sysnum[12] a0[3] a1
     {
@@ -1188,8 +1260,8 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
         const gl_t a0 = lv.ch(1, VAL), a1 = lv.ch(2, VAL), a2 = lv.ch(3, VAL), rv0 = lv.ch(4, VAL), rv1 = lv.ch(5, VAL);
         const gl_t c6 = lv.ch(6, VAL), rheap = lv.ch(7, VAL);
         const gl_t bad0 = gl_sub(0xFFFFFFFFULL, rv0), bad1 = gl_sub(9, rv1), zero1 = gl_sub(0, rv1);
-        auto fc = [&](gl_t c, gl_t x) { k.constraint(gl_mul(gl_mul(f, c), x)); };
-        auto def = [&](gl_t c, gl_t a, gl_t b) { k.constraint(gl_mul(f, gl_sub(c, gl_mul(a, b)))); };
+        auto fc = [&](gl_t c, gl_t x) { k.constraint(gl_mul_loose(gl_mul(f, c), x)); };
+        auto def = [&](gl_t c, gl_t a, gl_t b) { k.constraint(gl_mul_loose(f, gl_sub(c, gl_mul(a, b)))); };
         const gl_t is_map = sysnum(1);
         def(cond(0), is_map, a0_is0);
         def(cond(1), cond(0), sz_nz);
@@ -1237,77 +1309,77 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
     // ---- bits (SEB / SEH / WSBH) on io().rt_le
     {
         gl_t seh = lv(SIGNEXT16), seb = lv(SIGNEXT8), wsbh = lv(SWAPHALF), f = gl_add(gl_add(seh, seb), wsbh);
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rt_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(1, VIRT), rd_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rt_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(1, VIRT), rd_f)));
         gl_t B[4] = {0, 0, 0, 0};
 #pragma unroll 1
         for (int i = 0; i < 32; i++) {
             gl_t b = lv(GEN + 32 + i);
-            k.constraint(gl_mul(gl_mul(f, b), gl_sub(1, b)));
+            k.constraint(gl_mul_loose(gl_mul(f, b), gl_sub(1, b)));
             B[i >> 3] = gl_add(B[i >> 3], gl_mul(b, (gl_t)1 << (i & 7)));
         }
         gl_t rd = lv.ch(1, VAL);
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VAL), word(B[0], B[1], B[2], B[3]))));
-        k.constraint(gl_mul(seb, gl_sub(rd, gl_add(B[0], gl_mul(lv(GEN + 32 + 7), 0xFFFFFF00ULL)))));
-        k.constraint(gl_mul(seh, gl_sub(rd, gl_add(gl_add(B[0], gl_mul(B[1], 256)), gl_mul(lv(GEN + 32 + 15), 0xFFFF0000ULL)))));
-        k.constraint(gl_mul(wsbh, gl_sub(rd, word(B[1], B[0], B[3], B[2]))));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VAL), word(B[0], B[1], B[2], B[3]))));
+        k.constraint(gl_mul_loose(seb, gl_sub(rd, gl_add(B[0], gl_mul(lv(GEN + 32 + 7), 0xFFFFFF00ULL)))));
+        k.constraint(gl_mul_loose(seh, gl_sub(rd, gl_add(gl_add(B[0], gl_mul(B[1], 256)), gl_mul(lv(GEN + 32 + 15), 0xFFFF0000ULL)))));
+        k.constraint(gl_mul_loose(wsbh, gl_sub(rd, word(B[1], B[0], B[3], B[2]))));
     }
     // ---- misc: rs_bits (GEN..), is_msb (GEN + 32..), is_lsb (GEN + 64..), auxm, auxl, auxs, rd_index, rd_index_eq_0, rd_index_eq_29
     const gl_t auxm = lv(GEN + 96), auxl = lv(GEN + 97), auxs = lv(GEN + 98);
     {  // rdhwr
         gl_t f = lv(RDHWR), rd_index = lv(GEN + 99), eq0 = lv(GEN + 100), eq29 = lv(GEN + 101), rt_val = lv.ch(0, VAL);
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rt_f)));
-        k.constraint(gl_mul(f, gl_sub(rd_index, rd_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rt_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(rd_index, rd_f)));
         gl_t f0 = gl_mul(f, eq0), f29 = gl_mul(f, eq29);
-        k.constraint(gl_mul(f0, rd_index));
-        k.constraint(gl_mul(f0, gl_sub(rt_val, 1)));
-        k.constraint(gl_mul(f29, gl_sub(rd_index, 29)));
-        k.constraint(gl_mul(f29, gl_sub(rt_val, lv.ch(1, VAL))));
-        k.constraint(gl_mul(gl_mul(f, gl_sub(gl_sub(1, eq29), eq0)), rt_val));
+        k.constraint(gl_mul_loose(f0, rd_index));
+        k.constraint(gl_mul_loose(f0, gl_sub(rt_val, 1)));
+        k.constraint(gl_mul_loose(f29, gl_sub(rd_index, 29)));
+        k.constraint(gl_mul_loose(f29, gl_sub(rt_val, lv.ch(1, VAL))));
+        k.constraint(gl_mul_loose(gl_mul(f, gl_sub(gl_sub(1, eq29), eq0)), rt_val));
     }
     {  // condmov
         gl_t rs = lv.ch(0, VAL), rt = lv.ch(1, VAL), rd = lv.ch(2, VAL), out = lv.ch(3, VAL), mov = lv.ch(4, VAL);
         gl_t movn = lv(MOVN), movz = lv(MOVZ), f = gl_add(movn, movz), is_ne = gl_mul(lv(GEN), rt), no_mov = gl_sub(1, mov);
-        k.constraint(gl_mul(movn, gl_sub(mov, is_ne)));
-        k.constraint(gl_mul(movz, gl_sub(mov, gl_sub(1, is_ne))));
-        k.constraint(gl_mul(gl_mul(f, mov), no_mov));
-        k.constraint(gl_mul(f, gl_sub(out, gl_add(gl_mul(mov, rs), gl_mul(no_mov, rd)))));
+        k.constraint(gl_mul_loose(movn, gl_sub(mov, is_ne)));
+        k.constraint(gl_mul_loose(movz, gl_sub(mov, gl_sub(1, is_ne))));
+        k.constraint(gl_mul_loose(gl_mul(f, mov), no_mov));
+        k.constraint(gl_mul_loose(f, gl_sub(out, gl_add(gl_mul(mov, rs), gl_mul(no_mov, rd)))));
     }
     {  // teq
         gl_t f = lv(TEQ);
-        k.constraint(gl_mul(f, gl_sub(lv.ch(1, VIRT), rt_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rs_f)));
-        k.constraint(gl_mul(f, gl_sub(1, gl_mul(gl_sub(lv.ch(0, VAL), lv.ch(1, VAL)), lv(GEN)))));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(1, VIRT), rt_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rs_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(1, gl_mul(gl_sub(lv.ch(0, VAL), lv.ch(1, VAL)), lv(GEN)))));
     }
     {  // ext
         gl_t f = lv(EXT);
-        k.constraint(gl_mul(f, gl_sub(lv.ch(1, VIRT), rt_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rs_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(1, VIRT), rt_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rs_f)));
         gl_t msb = gl_add(sa_f, rd_f);
-        k.constraint(gl_mul(f, gl_sub(gl_add(gl_mul(lv.ch(1, VAL), auxs), auxl), auxm)));
+        k.constraint(gl_mul_loose(f, gl_sub(gl_add(gl_mul(lv.ch(1, VAL), auxs), auxl), auxm)));
         gl_t prefix = 0;  // rs_bits[0..i)
 #pragma unroll 1
         for (int i = 0; i < 32; i++) {
             gl_t lpartial = prefix;
             prefix = gl_add(prefix, gl_mul(lv(GEN + i), (gl_t)1 << i));
             gl_t fm = gl_mul(f, lv(GEN + 32 + i)), fl = gl_mul(f, lv(GEN + 64 + i));
-            k.constraint(gl_mul(fm, gl_sub(msb, (gl_t)i)));
-            k.constraint(gl_mul(fm, gl_sub(auxm, prefix)));
-            k.constraint(gl_mul(fl, gl_sub(sa_f, (gl_t)i)));
-            k.constraint(gl_mul(fl, gl_sub(auxl, lpartial)));
-            k.constraint(gl_mul(fl, gl_sub(auxs, (gl_t)1 << i)));
+            k.constraint(gl_mul_loose(fm, gl_sub(msb, (gl_t)i)));
+            k.constraint(gl_mul_loose(fm, gl_sub(auxm, prefix)));
+            k.constraint(gl_mul_loose(fl, gl_sub(sa_f, (gl_t)i)));
+            k.constraint(gl_mul_loose(fl, gl_sub(auxl, lpartial)));
+            k.constraint(gl_mul_loose(fl, gl_sub(auxs, (gl_t)1 << i)));
         }
     }
     {  // ror: rotate right by i = (x >> i) + (x mod 2^i) << (32 - i)
         gl_t f = lv(ROR);
-        k.constraint(gl_mul(f, gl_sub(lv.ch(1, VIRT), rd_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rt_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(1, VIRT), rd_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rt_f)));
         gl_t rd_val = lv.ch(1, VAL), hi = lv.le(GEN, 32), lo = 0;
 #pragma unroll 1
         for (int i = 0; i < 32; i++) {
             gl_t fs = gl_mul(f, lv(GEN + 64 + i));
-            k.constraint(gl_mul(fs, gl_sub(sa_f, (gl_t)i)));
-            k.constraint(gl_mul(fs, gl_sub(rd_val, gl_add(hi, gl_mul(lo, (gl_t)1 << ((32 - i) & 63))))));
+            k.constraint(gl_mul_loose(fs, gl_sub(sa_f, (gl_t)i)));
+            k.constraint(gl_mul_loose(fs, gl_sub(rd_val, gl_add(hi, gl_mul(lo, (gl_t)1 << ((32 - i) & 63))))));
             gl_t b = lv(GEN + i);
             lo = gl_add(lo, gl_mul(b, (gl_t)1 << i));
             hi = gl_mul(gl_sub(hi, b), INV_2);
@@ -1315,33 +1387,33 @@ __device__ void eval_cpu_constraints(const gl_t* __restrict__ lvp, size_t cs, pt
     }
     {  // ins
         gl_t f = lv(INS);
-        k.constraint(gl_mul(f, gl_sub(lv.ch(1, VIRT), rt_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(2, VIRT), rt_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rs_f)));
-        k.constraint(gl_mul(f, gl_sub(gl_sub(lv.ch(2, VAL), auxm), gl_mul(auxl, auxs))));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(1, VIRT), rt_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(2, VIRT), rt_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rs_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(gl_sub(lv.ch(2, VAL), auxm), gl_mul(auxl, auxs))));
         gl_t size = gl_sub(rd_f, sa_f), prefix = 0;
 #pragma unroll 1
         for (int i = 0; i < 32; i++) {
             prefix = gl_add(prefix, gl_mul(lv(GEN + i), (gl_t)1 << i));
             gl_t fm = gl_mul(f, lv(GEN + 32 + i)), fl = gl_mul(f, lv(GEN + 64 + i));
-            k.constraint(gl_mul(fl, gl_sub(sa_f, (gl_t)i)));
-            k.constraint(gl_mul(fl, gl_sub(auxs, (gl_t)1 << i)));
-            k.constraint(gl_mul(fm, gl_sub(size, (gl_t)i)));
-            k.constraint(gl_mul(fm, gl_sub(auxl, prefix)));
+            k.constraint(gl_mul_loose(fl, gl_sub(sa_f, (gl_t)i)));
+            k.constraint(gl_mul_loose(fl, gl_sub(auxs, (gl_t)1 << i)));
+            k.constraint(gl_mul_loose(fm, gl_sub(size, (gl_t)i)));
+            k.constraint(gl_mul_loose(fm, gl_sub(auxl, prefix)));
         }
     }
     {  // maddu
         gl_t f = lv(MADDU);
-        k.constraint(gl_mul(f, gl_sub(lv.ch(0, VIRT), rs_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(1, VIRT), rt_f)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(2, VIRT), 33)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(4, VIRT), 33)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(3, VIRT), 32)));
-        k.constraint(gl_mul(f, gl_sub(lv.ch(5, VIRT), 32)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(0, VIRT), rs_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(1, VIRT), rt_f)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(2, VIRT), 33)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(4, VIRT), 33)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(3, VIRT), 32)));
+        k.constraint(gl_mul_loose(f, gl_sub(lv.ch(5, VIRT), 32)));
         gl_t result = gl_add(gl_mul(lv.ch(4, VAL), P32), lv.ch(5, VAL)), addend = gl_add(gl_mul(lv.ch(2, VAL), P32), lv.ch(3, VAL));
         gl_t mul = gl_mul(lv.ch(0, VAL), lv.ch(1, VAL));
-        k.constraint(gl_mul(gl_mul(f, auxm), gl_sub(auxm, P32)));
-        k.constraint(gl_mul(f, gl_sub(gl_sub(gl_add(mul, addend), gl_mul(auxm, P32)), result)));
+        k.constraint(gl_mul_loose(gl_mul(f, auxm), gl_sub(auxm, P32)));
+        k.constraint(gl_mul_loose(f, gl_sub(gl_sub(gl_add(mul, addend), gl_mul(auxm, P32)), result)));
     }
 }
 

@@ -260,6 +260,41 @@ GL_HD uint64_t gl_mul_loose(uint64_t a, uint64_t b) {
     return gl_reduce128(lo, hi);
 #endif
 }
+// loose * loose + loose -> loose: the addend rides in the product's own multiply-adds and the 128-bit sum is reduced once.
+//   p00 = al bl + c_lo <= (2^32-1)^2 + 2^32 - 1 < 2^64;   m1 = al bh + (p00 >> 32) + c_hi <= (2^32-1)^2 + 2^33 - 2 = 2^64 - 1;
+//   the rest is gl_mul_loose's chain (a b + c < 2^128, so the high word still fits).  Three instructions more than a product,
+//   where a canonical add behind a canonical product costs a dozen (two 64-bit compare / select chains).
+GL_HD uint64_t gl_mul_add_loose(uint64_t a, uint64_t b, uint64_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t al = (uint32_t)a, ah = (uint32_t)(a >> 32), bl = (uint32_t)b, bh = (uint32_t)(b >> 32);
+    const uint64_t p00 = (uint64_t)al * bl + (uint32_t)c;
+    const uint64_t m1 = (uint64_t)al * bh + ((p00 >> 32) + (c >> 32));
+#if defined(GL_REDUCE_BRANCHFREE)
+    uint64_t m2, cy;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=&v"(m2), "=&s"(cy) : "v"(ah), "v"(bl), "v"(m1));
+    const uint64_t hi = (uint64_t)ah * bh + (m2 >> 32);
+    uint32_t tl, th;
+    asm("v_subb_co_u32 %0, vcc, %2, %4, %5\n\tv_subbrev_co_u32 %1, vcc, 0, %3, vcc"
+        : "=&v"(tl), "=&v"(th)
+        : "v"((uint32_t)p00), "v"((uint32_t)m2), "v"((uint32_t)(hi >> 32)), "s"(cy)
+        : "vcc");
+    uint64_t t0 = ((uint64_t)th << 32) | tl;
+    t0 -= (uint32_t)((int32_t)(th & ~(uint32_t)m2) >> 31);
+    uint64_t r, carry;
+    uint32_t wrap;
+    asm("v_mad_u64_u32 %0, %1, %3, -1, %4\n\ts_nop 1\n\tv_cndmask_b32 %2, 0, -1, %1" : "=&v"(r), "=&s"(carry), "=v"(wrap) : "v"((uint32_t)hi), "v"(t0));
+    return r + wrap;
+#else
+    uint64_t m2, cy;
+    uint32_t cw;
+    asm("v_mad_u64_u32 %0, %1, %3, %4, %5\n\ts_nop 1\n\tv_cndmask_b32 %2, 0, 1, %1" : "=&v"(m2), "=&s"(cy), "=v"(cw) : "v"(ah), "v"(bl), "v"(m1));
+    return gl_reduce128((m2 << 32) | (uint32_t)p00, (uint64_t)ah * bh + ((m2 >> 32) | ((uint64_t)cw << 32)));
+#endif
+#else
+    unsigned __int128 p = (unsigned __int128)a * b + c;
+    return gl_reduce128((uint64_t)p, (uint64_t)(p >> 64));
+#endif
+}
 // loose * loose -> canonical
 GL_HD gl_t gl_mul(uint64_t a, uint64_t b) { return gl_canon(gl_mul_loose(a, b)); }
 GL_HD gl_t gl_sqr(uint64_t a) { return gl_mul(a, a); }

@@ -151,8 +151,10 @@ GL_HD constexpr uint32_t poseidon_m1(int i, int j) {
 }
 
 // T linear layers (T = 3 or 2) with the T - 1 lane-0 s-boxes between them; c3 = constants after the last layer.
-template <int T>
-GL_HD void poseidon_partial_group(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3) {
+// delta(k, a) = what lane 0 gains at s-box k = 0, 1 of the group on its input a: sbox(a) - a in the permutation; the constraint
+// evaluator (constraints_dev.h) takes the s-box output from a witness cell instead.
+template <int T, class DELTA>
+GL_HD void poseidon_partial_group_t(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3, DELTA&& delta) {
     uint32_t lo[12], hi[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) {
@@ -165,7 +167,7 @@ GL_HD void poseidon_partial_group(uint64_t s[12], uint64_t c1, uint64_t c2, cons
         al += (uint64_t)lo[j] * poseidon_m1(0, j);
         ah += (uint64_t)hi[j] * poseidon_m1(0, j);
     }
-    const uint64_t d1 = poseidon_sbox_delta(poseidon_fold(al, ah));
+    const uint64_t d1 = delta(0, poseidon_fold(al, ah));
     const uint32_t d1l = (uint32_t)d1, d1h = (uint32_t)(d1 >> 32);
     uint32_t d2l = 0, d2h = 0;
     POSEIDON_SCHED_FENCE();
@@ -177,7 +179,7 @@ GL_HD void poseidon_partial_group(uint64_t s[12], uint64_t c1, uint64_t c2, cons
             al += (uint64_t)lo[j] * PC::ZKM_POSEIDON_M2[0][j];
             ah += (uint64_t)hi[j] * PC::ZKM_POSEIDON_M2[0][j];
         }
-        const uint64_t d2 = poseidon_sbox_delta(poseidon_fold(al, ah));
+        const uint64_t d2 = delta(1, poseidon_fold(al, ah));
         d2l = (uint32_t)d2;
         d2h = (uint32_t)(d2 >> 32);
         POSEIDON_SCHED_FENCE();
@@ -204,6 +206,10 @@ GL_HD void poseidon_partial_group(uint64_t s[12], uint64_t c1, uint64_t c2, cons
         s[i] = poseidon_fold(al, ah);
         if ((i & 1) == 1) POSEIDON_SCHED_FENCE();
     }
+}
+template <int T>
+GL_HD void poseidon_partial_group(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3) {
+    poseidon_partial_group_t<T>(s, c1, c2, c3, [](int, uint64_t a) { return poseidon_sbox_delta(a); });
 }
 
 // One loop over the eight full rounds with the partial-round section hanging off round 3: every piece of round code exists

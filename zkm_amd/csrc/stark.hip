@@ -124,7 +124,7 @@ __device__ __forceinline__ quotient_point quotient_setup(size_t j, unsigned lde_
         const unsigned h = (lde_bits + 1) / 2;
         const gl_t x = gl_mul_loose(wpow[j & ((1u << h) - 1)], wpow[((size_t)1 << h) + (j >> h)]);
 #pragma unroll
-        for (int a = 0; a < NA; a++) { k.alpha[a] = alphas[a]; k.acc[a] = 0; }
+        for (int a = 0; a < NA; a++) { k.set_alpha(a, alphas[a]); k.acc[a] = 0; }
         k.z_last = gl_sub(x, last);
         k.l_first = j == 0 ? 1 : 0;
         k.l_last = j == N - 1 ? 1 : 0;
@@ -137,7 +137,7 @@ __device__ __forceinline__ quotient_point quotient_setup(size_t j, unsigned lde_
     unsigned h = (lde_bits + 1) / 2;
     gl_t x = gl_mul(GL_GENERATOR, gl_mul_loose(wpow[t & ((1u << h) - 1)], wpow[((size_t)1 << h) + (t >> h)]));
 #pragma unroll
-    for (int a = 0; a < NA; a++) { k.alpha[a] = alphas[a]; k.acc[a] = 0; }
+    for (int a = 0; a < NA; a++) { k.set_alpha(a, alphas[a]); k.acc[a] = 0; }
     k.z_last = gl_sub(x, last);
     // Z_H(x) = x^n - 1 = g^n (-1)^i - 1;  L_first = Z_H / (n (x - 1)),  L_last = Z_H / (n (w x - 1))
     gl_t zh = gl_sub((i & 1) ? gl_neg(gn) : gn, 1);
@@ -181,7 +181,7 @@ __global__ __launch_bounds__(256, (TABLE == ZKM_TABLE_CPU || TABLE == ZKM_TABLE_
     if constexpr (TABLE == ZKM_TABLE_MEMORY || TABLE == ZKM_TABLE_ARITHMETIC)
         eval_lookup_constraints<NA>(lookups, lookup_ch.v + 2 * blockIdx.z, trace + j, N, aux, j, q.jn, k);
 #pragma unroll
-    for (int a = 0; a < NA; a++) out[(size_t)a * size + q.i] = k.acc[a];
+    for (int a = 0; a < NA; a++) out[(size_t)a * size + q.i] = k.value(a);
 }
 
 // Short Keccak tables: KECCAK_CONSTRAINT_PARTS threads per point (constraints_dev.h, eval_keccak_constraints_part); blockIdx.y = part.
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void k_quotient_keccak_parts(const gl_t* __res
     const quotient_point q = quotient_setup<NA>(j, lde_bits, alphas, wpow, gn, last, w_n, n_inv, k);
     eval_keccak_constraints_part<NA>(trace + j, N, (ptrdiff_t)q.jn - (ptrdiff_t)j, k, (int)blockIdx.y, apw);
 #pragma unroll
-    for (int a = 0; a < NA; a++) tmp[((size_t)blockIdx.y * NA + a) * size + q.i] = k.acc[a];
+    for (int a = 0; a < NA; a++) tmp[((size_t)blockIdx.y * NA + a) * size + q.i] = k.value(a);
 }
 __global__ __launch_bounds__(256) void k_sum_parts(const gl_t* __restrict__ tmp, unsigned nparts, size_t words, gl_t* __restrict__ out) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(64) void k_verify_line(const gl_t* __restrict__ row
     const gl_t* const aux = tl + 2 * (size_t)W;
     consumer_t<2> k;
 #pragma unroll
-    for (int a = 0; a < 2; a++) { k.alpha[a] = alphas_v.v[2 * blockIdx.z + a]; k.acc[a] = 0; }
+    for (int a = 0; a < 2; a++) { k.set_alpha(a, alphas_v.v[2 * blockIdx.z + a]); k.acc[a] = 0; }
     k.z_last = setting == 1 ? 1 : 0;
     k.l_first = setting == 2 ? 1 : 0;
     k.l_last = setting == 3 ? 1 : 0;
@@ -466,8 +466,8 @@ __global__ __launch_bounds__(64) void k_verify_line(const gl_t* __restrict__ row
     ctl.zs += (size_t)blockIdx.z * ctl.nzs;
     eval_ctl_constraints<2>(ctl, tl, 2, 1, aux + 2 * (size_t)NL, 0, 1, k);
     gl_t* const o = acc + acc_off.v[blockIdx.z] + 2 * tid;
-    o[0] = k.acc[0];
-    o[1] = k.acc[1];
+    o[0] = k.value(0);
+    o[1] = k.value(1);
 }
 
 void zkm_verify_line_constraints(zkm_ctx* c, int table_id, size_t nalphas, const ctl_dev& own, size_t naux, const uint64_t* lookup_challenges,
@@ -1602,7 +1602,68 @@ void zkm_launch_mul_selftest_branchfree(zkm_ctx* c, const uint64_t* a, const uin
     ZKM_HIP_CHECK(hipGetLastError());
 }
 
+// parity / debug: this translation unit's consumer_t on chosen challenges and loose terms (zkm_consumer_selftest, include/zkm_hip.h)
+template <int NA, int B>
+__device__ __forceinline__ void consumer_take(consumer_t<NA>& k, const uint64_t* __restrict__ t, size_t n) {
+    if constexpr (B == 1) {
+        k.constraint(t[0]);
+    } else {
+        uint64_t c[B];
+#pragma unroll
+        for (int i = 0; i < B; i++) c[i] = t[(size_t)i * n];
+        k.constraints(c);
+    }
+}
+template <int NA>
+__device__ void consumer_take_n(consumer_t<NA>& k, const uint64_t* __restrict__ t, size_t n, uint32_t b) {
+    switch (b) {   // (wave-uniform)
+        case 1: consumer_take<NA, 1>(k, t, n); break;
+        case 2: consumer_take<NA, 2>(k, t, n); break;
+        case 3: consumer_take<NA, 3>(k, t, n); break;
+        case 4: consumer_take<NA, 4>(k, t, n); break;
+        case 5: consumer_take<NA, 5>(k, t, n); break;
+        case 6: consumer_take<NA, 6>(k, t, n); break;
+        case 7: consumer_take<NA, 7>(k, t, n); break;
+        default: consumer_take<NA, 8>(k, t, n); break;
+    }
+}
+template <int NA>
+__global__ __launch_bounds__(256) void k_consumer_selftest(alpha_args alphas, const uint64_t* __restrict__ terms, size_t K, size_t n, uint32_t run,
+                                                           uint64_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    consumer_t<NA> k;
+#pragma unroll
+    for (int a = 0; a < NA; a++) { k.set_alpha(a, alphas.v[a]); k.acc[a] = 0; }
+    k.z_last = k.l_first = k.l_last = 0;
+    size_t t = 0;
+    for (; K - t >= run; t += run) consumer_take_n<NA>(k, terms + t * n + i, n, run);
+    if (t < K) consumer_take_n<NA>(k, terms + t * n + i, n, (uint32_t)(K - t));
+#pragma unroll
+    for (int a = 0; a < NA; a++) out[(size_t)a * n + i] = k.value(a);
+}
+
 extern "C" {
+
+int zkm_consumer_selftest(zkm_ctx* c, const uint64_t* alphas, size_t nalphas, const uint64_t* terms, size_t K, size_t n, uint32_t run,
+                          uint64_t* out, char** err) {
+    return zkm_api("zkm_consumer_selftest", c, err, [&] {
+        if (!alphas || !terms || !out) throw std::runtime_error("zkm_consumer_selftest: null argument");
+        if (nalphas < 1 || nalphas > 2) throw std::runtime_error("zkm_consumer_selftest: 1 or 2 challenges");
+        if (run < 1 || run > (uint32_t)consumer_t<2>::RUN) throw std::runtime_error("zkm_consumer_selftest: run must be 1 .. 8");
+        if (K == 0 || n == 0 || n > ((size_t)1 << 20) || K > ((size_t)1 << 26) / n) throw std::runtime_error("zkm_consumer_selftest: K, n out of range");
+        alpha_args a{};
+        for (size_t j = 0; j < nalphas; j++) a.v[j] = alphas[j];
+        zkm_scratch dt(c, K * n * 8), dout(c, nalphas * n * 8);
+        ZKM_HIP_CHECK(hipMemcpyAsync(dt.p, terms, K * n * 8, hipMemcpyHostToDevice, c->stream));
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        if (nalphas == 1) hipLaunchKernelGGL((k_consumer_selftest<1>), grid, block, 0, c->stream, a, dt.as<uint64_t>(), K, n, run, dout.as<uint64_t>());
+        else hipLaunchKernelGGL((k_consumer_selftest<2>), grid, block, 0, c->stream, a, dt.as<uint64_t>(), K, n, run, dout.as<uint64_t>());
+        ZKM_HIP_CHECK(hipGetLastError());
+        ZKM_HIP_CHECK(hipMemcpyAsync(out, dout.p, nalphas * n * 8, hipMemcpyDeviceToHost, c->stream));
+        c->sync();
+    });
+}
 
 size_t zkm_fri_proof_words(const zkm_stark_config* cfg, unsigned log_n, const size_t* oracle_cols, size_t noracles) {
     zkm_fri_part y{};   // (0 = unsupported configuration)
