@@ -110,6 +110,12 @@ void zkm_ctx_trim(zkm_ctx* ctx);
  *                               a chain of 129 permutations took 1.43 ms in the row form and 2.11 ms in the quad form on an MI355X, at
  *                               16, 64 and 256 pages alike (profiles/boot_time.json).  A measurement aid: tools/boot_time.py sets it to
  *                               time both, nothing else should
+ *   "image_hash_form"           the lane form of the level launches of zkm_image_hash / zkm_images_hash: 1 a 16-lane row a chain (four chains
+ *                               a wave), 2 a quad of lanes a chain (sixteen a wave), 0 (default; so is any value above 2) chosen per level
+ *                               from the launch's chain count: the row form up to 8192 chains of a level (all images of the call together),
+ *                               the quad form above -- the crossover tools/image_hash_time.py measured on an MI355X (a level of 8192
+ *                               chains: 2.12 ms against 2.32; of 10240: 2.70 against 2.35; profiles/image_hash_time.json).  The words are
+ *                               the same in every form
  *   "debug_verify_flip"         TEST HOOK, accepted only when the process environment holds ZKM_ENABLE_TEST_HOOKS=1 (an unknown key otherwise):
  *                               under "verify", word `value` (0: off) of the blobs of segment 1 of the call (segment 0 of a call of one) is
  *                               increased by one mod p between proving and verifying (tests/test_gpu_verify.py)
@@ -791,6 +797,47 @@ int zkm_prove_segments_ops_boot(zkm_ctx* ctx, const zkm_stark_config* cfg, size_
  * digests_out sponge_ops x 4.  Refusals as above.  Two host waits. */
 int zkm_boot_witness(zkm_ctx* ctx, const zkm_boot_image* image, uint64_t* cpu_rows_out, uint64_t* memory_ops_out, uint64_t* poseidon_inputs_out,
                      uint64_t* poseidon_ts_out, uint64_t* digests_out, char** err);
+
+/* ------------------------------------------------------------------ a memory image's hash pages, root and image id
+ * What the emulator does at every segment split -- Memory::update_page_hash and Memory::compute_image_id (emulator/src/memory.rs:388-471,
+ * with poseidon / hash_page / CONST_HASH_PAGES, :43-118, and alloc_hash_page, :378-386; called from split_segment, state.rs:1477-1530) --
+ * as one device call: the producer of the hash words, pre_hash_root and pre_image_id that the bootstrap above checks.  Page q
+ * (q = addr >> 12) is hashed into the eight words at 0x80000000 + (q << 5): a dirty page p into its L1 page 0x80000 + (p >> 7), that
+ * into its L2 page 0x81000 + (p >> 14), that into the root page 0x81020.
+ *   zkm_image_hash_plan   pure (no context): the ascending list of hash pages update_page_hash writes for these (ascending) dirty
+ *                         pages -- the L1 pages, the L2 pages, then the root, which is always there (ndirty = 0 gives the root alone).
+ *                         Returns the count and writes min(count, capacity) entries; hash_index_out may be NULL.
+ *   zkm_image_hash        A plan page listed in `known` starts from the given words, every other as alloc_hash_page makes it (128
+ *                         copies of the digest of the level below's fresh page; the zero page's digest at the bottom).  Every dirty
+ *                         page is hashed into its L1 slot, every plan L1 page into its L2 slot, every plan L2 page into its root slot;
+ *                         `registers` go to byte 0x400 of the root page; the root page's hash is page_hash_root_out; the image id is the
+ *                         sponge over the root's eight words byte-swapped and pc.  The sponge is overwrite-mode over from_canonical_u32
+ *                         of the little-endian words with pad10*1 (a 129th block for a page); a digest is four canonical words, word j
+ *                         stored as page words 2j (low half) and 2j + 1.  hash_words_out: nplan x 1024 words in plan order, host or
+ *                         device memory -- the pages as the emulator leaves them, the root page with the registers in it; passed as the
+ *                         next call's `known` (device pointers), the hash pages stay on the device between splits.
+ *                         Refused (nonzero; the message names the position and the index), on the host before any device work: a NULL
+ *                         pointer with a nonzero count; indices not strictly ascending; a dirty index >= 0x80000; a known index that is
+ *                         not in the plan; ndirty == 0 without the root among the known pages (the reference panics with "compute image
+ *                         ID fail").  A refusal leaves the context usable and its live memory as it was.  One host wait, for the outputs.
+ *   zkm_images_hash       nimg independent memories in ONE set of launches (the image is a grid dimension, the chains of a level run
+ *                         side by side: K images cost about one image's latency).  hash_words_out[m] as above for image m; roots and
+ *                         ids 32 bytes an image; every word is what zkm_image_hash gives for that image alone, and zkm_image_hash is
+ *                         the nimg = 1 case of the same code.  A refusal names the image's position.
+ * The lane form of the level launches: "image_hash_form" (zkm_ctx_set_tuning).  Profile scopes image_hash/init and image_hash/level. */
+typedef struct zkm_image_pages {
+    const uint32_t* dirty_index; size_t ndirty;  /* HOST memory: page indices (addr >> 12) below 0x80000, strictly ascending (wtrace[0]) */
+    const uint32_t* dirty_words;                 /* ndirty x 1024 LE words, host or device memory */
+    const uint32_t* known_index; size_t nknown;  /* HOST memory: hash pages that exist already, strictly ascending, each one in the plan */
+    const uint32_t* known_words;                 /* nknown x 1024, host or device memory */
+    uint32_t pc;                                 /* compute_image_id's pc */
+    uint8_t registers[156];                      /* get_registers_bytes(), copied to the root page at 0x400 */
+} zkm_image_pages;
+size_t zkm_image_hash_plan(const uint32_t* dirty_index, size_t ndirty, uint32_t* hash_index_out, size_t capacity);
+int zkm_image_hash(zkm_ctx* ctx, const zkm_image_pages* in, uint32_t* hash_words_out, uint8_t page_hash_root_out[32], uint8_t image_id_out[32],
+                   char** err);
+int zkm_images_hash(zkm_ctx* ctx, size_t nimg, const zkm_image_pages* in, uint32_t* const* hash_words_out, uint8_t* page_hash_roots_out,
+                    uint8_t* image_ids_out, char** err);
 
 /* ------------------------------------------------------------------ one process, many GPUs: a pool of contexts
  * The reference drives all segments of a program from ONE process (prover/examples/utils/src/utils.rs:57-68 prove_single_seg_common,

@@ -116,6 +116,14 @@ pub struct ZkmBootImage {
     pub pre_hash_root: [u8; 32], pub pre_image_id: [u8; 32],
 }
 pub type zkm_boot_image = ZkmBootImage;
+/// the dirty pages of a split, the hash pages that exist already, pc and the registers for zkm_image[s]_hash (include/zkm_hip.h;
+/// compared with `abi_layout image` by tests/test_image_hash_abi.py)
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct ZkmImagePages {
+    pub dirty_index: *const u32, pub ndirty: usize, pub dirty_words: *const u32, pub known_index: *const u32, pub nknown: usize,
+    pub known_words: *const u32, pub pc: u32, pub registers: [u8; 156],
+}
+pub type zkm_image_pages = ZkmImagePages;
 pub const ZKM_VERIFY_OK: u32 = 0; pub const ZKM_VERIFY_SHAPE: u32 = 1; pub const ZKM_VERIFY_TRANSCRIPT_STATE: u32 = 2;
 pub const ZKM_VERIFY_CTL_CHALLENGES: u32 = 3; pub const ZKM_VERIFY_QUOTIENT: u32 = 4; pub const ZKM_VERIFY_POW: u32 = 5;
 pub const ZKM_VERIFY_INITIAL_MERKLE: u32 = 6; pub const ZKM_VERIFY_FRI_EVAL: u32 = 7; pub const ZKM_VERIFY_FRI_MERKLE: u32 = 8;
@@ -290,6 +298,12 @@ extern "C" {
                                        err: *mut *mut c_char) -> c_int;
     pub fn zkm_boot_witness(ctx: *mut zkm_ctx, image: *const zkm_boot_image, cpu_rows_out: *mut u64, memory_ops_out: *mut u64,
                             poseidon_inputs_out: *mut u64, poseidon_ts_out: *mut u64, digests_out: *mut u64, err: *mut *mut c_char) -> c_int;
+    // what the emulator hashes between two segments: hash pages, root and image id of a memory image
+    pub fn zkm_image_hash_plan(dirty_index: *const u32, ndirty: usize, hash_index_out: *mut u32, capacity: usize) -> usize;
+    pub fn zkm_image_hash(ctx: *mut zkm_ctx, r#in: *const zkm_image_pages, hash_words_out: *mut u32, page_hash_root_out: *mut u8,
+                          image_id_out: *mut u8, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_images_hash(ctx: *mut zkm_ctx, nimg: usize, r#in: *const zkm_image_pages, hash_words_out: *const *mut u32,
+                           page_hash_roots_out: *mut u8, image_ids_out: *mut u8, err: *mut *mut c_char) -> c_int;
     pub fn zkm_ctx_host_waits(ctx: *const zkm_ctx) -> u64;
     // staged operations: the next call's lists uploaded behind the current proofs
     pub fn zkm_segment_ops_stage(ctx: *mut zkm_ctx, ops: *const zkm_segment_ops, out: *mut *mut zkm_staged_ops, err: *mut *mut c_char) -> c_int;

@@ -91,9 +91,32 @@ static void print_boot(void) {
     printf("\n}\n");
 }
 
+/* `abi_layout image`: the struct of zkm_image[s]_hash (tests/test_image_hash_abi.py compares it with its mirrors); on request only, as
+ * above. */
+static void print_image_hash(void) {
+    int first_struct = 1, first_field = 1;
+    size_t (*plan)(const uint32_t*, size_t, uint32_t*, size_t) = 0;
+    int (*one)(zkm_ctx*, const zkm_image_pages*, uint32_t*, uint8_t*, uint8_t*, char**) = 0;
+    int (*many)(zkm_ctx*, size_t, const zkm_image_pages*, uint32_t* const*, uint8_t*, uint8_t*, char**) = 0;
+    (void)sizeof(plan = zkm_image_hash_plan);
+    (void)sizeof(one = zkm_image_hash);
+    (void)sizeof(many = zkm_images_hash);
+    printf("{");
+    BEGIN(zkm_image_pages);
+    FIELD(zkm_image_pages, dirty_index); FIELD(zkm_image_pages, ndirty); FIELD(zkm_image_pages, dirty_words);
+    FIELD(zkm_image_pages, known_index); FIELD(zkm_image_pages, nknown); FIELD(zkm_image_pages, known_words); FIELD(zkm_image_pages, pc);
+    FIELD(zkm_image_pages, registers);
+    END();
+    printf("\n}\n");
+}
+
 int main(int argc, char** argv) {
     int first_struct = 1, first_field = 1;
     check_segments_ops_prototypes();
+    if (argc > 1 && argv[1][0] == 'i') {
+        print_image_hash();
+        return 0;
+    }
     if (argc > 1 && argv[1][0] == 'b') {
         print_boot();
         return 0;

@@ -57,6 +57,7 @@ EXPORTS = [
     "zkm_check_ctls", "zkm_segment_check_ctls",
     "zkm_ctx_host_waits", "zkm_boot_counts", "zkm_boot_witness", "zkm_segment_tables_boot", "zkm_segments_tables_boot", "zkm_prove_segment_ops_boot",
     "zkm_prove_segments_ops_boot",
+    "zkm_image_hash_plan", "zkm_image_hash", "zkm_images_hash",
     "zkm_verify_proofs", "zkm_verify_segments", "zkm_verify_single_table",
 ]
 
@@ -144,6 +145,17 @@ class BootImageStruct(C.Structure):
 def abi_mirrors_boot():
     """The struct of the zkm_*_boot calls -> its mirror; tests/test_boot_abi.py compares it with `tools/abi_layout boot`."""
     return {"zkm_boot_image": BootImageStruct}
+
+
+class ImagePagesStruct(C.Structure):
+    """zkm_image_pages: the dirty pages of a split, the hash pages that exist already, pc and the registers (include/zkm_hip.h)."""
+    _fields_ = [("dirty_index", C.c_void_p), ("ndirty", C.c_size_t), ("dirty_words", C.c_void_p), ("known_index", C.c_void_p),
+                ("nknown", C.c_size_t), ("known_words", C.c_void_p), ("pc", C.c_uint32), ("registers", C.c_uint8 * 156)]
+
+
+def abi_mirrors_image_hash():
+    """The struct of zkm_image[s]_hash -> its mirror; tests/test_image_hash_abi.py compares it with `tools/abi_layout image`."""
+    return {"zkm_image_pages": ImagePagesStruct}
 
 
 class CtlLocation(C.Structure):
@@ -317,6 +329,9 @@ def load():
         "zkm_prove_segments_ops_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct),
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                   C.POINTER(C.c_void_p), err]),
+        "zkm_image_hash_plan": (C.c_size_t, [cp, C.c_size_t, cp, C.c_size_t]),
+        "zkm_image_hash": (C.c_int, [cp, C.POINTER(ImagePagesStruct), cp, cp, cp, err]),
+        "zkm_images_hash": (C.c_int, [cp, C.c_size_t, C.POINTER(ImagePagesStruct), C.POINTER(C.c_void_p), cp, cp, err]),
         "zkm_staged_ops_get": (C.c_int, [cp, C.POINTER(SegmentOpsStruct)]),
         "zkm_staged_ops_ready": (C.c_int, [cp, C.c_int]),
         "zkm_staged_ops_free": (None, [cp]),
@@ -602,6 +617,36 @@ class BootImage:
         out = [C.c_size_t() for _ in range(5)]
         load().zkm_boot_counts(C.byref(self.struct()), *[C.byref(x) for x in out])
         return tuple(int(x.value) for x in out)
+
+
+def image_hash_plan(indices):
+    """zkm_image_hash_plan: the ascending hash pages (L1 pages, L2 pages, the root 0x81020) that hashing these ascending dirty page
+    indices writes, as a uint32 array."""
+    idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1)
+    L = load()
+    n = L.zkm_image_hash_plan(idx.ctypes.data, idx.size, None, 0)
+    out = np.zeros(n, dtype=np.uint32)
+    L.zkm_image_hash_plan(idx.ctypes.data, idx.size, out.ctypes.data, n)
+    return out
+
+
+def _pages_ptr(words, n):
+    """Page words for zkm_image_pages: a host array of n x 1024 uint32 (returned too: it must outlive the call) or device memory."""
+    if words is None or isinstance(words, (np.ndarray, list, tuple)):
+        a = np.ascontiguousarray(words if words is not None else [], dtype=np.uint32).reshape(-1)
+        assert a.size == 1024 * n, "%d page words for %d pages" % (a.size, n)
+        return a.ctypes.data if n else None, a
+    return _data_ptr(words).value, words
+
+
+def boot_image_from_pages(dirty, plan, hash_pages, root, image_id, entry, check=True):
+    """The BootImage of a memory that holds the dirty pages (indices, n x 1024 words) and the hash pages of an image_hash result: every
+    word of every page as addrs / values, pre_hash_root and pre_image_id from the call."""
+    index = np.concatenate([np.asarray(dirty[0], dtype=np.uint32).reshape(-1), np.asarray(plan, dtype=np.uint32).reshape(-1)])
+    words = np.concatenate([np.asarray(dirty[1], dtype=np.uint32).reshape(-1, 1024), np.asarray(hash_pages, dtype=np.uint32).reshape(-1, 1024)])
+    assert len(index) == len(words) and (np.diff(index.astype(np.int64)) > 0).all()
+    addrs = ((index.astype(np.uint64)[:, None] << np.uint64(12)) + np.arange(0, 4096, 4, dtype=np.uint64)[None, :]).astype(np.uint32)
+    return BootImage(addrs.reshape(-1), words.reshape(-1), root, image_id, entry, check=check)
 
 
 class StagedOps:
@@ -1231,6 +1276,43 @@ class Context:
         finally:
             for b in bufs:
                 b.free()
+
+    # ---- what the emulator hashes between two segments (include/zkm_hip.h "a memory image's hash pages, root and image id")
+    def images_hash(self, images, outs=None):
+        """zkm_images_hash: `images` is a list of (dirty, known, pc, registers) -- dirty and known each (indices, words) with words an
+        n x 1024 uint32 array or device memory (DeviceBuffer, torch tensor, integer pointer), known may be None, registers 156 bytes.
+        outs[m], where given, is device memory for image m's hash pages and is returned in their place.  Returns a list of
+        (plan, hash_pages nplan x 1024 uint32, root 32 bytes, image_id 32 bytes)."""
+        K = len(images)
+        outs = list(outs) if outs is not None else [None] * K
+        st, keep, plans, pages = (ImagePagesStruct * max(K, 1))(), [], [], []
+        for m, (dirty, known, pc, registers) in enumerate(images):
+            d_idx = np.ascontiguousarray(dirty[0] if dirty is not None else [], dtype=np.uint32).reshape(-1)
+            k_idx = np.ascontiguousarray(known[0] if known is not None else [], dtype=np.uint32).reshape(-1)
+            d_ptr, d_keep = _pages_ptr(dirty[1] if dirty is not None else None, d_idx.size)
+            k_ptr, k_keep = _pages_ptr(known[1] if known is not None else None, k_idx.size)
+            keep += [d_idx, k_idx, d_keep, k_keep]
+            st[m].dirty_index, st[m].ndirty, st[m].dirty_words = d_idx.ctypes.data if d_idx.size else None, d_idx.size, d_ptr
+            st[m].known_index, st[m].nknown, st[m].known_words = k_idx.ctypes.data if k_idx.size else None, k_idx.size, k_ptr
+            st[m].pc = int(pc)
+            registers = bytes(registers)
+            assert len(registers) == 156
+            st[m].registers[:] = registers
+            plans.append(self.L.zkm_image_hash_plan(d_idx.ctypes.data, d_idx.size, None, 0))
+            pages.append(np.zeros((plans[-1], 1024), dtype=np.uint32) if outs[m] is None else outs[m])
+        out_ptrs = (C.c_void_p * max(K, 1))(*[p.ctypes.data if isinstance(p, np.ndarray) else _data_ptr(p).value for p in pages])
+        roots, ids, err = np.zeros(32 * K, dtype=np.uint8), np.zeros(32 * K, dtype=np.uint8), C.c_char_p()
+        if K == 1:
+            rc = self.L.zkm_image_hash(self.h, C.byref(st[0]), out_ptrs[0], roots.ctypes.data, ids.ctypes.data, C.byref(err))
+        else:
+            rc = self.L.zkm_images_hash(self.h, K, st, out_ptrs, roots.ctypes.data, ids.ctypes.data, C.byref(err))
+        _check(rc, err)
+        return [(image_hash_plan(images[m][0][0] if images[m][0] is not None else []), pages[m], roots[32 * m:32 * m + 32].tobytes(),
+                 ids[32 * m:32 * m + 32].tobytes()) for m in range(K)]
+
+    def image_hash(self, dirty, known=None, pc=0, registers=bytes(156), out=None):
+        """zkm_image_hash: one memory (images_hash with one image).  Returns (plan, hash_pages, root, image_id)."""
+        return self.images_hash([(dirty, known, pc, registers)], outs=[out])[0]
 
     def segment_tables_boot(self, image, ops, cfg=None, sizing=False):
         """zkm_segment_tables_boot: segment_tables with the bootstrap of `image` (a BootImage) in front of ops.  Returns (staged,

@@ -73,6 +73,9 @@ struct zkm_ctx {
     hipStream_t copy_stream2 = nullptr; // second upload stream of staged traces (zkm_trace_stage: alternate pieces, two copy engines)
     hipStream_t side_stream = nullptr;  // the bootstrap's sponge chains beside the other tables' generation (created on first use)
     int boot_chain_quad = 0;            // the chains' permutation across a quad of lanes instead of a 16-lane row (tools/boot_time.py times both)   } zkm_ctx_set_tuning
+    int image_hash_form = 0;            // the level launches of zkm_image[s]_hash: 0 by chain count, 1 the 16-lane row form, 2 the quad form   } zkm_ctx_set_tuning
+    size_t image_hash_row_max = 8192;   // ... by chain count: the row form up to this many chains of a level in one launch -- two waves on each of the
+                                        // 1024 SIMDs -- the quad form above (profiles/image_hash_time.json: 2.12 against 2.32 ms at 8192 chains, 2.70 against 2.35 at 10240)
     size_t ingest_chunk_cols = 32;     // columns per ingest chunk (0 = monolithic upload)           } zkm_ctx_set_tuning
     size_t keccak_parts_max_points = (size_t)1 << 15;   // k_quotient_keccak_parts up to this many points  }
     size_t fri_fused_division_min = ~(size_t)0;         // k_seg_scan_final from this many coefficients (default: never -- since the
