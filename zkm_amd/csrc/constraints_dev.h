@@ -145,14 +145,14 @@ __device__ void eval_poseidon_constraints(const gl_t* __restrict__ lv, size_t cs
 #pragma unroll 1
     for (int g = 0; g < 7; g++) {
         uint64_t c[6];
-        poseidon_partial_group_t<3>(s, PC::ZKM_POSEIDON_FUSED_C1[g], PC::ZKM_POSEIDON_FUSED_C2[g], PC::ZKM_POSEIDON_FUSED_C3[g],
+        poseidon_partial_group_t<3, false>(s, PC::ZKM_POSEIDON_FUSED_C1[g], PC::ZKM_POSEIDON_FUSED_C2[g], PC::ZKM_POSEIDON_FUSED_C3[g],
                                     [&](int kk, uint64_t a) { return gl_sub(partial_check(&c[2 * kk], 3 * g + kk, a), gl_canon(a)); });
         s[0] = partial_check(&c[4], 3 * g + 2, s[0]);
         k.constraints(c);
     }
     {
         uint64_t c[2];
-        poseidon_partial_group_t<2>(s, PC::ZKM_POSEIDON_FUSED_C1[7], 0, PC::ZKM_POSEIDON_FUSED_C3[7],
+        poseidon_partial_group_t<2, false>(s, PC::ZKM_POSEIDON_FUSED_C1[7], 0, PC::ZKM_POSEIDON_FUSED_C3[7],
                                     [&](int, uint64_t a) { return gl_sub(partial_check(c, 21, a), gl_canon(a)); });
         k.constraints(c);
     }

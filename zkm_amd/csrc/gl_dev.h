@@ -122,6 +122,50 @@ GL_HD uint64_t gl_sub_rr(uint64_t a, uint64_t b) {
 }
 #endif
 
+// x * IMM + c (64-bit, the caller keeps it from wrapping) as ONE v_mad_u64_u32 whose multiplier is an inline constant of the ISA
+// (0 .. 64) -- the small entries of a matrix.  Written out because the compiler turns such a term into something dearer where IMM is a
+// power of two (v_lshl_add_u64 on x zero-extended into a register pair: a move more) or shared by two terms (13 a + 13 b as 13 (a + b) on
+// two zero-extended pairs).
+//   gl_mad_imm:    c is any 64-bit value.
+//   gl_mad_imm_sc: c is WAVE-UNIFORM (a word of a constant table at a uniform index) and rides in as a scalar register pair.  A VALU
+//                  instruction of this ISA reads ONE scalar operand: with the multiplier in an SGPR too, the compiler starts the sum at 0
+//                  and adds the constant in a 64-bit add of its own; with an inline multiplier the constant is the addend of the first
+//                  multiply-add.  (Setting up the pair is scalar work: no vector issue.)
+template <uint32_t IMM>
+GL_HD uint64_t gl_mad_imm(uint32_t x, uint64_t c) {
+    static_assert(IMM <= 64, "gl_mad_imm: the multiplier must be an inline constant");
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t r, carry;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry) : "v"(x), "n"(IMM), "v"(c));
+    return r;
+#else
+    return (uint64_t)x * IMM + c;
+#endif
+}
+template <uint32_t IMM>
+GL_HD uint64_t gl_mad_imm_sc(uint32_t x, uint64_t c) {
+    static_assert(IMM <= 64, "gl_mad_imm_sc: the multiplier must be an inline constant");
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t r, carry;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry) : "v"(x), "n"(IMM), "s"(c));
+    return r;
+#else
+    return (uint64_t)x * IMM + c;
+#endif
+}
+// x * m + c with the multiplier in a scalar register (m wave-uniform): one v_mad_u64_u32 the optimiser cannot move to another place in
+// a sum.  A sum opened with gl_mad_imm_sc stays a chain of multiply-adds only if its other terms are opaque too: left plain, the
+// compiler re-associates it into a chain that starts at 0 and a 64-bit add of the opening term.
+GL_HD uint64_t gl_mad_s(uint32_t x, uint32_t m, uint64_t c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t r, carry;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry) : "v"(x), "s"(m), "v"(c));
+    return r;
+#else
+    return (uint64_t)x * m + c;
+#endif
+}
+
 // 128-bit (hi:lo) -> loose.  Standard Goldilocks reduction: 2^64 == 2^32 - 1, 2^96 == -1, written for gfx950 issue costs
 // (tools/ubench3.hip: compare + select chains are the expensive part of a modmul, moves and plain 32-bit ops are cheap):
 //   t0 = lo - h1           borrow <=> lo < h1 < 2^32 <=> the high word went from 0 to 0xFFFFFFFF; the borrow mask

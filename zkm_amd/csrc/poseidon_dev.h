@@ -127,9 +127,11 @@ GL_HD void poseidon_mds_add(uint64_t s[12], const uint64_t* add) {
     POSEIDON_OPAQUE(diag);
 #pragma unroll
     for (int r = ROW0; r < ROW1; r++) {   // (rows outside [ROW0, ROW1) keep their input word: callers treat them as dead)
-        uint64_t al = ADD ? (uint64_t)(uint32_t)add[r] : 0, ah = ADD ? add[r] >> 32 : 0;
+        // ADD: the constant is the addend of the row's first multiply-add, whose multiplier C[0] = 17 is then an inline constant and not
+        // the opaque SGPR (gl_mad_imm_sc: an instruction reads one scalar operand) -- no 64-bit add of its own per half-sum
+        uint64_t al = ADD ? gl_mad_imm_sc<17>(lo[r], (uint64_t)(uint32_t)add[r]) : 0, ah = ADD ? gl_mad_imm_sc<17>(hi[r], add[r] >> 32) : 0;
 #pragma unroll
-        for (int i = 0; i < 12; i++) {
+        for (int i = ADD ? 1 : 0; i < 12; i++) {
             al += (uint64_t)lo[(i + r) % 12] * C[i];
             ah += (uint64_t)hi[(i + r) % 12] * C[i];
         }
@@ -150,10 +152,53 @@ GL_HD constexpr uint32_t poseidon_m1(int i, int j) {
     return C[(j - i + 12) % 12] + ((i == 0 && j == 0) ? 8u : 0u);
 }
 
+// Row 0 of M on the halves, from term J on: every multiplier is an inline constant, so every term is one multiply-add (gl_mad_imm)
+template <int J>
+GL_HD void poseidon_m_row0(const uint32_t lo[12], const uint32_t hi[12], uint64_t& al, uint64_t& ah) {
+    if constexpr (J < 12) {
+        al = gl_mad_imm<poseidon_m1(0, J)>(lo[J], al);
+        ah = gl_mad_imm<poseidon_m1(0, J)>(hi[J], ah);
+        poseidon_m_row0<J + 1>(lo, hi, al, ah);
+    }
+}
+// Rows I .. 11 of the dense layer that closes a fused group (M^3 for T = 3, M^2 for T = 2).  The constant c3[i] opens both half-sums as
+// the addend of the term with the inline multiplier M[i][0] (<= 41): d2 M[i][0] for T = 3, d1 M[i][0] for T = 2.
+template <int T, int I>
+GL_HD void poseidon_group_rows(uint64_t s[12], const uint32_t lo[12], const uint32_t hi[12], uint32_t d1l, uint32_t d1h, uint32_t d2l, uint32_t d2h,
+                               const uint64_t* c3) {
+    if constexpr (I < 12) {
+        uint64_t al, ah;
+        if (T == 3) {
+            al = gl_mad_s(d1l, PC::ZKM_POSEIDON_M2[I][0], gl_mad_imm_sc<poseidon_m1(I, 0)>(d2l, (uint64_t)(uint32_t)c3[I]));
+            ah = gl_mad_s(d1h, PC::ZKM_POSEIDON_M2[I][0], gl_mad_imm_sc<poseidon_m1(I, 0)>(d2h, c3[I] >> 32));
+#pragma unroll
+            for (int j = 0; j < 12; j++) {
+                al = gl_mad_s(lo[j], PC::ZKM_POSEIDON_M3[I][j], al);
+                ah = gl_mad_s(hi[j], PC::ZKM_POSEIDON_M3[I][j], ah);
+            }
+        } else {
+            al = gl_mad_imm_sc<poseidon_m1(I, 0)>(d1l, (uint64_t)(uint32_t)c3[I]);
+            ah = gl_mad_imm_sc<poseidon_m1(I, 0)>(d1h, c3[I] >> 32);
+#pragma unroll
+            for (int j = 0; j < 12; j++) {
+                al = gl_mad_s(lo[j], PC::ZKM_POSEIDON_M2[I][j], al);
+                ah = gl_mad_s(hi[j], PC::ZKM_POSEIDON_M2[I][j], ah);
+            }
+        }
+        s[I] = poseidon_fold(al, ah);
+        if ((I & 1) == 1) POSEIDON_SCHED_FENCE();
+        poseidon_group_rows<T, I + 1>(s, lo, hi, d1l, d1h, d2l, d2h, c3);
+    }
+}
+
 // T linear layers (T = 3 or 2) with the T - 1 lane-0 s-boxes between them; c3 = constants after the last layer.
 // delta(k, a) = what lane 0 gains at s-box k = 0, 1 of the group on its input a: sbox(a) - a in the permutation; the constraint
 // evaluator (constraints_dev.h) takes the s-box output from a witness cell instead.
-template <int T, class DELTA>
+// c1, c2, c3[] are wave-uniform on the device: their halves are the scalar addends of each sum's first multiply-add (gl_mad_imm_sc).
+// ROW0_ASM: the first single row (M, inline multipliers) written out term by term (poseidon_m_row0).  The sponge kernels want it: left to
+// the compiler the row's shifts and shared multipliers need zero-extended register pairs, and with those gone it keeps ONE zeroed
+// scratch pair for the whole kernel.  The constraint evaluator does not: k_quotient<POSEIDON, 1> needs 93 registers with it, 69 without.
+template <int T, bool ROW0_ASM = true, class DELTA>
 GL_HD void poseidon_partial_group_t(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3, DELTA&& delta) {
     uint32_t lo[12], hi[12];
 #pragma unroll
@@ -161,51 +206,34 @@ GL_HD void poseidon_partial_group_t(uint64_t s[12], uint64_t c1, uint64_t c2, co
         lo[i] = (uint32_t)s[i];
         hi[i] = (uint32_t)(s[i] >> 32);
     }
-    uint64_t al = (uint32_t)c1, ah = c1 >> 32;
+    uint64_t al = gl_mad_imm_sc<poseidon_m1(0, 0)>(lo[0], (uint64_t)(uint32_t)c1), ah = gl_mad_imm_sc<poseidon_m1(0, 0)>(hi[0], c1 >> 32);
+    if constexpr (ROW0_ASM) {
+        poseidon_m_row0<1>(lo, hi, al, ah);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 12; j++) {
-        al += (uint64_t)lo[j] * poseidon_m1(0, j);
-        ah += (uint64_t)hi[j] * poseidon_m1(0, j);
+        for (int j = 1; j < 12; j++) {
+            al += (uint64_t)lo[j] * poseidon_m1(0, j);
+            ah += (uint64_t)hi[j] * poseidon_m1(0, j);
+        }
     }
     const uint64_t d1 = delta(0, poseidon_fold(al, ah));
     const uint32_t d1l = (uint32_t)d1, d1h = (uint32_t)(d1 >> 32);
     uint32_t d2l = 0, d2h = 0;
     POSEIDON_SCHED_FENCE();
     if (T == 3) {
-        al = (uint64_t)d1l * poseidon_m1(0, 0) + (uint32_t)c2;
-        ah = (uint64_t)d1h * poseidon_m1(0, 0) + (c2 >> 32);
+        al = gl_mad_imm_sc<poseidon_m1(0, 0)>(d1l, (uint64_t)(uint32_t)c2);
+        ah = gl_mad_imm_sc<poseidon_m1(0, 0)>(d1h, c2 >> 32);
 #pragma unroll
         for (int j = 0; j < 12; j++) {
-            al += (uint64_t)lo[j] * PC::ZKM_POSEIDON_M2[0][j];
-            ah += (uint64_t)hi[j] * PC::ZKM_POSEIDON_M2[0][j];
+            al = gl_mad_s(lo[j], PC::ZKM_POSEIDON_M2[0][j], al);
+            ah = gl_mad_s(hi[j], PC::ZKM_POSEIDON_M2[0][j], ah);
         }
         const uint64_t d2 = delta(1, poseidon_fold(al, ah));
         d2l = (uint32_t)d2;
         d2h = (uint32_t)(d2 >> 32);
         POSEIDON_SCHED_FENCE();
     }
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-        if (T == 3) {
-            al = (uint64_t)d1l * PC::ZKM_POSEIDON_M2[i][0] + (uint64_t)d2l * poseidon_m1(i, 0) + (uint32_t)c3[i];
-            ah = (uint64_t)d1h * PC::ZKM_POSEIDON_M2[i][0] + (uint64_t)d2h * poseidon_m1(i, 0) + (c3[i] >> 32);
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                al += (uint64_t)lo[j] * PC::ZKM_POSEIDON_M3[i][j];
-                ah += (uint64_t)hi[j] * PC::ZKM_POSEIDON_M3[i][j];
-            }
-        } else {
-            al = (uint64_t)d1l * poseidon_m1(i, 0) + (uint32_t)c3[i];
-            ah = (uint64_t)d1h * poseidon_m1(i, 0) + (c3[i] >> 32);
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                al += (uint64_t)lo[j] * PC::ZKM_POSEIDON_M2[i][j];
-                ah += (uint64_t)hi[j] * PC::ZKM_POSEIDON_M2[i][j];
-            }
-        }
-        s[i] = poseidon_fold(al, ah);
-        if ((i & 1) == 1) POSEIDON_SCHED_FENCE();
-    }
+    poseidon_group_rows<T, 0>(s, lo, hi, d1l, d1h, d2l, d2h, c3);
 }
 template <int T>
 GL_HD void poseidon_partial_group(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3) {

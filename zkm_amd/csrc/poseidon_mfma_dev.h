@@ -182,7 +182,11 @@ __device__ __forceinline__ void poseidon_mds_add_mfma(uint64_t s[12], int next, 
                     asm("v_mad_i64_i32 %0, %1, %2, 1, %3" : "=&v"(acc), "=&s"(unused) : "v"(X[r]), "s"(t0[r]));
                     acc += (int64_t)(int32_t)Z[r] * m16;
                     const uint32_t u = PARK ? park[r * ZKM_MFMA_PARK_STRIDE] : U[r], y = PARK ? park[(12 + r) * ZKM_MFMA_PARK_STRIDE] : Y[r];
-                    const uint64_t T = ((uint64_t)((uint32_t)((uint64_t)acc >> 32) + u) << 32) | (uint32_t)acc;
+                    // (the high word is added here and not behind the fold's multiply-add, where the compiler moves a plain add: that
+                    // costs a zero-extended copy of the low word)
+                    uint32_t thi;
+                    asm("v_add_u32 %0, %1, %2" : "=v"(thi) : "v"((uint32_t)((uint64_t)acc >> 32)), "v"(u));
+                    const uint64_t T = ((uint64_t)thi << 32) | (uint32_t)acc;
                     s[r] = poseidon_fold_ty(T, y);
                     if ((r & 1) == 1) POSEIDON_SCHED_FENCE();   // (two rows' temporaries at a time)
                 }
