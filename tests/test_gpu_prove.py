@@ -506,3 +506,28 @@ def test_single_table_proofs_in_lockstep_equal_single_proofs(ctx, zkm, oracle, o
         t.free()
     if log_n >= 20:
         ctx.trim()      # (four proofs' worth of cached buffers: give them back before the next test)
+
+
+def test_failed_prove_call_leaves_the_transcript_where_it_was(ctx, zkm):
+    """A prove call that fails after it has begun hands no transcript back: zkm_prove_openings on a quotient commitment of another height
+    (through the loaded library, so that no Python-side check refuses first) returns an error, and the caller's challenger is byte for
+    byte what it was."""
+    import ctypes as C
+    rng = np.random.default_rng(77)
+    tv, av = (rng.integers(0, P, k << 5, dtype=np.uint64) for k in (13, 4))
+    qc = rng.integers(0, P, 4 << 6, dtype=np.uint64)
+    tb, ab = zkm.PolynomialBatch.from_values(ctx, tv, 13, 5), zkm.PolynomialBatch.from_values(ctx, av, 4, 5)
+    qb = zkm.PolynomialBatch.from_coeffs(ctx, qc, 4, 6)
+    ch = zkm.challenger_new()
+    zkm.challenger_observe(ch, [42])
+    before = zkm.Challenger.from_buffer_copy(ch)
+    cfg = ctx.standard_config()
+    proof = np.zeros(ctx.proof_words(cfg, 6, 13, 4, 2), dtype=np.uint64)
+    err = C.c_char_p()
+    rc = zkm.load().zkm_prove_openings(ctx.h, C.byref(cfg), tb.h, ab.h, qb.h, 2, C.byref(ch), proof.ctypes.data_as(zkm.u64p), C.byref(err))
+    assert rc != 0 and err.value
+    for field in ("state", "in_buf", "n_in", "out_buf", "n_out"):
+        got, want = getattr(ch, field), getattr(before, field)
+        assert (got == want) if isinstance(got, int) else (bytes(got) == bytes(want)), field
+    for b in (tb, ab, qb):
+        b.free()

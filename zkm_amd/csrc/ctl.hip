@@ -1074,8 +1074,8 @@ struct lockstep_call {
                 chs[k] = &local[k];
                 proofs[k] = io[g.segs[k]].proofs + offs[g.segs[k]][t];
             }
-            zkm_prove_single_table_aux(c, T0[t].table_id, cfg, T0[t].ncols, g.log_n, g.commit.get(), g.aux.get(), tz0[t].naux, T0[t].ctl,
-                                       gzs[j].data(), tz0[t].ids.data(), tz0[t].zs.size(), glookup[j].data(), chs, proofs);
+            zkm_prove_table_from_commitments(c, T0[t].table_id, cfg, T0[t].ncols, g.log_n, g.commit.get(), g.aux.get(), tz0[t].naux, T0[t].ctl,
+                                             gzs[j].data(), tz0[t].ids.data(), tz0[t].zs.size(), glookup[j].data(), chs, proofs);
             for (size_t k = 0; k < g.segs.size(); k++) ch[g.segs[k]] = local[k];
         } catch (const zkm_segment_error& e) {
             throw std::runtime_error(label(g, e.seg) + e.what());

@@ -1,13 +1,16 @@
 // stark.hip -- prove_single_table on the GPU: quotient (K7-K9), openings (K10), FRI (K11-K14), queries.
 //
-// Host orchestration restates the reference's prover/src/prover.rs:441-641 (stage and transcript order);
-// the kernels replace the rayon loops of compute_quotient_polys (:700-782), StarkOpeningSet::new
+// Host orchestration restates the reference's prover/src/prover.rs:441-641 (stage and transcript order) as stages over one state, the
+// table_proof (a proof_stack: the transcripts, blobs and scratch of a stack of proofs in flight): commit_trace -> commit_aux ->
+// commit_quotient (alphas, quotient_device) -> draw_zeta, write_openings -> prove_openings (FRI alpha, combination, then fri_finish:
+// composites to natural order, divide_accumulate_all, fri_commit_phase, fri_proof_of_work, fri_query_rounds).  Three drivers enter
+// that line: from values (zkm_prove_single_table[_ctl]), from the trace and auxiliary commitments (zkm_prove_table_from_commitments:
+// zkm_prove_single_tables, ctl.hip) and from all three commitments (zkm_prove_openings).
+// The kernels replace the rayon loops of compute_quotient_polys (:700-782), StarkOpeningSet::new
 // (proof.rs:299-334) and plonky2's PolynomialBatch::prove_openings / fri_proof.
 // The Challenger stays on the host (a few hundred field elements per table); only caps, openings,
 // the final polynomial and the query openings cross PCIe.
 #define GL_REDUCE_BRANCHFREE 1   // (gl_dev.h: these kernels interleave independent products at low occupancy)
-#include <memory>
-
 #include "constraints_dev.h"
 #include "ctl_dev.h"
 
@@ -305,6 +308,116 @@ static uint32_t table_lookup_args(int table_id, size_t nalphas, const uint64_t* 
     return NL;
 }
 
+// f(std::integral_constant<int, NA>) for a run-time number of constraint challenges: the one way from it to a template argument
+// (tables.h zkm_with_table does the same for the table id)
+template <class F> decltype(auto) with_nalphas(size_t nalphas, F&& f) {
+    switch (nalphas) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: throw std::runtime_error("1 or 2 challenges supported");
+    }
+}
+
+// what every quotient launch of one table takes beside the columns: the two-level table of w_{4n}^t, g^n (0: the kernels' check mode,
+// quotient_setup), 1 / Z_H on the even and odd points, w_n^-1 (the last row), w_n, 1 / n
+struct quotient_consts {
+    const gl_t* wpow;
+    gl_t gn, zh0, zh1, last, w_n, n_inv;
+};
+// points of the quotient domain per segment (check mode, rate_bits = 0: every row of the trace)
+static size_t quotient_points(const zkm_batch* trace) { return trace->rate_bits ? trace->N() >> 1 : trace->N(); }
+
+// the table's own constraints and lookups: d_vals = the running accumulators, nseg x nalphas x points
+static void launch_table_constraints(zkm_ctx* c, int table_id, const zkm_batch* trace, const zkm_batch* aux, const lookup_dev& lookups,
+                                     const seg_gl2& lookup_ch, const alpha_args& alphas, size_t nalphas, const quotient_consts& q, gl_t* d_vals) {
+    const size_t nseg = trace->nseg, size = quotient_points(trace), trace_seg = trace->lde_seg(), aux_seg = aux->lde_seg();
+    const unsigned z = (unsigned)nseg, log_n = trace->log_n, lde_bits = trace->lde_bits();
+    zkm_prof_scope ps(c, zkm_table(table_id)->quotient_scope);
+    dim3 grid((size + 255) / 256, 1, z), block(256);
+    if (table_id == ZKM_TABLE_KECCAK && size * nseg <= c->keccak_parts_max_points && q.gn != 0) {
+        // short table: 25 threads per point, then the sum of the parts (constraints_dev.h)
+        const size_t per = nalphas * (KECCAK_NUM_CONSTRAINTS + 1);
+        std::vector<gl_t> apw(nseg * per);
+        for (size_t sg = 0; sg < nseg; sg++)
+            for (size_t a = 0; a < nalphas; a++) {
+                gl_t p = 1;
+                for (size_t e = 0; e <= KECCAK_NUM_CONSTRAINTS; e++) {
+                    apw[sg * per + a * (KECCAK_NUM_CONSTRAINTS + 1) + e] = p;
+                    p = gl_mul(p, gl_canon(alphas.v[2 * sg + a]));
+                }
+            }
+        zkm_scratch d_apw(c, apw.size() * sizeof(gl_t)), d_tmp(c, nseg * (size_t)KECCAK_CONSTRAINT_PARTS * nalphas * size * sizeof(gl_t));
+        c->upload(d_apw.p, apw.data(), apw.size() * sizeof(gl_t));
+        dim3 gridp((unsigned)((size + 255) / 256), KECCAK_CONSTRAINT_PARTS, z);
+        with_nalphas(nalphas, [&](auto NA) {
+            hipLaunchKernelGGL((k_quotient_keccak_parts<decltype(NA)::value>), gridp, block, 0, c->stream, trace->lde, lde_bits, alphas, q.wpow, q.gn, q.last,
+                               q.w_n, q.n_inv, d_apw.as<gl_t>(), d_tmp.as<gl_t>(), trace_seg);
+        });
+        hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)((nalphas * size + 255) / 256), 1, z), block, 0, c->stream, d_tmp.as<gl_t>(),
+                           (unsigned)KECCAK_CONSTRAINT_PARTS, nalphas * size, d_vals);
+    } else
+        zkm_with_table(table_id, [&](auto T) {
+            with_nalphas(nalphas, [&](auto NA) {
+                hipLaunchKernelGGL((k_quotient<decltype(T)::value, decltype(NA)::value>), grid, block, 0, c->stream, trace->lde, aux->lde, log_n, lde_bits,
+                                   lookups, alphas, lookup_ch, q.wpow, q.gn, q.last, q.w_n, q.n_inv, d_vals, trace_seg, aux_seg);
+            });
+        });
+    ZKM_HIP_CHECK(hipGetLastError());
+}
+
+// the CTL checks behind NL lookup columns, continuing the accumulators in d_vals, and the division by Z_H
+static void launch_ctl_checks(zkm_ctx* c, const zkm_batch* trace, const zkm_batch* aux, const ctl_dev_owner& own, uint32_t NL, const alpha_args& alphas,
+                              size_t nalphas, const quotient_consts& q, gl_t* d_vals) {
+    const size_t nseg = trace->nseg, size = quotient_points(trace), trace_seg = trace->lde_seg(), aux_seg = aux->lde_seg();
+    const unsigned z = (unsigned)nseg, lde_bits = trace->lde_bits();
+    zkm_prof_scope ps(c, "quotient_ctl");
+    dim3 grid((size + 255) / 256, 1, z), block(256);
+    // chunk plan: at most CHUNK helper checks per chunk, the closing checks with the last chunk of their Z.  A thread's work is a
+    // chain of column-combination evaluations whatever the table's height: on short tables (a launch cannot fill the GPU anyway)
+    // one helper check per chunk -- four times the workgroups, a quarter of the chain (KeccakSponge at 2^8 rows: 340 us per launch)
+    const bool short_table = size * nseg <= ((size_t)1 << 15);
+    const uint32_t CHUNK = short_table ? 1 : 4;
+    std::vector<ctl_chunk> plan;
+    uint32_t K = 0, hstart = 0;
+    for (uint32_t zi = 0; zi < own.h_zs.size(); zi++) {
+        // helper checks exist only for real column sets (the benchmark's fake CTL data has helper columns but no sets)
+        const uint32_t np = own.h_zs[zi].num_helpers ? (own.h_zs[zi].ncolsets + 1) / 2 : 0;
+        uint32_t q0 = 0;
+        do {
+            const uint32_t q1 = np - q0 > CHUNK ? q0 + CHUNK : np;
+            const bool closing = q1 == np;
+            K += (q1 - q0) + (closing ? 2 : 0);
+            plan.push_back(ctl_chunk{zi, hstart, q0, q1, closing ? 1u : 0u, K});   // (tail: k_end until the count K is known)
+            q0 = q1;
+        } while (q0 < np);
+        hstart += own.h_zs[zi].num_helpers;
+    }
+    for (ctl_chunk& ch : plan) ch.tail = K - ch.tail;
+    const bool chunked = plan.size() >= (short_table ? 2u : 8u) && size * nseg <= ((size_t)1 << 18) && q.gn != 0;
+    if (!chunked) {
+        with_nalphas(nalphas, [&](auto NA) {
+            hipLaunchKernelGGL((k_quotient_ctl<decltype(NA)::value>), grid, block, 0, c->stream, trace->lde, aux->lde, lde_bits, own.d, NL, alphas, q.wpow, q.gn,
+                               q.zh0, q.zh1, q.last, q.w_n, q.n_inv, d_vals, trace_seg, aux_seg);
+        });
+    } else {
+        zkm_scratch_list tmp(c);
+        ctl_chunk* d_plan = tmp.alloc<ctl_chunk>(plan.size() * sizeof(ctl_chunk));
+        gl_t* d_tmp = tmp.alloc<gl_t>(nseg * plan.size() * nalphas * size * sizeof(gl_t));
+        c->upload(d_plan, plan.data(), plan.size() * sizeof(ctl_chunk));
+        dim3 grid2((unsigned)((size + 255) / 256), (unsigned)plan.size(), z);
+        with_nalphas(nalphas, [&](auto NA) {
+            hipLaunchKernelGGL((k_quotient_ctl_chunk<decltype(NA)::value>), grid2, block, 0, c->stream, trace->lde, aux->lde, lde_bits, own.d, d_plan, NL, alphas,
+                               q.wpow, q.gn, q.last, q.w_n, q.n_inv, d_tmp, trace_seg, aux_seg);
+            hipLaunchKernelGGL((k_quotient_ctl_sum<decltype(NA)::value>), grid, block, 0, c->stream, d_tmp, (uint32_t)plan.size(), K, alphas, q.zh0, q.zh1,
+                               size, d_vals);
+        });
+        ZKM_HIP_CHECK(hipGetLastError());
+        // (no host sync: upload() has copied `plan` into the pinned ring -- or waited itself if it was too large for it -- and the
+        // blocks released here are only reused by later work on this stream)
+    }
+    ZKM_HIP_CHECK(hipGetLastError());
+}
+
 // quotient polys: d_out = nalphas x 2n natural-order coefficients (device) -- per segment of the stack (trace / aux: stacked batches of
 // the same nseg; alphas_host: nseg x nalphas; lookup_challenges: nseg x nalphas; own: a description with nseg lists of CtlZData)
 // check = true (zkm_check_constraints): trace / aux describe the VALUES (lde = ncols x n values, rate_bits 0) and d_out receives the
@@ -315,7 +428,6 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
     seg_gl2 lookup_ch{};
     const size_t nseg = trace->nseg;
     if (aux->nseg != nseg || nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_quotient: batches of different stacks");
-    const unsigned z = (unsigned)nseg;
     const uint32_t NL = table_lookup_args(table_id, nalphas, lookup_challenges, nseg, lookups, lookup_ch);
     if (zkm_table_width(table_id) == 0 || trace->ncols != zkm_table_width(table_id))
         throw std::runtime_error("zkm_quotient: unknown table id, or the trace width does not match the table");
@@ -323,111 +435,18 @@ static void quotient_device(zkm_ctx* c, int table_id, const zkm_batch* trace, co
         throw std::runtime_error("zkm_quotient: rate_bits must be 2 and the batches must have equal degree");
     if (nalphas < 1 || nalphas > 2) throw std::runtime_error("zkm_quotient: 1 or 2 challenges supported");
     if (own.naux + NL != aux->ncols) throw std::runtime_error("zkm_quotient: aux column count does not match the CTL description");
-    const ctl_dev& ctl = own.d;
-    unsigned log_n = trace->log_n, lde_bits = check ? log_n : log_n + 2, log_q = check ? log_n : log_n + 1;
-    size_t size = (size_t)1 << log_q;
-    const size_t trace_seg = trace->lde_seg(), aux_seg = aux->lde_seg();
-    gl_t w4 = gl_root_of_unity(lde_bits);
-    const gl_t* wpow = c->pow_table(w4, lde_bits);
-    gl_t gn = check ? 0 : gl_exp_pow2(GL_GENERATOR, log_n);      // (0: the kernels' check mode, quotient_setup)
-    gl_t zh0 = check ? 1 : gl_inv(gl_sub(gn, 1)), zh1 = check ? 1 : gl_inv(gl_sub(gl_neg(gn), 1));
-    gl_t w_n = gl_root_of_unity(log_n), last = gl_inv(w_n);
-    gl_t n_inv = gl_inv((gl_t)(((uint64_t)1 << log_n) % GL_P));
+    const unsigned log_n = trace->log_n, lde_bits = trace->lde_bits(), log_q = check ? log_n : log_n + 1;
+    const size_t size = quotient_points(trace);
+    const gl_t gn = check ? 0 : gl_exp_pow2(GL_GENERATOR, log_n), w_n = gl_root_of_unity(log_n);
+    const quotient_consts q{c->pow_table(gl_root_of_unity(lde_bits), lde_bits), gn, check ? 1 : gl_inv(gl_sub(gn, 1)), check ? 1 : gl_inv(gl_sub(gl_neg(gn), 1)),
+                            gl_inv(w_n), w_n, gl_inv((gl_t)(((uint64_t)1 << log_n) % GL_P))};
     alpha_args d_alphas{};
     for (size_t sg = 0; sg < nseg; sg++)
-        for (size_t a = 0; a < nalphas && a < 2; a++) d_alphas.v[2 * sg + a] = alphas_host[sg * nalphas + a];
+        for (size_t a = 0; a < nalphas; a++) d_alphas.v[2 * sg + a] = alphas_host[sg * nalphas + a];
     zkm_scratch vals(c, nseg * nalphas * size * sizeof(gl_t));
     gl_t* const d_vals = vals.as<gl_t>();
-    {
-        zkm_prof_scope ps(c, zkm_table(table_id)->quotient_scope);
-        dim3 grid((size + 255) / 256, 1, z), block(256);
-        if (table_id == ZKM_TABLE_KECCAK && size * nseg <= c->keccak_parts_max_points && !check) {
-            // short table: 25 threads per point, then the sum of the parts (constraints_dev.h)
-            const size_t per = nalphas * (KECCAK_NUM_CONSTRAINTS + 1);
-            std::vector<gl_t> apw(nseg * per);
-            for (size_t sg = 0; sg < nseg; sg++)
-                for (size_t a = 0; a < nalphas; a++) {
-                    gl_t p = 1;
-                    for (size_t e = 0; e <= KECCAK_NUM_CONSTRAINTS; e++) {
-                        apw[sg * per + a * (KECCAK_NUM_CONSTRAINTS + 1) + e] = p;
-                        p = gl_mul(p, gl_canon(alphas_host[sg * nalphas + a]));
-                    }
-                }
-            zkm_scratch d_apw(c, apw.size() * sizeof(gl_t)), d_tmp(c, nseg * (size_t)KECCAK_CONSTRAINT_PARTS * nalphas * size * sizeof(gl_t));
-            c->upload(d_apw.p, apw.data(), apw.size() * sizeof(gl_t));
-            dim3 gridp((unsigned)((size + 255) / 256), KECCAK_CONSTRAINT_PARTS, z);
-            if (nalphas == 1)
-                hipLaunchKernelGGL((k_quotient_keccak_parts<1>), gridp, block, 0, c->stream, trace->lde, lde_bits, d_alphas, wpow, gn, last, w_n, n_inv,
-                                   d_apw.as<gl_t>(), d_tmp.as<gl_t>(), trace_seg);
-            else
-                hipLaunchKernelGGL((k_quotient_keccak_parts<2>), gridp, block, 0, c->stream, trace->lde, lde_bits, d_alphas, wpow, gn, last, w_n, n_inv,
-                                   d_apw.as<gl_t>(), d_tmp.as<gl_t>(), trace_seg);
-            hipLaunchKernelGGL(k_sum_parts, dim3((unsigned)((nalphas * size + 255) / 256), 1, z), block, 0, c->stream, d_tmp.as<gl_t>(),
-                               (unsigned)KECCAK_CONSTRAINT_PARTS, nalphas * size, d_vals);
-        } else
-            zkm_with_table(table_id, [&](auto T) {
-                constexpr int TABLE = decltype(T)::value;
-                auto* const kernel = nalphas == 1 ? k_quotient<TABLE, 1> : k_quotient<TABLE, 2>;
-                hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, trace->lde, aux->lde, log_n, lde_bits, lookups, d_alphas, lookup_ch, wpow, gn, last,
-                                   w_n, n_inv, d_vals, trace_seg, aux_seg);
-            });
-        ZKM_HIP_CHECK(hipGetLastError());
-    }
-    {
-        zkm_prof_scope ps(c, "quotient_ctl");
-        dim3 grid((size + 255) / 256, 1, z), block(256);
-        // chunk plan: at most CHUNK helper checks per chunk, the closing checks with the last chunk of their Z.  A thread's work is a
-        // chain of column-combination evaluations whatever the table's height: on short tables (a launch cannot fill the GPU anyway)
-        // one helper check per chunk -- four times the workgroups, a quarter of the chain (KeccakSponge at 2^8 rows: 340 us per launch)
-        const bool short_table = size * nseg <= ((size_t)1 << 15);
-        const uint32_t CHUNK = short_table ? 1 : 4;
-        std::vector<ctl_chunk> plan;
-        uint32_t K = 0, hstart = 0;
-        std::vector<uint32_t> kend;
-        for (uint32_t zi = 0; zi < own.h_zs.size(); zi++) {
-            // helper checks exist only for real column sets (the benchmark's fake CTL data has helper columns but no sets)
-            const uint32_t np = own.h_zs[zi].num_helpers ? (own.h_zs[zi].ncolsets + 1) / 2 : 0;
-            uint32_t q = 0;
-            do {
-                const uint32_t q1 = np - q > CHUNK ? q + CHUNK : np;
-                const bool closing = q1 == np;
-                K += (q1 - q) + (closing ? 2 : 0);
-                plan.push_back(ctl_chunk{zi, hstart, q, q1, closing ? 1u : 0u, 0});
-                kend.push_back(K);
-                q = q1;
-            } while (q < np);
-            hstart += own.h_zs[zi].num_helpers;
-        }
-        for (size_t i = 0; i < plan.size(); i++) plan[i].tail = K - kend[i];
-        const bool chunked = plan.size() >= (short_table ? 2u : 8u) && size * nseg <= ((size_t)1 << 18) && !check;
-        if (!chunked) {
-            if (nalphas == 1)
-                hipLaunchKernelGGL((k_quotient_ctl<1>), grid, block, 0, c->stream, trace->lde, aux->lde, lde_bits, ctl, NL, d_alphas, wpow, gn, zh0, zh1,
-                                   last, w_n, n_inv, d_vals, trace_seg, aux_seg);
-            else
-                hipLaunchKernelGGL((k_quotient_ctl<2>), grid, block, 0, c->stream, trace->lde, aux->lde, lde_bits, ctl, NL, d_alphas, wpow, gn, zh0, zh1,
-                                   last, w_n, n_inv, d_vals, trace_seg, aux_seg);
-        } else {
-            zkm_scratch_list tmp(c);
-            ctl_chunk* d_plan = tmp.alloc<ctl_chunk>(plan.size() * sizeof(ctl_chunk));
-            gl_t* d_tmp = tmp.alloc<gl_t>(nseg * plan.size() * nalphas * size * sizeof(gl_t));
-            c->upload(d_plan, plan.data(), plan.size() * sizeof(ctl_chunk));
-            dim3 grid2((unsigned)((size + 255) / 256), (unsigned)plan.size(), z);
-            if (nalphas == 1) {
-                hipLaunchKernelGGL((k_quotient_ctl_chunk<1>), grid2, block, 0, c->stream, trace->lde, aux->lde, lde_bits, ctl, d_plan, NL, d_alphas, wpow,
-                                   gn, last, w_n, n_inv, d_tmp, trace_seg, aux_seg);
-                hipLaunchKernelGGL((k_quotient_ctl_sum<1>), grid, block, 0, c->stream, d_tmp, (uint32_t)plan.size(), K, d_alphas, zh0, zh1, size, d_vals);
-            } else {
-                hipLaunchKernelGGL((k_quotient_ctl_chunk<2>), grid2, block, 0, c->stream, trace->lde, aux->lde, lde_bits, ctl, d_plan, NL, d_alphas, wpow,
-                                   gn, last, w_n, n_inv, d_tmp, trace_seg, aux_seg);
-                hipLaunchKernelGGL((k_quotient_ctl_sum<2>), grid, block, 0, c->stream, d_tmp, (uint32_t)plan.size(), K, d_alphas, zh0, zh1, size, d_vals);
-            }
-            ZKM_HIP_CHECK(hipGetLastError());
-            // (no host sync: upload() has copied `plan` into the pinned ring -- or waited itself if it was too large for it -- and the
-            // blocks released here are only reused by later work on this stream)
-        }
-        ZKM_HIP_CHECK(hipGetLastError());
-    }
+    launch_table_constraints(c, table_id, trace, aux, lookups, lookup_ch, d_alphas, nalphas, q, d_vals);
+    launch_ctl_checks(c, trace, aux, own, NL, d_alphas, nalphas, q, d_vals);
     if (check) {
         ZKM_HIP_CHECK(hipMemcpyAsync(d_out, d_vals, nseg * nalphas * size * sizeof(gl_t), hipMemcpyDeviceToDevice, c->stream));
         return;
@@ -959,12 +978,6 @@ __global__ __launch_bounds__(256) void k_seg_combine(seg_batches p, size_t m, co
     f1[i] = f.c1;
 }
 
-struct fri_composite;
-// fin = sum over the batches (in order) of: fin * shift_b + (comp_b(X) - comp_b(z_b)) / (X - z_b), re-padded to n coefficients.
-// fin is written completely (no zero-fill needed).  Stacked: comps[s] = segment s's composites (pointers: segment 0's, the others'
-// comp_seg words further per segment), fin of segment s at f0 / f1 + s * 2 n.
-static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_composite>>& comps, size_t comp_seg, size_t n, gl_t* f0, gl_t* f1);
-
 // ------------------------------------------------------------------ K13: FRI fold
 // c'_j = sum_{i < arity} beta^i c_{arity j + i}   (reduce_with_powers per chunk)
 // A thread's 16 coefficients are one 128-byte line of each array: read with one 8-byte load per step they were fetched from HBM again
@@ -1097,13 +1110,6 @@ __global__ void k_gather_queries(gather_args g, const uint32_t* __restrict__ qs 
 }
 
 // ------------------------------------------------------------------ host helpers
-struct fri_layer {
-    gl_t* values = nullptr;   // [segment][2][len] bit-reversed
-    gl_t* digests = nullptr;  // [segment][dig_words]
-    std::vector<size_t> level_off;
-    size_t len = 0, dig_words = 0;
-    unsigned log_leaves = 0;
-};
 
 // ------------------------------------------------------------------ FRI: everything after the alpha-combination
 // One composite polynomial per FriBatchInfo (coefficients, F2 as two arrays), its opening point and the factor alpha^(#polys of
@@ -1115,6 +1121,9 @@ struct fri_composite {
     gl2_t point, shift;
 };
 
+// fin = sum over the batches (in order) of: fin * shift_b + (comp_b(X) - comp_b(z_b)) / (X - z_b), re-padded to n coefficients.
+// fin is written completely (no zero-fill needed).  Stacked: comps[s] = segment s's composites (pointers: segment 0's, the others'
+// comp_seg words further per segment), fin of segment s at f0 / f1 + s * 2 n.
 static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_composite>>& comps, size_t comp_seg, size_t n, gl_t* f0, gl_t* f1) {
     const size_t nseg = comps.size();
     if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("FRI: bad stack size");
@@ -1128,7 +1137,6 @@ static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_
     while (m.back() > FRI_SEG) m.push_back((m.back() + FRI_SEG - 1) / FRI_SEG);
     const size_t L = m.size();
     std::vector<seg_batches> lv(L);
-    std::vector<gl_t*> tot(L, nullptr), suf(L, nullptr);   // tot[l]: [segment][nb][2][m[l]] totals feeding level l (l >= 1); suf[l]: suffix values of level l
     zkm_scratch_list tmp(c);
     // points and weights of every level and segment: zw[l][s][b] = (z_b^(FRI_SEG^l), w_b), w_b = product of the shifts of the batches after b
     const size_t per_level = nseg * nb * 2;
@@ -1152,95 +1160,92 @@ static void divide_accumulate_all(zkm_ctx* c, const std::vector<std::vector<fri_
     lv[0].a_seg = comp_seg;
     lv[0].zw = d_zw;
     for (size_t l = 1; l < L; l++) {
-        tot[l] = tmp.alloc<gl_t>(nseg * 2 * nb * m[l] * sizeof(gl_t));
-        hipLaunchKernelGGL(k_seg_totals, dim3((unsigned)((m[l] + 63) / 64), nb, z), dim3(64), 0, c->stream, lv[l - 1], m[l - 1], tot[l]);
+        gl_t* const tot = tmp.alloc<gl_t>(nseg * 2 * nb * m[l] * sizeof(gl_t));   // [segment][nb][2][m[l]]: the totals that feed level l
+        hipLaunchKernelGGL(k_seg_totals, dim3((unsigned)((m[l] + 63) / 64), nb, z), dim3(64), 0, c->stream, lv[l - 1], m[l - 1], tot);
         lv[l] = lv[0];
         for (unsigned b = 0; b < nb; b++) {
-            lv[l].a0[b] = tot[l] + (2 * b) * m[l];
-            lv[l].a1[b] = tot[l] + (2 * b + 1) * m[l];
+            lv[l].a0[b] = tot + (2 * b) * m[l];
+            lv[l].a1[b] = tot + (2 * b + 1) * m[l];
         }
         lv[l].a_seg = 2 * nb * m[l];
         lv[l].zw = d_zw + l * per_level;
     }
     // top-down: suffix values of each level, then the weighted sum of the bottom level's
+    const gl_t* upper = nullptr;   // the suffix values of the level above
     for (size_t l = L; l-- > 0;) {
         const size_t nsegm = (m[l] + FRI_SEG - 1) / FRI_SEG;
-        const gl_t* upper = l + 1 < L ? suf[l + 1] : nullptr;
         const size_t nupper = l + 1 < L ? m[l + 1] : 0;
-        if (l == 0 && n >= c->fri_fused_division_min) {
-            const size_t lds = 4 * 64 * SEG_ROW * sizeof(gl_t);
-            static std::atomic<uint64_t> lds_ok{0};                 // (only a build with longer segments needs the raised limit -- ADVICE r04)
-            if (lds > 64 * 1024) ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_seg_scan_final, lds_ok));
-            hipLaunchKernelGGL(k_seg_scan_final, dim3((unsigned)((nsegm + 63) / 64), 1, z), dim3(64), lds, c->stream, lv[0], n, upper, nupper, f0, f1);
+        if (l == 0 && (n >= c->fri_fused_division_min || c->fri_scan_combine)) {
+            // bottom level in one launch (no suffix arrays in HBM): k_seg_scan_final from fri_fused_division_min coefficients on -- four tiles;
+            // else k_seg_scan_combine -- scan + weighted sum, two tiles per batch: 9,216 B per batch with segments of 8, eight batches
+            // (FRI_MAX_BATCHES) are 73,728 B, over the 64 KB a launch gets without asking.  The limit is raised once per
+            // device like k_fri_fold's (k_seg_scan_final: only a build with longer segments needs that -- ADVICE r04)
+            const bool fused = n >= c->fri_fused_division_min;
+            auto* const kernel = fused ? k_seg_scan_final : k_seg_scan_combine;
+            const size_t lds = (fused ? 4 : 2 * (size_t)nb) * 64 * SEG_ROW * sizeof(gl_t);
+            static std::atomic<uint64_t> lds_ok[2];
+            if (lds > 64 * 1024) ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)kernel, lds_ok[fused]));
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((nsegm + 63) / 64), 1, z), dim3(fused ? 64 : 64 * nb), lds, c->stream, lv[0], n, upper, nupper, f0, f1);
             break;
         }
-        if (l == 0 && c->fri_scan_combine) {   // bottom level: scan + weighted sum of the batches in one launch (no suffix arrays in HBM)
-            // two tiles per batch: 9,216 B per batch with segments of 8 -- eight batches (FRI_MAX_BATCHES) are 73,728 B, over the 64 KB a
-            // launch gets without asking; the limit is raised once per device like k_fri_fold's
-            const size_t lds = (size_t)2 * nb * 64 * SEG_ROW * sizeof(gl_t);
-            static std::atomic<uint64_t> sc_lds_ok{0};
-            if (lds > 64 * 1024) ZKM_HIP_CHECK(zkm_allow_big_lds(c, (const void*)k_seg_scan_combine, sc_lds_ok));
-            hipLaunchKernelGGL(k_seg_scan_combine, dim3((unsigned)((nsegm + 63) / 64), 1, z), dim3(64 * nb), lds, c->stream, lv[0], n, upper, nupper, f0,
-                               f1);
-            break;
-        }
-        suf[l] = tmp.alloc<gl_t>(nseg * 2 * nb * m[l] * sizeof(gl_t));
-        hipLaunchKernelGGL(k_seg_scan, dim3((unsigned)((nsegm + 63) / 64), nb, z), dim3(64), 0, c->stream, lv[l], m[l], upper, nupper, suf[l]);
-        if (l == 0) hipLaunchKernelGGL(k_seg_combine, dim3((unsigned)((n + 255) / 256), 1, z), dim3(256), 0, c->stream, lv[0], n, suf[0], f0, f1);
+        gl_t* const suf = tmp.alloc<gl_t>(nseg * 2 * nb * m[l] * sizeof(gl_t));
+        hipLaunchKernelGGL(k_seg_scan, dim3((unsigned)((nsegm + 63) / 64), nb, z), dim3(64), 0, c->stream, lv[l], m[l], upper, nupper, suf);
+        if (l == 0) hipLaunchKernelGGL(k_seg_combine, dim3((unsigned)((n + 255) / 256), 1, z), dim3(256), 0, c->stream, lv[0], n, suf, f0, f1);
+        upper = suf;
     }
     ZKM_HIP_CHECK(hipGetLastError());
 }   // (`tmp` goes back without a host sync: released blocks are only reused by later work on this stream)
 
-// Everything of a FRI proof after the alpha-combination, for a STACK of independent proofs of the same shape (one proof: vectors of
-// length 1): comps[s] = proof s's composites (pointers: proof 0's; proof s's are s * comp_seg words further), orc = the stacked initial
-// oracles, chs[s] = proof s's transcript, blobs[s] its blob, whose FRI fields lie where `part` says.  Every stage is ONE launch (or group of launches) for all
-// proofs, and every transcript round trip brings the words of all of them down together.
-static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, const std::vector<std::vector<fri_composite>>& comps, size_t comp_seg,
-                       const zkm_batch* const* orc, size_t noracles, const std::vector<zkm_challenger*>& chs, const zkm_fri_part& part,
-                       const std::vector<uint64_t*>& blobs) {
-    const zkm_query_round& round = part.round;
-    if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES || round.noracles != noracles) throw std::runtime_error("FRI: 1..8 initial oracles");
-    const unsigned L = (unsigned)round.L;
-    if (L > ZKM_FRI_GATHER_LAYERS) throw std::runtime_error("too many FRI layers");
-    const size_t nseg = comps.size();
-    if (nseg == 0 || nseg > ZKM_MAX_SEG || chs.size() != nseg || blobs.size() != nseg) throw std::runtime_error("FRI: bad stack size");
-    const unsigned z = (unsigned)nseg;
-    const size_t n = (size_t)1 << log_n, C4 = part.cap_words, nq = part.nq;
-    const unsigned lde_bits = log_n + cfg->rate_bits;
-    std::vector<fri_layer> layers(L);
-    zkm_scratch_list scratch(c);   // (the layers' blocks too)
-    gl_t* d_fin = scratch.alloc<gl_t>(nseg * 2 * n * sizeof(gl_t));  // final poly coefficients [segment][2][n]
-    divide_accumulate_all(c, comps, comp_seg, n, d_fin, d_fin + n);
+// A STACK of nseg = chs.size() independent proofs of the same shape in flight (one proof: vectors of length 1): chs[s] = proof s's
+// transcript, blobs[s] its blob.  Every stage below is ONE launch (or group of launches) for all proofs, and every transcript round
+// trip brings the words of all of them down together.
+struct proof_stack {
+    zkm_ctx* c;
+    const zkm_stark_config* cfg;
+    unsigned log_n;
+    const std::vector<zkm_challenger*>& chs;
+    const std::vector<uint64_t*>& blobs;
+    zkm_scratch_list scratch{c};
+    size_t nseg() const { return chs.size(); }
+    size_t n() const { return (size_t)1 << log_n; }
+};
 
-    // commit phase: coefficients stay in d_fin (length clen, implicitly zero-padded x4)
-    size_t clen = n;
-    unsigned clog = log_n;
+// ------------------------------------------------------------------ FRI: everything after the alpha-combination, in four stages; the
+// blobs' FRI fields lie where `part` says.  Shared by the STARK instance (prove_openings below, stark.rs:91-148) and zkm_fri_prove.
+// commit phase: LDE, Merkle tree, cap -> transcript, beta, fold, layer after layer; then the final polynomial.  d_coef: the
+// coefficients of the current layer, first d_fin (length clen, implicitly zero-padded x4)
+static std::vector<gather_layer> fri_commit_phase(proof_stack& f, const zkm_fri_part& part, gl_t* d_coef /* [segment][2][clen]: c0 array, then c1 */) {
+    zkm_ctx* const c = f.c;
+    const zkm_stark_config* const cfg = f.cfg;
+    const size_t nseg = f.nseg(), C4 = part.cap_words;
+    const unsigned z = (unsigned)nseg, arity = 1u << cfg->arity_bits;
+    std::vector<gather_layer> layers;
+    size_t clen = (size_t)1 << f.log_n;
+    unsigned clog = f.log_n;
     gl_t shift = GL_GENERATOR;
-    unsigned arity = 1u << cfg->arity_bits;
-    gl_t* d_coef = d_fin;       // [segment][2][clen]: c0 array, then c1
     std::vector<uint64_t> capbuf(nseg * C4);
-    for (unsigned l = 0; l < L; l++) {
-        fri_layer& fl = layers[l];
-        fl.len = clen << cfg->rate_bits;
-        fl.values = scratch.alloc<gl_t>(nseg * 2 * fl.len * sizeof(gl_t));
+    std::vector<size_t> level_off;
+    for (unsigned l = 0; l < part.round.L; l++) {
+        const size_t len = clen << cfg->rate_bits;
+        gl_t* const values = f.scratch.alloc<gl_t>(nseg * 2 * len * sizeof(gl_t));
         // values = coset_fft(shift) of the zero-padded coefficients, bit-reversed: two base-field columns per proof
         // (the coefficient arrays are contiguous: [c0 | c1] per proof, column stride clen)
-        zkm_lde_bitrev(c, d_coef, fl.values, 2 * nseg, clog, cfg->rate_bits, shift);
-        fl.log_leaves = clog + cfg->rate_bits - cfg->arity_bits;
-        size_t dwords = zkm_merkle_layout(fl.log_leaves, cfg->cap_height, fl.level_off);
-        fl.dig_words = dwords;
-        fl.digests = scratch.alloc<gl_t>(nseg * dwords * sizeof(gl_t));
-        zkm_launch_merkle_leaves_ext(c, fl.values, fl.values + fl.len, (size_t)1 << fl.log_leaves, arity, fl.digests, nseg, 2 * fl.len, dwords);
-        zkm_merkle_build_inner_cap(c, fl.digests, fl.level_off, fl.log_leaves, cfg->cap_height, capbuf.data(), nseg, dwords);
+        zkm_lde_bitrev(c, d_coef, values, 2 * nseg, clog, cfg->rate_bits, shift);
+        const unsigned log_leaves = clog + cfg->rate_bits - cfg->arity_bits;
+        const size_t dwords = zkm_merkle_layout(log_leaves, cfg->cap_height, level_off);
+        gl_t* const digests = f.scratch.alloc<gl_t>(nseg * dwords * sizeof(gl_t));
+        layers.push_back(gather_layer{values, values + len, digests, 2 * len, dwords});   // ([segment][2][len] values, bit-reversed)
+        zkm_launch_merkle_leaves_ext(c, values, values + len, (size_t)1 << log_leaves, arity, digests, nseg, 2 * len, dwords);
+        zkm_merkle_build_inner_cap(c, digests, level_off, log_leaves, cfg->cap_height, capbuf.data(), nseg, dwords);
         seg_gl2 betas{};
         for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t* capo = blobs[sg] + part.o_cap(l);
+            uint64_t* capo = f.blobs[sg] + part.o_cap(l);
             memcpy(capo, capbuf.data() + sg * C4, C4 * sizeof(uint64_t));
-            gl2_t beta = zkm_transcript_fri_beta(chs[sg], capo, C4);
+            gl2_t beta = zkm_transcript_fri_beta(f.chs[sg], capo, C4);
             betas.v[2 * sg] = beta.c0; betas.v[2 * sg + 1] = beta.c1;
         }
         size_t nout = clen >> cfg->arity_bits;
-        gl_t* d_new = scratch.alloc<gl_t>(nseg * 2 * nout * sizeof(gl_t));
+        gl_t* d_new = f.scratch.alloc<gl_t>(nseg * 2 * nout * sizeof(gl_t));
         {
             zkm_prof_scope ps(c, "fri_fold");
             const size_t lds = 2 * 64 * ((size_t)arity + 1) * sizeof(gl_t);
@@ -1256,314 +1261,350 @@ static void fri_finish(zkm_ctx* c, const zkm_stark_config* cfg, unsigned log_n, 
         shift = gl_pow(shift, arity);
     }
     if (clen != part.F) throw std::runtime_error("internal: final polynomial length mismatch");
-    {
-        std::vector<gl_t> f(nseg * 2 * clen);
-        c->download(f.data(), d_coef, nseg * 2 * clen * 8);
-        for (size_t sg = 0; sg < nseg; sg++) {
-            uint64_t* fp = blobs[sg] + part.o_final();
-            const gl_t* fs = f.data() + sg * 2 * clen;
-            for (size_t i = 0; i < clen; i++) { fp[2 * i] = fs[i]; fp[2 * i + 1] = fs[clen + i]; }
-            zkm_transcript_final_poly(chs[sg], fp, clen);
-        }
+    std::vector<gl_t> fin(nseg * 2 * clen);
+    c->download(fin.data(), d_coef, nseg * 2 * clen * 8);
+    for (size_t sg = 0; sg < nseg; sg++) {
+        uint64_t* fp = f.blobs[sg] + part.o_final();
+        const gl_t* fs = fin.data() + sg * 2 * clen;
+        for (size_t i = 0; i < clen; i++) { fp[2 * i] = fs[i]; fp[2 * i + 1] = fs[clen + i]; }
+        zkm_transcript_final_poly(f.chs[sg], fp, clen);
     }
-
-    // proof of work (App. A.9), smallest witness of every proof
-    {
-        std::vector<pow_state> sts(nseg);
-        seg_u32 pos{}, done{};
-        for (size_t sg = 0; sg < nseg; sg++) {
-            memcpy(sts[sg].s, chs[sg]->state, sizeof sts[sg].s);
-            for (uint32_t i = 0; i < chs[sg]->n_in; i++) sts[sg].s[i] = chs[sg]->in_buf[i];
-            pos.v[sg] = chs[sg]->n_in;
-        }
-        pow_state* d_sts = scratch.alloc<pow_state>(nseg * sizeof(pow_state));
-        c->upload(d_sts, sts.data(), nseg * sizeof(pow_state));
-        unsigned long long* d_best = c->pow_best();      // ZKM_MAX_SEG words, all ones between searches (the kernel leaves them that way)
-        std::vector<unsigned long long> best(nseg, ~0ULL), got(nseg);
-        // 2^pow_round_log candidates per round and proof (17 for a proof alone: two waves per SIMD -- a wave alone issues at half the
-        // SIMD's rate, so the round is barely longer than with one, and it holds the hit with probability 0.86 instead of 0.63 at 16
-        // bits; the searches of a stack share the machine: the round of each shrinks with their number, down to 2^12, so that the
-        // stack's round is still one launch-filling set of waves and few candidates are tried beyond the round of a proof's first hit),
-        // up to 2^6 rounds per launch (a launch without a hit: probability e^-128 for a proof alone)
-        unsigned round_log = c->pow_round_log;
-        for (size_t k = 1; k < nseg && round_log > 12; k <<= 1) round_log--;
-        const uint64_t stride = (uint64_t)1 << round_log, span = stride << 6;
-        size_t open = nseg;
-        for (uint64_t base = 0; open; base += span) {
-            if (base > ((uint64_t)1 << 40)) throw std::runtime_error("Proof of work failed. This is highly unlikely!");
-            uint64_t *host_slot, *flag;
-            unsigned* counter;
-            const uint64_t seq = c->xfer_begin(8 * nseg, &host_slot, &flag, &counter);
-            {
-                zkm_prof_scope ps(c, "fri_pow_search");
-                hipLaunchKernelGGL(k_pow_search, dim3(stride / 256, z), dim3(256), 0, c->stream, d_sts, pos, done, cfg->pow_bits, base, base + span,
-                                   d_best, counter, host_slot, flag, seq);
-                ZKM_HIP_CHECK(hipGetLastError());
-            }
-            c->xfer_finish(seq, got.data(), 8 * nseg);
-            for (size_t sg = 0; sg < nseg; sg++)
-                if (!done.v[sg] && got[sg] != ~0ULL) { best[sg] = got[sg]; done.v[sg] = 1; open--; }
-        }
-        for (size_t sg = 0; sg < nseg; sg++) {
-            blobs[sg][part.o_pow()] = best[sg];
-            if (!zkm_transcript_pow(chs[sg], best[sg], cfg->pow_bits)) throw std::runtime_error("internal: proof-of-work response check failed");
-        }
-    }
-
-    // query rounds
-    {
-        if (nq > ZKM_FRI_MAX_QUERIES || lde_bits > 32) throw std::runtime_error("FRI: at most 128 query rounds on domains of at most 2^32 points");
-        std::vector<uint32_t> qs(nseg * nq);
-        for (size_t sg = 0; sg < nseg; sg++) zkm_transcript_query_indices(chs[sg], nq, lde_bits, qs.data() + sg * nq);
-        uint32_t* d_qs = scratch.alloc<uint32_t>(qs.size() * sizeof(uint32_t));
-        c->upload(d_qs, qs.data(), qs.size() * sizeof(uint32_t));
-        gather_args ga{};
-        ga.round = round;
-        for (size_t k = 0; k < noracles; k++) {
-            if (orc[k]->lde_bits() != lde_bits || orc[k]->nseg != nseg || orc[k]->ncols != round.cols[k])
-                throw std::runtime_error("internal: oracle of another shape in the query gather");
-            ga.o[k] = {orc[k]->lde, orc[k]->digests, orc[k]->lde_seg(), orc[k]->dig_words};
-        }
-        for (unsigned l = 0; l < L; l++)
-            ga.l[l] = {layers[l].values, layers[l].values + layers[l].len, layers[l].digests, 2 * layers[l].len, layers[l].dig_words};
-        const size_t qwords = nq * round.words();
-        gl_t* d_q = scratch.alloc<gl_t>(nseg * qwords * 8);
-        {
-            zkm_prof_scope ps(c, "fri_gather_queries");
-            hipLaunchKernelGGL(k_gather_queries, dim3(nq, z), dim3(256), 0, c->stream, ga, d_qs, d_q);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        if (nseg == 1) {
-            c->download(blobs[0] + part.o_queries(), d_q, qwords * 8);
-        } else {
-            std::vector<gl_t> all(nseg * qwords);
-            c->download(all.data(), d_q, nseg * qwords * 8);
-            for (size_t sg = 0; sg < nseg; sg++) memcpy(blobs[sg] + part.o_queries(), all.data() + sg * qwords, qwords * 8);
-        }
-    }
-
+    return layers;
 }
 
-// prove_single_table for a STACK of nseg = chs.size() independent proofs of the same table at the same height (one proof: vectors of
-// length 1, the single-table entry points): the commitments are stacked batches (zkm_internal.h), zs = nseg lists of CtlZData,
-// lookup_challenges = nseg x num_challenges, chs[s] / proofs[s] = proof s's transcript and output blob.  Every stage is one launch (or
-// group of launches) for all proofs; the transcripts advance side by side on the host between the round trips.
-static void prove_single_table(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, const uint64_t* trace, size_t W, unsigned log_n,
-                               const zkm_batch* trace_batch, const uint64_t* aux, size_t A_ctl, const zkm_ctl_table* ctl_table,
-                               const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t Z, const uint64_t* lookup_challenges,
-                               const std::vector<zkm_challenger*>& chs, const std::vector<uint64_t*>& proofs, const zkm_batch* aux_batch_in = nullptr,
-                               const zkm_batch* quot_batch_in = nullptr) {
-    // openings-only mode (zkm_prove_openings, BASELINE config 4): the three commitments exist already; the transcript
-    // is compact -> zeta -> openings -> prove_openings.  aux_given (zkm_prove_with_traces): the auxiliary commitment was built ahead of
-    // the transcript (it only depends on the CTL challenges); everything from observing its cap on runs here.
-    const bool openings_only = quot_batch_in != nullptr;
-    const bool aux_given = aux_batch_in != nullptr && !openings_only;
-    const size_t nseg = chs.size();
-    if (nseg == 0 || nseg > ZKM_MAX_SEG || proofs.size() != nseg) throw std::runtime_error("prove_single_table: bad stack size");
-    if (nseg > 1 && !(aux_given && trace_batch)) throw std::runtime_error("internal: a stack of proofs needs its stacked commitments");
-    validate_config(cfg, log_n);  // before zkm_num_lookup_columns reads it; zkm_blob_describe checks again
-    // the table's own lookup helper columns come first among the auxiliary polynomials (prover.rs:467-508)
-    const size_t NL = openings_only ? 0 : zkm_num_lookup_columns(table_id, cfg);
-    if (NL && !lookup_challenges) throw std::runtime_error("this table has lookups: lookup challenges are required");
-    if (NL && !trace && !aux_given) throw std::runtime_error("this table has lookups: the trace values are required to build their helper columns");
-    if (!NL) lookup_challenges = nullptr;
-    const size_t A = NL + A_ctl;
-    const zkm_blob_desc y = zkm_blob_describe(cfg, log_n, W, A, Z);
-    if (y.L > ZKM_FRI_GATHER_LAYERS) throw std::runtime_error("too many FRI layers");
-    size_t n = (size_t)1 << log_n;
-    if (openings_only) {
-        if (Z > A) throw std::runtime_error("zkm_prove_openings: more CTL Zs than auxiliary polynomials");
-    } else {
-        size_t ctl_helpers = 0;
-        for (size_t i = 0; i < Z; i++) ctl_helpers += zs[i].num_helpers;
-        if (ctl_helpers + Z != A_ctl) throw std::runtime_error("No CTL? aux column count does not match the CTL description");
-    }
-    if (A_ctl == 0) throw std::runtime_error("No CTL? aux column count does not match the CTL description");  // prover.rs:509
-    const size_t total_helpers = A - Z;  // index of the first CTL Z among the auxiliary polynomials
-    ctl_dev_owner own;
-    if (!openings_only) own.upload(c, ctl_table, zs, colset_ids, Z, false, W, nseg);
-    if (ctl_table && !openings_only)
-        for (size_t i = 0; i < ctl_table->nterms; i++)
-            if (ctl_table->term_col[i] >= W) throw std::runtime_error("CTL description: trace column index out of range");
-
-    // (the query rounds -- nine tenths of the blob, 2 MB for the Keccak table -- are written in full by the download at the end of
-    // fri_finish: zeroing them here was 0.2 ms of host time per segment in front of the table's first launch)
-    for (uint64_t* proof : proofs) {
-        memset(proof, 0, y.fri().o_queries() * sizeof(uint64_t));
-        zkm_blob_header_write(proof, y);
-    }
-
-    zkm_scratch_list scratch(c);
-    zkm_batch_ptr own_trace, ab, qb;   // (freed before the scratch goes back: zkm_batch_free waits for the stream)
-    const zkm_batch* tb = trace_batch;
-    if (!tb) {
-        own_trace = zkm_batch_new(c, W, 1, log_n, cfg->rate_bits, cfg->cap_height);
-        zkm_prof_scope st(c, "stage/compute trace commitment");  // prover.rs:146-163 (done by the caller in the reference)
-        zkm_batch_build(own_trace.get(), trace, true);
-        tb = own_trace.get();
-    }
-    if (tb->ncols != W || tb->log_n != log_n || tb->rate_bits != cfg->rate_bits || tb->cap_height != cfg->cap_height || tb->nseg != nseg)
-        throw std::runtime_error("trace commitment does not match the table shape / config");
-
-    const size_t C4 = y.cap_words();
-    auto put_cap = [&](size_t sg, unsigned tree, const zkm_batch* b) { memcpy(proofs[sg] + y.o_cap(tree), b->cap.data() + sg * C4, C4 * 8); };
+// proof of work (App. A.9), smallest witness of every proof
+static void fri_proof_of_work(proof_stack& f, const zkm_fri_part& part) {
+    zkm_ctx* const c = f.c;
+    const size_t nseg = f.nseg();
+    std::vector<pow_state> sts(nseg);
+    seg_u32 pos{}, done{};
     for (size_t sg = 0; sg < nseg; sg++) {
-        zkm_challenger_compact(chs[sg], proofs[sg] + y.o_init());  // :466
-        put_cap(sg, 0, tb);
+        memcpy(sts[sg].s, f.chs[sg]->state, sizeof sts[sg].s);
+        for (uint32_t i = 0; i < f.chs[sg]->n_in; i++) sts[sg].s[i] = f.chs[sg]->in_buf[i];
+        pos.v[sg] = f.chs[sg]->n_in;
     }
-    const zkm_batch *abp = aux_batch_in, *qbp = quot_batch_in;
-    if (aux_given) {
-        if (abp->ncols != A || abp->log_n != log_n || abp->rate_bits != cfg->rate_bits || abp->cap_height != cfg->cap_height || abp->nseg != nseg)
-            throw std::runtime_error("auxiliary commitment does not match the table shape / config");
-    } else if (!openings_only) {
-        // auxiliary commitment :511-522
-        ab = zkm_batch_new(c, A, 1, log_n, cfg->rate_bits, cfg->cap_height);
-        if (NL) {
-            // "compute lookup helper columns" :475-493, then the CTL columns behind them
-            auto st = std::make_unique<zkm_prof_scope>(c, "stage/compute lookup helper columns");
-            gl_t* d_all = scratch.alloc<gl_t>(A * n * sizeof(gl_t));
-            const gl_t* d_trace = trace;
-            if (!zkm_is_device_ptr(trace)) {
-                gl_t* d = scratch.alloc<gl_t>(W * n * sizeof(gl_t));
-                c->upload(d, trace, W * n * sizeof(gl_t));
-                zkm_launch_canon(c, d, W * n);   // (host words may be any representative; the lookup kernels want canonical ones)
-                d_trace = d;
-            }
-            zkm_table_lookup_columns_device(c, table_id, lookup_challenges, cfg->num_challenges, d_trace, n, d_all);
-            ZKM_HIP_CHECK(hipMemcpyAsync(d_all + NL * n, aux, A_ctl * n * sizeof(gl_t), hipMemcpyDefault, c->stream));
-            st.reset();
-            zkm_prof_scope st2(c, "stage/compute auxiliary polynomials commitment");  // :511-522
-            zkm_batch_build(ab.get(), d_all, true);
-        } else {
-            zkm_prof_scope st2(c, "stage/compute auxiliary polynomials commitment");
-            zkm_batch_build(ab.get(), aux, true);
-        }
-        abp = ab.get();
-    }
-    if (!openings_only) {
-        std::vector<gl_t> alphas(nseg * cfg->num_challenges);
-        for (size_t sg = 0; sg < nseg; sg++) {
-            put_cap(sg, 1, abp);
-            zkm_transcript_alphas(chs[sg], y, proofs[sg], cfg->num_challenges, alphas.data() + sg * cfg->num_challenges);
-        }
-
-        // quotient :543-587
-        gl_t* d_quot = scratch.alloc<gl_t>(nseg * cfg->num_challenges * 2 * n * sizeof(gl_t));
+    pow_state* d_sts = f.scratch.alloc<pow_state>(nseg * sizeof(pow_state));
+    c->upload(d_sts, sts.data(), nseg * sizeof(pow_state));
+    unsigned long long* d_best = c->pow_best();      // ZKM_MAX_SEG words, all ones between searches (the kernel leaves them that way)
+    std::vector<unsigned long long> best(nseg, ~0ULL), got(nseg);
+    // 2^pow_round_log candidates per round and proof (17 for a proof alone: two waves per SIMD -- a wave alone issues at half the
+    // SIMD's rate, so the round is barely longer than with one, and it holds the hit with probability 0.86 instead of 0.63 at 16
+    // bits; the searches of a stack share the machine: the round of each shrinks with their number, down to 2^12, so that the
+    // stack's round is still one launch-filling set of waves and few candidates are tried beyond the round of a proof's first hit),
+    // up to 2^6 rounds per launch (a launch without a hit: probability e^-128 for a proof alone)
+    unsigned round_log = c->pow_round_log;
+    for (size_t k = 1; k < nseg && round_log > 12; k <<= 1) round_log--;
+    const uint64_t stride = (uint64_t)1 << round_log, span = stride << 6;
+    size_t open = nseg;
+    for (uint64_t base = 0; open; base += span) {
+        if (base > ((uint64_t)1 << 40)) throw std::runtime_error("Proof of work failed. This is highly unlikely!");
+        uint64_t *host_slot, *flag;
+        unsigned* counter;
+        const uint64_t seq = c->xfer_begin(8 * nseg, &host_slot, &flag, &counter);
         {
-            zkm_prof_scope st(c, "stage/compute quotient polys");  // :543-559
-            quotient_device(c, table_id, tb, abp, own, lookup_challenges, alphas.data(), cfg->num_challenges, d_quot);
+            zkm_prof_scope ps(c, "fri_pow_search");
+            hipLaunchKernelGGL(k_pow_search, dim3(stride / 256, (unsigned)nseg), dim3(256), 0, c->stream, d_sts, pos, done, f.cfg->pow_bits, base, base + span,
+                               d_best, counter, host_slot, flag, seq);
+            ZKM_HIP_CHECK(hipGetLastError());
         }
-        qb = zkm_batch_new(c, y.Q, nseg, log_n, cfg->rate_bits, cfg->cap_height);
-        {
-            zkm_prof_scope st(c, "stage/compute quotient commitment");  // :576-587
-            zkm_batch_build(qb.get(), d_quot, false);  // chunks [q0_lo, q0_hi, q1_lo, q1_hi] == d_quot viewed as Q columns of n, proof after proof
-        }
-        qbp = qb.get();
-    } else {
-        for (const zkm_batch* b : {abp, qbp})
-            if (!b || b->log_n != log_n || b->rate_bits != cfg->rate_bits || b->cap_height != cfg->cap_height || b->nseg != nseg)
-                throw std::runtime_error("zkm_prove_openings: commitments do not match the table shape / config");
-        if (abp->ncols != A || qbp->ncols != y.Q) throw std::runtime_error("zkm_prove_openings: unexpected number of polynomials");
-        for (size_t sg = 0; sg < nseg; sg++) put_cap(sg, 1, abp);
+        c->xfer_finish(seq, got.data(), 8 * nseg);
+        for (size_t sg = 0; sg < nseg; sg++)
+            if (!done.v[sg] && got[sg] != ~0ULL) { best[sg] = got[sg]; done.v[sg] = 1; open--; }
     }
-
-    std::vector<gl2_t> zeta(nseg), zeta_next(nseg);
-    gl_t g = gl_root_of_unity(log_n);
     for (size_t sg = 0; sg < nseg; sg++) {
-        put_cap(sg, 2, qbp);   // (openings-only: the transcript goes from the compacted state straight to zeta)
-        zeta[sg] = openings_only ? zkm_challenger_get_ext(chs[sg]) : zkm_transcript_zeta(chs[sg], y, proofs[sg]);
-        if (gl2_eq(gl2_exp_pow2(zeta[sg], log_n), gl2_t{1, 0})) throw std::runtime_error("Opening point is in the subgroup.");  // :596-599
-        zeta_next[sg] = gl2_scalar_mul(zeta[sg], g);
+        f.blobs[sg][part.o_pow()] = best[sg];
+        if (!zkm_transcript_pow(f.chs[sg], best[sg], f.cfg->pow_bits)) throw std::runtime_error("internal: proof-of-work response check failed");
     }
+}
 
-    // openings proof.rs:299-334
+// query rounds: the indices from the transcripts, one gather over the initial oracles and the layers, one download
+static void fri_query_rounds(proof_stack& f, const zkm_fri_part& part, const std::vector<gather_layer>& layers, const zkm_batch* const* orc,
+                             size_t noracles) {
+    zkm_ctx* const c = f.c;
+    const zkm_query_round& round = part.round;
+    const size_t nseg = f.nseg(), nq = part.nq;
+    const unsigned lde_bits = f.log_n + f.cfg->rate_bits;
+    std::vector<uint32_t> qs(nseg * nq);
+    for (size_t sg = 0; sg < nseg; sg++) zkm_transcript_query_indices(f.chs[sg], nq, lde_bits, qs.data() + sg * nq);
+    uint32_t* d_qs = f.scratch.alloc<uint32_t>(qs.size() * sizeof(uint32_t));
+    c->upload(d_qs, qs.data(), qs.size() * sizeof(uint32_t));
+    gather_args ga{};
+    ga.round = round;
+    for (size_t k = 0; k < noracles; k++) ga.o[k] = {orc[k]->lde, orc[k]->digests, orc[k]->lde_seg(), orc[k]->dig_words};
+    std::copy(layers.begin(), layers.end(), ga.l);
+    const size_t qwords = nq * round.words();
+    gl_t* d_q = f.scratch.alloc<gl_t>(nseg * qwords * 8);
     {
-        zkm_prof_scope st(c, "stage/openings (StarkOpeningSet::new)");  // proof.rs:299-334, between two timed! scopes in the reference
-        auto ev = eval_batches(c, {tb, abp, qbp}, zeta.data(), zeta_next.data());
-        for (size_t sg = 0; sg < nseg; sg++) {
-            const auto o = y.openings(proofs[sg]);
-            const auto &tv = ev[sg][0], &av = ev[sg][1], &qv = ev[sg][2];
-            for (size_t i = 0; i < W; i++) {
-                o.local[2 * i] = tv[i].at_z0.c0; o.local[2 * i + 1] = tv[i].at_z0.c1;
-                o.next[2 * i] = tv[i].at_z1.c0; o.next[2 * i + 1] = tv[i].at_z1.c1;
-            }
-            for (size_t i = 0; i < A; i++) {
-                o.aux[2 * i] = av[i].at_z0.c0; o.aux[2 * i + 1] = av[i].at_z0.c1;
-                o.aux_next[2 * i] = av[i].at_z1.c0; o.aux_next[2 * i + 1] = av[i].at_z1.c1;
-                if (i >= total_helpers) o.ctl_zs_first[i - total_helpers] = av[i].at_one;
-            }
-            for (size_t i = 0; i < y.Q; i++) { o.quotient[2 * i] = qv[i].at_z0.c0; o.quotient[2 * i + 1] = qv[i].at_z0.c1; }
+        zkm_prof_scope ps(c, "fri_gather_queries");
+        hipLaunchKernelGGL(k_gather_queries, dim3(nq, (unsigned)nseg), dim3(256), 0, c->stream, ga, d_qs, d_q);
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+    if (nseg == 1) {
+        c->download(f.blobs[0] + part.o_queries(), d_q, qwords * 8);
+    } else {
+        std::vector<gl_t> all(nseg * qwords);
+        c->download(all.data(), d_q, nseg * qwords * 8);
+        for (size_t sg = 0; sg < nseg; sg++) memcpy(f.blobs[sg] + part.o_queries(), all.data() + sg * qwords, qwords * 8);
+    }
+}
+
+// ---- what the STARK instance and zkm_fri_prove share around their combination kernels
+// out[2 j], out[2 j + 1] = alpha^j for j <= np (alpha^np: the shift of a batch of np polynomials)
+static void alpha_powers(gl2_t alpha, size_t np, gl_t* out) {
+    gl2_t p{1, 0};
+    for (size_t j = 0; j <= np; j++) { out[2 * j] = p.c0; out[2 * j + 1] = p.c1; p = gl2_mul(p, alpha); }
+}
+// From the composites to the finished proofs.  d_comp: [proof][batch][2][n] words as the combination left them, comps[s][b] = the point
+// and shift of proof s's batch b (its pointers are filled in here); orc = the stacked initial oracles.  Everything the gather reads by
+// index is checked here, before the first launch.
+static void fri_finish(proof_stack& f, const zkm_fri_part& part, unsigned coeff_s1, gl_t* d_comp, std::vector<std::vector<fri_composite>> comps,
+                       const zkm_batch* const* orc, size_t noracles) {
+    const zkm_query_round& round = part.round;
+    if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES || round.noracles != noracles) throw std::runtime_error("FRI: 1..8 initial oracles");
+    if (round.L > ZKM_FRI_GATHER_LAYERS) throw std::runtime_error("too many FRI layers");
+    const size_t nseg = comps.size(), n = f.n(), nb = comps.at(0).size();
+    if (nseg == 0 || nseg > ZKM_MAX_SEG || f.nseg() != nseg || f.blobs.size() != nseg) throw std::runtime_error("FRI: bad stack size");
+    const unsigned lde_bits = f.log_n + f.cfg->rate_bits;
+    if (part.nq > ZKM_FRI_MAX_QUERIES || lde_bits > 32) throw std::runtime_error("FRI: at most 128 query rounds on domains of at most 2^32 points");
+    for (size_t k = 0; k < noracles; k++)
+        if (orc[k]->lde_bits() != lde_bits || orc[k]->nseg != nseg || orc[k]->ncols != round.cols[k])
+            throw std::runtime_error("internal: oracle of another shape in the query gather");
+    if (coeff_s1) {
+        // the combination is position-wise, so the composites come out in the oracles' coefficient layout (a function of the height: the
+        // same for every oracle); the division by (X - point) walks exponents in order
+        gl_t* d_nat = f.scratch.alloc<gl_t>(nseg * 2 * nb * n * sizeof(gl_t));
+        zkm_coeff_layout_convert(f.c, d_comp, n, d_nat, n, 2 * nb * nseg, f.log_n, /*to_natural=*/true);
+        d_comp = d_nat;
+    }
+    for (auto& proof : comps)   // (proof 0's pointers; proof s's are s * 2 nb n words further)
+        for (size_t b = 0; b < proof.size(); b++) { proof[b].c0 = d_comp + 2 * b * n; proof[b].c1 = d_comp + (2 * b + 1) * n; }
+    gl_t* d_fin = f.scratch.alloc<gl_t>(nseg * 2 * n * sizeof(gl_t));  // final poly coefficients [segment][2][n]
+    divide_accumulate_all(f.c, comps, 2 * nb * n, n, d_fin, d_fin + n);
+    const std::vector<gather_layer> layers = fri_commit_phase(f, part, d_fin);
+    fri_proof_of_work(f, part);
+    fri_query_rounds(f, part, layers, orc, noracles);
+}
+
+// ------------------------------------------------------------------ prove_single_table (prover.rs:441-641)
+// A STACK of nseg = chs.size() independent proofs of one table at one height on its way down the reference's line
+//   commit trace -> commit aux -> alphas, quotient, commit quotient -> zeta, openings -> FRI
+// (one proof: vectors of length 1).  The oracles are stacked batches (zkm_internal.h) -- the caller's, or built here and then owned
+// here; chs[s] / blobs[s] = proof s's transcript and output blob.  Each stage below is one launch (or group of launches) for all
+// proofs; the transcripts advance side by side on the host between the round trips.  Three drivers enter the line: from values
+// (zkm_prove_single_table[_ctl]), from the trace and auxiliary commitments (zkm_prove_table_from_commitments: zkm_prove_single_tables
+// and ctl.hip) and from all three commitments (zkm_prove_openings).
+struct table_proof : proof_stack {
+    zkm_blob_desc y;
+    const zkm_batch *trace = nullptr, *aux = nullptr, *quot = nullptr;
+    zkm_batch_ptr own_trace, own_aux, own_quot;   // (members: freed before the base's scratch goes back -- zkm_batch_free waits for the stream)
+    std::vector<gl2_t> zeta = std::vector<gl2_t>(chs.size()), zeta_next = zeta;   // one opening point per proof, and g times it
+};
+
+// does the batch hold `ncols` polynomials per proof of a stack of `nseg`, at this height and with the config's rate and cap?
+static void require_batch(const zkm_batch* b, size_t ncols, unsigned log_n, const zkm_stark_config* cfg, size_t nseg, const char* or_else) {
+    if (!b || b->ncols != ncols || b->log_n != log_n || b->rate_bits != cfg->rate_bits || b->cap_height != cfg->cap_height || b->nseg != nseg)
+        throw std::runtime_error(or_else);
+}
+// What the drivers that hold a CTL description check before they touch a blob or a transcript; returns the blobs' description.  The
+// table's own lookup helper columns come first among the auxiliary polynomials (prover.rs:467-508): A - A_ctl of them.
+static zkm_blob_desc describe_table_proof(int table_id, const zkm_stark_config* cfg, size_t W, unsigned log_n, size_t A_ctl, const zkm_ctl_z* zs, size_t Z,
+                                          const uint64_t* lookup_challenges) {
+    validate_config(cfg, log_n);  // before zkm_num_lookup_columns reads it; zkm_blob_describe checks again
+    const size_t NL = zkm_num_lookup_columns(table_id, cfg);
+    if (NL && !lookup_challenges) throw std::runtime_error("this table has lookups: lookup challenges are required");
+    const zkm_blob_desc y = zkm_blob_describe(cfg, log_n, W, NL + A_ctl, Z);
+    if (y.L > ZKM_FRI_GATHER_LAYERS) throw std::runtime_error("too many FRI layers");
+    size_t ctl_helpers = 0;
+    for (size_t i = 0; i < Z; i++) ctl_helpers += zs[i].num_helpers;
+    if (ctl_helpers + Z != A_ctl || A_ctl == 0) throw std::runtime_error("No CTL? aux column count does not match the CTL description");  // prover.rs:509
+    return y;
+}
+// the device copy of the CTL description (every trace column it names is checked against W)
+static void upload_ctl(table_proof& p, ctl_dev_owner& own, const zkm_ctl_table* ctl_table, const zkm_ctl_z* zs, const uint32_t* colset_ids) {
+    own.upload(p.c, ctl_table, zs, colset_ids, p.y.Z, false, p.y.W, p.nseg());
+    if (ctl_table)
+        for (size_t i = 0; i < ctl_table->nterms; i++)
+            if (ctl_table->term_col[i] >= p.y.W) throw std::runtime_error("CTL description: trace column index out of range");
+}
+
+// the blobs' heads, the transcripts' start (:466) and the trace caps.  (The query rounds -- nine tenths of the blob, 2 MB for the Keccak table -- are
+// written in full by the download at the end of fri_finish: zeroing them here was 0.2 ms of host time per segment in front of the
+// table's first launch)
+static void put_caps(table_proof& p, unsigned tree, const zkm_batch* b) {
+    const size_t C4 = p.y.cap_words();
+    for (size_t sg = 0; sg < p.nseg(); sg++) memcpy(p.blobs[sg] + p.y.o_cap(tree), b->cap.data() + sg * C4, C4 * 8);
+}
+static void begin_blobs(table_proof& p) {
+    for (size_t sg = 0; sg < p.nseg(); sg++) {
+        memset(p.blobs[sg], 0, p.y.fri().o_queries() * sizeof(uint64_t));
+        zkm_blob_header_write(p.blobs[sg], p.y);
+        zkm_challenger_compact(p.chs[sg], p.blobs[sg] + p.y.o_init());
+    }
+    put_caps(p, 0, p.trace);
+}
+
+// a commitment to values under the reference's stage scope: one matrix, or one per proof of a stack (device matrices are transformed
+// where they lie)
+static zkm_batch_ptr commit_values(zkm_ctx* c, const zkm_stark_config* cfg, const char* stage, size_t ncols, unsigned log_n, const uint64_t* const* srcs,
+                                   size_t nseg) {
+    zkm_batch_ptr b = zkm_batch_new(c, ncols, nseg, log_n, cfg->rate_bits, cfg->cap_height);
+    zkm_prof_scope st(c, stage);
+    if (nseg == 1) zkm_batch_build(b.get(), srcs[0], true);
+    else zkm_batch_build(b.get(), nullptr, true, nullptr, nullptr, srcs);
+    return b;
+}
+
+// ---- stage: the trace commitment from values (prover.rs:146-163, done by the caller in the reference)
+static void commit_trace(table_proof& p, const uint64_t* trace) {
+    p.own_trace = commit_values(p.c, p.cfg, "stage/compute trace commitment", p.y.W, p.log_n, &trace, 1);
+    p.trace = p.own_trace.get();
+}
+
+// ---- stage: the auxiliary commitment (:511-522) from the CTL columns `aux` (host or device), behind the NL helper columns of the
+// table's own lookups, which are built here from the trace values
+static void commit_aux(table_proof& p, int table_id, const uint64_t* trace, const uint64_t* aux, const uint64_t* lookup_challenges) {
+    zkm_ctx* const c = p.c;
+    const size_t n = p.n(), W = p.y.W, A = p.y.A, NL = zkm_num_lookup_columns(table_id, p.cfg);
+    if (NL) {
+        // "compute lookup helper columns" :475-493, then the CTL columns behind them
+        zkm_prof_scope st(c, "stage/compute lookup helper columns");
+        gl_t* d_all = p.scratch.alloc<gl_t>(A * n * sizeof(gl_t));
+        const gl_t* d_trace = trace;
+        if (!zkm_is_device_ptr(trace)) {
+            gl_t* d = p.scratch.alloc<gl_t>(W * n * sizeof(gl_t));
+            c->upload(d, trace, W * n * sizeof(gl_t));
+            zkm_launch_canon(c, d, W * n);   // (host words may be any representative; the lookup kernels want canonical ones)
+            d_trace = d;
         }
+        zkm_table_lookup_columns_device(c, table_id, lookup_challenges, p.cfg->num_challenges, d_trace, n, d_all);
+        ZKM_HIP_CHECK(hipMemcpyAsync(d_all + NL * n, aux, (A - NL) * n * sizeof(gl_t), hipMemcpyDefault, c->stream));
+        aux = d_all;
     }
-    // ---- prove_openings (App. A.8)
-    zkm_prof_scope st_fri(c, "stage/compute openings proof");  // prover.rs:618-628
-    const size_t np0 = W + A + y.Q, np1 = W + A, np2 = Z, apow_seg = 2 * (np0 + 1);
+    p.own_aux = commit_values(c, p.cfg, "stage/compute auxiliary polynomials commitment", A, p.log_n, &aux, 1);  // :511-522
+    p.aux = p.own_aux.get();
+}
+
+// ---- stage: auxiliary caps -> alphas (:525-527), the quotient polynomials (:543-559) and their commitment (:576-587)
+static void commit_quotient(table_proof& p, int table_id, const ctl_dev_owner& own, const uint64_t* lookup_challenges) {
+    zkm_ctx* const c = p.c;
+    const size_t nseg = p.nseg(), nch = p.cfg->num_challenges;
+    put_caps(p, 1, p.aux);
+    std::vector<gl_t> alphas(nseg * nch);
+    for (size_t sg = 0; sg < nseg; sg++) zkm_transcript_alphas(p.chs[sg], p.y, p.blobs[sg], p.cfg->num_challenges, alphas.data() + sg * nch);
+    gl_t* d_quot = p.scratch.alloc<gl_t>(nseg * nch * 2 * p.n() * sizeof(gl_t));
+    {
+        zkm_prof_scope st(c, "stage/compute quotient polys");  // :543-559
+        quotient_device(c, table_id, p.trace, p.aux, own, lookup_challenges, alphas.data(), nch, d_quot);
+    }
+    p.own_quot = zkm_batch_new(c, p.y.Q, nseg, p.log_n, p.cfg->rate_bits, p.cfg->cap_height);
+    zkm_prof_scope st(c, "stage/compute quotient commitment");  // :576-587
+    zkm_batch_build(p.own_quot.get(), d_quot, false);  // chunks [q0_lo, q0_hi, q1_lo, q1_hi] == d_quot viewed as Q columns of n, proof after proof
+    p.quot = p.own_quot.get();
+}
+
+// ---- stage: the opening points.  On the line the quotient caps are observed first (:589-591); a proof from three commitments draws
+// zeta straight from its compacted transcript.
+static void set_zeta(table_proof& p, size_t sg, gl2_t zeta) {
+    if (gl2_eq(gl2_exp_pow2(zeta, p.log_n), gl2_t{1, 0})) throw std::runtime_error("Opening point is in the subgroup.");  // :596-599
+    p.zeta[sg] = zeta;
+    p.zeta_next[sg] = gl2_scalar_mul(zeta, gl_root_of_unity(p.log_n));
+}
+static void draw_zeta(table_proof& p) {
+    put_caps(p, 2, p.quot);
+    for (size_t sg = 0; sg < p.nseg(); sg++) set_zeta(p, sg, zkm_transcript_zeta(p.chs[sg], p.y, p.blobs[sg]));
+}
+
+// ---- stage: StarkOpeningSet::new (proof.rs:299-334, between two timed! scopes in the reference)
+static void write_openings(table_proof& p) {
+    const zkm_blob_desc& y = p.y;
+    const size_t total_helpers = y.A - y.Z;  // index of the first CTL Z among the auxiliary polynomials
+    zkm_prof_scope st(p.c, "stage/openings (StarkOpeningSet::new)");
+    auto ev = eval_batches(p.c, {p.trace, p.aux, p.quot}, p.zeta.data(), p.zeta_next.data());
+    auto put = [](uint64_t* at, size_t i, gl2_t v) { at[2 * i] = v.c0; at[2 * i + 1] = v.c1; };
+    for (size_t sg = 0; sg < p.nseg(); sg++) {
+        const auto o = y.openings(p.blobs[sg]);
+        const auto &tv = ev[sg][0], &av = ev[sg][1], &qv = ev[sg][2];
+        for (size_t i = 0; i < y.W; i++) { put(o.local, i, tv[i].at_z0); put(o.next, i, tv[i].at_z1); }
+        for (size_t i = 0; i < y.A; i++) { put(o.aux, i, av[i].at_z0); put(o.aux_next, i, av[i].at_z1); }
+        for (size_t i = 0; i < y.Z; i++) o.ctl_zs_first[i] = av[total_helpers + i].at_one;
+        for (size_t i = 0; i < y.Q; i++) put(o.quotient, i, qv[i].at_z0);
+    }
+}
+
+// ---- stage: prove_openings (:618-628, App. A.8): the FRI alpha, the three composites of the STARK instance, then fri_finish
+static void prove_openings(table_proof& p) {
+    zkm_ctx* const c = p.c;
+    const zkm_blob_desc& y = p.y;
+    const size_t nseg = p.nseg(), n = p.n(), W = y.W, A = y.A, total_helpers = A - y.Z;
+    zkm_prof_scope st_fri(c, "stage/compute openings proof");
+    const size_t np0 = W + A + y.Q, np1 = W + A, np2 = y.Z, apow_seg = 2 * (np0 + 1);
     std::vector<gl_t> apow(nseg * apow_seg);
-    for (size_t sg = 0; sg < nseg; sg++) {
-        gl2_t alpha = zkm_transcript_fri_alpha(chs[sg], y, proofs[sg]);
-        gl2_t p{1, 0};
-        gl_t* ap = apow.data() + sg * apow_seg;
-        for (size_t j = 0; j <= np0; j++) { ap[2 * j] = p.c0; ap[2 * j + 1] = p.c1; p = gl2_mul(p, alpha); }
-    }
-    gl_t* d_apow = scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
+    for (size_t sg = 0; sg < nseg; sg++) alpha_powers(zkm_transcript_fri_alpha(p.chs[sg], y, p.blobs[sg]), np0, apow.data() + sg * apow_seg);
+    gl_t* d_apow = p.scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
     c->upload(d_apow, apow.data(), apow.size() * sizeof(gl_t));
-    gl_t* d_comp = scratch.alloc<gl_t>(nseg * 6 * n * sizeof(gl_t));
-    if (tb->coeff_s1 != abp->coeff_s1 || tb->coeff_s1 != qbp->coeff_s1) throw std::runtime_error("internal: coefficient layouts of the three oracles differ");
+    gl_t* d_comp = p.scratch.alloc<gl_t>(nseg * 6 * n * sizeof(gl_t));
+    const zkm_batch *tb = p.trace, *ab = p.aux, *qb = p.quot;
+    if (tb->coeff_s1 != ab->coeff_s1 || tb->coeff_s1 != qb->coeff_s1) throw std::runtime_error("internal: coefficient layouts of the three oracles differ");
     {
         zkm_prof_scope ps(c, "fri_combine");
-        const size_t npoly = W + A + y.Q;
         const unsigned z = (unsigned)nseg;
         // slices of >= 32 polynomials while the launch stays below ~2^17 threads (two waves per SIMD)
-        size_t slices = npoly / 32 < 1 ? 1 : npoly / 32;
+        size_t slices = np0 / 32 < 1 ? 1 : np0 / 32;
         while (slices > 1 && slices * n * nseg > ((size_t)1 << 17)) slices >>= 1;
         if (slices >= 4) {
-            const size_t per = (npoly + slices - 1) / slices;
-            slices = (npoly + per - 1) / per;
-            gl_t* d_part = scratch.alloc<gl_t>(nseg * slices * 6 * n * sizeof(gl_t));
-            hipLaunchKernelGGL(k_fri_combine_slice, dim3((n + 255) / 256, (unsigned)slices, z), dim3(256), 0, c->stream, tb->coeffs, W, abp->coeffs, A,
-                               qbp->coeffs, y.Q, total_helpers, d_apow, n, per, d_part, apow_seg);
+            const size_t per = (np0 + slices - 1) / slices;
+            slices = (np0 + per - 1) / per;
+            gl_t* d_part = p.scratch.alloc<gl_t>(nseg * slices * 6 * n * sizeof(gl_t));
+            hipLaunchKernelGGL(k_fri_combine_slice, dim3((n + 255) / 256, (unsigned)slices, z), dim3(256), 0, c->stream, tb->coeffs, W, ab->coeffs, A,
+                               qb->coeffs, y.Q, total_helpers, d_apow, n, per, d_part, apow_seg);
             hipLaunchKernelGGL(k_fri_combine_sum, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, d_part, (unsigned)slices, n, d_comp);
         } else {
-            hipLaunchKernelGGL(k_fri_combine, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, tb->coeffs, W, abp->coeffs, A, qbp->coeffs, y.Q,
+            hipLaunchKernelGGL(k_fri_combine, dim3((n + 255) / 256, 1, z), dim3(256), 0, c->stream, tb->coeffs, W, ab->coeffs, A, qb->coeffs, y.Q,
                                total_helpers, d_apow, n, d_comp, apow_seg);
         }
         ZKM_HIP_CHECK(hipGetLastError());
     }
-    if (tb->coeff_s1) {
-        // the combination is position-wise, so the six composite arrays come out in the batches' coefficient layout; the division by
-        // (X - point) walks exponents in order
-        gl_t* d_nat = scratch.alloc<gl_t>(nseg * 6 * n * sizeof(gl_t));
-        zkm_coeff_layout_convert(c, d_comp, n, d_nat, n, 6 * nseg, log_n, /*to_natural=*/true);
-        d_comp = d_nat;
+    // the batches at zeta, g zeta and 1 (stark.rs:127-148)
+    std::vector<std::vector<fri_composite>> comps(nseg);
+    for (size_t sg = 0; sg < nseg; sg++) {
+        const gl_t* ap = apow.data() + sg * apow_seg;
+        comps[sg] = {{nullptr, nullptr, p.zeta[sg], gl2_t{ap[2 * np0], ap[2 * np0 + 1]}},
+                     {nullptr, nullptr, p.zeta_next[sg], gl2_t{ap[2 * np1], ap[2 * np1 + 1]}},
+                     {nullptr, nullptr, gl2_t{1, 0}, gl2_t{ap[2 * np2], ap[2 * np2 + 1]}}};
     }
-    // divide by (X - point), accumulate, commit phase, proof of work, query rounds: shared with zkm_fri_prove
-    {
-        std::vector<std::vector<fri_composite>> comps(nseg);
-        for (size_t sg = 0; sg < nseg; sg++) {
-            const gl_t* ap = apow.data() + sg * apow_seg;
-            comps[sg] = {{d_comp, d_comp + n, zeta[sg], gl2_t{ap[2 * np0], ap[2 * np0 + 1]}},
-                         {d_comp + 2 * n, d_comp + 3 * n, zeta_next[sg], gl2_t{ap[2 * np1], ap[2 * np1 + 1]}},
-                         {d_comp + 4 * n, d_comp + 5 * n, gl2_t{1, 0}, gl2_t{ap[2 * np2], ap[2 * np2 + 1]}}};
-        }
-        const zkm_batch* orc[3] = {tb, abp, qbp};
-        fri_finish(c, cfg, log_n, comps, 6 * n, orc, 3, chs, y.fri(), proofs);
-    }
+    const zkm_batch* orc[3] = {tb, ab, qb};
+    fri_finish(p, y.fri(), tb->coeff_s1, d_comp, std::move(comps), orc, 3);
 }
 
-// prove_single_table on existing (stacked) trace AND auxiliary commitments (zkm_prove_with_traces builds the auxiliary commitments of all
-// tables ahead of the transcript, side by side); zs = chs.size() lists of CtlZData, lookup_challenges = chs.size() x num_challenges; throws
-void zkm_prove_single_table_aux(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, size_t ncols, unsigned log_n, const zkm_batch* trace_batch,
-                                const zkm_batch* aux_batch, size_t naux_ctl, const zkm_ctl_table* table, const zkm_ctl_z* zs,
-                                const uint32_t* colset_ids, size_t nzs, const uint64_t* lookup_challenges, const std::vector<zkm_challenger*>& chs,
-                                const std::vector<uint64_t*>& proofs) {
+// the line from the point where both commitments exist
+static void prove_from_aux(table_proof& p, int table_id, const ctl_dev_owner& own, const uint64_t* lookup_challenges) {
+    commit_quotient(p, table_id, own, lookup_challenges);
+    draw_zeta(p);
+    write_openings(p);
+    prove_openings(p);
+}
+
+// ---- driver: from existing (stacked) trace AND auxiliary commitments (zkm_prove_with_traces builds the auxiliary commitments of all
+// tables ahead of the transcript, side by side -- they only depend on the CTL challenges); zs = chs.size() lists of CtlZData,
+// lookup_challenges = chs.size() x num_challenges; throws
+void zkm_prove_table_from_commitments(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, size_t ncols, unsigned log_n, const zkm_batch* trace_batch,
+                                      const zkm_batch* aux_batch, size_t naux_ctl, const zkm_ctl_table* table, const zkm_ctl_z* zs,
+                                      const uint32_t* colset_ids, size_t nzs, const uint64_t* lookup_challenges, const std::vector<zkm_challenger*>& chs,
+                                      const std::vector<uint64_t*>& proofs) {
     if (!trace_batch || !aux_batch) throw std::runtime_error("prove_single_table: commitments are required");
-    prove_single_table(c, table_id, cfg, nullptr, ncols, log_n, trace_batch, nullptr, naux_ctl, table, zs, colset_ids, nzs, lookup_challenges, chs,
-                       proofs, aux_batch, nullptr);
+    if (chs.empty() || chs.size() > ZKM_MAX_SEG || proofs.size() != chs.size()) throw std::runtime_error("prove_single_table: bad stack size");
+    table_proof p{{c, cfg, log_n, chs, proofs}, describe_table_proof(table_id, cfg, ncols, log_n, naux_ctl, zs, nzs, lookup_challenges), trace_batch, aux_batch};
+    require_batch(p.trace, ncols, log_n, cfg, p.nseg(), "trace commitment does not match the table shape / config");
+    require_batch(p.aux, p.y.A, log_n, cfg, p.nseg(), "auxiliary commitment does not match the table shape / config");
+    ctl_dev_owner own;
+    upload_ctl(p, own, table, zs, colset_ids);
+    begin_blobs(p);
+    prove_from_aux(p, table_id, own, lookup_challenges);
 }
 
 // ------------------------------------------------------------------ C ABI
-// (a prove entry point advances the transcript on a copy and hands it back only when the whole proof exists: a failed call leaves the
-// caller's challenger where it was -- the reference's prove_openings cannot fail half way; a C ABI call can)
+// (a prove entry point advances copies of its callers' transcripts and hands them back only when the whole proof exists:
+// zkm_transcripts, zkm_internal.h)
 
 // ---- PolynomialBatch::prove_openings for an arbitrary FriInstanceInfo (plonky2 fri/oracle.rs; instance of the STARKs: stark.rs:91-148)
 // composite of one batch: sum_j alpha^j p_j, polynomials named by pointer (any oracle, any column)
@@ -1657,8 +1698,9 @@ int zkm_consumer_selftest(zkm_ctx* c, const uint64_t* alphas, size_t nalphas, co
         zkm_scratch dt(c, K * n * 8), dout(c, nalphas * n * 8);
         ZKM_HIP_CHECK(hipMemcpyAsync(dt.p, terms, K * n * 8, hipMemcpyHostToDevice, c->stream));
         const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        if (nalphas == 1) hipLaunchKernelGGL((k_consumer_selftest<1>), grid, block, 0, c->stream, a, dt.as<uint64_t>(), K, n, run, dout.as<uint64_t>());
-        else hipLaunchKernelGGL((k_consumer_selftest<2>), grid, block, 0, c->stream, a, dt.as<uint64_t>(), K, n, run, dout.as<uint64_t>());
+        with_nalphas(nalphas, [&](auto NA) {
+            hipLaunchKernelGGL((k_consumer_selftest<decltype(NA)::value>), grid, block, 0, c->stream, a, dt.as<uint64_t>(), K, n, run, dout.as<uint64_t>());
+        });
         ZKM_HIP_CHECK(hipGetLastError());
         ZKM_HIP_CHECK(hipMemcpyAsync(out, dout.p, nalphas * n * 8, hipMemcpyDeviceToHost, c->stream));
         c->sync();
@@ -1674,9 +1716,6 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
                   size_t nbatches, zkm_challenger* ch_io, uint64_t* proof, char** err) {
     return zkm_api("zkm_fri_prove", c, err, [&] {
         if (!cfg || !oracles || !batches || !nbatches || !ch_io || !proof) throw std::runtime_error("zkm_fri_prove: null argument");
-        zkm_challenger local = *ch_io;
-        zkm_challenger* const ch = &local;
-        zkm_scratch_list scratch(c);
         if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error("zkm_fri_prove: 1..8 oracles");
         const unsigned log_n = oracles[0]->log_n;
         size_t cols[ZKM_FRI_MAX_ORACLES];
@@ -1684,6 +1723,7 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
             if (!oracles[k] || oracles[k]->log_n != log_n || oracles[k]->rate_bits != cfg->rate_bits || oracles[k]->cap_height != cfg->cap_height ||
                 oracles[k]->coeff_s1 != oracles[0]->coeff_s1)
                 throw std::runtime_error("zkm_fri_prove: oracles must share degree, rate and cap height with the config");
+            if (oracles[k]->nseg != 1) throw std::runtime_error("zkm_fri_prove: stacked batches are internal");
             cols[k] = oracles[k]->ncols;
         }
         const zkm_fri_part y = fri_blob_describe(cfg, log_n, cols, noracles);
@@ -1702,50 +1742,33 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
         proof[6] = cfg->num_queries; proof[7] = cfg->rate_bits; proof[8] = cfg->arity_bits;
         for (size_t k = 0; k < noracles; k++) proof[16 + k] = cols[k];
 
-        gl2_t alpha = zkm_challenger_get_ext(ch);
+        zkm_transcripts tr(ch_io);
+        const std::vector<uint64_t*> blobs{proof};
+        proof_stack f{c, cfg, log_n, tr.chs, blobs};
         std::vector<gl_t> apow(2 * (maxp + 1));
-        {
-            gl2_t pw{1, 0};
-            for (size_t j = 0; j <= maxp; j++) { apow[2 * j] = pw.c0; apow[2 * j + 1] = pw.c1; pw = gl2_mul(pw, alpha); }
-        }
-        gl_t* d_apow = scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
+        alpha_powers(zkm_challenger_get_ext(tr.chs[0]), maxp, apow.data());
+        gl_t* d_apow = f.scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
         c->upload(d_apow, apow.data(), apow.size() * sizeof(gl_t));
-        gl_t* d_comp = scratch.alloc<gl_t>(2 * nbatches * n * sizeof(gl_t));
+        gl_t* d_comp = f.scratch.alloc<gl_t>(2 * nbatches * n * sizeof(gl_t));
         std::vector<const gl_t*> ptrs;
-        std::vector<size_t> first(nbatches);
-        for (size_t b = 0; b < nbatches; b++) {
-            first[b] = ptrs.size();
+        for (size_t b = 0; b < nbatches; b++)
             for (size_t j = 0; j < batches[b].npolys; j++) ptrs.push_back(oracles[batches[b].polys[j].oracle]->coeffs + (size_t)batches[b].polys[j].poly * n);
-        }
-        const gl_t** d_ptrs = scratch.alloc<const gl_t*>(ptrs.size() * sizeof(gl_t*));
+        const gl_t** d_ptrs = f.scratch.alloc<const gl_t*>(ptrs.size() * sizeof(gl_t*));
         c->upload((void*)d_ptrs, ptrs.data(), ptrs.size() * sizeof(gl_t*));
-        std::vector<std::vector<fri_composite>> comps_v(1);
-        std::vector<fri_composite>& comps = comps_v[0];
-        for (size_t b = 0; b < nbatches; b++) {
+        std::vector<std::vector<fri_composite>> comps(1);
+        for (size_t b = 0, first = 0; b < nbatches; first += batches[b++].npolys) {
             zkm_prof_scope ps(c, "fri_combine");
-            hipLaunchKernelGGL(k_fri_combine_generic, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_ptrs + first[b], batches[b].npolys, d_apow, n,
+            hipLaunchKernelGGL(k_fri_combine_generic, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_ptrs + first, batches[b].npolys, d_apow, n,
                                d_comp + 2 * b * n, d_comp + (2 * b + 1) * n);
             ZKM_HIP_CHECK(hipGetLastError());
             const size_t np = batches[b].npolys;
-            comps.push_back({d_comp + 2 * b * n, d_comp + (2 * b + 1) * n, gl2_t{batches[b].point[0], batches[b].point[1]},
-                             gl2_t{apow[2 * np], apow[2 * np + 1]}});
-        }
-        if (oracles[0]->coeff_s1) {   // (the layout is a function of the height: the same for every oracle; see prove_single_table)
-            gl_t* d_nat = scratch.alloc<gl_t>(2 * nbatches * n * sizeof(gl_t));
-            zkm_coeff_layout_convert(c, d_comp, n, d_nat, n, 2 * nbatches, log_n, /*to_natural=*/true);
-            for (auto& k : comps) { k.c0 = d_nat + (k.c0 - d_comp); k.c1 = d_nat + (k.c1 - d_comp); }
+            comps[0].push_back({nullptr, nullptr, gl2_t{batches[b].point[0], batches[b].point[1]}, gl2_t{apow[2 * np], apow[2 * np + 1]}});
         }
         ZKM_HIP_CHECK(hipStreamSynchronize(c->stream));  // host vectors (ptrs, apow) are consumed
-        for (size_t k = 0; k < noracles; k++)
-            if (oracles[k]->nseg != 1) throw std::runtime_error("zkm_fri_prove: stacked batches are internal");
-        fri_finish(c, cfg, log_n, comps_v, 0, oracles, noracles, {ch}, y, {proof});
-        *ch_io = local;
+        fri_finish(f, y, oracles[0]->coeff_s1, d_comp, std::move(comps), oracles, noracles);
+        tr.commit();
     });
 }
-
-}  // extern "C"
-
-extern "C" {
 
 size_t zkm_proof_words(const zkm_stark_config* cfg, unsigned log_n, size_t ncols, size_t naux, size_t nctl_zs) {
     zkm_blob_desc y{};   // (0 = unsupported configuration: the prove entry points report which field)
@@ -1762,6 +1785,7 @@ static std::vector<zkm_ctl_z> fake_zs(const uint32_t* num_helpers, size_t n) {
     return zs;
 }
 
+// ---- driver: from values -- the trace's (or its commitment, if the caller has one) and the CTL columns'
 int zkm_prove_single_table_ctl(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, const uint64_t* trace, size_t ncols, unsigned log_n,
                                const zkm_batch* trace_batch, const uint64_t* aux, size_t naux, const zkm_ctl_table* table,
                                const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs, const uint64_t* lookup_challenges,
@@ -1769,22 +1793,47 @@ int zkm_prove_single_table_ctl(zkm_ctx* c, int table_id, const zkm_stark_config*
     return zkm_api("zkm_prove_single_table", c, err, [&] {
         if (!cfg || !challenger || !proof_out) throw std::runtime_error("zkm_prove_single_table: null argument");
         if (!trace && !trace_batch) throw std::runtime_error("zkm_prove_single_table: need trace values or a trace commitment");
-        zkm_challenger local = *challenger;
-        prove_single_table(c, table_id, cfg, trace, ncols, log_n, trace_batch, aux, naux, table, zs, colset_ids, nzs, lookup_challenges,
-                           {&local}, {proof_out});
-        *challenger = local;
+        zkm_transcripts tr(challenger);
+        const std::vector<uint64_t*> blobs{proof_out};
+        table_proof p{{c, cfg, log_n, tr.chs, blobs}, describe_table_proof(table_id, cfg, ncols, log_n, naux, zs, nzs, lookup_challenges), trace_batch};
+        if (p.y.A != naux && !trace) throw std::runtime_error("this table has lookups: the trace values are required to build their helper columns");
+        ctl_dev_owner own;
+        upload_ctl(p, own, table, zs, colset_ids);
+        if (!p.trace) commit_trace(p, trace);
+        require_batch(p.trace, ncols, log_n, cfg, 1, "trace commitment does not match the table shape / config");
+        begin_blobs(p);
+        commit_aux(p, table_id, trace, aux, lookup_challenges);
+        prove_from_aux(p, table_id, own, lookup_challenges);
+        tr.commit();
     });
 }
 
+// ---- driver: from three commitments (BASELINE config 4): compact -> zeta -> openings -> prove_openings.  No table: the widths are
+// the commitments' own, and of the CTL description only the number of Zs -- the last nctl_zs auxiliary polynomials -- matters.
 int zkm_prove_openings(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* trace_batch, const zkm_batch* aux_batch,
                        const zkm_batch* quot_batch, size_t nctl_zs, zkm_challenger* challenger, uint64_t* proof_out, char** err) {
     return zkm_api("zkm_prove_openings", c, err, [&] {
         if (!cfg || !challenger || !proof_out) throw std::runtime_error("zkm_prove_openings: null argument");
         if (!trace_batch || !aux_batch || !quot_batch) throw std::runtime_error("zkm_prove_openings: three commitments are required");
-        zkm_challenger local = *challenger;
-        prove_single_table(c, -1, cfg, nullptr, trace_batch->ncols, trace_batch->log_n, trace_batch, nullptr, aux_batch->ncols, nullptr,
-                           nullptr, nullptr, nctl_zs, nullptr, {&local}, {proof_out}, aux_batch, quot_batch);
-        *challenger = local;
+        const unsigned log_n = trace_batch->log_n;
+        const size_t A = aux_batch->ncols;
+        zkm_transcripts tr(challenger);
+        const std::vector<uint64_t*> blobs{proof_out};
+        table_proof p{{c, cfg, log_n, tr.chs, blobs}, zkm_blob_describe(cfg, log_n, trace_batch->ncols, A, nctl_zs), trace_batch, aux_batch, quot_batch};
+        if (p.y.L > ZKM_FRI_GATHER_LAYERS) throw std::runtime_error("too many FRI layers");
+        if (nctl_zs > A) throw std::runtime_error("zkm_prove_openings: more CTL Zs than auxiliary polynomials");
+        if (A == 0) throw std::runtime_error("No CTL? aux column count does not match the CTL description");  // prover.rs:509
+        require_batch(p.trace, p.y.W, log_n, cfg, 1, "trace commitment does not match the table shape / config");
+        for (const zkm_batch* b : {p.aux, p.quot})   // (their widths: the auxiliary commitment's is A by definition, the quotient's follows)
+            require_batch(b, b->ncols, log_n, cfg, 1, "zkm_prove_openings: commitments do not match the table shape / config");
+        if (p.quot->ncols != p.y.Q) throw std::runtime_error("zkm_prove_openings: unexpected number of polynomials");
+        begin_blobs(p);
+        put_caps(p, 1, p.aux);
+        put_caps(p, 2, p.quot);
+        set_zeta(p, 0, zkm_challenger_get_ext(tr.chs[0]));
+        write_openings(p);
+        prove_openings(p);
+        tr.commit();
     });
 }
 
@@ -1813,33 +1862,15 @@ int zkm_prove_single_tables(zkm_ctx* c, int table_id, const zkm_stark_config* cf
         auto zs1 = fake_zs(num_helpers, nctl_zs);
         std::vector<zkm_ctl_z> zs;
         for (size_t k = 0; k < nproofs; k++) zs.insert(zs.end(), zs1.begin(), zs1.end());
-        std::vector<zkm_challenger> local(nproofs);
-        std::vector<zkm_challenger*> chs(nproofs);
-        std::vector<uint64_t*> proofs(nproofs);
-        for (size_t k = 0; k < nproofs; k++) {
+        for (size_t k = 0; k < nproofs; k++)
             if (!traces[k] || !aux[k] || !challengers[k] || !proofs_out[k]) throw std::runtime_error("zkm_prove_single_tables: null proof argument");
-            local[k] = *challengers[k];
-            chs[k] = &local[k];
-            proofs[k] = proofs_out[k];
-        }
-        auto stacked = [&](size_t cols, const uint64_t* const* srcs) {
-            zkm_batch_ptr b = zkm_batch_new(c, cols, nproofs, log_n, cfg->rate_bits, cfg->cap_height);
-            if (nproofs == 1) zkm_batch_build(b.get(), srcs[0], true);
-            else zkm_batch_build(b.get(), nullptr, true, nullptr, nullptr, srcs);   // (device matrices are transformed where they lie)
-            return b;
-        };
-        zkm_batch_ptr tb, ab;
-        {
-            zkm_prof_scope st(c, "stage/compute trace commitment");
-            tb = stacked(ncols, traces);
-        }
-        {
-            zkm_prof_scope st(c, "stage/compute auxiliary polynomials commitment");
-            ab = stacked(naux, aux);
-        }
-        prove_single_table(c, table_id, cfg, nullptr, ncols, log_n, tb.get(), nullptr, naux, nullptr, zs.data(), nullptr, nctl_zs, nullptr, chs, proofs,
-                           ab.get(), nullptr);
-        for (size_t k = 0; k < nproofs; k++) *challengers[k] = local[k];
+        zkm_transcripts tr(challengers, nproofs);
+        const std::vector<uint64_t*> proofs(proofs_out, proofs_out + nproofs);
+        const zkm_batch_ptr tb = commit_values(c, cfg, "stage/compute trace commitment", ncols, log_n, traces, nproofs),
+                            ab = commit_values(c, cfg, "stage/compute auxiliary polynomials commitment", naux, log_n, aux, nproofs);
+        zkm_prove_table_from_commitments(c, table_id, cfg, ncols, log_n, tb.get(), ab.get(), naux, nullptr, zs.data(), nullptr, nctl_zs, nullptr, tr.chs,
+                                         proofs);
+        tr.commit();
     });
 }
 
@@ -1876,7 +1907,7 @@ int zkm_check_constraints(zkm_ctx* c, int table_id, const zkm_stark_config* cfg,
     return zkm_api("zkm_check_constraints", c, err, [&] {
         if (!cfg || !trace || !aux || !alphas || !first_failing_row) throw std::runtime_error("zkm_check_constraints: null argument");
         validate_config(cfg, log_n);
-        if (table_id < 0 || table_id >= 12) throw std::runtime_error("zkm_check_constraints: unknown table id");
+        if (!zkm_table(table_id)) throw std::runtime_error("zkm_check_constraints: unknown table id");
         // a table with lookups of its own (Memory, Arithmetic) takes its challenges from the caller: none given is an error here, not a
         // null dereference on the host
         if (!lookup_challenges && zkm_num_lookup_columns(table_id, cfg)) throw std::runtime_error("zkm_check_constraints: this table has lookups of its own: lookup challenges are required");
@@ -1907,12 +1938,8 @@ int zkm_check_constraints(zkm_ctx* c, int table_id, const zkm_stark_config* cfg,
         unsigned long long first = ~0ULL;
         c->download(&first, d_first, 8);
         *first_failing_row = first;
-        if (first != ~0ULL) {
-            static const char* const names[] = {"PoseidonStark", "LogicStark", "KeccakSpongeStark", "KeccakStark", "MemoryStark", "PoseidonSpongeStark",
-                                                "ShaExtendStark", "ShaExtendSpongeStark", "ShaCompressStark", "ShaCompressSpongeStark", "ArithmeticStark",
-                                                "CpuStark"};
-            throw std::runtime_error(std::string("Constraint failed in ") + names[table_id] + " (first failing row " + std::to_string(first) + ")");   // prover.rs:903-908
-        }
+        if (first != ~0ULL)
+            throw std::runtime_error(std::string("Constraint failed in ") + zkm_table(table_id)->name + "Stark (first failing row " + std::to_string(first) + ")");   // prover.rs:903-908
     });
 }
 

@@ -345,6 +345,23 @@ using zkm_batch_ptr = std::unique_ptr<zkm_batch, zkm_batch_deleter>;
 // an empty batch of this shape (zkm_batch_build fills it in); core.hip
 zkm_batch_ptr zkm_batch_new(zkm_ctx* c, size_t ncols, size_t nseg, unsigned log_n, unsigned rate_bits, unsigned cap_height);
 
+// Copies of the callers' transcripts for a prove call to advance (chs: what the stages take); commit() hands them back once the whole
+// proof exists.  A call that fails on the way -- the reference's prove_openings cannot fail half way; a C ABI call can -- never gets
+// there, and leaves every caller's challenger where it was.
+struct zkm_transcripts {
+    std::vector<zkm_challenger*> callers;
+    std::vector<zkm_challenger> local;
+    std::vector<zkm_challenger*> chs;
+    zkm_transcripts(zkm_challenger* const* callers_, size_t n) : callers(callers_, callers_ + n), local(n), chs(n) {
+        for (size_t k = 0; k < n; k++) { local[k] = *callers[k]; chs[k] = &local[k]; }
+    }
+    explicit zkm_transcripts(zkm_challenger* caller) : zkm_transcripts(&caller, 1) {}
+    zkm_transcripts(const zkm_transcripts&) = delete;   // (chs points into local)
+    void commit() {
+        for (size_t k = 0; k < callers.size(); k++) *callers[k] = local[k];
+    }
+};
+
 inline bool zkm_is_device_ptr(const void* p) {
     hipPointerAttribute_t a;
     hipError_t e = hipPointerGetAttributes(&a, p);
@@ -428,11 +445,11 @@ void zkm_batch_build(zkm_batch* b, const uint64_t* src, bool src_is_values, gl_t
                      const uint64_t* const* src_cols = nullptr, const uint64_t* const* seg_srcs = nullptr);
 zkm_batch* zkm_batch_commit_values_keep(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, unsigned rate_bits,
                                         unsigned cap_height, gl_t* dev_values, const uint64_t* const* columns = nullptr);
-// stark.hip: prove_single_table on an existing trace and auxiliary commitment (throws)
-void zkm_prove_single_table_aux(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, size_t ncols, unsigned log_n, const zkm_batch* trace_batch,
-                                const zkm_batch* aux_batch, size_t naux_ctl, const zkm_ctl_table* table, const zkm_ctl_z* zs,
-                                const uint32_t* colset_ids, size_t nzs, const uint64_t* lookup_challenges, const std::vector<zkm_challenger*>& chs,
-                                const std::vector<uint64_t*>& proofs);
+// stark.hip: prove_single_table from existing (stacked) trace and auxiliary commitments, for chs.size() proofs in lock-step (throws)
+void zkm_prove_table_from_commitments(zkm_ctx* c, int table_id, const zkm_stark_config* cfg, size_t ncols, unsigned log_n, const zkm_batch* trace_batch,
+                                      const zkm_batch* aux_batch, size_t naux_ctl, const zkm_ctl_table* table, const zkm_ctl_z* zs,
+                                      const uint32_t* colset_ids, size_t nzs, const uint64_t* lookup_challenges, const std::vector<zkm_challenger*>& chs,
+                                      const std::vector<uint64_t*>& proofs);
 void zkm_launch_canon(zkm_ctx* c, gl_t* v, size_t total);   // v[i] = canonical representative of v[i], in place
 void zkm_host_poseidon_permute(uint64_t st[12]);
 void zkm_host_poseidon_permute_reference(uint64_t st[12]);   // poseidon_dev.h compiled for the host (cross-check)
