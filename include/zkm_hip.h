@@ -798,6 +798,110 @@ int zkm_prove_segments_ops_boot(zkm_ctx* ctx, const zkm_stark_config* cfg, size_
 int zkm_boot_witness(zkm_ctx* ctx, const zkm_boot_image* image, uint64_t* cpu_rows_out, uint64_t* memory_ops_out, uint64_t* poseidon_inputs_out,
                      uint64_t* poseidon_ts_out, uint64_t* digests_out, char** err);
 
+/* ------------------------------------------------------------------ a segment's CPU table from a compact step log
+ * The row filling of witness/operation.rs (the generate_* functions that turn the values an instruction read into columns) on the
+ * device.  The emulator's fetch, decode and execute stay on the host: instead of a 259-word CpuColumnsView a cycle it records one
+ * zkm_cpu_step, 48 bytes, and the step at position i of the list becomes
+ *   row first_clock + i of the CPU table, written column-major straight into the table (clock = first_clock + i);
+ *   its memory operations (zkm_memory_trace's 6 words, context 0 for registers and the shift table, timestamp clock * 10), its logic
+ *   operation and its arithmetic operation ({op, in0, in1} as zkm_logic_trace / zkm_arithmetic_trace take them; results are computed
+ *   on the device), each list in the order the reference pushes: per row the order of the generator's reg_read / reg_write /
+ *   mem_read / mem_write calls, which is not channel order (binary_imm writes rt on channels 1 and 2; syscall uses channels 0-3, then
+ *   6 and 7, then 4 and 5).  A write to register 0 fills its channel with used = 0 and pushes nothing (witness/util.rs:198-204).
+ *   pc, next_pc   program_counter and next_program_counter of the row, both from before the step (next_pc is the delay-slot value)
+ *   insn          the instruction word; its 32 bits fill the six bit fields of the row
+ *   kind          ZKM_STEP_*, below
+ *   flags         bit 0: kernel mode; bit 1 (ZKM_STEP_FLAG_BRANCH_R0), BRANCH against zero only: channel 1 reads register 0 whatever the
+ *                 rt field (the reference decodes BGEZ so); bits 8-11, SYSCALL only: ZKM_SYSCALL_* (the branch of generate_syscall taken)
+ *   context       the row's context, and the context of a load's / store's memory channels
+ *   reads         the values the step reads through the memory channels, in the order the generator reads them: register reads, then
+ *                 memory reads (RDHWR of register 29: the one read follows the write)
+ * Kinds, one per op flag that has a witness model (tests/cpu_fixtures.py Machine), each with exactly these encodings:
+ *   BINARY_OP ADD ADDU SUB SUBU SLT SLTU; BINARY_IMM_OP ADDI ADDIU SLTI SLTIU; LOGIC_OP AND OR XOR NOR; LOGIC_IMM_OP ANDI ORI XORI
+ *   (pushes no logic operation, as the reference); SHIFT SLLV SRLV SRAV;
+ *   SHIFT_IMM SLL SRL SRA (rs = 0); BRANCH BEQ BNE BLEZ BGTZ BLTZ BGEZ (channel 1 reads the register the rt field names, see flags);
+ *   JUMPS JR JALR; JUMPI J JAL; JUMPDIRECT BAL; M_OP_LOAD LB LH LWL LW LBU LHU LWR LL; M_OP_STORE SB SH SWL SW SWR SC; NOP (word 0);
+ *   CLZ_OP; CLO_OP; SIGNEXT8 SEB; SIGNEXT16 SEH; SWAPHALF WSBH; RDHWR; MOVZ_OP; MOVN_OP; TEQ (operands that differ); EXT; INS; ROR;
+ *   MADDU; SYSCALL (mmap, brk, clone, read, write, fcntl, set_thread_area, other).  Every other encoding is refused.
+ *   PAD   the padding row of simulate_cpu (generation/mod.rs:170-185): clock, context, pc, next_pc and is_exit_kernel = 1
+ *   RAW   reads[0] indexes a ready-made row in raw_rows (nraw x ZKM_CPU_COLS words row-major, any representative mod p, host or device
+ *         memory); reads[1] has bit k set for each of the eight channels k whose `used` cell is 1 -- the counts and the operations
+ *         follow this mask.  Rows in host memory are held to it on the walk (a mismatch is refused); for rows in device memory a
+ *         mismatch is NOT detected: a used channel the mask leaves out pushes nothing.  The row is copied canonical and the masked
+ *         channels become memory operations in ascending channel order, timestamped from the row's OWN clock cell (every other
+ *         kind: first_clock + position); no logic or arithmetic operation.  The escape for everything the kinds do not cover: keccak_general and the precompile rows, a bootstrap row
+ *         handed over by the caller, a register written outside an instruction.
+ * `steps` is host memory (pageable or pinned); the library walks it once on the host, and every refusal -- an unknown kind, an encoding
+ * the kind does not take, a RAW index >= nraw, a RAW mask that is not its host row's, a NULL pointer with a nonzero count -- is made
+ * on that walk, before any device work, and names the step's index.  The counts of a step are a function of its record alone
+ * (csrc/cpu_steps_dev.h, one __host__ __device__ function for the walk and the kernels).
+ *   zkm_cpu_steps_counts   the three list lengths of a step list; needs no GPU
+ *   zkm_cpu_witness        the kernels alone (tests and tools): cpu_out_dev ZKM_CPU_COLS x 2^log_n words column-major, zero outside rows
+ *                          [first_clock, first_clock + nsteps), which must fit; memory_ops_out_dev n x 6 words, logic_ops_out_dev and
+ *                          arithmetic_ops_out_dev n x 3 uint32, sized by zkm_cpu_steps_counts (a list of count 0 may be NULL).
+ *                          Returns once the outputs are complete (one host wait).
+ *   zkm_segments_tables_steps / zkm_prove_segments_ops_steps   zkm_segments_tables[_boot] / zkm_prove_segments_ops[_boot] with the CPU
+ *                          rows built from steps[s]: ops[s].cpu_rows must be NULL with ncpu_rows 0; images may be NULL (no bootstrap);
+ *                          first_clock is the bootstrap's row count.  The joined Memory, Logic and Arithmetic lists are the
+ *                          bootstrap's, then the steps', then ops[s]'s own (the Memory sort is stable).  (bootstrap rows) + nsteps
+ *                          must be a power of two: the caller appends PAD steps as simulate_cpu does.  Heights are those of
+ *                          into_tables on the joined lists; "check_ctls", "verify", waves, memory budget and sizing mode as in the
+ *                          calls without steps, and so are the three host waits whatever K: the step path adds none.  Every table,
+ *                          blob and challenge is word for word what the calls without steps give for the expanded rows and lists.
+ * Steps are not staged (zkm_segment_ops_stage takes none), the pool takes none, kinds outside the list go RAW, and there is no exit
+ * kernel.  Profile scopes cpu_steps/lists and cpu_steps/rows (zkm_cpu_witness: cpu_steps/rows_lists). */
+#define ZKM_STEP_BINARY_OP 0
+#define ZKM_STEP_BINARY_IMM_OP 1
+#define ZKM_STEP_LOGIC_OP 2
+#define ZKM_STEP_LOGIC_IMM_OP 3
+#define ZKM_STEP_SHIFT 4
+#define ZKM_STEP_SHIFT_IMM 5
+#define ZKM_STEP_BRANCH 6
+#define ZKM_STEP_JUMPS 7
+#define ZKM_STEP_JUMPI 8
+#define ZKM_STEP_JUMPDIRECT 9
+#define ZKM_STEP_M_OP_LOAD 10
+#define ZKM_STEP_M_OP_STORE 11
+#define ZKM_STEP_NOP 12
+#define ZKM_STEP_CLZ_OP 13
+#define ZKM_STEP_CLO_OP 14
+#define ZKM_STEP_SIGNEXT8 15
+#define ZKM_STEP_SIGNEXT16 16
+#define ZKM_STEP_SWAPHALF 17
+#define ZKM_STEP_RDHWR 18
+#define ZKM_STEP_MOVZ_OP 19
+#define ZKM_STEP_MOVN_OP 20
+#define ZKM_STEP_TEQ 21
+#define ZKM_STEP_EXT 22
+#define ZKM_STEP_INS 23
+#define ZKM_STEP_ROR 24
+#define ZKM_STEP_MADDU 25
+#define ZKM_STEP_SYSCALL 26
+#define ZKM_STEP_PAD 27
+#define ZKM_STEP_RAW 28
+#define ZKM_STEP_FLAG_KERNEL 1u
+#define ZKM_STEP_FLAG_BRANCH_R0 2u
+#define ZKM_SYSCALL_OTHER 0
+#define ZKM_SYSCALL_MMAP 1
+#define ZKM_SYSCALL_BRK 2
+#define ZKM_SYSCALL_CLONE 3
+#define ZKM_SYSCALL_READ 5
+#define ZKM_SYSCALL_WRITE 6
+#define ZKM_SYSCALL_FCNTL 7
+#define ZKM_SYSCALL_SET_THREAD_AREA 8
+/* (Layout lock: `tools/abi_layout steps` prints these two structs, tests/test_cpu_steps_abi.py compares them with the numpy, ctypes and
+ * Rust mirrors.) */
+typedef struct zkm_cpu_step { uint32_t pc, next_pc, insn, kind, flags, context; uint32_t reads[6]; } zkm_cpu_step;   /* 48 bytes */
+typedef struct zkm_cpu_steps { const zkm_cpu_step* steps; size_t nsteps; const uint64_t* raw_rows; size_t nraw; } zkm_cpu_steps;
+int zkm_cpu_steps_counts(const zkm_cpu_steps* steps, size_t* memory_ops, size_t* logic_ops, size_t* arithmetic_ops, char** err);
+int zkm_cpu_witness(zkm_ctx* ctx, const zkm_cpu_steps* steps, uint64_t first_clock, unsigned log_n, uint64_t* cpu_out_dev,
+                    uint64_t* memory_ops_out_dev, uint32_t* logic_ops_out_dev, uint32_t* arithmetic_ops_out_dev, char** err);
+int zkm_segments_tables_steps(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_cpu_steps* steps,
+                              const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out, char** err);
+int zkm_prove_segments_ops_steps(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_cpu_steps* steps,
+                                 const zkm_segment_ops* ops, const uint64_t* const* public_values, const size_t* npublic,
+                                 uint64_t* const* proofs_out, size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
+
 /* ------------------------------------------------------------------ a memory image's hash pages, root and image id
  * What the emulator does at every segment split -- Memory::update_page_hash and Memory::compute_image_id (emulator/src/memory.rs:388-471,
  * with poseidon / hash_page / CONST_HASH_PAGES, :43-118, and alloc_hash_page, :378-386; called from split_segment, state.rs:1477-1530) --

@@ -124,6 +124,31 @@ pub struct ZkmImagePages {
     pub known_words: *const u32, pub pc: u32, pub registers: [u8; 156],
 }
 pub type zkm_image_pages = ZkmImagePages;
+/// one cycle of the compact step log and a segment's step list (include/zkm_hip.h; compared with `abi_layout steps` by
+/// tests/test_cpu_steps_abi.py): the CPU rows and the operations they push are built from them on the device
+#[repr(C)] #[derive(Clone, Copy, Debug, Default)]
+pub struct ZkmCpuStep {
+    pub pc: u32, pub next_pc: u32, pub insn: u32, pub kind: u32, pub flags: u32, pub context: u32, pub reads: [u32; 6],
+}
+pub type zkm_cpu_step = ZkmCpuStep;
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct ZkmCpuSteps {
+    pub steps: *const zkm_cpu_step, pub nsteps: usize, pub raw_rows: *const u64, pub nraw: usize,
+}
+pub type zkm_cpu_steps = ZkmCpuSteps;
+pub const ZKM_STEP_BINARY_OP: u32 = 0; pub const ZKM_STEP_BINARY_IMM_OP: u32 = 1; pub const ZKM_STEP_LOGIC_OP: u32 = 2;
+pub const ZKM_STEP_LOGIC_IMM_OP: u32 = 3; pub const ZKM_STEP_SHIFT: u32 = 4; pub const ZKM_STEP_SHIFT_IMM: u32 = 5;
+pub const ZKM_STEP_BRANCH: u32 = 6; pub const ZKM_STEP_JUMPS: u32 = 7; pub const ZKM_STEP_JUMPI: u32 = 8; pub const ZKM_STEP_JUMPDIRECT: u32 = 9;
+pub const ZKM_STEP_M_OP_LOAD: u32 = 10; pub const ZKM_STEP_M_OP_STORE: u32 = 11; pub const ZKM_STEP_NOP: u32 = 12;
+pub const ZKM_STEP_CLZ_OP: u32 = 13; pub const ZKM_STEP_CLO_OP: u32 = 14; pub const ZKM_STEP_SIGNEXT8: u32 = 15;
+pub const ZKM_STEP_SIGNEXT16: u32 = 16; pub const ZKM_STEP_SWAPHALF: u32 = 17; pub const ZKM_STEP_RDHWR: u32 = 18;
+pub const ZKM_STEP_MOVZ_OP: u32 = 19; pub const ZKM_STEP_MOVN_OP: u32 = 20; pub const ZKM_STEP_TEQ: u32 = 21; pub const ZKM_STEP_EXT: u32 = 22;
+pub const ZKM_STEP_INS: u32 = 23; pub const ZKM_STEP_ROR: u32 = 24; pub const ZKM_STEP_MADDU: u32 = 25; pub const ZKM_STEP_SYSCALL: u32 = 26;
+pub const ZKM_STEP_PAD: u32 = 27; pub const ZKM_STEP_RAW: u32 = 28;
+pub const ZKM_STEP_FLAG_KERNEL: u32 = 1; pub const ZKM_STEP_FLAG_BRANCH_R0: u32 = 2;
+pub const ZKM_SYSCALL_OTHER: u32 = 0; pub const ZKM_SYSCALL_MMAP: u32 = 1; pub const ZKM_SYSCALL_BRK: u32 = 2; pub const ZKM_SYSCALL_CLONE: u32 = 3;
+pub const ZKM_SYSCALL_READ: u32 = 5; pub const ZKM_SYSCALL_WRITE: u32 = 6; pub const ZKM_SYSCALL_FCNTL: u32 = 7;
+pub const ZKM_SYSCALL_SET_THREAD_AREA: u32 = 8;
 pub const ZKM_VERIFY_OK: u32 = 0; pub const ZKM_VERIFY_SHAPE: u32 = 1; pub const ZKM_VERIFY_TRANSCRIPT_STATE: u32 = 2;
 pub const ZKM_VERIFY_CTL_CHALLENGES: u32 = 3; pub const ZKM_VERIFY_QUOTIENT: u32 = 4; pub const ZKM_VERIFY_POW: u32 = 5;
 pub const ZKM_VERIFY_INITIAL_MERKLE: u32 = 6; pub const ZKM_VERIFY_FRI_EVAL: u32 = 7; pub const ZKM_VERIFY_FRI_MERKLE: u32 = 8;
@@ -298,6 +323,19 @@ extern "C" {
                                        err: *mut *mut c_char) -> c_int;
     pub fn zkm_boot_witness(ctx: *mut zkm_ctx, image: *const zkm_boot_image, cpu_rows_out: *mut u64, memory_ops_out: *mut u64,
                             poseidon_inputs_out: *mut u64, poseidon_ts_out: *mut u64, digests_out: *mut u64, err: *mut *mut c_char) -> c_int;
+    // the same calls with the CPU rows built on the device from a compact step log
+    pub fn zkm_cpu_steps_counts(steps: *const zkm_cpu_steps, memory_ops: *mut usize, logic_ops: *mut usize, arithmetic_ops: *mut usize,
+                                err: *mut *mut c_char) -> c_int;
+    pub fn zkm_cpu_witness(ctx: *mut zkm_ctx, steps: *const zkm_cpu_steps, first_clock: u64, log_n: c_uint, cpu_out_dev: *mut u64,
+                           memory_ops_out_dev: *mut u64, logic_ops_out_dev: *mut u32, arithmetic_ops_out_dev: *mut u32,
+                           err: *mut *mut c_char) -> c_int;
+    pub fn zkm_segments_tables_steps(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, images: *const zkm_boot_image,
+                                     steps: *const zkm_cpu_steps, ops: *const zkm_segment_ops, log_n_out: *mut c_uint,
+                                     out: *mut *mut zkm_staged, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_prove_segments_ops_steps(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, images: *const zkm_boot_image,
+                                        steps: *const zkm_cpu_steps, ops: *const zkm_segment_ops, public_values: *const *const u64,
+                                        npublic: *const usize, proofs_out: *const *mut u64, proof_offsets_out: *mut usize,
+                                        ctl_challenges_out: *const *mut u64, err: *mut *mut c_char) -> c_int;
     // what the emulator hashes between two segments: hash pages, root and image id of a memory image
     pub fn zkm_image_hash_plan(dirty_index: *const u32, ndirty: usize, hash_index_out: *mut u32, capacity: usize) -> usize;
     pub fn zkm_image_hash(ctx: *mut zkm_ctx, r#in: *const zkm_image_pages, hash_words_out: *mut u32, page_hash_root_out: *mut u8,

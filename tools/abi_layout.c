@@ -110,9 +110,38 @@ static void print_image_hash(void) {
     printf("\n}\n");
 }
 
+/* `abi_layout steps`: the structs of the step log (tests/test_cpu_steps_abi.py compares them with their mirrors); on request only, as
+ * above. */
+static void print_steps(void) {
+    int first_struct = 1, first_field = 1;
+    int (*counts)(const zkm_cpu_steps*, size_t*, size_t*, size_t*, char**) = 0;
+    int (*witness)(zkm_ctx*, const zkm_cpu_steps*, uint64_t, unsigned, uint64_t*, uint64_t*, uint32_t*, uint32_t*, char**) = 0;
+    int (*tables)(zkm_ctx*, const zkm_stark_config*, size_t, const zkm_boot_image*, const zkm_cpu_steps*, const zkm_segment_ops*, unsigned*,
+                  zkm_staged**, char**) = 0;
+    int (*prove)(zkm_ctx*, const zkm_stark_config*, size_t, const zkm_boot_image*, const zkm_cpu_steps*, const zkm_segment_ops*,
+                 const uint64_t* const*, const size_t*, uint64_t* const*, size_t*, uint64_t* const*, char**) = 0;
+    (void)sizeof(counts = zkm_cpu_steps_counts);
+    (void)sizeof(witness = zkm_cpu_witness);
+    (void)sizeof(tables = zkm_segments_tables_steps);
+    (void)sizeof(prove = zkm_prove_segments_ops_steps);
+    printf("{");
+    BEGIN(zkm_cpu_step);
+    FIELD(zkm_cpu_step, pc); FIELD(zkm_cpu_step, next_pc); FIELD(zkm_cpu_step, insn); FIELD(zkm_cpu_step, kind); FIELD(zkm_cpu_step, flags);
+    FIELD(zkm_cpu_step, context); FIELD(zkm_cpu_step, reads);
+    END();
+    BEGIN(zkm_cpu_steps);
+    FIELD(zkm_cpu_steps, steps); FIELD(zkm_cpu_steps, nsteps); FIELD(zkm_cpu_steps, raw_rows); FIELD(zkm_cpu_steps, nraw);
+    END();
+    printf("\n}\n");
+}
+
 int main(int argc, char** argv) {
     int first_struct = 1, first_field = 1;
     check_segments_ops_prototypes();
+    if (argc > 1 && argv[1][0] == 's') {
+        print_steps();
+        return 0;
+    }
     if (argc > 1 && argv[1][0] == 'i') {
         print_image_hash();
         return 0;

@@ -59,6 +59,7 @@ EXPORTS = [
     "zkm_prove_segments_ops_boot",
     "zkm_image_hash_plan", "zkm_image_hash", "zkm_images_hash",
     "zkm_verify_proofs", "zkm_verify_segments", "zkm_verify_single_table",
+    "zkm_cpu_steps_counts", "zkm_cpu_witness", "zkm_segments_tables_steps", "zkm_prove_segments_ops_steps",
 ]
 
 
@@ -156,6 +157,57 @@ class ImagePagesStruct(C.Structure):
 def abi_mirrors_image_hash():
     """The struct of zkm_image[s]_hash -> its mirror; tests/test_image_hash_abi.py compares it with `tools/abi_layout image`."""
     return {"zkm_image_pages": ImagePagesStruct}
+
+
+# zkm_cpu_step (include/zkm_hip.h): one cycle of the compact step log; STEP_KINDS[k] names ZKM_STEP_<k>, SYSCALL_KINDS the ZKM_SYSCALL_*
+CPU_STEP_DT = np.dtype([("pc", "<u4"), ("next_pc", "<u4"), ("insn", "<u4"), ("kind", "<u4"), ("flags", "<u4"), ("context", "<u4"),
+                        ("reads", "<u4", (6,))])
+STEP_KINDS = ("BINARY_OP", "BINARY_IMM_OP", "LOGIC_OP", "LOGIC_IMM_OP", "SHIFT", "SHIFT_IMM", "BRANCH", "JUMPS", "JUMPI", "JUMPDIRECT", "M_OP_LOAD",
+              "M_OP_STORE", "NOP", "CLZ_OP", "CLO_OP", "SIGNEXT8", "SIGNEXT16", "SWAPHALF", "RDHWR", "MOVZ_OP", "MOVN_OP", "TEQ", "EXT", "INS", "ROR",
+              "MADDU", "SYSCALL", "PAD", "RAW")
+STEP = {name: k for k, name in enumerate(STEP_KINDS)}
+SYSCALL_KINDS = {"other": 0, "mmap": 1, "brk": 2, "clone": 3, "read": 5, "write": 6, "fcntl": 7, "set_thread_area": 8}
+
+
+class CpuStepsStruct(C.Structure):
+    """zkm_cpu_steps: a segment's step list and the ready-made rows its RAW steps index."""
+    _fields_ = [("steps", C.c_void_p), ("nsteps", C.c_size_t), ("raw_rows", C.c_void_p), ("nraw", C.c_size_t)]
+
+
+def abi_mirrors_cpu_steps():
+    """The structs of the step log -> their mirrors; tests/test_cpu_steps_abi.py compares them with `tools/abi_layout steps`."""
+    return {"zkm_cpu_step": CPU_STEP_DT, "zkm_cpu_steps": CpuStepsStruct}
+
+
+class CpuSteps:
+    """A segment's compact step log for Context.cpu_witness / segments_tables_steps / prove_segments_ops_steps (include/zkm_hip.h
+    zkm_cpu_steps).  steps: a CPU_STEP_DT array (host memory); raw_rows: nraw x 259 uint64 (numpy, or a DeviceBuffer with nraw given)."""
+
+    def __init__(self, steps, raw_rows=None, nraw=None):
+        self.steps = np.ascontiguousarray(steps, dtype=CPU_STEP_DT).reshape(-1)
+        if raw_rows is None:
+            raw_rows = np.zeros((0, 259), dtype=np.uint64)
+        self.raw_rows = raw_rows if isinstance(raw_rows, DeviceBuffer) else np.ascontiguousarray(raw_rows, dtype=np.uint64).reshape(-1, 259)
+        self.nraw = int(nraw) if nraw is not None else len(self.raw_rows)
+
+    def struct(self):
+        st = CpuStepsStruct()
+        st.steps, st.nsteps = (self.steps.ctypes.data if self.steps.size else None), self.steps.size
+        st.raw_rows = self.raw_rows.ptr if isinstance(self.raw_rows, DeviceBuffer) else (self.raw_rows.ctypes.data if self.nraw else None)
+        st.nraw = self.nraw
+        return st
+
+    def counts(self):
+        """zkm_cpu_steps_counts: (memory_ops, logic_ops, arithmetic_ops) the steps push; needs no GPU."""
+        return cpu_steps_counts(self)
+
+
+def cpu_steps_counts(steps):
+    """zkm_cpu_steps_counts on a CpuSteps: the lengths of the three lists its steps push.  Every refusal of the host walk (an unknown
+    kind, an encoding the kind does not take, a RAW index out of range) raises ZkmError naming the step."""
+    out, err, st = [C.c_size_t() for _ in range(3)], C.c_char_p(), steps.struct()
+    _check(load().zkm_cpu_steps_counts(C.byref(st), *[C.byref(x) for x in out], C.byref(err)), err)
+    return tuple(int(x.value) for x in out)
 
 
 class CtlLocation(C.Structure):
@@ -329,6 +381,13 @@ def load():
         "zkm_prove_segments_ops_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct),
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                   C.POINTER(C.c_void_p), err]),
+        "zkm_cpu_steps_counts": (C.c_int, [C.POINTER(CpuStepsStruct)] + [C.POINTER(C.c_size_t)] * 3 + [err]),
+        "zkm_cpu_witness": (C.c_int, [cp, C.POINTER(CpuStepsStruct), C.c_uint64, C.c_uint, cp, cp, cp, cp, err]),
+        "zkm_segments_tables_steps": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(CpuStepsStruct),
+                                                C.POINTER(SegmentOpsStruct), C.POINTER(C.c_uint), cpp, err]),
+        "zkm_prove_segments_ops_steps": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(CpuStepsStruct),
+                                                   C.POINTER(SegmentOpsStruct), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), err]),
         "zkm_image_hash_plan": (C.c_size_t, [cp, C.c_size_t, cp, C.c_size_t]),
         "zkm_image_hash": (C.c_int, [cp, C.POINTER(ImagePagesStruct), cp, cp, cp, err]),
         "zkm_images_hash": (C.c_int, [cp, C.c_size_t, C.POINTER(ImagePagesStruct), C.POINTER(C.c_void_p), cp, cp, err]),
@@ -1354,6 +1413,56 @@ class Context:
         _check(self.L.zkm_prove_segments_ops_boot(self.h, C.byref(cfg), m.K, m.im, m.st, m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
         m.alloc()
         _check(self.L.zkm_prove_segments_ops_boot(self.h, C.byref(cfg), m.K, m.im, m.st, m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
+        return m.results()
+
+    # ---- the same calls with the CPU rows built from a compact step log (include/zkm_hip.h "a segment's CPU table from a compact step log")
+    def cpu_witness(self, steps, log_n, first_clock=0):
+        """zkm_cpu_witness: the step kernel alone.  steps: a CpuSteps.  Returns numpy (cpu table 259 * 2^log_n words column-major,
+        memory_ops n x 6 uint64, logic_ops n x 3 uint32, arithmetic_ops n x 3 uint32)."""
+        nm, nl, na = steps.counts()
+        bufs = [self.alloc(max(n, 1)) for n in (259 << log_n, nm * 6, (nl * 3 + 1) // 2, (na * 3 + 1) // 2)]
+        try:
+            st, err = steps.struct(), C.c_char_p()
+            _check(self.L.zkm_cpu_witness(self.h, C.byref(st), first_clock, log_n, *[C.c_void_p(b.ptr) for b in bufs], C.byref(err)), err)
+            return (bufs[0].download()[:259 << log_n], bufs[1].download()[:nm * 6].reshape(nm, 6),
+                    bufs[2].download().view(np.uint32)[:nl * 3].reshape(nl, 3), bufs[3].download().view(np.uint32)[:na * 3].reshape(na, 3))
+        finally:
+            for b in bufs:
+                b.free()
+
+    def cpu_steps_counts(self, steps):
+        """zkm_cpu_steps_counts (module-level cpu_steps_counts: no GPU is involved)."""
+        return cpu_steps_counts(steps)
+
+    def segments_tables_steps(self, steps_list, ops_list, images=None, cfg=None, sizing=False):
+        """zkm_segments_tables_steps: segments_tables[_boot] with each segment's CPU rows built from its CpuSteps; the SegmentOps carry no
+        cpu_rows.  images: one BootImage per segment, or None.  Returns [(staged, log_ns)]; sizing=True: the log heights only."""
+        cfg = cfg or self.standard_config()
+        K = len(ops_list)
+        assert len(steps_list) == K and (images is None or len(images) == K), "one step list (and image) per segment"
+        im = (BootImageStruct * max(K, 1))(*[i.struct() for i in images]) if images is not None else None
+        sl = (CpuStepsStruct * max(K, 1))(*[x.struct() for x in steps_list])
+        st = (SegmentOpsStruct * max(K, 1))(*[o.struct() for o in ops_list])
+        lg, hs, err = (C.c_uint * (12 * max(K, 1)))(), (C.c_void_p * max(K, 1))(), C.c_char_p()
+        _check(self.L.zkm_segments_tables_steps(self.h, C.byref(cfg), K, im, sl, st, lg, None if sizing else hs, C.byref(err)), err)
+        if sizing:
+            return [list(lg[12 * s:12 * s + 12]) for s in range(K)]
+        return [(StagedTrace(self, C.c_void_p(hs[s]), 0), list(lg[12 * s:12 * s + 12])) for s in range(K)]
+
+    def prove_segments_ops_steps(self, steps_list, ops_list, images=None, public_values=None, cfg=None, sizes=None):
+        """zkm_prove_segments_ops_steps: prove_segments_ops[_boot] with each segment's CPU rows built from its CpuSteps.  sizes: as
+        prove_segments_ops takes them (the sizing call is skipped)."""
+        cfg = cfg or self.standard_config()
+        m, err = _marshal_ops(ops_list, public_values, cfg, images), C.c_char_p()
+        assert len(steps_list) == m.K, "one step list per segment"
+        im = m.im if images is not None else None
+        sl = (CpuStepsStruct * max(m.K, 1))(*[x.struct() for x in steps_list])
+        if sizes is None:
+            _check(self.L.zkm_prove_segments_ops_steps(self.h, C.byref(cfg), m.K, im, sl, m.st, m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
+        else:
+            m.offs[:] = [x for o in sizes for x in o]
+        m.alloc()
+        _check(self.L.zkm_prove_segments_ops_steps(self.h, C.byref(cfg), m.K, im, sl, m.st, m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
         return m.results()
 
     def stage_segment_ops(self, ops):

@@ -11,6 +11,10 @@
 //                            caller's lists: the boot's rows are the first of the CPU, Poseidon and PoseidonSponge tables and its
 //                            memory operations the first of the joined list.  Its sponge chains run on the context's side stream
 //                            beside the Memory, Arithmetic and Logic tables; its flags ride on waits (1) and (3).
+//   zkm_*_steps              the same calls with each segment's CPU rows built from its compact step log (cpu_steps.hip) behind the
+//                            bootstrap's rows: the steps' memory, logic and arithmetic operations are written into the joined lists
+//                            in the early phase (Memory and Arithmetic are sized on them), the rows into the zeroed table once the
+//                            output block exists.  No host wait is added; k_cpu_rows_to_cols is not launched for such a segment.
 //
 // The one kernel here, k_cpu_rows_to_cols, turns the emulator's CPU rows (Vec<CpuColumnsView<F>>: 259 words a row, row-major) into the
 // column-major table of trace_rows_to_poly_values (util.rs:37-46), canonical.  Every other table comes from its existing launcher;
@@ -199,6 +203,10 @@ struct builder {
     const zkm_segment_ops* o;     // the caller's lists
     const zkm_boot_image* im;     // the image whose bootstrap goes in front of them, or null
     zkm_boot_counts_t bn{};       // ... and what it adds to each list (zeros without an image)
+    const zkm_cpu_steps* st;      // the step log the CPU rows are built from (behind the bootstrap's, in place of the caller's), or null
+    zkm_steps_counts_t sn{};      // ... and what it adds to the Memory, Logic and Arithmetic lists, behind the bootstrap's part
+    std::vector<uint32_t> step_base;   // ... where each workgroup of steps starts in them (cpu_steps.hip)
+    const void *d_steps = nullptr, *d_step_base = nullptr, *d_raw = nullptr;   // device copies of the steps, the bases and the RAW rows
     zkm_segment_ops d{};          // ... and where the device reads them: the caller's device pointers, or places in the staging block
     unsigned lg[NTAB] = {};
     std::vector<uint64_t> ps_row, ks_row;   // first row of each sponge operation
@@ -212,11 +220,15 @@ struct builder {
     size_t cpu_off = 0, piece_rows = 0;
     std::vector<zkm_event> piece_done;
 
-    builder(const char* entry, zkm_ctx* ctx, const zkm_segment_ops* ops, size_t pos, bool label, const zkm_boot_image* image = nullptr)
-        : what(label ? std::string(entry) + ": segment " + std::to_string(pos) : std::string(entry)), c(ctx), o(ops), im(image) {}
-    size_t nmemory() const { return bn.memory_ops + o->nmemory; }
+    builder(const char* entry, zkm_ctx* ctx, const zkm_segment_ops* ops, size_t pos, bool label, const zkm_boot_image* image = nullptr,
+            const zkm_cpu_steps* steps = nullptr)
+        : what(label ? std::string(entry) + ": segment " + std::to_string(pos) : std::string(entry)), c(ctx), o(ops), im(image), st(steps) {}
+    size_t nmemory() const { return bn.memory_ops + sn.mem + o->nmemory; }
+    size_t nlogic() const { return sn.logic + o->nlogic; }
+    size_t narithmetic() const { return sn.arith + o->narithmetic; }
     size_t nposeidon() const { return bn.poseidon + o->nposeidon; }
-    size_t ncpu_rows() const { return bn.cpu_rows + o->ncpu_rows; }
+    size_t nsteps() const { return st ? st->nsteps : 0; }
+    size_t ncpu_rows() const { return bn.cpu_rows + nsteps() + o->ncpu_rows; }
 
     [[noreturn]] void refuse(int t, const std::string& msg) const { throw std::runtime_error(what + ": " + zkm_table_at(t)->name + ": " + msg); }
     // a height of max(rows, min_rows) rounded up to a power of two; rows = count x per, refused above 2^SEG_MAX_LOG_N
@@ -246,7 +258,8 @@ struct builder {
         return row_off[nops];
     }
 
-    // ---- phase: every check that needs no device (zkm_segment_ops_stage runs it too)
+    // ---- phase: every check that needs no device (zkm_segment_ops_stage runs it too).  This phase and heights() never use `c`: the
+    // *_steps calls run both without a context (steps_without_context), so that the host's refusals can be made where there is no GPU
     void check_host() {
         const zkm_segment_ops& o = *this->o;
         need(CPU, o.ncpu_rows, {o.cpu_rows});
@@ -263,13 +276,21 @@ struct builder {
                 refuse(CPU, std::string("bootstrap image: ") + e.what());
             }
         }
+        if (st) {
+            if (o.cpu_rows || o.ncpu_rows) refuse(CPU, "cpu_rows must be NULL with ncpu_rows 0: the steps take their place");
+            try {
+                zkm_cpu_steps_walk(st, &sn, &step_base);
+            } catch (const std::exception& e) {
+                refuse(CPU, e.what());
+            }
+        }
         const size_t rows = ncpu_rows();
-        if (o.ncpu_rows == 0 || (rows & (rows - 1)) || rows > ((size_t)1 << SEG_MAX_LOG_N))
+        if ((st ? st->nsteps : o.ncpu_rows) == 0 || (rows & (rows - 1)) || rows > ((size_t)1 << SEG_MAX_LOG_N))
             refuse(CPU, std::to_string(rows) + " rows" + (im ? " (" + std::to_string(bn.cpu_rows) + " of the bootstrap)" : std::string()) +
                             ": not a power of two of at most 2^" + std::to_string(SEG_MAX_LOG_N));
         if (nmemory() == 0) refuse(ME, "No memory ops?");
         if (nmemory() >= ((size_t)1 << 32)) refuse(ME, "2^32 or more memory ops");
-        if (o.narithmetic >= ((size_t)1 << 31)) refuse(AR, "2^31 or more arithmetic ops");
+        if (narithmetic() >= ((size_t)1 << 31)) refuse(AR, "2^31 or more arithmetic ops");
         ps_rows = sponge_rows(PS, o.poseidon_sponge_off, o.nposeidon_sponge, 32, ps_row) + bn.poseidon;
         for (uint64_t& r : ps_row) r += bn.poseidon;      // the bootstrap's sponge rows come first
         ks_rows = sponge_rows(KS, o.keccak_sponge_off, o.nkeccak_sponge, 136, ks_row);
@@ -287,7 +308,8 @@ struct builder {
         lg[PO] = height(PO, nposeidon(), 1, min_rows);
         lg[PS] = height(PS, ps_rows, 1, min_rows);
         lg[KS] = height(KS, ks_rows, 1, min_rows);
-        lg[AR] = height(AR, o.narithmetic, 1, (size_t)1 << 16);
+        lg[LO] = height(LO, nlogic(), 1, min_rows);
+        lg[AR] = height(AR, narithmetic(), 1, (size_t)1 << 16);
         lg[CPU] = log2_of(ncpu_rows());
         lg[ME] = height(ME, nmemory(), 1, 1);
     }
@@ -296,9 +318,9 @@ struct builder {
     size_t plan(bool write, size_t base) {
         const zkm_segment_ops& o = *this->o;
         d = o;
-        d_pso = d_psr = d_kso = d_ksr = nullptr;
+        d_pso = d_psr = d_kso = d_ksr = d_steps = d_step_base = d_raw = nullptr;
         ups.clear();
-        cpu_host = write && !zkm_is_device_ptr(o.cpu_rows);
+        cpu_host = write && o.ncpu_rows && !zkm_is_device_ptr(o.cpu_rows);
         cpu_off = base;
         size_t at = base + align_up(cpu_host ? o.ncpu_rows * CPU_W * 8 : 0);
         auto add = [&](const list_ref& l, const void* src, size_t skip = 0) {
@@ -306,12 +328,21 @@ struct builder {
             ups.push_back(upload{l, src, at, skip});
             at += align_up(l.bytes + skip);
         };
-        // the lists the bootstrap writes the head of are joined in the staging block, wherever the caller's part lies
+        // the lists the bootstrap and the steps write the head of are joined in the staging block, wherever the caller's part lies
         for (const list_ref& l : lists_of(d)) {
-            const size_t skip = l.field == (void*)&d.memory_ops ? bn.memory_ops * 48
+            const size_t skip = l.field == (void*)&d.memory_ops ? (bn.memory_ops + sn.mem) * 48
+                                : l.field == (void*)&d.arithmetic_ops ? sn.arith * 12
+                                : l.field == (void*)&d.logic_ops ? sn.logic * 12
                                 : l.field == (void*)&d.poseidon_inputs ? bn.poseidon * 96
                                 : l.field == (void*)&d.poseidon_timestamps ? bn.poseidon * 8 : 0;
             if (skip || !zkm_is_device_ptr(l.get())) add(l, l.get(), skip);
+        }
+        // the steps, their workgroups' bases and the RAW rows that lie in host memory: read by the launch that sizes Memory and Arithmetic
+        if (st) {
+            add(list_ref{&d_steps, st->nsteps * sizeof(zkm_cpu_step), true}, st->steps);
+            add(list_ref{&d_step_base, step_base.size() * 4, true}, step_base.data());
+            d_raw = st->raw_rows;
+            if (st->nraw && !zkm_is_device_ptr(st->raw_rows)) add(list_ref{&d_raw, st->nraw * CPU_W * 8, true}, st->raw_rows);
         }
         const size_t nps = o.nposeidon_sponge ? (o.nposeidon_sponge + 1) * 8 : 0, nks = o.nkeccak_sponge ? (o.nkeccak_sponge + 1) * 8 : 0;
         add(list_ref{&d_pso, nps, false}, o.poseidon_sponge_off);
@@ -350,6 +381,12 @@ struct builder {
             if (u.skip) u.dst.set(sb + u.off);
     }
     size_t n(int t) const { return (size_t)1 << lg[t]; }
+    // the steps' descriptor: their operations lie behind the bootstrap's in the joined lists (`logic`: null where the list is not staged)
+    zkm_steps_seg steps_seg(gl_t* cpu, bool logic) const {
+        return zkm_steps_seg{(const zkm_cpu_step*)d_steps, (const uint32_t*)d_step_base, (const uint64_t*)d_raw, st->nsteps, n(CPU), bn.cpu_rows,
+                             bn.cpu_rows, cpu, (uint64_t*)d.memory_ops + 6 * bn.memory_ops, logic ? (uint32_t*)d.logic_ops : nullptr,
+                             (uint32_t*)d.arithmetic_ops};
+    }
 };
 
 constexpr size_t SYNC_WORDS = 16;   // per segment: [0, 5) Memory key widths and >= p flag, [5] Memory last op with dummies, [6] Memory row count,
@@ -403,8 +440,8 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     bj.reserve(K);
     for (size_t s = 0; s < K; s++) {
         bj.emplace_back(c, b[s].im);
+        if (b[s].im || b[s].st) b[s].point_joined(sb);
         if (!b[s].im) continue;
-        b[s].point_joined(sb);
         bj[s].prepare();
         bj[s].d.flags = (unsigned long long*)(d_sync + s * SYNC_WORDS + 11);
         bj[s].d.mem = (uint64_t*)b[s].d.memory_ops;
@@ -424,6 +461,15 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
         chains_done.record(st);
     }
 
+    // ---- the steps' memory, logic and arithmetic operations, behind the bootstrap's in the joined lists (Memory and Arithmetic are sized
+    // on them); the rows follow once the table exists
+    size_t nstep = 0;
+    {
+        zkm_steps_seg ss[ZKM_MAX_SEG];
+        for (size_t s = 0; s < K; s++)
+            if (b[s].st) ss[nstep++] = b[s].steps_seg(nullptr, write);
+        if (nstep) zkm_cpu_steps_launch(c, ss, nstep, false, true);
+    }
     // ---- Memory and Arithmetic sizing phases; waits (1) and (2)
     std::vector<zkm_memory_job> mj;
     std::vector<zkm_arith_job> aj;
@@ -433,7 +479,7 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
         b[s].me_what = b[s].what + ": " + zkm_table_at(ME)->name;
         b[s].ar_what = b[s].what + ": " + zkm_table_at(AR)->name;
         mj.emplace_back(c, b[s].me_what.c_str(), b[s].d.memory_ops, b[s].nmemory());
-        aj.emplace_back(c, b[s].ar_what.c_str(), b[s].d.arithmetic_ops, b[s].o->narithmetic);
+        aj.emplace_back(c, b[s].ar_what.c_str(), b[s].d.arithmetic_ops, b[s].narithmetic());
         mj[s].d_acc = (unsigned long long*)(d_sync + s * SYNC_WORDS);
         mj[s].d_count = d_sync + s * SYNC_WORDS + 6;
         aj[s].d_counts = d_sync + s * SYNC_WORDS + 7;
@@ -468,6 +514,9 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     for (size_t s = 0; s < K; s++) {
         b[s].put(sb, false);
         out[s].block = zkm_scratch(c, out[s].off[NTAB] * sizeof(gl_t));
+        // (a CPU table built from steps: the kinds store the cells they set over zeros)
+        if (b[s].st)
+            ZKM_HIP_CHECK(hipMemsetAsync(out[s].block.as<gl_t>() + out[s].off[CPU], 0, (out[s].off[CPU + 1] - out[s].off[CPU]) * sizeof(gl_t), c->stream));
     }
     auto T = [&](size_t s, int t) { return out[s].block.as<gl_t>() + out[s].off[t]; };
     auto flag = [&](size_t s, int k) { return (unsigned*)(d_sync + s * SYNC_WORDS + 9) + k; };   // 0 Logic, 1 Memory, 2 Arithmetic
@@ -518,7 +567,7 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     writers(KK, [](size_t, W) {});
     writers(KS, [&](size_t s, W w) { w.in[1] = b[s].d_kso; w.in[3] = b[s].d_ksr; w.aux = b[s].ks_rows; });
     for (const int t : {SE, SES, SC, SCS}) writers(t, [](size_t, W) {});
-    writers(LO, [&](size_t s, W w) { w.bad = (int*)flag(s, 0); });
+    writers(LO, [&](size_t s, W w) { w.k = b[s].nlogic(); w.bad = (int*)flag(s, 0); });
     {
         unsigned lg[ZKM_MAX_SEG];
         gl_t* o[ZKM_MAX_SEG];
@@ -528,11 +577,18 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     }
     // the CPU table: device-resident rows of every segment in one launch; host rows piece by piece, each behind its own copy (last: the
     // copies overlap everything above)
+    if (nstep) {
+        zkm_steps_seg ss[ZKM_MAX_SEG];
+        size_t k = 0;
+        for (size_t s = 0; s < K; s++)
+            if (b[s].st) ss[k++] = b[s].steps_seg(T(s, CPU), false);
+        zkm_cpu_steps_launch(c, ss, k, true, false);
+    }
     {
         cpu_seg cs[ZKM_MAX_SEG];
         size_t nd = 0;
         for (size_t s = 0; s < K; s++)
-            if (!b[s].cpu_host) cs[nd++] = cpu_seg{b[s].d.cpu_rows, b[s].o->ncpu_rows, b[s].bn.cpu_rows, b[s].n(CPU), T(s, CPU)};
+            if (!b[s].cpu_host && !b[s].st) cs[nd++] = cpu_seg{b[s].d.cpu_rows, b[s].o->ncpu_rows, b[s].bn.cpu_rows, b[s].n(CPU), T(s, CPU)};
         if (nd) launch_cpu_rows_to_cols(c, cs, nd);
         for (size_t s = 0; s < K; s++) {
             if (!b[s].cpu_host) continue;
@@ -559,14 +615,14 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
 // the builders of a call: argument checks, every host check of every segment, the host-known heights.  A call of one segment through
 // the one-segment entry points names no position (label = false).
 std::vector<builder> make_builders(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, const zkm_segment_ops* ops, size_t nseg, size_t seg_base,
-                                   bool label, const zkm_boot_image* images = nullptr) {
+                                   bool label, const zkm_boot_image* images = nullptr, const zkm_cpu_steps* steps = nullptr) {
     if (!cfg || !ops) throw std::runtime_error(std::string(what) + ": null argument");
     if (nseg == 0) throw std::runtime_error(std::string(what) + ": no segments");
     if (cfg->cap_height > SEG_MAX_LOG_N) throw std::runtime_error(std::string(what) + ": cap_height out of range");
     std::vector<builder> b;
     b.reserve(nseg);
     for (size_t s = 0; s < nseg; s++) {
-        b.emplace_back(what, c, ops + s, seg_base + s, label, images ? images + s : nullptr);
+        b.emplace_back(what, c, ops + s, seg_base + s, label, images ? images + s : nullptr, steps ? steps + s : nullptr);
         b.back().check_host();
         b.back().heights(cfg);
     }
@@ -601,10 +657,10 @@ extern "C" {
 
 // the body of zkm_segments_tables[_boot] (images: one per segment, or null)
 static int segments_tables(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
-                           const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out, char** err) {
+                           const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out, char** err, const zkm_cpu_steps* steps = nullptr) {
     return zkm_api(what, c, err, [&] {
         if (!log_n_out) throw std::runtime_error(std::string(what) + ": null argument");
-        std::vector<builder> b = make_builders(what, c, cfg, ops, nseg, 0, true, images);
+        std::vector<builder> b = make_builders(what, c, cfg, ops, nseg, 0, true, images, steps);
         std::vector<segment_block> blocks;   // (a failure in a later wave releases the earlier waves' blocks: no handle is left behind)
         size_t s0 = 0;
         for (const size_t k : even_waves(nseg, 1)) {
@@ -637,14 +693,30 @@ int zkm_segments_tables_boot(zkm_ctx* c, const zkm_stark_config* cfg, size_t nse
     return segments_tables("zkm_segments_tables_boot", c, cfg, nseg, images, ops, log_n_out, out, err);
 }
 
-// the body of zkm_prove_segments_ops[_boot] and of the pool's workers (images: one per segment, or null)
+// A *_steps call without a context still makes every refusal that needs no device -- the walk over the steps among them -- before it
+// reports the missing context: what the host decides can be checked where there is no GPU.
+static int steps_without_context(const char* what, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_cpu_steps* steps,
+                                 const zkm_segment_ops* ops, char** err) {
+    return zkm_api(what, err, [&] {
+        make_builders(what, nullptr, cfg, ops, nseg, 0, true, images, steps);
+        throw std::runtime_error(std::string(what) + ": null argument");
+    });
+}
+int zkm_segments_tables_steps(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_cpu_steps* steps,
+                              const zkm_segment_ops* ops, unsigned* log_n_out, zkm_staged** out, char** err) {
+    if (!steps) return zkm_fail(err, "zkm_segments_tables_steps: null argument");
+    if (!c) return steps_without_context("zkm_segments_tables_steps", cfg, nseg, images, steps, ops, err);
+    return segments_tables("zkm_segments_tables_steps", c, cfg, nseg, images, ops, log_n_out, out, err, steps);
+}
+
+// the body of zkm_prove_segments_ops[_boot | _steps] and of the pool's workers (images, steps: one per segment, or null)
 static int prove_segments_ops(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
                               const zkm_segment_ops* ops, const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs,
-                              size_t* offsets_out, uint64_t* const* challenges, char** err, size_t seg_base) {
+                              size_t* offsets_out, uint64_t* const* challenges, char** err, size_t seg_base, const zkm_cpu_steps* steps = nullptr) {
     return zkm_api(what, c, err, [&]() -> int {
         if (proofs && !challenges) throw std::runtime_error(std::string(what) + ": null argument");
         if (!proofs && !offsets_out) throw std::runtime_error(std::string(what) + ": null argument");
-        std::vector<builder> b = make_builders(what, c, cfg, ops, nseg, seg_base, true, images);
+        std::vector<builder> b = make_builders(what, c, cfg, ops, nseg, seg_base, true, images, steps);
         // ---- the waves: what a segment holds while it is proven (the prover's estimate at the heights the host knows), its tables,
         // its part of the staging block and its bootstrap's scratch, against the budget of zkm_prove_segments
         size_t nwaves = 1;
@@ -699,6 +771,14 @@ int zkm_prove_segments_ops_boot(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
                                 uint64_t* const* challenges, char** err) {
     if (!images) return zkm_fail(err, "zkm_prove_segments_ops_boot: null argument");
     return prove_segments_ops("zkm_prove_segments_ops_boot", c, cfg, nseg, images, ops, pub, npub, proofs, offsets_out, challenges, err, 0);
+}
+
+int zkm_prove_segments_ops_steps(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_cpu_steps* steps,
+                                 const zkm_segment_ops* ops, const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs,
+                                 size_t* offsets_out, uint64_t* const* challenges, char** err) {
+    if (!steps) return zkm_fail(err, "zkm_prove_segments_ops_steps: null argument");
+    if (!c) return steps_without_context("zkm_prove_segments_ops_steps", cfg, nseg, images, steps, ops, err);
+    return prove_segments_ops("zkm_prove_segments_ops_steps", c, cfg, nseg, images, ops, pub, npub, proofs, offsets_out, challenges, err, 0, steps);
 }
 
 // the body of zkm_segment_tables[_boot] (image: or null)

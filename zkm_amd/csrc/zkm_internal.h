@@ -546,6 +546,24 @@ void zkm_boot_late(zkm_ctx* c, zkm_boot_job* j, size_t nseg, zkm_boot_seg* d_des
 std::string zkm_boot_refusal_early(const zkm_boot_job& j, const uint64_t flags[4]);    // "" or the message (flags 0, 1: known after early)
 std::string zkm_boot_refusal_late(const zkm_boot_job& j, const uint64_t flags[4]);     // flags 2, 3: known after late
 
+// ---- cpu_steps.hip: CPU rows and the operations they push from the compact step log.  The host walk makes every refusal (throws the
+// bare message, "step <i>: ..."), counts the three lists and gives the base of each workgroup of ZKM_CPU_STEPS_BLOCK steps in them (three
+// words a workgroup; `base` may be null); one descriptor per segment for the launch.
+struct zkm_steps_counts_t { size_t mem = 0, logic = 0, arith = 0; };
+void zkm_cpu_steps_walk(const zkm_cpu_steps* steps, zkm_steps_counts_t* n, std::vector<uint32_t>* base);
+struct zkm_steps_seg {
+    const zkm_cpu_step* steps;   // device
+    const uint32_t* base;        // device: the walk's base triples
+    const uint64_t* raw;         // device: the ready-made rows of the RAW steps
+    size_t nsteps, n, row0;      // step i is row row0 + i of the n-row column-major table at `out` ...
+    uint64_t clock0;             // ... with clock clock0 + i
+    gl_t* out;                   // (rows = false: unused)
+    uint64_t* mem;               // where the steps' first operation of each list goes (a null list is not written; lists = false: unused)
+    uint32_t *logic, *arith;
+};
+// nseg <= ZKM_MAX_SEG segments of one context, ONE launch: the rows (over a zeroed table), the lists, or both
+void zkm_cpu_steps_launch(zkm_ctx* c, const zkm_steps_seg* segs, size_t nseg, bool rows, bool lists);
+
 // ctl_check.hip: check_ctls on one segment's tables.  Returns the report's kind (0 consistent, 1 non-binary filter, 2 multisets differ)
 // with the reference's message in *msg; throws when the check cannot be made
 int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
