@@ -889,8 +889,8 @@ int zkm_boot_witness(zkm_ctx* ctx, const zkm_boot_image* image, uint64_t* cpu_ro
 #define ZKM_SYSCALL_WRITE 6
 #define ZKM_SYSCALL_FCNTL 7
 #define ZKM_SYSCALL_SET_THREAD_AREA 8
-/* (Layout lock: `tools/abi_layout steps` prints these two structs, tests/test_cpu_steps_abi.py compares them with the numpy, ctypes and
- * Rust mirrors.) */
+/* (Layout lock: tests/test_abi.py compares these two structs, like every struct of this header, as the C compiler lays them out with
+ * the numpy, ctypes and Rust mirrors.) */
 typedef struct zkm_cpu_step { uint32_t pc, next_pc, insn, kind, flags, context; uint32_t reads[6]; } zkm_cpu_step;   /* 48 bytes */
 typedef struct zkm_cpu_steps { const zkm_cpu_step* steps; size_t nsteps; const uint64_t* raw_rows; size_t nraw; } zkm_cpu_steps;
 int zkm_cpu_steps_counts(const zkm_cpu_steps* steps, size_t* memory_ops, size_t* logic_ops, size_t* arithmetic_ops, char** err);
@@ -1075,8 +1075,8 @@ int zkm_check_constraints(zkm_ctx* ctx, int table_id, const zkm_stark_config* cf
  * zkm_segment_check_ctls: the same for the AllStark that ships with the library, traces[t] / log_n[t] of Table::all()[t] as
  * zkm_prove_segment takes them -- e.g. the twelve device pointers of zkm_staged_segment_ptrs for a block zkm_segment_tables built.
  * Both run on the context's stream, behind what is queued there.  A debugging aid: on the proving path only under "check_ctls". */
-/* (Layout lock: `tools/abi_layout check_ctls` prints these two structs, tests/test_check_ctls_abi.py compares them with the ctypes and
- * Rust mirrors.) */
+/* (Layout lock: tests/test_abi.py compares these two structs, like every struct of this header, as the C compiler lays them out with
+ * the ctypes and Rust mirrors.) */
 #define ZKM_CTL_REPORT_WORDS 64
 #define ZKM_CTL_REPORT_LOCATIONS 8
 typedef struct zkm_ctl_location { uint32_t side, table; uint64_t row; } zkm_ctl_location;
@@ -1114,7 +1114,7 @@ int zkm_segment_check_ctls(zkm_ctx* ctx, const uint64_t* const* traces, const un
  * challenge), POW, then the lowest query and inside it trace tree, auxiliary tree, quotient tree, per layer evaluation before Merkle
  * path, the final polynomial; CTL_SUM (lowest lookup, lowest challenge) only when every table passes.  A blob with a SHAPE finding in
  * any table is reported as SHAPE at that table and nothing of its segment is launched.
- * (Layout lock: `tools/abi_layout verify` prints the struct, tests/test_verify_abi.py compares it with the ctypes and Rust mirrors.) */
+ * (Layout lock: tests/test_abi.py compares the struct, like every struct of this header, with the ctypes and Rust mirrors.) */
 #define ZKM_VERIFY_OK 0
 #define ZKM_VERIFY_SHAPE 1
 #define ZKM_VERIFY_TRANSCRIPT_STATE 2

@@ -6,7 +6,7 @@
 //!     println!("cargo:rustc-link-search=native={}", std::env::var("ZKM_HIP_LIB_DIR").unwrap());
 //!     println!("cargo:rustc-link-lib=dylib=zkmhip");
 //! NOT COMPILED in the build image (no cargo / rustc there); checked against the header by eye and by
-//! tests/test_abi.py::test_rust_sys_block_names_every_export.
+//! tests/test_abi.py (every declaration, struct layout and constant).
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_double, c_int, c_uint, c_void};
 
@@ -80,9 +80,8 @@ pub struct zkm_segment_ops {
     pub nsha_compress_sponge: usize,
 }
 pub type ZkmSegmentOps = zkm_segment_ops;
-// (The two structs of zkm_check_ctls carry Rust-style names, with the C names as aliases: the snake-case #[repr(C)] structs of this
-// file are the fixed set tests/test_abi.py compares with tools/abi_layout.c's plain output; these two are compared with
-// `abi_layout check_ctls` by tests/test_check_ctls_abi.py.)
+// (The structs from here on carry Rust-style names, with the C names as aliases; tests/test_abi.py compares every struct of this file,
+// under its C name, with the C compiler's layout of the header.)
 /// one occurrence of a tuple zkm_check_ctls reports: side of the lookup (the looked side last), index of the table, row
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct ZkmCtlLocation { pub side: u32, pub table: u32, pub row: u64 }
@@ -101,14 +100,14 @@ pub struct ZkmCtlReport {
     pub looking: [ZkmCtlLocation; 8], pub looked: [ZkmCtlLocation; 8],
 }
 pub type zkm_ctl_report = ZkmCtlReport;
-/// the verdict of zkm_verify_* on one proof (include/zkm_hip.h; compared with `abi_layout verify` by tests/test_verify_abi.py):
+/// the verdict of zkm_verify_* on one proof (include/zkm_hip.h):
 /// code = ZKM_VERIFY_*, the check that failed, in the reference's order of checks
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct ZkmVerifyReport {
     pub code: u32, pub table: u32, pub challenge: u32, pub query: u32, pub tree: u32, pub layer: u32, pub ctl: u32, pub host_waits: u32,
 }
 pub type zkm_verify_report = ZkmVerifyReport;
-/// a segment's memory image for the zkm_*_boot calls (include/zkm_hip.h; compared with `abi_layout boot` by tests/test_boot_abi.py):
+/// a segment's memory image for the zkm_*_boot calls (include/zkm_hip.h):
 /// the bootstrap kernel's part of Traces is built from it on the device
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct ZkmBootImage {
@@ -116,16 +115,15 @@ pub struct ZkmBootImage {
     pub pre_hash_root: [u8; 32], pub pre_image_id: [u8; 32],
 }
 pub type zkm_boot_image = ZkmBootImage;
-/// the dirty pages of a split, the hash pages that exist already, pc and the registers for zkm_image[s]_hash (include/zkm_hip.h;
-/// compared with `abi_layout image` by tests/test_image_hash_abi.py)
+/// the dirty pages of a split, the hash pages that exist already, pc and the registers for zkm_image[s]_hash (include/zkm_hip.h)
 #[repr(C)] #[derive(Clone, Copy, Debug)]
 pub struct ZkmImagePages {
     pub dirty_index: *const u32, pub ndirty: usize, pub dirty_words: *const u32, pub known_index: *const u32, pub nknown: usize,
     pub known_words: *const u32, pub pc: u32, pub registers: [u8; 156],
 }
 pub type zkm_image_pages = ZkmImagePages;
-/// one cycle of the compact step log and a segment's step list (include/zkm_hip.h; compared with `abi_layout steps` by
-/// tests/test_cpu_steps_abi.py): the CPU rows and the operations they push are built from them on the device
+/// one cycle of the compact step log and a segment's step list (include/zkm_hip.h): the CPU rows and the operations they push are built
+/// from them on the device
 #[repr(C)] #[derive(Clone, Copy, Debug, Default)]
 pub struct ZkmCpuStep {
     pub pc: u32, pub next_pc: u32, pub insn: u32, pub kind: u32, pub flags: u32, pub context: u32, pub reads: [u32; 6],
@@ -212,7 +210,7 @@ extern "C" {
     pub fn zkm_poseidon_permute_batch(ctx: *mut zkm_ctx, states: *mut u64, k: usize, err: *mut *mut c_char) -> c_int;
     pub fn zkm_keccakf_batch(ctx: *mut zkm_ctx, states: *mut u64, k: usize, err: *mut *mut c_char) -> c_int;
     /// parity / debug: one piece of the device's Poseidon permutation on chosen words (probe: ZKM_POSEIDON_PROBE_*, arg: see the header)
-    pub fn zkm_poseidon_selftest(ctx: *mut zkm_ctx, probe: u32, arg: u32, input: *const u64, n: usize, out: *mut u64, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_poseidon_selftest(ctx: *mut zkm_ctx, probe: u32, arg: u32, r#in: *const u64, n: usize, out: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_consumer_selftest(ctx: *mut zkm_ctx, alphas: *const u64, nalphas: usize, terms: *const u64, K: usize, n: usize, run: u32, out: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_poseidon_trace(ctx: *mut zkm_ctx, seed: u64, num_perms: usize, log_n: c_uint, out_dev: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_poseidon_trace_inputs(ctx: *mut zkm_ctx, inputs: *const u64, timestamps: *const u64, num_perms: usize, log_n: c_uint,

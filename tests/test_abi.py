@@ -1,29 +1,95 @@
-"""CPU suite: the C-ABI library loads and exports every symbol include/zkm_hip.h declares; host-side
+"""CPU suite: the lock on the C ABI.  include/zkm_hip.h is its only statement (zkm_amd/abi.py reads it, the ctypes binding is derived from
+it); three independent judges are held against it here, for every function, struct and constant at once: the C compiler (the layout
+probe), the linker (`nm -D` of libzkmhip.so) and the hand-written Rust block integration/rust/zkm_hip_sys.rs.  Below that: host-side
 transcript code (no GPU needed) agrees with the oracle."""
 import ctypes as C
+import functools
+import glob
 import itertools
+import json
 import os
 import re
+import subprocess
+import tempfile
 
 import numpy as np
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RUST_SYS = os.path.join(ROOT, "integration", "rust", "zkm_hip_sys.rs")
 
 
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "zkm_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(zkm_[a-z0-9_]+)\s*\(", text)))
+def read(*path):
+    return open(os.path.join(ROOT, *path)).read()
+
+
+def header_text():
+    """include/zkm_hip.h without its comments."""
+    return re.sub(r"/\*.*?\*/", " ", read("include", "zkm_hip.h"), flags=re.S)
+
+
+def prototypes():
+    """{function: (return type, [(parameter type, parameter name)])} of the header."""
+    from zkm_amd import abi
+    return {name: (ret, params) for name, ret, params in abi.prototypes()}
+
+
+def rust_sys_text():
+    return re.sub(r"//[^\n]*", "", open(RUST_SYS).read())
+
+
+# extern "C" functions one file of csrc/ calls in another (csrc/zkm_internal.h): visible to the linker, no part of the C ABI
+LINKAGE_ONLY = {"zkm_prove_segments_entry", "zkm_prove_segments_ops_entry", "zkm_staged_from_segment"}
 
 
 def test_library_exports_every_declared_symbol(zkm):
+    """The linker's list of the library's zkm_* functions, the header's prototypes and the binding's EXPORTS are one set; the header
+    reader saw every `typedef struct` (a struct or a handle it skipped would leave the locks below with a hole)."""
     lib = zkm.load()
-    names = header_functions()
-    assert len(names) >= 30
-    for n in names:
-        assert hasattr(lib, n), "libzkmhip.so does not export %s" % n
-    assert set(names) == set(zkm.EXPORTS), set(names) ^ set(zkm.EXPORTS)
+    names = [n for n, _, _ in zkm.abi.prototypes()]
+    assert len(names) == len(set(names)) >= 129 and names == zkm.EXPORTS
+    dynamic = subprocess.check_output(["nm", "-D", "--defined-only", zkm._LIB_PATH], text=True)
+    assert set(re.findall(r" T (zkm_\w+)", dynamic)) - LINKAGE_ONLY == set(names), (set(re.findall(r" T (zkm_\w+)", dynamic)) - LINKAGE_ONLY) ^ set(names)
+    assert len(re.findall(r"\btypedef\s+struct\b", header_text())) == len(zkm.abi.structs()) + len(zkm.abi.opaque())
+    assert zkm.abi.opaque() == ["zkm_ctx", "zkm_batch", "zkm_staged", "zkm_staged_ops", "zkm_pool"]
     assert b"gfx950" in lib.zkm_version()
+
+
+# the binding's own statement of the C types, independent of zkm_amd's: scalars and returns exactly, pointers by kind
+C_TO_CTYPES = {"int": C.c_int, "unsigned": C.c_uint, "size_t": C.c_size_t, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "void": None}
+C_TYPED_POINTEES = {"size_t": C.c_size_t, "unsigned": C.c_uint, "int": C.c_int, "double": C.c_double}
+
+
+def test_python_binding_has_the_headers_types_for_every_function(zkm):
+    """restype and every argtype of the ctypes binding against the header, by a table of this file's own: scalars and scalar returns exactly;
+    `const char*` is c_char_p; a pointer return is c_void_p; every pointer parameter is c_void_p or a ctypes pointer, typed where the
+    pointee is a count (size_t / unsigned / int / double), the struct's mirror where the struct is passed by reference, and never typed
+    where it is a data word (device addresses are passed as integers)."""
+    lib, mirrors = zkm.load(), zkm.abi_mirrors()
+    checked = 0
+    for name, (ret, params) in prototypes().items():
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == len(params), name
+        if "*" not in ret:
+            assert fn.restype is C_TO_CTYPES[ret], (name, ret)
+        else:
+            assert fn.restype is (C.c_char_p if ret == "const char*" else C.c_void_p), (name, ret)
+        for got, (ty, arg) in zip(fn.argtypes, params):
+            base, stars = ty.replace("const ", "").replace(" const", "").rstrip("*"), ty.count("*")
+            if stars == 0:
+                assert got is C_TO_CTYPES[base] and got is not None, (name, arg, ty)
+            elif base == "char":
+                assert got is {"const char*": C.c_char_p, "char**": C.POINTER(C.c_char_p), "const char**": C.POINTER(C.c_char_p)}[ty], (name, arg)
+            elif stars > 1:
+                assert got is C.POINTER(C.c_void_p), (name, arg, ty)
+            elif base in C_TYPED_POINTEES:
+                assert got is C.POINTER(C_TYPED_POINTEES[base]), (name, arg, ty)
+            elif base in zkm.BY_REFERENCE:
+                assert issubclass(got, C._Pointer) and got._type_ is mirrors[base], (name, arg, ty)
+            else:
+                assert got is C.c_void_p and (base in ("void", "uint8_t", "uint32_t", "uint64_t") or base in mirrors or base in zkm.abi.opaque()), (name, arg, ty)
+            checked += 1
+    assert checked >= 737
 
 
 def test_no_gpu_fails_loudly(zkm):
@@ -208,97 +274,79 @@ def test_prove_segment_sizing_and_descriptors(zkm, oracle):
     assert lib.zkm_prove_segment(None, C.byref(cfg), ptrs, lg, None, 0, None, offs, None, C.byref(err)) != 0
 
 
-def test_rust_sys_block_names_every_export(zkm):
-    """integration/rust/zkm_hip_sys.rs (the extern "C" block a maintainer adds to the plonky2 fork) declares exactly the exported
-    functions of include/zkm_hip.h."""
-    text = open(os.path.join(ROOT, "integration", "rust", "zkm_hip_sys.rs")).read()
-    rust = set(re.findall(r"pub fn (zkm_[a-z0-9_]+)\s*\(", text))
-    assert rust == set(header_functions()), rust ^ set(header_functions())
-
-
 # ------------------------------------------------------------------ struct layouts: header == ctypes / numpy mirrors == Rust mirror
-def c_layouts(tmp_path):
-    """sizeof / offsetof of every struct of include/zkm_hip.h, from the C compiler (tools/abi_layout.c built with gcc as C99)."""
-    import json
-    import subprocess
-    exe = str(tmp_path / "abi_layout")
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "abi_layout.c")])
-    return json.loads(subprocess.check_output([exe]))
+# sizeof of every struct of the header, in bytes: a struct that grows or shrinks is a decision, made here
+SIZES = {"zkm_challenger": 232, "zkm_stark_config": 28, "zkm_proof_layout": 216, "zkm_proof_query_layout": 464, "zkm_column": 24,
+         "zkm_colset": 32, "zkm_ctl_table": 72, "zkm_ctl_z": 32, "zkm_ctl_side": 8, "zkm_cross_table_lookup": 16, "zkm_table_input": 48,
+         "zkm_segment_ops": 288, "zkm_boot_image": 104, "zkm_cpu_step": 48, "zkm_cpu_steps": 32, "zkm_image_pages": 208, "zkm_fri_poly": 8,
+         "zkm_fri_batch": 32, "zkm_ctl_location": 16, "zkm_ctl_report": 840, "zkm_verify_report": 32}
 
 
-def header_structs():
-    """{struct name: [field names in declaration order]} parsed from the header text (comments stripped)."""
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "zkm_hip.h")).read(), flags=re.S)
-    out = {}
-    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(zkm_[a-z0-9_]+)\s*;", text, flags=re.S):
-        fields = []
-        for decl in filter(None, (d.strip() for d in body.split(";"))):
-            # "const uint64_t* const* columns" / "uint32_t a, b" / "size_t x[3], y": the names are the identifiers before , [ or the end
-            decl = re.sub(r"\[[^\]]*\]", "", decl)
-            first, *rest = decl.split(",")
-            fields.append(re.findall(r"[A-Za-z_][A-Za-z0-9_]*", first)[-1])
-            fields += [re.findall(r"[A-Za-z_][A-Za-z0-9_]*", r)[-1] for r in rest]
-        out[name] = fields
-    return out
+@functools.lru_cache(maxsize=None)
+def c_layouts():
+    """{struct: {"size", "align", "fields": [[name, offset, size]]}} of every struct of include/zkm_hip.h, from the C compiler: the probe
+    zkm_amd/abi.py generates from the header, built as pedantic C99 in a temporary directory and run."""
+    from zkm_amd import abi
+    with tempfile.TemporaryDirectory() as tmp:
+        src, exe = os.path.join(tmp, "abi_layout.c"), os.path.join(tmp, "abi_layout")
+        open(src, "w").write(abi.layout_probe_source())
+        subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-o", exe, src])
+        return json.loads(subprocess.check_output([exe]))
 
 
-def test_abi_layout_tool_covers_every_header_struct(tmp_path):
-    """tools/abi_layout.c must list every struct of the header with every field, in order: a field added to the header and forgotten
-    there (or in a mirror, below) is an error here, not a silent hole in the lock."""
-    lay = c_layouts(tmp_path)
-    hdr = header_structs()
-    assert set(lay) == set(hdr), set(lay) ^ set(hdr)
-    for name, fields in hdr.items():
-        assert [f[0] for f in lay[name]["fields"]] == fields, name
-        # fields tile the struct without overlap, in order
+def test_the_compiler_lays_out_every_header_struct(zkm):
+    """Every struct the header declares, tagged or not, with every field in order; the fields tile the struct without overlap; and no
+    struct changed its size."""
+    lay = c_layouts()
+    assert {name: [f[0] for f in v["fields"]] for name, v in lay.items()} == zkm.abi.structs()
+    for name, v in lay.items():
         end = 0
-        for _, off, size in lay[name]["fields"]:
-            assert off >= end, name
+        for _, off, size in v["fields"]:
+            assert off >= end and size > 0, name
             end = off + size
-        assert end <= lay[name]["size"], name
+        assert end <= v["size"] and v["size"] % v["align"] == 0, name
+    assert {name: v["size"] for name, v in lay.items()} == SIZES
 
 
-def test_python_mirrors_match_the_c_layout(zkm, tmp_path):
+def test_python_mirrors_match_the_c_layout(zkm):
     """The ctypes Structures and numpy dtypes that cross the C ABI (zkm_amd/__init__.py, zkm_amd/ctl.py) against the compiler's layout:
-    total size, and offset + size of every field in declaration order."""
-    import numpy as np
-    lay = c_layouts(tmp_path)
+    total size, alignment, and name, offset and size of every field in declaration order."""
+    lay = c_layouts()
     mirrors = zkm.abi_mirrors()
     assert set(mirrors) == set(lay), set(mirrors) ^ set(lay)
+    assert set(zkm.BY_REFERENCE) <= set(mirrors) and all(issubclass(mirrors[n], C.Structure) for n in zkm.BY_REFERENCE)
     for name, m in mirrors.items():
-        want = [(off, size) for _, off, size in lay[name]["fields"]]
+        want = [tuple(f) for f in lay[name]["fields"]]
         if isinstance(m, np.dtype):
-            got = [(m.fields[f][1], m.fields[f][0].itemsize) for f in m.names]
-            size = m.itemsize
+            got = [(f, m.fields[f][1], m.fields[f][0].itemsize) for f in m.names]
+            size, align = m.itemsize, max(m.fields[f][0].base.alignment for f in m.names)    # (the dtypes are packed: what their fields need)
             if name == "zkm_cross_table_lookup":      # the nested zkm_ctl_side `looked` is flattened into two u32 in the dtype
-                got = got[:2] + [(got[2][0], got[2][1] + got[3][1])]
-                assert m.names[2:] == ("looked_table", "looked_colset") and got[2][1] == lay["zkm_ctl_side"]["size"]
-            names = None
+                assert m.names[2:] == ("looked_table", "looked_colset") and got[2][2] + got[3][2] == lay["zkm_ctl_side"]["size"]
+                got = got[:2] + [("looked", got[2][1], got[2][2] + got[3][2])]
         else:
-            got = [(getattr(m, f).offset, getattr(m, f).size) for f, _ in m._fields_]
-            size = C.sizeof(m)
-            names = [f for f, _ in m._fields_]
-        assert size == lay[name]["size"], (name, size, lay[name]["size"])
+            got = [(f, getattr(m, f).offset, getattr(m, f).size) for f, _ in m._fields_]
+            size, align = C.sizeof(m), C.alignment(m)
         assert got == want, (name, got, want)
-        if names is not None:
-            assert names == [f[0] for f in lay[name]["fields"]], name
+        assert (size, align) == (lay[name]["size"], lay[name]["align"]), (name, size, align)
 
 
 RUST_PRIM = {"u64": (8, 8), "usize": (8, 8), "u32": (4, 4), "c_uint": (4, 4), "c_int": (4, 4), "i32": (4, 4), "u8": (1, 1)}
 
 
 def rust_structs():
-    """{name: [(field, type text)]} of the #[repr(C)] structs in integration/rust/zkm_hip_sys.rs (uncompiled here: parsed)."""
-    text = open(os.path.join(ROOT, "integration", "rust", "zkm_hip_sys.rs")).read()
-    text = re.sub(r"//[^\n]*", "", text)
+    """{name: [(field, type text)]} of the #[repr(C)] structs in integration/rust/zkm_hip_sys.rs (uncompiled here: parsed), under their
+    C names: a struct with a Rust-style name answers to its alias (`pub type zkm_boot_image = ZkmBootImage;`) too."""
+    text = rust_sys_text()
     out = {}
-    for m in re.finditer(r"#\[repr\(C\)\][^{;]*?pub struct (zkm_[a-z0-9_]+)\s*\{(.*?)\}", text, flags=re.S):
+    for m in re.finditer(r"#\[repr\(C\)\][^{;]*?pub struct (\w+)\s*\{(.*?)\}", text, flags=re.S):
         fields = []
         for f in filter(None, (x.strip() for x in re.split(r",(?![^\[]*\])", m.group(2)))):
             fm = re.match(r"(?:pub\s+)?([A-Za-z_][A-Za-z0-9_]*)\s*:\s*(.+)$", f, flags=re.S)
             assert fm, (m.group(1), f)
             fields.append((fm.group(1), " ".join(fm.group(2).split())))
         out[m.group(1)] = fields
+    for alias, name in re.findall(r"pub type (zkm_\w+) = (\w+);", text):
+        out[alias] = out[name]
     return out
 
 
@@ -329,14 +377,15 @@ def rust_struct_layout(name, structs, memo):
     return memo[name]
 
 
-def test_rust_mirror_matches_the_c_layout(tmp_path):
+def test_rust_mirror_matches_the_c_layout():
     """The #[repr(C)] structs of integration/rust/zkm_hip_sys.rs, laid out by the repr(C) rules (fields in order, each aligned to its
-    type, size rounded to the struct's alignment), against the compiler's layout of the header -- names, offsets, sizes, total size."""
-    lay = c_layouts(tmp_path)
+    type, size rounded to the struct's alignment), against the compiler's layout of the header -- names, offsets, sizes, total size,
+    alignment -- for every struct of the header."""
+    lay = c_layouts()
     structs = rust_structs()
     opaque = {k for k, v in structs.items() if [f for f, _ in v] == ["_p"]}
     assert opaque == {"zkm_ctx", "zkm_batch", "zkm_pool", "zkm_staged"}
-    assert set(structs) - opaque == set(lay), (set(structs) - opaque) ^ set(lay)
+    assert {k for k in structs if k.startswith("zkm_")} - opaque == set(lay), ({k for k in structs if k.startswith("zkm_")} - opaque) ^ set(lay)
     memo = {}
     for name in lay:
         size, align, fields = rust_struct_layout(name, structs, memo)
@@ -344,8 +393,89 @@ def test_rust_mirror_matches_the_c_layout(tmp_path):
         assert (size, align) == (lay[name]["size"], lay[name]["align"]), name
 
 
+# ------------------------------------------------------------------ declarations: header == Rust extern block, for every function
+C_TO_RUST = {"int": "c_int", "unsigned": "c_uint", "size_t": "usize", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64",
+             "double": "c_double", "char": "c_char", "void": "c_void"}
+# constants of the header that the Rust block does not declare (a new one is a decision: declare it there, or list it here)
+HEADER_ONLY = {"ZKM_ARITHMETIC_MAX_LOG_N", "ZKM_CPU_COLS", "ZKM_CTL_REPORT_LOCATIONS", "ZKM_CTL_REPORT_WORDS", "ZKM_KECCAK_COLS",
+               "ZKM_KECCAK_SPONGE_COLS", "ZKM_LOGIC_COLS", "ZKM_MEMORY_MAX_LOG_N", "ZKM_POSEIDON_COLS", "ZKM_POSEIDON_SPONGE_COLS",
+               "ZKM_SHA_COMPRESS_COLS", "ZKM_SHA_COMPRESS_SPONGE_COLS", "ZKM_SHA_EXTEND_COLS", "ZKM_SHA_EXTEND_SPONGE_COLS",
+               "ZKM_PROOF_MAGIC", "ZKM_FRI_PROOF_MAGIC"}
+
+
+def c_to_rust(ty, known):
+    """`const uint64_t* const*` -> `*const *const u64`: each pointer is *const or *mut by the constness of what it points to."""
+    m = re.fullmatch(r"(const )?(\w+)((?:\*(?: const)?)*)", ty)
+    assert m and (m.group(2) in C_TO_RUST or m.group(2) in known), "no Rust spelling for the C type %r" % ty
+    out, const = C_TO_RUST.get(m.group(2), m.group(2)), bool(m.group(1))
+    for qualifier in re.findall(r"\*( const)?", m.group(3)):
+        out, const = ("*const " if const else "*mut ") + out, bool(qualifier)
+    return out
+
+
+def rust_functions():
+    """{function: (return type, [(parameter type, parameter name)])} of the extern block, in Rust's spelling (f64 read as c_double, the
+    keyword `in` without its r#)."""
+    rust = {}
+    for name, args, ret in re.findall(r"pub fn (zkm_\w+)\s*\(([^)]*)\)\s*(?:->\s*([^;]+?)\s*)?;", rust_sys_text()):
+        assert name not in rust, name
+        params = [tuple(x.strip() for x in a.split(":")) for a in args.split(",") if a.strip()]
+        rust[name] = (ret.replace("f64", "c_double"), [(" ".join(ty.split()).replace("f64", "c_double"), arg.replace("r#", "")) for arg, ty in params])
+    return rust
+
+
+def declared_alike(zkm, fn):
+    """One function is exported, bound, and named in the extern block with the header's parameter names (the whole-ABI tests of this file
+    hold the same, and the types, for every function; the per-feature tests call this for the functions they are about)."""
+    assert hasattr(zkm.load(), fn) and fn in zkm.EXPORTS, fn
+    assert [arg for _, arg in rust_functions()[fn][1]] == [arg for _, arg in prototypes()[fn][1]], fn
+
+
+def test_every_function_and_constant_is_declared_alike_in_the_rust_block(zkm):
+    """Every prototype of the header against its `pub fn` in the extern block: the parameter names in order, every parameter type and the
+    return type (`in` is a keyword of Rust: the block spells it r#in).  Every function that reports through the error channel takes
+    `char** err` last and returns int.  Every integer constant the block declares has the header's value."""
+    text = rust_sys_text()
+    known = set(zkm.abi.structs()) | set(zkm.abi.opaque())
+    rust, protos = rust_functions(), prototypes()
+    assert set(rust) == set(protos), set(rust) ^ set(protos)
+    assert all(re.search(r"pub (enum|struct) %s\b" % handle, text) for handle in zkm.abi.opaque())
+    for name, (ret, params) in protos.items():
+        want = ("" if ret == "void" else c_to_rust(ret, known), [(c_to_rust(ty, known), arg) for ty, arg in params])
+        assert rust[name] == want, (name, rust[name], want)
+        if any(ty == "char**" for ty, _ in params):
+            assert params[-1] == ("char**", "err") and ret == "int" and [ty for ty, _ in params].count("char**") == 1, name
+        if params and params[0][0] == "zkm_ctx*":
+            assert params[0][1] == "ctx", name
+    consts = zkm.abi.constants()
+    declared = {name: int(value, 0) for name, value in re.findall(r"pub const (ZKM_\w+): \w+ = (\w+);", text)}
+    assert declared == {k: v for k, v in consts.items() if k not in HEADER_ONLY}
+    assert HEADER_ONLY <= set(consts)
+    magic = re.search(r"pub const ZKM_PROOF_MAGIC: u64 = (\w+);", read("integration", "rust", "proof_blob.rs")).group(1)   # (the wrapper's own copy)
+    assert int(magic.replace("_", ""), 0) == consts["ZKM_PROOF_MAGIC"]
+
+
+# what a wrapper may name that the extern block does not declare: the two converters prove_hip.rs defines (and the files that call them),
+# the header's magic that proof_blob.rs restates
+WRAPPER_ITEMS = {"prove_hip.rs": {"zkm_table_id", "zkm_config"}, "check_ctls_hip.rs": {"zkm_table_id"}, "verify_hip.rs": {"zkm_config"},
+                 "proof_blob.rs": {"ZKM_PROOF_MAGIC"}}
+WRAPPERS = sorted(os.path.basename(f) for f in glob.glob(os.path.join(ROOT, "integration", "rust", "*.rs")) if f != RUST_SYS)
+
+
+@pytest.mark.parametrize("wrapper", WRAPPERS)
+def test_the_rust_wrappers_name_only_declared_library_items(wrapper):
+    """Every zkm_* function, struct or handle and every ZKM_* constant a file of integration/rust names is declared in the extern block
+    (or is one of the few items the wrappers define themselves)."""
+    from .test_rust_names import strip_comments
+    sys_rs = strip_comments(open(RUST_SYS).read())
+    declared = set(re.findall(r"pub fn (zkm_\w+)\s*\(", sys_rs)) | set(re.findall(r"pub (?:struct|enum|type) (zkm_\w+)", sys_rs)) | \
+        set(re.findall(r"pub const (ZKM_\w+):", sys_rs))
+    src = strip_comments(read("integration", "rust", wrapper))
+    used = set(re.findall(r"\b(zkm_[a-z0-9_]+|ZKM_[A-Z0-9_]+)\b", src))
+    assert used - WRAPPER_ITEMS.get(wrapper, set()) <= declared, (wrapper, used - declared)
+
+
 def build_c_smoke(tmp_path):
-    import subprocess
     exe = str(tmp_path / "c_smoke")
     libdir = os.path.join(ROOT, "zkm_amd", "csrc")
     subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"),
@@ -357,8 +487,6 @@ def build_c_smoke(tmp_path):
 def test_pure_c_caller_builds_and_reports_errors(zkm, oracle, tmp_path):
     """tools/c_smoke.c: the header used from pedantic C99 and linked against libzkmhip.so with no Python in the process.  Without a GPU
     the run must end in the library's error channel (nonzero status + malloc'd message), not in a crash."""
-    import subprocess
-    import numpy as np
     from zkm_amd import tables as T
     exe = build_c_smoke(tmp_path)
     seg = np.load(os.path.join(ROOT, "tests", "golden", "segment12.npz"))

@@ -22,12 +22,9 @@ def test_memory_cols_is_the_oracle_width(zkm, oracle):
 
 
 def test_rust_sys_declaration_matches_the_header():
-    header = open(os.path.join(ROOT, "include", "zkm_hip.h")).read()
-    c_args = re.search(r"int zkm_memory_trace\(([^)]*)\)", header).group(1)
-    rust = open(os.path.join(ROOT, "integration", "rust", "zkm_hip_sys.rs")).read()
-    r_args = re.search(r"pub fn zkm_memory_trace\(([^)]*)\)", rust).group(1)
-    names = lambda args, pat: [re.search(pat, a.strip()).group(1) for a in args.split(",")]
-    assert names(c_args, r"(\w+)$") == names(r_args, r"^(\w+):") == ["ctx", "ops", "nops", "log_n", "out_dev", "natural_rows_out", "err"]
+    from .test_abi import prototypes, rust_functions
+    c, r = prototypes()["zkm_memory_trace"][1], rust_functions()["zkm_memory_trace"][1]
+    assert [n for _, n in c] == [n for _, n in r] == ["ctx", "ops", "nops", "log_n", "out_dev", "natural_rows_out", "err"]
 
 
 def test_rust_wrapper_packs_fields_in_the_oracle_order():

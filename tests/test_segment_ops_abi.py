@@ -7,7 +7,6 @@ import re
 ROOT = os.path.dirname(os.path.abspath(os.path.dirname(__file__)))
 C_WIDTH = {"const uint64_t*": 8, "const uint32_t*": 8, "const uint8_t*": 8, "size_t": 8}
 RUST_WIDTH = {"*const u64": 8, "*const u32": 8, "*const u8": 8, "usize": 8}
-C_TO_RUST = {"const uint64_t*": "*const u64", "const uint32_t*": "*const u32", "const uint8_t*": "*const u8", "size_t": "usize"}
 
 
 def header_fields():
@@ -21,9 +20,8 @@ def header_fields():
 
 
 def rust_fields():
-    text = re.sub(r"//[^\n]*", "", open(os.path.join(ROOT, "integration", "rust", "zkm_hip_sys.rs")).read())
-    body = re.search(r"pub struct zkm_segment_ops \{(.*?)\}", text, flags=re.S).group(1)
-    return [re.match(r"pub (\w+): (.+)$", f.strip()).groups() for f in body.split(",") if f.strip()]
+    from .test_abi import rust_structs
+    return rust_structs()["zkm_segment_ops"]
 
 
 def test_symbols_are_exported(zkm):
@@ -36,10 +34,11 @@ def test_symbols_are_exported(zkm):
 def test_struct_fields_agree_in_header_rust_and_ctypes(zkm):
     """Same fields, same order, same widths: the header, the Rust mirror and the ctypes mirror; one pointer group and one count per field
     of the reference's Traces, in its order."""
+    from .test_abi import c_to_rust
     hdr = header_fields()
     rust = rust_fields()
     assert [n for n, _ in hdr] == [n for n, _ in rust] == [n for n, _ in zkm.SegmentOpsStruct._fields_]
-    assert [C_TO_RUST[t] for _, t in hdr] == [t for _, t in rust]
+    assert [c_to_rust(t, ()) for _, t in hdr] == [t for _, t in rust]
     assert [C_WIDTH[t] for _, t in hdr] == [RUST_WIDTH[t] for _, t in rust] == \
         [getattr(zkm.SegmentOpsStruct, n).size for n, _ in zkm.SegmentOpsStruct._fields_]
     assert C.sizeof(zkm.SegmentOpsStruct) == 8 * len(hdr)
@@ -49,16 +48,13 @@ def test_struct_fields_agree_in_header_rust_and_ctypes(zkm):
 
 
 def test_rust_declarations_match_the_header():
-    header = open(os.path.join(ROOT, "include", "zkm_hip.h")).read()
-    rust = open(os.path.join(ROOT, "integration", "rust", "zkm_hip_sys.rs")).read()
-    names = lambda args, pat: [re.search(pat, a.strip()).group(1) for a in args.split(",")]
+    from .test_abi import prototypes, rust_functions
     for fn, want in (("zkm_segment_tables", ["ctx", "cfg", "ops", "log_n_out", "out", "err"]),
                      ("zkm_prove_segment_ops", ["ctx", "cfg", "ops", "public_values", "npublic", "proofs_out", "proof_offsets_out",
                                                 "ctl_challenges_out", "err"])):
-        c_args = re.search(r"int %s\(([^)]*)\)" % fn, header).group(1)
-        r_args = re.search(r"pub fn %s\(([^)]*)\)" % fn, rust).group(1)
-        assert names(c_args, r"(\w+)$") == names(r_args, r"^(\w+):") == want, fn
-        assert "const zkm_segment_ops* ops" in c_args and "ops: *const zkm_segment_ops" in r_args
+        c, r = prototypes()[fn][1], rust_functions()[fn][1]
+        assert [n for _, n in c] == [n for _, n in r] == want, fn
+        assert ("const zkm_segment_ops*", "ops") in c and ("*const zkm_segment_ops", "ops") in r
 
 
 def test_sizing_needs_a_context(zkm):

@@ -1,38 +1,17 @@
-"""CPU suite: the K-segment operations entry points -- zkm_segments_tables, zkm_prove_segments_ops, zkm_pool_prove_segments_ops and the
-staged operations (zkm_segment_ops_stage, zkm_staged_ops_get / _ready / _free) -- are declared in the header, exported by the library,
-bound in Python with the declared argument types, and refuse their bad arguments through the error channel without a GPU; no existing
-struct of the C ABI changed its size."""
+"""CPU suite: what is particular to the K-segment operations entry points -- zkm_segments_tables, zkm_prove_segments_ops,
+zkm_pool_prove_segments_ops and the staged operations (zkm_segment_ops_stage, zkm_staged_ops_get / _ready / _free); tests/test_abi.py
+holds every declaration and layout of the C ABI.  They take the arguments the contract names, are bound in Python, and refuse their bad
+arguments through the error channel without a GPU."""
 import ctypes as C
-import json
-import os
-import re
-import subprocess
 
-ROOT = os.path.dirname(os.path.abspath(os.path.dirname(__file__)))
+from .test_abi import declared_alike, prototypes, read
+
 NEW = ["zkm_segments_tables", "zkm_prove_segments_ops", "zkm_pool_prove_segments_ops", "zkm_segment_ops_stage", "zkm_staged_ops_get",
        "zkm_staged_ops_ready", "zkm_staged_ops_free"]
-# sizeof of every struct tools/abi_layout.c printed before these entry points existed (zkm_segment_ops: locked, 36 x 8)
-SIZES = {"zkm_challenger": 232, "zkm_stark_config": 28, "zkm_proof_layout": 216, "zkm_proof_query_layout": 464, "zkm_column": 24,
-         "zkm_colset": 32, "zkm_ctl_table": 72, "zkm_ctl_z": 32, "zkm_ctl_side": 8, "zkm_cross_table_lookup": 16, "zkm_table_input": 48,
-         "zkm_fri_poly": 8, "zkm_fri_batch": 32, "zkm_segment_ops": 288}
-
-
-def header_prototypes():
-    """{name: (return type, [(type, name)])} of the new exports, from the header text."""
-    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "zkm_hip.h")).read(), flags=re.S)
-    out = {}
-    for name in NEW:
-        ret, args = re.search(r"\b(int|void)\s+%s\(([^)]*)\)\s*;" % name, text).groups()
-        params = []
-        for a in args.split(","):
-            ty, arg = re.match(r"\s*(.*?)(\w+)\s*$", a, flags=re.S).groups()
-            params.append((re.sub(r"\s+", " ", ty).strip(), arg))
-        out[name] = (ret, params)
-    return out
 
 
 def test_header_declares_them_and_the_library_exports_them(zkm):
-    protos = header_prototypes()
+    protos = prototypes()
     assert protos["zkm_segments_tables"][1] == [("zkm_ctx*", "ctx"), ("const zkm_stark_config*", "cfg"), ("size_t", "nseg"),
                                                 ("const zkm_segment_ops*", "ops"), ("unsigned*", "log_n_out"), ("zkm_staged**", "out"),
                                                 ("char**", "err")]
@@ -40,17 +19,16 @@ def test_header_declares_them_and_the_library_exports_them(zkm):
                                                                    "proof_offsets_out", "ctl_challenges_out", "err"]
     assert [n for _, n in protos["zkm_pool_prove_segments_ops"][1]] == ["pool", "cfg", "nseg", "max_stack", "ops", "public_values", "npublic",
                                                                         "proofs_out", "proof_offsets_out", "ctl_challenges_out", "err"]
-    assert "typedef struct zkm_staged_ops zkm_staged_ops;" in open(os.path.join(ROOT, "include", "zkm_hip.h")).read()
-    dynamic = subprocess.check_output(["nm", "-D", "--defined-only", zkm._LIB_PATH], text=True)
-    exported = set(re.findall(r" T (zkm_\w+)", dynamic))
-    assert set(NEW) <= exported, set(NEW) - exported
-    assert set(NEW) <= set(zkm.EXPORTS)
+    assert "typedef struct zkm_staged_ops zkm_staged_ops;" in read("include", "zkm_hip.h")
+    for name in NEW:
+        declared_alike(zkm, name)
 
 
 def test_python_binding_has_the_declared_argument_types(zkm):
-    L = zkm.load()
+    L, protos = zkm.load(), prototypes()
     pointer = lambda t: t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer)
-    for name, (ret, params) in header_prototypes().items():
+    for name in NEW:
+        ret, params = protos[name]
         fn = getattr(L, name)
         assert fn.restype is (C.c_int if ret == "int" else None), name
         assert len(fn.argtypes) == len(params), name
@@ -61,22 +39,12 @@ def test_python_binding_has_the_declared_argument_types(zkm):
                 assert got is C.c_int, (name, arg)
             else:
                 assert ty.endswith("*") and pointer(got), (name, arg)
-            if ty == "const zkm_segment_ops*" or ty == "zkm_segment_ops*":
+            if ty in ("const zkm_segment_ops*", "zkm_segment_ops*"):
                 assert got._type_ is zkm.SegmentOpsStruct, (name, arg)
     for method in ("segments_tables", "prove_segments_ops", "stage_segment_ops"):
         assert callable(getattr(zkm.Context, method))
     assert callable(zkm.Pool.prove_segments_ops)
     assert all(callable(getattr(zkm.StagedOps, m)) for m in ("ops", "ready", "free", "__enter__", "__exit__"))
-
-
-def test_existing_struct_sizes_are_unchanged(tmp_path):
-    exe = str(tmp_path / "abi_layout")
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-o", exe, os.path.join(ROOT, "tools", "abi_layout.c")])
-    lay = json.loads(subprocess.check_output([exe]))
-    assert {k: v["size"] for k, v in lay.items()} == SIZES
-    # the file also holds the new prototypes to their argument types (a mismatch would have failed the build above)
-    text = open(os.path.join(ROOT, "tools", "abi_layout.c")).read()
-    assert all("= %s)" % name in text for name in NEW)
 
 
 def test_bad_arguments_are_refused_without_a_gpu(zkm):

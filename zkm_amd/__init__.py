@@ -18,53 +18,26 @@ _CSRC = os.path.join(_HERE, "csrc")
 _LIB_PATH = os.environ.get("ZKM_HIP_LIB") or os.path.join(_CSRC, "libzkmhip.so")   # (ZKM_HIP_LIB: A/B builds of the same in-tree sources)
 
 P = 0xFFFFFFFF00000001
-POSEIDON_COLS = 262
-KECCAK_SPONGE_COLS = 470
-LOGIC_COLS = 69
-MEMORY_COLS = 13
-ARITHMETIC_COLS = 54
-KECCAK_COLS = 2431
-POSEIDON_SPONGE_COLS = 110
-TABLE_POSEIDON, TABLE_LOGIC, TABLE_KECCAK_SPONGE, TABLE_KECCAK, TABLE_MEMORY, TABLE_POSEIDON_SPONGE = 0, 1, 2, 3, 4, 5
-TABLE_SHA_EXTEND, TABLE_SHA_EXTEND_SPONGE, TABLE_SHA_COMPRESS, TABLE_SHA_COMPRESS_SPONGE, TABLE_ARITHMETIC, TABLE_CPU = 6, 7, 8, 9, 10, 11
-# zkm_poseidon_selftest: ZKM_POSEIDON_OUT_* and ZKM_POSEIDON_PROBE_* of include/zkm_hip.h
-POSEIDON_OUT_ALL, POSEIDON_OUT_CAPACITY, POSEIDON_OUT_DIGEST = 0, 1, 2
-POSEIDON_PROBE = {name: i for i, name in enumerate((
-    "PERMUTE_LANE", "PERMUTE_LANE_MFMA", "PERMUTE_QUAD", "PERMUTE_WIDE", "MDS_VALU", "MDS_MFMA", "MDS_QUAD", "MDS_ROWS", "GROUP3", "GROUP3_QUAD",
-    "GROUP2", "FOLD", "FOLD_TY", "SBOX7", "SBOX_DELTA", "ADD_RC0"))}
-u64p = C.POINTER(C.c_uint64)
-
-EXPORTS = [
-    "zkm_ctx_create", "zkm_ctx_destroy", "zkm_ctx_memory", "zkm_ctx_resident_bytes", "zkm_ctx_trim", "zkm_ctx_set_tuning", "zkm_table_enum_index", "zkm_host_alloc", "zkm_host_free",
-    "zkm_host_register", "zkm_host_unregister", "zkm_all_stark_ctls", "zkm_all_stark_ctl_table", "zkm_prove_segment", "zkm_prove_segments", "zkm_prove_segments_columns", "zkm_prove_segment_columns", "zkm_ctx_synchronize", "zkm_ctx_stream", "zkm_dev_alloc", "zkm_dev_free",
-    "zkm_dev_upload", "zkm_dev_download", "zkm_ntt", "zkm_field_selftest", "zkm_batch_commit_values", "zkm_batch_commit_coeffs", "zkm_batch_commit_columns", "zkm_batch_free",
-    "zkm_batch_cap", "zkm_batch_coeffs", "zkm_batch_lde_row", "zkm_batch_lde_rows", "zkm_batch_leaf", "zkm_batch_merkle_path",
-    "zkm_batch_digest_layer", "zkm_poseidon_permute_batch", "zkm_keccakf_batch", "zkm_poseidon_selftest", "zkm_consumer_selftest", "zkm_poseidon_trace", "zkm_keccak_sponge_trace", "zkm_keccak_trace", "zkm_logic_trace", "zkm_memory_trace", "zkm_arithmetic_trace",
-    "zkm_poseidon_sponge_trace", "zkm_poseidon_trace_inputs", "zkm_sha_extend_trace", "zkm_sha_extend_sponge_trace",
-    "zkm_sha_compress_trace", "zkm_sha_compress_sponge_trace",
-    "zkm_table_width", "zkm_num_lookup_columns", "zkm_challenger_init",
-    "zkm_challenger_observe", "zkm_challenger_get", "zkm_challenger_compact", "zkm_standard_config", "zkm_proof_words",
-    "zkm_prove_single_table", "zkm_prove_single_tables", "zkm_prove_openings", "zkm_fri_prove", "zkm_fri_proof_words", "zkm_prove_single_table_ctl", "zkm_ctl_data", "zkm_lookup_helper_columns", "zkm_all_proof_words", "zkm_prove_with_traces",
-    "zkm_proof_get_layout", "zkm_proof_get_query_layout", "zkm_segment_image_words", "zkm_segment_image_write", "zkm_prove_segment_image",
-    "zkm_quotient", "zkm_eval_openings", "zkm_check_constraints", "zkm_profile_enable", "zkm_profile_reset",
-    "zkm_profile_count", "zkm_profile_get", "zkm_version",
-    "zkm_trace_stage", "zkm_trace_stage_columns", "zkm_segment_stage", "zkm_segment_stage_columns", "zkm_staged_segment_ptrs", "zkm_staged_ptr", "zkm_staged_ready", "zkm_staged_free",
-    "zkm_pool_create", "zkm_pool_destroy", "zkm_pool_workers", "zkm_pool_context", "zkm_pool_device", "zkm_pool_set_tuning",
-    "zkm_pool_prove_segments", "zkm_pool_prove_segments_columns", "zkm_pool_plan", "zkm_pool_last_assignment",
-    "zkm_segment_tables", "zkm_prove_segment_ops",
-    "zkm_segments_tables", "zkm_prove_segments_ops", "zkm_pool_prove_segments_ops",
-    "zkm_segment_ops_stage", "zkm_staged_ops_get", "zkm_staged_ops_ready", "zkm_staged_ops_free",
-    "zkm_check_ctls", "zkm_segment_check_ctls",
-    "zkm_ctx_host_waits", "zkm_boot_counts", "zkm_boot_witness", "zkm_segment_tables_boot", "zkm_segments_tables_boot", "zkm_prove_segment_ops_boot",
-    "zkm_prove_segments_ops_boot",
-    "zkm_image_hash_plan", "zkm_image_hash", "zkm_images_hash",
-    "zkm_verify_proofs", "zkm_verify_segments", "zkm_verify_single_table",
-    "zkm_cpu_steps_counts", "zkm_cpu_witness", "zkm_segments_tables_steps", "zkm_prove_segments_ops_steps",
-]
 
 
 class ZkmError(RuntimeError):
     pass
+
+
+from . import abi  # noqa: E402  (abi raises ZkmError)
+
+# the constants below restate nothing: each is read from its #define in include/zkm_hip.h (a name the header lacks fails the import)
+_H = abi.constants("ZKM_")
+POSEIDON_COLS, KECCAK_SPONGE_COLS, LOGIC_COLS, MEMORY_COLS, ARITHMETIC_COLS, KECCAK_COLS, POSEIDON_SPONGE_COLS = (
+    _H[n + "_COLS"] for n in ("POSEIDON", "KECCAK_SPONGE", "LOGIC", "MEMORY", "ARITHMETIC", "KECCAK", "POSEIDON_SPONGE"))
+TABLE_POSEIDON, TABLE_LOGIC, TABLE_KECCAK_SPONGE, TABLE_KECCAK, TABLE_MEMORY, TABLE_POSEIDON_SPONGE = 0, 1, 2, 3, 4, 5
+TABLE_SHA_EXTEND, TABLE_SHA_EXTEND_SPONGE, TABLE_SHA_COMPRESS, TABLE_SHA_COMPRESS_SPONGE, TABLE_ARITHMETIC, TABLE_CPU = 6, 7, 8, 9, 10, 11
+# zkm_poseidon_selftest: ZKM_POSEIDON_OUT_* and ZKM_POSEIDON_PROBE_*
+POSEIDON_OUT_ALL, POSEIDON_OUT_CAPACITY, POSEIDON_OUT_DIGEST = (_H["POSEIDON_OUT_" + n] for n in ("ALL", "CAPACITY", "DIGEST"))
+POSEIDON_PROBE = abi.constants("ZKM_POSEIDON_PROBE_")
+u64p = C.POINTER(C.c_uint64)
+
+EXPORTS = [name for name, _, _ in abi.prototypes()]
 
 
 def build(force=False):
@@ -143,40 +116,24 @@ class BootImageStruct(C.Structure):
                 ("check", C.c_uint32), ("pre_hash_root", C.c_uint8 * 32), ("pre_image_id", C.c_uint8 * 32)]
 
 
-def abi_mirrors_boot():
-    """The struct of the zkm_*_boot calls -> its mirror; tests/test_boot_abi.py compares it with `tools/abi_layout boot`."""
-    return {"zkm_boot_image": BootImageStruct}
-
-
 class ImagePagesStruct(C.Structure):
     """zkm_image_pages: the dirty pages of a split, the hash pages that exist already, pc and the registers (include/zkm_hip.h)."""
     _fields_ = [("dirty_index", C.c_void_p), ("ndirty", C.c_size_t), ("dirty_words", C.c_void_p), ("known_index", C.c_void_p),
                 ("nknown", C.c_size_t), ("known_words", C.c_void_p), ("pc", C.c_uint32), ("registers", C.c_uint8 * 156)]
 
 
-def abi_mirrors_image_hash():
-    """The struct of zkm_image[s]_hash -> its mirror; tests/test_image_hash_abi.py compares it with `tools/abi_layout image`."""
-    return {"zkm_image_pages": ImagePagesStruct}
-
-
 # zkm_cpu_step (include/zkm_hip.h): one cycle of the compact step log; STEP_KINDS[k] names ZKM_STEP_<k>, SYSCALL_KINDS the ZKM_SYSCALL_*
 CPU_STEP_DT = np.dtype([("pc", "<u4"), ("next_pc", "<u4"), ("insn", "<u4"), ("kind", "<u4"), ("flags", "<u4"), ("context", "<u4"),
                         ("reads", "<u4", (6,))])
-STEP_KINDS = ("BINARY_OP", "BINARY_IMM_OP", "LOGIC_OP", "LOGIC_IMM_OP", "SHIFT", "SHIFT_IMM", "BRANCH", "JUMPS", "JUMPI", "JUMPDIRECT", "M_OP_LOAD",
-              "M_OP_STORE", "NOP", "CLZ_OP", "CLO_OP", "SIGNEXT8", "SIGNEXT16", "SWAPHALF", "RDHWR", "MOVZ_OP", "MOVN_OP", "TEQ", "EXT", "INS", "ROR",
-              "MADDU", "SYSCALL", "PAD", "RAW")
-STEP = {name: k for k, name in enumerate(STEP_KINDS)}
-SYSCALL_KINDS = {"other": 0, "mmap": 1, "brk": 2, "clone": 3, "read": 5, "write": 6, "fcntl": 7, "set_thread_area": 8}
+STEP = {n: v for n, v in abi.constants("ZKM_STEP_").items() if not n.startswith("FLAG_")}
+STEP_KINDS = tuple(STEP)
+assert list(STEP.values()) == list(range(len(STEP)))      # STEP_KINDS[k] names kind k
+SYSCALL_KINDS = {n.lower(): v for n, v in abi.constants("ZKM_SYSCALL_").items()}
 
 
 class CpuStepsStruct(C.Structure):
     """zkm_cpu_steps: a segment's step list and the ready-made rows its RAW steps index."""
     _fields_ = [("steps", C.c_void_p), ("nsteps", C.c_size_t), ("raw_rows", C.c_void_p), ("nraw", C.c_size_t)]
-
-
-def abi_mirrors_cpu_steps():
-    """The structs of the step log -> their mirrors; tests/test_cpu_steps_abi.py compares them with `tools/abi_layout steps`."""
-    return {"zkm_cpu_step": CPU_STEP_DT, "zkm_cpu_steps": CpuStepsStruct}
 
 
 class CpuSteps:
@@ -236,10 +193,10 @@ class CtlReport(C.Structure):
         return [(l.side, l.table, l.row) for l in self.looked[:self.nlooked_locations]]
 
 
-VERIFY_CODES = ("OK", "SHAPE", "TRANSCRIPT_STATE", "CTL_CHALLENGES", "QUOTIENT", "POW", "INITIAL_MERKLE", "FRI_EVAL", "FRI_MERKLE", "FINAL_POLY",
-                "CTL_SUM", "FAILED")
+VERIFY_CODES = tuple(abi.constants("ZKM_VERIFY_"))
 (VERIFY_OK, VERIFY_SHAPE, VERIFY_TRANSCRIPT_STATE, VERIFY_CTL_CHALLENGES, VERIFY_QUOTIENT, VERIFY_POW, VERIFY_INITIAL_MERKLE, VERIFY_FRI_EVAL,
- VERIFY_FRI_MERKLE, VERIFY_FINAL_POLY, VERIFY_CTL_SUM, VERIFY_FAILED) = range(12)
+ VERIFY_FRI_MERKLE, VERIFY_FINAL_POLY, VERIFY_CTL_SUM, VERIFY_FAILED) = (_H["VERIFY_" + n] for n in VERIFY_CODES)
+assert VERIFY_FAILED == len(VERIFY_CODES) - 1
 
 
 class VerifyReport(C.Structure):
@@ -256,204 +213,71 @@ class VerifyReport(C.Structure):
         return tuple(getattr(self, n) for n, _ in self._fields_)
 
 
-def abi_mirrors_verify():
-    """The struct of zkm_verify_* -> its mirror; tests/test_verify_abi.py compares it with `tools/abi_layout verify`."""
-    return {"zkm_verify_report": VerifyReport}
-
-
 def abi_mirrors():
     """Every struct of include/zkm_hip.h -> its Python mirror (a ctypes Structure or a numpy dtype); tests/test_abi.py compares
-    size and field offsets of each with what the C compiler says (tools/abi_layout.c)."""
+    size, alignment and field offsets of each with what the C compiler says (abi.layout_probe_source)."""
     from . import ctl
     return {"zkm_challenger": Challenger, "zkm_stark_config": StarkConfig, "zkm_proof_layout": ProofLayout,
             "zkm_proof_query_layout": ProofQueryLayout, "zkm_column": ctl.COLUMN_DT, "zkm_colset": ctl.COLSET_DT,
             "zkm_ctl_table": ctl.CtlTableStruct, "zkm_ctl_z": ctl.CTLZ_DT, "zkm_ctl_side": ctl.SIDE_DT,
             "zkm_cross_table_lookup": ctl.CTL_DT, "zkm_table_input": ctl.TableInputStruct, "zkm_fri_poly": FriPoly,
-            "zkm_fri_batch": FriBatch, "zkm_segment_ops": SegmentOpsStruct}
+            "zkm_fri_batch": FriBatch, "zkm_segment_ops": SegmentOpsStruct, "zkm_boot_image": BootImageStruct,
+            "zkm_cpu_step": CPU_STEP_DT, "zkm_cpu_steps": CpuStepsStruct, "zkm_image_pages": ImagePagesStruct,
+            "zkm_ctl_location": CtlLocation, "zkm_ctl_report": CtlReport, "zkm_verify_report": VerifyReport}
 
 
-def abi_mirrors_check_ctls():
-    """The structs of zkm_check_ctls -> their mirrors; tests/test_check_ctls_abi.py compares them with `tools/abi_layout check_ctls`."""
-    return {"zkm_ctl_location": CtlLocation, "zkm_ctl_report": CtlReport}
+# the structs the binding passes by reference: a pointer to one of them is POINTER(its mirror); every other struct pointer (arrays packed
+# by zkm_amd/ctl.py, handles) is a plain address
+BY_REFERENCE = ("zkm_stark_config", "zkm_challenger", "zkm_segment_ops", "zkm_boot_image", "zkm_cpu_steps", "zkm_image_pages", "zkm_ctl_report",
+                "zkm_verify_report", "zkm_proof_layout", "zkm_proof_query_layout")
+_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "size_t": C.c_size_t, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+_COUNTS = {"size_t": C.c_size_t, "unsigned": C.c_uint, "int": C.c_int, "double": C.c_double}    # pointees that stay typed: never device memory
+_DATA = ("void", "uint8_t", "uint32_t", "uint64_t")    # device addresses as integers, host arrays as casts: c_void_p takes both
+
+
+def _ctype(text, mirrors, ret=False):
+    """The ctypes type of a parameter or return type of the header; a type the rules below do not name raises ZkmError."""
+    base = " ".join(w for w in text.replace("*", " ").split() if w != "const")
+    stars = text.count("*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 0 and base == "void" and ret:
+        return None
+    if base == "char" and stars in (1, 2) and (stars == 2 or text.startswith("const ")):
+        return C.c_char_p if stars == 1 else C.POINTER(C.c_char_p)
+    known = base in _SCALARS or base in _COUNTS or base in _DATA or base in abi.structs() or base in abi.opaque()
+    if stars and known and ret:
+        return C.c_void_p
+    if stars >= 2 and known:
+        return C.POINTER(C.c_void_p)
+    if stars == 1 and base in _COUNTS:
+        return C.POINTER(_COUNTS[base])
+    if stars == 1 and base in BY_REFERENCE:
+        return C.POINTER(mirrors[base])
+    if stars == 1 and known:
+        return C.c_void_p
+    raise ZkmError("include/zkm_hip.h: no ctypes binding for the C type %r" % text)
 
 
 _lib = None
 
 
 def load():
-    """Load the extension (no GPU needed just to load and resolve symbols)."""
+    """Load the extension (no GPU needed just to load and resolve symbols) and give every function of include/zkm_hip.h its argument and
+    return types."""
     global _lib
     if _lib is not None:
         return _lib
     if not os.path.exists(_LIB_PATH):
         raise ZkmError("HIP extension %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'`" % _LIB_PATH)
     L = C.CDLL(_LIB_PATH)
-    cp, cpp = C.c_void_p, C.POINTER(C.c_void_p)
-    err = C.POINTER(C.c_char_p)
-    sigs = {
-        "zkm_ctx_create": (C.c_int, [C.c_int, cpp, err]),
-        "zkm_ctx_destroy": (None, [cp]),
-        "zkm_ctx_synchronize": (C.c_int, [cp, err]),
-        "zkm_ctx_stream": (cp, [cp]),
-        "zkm_dev_alloc": (C.c_int, [cp, C.c_size_t, cpp, err]),
-        "zkm_dev_free": (C.c_int, [cp, cp]),
-        "zkm_dev_upload": (C.c_int, [cp, cp, cp, C.c_size_t, err]),
-        "zkm_dev_download": (C.c_int, [cp, cp, cp, C.c_size_t, err]),
-        "zkm_field_selftest": (C.c_int, [cp, u64p, u64p, C.c_size_t, u64p, err]),
-        "zkm_ntt": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, C.c_int, C.c_uint64, err]),
-        "zkm_batch_commit_values": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, cpp, err]),
-        "zkm_batch_commit_coeffs": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, C.c_uint, C.c_uint, cpp, err]),
-        "zkm_batch_commit_columns": (C.c_int, [cp, C.POINTER(C.c_void_p), C.c_size_t, C.c_uint, C.c_int, C.c_uint, C.c_uint, cpp, err]),
-        "zkm_batch_free": (None, [cp]),
-        "zkm_batch_cap": (C.c_int, [cp, u64p]),
-        "zkm_batch_coeffs": (C.c_int, [cp, cp]),
-        "zkm_batch_lde_row": (C.c_int, [cp, C.c_size_t, u64p]),
-        "zkm_batch_lde_rows": (C.c_int, [cp, C.c_size_t, C.c_size_t, C.c_size_t, cp]),
-        "zkm_batch_leaf": (C.c_int, [cp, C.c_size_t, u64p]),
-        "zkm_batch_merkle_path": (C.c_int, [cp, C.c_size_t, u64p]),
-        "zkm_batch_digest_layer": (C.c_int, [cp, C.c_uint, u64p]),
-        "zkm_poseidon_permute_batch": (C.c_int, [cp, cp, C.c_size_t, err]),
-        "zkm_keccakf_batch": (C.c_int, [cp, cp, C.c_size_t, err]),
-        "zkm_poseidon_selftest": (C.c_int, [cp, C.c_uint32, C.c_uint32, u64p, C.c_size_t, u64p, err]),
-        "zkm_consumer_selftest": (C.c_int, [cp, u64p, C.c_size_t, u64p, C.c_size_t, C.c_size_t, C.c_uint32, u64p, err]),
-        "zkm_poseidon_trace": (C.c_int, [cp, C.c_uint64, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_keccak_sponge_trace": (C.c_int, [cp, cp, u64p, u64p, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
-        "zkm_poseidon_sponge_trace": (C.c_int, [cp, cp, u64p, u64p, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
-        "zkm_poseidon_trace_inputs": (C.c_int, [cp, cp, cp, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_sha_extend_trace": (C.c_int, [cp, cp, cp, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_sha_extend_sponge_trace": (C.c_int, [cp, cp, cp, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_sha_compress_trace": (C.c_int, [cp, cp, cp, cp, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_sha_compress_sponge_trace": (C.c_int, [cp, cp, cp, cp, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_keccak_trace": (C.c_int, [cp, cp, cp, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_ctx_memory": (None, [cp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-        "zkm_ctx_resident_bytes": (C.c_size_t, [cp]),
-        "zkm_ctx_trim": (None, [cp]),
-        "zkm_ctx_set_tuning": (C.c_int, [cp, C.c_char_p, C.c_uint64, err]),
-        "zkm_all_stark_ctls": (C.c_int, [cpp, C.POINTER(C.c_size_t), cpp, C.POINTER(C.c_size_t)]),
-        "zkm_all_stark_ctl_table": (cp, [C.c_int]),
-        "zkm_prove_segment": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(C.c_void_p), C.POINTER(C.c_uint), u64p, C.c_size_t, u64p,
-                                        C.POINTER(C.c_size_t), u64p, err]),
-        "zkm_prove_segments": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                         C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), err]),
-        "zkm_prove_segments_columns": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), err]),
-        "zkm_prove_segment_columns": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(C.c_void_p), C.POINTER(C.c_uint), u64p, C.c_size_t, u64p,
-                                                C.POINTER(C.c_size_t), u64p, err]),
-        "zkm_pool_create": (C.c_int, [C.POINTER(C.c_int), C.c_size_t, C.c_size_t, cpp, err]),
-        "zkm_pool_destroy": (None, [cp]),
-        "zkm_pool_workers": (C.c_size_t, [cp]),
-        "zkm_pool_context": (cp, [cp, C.c_size_t]),
-        "zkm_pool_device": (C.c_int, [cp, C.c_size_t]),
-        "zkm_pool_set_tuning": (C.c_int, [cp, C.c_char_p, C.c_uint64, err]),
-        "zkm_pool_prove_segments": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                              C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), err]),
-        "zkm_pool_prove_segments_columns": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
-                                                      C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), err]),
-        "zkm_pool_plan": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t]),
-        "zkm_pool_last_assignment": (C.c_int, [cp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
-        "zkm_trace_stage": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, C.c_int, cpp, err]),
-        "zkm_trace_stage_columns": (C.c_int, [cp, C.POINTER(C.c_void_p), C.c_size_t, C.c_uint, C.c_int, cpp, err]),
-        "zkm_segment_stage": (C.c_int, [cp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint), C.c_int, cpp, err]),
-        "zkm_segment_stage_columns": (C.c_int, [cp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint), C.c_int, cpp, err]),
-        "zkm_staged_segment_ptrs": (C.c_int, [cp, C.POINTER(C.c_void_p)]),
-        "zkm_staged_ptr": (cp, [cp]),
-        "zkm_staged_ready": (C.c_int, [cp, C.c_int]),
-        "zkm_staged_free": (None, [cp]),
-        "zkm_segment_tables": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(SegmentOpsStruct), C.POINTER(C.c_uint), cpp, err]),
-        "zkm_prove_segment_ops": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(SegmentOpsStruct), u64p, C.c_size_t, u64p,
-                                            C.POINTER(C.c_size_t), u64p, err]),
-        "zkm_segments_tables": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(SegmentOpsStruct), C.POINTER(C.c_uint), cpp, err]),
-        "zkm_prove_segments_ops": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(SegmentOpsStruct), C.POINTER(C.c_void_p),
-                                             C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), err]),
-        "zkm_pool_prove_segments_ops": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.c_size_t, C.POINTER(SegmentOpsStruct),
-                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                                  C.POINTER(C.c_void_p), err]),
-        "zkm_segment_ops_stage": (C.c_int, [cp, C.POINTER(SegmentOpsStruct), cpp, err]),
-        "zkm_ctx_host_waits": (C.c_uint64, [cp]),
-        "zkm_boot_counts": (None, [C.POINTER(BootImageStruct)] + [C.POINTER(C.c_size_t)] * 5),
-        "zkm_boot_witness": (C.c_int, [cp, C.POINTER(BootImageStruct), cp, cp, cp, cp, cp, err]),
-        "zkm_segment_tables_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct),
-                                              C.POINTER(C.c_uint), cpp, err]),
-        "zkm_segments_tables_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct),
-                                               C.POINTER(C.c_uint), cpp, err]),
-        "zkm_prove_segment_ops_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct), u64p,
-                                                 C.c_size_t, u64p, C.POINTER(C.c_size_t), u64p, err]),
-        "zkm_prove_segments_ops_boot": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(SegmentOpsStruct),
-                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
-                                                  C.POINTER(C.c_void_p), err]),
-        "zkm_cpu_steps_counts": (C.c_int, [C.POINTER(CpuStepsStruct)] + [C.POINTER(C.c_size_t)] * 3 + [err]),
-        "zkm_cpu_witness": (C.c_int, [cp, C.POINTER(CpuStepsStruct), C.c_uint64, C.c_uint, cp, cp, cp, cp, err]),
-        "zkm_segments_tables_steps": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(CpuStepsStruct),
-                                                C.POINTER(SegmentOpsStruct), C.POINTER(C.c_uint), cpp, err]),
-        "zkm_prove_segments_ops_steps": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(BootImageStruct), C.POINTER(CpuStepsStruct),
-                                                   C.POINTER(SegmentOpsStruct), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
-                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), err]),
-        "zkm_image_hash_plan": (C.c_size_t, [cp, C.c_size_t, cp, C.c_size_t]),
-        "zkm_image_hash": (C.c_int, [cp, C.POINTER(ImagePagesStruct), cp, cp, cp, err]),
-        "zkm_images_hash": (C.c_int, [cp, C.c_size_t, C.POINTER(ImagePagesStruct), C.POINTER(C.c_void_p), cp, cp, err]),
-        "zkm_staged_ops_get": (C.c_int, [cp, C.POINTER(SegmentOpsStruct)]),
-        "zkm_staged_ops_ready": (C.c_int, [cp, C.c_int]),
-        "zkm_staged_ops_free": (None, [cp]),
-        "zkm_host_alloc": (C.c_int, [cp, C.c_size_t, cpp, err]),
-        "zkm_host_free": (C.c_int, [cp, cp]),
-        "zkm_host_register": (C.c_int, [cp, cp, C.c_size_t, err]),
-        "zkm_host_unregister": (C.c_int, [cp, cp]),
-        "zkm_table_enum_index": (C.c_int, [C.c_int]),
-        "zkm_logic_trace": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_memory_trace": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
-        "zkm_arithmetic_trace": (C.c_int, [cp, cp, C.c_size_t, C.c_uint, cp, C.POINTER(C.c_size_t), err]),
-        "zkm_table_width": (C.c_size_t, [C.c_int]),
-        "zkm_challenger_init": (None, [C.POINTER(Challenger)]),
-        "zkm_challenger_observe": (None, [C.POINTER(Challenger), u64p, C.c_size_t]),
-        "zkm_challenger_get": (C.c_uint64, [C.POINTER(Challenger)]),
-        "zkm_challenger_compact": (None, [C.POINTER(Challenger), u64p]),
-        "zkm_standard_config": (None, [C.POINTER(StarkConfig)]),
-        "zkm_proof_words": (C.c_size_t, [C.POINTER(StarkConfig), C.c_uint, C.c_size_t, C.c_size_t, C.c_size_t]),
-        "zkm_prove_single_table": (C.c_int, [cp, C.c_int, C.POINTER(StarkConfig), cp, C.c_size_t, C.c_uint, cp, cp, C.c_size_t,
-                                             C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(Challenger), u64p, err]),
-        "zkm_prove_single_tables": (C.c_int, [cp, C.c_int, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t, C.c_uint,
-                                              C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_uint32), C.c_size_t, C.POINTER(C.c_void_p),
-                                              C.POINTER(C.c_void_p), err]),
-        "zkm_fri_proof_words": (C.c_size_t, [C.POINTER(StarkConfig), C.c_uint, C.POINTER(C.c_size_t), C.c_size_t]),
-        "zkm_fri_prove": (C.c_int, [cp, C.POINTER(StarkConfig), cpp, C.c_size_t, cp, C.c_size_t, C.POINTER(Challenger), u64p, err]),
-        "zkm_prove_openings": (C.c_int, [cp, C.POINTER(StarkConfig), cp, cp, cp, C.c_size_t, C.POINTER(Challenger), u64p, err]),
-        "zkm_prove_single_table_ctl": (C.c_int, [cp, C.c_int, C.POINTER(StarkConfig), cp, C.c_size_t, C.c_uint, cp, cp, C.c_size_t,
-                                                 cp, cp, cp, C.c_size_t, u64p, C.POINTER(Challenger), u64p, err]),
-        "zkm_num_lookup_columns": (C.c_size_t, [C.c_int, C.POINTER(StarkConfig)]),
-        "zkm_ctl_data": (C.c_int, [cp, cp, cp, cp, C.c_size_t, cp, C.c_size_t, C.c_uint, cp, err]),
-        "zkm_lookup_helper_columns": (C.c_int, [cp, cp, cp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint64, cp, C.c_size_t, C.c_uint, cp,
-                                                err]),
-        "zkm_all_proof_words": (C.c_size_t, [C.POINTER(StarkConfig), cp, C.c_size_t, cp, cp, C.c_size_t, C.POINTER(C.c_size_t)]),
-        "zkm_prove_with_traces": (C.c_int, [cp, C.POINTER(StarkConfig), cp, C.c_size_t, cp, cp, C.c_size_t, u64p, C.c_size_t, u64p,
-                                            u64p, err]),
-        "zkm_proof_get_layout": (C.c_int, [u64p, C.POINTER(ProofLayout)]),
-        "zkm_proof_get_query_layout": (C.c_int, [u64p, C.POINTER(ProofQueryLayout)]),
-        "zkm_segment_image_words": (C.c_size_t, [cp, C.c_size_t, cp, cp, C.c_size_t, C.c_size_t]),
-        "zkm_segment_image_write": (C.c_int, [cp, C.c_size_t, cp, cp, C.c_size_t, u64p, C.c_size_t, u64p, err]),
-        "zkm_prove_segment_image": (C.c_int, [cp, C.POINTER(StarkConfig), u64p, C.c_size_t, u64p, C.POINTER(C.c_size_t),
-                                              C.POINTER(C.c_size_t), u64p, err]),
-        "zkm_quotient": (C.c_int, [cp, C.c_int, cp, cp, C.POINTER(C.c_uint32), C.c_size_t, u64p, C.c_size_t, cp, err]),
-        "zkm_eval_openings": (C.c_int, [cp, cp, u64p, u64p, err]),
-        "zkm_check_constraints": (C.c_int, [cp, C.c_int, C.POINTER(StarkConfig), cp, C.c_size_t, C.c_uint, cp, C.c_size_t, cp, cp, cp, C.c_size_t,
-                                            u64p, u64p, C.c_size_t, u64p, err]),
-        "zkm_check_ctls": (C.c_int, [cp, cp, C.c_size_t, cp, cp, C.c_size_t, C.POINTER(CtlReport), err]),
-        "zkm_segment_check_ctls": (C.c_int, [cp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint), C.POINTER(CtlReport), err]),
-        "zkm_verify_proofs": (C.c_int, [cp, C.POINTER(StarkConfig), cp, C.c_size_t, cp, cp, C.c_size_t, u64p, C.c_size_t, u64p, C.c_size_t, u64p,
-                                        C.POINTER(VerifyReport), err]),
-        "zkm_verify_segments": (C.c_int, [cp, C.POINTER(StarkConfig), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
-                                          C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.POINTER(VerifyReport), err]),
-        "zkm_verify_single_table": (C.c_int, [cp, C.c_int, C.POINTER(StarkConfig), u64p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32),
-                                              C.c_size_t, C.POINTER(Challenger), C.POINTER(VerifyReport), err]),
-        "zkm_profile_enable": (None, [cp, C.c_int]),
-        "zkm_profile_reset": (None, [cp]),
-        "zkm_profile_count": (C.c_size_t, [cp]),
-        "zkm_profile_get": (C.c_int, [cp, C.c_size_t, C.POINTER(C.c_char_p), u64p, C.POINTER(C.c_double)]),
-        "zkm_version": (C.c_char_p, []),
-    }
-    for name, (res, args) in sigs.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
+    mirrors = abi_mirrors()
+    for name, ret, params in abi.prototypes():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise ZkmError("%s does not export %s, which include/zkm_hip.h declares: rebuild it" % (_LIB_PATH, name))
+        fn.restype = _ctype(ret, mirrors, ret=True)
+        fn.argtypes = [_ctype(ty, mirrors) for ty, _ in params]
     _lib = L
     return L
 
