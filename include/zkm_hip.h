@@ -902,6 +902,59 @@ int zkm_prove_segments_ops_steps(zkm_ctx* ctx, const zkm_stark_config* cfg, size
                                  const zkm_segment_ops* ops, const uint64_t* const* public_values, const size_t* npublic,
                                  uint64_t* const* proofs_out, size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
 
+/* ------------------------------------------------------------------ SHA-256 precompile calls from their inputs
+ * What generate_sha_extend and generate_sha_compress (witness/operation.rs:1183-1285, :1298-1458) and their helpers sha_extend_sponge_log
+ * and sha_compress_sponge_log (witness/util.rs:559-694) turn one SYSSHAEXTEND / SYSSHACOMPRESS call into, on the device, from the lists
+ * the caller hands over for the sponge tables anyway: sha_extend_sponge_w16 / _meta and sha_compress_sponge_hx / _w / _meta of
+ * zkm_segment_ops, in the layouts of zkm_sha_extend_sponge_trace and zkm_sha_compress_trace.  With E extend and C compress calls:
+ *   cpu_rows          96 E + 11 C   ready-made CpuColumnsView rows for RAW steps.  Extend call e: rows 96 e + 2 r (the read row of round r:
+ *                                   channels 0-3 read w[i-15], w[i-2], w[i-16], w[i-7], channel 4 writes w[i], i = r + 16; mask 0x1F) and
+ *                                   96 e + 2 r + 1 (its sponge row; mask 0).  Compress call c: rows 96 E + 11 c + 0 .. 10 -- the hx row (eight
+ *                                   reads), eight w rows (eight reads each), the sponge row (mask 0), the write row (eight writes of
+ *                                   hx[q] + state[q]); mask 0xFF but for the sponge row
+ *   memory_ops        768 E + 288 C the SPONGE's reads only (four of each input word, at the sponge row's timestamp), zkm_memory_trace's six
+ *                                   words; the operations of the rows' channels are pushed by their RAW steps, as for any RAW row
+ *   logic_ops         192 E + 768 C {op, in0, in1}: a round's four XORs / twelve operations, from xor(e ror 6, e ror 11) through
+ *                                   xor(maj_inter, b & c), in the generators' push order
+ *   sha_extend_rows   48 E          the ShaExtend table's inputs (16 bytes: w[i-15], w[i-2], w[i-16], w[i-7] little-endian) and timestamps
+ * Every list holds all extend calls in list order, round by round, then all compress calls in list order, round by round.
+ * A row holds exactly what the generators put into a CpuColumnsView::default(): clock; the six cells of each used channel (context, segment
+ * and address from the meta -- w's own context and segment for the w rows of a compress call; is_read; value); on a sponge row
+ * is_sha_extend_sponge / is_sha_compress_sponge, the values of channels 0-2 with used = 0 (context, segment, and the address of w[i] /
+ * of hx[0]) and general.element.value = w[i] / general.shash.value[q] = hx[q] + state[q].  Every other cell is 0.
+ * Clocks follow from the meta's timestamp, the sponge row's: S = timestamp / 10 (NUM_CHANNELS).  Extend: round r's sponge row at S + 2 r
+ * (the meta's timestamp is round 0's; zkm_sha_extend_sponge_trace stamps round r timestamp + 20 r), its read row one clock before.
+ * Compress: the hx row at S - 9, w row k at S - 8 + k, the sponge row at S, the write row at S + 1.
+ *   zkm_sha_calls_counts    the four counts above (any out pointer may be NULL); pure: no context, no GPU
+ *   zkm_sha_calls_steps     pure.  The cpu_rows RAW records (reads[0] = raw_base + j for row j: raw_base is where the generated rows start in
+ *                           the caller's raw_rows block; reads[1] = the row's channel mask; every other field 0) into steps_out, and the clock
+ *                           each belongs at into clocks_out: the caller puts record j at position clocks_out[j] - first_clock of its step
+ *                           list.  THE statement of masks and positions: the binding, the Rust recorder and the kernel's indexing follow it.
+ *                           The meta lists are host memory here (device memory is refused), and raw_base + cpu_rows must fit in 32 bits.
+ *   zkm_sha_calls_witness   the kernel (one launch for all calls of both kinds, one workgroup a call).  The five lists may be host or device
+ *                           memory; the five outputs are plain device pointers, so each may aim into the middle of a larger block (own RAW
+ *                           rows, own operations in front): raw_rows_out_dev cpu_rows x ZKM_CPU_COLS words row-major, canonical;
+ *                           memory_ops_out_dev memory_ops x 6 words; logic_ops_out_dev logic_ops x 3 uint32; sha_extend_inputs_out_dev
+ *                           48 E x 16 bytes; sha_extend_timestamps_out_dev 48 E words (8-byte aligned; 4 for the logic operations and the
+ *                           inputs).  Returns once the outputs are complete: one host wait.  Profile scope sha_calls/rows_lists.
+ * Refused by both, on the host before any device work, the message naming the list (extend_meta, compress_meta, extend_w16, compress_hx,
+ * compress_w) and the call's position in it: a NULL list with a nonzero count; a timestamp that is not a multiple of 10 or too small for
+ * the call's first row to have a clock >= 0; an address whose last word (w[63], hx[7], the 65th round's dummy address w + 256) does not fit
+ * in 32 bits; a context or segment of 2^32 or more.  zkm_sha_calls_witness also refuses a NULL output with a nonzero count, and makes every
+ * refusal before it reports a missing context; a refusal leaves the context usable.  A meta list in DEVICE memory is not read by the host
+ * and so not held to these rules: its words go into the rows and lists as they are (no store's address depends on them).
+ * Out of scope: the Keccak and Poseidon sponge calls stay RAW (variable length, and a digest to compute); the SYSCALL row in front of a
+ * call stays whatever the caller logs today; nothing is staged, the pool takes none, and nothing is fused into the segment builder -- the
+ * expansion is a call of its own with its own host wait, and its outputs go into zkm_cpu_steps.raw_rows and the lists of zkm_segment_ops,
+ * all of which may be device memory. */
+void zkm_sha_calls_counts(size_t nextend, size_t ncompress, size_t* cpu_rows, size_t* memory_ops, size_t* logic_ops, size_t* sha_extend_rows);
+int zkm_sha_calls_steps(const uint64_t* extend_meta, size_t nextend, const uint64_t* compress_meta, size_t ncompress, size_t raw_base,
+                        zkm_cpu_step* steps_out, uint64_t* clocks_out, char** err);
+int zkm_sha_calls_witness(zkm_ctx* ctx, const uint32_t* extend_w16, const uint64_t* extend_meta, size_t nextend, const uint32_t* compress_hx,
+                          const uint32_t* compress_w, const uint64_t* compress_meta, size_t ncompress, uint64_t* raw_rows_out_dev,
+                          uint64_t* memory_ops_out_dev, uint32_t* logic_ops_out_dev, uint8_t* sha_extend_inputs_out_dev,
+                          uint64_t* sha_extend_timestamps_out_dev, char** err);
+
 /* ------------------------------------------------------------------ a memory image's hash pages, root and image id
  * What the emulator does at every segment split -- Memory::update_page_hash and Memory::compute_image_id (emulator/src/memory.rs:388-471,
  * with poseidon / hash_page / CONST_HASH_PAGES, :43-118, and alloc_hash_page, :378-386; called from split_segment, state.rs:1477-1530) --

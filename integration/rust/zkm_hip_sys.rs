@@ -334,6 +334,15 @@ extern "C" {
                                         steps: *const zkm_cpu_steps, ops: *const zkm_segment_ops, public_values: *const *const u64,
                                         npublic: *const usize, proofs_out: *const *mut u64, proof_offsets_out: *mut usize,
                                         ctl_challenges_out: *const *mut u64, err: *mut *mut c_char) -> c_int;
+    // SHA-256 precompile calls expanded on the device from the sponge tables' lists: counts, the RAW records with their clocks, the kernel
+    pub fn zkm_sha_calls_counts(nextend: usize, ncompress: usize, cpu_rows: *mut usize, memory_ops: *mut usize, logic_ops: *mut usize,
+                                sha_extend_rows: *mut usize);
+    pub fn zkm_sha_calls_steps(extend_meta: *const u64, nextend: usize, compress_meta: *const u64, ncompress: usize, raw_base: usize,
+                               steps_out: *mut zkm_cpu_step, clocks_out: *mut u64, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_sha_calls_witness(ctx: *mut zkm_ctx, extend_w16: *const u32, extend_meta: *const u64, nextend: usize, compress_hx: *const u32,
+                                 compress_w: *const u32, compress_meta: *const u64, ncompress: usize, raw_rows_out_dev: *mut u64,
+                                 memory_ops_out_dev: *mut u64, logic_ops_out_dev: *mut u32, sha_extend_inputs_out_dev: *mut u8,
+                                 sha_extend_timestamps_out_dev: *mut u64, err: *mut *mut c_char) -> c_int;
     // what the emulator hashes between two segments: hash pages, root and image id of a memory image
     pub fn zkm_image_hash_plan(dirty_index: *const u32, ndirty: usize, hash_index_out: *mut u32, capacity: usize) -> usize;
     pub fn zkm_image_hash(ctx: *mut zkm_ctx, r#in: *const zkm_image_pages, hash_words_out: *mut u32, page_hash_root_out: *mut u8,

@@ -167,6 +167,30 @@ def cpu_steps_counts(steps):
     return tuple(int(x.value) for x in out)
 
 
+def sha_calls_counts(nextend, ncompress):
+    """zkm_sha_calls_counts: (cpu_rows, memory_ops, logic_ops, sha_extend_rows) that nextend SYSSHAEXTEND and ncompress SYSSHACOMPRESS calls
+    expand into; needs no GPU."""
+    out = [C.c_size_t() for _ in range(4)]
+    load().zkm_sha_calls_counts(nextend, ncompress, *[C.byref(x) for x in out])
+    return tuple(int(x.value) for x in out)
+
+
+def _sha_meta(meta, width):
+    return np.ascontiguousarray(meta if meta is not None else [], dtype=np.uint64).reshape(-1, width)
+
+
+def sha_calls_steps(extend_meta=None, compress_meta=None, raw_base=0):
+    """zkm_sha_calls_steps: the RAW step records (a CPU_STEP_DT array) of the calls' rows and the clock each belongs at (uint64); needs no
+    GPU.  extend_meta n x 4, compress_meta n x 8 uint64, as the sponge tables take them.  Every refusal raises ZkmError naming the list
+    and the call."""
+    em, cm = _sha_meta(extend_meta, 4), _sha_meta(compress_meta, 8)
+    rows = sha_calls_counts(len(em), len(cm))[0]
+    steps, clocks, err = np.zeros(rows, dtype=CPU_STEP_DT), np.zeros(rows, dtype=np.uint64), C.c_char_p()
+    _check(load().zkm_sha_calls_steps(em.ctypes.data if len(em) else None, len(em), cm.ctypes.data if len(cm) else None, len(cm), raw_base,
+                                      steps.ctypes.data if rows else None, clocks.ctypes.data if rows else None, C.byref(err)), err)
+    return steps, clocks
+
+
 class CtlLocation(C.Structure):
     """zkm_ctl_location: one occurrence of a reported tuple (side of the lookup, index of the table, row)."""
     _fields_ = [("side", C.c_uint32), ("table", C.c_uint32), ("row", C.c_uint64)]
@@ -1288,6 +1312,79 @@ class Context:
         m.alloc()
         _check(self.L.zkm_prove_segments_ops_steps(self.h, C.byref(cfg), m.K, im, sl, m.st, m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
         return m.results()
+
+    # ---- SHA-256 precompile calls expanded on the device (include/zkm_hip.h "SHA-256 precompile calls from their inputs")
+    def sha_calls_witness_into(self, extend, compress, nextend, ncompress, raw_rows, memory_ops, logic_ops, sha_extend_inputs, sha_extend_timestamps):
+        """zkm_sha_calls_witness as it is: extend = (w16, meta) and compress = (hx, w, meta), each list a numpy array of the right dtype
+        or device memory (or None with a count of 0); the five outputs are device addresses (integers) or None."""
+        ptr = lambda x: None if x is None else x.ctypes.data if isinstance(x, np.ndarray) else _data_ptr(x).value
+        lists = [ptr(x) for x in (tuple(extend or (None, None)) + tuple(compress or (None, None, None)))]
+        err = C.c_char_p()
+        _check(self.L.zkm_sha_calls_witness(self.h, lists[0], lists[1], nextend, lists[2], lists[3], lists[4], ncompress, raw_rows, memory_ops,
+                                            logic_ops, sha_extend_inputs, sha_extend_timestamps, C.byref(err)), err)
+
+    @staticmethod
+    def _sha_lists(extend, compress):
+        """((w16, meta), (hx, w, meta), nextend, ncompress) as contiguous numpy arrays."""
+        e = (np.ascontiguousarray(extend[0], dtype=np.uint32).reshape(-1, 16), _sha_meta(extend[1], 4)) if extend is not None else None
+        c = (np.ascontiguousarray(compress[0], dtype=np.uint32).reshape(-1, 8), np.ascontiguousarray(compress[1], dtype=np.uint32).reshape(-1, 64),
+             _sha_meta(compress[2], 8)) if compress is not None else None
+        ne, nc = (len(e[1]) if e else 0), (len(c[2]) if c else 0)
+        assert (not e or len(e[0]) == ne) and (not c or len(c[0]) == len(c[1]) == nc), "one entry of every list per call"
+        return (e if ne else None), (c if nc else None), ne, nc
+
+    def sha_calls_witness(self, extend=None, compress=None):
+        """zkm_sha_calls_witness into buffers of its own.  Returns numpy (raw_rows n x 259 uint64, memory_ops n x 6 uint64, logic_ops n x 3
+        uint32, sha_extend_inputs n x 16 uint8, sha_extend_timestamps n uint64)."""
+        e, c, ne, nc = self._sha_lists(extend, compress)
+        rows, mem, logic, ext = sha_calls_counts(ne, nc)
+        bufs = [self.alloc(max(n, 1)) for n in (rows * 259, mem * 6, (logic * 3 + 1) // 2, ext * 2, ext)]
+        try:
+            self.sha_calls_witness_into(e, c, ne, nc, *[b.ptr for b in bufs])
+            return (bufs[0].download()[:rows * 259].reshape(rows, 259), bufs[1].download()[:mem * 6].reshape(mem, 6),
+                    bufs[2].download().view(np.uint32)[:logic * 3].reshape(logic, 3), bufs[3].download().view(np.uint8)[:ext * 16].reshape(ext, 16),
+                    bufs[4].download()[:ext])
+        finally:
+            for b in bufs:
+                b.free()
+
+    def sha_calls_expand(self, steps, first_clock=0, extend=None, compress=None, memory_ops=None, logic_ops=None, **groups):
+        """A segment with SHA calls made ready for segments_tables_steps / prove_segments_ops_steps.  steps: a CpuSteps with the segment's
+        own RAW rows (host memory) whose list holds a placeholder at the position of every row of a call (sha_calls_steps says which:
+        clock - first_clock); memory_ops / logic_ops: the segment's own operations; extend = (w16, meta), compress = (hx, w, meta): the
+        calls; groups: the other groups of SegmentOps, passed on.  Returns (CpuSteps, SegmentOps): the steps with the calls' RAW records in
+        place and raw_rows a DeviceBuffer of own + generated rows; the operations with memory_ops, logic_ops and sha_extend in device
+        memory (own + generated) and the sponge groups set from the calls.  Free with ops.free() and steps.raw_rows.free()."""
+        e, c, ne, nc = self._sha_lists(extend, compress)
+        rows, mem, logic, ext = sha_calls_counts(ne, nc)
+        assert not isinstance(steps.raw_rows, DeviceBuffer) and "sha_extend" not in groups
+        own_raw = steps.raw_rows.reshape(-1)
+        own_mem = np.ascontiguousarray(memory_ops if memory_ops is not None else [], dtype=np.uint64).reshape(-1)
+        own_logic = np.ascontiguousarray(logic_ops if logic_ops is not None else [], dtype=np.uint32).reshape(-1)
+        records, clocks = sha_calls_steps(e[1] if e else None, c[2] if c else None, raw_base=steps.nraw)
+        at = clocks.astype(np.int64) - first_clock
+        assert rows == 0 or (at.min() >= 0 and at.max() < steps.steps.size and len(set(at.tolist())) == rows), "a call's rows lie outside the step list"
+        patched = steps.steps.copy()
+        patched[at] = records
+        # one device block a list: own items in front, the generated ones behind
+        sizes = (own_raw.size + rows * 259, own_mem.size + mem * 6, (own_logic.size + logic * 3 + 1) // 2, ext * 2, ext)
+        bufs = [self.alloc(n) if n else None for n in sizes]
+        try:
+            for buf, own in zip(bufs, (own_raw, own_mem, own_logic)):
+                if own.size:
+                    buf.upload(_as_words(own))
+            if rows:
+                self.sha_calls_witness_into(e, c, ne, nc, bufs[0].ptr + 8 * own_raw.size, bufs[1].ptr + 8 * own_mem.size, bufs[2].ptr + 4 * own_logic.size,
+                                            bufs[3].ptr if ext else None, bufs[4].ptr if ext else None)
+        except Exception:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+            raise
+        ops = SegmentOps(None, bufs[1], logic_ops=bufs[2], sha_extend=(bufs[3], bufs[4]) if ext else None, sha_extend_sponge=e, sha_compress=c,
+                         sha_compress_sponge=c, **groups)
+        ops.counts["nlogic"] = own_logic.size // 3 + logic     # (a DeviceBuffer is counted in whole words)
+        return CpuSteps(patched, bufs[0] if bufs[0] is not None else None, nraw=steps.nraw + rows), ops
 
     def stage_segment_ops(self, ops):
         """zkm_segment_ops_stage: queue the upload of a segment's lists behind the context's current work and return at once.  The

@@ -1,0 +1,353 @@
+// sha_calls.hip -- the SHA-256 precompile calls of a segment expanded on the device from the lists the caller already hands over for the
+// sponge tables (include/zkm_hip.h "SHA-256 precompile calls from their inputs"): the CPU rows of generate_sha_extend /
+// generate_sha_compress (witness/operation.rs:1183-1285, :1298-1458) as ready-made rows for RAW steps, and what sha_extend_sponge_log /
+// sha_compress_sponge_log (witness/util.rs:559-694) push -- the sponge's memory reads, the logic operations, the ShaExtend inputs and
+// timestamps.
+//
+// Where a call's rows and operations go is stated once, in `place` below: zkm_sha_calls_counts, zkm_sha_calls_steps (masks, clocks, RAW
+// indices) and the kernel's indexing all read it.
+//
+// k_sha_calls: ONE launch for all calls of both kinds, one workgroup of 256 threads a call (workgroups [0, E) extend, [E, E + C)
+// compress: the branch is uniform in a workgroup, the calls are independent, and a second launch would only add its gap).  The
+// sequential part -- 48 schedule steps, or 64 rounds of eight words -- is run once by one lane into LDS; after the barrier all lanes
+// write from LDS: the 49 contiguous clock and channel cells of a row by adjacent lanes, every list by adjacent lanes on adjacent words.
+// The row block is zeroed by one memset before the launch, so only the cells a row sets are stored.
+#include "cpu_steps_dev.h"
+#include "hash_constants_dev.h"
+#include "zkm_internal.h"
+
+namespace {
+
+using zkm_step::C_CH0;
+using zkm_step::C_CLOCK;
+using zkm_step::C_GEN;
+constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256;
+constexpr unsigned C_IS_SHA_EXTEND_SPONGE = 84, C_IS_SHA_COMPRESS_SPONGE = 85;   // cpu/columns/mod.rs: the sponge flags behind the bit fields
+constexpr uint32_t OP_AND = 0, OP_XOR = 2;                                       // zkm_logic_trace's codes
+static_assert(C_CLOCK + 1 == C_CH0, "a row's clock and its 48 channel cells are 49 contiguous words");
+
+// ---- the one statement of where things go.  E extend calls, then C compress calls, in every list.
+namespace place {
+constexpr unsigned EXT_ROUNDS = 48, EXT_ROWS = 2 * EXT_ROUNDS, EXT_MEM = 16 * EXT_ROUNDS, EXT_LOGIC = 4 * EXT_ROUNDS;
+constexpr unsigned CMP_ROWS = 11, CMP_MEM = 4 * 8 + 4 * 64, CMP_LOGIC = 12 * 64;
+constexpr unsigned CMP_HX = 0, CMP_W0 = 1, CMP_SPONGE = 9, CMP_WRITE = 10;       // a compress call's rows
+constexpr uint32_t MASK_EXT_READ = 0x1F, MASK_CMP = 0xFF, MASK_SPONGE = 0;       // the channels a row uses
+// rows: extend call e owns 96 e + 2 r (read row of round r) and 96 e + 2 r + 1 (its sponge row); compress call c owns 96 E + 11 c + 0..10
+GL_HD size_t ext_row(size_t e, unsigned r, unsigned sponge) { return EXT_ROWS * e + 2 * r + sponge; }
+GL_HD size_t cmp_row(size_t E, size_t c, unsigned k) { return EXT_ROWS * E + CMP_ROWS * c + k; }
+// clocks, counted from the sponge row's S = timestamp / NUM_CHANNELS: an extend round's read row is one clock before its sponge row at
+// S + 2 r; a compress call's hx row is at S - 9, w row k at S - 8 + k, the sponge row at S, the write row at S + 1
+GL_HD uint64_t ext_clock(uint64_t S, unsigned r, unsigned sponge) { return S + 2 * r - 1 + sponge; }
+GL_HD uint64_t cmp_clock(uint64_t S, unsigned k) { return S - 9 + k; }
+GL_HD uint32_t cmp_mask(unsigned k) { return k == CMP_SPONGE ? MASK_SPONGE : MASK_CMP; }
+GL_HD size_t mem_base(size_t E, size_t e_or_c, bool compress) { return compress ? EXT_MEM * E + CMP_MEM * e_or_c : EXT_MEM * e_or_c; }
+GL_HD size_t logic_base(size_t E, size_t e_or_c, bool compress) { return compress ? EXT_LOGIC * E + CMP_LOGIC * e_or_c : EXT_LOGIC * e_or_c; }
+}  // namespace place
+
+struct sha_calls_args {
+    const uint32_t* w16;     // E x 16
+    const uint64_t* emeta;   // E x 4 {context, segment, address of w[0], timestamp of round 0's sponge row}
+    const uint32_t *hx, *w;  // C x 8, C x 64
+    const uint64_t* cmeta;   // C x 8 {context, segment, address of hx[0], timestamp, address of w[0], segment of w, context of w, unused}
+    size_t E, C;
+    uint64_t *rows, *mem, *ext_ts;
+    uint32_t *logic, *ext_in;
+};
+
+__device__ __forceinline__ uint32_t ror(uint32_t x, unsigned r) { return (x >> r) | (x << (32 - r)); }
+
+// the cell `f` of a used channel (cpu/columns/mod.rs MemoryChannelView: used, is_read, addr_context, addr_segment, addr_virtual, value)
+__device__ __forceinline__ uint64_t chan_cell(unsigned f, bool is_read, uint64_t ctx, uint64_t seg, uint64_t virt, uint32_t value) {
+    return f == 0 ? 1 : f == 1 ? (uint64_t)is_read : f == 2 ? ctx : f == 3 ? seg : f == 4 ? virt : (uint64_t)value;
+}
+// the word `f` of a memory read of the sponge (zkm_memory_trace's six words)
+__device__ __forceinline__ uint64_t read_word(unsigned f, uint64_t ctx, uint64_t seg, uint64_t virt, uint64_t ts, uint32_t value) {
+    return f == 0 ? ctx : f == 1 ? seg : f == 2 ? virt : f == 3 ? ts : f == 4 ? 1 : (uint64_t)value;
+}
+
+// schedule word indices a round i reads, in the generator's order: w[i-15], w[i-2], w[i-16], w[i-7]
+__device__ __forceinline__ unsigned ext_src(unsigned i, unsigned q) { return i - (q == 0 ? 15 : q == 1 ? 2 : q == 2 ? 16 : 7); }
+
+__device__ void extend_call(const sha_calls_args& A, size_t e, uint32_t* w) {
+    const unsigned t = threadIdx.x;
+    if (t < 16) w[t] = A.w16[16 * e + t];
+    __syncthreads();
+    if (t == 0)
+        for (unsigned i = 16; i < 64; i++) {
+            const uint32_t w15 = w[i - 15], w2 = w[i - 2];
+            w[i] = (ror(w2, 17) ^ ror(w2, 19) ^ (w2 >> 10)) + w[i - 16] + (ror(w15, 7) ^ ror(w15, 18) ^ (w15 >> 3)) + w[i - 7];
+        }
+    __syncthreads();
+    const uint64_t ctx = A.emeta[4 * e], seg = A.emeta[4 * e + 1], addr = A.emeta[4 * e + 2], ts = A.emeta[4 * e + 3], S = ts / 10;
+    // the read rows: clock, then channels 0-3 reading w[i-15], w[i-2], w[i-16], w[i-7] and channel 4 writing w[i] (31 contiguous cells)
+    for (unsigned j = t; j < place::EXT_ROUNDS * 32; j += THREADS) {
+        const unsigned r = j >> 5, cell = j & 31, i = r + 16;
+        if (cell > 30) continue;
+        uint64_t v = place::ext_clock(S, r, 0);
+        if (cell) {
+            const unsigned ch = (cell - 1) / 6, f = (cell - 1) % 6, idx = ch < 4 ? ext_src(i, ch) : i;
+            v = chan_cell(f, ch < 4, ctx, seg, addr + 4 * idx, w[idx]);
+        }
+        A.rows[place::ext_row(e, r, 0) * CPU_W + C_CLOCK + cell] = v;
+    }
+    // the sponge rows: the flag, element.value = w_i, the clock, and context / segment / address of w[i] in the values of channels 0-2
+    for (unsigned j = t; j < place::EXT_ROUNDS * 8; j += THREADS) {
+        const unsigned r = j >> 3, cell = j & 7, i = r + 16;
+        if (cell > 5) continue;
+        uint64_t* row = A.rows + place::ext_row(e, r, 1) * CPU_W;
+        if (cell == 0) row[C_IS_SHA_EXTEND_SPONGE] = 1;
+        else if (cell == 1) row[C_GEN] = w[i];
+        else if (cell == 2) row[C_CLOCK] = place::ext_clock(S, r, 1);
+        else row[C_CH0 + 6 * (cell - 3) + 5] = cell == 3 ? ctx : cell == 4 ? seg : addr + 4 * i;
+    }
+    // the sponge's reads: four of each of the round's four input words (sha_extend_sponge_log), six words a read
+    uint64_t* mem = A.mem + 6 * place::mem_base(A.E, e, false);
+    for (unsigned j = t; j < 6 * place::EXT_MEM; j += THREADS) {
+        const unsigned op = j / 6, f = j % 6, r = op >> 4, idx = ext_src(r + 16, (op >> 2) & 3);
+        mem[j] = read_word(f, ctx, seg, addr + 4 * idx, ts + 20 * r, w[idx]);
+    }
+    // the four XORs of a round (generate_sha_extend), three words an operation
+    uint32_t* logic = A.logic + 3 * place::logic_base(A.E, e, false);
+    for (unsigned j = t; j < 3 * place::EXT_LOGIC; j += THREADS) {
+        const unsigned op = j / 3, f = j % 3, r = op >> 2, k = op & 3, i = r + 16;
+        const uint32_t x = w[k < 2 ? i - 15 : i - 2];
+        const uint32_t a = k == 0 ? ror(x, 7) : k == 1 ? ror(x, 7) ^ ror(x, 18) : k == 2 ? ror(x, 17) : ror(x, 17) ^ ror(x, 19);
+        const uint32_t b = k == 0 ? ror(x, 18) : k == 1 ? x >> 3 : k == 2 ? ror(x, 19) : x >> 10;
+        logic[j] = f == 0 ? OP_XOR : f == 1 ? a : b;
+    }
+    // the ShaExtend table's inputs (the four words as little-endian bytes) and timestamps
+    for (unsigned j = t; j < 4 * place::EXT_ROUNDS; j += THREADS) A.ext_in[4 * place::EXT_ROUNDS * e + j] = w[ext_src((j >> 2) + 16, j & 3)];
+    if (t < place::EXT_ROUNDS) A.ext_ts[place::EXT_ROUNDS * e + t] = ts + 20 * t;
+}
+
+__device__ void compress_call(const sha_calls_args& A, size_t c, uint32_t* w, uint32_t* st) {
+    const unsigned t = threadIdx.x;
+    if (t < 64) w[t] = A.w[64 * c + t];
+    if (t < 8) st[t] = A.hx[8 * c + t];
+    __syncthreads();
+    if (t == 0)   // st[8 i + q]: the state before round i; st[512 ..]: the compressed state
+        for (unsigned i = 0; i < 64; i++) {
+            const uint32_t* s = st + 8 * i;
+            const uint32_t a = s[0], b = s[1], cc = s[2], d = s[3], e = s[4], f = s[5], g = s[6], h = s[7];
+            const uint32_t t1 = h + (ror(e, 6) ^ ror(e, 11) ^ ror(e, 25)) + ((e & f) ^ (~e & g)) + SHA256_K_DEV[i] + w[i];
+            const uint32_t t2 = (ror(a, 2) ^ ror(a, 13) ^ ror(a, 22)) + ((a & b) ^ (a & cc) ^ (b & cc));
+            uint32_t* n = st + 8 * (i + 1);
+            n[0] = t1 + t2; n[1] = a; n[2] = b; n[3] = cc; n[4] = d + t1; n[5] = e; n[6] = f; n[7] = g;
+        }
+    __syncthreads();
+    const uint64_t* m = A.cmeta + 8 * c;
+    const uint64_t hctx = m[0], hseg = m[1], haddr = m[2], ts = m[3], waddr = m[4], wseg = m[5], wctx = m[6], S = ts / 10;
+    // the ten rows that use all eight channels: hx row (reads), eight w rows (reads), write row (hx + state); clock + 48 channel cells each
+    for (unsigned j = t; j < 10 * 64; j += THREADS) {
+        const unsigned kk = j >> 6, cell = j & 63, k = kk < 9 ? kk : place::CMP_WRITE;
+        if (cell > 48) continue;
+        uint64_t v = place::cmp_clock(S, k);
+        if (cell) {
+            const unsigned ch = (cell - 1) / 6, f = (cell - 1) % 6;
+            if (k == place::CMP_HX) v = chan_cell(f, true, hctx, hseg, haddr + 4 * ch, st[ch]);
+            else if (k == place::CMP_WRITE) v = chan_cell(f, false, hctx, hseg, haddr + 4 * ch, st[ch] + st[512 + ch]);
+            else v = chan_cell(f, true, wctx, wseg, waddr + 4 * (8 * (k - place::CMP_W0) + ch), w[8 * (k - place::CMP_W0) + ch]);
+        }
+        A.rows[place::cmp_row(A.E, c, k) * CPU_W + C_CLOCK + cell] = v;
+    }
+    // the sponge row: the flag, shash.value[q] = hx[q] + state[q], the clock, context / segment / address of hx[0] in channels 0-2
+    if (t < 13) {
+        uint64_t* row = A.rows + place::cmp_row(A.E, c, place::CMP_SPONGE) * CPU_W;
+        if (t < 8) row[C_GEN + t] = (uint32_t)(st[t] + st[512 + t]);
+        else if (t == 8) row[C_IS_SHA_COMPRESS_SPONGE] = 1;
+        else if (t == 9) row[C_CLOCK] = place::cmp_clock(S, place::CMP_SPONGE);
+        else row[C_CH0 + 6 * (t - 10) + 5] = t == 10 ? hctx : t == 11 ? hseg : haddr;
+    }
+    // the sponge's reads: four of each hx word, then four of each w_i (sha_compress_sponge_log)
+    uint64_t* mem = A.mem + 6 * place::mem_base(A.E, c, true);
+    for (unsigned j = t; j < 6 * place::CMP_MEM; j += THREADS) {
+        const unsigned op = j / 6, f = j % 6, q = op >> 2;
+        mem[j] = q < 8 ? read_word(f, hctx, hseg, haddr + 4 * q, ts, st[q]) : read_word(f, wctx, wseg, waddr + 4 * (q - 8), ts, w[q - 8]);
+    }
+    // the twelve operations of a round (generate_sha_compress), from xor(e ror 6, e ror 11) through xor(maj_inter, b & c)
+    uint32_t* logic = A.logic + 3 * place::logic_base(A.E, c, true);
+    for (unsigned j = t; j < 3 * place::CMP_LOGIC; j += THREADS) {
+        const unsigned op = j / 3, f = j % 3, i = op / 12, k = op % 12;
+        const uint32_t* s = st + 8 * i;
+        const uint32_t a = s[0], b = s[1], cc = s[2], e = s[4], ff = s[5], g = s[6];
+        uint32_t code = OP_XOR, x, y;
+        switch (k) {
+        case 0: x = ror(e, 6); y = ror(e, 11); break;
+        case 1: x = ror(e, 6) ^ ror(e, 11); y = ror(e, 25); break;
+        case 2: code = OP_AND; x = e; y = ff; break;
+        case 3: code = OP_AND; x = ~e; y = g; break;
+        case 4: x = e & ff; y = ~e & g; break;
+        case 5: x = ror(a, 2); y = ror(a, 13); break;
+        case 6: x = ror(a, 2) ^ ror(a, 13); y = ror(a, 22); break;
+        case 7: code = OP_AND; x = a; y = b; break;
+        case 8: code = OP_AND; x = a; y = cc; break;
+        case 9: code = OP_AND; x = b; y = cc; break;
+        case 10: x = a & b; y = a & cc; break;
+        default: x = (a & b) ^ (a & cc); y = b & cc; break;
+        }
+        logic[j] = f == 0 ? code : f == 1 ? x : y;
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void k_sha_calls(sha_calls_args A) {
+    __shared__ uint32_t w[64], st[8 * 65];
+    if (blockIdx.x < A.E) extend_call(A, blockIdx.x, w);
+    else compress_call(A, blockIdx.x - A.E, w, st);
+}
+
+// ---- the host's refusals: one walk over the two meta lists, naming the list and the call's position (throws the bare message)
+std::string dec(uint64_t v) { return std::to_string(v); }
+std::string hex(uint64_t v) {
+    char buf[24];
+    snprintf(buf, sizeof buf, "0x%llx", (unsigned long long)v);
+    return buf;
+}
+
+void check_meta(const uint64_t* emeta, size_t E, const uint64_t* cmeta, size_t C) {
+    constexpr uint64_t LIM = (uint64_t)1 << 32;
+    if (E >= LIM / place::EXT_MEM || C >= LIM / place::CMP_LOGIC) throw std::runtime_error("2^32 or more operations");
+    auto timestamp = [](const std::string& at, uint64_t ts, uint64_t before, const char* first) {
+        if (ts % 10) throw std::runtime_error(at + "timestamp " + dec(ts) + " is not a multiple of 10 (NUM_CHANNELS)");
+        if (ts / 10 < before) throw std::runtime_error(at + "timestamp " + dec(ts) + " puts " + first + " before clock 0");
+    };
+    auto fits = [&](const std::string& at, const char* what, uint64_t v) {
+        if (v >= LIM) throw std::runtime_error(at + what + " " + dec(v) + " does not fit in 32 bits");
+    };
+    auto address = [&](const std::string& at, const char* base, uint64_t v, uint64_t span, const char* last) {
+        if (v >= LIM || v + span >= LIM) throw std::runtime_error(at + "address of " + base + " " + hex(v) + ": " + last + " does not fit in 32 bits");
+    };
+    if (E && !emeta) throw std::runtime_error("extend_meta: NULL with a count of " + dec(E));
+    if (C && !cmeta) throw std::runtime_error("compress_meta: NULL with a count of " + dec(C));
+    // (a list in device memory is not read by the host: see the header)
+    for (size_t e = 0; e < E && !zkm_is_device_ptr(emeta); e++) {
+        const uint64_t* m = emeta + 4 * e;
+        const std::string at = "extend_meta: call " + dec(e) + ": ";
+        fits(at, "context", m[0]);
+        fits(at, "segment", m[1]);
+        address(at, "w[0]", m[2], 4 * 63, "w[63]");
+        timestamp(at, m[3], 1, "the first read row");
+    }
+    for (size_t c = 0; c < C && !zkm_is_device_ptr(cmeta); c++) {
+        const uint64_t* m = cmeta + 8 * c;
+        const std::string at = "compress_meta: call " + dec(c) + ": ";
+        fits(at, "context", m[0]);
+        fits(at, "segment", m[1]);
+        fits(at, "segment of w", m[5]);
+        fits(at, "context of w", m[6]);
+        address(at, "hx[0]", m[2], 4 * 7, "hx[7]");
+        address(at, "w[0]", m[4], 4 * 64, "the 65th round's dummy address w + 256");
+        timestamp(at, m[3], 9, "the hx row");
+    }
+}
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+void zkm_sha_calls_counts(size_t E, size_t C, size_t* cpu_rows, size_t* memory_ops, size_t* logic_ops, size_t* sha_extend_rows) {
+    if (cpu_rows) *cpu_rows = place::cmp_row(E, C, 0);
+    if (memory_ops) *memory_ops = place::mem_base(E, C, true);
+    if (logic_ops) *logic_ops = place::logic_base(E, C, true);
+    if (sha_extend_rows) *sha_extend_rows = place::EXT_ROUNDS * E;
+}
+
+int zkm_sha_calls_steps(const uint64_t* extend_meta, size_t nextend, const uint64_t* compress_meta, size_t ncompress, size_t raw_base,
+                        zkm_cpu_step* steps_out, uint64_t* clocks_out, char** err) {
+    return zkm_api("zkm_sha_calls_steps", err, [&] {
+        auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_sha_calls_steps: " + m); };
+        try {
+            check_meta(extend_meta, nextend, compress_meta, ncompress);
+        } catch (const std::exception& e) {
+            refuse(e.what());
+        }
+        if ((nextend && zkm_is_device_ptr(extend_meta)) || (ncompress && zkm_is_device_ptr(compress_meta))) refuse("the meta lists must be host memory");
+        const size_t rows = place::cmp_row(nextend, ncompress, 0);
+        if (rows && (!steps_out || !clocks_out)) refuse("null argument");
+        if (raw_base >= ((uint64_t)1 << 32) || raw_base + rows > ((uint64_t)1 << 32)) refuse("raw_base " + dec(raw_base) + ": a RAW index does not fit in 32 bits");
+        auto put = [&](size_t j, uint32_t mask, uint64_t clock) {
+            zkm_cpu_step s{};
+            s.kind = ZKM_STEP_RAW;
+            s.reads[0] = (uint32_t)(raw_base + j);
+            s.reads[1] = mask;
+            steps_out[j] = s;
+            clocks_out[j] = clock;
+        };
+        for (size_t e = 0; e < nextend; e++) {
+            const uint64_t S = extend_meta[4 * e + 3] / 10;
+            for (unsigned r = 0; r < place::EXT_ROUNDS; r++) {
+                put(place::ext_row(e, r, 0), place::MASK_EXT_READ, place::ext_clock(S, r, 0));
+                put(place::ext_row(e, r, 1), place::MASK_SPONGE, place::ext_clock(S, r, 1));
+            }
+        }
+        for (size_t c = 0; c < ncompress; c++) {
+            const uint64_t S = compress_meta[8 * c + 3] / 10;
+            for (unsigned k = 0; k < place::CMP_ROWS; k++) put(place::cmp_row(nextend, c, k), place::cmp_mask(k), place::cmp_clock(S, k));
+        }
+    });
+}
+
+int zkm_sha_calls_witness(zkm_ctx* c, const uint32_t* extend_w16, const uint64_t* extend_meta, size_t nextend, const uint32_t* compress_hx,
+                          const uint32_t* compress_w, const uint64_t* compress_meta, size_t ncompress, uint64_t* raw_rows_out_dev,
+                          uint64_t* memory_ops_out_dev, uint32_t* logic_ops_out_dev, uint8_t* sha_extend_inputs_out_dev,
+                          uint64_t* sha_extend_timestamps_out_dev, char** err) {
+    return zkm_api("zkm_sha_calls_witness", err, [&] {
+        auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_sha_calls_witness: " + m); };
+        // every refusal first, on the host: the lists, the outputs, then the context
+        try {
+            check_meta(extend_meta, nextend, compress_meta, ncompress);
+        } catch (const std::exception& e) {
+            refuse(e.what());
+        }
+        if (nextend && !extend_w16) refuse("extend_w16: NULL with a count of " + dec(nextend));
+        if (ncompress && !compress_hx) refuse("compress_hx: NULL with a count of " + dec(ncompress));
+        if (ncompress && !compress_w) refuse("compress_w: NULL with a count of " + dec(ncompress));
+        const size_t E = nextend, C = ncompress;
+        if (E + C == 0) {
+            if (!c) refuse("null argument");
+            return;
+        }
+        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(place::cmp_row(E, C, 0)) + " rows to write");
+        if (!memory_ops_out_dev) refuse("memory_ops_out_dev: NULL with " + dec(place::mem_base(E, C, true)) + " operations to write");
+        if (!logic_ops_out_dev) refuse("logic_ops_out_dev: NULL with " + dec(place::logic_base(E, C, true)) + " operations to write");
+        if (E && !sha_extend_inputs_out_dev) refuse("sha_extend_inputs_out_dev: NULL with " + dec(place::EXT_ROUNDS * E) + " rows to write");
+        if (E && !sha_extend_timestamps_out_dev) refuse("sha_extend_timestamps_out_dev: NULL with " + dec(place::EXT_ROUNDS * E) + " rows to write");
+        if (((uintptr_t)raw_rows_out_dev | (uintptr_t)memory_ops_out_dev | (uintptr_t)sha_extend_timestamps_out_dev) & 7 ||
+            ((uintptr_t)logic_ops_out_dev | (uintptr_t)sha_extend_inputs_out_dev) & 3)
+            refuse("an output is not aligned to its words (8 bytes; 4 for the logic operations and the ShaExtend inputs)");
+        if (!c) refuse("null argument");
+        if (E + C > 0x7FFFFFFF) refuse("2^31 or more calls");
+        ZKM_HIP_CHECK(hipSetDevice(c->device));
+        // the lists the host holds go up in one block
+        const struct { const void* p; size_t bytes; } in[5] = {{extend_w16, 64 * E}, {extend_meta, 32 * E}, {compress_hx, 32 * C}, {compress_w, 256 * C},
+                                                               {compress_meta, 64 * C}};
+        const void* dev[5];
+        size_t off[5], total = 0;
+        for (int i = 0; i < 5; i++) {
+            off[i] = total;
+            if (in[i].bytes && !zkm_is_device_ptr(in[i].p)) total += up256(in[i].bytes);
+        }
+        zkm_scratch block;
+        if (total) block = zkm_scratch(c, total);
+        for (int i = 0; i < 5; i++) {
+            dev[i] = in[i].p;
+            if (in[i].bytes && !zkm_is_device_ptr(in[i].p)) {
+                dev[i] = block.as<char>() + off[i];
+                ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        ZKM_HIP_CHECK(hipMemsetAsync(raw_rows_out_dev, 0, place::cmp_row(E, C, 0) * CPU_W * sizeof(uint64_t), c->stream));
+        const sha_calls_args A{(const uint32_t*)dev[0], (const uint64_t*)dev[1], (const uint32_t*)dev[2], (const uint32_t*)dev[3], (const uint64_t*)dev[4],
+                               E, C, raw_rows_out_dev, memory_ops_out_dev, sha_extend_timestamps_out_dev, logic_ops_out_dev,
+                               (uint32_t*)sha_extend_inputs_out_dev};
+        {
+            zkm_prof_scope ps(c, "sha_calls/rows_lists");
+            hipLaunchKernelGGL(k_sha_calls, dim3((unsigned)(E + C)), dim3(THREADS), 0, c->stream, A);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        c->sync();   // (the block and the caller's lists are in use until here)
+    });
+}
+
+}  // extern "C"
