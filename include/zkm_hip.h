@@ -275,9 +275,13 @@ int zkm_poseidon_sponge_trace(zkm_ctx* ctx, const uint8_t* inputs, const uint64_
  *   inputs        concatenated input bytes of all operations (host or device)
  *   input_off     nops + 1 byte offsets into `inputs` (host)
  *   meta          nops x 4 words (host): context, segment, virt_base, timestamp; word i of the input is read at
- *                 virt_base + i (contiguous base addresses)
+ *                 virt_base + i (contiguous base addresses), or, with ZKM_SPONGE_BYTE_ADDRESSED set in virt_base, at
+ *                 (virt_base & ~ZKM_SPONGE_BYTE_ADDRESSED) + 4 i: the addresses generate_keccak hands to keccak_sponge_log
+ *                 (witness/operation.rs:1118-1134), one memory word every 4 bytes.  The flag is per operation and changes
+ *                 nothing else of a row; zkm_poseidon_sponge_trace reads it the same way.
  * Output: 470 x 2^log_n column-major, device pointer.  Fails if the operations need more than 2^log_n rows or if an
  * operation is empty (the reference indexes base_address[0]). */
+#define ZKM_SPONGE_BYTE_ADDRESSED 0x8000000000000000ULL
 #define ZKM_KECCAK_SPONGE_COLS 470
 int zkm_keccak_sponge_trace(zkm_ctx* ctx, const uint8_t* inputs, const uint64_t* input_off, const uint64_t* meta, size_t nops,
                             unsigned log_n, uint64_t* out_dev, size_t* rows_used_out, char** err);
@@ -943,7 +947,8 @@ int zkm_prove_segments_ops_steps(zkm_ctx* ctx, const zkm_stark_config* cfg, size
  * in 32 bits; a context or segment of 2^32 or more.  zkm_sha_calls_witness also refuses a NULL output with a nonzero count, and makes every
  * refusal before it reports a missing context; a refusal leaves the context usable.  A meta list in DEVICE memory is not read by the host
  * and so not held to these rules: its words go into the rows and lists as they are (no store's address depends on them).
- * Out of scope: the Keccak and Poseidon sponge calls stay RAW (variable length, and a digest to compute); the SYSCALL row in front of a
+ * Out of scope: the Keccak calls have their own expansion (the next section), and the Poseidon sponge has no syscall in the reference (only
+ * the bootstrap produces such operations); the SYSCALL row in front of a
  * call stays whatever the caller logs today; nothing is staged, the pool takes none, and nothing is fused into the segment builder -- the
  * expansion is a call of its own with its own host wait, and its outputs go into zkm_cpu_steps.raw_rows and the lists of zkm_segment_ops,
  * all of which may be device memory. */
@@ -954,6 +959,56 @@ int zkm_sha_calls_witness(zkm_ctx* ctx, const uint32_t* extend_w16, const uint64
                           const uint32_t* compress_w, const uint64_t* compress_meta, size_t ncompress, uint64_t* raw_rows_out_dev,
                           uint64_t* memory_ops_out_dev, uint32_t* logic_ops_out_dev, uint8_t* sha_extend_inputs_out_dev,
                           uint64_t* sha_extend_timestamps_out_dev, char** err);
+
+/* ------------------------------------------------------------------ SYSKECCAK precompile calls from their input bytes
+ * What generate_keccak (witness/operation.rs:1101-1181) and its helper keccak_sponge_log (witness/util.rs:471-557, with xor_into_sponge,
+ * :724-741) turn one SYSKECCAK call into, on the device, from the lists the caller hands over for the KeccakSponge table anyway:
+ * keccak_sponge_inputs / _off / _meta of zkm_segment_ops, in the layout of zkm_keccak_sponge_trace, with ZKM_SPONGE_BYTE_ADDRESSED set in
+ * every meta's virt_base (a call reads one memory word every 4 bytes), and one more word a call: digest_addrs, the address the digest is
+ * written to (a2).  For a call of L = 4 W input bytes, with R = ceil(W / 8) and B = L / 136 + 1:
+ *   cpu_rows      R + 2    ready-made CpuColumnsView rows for RAW steps: read row j (channels 0 .. min(8, W - 8 j) - 1 read word 8 j + i at
+ *                          base + 4 (8 j + i), the value the big-endian reading of the word's four input bytes; mask = that many low
+ *                          bits), the sponge row (mask 0: is_keccak_sponge; the values of channels 0-3 with used = 0 are context, segment,
+ *                          the address of word (L / 136) * 34 -- 0 if the input has no such word -- and L; general.khash.value[i] the
+ *                          big-endian reading of digest bytes 4 (7 - i) ..), the write row (mask 0xFF: channel i writes the big-endian
+ *                          reading of digest bytes 4 i .. to digest_addr + 4 i).  Every other cell is 0
+ *   memory_ops    L        the SPONGE's reads only, zkm_memory_trace's six words: one a byte, of the word that holds it, in byte order, at
+ *                          the sponge row's timestamp; the operations of the rows' channels are pushed by their RAW steps
+ *   logic_ops     34 B     {XOR, lhs, rhs}, block by block: lhs the state's 32-bit word before the absorption, rhs the padded block's word,
+ *                          both little-endian; the last block carries pad10*1
+ *   keccak_perms  B        the KeccakStark inputs (25 words: the state after the XOR, before the permutation) and timestamps (the sponge
+ *                          row's)
+ * Every list holds the calls in list order; call k's items start at the sum of the earlier calls' counts.  Context and segment come from
+ * the meta (the reference hard-codes 0 and Segment::Code: for its callers the rows are identical).  Clocks follow from the meta's
+ * timestamp, the sponge row's: S = timestamp / 10 (NUM_CHANNELS); read row j at S - R + j, the sponge row at S, the write row at S + 1.
+ *   zkm_keccak_calls_counts   the four totals (any out pointer may be NULL); pure: no context, no GPU
+ *   zkm_keccak_calls_steps    pure.  The cpu_rows RAW records (reads[0] = raw_base + j, reads[1] = the row's channel mask, every other field
+ *                             0) into steps_out and the clock each belongs at into clocks_out, as zkm_sha_calls_steps does.  THE statement
+ *                             of masks and positions: the binding, the Rust recorder and the kernel's indexing follow it.  meta is host
+ *                             memory here, and raw_base + cpu_rows must fit in 32 bits.
+ *   zkm_keccak_calls_witness  the kernel (one launch, one workgroup a call).  input_off is host memory; inputs, meta and digest_addrs may be
+ *                             host or device memory; the five outputs are plain device pointers, so each may aim into the middle of a
+ *                             larger block: raw_rows_out_dev cpu_rows x ZKM_CPU_COLS words row-major, canonical; memory_ops_out_dev
+ *                             memory_ops x 6 words; logic_ops_out_dev logic_ops x 3 uint32 (4-byte aligned, the others 8);
+ *                             keccak_inputs_out_dev keccak_perms x 25 words; keccak_timestamps_out_dev keccak_perms words.  Returns once
+ *                             the outputs are complete: one host wait.  Profile scope keccak_calls/rows_lists.
+ * Refused, on the host before any device work and before a missing context is reported, the message naming the list (input_off, meta,
+ * digest_addrs, inputs, or the output) and the call's position: a NULL list or output with a nonzero count; input_off in device memory;
+ * offsets that do not increase; a length that is 0 or not a multiple of 4; a meta without ZKM_SPONGE_BYTE_ADDRESSED; a timestamp that is
+ * not a multiple of 10 or too small for the first read row's clock to be >= 0; base + 4 (W - 1) or digest_addr + 28 that does not fit in
+ * 32 bits; a context or segment of 2^32 or more; raw_base + cpu_rows that does not fit in 32 bits; an output that is not aligned to its
+ * words.  A refusal leaves the context usable.  meta or digest_addrs in DEVICE memory is not read by the host and so not held to these
+ * rules (no store's address depends on them).
+ * Lengths that are not a multiple of 4: the reference's sponge read of the last word then carries the padding byte (rem_data,
+ * util.rs:515-535) and the other bytes of that memory word follow from no list, so such a call is refused here.  It can still travel as
+ * RAW rows and the caller's own lists beside a flagged sponge operation: zkm_keccak_sponge_trace takes any length. */
+int zkm_keccak_calls_counts(const uint64_t* input_off, size_t ncalls, size_t* cpu_rows, size_t* memory_ops, size_t* logic_ops,
+                            size_t* keccak_perms, char** err);
+int zkm_keccak_calls_steps(const uint64_t* input_off, const uint64_t* meta, size_t ncalls, size_t raw_base, zkm_cpu_step* steps_out,
+                           uint64_t* clocks_out, char** err);
+int zkm_keccak_calls_witness(zkm_ctx* ctx, const uint8_t* inputs, const uint64_t* input_off, const uint64_t* meta,
+                             const uint64_t* digest_addrs, size_t ncalls, uint64_t* raw_rows_out_dev, uint64_t* memory_ops_out_dev,
+                             uint32_t* logic_ops_out_dev, uint64_t* keccak_inputs_out_dev, uint64_t* keccak_timestamps_out_dev, char** err);
 
 /* ------------------------------------------------------------------ a memory image's hash pages, root and image id
  * What the emulator does at every segment split -- Memory::update_page_hash and Memory::compute_image_id (emulator/src/memory.rs:388-471,

@@ -55,18 +55,22 @@ fn sponge_lists<'a>(ops: impl Iterator<Item = (&'a [MemoryAddress], usize, &'a [
     for (k, (base_address, timestamp, input)) in ops.enumerate() {
         ensure!(!input.is_empty() && !base_address.is_empty(), "{} op {}: empty input (base_address[0] is required)", what, k);
         let (ctx, seg, virt) = addr_words(&base_address[0]);
+        // the words sit 1 apart (the bootstrap's operations) or 4 apart (a SYSKECCAK call reads one memory word every 4 bytes: the meta
+        // says so with ZKM_SPONGE_BYTE_ADDRESSED); an operation of one word is logged unflagged
+        let step = if base_address.len() > 1 { addr_words(&base_address[1]).2.wrapping_sub(virt) } else { 1 };
+        ensure!(step == 1 || step == 4, "{} op {}: base addresses are neither 1 nor 4 apart", what, k);
         for (i, a) in base_address.iter().enumerate() {
-            ensure!(addr_words(a) == (ctx, seg, virt + i as u64), "{} op {}: base addresses are not contiguous", what, k);
+            ensure!(addr_words(a) == (ctx, seg, virt + step * i as u64), "{} op {}: base addresses are not {} apart throughout", what, k, step);
         }
         bytes.extend_from_slice(input);
         off.push(bytes.len() as u64);
-        meta.extend_from_slice(&[ctx, seg, virt, timestamp as u64]);
+        meta.extend_from_slice(&[ctx, seg, if step == 4 { virt | ZKM_SPONGE_BYTE_ADDRESSED } else { virt }, timestamp as u64]);
     }
     Ok((bytes, off, meta))
 }
 
 /// Packs a segment's Traces into the lists of zkm_segment_ops.  Fails where the C layouts cannot express the data: sponge addresses
-/// that are not contiguous, SHA-extend round operations that are not complete 48-round schedules, SHA-compress rows that are not 65
+/// that are neither 1 nor 4 apart throughout an operation, SHA-extend round operations that are not complete 48-round schedules, SHA-compress rows that are not 65
 /// per compression (or do not follow their compression's addresses and timestamp).
 pub fn segment_ops_host<F: PrimeField64>(traces: &Traces<F>) -> Result<SegmentOpsHost> {
     let le = |b: &[u8]| u32::from_le_bytes([b[0], b[1], b[2], b[3]]);

@@ -14,7 +14,7 @@
 //!   * at the end of the segment `finish` expands the calls into device memory and patches the reserved steps; the segment is then
 //!     proven with `prove_segments_ops_steps_raw`, its `zkm_cpu_steps.raw_rows` and the memory / logic / ShaExtend lists of its
 //!     `zkm_segment_ops` pointing at the device blocks `finish` returns.
-//! The SYSCALL row in front of a call is logged as today.  Keccak and Poseidon sponge calls stay RAW rows.
+//! The SYSCALL row in front of a call is logged as today.  SYSKECCAK calls: keccak_calls_hip.rs (the Poseidon sponge has no syscall).
 //!
 //! Goes into the zkm-prover crate as `prover/src/sha_calls_hip.rs`, beside `cpu_steps_hip.rs`.  NOT COMPILED in the build image (no
 //! cargo / rustc there).

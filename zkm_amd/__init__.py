@@ -191,6 +191,33 @@ def sha_calls_steps(extend_meta=None, compress_meta=None, raw_base=0):
     return steps, clocks
 
 
+def keccak_calls_counts(input_off):
+    """zkm_keccak_calls_counts: (cpu_rows, memory_ops, logic_ops, keccak_perms) that the SYSKECCAK calls with these ncalls + 1 input
+    offsets expand into; needs no GPU.  A length that is 0 or not a multiple of 4 raises ZkmError naming the call."""
+    off = np.ascontiguousarray(input_off, dtype=np.uint64).reshape(-1)
+    out, err = [C.c_size_t() for _ in range(4)], C.c_char_p()
+    _check(load().zkm_keccak_calls_counts(off.ctypes.data if off.size > 1 else None, max(off.size, 1) - 1, *[C.byref(x) for x in out],
+                                          C.byref(err)), err)
+    return tuple(int(x.value) for x in out)
+
+
+def keccak_calls_steps(input_off, meta, raw_base=0):
+    """zkm_keccak_calls_steps: the RAW step records (a CPU_STEP_DT array) of the calls' rows and the clock each belongs at (uint64); needs
+    no GPU.  input_off ncalls + 1, meta ncalls x 4 uint64 with ZKM_SPONGE_BYTE_ADDRESSED in word 2, as the KeccakSponge table takes
+    them.  Every refusal raises ZkmError naming the list and the call."""
+    off, m = np.ascontiguousarray(input_off, dtype=np.uint64).reshape(-1), _sha_meta(meta, 4)
+    n = len(m)
+    assert off.size == n + 1, "one offset more than calls"
+    rows = keccak_calls_counts(off)[0]
+    steps, clocks, err = np.zeros(rows, dtype=CPU_STEP_DT), np.zeros(rows, dtype=np.uint64), C.c_char_p()
+    _check(load().zkm_keccak_calls_steps(off.ctypes.data if n else None, m.ctypes.data if n else None, n, raw_base,
+                                         steps.ctypes.data if rows else None, clocks.ctypes.data if rows else None, C.byref(err)), err)
+    return steps, clocks
+
+
+SPONGE_BYTE_ADDRESSED = _H["SPONGE_BYTE_ADDRESSED"]
+
+
 class CtlLocation(C.Structure):
     """zkm_ctl_location: one occurrence of a reported tuple (side of the lookup, index of the table, row)."""
     _fields_ = [("side", C.c_uint32), ("table", C.c_uint32), ("row", C.c_uint64)]
@@ -1349,42 +1376,105 @@ class Context:
                 b.free()
 
     def sha_calls_expand(self, steps, first_clock=0, extend=None, compress=None, memory_ops=None, logic_ops=None, **groups):
-        """A segment with SHA calls made ready for segments_tables_steps / prove_segments_ops_steps.  steps: a CpuSteps with the segment's
-        own RAW rows (host memory) whose list holds a placeholder at the position of every row of a call (sha_calls_steps says which:
-        clock - first_clock); memory_ops / logic_ops: the segment's own operations; extend = (w16, meta), compress = (hx, w, meta): the
-        calls; groups: the other groups of SegmentOps, passed on.  Returns (CpuSteps, SegmentOps): the steps with the calls' RAW records in
-        place and raw_rows a DeviceBuffer of own + generated rows; the operations with memory_ops, logic_ops and sha_extend in device
-        memory (own + generated) and the sponge groups set from the calls.  Free with ops.free() and steps.raw_rows.free()."""
+        """calls_expand for a segment whose only calls are SHA calls; groups: the other groups of SegmentOps, passed on (keccak = the
+        segment's own permutations)."""
+        assert "sha_extend" not in groups
+        return self.calls_expand(steps, first_clock, extend=extend, compress=compress, memory_ops=memory_ops, logic_ops=logic_ops,
+                                 keccak_perms=groups.pop("keccak", None), **groups)
+
+    # ---- SYSKECCAK precompile calls expanded on the device (include/zkm_hip.h "SYSKECCAK precompile calls from their input bytes")
+    @staticmethod
+    def _keccak_lists(keccak):
+        """(inputs u8, off n + 1, meta n x 4, digest_addrs n) as contiguous numpy arrays and the number of calls; None, 0 without calls."""
+        if keccak is None:
+            return None, 0
+        inputs, off, meta, digest_addrs = keccak
+        k = (np.ascontiguousarray(inputs, dtype=np.uint8).reshape(-1), np.ascontiguousarray(off, dtype=np.uint64).reshape(-1), _sha_meta(meta, 4),
+             np.ascontiguousarray(digest_addrs, dtype=np.uint64).reshape(-1))
+        n = len(k[2])
+        assert k[1].size == n + 1 and k[3].size == n, "one meta and one digest address per call, and one offset more"
+        return (k if n else None), n
+
+    def keccak_calls_witness_into(self, keccak, ncalls, raw_rows, memory_ops, logic_ops, keccak_inputs, keccak_timestamps):
+        """zkm_keccak_calls_witness as it is: keccak = (inputs, input_off, meta, digest_addrs), input_off a numpy array, the others numpy
+        arrays of the right dtype or device memory (or None with a count of 0); the five outputs are device addresses (integers) or None."""
+        ptr = lambda x: None if x is None else x.ctypes.data if isinstance(x, np.ndarray) else _data_ptr(x).value
+        lists = [ptr(x) for x in tuple(keccak or (None,) * 4)]
+        err = C.c_char_p()
+        _check(self.L.zkm_keccak_calls_witness(self.h, *lists, ncalls, raw_rows, memory_ops, logic_ops, keccak_inputs, keccak_timestamps,
+                                               C.byref(err)), err)
+
+    def keccak_calls_witness(self, inputs, input_off, meta, digest_addrs):
+        """zkm_keccak_calls_witness into buffers of its own.  Returns numpy (raw_rows n x 259 uint64, memory_ops n x 6 uint64, logic_ops
+        n x 3 uint32, keccak_inputs n x 25 uint64, keccak_timestamps n uint64)."""
+        k, n = self._keccak_lists((inputs, input_off, meta, digest_addrs))
+        rows, mem, logic, perms = keccak_calls_counts(k[1]) if n else (0, 0, 0, 0)
+        bufs = [self.alloc(max(w, 1)) for w in (rows * 259, mem * 6, (logic * 3 + 1) // 2, perms * 25, perms)]
+        try:
+            self.keccak_calls_witness_into(k, n, *[b.ptr for b in bufs])
+            return (bufs[0].download()[:rows * 259].reshape(rows, 259), bufs[1].download()[:mem * 6].reshape(mem, 6),
+                    bufs[2].download().view(np.uint32)[:logic * 3].reshape(logic, 3), bufs[3].download()[:perms * 25].reshape(perms, 25),
+                    bufs[4].download()[:perms])
+        finally:
+            for b in bufs:
+                b.free()
+
+    def calls_expand(self, steps, first_clock=0, extend=None, compress=None, keccak=None, memory_ops=None, logic_ops=None, keccak_perms=None,
+                     **groups):
+        """A segment with precompile calls made ready for segments_tables_steps / prove_segments_ops_steps.  steps: a CpuSteps with the
+        segment's own RAW rows (host memory) whose list holds a placeholder at the position of every row of a call (sha_calls_steps and
+        keccak_calls_steps say which: clock - first_clock); extend = (w16, meta), compress = (hx, w, meta), keccak = (inputs, input_off,
+        meta, digest_addrs): the calls; memory_ops / logic_ops / keccak_perms = (inputs, timestamps): the segment's own operations;
+        groups: the other groups of SegmentOps, passed on.  Returns (CpuSteps, SegmentOps): the steps with the calls' RAW records in place
+        and raw_rows a DeviceBuffer of own rows, then the SHA calls', then the Keccak calls'; the operations with memory_ops, logic_ops,
+        sha_extend and keccak in device memory (own items in front, the generated ones behind in the same order) and the sponge groups
+        set from the calls.  Free with ops.free() and steps.raw_rows.free()."""
         e, c, ne, nc = self._sha_lists(extend, compress)
+        k, nk = self._keccak_lists(keccak)
         rows, mem, logic, ext = sha_calls_counts(ne, nc)
-        assert not isinstance(steps.raw_rows, DeviceBuffer) and "sha_extend" not in groups
+        krows, kmem, klogic, kperms = keccak_calls_counts(k[1]) if nk else (0, 0, 0, 0)
+        assert not isinstance(steps.raw_rows, DeviceBuffer) and not {"sha_extend", "keccak_sponge"} & set(groups)
         own_raw = steps.raw_rows.reshape(-1)
         own_mem = np.ascontiguousarray(memory_ops if memory_ops is not None else [], dtype=np.uint64).reshape(-1)
         own_logic = np.ascontiguousarray(logic_ops if logic_ops is not None else [], dtype=np.uint32).reshape(-1)
+        own_perms = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (keccak_perms if keccak_perms is not None else ([], []))]
+        assert own_perms[0].size == 25 * own_perms[1].size, "25 words and one timestamp per permutation"
         records, clocks = sha_calls_steps(e[1] if e else None, c[2] if c else None, raw_base=steps.nraw)
+        if nk:
+            krecords, kclocks = keccak_calls_steps(k[1], k[2], raw_base=steps.nraw + rows)
+            records, clocks = (np.concatenate([records, krecords]), np.concatenate([clocks, kclocks])) if rows else (krecords, kclocks)
         at = clocks.astype(np.int64) - first_clock
-        assert rows == 0 or (at.min() >= 0 and at.max() < steps.steps.size and len(set(at.tolist())) == rows), "a call's rows lie outside the step list"
+        taken = np.zeros(steps.steps.size, dtype=bool)
+        if at.size and at.min() >= 0 and at.max() < taken.size:
+            taken[at] = True
+        assert np.count_nonzero(taken) == at.size, "a call's rows lie outside the step list, or two rows share a clock"
         patched = steps.steps.copy()
         patched[at] = records
         # one device block a list: own items in front, the generated ones behind
-        sizes = (own_raw.size + rows * 259, own_mem.size + mem * 6, (own_logic.size + logic * 3 + 1) // 2, ext * 2, ext)
+        sizes = (own_raw.size + (rows + krows) * 259, own_mem.size + (mem + kmem) * 6, (own_logic.size + (logic + klogic) * 3 + 1) // 2, ext * 2, ext,
+                 own_perms[0].size + kperms * 25, own_perms[1].size + kperms)
         bufs = [self.alloc(n) if n else None for n in sizes]
         try:
-            for buf, own in zip(bufs, (own_raw, own_mem, own_logic)):
-                if own.size:
+            for buf, own in zip(bufs, (own_raw, own_mem, own_logic, None, None, own_perms[0], own_perms[1])):
+                if own is not None and own.size:
                     buf.upload(_as_words(own))
             if rows:
                 self.sha_calls_witness_into(e, c, ne, nc, bufs[0].ptr + 8 * own_raw.size, bufs[1].ptr + 8 * own_mem.size, bufs[2].ptr + 4 * own_logic.size,
                                             bufs[3].ptr if ext else None, bufs[4].ptr if ext else None)
+            if nk:
+                self.keccak_calls_witness_into(k, nk, bufs[0].ptr + 8 * (own_raw.size + rows * 259), bufs[1].ptr + 8 * (own_mem.size + mem * 6),
+                                               bufs[2].ptr + 4 * (own_logic.size + logic * 3), bufs[5].ptr + 8 * own_perms[0].size,
+                                               bufs[6].ptr + 8 * own_perms[1].size)
         except Exception:
             for b in bufs:
                 if b is not None:
                     b.free()
             raise
         ops = SegmentOps(None, bufs[1], logic_ops=bufs[2], sha_extend=(bufs[3], bufs[4]) if ext else None, sha_extend_sponge=e, sha_compress=c,
-                         sha_compress_sponge=c, **groups)
-        ops.counts["nlogic"] = own_logic.size // 3 + logic     # (a DeviceBuffer is counted in whole words)
-        return CpuSteps(patched, bufs[0] if bufs[0] is not None else None, nraw=steps.nraw + rows), ops
+                         sha_compress_sponge=c, keccak=(bufs[5], bufs[6]) if bufs[5] is not None else None, keccak_sponge=k[:3] if nk else None,
+                         **groups)
+        ops.counts["nlogic"] = own_logic.size // 3 + logic + klogic     # (a DeviceBuffer is counted in whole words)
+        return CpuSteps(patched, bufs[0] if bufs[0] is not None else None, nraw=steps.nraw + rows + krows), ops
 
     def stage_segment_ops(self, ops):
         """zkm_segment_ops_stage: queue the upload of a segment's lists behind the context's current work and return at once.  The

@@ -1,0 +1,350 @@
+// keccak_calls.hip -- the SYSKECCAK precompile calls of a segment expanded on the device from the lists the caller already hands over for
+// the KeccakSponge table (include/zkm_hip.h "SYSKECCAK precompile calls from their input bytes"): the CPU rows of generate_keccak
+// (witness/operation.rs:1101-1181) as ready-made rows for RAW steps, and what keccak_sponge_log (witness/util.rs:471-557, with
+// xor_into_sponge, :724-741) pushes -- the sponge's memory reads, the XORs of every absorption, the Keccak-f inputs and timestamps.
+//
+// Where a call's rows and operations go is stated once, in `place` below: zkm_keccak_calls_counts, zkm_keccak_calls_steps (masks, clocks,
+// RAW indices) and the kernel's indexing all read it.  A call's length varies, so where call k starts in each list is a prefix sum over the
+// earlier calls; the host computes the four sums a call from input_off and uploads them with the lists.
+//
+// k_keccak_calls: ONE launch, one workgroup of 256 threads a call.  The sequential part -- B absorptions and permutations -- is run by one
+// lane, block by block: all lanes stage the padded 136-byte block in LDS, lane 0 XORs it into the state, stores the state (the Keccak-f
+// input, an output anyway) and permutes.  The digest goes into LDS.  After the barrier all lanes write: the 49 contiguous clock and
+// channel cells of a row by adjacent lanes, every list by adjacent lanes on adjacent words; an XOR's lhs is the stored state word ^ the
+// block word.  The row block is zeroed by one memset before the launch, so only the cells a row sets are stored.
+#include <vector>
+
+#include "cpu_steps_dev.h"
+#include "hash_constants_dev.h"
+#include "zkm_internal.h"
+
+namespace {
+
+using zkm_step::C_CH0;
+using zkm_step::C_CLOCK;
+using zkm_step::C_GEN;
+constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256;
+constexpr unsigned C_IS_KECCAK_SPONGE = 83;   // cpu/columns/mod.rs: the sponge flags behind the bit fields
+constexpr uint32_t OP_XOR = 2;                // zkm_logic_trace's code
+constexpr uint64_t FLAG = ZKM_SPONGE_BYTE_ADDRESSED;
+static_assert(C_CLOCK + 1 == C_CH0, "a row's clock and its 48 channel cells are 49 contiguous words");
+
+// ---- the one statement of where things go, for a call of L input bytes (a positive multiple of 4)
+namespace place {
+constexpr unsigned RATE = 136, RATE_U32 = 34, STATE = 25;                         // KECCAK_RATE_BYTES, KECCAK_RATE_U32S, the state's u64 words
+constexpr uint32_t MASK_SPONGE = 0, MASK_WRITE = 0xFF;
+GL_HD size_t words(size_t L) { return L / 4; }
+GL_HD size_t read_rows(size_t L) { return (words(L) + 7) / 8; }                   // R: eight words a row
+GL_HD size_t blocks(size_t L) { return L / RATE + 1; }                            // B: the last one carries pad10*1 (it may hold nothing else)
+// what a call adds to each list
+GL_HD size_t rows(size_t L) { return read_rows(L) + 2; }
+GL_HD size_t mem(size_t L) { return L; }
+GL_HD size_t logic(size_t L) { return RATE_U32 * blocks(L); }
+// a call's rows: read rows 0 .. R - 1, the sponge row, the write row
+GL_HD size_t sponge_row(size_t L) { return read_rows(L); }
+GL_HD size_t write_row(size_t L) { return read_rows(L) + 1; }
+// clocks, counted from the sponge row's S = timestamp / NUM_CHANNELS: read row j at S - R + j, the write row at S + 1
+GL_HD uint64_t row_clock(uint64_t S, size_t L, size_t j) { return S - read_rows(L) + j; }
+GL_HD unsigned read_channels(size_t L, size_t j) { return words(L) - 8 * j < 8 ? (unsigned)(words(L) - 8 * j) : 8; }
+GL_HD uint32_t row_mask(size_t L, size_t j) { return j < read_rows(L) ? (1u << read_channels(L, j)) - 1 : j == sponge_row(L) ? MASK_SPONGE : MASK_WRITE; }
+// the word whose address the sponge row carries: the first of the final block (0 where the input ends before it)
+GL_HD size_t final_word(size_t L) { return L / RATE * RATE_U32; }
+}  // namespace place
+
+struct call_base { uint64_t row, mem, logic, perm; };   // where a call starts in each list: the sums of the earlier calls' counts
+
+struct keccak_calls_args {
+    const uint8_t* inputs;
+    const uint64_t* off;         // ncalls + 1
+    const uint64_t* meta;        // ncalls x 4 {context, segment, address of word 0 | FLAG, timestamp of the sponge row}
+    const uint64_t* digest_addr; // ncalls
+    const call_base* base;       // ncalls
+    uint64_t *rows, *mem, *perm_in, *perm_ts;
+    uint32_t* logic;
+};
+
+// the cell `f` of a used channel (cpu/columns/mod.rs MemoryChannelView: used, is_read, addr_context, addr_segment, addr_virtual, value)
+__device__ __forceinline__ uint64_t chan_cell(unsigned f, bool is_read, uint64_t ctx, uint64_t seg, uint64_t virt, uint32_t value) {
+    return f == 0 ? 1 : f == 1 ? (uint64_t)is_read : f == 2 ? ctx : f == 3 ? seg : f == 4 ? virt : (uint64_t)value;
+}
+// the word `f` of a memory read of the sponge (zkm_memory_trace's six words)
+__device__ __forceinline__ uint64_t read_word(unsigned f, uint64_t ctx, uint64_t seg, uint64_t virt, uint64_t ts, uint32_t value) {
+    return f == 0 ? ctx : f == 1 ? seg : f == 2 ? virt : f == 3 ? ts : f == 4 ? 1 : (uint64_t)value;
+}
+// byte `pos` of the padded message: the input, then pad10*1 up to the end of the last block
+__device__ __forceinline__ uint32_t padded_byte(const uint8_t* __restrict__ msg, size_t L, size_t pos) {
+    if (pos < L) return msg[pos];
+    return (pos == L ? 0x01u : 0u) | (pos == place::RATE * place::blocks(L) - 1 ? 0x80u : 0u);
+}
+// memory word w of the input as the CPU reads it: the big-endian reading of its four bytes
+__device__ __forceinline__ uint32_t be_word(const uint8_t* __restrict__ msg, size_t w) {
+    return (uint32_t)msg[4 * w] << 24 | (uint32_t)msg[4 * w + 1] << 16 | (uint32_t)msg[4 * w + 2] << 8 | msg[4 * w + 3];
+}
+__device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
+
+__global__ __launch_bounds__(THREADS) void k_keccak_calls(keccak_calls_args A) {
+    __shared__ uint64_t block[place::RATE / 8];   // the padded block being absorbed
+    __shared__ uint32_t digest[8];                // the digest's bytes as little-endian words
+    const unsigned t = threadIdx.x;
+    const size_t k = blockIdx.x;
+    const uint8_t* __restrict__ msg = A.inputs + A.off[k];
+    const size_t L = A.off[k + 1] - A.off[k], W = place::words(L), R = place::read_rows(L), B = place::blocks(L);
+    const call_base at = A.base[k];
+    const uint64_t ctx = A.meta[4 * k], seg = A.meta[4 * k + 1], addr = A.meta[4 * k + 2] & ~FLAG, ts = A.meta[4 * k + 3], S = ts / 10;
+    const uint64_t daddr = A.digest_addr[k];
+    uint64_t* __restrict__ perm_in = A.perm_in + place::STATE * at.perm;
+
+    // ---- the sponge, block by block: lane 0 holds the state
+    uint64_t st[place::STATE];
+#pragma unroll
+    for (unsigned i = 0; i < place::STATE; i++) st[i] = 0;
+    for (size_t b = 0; b < B; b++) {
+        if (t < place::RATE) ((uint8_t*)block)[t] = (uint8_t)padded_byte(msg, L, place::RATE * b + t);
+        __syncthreads();
+        if (t == 0) {
+#pragma unroll
+            for (unsigned i = 0; i < place::RATE / 8; i++) st[i] ^= block[i];
+#pragma unroll
+            for (unsigned i = 0; i < place::STATE; i++) perm_in[place::STATE * b + i] = st[i];
+            keccakf_dev(st);
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) {
+            digest[2 * i] = (uint32_t)st[i];
+            digest[2 * i + 1] = (uint32_t)(st[i] >> 32);
+        }
+    }
+    __syncthreads();
+
+    // ---- the read rows: the clock, then the six cells of every channel that reads a word (64 slots a row, 49 cells)
+    for (size_t j = t; j < R * 64; j += THREADS) {
+        const size_t r = j >> 6;
+        const unsigned cell = j & 63;
+        if (cell > 48) continue;
+        uint64_t v = place::row_clock(S, L, r);
+        if (cell) {
+            const unsigned ch = (cell - 1) / 6, f = (cell - 1) % 6;
+            if (ch >= place::read_channels(L, r)) continue;
+            const size_t w = 8 * r + ch;
+            v = chan_cell(f, true, ctx, seg, addr + 4 * w, be_word(msg, w));
+        }
+        A.rows[(at.row + r) * CPU_W + C_CLOCK + cell] = v;
+    }
+    // the sponge row: the flag, the clock, context / segment / address of the final block's first word / length in the values of
+    // channels 0-3, general.khash.value = the digest's words in reverse
+    if (t < 14) {
+        uint64_t* row = A.rows + (at.row + place::sponge_row(L)) * CPU_W;
+        const size_t fw = place::final_word(L);
+        if (t < 8) row[C_GEN + t] = bswap(digest[7 - t]);
+        else if (t == 8) row[C_IS_KECCAK_SPONGE] = 1;
+        else if (t == 9) row[C_CLOCK] = place::row_clock(S, L, place::sponge_row(L));
+        else row[C_CH0 + 6 * (t - 10) + 5] = t == 10 ? ctx : t == 11 ? seg : t == 12 ? (fw < W ? addr + 4 * fw : 0) : (uint64_t)L;
+    }
+    // the write row: eight writes of the digest's words
+    if (t >= 64 && t < 64 + 49) {
+        const unsigned cell = t - 64;
+        uint64_t v = place::row_clock(S, L, place::write_row(L));
+        if (cell) {
+            const unsigned ch = (cell - 1) / 6, f = (cell - 1) % 6;
+            v = chan_cell(f, false, ctx, seg, daddr + 4 * ch, bswap(digest[ch]));
+        }
+        A.rows[(at.row + place::write_row(L)) * CPU_W + C_CLOCK + cell] = v;
+    }
+    // the sponge's reads: one a byte, of the word that holds it (keccak_sponge_log), six words a read
+    uint64_t* __restrict__ mem = A.mem + 6 * at.mem;
+    for (size_t j = t; j < 6 * place::mem(L); j += THREADS) {
+        const size_t w = j / 24;
+        mem[j] = read_word((unsigned)(j % 6), ctx, seg, addr + 4 * w, ts, be_word(msg, w));
+    }
+    // the 34 XORs of every absorption (xor_into_sponge), three words an operation: the state before = the stored state ^ the block
+    uint32_t* __restrict__ logic = A.logic + 3 * at.logic;
+    for (size_t j = t; j < 3 * place::logic(L); j += THREADS) {
+        const size_t op = j / 3, b = op / place::RATE_U32;
+        const unsigned f = (unsigned)(j % 3), i = (unsigned)(op % place::RATE_U32);
+        uint32_t rhs = 0;
+#pragma unroll
+        for (unsigned q = 0; q < 4; q++) rhs |= padded_byte(msg, L, place::RATE * b + 4 * i + q) << (8 * q);
+        const uint32_t after = (uint32_t)(perm_in[place::STATE * b + i / 2] >> (32 * (i & 1)));
+        logic[j] = f == 0 ? OP_XOR : f == 1 ? after ^ rhs : rhs;
+    }
+    for (size_t b = t; b < B; b += THREADS) A.perm_ts[at.perm + b] = ts;
+}
+
+// ---- the host's refusals, naming the list and the call's position (they throw the bare message)
+std::string dec(uint64_t v) { return std::to_string(v); }
+std::string hex(uint64_t v) {
+    char buf[24];
+    snprintf(buf, sizeof buf, "0x%llx", (unsigned long long)v);
+    return buf;
+}
+constexpr uint64_t LIM = (uint64_t)1 << 32;
+
+// the offsets: host memory, increasing, every length a positive multiple of 4.  Returns the totals, and the sums a call if asked.
+call_base check_offsets(const uint64_t* off, size_t n, std::vector<call_base>* bases) {
+    call_base sum{0, 0, 0, 0};
+    if (n && !off) throw std::runtime_error("input_off: NULL with a count of " + dec(n));
+    if (n && zkm_is_device_ptr(off)) throw std::runtime_error("input_off: device memory (the offsets size the outputs: they must be host memory)");
+    if (bases) bases->resize(n);
+    for (size_t k = 0; k < n; k++) {
+        const std::string at = "input_off: call " + dec(k) + ": ";
+        if (off[k + 1] < off[k]) throw std::runtime_error(at + "the offsets do not increase (" + dec(off[k]) + " then " + dec(off[k + 1]) + ")");
+        const uint64_t L = off[k + 1] - off[k];
+        if (L == 0 || L % 4)
+            throw std::runtime_error(at + "length " + dec(L) + " is not a positive multiple of 4 (the other bytes of the last memory word follow from no list: "
+                                          "such a call travels as RAW rows beside a sponge operation with ZKM_SPONGE_BYTE_ADDRESSED)");
+        if (bases) (*bases)[k] = sum;
+        sum.row += place::rows(L);
+        sum.mem += place::mem(L);
+        sum.logic += place::logic(L);
+        sum.perm += place::blocks(L);
+    }
+    return sum;
+}
+
+void check_meta(const uint64_t* off, const uint64_t* meta, size_t n) {
+    if (n && !meta) throw std::runtime_error("meta: NULL with a count of " + dec(n));
+    // (a list in device memory is not read by the host: see the header)
+    for (size_t k = 0; k < n && !zkm_is_device_ptr(meta); k++) {
+        const uint64_t* m = meta + 4 * k;
+        const uint64_t L = off[k + 1] - off[k], base = m[2] & ~FLAG;
+        const std::string at = "meta: call " + dec(k) + ": ";
+        if (m[0] >= LIM) throw std::runtime_error(at + "context " + dec(m[0]) + " does not fit in 32 bits");
+        if (m[1] >= LIM) throw std::runtime_error(at + "segment " + dec(m[1]) + " does not fit in 32 bits");
+        if (!(m[2] & FLAG)) throw std::runtime_error(at + "virt_base " + hex(m[2]) + " lacks ZKM_SPONGE_BYTE_ADDRESSED (a call reads one memory word every 4 bytes)");
+        if (base >= LIM || base + (L - 4) >= LIM) throw std::runtime_error(at + "address of word 0 " + hex(base) + ": word " + dec(L / 4 - 1) + " does not fit in 32 bits");
+        if (m[3] % 10) throw std::runtime_error(at + "timestamp " + dec(m[3]) + " is not a multiple of 10 (NUM_CHANNELS)");
+        if (m[3] / 10 < place::read_rows(L)) throw std::runtime_error(at + "timestamp " + dec(m[3]) + " puts the first read row before clock 0");
+    }
+}
+
+void check_digest_addrs(const uint64_t* addrs, size_t n) {
+    if (n && !addrs) throw std::runtime_error("digest_addrs: NULL with a count of " + dec(n));
+    for (size_t k = 0; k < n && !zkm_is_device_ptr(addrs); k++)
+        if (addrs[k] >= LIM || addrs[k] + 28 >= LIM)
+            throw std::runtime_error("digest_addrs: call " + dec(k) + ": address " + hex(addrs[k]) + ": the digest's eighth word does not fit in 32 bits");
+}
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+int zkm_keccak_calls_counts(const uint64_t* input_off, size_t ncalls, size_t* cpu_rows, size_t* memory_ops, size_t* logic_ops,
+                            size_t* keccak_perms, char** err) {
+    return zkm_api("zkm_keccak_calls_counts", err, [&] {
+        call_base sum;
+        try {
+            sum = check_offsets(input_off, ncalls, nullptr);
+        } catch (const std::exception& e) {
+            throw std::runtime_error(std::string("zkm_keccak_calls_counts: ") + e.what());
+        }
+        if (cpu_rows) *cpu_rows = sum.row;
+        if (memory_ops) *memory_ops = sum.mem;
+        if (logic_ops) *logic_ops = sum.logic;
+        if (keccak_perms) *keccak_perms = sum.perm;
+    });
+}
+
+int zkm_keccak_calls_steps(const uint64_t* input_off, const uint64_t* meta, size_t ncalls, size_t raw_base, zkm_cpu_step* steps_out,
+                           uint64_t* clocks_out, char** err) {
+    return zkm_api("zkm_keccak_calls_steps", err, [&] {
+        auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_keccak_calls_steps: " + m); };
+        std::vector<call_base> bases;
+        call_base sum;
+        try {
+            sum = check_offsets(input_off, ncalls, &bases);
+            check_meta(input_off, meta, ncalls);
+        } catch (const std::exception& e) {
+            refuse(e.what());
+        }
+        if (ncalls && zkm_is_device_ptr(meta)) refuse("meta: device memory (the clocks are read on the host)");
+        if (sum.row && (!steps_out || !clocks_out)) refuse("null argument");
+        if (raw_base >= LIM || raw_base + sum.row > LIM) refuse("raw_base " + dec(raw_base) + ": a RAW index does not fit in 32 bits");
+        for (size_t k = 0; k < ncalls; k++) {
+            const uint64_t L = input_off[k + 1] - input_off[k], S = meta[4 * k + 3] / 10;
+            for (size_t j = 0; j < place::rows(L); j++) {
+                zkm_cpu_step s{};
+                s.kind = ZKM_STEP_RAW;
+                s.reads[0] = (uint32_t)(raw_base + bases[k].row + j);
+                s.reads[1] = place::row_mask(L, j);
+                steps_out[bases[k].row + j] = s;
+                clocks_out[bases[k].row + j] = place::row_clock(S, L, j);
+            }
+        }
+    });
+}
+
+int zkm_keccak_calls_witness(zkm_ctx* c, const uint8_t* inputs, const uint64_t* input_off, const uint64_t* meta, const uint64_t* digest_addrs,
+                             size_t ncalls, uint64_t* raw_rows_out_dev, uint64_t* memory_ops_out_dev, uint32_t* logic_ops_out_dev,
+                             uint64_t* keccak_inputs_out_dev, uint64_t* keccak_timestamps_out_dev, char** err) {
+    return zkm_api("zkm_keccak_calls_witness", err, [&] {
+        auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_keccak_calls_witness: " + m); };
+        // every refusal first, on the host: the lists, the outputs, then the context
+        std::vector<call_base> bases;
+        call_base sum;
+        try {
+            sum = check_offsets(input_off, ncalls, &bases);
+            check_meta(input_off, meta, ncalls);
+            check_digest_addrs(digest_addrs, ncalls);
+        } catch (const std::exception& e) {
+            refuse(e.what());
+        }
+        if (ncalls && !inputs) refuse("inputs: NULL with a count of " + dec(ncalls));
+        if (ncalls == 0) {
+            if (!c) refuse("null argument");
+            return;
+        }
+        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(sum.row) + " rows to write");
+        if (!memory_ops_out_dev) refuse("memory_ops_out_dev: NULL with " + dec(sum.mem) + " operations to write");
+        if (!logic_ops_out_dev) refuse("logic_ops_out_dev: NULL with " + dec(sum.logic) + " operations to write");
+        if (!keccak_inputs_out_dev) refuse("keccak_inputs_out_dev: NULL with " + dec(sum.perm) + " permutations to write");
+        if (!keccak_timestamps_out_dev) refuse("keccak_timestamps_out_dev: NULL with " + dec(sum.perm) + " permutations to write");
+        if (((uintptr_t)raw_rows_out_dev | (uintptr_t)memory_ops_out_dev | (uintptr_t)keccak_inputs_out_dev | (uintptr_t)keccak_timestamps_out_dev) & 7 ||
+            (uintptr_t)logic_ops_out_dev & 3)
+            refuse("an output is not aligned to its words (8 bytes; 4 for the logic operations)");
+        if (!c) refuse("null argument");
+        if (ncalls > 0x7FFFFFFF) refuse("2^31 or more calls");
+        ZKM_HIP_CHECK(hipSetDevice(c->device));
+        // the lists the host holds go up in one block, with the sums a call; the input bytes from the first call's offset on, so the
+        // offsets that go up count from there
+        const size_t first = input_off[0], nbytes = input_off[ncalls] - first;
+        const bool inputs_up = !zkm_is_device_ptr(inputs);
+        std::vector<uint64_t> off(input_off, input_off + ncalls + 1);
+        if (inputs_up)
+            for (uint64_t& o : off) o -= first;
+        const struct { const void* p; size_t bytes; bool up; } in[5] = {{inputs_up ? inputs + first : inputs, nbytes, inputs_up},
+                                                                        {off.data(), 8 * (ncalls + 1), true},
+                                                                        {meta, 32 * ncalls, !zkm_is_device_ptr(meta)},
+                                                                        {digest_addrs, 8 * ncalls, !zkm_is_device_ptr(digest_addrs)},
+                                                                        {bases.data(), sizeof(call_base) * ncalls, true}};
+        const void* dev[5];
+        size_t at[5], total = 0;
+        for (int i = 0; i < 5; i++) {
+            at[i] = total;
+            if (in[i].up) total += up256(in[i].bytes);
+        }
+        zkm_scratch block(c, total);
+        for (int i = 0; i < 5; i++) {
+            dev[i] = in[i].p;
+            if (in[i].up) {
+                dev[i] = block.as<char>() + at[i];
+                ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        ZKM_HIP_CHECK(hipMemsetAsync(raw_rows_out_dev, 0, sum.row * CPU_W * sizeof(uint64_t), c->stream));
+        const keccak_calls_args A{(const uint8_t*)dev[0], (const uint64_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const call_base*)dev[4],
+                                  raw_rows_out_dev, memory_ops_out_dev, keccak_inputs_out_dev, keccak_timestamps_out_dev, logic_ops_out_dev};
+        {
+            zkm_prof_scope ps(c, "keccak_calls/rows_lists");
+            hipLaunchKernelGGL(k_keccak_calls, dim3((unsigned)ncalls), dim3(THREADS), 0, c->stream, A);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        c->sync();   // (the block, the host vectors and the caller's lists are in use until here)
+    });
+}
+
+}  // extern "C"

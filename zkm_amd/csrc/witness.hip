@@ -22,6 +22,15 @@
 //       0.25 ms) and stores all 470 cells, zeros included -- lane = row, so every column store is one contiguous 512 B wave access
 //       and the table needs no zero-fill.  (The one-lane-per-operation form stored only the non-zero cells of a zero-filled table,
 //       4.6 rows apart per lane: 8-byte partial-line writes, 14 GB of HBM traffic for a 3.9 GB table -- profiles/r03_a_*.)
+// where word w of a sponge operation's input is read (both sponges): the meta's virt_base + w, or with ZKM_SPONGE_BYTE_ADDRESSED set in
+// it, one memory word every 4 bytes (include/zkm_hip.h, zkm_keccak_sponge_trace)
+struct sponge_virt {
+    uint64_t base, step;
+    __device__ explicit sponge_virt(uint64_t meta_word)
+        : base(meta_word & ~ZKM_SPONGE_BYTE_ADDRESSED), step(meta_word & ZKM_SPONGE_BYTE_ADDRESSED ? 4 : 1) {}
+    __device__ uint64_t of(size_t w) const { return base + step * w; }
+};
+
 // word i of the padded 136-byte block of a row (pad10*1 on the final row, :334-341)
 __device__ __forceinline__ uint64_t sponge_block_word(const uint8_t* __restrict__ msg, size_t rem, bool full, int i) {
     uint64_t w = 0;
@@ -97,11 +106,11 @@ __global__ __launch_bounds__(256) void k_keccak_sponge_rows(zkm_seg_args<zkm_wri
     o[1 * n] = meta[4 * op];
     o[2 * n] = meta[4 * op + 1];
     {
-        const uint64_t vbase = meta[4 * op + 2];
+        const sponge_virt virt(meta[4 * op + 2]);
 #pragma unroll 2
         for (size_t i = 0; i < 34; i++) {
             const size_t w = absorbed / 4 + i;
-            o[(3 + i) * n] = w < nwords ? vbase + w : 0;
+            o[(3 + i) * n] = w < nwords ? virt.of(w) : 0;
         }
     }
     o[37 * n] = meta[4 * op + 3];
@@ -328,7 +337,8 @@ __global__ __launch_bounds__(128) void k_poseidon_sponge_trace(zkm_seg_args<zkm_
     if (op >= nops) return;
     const uint8_t* msg = inputs + off[op];
     const size_t len = off[op + 1] - off[op], nwords = (len + 3) / 4;
-    const uint64_t ctxv = meta[4 * op], seg = meta[4 * op + 1], vbase = meta[4 * op + 2], ts = meta[4 * op + 3];
+    const uint64_t ctxv = meta[4 * op], seg = meta[4 * op + 1], ts = meta[4 * op + 3];
+    const sponge_virt virt(meta[4 * op + 2]);
     uint64_t st[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) st[i] = 0;
@@ -343,7 +353,7 @@ __global__ __launch_bounds__(128) void k_poseidon_sponge_trace(zkm_seg_args<zkm_
         o[2 * n] = seg;
         for (size_t i = 0; i < 8; i++) {
             size_t w = absorbed / 4 + i;
-            if (w < nwords) o[(3 + i) * n] = vbase + w;
+            if (w < nwords) o[(3 + i) * n] = virt.of(w);
         }
         o[11 * n] = ts;
         o[12 * n] = len;
