@@ -1010,6 +1010,60 @@ int zkm_keccak_calls_witness(zkm_ctx* ctx, const uint8_t* inputs, const uint64_t
                              const uint64_t* digest_addrs, size_t ncalls, uint64_t* raw_rows_out_dev, uint64_t* memory_ops_out_dev,
                              uint32_t* logic_ops_out_dev, uint64_t* keccak_inputs_out_dev, uint64_t* keccak_timestamps_out_dev, char** err);
 
+/* ------------------------------------------------------------------ the I/O syscalls' rows from their bytes
+ * What the four data-moving helpers that generate_syscall calls behind its own row (witness/operation.rs:1660-1673) push, on the device,
+ * from the bytes each moves: load_input (:1024-1067, SYSHINTREAD), commit (:1069-1099, SYSWRITE to FD_PUBLIC_VALUES), verify (:991-1022,
+ * SYSVERIFY) and load_preimage (:908-989, SYSGETPID).  A row is a CpuColumnsView::default() with clock set and, for every used channel,
+ * used = 1, is_read, the three address cells and the value (witness/util.rs:304-349); every other cell is 0.  The lists:
+ *   kinds     ncalls uint32, one of the four constants below; host memory
+ *   data_off  ncalls + 1 words: call k's bytes are data[data_off[k] .. data_off[k + 1]); host memory
+ *   data      the calls' bytes, host or device memory (may be NULL when the calls hold no byte)
+ *   meta      ncalls x 4 words {context, segment, address, timestamp}; timestamp = the first row's clock x 10 (NUM_CHANNELS), the clock
+ *             after the SYSCALL row.  Context and segment come from here (the reference hard-codes 0 and Segment::Code: for its callers
+ *             the rows are identical)
+ * What a call's L bytes are, and the rows they make (a word's value is the big-endian reading of its four bytes unless said otherwise):
+ *   HINT_READ  the input-stream vector, any L >= 0: W = ceil(L / 4) words, the last right-padded with 0.  max(1, ceil(W / 8)) rows (a call
+ *              of 0 bytes still pushes one row, with no channel used); row j, channel i WRITES word 8 j + i to address + 4 (8 j + i)
+ *   COMMIT     the W = L / 4 memory words the call reads (the reference reads whole words whatever `size` is); rows and addresses as for
+ *              the hint read, the channels READ
+ *   VERIFY     the 32 bytes of the claim digest: one row, channels 0-7 read at address + 4 i
+ *   PREIMAGE   the 32 hash bytes, then the content of C = L - 32 bytes; address must be 0x31000000.  Row 0: channels 0-7 read the hash
+ *              words at 0x30001000 + 4 i.  Then Q = 1 + ceil(C / 4) write words in ceil(Q / 8) rows, word q in row 1 + q / 8, channel
+ *              q % 8, at address + 4 q: word 0 is C, word 1 + k content word k.  A last content word of n < 4 bytes is those bytes read
+ *              little-endian, | 1 << 8 n, | 0x80 << 24 if C % 32 + 4 > 32, byte-swapped (:960-980)
+ * Rows are canonical and row-major, calls in list order; the clock of a call's row j is timestamp / 10 + j; the channel mask of a row is
+ * its used channels (always the low ones).  memory_ops counts the used channels: the operations themselves are pushed by the rows' RAW
+ * steps, as for any RAW row -- this expansion writes no operation list of its own.
+ *   zkm_io_calls_counts   the two totals (any out pointer may be NULL); pure: no context, no GPU
+ *   zkm_io_calls_steps    pure.  The cpu_rows RAW records (reads[0] = raw_base + j, reads[1] = the row's channel mask, every other field 0)
+ *                         into steps_out and the clock each belongs at into clocks_out, as zkm_keccak_calls_steps does.  THE statement of
+ *                         masks and positions: the binding, the Rust recorder and the kernel's indexing follow it.  meta is host memory
+ *                         here, and raw_base + cpu_rows must fit in 32 bits.
+ *   zkm_io_calls_witness  the kernel: one launch for all calls, the work divided by ROW (one call may be half a segment, the next one
+ *                         row): the host's walk uploads the calls' row offsets and a workgroup finds the call of each of its rows by a
+ *                         search over them.  Every word of the block is written (zeros, clocks, channel cells): nothing is zeroed in
+ *                         front.  meta may be host or device memory; raw_rows_out_dev is a plain device pointer (8-byte aligned), so it may
+ *                         aim into the middle of a larger block, cpu_rows x ZKM_CPU_COLS words.  Returns once the rows are complete: one
+ *                         host wait.  Profile scope io_calls/rows.
+ * Refused, on the host before any device work and before a missing context is reported, the message naming the list (kinds, data_off,
+ * meta, data, or the output) and the call's position: a NULL list or output with a nonzero count; kinds or data_off in device memory; an
+ * unknown kind; offsets that decrease; a verify call that is not 32 bytes; a commit length that is not a multiple of 4; a preimage
+ * shorter than 32 bytes or with another address; an address that is not 4-aligned; a last word whose address does not fit in 32 bits; a
+ * context or segment of 2^32 or more; a timestamp that is not a multiple of 10; raw_base + cpu_rows that does not fit in 32 bits; a
+ * misaligned output.  A refusal leaves the context usable.  A meta in DEVICE memory is not read by the host and so not held to these
+ * rules (no store's address depends on it).
+ * Out of scope: the SYSCALL row in front of a call stays whatever the caller logs today; commit and verify READ memory, so the caller
+ * supplies the words; nothing is staged, the pool takes none, and nothing is fused into the segment builder. */
+#define ZKM_IO_HINT_READ 0
+#define ZKM_IO_COMMIT 1
+#define ZKM_IO_VERIFY 2
+#define ZKM_IO_PREIMAGE 3
+int zkm_io_calls_counts(const uint32_t* kinds, const uint64_t* data_off, size_t ncalls, size_t* cpu_rows, size_t* memory_ops, char** err);
+int zkm_io_calls_steps(const uint32_t* kinds, const uint64_t* data_off, const uint64_t* meta, size_t ncalls, size_t raw_base,
+                       zkm_cpu_step* steps_out, uint64_t* clocks_out, char** err);
+int zkm_io_calls_witness(zkm_ctx* ctx, const uint32_t* kinds, const uint8_t* data, const uint64_t* data_off, const uint64_t* meta,
+                         size_t ncalls, uint64_t* raw_rows_out_dev, char** err);
+
 /* ------------------------------------------------------------------ a memory image's hash pages, root and image id
  * What the emulator does at every segment split -- Memory::update_page_hash and Memory::compute_image_id (emulator/src/memory.rs:388-471,
  * with poseidon / hash_page / CONST_HASH_PAGES, :43-118, and alloc_hash_page, :378-386; called from split_segment, state.rs:1477-1530) --

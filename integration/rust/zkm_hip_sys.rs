@@ -149,6 +149,8 @@ pub const ZKM_SYSCALL_READ: u32 = 5; pub const ZKM_SYSCALL_WRITE: u32 = 6; pub c
 pub const ZKM_SYSCALL_SET_THREAD_AREA: u32 = 8;
 // a sponge operation's meta word 2 (virt_base) with this bit set: word w of the input is read at (virt_base & !bit) + 4 w
 pub const ZKM_SPONGE_BYTE_ADDRESSED: u64 = 0x8000000000000000;
+// the kinds of zkm_io_calls_*: the data-moving helper behind generate_syscall's row (load_input, commit, verify, load_preimage)
+pub const ZKM_IO_HINT_READ: u32 = 0; pub const ZKM_IO_COMMIT: u32 = 1; pub const ZKM_IO_VERIFY: u32 = 2; pub const ZKM_IO_PREIMAGE: u32 = 3;
 pub const ZKM_VERIFY_OK: u32 = 0; pub const ZKM_VERIFY_SHAPE: u32 = 1; pub const ZKM_VERIFY_TRANSCRIPT_STATE: u32 = 2;
 pub const ZKM_VERIFY_CTL_CHALLENGES: u32 = 3; pub const ZKM_VERIFY_QUOTIENT: u32 = 4; pub const ZKM_VERIFY_POW: u32 = 5;
 pub const ZKM_VERIFY_INITIAL_MERKLE: u32 = 6; pub const ZKM_VERIFY_FRI_EVAL: u32 = 7; pub const ZKM_VERIFY_FRI_MERKLE: u32 = 8;
@@ -353,6 +355,13 @@ extern "C" {
     pub fn zkm_keccak_calls_witness(ctx: *mut zkm_ctx, inputs: *const u8, input_off: *const u64, meta: *const u64, digest_addrs: *const u64,
                                     ncalls: usize, raw_rows_out_dev: *mut u64, memory_ops_out_dev: *mut u64, logic_ops_out_dev: *mut u32,
                                     keccak_inputs_out_dev: *mut u64, keccak_timestamps_out_dev: *mut u64, err: *mut *mut c_char) -> c_int;
+    // the I/O syscalls' rows (hint read, commit, verify, preimage) expanded on the device from the bytes each call moves
+    pub fn zkm_io_calls_counts(kinds: *const u32, data_off: *const u64, ncalls: usize, cpu_rows: *mut usize, memory_ops: *mut usize,
+                               err: *mut *mut c_char) -> c_int;
+    pub fn zkm_io_calls_steps(kinds: *const u32, data_off: *const u64, meta: *const u64, ncalls: usize, raw_base: usize,
+                              steps_out: *mut zkm_cpu_step, clocks_out: *mut u64, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_io_calls_witness(ctx: *mut zkm_ctx, kinds: *const u32, data: *const u8, data_off: *const u64, meta: *const u64, ncalls: usize,
+                                raw_rows_out_dev: *mut u64, err: *mut *mut c_char) -> c_int;
     // what the emulator hashes between two segments: hash pages, root and image id of a memory image
     pub fn zkm_image_hash_plan(dirty_index: *const u32, ndirty: usize, hash_index_out: *mut u32, capacity: usize) -> usize;
     pub fn zkm_image_hash(ctx: *mut zkm_ctx, r#in: *const zkm_image_pages, hash_words_out: *mut u32, page_hash_root_out: *mut u8,

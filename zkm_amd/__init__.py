@@ -216,6 +216,47 @@ def keccak_calls_steps(input_off, meta, raw_base=0):
 
 
 SPONGE_BYTE_ADDRESSED = _H["SPONGE_BYTE_ADDRESSED"]
+# the kinds of the I/O calls (ZKM_IO_*): hint_read, commit, verify, preimage
+IO_KINDS = {n.lower(): v for n, v in abi.constants("ZKM_IO_").items()}
+
+
+def _io_lists(io):
+    """(kinds u32 n, data u8 or device memory, data_off n + 1, meta n x 4 or device memory) with the host lists as contiguous numpy
+    arrays, and the number of calls; None, 0 without calls."""
+    if io is None:
+        return None, 0
+    kinds, data, off, meta = io
+    host = lambda x, dt: np.ascontiguousarray(x if x is not None else [], dtype=dt) if not isinstance(x, DeviceBuffer) else x
+    k = (np.ascontiguousarray(kinds, dtype=np.uint32).reshape(-1), host(data, np.uint8), np.ascontiguousarray(off, dtype=np.uint64).reshape(-1),
+         _sha_meta(meta, 4) if not isinstance(meta, DeviceBuffer) else meta)
+    n = k[0].size
+    assert k[2].size == n + 1 and (isinstance(k[3], DeviceBuffer) or len(k[3]) == n), "one kind and one meta per call, and one offset more"
+    return (k if n else None), n
+
+
+def io_calls_counts(kinds, data_off):
+    """zkm_io_calls_counts: (cpu_rows, memory_ops) that the I/O calls of these kinds (IO_KINDS) with these ncalls + 1 offsets expand
+    into; needs no GPU.  An unknown kind or a length the kind does not take raises ZkmError naming the list and the call."""
+    kd, off = np.ascontiguousarray(kinds, dtype=np.uint32).reshape(-1), np.ascontiguousarray(data_off, dtype=np.uint64).reshape(-1)
+    assert off.size == kd.size + 1 or kd.size == 0, "one offset more than calls"
+    out, err = [C.c_size_t() for _ in range(2)], C.c_char_p()
+    _check(load().zkm_io_calls_counts(kd.ctypes.data if kd.size else None, off.ctypes.data if kd.size else None, kd.size,
+                                      *[C.byref(x) for x in out], C.byref(err)), err)
+    return tuple(int(x.value) for x in out)
+
+
+def io_calls_steps(kinds, data_off, meta, raw_base=0):
+    """zkm_io_calls_steps: the RAW step records (a CPU_STEP_DT array) of the calls' rows and the clock each belongs at (uint64); needs no
+    GPU.  kinds ncalls, data_off ncalls + 1, meta ncalls x 4 uint64 (context, segment, address, the first row's timestamp).  Every refusal
+    raises ZkmError naming the list and the call."""
+    kd, off, m = np.ascontiguousarray(kinds, dtype=np.uint32).reshape(-1), np.ascontiguousarray(data_off, dtype=np.uint64).reshape(-1), _sha_meta(meta, 4)
+    n = kd.size
+    assert off.size == n + 1 and len(m) == n, "one meta per call, and one offset more"
+    rows = io_calls_counts(kd, off)[0]
+    steps, clocks, err = np.zeros(rows, dtype=CPU_STEP_DT), np.zeros(rows, dtype=np.uint64), C.c_char_p()
+    _check(load().zkm_io_calls_steps(kd.ctypes.data if n else None, off.ctypes.data if n else None, m.ctypes.data if n else None, n, raw_base,
+                                     steps.ctypes.data if rows else None, clocks.ctypes.data if rows else None, C.byref(err)), err)
+    return steps, clocks
 
 
 class CtlLocation(C.Structure):
@@ -1419,20 +1460,43 @@ class Context:
             for b in bufs:
                 b.free()
 
+    # ---- the I/O syscalls' rows expanded on the device (include/zkm_hip.h "the I/O syscalls' rows from their bytes")
+    def io_calls_witness_into(self, io, ncalls, raw_rows):
+        """zkm_io_calls_witness as it is: io = (kinds, data, data_off, meta), kinds and data_off numpy arrays, data and meta numpy arrays
+        of the right dtype or device memory (or None with a count of 0); raw_rows is a device address (an integer) or None."""
+        ptr = lambda x: None if x is None else x.ctypes.data if isinstance(x, np.ndarray) else _data_ptr(x).value
+        lists = [ptr(x) for x in tuple(io or (None,) * 4)]
+        err = C.c_char_p()
+        _check(self.L.zkm_io_calls_witness(self.h, *lists, ncalls, raw_rows, C.byref(err)), err)
+
+    def io_calls_witness(self, kinds, data, data_off, meta):
+        """zkm_io_calls_witness into a buffer of its own.  Returns numpy raw_rows n x 259 uint64."""
+        k, n = _io_lists((kinds, data, data_off, meta))
+        rows = io_calls_counts(k[0], k[2])[0] if n else 0
+        buf = self.alloc(max(rows * 259, 1))
+        try:
+            self.io_calls_witness_into(k, n, buf.ptr)
+            return buf.download()[:rows * 259].reshape(rows, 259)
+        finally:
+            buf.free()
+
     def calls_expand(self, steps, first_clock=0, extend=None, compress=None, keccak=None, memory_ops=None, logic_ops=None, keccak_perms=None,
-                     **groups):
-        """A segment with precompile calls made ready for segments_tables_steps / prove_segments_ops_steps.  steps: a CpuSteps with the
-        segment's own RAW rows (host memory) whose list holds a placeholder at the position of every row of a call (sha_calls_steps and
-        keccak_calls_steps say which: clock - first_clock); extend = (w16, meta), compress = (hx, w, meta), keccak = (inputs, input_off,
-        meta, digest_addrs): the calls; memory_ops / logic_ops / keccak_perms = (inputs, timestamps): the segment's own operations;
-        groups: the other groups of SegmentOps, passed on.  Returns (CpuSteps, SegmentOps): the steps with the calls' RAW records in place
-        and raw_rows a DeviceBuffer of own rows, then the SHA calls', then the Keccak calls'; the operations with memory_ops, logic_ops,
-        sha_extend and keccak in device memory (own items in front, the generated ones behind in the same order) and the sponge groups
-        set from the calls.  Free with ops.free() and steps.raw_rows.free()."""
+                     io=None, **groups):
+        """A segment with precompile and I/O calls made ready for segments_tables_steps / prove_segments_ops_steps.  steps: a CpuSteps with
+        the segment's own RAW rows (host memory) whose list holds a placeholder at the position of every row of a call (sha_calls_steps,
+        keccak_calls_steps and io_calls_steps say which: clock - first_clock); extend = (w16, meta), compress = (hx, w, meta), keccak =
+        (inputs, input_off, meta, digest_addrs), io = (kinds, data, data_off, meta): the calls; memory_ops / logic_ops / keccak_perms =
+        (inputs, timestamps): the segment's own operations; groups: the other groups of SegmentOps, passed on.  Returns (CpuSteps,
+        SegmentOps): the steps with the calls' RAW records in place and raw_rows a DeviceBuffer of own rows, then the SHA calls', then the
+        Keccak calls', then the I/O calls'; the operations with memory_ops, logic_ops, sha_extend and keccak in device memory (own items
+        in front, the generated ones behind in the same order) and the sponge groups set from the calls.  Free with ops.free() and
+        steps.raw_rows.free()."""
         e, c, ne, nc = self._sha_lists(extend, compress)
         k, nk = self._keccak_lists(keccak)
+        i, ni = _io_lists(io)
         rows, mem, logic, ext = sha_calls_counts(ne, nc)
         krows, kmem, klogic, kperms = keccak_calls_counts(k[1]) if nk else (0, 0, 0, 0)
+        irows = io_calls_counts(i[0], i[2])[0] if ni else 0
         assert not isinstance(steps.raw_rows, DeviceBuffer) and not {"sha_extend", "keccak_sponge"} & set(groups)
         own_raw = steps.raw_rows.reshape(-1)
         own_mem = np.ascontiguousarray(memory_ops if memory_ops is not None else [], dtype=np.uint64).reshape(-1)
@@ -1443,15 +1507,22 @@ class Context:
         if nk:
             krecords, kclocks = keccak_calls_steps(k[1], k[2], raw_base=steps.nraw + rows)
             records, clocks = (np.concatenate([records, krecords]), np.concatenate([clocks, kclocks])) if rows else (krecords, kclocks)
+        if ni:
+            assert not isinstance(i[3], DeviceBuffer), "the records' clocks are read on the host: meta in host memory"
+            irecords, iclocks = io_calls_steps(i[0], i[2], i[3], raw_base=steps.nraw + rows + krows)
+            records, clocks = (np.concatenate([records, irecords]), np.concatenate([clocks, iclocks])) if rows + krows else (irecords, iclocks)
         at = clocks.astype(np.int64) - first_clock
         taken = np.zeros(steps.steps.size, dtype=bool)
         if at.size and at.min() >= 0 and at.max() < taken.size:
             taken[at] = True
         assert np.count_nonzero(taken) == at.size, "a call's rows lie outside the step list, or two rows share a clock"
         patched = steps.steps.copy()
-        patched[at] = records
+        if at.size and at[-1] - at[0] + 1 == at.size and (np.diff(at) == 1).all():
+            patched[at[0]:at[0] + at.size] = records          # one run of clocks (one long call): a plain copy
+        else:
+            patched[at] = records
         # one device block a list: own items in front, the generated ones behind
-        sizes = (own_raw.size + (rows + krows) * 259, own_mem.size + (mem + kmem) * 6, (own_logic.size + (logic + klogic) * 3 + 1) // 2, ext * 2, ext,
+        sizes = (own_raw.size + (rows + krows + irows) * 259, own_mem.size + (mem + kmem) * 6, (own_logic.size + (logic + klogic) * 3 + 1) // 2, ext * 2, ext,
                  own_perms[0].size + kperms * 25, own_perms[1].size + kperms)
         bufs = [self.alloc(n) if n else None for n in sizes]
         try:
@@ -1465,6 +1536,8 @@ class Context:
                 self.keccak_calls_witness_into(k, nk, bufs[0].ptr + 8 * (own_raw.size + rows * 259), bufs[1].ptr + 8 * (own_mem.size + mem * 6),
                                                bufs[2].ptr + 4 * (own_logic.size + logic * 3), bufs[5].ptr + 8 * own_perms[0].size,
                                                bufs[6].ptr + 8 * own_perms[1].size)
+            if ni:
+                self.io_calls_witness_into(i, ni, bufs[0].ptr + 8 * (own_raw.size + (rows + krows) * 259))
         except Exception:
             for b in bufs:
                 if b is not None:
@@ -1474,7 +1547,7 @@ class Context:
                          sha_compress_sponge=c, keccak=(bufs[5], bufs[6]) if bufs[5] is not None else None, keccak_sponge=k[:3] if nk else None,
                          **groups)
         ops.counts["nlogic"] = own_logic.size // 3 + logic + klogic     # (a DeviceBuffer is counted in whole words)
-        return CpuSteps(patched, bufs[0] if bufs[0] is not None else None, nraw=steps.nraw + rows + krows), ops
+        return CpuSteps(patched, bufs[0] if bufs[0] is not None else None, nraw=steps.nraw + rows + krows + irows), ops
 
     def stage_segment_ops(self, ops):
         """zkm_segment_ops_stage: queue the upload of a segment's lists behind the context's current work and return at once.  The

@@ -1,0 +1,318 @@
+// io_calls.hip -- the rows of a segment's I/O syscalls expanded on the device from the bytes each call moves (include/zkm_hip.h "the I/O
+// syscalls' rows from their bytes"): what the four data-moving helpers behind generate_syscall's own row push -- load_input
+// (witness/operation.rs:1024-1067), commit (:1069-1099), verify (:991-1022) and load_preimage (:908-989) -- as ready-made rows for RAW
+// steps.  A row holds its clock and up to eight channels of six cells; every cell is a function of the call's bytes, address and clock.
+//
+// Where a call's rows go and what each channel holds is stated once, in `place` below: zkm_io_calls_counts, zkm_io_calls_steps (masks,
+// clocks, RAW indices) and the kernel all read it.  A call's length varies (one call may be half a segment, the next one row), so the work
+// is divided by ROW: the host's walk computes the calls' row offsets and uploads them, and a workgroup finds the call of each of its rows
+// by a search over them.
+//
+// k_io_calls: ONE launch, a workgroup of 256 threads for ROWS_PER_WG consecutive rows.  The first ROWS_PER_WG lanes search the row
+// offsets and put what their row needs (the call's kind, bytes, meta; the row's position, clock and channel count) into LDS.  Then all
+// lanes walk the workgroup's span of the row-major block word by word, adjacent lanes on adjacent words with 8-byte stores: zeros, the
+// clock, and the channel cells computed in place.  Every word is written, so no zero-fill pass comes in front; the kernel is write-only
+// but for the calls' bytes, and its floor is the 2,072 bytes a row it has to write.
+#include <vector>
+
+#include "cpu_steps_dev.h"
+#include "zkm_internal.h"
+
+namespace {
+
+using zkm_step::C_CH0;
+using zkm_step::C_CLOCK;
+constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256, ROWS_PER_WG = 8;
+static_assert(C_CLOCK + 1 == C_CH0 && C_CH0 + 48 <= CPU_W, "a row's clock and its 48 channel cells are 49 contiguous words");
+
+// ---- the one statement of where things go, for a call of kind `kind` with L bytes (the host has refused the lengths a kind does not take)
+namespace place {
+constexpr uint32_t NKINDS = 4;
+constexpr uint64_t PREIMAGE_HASH = 0x30001000, PREIMAGE_MAP = 0x31000000;   // load_preimage's two addresses
+constexpr unsigned POSEIDON_RATE_BYTES = 32;
+GL_HD size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
+// the words a call moves through channels beyond its first row's fixed part: hint read / commit W, verify 8, preimage Q = 1 + ceil(C / 4)
+GL_HD size_t words(uint32_t kind, size_t L) {
+    return kind == ZKM_IO_HINT_READ ? ceil_div(L, 4) : kind == ZKM_IO_COMMIT ? L / 4 : kind == ZKM_IO_VERIFY ? 8 : 1 + ceil_div(L - 32, 4);
+}
+// a preimage call's hash row stands in front of its write rows
+GL_HD size_t lead_rows(uint32_t kind) { return kind == ZKM_IO_PREIMAGE ? 1 : 0; }
+// what a call adds: rows (a hint read or commit of no word still pushes one row) and used channels
+GL_HD size_t rows(uint32_t kind, size_t L) {
+    const size_t r = ceil_div(words(kind, L), 8);
+    return lead_rows(kind) + (r ? r : 1);
+}
+GL_HD size_t mem(uint32_t kind, size_t L) { return 8 * lead_rows(kind) + words(kind, L); }
+GL_HD uint64_t row_clock(uint64_t timestamp, size_t j) { return timestamp / 10 + j; }
+// the used channels of a call's row j: always the low ones
+GL_HD unsigned channels(uint32_t kind, size_t L, size_t j) {
+    if (j < lead_rows(kind)) return 8;
+    const size_t left = words(kind, L) - 8 * (j - lead_rows(kind));
+    return left < 8 ? (unsigned)left : 8;
+}
+GL_HD uint32_t row_mask(uint32_t kind, size_t L, size_t j) { return (1u << channels(kind, L, j)) - 1; }
+// the address of the last word a call touches, given its meta's address (the hash row's are constants)
+GL_HD uint64_t last_address(uint32_t kind, size_t L, uint64_t address) {
+    const size_t w = words(kind, L);
+    return address + 4 * (w ? w - 1 : 0);
+}
+}  // namespace place
+
+struct io_calls_args {
+    const uint32_t* kinds;      // ncalls
+    const uint8_t* data;
+    const uint64_t* off;        // ncalls + 1
+    const uint64_t* meta;       // ncalls x 4 {context, segment, address, timestamp of the first row}
+    const uint64_t* row_off;    // ncalls + 1: where a call's rows start; strictly increasing (every call has a row)
+    uint64_t* rows;
+    uint64_t nrows;
+    uint32_t ncalls;
+};
+
+// what a row needs of its call
+struct row_info {
+    const uint8_t* bytes;       // the call's bytes
+    uint64_t L, ctx, seg, address, clock, j;
+    uint32_t kind, channels;
+};
+
+// byte p of a call, 0 behind its end
+__device__ __forceinline__ uint32_t byte_or_0(const uint8_t* __restrict__ b, uint64_t L, uint64_t p) { return p < L ? b[p] : 0u; }
+// memory word w of the bytes from `at` on as the CPU holds it: the big-endian reading of its four bytes, right-padded with 0
+__device__ __forceinline__ uint32_t be_word(const uint8_t* __restrict__ b, uint64_t L, uint64_t at) {
+    return byte_or_0(b, L, at) << 24 | byte_or_0(b, L, at + 1) << 16 | byte_or_0(b, L, at + 2) << 8 | byte_or_0(b, L, at + 3);
+}
+// write word q of a preimage call: the content's length, then the content's words; a last word of n < 4 bytes as load_preimage builds it
+// (:960-980): the bytes little-endian, | 1 << 8 n, | 0x80 << 24 if C % 32 + 4 > 32, byte-swapped -- which is the big-endian reading of the
+// zero-padded bytes with 0x01 in byte n and 0x80 in byte 3
+__device__ __forceinline__ uint32_t preimage_word(const uint8_t* __restrict__ b, uint64_t L, uint64_t q) {
+    const uint64_t C = L - 32;
+    if (q == 0) return (uint32_t)C;
+    const uint64_t at = 4 * (q - 1), n = C - at;
+    uint32_t v = be_word(b, L, 32 + at);
+    if (n < 4) v |= (1u << (8 * (3 - n))) | (C % place::POSEIDON_RATE_BYTES + 4 > place::POSEIDON_RATE_BYTES ? 0x80u : 0u);
+    return v;
+}
+
+// cell f of channel i of a row (cpu/columns/mod.rs MemoryChannelView: used, is_read, addr_context, addr_segment, addr_virtual, value)
+__device__ __forceinline__ uint64_t chan_cell(const row_info& r, unsigned i, unsigned f) {
+    if (f == 0) return 1;
+    if (f == 2) return r.ctx;
+    if (f == 3) return r.seg;
+    const bool hash_row = r.kind == ZKM_IO_PREIMAGE && r.j == 0;
+    if (f == 1) return r.kind != ZKM_IO_HINT_READ && (r.kind != ZKM_IO_PREIMAGE || hash_row);
+    const uint64_t w = 8 * (r.j - place::lead_rows(r.kind)) + i;                  // the word among the call's (the hash row: i itself)
+    if (f == 4) return hash_row ? place::PREIMAGE_HASH + 4 * i : r.address + 4 * w;
+    if (r.kind == ZKM_IO_PREIMAGE) return hash_row ? be_word(r.bytes, r.L, 4 * i) : preimage_word(r.bytes, r.L, w);
+    return be_word(r.bytes, r.L, 4 * w);
+}
+
+__global__ __launch_bounds__(THREADS) void k_io_calls(io_calls_args A) {
+    __shared__ row_info info[ROWS_PER_WG];
+    const unsigned t = threadIdx.x;
+    const uint64_t row0 = (uint64_t)blockIdx.x * ROWS_PER_WG;
+    const unsigned nrows = A.nrows - row0 < ROWS_PER_WG ? (unsigned)(A.nrows - row0) : ROWS_PER_WG;
+    if (t < nrows) {
+        // the call k with row_off[k] <= row < row_off[k + 1]
+        const uint64_t row = row0 + t;
+        uint32_t lo = 0, hi = A.ncalls;   // the answer lies in [lo, hi)
+        while (hi - lo > 1) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (A.row_off[mid] <= row) lo = mid;
+            else hi = mid;
+        }
+        const uint32_t k = lo;
+        row_info r;
+        r.kind = A.kinds[k];
+        r.bytes = A.data + A.off[k];
+        r.L = A.off[k + 1] - A.off[k];
+        r.ctx = A.meta[4 * k];
+        r.seg = A.meta[4 * k + 1];
+        r.address = A.meta[4 * k + 2];
+        r.j = row - A.row_off[k];
+        r.clock = place::row_clock(A.meta[4 * k + 3], r.j);
+        r.channels = place::channels(r.kind, r.L, r.j);
+        info[t] = r;
+    }
+    __syncthreads();
+    // the workgroup's span of the block, word by word: adjacent lanes store adjacent words
+    uint64_t* __restrict__ out = A.rows + row0 * CPU_W;
+    for (unsigned w = t; w < nrows * CPU_W; w += THREADS) {
+        const unsigned r = w / CPU_W, col = w % CPU_W;
+        uint64_t v = 0;
+        if (col == C_CLOCK) v = info[r].clock;
+        else if (col >= C_CH0 && col < C_CH0 + 48) {
+            const unsigned ch = (col - C_CH0) / 6, f = (col - C_CH0) % 6;
+            if (ch < info[r].channels) v = chan_cell(info[r], ch, f);
+        }
+        out[w] = v;
+    }
+}
+
+// ---- the host's refusals, naming the list and the call's position (they throw the bare message)
+std::string dec(uint64_t v) { return std::to_string(v); }
+std::string hex(uint64_t v) {
+    char buf[24];
+    snprintf(buf, sizeof buf, "0x%llx", (unsigned long long)v);
+    return buf;
+}
+constexpr uint64_t LIM = (uint64_t)1 << 32;
+const char* const KIND_NAME[place::NKINDS] = {"hint read", "commit", "verify", "preimage"};
+
+struct totals { uint64_t rows, mem; };
+
+// kinds and offsets: host memory, known kinds, offsets that do not decrease, the lengths each kind takes.  Returns the totals, and where
+// each call's rows start (ncalls + 1 entries) if asked.
+totals check_calls(const uint32_t* kinds, const uint64_t* off, size_t n, std::vector<uint64_t>* row_off) {
+    totals sum{0, 0};
+    if (n && !kinds) throw std::runtime_error("kinds: NULL with a count of " + dec(n));
+    if (n && !off) throw std::runtime_error("data_off: NULL with a count of " + dec(n));
+    if (n && zkm_is_device_ptr(kinds)) throw std::runtime_error("kinds: device memory (the kinds size the output: they must be host memory)");
+    if (n && zkm_is_device_ptr(off)) throw std::runtime_error("data_off: device memory (the offsets size the output: they must be host memory)");
+    if (row_off) row_off->assign(n + 1, 0);
+    for (size_t k = 0; k < n; k++) {
+        if (kinds[k] >= place::NKINDS)
+            throw std::runtime_error("kinds: call " + dec(k) + ": unknown kind " + dec(kinds[k]) + " (ZKM_IO_HINT_READ, _COMMIT, _VERIFY and _PREIMAGE are 0 to 3)");
+        const std::string at = "data_off: call " + dec(k) + ": ";
+        if (off[k + 1] < off[k]) throw std::runtime_error(at + "the offsets decrease (" + dec(off[k]) + " then " + dec(off[k + 1]) + ")");
+        const uint64_t L = off[k + 1] - off[k];
+        if (kinds[k] == ZKM_IO_VERIFY && L != 32) throw std::runtime_error(at + "a verify call of " + dec(L) + " bytes (the claim digest is 32)");
+        if (kinds[k] == ZKM_IO_COMMIT && L % 4)
+            throw std::runtime_error(at + "a commit call of " + dec(L) + " bytes is not a multiple of 4 (the call reads whole memory words: hand over the words)");
+        if (kinds[k] == ZKM_IO_PREIMAGE && L < 32) throw std::runtime_error(at + "a preimage call of " + dec(L) + " bytes is shorter than its 32 hash bytes");
+        sum.rows += place::rows(kinds[k], L);
+        sum.mem += place::mem(kinds[k], L);
+        if (row_off) (*row_off)[k + 1] = sum.rows;
+    }
+    return sum;
+}
+
+void check_meta(const uint32_t* kinds, const uint64_t* off, const uint64_t* meta, size_t n) {
+    if (n && !meta) throw std::runtime_error("meta: NULL with a count of " + dec(n));
+    // (a list in device memory is not read by the host: see the header)
+    for (size_t k = 0; k < n && !zkm_is_device_ptr(meta); k++) {
+        const uint64_t* m = meta + 4 * k;
+        const uint64_t L = off[k + 1] - off[k];
+        const std::string at = "meta: call " + dec(k) + ": ";
+        if (m[0] >= LIM) throw std::runtime_error(at + "context " + dec(m[0]) + " does not fit in 32 bits");
+        if (m[1] >= LIM) throw std::runtime_error(at + "segment " + dec(m[1]) + " does not fit in 32 bits");
+        if (kinds[k] == ZKM_IO_PREIMAGE && m[2] != place::PREIMAGE_MAP)
+            throw std::runtime_error(at + "address " + hex(m[2]) + " of a preimage call is not 0x31000000");
+        if (m[2] % 4) throw std::runtime_error(at + "address " + hex(m[2]) + " is not aligned to 4 bytes");
+        if (m[2] >= LIM || place::last_address(kinds[k], L, m[2]) >= LIM)
+            throw std::runtime_error(at + "address " + hex(m[2]) + ": the last word of the " + KIND_NAME[kinds[k]] + " (" + dec(place::words(kinds[k], L)) +
+                                     " words) does not fit in 32 bits");
+        if (m[3] % 10) throw std::runtime_error(at + "timestamp " + dec(m[3]) + " is not a multiple of 10 (NUM_CHANNELS)");
+    }
+}
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+extern "C" {
+
+int zkm_io_calls_counts(const uint32_t* kinds, const uint64_t* data_off, size_t ncalls, size_t* cpu_rows, size_t* memory_ops, char** err) {
+    return zkm_api("zkm_io_calls_counts", err, [&] {
+        totals sum;
+        try {
+            sum = check_calls(kinds, data_off, ncalls, nullptr);
+        } catch (const std::exception& e) {
+            throw std::runtime_error(std::string("zkm_io_calls_counts: ") + e.what());
+        }
+        if (cpu_rows) *cpu_rows = sum.rows;
+        if (memory_ops) *memory_ops = sum.mem;
+    });
+}
+
+int zkm_io_calls_steps(const uint32_t* kinds, const uint64_t* data_off, const uint64_t* meta, size_t ncalls, size_t raw_base,
+                       zkm_cpu_step* steps_out, uint64_t* clocks_out, char** err) {
+    return zkm_api("zkm_io_calls_steps", err, [&] {
+        auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_io_calls_steps: " + m); };
+        std::vector<uint64_t> row_off;
+        totals sum;
+        try {
+            sum = check_calls(kinds, data_off, ncalls, &row_off);
+            check_meta(kinds, data_off, meta, ncalls);
+        } catch (const std::exception& e) {
+            refuse(e.what());
+        }
+        if (ncalls && zkm_is_device_ptr(meta)) refuse("meta: device memory (the clocks are read on the host)");
+        if (sum.rows && (!steps_out || !clocks_out)) refuse("null argument");
+        if (raw_base >= LIM || raw_base + sum.rows > LIM) refuse("raw_base " + dec(raw_base) + ": a RAW index does not fit in 32 bits");
+        for (size_t k = 0; k < ncalls; k++) {
+            const uint64_t L = data_off[k + 1] - data_off[k];
+            for (size_t j = 0; j < place::rows(kinds[k], L); j++) {
+                zkm_cpu_step s{};
+                s.kind = ZKM_STEP_RAW;
+                s.reads[0] = (uint32_t)(raw_base + row_off[k] + j);
+                s.reads[1] = place::row_mask(kinds[k], L, j);
+                steps_out[row_off[k] + j] = s;
+                clocks_out[row_off[k] + j] = place::row_clock(meta[4 * k + 3], j);
+            }
+        }
+    });
+}
+
+int zkm_io_calls_witness(zkm_ctx* c, const uint32_t* kinds, const uint8_t* data, const uint64_t* data_off, const uint64_t* meta, size_t ncalls,
+                         uint64_t* raw_rows_out_dev, char** err) {
+    return zkm_api("zkm_io_calls_witness", err, [&] {
+        auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_io_calls_witness: " + m); };
+        // every refusal first, on the host: the lists, the output, then the context
+        std::vector<uint64_t> row_off;
+        totals sum;
+        try {
+            sum = check_calls(kinds, data_off, ncalls, &row_off);
+            check_meta(kinds, data_off, meta, ncalls);
+        } catch (const std::exception& e) {
+            refuse(e.what());
+        }
+        if (ncalls == 0) {
+            if (!c) refuse("null argument");
+            return;
+        }
+        const size_t first = data_off[0], nbytes = data_off[ncalls] - first;
+        if (nbytes && !data) refuse("data: NULL with " + dec(nbytes) + " bytes to read");
+        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(sum.rows) + " rows to write");
+        if ((uintptr_t)raw_rows_out_dev & 7) refuse("raw_rows_out_dev is not aligned to its words (8 bytes)");
+        if (sum.rows > LIM) refuse(dec(sum.rows) + " rows: a RAW index does not fit in 32 bits");
+        if (ncalls > 0x7FFFFFFF) refuse("2^31 or more calls");
+        if (!c) refuse("null argument");
+        ZKM_HIP_CHECK(hipSetDevice(c->device));
+        // the lists the host holds go up in one block, with the row offsets; the bytes from the first call's offset on, so the offsets
+        // that go up count from there
+        const bool data_up = !zkm_is_device_ptr(data);
+        std::vector<uint64_t> off(data_off, data_off + ncalls + 1);
+        if (data_up)
+            for (uint64_t& o : off) o -= first;
+        const struct { const void* p; size_t bytes; bool up; } in[5] = {{kinds, 4 * ncalls, true},
+                                                                        {data_up && data ? data + first : data, nbytes, data_up},
+                                                                        {off.data(), 8 * (ncalls + 1), true},
+                                                                        {meta, 32 * ncalls, !zkm_is_device_ptr(meta)},
+                                                                        {row_off.data(), 8 * (ncalls + 1), true}};
+        const void* dev[5];
+        size_t at[5], total = 0;
+        for (int i = 0; i < 5; i++) {
+            at[i] = total;
+            if (in[i].up) total += up256(in[i].bytes);
+        }
+        zkm_scratch block(c, total);
+        for (int i = 0; i < 5; i++) {
+            dev[i] = in[i].p;
+            if (in[i].up) {
+                dev[i] = block.as<char>() + at[i];
+                if (in[i].bytes) ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        const io_calls_args A{(const uint32_t*)dev[0], (const uint8_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const uint64_t*)dev[4],
+                              raw_rows_out_dev, sum.rows, (uint32_t)ncalls};
+        {
+            zkm_prof_scope ps(c, "io_calls/rows");
+            hipLaunchKernelGGL(k_io_calls, dim3((unsigned)((sum.rows + ROWS_PER_WG - 1) / ROWS_PER_WG)), dim3(THREADS), 0, c->stream, A);
+            ZKM_HIP_CHECK(hipGetLastError());
+        }
+        c->sync();   // (the block, the host vectors and the caller's lists are in use until here)
+    });
+}
+
+}  // extern "C"
