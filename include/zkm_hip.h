@@ -1211,6 +1211,31 @@ int zkm_quotient(zkm_ctx* ctx, int table_id, const zkm_batch* trace, const zkm_b
 int zkm_check_constraints(zkm_ctx* ctx, int table_id, const zkm_stark_config* cfg, const uint64_t* trace, size_t ncols, unsigned log_n,
                           const uint64_t* aux, size_t naux, const zkm_ctl_table* table, const zkm_ctl_z* zs, const uint32_t* colset_ids, size_t nzs,
                           const uint64_t* lookup_challenges, const uint64_t* alphas, size_t nalphas, uint64_t* first_failing_row, char** err);
+/* The table's OWN constraints on every row of the trace domain, from the trace alone -- no challenges, no auxiliary columns -- naming the
+ * first one that fails: what zkm_check_constraints answers with one row, answered with the row, the constraint and its value.  The
+ * constraints are those of the table's eval_packed_generic in emission order (the order of the alpha powers, constraint_consumer.rs:57-62):
+ * row r is paired with row (r + 1) mod n, transition constraints are switched off on the last row, first-row and last-row constraints
+ * are switched on only on their row.  NOT covered, because they are not table constraints: the range-check lookups of Memory and
+ * Arithmetic (Stark::lookups(); zkm_check_constraints evaluates them with their helper columns) and the cross-table lookups
+ * (zkm_check_ctls).
+ *   trace     ncols x 2^log_n canonical words, column-major, host or device (a host table is copied up for the call); ncols must be
+ *             zkm_table_width(table_id), log_n at most 30
+ *   finding   ZKM_WITNESS_FINDING_WORDS words (host): the row (all ones when every constraint holds), the index of the first nonzero
+ *             constraint on that row, its canonical value, the number of rows with at least one nonzero constraint, the number of
+ *             constraints a row emits
+ * Returns 0 when every constraint holds on every row.  Otherwise nonzero, with the finding filled and *err =
+ *   Constraint failed in <Name>Stark: row r, constraint i of N = 0x.. (m of n rows fail)        (the prefix: prover.rs:903-908)
+ * WHICH finding is reported is fixed: the lowest failing row, and within it the lowest constraint index.  A refusal -- a null argument, an
+ * unknown table id, ncols that is not the table's width, log_n out of range -- names its argument and is made on the host before any
+ * device work.
+ * zkm_segment_witness_check: the same for the twelve tables of a segment, traces[t] / log_n[t] of Table::all()[t] as
+ * zkm_segment_check_ctls takes them (the twelve pointers of zkm_staged_segment_ptrs, for one), in ONE set of launches with one download
+ * and one host wait whatever the tables (zkm_ctx_host_waits).  findings = 12 x ZKM_WITNESS_FINDING_WORDS words, every table's own
+ * result; *err names the lowest failing table in Table::all() order.
+ * Both run on the context's stream, behind what is queued there.  A debugging aid: not on the proving path. */
+#define ZKM_WITNESS_FINDING_WORDS 5
+int zkm_witness_check(zkm_ctx* ctx, int table_id, const uint64_t* trace, size_t ncols, unsigned log_n, uint64_t* finding, char** err);
+int zkm_segment_witness_check(zkm_ctx* ctx, const uint64_t* const* traces, const unsigned* log_n, uint64_t* findings, char** err);
 /* check_ctls (cross_table_lookup.rs:1486-1581 testutils::check_ctls; prove_with_traces calls it under the `test` feature, prover.rs:171-176):
  * for each CrossTableLookup, the multiset of the rows of the looking tables whose filter is 1 (check_ctl :1505-1536, process_table
  * :1538-1563) must equal that of the looked table -- on the device, nothing downloaded.  tables / ctls / sides / nctls as

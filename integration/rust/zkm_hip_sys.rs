@@ -421,6 +421,12 @@ extern "C" {
                           sides: *const zkm_ctl_side, nctls: usize, report: *mut zkm_ctl_report, err: *mut *mut c_char) -> c_int;
     pub fn zkm_segment_check_ctls(ctx: *mut zkm_ctx, traces: *const *const u64, log_n: *const c_uint, report: *mut zkm_ctl_report,
                                   err: *mut *mut c_char) -> c_int;
+    // each table's own constraints on every row of the trace, from the trace alone: rc != 0 + "Constraint failed in <Stark>: row r, constraint
+    // i of N = 0x.. (m of n rows fail)" and the finding(s), ZKM_WITNESS_FINDING_WORDS words a table (witness_check_hip.rs)
+    pub fn zkm_witness_check(ctx: *mut zkm_ctx, table_id: c_int, trace: *const u64, ncols: usize, log_n: c_uint, finding: *mut u64,
+                             err: *mut *mut c_char) -> c_int;
+    pub fn zkm_segment_witness_check(ctx: *mut zkm_ctx, traces: *const *const u64, log_n: *const c_uint, findings: *mut u64,
+                                     err: *mut *mut c_char) -> c_int;
     // verify_proof (verifier.rs:27-176) on the device: the general form, K AllStark segments, and the mirror of zkm_prove_single_table
     pub fn zkm_verify_proofs(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, tables: *const zkm_table_input, ntables: usize,
                              ctls: *const zkm_cross_table_lookup, sides: *const zkm_ctl_side, nctls: usize, public_values: *const u64,
@@ -443,6 +449,10 @@ extern "C" {
     pub fn zkm_profile_get(ctx: *mut zkm_ctx, i: usize, name: *mut *const c_char, launches: *mut u64, total_ms: *mut c_double) -> c_int;
     pub fn zkm_version() -> *const c_char;
 }
+
+/// words of one finding of zkm_witness_check / zkm_segment_witness_check: row (all ones: every constraint holds), index of the first nonzero
+/// constraint on that row, its canonical value, rows with a nonzero constraint, constraints a row emits
+pub const ZKM_WITNESS_FINDING_WORDS: usize = 5;
 
 /// status + message -> anyhow::Error; the message is released with free() like recursion/src/snark/snarks.rs:55-57
 pub fn check(rc: c_int, err: *mut c_char) -> anyhow::Result<()> {

@@ -35,6 +35,7 @@ TABLE_SHA_EXTEND, TABLE_SHA_EXTEND_SPONGE, TABLE_SHA_COMPRESS, TABLE_SHA_COMPRES
 # zkm_poseidon_selftest: ZKM_POSEIDON_OUT_* and ZKM_POSEIDON_PROBE_*
 POSEIDON_OUT_ALL, POSEIDON_OUT_CAPACITY, POSEIDON_OUT_DIGEST = (_H["POSEIDON_OUT_" + n] for n in ("ALL", "CAPACITY", "DIGEST"))
 POSEIDON_PROBE = abi.constants("ZKM_POSEIDON_PROBE_")
+WITNESS_FINDING_WORDS = _H["WITNESS_FINDING_WORDS"]   # zkm_witness_check: row, constraint index, value, failing rows, constraints per row
 u64p = C.POINTER(C.c_uint64)
 
 EXPORTS = [name for name, _, _ in abi.prototypes()]
@@ -834,6 +835,7 @@ class Context:
         _check(self.L.zkm_ctx_create(device, C.byref(h), C.byref(err)), err)
         self.h = h
         self._staged = weakref.WeakSet()     # outstanding StagedTraces: freed by close() before the context goes
+        self.witness_message = None          # the message of the last witness_check / segment_witness_check (None: every constraint held)
 
     def close(self):
         if self.h:
@@ -1713,6 +1715,42 @@ class Context:
         rep, err = CtlReport(), C.c_char_p()
         rc = self.L.zkm_segment_check_ctls(self.h, ptrs, lg, C.byref(rep), C.byref(err))
         return self._ctl_report(rc, rep, err)
+
+    @staticmethod
+    def _witness_findings(rc, words, err):
+        """The findings of a witness check as tuples (row or None, constraint index, value, failing rows, constraints per row); a call
+        that could not be made raises.  The message (None when every constraint holds) belongs to the first failing table."""
+        msg = err.value.decode() if err.value else None
+        if rc != 0 and "Constraint failed" not in (msg or ""):
+            raise ZkmError(msg or "witness_check: error %d" % rc)
+        w = [int(x) for x in words]
+        none = (1 << 64) - 1
+        return [(None if w[i] == none else w[i],) + tuple(w[i + 1:i + WITNESS_FINDING_WORDS]) for i in range(0, len(w), WITNESS_FINDING_WORDS)], msg
+
+    def witness_check(self, table_id, trace, log_n):
+        """zkm_witness_check: the table's own constraints on every row of the trace (an array, a DeviceBuffer or a device pointer), from the
+        trace alone.  Returns (row, constraint index, canonical value, failing rows, constraints per row) of the first failure -- the
+        lowest row, within it the lowest index -- with row None when every constraint holds; .witness_message holds the call's message."""
+        words, err = (C.c_uint64 * WITNESS_FINDING_WORDS)(), C.c_char_p()
+        keep = trace if isinstance(trace, (DeviceBuffer, StagedTrace, int)) else np.ascontiguousarray(trace, dtype=np.uint64)
+        rc = self.L.zkm_witness_check(self.h, table_id, _data_ptr(keep), self.L.zkm_table_width(table_id), log_n, words, C.byref(err))
+        findings, self.witness_message = self._witness_findings(rc, words, err)
+        return findings[0]
+
+    def segment_witness_check(self, traces, log_ns):
+        """zkm_segment_witness_check: witness_check on the twelve tables of a segment (Table::all() order; arrays, DeviceBuffers, device
+        pointers, or a staged segment) in one set of launches and one host wait.  Returns the twelve findings; .witness_message names
+        the first failing table (None when all hold)."""
+        if isinstance(traces, StagedTrace):
+            traces = traces.tables()
+        assert len(traces) == 12 and len(log_ns) == 12
+        keep = [t if isinstance(t, (DeviceBuffer, StagedTrace, int)) else np.ascontiguousarray(t, dtype=np.uint64) for t in traces]
+        ptrs = (C.c_void_p * 12)(*[_data_ptr(t).value for t in keep])
+        lg = (C.c_uint * 12)(*[int(x) for x in log_ns])
+        words, err = (C.c_uint64 * (12 * WITNESS_FINDING_WORDS))(), C.c_char_p()
+        rc = self.L.zkm_segment_witness_check(self.h, ptrs, lg, words, C.byref(err))
+        findings, self.witness_message = self._witness_findings(rc, words, err)
+        return findings
 
     @staticmethod
     def _verify_reports(rc, reps, err):
