@@ -1217,7 +1217,7 @@ int zkm_check_constraints(zkm_ctx* ctx, int table_id, const zkm_stark_config* cf
  * row r is paired with row (r + 1) mod n, transition constraints are switched off on the last row, first-row and last-row constraints
  * are switched on only on their row.  NOT covered, because they are not table constraints: the range-check lookups of Memory and
  * Arithmetic (Stark::lookups(); zkm_check_constraints evaluates them with their helper columns) and the cross-table lookups
- * (zkm_check_ctls).
+ * (zkm_check_ctls); zkm_lookup_check below checks those lookups from the trace alone.
  *   trace     ncols x 2^log_n canonical words, column-major, host or device (a host table is copied up for the call); ncols must be
  *             zkm_table_width(table_id), log_n at most 30
  *   finding   ZKM_WITNESS_FINDING_WORDS words (host): the row (all ones when every constraint holds), the index of the first nonzero
@@ -1236,6 +1236,40 @@ int zkm_check_constraints(zkm_ctx* ctx, int table_id, const zkm_stark_config* cf
 #define ZKM_WITNESS_FINDING_WORDS 5
 int zkm_witness_check(zkm_ctx* ctx, int table_id, const uint64_t* trace, size_t ncols, unsigned log_n, uint64_t* finding, char** err);
 int zkm_segment_witness_check(zkm_ctx* ctx, const uint64_t* const* traces, const unsigned* log_n, uint64_t* findings, char** err);
+/* The table's own range-check LOOKUPS (Stark::lookups(): Memory looks RANGE_CHECK up in COUNTER with FREQUENCIES, memory_stark.rs:476-483;
+ * Arithmetic its 18 shared columns in RANGE_COUNTER with RC_FREQUENCIES, arithmetic_stark.rs:269-276) from the trace alone -- no
+ * challenges, no helper columns, no Z -- naming the value that fails.  For a lookup with looking columns cols[], table_col and freq_col,
+ * and a value v (words are read as field elements: a word >= p counts as its residue):
+ *   looking(v)   = the number of cells (c in cols, row r) with trace[c][r] == v                            (an integer)
+ *   frequency(v) = the sum over the rows r with trace[table_col][r] == v of trace[freq_col][r]             (mod p)
+ * The lookup holds iff looking(v) == frequency(v) (mod p) for every v: exactly what the logUp argument enforces for every challenge
+ * (lookup.rs:106-121, 183-194).  The table column need not be 0 .. n - 1: rows that share a value add their frequencies; frequencies are
+ * field elements (p - 1 and looking + 1 on two rows of one value balance; p - 1 on a value nobody looks up does not).
+ *   trace, ncols, log_n   as zkm_witness_check; also refused: a lookup of more than 2^30 records, rows x (looking columns + 1)
+ *   finding   ZKM_LOOKUP_FINDING_WORDS words (host):
+ *             0     index of the failing lookup among the table's lookups; all ones when every lookup holds, and for a table without lookups
+ *             1     the value: the smallest unbalanced canonical value of that lookup (the lowest failing lookup)
+ *             2     looking(value)                        3     frequency(value), canonical
+ *             4     the number of rows whose table column holds the value
+ *             5, 6  trace column and row of the first looking cell that holds it, in (the lookup's column order, then row) order; all ones
+ *                   in both when there is none
+ *             7     the lowest row whose table column holds it; all ones when there is none
+ *             8     the number of unbalanced values of that lookup
+ *             (words 1 .. 8 are 0 when every lookup holds)
+ * Returns 0 when every lookup holds.  Otherwise nonzero, with the finding filled and *err =
+ *   Lookup failed in <Name>Stark: lookup l: value 0x.. is looked up a times (first: column c, row r) and has frequency 0x.. in k table
+ *   rows (first: row t); m values fail                                   ("first: none" for a location that does not exist)
+ * Refusals are made on the host before any device work and write nothing to `finding`.  A table without lookups costs no launch and no
+ * host wait.
+ * zkm_segment_lookup_check: the same for the twelve tables of a segment, as zkm_segment_witness_check takes them: the tables with lookups
+ * share ONE set of launches, one download and one host wait (zkm_ctx_host_waits).  findings = 12 x ZKM_LOOKUP_FINDING_WORDS words in
+ * Table::all() order, every table's own result; *err names the lowest failing table in that order.
+ * Both run on the context's stream, behind what is queued there; a finding or a failure leaves the context usable.  A debugging aid: not
+ * on the proving path.  With zkm_witness_check and zkm_check_ctls this covers what eval_vanishing_poly and verify_cross_table_lookups ask
+ * of a witness. */
+#define ZKM_LOOKUP_FINDING_WORDS 9
+int zkm_lookup_check(zkm_ctx* ctx, int table_id, const uint64_t* trace, size_t ncols, unsigned log_n, uint64_t* finding, char** err);
+int zkm_segment_lookup_check(zkm_ctx* ctx, const uint64_t* const* traces, const unsigned* log_n, uint64_t* findings, char** err);
 /* check_ctls (cross_table_lookup.rs:1486-1581 testutils::check_ctls; prove_with_traces calls it under the `test` feature, prover.rs:171-176):
  * for each CrossTableLookup, the multiset of the rows of the looking tables whose filter is 1 (check_ctl :1505-1536, process_table
  * :1538-1563) must equal that of the looked table -- on the device, nothing downloaded.  tables / ctls / sides / nctls as

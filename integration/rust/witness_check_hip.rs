@@ -4,7 +4,7 @@
 //! The reference's check_constraints (prover.rs:793-910) panics with "Constraint failed in <Stark>" and nothing else; these calls need
 //! the trace alone -- no challenges, no auxiliary columns -- and name the lowest failing row, the lowest nonzero constraint on it (its
 //! index in the emission order of the table's eval_packed_generic), its value, and how many rows fail.  The table's own range-check
-//! lookups and the cross-table lookups are not table constraints: check_ctls_hip.rs covers the latter.
+//! lookups and the cross-table lookups are not table constraints: lookup_check_hip.rs covers the former, check_ctls_hip.rs the latter.
 //!
 //! Goes into the crate as `prover/src/witness_check_hip.rs` (`#[cfg(feature = "hip")] pub(crate) mod witness_check_hip;`), beside
 //! segment_hip.rs, whose `DeviceSegment::tables()` gives the twelve device pointers.  NOT COMPILED in the build image (no cargo / rustc

@@ -427,6 +427,13 @@ extern "C" {
                              err: *mut *mut c_char) -> c_int;
     pub fn zkm_segment_witness_check(ctx: *mut zkm_ctx, traces: *const *const u64, log_n: *const c_uint, findings: *mut u64,
                                      err: *mut *mut c_char) -> c_int;
+    // each table's own range-check lookups from the trace alone: rc != 0 + "Lookup failed in <Stark>: lookup l: value 0x.. is looked up a
+    // times (..) and has frequency 0x.. in k table rows (..); m values fail" and the finding(s), ZKM_LOOKUP_FINDING_WORDS words a table
+    // (lookup_check_hip.rs)
+    pub fn zkm_lookup_check(ctx: *mut zkm_ctx, table_id: c_int, trace: *const u64, ncols: usize, log_n: c_uint, finding: *mut u64,
+                            err: *mut *mut c_char) -> c_int;
+    pub fn zkm_segment_lookup_check(ctx: *mut zkm_ctx, traces: *const *const u64, log_n: *const c_uint, findings: *mut u64,
+                                    err: *mut *mut c_char) -> c_int;
     // verify_proof (verifier.rs:27-176) on the device: the general form, K AllStark segments, and the mirror of zkm_prove_single_table
     pub fn zkm_verify_proofs(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, tables: *const zkm_table_input, ntables: usize,
                              ctls: *const zkm_cross_table_lookup, sides: *const zkm_ctl_side, nctls: usize, public_values: *const u64,
@@ -453,6 +460,9 @@ extern "C" {
 /// words of one finding of zkm_witness_check / zkm_segment_witness_check: row (all ones: every constraint holds), index of the first nonzero
 /// constraint on that row, its canonical value, rows with a nonzero constraint, constraints a row emits
 pub const ZKM_WITNESS_FINDING_WORDS: usize = 5;
+/// words of one finding of zkm_lookup_check / zkm_segment_lookup_check: failing lookup (all ones: every lookup holds), the value, its looking
+/// count, its frequency, its table rows, column and row of its first looking cell, its first table row, the unbalanced values
+pub const ZKM_LOOKUP_FINDING_WORDS: usize = 9;
 
 /// status + message -> anyhow::Error; the message is released with free() like recursion/src/snark/snarks.rs:55-57
 pub fn check(rc: c_int, err: *mut c_char) -> anyhow::Result<()> {

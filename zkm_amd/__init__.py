@@ -36,6 +36,8 @@ TABLE_SHA_EXTEND, TABLE_SHA_EXTEND_SPONGE, TABLE_SHA_COMPRESS, TABLE_SHA_COMPRES
 POSEIDON_OUT_ALL, POSEIDON_OUT_CAPACITY, POSEIDON_OUT_DIGEST = (_H["POSEIDON_OUT_" + n] for n in ("ALL", "CAPACITY", "DIGEST"))
 POSEIDON_PROBE = abi.constants("ZKM_POSEIDON_PROBE_")
 WITNESS_FINDING_WORDS = _H["WITNESS_FINDING_WORDS"]   # zkm_witness_check: row, constraint index, value, failing rows, constraints per row
+# zkm_lookup_check: failing lookup, value, looking count, frequency, table rows, first looking cell (column, row), first table row, failing values
+LOOKUP_FINDING_WORDS = _H["LOOKUP_FINDING_WORDS"]
 u64p = C.POINTER(C.c_uint64)
 
 EXPORTS = [name for name, _, _ in abi.prototypes()]
@@ -836,6 +838,7 @@ class Context:
         self.h = h
         self._staged = weakref.WeakSet()     # outstanding StagedTraces: freed by close() before the context goes
         self.witness_message = None          # the message of the last witness_check / segment_witness_check (None: every constraint held)
+        self.lookup_message = None           # ... of the last lookup_check / segment_lookup_check (None: every lookup held)
 
     def close(self):
         if self.h:
@@ -1750,6 +1753,47 @@ class Context:
         words, err = (C.c_uint64 * (12 * WITNESS_FINDING_WORDS))(), C.c_char_p()
         rc = self.L.zkm_segment_witness_check(self.h, ptrs, lg, words, C.byref(err))
         findings, self.witness_message = self._witness_findings(rc, words, err)
+        return findings
+
+    @staticmethod
+    def _lookup_findings(rc, words, err):
+        """The findings of a lookup check as tuples (lookup or None, value, looking count, frequency, table rows, column and row of the first
+        looking cell, first table row, failing values), a location that does not exist as None; a call that could not be made raises.  The
+        message (None when every lookup holds) belongs to the first failing table."""
+        msg = err.value.decode() if err.value else None
+        if rc != 0 and not (msg or "").startswith("Lookup failed in "):
+            raise ZkmError(msg or "lookup_check: error %d" % rc)
+        w = [int(x) for x in words]
+        none = (1 << 64) - 1
+        out = []
+        for i in range(0, len(w), LOOKUP_FINDING_WORDS):
+            f = w[i:i + LOOKUP_FINDING_WORDS]
+            out.append(tuple(None if k in (0, 5, 6, 7) and x == none else x for k, x in enumerate(f)))
+        return out, msg
+
+    def lookup_check(self, table_id, trace, log_n):
+        """zkm_lookup_check: the table's own range-check lookups (Memory, Arithmetic) from the trace alone (an array, a DeviceBuffer, a
+        device pointer or a StagedTrace).  Returns the nine words of the finding -- the smallest unbalanced value of the lowest failing
+        lookup -- with the lookup None when every lookup holds (and for a table without lookups); .lookup_message holds the call's message."""
+        words, err = (C.c_uint64 * LOOKUP_FINDING_WORDS)(), C.c_char_p()
+        keep = trace if isinstance(trace, (DeviceBuffer, StagedTrace, int)) else np.ascontiguousarray(trace, dtype=np.uint64)
+        rc = self.L.zkm_lookup_check(self.h, table_id, _data_ptr(keep), self.L.zkm_table_width(table_id), log_n, words, C.byref(err))
+        findings, self.lookup_message = self._lookup_findings(rc, words, err)
+        return findings[0]
+
+    def segment_lookup_check(self, traces, log_ns):
+        """zkm_segment_lookup_check: lookup_check on the twelve tables of a segment (Table::all() order; arrays, DeviceBuffers, device
+        pointers, or a staged segment): the tables with lookups in one set of launches and one host wait.  Returns the twelve findings;
+        .lookup_message names the first failing table (None when all hold)."""
+        if isinstance(traces, StagedTrace):
+            traces = traces.tables()
+        assert len(traces) == 12 and len(log_ns) == 12
+        keep = [t if isinstance(t, (DeviceBuffer, StagedTrace, int)) else np.ascontiguousarray(t, dtype=np.uint64) for t in traces]
+        ptrs = (C.c_void_p * 12)(*[_data_ptr(t).value for t in keep])
+        lg = (C.c_uint * 12)(*[int(x) for x in log_ns])
+        words, err = (C.c_uint64 * (12 * LOOKUP_FINDING_WORDS))(), C.c_char_p()
+        rc = self.L.zkm_segment_lookup_check(self.h, ptrs, lg, words, C.byref(err))
+        findings, self.lookup_message = self._lookup_findings(rc, words, err)
         return findings
 
     @staticmethod
