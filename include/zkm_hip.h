@@ -852,7 +852,8 @@ int zkm_boot_witness(zkm_ctx* ctx, const zkm_boot_image* image, uint64_t* cpu_ro
  *                          into_tables on the joined lists; "check_ctls", "verify", waves, memory budget and sizing mode as in the
  *                          calls without steps, and so are the three host waits whatever K: the step path adds none.  Every table,
  *                          blob and challenge is word for word what the calls without steps give for the expanded rows and lists.
- * Steps are not staged (zkm_segment_ops_stage takes none), the pool takes none, kinds outside the list go RAW, and there is no exit
+ * Steps are not staged (zkm_segment_ops_stage takes none), the pool takes none, kinds outside the list go RAW (the thirteen other
+ * encodings decode() accepts as rows expanded on the device: zkm_insn_rows_* below), and there is no exit
  * kernel.  Profile scopes cpu_steps/lists and cpu_steps/rows (zkm_cpu_witness: cpu_steps/rows_lists). */
 #define ZKM_STEP_BINARY_OP 0
 #define ZKM_STEP_BINARY_IMM_OP 1
@@ -1063,6 +1064,70 @@ int zkm_io_calls_steps(const uint32_t* kinds, const uint64_t* data_off, const ui
                        zkm_cpu_step* steps_out, uint64_t* clocks_out, char** err);
 int zkm_io_calls_witness(zkm_ctx* ctx, const uint32_t* kinds, const uint8_t* data, const uint64_t* data_off, const uint64_t* meta,
                          size_t ncalls, uint64_t* raw_rows_out_dev, char** err);
+
+/* ------------------------------------------------------------------ the instructions the step kinds refuse, as rows
+ * decode() (witness/transition.rs:42-312) accepts thirteen encodings that no ZKM_STEP_* kind takes.  Their rows are expanded here, on the
+ * device, as ready-made rows for RAW steps, and the arithmetic operations they push go into a device list for zkm_segment_ops -- the
+ * route the calls above take; the step kinds, their refusals and their messages stay as they are.  A record is a zkm_cpu_step in host
+ * memory: pc, next_pc, insn, flags bit 0 (kernel mode) and context as in the step log; kind one of the constants below; reads the values
+ * read, in the generator's order; clocks[k] is the clock of record k's row.  Each kind takes exactly the (opcode, func) pair decode
+ * matches for it; the other fields are free: they go into the row's bits and, where decode uses them, into the operands.
+ *   MUL (0x1C, 0x02)  generate_binary_arithmetic_op (witness/operation.rs:286-318): channels 0 and 1 read rs and rt (reads[0], reads[1]),
+ *                     channel 2 writes the product's low word to rd; pushes {IS_MUL, in0, in1}
+ *   MFHI MTHI MFLO MTLO (0, 0x10 .. 0x13)  the same generator with decode's operands: MFHI reads register 33 and register 0 and writes
+ *                     rd, MTHI reads rs and register 0 and writes register 33, MFLO reads 32 and 0 and writes rd, MTLO reads rs and 0 and
+ *                     writes 32; the value written is reads[0]; reads[1], the value of register 0, must be 0; pushes {IS_M*, in0, 0}
+ *   MULT MULTU DIV DIVU (0, 0x18 .. 0x1B)  generate_binary_arithmetic_hilo_op (:320-375): channels 0 and 1 read rs and rt, channel 2
+ *                     writes lo to register 32, channel 3 hi to register 33 (DIV: quotient and remainder as Rust's / and %); pushes one
+ *   LUI (0x0F)        generate_lui (:405-433): no read; channel 0 is a write of sext(imm) to register rs, channel 1 a write of 1 << 16 to
+ *                     rt, channel 2 the write of imm << 16 to rt; pushes {IS_LUI, sext(imm), 1 << 16}
+ *   SDC1 (0x3D)       generate_mstore_general with MemOp::SDC1 (:1804-1928): channels 0 and 1 read base and rt, channel 2 reads the word
+ *                     at (base + sext(imm)) & ~3 in the record's context (reads[0 .. 2]), channel 3 stores 0 there; the three bit
+ *                     decompositions, aux_filter and is_sdc1 are set, aux_rs0_mul_rs1 is 0; pushes nothing
+ *   SYNC (0, 0x0F), PREF (0x33)  generate_nop: the op flag alone; no channel, no operation
+ * A row is the whole CpuColumnsView: clock, context, pc, next_pc, the kernel flag, the 32 instruction bits, one op flag (binary_op,
+ * binary_imm_op for LUI, m_op_store, nop), the channels, the kind's own cells, every other cell 0, all words canonical.  A write to
+ * register 0 fills its channel with used = 0 and pushes nothing (witness/util.rs:198-204).  Results are computed on the device as
+ * BinaryOperator::result does (arithmetic/mod.rs:48-133).  The arithmetic operations are {row filter, in0, in1} triples of uint32 as
+ * zkm_arithmetic_trace takes them, in record order; a record that pushes none takes no slot.  The rows' memory operations are pushed by
+ * their RAW steps, as for any RAW row (all thirteen generators push them in channel order).
+ * What a record produces is one __host__ __device__ function (csrc/insn_rows.hip zkm_insn::expand) for the host walk and the kernel.
+ *   zkm_insn_rows_counts    the used channels and the operations of the records (any out pointer may be NULL); pure: no context, no GPU
+ *   zkm_insn_rows_steps     pure.  The RAW records (kind ZKM_STEP_RAW, reads[0] = raw_base + k, reads[1] = the row's mask of used channels,
+ *                           every other field 0) into steps_out; the caller places record k at clocks[k] - first_clock of its step list.
+ *                           THE statement of masks: MUL and the four moves 3 | (dest != 0) << 2; the hi/lo kinds and SDC1 0xF; LUI
+ *                           (rs != 0) | (rt != 0) << 1 | (rt != 0) << 2; SYNC and PREF 0.  raw_base + ninsns must fit in 32 bits.
+ *   zkm_insn_rows_witness   the kernel: one launch for all records; a workgroup builds a fixed number of rows in LDS, one lane a row, then
+ *                           all its lanes stream the block out, adjacent lanes on adjacent words.  Every word of the ninsns x ZKM_CPU_COLS
+ *                           block is written exactly once: nothing is zeroed in front.  raw_rows_out_dev is a plain device pointer (8-byte
+ *                           aligned), so it may aim into the middle of a larger block; arithmetic_ops_out_dev (4-byte aligned) takes
+ *                           arithmetic_ops x 3 uint32 and may be NULL when no record pushes an operation.  The host walk uploads each
+ *                           workgroup's base in the arithmetic list.  Returns once both outputs are complete: one host wait.  Profile
+ *                           scope insn_rows/rows.
+ * Refused, on the host walk before any device work and before a missing context is reported, the message naming the function and
+ * `record k`: an unknown kind; an encoding the kind does not take; DIV or DIVU with a zero divisor and DIV of 0x80000000 by 0xFFFFFFFF
+ * (result() panics on all three); MFHI, MFLO, MTHI or MTLO whose reads[1] is not 0; a clock of 2^32 or more; raw_base + ninsns that does
+ * not fit in 32 bits; a NULL list or output with a nonzero count; records or clocks in device memory; a misaligned output.  A refusal
+ * leaves the context usable and its live memory as it was.
+ * Out of scope: new step kinds; the records are not staged and the pool takes none; nothing is fused into the segment builder;
+ * keccak_general, Pc and GetContext / SetContext (decode never produces them); the exit kernel. */
+#define ZKM_INSN_LUI 0
+#define ZKM_INSN_MUL 1
+#define ZKM_INSN_MULT 2
+#define ZKM_INSN_MULTU 3
+#define ZKM_INSN_DIV 4
+#define ZKM_INSN_DIVU 5
+#define ZKM_INSN_MFHI 6
+#define ZKM_INSN_MTHI 7
+#define ZKM_INSN_MFLO 8
+#define ZKM_INSN_MTLO 9
+#define ZKM_INSN_SDC1 10
+#define ZKM_INSN_SYNC 11
+#define ZKM_INSN_PREF 12
+int zkm_insn_rows_counts(const zkm_cpu_step* insns, size_t ninsns, size_t* memory_ops, size_t* arithmetic_ops, char** err);
+int zkm_insn_rows_steps(const zkm_cpu_step* insns, size_t ninsns, size_t raw_base, zkm_cpu_step* steps_out, char** err);
+int zkm_insn_rows_witness(zkm_ctx* ctx, const zkm_cpu_step* insns, const uint64_t* clocks, size_t ninsns, uint64_t* raw_rows_out_dev,
+                          uint32_t* arithmetic_ops_out_dev, char** err);
 
 /* ------------------------------------------------------------------ a memory image's hash pages, root and image id
  * What the emulator does at every segment split -- Memory::update_page_hash and Memory::compute_image_id (emulator/src/memory.rs:388-471,

@@ -82,6 +82,12 @@ impl StepLog {
         self.nreads += 1;
     }
 
+    /// The values read since the last step, handed to a recorder that logs the row elsewhere (insn_rows_hip.rs); the log starts afresh.
+    pub fn take_reads(&mut self) -> [u32; 6] {
+        self.nreads = 0;
+        std::mem::take(&mut self.reads)
+    }
+
     /// The step of an instruction the library derives.  `registers`: the state BEFORE the step (program_counter and next_pc are the
     /// row's).  `syscall`: ZKM_SYSCALL_* for a SYSCALL, 0 otherwise.  Returns false, and logs nothing, for an operation without a kind
     /// (or a word the kind does not take: a NOP that is not word 0, SDC1): the caller fills the row and calls push_raw.

@@ -151,6 +151,11 @@ pub const ZKM_SYSCALL_SET_THREAD_AREA: u32 = 8;
 pub const ZKM_SPONGE_BYTE_ADDRESSED: u64 = 0x8000000000000000;
 // the kinds of zkm_io_calls_*: the data-moving helper behind generate_syscall's row (load_input, commit, verify, load_preimage)
 pub const ZKM_IO_HINT_READ: u32 = 0; pub const ZKM_IO_COMMIT: u32 = 1; pub const ZKM_IO_VERIFY: u32 = 2; pub const ZKM_IO_PREIMAGE: u32 = 3;
+// the kinds of zkm_insn_rows_*: the thirteen encodings decode() accepts and no ZKM_STEP_* kind takes
+pub const ZKM_INSN_LUI: u32 = 0; pub const ZKM_INSN_MUL: u32 = 1; pub const ZKM_INSN_MULT: u32 = 2; pub const ZKM_INSN_MULTU: u32 = 3;
+pub const ZKM_INSN_DIV: u32 = 4; pub const ZKM_INSN_DIVU: u32 = 5; pub const ZKM_INSN_MFHI: u32 = 6; pub const ZKM_INSN_MTHI: u32 = 7;
+pub const ZKM_INSN_MFLO: u32 = 8; pub const ZKM_INSN_MTLO: u32 = 9; pub const ZKM_INSN_SDC1: u32 = 10; pub const ZKM_INSN_SYNC: u32 = 11;
+pub const ZKM_INSN_PREF: u32 = 12;
 pub const ZKM_VERIFY_OK: u32 = 0; pub const ZKM_VERIFY_SHAPE: u32 = 1; pub const ZKM_VERIFY_TRANSCRIPT_STATE: u32 = 2;
 pub const ZKM_VERIFY_CTL_CHALLENGES: u32 = 3; pub const ZKM_VERIFY_QUOTIENT: u32 = 4; pub const ZKM_VERIFY_POW: u32 = 5;
 pub const ZKM_VERIFY_INITIAL_MERKLE: u32 = 6; pub const ZKM_VERIFY_FRI_EVAL: u32 = 7; pub const ZKM_VERIFY_FRI_MERKLE: u32 = 8;
@@ -362,6 +367,13 @@ extern "C" {
                               steps_out: *mut zkm_cpu_step, clocks_out: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_io_calls_witness(ctx: *mut zkm_ctx, kinds: *const u32, data: *const u8, data_off: *const u64, meta: *const u64, ncalls: usize,
                                 raw_rows_out_dev: *mut u64, err: *mut *mut c_char) -> c_int;
+    // the rows of the instructions no step kind takes (LUI, MUL, the hi/lo kinds and moves, SDC1, SYNC, PREF) expanded on the device
+    pub fn zkm_insn_rows_counts(insns: *const zkm_cpu_step, ninsns: usize, memory_ops: *mut usize, arithmetic_ops: *mut usize,
+                                err: *mut *mut c_char) -> c_int;
+    pub fn zkm_insn_rows_steps(insns: *const zkm_cpu_step, ninsns: usize, raw_base: usize, steps_out: *mut zkm_cpu_step,
+                               err: *mut *mut c_char) -> c_int;
+    pub fn zkm_insn_rows_witness(ctx: *mut zkm_ctx, insns: *const zkm_cpu_step, clocks: *const u64, ninsns: usize, raw_rows_out_dev: *mut u64,
+                                 arithmetic_ops_out_dev: *mut u32, err: *mut *mut c_char) -> c_int;
     // what the emulator hashes between two segments: hash pages, root and image id of a memory image
     pub fn zkm_image_hash_plan(dirty_index: *const u32, ndirty: usize, hash_index_out: *mut u32, capacity: usize) -> usize;
     pub fn zkm_image_hash(ctx: *mut zkm_ctx, r#in: *const zkm_image_pages, hash_words_out: *mut u32, page_hash_root_out: *mut u8,

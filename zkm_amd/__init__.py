@@ -262,6 +262,38 @@ def io_calls_steps(kinds, data_off, meta, raw_base=0):
     return steps, clocks
 
 
+# the kinds of the instruction rows (ZKM_INSN_*): lui, mul, mult, multu, div, divu, mfhi, mthi, mflo, mtlo, sdc1, sync, pref
+INSN_KINDS = {n.lower(): v for n, v in abi.constants("ZKM_INSN_").items()}
+
+
+def _insn_lists(insns):
+    """(records CPU_STEP_DT n, clocks u64 n) as contiguous numpy arrays, and the number of records; None, 0 without records."""
+    if insns is None:
+        return None, 0
+    records, clocks = insns
+    k = (np.ascontiguousarray(records, dtype=CPU_STEP_DT).reshape(-1), np.ascontiguousarray(clocks, dtype=np.uint64).reshape(-1))
+    assert k[0].size == k[1].size, "one clock per record"
+    return (k if k[0].size else None), k[0].size
+
+
+def insn_rows_counts(records):
+    """zkm_insn_rows_counts: (memory_ops, arithmetic_ops) that the rows of these instruction records (a CPU_STEP_DT array, kind one of
+    INSN_KINDS) push; needs no GPU.  Every refusal of the host walk raises ZkmError naming the record."""
+    r = np.ascontiguousarray(records, dtype=CPU_STEP_DT).reshape(-1)
+    out, err = [C.c_size_t() for _ in range(2)], C.c_char_p()
+    _check(load().zkm_insn_rows_counts(r.ctypes.data if r.size else None, r.size, *[C.byref(x) for x in out], C.byref(err)), err)
+    return tuple(int(x.value) for x in out)
+
+
+def insn_rows_steps(records, raw_base=0):
+    """zkm_insn_rows_steps: the RAW step records (a CPU_STEP_DT array) of the instruction records' rows, record k for the position
+    clocks[k] - first_clock of the step list; needs no GPU.  Every refusal raises ZkmError naming the record."""
+    r = np.ascontiguousarray(records, dtype=CPU_STEP_DT).reshape(-1)
+    steps, err = np.zeros(r.size, dtype=CPU_STEP_DT), C.c_char_p()
+    _check(load().zkm_insn_rows_steps(r.ctypes.data if r.size else None, r.size, raw_base, steps.ctypes.data if r.size else None, C.byref(err)), err)
+    return steps
+
+
 class CtlLocation(C.Structure):
     """zkm_ctl_location: one occurrence of a reported tuple (side of the lookup, index of the table, row)."""
     _fields_ = [("side", C.c_uint32), ("table", C.c_uint32), ("row", C.c_uint64)]
@@ -1485,27 +1517,52 @@ class Context:
         finally:
             buf.free()
 
+    # ---- the instructions the step kinds refuse, as rows (include/zkm_hip.h "the instructions the step kinds refuse, as rows")
+    def insn_rows_witness_into(self, insns, ninsns, raw_rows, arithmetic_ops):
+        """zkm_insn_rows_witness as it is: insns = (records, clocks), numpy arrays of CPU_STEP_DT and uint64 (or None with a count of 0);
+        raw_rows and arithmetic_ops are device addresses (integers) or None."""
+        ptr = lambda x: None if x is None else x.ctypes.data if isinstance(x, np.ndarray) else _data_ptr(x).value
+        lists = [ptr(x) for x in tuple(insns or (None, None))]
+        err = C.c_char_p()
+        _check(self.L.zkm_insn_rows_witness(self.h, *lists, ninsns, raw_rows, arithmetic_ops, C.byref(err)), err)
+
+    def insn_rows_witness(self, records, clocks):
+        """zkm_insn_rows_witness into buffers of its own.  Returns numpy (raw_rows n x 259 uint64, arithmetic_ops n x 3 uint32)."""
+        k, n = _insn_lists((records, clocks))
+        arith = insn_rows_counts(k[0])[1] if n else 0
+        bufs = [self.alloc(max(w, 1)) for w in (n * 259, (arith * 3 + 1) // 2)]
+        try:
+            self.insn_rows_witness_into(k, n, bufs[0].ptr, bufs[1].ptr if arith else None)
+            return bufs[0].download()[:n * 259].reshape(n, 259), bufs[1].download().view(np.uint32)[:arith * 3].reshape(arith, 3)
+        finally:
+            for b in bufs:
+                b.free()
+
     def calls_expand(self, steps, first_clock=0, extend=None, compress=None, keccak=None, memory_ops=None, logic_ops=None, keccak_perms=None,
-                     io=None, **groups):
+                     io=None, insns=None, arithmetic_ops=None, **groups):
         """A segment with precompile and I/O calls made ready for segments_tables_steps / prove_segments_ops_steps.  steps: a CpuSteps with
         the segment's own RAW rows (host memory) whose list holds a placeholder at the position of every row of a call (sha_calls_steps,
         keccak_calls_steps and io_calls_steps say which: clock - first_clock); extend = (w16, meta), compress = (hx, w, meta), keccak =
-        (inputs, input_off, meta, digest_addrs), io = (kinds, data, data_off, meta): the calls; memory_ops / logic_ops / keccak_perms =
-        (inputs, timestamps): the segment's own operations; groups: the other groups of SegmentOps, passed on.  Returns (CpuSteps,
-        SegmentOps): the steps with the calls' RAW records in place and raw_rows a DeviceBuffer of own rows, then the SHA calls', then the
-        Keccak calls', then the I/O calls'; the operations with memory_ops, logic_ops, sha_extend and keccak in device memory (own items
-        in front, the generated ones behind in the same order) and the sponge groups set from the calls.  Free with ops.free() and
-        steps.raw_rows.free()."""
+        (inputs, input_off, meta, digest_addrs), io = (kinds, data, data_off, meta): the calls; insns = (records, clocks): the
+        instructions no step kind takes (insn_rows_steps; their placeholders sit at clocks - first_clock); memory_ops / logic_ops /
+        arithmetic_ops / keccak_perms = (inputs, timestamps): the segment's own operations; groups: the other groups of SegmentOps, passed
+        on.  Returns (CpuSteps, SegmentOps): the steps with the calls' RAW records in place and raw_rows a DeviceBuffer of own rows, then
+        the SHA calls', then the Keccak calls', then the I/O calls', then the instructions'; the operations with memory_ops, logic_ops,
+        sha_extend and keccak (and, with insns, arithmetic_ops) in device memory (own items in front, the generated ones behind in the
+        same order) and the sponge groups set from the calls.  Free with ops.free() and steps.raw_rows.free()."""
         e, c, ne, nc = self._sha_lists(extend, compress)
         k, nk = self._keccak_lists(keccak)
         i, ni = _io_lists(io)
+        q, nq = _insn_lists(insns)
         rows, mem, logic, ext = sha_calls_counts(ne, nc)
         krows, kmem, klogic, kperms = keccak_calls_counts(k[1]) if nk else (0, 0, 0, 0)
         irows = io_calls_counts(i[0], i[2])[0] if ni else 0
+        qarith = insn_rows_counts(q[0])[1] if nq else 0
         assert not isinstance(steps.raw_rows, DeviceBuffer) and not {"sha_extend", "keccak_sponge"} & set(groups)
         own_raw = steps.raw_rows.reshape(-1)
         own_mem = np.ascontiguousarray(memory_ops if memory_ops is not None else [], dtype=np.uint64).reshape(-1)
         own_logic = np.ascontiguousarray(logic_ops if logic_ops is not None else [], dtype=np.uint32).reshape(-1)
+        own_arith = np.ascontiguousarray(arithmetic_ops if arithmetic_ops is not None else [], dtype=np.uint32).reshape(-1)
         own_perms = [np.ascontiguousarray(a, dtype=np.uint64).reshape(-1) for a in (keccak_perms if keccak_perms is not None else ([], []))]
         assert own_perms[0].size == 25 * own_perms[1].size, "25 words and one timestamp per permutation"
         records, clocks = sha_calls_steps(e[1] if e else None, c[2] if c else None, raw_base=steps.nraw)
@@ -1516,22 +1573,28 @@ class Context:
             assert not isinstance(i[3], DeviceBuffer), "the records' clocks are read on the host: meta in host memory"
             irecords, iclocks = io_calls_steps(i[0], i[2], i[3], raw_base=steps.nraw + rows + krows)
             records, clocks = (np.concatenate([records, irecords]), np.concatenate([clocks, iclocks])) if rows + krows else (irecords, iclocks)
+        if nq:
+            qrecords = insn_rows_steps(q[0], raw_base=steps.nraw + rows + krows + irows)
+            records, clocks = (np.concatenate([records, qrecords]), np.concatenate([clocks, q[1]])) if rows + krows + irows else (qrecords, q[1])
         at = clocks.astype(np.int64) - first_clock
         taken = np.zeros(steps.steps.size, dtype=bool)
         if at.size and at.min() >= 0 and at.max() < taken.size:
             taken[at] = True
         assert np.count_nonzero(taken) == at.size, "a call's rows lie outside the step list, or two rows share a clock"
-        patched = steps.steps.copy()
+        # (the records as rows of twelve words: numpy copies and scatters a plain matrix several times faster than a structured array)
+        patched = steps.steps.view(np.uint32).reshape(-1, 12).copy()
+        words = np.ascontiguousarray(records).view(np.uint32).reshape(-1, 12)
         if at.size and at[-1] - at[0] + 1 == at.size and (np.diff(at) == 1).all():
-            patched[at[0]:at[0] + at.size] = records          # one run of clocks (one long call): a plain copy
+            patched[at[0]:at[0] + at.size] = words            # one run of clocks (one long call): a plain copy
         else:
-            patched[at] = records
+            patched[at] = words
+        patched = patched.reshape(-1).view(CPU_STEP_DT)
         # one device block a list: own items in front, the generated ones behind
-        sizes = (own_raw.size + (rows + krows + irows) * 259, own_mem.size + (mem + kmem) * 6, (own_logic.size + (logic + klogic) * 3 + 1) // 2, ext * 2, ext,
-                 own_perms[0].size + kperms * 25, own_perms[1].size + kperms)
+        sizes = (own_raw.size + (rows + krows + irows + nq) * 259, own_mem.size + (mem + kmem) * 6, (own_logic.size + (logic + klogic) * 3 + 1) // 2, ext * 2, ext,
+                 own_perms[0].size + kperms * 25, own_perms[1].size + kperms, (own_arith.size + qarith * 3 + 1) // 2 if nq else 0)
         bufs = [self.alloc(n) if n else None for n in sizes]
         try:
-            for buf, own in zip(bufs, (own_raw, own_mem, own_logic, None, None, own_perms[0], own_perms[1])):
+            for buf, own in zip(bufs, (own_raw, own_mem, own_logic, None, None, own_perms[0], own_perms[1], own_arith if nq else None)):
                 if own is not None and own.size:
                     buf.upload(_as_words(own))
             if rows:
@@ -1543,6 +1606,9 @@ class Context:
                                                bufs[6].ptr + 8 * own_perms[1].size)
             if ni:
                 self.io_calls_witness_into(i, ni, bufs[0].ptr + 8 * (own_raw.size + (rows + krows) * 259))
+            if nq:
+                self.insn_rows_witness_into(q, nq, bufs[0].ptr + 8 * (own_raw.size + (rows + krows + irows) * 259),
+                                            bufs[7].ptr + 4 * own_arith.size if qarith else None)
         except Exception:
             for b in bufs:
                 if b is not None:
@@ -1550,9 +1616,11 @@ class Context:
             raise
         ops = SegmentOps(None, bufs[1], logic_ops=bufs[2], sha_extend=(bufs[3], bufs[4]) if ext else None, sha_extend_sponge=e, sha_compress=c,
                          sha_compress_sponge=c, keccak=(bufs[5], bufs[6]) if bufs[5] is not None else None, keccak_sponge=k[:3] if nk else None,
-                         **groups)
+                         arithmetic_ops=bufs[7] if nq else arithmetic_ops, **groups)
         ops.counts["nlogic"] = own_logic.size // 3 + logic + klogic     # (a DeviceBuffer is counted in whole words)
-        return CpuSteps(patched, bufs[0] if bufs[0] is not None else None, nraw=steps.nraw + rows + krows + irows), ops
+        if nq:
+            ops.counts["narithmetic"] = own_arith.size // 3 + qarith
+        return CpuSteps(patched, bufs[0] if bufs[0] is not None else None, nraw=steps.nraw + rows + krows + irows + nq), ops
 
     def stage_segment_ops(self, ops):
         """zkm_segment_ops_stage: queue the upload of a segment's lists behind the context's current work and return at once.  The
