@@ -1,7 +1,9 @@
 """GPU suite: zkm_verify_segments / zkm_verify_proofs / zkm_verify_single_table -- verify_proof (verifier.rs:27-176) on the device.
 The judge of every verdict is the oracle's sequential verifier (oracle.verify_all / oracle.verify): its return code is translated by
 `expected` below and the device's report must name the same check, table, tree and lookup; `query` and `layer` are predicted from
-where the test changed the blob.  Then hostile blobs, the launch accounting, and the "verify" key in front of the prove calls."""
+where the test changed the blob.  Then hostile blobs, the launch accounting, and the "verify" key in front of the prove calls.
+The rejections here touch four tables, two queries and the quad form of the chain kernel; tests/test_gpu_verify_sweep.py sweeps all
+twelve tables, every query, layer and chain in both forms of that kernel, and blobs with more than one finding."""
 import ctypes as C
 import os
 
