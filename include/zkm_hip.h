@@ -1129,6 +1129,79 @@ int zkm_insn_rows_steps(const zkm_cpu_step* insns, size_t ninsns, size_t raw_bas
 int zkm_insn_rows_witness(zkm_ctx* ctx, const zkm_cpu_step* insns, const uint64_t* clocks, size_t ninsns, uint64_t* raw_rows_out_dev,
                           uint32_t* arithmetic_ops_out_dev, char** err);
 
+/* ------------------------------------------------------------------ K segments' calls expanded in one set of launches
+ * The four expansions above, composed: which RAW index each generated row gets, where its record goes in the step list, one device
+ * block per list with the segment's own items in front, and which groups of zkm_segment_ops the calls set -- for K segments at once,
+ * in front of zkm_segments_tables_steps / zkm_prove_segments_ops_steps, whose inputs it produces.  A segment as the emulator records
+ * it is one zkm_segment_calls:
+ *   steps         the segment's own step list with a placeholder record (any record: it is overwritten) at the position of every row of
+ *                 a call and of every `insns` record; raw_rows: the segment's own ready-made rows, HOST memory
+ *   first_clock   the clock of steps.steps[0] (the bootstrap's row count, or 0)
+ *   own           the segment's own operations, and the groups that are passed on untouched.  cpu_rows must be NULL; memory_ops,
+ *                 logic_ops, arithmetic_ops, keccak_* (the segment's own permutations), poseidon_* and poseidon_sponge_* may be set;
+ *                 sha_extend_*, sha_extend_sponge_*, sha_compress_*, sha_compress_sponge_* and keccak_sponge_* must be empty: the
+ *                 calls own them
+ *   extend_* compress_*   the SHA calls as zkm_sha_calls_witness takes them       } every list the host reads -- the metas, the offsets, the
+ *   keccak_*              the SYSKECCAK calls as zkm_keccak_calls_witness does   } kinds, the records, the clocks -- is HOST memory here; the
+ *   io_*                  the I/O calls as zkm_io_calls_witness does             } payloads (w16, hx, w, the input bytes, the data bytes,
+ *   insns, insn_clocks    the records of zkm_insn_rows_witness and their clocks  } the digest addresses) are host or device memory
+ * RAW indices continue steps.nraw in the order own, SHA, Keccak, I/O, instructions; every list holds the segment's own items in front and
+ * the generated ones behind in that order.
+ *   zkm_segment_calls_steps     pure (no context, no GPU): the host half, built from the four zkm_*_steps / zkm_*_counts above.  Writes the
+ *                               patched list (steps.nsteps records: the segment's own with every call's RAW record at clock - first_clock)
+ *                               into steps_out, and counts_out[ZKM_CALLS_COUNTS]: [0..3] the rows of the SHA, Keccak, I/O calls and the
+ *                               instructions; [4] the total nraw (steps.nraw + those); the items GENERATED into the lists: [5] memory
+ *                               operations (the SHA and Keccak sponges' reads), [6] logic operations, [7] arithmetic operations, [8]
+ *                               ShaExtend rows, [9] Keccak permutations; [10] the memory operations the I/O and instruction rows' RAW
+ *                               steps will push (no list item).  Either output may be NULL.
+ *   zkm_segments_calls_expand   the calls of all nseg segments.  A group of up to 32 segments takes ONE scratch block (every list the
+ *                               host holds, of every kind and segment, and the kernels' descriptors), at most ONE launch per kind
+ *                               (none for a kind no segment of the group uses; profile scopes as the four entry points) and ONE host
+ *                               wait; more segments are expanded in consecutive groups.  *out holds the results:
+ *   zkm_expanded_calls_get      for segment `segment`: steps_out = the patched list (held by the handle) with raw_rows in device memory --
+ *                               own rows, then the SHA calls', the Keccak calls', the I/O calls', the instructions' -- and ops_out = `own`
+ *                               with memory_ops, logic_ops, keccak_* and sha_extend_* in device memory (arithmetic_ops too when the
+ *                               segment has instruction records; otherwise it is passed on), sha_extend_sponge_*, sha_compress_*,
+ *                               sha_compress_sponge_* and keccak_sponge_* pointing at the CALLER's call lists, which therefore stay
+ *                               as they are until the handle is freed.  A segment with no calls at all passes through unchanged, its own
+ *                               rows and lists uploaded.  Every word is what the four entry points write when composed by hand.
+ *   zkm_expanded_calls_free     releases the handle and its device blocks (NULL is allowed)
+ *   zkm_segments_tables_calls / zkm_prove_segments_ops_calls   the expansion, zkm_segments_tables_steps / zkm_prove_segments_ops_steps on
+ *                               its outputs, the free.  Arguments as those take them with `calls` in place of steps and ops; images may be
+ *                               NULL; sizing mode, waves, "check_ctls" and "verify" are the inner call's, and so are its three host waits:
+ *                               the expansion in front adds one per 32 segments.
+ * Refused by all of them, on the host before any device work, the message naming the function and the segment's position in the call and
+ * then what the kind's entry point says ("zkm_segments_calls_expand: segment 1: zkm_io_calls_counts: kinds: call 2: ..."): every refusal of the four
+ * entry points that concerns the lists (a NULL pointer with a nonzero count, a Keccak length that is not a positive multiple of 4, an
+ * unknown I/O kind, an instruction record outside the thirteen, ...); a meta, offset, kind, record or clock list in device memory; a
+ * call row whose clock lies outside the step list; two records on one clock; a group of `own` that the calls own; own.cpu_rows; raw_rows
+ * in device memory; nseg = 0 or NULL calls.  A refusal leaves the context usable, its live memory as it was, and no handle behind.
+ * Out of scope: nothing is fused into the builder (its kernels and its three host waits are untouched), calls and steps are not staged,
+ * the pool takes none, and the records are placed into the step list on the host (the builder walks it there).
+ * (The struct and the handle are tagged, not typedef'd: to the header-driven bindings a pointer to either is a plain address.) */
+#define ZKM_CALLS_COUNTS 11
+struct zkm_segment_calls {
+    zkm_cpu_steps steps;
+    uint64_t first_clock;
+    zkm_segment_ops own;
+    const uint32_t* extend_w16; const uint64_t* extend_meta; size_t nextend;                                /* zkm_sha_calls_witness */
+    const uint32_t* compress_hx; const uint32_t* compress_w; const uint64_t* compress_meta; size_t ncompress;
+    const uint8_t* keccak_inputs; const uint64_t* keccak_input_off; const uint64_t* keccak_meta; const uint64_t* keccak_digest_addrs;
+    size_t nkeccak;                                                                                         /* zkm_keccak_calls_witness */
+    const uint32_t* io_kinds; const uint8_t* io_data; const uint64_t* io_data_off; const uint64_t* io_meta; size_t nio;   /* zkm_io_calls_witness */
+    const zkm_cpu_step* insns; const uint64_t* insn_clocks; size_t ninsns;                                  /* zkm_insn_rows_witness */
+};
+struct zkm_expanded_calls;
+int zkm_segment_calls_steps(const struct zkm_segment_calls* calls, zkm_cpu_step* steps_out, size_t* counts_out, char** err);
+int zkm_segments_calls_expand(zkm_ctx* ctx, size_t nseg, const struct zkm_segment_calls* calls, struct zkm_expanded_calls** out, char** err);
+int zkm_expanded_calls_get(const struct zkm_expanded_calls* expanded, size_t segment, zkm_cpu_steps* steps_out, zkm_segment_ops* ops_out);
+void zkm_expanded_calls_free(struct zkm_expanded_calls* expanded);
+int zkm_segments_tables_calls(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
+                              const struct zkm_segment_calls* calls, unsigned* log_n_out, zkm_staged** out, char** err);
+int zkm_prove_segments_ops_calls(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
+                                 const struct zkm_segment_calls* calls, const uint64_t* const* public_values, const size_t* npublic,
+                                 uint64_t* const* proofs_out, size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
+
 /* ------------------------------------------------------------------ a memory image's hash pages, root and image id
  * What the emulator does at every segment split -- Memory::update_page_hash and Memory::compute_image_id (emulator/src/memory.rs:388-471,
  * with poseidon / hash_page / CONST_HASH_PAGES, :43-118, and alloc_hash_page, :378-386; called from split_segment, state.rs:1477-1530) --

@@ -17,10 +17,11 @@
 //!     segment's own RAW rows and patches the reserved steps; the segment is then proven with `prove_segments_ops_steps_raw`, its
 //!     `zkm_cpu_steps.raw_rows` pointing at `blocks.raw_rows` and its `zkm_segment_ops.arithmetic_ops` at `blocks.arithmetic_ops`.
 //! With this every instruction `decode` accepts has a device path: RAW rows remain for the bootstrap rows a caller hands over and for
-//! registers written outside an instruction.  A segment that also has precompile or I/O calls composes the expansions as
-//! `Context.calls_expand` of the Python binding does: one block of rows, the own rows, then the SHA calls', the Keccak calls', the I/O
-//! calls', then these (`own_raw` below then counts the calls' rows too); a segment whose `Traces` still hold arithmetic operations puts
-//! them in front of the generated ones in one device list.  This file shows the segment without calls and without own operations.
+//! registers written outside an instruction.  A segment that also has precompile or I/O calls does not compose the
+//! expansions itself: it hands this log and the calls' logs to `calls_hip.rs` (`SegmentCalls`, `prove_segments_ops_calls_raw`:
+//! zkm_prove_segments_ops_calls), and the library places the records and orders the rows -- the own rows, then the SHA calls', the
+//! Keccak calls', the I/O calls', then these -- and puts the arithmetic operations `Traces` still hold in front of the generated ones,
+//! for K segments in one set of launches.  `finish` below is the segment without calls and without own operations.
 //!
 //! Goes into the zkm-prover crate as `prover/src/insn_rows_hip.rs`, beside `cpu_steps_hip.rs`.  NOT COMPILED in the build image (no
 //! cargo / rustc there).

@@ -16,9 +16,10 @@
 //!   * at the end of the segment `finish` expands the calls into device memory behind the segment's own RAW rows and patches the reserved
 //!     steps; the segment is then proven with `prove_segments_ops_steps_raw`, its `zkm_cpu_steps.raw_rows` pointing at the block `finish`
 //!     returns.
-//! The SYSCALL row in front of a call is logged as today.  A segment that also has SHA or Keccak calls composes the expansions as
-//! `Context.calls_expand` of the Python binding does: one block of rows, the own rows, then the SHA calls', the Keccak calls', the I/O
-//! calls' (`own_raw` below then counts the SHA and Keccak rows too); this file shows the segment whose only calls are I/O calls.
+//! The SYSCALL row in front of a call is logged as today.  A segment that also has calls of another kind does not
+//! compose the expansions itself: it hands this log and the others to `calls_hip.rs` (`SegmentCalls`, `prove_segments_ops_calls_raw`:
+//! zkm_prove_segments_ops_calls), and the library places the records and orders the rows -- the own rows, then the SHA calls', the
+//! Keccak calls', the I/O calls' -- for K segments in one set of launches; `finish` below is the segment whose only calls are I/O calls.
 //!
 //! Goes into the zkm-prover crate as `prover/src/io_calls_hip.rs`, beside `cpu_steps_hip.rs`.  NOT COMPILED in the build image (no
 //! cargo / rustc there).

@@ -16,9 +16,10 @@
 //!     proven with `prove_segments_ops_steps_raw`, its `zkm_cpu_steps.raw_rows` and the memory / logic / Keccak lists of its
 //!     `zkm_segment_ops` pointing at the device blocks `finish` returns, and `keccak_sponge_*` at the log's own three lists (with the
 //!     operations segment_hip.rs packed for the calls that were not recorded, if any, appended by the caller).
-//! The SYSCALL row in front of a call is logged as today.  A segment that also has SHA calls composes the two expansions as
-//! `Context.calls_expand` of the Python binding does: one block a list, the own items, then the SHA calls', then the Keccak calls'
-//! (`own_raw` below counts the SHA rows); this file shows the Keccak-only segment.
+//! The SYSCALL row in front of a call is logged as today.  A segment that also has calls of another kind does not
+//! compose the expansions itself: it hands this log and the others to `calls_hip.rs` (`SegmentCalls`, `prove_segments_ops_calls_raw`:
+//! zkm_prove_segments_ops_calls), and the library places the records and orders every list -- the own items, then the SHA calls', then
+//! the Keccak calls' -- for K segments in one set of launches; `finish` below is the Keccak-only segment.
 //!
 //! Goes into the zkm-prover crate as `prover/src/keccak_calls_hip.rs`, beside `cpu_steps_hip.rs`.  NOT COMPILED in the build image (no
 //! cargo / rustc there).

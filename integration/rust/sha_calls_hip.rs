@@ -15,6 +15,9 @@
 //!     proven with `prove_segments_ops_steps_raw`, its `zkm_cpu_steps.raw_rows` and the memory / logic / ShaExtend lists of its
 //!     `zkm_segment_ops` pointing at the device blocks `finish` returns.
 //! The SYSCALL row in front of a call is logged as today.  SYSKECCAK calls: keccak_calls_hip.rs (the Poseidon sponge has no syscall).
+//! A segment that also has calls of another kind does not compose the expansions itself: it hands this log and the others to
+//! `calls_hip.rs` (`SegmentCalls`, `prove_segments_ops_calls_raw`: zkm_prove_segments_ops_calls), which expands K segments' calls in one
+//! set of launches; `finish` below is the segment whose only calls are SHA calls.
 //!
 //! Goes into the zkm-prover crate as `prover/src/sha_calls_hip.rs`, beside `cpu_steps_hip.rs`.  NOT COMPILED in the build image (no
 //! cargo / rustc there).

@@ -134,6 +134,21 @@ pub struct ZkmCpuSteps {
     pub steps: *const zkm_cpu_step, pub nsteps: usize, pub raw_rows: *const u64, pub nraw: usize,
 }
 pub type zkm_cpu_steps = ZkmCpuSteps;
+/// `struct zkm_segment_calls` (include/zkm_hip.h "K segments' calls expanded in one set of launches"): one segment as the emulator records
+/// it -- its step list with placeholders, its own operations, and the calls of the four kinds.  The header tags this struct and the
+/// handle below instead of typedef'ing them; the extern block passes pointers to them as plain addresses (`*const c_void`)
+#[repr(C)] #[derive(Clone, Copy, Debug)]
+pub struct ZkmSegmentCalls {
+    pub steps: zkm_cpu_steps, pub first_clock: u64, pub own: zkm_segment_ops,
+    pub extend_w16: *const u32, pub extend_meta: *const u64, pub nextend: usize,
+    pub compress_hx: *const u32, pub compress_w: *const u32, pub compress_meta: *const u64, pub ncompress: usize,
+    pub keccak_inputs: *const u8, pub keccak_input_off: *const u64, pub keccak_meta: *const u64, pub keccak_digest_addrs: *const u64,
+    pub nkeccak: usize,
+    pub io_kinds: *const u32, pub io_data: *const u8, pub io_data_off: *const u64, pub io_meta: *const u64, pub nio: usize,
+    pub insns: *const zkm_cpu_step, pub insn_clocks: *const u64, pub ninsns: usize,
+}
+pub enum ZkmExpandedCalls {}   // `struct zkm_expanded_calls`: opaque, only ever behind a pointer
+pub const ZKM_CALLS_COUNTS: usize = 11;
 pub const ZKM_STEP_BINARY_OP: u32 = 0; pub const ZKM_STEP_BINARY_IMM_OP: u32 = 1; pub const ZKM_STEP_LOGIC_OP: u32 = 2;
 pub const ZKM_STEP_LOGIC_IMM_OP: u32 = 3; pub const ZKM_STEP_SHIFT: u32 = 4; pub const ZKM_STEP_SHIFT_IMM: u32 = 5;
 pub const ZKM_STEP_BRANCH: u32 = 6; pub const ZKM_STEP_JUMPS: u32 = 7; pub const ZKM_STEP_JUMPI: u32 = 8; pub const ZKM_STEP_JUMPDIRECT: u32 = 9;
@@ -374,6 +389,18 @@ extern "C" {
                                err: *mut *mut c_char) -> c_int;
     pub fn zkm_insn_rows_witness(ctx: *mut zkm_ctx, insns: *const zkm_cpu_step, clocks: *const u64, ninsns: usize, raw_rows_out_dev: *mut u64,
                                  arithmetic_ops_out_dev: *mut u32, err: *mut *mut c_char) -> c_int;
+    // K segments' calls expanded in one set of launches: the host half, the expansion with its handle, and the two calls that run the
+    // builder behind it (calls: *const ZkmSegmentCalls, nseg of them; expanded / *out: *mut ZkmExpandedCalls)
+    pub fn zkm_segment_calls_steps(calls: *const c_void, steps_out: *mut zkm_cpu_step, counts_out: *mut usize, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_segments_calls_expand(ctx: *mut zkm_ctx, nseg: usize, calls: *const c_void, out: *mut *mut c_void, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_expanded_calls_get(expanded: *const c_void, segment: usize, steps_out: *mut zkm_cpu_steps, ops_out: *mut zkm_segment_ops) -> c_int;
+    pub fn zkm_expanded_calls_free(expanded: *mut c_void);
+    pub fn zkm_segments_tables_calls(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, images: *const zkm_boot_image,
+                                     calls: *const c_void, log_n_out: *mut c_uint, out: *mut *mut zkm_staged, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_prove_segments_ops_calls(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nseg: usize, images: *const zkm_boot_image,
+                                        calls: *const c_void, public_values: *const *const u64, npublic: *const usize,
+                                        proofs_out: *const *mut u64, proof_offsets_out: *mut usize, ctl_challenges_out: *const *mut u64,
+                                        err: *mut *mut c_char) -> c_int;
     // what the emulator hashes between two segments: hash pages, root and image id of a memory image
     pub fn zkm_image_hash_plan(dirty_index: *const u32, ndirty: usize, hash_index_out: *mut u32, capacity: usize) -> usize;
     pub fn zkm_image_hash(ctx: *mut zkm_ctx, r#in: *const zkm_image_pages, hash_words_out: *mut u32, page_hash_root_out: *mut u8,

@@ -294,6 +294,71 @@ def insn_rows_steps(records, raw_base=0):
     return steps
 
 
+CALLS_COUNTS = ("sha_rows", "keccak_rows", "io_rows", "insn_rows", "nraw", "memory_ops", "logic_ops", "arithmetic_ops", "sha_extend_rows",
+                "keccak_perms", "row_memory_ops")
+assert len(CALLS_COUNTS) == _H["CALLS_COUNTS"]
+
+
+class SegmentCallsStruct(C.Structure):
+    """struct zkm_segment_calls: one segment as the emulator records it (include/zkm_hip.h "K segments' calls expanded in one set of
+    launches")."""
+    _fields_ = [("steps", CpuStepsStruct), ("first_clock", C.c_uint64), ("own", SegmentOpsStruct)] + \
+               [(n, C.c_size_t if n.startswith("n") else C.c_void_p) for n in
+                ("extend_w16", "extend_meta", "nextend", "compress_hx", "compress_w", "compress_meta", "ncompress", "keccak_inputs",
+                 "keccak_input_off", "keccak_meta", "keccak_digest_addrs", "nkeccak", "io_kinds", "io_data", "io_data_off", "io_meta", "nio",
+                 "insns", "insn_clocks", "ninsns")]
+
+
+def abi_tagged_mirrors():
+    """Every tagged struct of include/zkm_hip.h (abi.tagged()) -> its ctypes mirror; tests/test_calls_entry_abi.py compares each with what
+    the C compiler says, as tests/test_abi.py does for abi_mirrors()."""
+    return {"zkm_segment_calls": SegmentCallsStruct}
+
+
+class SegmentCalls:
+    """One segment with its calls, for segment_calls_steps and Context.segments_calls_expand / segments_tables_calls /
+    prove_segments_ops_calls (include/zkm_hip.h struct zkm_segment_calls).  The arguments are Context.calls_expand's: steps, a CpuSteps
+    with the segment's own RAW rows (host memory) and a placeholder at every row of a call; extend = (w16, meta), compress = (hx, w,
+    meta), keccak = (inputs, input_off, meta, digest_addrs), io = (kinds, data, data_off, meta), insns = (records, clocks); memory_ops /
+    logic_ops / arithmetic_ops / keccak_perms = (inputs, timestamps): the segment's own operations; groups: the other groups of
+    SegmentOps, passed on."""
+
+    def __init__(self, steps, first_clock=0, extend=None, compress=None, keccak=None, memory_ops=None, logic_ops=None, keccak_perms=None,
+                 io=None, insns=None, arithmetic_ops=None, **groups):
+        self.steps, self.first_clock = steps, int(first_clock)
+        self.own = SegmentOps(None, memory_ops, arithmetic_ops=arithmetic_ops, logic_ops=logic_ops, keccak=keccak_perms, **groups)
+        e, c, ne, nc = Context._sha_lists(extend, compress)
+        k, nk = Context._keccak_lists(keccak)
+        i, ni = _io_lists(io)
+        q, nq = _insn_lists(insns)
+        self.lists = {}
+        for names, vals in ((("extend_w16", "extend_meta"), e), (("compress_hx", "compress_w", "compress_meta"), c),
+                            (("keccak_inputs", "keccak_input_off", "keccak_meta", "keccak_digest_addrs"), k),
+                            (("io_kinds", "io_data", "io_data_off", "io_meta"), i), (("insns", "insn_clocks"), q)):
+            if vals is not None:
+                self.lists.update(zip(names, vals))
+        self.counts = {"nextend": ne, "ncompress": nc, "nkeccak": nk, "nio": ni, "ninsns": nq}
+
+    def struct(self):
+        st = SegmentCallsStruct()
+        st.steps, st.first_clock, st.own = self.steps.struct(), self.first_clock, self.own.struct()
+        for name, v in self.lists.items():
+            setattr(st, name, v.ptr if isinstance(v, DeviceBuffer) else (v.ctypes.data if v.size else None))
+        for name, n in self.counts.items():
+            setattr(st, name, n)
+        return st
+
+
+def segment_calls_steps(calls):
+    """zkm_segment_calls_steps on a SegmentCalls: the host half of the expansion; needs no GPU.  Returns (the patched step list, a
+    CPU_STEP_DT array with every call's RAW record at clock - first_clock; {name: count} for CALLS_COUNTS).  Every refusal raises
+    ZkmError."""
+    st, err = calls.struct(), C.c_char_p()
+    steps, counts = np.zeros(calls.steps.steps.size, dtype=CPU_STEP_DT), (C.c_size_t * len(CALLS_COUNTS))()
+    _check(load().zkm_segment_calls_steps(C.addressof(st), steps.ctypes.data if steps.size else None, counts, C.byref(err)), err)
+    return steps, dict(zip(CALLS_COUNTS, (int(x) for x in counts)))
+
+
 class CtlLocation(C.Structure):
     """zkm_ctl_location: one occurrence of a reported tuple (side of the lookup, index of the table, row)."""
     _fields_ = [("side", C.c_uint32), ("table", C.c_uint32), ("row", C.c_uint64)]
@@ -702,6 +767,85 @@ class StagedOps:
             self.ctx._staged.discard(self)
             if self.ctx.h:
                 self.ctx.L.zkm_staged_ops_free(h)
+
+
+class _ExpandedSteps:
+    """A segment's patched step list as ExpandedCalls hands it out: .steps a numpy copy, raw_rows on the device (the handle's)."""
+
+    def __init__(self, st, owner):
+        self._st, self._owner, self.nraw, self.raw_rows_ptr = st, owner, st.nraw, st.raw_rows
+        self.steps = np.ctypeslib.as_array(C.cast(st.steps, C.POINTER(C.c_uint8)), (st.nsteps * 48,)).view(CPU_STEP_DT).copy() if st.nsteps \
+            else np.zeros(0, dtype=CPU_STEP_DT)
+
+    def struct(self):
+        return self._st
+
+
+class ExpandedCalls:
+    """struct zkm_expanded_calls: the expanded calls of K segments (Context.segments_calls_expand).  segment(s) gives what
+    segments_tables_steps / prove_segments_ops_steps take for segment s; the SegmentCalls' lists must stay as they are until free().
+    Freed like a StagedTrace when dropped, at the end of a `with` block or by Context.close()."""
+
+    def __init__(self, ctx, handle, calls):
+        self.ctx, self.h, self.calls = ctx, handle, list(calls)
+        ctx._staged.add(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return len(self.calls)
+
+    def structs(self, s):
+        """(CpuStepsStruct, SegmentOpsStruct) of segment s, as zkm_expanded_calls_get fills them."""
+        st, ops = CpuStepsStruct(), SegmentOpsStruct()
+        if not self.h or self.ctx.L.zkm_expanded_calls_get(self.h, s, C.byref(st), C.byref(ops)) != 0:
+            raise ZkmError("zkm_expanded_calls_get: freed handle, or no segment %d" % s)
+        return st, ops
+
+    def segment(self, s):
+        """(steps, ops) of segment s for segments_tables_steps / prove_segments_ops_steps: device pointers the handle owns."""
+        st, o = self.structs(s)
+        ops = SegmentOps.__new__(SegmentOps)
+        ops.lists, ops.counts, ops._staged_struct, ops._owner = {}, {}, o, self
+        return _ExpandedSteps(st, self), ops
+
+    def download(self, s):
+        """Segment s's outputs as numpy arrays, for comparisons: steps, nraw, raw_rows (nraw x 259) and every list of the operations that
+        lies in device memory, under its zkm_segment_ops name; "counts": every count of the operations."""
+        st, o = self.structs(s)
+
+        def down(ptr, n, dtype, shape):
+            out = np.zeros(n, dtype=dtype)
+            if n:
+                err = C.c_char_p()
+                _check(self.ctx.L.zkm_dev_download(self.ctx.h, out.ctypes.data, ptr, out.nbytes, C.byref(err)), err)
+            return out.reshape(shape)
+        got = {"steps": _ExpandedSteps(st, self).steps, "nraw": st.nraw, "raw_rows": down(st.raw_rows, st.nraw * 259, np.uint64, (-1, 259)),
+               "memory_ops": down(o.memory_ops, o.nmemory * 6, np.uint64, (-1, 6)), "logic_ops": down(o.logic_ops, o.nlogic * 3, np.uint32, (-1, 3)),
+               "keccak_inputs": down(o.keccak_inputs, o.nkeccak * 25, np.uint64, (-1, 25)), "keccak_timestamps": down(o.keccak_timestamps, o.nkeccak, np.uint64, (-1,)),
+               "sha_extend_inputs": down(o.sha_extend_inputs, o.nsha_extend * 16, np.uint8, (-1, 16)),
+               "sha_extend_timestamps": down(o.sha_extend_timestamps, o.nsha_extend, np.uint64, (-1,)),
+               "counts": {count: getattr(o, count) for _, _, count in SEGMENT_OPS_GROUPS}}
+        if self.calls[s].counts["ninsns"]:
+            got["arithmetic_ops"] = down(o.arithmetic_ops, o.narithmetic * 3, np.uint32, (-1, 3))
+        return got
+
+    def free(self):
+        if self.h:
+            h, self.h = self.h, None
+            self.ctx._staged.discard(self)
+            if self.ctx.h:
+                self.ctx.L.zkm_expanded_calls_free(h)
 
 
 class _marshal_ops:
@@ -1621,6 +1765,48 @@ class Context:
         if nq:
             ops.counts["narithmetic"] = own_arith.size // 3 + qarith
         return CpuSteps(patched, bufs[0] if bufs[0] is not None else None, nraw=steps.nraw + rows + krows + irows + nq), ops
+
+    # ---- K segments' calls in one set of launches (include/zkm_hip.h "K segments' calls expanded in one set of launches")
+    @staticmethod
+    def _calls_array(calls_list):
+        structs = [q.struct() for q in calls_list]
+        return (SegmentCallsStruct * max(len(structs), 1))(*structs)
+
+    def segments_calls_expand(self, calls_list):
+        """zkm_segments_calls_expand: the calls of all the SegmentCalls expanded -- per 32 segments one scratch block, at most one launch per
+        kind and one host wait.  Returns an ExpandedCalls; every word is what calls_expand gives for that segment alone."""
+        arr, h, err = self._calls_array(calls_list), C.c_void_p(), C.c_char_p()
+        _check(self.L.zkm_segments_calls_expand(self.h, len(calls_list), C.addressof(arr), C.byref(h), C.byref(err)), err)
+        return ExpandedCalls(self, h, calls_list)
+
+    def segments_tables_calls(self, calls_list, images=None, cfg=None, sizing=False):
+        """zkm_segments_tables_calls: segments_calls_expand, segments_tables_steps on its outputs, the free.  Returns as
+        segments_tables_steps."""
+        cfg = cfg or self.standard_config()
+        K = len(calls_list)
+        assert images is None or len(images) == K, "one image per segment"
+        im = (BootImageStruct * max(K, 1))(*[i.struct() for i in images]) if images is not None else None
+        arr = self._calls_array(calls_list)
+        lg, hs, err = (C.c_uint * (12 * max(K, 1)))(), (C.c_void_p * max(K, 1))(), C.c_char_p()
+        _check(self.L.zkm_segments_tables_calls(self.h, C.byref(cfg), K, im, C.addressof(arr), lg, None if sizing else hs, C.byref(err)), err)
+        if sizing:
+            return [list(lg[12 * s:12 * s + 12]) for s in range(K)]
+        return [(StagedTrace(self, C.c_void_p(hs[s]), 0), list(lg[12 * s:12 * s + 12])) for s in range(K)]
+
+    def prove_segments_ops_calls(self, calls_list, images=None, public_values=None, cfg=None, sizes=None):
+        """zkm_prove_segments_ops_calls: segments_calls_expand, prove_segments_ops_steps on its outputs, the free.  sizes: as
+        prove_segments_ops takes them (the sizing call, which expands the calls too, is skipped)."""
+        cfg = cfg or self.standard_config()
+        m, err = _marshal_ops([q.own for q in calls_list], public_values, cfg, images), C.c_char_p()
+        im = m.im if images is not None else None
+        arr = self._calls_array(calls_list)
+        if sizes is None:
+            _check(self.L.zkm_prove_segments_ops_calls(self.h, C.byref(cfg), m.K, im, C.addressof(arr), m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
+        else:
+            m.offs[:] = [x for o in sizes for x in o]
+        m.alloc()
+        _check(self.L.zkm_prove_segments_ops_calls(self.h, C.byref(cfg), m.K, im, C.addressof(arr), m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
+        return m.results()
 
     def stage_segment_ops(self, ops):
         """zkm_segment_ops_stage: queue the upload of a segment's lists behind the context's current work and return at once.  The

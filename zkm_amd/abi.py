@@ -18,6 +18,8 @@ _STATEMENT = re.compile(r"""\s*(?:
     | extern\s+"C"\s*\{ | \}                                                      # the C++ guard's braces
     | typedef\s+struct\s+(?P<opaque>\w+)\s+(?P=opaque)\s*;                        # an opaque handle
     | typedef\s+struct\s*(?P<tag>\w*)\s*\{(?P<body>[^{}]*)\}\s*(?P<struct>\w+)\s*;
+    | struct\s+(?P<tagged>zkm_\w+)\s*\{(?P<tbody>[^{}]*)\}\s*;                  # a tagged struct (no typedef): `struct zkm_x` in prototypes
+    | struct\s+(?P<handle>zkm_\w+)\s*;                                          # a tagged handle that is only declared
     | (?P<ret>[\w\s*]+?)\b(?P<fn>zkm_\w+)\s*\((?P<params>[^()]*)\)\s*;            # a prototype
     )""", re.X)
 
@@ -36,11 +38,20 @@ def _declarator(text, where):
     return _type(m.group(1)), m.group(2), m.group(3)
 
 
+def _fields(body, where):
+    """The field names of a struct's body, in order."""
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        first, *rest = decl.split(",")
+        fields += [_declarator(first, where)[1]] + [_declarator(r, where)[1] for r in rest]
+    return fields
+
+
 @functools.lru_cache(maxsize=None)
 def _parse():
     raw = open(HEADER).read()
     text = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), raw, flags=re.S)   # comments -> blanks: lines keep their numbers
-    protos, structs, opaque, consts = [], {}, [], {}
+    protos, structs, opaque, consts, tagged, handles = [], {}, [], {}, {}, []
     pos, end = 0, len(text.rstrip())
     while pos < end:
         m = _STATEMENT.match(text, pos)
@@ -58,17 +69,23 @@ def _parse():
         elif m.group("struct"):
             if m.group("tag") not in ("", m.group("struct")):
                 raise ZkmError("%s: struct tag %s differs from its typedef %s" % (where, m.group("tag"), m.group("struct")))
-            fields = []
-            for decl in filter(None, (d.strip() for d in m.group("body").split(";"))):
-                first, *rest = decl.split(",")
-                fields += [_declarator(first, where)[1]] + [_declarator(r, where)[1] for r in rest]
-            structs[m.group("struct")] = fields
+            structs[m.group("struct")] = _fields(m.group("body"), where)
+        elif m.group("tagged"):
+            tagged[m.group("tagged")] = _fields(m.group("tbody"), where)
+        elif m.group("handle"):
+            handles.append(m.group("handle"))
         elif m.group("fn"):
-            params = [] if m.group("params").strip() == "void" else [_declarator(p, where) for p in m.group("params").split(",")]
+            # a pointer to a tagged struct or handle is a plain address to the bindings: `struct zkm_x` reads as `void`
+            def address(t):
+                if t.group(1) not in tagged and t.group(1) not in handles:
+                    raise ZkmError("%s: %s names struct %s before its declaration" % (where, m.group("fn"), t.group(1)))
+                return "void"
+            plain = re.sub(r"\bstruct\s+(\w+)", address, m.group("params"))
+            params = [] if plain.strip() == "void" else [_declarator(p, where) for p in plain.split(",")]
             if any(not ty for ty, _, _ in params):
                 raise ZkmError("%s: %s has a parameter without a type or a name" % (where, m.group("fn")))
             protos.append((m.group("fn"), _type(m.group("ret")), [(ty + "*" if arr else ty, name) for ty, name, arr in params]))
-    return protos, structs, opaque, consts
+    return protos, structs, opaque, consts, tagged, handles
 
 
 def prototypes():
@@ -86,15 +103,28 @@ def opaque():
     return _parse()[2]
 
 
+def tagged():
+    """{struct: [field names in order]} of every `struct zkm_x { ... };` (tagged, no typedef: prototypes spell it `struct zkm_x`, which
+    prototypes() reports as `void` -- to the bindings a pointer to one is a plain address; tests/test_calls_entry_abi.py locks them)."""
+    return _parse()[4]
+
+
+def tagged_handles():
+    """The tagged handles that are only ever declared (`struct zkm_x;`); `void` in prototypes() like the tagged structs."""
+    return _parse()[5]
+
+
 def constants(prefix=""):
     """{name: value} of every `#define ZKM_* <integer>`; with a prefix, the names that begin with it, without it."""
     return {k[len(prefix):]: v for k, v in _parse()[3].items() if k.startswith(prefix)}
 
 
-def layout_probe_source():
-    """A C99 program that prints {"struct": {"size", "align", "fields": [[name, offset, size]]}} for every struct of the header, as JSON."""
+def layout_probe_source(of_tagged=False):
+    """A C99 program that prints {"struct": {"size", "align", "fields": [[name, offset, size]]}} for every struct of the header (of_tagged:
+    for every tagged struct, under its tag), as JSON."""
     out = ["#include <stddef.h>", "#include <stdio.h>", '#include "%s"' % HEADER, "int main(void) {", '    printf("{");']
-    for i, (name, fields) in enumerate(structs().items()):
+    for i, (name, fields) in enumerate((tagged() if of_tagged else structs()).items()):
+        name = "struct " + name if of_tagged else name
         out.append('    printf("%s\\n  \\"%s\\": {\\"size\\": %%zu, \\"align\\": %%zu, \\"fields\\": [", sizeof(%s), offsetof(struct { char c; %s t; }, t));'
                    % ("," if i else "", name, name, name))
         out += ['    printf("%s[\\"%s\\", %%zu, %%zu]", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (", " if k else "", f, name, f, name, f)

@@ -9,11 +9,14 @@
 // zkm_insn_rows_steps, the two counts, each workgroup's base in the arithmetic list); the kernel runs it with a sink that writes an LDS
 // row and the operation -- so masks, offsets and cells agree by construction.
 //
-// k_insn_rows: ONE launch, a workgroup of 256 threads for ROWS_PER_WG consecutive records.  All lanes zero the workgroup's LDS block
-// (2,072 bytes a row); the first ROWS_PER_WG lanes load their record (three 16-byte loads), find their slot in the arithmetic list (the
-// workgroup's uploaded base + a ballot over the lanes in front) and build their row in LDS through expand; then all lanes stream the
-// block out word by word, adjacent lanes on adjacent words with 8-byte stores.  Every word is written exactly once, so no zero-fill
-// pass comes in front; the kernel's floor is the 2,072 bytes a row it has to write.
+// k_insn_rows: ONE launch for the records of K segments (the segment is blockIdx.z; its descriptor is read from device memory, where it
+// went up with the lists as the bootstrap's do -- a uniform read; zkm_insn_rows_witness is the K = 1 case), a workgroup of 256 threads
+// for ROWS_PER_WG consecutive records of one segment.  All lanes zero the workgroup's LDS block (2,072 bytes a row); the first
+// ROWS_PER_WG lanes load their record (three 16-byte loads), find their slot in the arithmetic list (the workgroup's uploaded base + a
+// ballot over the lanes in front) and build their row in LDS through expand; then all lanes stream the block out word by word, adjacent
+// lanes on adjacent words with 8-byte stores.  Every word is written exactly once, so no zero-fill pass comes in front; the kernel's
+// floor is the 2,072 bytes a row it has to write.
+#include <array>
 #include <vector>
 
 #include "cpu_steps_dev.h"
@@ -182,6 +185,7 @@ struct insn_rows_args {
     uint64_t* rows;
     uint32_t* arith;             // null: no record pushes an operation
     uint64_t ninsns;
+    uint32_t nwg;                // the segment's own extent of the grid
 };
 
 // the writing sink: a row in LDS (zeroed in front) and the record's slot in the arithmetic list
@@ -198,8 +202,10 @@ struct lds_sink {
     }
 };
 
-__global__ __launch_bounds__(THREADS) void k_insn_rows(insn_rows_args A) {
+__global__ __launch_bounds__(THREADS) void k_insn_rows(const insn_rows_args* __restrict__ segs) {
     __shared__ uint64_t block[ROWS_PER_WG * CPU_W];
+    const insn_rows_args A = zkm_seg_desc(segs);   // (uniform: scalar loads)
+    if (blockIdx.x >= A.nwg) return;
     const unsigned t = threadIdx.x;
     const uint64_t row0 = (uint64_t)blockIdx.x * ROWS_PER_WG;
     const unsigned nrows = A.ninsns - row0 < ROWS_PER_WG ? (unsigned)(A.ninsns - row0) : ROWS_PER_WG;
@@ -283,7 +289,51 @@ void check_clocks(const uint64_t* clocks, size_t n) {
         if (clocks[k] >= LIM) throw std::runtime_error("record " + dec(k) + ": clock " + dec(clocks[k]) + " does not fit in 32 bits");
 }
 
+size_t wgs(size_t n) { return (n + ROWS_PER_WG - 1) / ROWS_PER_WG; }
+// where a job's three uploads lie behind the K descriptors
+size_t layout(const zkm_insn_job* j, size_t nseg, std::array<size_t, 3>* at) {
+    size_t total = up256(nseg * sizeof(insn_rows_args));
+    for (size_t s = 0; s < nseg; s++) {
+        const size_t bytes[3] = {j[s].n * sizeof(zkm_cpu_step), j[s].n * 8, wgs(j[s].n) * 4};
+        for (int i = 0; i < 3; i++) {
+            if (at) at[s][i] = total;
+            total += up256(bytes[i]);
+        }
+    }
+    return total;
+}
+
 }  // namespace
+
+void zkm_insn_rows_check(zkm_insn_job& j) {
+    const totals sum = check_insns(j.insns, j.n, nullptr, &j.base);
+    check_clocks(j.clocks, j.n);
+    if (j.n > LIM) throw std::runtime_error(dec(j.n) + " rows: a RAW index does not fit in 32 bits");
+    j.nmem = sum.mem;
+    j.narith = sum.arith;
+}
+size_t zkm_insn_rows_scratch(const zkm_insn_job* j, size_t nseg) { return layout(j, nseg, nullptr); }
+void zkm_insn_rows_launch(zkm_ctx* c, const zkm_insn_job* j, size_t nseg, char* sb, zkm_calls_hold& hold) {
+    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_insn_rows_launch: segment count out of range");
+    std::vector<std::array<size_t, 3>> at(nseg);
+    layout(j, nseg, at.data());
+    insn_rows_args* d = hold.make<insn_rows_args>(nseg);
+    size_t grid = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        const void* in[3] = {j[s].insns, j[s].clocks, j[s].base.data()};
+        const size_t bytes[3] = {j[s].n * sizeof(zkm_cpu_step), j[s].n * 8, j[s].base.size() * 4};
+        for (int i = 0; i < 3; i++)
+            if (bytes[i]) ZKM_HIP_CHECK(hipMemcpyAsync(sb + at[s][i], in[i], bytes[i], hipMemcpyHostToDevice, c->stream));
+        d[s] = insn_rows_args{(const zkm_cpu_step*)(sb + at[s][0]), (const uint64_t*)(sb + at[s][1]), (const uint32_t*)(sb + at[s][2]), j[s].rows,
+                              j[s].narith ? j[s].arith : nullptr, j[s].n, (uint32_t)wgs(j[s].n)};
+        grid = std::max(grid, wgs(j[s].n));
+    }
+    if (!grid) return;
+    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(insn_rows_args), hipMemcpyHostToDevice, c->stream));
+    zkm_prof_scope ps(c, "insn_rows/rows");
+    hipLaunchKernelGGL(k_insn_rows, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(THREADS), 0, c->stream, (const insn_rows_args*)sb);
+    ZKM_HIP_CHECK(hipGetLastError());
+}
 
 extern "C" {
 
@@ -326,11 +376,12 @@ int zkm_insn_rows_witness(zkm_ctx* c, const zkm_cpu_step* insns, const uint64_t*
     return zkm_api("zkm_insn_rows_witness", err, [&] {
         auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_insn_rows_witness: " + m); };
         // every refusal first, on the host: the records, the clocks, the outputs, then the context
-        std::vector<uint32_t> base;
-        totals sum;
+        zkm_insn_job j;
+        j.insns = insns, j.clocks = clocks, j.n = ninsns, j.rows = raw_rows_out_dev, j.arith = arithmetic_ops_out_dev;
         try {
-            sum = check_insns(insns, ninsns, nullptr, &base);
+            const totals sum = check_insns(insns, ninsns, nullptr, &j.base);
             check_clocks(clocks, ninsns);
+            j.nmem = sum.mem, j.narith = sum.arith;
         } catch (const std::exception& e) {
             refuse(e.what());
         }
@@ -340,29 +391,16 @@ int zkm_insn_rows_witness(zkm_ctx* c, const zkm_cpu_step* insns, const uint64_t*
         }
         if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(ninsns) + " rows to write");
         if ((uintptr_t)raw_rows_out_dev & 7) refuse("raw_rows_out_dev is not aligned to its words (8 bytes)");
-        if (sum.arith && !arithmetic_ops_out_dev) refuse("arithmetic_ops_out_dev: NULL with " + dec(sum.arith) + " operations to write");
+        if (j.narith && !arithmetic_ops_out_dev) refuse("arithmetic_ops_out_dev: NULL with " + dec(j.narith) + " operations to write");
         if ((uintptr_t)arithmetic_ops_out_dev & 3) refuse("arithmetic_ops_out_dev is not aligned to its words (4 bytes)");
         if (ninsns > LIM) refuse(dec(ninsns) + " rows: a RAW index does not fit in 32 bits");
         if (!c) refuse("null argument");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        // the records, the clocks and the workgroups' bases go up in one block
-        const struct { const void* p; size_t bytes; } in[3] = {{insns, ninsns * sizeof(zkm_cpu_step)}, {clocks, ninsns * 8}, {base.data(), base.size() * 4}};
-        size_t at[3], total = 0;
-        for (int i = 0; i < 3; i++) {
-            at[i] = total;
-            total += up256(in[i].bytes);
-        }
-        zkm_scratch block(c, total);
-        char* sb = block.as<char>();
-        for (int i = 0; i < 3; i++) ZKM_HIP_CHECK(hipMemcpyAsync(sb + at[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
-        const insn_rows_args A{(const zkm_cpu_step*)(sb + at[0]), (const uint64_t*)(sb + at[1]), (const uint32_t*)(sb + at[2]), raw_rows_out_dev,
-                               sum.arith ? arithmetic_ops_out_dev : nullptr, ninsns};
-        {
-            zkm_prof_scope ps(c, "insn_rows/rows");
-            hipLaunchKernelGGL(k_insn_rows, dim3((unsigned)base.size()), dim3(THREADS), 0, c->stream, A);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        c->sync();   // (the block, `base` and the caller's lists are in use until here)
+        // the K = 1 case of the segments' launch: the descriptor, the records, the clocks and the workgroups' bases go up in one block
+        zkm_calls_hold hold;   // (declared first: it outlives the block's wait for the stream when an exception unwinds)
+        zkm_scratch block(c, zkm_insn_rows_scratch(&j, 1));
+        zkm_insn_rows_launch(c, &j, 1, block.as<char>(), hold);
+        c->sync();   // (the block, the job and the caller's lists are in use until here)
     });
 }
 

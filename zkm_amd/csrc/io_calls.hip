@@ -8,11 +8,14 @@
 // is divided by ROW: the host's walk computes the calls' row offsets and uploads them, and a workgroup finds the call of each of its rows
 // by a search over them.
 //
-// k_io_calls: ONE launch, a workgroup of 256 threads for ROWS_PER_WG consecutive rows.  The first ROWS_PER_WG lanes search the row
-// offsets and put what their row needs (the call's kind, bytes, meta; the row's position, clock and channel count) into LDS.  Then all
-// lanes walk the workgroup's span of the row-major block word by word, adjacent lanes on adjacent words with 8-byte stores: zeros, the
-// clock, and the channel cells computed in place.  Every word is written, so no zero-fill pass comes in front; the kernel is write-only
-// but for the calls' bytes, and its floor is the 2,072 bytes a row it has to write.
+// k_io_calls: ONE launch for the calls of K segments (the segment is blockIdx.z; its descriptor is read from device memory, where it went
+// up with the lists as the bootstrap's do -- a uniform read; zkm_io_calls_witness is the K = 1 case), a workgroup of 256 threads for
+// ROWS_PER_WG consecutive rows of one segment.  The first ROWS_PER_WG lanes search the row offsets and put what their row needs (the
+// call's kind, bytes, meta; the row's position, clock and channel count) into LDS.  Then all lanes walk the workgroup's span of the
+// row-major block word by word, adjacent lanes on adjacent words with 8-byte stores: zeros, the clock, and the channel cells computed in
+// place.  Every word is written, so no zero-fill pass comes in front; the kernel is write-only but for the calls' bytes, and its floor is
+// the 2,072 bytes a row it has to write.
+#include <array>
 #include <vector>
 
 #include "cpu_steps_dev.h"
@@ -67,6 +70,7 @@ struct io_calls_args {
     uint64_t* rows;
     uint64_t nrows;
     uint32_t ncalls;
+    uint32_t nwg;               // the segment's own extent of the grid
 };
 
 // what a row needs of its call
@@ -107,8 +111,10 @@ __device__ __forceinline__ uint64_t chan_cell(const row_info& r, unsigned i, uns
     return be_word(r.bytes, r.L, 4 * w);
 }
 
-__global__ __launch_bounds__(THREADS) void k_io_calls(io_calls_args A) {
+__global__ __launch_bounds__(THREADS) void k_io_calls(const io_calls_args* __restrict__ segs) {
     __shared__ row_info info[ROWS_PER_WG];
+    const io_calls_args A = zkm_seg_desc(segs);   // (uniform: scalar loads)
+    if (blockIdx.x >= A.nwg) return;
     const unsigned t = threadIdx.x;
     const uint64_t row0 = (uint64_t)blockIdx.x * ROWS_PER_WG;
     const unsigned nrows = A.nrows - row0 < ROWS_PER_WG ? (unsigned)(A.nrows - row0) : ROWS_PER_WG;
@@ -208,7 +214,77 @@ void check_meta(const uint32_t* kinds, const uint64_t* off, const uint64_t* meta
 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+size_t wgs(size_t rows) { return (rows + ROWS_PER_WG - 1) / ROWS_PER_WG; }
+// a job's five lists: the kinds, the bytes, the offsets, the meta, the row offsets; which of them go up, and where behind the K descriptors
+struct list { const void* p; size_t bytes; bool up; };
+std::array<list, 5> lists(const zkm_io_job& j) {
+    const size_t n = j.n, first = n ? j.off[0] : 0, nbytes = n ? j.off[n] - first : 0;
+    const bool data_up = !zkm_is_device_ptr(j.data);
+    return {{{j.kinds, 4 * n, true},
+             {data_up && j.data ? j.data + first : j.data, nbytes, data_up},
+             {j.off_up.data(), n ? 8 * (n + 1) : 0, true},
+             {j.meta, 32 * n, !zkm_is_device_ptr(j.meta)},
+             {j.row_off.data(), n ? 8 * (n + 1) : 0, true}}};
+}
+// the bytes go up from the first call's offset on, so the offsets that go up count from there
+void rebase_offsets(zkm_io_job& j) {
+    j.off_up.assign(j.off, j.off + j.n + 1);
+    if (!zkm_is_device_ptr(j.data))
+        for (uint64_t& o : j.off_up) o -= j.off[0];
+}
+size_t layout(const zkm_io_job* j, size_t nseg, std::array<size_t, 5>* at) {
+    size_t total = up256(nseg * sizeof(io_calls_args));
+    for (size_t s = 0; s < nseg; s++) {
+        const auto in = lists(j[s]);
+        for (int i = 0; i < 5; i++) {
+            if (at) at[s][i] = total;
+            if (in[i].up) total += up256(in[i].bytes);
+        }
+    }
+    return total;
+}
+
 }  // namespace
+
+void zkm_io_calls_check(zkm_io_job& j) {
+    const totals sum = check_calls(j.kinds, j.off, j.n, &j.row_off);
+    check_meta(j.kinds, j.off, j.meta, j.n);
+    j.nrows = sum.rows, j.nmem = sum.mem;
+    j.off_up.clear();
+    if (j.n == 0) return;
+    const size_t first = j.off[0], nbytes = j.off[j.n] - first;
+    if (nbytes && !j.data) throw std::runtime_error("data: NULL with " + dec(nbytes) + " bytes to read");
+    if (sum.rows > LIM) throw std::runtime_error(dec(sum.rows) + " rows: a RAW index does not fit in 32 bits");
+    if (j.n > 0x7FFFFFFF) throw std::runtime_error("2^31 or more calls");
+    rebase_offsets(j);
+}
+size_t zkm_io_calls_scratch(const zkm_io_job* j, size_t nseg) { return layout(j, nseg, nullptr); }
+void zkm_io_calls_launch(zkm_ctx* c, const zkm_io_job* j, size_t nseg, char* sb, zkm_calls_hold& hold) {
+    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_io_calls_launch: segment count out of range");
+    std::vector<std::array<size_t, 5>> at(nseg);
+    layout(j, nseg, at.data());
+    io_calls_args* d = hold.make<io_calls_args>(nseg);
+    size_t grid = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        const auto in = lists(j[s]);
+        const void* dev[5];
+        for (int i = 0; i < 5; i++) {
+            dev[i] = in[i].p;
+            if (in[i].up) {
+                dev[i] = sb + at[s][i];
+                if (in[i].bytes) ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        d[s] = io_calls_args{(const uint32_t*)dev[0], (const uint8_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const uint64_t*)dev[4],
+                             j[s].rows, j[s].nrows, (uint32_t)j[s].n, (uint32_t)wgs(j[s].nrows)};
+        grid = std::max(grid, wgs(j[s].nrows));
+    }
+    if (!grid) return;
+    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(io_calls_args), hipMemcpyHostToDevice, c->stream));
+    zkm_prof_scope ps(c, "io_calls/rows");
+    hipLaunchKernelGGL(k_io_calls, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(THREADS), 0, c->stream, (const io_calls_args*)sb);
+    ZKM_HIP_CHECK(hipGetLastError());
+}
 
 extern "C" {
 
@@ -259,11 +335,12 @@ int zkm_io_calls_witness(zkm_ctx* c, const uint32_t* kinds, const uint8_t* data,
     return zkm_api("zkm_io_calls_witness", err, [&] {
         auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_io_calls_witness: " + m); };
         // every refusal first, on the host: the lists, the output, then the context
-        std::vector<uint64_t> row_off;
-        totals sum;
+        zkm_io_job j;
+        j.kinds = kinds, j.data = data, j.off = data_off, j.meta = meta, j.n = ncalls, j.rows = raw_rows_out_dev;
         try {
-            sum = check_calls(kinds, data_off, ncalls, &row_off);
+            const totals sum = check_calls(kinds, data_off, ncalls, &j.row_off);
             check_meta(kinds, data_off, meta, ncalls);
+            j.nrows = sum.rows, j.nmem = sum.mem;
         } catch (const std::exception& e) {
             refuse(e.what());
         }
@@ -273,45 +350,18 @@ int zkm_io_calls_witness(zkm_ctx* c, const uint32_t* kinds, const uint8_t* data,
         }
         const size_t first = data_off[0], nbytes = data_off[ncalls] - first;
         if (nbytes && !data) refuse("data: NULL with " + dec(nbytes) + " bytes to read");
-        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(sum.rows) + " rows to write");
+        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(j.nrows) + " rows to write");
         if ((uintptr_t)raw_rows_out_dev & 7) refuse("raw_rows_out_dev is not aligned to its words (8 bytes)");
-        if (sum.rows > LIM) refuse(dec(sum.rows) + " rows: a RAW index does not fit in 32 bits");
+        if (j.nrows > LIM) refuse(dec(j.nrows) + " rows: a RAW index does not fit in 32 bits");
         if (ncalls > 0x7FFFFFFF) refuse("2^31 or more calls");
         if (!c) refuse("null argument");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        // the lists the host holds go up in one block, with the row offsets; the bytes from the first call's offset on, so the offsets
-        // that go up count from there
-        const bool data_up = !zkm_is_device_ptr(data);
-        std::vector<uint64_t> off(data_off, data_off + ncalls + 1);
-        if (data_up)
-            for (uint64_t& o : off) o -= first;
-        const struct { const void* p; size_t bytes; bool up; } in[5] = {{kinds, 4 * ncalls, true},
-                                                                        {data_up && data ? data + first : data, nbytes, data_up},
-                                                                        {off.data(), 8 * (ncalls + 1), true},
-                                                                        {meta, 32 * ncalls, !zkm_is_device_ptr(meta)},
-                                                                        {row_off.data(), 8 * (ncalls + 1), true}};
-        const void* dev[5];
-        size_t at[5], total = 0;
-        for (int i = 0; i < 5; i++) {
-            at[i] = total;
-            if (in[i].up) total += up256(in[i].bytes);
-        }
-        zkm_scratch block(c, total);
-        for (int i = 0; i < 5; i++) {
-            dev[i] = in[i].p;
-            if (in[i].up) {
-                dev[i] = block.as<char>() + at[i];
-                if (in[i].bytes) ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-        const io_calls_args A{(const uint32_t*)dev[0], (const uint8_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const uint64_t*)dev[4],
-                              raw_rows_out_dev, sum.rows, (uint32_t)ncalls};
-        {
-            zkm_prof_scope ps(c, "io_calls/rows");
-            hipLaunchKernelGGL(k_io_calls, dim3((unsigned)((sum.rows + ROWS_PER_WG - 1) / ROWS_PER_WG)), dim3(THREADS), 0, c->stream, A);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        c->sync();   // (the block, the host vectors and the caller's lists are in use until here)
+        rebase_offsets(j);
+        // the K = 1 case of the segments' launch: the descriptor and the lists the host holds go up in one block, with the row offsets
+        zkm_calls_hold hold;   // (declared first: it outlives the block's wait for the stream when an exception unwinds)
+        zkm_scratch block(c, zkm_io_calls_scratch(&j, 1));
+        zkm_io_calls_launch(c, &j, 1, block.as<char>(), hold);
+        c->sync();   // (the block, the job and the caller's lists are in use until here)
     });
 }
 

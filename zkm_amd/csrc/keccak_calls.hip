@@ -7,11 +7,14 @@
 // RAW indices) and the kernel's indexing all read it.  A call's length varies, so where call k starts in each list is a prefix sum over the
 // earlier calls; the host computes the four sums a call from input_off and uploads them with the lists.
 //
-// k_keccak_calls: ONE launch, one workgroup of 256 threads a call.  The sequential part -- B absorptions and permutations -- is run by one
-// lane, block by block: all lanes stage the padded 136-byte block in LDS, lane 0 XORs it into the state, stores the state (the Keccak-f
-// input, an output anyway) and permutes.  The digest goes into LDS.  After the barrier all lanes write: the 49 contiguous clock and
-// channel cells of a row by adjacent lanes, every list by adjacent lanes on adjacent words; an XOR's lhs is the stored state word ^ the
-// block word.  The row block is zeroed by one memset before the launch, so only the cells a row sets are stored.
+// k_keccak_calls: ONE launch for the calls of K segments (the segment is blockIdx.z; its descriptor is read from device memory, where it
+// went up with the lists as the bootstrap's do -- a uniform read; zkm_keccak_calls_witness is the K = 1 case), one workgroup of 256
+// threads a call.  The sequential part -- B absorptions and permutations -- is run by one lane, block by block: all lanes stage the
+// padded 136-byte block in LDS, lane 0 XORs it into the state, stores the state (the Keccak-f input, an output anyway) and permutes.  The
+// digest goes into LDS.  After the barrier all lanes write: the 49 contiguous clock and channel cells of a row by adjacent lanes, every
+// list by adjacent lanes on adjacent words; an XOR's lhs is the stored state word ^ the block word.  The row block is zeroed by one
+// memset before the launch, so only the cells a row sets are stored.
+#include <array>
 #include <vector>
 
 #include "cpu_steps_dev.h"
@@ -51,7 +54,7 @@ GL_HD uint32_t row_mask(size_t L, size_t j) { return j < read_rows(L) ? (1u << r
 GL_HD size_t final_word(size_t L) { return L / RATE * RATE_U32; }
 }  // namespace place
 
-struct call_base { uint64_t row, mem, logic, perm; };   // where a call starts in each list: the sums of the earlier calls' counts
+using call_base = zkm_keccak_base;   // where a call starts in each list: the sums of the earlier calls' counts
 
 struct keccak_calls_args {
     const uint8_t* inputs;
@@ -61,6 +64,7 @@ struct keccak_calls_args {
     const call_base* base;       // ncalls
     uint64_t *rows, *mem, *perm_in, *perm_ts;
     uint32_t* logic;
+    uint32_t ncalls;             // the segment's own extent of the grid
 };
 
 // the cell `f` of a used channel (cpu/columns/mod.rs MemoryChannelView: used, is_read, addr_context, addr_segment, addr_virtual, value)
@@ -82,9 +86,11 @@ __device__ __forceinline__ uint32_t be_word(const uint8_t* __restrict__ msg, siz
 }
 __device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
 
-__global__ __launch_bounds__(THREADS) void k_keccak_calls(keccak_calls_args A) {
+__global__ __launch_bounds__(THREADS) void k_keccak_calls(const keccak_calls_args* __restrict__ segs) {
     __shared__ uint64_t block[place::RATE / 8];   // the padded block being absorbed
     __shared__ uint32_t digest[8];                // the digest's bytes as little-endian words
+    const keccak_calls_args A = zkm_seg_desc(segs);   // (uniform: scalar loads)
+    if (blockIdx.x >= A.ncalls) return;
     const unsigned t = threadIdx.x;
     const size_t k = blockIdx.x;
     const uint8_t* __restrict__ msg = A.inputs + A.off[k];
@@ -229,7 +235,75 @@ void check_digest_addrs(const uint64_t* addrs, size_t n) {
 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// a job's five lists: the bytes, the offsets, the meta, the digest addresses, the sums a call; which of them go up
+struct list { const void* p; size_t bytes; bool up; };
+std::array<list, 5> lists(const zkm_keccak_job& j) {
+    const size_t n = j.n, first = n ? j.off[0] : 0, nbytes = n ? j.off[n] - first : 0;
+    const bool inputs_up = !zkm_is_device_ptr(j.inputs);
+    return {{{inputs_up && j.inputs ? j.inputs + first : j.inputs, nbytes, inputs_up},
+             {j.off_up.data(), n ? 8 * (n + 1) : 0, true},
+             {j.meta, 32 * n, !zkm_is_device_ptr(j.meta)},
+             {j.digest_addrs, 8 * n, !zkm_is_device_ptr(j.digest_addrs)},
+             {j.bases.data(), sizeof(call_base) * n, true}}};
+}
+// the input bytes go up from the first call's offset on, so the offsets that go up count from there
+void rebase_offsets(zkm_keccak_job& j) {
+    j.off_up.assign(j.off, j.off + j.n + 1);
+    if (!zkm_is_device_ptr(j.inputs))
+        for (uint64_t& o : j.off_up) o -= j.off[0];
+}
+size_t layout(const zkm_keccak_job* j, size_t nseg, std::array<size_t, 5>* at) {
+    size_t total = up256(nseg * sizeof(keccak_calls_args));
+    for (size_t s = 0; s < nseg; s++) {
+        const auto in = lists(j[s]);
+        for (int i = 0; i < 5; i++) {
+            if (at) at[s][i] = total;
+            if (in[i].up) total += up256(in[i].bytes);
+        }
+    }
+    return total;
+}
+
 }  // namespace
+
+void zkm_keccak_calls_check(zkm_keccak_job& j) {
+    const call_base sum = check_offsets(j.off, j.n, &j.bases);
+    check_meta(j.off, j.meta, j.n);
+    check_digest_addrs(j.digest_addrs, j.n);
+    if (j.n && !j.inputs) throw std::runtime_error("inputs: NULL with a count of " + dec(j.n));
+    if (j.n > 0x7FFFFFFF) throw std::runtime_error("2^31 or more calls");
+    j.nrows = sum.row, j.nmem = sum.mem, j.nlogic = sum.logic, j.nperm = sum.perm;
+    j.off_up.clear();
+    if (j.n) rebase_offsets(j);
+}
+size_t zkm_keccak_calls_scratch(const zkm_keccak_job* j, size_t nseg) { return layout(j, nseg, nullptr); }
+void zkm_keccak_calls_launch(zkm_ctx* c, const zkm_keccak_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows) {
+    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_keccak_calls_launch: segment count out of range");
+    std::vector<std::array<size_t, 5>> at(nseg);
+    layout(j, nseg, at.data());
+    keccak_calls_args* d = hold.make<keccak_calls_args>(nseg);
+    size_t grid = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        const auto in = lists(j[s]);
+        const void* dev[5];
+        for (int i = 0; i < 5; i++) {
+            dev[i] = in[i].p;
+            if (in[i].up) {
+                dev[i] = sb + at[s][i];
+                if (in[i].bytes) ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        if (zero_rows && j[s].nrows) ZKM_HIP_CHECK(hipMemsetAsync(j[s].rows, 0, j[s].nrows * CPU_W * sizeof(uint64_t), c->stream));
+        d[s] = keccak_calls_args{(const uint8_t*)dev[0], (const uint64_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const call_base*)dev[4],
+                                 j[s].rows, j[s].mem, j[s].perm_in, j[s].perm_ts, j[s].logic, (uint32_t)j[s].n};
+        grid = std::max(grid, j[s].n);
+    }
+    if (!grid) return;
+    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(keccak_calls_args), hipMemcpyHostToDevice, c->stream));
+    zkm_prof_scope ps(c, "keccak_calls/rows_lists");
+    hipLaunchKernelGGL(k_keccak_calls, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(THREADS), 0, c->stream, (const keccak_calls_args*)sb);
+    ZKM_HIP_CHECK(hipGetLastError());
+}
 
 extern "C" {
 
@@ -284,15 +358,18 @@ int zkm_keccak_calls_witness(zkm_ctx* c, const uint8_t* inputs, const uint64_t* 
     return zkm_api("zkm_keccak_calls_witness", err, [&] {
         auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_keccak_calls_witness: " + m); };
         // every refusal first, on the host: the lists, the outputs, then the context
-        std::vector<call_base> bases;
+        zkm_keccak_job j;
+        j.inputs = inputs, j.off = input_off, j.meta = meta, j.digest_addrs = digest_addrs, j.n = ncalls;
+        j.rows = raw_rows_out_dev, j.mem = memory_ops_out_dev, j.logic = logic_ops_out_dev, j.perm_in = keccak_inputs_out_dev, j.perm_ts = keccak_timestamps_out_dev;
         call_base sum;
         try {
-            sum = check_offsets(input_off, ncalls, &bases);
+            sum = check_offsets(input_off, ncalls, &j.bases);
             check_meta(input_off, meta, ncalls);
             check_digest_addrs(digest_addrs, ncalls);
         } catch (const std::exception& e) {
             refuse(e.what());
         }
+        j.nrows = sum.row, j.nmem = sum.mem, j.nlogic = sum.logic, j.nperm = sum.perm;
         if (ncalls && !inputs) refuse("inputs: NULL with a count of " + dec(ncalls));
         if (ncalls == 0) {
             if (!c) refuse("null argument");
@@ -309,41 +386,12 @@ int zkm_keccak_calls_witness(zkm_ctx* c, const uint8_t* inputs, const uint64_t* 
         if (!c) refuse("null argument");
         if (ncalls > 0x7FFFFFFF) refuse("2^31 or more calls");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        // the lists the host holds go up in one block, with the sums a call; the input bytes from the first call's offset on, so the
-        // offsets that go up count from there
-        const size_t first = input_off[0], nbytes = input_off[ncalls] - first;
-        const bool inputs_up = !zkm_is_device_ptr(inputs);
-        std::vector<uint64_t> off(input_off, input_off + ncalls + 1);
-        if (inputs_up)
-            for (uint64_t& o : off) o -= first;
-        const struct { const void* p; size_t bytes; bool up; } in[5] = {{inputs_up ? inputs + first : inputs, nbytes, inputs_up},
-                                                                        {off.data(), 8 * (ncalls + 1), true},
-                                                                        {meta, 32 * ncalls, !zkm_is_device_ptr(meta)},
-                                                                        {digest_addrs, 8 * ncalls, !zkm_is_device_ptr(digest_addrs)},
-                                                                        {bases.data(), sizeof(call_base) * ncalls, true}};
-        const void* dev[5];
-        size_t at[5], total = 0;
-        for (int i = 0; i < 5; i++) {
-            at[i] = total;
-            if (in[i].up) total += up256(in[i].bytes);
-        }
-        zkm_scratch block(c, total);
-        for (int i = 0; i < 5; i++) {
-            dev[i] = in[i].p;
-            if (in[i].up) {
-                dev[i] = block.as<char>() + at[i];
-                ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-        ZKM_HIP_CHECK(hipMemsetAsync(raw_rows_out_dev, 0, sum.row * CPU_W * sizeof(uint64_t), c->stream));
-        const keccak_calls_args A{(const uint8_t*)dev[0], (const uint64_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const call_base*)dev[4],
-                                  raw_rows_out_dev, memory_ops_out_dev, keccak_inputs_out_dev, keccak_timestamps_out_dev, logic_ops_out_dev};
-        {
-            zkm_prof_scope ps(c, "keccak_calls/rows_lists");
-            hipLaunchKernelGGL(k_keccak_calls, dim3((unsigned)ncalls), dim3(THREADS), 0, c->stream, A);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        c->sync();   // (the block, the host vectors and the caller's lists are in use until here)
+        rebase_offsets(j);
+        // the K = 1 case of the segments' launch: the descriptor and the lists the host holds go up in one block, with the sums a call
+        zkm_calls_hold hold;   // (declared first: it outlives the block's wait for the stream when an exception unwinds)
+        zkm_scratch block(c, zkm_keccak_calls_scratch(&j, 1));
+        zkm_keccak_calls_launch(c, &j, 1, block.as<char>(), hold, true);
+        c->sync();   // (the block, the job and the caller's lists are in use until here)
     });
 }
 

@@ -7,11 +7,16 @@
 // Where a call's rows and operations go is stated once, in `place` below: zkm_sha_calls_counts, zkm_sha_calls_steps (masks, clocks, RAW
 // indices) and the kernel's indexing all read it.
 //
-// k_sha_calls: ONE launch for all calls of both kinds, one workgroup of 256 threads a call (workgroups [0, E) extend, [E, E + C)
-// compress: the branch is uniform in a workgroup, the calls are independent, and a second launch would only add its gap).  The
-// sequential part -- 48 schedule steps, or 64 rounds of eight words -- is run once by one lane into LDS; after the barrier all lanes
-// write from LDS: the 49 contiguous clock and channel cells of a row by adjacent lanes, every list by adjacent lanes on adjacent words.
-// The row block is zeroed by one memset before the launch, so only the cells a row sets are stored.
+// k_sha_calls: ONE launch for all calls of both kinds of K segments (the segment is blockIdx.z; its descriptor is read from device
+// memory, where it went up with the lists as the bootstrap's do -- a uniform read; zkm_sha_calls_witness is the K = 1 case), one
+// workgroup of 256 threads a call (workgroups [0, E) extend, [E, E + C) compress: the branch is uniform in a workgroup, the calls are
+// independent, and a second launch would only add its gap).  The sequential part -- 48 schedule steps, or 64 rounds of eight words -- is
+// run once by one lane into LDS; after the barrier all lanes write from LDS: the 49 contiguous clock and channel cells of a row by
+// adjacent lanes, every list by adjacent lanes on adjacent words. The row block is zeroed by one memset before the launch, so only the
+// cells a row sets are stored.
+#include <array>
+#include <vector>
+
 #include "cpu_steps_dev.h"
 #include "hash_constants_dev.h"
 #include "zkm_internal.h"
@@ -189,10 +194,11 @@ __device__ void compress_call(const sha_calls_args& A, size_t c, uint32_t* w, ui
     }
 }
 
-__global__ __launch_bounds__(THREADS) void k_sha_calls(sha_calls_args A) {
+__global__ __launch_bounds__(THREADS) void k_sha_calls(const sha_calls_args* __restrict__ segs) {
     __shared__ uint32_t w[64], st[8 * 65];
+    const sha_calls_args A = zkm_seg_desc(segs);   // (uniform: scalar loads)
     if (blockIdx.x < A.E) extend_call(A, blockIdx.x, w);
-    else compress_call(A, blockIdx.x - A.E, w, st);
+    else if (blockIdx.x < A.E + A.C) compress_call(A, blockIdx.x - A.E, w, st);
 }
 
 // ---- the host's refusals: one walk over the two meta lists, naming the list and the call's position (throws the bare message)
@@ -242,7 +248,63 @@ void check_meta(const uint64_t* emeta, size_t E, const uint64_t* cmeta, size_t C
 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// a job's five lists: which of them go up (the ones the host holds), and where behind the K descriptors
+struct list { const void* p; size_t bytes; };
+std::array<list, 5> lists(const zkm_sha_job& j) {
+    return {{{j.w16, 64 * j.E}, {j.emeta, 32 * j.E}, {j.hx, 32 * j.C}, {j.w, 256 * j.C}, {j.cmeta, 64 * j.C}}};
+}
+size_t layout(const zkm_sha_job* j, size_t nseg, std::array<size_t, 5>* at) {
+    size_t total = up256(nseg * sizeof(sha_calls_args));
+    for (size_t s = 0; s < nseg; s++) {
+        const auto in = lists(j[s]);
+        for (int i = 0; i < 5; i++) {
+            if (at) at[s][i] = total;
+            if (in[i].bytes && !zkm_is_device_ptr(in[i].p)) total += up256(in[i].bytes);
+        }
+    }
+    return total;
+}
+
 }  // namespace
+
+void zkm_sha_calls_check(zkm_sha_job& j) {
+    check_meta(j.emeta, j.E, j.cmeta, j.C);
+    if (j.E && !j.w16) throw std::runtime_error("extend_w16: NULL with a count of " + dec(j.E));
+    if (j.C && !j.hx) throw std::runtime_error("compress_hx: NULL with a count of " + dec(j.C));
+    if (j.C && !j.w) throw std::runtime_error("compress_w: NULL with a count of " + dec(j.C));
+    if (j.E + j.C > 0x7FFFFFFF) throw std::runtime_error("2^31 or more calls");
+    j.nrows = place::cmp_row(j.E, j.C, 0), j.nmem = place::mem_base(j.E, j.C, true), j.nlogic = place::logic_base(j.E, j.C, true);
+    j.next = place::EXT_ROUNDS * j.E;
+}
+size_t zkm_sha_calls_scratch(const zkm_sha_job* j, size_t nseg) { return layout(j, nseg, nullptr); }
+void zkm_sha_calls_launch(zkm_ctx* c, const zkm_sha_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows) {
+    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_sha_calls_launch: segment count out of range");
+    std::vector<std::array<size_t, 5>> at(nseg);
+    layout(j, nseg, at.data());
+    sha_calls_args* d = hold.make<sha_calls_args>(nseg);
+    size_t grid = 0;
+    for (size_t s = 0; s < nseg; s++) {
+        const auto in = lists(j[s]);
+        const void* dev[5];
+        for (int i = 0; i < 5; i++) {
+            dev[i] = in[i].p;
+            if (in[i].bytes && !zkm_is_device_ptr(in[i].p)) {
+                dev[i] = sb + at[s][i];
+                ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
+            }
+        }
+        const size_t E = j[s].E, C = j[s].C;
+        if (zero_rows && E + C) ZKM_HIP_CHECK(hipMemsetAsync(j[s].rows, 0, place::cmp_row(E, C, 0) * CPU_W * sizeof(uint64_t), c->stream));
+        d[s] = sha_calls_args{(const uint32_t*)dev[0], (const uint64_t*)dev[1], (const uint32_t*)dev[2], (const uint32_t*)dev[3], (const uint64_t*)dev[4],
+                              E, C, j[s].rows, j[s].mem, j[s].ext_ts, j[s].logic, j[s].ext_in};
+        grid = std::max(grid, E + C);
+    }
+    if (!grid) return;
+    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(sha_calls_args), hipMemcpyHostToDevice, c->stream));
+    zkm_prof_scope ps(c, "sha_calls/rows_lists");
+    hipLaunchKernelGGL(k_sha_calls, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(THREADS), 0, c->stream, (const sha_calls_args*)sb);
+    ZKM_HIP_CHECK(hipGetLastError());
+}
 
 extern "C" {
 
@@ -319,33 +381,14 @@ int zkm_sha_calls_witness(zkm_ctx* c, const uint32_t* extend_w16, const uint64_t
         if (!c) refuse("null argument");
         if (E + C > 0x7FFFFFFF) refuse("2^31 or more calls");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        // the lists the host holds go up in one block
-        const struct { const void* p; size_t bytes; } in[5] = {{extend_w16, 64 * E}, {extend_meta, 32 * E}, {compress_hx, 32 * C}, {compress_w, 256 * C},
-                                                               {compress_meta, 64 * C}};
-        const void* dev[5];
-        size_t off[5], total = 0;
-        for (int i = 0; i < 5; i++) {
-            off[i] = total;
-            if (in[i].bytes && !zkm_is_device_ptr(in[i].p)) total += up256(in[i].bytes);
-        }
-        zkm_scratch block;
-        if (total) block = zkm_scratch(c, total);
-        for (int i = 0; i < 5; i++) {
-            dev[i] = in[i].p;
-            if (in[i].bytes && !zkm_is_device_ptr(in[i].p)) {
-                dev[i] = block.as<char>() + off[i];
-                ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-        ZKM_HIP_CHECK(hipMemsetAsync(raw_rows_out_dev, 0, place::cmp_row(E, C, 0) * CPU_W * sizeof(uint64_t), c->stream));
-        const sha_calls_args A{(const uint32_t*)dev[0], (const uint64_t*)dev[1], (const uint32_t*)dev[2], (const uint32_t*)dev[3], (const uint64_t*)dev[4],
-                               E, C, raw_rows_out_dev, memory_ops_out_dev, sha_extend_timestamps_out_dev, logic_ops_out_dev,
-                               (uint32_t*)sha_extend_inputs_out_dev};
-        {
-            zkm_prof_scope ps(c, "sha_calls/rows_lists");
-            hipLaunchKernelGGL(k_sha_calls, dim3((unsigned)(E + C)), dim3(THREADS), 0, c->stream, A);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
+        // the K = 1 case of the segments' launch: the descriptor and the lists the host holds go up in one block
+        zkm_sha_job j;
+        j.w16 = extend_w16, j.emeta = extend_meta, j.E = E, j.hx = compress_hx, j.w = compress_w, j.cmeta = compress_meta, j.C = C;
+        j.rows = raw_rows_out_dev, j.mem = memory_ops_out_dev, j.ext_ts = sha_extend_timestamps_out_dev, j.logic = logic_ops_out_dev;
+        j.ext_in = (uint32_t*)sha_extend_inputs_out_dev;
+        zkm_calls_hold hold;   // (declared first: it outlives the block's wait for the stream when an exception unwinds)
+        zkm_scratch block(c, zkm_sha_calls_scratch(&j, 1));
+        zkm_sha_calls_launch(c, &j, 1, block.as<char>(), hold, true);
         c->sync();   // (the block and the caller's lists are in use until here)
     });
 }

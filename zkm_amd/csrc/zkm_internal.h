@@ -59,6 +59,17 @@ struct seg_gl2 { gl_t v[2 * ZKM_MAX_SEG]; };     // two per segment (an F2 eleme
 // kernel-argument slot s, the kernel takes its segment from blockIdx.z -- a uniform read, so the descriptor lives in scalar registers --
 // and the grid's x extent is the largest segment's; workgroups beyond a segment's own extent leave at once.
 template <class A> struct zkm_seg_args { A v[ZKM_MAX_SEG]; };
+// Descriptors that travel in device memory instead (the calls' expansions'): zkm_seg_desc is segment blockIdx.z's, read through the
+// constant address space -- the descriptors went up before the launch and no kernel writes them -- so the read is scalar, and the
+// pointers it holds are known to be global as kernel-argument pointers are (read as generic pointers they would make every access a
+// flat one and no second-level load a scalar one).
+#ifdef __HIPCC__
+template <class A> __device__ __forceinline__ A zkm_seg_desc(const A* segs) {
+    A a;
+    __builtin_memcpy(&a, (const __attribute__((address_space(4))) A*)segs + blockIdx.z, sizeof(A));
+    return a;
+}
+#endif
 
 struct zkm_twiddles {
     gl_t* fwd = nullptr;  // per-stage tables concatenated: entry (1<<s) + j = w_{2^(s+1)}^j, j < 2^s
@@ -563,6 +574,66 @@ struct zkm_steps_seg {
 };
 // nseg <= ZKM_MAX_SEG segments of one context, ONE launch: the rows (over a zeroed table), the lists, or both
 void zkm_cpu_steps_launch(zkm_ctx* c, const zkm_steps_seg* segs, size_t nseg, bool rows, bool lists);
+
+// ---- the calls' expansions (sha_calls.hip, keccak_calls.hip, io_calls.hip, insn_rows.hip): K segments served by ONE launch a kind.
+// A job is one segment's calls of one kind: the caller's lists (host or device memory as the kind's entry point says), where the
+// outputs go (device) and what the host walk found.  The K descriptors travel in device memory, uploaded with the lists in the one
+// scratch block, as the bootstrap's do (d_desc): the kernel-argument block is one pointer.
+//   check    every refusal that concerns the lists (throws the bare message), the counts and the host walk's vectors
+//   scratch  the bytes a launch of these jobs puts up: the K descriptors and the lists the host holds
+//   launch   queues the uploads into `scratch` and ONE launch for nseg <= ZKM_MAX_SEG checked jobs (none when no job has a call).  The
+//            SHA and Keccak kernels store only the cells a row sets: zero_rows queues a memset of each job's rows in front (false: the
+//            caller has zeroed them).  The jobs, `hold` (the descriptors' host copy) and the caller's lists are in use until the
+//            stream has been waited for.
+// The per-kind entry points are the nseg = 1 case.
+struct zkm_calls_hold {
+    std::vector<std::unique_ptr<char[]>> blocks;
+    template <class T> T* make(size_t n) {
+        blocks.emplace_back(new char[n * sizeof(T) + 1]());
+        return (T*)blocks.back().get();
+    }
+};
+struct zkm_sha_job {
+    const uint32_t* w16 = nullptr; const uint64_t* emeta = nullptr; size_t E = 0;
+    const uint32_t *hx = nullptr, *w = nullptr; const uint64_t* cmeta = nullptr; size_t C = 0;
+    uint64_t *rows = nullptr, *mem = nullptr, *ext_ts = nullptr;
+    uint32_t *logic = nullptr, *ext_in = nullptr;
+    size_t nrows = 0, nmem = 0, nlogic = 0, next = 0;
+};
+void zkm_sha_calls_check(zkm_sha_job& j);
+size_t zkm_sha_calls_scratch(const zkm_sha_job* j, size_t nseg);
+void zkm_sha_calls_launch(zkm_ctx* c, const zkm_sha_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold, bool zero_rows);
+struct zkm_keccak_base { uint64_t row, mem, logic, perm; };   // where a call starts in each list: the sums of the earlier calls' counts
+struct zkm_keccak_job {
+    const uint8_t* inputs = nullptr; const uint64_t *off = nullptr, *meta = nullptr, *digest_addrs = nullptr; size_t n = 0;
+    uint64_t *rows = nullptr, *mem = nullptr, *perm_in = nullptr, *perm_ts = nullptr;
+    uint32_t* logic = nullptr;
+    size_t nrows = 0, nmem = 0, nlogic = 0, nperm = 0;
+    std::vector<zkm_keccak_base> bases;
+    std::vector<uint64_t> off_up;   // the offsets as they go up: from the first call's on, where the bytes go up
+};
+void zkm_keccak_calls_check(zkm_keccak_job& j);
+size_t zkm_keccak_calls_scratch(const zkm_keccak_job* j, size_t nseg);
+void zkm_keccak_calls_launch(zkm_ctx* c, const zkm_keccak_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold, bool zero_rows);
+struct zkm_io_job {
+    const uint32_t* kinds = nullptr; const uint8_t* data = nullptr; const uint64_t *off = nullptr, *meta = nullptr; size_t n = 0;
+    uint64_t* rows = nullptr;
+    size_t nrows = 0, nmem = 0;
+    std::vector<uint64_t> row_off, off_up;
+};
+void zkm_io_calls_check(zkm_io_job& j);
+size_t zkm_io_calls_scratch(const zkm_io_job* j, size_t nseg);
+void zkm_io_calls_launch(zkm_ctx* c, const zkm_io_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold);
+struct zkm_insn_job {
+    const zkm_cpu_step* insns = nullptr; const uint64_t* clocks = nullptr; size_t n = 0;
+    uint64_t* rows = nullptr;
+    uint32_t* arith = nullptr;
+    size_t nmem = 0, narith = 0;
+    std::vector<uint32_t> base;     // one per workgroup: the operations the records in front of it push
+};
+void zkm_insn_rows_check(zkm_insn_job& j);
+size_t zkm_insn_rows_scratch(const zkm_insn_job* j, size_t nseg);
+void zkm_insn_rows_launch(zkm_ctx* c, const zkm_insn_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold);
 
 // ctl_check.hip: check_ctls on one segment's tables.  Returns the report's kind (0 consistent, 1 non-binary filter, 2 multisets differ)
 // with the reference's message in *msg; throws when the check cannot be made
