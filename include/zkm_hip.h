@@ -97,6 +97,15 @@ void zkm_ctx_trim(zkm_ctx* ctx);
  *                               zkm_prove_segments_ops run zkm_check_ctls on each segment's tables before they prove -- the reference's `test`
  *                               feature (prover.rs:171-176) -- and fail with "check_ctls: segment <position in the call>: " and that call's
  *                               message; no proof is written.  Default 0: no launch is added and every proof word stays what it is
+ *   "check_witness"             1: the same prove calls (with the _ops_boot, _ops_steps and _ops_calls forms and a pool's groups) run
+ *                               zkm_segments_check on the segments of each wave before anything is committed -- table constraints, the
+ *                               range-check lookups and the cross-table lookups, two host waits a wave whatever its segments -- and fail with
+ *                               "check_witness: segment <position in the call>: " and that call's message ("Constraint failed in <Name>Stark:
+ *                               ..", "Lookup failed in <Name>Stark: ..", "CTL #j: .."); no proof or challenge word is written.  A
+ *                               zkm_prove_with_traces call on tables other than the twelve of the AllStark gets the cross-table part only.
+ *                               With "check_ctls" also set the cross-table lookups are checked once, here.  A wave whose checks' scratch
+ *                               would not fit beside its tables is checked in consecutive sub-groups.  Default 0: no launch is added and
+ *                               every proof word stays what it is
  *   "verify"                    1: the same prove calls verify what they have written (zkm_verify_proofs on every segment's blobs) before they
  *                               return, as prove_root does (fixed_recursive_verifier.rs:777, 853); on a rejection the call fails with
  *                               "verify: segment <position in the call>: " and that call's message, and no proof word is handed out -- of any
@@ -1370,7 +1379,7 @@ int zkm_check_constraints(zkm_ctx* ctx, int table_id, const zkm_stark_config* cf
  * zkm_segment_check_ctls takes them (the twelve pointers of zkm_staged_segment_ptrs, for one), in ONE set of launches with one download
  * and one host wait whatever the tables (zkm_ctx_host_waits).  findings = 12 x ZKM_WITNESS_FINDING_WORDS words, every table's own
  * result; *err names the lowest failing table in Table::all() order.
- * Both run on the context's stream, behind what is queued there.  A debugging aid: not on the proving path. */
+ * Both run on the context's stream, behind what is queued there.  On the proving path only under "check_witness" (zkm_segments_check). */
 #define ZKM_WITNESS_FINDING_WORDS 5
 int zkm_witness_check(zkm_ctx* ctx, int table_id, const uint64_t* trace, size_t ncols, unsigned log_n, uint64_t* finding, char** err);
 int zkm_segment_witness_check(zkm_ctx* ctx, const uint64_t* const* traces, const unsigned* log_n, uint64_t* findings, char** err);
@@ -1402,8 +1411,8 @@ int zkm_segment_witness_check(zkm_ctx* ctx, const uint64_t* const* traces, const
  * zkm_segment_lookup_check: the same for the twelve tables of a segment, as zkm_segment_witness_check takes them: the tables with lookups
  * share ONE set of launches, one download and one host wait (zkm_ctx_host_waits).  findings = 12 x ZKM_LOOKUP_FINDING_WORDS words in
  * Table::all() order, every table's own result; *err names the lowest failing table in that order.
- * Both run on the context's stream, behind what is queued there; a finding or a failure leaves the context usable.  A debugging aid: not
- * on the proving path.  With zkm_witness_check and zkm_check_ctls this covers what eval_vanishing_poly and verify_cross_table_lookups ask
+ * Both run on the context's stream, behind what is queued there; a finding or a failure leaves the context usable.  On the proving path
+ * only under "check_witness" (zkm_segments_check).  With zkm_witness_check and zkm_check_ctls this covers what eval_vanishing_poly and verify_cross_table_lookups ask
  * of a witness. */
 #define ZKM_LOOKUP_FINDING_WORDS 9
 int zkm_lookup_check(zkm_ctx* ctx, int table_id, const uint64_t* trace, size_t ncols, unsigned log_n, uint64_t* finding, char** err);
@@ -1452,6 +1461,36 @@ typedef struct zkm_ctl_report {
 int zkm_check_ctls(zkm_ctx* ctx, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
                    size_t nctls, zkm_ctl_report* report, char** err);
 int zkm_segment_check_ctls(zkm_ctx* ctx, const uint64_t* const* traces, const unsigned* log_n, zkm_ctl_report* report, char** err);
+/* The three checks -- zkm_segment_witness_check, zkm_segment_lookup_check and zkm_segment_check_ctls -- on nseg segments in ONE
+ * call: everything eval_vanishing_poly and verify_cross_table_lookups ask of a witness, in ONE set of launches for all segments (the
+ * tables of a kind share a launch, the lookups' jobs share theirs 32 at a time) and TWO host waits whatever nseg when every segment is
+ * consistent: the cross-table record counts, then one download of the cross-table verdicts with the witness and lookup findings.
+ * A key collision adds one wait per extra attempt, failing cross-table lookups add one for all their reports, failing constraints or
+ * range-check lookups add none (zkm_ctx_host_waits).
+ *   traces[s][t], log_n[s][t]   table t of segment s in Table::all() order, column-major, host or device memory (the two may be mixed:
+ *                      host tables are copied up for the call) -- e.g. the twelve pointers of zkm_staged_segment_ptrs for each segment
+ *   verdicts           nseg x ZKM_SEGMENT_VERDICT_WORDS words, or NULL: [2 s] the kind of segment s's FIRST finding in the order of
+ *                      eval_vanishing_poly (vanishing_poly.rs:17-46) -- 0 consistent; 1 a table constraint, [2 s + 1] the position of the
+ *                      lowest failing table in Table::all(); 2 a range-check lookup, [2 s + 1] likewise; 3 a cross-table lookup,
+ *                      [2 s + 1] the lookup's index
+ *   witness_findings   nseg x 12 x ZKM_WITNESS_FINDING_WORDS words, or NULL: what zkm_segment_witness_check writes for each segment alone
+ *   lookup_findings    nseg x 12 x ZKM_LOOKUP_FINDING_WORDS words, or NULL: what zkm_segment_lookup_check writes for each segment alone
+ *   ctl_reports        nseg reports, or NULL: what zkm_segment_check_ctls writes for each segment alone, except `attempts` and
+ *                      `host_waits`, which are the CALL's in every report
+ * All three checks always run to the end on every segment, and the outputs are filled whatever they find.  Returns 0 when every segment
+ * is consistent; otherwise nonzero with *err = "zkm_segments_check: segment <s>: <message>": s the lowest segment with a finding, the
+ * message the one the owning per-segment check gives for that segment's first finding ("Constraint failed in <Name>Stark: ..",
+ * "Lookup failed in <Name>Stark: ..", "CTL #j: ..").  Refusals -- nseg = 0, a NULL traces, log_n, traces[s], log_n[s] or table, a log_n
+ * above 30, a lookup of more than 2^30 records -- are made on the host before any device work and before the context is needed, and
+ * name the function, the segment and the table ("zkm_segments_check: segment 1: Logic: trace: null argument"); they leave the context
+ * usable.  Everything runs on the context's stream, and all scratch is back in the context's cache when the call returns.  Segments
+ * whose scratch would not fit in device memory together are checked in consecutive sub-groups, each with its own waits.
+ * zkm_segment_check: the call for one segment (messages name zkm_segment_check).  In front of the prove calls under "check_witness". */
+#define ZKM_SEGMENT_VERDICT_WORDS 2
+int zkm_segments_check(zkm_ctx* ctx, size_t nseg, const uint64_t* const* const* traces, const unsigned* const* log_n, uint64_t* verdicts,
+                       uint64_t* witness_findings, uint64_t* lookup_findings, zkm_ctl_report* ctl_reports, char** err);
+int zkm_segment_check(zkm_ctx* ctx, const uint64_t* const* traces, const unsigned* log_n, uint64_t* verdict, uint64_t* witness_findings,
+                      uint64_t* lookup_findings, zkm_ctl_report* ctl_report, char** err);
 /* ------------------------------------------------------------------ verify_proof on the device
  * verify_proof (verifier.rs:27-176) with verify_stark_proof_with_challenges (:178-292) per table and verify_cross_table_lookups, for the
  * proof blobs this library writes, from the blobs alone -- what prove_root / prove_root_with_assumption run on every segment proof

@@ -473,6 +473,13 @@ extern "C" {
                             err: *mut *mut c_char) -> c_int;
     pub fn zkm_segment_lookup_check(ctx: *mut zkm_ctx, traces: *const *const u64, log_n: *const c_uint, findings: *mut u64,
                                     err: *mut *mut c_char) -> c_int;
+    // the three checks on nseg segments in one set of launches and two host waits: rc != 0 + "zkm_segments_check: segment s: " and the
+    // owning check's message; verdicts ZKM_SEGMENT_VERDICT_WORDS words a segment (segment_check_hip.rs)
+    pub fn zkm_segments_check(ctx: *mut zkm_ctx, nseg: usize, traces: *const *const *const u64, log_n: *const *const c_uint, verdicts: *mut u64,
+                              witness_findings: *mut u64, lookup_findings: *mut u64, ctl_reports: *mut zkm_ctl_report,
+                              err: *mut *mut c_char) -> c_int;
+    pub fn zkm_segment_check(ctx: *mut zkm_ctx, traces: *const *const u64, log_n: *const c_uint, verdict: *mut u64, witness_findings: *mut u64,
+                             lookup_findings: *mut u64, ctl_report: *mut zkm_ctl_report, err: *mut *mut c_char) -> c_int;
     // verify_proof (verifier.rs:27-176) on the device: the general form, K AllStark segments, and the mirror of zkm_prove_single_table
     pub fn zkm_verify_proofs(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, tables: *const zkm_table_input, ntables: usize,
                              ctls: *const zkm_cross_table_lookup, sides: *const zkm_ctl_side, nctls: usize, public_values: *const u64,
@@ -502,6 +509,9 @@ pub const ZKM_WITNESS_FINDING_WORDS: usize = 5;
 /// words of one finding of zkm_lookup_check / zkm_segment_lookup_check: failing lookup (all ones: every lookup holds), the value, its looking
 /// count, its frequency, its table rows, column and row of its first looking cell, its first table row, the unbalanced values
 pub const ZKM_LOOKUP_FINDING_WORDS: usize = 9;
+/// words of one segment's verdict of zkm_segments_check / zkm_segment_check: the kind of its first finding (0 consistent, 1 a table
+/// constraint, 2 a range-check lookup, 3 a cross-table lookup), then the failing table's position in Table::all() or the lookup's index
+pub const ZKM_SEGMENT_VERDICT_WORDS: usize = 2;
 
 /// status + message -> anyhow::Error; the message is released with free() like recursion/src/snark/snarks.rs:55-57
 pub fn check(rc: c_int, err: *mut c_char) -> anyhow::Result<()> {

@@ -8,6 +8,7 @@ missing or no GPU is present, every compute entry point raises.
 """
 import ctypes as C
 import os
+import re
 import subprocess
 import weakref
 
@@ -38,6 +39,7 @@ POSEIDON_PROBE = abi.constants("ZKM_POSEIDON_PROBE_")
 WITNESS_FINDING_WORDS = _H["WITNESS_FINDING_WORDS"]   # zkm_witness_check: row, constraint index, value, failing rows, constraints per row
 # zkm_lookup_check: failing lookup, value, looking count, frequency, table rows, first looking cell (column, row), first table row, failing values
 LOOKUP_FINDING_WORDS = _H["LOOKUP_FINDING_WORDS"]
+SEGMENT_VERDICT_WORDS = _H["SEGMENT_VERDICT_WORDS"]   # zkm_segments_check: kind of the first finding, its table position or lookup index
 u64p = C.POINTER(C.c_uint64)
 
 EXPORTS = [name for name, _, _ in abi.prototypes()]
@@ -1015,6 +1017,7 @@ class Context:
         self._staged = weakref.WeakSet()     # outstanding StagedTraces: freed by close() before the context goes
         self.witness_message = None          # the message of the last witness_check / segment_witness_check (None: every constraint held)
         self.lookup_message = None           # ... of the last lookup_check / segment_lookup_check (None: every lookup held)
+        self.check_message = None            # ... of the last segments_check / segment_check (None: every segment consistent)
 
     def close(self):
         if self.h:
@@ -2049,6 +2052,53 @@ class Context:
         rc = self.L.zkm_segment_lookup_check(self.h, ptrs, lg, words, C.byref(err))
         findings, self.lookup_message = self._lookup_findings(rc, words, err)
         return findings
+
+    def segments_check(self, segments):
+        """zkm_segments_check: the three checks -- table constraints, range-check lookups, cross-table lookups -- on K segments in one set
+        of launches and two host waits.  segments: a list of (traces, log_ns), traces as segment_witness_check takes them.  Returns per
+        segment (verdict, witness findings, lookup findings, CtlReport): verdict = (kind, index) of the segment's first finding (kind 0
+        consistent, 1 a table constraint, 2 a range-check lookup, 3 a cross-table lookup), the rest in the shapes of
+        segment_witness_check, segment_lookup_check and segment_check_ctls.  .check_message holds the call's message: None when every
+        segment is consistent, else "zkm_segments_check: segment <s>: ..." for the lowest segment with a finding."""
+        return self._segments_check(segments, False)
+
+    def segment_check(self, traces, log_ns):
+        """zkm_segment_check: segments_check on one segment; returns its (verdict, witness findings, lookup findings, CtlReport)."""
+        return self._segments_check([(traces, log_ns)], True)[0]
+
+    def _segments_check(self, segments, single):
+        k = len(segments)
+        keep, seg_ptrs, seg_lgs = [], [], []
+        for traces, log_ns in segments:
+            if isinstance(traces, StagedTrace):
+                traces = traces.tables()
+            assert len(traces) == 12 and len(log_ns) == 12
+            held = [t if isinstance(t, (DeviceBuffer, StagedTrace, int)) else np.ascontiguousarray(t, dtype=np.uint64) for t in traces]
+            keep.append(held)
+            seg_ptrs.append((C.c_void_p * 12)(*[_data_ptr(t).value for t in held]))
+            seg_lgs.append((C.c_uint * 12)(*[int(x) for x in log_ns]))
+        tp = (C.c_void_p * max(k, 1))(*[C.addressof(p) for p in seg_ptrs])
+        lp = (C.c_void_p * max(k, 1))(*[C.addressof(p) for p in seg_lgs])
+        verdicts = (C.c_uint64 * (SEGMENT_VERDICT_WORDS * max(k, 1)))()
+        wf = (C.c_uint64 * (12 * WITNESS_FINDING_WORDS * max(k, 1)))()
+        lf = (C.c_uint64 * (12 * LOOKUP_FINDING_WORDS * max(k, 1)))()
+        reps, err = (CtlReport * max(k, 1))(), C.c_char_p()
+        if single:
+            rc = self.L.zkm_segment_check(self.h, seg_ptrs[0], seg_lgs[0], verdicts, wf, lf, reps, C.byref(err))
+        else:
+            rc = self.L.zkm_segments_check(self.h, k, tp, lp, verdicts, wf, lf, reps, C.byref(err))
+        msg = err.value.decode() if err.value else None
+        if rc != 0 and not re.match(r"zkm_segments?_check: segment \d+: (Constraint failed in |Lookup failed in |CTL #)", msg or ""):
+            raise ZkmError(msg or "segments_check: error %d" % rc)
+        self.check_message = msg
+        witness, _ = self._witness_findings(0, wf, C.c_char_p())
+        lookups, _ = self._lookup_findings(0, lf, C.c_char_p())
+        out = []
+        for s in range(k):
+            rep = CtlReport.from_buffer_copy(reps[s])
+            rep.message = None
+            out.append(((int(verdicts[2 * s]), int(verdicts[2 * s + 1])), witness[12 * s:12 * s + 12], lookups[12 * s:12 * s + 12], rep))
+        return out
 
     @staticmethod
     def _verify_reports(rc, reps, err):

@@ -553,6 +553,7 @@ int zkm_ctx_set_tuning(zkm_ctx* c, const char* key, uint64_t value, char** err) 
                 x->pow_round_log = value ? 16 : 17;                 // (half-filled SIMDs are somebody else's slots here: 76.3 vs 75.4 segments/s)
             }
             else if (k == "check_ctls") x->check_ctls = value ? 1 : 0;
+            else if (k == "check_witness") x->check_witness = value ? 1 : 0;
             else if (k == "verify") x->verify = value ? 1 : 0;
             else if (k == "boot_chain_quad") x->boot_chain_quad = value ? 1 : 0;
             else if (k == "image_hash_form") x->image_hash_form = value > 2 ? 0 : (int)value;

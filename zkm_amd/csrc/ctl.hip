@@ -1118,14 +1118,38 @@ static void prove_segments_impl(zkm_ctx* c, const zkm_stark_config* cfg, size_t 
     lockstep_call call{c, cfg, nseg, io, ntables, ctls, sides, nctls, seg_base};
     ZKM_HIP_CHECK(hipSetDevice(c->device));
     if (nseg == 0) return;
-    if (c->check_ctls)   // the reference's `test` feature (prover.rs:171-176): nothing is proven from inconsistent tables
-        for (size_t s = 0; s < nseg; s++) {
-            zkm_ctl_report rep{};
-            std::string msg;
-            if (!io[s].tables) throw std::runtime_error("zkm_prove_with_traces: null argument");
-            if (zkm_check_ctls_run(c, io[s].tables, ntables, ctls, sides, nctls, &rep, &msg))
-                throw std::runtime_error("check_ctls: segment " + std::to_string(seg_base + s) + ": " + msg);
+    if (c->check_witness || c->check_ctls) {   // nothing is proven from an inconsistent witness: the wave's segments in one set of launches
+        std::vector<const zkm_table_input*> tabs(nseg);
+        bool all_stark = ntables == (size_t)ZKM_NUM_TABLES && nctls == AS_NCTLS;   // the AllStark's description, from the library or restated
+        for (size_t j = 0; j < nctls && all_stark; j++) {
+            all_stark = ctls[j].nlooking == AS_CTLS[j].nlooking && ctls[j].looked.table == AS_CTLS[j].looked.table && ctls[j].looked.colset == AS_CTLS[j].looked.colset;
+            for (uint32_t i = 0; i < AS_CTLS[j].nlooking && all_stark; i++) {
+                const zkm_ctl_side a = sides[ctls[j].looking_off + i], b = AS_SIDES[AS_CTLS[j].looking_off + i];
+                all_stark = a.table == b.table && a.colset == b.colset;
+            }
         }
+        for (size_t s = 0; s < nseg; s++) {
+            if (!io[s].tables) throw std::runtime_error("zkm_prove_with_traces: null argument");
+            tabs[s] = io[s].tables;
+            for (size_t t = 0; t < ntables && all_stark; t++)
+                all_stark = io[s].tables[t].table_id == zkm_table_at((int)t)->id && io[s].tables[t].ncols == zkm_table_at((int)t)->width &&
+                            io[s].tables[t].log_n <= 30 && (io[s].tables[t].trace || io[s].tables[t].columns);
+        }
+        std::string msg;
+        size_t bad = nseg;
+        const char* key = c->check_witness ? "check_witness" : "check_ctls";
+        if (c->check_witness && all_stark) {
+            // table constraints, range-check lookups, cross-table lookups (segment_check.hip); the registry checks need the twelve tables
+            bad = zkm_segments_check_run(c, nseg, tabs.data(), nullptr, nullptr, nullptr, nullptr, &msg);
+        } else {
+            // the reference's `test` feature (prover.rs:171-176), and all "check_witness" can ask of another table list
+            std::vector<zkm_ctl_report> reps(nseg);
+            std::vector<std::string> msgs(nseg);
+            bad = zkm_check_ctls_run_segments(c, nseg, tabs.data(), ntables, ctls, sides, nctls, reps.data(), msgs.data());
+            if (bad < nseg) msg = msgs[bad];
+        }
+        if (bad < nseg) throw std::runtime_error(std::string(key) + ": segment " + std::to_string(seg_base + bad) + ": " + msg);
+    }
     call.note_stack_height();
     call.plan();
     call.commit_traces();

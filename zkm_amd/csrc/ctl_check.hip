@@ -2,7 +2,8 @@
 // prover.rs:171-176) on device-resident tables: for every CrossTableLookup, the multiset of the filtered rows of the looking tables
 // against that of the looked table, with the row and its locations named when they differ.
 //
-// One job per lookup; the jobs of a call share every launch (zkm_seg_args: the job from blockIdx.z).  A job's candidate rows are its
+// One job per (segment, lookup) -- a call takes the table lists of K segments, the single-segment entry points are K = 1; the jobs of a
+// call share every launch, ZKM_MAX_SEG at a time (zkm_seg_args: the job from blockIdx.z).  A job's candidate rows are its
 // sides' rows, side after side (the looking sides in the lookup's order, the looked side last), cut into tiles of CC_TILE rows:
 //   (1) k_cc_count    one lane per (side, row): the filter; the smallest (side, row) with a value other than 0 or 1; per-tile counts of
 //                     the rows with filter 1 (the job's RECORDS);
@@ -19,7 +20,7 @@
 //                     the same amount in both halves; the unbalanced run whose head is the earliest record (atomicMin) is the one
 //                     reported: the sort is stable, so a run's head is its tuple's first occurrence in candidate order;
 //   (9) k_cc_report   the reported tuple, its two counts and its first locations (or the filter's value).
-// Host waits: the record counts, the verdict of each attempt (one unless keys collided), the report of a failing call.
+// Host waits, whatever K: the record counts, the verdict of each attempt (one unless keys collided), the reports of a failing call.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -271,73 +272,111 @@ std::string locations_text(const zkm_table_input* tables, const zkm_ctl_location
 
 }  // namespace
 
-// zkm_internal.h: the check on one segment's tables.  Returns the report's kind (0, 1 or 2) with the reference's message in *msg; throws
-// when the check cannot be made (the entry points turn that into kind 3).
-int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
-                       size_t nctls, zkm_ctl_report* rep, std::string* msg) {
-    if ((!tables && ntables) || (nctls && (!ctls || !sides))) throw std::runtime_error("check_ctls: null argument");
-    if (nctls >= ((size_t)1 << 31)) throw std::runtime_error("check_ctls: too many lookups");
-    rep->attempts = 0;
-    rep->host_waits = 0;
-    // ---- the description: every side names a table and one of its column sets; the sides of a lookup agree in width
-    std::vector<char> used(ntables, 0);
-    std::vector<cc_side> h_sides;
-    std::vector<size_t> side_off(nctls + 1, 0);
-    std::vector<uint32_t> width(nctls), ntiles(nctls);
-    for (size_t j = 0; j < nctls; j++) {
-        const zkm_cross_table_lookup& L = ctls[j];
-        if (L.nlooking + 1 == 0) throw std::runtime_error("check_ctls: malformed cross-table lookups");
-        uint64_t tile = 0;
-        for (uint32_t i = 0; i <= L.nlooking; i++) {
-            const zkm_ctl_side sd = i < L.nlooking ? sides[L.looking_off + i] : L.looked;
-            if (sd.table >= ntables) throw std::runtime_error("CTL #" + std::to_string(j) + ": table index out of range");
-            const zkm_table_input& t = tables[sd.table];
-            if (!t.ctl || sd.colset >= t.ctl->ncolsets) throw std::runtime_error("CTL #" + std::to_string(j) + ": column-set index out of range");
-            if (t.ncols == 0 || t.log_n > 30 || (!t.trace && !t.columns)) throw std::runtime_error("check_ctls: bad table shape");
-            const uint32_t w = t.ctl->colsets[sd.colset].ncols;
-            if (i == 0) width[j] = w;
-            if (w != width[j])   // (the oracle's 100 + c)
-                throw std::runtime_error("CTL #" + std::to_string(j) + ": the column sets of the looking and looked tables differ in width");
-            used[sd.table] = 1;
-            h_sides.push_back(cc_side{sd.table, sd.colset, (uint32_t)tile, 0});
-            tile += blocks_for((size_t)1 << t.log_n, CC_TILE);
-            if (tile >= ((uint64_t)1 << 31)) throw std::runtime_error("CTL #" + std::to_string(j) + ": too many candidate rows");
+// zkm_internal.h: the check on the tables of nseg segments, job s nctls + j = lookup j of segment s.  Fills reps[s] / msgs[s] (kind 0, 1
+// or 2 with the reference's message) and returns the lowest failing segment (nseg: none); throws when the check cannot be made (the
+// entry points turn that into kind 3).
+size_t zkm_check_ctls_run_segments(zkm_ctx* c, size_t nseg, const zkm_table_input* const* tables, size_t ntables, const zkm_cross_table_lookup* ctls,
+                                   const zkm_ctl_side* sides, size_t nctls, zkm_ctl_report* reps, std::string* msgs, const zkm_ctx::xfer* ride) {
+    if (!nseg || !tables || !reps || !msgs) throw std::runtime_error("check_ctls: null argument");
+    for (size_t s = 0; s < nseg; s++)
+        if ((!tables[s] && ntables) || (nctls && (!ctls || !sides))) throw std::runtime_error("check_ctls: null argument");
+    if (nctls >= ((size_t)1 << 31) / nseg) throw std::runtime_error("check_ctls: too many lookups");
+    uint32_t attempts = 0, host_waits = 0;
+    auto stamp = [&] {   // (the waits and attempts are the call's: every segment's report carries them)
+        for (size_t s = 0; s < nseg; s++) {
+            reps[s].attempts = attempts;
+            reps[s].host_waits = host_waits;
         }
-        ntiles[j] = (uint32_t)tile;
-        side_off[j + 1] = h_sides.size();
-    }
+    };
+    stamp();
+    const size_t njobs = nseg * nctls;
+    // ---- the description: every side names a table and one of its column sets; the sides of a lookup agree in width
+    std::vector<char> used(nseg * ntables, 0);
+    std::vector<cc_side> h_sides;
+    std::vector<size_t> side_off(njobs + 1, 0);
+    std::vector<uint32_t> width(nctls), ntiles(njobs);
+    for (size_t s = 0; s < nseg; s++)
+        for (size_t j = 0; j < nctls; j++) {
+            const zkm_cross_table_lookup& L = ctls[j];
+            if (L.nlooking + 1 == 0) throw std::runtime_error("check_ctls: malformed cross-table lookups");
+            uint64_t tile = 0;
+            for (uint32_t i = 0; i <= L.nlooking; i++) {
+                const zkm_ctl_side sd = i < L.nlooking ? sides[L.looking_off + i] : L.looked;
+                if (sd.table >= ntables) throw std::runtime_error("CTL #" + std::to_string(j) + ": table index out of range");
+                const zkm_table_input& t = tables[s][sd.table];
+                if (!t.ctl || sd.colset >= t.ctl->ncolsets) throw std::runtime_error("CTL #" + std::to_string(j) + ": column-set index out of range");
+                if (t.ncols == 0 || t.log_n > 30 || (!t.trace && !t.columns)) throw std::runtime_error("check_ctls: bad table shape");
+                const uint32_t w = t.ctl->colsets[sd.colset].ncols;
+                if (i == 0 && s == 0) width[j] = w;
+                if (w != width[j])   // (the oracle's 100 + c)
+                    throw std::runtime_error("CTL #" + std::to_string(j) + ": the column sets of the looking and looked tables differ in width");
+                used[s * ntables + sd.table] = 1;
+                h_sides.push_back(cc_side{sd.table, sd.colset, (uint32_t)tile, 0});
+                tile += blocks_for((size_t)1 << t.log_n, CC_TILE);
+                if (tile >= ((uint64_t)1 << 31)) throw std::runtime_error("CTL #" + std::to_string(j) + ": too many candidate rows");
+            }
+            ntiles[s * nctls + j] = (uint32_t)tile;
+            side_off[s * nctls + j + 1] = h_sides.size();
+        }
     // (the description is judged before the context is needed: a caller without a device still learns what is wrong with it)
     if (!c) throw std::runtime_error("check_ctls: null argument");
     ZKM_HIP_CHECK(hipSetDevice(c->device));
-    // ---- the tables on the device: in place, or a copy of host memory / of one pointer per column
-    std::vector<ctl_dev_owner> desc(ntables);
+    // ---- the tables on the device: in place, or a copy of host memory / of one pointer per column.  Segments that share a table's
+    // description (the same zkm_ctl_table and width) share its device copy
+    // (what is too large for the context's pinned ring goes up straight from `held`, which outlives the call's first wait: the ring
+    // would wait for the stream first, and that wait is one of the call's)
+    std::vector<std::vector<char>> held;
     std::vector<zkm_scratch> copies;
-    std::vector<cc_tab> h_tabs(ntables, cc_tab{});
-    for (size_t t = 0; t < ntables; t++) {
-        if (!used[t]) continue;
-        const zkm_table_input& in = tables[t];
-        const size_t n = (size_t)1 << in.log_n;
-        desc[t].upload(c, in.ctl, nullptr, nullptr, 0, false, in.ncols);
-        const gl_t* d_trace = in.trace;
-        if (in.columns) {
-            copies.emplace_back(c, in.ncols * n * 8);
-            for (size_t k = 0; k < in.ncols; k++) {
-                if (!in.columns[k]) throw std::runtime_error("check_ctls: null column");
-                ZKM_HIP_CHECK(hipMemcpyAsync(copies.back().as<gl_t>() + k * n, in.columns[k], n * 8, hipMemcpyDefault, c->stream));
+    auto put = [&](void* dst, std::vector<char>&& h, size_t bytes) {
+        if (bytes <= zkm_ctx::XFER_UP / 8) return c->upload(dst, h.data(), bytes);   // (`h` may go)
+        held.push_back(std::move(h));
+        ZKM_HIP_CHECK(hipMemcpyAsync(dst, held.back().data(), bytes, hipMemcpyHostToDevice, c->stream));
+    };
+    std::vector<ctl_dev> desc;
+    std::map<std::pair<const zkm_ctl_table*, size_t>, size_t> desc_of;
+    std::vector<cc_tab> h_tabs(nseg * ntables, cc_tab{});
+    for (size_t s = 0; s < nseg; s++)
+        for (size_t t = 0; t < ntables; t++) {
+            if (!used[s * ntables + t]) continue;
+            const zkm_table_input& in = tables[s][t];
+            const size_t n = (size_t)1 << in.log_n;
+            auto found = desc_of.find({in.ctl, in.ncols});
+            if (found == desc_of.end()) {
+                std::vector<char> h;
+                const ctl_dev_packed p = ctl_dev_pack(in.ctl, nullptr, nullptr, 0, false, in.ncols, 1, h);
+                const size_t bytes = h.size();
+                copies.emplace_back(c, std::max<size_t>(bytes, 64));
+                put(copies.back().p, std::move(h), bytes);
+                desc.push_back(ctl_dev_rebase(p.d, copies.back().as<char>()));
+                found = desc_of.emplace(std::make_pair(in.ctl, in.ncols), desc.size() - 1).first;
             }
-            d_trace = copies.back().as<gl_t>();
-        } else if (!zkm_is_device_ptr(in.trace)) {
-            copies.emplace_back(c, in.ncols * n * 8);
-            ZKM_HIP_CHECK(hipMemcpyAsync(copies.back().p, in.trace, in.ncols * n * 8, hipMemcpyHostToDevice, c->stream));
-            d_trace = copies.back().as<gl_t>();
+            const gl_t* d_trace = in.trace;
+            if (in.columns) {
+                copies.emplace_back(c, in.ncols * n * 8);
+                for (size_t k = 0; k < in.ncols; k++) {
+                    if (!in.columns[k]) throw std::runtime_error("check_ctls: null column");
+                    ZKM_HIP_CHECK(hipMemcpyAsync(copies.back().as<gl_t>() + k * n, in.columns[k], n * 8, hipMemcpyDefault, c->stream));
+                }
+                d_trace = copies.back().as<gl_t>();
+            } else if (!zkm_is_device_ptr(in.trace)) {
+                copies.emplace_back(c, in.ncols * n * 8);
+                ZKM_HIP_CHECK(hipMemcpyAsync(copies.back().p, in.trace, in.ncols * n * 8, hipMemcpyHostToDevice, c->stream));
+                d_trace = copies.back().as<gl_t>();
+            }
+            h_tabs[s * ntables + t] = cc_tab{desc[found->second], d_trace, n};
         }
-        h_tabs[t] = cc_tab{desc[t].d, d_trace, n};
+    if (nctls == 0) {
+        if (ride && ride->bytes) {
+            c->download(ride->dst, ride->src, ride->bytes);
+            host_waits++;
+            stamp();
+        }
+        return nseg;
     }
-    if (nctls == 0) return 0;
-    // ---- one block for the descriptors and the jobs' result words: [tabs | sides | res (2 per job) | ver (4 per job) | report]
+    // ---- one block for the descriptors and the jobs' result words, all segments': [tabs | sides | res (2 per job) | ver (4 per job) | report]
     auto al = [](size_t x) { return (x + 63) & ~(size_t)63; };
-    const size_t o_sides = al(ntables * sizeof(cc_tab)), o_res = al(o_sides + h_sides.size() * sizeof(cc_side)), o_ver = al(o_res + nctls * 16),
-                 o_rep = al(o_ver + nctls * 32), total = o_rep + CC_REPORT_WORDS * 8;
+    const size_t o_sides = al(h_tabs.size() * sizeof(cc_tab)), o_res = al(o_sides + h_sides.size() * sizeof(cc_side)), o_ver = al(o_res + njobs * 16),
+                 o_rep = al(o_ver + njobs * 32), total = o_rep + nseg * CC_REPORT_WORDS * 8;
     zkm_scratch block(c, total);
     char* const base = block.as<char>();
     const cc_tab* d_tabs = (const cc_tab*)base;
@@ -345,49 +384,54 @@ int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables
     unsigned long long* d_res = (unsigned long long*)(base + o_res);
     unsigned long long* d_ver = (unsigned long long*)(base + o_ver);
     uint64_t* d_rep = (uint64_t*)(base + o_rep);
+    auto upload_pieces = [&](void* dst, const void* src, size_t bytes) {   // (through the context's pinned ring, in pieces it takes without a wait)
+        constexpr size_t PIECE = zkm_ctx::XFER_UP / 8;
+        for (size_t o = 0; o < bytes; o += PIECE) c->upload((char*)dst + o, (const char*)src + o, std::min(PIECE, bytes - o));
+    };
     {
         std::vector<char> h(o_ver, 0);
-        memcpy(h.data(), h_tabs.data(), ntables * sizeof(cc_tab));
+        memcpy(h.data(), h_tabs.data(), h_tabs.size() * sizeof(cc_tab));
         memcpy(h.data() + o_sides, h_sides.data(), h_sides.size() * sizeof(cc_side));
-        for (size_t j = 0; j < nctls; j++) ((uint64_t*)(h.data() + o_res))[2 * j] = CC_NONE;
-        c->upload(base, h.data(), o_ver);   // (through the context's pinned ring: `h` may go)
+        for (size_t q = 0; q < njobs; q++) ((uint64_t*)(h.data() + o_res))[2 * q] = CC_NONE;
+        put(base, std::move(h), o_ver);
     }
-    std::vector<cc_job> jobs(nctls, cc_job{});
+    std::vector<cc_job> jobs(njobs, cc_job{});
     std::vector<zkm_scratch> cnt, part;
     std::vector<scan_seg> scans;
-    for (size_t j = 0; j < nctls; j++) {
-        cnt.emplace_back(c, ((size_t)ntiles[j] + 1) * 8);
-        part.emplace_back(c, blocks_for((size_t)ntiles[j] + 1, SCAN_TILE) * 8);
-        ZKM_HIP_CHECK(hipMemsetAsync(cnt.back().as<uint64_t>() + ntiles[j], 0, 8, c->stream));
-        cc_job& J = jobs[j];
-        J.tabs = d_tabs;
-        J.sides = d_sides + side_off[j];
-        J.nsides = (uint32_t)(side_off[j + 1] - side_off[j]);
-        J.width = width[j];
-        J.ntiles = ntiles[j];
+    for (size_t q = 0; q < njobs; q++) {
+        cnt.emplace_back(c, ((size_t)ntiles[q] + 1) * 8);
+        part.emplace_back(c, blocks_for((size_t)ntiles[q] + 1, SCAN_TILE) * 8);
+        ZKM_HIP_CHECK(hipMemsetAsync(cnt.back().as<uint64_t>() + ntiles[q], 0, 8, c->stream));
+        cc_job& J = jobs[q];
+        J.tabs = d_tabs + (q / nctls) * ntables;
+        J.sides = d_sides + side_off[q];
+        J.nsides = (uint32_t)(side_off[q + 1] - side_off[q]);
+        J.width = width[q % nctls];
+        J.ntiles = ntiles[q];
         J.cnt = cnt.back().as<uint64_t>();
-        J.res = d_res + 2 * j;
-        J.ver = d_ver + 4 * j;
-        scans.push_back(scan_seg{J.cnt, (size_t)ntiles[j] + 1, part.back().as<uint64_t>(), (uint64_t*)(J.res + 1)});
+        J.res = d_res + 2 * q;
+        J.ver = d_ver + 4 * q;
+        scans.push_back(scan_seg{J.cnt, (size_t)ntiles[q] + 1, part.back().as<uint64_t>(), (uint64_t*)(J.res + 1)});
     }
     auto tiles_of = [](const cc_job& J) { return (size_t)J.ntiles; };
     launch_jobs(c, "check_ctls/count", k_cc_count, jobs, tiles_of);
     scan_jobs(c, scans);
-    std::vector<uint64_t> h_res(2 * nctls);
-    c->download(h_res.data(), d_res, nctls * 16);
-    rep->host_waits++;
+    std::vector<uint64_t> h_res(2 * njobs);
+    c->download(h_res.data(), d_res, njobs * 16);
+    host_waits++;
+    stamp();
     // ---- the records
     std::vector<zkm_scratch> store;
-    std::vector<radix_seg> rx(nctls);
-    std::vector<uint64_t*> keys_b(nctls);   // the sort's second buffers
-    std::vector<uint32_t*> idx_b(nctls);
+    std::vector<radix_seg> rx(njobs);
+    std::vector<uint64_t*> keys_b(njobs);   // the sort's second buffers
+    std::vector<uint32_t*> idx_b(njobs);
     size_t max_rec = 0;
-    scans.clear();
-    for (size_t j = 0; j < nctls; j++) {
-        const size_t nrec = (size_t)h_res[2 * j + 1];
-        if (nrec > CC_MAX_RECORDS) throw std::runtime_error("CTL #" + std::to_string(j) + ": more than 2^30 filtered rows");
+    std::vector<scan_seg> scans_sgn, scans_flg;   // (a list each: a call's launches are one segment's times ceil(jobs / ZKM_MAX_SEG))
+    for (size_t q = 0; q < njobs; q++) {
+        const size_t nrec = (size_t)h_res[2 * q + 1];
+        if (nrec > CC_MAX_RECORDS) throw std::runtime_error("CTL #" + std::to_string(q % nctls) + ": more than 2^30 filtered rows");
         max_rec = std::max(max_rec, nrec);
-        cc_job& J = jobs[j];
+        cc_job& J = jobs[q];
         J.nrec = (uint32_t)nrec;
         auto take = [&](size_t bytes) {
             store.emplace_back(c, std::max<size_t>(bytes, 64));
@@ -402,34 +446,34 @@ int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables
         J.head = (uint32_t*)take(nrec * 4);
         J.end = (uint64_t*)take(nrec * 8);
         uint32_t* hist = (uint32_t*)take(((size_t)MT_RADIX * rtiles + MT_RADIX) * 4);
-        keys_b[j] = (uint64_t*)take(2 * nrec * 8);
-        idx_b[j] = (uint32_t*)take(nrec * 4);
-        rx[j] = radix_seg{J.keys, keys_b[j], J.idx, idx_b[j], hist, hist + (size_t)MT_RADIX * rtiles, (uint32_t)nrec, rtiles, 2};
-        scans.push_back(scan_seg{J.sgn, nrec + 1, (uint64_t*)take(blocks_for(nrec + 1, SCAN_TILE) * 8), nullptr});
-        scans.push_back(scan_seg{J.flg, nrec + 1, (uint64_t*)take(blocks_for(nrec + 1, SCAN_TILE) * 8), (uint64_t*)(J.ver + 2)});
+        keys_b[q] = (uint64_t*)take(2 * nrec * 8);
+        idx_b[q] = (uint32_t*)take(nrec * 4);
+        rx[q] = radix_seg{J.keys, keys_b[q], J.idx, idx_b[q], hist, hist + (size_t)MT_RADIX * rtiles, (uint32_t)nrec, rtiles, 2};
+        scans_sgn.push_back(scan_seg{J.sgn, nrec + 1, (uint64_t*)take(blocks_for(nrec + 1, SCAN_TILE) * 8), nullptr});
+        scans_flg.push_back(scan_seg{J.flg, nrec + 1, (uint64_t*)take(blocks_for(nrec + 1, SCAN_TILE) * 8), (uint64_t*)(J.ver + 2)});
     }
     launch_jobs(c, "check_ctls/emit", k_cc_emit, jobs, tiles_of);
     auto recs_of = [](const cc_job& J) { return blocks_for(J.nrec, CC_THREADS); };
     auto recs1_of = [](const cc_job& J) { return blocks_for((size_t)J.nrec + 1, CC_THREADS); };
-    std::vector<uint64_t> h_ver(4 * nctls), ver_init(4 * nctls, 0);
-    for (size_t j = 0; j < nctls; j++) ver_init[4 * j + 1] = CC_NONE;
-    bool confirmed = false;
-    for (int attempt = 1; attempt <= CC_MAX_ATTEMPTS && !confirmed; attempt++) {
-        rep->attempts = (uint32_t)attempt;
+    std::vector<uint64_t> h_ver(4 * njobs), ver_init(4 * njobs, 0);
+    for (size_t q = 0; q < njobs; q++) ver_init[4 * q + 1] = CC_NONE;
+    for (int attempt = 1; attempt <= CC_MAX_ATTEMPTS; attempt++) {
+        attempts = (uint32_t)attempt;
         const unsigned bits = attempt == 1 && c->debug_ctl_key_bits ? std::min<unsigned>(c->debug_ctl_key_bits, CC_KEY_BITS) : CC_KEY_BITS;
-        c->upload(d_ver, ver_init.data(), nctls * 32);
+        upload_pieces(d_ver, ver_init.data(), njobs * 32);
         launch_jobs(c, "check_ctls/keys", k_cc_keys, jobs, recs_of, cc_mix(0x5a4b4d43544cull + (uint64_t)attempt), bits);
         if (max_rec) {
-            for (size_t j = 0; j < nctls; j++) {   // (every attempt starts from the buffers k_cc_keys writes)
-                rx[j].kin = jobs[j].keys;
-                rx[j].kout = keys_b[j];
-                rx[j].iin = jobs[j].idx;
-                rx[j].iout = idx_b[j];
+            for (size_t q = 0; q < njobs; q++) {   // (every attempt starts from the buffers k_cc_keys writes)
+                rx[q].kin = jobs[q].keys;
+                rx[q].kout = keys_b[q];
+                rx[q].iin = jobs[q].idx;
+                rx[q].iout = idx_b[q];
             }
-            const size_t rtiles = blocks_for(max_rec, MT_TILE);
             for (unsigned bit = 0; bit < bits; bit += 8) {
-                for (size_t g0 = 0; g0 < nctls; g0 += ZKM_MAX_SEG) {
-                    const size_t k = std::min<size_t>(ZKM_MAX_SEG, nctls - g0);
+                for (size_t g0 = 0; g0 < njobs; g0 += ZKM_MAX_SEG) {
+                    const size_t k = std::min<size_t>(ZKM_MAX_SEG, njobs - g0);
+                    size_t rtiles = 0;   // (of the group's largest job)
+                    for (size_t q = g0; q < g0 + k; q++) rtiles = std::max<size_t>(rtiles, rx[q].ntiles);
                     {
                         zkm_prof_scope ps(c, "check_ctls/radix_upsweep");
                         zkm_launch_segs(c->stream, k_radix_upsweep, rx.data() + g0, k, rtiles, MT_THREADS, bit);
@@ -443,76 +487,104 @@ int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables
                         zkm_launch_segs(c->stream, k_radix_downsweep, rx.data() + g0, k, rtiles, MT_THREADS, bit);
                     }
                 }
-                for (size_t j = 0; j < nctls; j++) {
-                    std::swap(rx[j].kin, rx[j].kout);
-                    std::swap(rx[j].iin, rx[j].iout);
+                for (size_t q = 0; q < njobs; q++) {
+                    std::swap(rx[q].kin, rx[q].kout);
+                    std::swap(rx[q].iin, rx[q].iout);
                 }
             }
         }
         std::vector<cc_job> sorted = jobs;   // the same jobs reading the buffers the last pass wrote
-        for (size_t j = 0; j < nctls; j++) {
-            sorted[j].keys = rx[j].kin;
-            sorted[j].idx = rx[j].iin;
+        for (size_t q = 0; q < njobs; q++) {
+            sorted[q].keys = rx[q].kin;
+            sorted[q].idx = rx[q].iin;
         }
         launch_jobs(c, "check_ctls/flags", k_cc_flags, sorted, recs1_of);
-        scan_jobs(c, scans);
+        scan_jobs(c, scans_sgn);
+        scan_jobs(c, scans_flg);
         launch_jobs(c, "check_ctls/mark", k_cc_mark, sorted, recs_of);
         launch_jobs(c, "check_ctls/verdict", k_cc_verdict, sorted, recs_of);
-        c->download(h_ver.data(), d_ver, nctls * 32);
-        rep->host_waits++;
-        confirmed = true;
-        for (size_t j = 0; j < nctls; j++) confirmed = confirmed && !h_ver[4 * j];
+        // (what rides along is complete behind the first attempt: a second attempt brings the verdicts alone)
+        if (attempt == 1 && ride) c->download({zkm_ctx::xfer{h_ver.data(), d_ver, njobs * 32}, *ride});
+        else c->download(h_ver.data(), d_ver, njobs * 32);
+        host_waits++;
+        stamp();
+        bool confirmed = true;
+        for (size_t q = 0; q < njobs; q++) confirmed = confirmed && !h_ver[4 * q];
         if (!confirmed) continue;
-        // ---- the lowest failing lookup; within it a non-binary filter wins
-        size_t j = 0;
-        while (j < nctls && h_res[2 * j] == CC_NONE && h_ver[4 * j + 1] == CC_NONE) j++;
-        if (j == nctls) return 0;
-        const bool nonbin = h_res[2 * j] != CC_NONE;
-        {
+        // ---- per segment the lowest failing lookup; within it a non-binary filter wins.  The reports of all failing segments come
+        // down together
+        std::vector<size_t> failing, lookup;   // segment, its lookup
+        for (size_t s = 0; s < nseg; s++) {
+            size_t j = 0;
+            while (j < nctls && h_res[2 * (s * nctls + j)] == CC_NONE && h_ver[4 * (s * nctls + j) + 1] == CC_NONE) j++;
+            if (j == nctls) continue;
+            failing.push_back(s);
+            lookup.push_back(j);
+        }
+        if (failing.empty()) return nseg;
+        ZKM_HIP_CHECK(hipMemsetAsync(d_rep, 0, failing.size() * CC_REPORT_WORDS * 8, c->stream));
+        for (size_t f = 0; f < failing.size(); f++) {
+            const size_t q = failing[f] * nctls + lookup[f];
             zkm_prof_scope ps(c, "check_ctls/report");
-            ZKM_HIP_CHECK(hipMemsetAsync(d_rep, 0, CC_REPORT_WORDS * 8, c->stream));
-            hipLaunchKernelGGL(k_cc_report, dim3(1), dim3(CC_THREADS), 0, c->stream, sorted[j], (unsigned long long)(nonbin ? h_res[2 * j] : CC_NONE),
-                               (uint32_t)h_ver[4 * j + 1], d_rep);
+            hipLaunchKernelGGL(k_cc_report, dim3(1), dim3(CC_THREADS), 0, c->stream, sorted[q], (unsigned long long)h_res[2 * q], (uint32_t)h_ver[4 * q + 1],
+                               d_rep + f * CC_REPORT_WORDS);
             ZKM_HIP_CHECK(hipGetLastError());
         }
-        uint64_t out[CC_REPORT_WORDS];
-        c->download(out, d_rep, sizeof out);
-        rep->host_waits++;
-        rep->ctl = (uint32_t)j;
-        const cc_side* js = h_sides.data() + side_off[j];
-        if (nonbin) {
-            rep->kind = 1;
-            rep->side = (uint32_t)(h_res[2 * j] >> 32);
-            rep->table = js[rep->side].table;
-            rep->row = (uint32_t)h_res[2 * j];
-            rep->filter_value = out[0];
-            *msg = "CTL #" + std::to_string(j) + ": Non-binary filter? (side " + std::to_string(rep->side) + ", table " + table_label(tables, rep->table) +
-                   ", row " + std::to_string(rep->row) + ": the filter is " + std::to_string(rep->filter_value) + ")";
-            return 1;
+        std::vector<uint64_t> h_rep(failing.size() * CC_REPORT_WORDS);
+        c->download(h_rep.data(), d_rep, h_rep.size() * 8);
+        host_waits++;
+        stamp();
+        for (size_t f = 0; f < failing.size(); f++) {
+            const size_t s = failing[f], j = lookup[f], q = s * nctls + j;
+            const uint64_t* out = h_rep.data() + f * CC_REPORT_WORDS;
+            zkm_ctl_report* rep = reps + s;
+            const zkm_table_input* tabs = tables[s];
+            rep->ctl = (uint32_t)j;
+            const cc_side* js = h_sides.data() + side_off[q];
+            if (h_res[2 * q] != CC_NONE) {
+                rep->kind = 1;
+                rep->side = (uint32_t)(h_res[2 * q] >> 32);
+                rep->table = js[rep->side].table;
+                rep->row = (uint32_t)h_res[2 * q];
+                rep->filter_value = out[0];
+                msgs[s] = "CTL #" + std::to_string(j) + ": Non-binary filter? (side " + std::to_string(rep->side) + ", table " + table_label(tabs, rep->table) +
+                          ", row " + std::to_string(rep->row) + ": the filter is " + std::to_string(rep->filter_value) + ")";
+                continue;
+            }
+            rep->kind = 2;
+            rep->width = width[j];
+            rep->nwords = std::min<uint32_t>(width[j], ZKM_CTL_REPORT_WORDS);
+            memcpy(rep->tuple, out + 3, rep->nwords * 8);
+            rep->looking_count = out[1];
+            rep->looked_count = out[2];
+            rep->nlooking_locations = (uint32_t)std::min<uint64_t>(out[1], ZKM_CTL_REPORT_LOCATIONS);
+            rep->nlooked_locations = (uint32_t)std::min<uint64_t>(out[2], ZKM_CTL_REPORT_LOCATIONS);
+            auto fill = [&](zkm_ctl_location* l, const uint64_t* w, uint32_t k) {
+                for (uint32_t i = 0; i < k; i++) l[i] = zkm_ctl_location{(uint32_t)(w[i] >> 32), js[w[i] >> 32].table, (uint32_t)w[i]};
+            };
+            fill(rep->looking, out + 3 + ZKM_CTL_REPORT_WORDS, rep->nlooking_locations);
+            fill(rep->looked, out + 3 + ZKM_CTL_REPORT_WORDS + ZKM_CTL_REPORT_LOCATIONS, rep->nlooked_locations);
+            std::string row = "[";
+            for (uint32_t k = 0; k < rep->nwords; k++) row += (k ? ", " : "") + std::to_string(rep->tuple[k]);
+            if (rep->width > rep->nwords) row += ", ...";
+            msgs[s] = "CTL #" + std::to_string(j) + ": Row " + row + "] is present " + std::to_string(out[1]) + " times in the looking tables, but " +
+                      std::to_string(out[2]) + " times in the looked table. Looking locations (Table, Row index): " +
+                      locations_text(tabs, rep->looking, rep->nlooking_locations, out[1]) + ". Looked locations (Table, Row index): " +
+                      locations_text(tabs, rep->looked, rep->nlooked_locations, out[2]) + ".";
         }
-        rep->kind = 2;
-        rep->width = width[j];
-        rep->nwords = std::min<uint32_t>(width[j], ZKM_CTL_REPORT_WORDS);
-        memcpy(rep->tuple, out + 3, rep->nwords * 8);
-        rep->looking_count = out[1];
-        rep->looked_count = out[2];
-        rep->nlooking_locations = (uint32_t)std::min<uint64_t>(out[1], ZKM_CTL_REPORT_LOCATIONS);
-        rep->nlooked_locations = (uint32_t)std::min<uint64_t>(out[2], ZKM_CTL_REPORT_LOCATIONS);
-        auto fill = [&](zkm_ctl_location* l, const uint64_t* w, uint32_t k) {
-            for (uint32_t i = 0; i < k; i++) l[i] = zkm_ctl_location{(uint32_t)(w[i] >> 32), js[w[i] >> 32].table, (uint32_t)w[i]};
-        };
-        fill(rep->looking, out + 3 + ZKM_CTL_REPORT_WORDS, rep->nlooking_locations);
-        fill(rep->looked, out + 3 + ZKM_CTL_REPORT_WORDS + ZKM_CTL_REPORT_LOCATIONS, rep->nlooked_locations);
-        std::string row = "[";
-        for (uint32_t k = 0; k < rep->nwords; k++) row += (k ? ", " : "") + std::to_string(rep->tuple[k]);
-        if (rep->width > rep->nwords) row += ", ...";
-        *msg = "CTL #" + std::to_string(j) + ": Row " + row + "] is present " + std::to_string(out[1]) + " times in the looking tables, but " +
-               std::to_string(out[2]) + " times in the looked table. Looking locations (Table, Row index): " +
-               locations_text(tables, rep->looking, rep->nlooking_locations, out[1]) + ". Looked locations (Table, Row index): " +
-               locations_text(tables, rep->looked, rep->nlooked_locations, out[2]) + ".";
-        return 2;
+        return failing[0];
     }
     throw std::runtime_error("check_ctls: the keys of different rows collided in " + std::to_string(CC_MAX_ATTEMPTS) + " attempts");
+}
+
+// ... on one segment's tables: the report's kind
+int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
+                       size_t nctls, zkm_ctl_report* rep, std::string* msg) {
+    if ((!tables && ntables) || (nctls && (!ctls || !sides))) throw std::runtime_error("check_ctls: null argument");
+    rep->attempts = 0;
+    rep->host_waits = 0;
+    zkm_check_ctls_run_segments(c, 1, &tables, ntables, ctls, sides, nctls, rep, msg);
+    return (int)rep->kind;
 }
 
 namespace {

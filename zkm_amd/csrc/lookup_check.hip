@@ -188,11 +188,7 @@ __global__ __launch_bounds__(64) void k_lc_report(zkm_seg_args<lc_job> S) {
 
 size_t blocks_for(size_t items, size_t per) { return (items + per - 1) / per; }
 
-struct lc_table {
-    int id;
-    const uint64_t* trace;
-    unsigned log_n;
-};
+using lc_table = zkm_check_table;
 
 // the host's refusals, before any device work (and before the missing context is looked at)
 void lc_refuse(const char* what, const std::string& where, const lc_table& t, size_t ncols) {
@@ -226,49 +222,40 @@ std::string lc_hex(uint64_t v) {
     return s;
 }
 
-// ntab tables in ONE set of launches on the context's stream, one download, one host wait (none when no table has a lookup):
-// findings = ntab x 9 words (host); *msg names the first table with a failing lookup and stays empty when there is none.
-void lc_run_tables(zkm_ctx* c, const lc_table* tabs, size_t ntab, uint64_t* findings, std::string* msg) {
-    auto all_hold = [&] {   // (written once the device's answer is here: a call that fails on the way leaves the caller's words alone)
-        for (size_t t = 0; t < ntab; t++) {
-            uint64_t* f = findings + t * ZKM_LOOKUP_FINDING_WORDS;
-            f[F_LOOKUP] = LC_NONE;
-            std::fill(f + 1, f + ZKM_LOOKUP_FINDING_WORDS, 0);
-        }
-    };
+}  // namespace
+
+size_t zkm_lookup_check_jobs(const zkm_check_table* tabs, size_t ntab) {
     size_t njobs = 0;
     for (size_t t = 0; t < ntab; t++) njobs += zkm_table(tabs[t].id)->nlookups;
-    if (!njobs) return all_hold();
-    std::vector<zkm_scratch> store;   // every block of the call: host tables copied up, the jobs' buffers
+    return njobs;
+}
+
+// zkm_internal.h: the launches of ntab tables (device memory, whichever segments they belong to) on the context's stream; job j's nine
+// words land at d_out + 9 j
+void zkm_lookup_check_queue(zkm_ctx* c, const zkm_check_table* tabs, size_t ntab, uint64_t* d_out, zkm_lookup_queued* queued) {
+    const size_t njobs = zkm_lookup_check_jobs(tabs, ntab);
+    queued->job_table.clear();
+    if (!njobs) return;
+    std::vector<zkm_scratch>& store = queued->store;   // every block of the call: the jobs' buffers
     auto take = [&](size_t bytes) {
         store.emplace_back(c, std::max<size_t>(bytes, 64));
         return store.back().p;
     };
-    // [vmin of every job | vcnt of every job], nine words a job
+    // [vmin of every job | vcnt of every job]
     unsigned long long* d_ver = (unsigned long long*)take(njobs * 16);
-    uint64_t* d_out = (uint64_t*)take(njobs * ZKM_LOOKUP_FINDING_WORDS * 8);
     ZKM_HIP_CHECK(hipMemsetAsync(d_ver, 0xff, njobs * 8, c->stream));
     ZKM_HIP_CHECK(hipMemsetAsync(d_ver + njobs, 0, njobs * 8, c->stream));
     std::vector<lc_job> jobs;
-    std::vector<size_t> job_table;
     std::vector<radix_seg> rx;
     std::vector<scan_seg> scans;
     for (size_t t = 0; t < ntab; t++) {
         const zkm_table_row* row = zkm_table(tabs[t].id);
-        if (!row->nlookups) continue;
-        const gl_t* d_trace = tabs[t].trace;
-        if (!zkm_is_device_ptr(tabs[t].trace)) {
-            const size_t bytes = (row->width << tabs[t].log_n) * sizeof(gl_t);
-            gl_t* copy = (gl_t*)take(bytes);
-            ZKM_HIP_CHECK(hipMemcpyAsync(copy, tabs[t].trace, bytes, hipMemcpyHostToDevice, c->stream));
-            d_trace = copy;
-        }
         for (size_t l = 0; l < row->nlookups; l++) {
             const zkm_table_lookup& L = row->lookups[l];
             const size_t j = jobs.size(), nrec = ((size_t)L.ncols + 1) << tabs[t].log_n;
             const uint32_t rtiles = (uint32_t)blocks_for(nrec, MT_TILE);
             lc_job J{};
-            J.trace = d_trace;
+            J.trace = tabs[t].trace;
             J.log_n = tabs[t].log_n;
             J.ncols = L.ncols;
             J.cols_off = LC_COLS_HOST.off[zkm_table_index(tabs[t].id)][l];
@@ -289,7 +276,7 @@ void lc_run_tables(zkm_ctx* c, const lc_table* tabs, size_t ntab, uint64_t* find
             rx.push_back(radix_seg{J.keys, (uint64_t*)take(nrec * 8), J.idx, (uint32_t*)take(nrec * 4), hist, hist + (size_t)MT_RADIX * rtiles, (uint32_t)nrec, rtiles, 1});
             for (uint64_t* v : {J.a, J.flo, J.fhi}) scans.push_back(scan_seg{v, nrec + 1, (uint64_t*)take(blocks_for(nrec + 1, SCAN_TILE) * 8), nullptr});
             jobs.push_back(J);
-            job_table.push_back(t);
+            queued->job_table.push_back(t);
         }
     }
     auto records = [](const lc_job& J) { return blocks_for(J.nrec, LC_THREADS); };
@@ -300,11 +287,11 @@ void lc_run_tables(zkm_ctx* c, const lc_table* tabs, size_t ntab, uint64_t* find
     }
     {
         zkm_prof_scope ps(c, "lookup_check/sort");
-        size_t rtiles = 0;
-        for (const radix_seg& r : rx) rtiles = std::max<size_t>(rtiles, r.ntiles);
         for (unsigned bit = 0; bit < LC_KEY_BITS; bit += 8) {
             for (size_t g0 = 0; g0 < njobs; g0 += ZKM_MAX_SEG) {
                 const size_t k = std::min<size_t>(ZKM_MAX_SEG, njobs - g0);
+                size_t rtiles = 0;   // (of the group's tallest job)
+                for (size_t j = 0; j < k; j++) rtiles = std::max<size_t>(rtiles, rx[g0 + j].ntiles);
                 zkm_launch_segs(c->stream, k_radix_upsweep, rx.data() + g0, k, rtiles, MT_THREADS, bit);
                 zkm_launch_segs(c->stream, k_radix_scan, rx.data() + g0, k, MT_RADIX, MT_THREADS);
                 zkm_launch_segs(c->stream, k_radix_downsweep, rx.data() + g0, k, rtiles, MT_THREADS, bit);
@@ -324,24 +311,53 @@ void lc_run_tables(zkm_ctx* c, const lc_table* tabs, size_t ntab, uint64_t* find
         launch_jobs(c, k_lc_verdict, jobs, LC_THREADS, records);   // (runs <= records: the lanes beyond a job's runs leave at once)
         launch_jobs(c, k_lc_report, jobs, 64, [](const lc_job&) { return 1; });
     }
-    std::vector<uint64_t> h_out(njobs * ZKM_LOOKUP_FINDING_WORDS);
-    c->download(h_out.data(), d_out, h_out.size() * 8);
-    all_hold();
+}
+
+// ... and what the downloaded job words say.  findings: written here, once the device's answer is on the host (a call that fails on the
+// way leaves the caller's words alone)
+size_t zkm_lookup_check_read(const zkm_check_table* tabs, size_t ntab, const zkm_lookup_queued& queued, const uint64_t* job_words, uint64_t* findings,
+                             std::string* msg) {
+    for (size_t t = 0; t < ntab; t++) {
+        uint64_t* f = findings + t * ZKM_LOOKUP_FINDING_WORDS;
+        f[F_LOOKUP] = LC_NONE;
+        std::fill(f + 1, f + ZKM_LOOKUP_FINDING_WORDS, 0);
+    }
     // a table's finding is that of its lowest failing lookup; the message that of the lowest failing table
     size_t first = ntab;
-    for (size_t j = njobs; j-- > 0;) {
-        const uint64_t* f = h_out.data() + j * ZKM_LOOKUP_FINDING_WORDS;
+    for (size_t j = queued.job_table.size(); j-- > 0;) {
+        const uint64_t* f = job_words + j * ZKM_LOOKUP_FINDING_WORDS;
         if (f[F_LOOKUP] == LC_NONE) continue;
-        std::copy(f, f + ZKM_LOOKUP_FINDING_WORDS, findings + job_table[j] * ZKM_LOOKUP_FINDING_WORDS);
-        first = job_table[j];
+        std::copy(f, f + ZKM_LOOKUP_FINDING_WORDS, findings + queued.job_table[j] * ZKM_LOOKUP_FINDING_WORDS);
+        first = queued.job_table[j];
     }
-    if (first == ntab) return;
+    if (first == ntab) return first;
     const uint64_t* f = findings + first * ZKM_LOOKUP_FINDING_WORDS;
     const std::string cell = f[F_COL] == LC_NONE ? "none" : "column " + std::to_string(f[F_COL]) + ", row " + std::to_string(f[F_ROW]);
     const std::string trow = f[F_TABLE_ROW] == LC_NONE ? "none" : "row " + std::to_string(f[F_TABLE_ROW]);
     *msg = std::string("Lookup failed in ") + zkm_table(tabs[first].id)->name + "Stark: lookup " + std::to_string(f[F_LOOKUP]) + ": value " + lc_hex(f[F_VALUE]) +
            " is looked up " + std::to_string(f[F_LOOKING]) + " times (first: " + cell + ") and has frequency " + lc_hex(f[F_FREQ]) + " in " +
            std::to_string(f[F_ROWS]) + " table rows (first: " + trow + "); " + std::to_string(f[F_VALUES]) + " values fail";
+    return first;
+}
+
+namespace {
+
+// ntab tables in ONE set of launches on the context's stream, one download, one host wait (none when no table has a lookup):
+// findings = ntab x 9 words (host); *msg names the first table with a failing lookup and stays empty when there is none.
+void lc_run_tables(zkm_ctx* c, const lc_table* tabs, size_t ntab, uint64_t* findings, std::string* msg) {
+    const size_t njobs = zkm_lookup_check_jobs(tabs, ntab);
+    std::vector<zkm_scratch> copies;   // host tables are copied up for the call
+    std::vector<lc_table> d_tabs(tabs, tabs + ntab);
+    for (size_t t = 0; t < ntab; t++)
+        if (zkm_table(tabs[t].id)->nlookups) d_tabs[t].trace = zkm_check_table_on_device(c, tabs[t], copies);
+    zkm_lookup_queued queued;
+    std::vector<uint64_t> h_out(njobs * ZKM_LOOKUP_FINDING_WORDS);
+    if (njobs) {
+        zkm_scratch d_out(c, std::max<size_t>(h_out.size() * 8, 64));
+        zkm_lookup_check_queue(c, d_tabs.data(), ntab, d_out.as<uint64_t>(), &queued);
+        c->download(h_out.data(), d_out.p, h_out.size() * 8);
+    }
+    zkm_lookup_check_read(tabs, ntab, queued, h_out.data(), findings, msg);
 }
 
 // refusals first, then the context, then the run; a finding is a failure of the call with its message

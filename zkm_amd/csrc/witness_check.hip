@@ -55,19 +55,32 @@ static_assert(WC_MAX_LOG_N + WC_INDEX_BITS < 64, "row << 16 | index is one 64-bi
 enum { F_ROW = 0, F_INDEX = 1, F_VALUE = 2, F_ROWS = 3, F_COUNT = 4 };   // the finding's words; F_ROW holds the key between the launches
 static_assert(F_COUNT + 1 == ZKM_WITNESS_FINDING_WORDS, "five words a finding");
 
+// One descriptor per (segment, table of this kind): it travels in kernel-argument slot blockIdx.z (zkm_seg_args), the grid's x extent is
+// the tallest table's and the workgroups beyond a segment's own height leave at once.  f: the segment's OWN five words -- only its lanes
+// write them.
+struct wc_seg {
+    const gl_t* trace;
+    unsigned long long* f;
+    unsigned log_n;
+};
+static_assert(sizeof(zkm_seg_args<wc_seg>) + 8 <= 3840, "the descriptors travel as kernel arguments");
+
 // named = 0: the grid covers the n rows; f[F_ROW] <- min key, f[F_ROWS] += failing rows, f[F_COUNT] <- constraints per row (by row 0).
 // named = 1: one lane, on the row of the key the first launch left: f[F_ROW], f[F_INDEX], f[F_VALUE] <- the finding.  Nothing to do
 // when no row failed (the key is still all ones: the row word of "every constraint holds").
 template <int TABLE>
-__global__ __launch_bounds__(WC_THREADS) void k_witness_check(const gl_t* __restrict__ trace, unsigned log_n, unsigned long long* __restrict__ f, int named) {
-    const size_t n = (size_t)1 << log_n;
+__global__ __launch_bounds__(WC_THREADS) void k_witness_check(zkm_seg_args<wc_seg> S, int named) {
+    const wc_seg& J = S.v[blockIdx.z];
+    const gl_t* __restrict__ trace = J.trace;
+    unsigned long long* __restrict__ f = J.f;
+    const size_t n = (size_t)1 << J.log_n;
     size_t r = (size_t)blockIdx.x * WC_THREADS + threadIdx.x;
     if (named) {
         const unsigned long long key = f[F_ROW];
         if (threadIdx.x != 0 || key == WC_NONE) return;
         r = (size_t)(key >> WC_INDEX_BITS);
     }
-    if (r >= n) return;   // (a table shorter than a workgroup; a key is always a row of the table)
+    if (r >= n) return;   // (a table shorter than the tallest of the launch, or than a workgroup; a key is always a row of the table)
     consumer_t<0> k;
     k.start(r, n);
     eval_table_constraints<TABLE, 0>(trace + r, n, (ptrdiff_t)((r + 1) & (n - 1)) - (ptrdiff_t)r, k);
@@ -86,11 +99,7 @@ __global__ __launch_bounds__(WC_THREADS) void k_witness_check(const gl_t* __rest
     }
 }
 
-struct wc_table {
-    int id;
-    const uint64_t* trace;
-    unsigned log_n;
-};
+using wc_table = zkm_check_table;
 
 // the host's refusals, before any device work (and before the missing context is looked at)
 void wc_refuse(const char* what, const std::string& where, const wc_table& t, size_t ncols) {
@@ -102,37 +111,37 @@ void wc_refuse(const char* what, const std::string& where, const wc_table& t, si
     if (t.log_n > WC_MAX_LOG_N) throw std::runtime_error(std::string(what) + ": " + where + "log_n " + std::to_string(t.log_n) + " above " + std::to_string(WC_MAX_LOG_N));
 }
 
-// ntab tables in ONE set of launches on the context's stream, one download, one host wait: findings = ntab x 5 words (host); *msg names
-// the first table with a failing row and stays empty when there is none.
-void wc_run(zkm_ctx* c, const char* what, const wc_table* tabs, size_t ntab, uint64_t* findings, std::string* msg) {
-    std::vector<zkm_scratch> copies;   // host tables are copied up for the call
-    std::vector<const gl_t*> d_trace(ntab);
-    for (size_t t = 0; t < ntab; t++) {
-        d_trace[t] = tabs[t].trace;
-        if (zkm_is_device_ptr(tabs[t].trace)) continue;
-        const size_t bytes = (zkm_table(tabs[t].id)->width << tabs[t].log_n) * sizeof(gl_t);
-        copies.emplace_back(c, bytes);
-        ZKM_HIP_CHECK(hipMemcpyAsync(copies.back().p, tabs[t].trace, bytes, hipMemcpyHostToDevice, c->stream));
-        d_trace[t] = copies.back().as<gl_t>();
-    }
+}  // namespace
+
+// zkm_internal.h: the launches of ntab tables (device memory) into d_find = ntab x 5 words, queued on the context's stream: per table
+// KIND one `rows` and one `name` launch for up to ZKM_MAX_SEG tables of that kind, whichever segments they belong to
+void zkm_witness_check_queue(zkm_ctx* c, const zkm_check_table* tabs, size_t ntab, uint64_t* d_find) {
     const size_t words = ntab * ZKM_WITNESS_FINDING_WORDS;
-    std::vector<uint64_t> init(words, 0);
-    for (size_t t = 0; t < ntab; t++) init[t * ZKM_WITNESS_FINDING_WORDS + F_ROW] = WC_NONE;
-    zkm_scratch d_find(c, std::max<size_t>(words * 8, 64));
-    c->upload(d_find.p, init.data(), words * 8);
-    for (int named = 0; named < 2; named++) {
-        zkm_prof_scope ps(c, named ? "witness_check/name" : "witness_check/rows");
-        for (size_t t = 0; t < ntab; t++) {
-            const size_t n = (size_t)1 << tabs[t].log_n;
-            const unsigned grid = named ? 1u : (unsigned)((n + WC_THREADS - 1) / WC_THREADS);
-            unsigned long long* f = d_find.as<unsigned long long>() + t * ZKM_WITNESS_FINDING_WORDS;
-            zkm_with_table(tabs[t].id, [&](auto T) {
-                hipLaunchKernelGGL(k_witness_check<decltype(T)::value>, dim3(grid), dim3(named ? 64u : WC_THREADS), 0, c->stream, d_trace[t], tabs[t].log_n, f, named);
-            });
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
+    {
+        std::vector<uint64_t> init(words, 0);
+        for (size_t t = 0; t < ntab; t++) init[t * ZKM_WITNESS_FINDING_WORDS + F_ROW] = WC_NONE;
+        for (size_t o = 0, step = zkm_ctx::XFER_UP / 8 / 8; o < words; o += step)   // (pieces the pinned ring takes without a wait)
+            c->upload(d_find + o, init.data() + o, std::min(step, words - o) * 8);
     }
-    c->download(findings, d_find.p, words * 8);
+    std::vector<std::vector<wc_seg>> kinds(ZKM_NUM_TABLES);   // the tables of each kind, in the caller's order
+    for (size_t t = 0; t < ntab; t++)
+        kinds[zkm_table_index(tabs[t].id)].push_back(wc_seg{tabs[t].trace, (unsigned long long*)d_find + t * ZKM_WITNESS_FINDING_WORDS, tabs[t].log_n});
+    for (int named = 0; named < 2; named++)
+        for (int e = 0; e < ZKM_NUM_TABLES; e++)
+            for (size_t g0 = 0; g0 < kinds[e].size(); g0 += ZKM_MAX_SEG) {
+                const size_t k = std::min<size_t>(ZKM_MAX_SEG, kinds[e].size() - g0);
+                unsigned tallest = 0;
+                for (size_t j = 0; j < k; j++) tallest = std::max(tallest, kinds[e][g0 + j].log_n);
+                const size_t grid = named ? 1 : (((size_t)1 << tallest) + WC_THREADS - 1) / WC_THREADS;
+                zkm_prof_scope ps(c, named ? "witness_check/name" : "witness_check/rows");
+                zkm_with_table(zkm_table_at(e)->id, [&](auto T) {
+                    zkm_launch_segs(c->stream, k_witness_check<decltype(T)::value>, kinds[e].data() + g0, k, grid, named ? 64u : WC_THREADS, named);
+                });
+            }
+}
+
+// ... and what the downloaded words say: the first table with a failing row (ntab: none), its message in *msg
+size_t zkm_witness_check_read(const char* what, const zkm_check_table* tabs, size_t ntab, const uint64_t* findings, std::string* msg) {
     size_t first = ntab;
     for (size_t t = ntab; t-- > 0;) {
         const uint64_t* f = findings + t * ZKM_WITNESS_FINDING_WORDS;
@@ -147,6 +156,22 @@ void wc_run(zkm_ctx* c, const char* what, const wc_table* tabs, size_t ntab, uin
                std::to_string(f[F_INDEX]) + " of " + std::to_string(f[F_COUNT]) + " = " + value + " (" + std::to_string(f[F_ROWS]) + " of " +
                std::to_string((uint64_t)1 << tabs[first].log_n) + " rows fail)";
     }
+    return first;
+}
+
+namespace {
+
+// ntab tables in ONE set of launches on the context's stream, one download, one host wait: findings = ntab x 5 words (host); *msg names
+// the first table with a failing row and stays empty when there is none.
+void wc_run(zkm_ctx* c, const char* what, const wc_table* tabs, size_t ntab, uint64_t* findings, std::string* msg) {
+    std::vector<zkm_scratch> copies;   // host tables are copied up for the call
+    std::vector<wc_table> d_tabs(tabs, tabs + ntab);
+    for (size_t t = 0; t < ntab; t++) d_tabs[t].trace = zkm_check_table_on_device(c, tabs[t], copies);
+    const size_t words = ntab * ZKM_WITNESS_FINDING_WORDS;
+    zkm_scratch d_find(c, std::max<size_t>(words * 8, 64));
+    zkm_witness_check_queue(c, d_tabs.data(), ntab, d_find.as<uint64_t>());
+    c->download(findings, d_find.p, words * 8);
+    zkm_witness_check_read(what, tabs, ntab, findings, msg);
 }
 
 // refusals first, then the context, then the run; a finding is a failure of the call with the reference's message

@@ -119,6 +119,7 @@ struct zkm_ctx {
     zkm_ctx* parent = nullptr;          // of a commit lane: the context that owns it
     std::atomic<int> debug_fail_allocs{0};   // test hook (root context only): pretend the next k hipMalloc first attempts fail
     int check_ctls = 0;                 // the prove drivers run check_ctls on each segment's tables before they prove (ctl_check.hip)   } zkm_ctx_set_tuning
+    int check_witness = 0;              // the prove drivers run the three witness checks on each wave's segments before they commit (segment_check.hip)   } zkm_ctx_set_tuning
     unsigned debug_ctl_key_bits = 0;    // test hook: the FIRST attempt of a check_ctls call sorts by keys truncated to this many bits (0: off)
     int verify = 0;                     // the prove drivers verify every segment's blobs before they hand them out (verify.hip)   } zkm_ctx_set_tuning
     uint64_t debug_verify_flip = 0;     // test hook: under `verify`, this word of one segment's blobs is changed before it is verified (0: off)
@@ -635,10 +636,56 @@ void zkm_insn_rows_check(zkm_insn_job& j);
 size_t zkm_insn_rows_scratch(const zkm_insn_job* j, size_t nseg);
 void zkm_insn_rows_launch(zkm_ctx* c, const zkm_insn_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold);
 
-// ctl_check.hip: check_ctls on one segment's tables.  Returns the report's kind (0 consistent, 1 non-binary filter, 2 multisets differ)
-// with the reference's message in *msg; throws when the check cannot be made
+// ---- the three witness checks (witness_check.hip, lookup_check.hip, ctl_check.hip), each in two parts so that segment_check.hip can put
+// them behind ONE pair of host waits: a part that QUEUES its launches on the context's stream into result words the caller names, and a
+// part that READS those words once they are on the host.  A table of a check: registry id, column-major trace, height.
+struct zkm_check_table {
+    int id;
+    const uint64_t* trace;
+    unsigned log_n;
+};
+// the table's trace on the device: in place, or a copy of host memory queued on the stream and owned by `copies`
+inline const uint64_t* zkm_check_table_on_device(zkm_ctx* c, const zkm_check_table& t, std::vector<zkm_scratch>& copies) {
+    if (zkm_is_device_ptr(t.trace)) return t.trace;
+    const size_t bytes = (zkm_table(t.id)->width << t.log_n) * sizeof(gl_t);
+    copies.emplace_back(c, bytes);
+    ZKM_HIP_CHECK(hipMemcpyAsync(copies.back().p, t.trace, bytes, hipMemcpyHostToDevice, c->stream));
+    return copies.back().as<uint64_t>();
+}
+// witness_check.hip: ntab tables (device memory, any segments' in any order), d_find = ntab x ZKM_WITNESS_FINDING_WORDS device words; per
+// table kind one `rows` and one `name` launch per ZKM_MAX_SEG tables of that kind.  read: the first table with a failing row (ntab: none)
+// and its message
+void zkm_witness_check_queue(zkm_ctx* c, const zkm_check_table* tabs, size_t ntab, uint64_t* d_find);
+size_t zkm_witness_check_read(const char* what, const zkm_check_table* tabs, size_t ntab, const uint64_t* findings, std::string* msg);
+// lookup_check.hip: one job per (table, lookup) of the ntab tables (device memory), every launch serves ZKM_MAX_SEG jobs; d_out =
+// zkm_lookup_check_jobs x ZKM_LOOKUP_FINDING_WORDS device words (none queued when there is no job).  `queued` owns the jobs' scratch until
+// the stream has been waited for.  read: findings = ntab x ZKM_LOOKUP_FINDING_WORDS (every table's own result) from the downloaded job
+// words; the first table with a failing lookup (ntab: none) and its message
+struct zkm_lookup_queued {
+    std::vector<zkm_scratch> store;
+    std::vector<size_t> job_table;   // the table of each job
+};
+size_t zkm_lookup_check_jobs(const zkm_check_table* tabs, size_t ntab);
+void zkm_lookup_check_queue(zkm_ctx* c, const zkm_check_table* tabs, size_t ntab, uint64_t* d_out, zkm_lookup_queued* queued);
+size_t zkm_lookup_check_read(const zkm_check_table* tabs, size_t ntab, const zkm_lookup_queued& queued, const uint64_t* job_words, uint64_t* findings,
+                             std::string* msg);
+// ctl_check.hip: check_ctls on the tables of nseg segments (tables[s]: ntables inputs) in ONE set of launches: nseg x nctls jobs over one
+// descriptor block, ZKM_MAX_SEG jobs a launch; one download for the record counts, one per attempt for the verdicts, one for the reports
+// of all failing segments.  reps[s] / msgs[s]: segment s's report and the reference's message (kind 0: consistent, message empty);
+// attempts and host_waits are the CALL's in every report.  `ride` (may be null): a download of the caller's that travels with the FIRST
+// attempt's verdicts -- the words of checks queued in front of this call cost no wait of their own.  Returns the lowest failing segment
+// (nseg: none); throws when the check cannot be made
+size_t zkm_check_ctls_run_segments(zkm_ctx* c, size_t nseg, const zkm_table_input* const* tables, size_t ntables, const zkm_cross_table_lookup* ctls,
+                                   const zkm_ctl_side* sides, size_t nctls, zkm_ctl_report* reps, std::string* msgs, const zkm_ctx::xfer* ride = nullptr);
+// ... on one segment's tables.  Returns the report's kind (0 consistent, 1 non-binary filter, 2 multisets differ) with the reference's
+// message in *msg; throws when the check cannot be made
 int zkm_check_ctls_run(zkm_ctx* c, const zkm_table_input* tables, size_t ntables, const zkm_cross_table_lookup* ctls, const zkm_ctl_side* sides,
                        size_t nctls, zkm_ctl_report* rep, std::string* msg);
+// segment_check.hip: the three checks on nseg AllStark segments behind two host waits (the body of zkm_segments_check).  tables[s]: the
+// twelve inputs in Table::all() order, `trace` set (host or device).  Outputs as zkm_segments_check's (any may be null).  Returns the lowest
+// segment with a finding (nseg: none) and its message; throws when the check cannot be made
+size_t zkm_segments_check_run(zkm_ctx* c, size_t nseg, const zkm_table_input* const* tables, uint64_t* verdicts, uint64_t* witness_findings,
+                              uint64_t* lookup_findings, zkm_ctl_report* ctl_reports, std::string* msg);
 // ---- the verifier (verify.hip; the constraint evaluation on the line through the opening lives beside k_quotient in stark.hip)
 // per-table CtlZData lists in cross_table_lookup_data order (ctl.hip): the prover's derivation, which the verifier replays
 struct table_zs {
