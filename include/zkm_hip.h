@@ -1306,6 +1306,8 @@ int zkm_prove_openings(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_batc
  * ReducingFactor::shift_poly; commit phase with one cap + beta per reduction arity; final polynomial; proof of work; query rounds.
  * (The openings themselves are the caller's: observe them before the call, as StarkOpeningSet / OpeningSet do.)  With the three
  * STARK oracles and the three batches of stark.rs:91-148 the output equals the FRI part of zkm_prove_openings' blob.
+ * cfg->rate_bits may be 2 or 3 here and in zkm_fri_verify (3: plonky2's standard_recursion_config; the oracles are committed at the
+ * same rate); the STARK entry points take 2 only.
  * FRI proof blob: [0] magic "ZKMFRIPF" [1] degree_bits [2] noracles [3] cap_height [4] L fri layers [5] F final_poly_len
  *   [6] num_queries [7] rate_bits [8] arity_bits [9..15] 0 [16..23] columns of each oracle
  *   commit_phase_merkle_caps[L][C*4]  final_poly[2F]  pow_witness[1]
@@ -1549,6 +1551,38 @@ int zkm_verify_segments(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, 
 int zkm_verify_single_table(zkm_ctx* ctx, int table_id, const zkm_stark_config* cfg, const uint64_t* proof, size_t proof_words, size_t ncols,
                             size_t naux, const uint32_t* num_helpers, size_t nctl_zs, zkm_challenger* challenger, zkm_verify_report* report,
                             char** err);
+/* The mirror of zkm_fri_prove: plonky2's verify_fri_proof (fri/verifier.rs; call sites verifier.rs:276-289, and in circuit form
+ * recursive_verifier.rs:426) for ANY FriInstanceInfo, on nproofs FRI proof blobs (magic "ZKMFRIPF") in one set of launches behind one
+ * upload and before one download: one host wait whatever nproofs.  Claims of different heights and instances share a call.  Claim i:
+ *   proofs[i], proof_words[i]   the blob zkm_fri_prove wrote, HOST memory            log_n[i]   degree bits of the instance
+ *   oracle_cols[i], noracles[i] columns of each initial oracle, 1..8 oracles
+ *   oracle_caps[i]              noracles[i] pointers: each oracle's cap, 2^cap_height digests (zkm_batch_cap), host
+ *   batches[i], nbatches[i]     the instance exactly as zkm_fri_prove takes it, 1..8 batches
+ *   opened[i]                   nbatches[i] pointers: opened[i][b] = batches[i][b].npolys F2 values (2 words each), the claimed p(point) in
+ *                               the batch's polynomial order, e.g. from zkm_eval_openings; host
+ *   challengers[i]              in/out: the state zkm_fri_prove was entered with; advanced to the state zkm_fri_prove leaves only when
+ *                               claim i is accepted, untouched otherwise (as in zkm_verify_single_table)
+ * (The claims travel as parallel arrays, as zkm_verify_segments' segments do.)
+ * Transcript: the one zkm_fri_prove writes, replayed on the host from the blob alone: alpha is drawn; per layer the cap is observed and
+ * beta drawn; the final polynomial is observed; the proof-of-work witness is applied; the query indices are drawn.
+ * reports (nproofs entries, may be NULL): code is one of OK, SHAPE, POW, INITIAL_MERKLE, FRI_EVAL, FRI_MERKLE, FINAL_POLY, FAILED;
+ * table = 0, tree = the oracle's index, query / layer / host_waits as above (host_waits 1 for a claim that was launched, 0 for one
+ * refused on the host).  WHICH finding is reported follows plonky2's order: POW; then the lowest query, and inside it the oracles'
+ * Merkle proofs in ascending order, per layer the evaluation check before the Merkle proof, then the final polynomial.
+ * Returns 0 iff every claim is accepted; otherwise *err names the first rejected claim
+ * ("zkm_fri_verify: proof 3: query 5: Invalid Merkle proof. (initial oracle 2) [INITIAL_MERKLE]").
+ * SHAPE (found on the host: such a claim reaches no kernel): wrong magic; header words [1..8] and [16..23] that are not what cfg, log_n,
+ * oracle_cols and noracles give; proof_words below the blob's size; a word of the blob, an opened value, a cap word or a point >= p.
+ * FAILED (the call could not be made, every report says so): a NULL pointer or nproofs == 0; a polynomial index out of range, an empty
+ * batch, more than 8 oracles or batches; a base-field point on the LDE coset ((z / g)^(2^lde_bits) == 1: plonky2 would divide by
+ * zero); a device pointer; a configuration zkm_blob_describe refuses.  A refusal or a rejection leaves the context usable and its
+ * live memory as it was.
+ * Out of scope: PLONK's own checks (vanishing polynomial, partial products, public inputs); deriving the openings; compressed FRI
+ * proofs; the pool; running this check under the "verify" tuning key behind zkm_fri_prove, which has neither caps nor openings at hand. */
+int zkm_fri_verify(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nproofs, const uint64_t* const* proofs, const size_t* proof_words,
+                   const unsigned* log_n, const size_t* const* oracle_cols, const size_t* noracles, const uint64_t* const* const* oracle_caps,
+                   const zkm_fri_batch* const* batches, const size_t* nbatches, const uint64_t* const* const* opened,
+                   zkm_challenger* const* challengers, zkm_verify_report* reports, char** err);
 
 /* a9: StarkOpeningSet::new building block (proof.rs:299-334): p(zeta) in F2 for every polynomial of the
  * batch; out = ncols x 2 words, host. */

@@ -10,6 +10,8 @@
 //!   `trace_commitment.get_lde_values_packed(i_start, step)`                                                  prover.rs:687, :723-748
 //!   `c.polynomials` (coefficients, for StarkOpeningSet::new and check_constraints)                          proof.rs:310-320, prover.rs:824-830
 //!   `PolynomialBatch::prove_openings(&instance, &initial_merkle_trees, challenger, &fri_params, timing)`    prover.rs:621-627
+//!   `verify_fri_proof::<F, C, D>(&instance, &openings, &challenges, &merkle_caps, &proof, &fri_params)`      verifier.rs:276-289
+//!       -> `verify_fri_proof_hip` below: the same arguments with the challenger in place of the precomputed `FriChallenges`
 //!
 //! `HipPolynomialBatch<F, C, D>` has the same constructors and accessors with the same argument lists; what is a field in plonky2
 //! (`merkle_tree.cap`, `polynomials`) is a method here (`cap()`, `polynomials()`), because the data lives in HBM and comes to the host
@@ -26,7 +28,7 @@ use crate::field::polynomial::{PolynomialCoeffs, PolynomialValues};
 use crate::field::types::{Field, PrimeField64};
 use crate::fri::proof::{FriInitialTreeProof, FriProof, FriQueryRound, FriQueryStep};
 use crate::fri::reduction_strategies::FriReductionStrategy;
-use crate::fri::structure::{FriBatchInfo, FriInstanceInfo};
+use crate::fri::structure::{FriBatchInfo, FriInstanceInfo, FriOpenings};
 use crate::fri::FriParams;
 use crate::hash::hash_types::{HashOut, RichField};
 use crate::hash::merkle_proofs::MerkleProof;
@@ -294,4 +296,121 @@ where
         .collect();
     assert_eq!(at, blob.len(), "FRI proof blob has trailing words");
     FriProof { commit_phase_merkle_caps, query_round_proofs, final_poly, pow_witness }
+}
+
+/// `FriProof` -> the FRI proof blob zkm_fri_verify reads (the inverse of `fri_proof_from_blob`; include/zkm_hip.h "FRI proof blob").
+pub fn fri_proof_to_blob<F, C, const D: usize>(proof: &FriProof<F, C::Hasher, D>, cfg: &zkm_stark_config, log_n: u32, oracle_cols: &[usize]) -> Vec<u64>
+where
+    F: RichField + Extendable<D>,
+    C: GenericConfig<D, F = F>,
+    C::Hasher: Hasher<F, Hash = HashOut<F>>,
+{
+    let mut blob = vec![0u64; 24];
+    blob[0] = 0x4650_4952_464d_4b5a;
+    blob[1] = log_n as u64;
+    blob[2] = oracle_cols.len() as u64;
+    blob[3] = cfg.cap_height as u64;
+    blob[4] = proof.commit_phase_merkle_caps.len() as u64;
+    blob[5] = proof.final_poly.coeffs.len() as u64;
+    blob[6] = cfg.num_queries as u64;
+    blob[7] = cfg.rate_bits as u64;
+    blob[8] = cfg.arity_bits as u64;
+    for (o, &n) in oracle_cols.iter().enumerate() {
+        blob[16 + o] = n as u64;
+    }
+    let digests = |blob: &mut Vec<u64>, hs: &[HashOut<F>]| hs.iter().for_each(|h| blob.extend(h.elements.iter().map(|e| e.to_canonical_u64())));
+    let ext = |blob: &mut Vec<u64>, vs: &[F::Extension]| {
+        vs.iter().for_each(|v| {
+            let c: [F; D] = v.to_basefield_array();
+            blob.extend(c.iter().map(|e| e.to_canonical_u64()))
+        })
+    };
+    for cap in &proof.commit_phase_merkle_caps {
+        digests(&mut blob, &cap.0);
+    }
+    ext(&mut blob, &proof.final_poly.coeffs);
+    blob.push(proof.pow_witness.to_canonical_u64());
+    for round in &proof.query_round_proofs {
+        for (evals, path) in &round.initial_trees_proof.evals_proofs {
+            blob.extend(evals.iter().map(|e| e.to_canonical_u64()));
+            digests(&mut blob, &path.siblings);
+        }
+        for step in &round.steps {
+            ext(&mut blob, &step.evals);
+            digests(&mut blob, &step.merkle_proof.siblings);
+        }
+    }
+    blob
+}
+
+/// plonky2's `verify_fri_proof` (fri/verifier.rs; call site verifier.rs:276-289) on the GPU: one `zkm_fri_verify` call with one claim.
+/// Takes what `verify_fri_proof` takes -- instance, openings, the initial oracles' caps, the proof, the parameters -- and the
+/// challenger in place of the precomputed `FriChallenges`: it must stand where `prove_openings` was entered (openings observed), and
+/// is advanced to where the prover's stood afterwards only when the proof is accepted.  `degree_bits` is the instance's height
+/// (`FriParams::degree_bits`).  Err carries the library's message, which names the check plonky2 fails at.
+pub fn verify_fri_proof_hip<F, C, const D: usize>(
+    ctx: *mut zkm_ctx,
+    instance: &FriInstanceInfo<F, D>,
+    openings: &FriOpenings<F, D>,
+    challenger: &mut Challenger<F, C::Hasher>,
+    initial_merkle_caps: &[MerkleCap<F, C::Hasher>],
+    proof: &FriProof<F, C::Hasher, D>,
+    params: &FriParams,
+) -> anyhow::Result<()>
+where
+    F: RichField + Extendable<D>,
+    C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
+{
+    assert!(D == 2, "libzkmhip implements the quadratic extension of Goldilocks");
+    let cfg = fri_config_words(params);
+    let log_n = params.degree_bits as u32;
+    let first = proof.query_round_proofs.first().ok_or_else(|| anyhow::anyhow!("FRI proof without query rounds"))?;
+    let oracle_cols: Vec<usize> = first.initial_trees_proof.evals_proofs.iter().map(|(evals, _)| evals.len()).collect();
+    let blob = fri_proof_to_blob::<F, C, D>(proof, &cfg, log_n, &oracle_cols);
+    let caps: Vec<Vec<u64>> = initial_merkle_caps.iter().map(|c| c.0.iter().flat_map(|h| h.elements.iter().map(|e| e.to_canonical_u64())).collect()).collect();
+    let cap_ptrs: Vec<*const u64> = caps.iter().map(|c| c.as_ptr()).collect();
+    let polys: Vec<Vec<zkm_fri_poly>> = instance
+        .batches
+        .iter()
+        .map(|b: &FriBatchInfo<F, D>| b.polynomials.iter().map(|p| zkm_fri_poly { oracle: p.oracle_index as u32, poly: p.polynomial_index as u32 }).collect())
+        .collect();
+    let batches: Vec<zkm_fri_batch> = instance
+        .batches
+        .iter()
+        .zip(&polys)
+        .map(|(b, ps)| {
+            let c: [F; D] = b.point.to_basefield_array();
+            zkm_fri_batch { point: [c[0].to_canonical_u64(), c[1].to_canonical_u64()], polys: ps.as_ptr(), npolys: ps.len() }
+        })
+        .collect();
+    let opened: Vec<Vec<u64>> = openings
+        .batches
+        .iter()
+        .map(|b| {
+            b.values
+                .iter()
+                .flat_map(|v| {
+                    let c: [F; D] = v.to_basefield_array();
+                    c.into_iter().map(|e| e.to_canonical_u64())
+                })
+                .collect()
+        })
+        .collect();
+    let opened_ptrs: Vec<*const u64> = opened.iter().map(|o| o.as_ptr()).collect();
+    let mut ch = challenger.to_zkm();
+    let (proofs, words, heights) = ([blob.as_ptr()], [blob.len()], [log_n]);
+    let (cols, noracles, caps_of) = ([oracle_cols.as_ptr()], [oracle_cols.len()], [cap_ptrs.as_ptr()]);
+    let (batches_of, nbatches, opened_of) = ([batches.as_ptr()], [batches.len()], [opened_ptrs.as_ptr()]);
+    let challengers = [&mut ch as *mut zkm_challenger];
+    let mut report = zkm_verify_report::default();
+    let mut err = std::ptr::null_mut();
+    check(
+        unsafe {
+            zkm_fri_verify(ctx, &cfg, 1, proofs.as_ptr(), words.as_ptr(), heights.as_ptr(), cols.as_ptr(), noracles.as_ptr(), caps_of.as_ptr(),
+                           batches_of.as_ptr(), nbatches.as_ptr(), opened_of.as_ptr(), challengers.as_ptr(), &mut report, &mut err)
+        },
+        err,
+    )?;
+    challenger.set_from_zkm(&ch);
+    Ok(())
 }

@@ -491,6 +491,10 @@ extern "C" {
     pub fn zkm_verify_single_table(ctx: *mut zkm_ctx, table_id: c_int, cfg: *const zkm_stark_config, proof: *const u64, proof_words: usize,
                                    ncols: usize, naux: usize, num_helpers: *const u32, nctl_zs: usize, challenger: *mut zkm_challenger,
                                    report: *mut zkm_verify_report, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_fri_verify(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, nproofs: usize, proofs: *const *const u64, proof_words: *const usize,
+                          log_n: *const c_uint, oracle_cols: *const *const usize, noracles: *const usize, oracle_caps: *const *const *const u64,
+                          batches: *const *const zkm_fri_batch, nbatches: *const usize, opened: *const *const *const u64,
+                          challengers: *const *mut zkm_challenger, reports: *mut zkm_verify_report, err: *mut *mut c_char) -> c_int;
     pub fn zkm_check_constraints(ctx: *mut zkm_ctx, table_id: c_int, cfg: *const zkm_stark_config, trace: *const u64, ncols: usize, log_n: c_uint,
                                  aux: *const u64, naux: usize, table: *const zkm_ctl_table, zs: *const zkm_ctl_z, colset_ids: *const u32,
                                  nzs: usize, lookup_challenges: *const u64, alphas: *const u64, nalphas: usize, first_failing_row: *mut u64,

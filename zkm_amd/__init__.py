@@ -92,6 +92,16 @@ class FriBatch(C.Structure):
     _fields_ = [("point", C.c_uint64 * 2), ("polys", C.c_void_p), ("npolys", C.c_size_t)]
 
 
+class FriClaim:
+    """One claim of Context.fri_verify (zkm_fri_verify): the FRI proof blob of fri_prove, the instance it was made for -- log_n, the
+    columns and the cap of each oracle, batches as fri_prove takes them -- the opened values (opened[b] = 2 * npolys words, the claimed
+    p(point) of batch b's polynomials in the batch's order) and the challenger fri_prove was entered with (in/out)."""
+
+    def __init__(self, proof, log_n, oracle_cols, oracle_caps, batches, opened, challenger, proof_words=None):
+        self.proof, self.log_n, self.oracle_cols, self.oracle_caps = proof, log_n, list(oracle_cols), list(oracle_caps)
+        self.batches, self.opened, self.challenger, self.proof_words = list(batches), list(opened), challenger, proof_words
+
+
 # zkm_segment_ops (include/zkm_hip.h): per group of fields, the data pointers (with the bytes of one item of each) and the count
 SEGMENT_OPS_GROUPS = [
     ("cpu_rows", [("cpu_rows", 259 * 8)], "ncpu_rows"),
@@ -2105,7 +2115,9 @@ class Context:
         """The reports of a verify call; a call that could not be made (FAILED) raises.  The message belongs to the first rejection."""
         msg = err.value.decode() if err.value else None
         if rc != 0 and (not reps or all(r.code in (VERIFY_OK, VERIFY_FAILED) for r in reps)):
-            raise ZkmError(msg or "verify: error %d" % rc)
+            e = ZkmError(msg or "verify: error %d" % rc)
+            e.reports = reps
+            raise e
         for r in reps:
             if r.code != VERIFY_OK:
                 r.message = msg
@@ -2267,6 +2279,45 @@ class Context:
         _check(self.L.zkm_fri_prove(self.h, C.byref(cfg), C.cast(orc, C.POINTER(C.c_void_p)), len(oracles), C.cast(arr, C.c_void_p), len(batches),
                                     C.byref(challenger), out.ctypes.data_as(u64p), C.byref(err)), err)
         return out
+
+    def fri_verify(self, claims, cfg=None):
+        """zkm_fri_verify: plonky2's verify_fri_proof for any FriInstanceInfo, on all claims in one set of launches.  claims = list of
+        FriClaim.  Returns one VerifyReport per claim (the first rejected one carries .message); a call that could not be made raises
+        ZkmError.  An accepted claim's challenger is advanced to the state fri_prove left; a rejected claim's is untouched."""
+        cfg = cfg or self.standard_config()
+        K = len(claims)
+        keep = []
+
+        def words(a):
+            keep.append(np.ascontiguousarray(a, dtype=np.uint64))
+            return keep[-1].ctypes.data
+
+        def pointers(addresses):
+            keep.append((C.c_void_p * len(addresses))(*addresses))
+            return C.addressof(keep[-1])
+        proofs = [np.ascontiguousarray(cl.proof, dtype=np.uint64) for cl in claims]
+        pp = (C.c_void_p * K)(*[p.ctypes.data for p in proofs])
+        pw = (C.c_size_t * K)(*[p.size if cl.proof_words is None else cl.proof_words for p, cl in zip(proofs, claims)])
+        lg = (C.c_uint * K)(*[int(cl.log_n) for cl in claims])
+        cols = [(C.c_size_t * len(cl.oracle_cols))(*cl.oracle_cols) for cl in claims]
+        cc = (C.c_void_p * K)(*[C.addressof(a) for a in cols])
+        no = (C.c_size_t * K)(*[len(cl.oracle_cols) for cl in claims])
+        caps = (C.c_void_p * K)(*[pointers([words(cap) for cap in cl.oracle_caps]) for cl in claims])
+        barrs = []
+        for cl in claims:
+            arr = (FriBatch * len(cl.batches))()
+            for i, (pt, polys) in enumerate(cl.batches):
+                a = np.array(polys, dtype=np.uint32).reshape(-1, 2)
+                keep.append(a)
+                arr[i] = FriBatch((C.c_uint64 * 2)(int(pt[0]), int(pt[1])), a.ctypes.data, len(a))
+            barrs.append(arr)
+        bb = (C.c_void_p * K)(*[C.addressof(a) for a in barrs])
+        nb = (C.c_size_t * K)(*[len(cl.batches) for cl in claims])
+        opened = (C.c_void_p * K)(*[pointers([words(o) for o in cl.opened]) for cl in claims])
+        chs = (C.c_void_p * K)(*[C.addressof(cl.challenger) for cl in claims])
+        reps, err = (VerifyReport * K)(), C.c_char_p()
+        rc = self.L.zkm_fri_verify(self.h, C.byref(cfg), K, pp, pw, lg, cc, no, caps, bb, nb, opened, chs, reps, C.byref(err))
+        return self._verify_reports(rc, list(reps), err)
 
     def prove_openings(self, trace_batch, aux_batch, quot_batch, nctl_zs, challenger=None, cfg=None):
         """PolynomialBatch::prove_openings for the STARK FRI instance on three existing commitments (BASELINE config 4)."""

@@ -75,6 +75,16 @@ struct zkm_blob_desc {
 };
 // (cfg, log_n, W, A, Z) -> description; validates the configuration and throws on one the library does not support (stark.hip)
 zkm_blob_desc zkm_blob_describe(const zkm_stark_config* cfg, unsigned log_n, size_t W, size_t A, size_t Z);
+// the FRI-only blob of zkm_fri_prove: 24 header words (its own magic, the oracles' column counts from word 16), then the FRI part;
+// validates like zkm_blob_describe (stark.hip)
+#define ZKM_FRI_BLOB_HEADER_WORDS 24
+zkm_fri_part zkm_fri_blob_describe(const zkm_stark_config* cfg, unsigned log_n, const size_t* cols, size_t noracles);
+inline void zkm_fri_blob_header_write(uint64_t* p, const zkm_stark_config* cfg, unsigned log_n, const zkm_fri_part& y) {
+    const uint64_t h[ZKM_FRI_BLOB_HEADER_WORDS] = {ZKM_FRI_PROOF_MAGIC, log_n, y.round.noracles, cfg->cap_height, y.round.L, y.F, cfg->num_queries,
+                                                   cfg->rate_bits, cfg->arity_bits};
+    memcpy(p, h, sizeof h);
+    for (uint64_t k = 0; k < y.round.noracles; k++) p[16 + k] = y.round.cols[k];
+}
 // the 16 header words; a caller reading a header it did not write validates what it got
 inline void zkm_blob_header_write(uint64_t* p, const zkm_blob_desc& d) {
     const uint64_t h[16] = {ZKM_PROOF_MAGIC, d.log_n, d.W, d.A, d.Q, d.Z, d.cap_height, d.L, d.F, d.nq, d.rate_bits, d.arity_bits, 0, 0, 0, 0};

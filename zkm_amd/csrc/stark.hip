@@ -26,10 +26,13 @@ static unsigned fri_num_layers(const zkm_stark_config* c, unsigned degree_bits) 
 // Every field of the caller's config is checked once, here, before any allocation or transcript mutation (zkm_blob_describe is the
 // first thing every prove entry point and zkm_proof_words call).  The quotient kernels carry at most two alpha accumulators
 // (StarkConfig::num_challenges = 2 in standard_fast_config, config.rs:17-30).
-static void validate_config(const zkm_stark_config* c, unsigned log_n) {
+// fri_only: the FRI-only entry points (zkm_fri_prove, zkm_fri_verify) also take rate_bits = 3, the rate of plonky2's
+// standard_recursion_config: nothing behind them -- commitments, LDEs, folding, query rounds -- is tied to the quotient domain's rate.
+static void validate_config(const zkm_stark_config* c, unsigned log_n, bool fri_only = false) {
     if (!c) throw std::runtime_error("stark config: null");
     if (log_n == 0 || log_n > 32) throw std::runtime_error("stark config: degree_bits out of range");
-    if (c->rate_bits != 2) throw std::runtime_error("stark config: only rate_bits = 2 is supported");
+    if (fri_only && c->rate_bits != 2 && c->rate_bits != 3) throw std::runtime_error("stark config: rate_bits must be 2 or 3 for a FRI proof of its own");
+    if (!fri_only && c->rate_bits != 2) throw std::runtime_error("stark config: only rate_bits = 2 is supported");
     if (c->arity_bits < 2 || c->arity_bits > 6) throw std::runtime_error("stark config: arity_bits must be in 2..6");
     if (c->pow_bits == 0 || c->pow_bits > 32) throw std::runtime_error("stark config: proof_of_work_bits must be in 1..32");
     if (c->num_challenges < 1 || c->num_challenges > 2) throw std::runtime_error("stark config: num_challenges must be 1 or 2");
@@ -1622,12 +1625,12 @@ __global__ __launch_bounds__(256) void k_fri_combine_generic(const gl_t* const* 
     c1[i] = a1;
 }
 
-// the FRI-only blob of zkm_fri_prove: 24 header words (its own magic, the oracles' column counts from word 16), then the FRI part
-static zkm_fri_part fri_blob_describe(const zkm_stark_config* cfg, unsigned log_n, const size_t* cols, size_t noracles) {
-    validate_config(cfg, log_n);
+// the FRI-only blob of zkm_fri_prove (proof_blob.h)
+zkm_fri_part zkm_fri_blob_describe(const zkm_stark_config* cfg, unsigned log_n, const size_t* cols, size_t noracles) {
+    validate_config(cfg, log_n, /*fri_only=*/true);
     if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error("zkm_fri_prove: 1..8 oracles");
     const unsigned L = fri_num_layers(cfg, log_n);
-    zkm_fri_part y{24, (size_t)4 << cfg->cap_height, (size_t)1 << (log_n - L * cfg->arity_bits), cfg->num_queries,
+    zkm_fri_part y{ZKM_FRI_BLOB_HEADER_WORDS, (size_t)4 << cfg->cap_height, (size_t)1 << (log_n - L * cfg->arity_bits), cfg->num_queries,
                    zkm_query_round{{}, noracles, L, log_n + cfg->rate_bits, cfg->cap_height, cfg->arity_bits}};
     std::copy(cols, cols + noracles, y.round.cols);
     return y;
@@ -1709,7 +1712,7 @@ int zkm_consumer_selftest(zkm_ctx* c, const uint64_t* alphas, size_t nalphas, co
 
 size_t zkm_fri_proof_words(const zkm_stark_config* cfg, unsigned log_n, const size_t* oracle_cols, size_t noracles) {
     zkm_fri_part y{};   // (0 = unsupported configuration)
-    return zkm_api("zkm_fri_proof_words", nullptr, [&] { y = fri_blob_describe(cfg, log_n, oracle_cols, noracles); }) ? 0 : y.total();
+    return zkm_api("zkm_fri_proof_words", nullptr, [&] { y = zkm_fri_blob_describe(cfg, log_n, oracle_cols, noracles); }) ? 0 : y.total();
 }
 
 int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles, const zkm_fri_batch* batches,
@@ -1726,7 +1729,7 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
             if (oracles[k]->nseg != 1) throw std::runtime_error("zkm_fri_prove: stacked batches are internal");
             cols[k] = oracles[k]->ncols;
         }
-        const zkm_fri_part y = fri_blob_describe(cfg, log_n, cols, noracles);
+        const zkm_fri_part y = zkm_fri_blob_describe(cfg, log_n, cols, noracles);
         const size_t n = (size_t)1 << log_n;
         size_t maxp = 0;
         for (size_t b = 0; b < nbatches; b++) {
@@ -1738,9 +1741,7 @@ int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* cons
             maxp = std::max(maxp, batches[b].npolys);
         }
         memset(proof, 0, y.total() * sizeof(uint64_t));
-        proof[0] = ZKM_FRI_PROOF_MAGIC; proof[1] = log_n; proof[2] = noracles; proof[3] = cfg->cap_height; proof[4] = y.round.L; proof[5] = y.F;
-        proof[6] = cfg->num_queries; proof[7] = cfg->rate_bits; proof[8] = cfg->arity_bits;
-        for (size_t k = 0; k < noracles; k++) proof[16 + k] = cols[k];
+        zkm_fri_blob_header_write(proof, cfg, log_n, y);
 
         zkm_transcripts tr(ch_io);
         const std::vector<uint64_t*> blobs{proof};

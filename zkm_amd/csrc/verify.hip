@@ -17,6 +17,13 @@
 //   verify/reduce         first finding per (segment, table) in the fixed order
 // behind ONE upload (the parameter block with every CTL description, then the blobs) and before ONE download: the constraint
 // accumulators and the reduced verdicts.  The quotient comparison is finished on the host.
+//
+// zkm_fri_verify (below the STARK verifier): plonky2's verify_fri_proof for ANY FriInstanceInfo, the mirror of zkm_fri_prove.  The chains
+// and the reduction are the kernels above, working from zkm_verify_chains (zkm_internal.h), of which the STARK blob is the case of three
+// initial trees; the query arithmetic is
+//   verify/fri_instance_queries  one thread per (claim, query): fri_combine_initial through the batches' (oracle, polynomial) lists, then
+//                                the layers and the final polynomial as verify/fri_queries runs them (fri_query_layers)
+// All claims of a call share one upload, one set of launches and one download.
 #include <iterator>
 #include <memory>
 
@@ -46,56 +53,55 @@ __global__ __launch_bounds__(256) void k_verify_rows(const zkm_verify_table* __r
 }
 
 // One Merkle chain: the leaf's `len` words, `nsib` siblings, the leaf's index, the cap it must reach, and where its verdict goes.
-// Chains of one (segment, table) are numbered tree-major -- all queries of the trace tree, of the auxiliary tree, of the quotient
-// tree, then of each FRI layer -- so that the chains sharing a wave have leaves of the same length.
+// Chains of one entry (zkm_verify_chains: a (segment, table), or a claim of zkm_fri_verify) are numbered tree-major -- all queries of
+// initial tree 0, of tree 1, .., then of each FRI layer -- so that the chains sharing a wave have leaves of the same length.
 struct chain_t {
     const gl_t *leaf, *sib, *cap;
     uint32_t len, nsib, index, slot;
 };
-__device__ __forceinline__ bool chain_setup(const zkm_verify_table& T, const gl_t* __restrict__ blobs, const uint32_t* __restrict__ xs, uint32_t idx,
+__device__ __forceinline__ bool chain_setup(const zkm_verify_chains& E, const gl_t* __restrict__ blobs, const uint32_t* __restrict__ xs, uint32_t idx,
                                             chain_t& ch) {
-    const uint32_t nq = (uint32_t)T.d.nq;
-    if (idx >= nq * (3 + (uint32_t)T.d.L)) return false;
+    const zkm_query_round& R = E.fri.round;
+    const uint32_t nq = (uint32_t)E.fri.nq, initial = (uint32_t)R.noracles;
+    if (idx >= nq * E.trees()) return false;
     const uint32_t tree = idx / nq, q = idx - tree * nq;
-    const uint32_t x = xs[T.xs + q];
-    const gl_t* blob = blobs + T.blob;
-    const zkm_fri_part P = T.d.fri();
-    const zkm_query_round& R = P.round;
-    const gl_t* qr = blob + P.o_query(q);
+    const uint32_t x = xs[E.xs + q];
+    const gl_t* blob = blobs + E.blob;
+    const gl_t* qr = blob + E.fri.o_query(q);
     uint32_t slot;
-    if (tree < 3) {
-        ch.len = (uint32_t)(tree == 0 ? R.cols[0] : tree == 1 ? R.cols[1] : R.cols[2]);
-        ch.leaf = qr + (tree == 0 ? R.oracle_evals(0) : tree == 1 ? R.oracle_evals(1) : R.oracle_evals(2));
+    if (tree < initial) {
+        ch.len = (uint32_t)R.cols[tree];
+        ch.leaf = qr + R.oracle_evals(tree);
         ch.nsib = (uint32_t)R.initial_siblings();
         ch.index = x;
-        ch.cap = blob + T.d.o_cap(tree);
+        ch.cap = blobs + E.caps + tree * E.fri.cap_words;
         slot = tree;
     } else {
-        const uint32_t l = tree - 3;
+        const uint32_t l = tree - initial;
         ch.len = (uint32_t)R.layer_values();
         ch.leaf = qr + R.layer_evals(l);
         ch.nsib = (uint32_t)R.layer_sibling_count(l);
         ch.index = x >> ((uint32_t)R.arity_bits * (l + 1));
-        ch.cap = blob + P.o_cap(l);
-        slot = 4 + 2 * l;
+        ch.cap = blob + E.fri.o_cap(l);
+        slot = E.slot_layer_eval(l) + 1;
     }
     ch.sib = ch.leaf + ch.len;
-    ch.slot = T.verdicts + q * T.slots + slot;
+    ch.slot = E.verdicts + q * E.slots() + slot;
     return true;
 }
 
 // a chain per quad of lanes (poseidon_lat_dev.h): lane q holds state words q, q + 4, q + 8.  Every lane of a wave takes part in every
 // permutation (DPP), so the wave runs as many steps as its longest chain and a finished chain keeps its state.
-__global__ __launch_bounds__(256) void k_verify_chains_quad(const zkm_verify_table* __restrict__ tabs, const gl_t* __restrict__ blobs,
+__global__ __launch_bounds__(256) void k_verify_chains_quad(const zkm_verify_chains* __restrict__ ents, const gl_t* __restrict__ blobs,
                                                             const uint32_t* __restrict__ xs, uint32_t* __restrict__ verdicts) {
-    const zkm_verify_table& T = tabs[blockIdx.y];
-    if (blockIdx.x * 64u >= (uint32_t)T.d.nq * (3 + (uint32_t)T.d.L)) return;   // (uniform over the workgroup)
+    const zkm_verify_chains& E = ents[blockIdx.y];
+    if (blockIdx.x * 64u >= (uint32_t)E.fri.nq * E.trees()) return;   // (uniform over the workgroup)
     __shared__ __attribute__((aligned(16))) uint32_t qtab[ZKM_QUAD_TAB_WORDS];
     quad_tab_load(qtab);
     const poseidon_quad Q(threadIdx.x, qtab);
     const unsigned ql = threadIdx.x & 3;
     chain_t ch{};
-    const bool live = chain_setup(T, blobs, xs, (blockIdx.x * 256u + threadIdx.x) >> 2, ch);
+    const bool live = chain_setup(E, blobs, xs, (blockIdx.x * 256u + threadIdx.x) >> 2, ch);
     const uint32_t nabsorb = !live || ch.len <= 4 ? 0 : (ch.len + 7) / 8;   // hash_or_noop: a leaf of <= 4 words is its own digest
     const uint32_t steps = live ? nabsorb + ch.nsib : 0;
     uint32_t most = steps;
@@ -129,11 +135,10 @@ __global__ __launch_bounds__(256) void k_verify_chains_quad(const zkm_verify_tab
 }
 
 // a chain per lane: calls of so many chains that they fill the machine
-__global__ __launch_bounds__(256) void k_verify_chains(const zkm_verify_table* __restrict__ tabs, const gl_t* __restrict__ blobs,
+__global__ __launch_bounds__(256) void k_verify_chains(const zkm_verify_chains* __restrict__ ents, const gl_t* __restrict__ blobs,
                                                        const uint32_t* __restrict__ xs, uint32_t* __restrict__ verdicts) {
-    const zkm_verify_table& T = tabs[blockIdx.y];
     chain_t ch{};
-    if (!chain_setup(T, blobs, xs, blockIdx.x * 256u + threadIdx.x, ch)) return;
+    if (!chain_setup(ents[blockIdx.y], blobs, xs, blockIdx.x * 256u + threadIdx.x, ch)) return;
     uint64_t s[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) s[i] = 0;
@@ -190,19 +195,41 @@ __device__ gl2_t compute_evaluation(gl_t x, uint32_t within, uint32_t arity_bits
     return gl2_scalar_mul(gl2_mul(acc, zb), gl_inv(gl_mul((gl_t)m, sm)));
 }
 
+// the layers and the final polynomial of one query (fri_verifier_query_round after fri_combine_initial): per layer the evaluation check
+// and compute_evaluation, then the final polynomial at the last point.  v: the query's verdict word of layer 0's evaluation check (a
+// layer's Merkle path has the word between two of them), beta(l): layer l's challenge
+template <class Beta>
+__device__ __forceinline__ void fri_query_layers(const zkm_fri_part& P, const gl_t* blob, const gl_t* qr, uint32_t x, gl_t sub_x, gl2_t old_eval, Beta beta,
+                                                 uint32_t* v) {
+    const zkm_query_round& R = P.round;
+    const uint32_t L = (uint32_t)R.L, arity_bits = (uint32_t)R.arity_bits, arity = 1u << arity_bits;
+    for (uint32_t l = 0; l < L; l++) {
+        const gl_t* o = qr + R.layer_evals(l);
+        const uint32_t within = x & (arity - 1);
+        v[2 * l] = gl2_eq(ld2(o + 2 * (size_t)within), old_eval) ? 0u : 1u;
+        old_eval = compute_evaluation(sub_x, within, arity_bits, o, beta(l));
+        sub_x = gl_exp_pow2(sub_x, arity_bits);
+        x >>= arity_bits;
+    }
+    const gl_t* fp = blob + P.o_final();
+    gl2_t fe{0, 0};
+    for (uint32_t i = (uint32_t)P.F; i-- > 0;) fe = gl2_add(gl2_scalar_mul(fe, sub_x), ld2(fp + 2 * (size_t)i));
+    v[2 * L] = gl2_eq(fe, old_eval) ? 0u : 1u;
+}
+
 __global__ __launch_bounds__(64) void k_verify_fri(const zkm_verify_table* __restrict__ tabs, const gl_t* __restrict__ blobs,
                                                    const uint32_t* __restrict__ xs, uint32_t* __restrict__ verdicts) {
     const zkm_verify_table& T = tabs[blockIdx.y];
     const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
     const zkm_blob_desc& d = T.d;
     if (q >= (uint32_t)d.nq) return;
-    uint32_t x = xs[T.xs + q];
+    const uint32_t x = xs[T.xs + q];
     const gl_t* blob = blobs + T.blob;
     const zkm_fri_part P = d.fri();
     const zkm_query_round& R = P.round;
     const gl_t* qr = blob + P.o_query(q);
-    const uint32_t W = (uint32_t)d.W, A = (uint32_t)d.A, NQ = (uint32_t)d.Q, Z = (uint32_t)d.Z, L = (uint32_t)d.L;
-    const uint32_t lde_bits = (uint32_t)d.lde_bits(), arity_bits = (uint32_t)d.arity_bits, arity = 1u << arity_bits;
+    const uint32_t W = (uint32_t)d.W, A = (uint32_t)d.A, NQ = (uint32_t)d.Q, Z = (uint32_t)d.Z;
+    const uint32_t lde_bits = (uint32_t)d.lde_bits();
     const gl_t *ev0 = qr + R.oracle_evals(0), *ev1 = qr + R.oracle_evals(1), *ev2 = qr + R.oracle_evals(2);
     uint32_t* v = verdicts + T.verdicts + q * T.slots;
     const gl2_t fa = ld2(T.fri_alpha), apow_wa = ld2(T.apow_wa);
@@ -214,7 +241,7 @@ __global__ __launch_bounds__(64) void k_verify_fri(const zkm_verify_table* __res
     for (uint32_t c = NQ; c-- > 0;) redq = horner_base(redq, fa, ev2[c]);
     for (uint32_t c = A; c-- > A - Z;) redz = horner_base(redz, fa, ev1[c]);
     const gl2_t red0 = gl2_add(red1, gl2_mul(apow_wa, redq));
-    gl_t sub_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(lde_bits), bitrev32(x, lde_bits)));
+    const gl_t sub_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(lde_bits), bitrev32(x, lde_bits)));
     auto over = [&](gl2_t red, const gl_t* opened, gl2_t point) {
         gl2_t den{gl_sub(sub_x, point.c0), gl_neg(point.c1)};
         return gl2_mul(gl2_sub(red, ld2(opened)), gl2_inv(den));
@@ -222,30 +249,66 @@ __global__ __launch_bounds__(64) void k_verify_fri(const zkm_verify_table* __res
     gl2_t sum = over(red0, T.red_open[0], ld2(T.zeta));
     sum = gl2_add(gl2_mul(sum, apow_wa), over(red1, T.red_open[1], ld2(T.zeta_next)));
     sum = gl2_add(gl2_mul(sum, ld2(T.apow_z)), over(redz, T.red_open[2], gl2_t{1, 0}));
-    gl2_t old_eval = sum;
-    for (uint32_t l = 0; l < L; l++) {
-        const gl_t* o = qr + R.layer_evals(l);
-        const uint32_t within = x & (arity - 1);
-        v[3 + 2 * l] = gl2_eq(ld2(o + 2 * (size_t)within), old_eval) ? 0u : 1u;
-        old_eval = compute_evaluation(sub_x, within, arity_bits, o, ld2(T.betas[l]));
-        sub_x = gl_exp_pow2(sub_x, arity_bits);
-        x >>= arity_bits;
-    }
-    const gl_t* fp = blob + P.o_final();
-    gl2_t fe{0, 0};
-    for (uint32_t i = (uint32_t)d.F; i-- > 0;) fe = gl2_add(gl2_scalar_mul(fe, sub_x), ld2(fp + 2 * (size_t)i));
-    v[3 + 2 * L] = gl2_eq(fe, old_eval) ? 0u : 1u;
+    fri_query_layers(P, blob, qr, x, sub_x, sum, [&](uint32_t l) { return ld2(T.betas[l]); }, v + 3);
 }
 
-// first finding of a (segment, table): the lowest query, and inside it the lowest slot -- trace, auxiliary, quotient tree, per layer
-// evaluation then Merkle path, the final polynomial (the slots are numbered in that order); ~0 when every check passed
-__global__ __launch_bounds__(256) void k_verify_reduce(const zkm_verify_table* __restrict__ tabs, const uint32_t* __restrict__ verdicts,
+// One claim of zkm_fri_verify as its query kernel sees it, beside the claim's zkm_verify_chains: what the transcript replay gave and the
+// instance.  A batch's polynomials are `npolys` words of the call's list from `first` on: each the word offset of the polynomial's value
+// inside a query round (its oracle's row, its column), so the kernel reads the values through the (oracle, poly) list without knowing
+// the oracles.  The reduced openings and the alpha powers are worked out once per claim, on the host.
+constexpr uint32_t FRI_CLAIM_BATCHES = 8;   // FRI_MAX_BATCHES of zkm_fri_prove (stark.hip)
+struct fri_claim_batch {
+    gl_t point[2], red_open[2], shift[2];   // the opening point, the alpha-reduction of the opened values, alpha^npolys
+    uint32_t first, npolys;
+};
+struct fri_claim_dev {
+    gl_t alpha[2], betas[ZKM_FRI_HEADER_LAYERS][2];
+    uint32_t nbatches, reserved;
+    fri_claim_batch b[FRI_CLAIM_BATCHES];
+};
+#define ZKM_CONSTANT_AS __attribute__((address_space(4)))
+
+// plonky2 fri_verifier_query_round without the Merkle proofs, for any instance: one thread per (claim, query).  fri_combine_initial
+// (fri/verifier.rs): per batch in instance order the alpha-reduction of its polynomials' values at x, minus the batch's reduced opening,
+// over (x - point); ReducingFactor::shift chains the batches by alpha^npolys -- what k_fri_combine_generic and shift_poly do in
+// zkm_fri_prove.  Everything the lanes of a claim share -- the description, the challenges, the batches and their polynomial lists -- is
+// uniform over the workgroup and went up before the launch: it is read through the constant address space (scalar loads), as the calls'
+// expansions read their descriptors (zkm_seg_desc).  A base-field point on the LDE coset is refused on the host: x - point is never 0.
+__global__ __launch_bounds__(64) void k_fri_verify_queries(const zkm_verify_chains* __restrict__ ents, const fri_claim_dev* __restrict__ claims,
+                                                           const uint32_t* __restrict__ polys, const gl_t* __restrict__ blobs,
+                                                           const uint32_t* __restrict__ xs, uint32_t* __restrict__ verdicts) {
+    const zkm_verify_chains& E = ents[blockIdx.y];
+    const ZKM_CONSTANT_AS fri_claim_dev* K = (const ZKM_CONSTANT_AS fri_claim_dev*)claims + blockIdx.y;
+    const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= (uint32_t)E.fri.nq) return;
+    const uint32_t x = xs[E.xs + q], lde_bits = (uint32_t)E.fri.round.lde_bits;
+    const gl_t* blob = blobs + E.blob;
+    const gl_t* qr = blob + E.fri.o_query(q);
+    const gl_t sub_x = gl_mul(GL_GENERATOR, gl_pow(gl_root_of_unity(lde_bits), bitrev32(x, lde_bits)));
+    const gl2_t alpha{K->alpha[0], K->alpha[1]};
+    gl2_t sum{0, 0};
+    const uint32_t nbatches = K->nbatches;
+    for (uint32_t b = 0; b < nbatches; b++) {
+        const ZKM_CONSTANT_AS uint32_t* at = (const ZKM_CONSTANT_AS uint32_t*)polys + K->b[b].first;
+        gl2_t red{0, 0};
+        for (uint32_t j = K->b[b].npolys; j-- > 0;) red = horner_base(red, alpha, qr[at[j]]);
+        const gl2_t den{gl_sub(sub_x, K->b[b].point[0]), gl_neg(K->b[b].point[1])};
+        const gl2_t term = gl2_mul(gl2_sub(red, gl2_t{K->b[b].red_open[0], K->b[b].red_open[1]}), gl2_inv(den));
+        sum = gl2_add(gl2_mul(sum, gl2_t{K->b[b].shift[0], K->b[b].shift[1]}), term);
+    }
+    fri_query_layers(E.fri, blob, qr, x, sub_x, sum, [&](uint32_t l) { return gl2_t{K->betas[l][0], K->betas[l][1]}; },
+                     verdicts + E.verdicts + q * E.slots() + E.slot_layer_eval(0));
+}
+
+// first finding of an entry: the lowest query, and inside it the lowest slot -- the initial trees in order, per layer evaluation then
+// Merkle path, the final polynomial (zkm_verify_chains numbers the slots in that order); ~0 when every check passed
+__global__ __launch_bounds__(256) void k_verify_reduce(const zkm_verify_chains* __restrict__ ents, const uint32_t* __restrict__ verdicts,
                                                        uint32_t* __restrict__ first) {
-    const zkm_verify_table& T = tabs[blockIdx.x];
+    const zkm_verify_chains& T = ents[blockIdx.x];
     __shared__ uint32_t best;
     if (threadIdx.x == 0) best = ~0u;
     __syncthreads();
-    const uint32_t n = (uint32_t)T.d.nq * T.slots;
+    const uint32_t n = (uint32_t)T.fri.nq * T.slots();
     uint32_t mine = ~0u;
     for (uint32_t i = threadIdx.x; i < n && mine == ~0u; i += blockDim.x)
         if (verdicts[T.verdicts + i]) mine = i;
@@ -449,6 +512,40 @@ void check_ctl_sums(const zkm_stark_config* cfg, const verify_input& in, size_t 
     }
 }
 
+// The Merkle chains of a call's nent entries, ONE launch.  The hash chains do not depend on each other or on the arithmetic; a call of
+// few chains costs the longest chain's latency (the Keccak table's leaf: 304 permutations), so it takes the four-lane form of the
+// permutation; one that fills the machine one lane.  most_chains: the largest entry's chains, nchains: the call's
+void launch_chains(zkm_ctx* c, const zkm_verify_chains* d_ents, size_t nent, uint32_t most_chains, size_t nchains, const gl_t* d_blobs,
+                   const uint32_t* d_xs, uint32_t* d_verdicts) {
+    zkm_prof_scope ps(c, "verify/merkle_chains");
+    if (nchains <= c->quad_max_hashes)
+        hipLaunchKernelGGL(k_verify_chains_quad, dim3((most_chains + 63) / 64, (unsigned)nent), dim3(256), 0, c->stream, d_ents, d_blobs, d_xs, d_verdicts);
+    else
+        hipLaunchKernelGGL(k_verify_chains, dim3((most_chains + 255) / 256, (unsigned)nent), dim3(256), 0, c->stream, d_ents, d_blobs, d_xs, d_verdicts);
+    ZKM_HIP_CHECK(hipGetLastError());
+}
+void launch_reduce(zkm_ctx* c, const zkm_verify_chains* d_ents, size_t nent, const uint32_t* d_verdicts, uint32_t* d_first) {
+    zkm_prof_scope ps(c, "verify/reduce");
+    hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)nent), dim3(256), 0, c->stream, d_ents, d_verdicts, d_first);
+    ZKM_HIP_CHECK(hipGetLastError());
+}
+// a first finding of k_verify_reduce -> the report's query, tree and layer, the code and the reference's wording (`who`: what the
+// message starts with)
+struct query_finding {
+    uint32_t code, query, tree, layer;
+    std::string text;
+};
+query_finding decode_finding(uint32_t f, const zkm_verify_chains& E, const std::string& who) {
+    const uint32_t q = f / E.slots(), slot = f % E.slots(), initial = (uint32_t)E.fri.round.noracles;
+    const std::string at = who + "query " + std::to_string(q) + ": ";
+    if (slot < initial) return {ZKM_VERIFY_INITIAL_MERKLE, q, slot, 0, at + "Invalid Merkle proof. (initial oracle " + std::to_string(slot) + ")"};
+    if (slot == E.slot_final()) return {ZKM_VERIFY_FINAL_POLY, q, 0, 0, at + "Final polynomial evaluation is invalid."};
+    const uint32_t layer = (slot - initial) / 2;
+    if ((slot - initial) % 2 == 0)
+        return {ZKM_VERIFY_FRI_EVAL, q, 0, layer, at + "FRI layer " + std::to_string(layer) + ": the opened evaluation is not the folded one"};
+    return {ZKM_VERIFY_FRI_MERKLE, q, 0, layer, at + "Invalid Merkle proof. (FRI layer " + std::to_string(layer) + ")"};
+}
+
 // `fixed`: the single-table form -- no transcript seeding, no CTL challenges and sums; *fixed holds the table's CtlZData list and
 // `start` the caller's challenger (advanced only when the proof is accepted)
 void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const verify_input* in, size_t ntables, const zkm_cross_table_lookup* ctls,
@@ -504,6 +601,7 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
     if (tabs.empty()) return;   // (every segment was refused on the host: nothing is launched)
 
     const size_t nent = tabs.size();
+    std::vector<zkm_verify_chains> ents(nent);
     size_t blob_words = 0, row_words = 0, nverdicts = 0, nchains = 0;
     for (size_t k = 0; k < launched.size(); k++) {
         const seg_state& S = segs[launched[k]];
@@ -514,7 +612,9 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
             T.verdicts = (uint32_t)nverdicts;
             row_words += (size_t)ZKM_VERIFY_LINE_POINTS * 2 * (T.d.W + T.d.A);
             nverdicts += (size_t)T.d.nq * T.slots;
-            nchains += (size_t)T.d.nq * (3 + T.d.L);
+            // the STARK blob: three initial trees -- trace, auxiliary, quotient -- whose caps lie in the blob
+            ents[S.first_entry + t] = zkm_verify_chains{T.blob, T.blob + T.d.o_cap(0), T.d.fri(), T.xs, T.verdicts};
+            nchains += (size_t)T.d.nq * ents[S.first_entry + t].trees();
         }
         blob_words += S.ts[ntables - 1].off + S.ts[ntables - 1].y.total();
     }
@@ -528,10 +628,11 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
         std::vector<uint64_t> lookup_ch, rows_off, acc_off;
         std::vector<gl_t> alphas;
     };
-    const size_t tab_bytes = nent * sizeof(zkm_verify_table), xs_bytes = (xs.size() * 4 + 15) & ~(size_t)15;
-    std::vector<char> params(tab_bytes + xs_bytes, 0);   // (alive until the download: the copy may read it after the call that queues it)
+    const size_t tab_bytes = nent * sizeof(zkm_verify_table), ent_bytes = nent * sizeof(zkm_verify_chains), xs_bytes = (xs.size() * 4 + 15) & ~(size_t)15;
+    std::vector<char> params(tab_bytes + ent_bytes + xs_bytes, 0);   // (alive until the download: the copy may read it after the call that queues it)
     memcpy(params.data(), tabs.data(), tab_bytes);
-    if (!xs.empty()) memcpy(params.data() + tab_bytes, xs.data(), xs.size() * 4);
+    memcpy(params.data() + tab_bytes, ents.data(), ent_bytes);
+    if (!xs.empty()) memcpy(params.data() + tab_bytes + ent_bytes, xs.data(), xs.size() * 4);
     std::vector<line_launch> lines;
     for (size_t g0 = 0; g0 < launched.size(); g0 += ZKM_MAX_SEG) {
         const size_t G = std::min<size_t>(ZKM_MAX_SEG, launched.size() - g0);
@@ -559,7 +660,8 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
     // | first findings].  Nothing between the first copy and the download waits for the device.
     zkm_scratch up(c, param_bytes + blob_words * 8), d_rows(c, row_words * 8), d_verdicts(c, nverdicts * 4), d_out(c, out_bytes);
     const zkm_verify_table* d_tabs = up.as<zkm_verify_table>();
-    const uint32_t* d_xs = (const uint32_t*)(up.as<char>() + tab_bytes);
+    const zkm_verify_chains* d_ents = (const zkm_verify_chains*)(up.as<char>() + tab_bytes);
+    const uint32_t* d_xs = (const uint32_t*)(up.as<char>() + tab_bytes + ent_bytes);
     gl_t* d_blobs = (gl_t*)(up.as<char>() + param_bytes);
     gl_t* d_acc = d_out.as<gl_t>();
     uint32_t* d_first = (uint32_t*)(d_acc + acc_words);
@@ -575,7 +677,7 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
     uint32_t most_cols = 0, most_chains = 0, most_q = 0;
     for (const zkm_verify_table& T : tabs) {
         most_cols = std::max(most_cols, (uint32_t)(T.d.W + T.d.A));
-        most_chains = std::max(most_chains, (uint32_t)(T.d.nq * (3 + T.d.L)));
+        most_chains = std::max(most_chains, (uint32_t)(T.d.nq * (3 + T.d.L)));   // (= nq * trees() of its entry)
         most_q = std::max(most_q, (uint32_t)T.d.nq);
     }
     {
@@ -588,29 +690,14 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
         zkm_verify_line_constraints(c, in[0].tables[ll.t].table_id, nch, ctl_dev_rebase(ll.ctl.d, up.as<char>()), ll.ctl.naux, ll.lookup_ch.data(),
                                     ll.alphas.data(), d_rows.as<gl_t>(), ll.rows_off.data(), d_acc, ll.acc_off.data(), T0.d.W, T0.d.A, ll.G);
     }
-    // the hash chains do not depend on each other or on the arithmetic; a call of few chains costs the longest chain's latency (the
-    // Keccak table's leaf: 304 permutations), so it takes the four-lane form of the permutation; one that fills the machine one lane
-    {
-        zkm_prof_scope ps(c, "verify/merkle_chains");
-        if (nchains <= c->quad_max_hashes)
-            hipLaunchKernelGGL(k_verify_chains_quad, dim3((most_chains + 63) / 64, (unsigned)nent), dim3(256), 0, c->stream, d_tabs, (const gl_t*)d_blobs, d_xs,
-                               d_verdicts.as<uint32_t>());
-        else
-            hipLaunchKernelGGL(k_verify_chains, dim3((most_chains + 255) / 256, (unsigned)nent), dim3(256), 0, c->stream, d_tabs, (const gl_t*)d_blobs, d_xs,
-                               d_verdicts.as<uint32_t>());
-        ZKM_HIP_CHECK(hipGetLastError());
-    }
+    launch_chains(c, d_ents, nent, most_chains, nchains, d_blobs, d_xs, d_verdicts.as<uint32_t>());
     {
         zkm_prof_scope ps(c, "verify/fri_queries");
         hipLaunchKernelGGL(k_verify_fri, dim3((most_q + 63) / 64, (unsigned)nent), dim3(64), 0, c->stream, d_tabs, (const gl_t*)d_blobs, d_xs,
                            d_verdicts.as<uint32_t>());
         ZKM_HIP_CHECK(hipGetLastError());
     }
-    {
-        zkm_prof_scope ps(c, "verify/reduce");
-        hipLaunchKernelGGL(k_verify_reduce, dim3((unsigned)nent), dim3(256), 0, c->stream, d_tabs, (const uint32_t*)d_verdicts.as<uint32_t>(), d_first);
-        ZKM_HIP_CHECK(hipGetLastError());
-    }
+    launch_reduce(c, d_ents, nent, d_verdicts.as<uint32_t>(), d_first);
     std::vector<uint64_t> out(out_bytes / 8);
     c->download(out.data(), d_out.p, out_bytes);   // the call's one host wait
     const uint32_t waits = (uint32_t)(c->host_waits - waits_before);   // (counted where the context waits: zkm_ctx::sync / wait_flag / ensure_down)
@@ -622,7 +709,6 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
         S.rep.host_waits = waits;
         for (size_t t = 0; t < ntables && S.rep.code == ZKM_VERIFY_OK; t++) {
             const table_state& ts = S.ts[t];
-            const zkm_verify_table& T = tabs[S.first_entry + t];
             const std::string who = table_label(in[s].tables, t) + ": ";
             if (!ts.state_ok) {
                 reject(S, ZKM_VERIFY_TRANSCRIPT_STATE, t, who + "the recorded challenger state is not the transcript's");
@@ -640,31 +726,23 @@ void verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const
             }
             const uint32_t f = first[S.first_entry + t];
             if (f == ~0u) continue;
-            const uint32_t q = f / T.slots, slot = f % T.slots;
-            S.rep.query = q;
-            const std::string at = who + "query " + std::to_string(q) + ": ";
-            if (slot < 3) {
-                reject(S, ZKM_VERIFY_INITIAL_MERKLE, t, at + "Invalid Merkle proof. (initial oracle " + std::to_string(slot) + ")");
-                S.rep.tree = slot;
-            } else if (slot == 3 + 2 * (uint32_t)T.d.L) {
-                reject(S, ZKM_VERIFY_FINAL_POLY, t, at + "Final polynomial evaluation is invalid.");
-            } else {
-                S.rep.layer = (slot - 3) / 2;
-                if ((slot - 3) % 2 == 0) reject(S, ZKM_VERIFY_FRI_EVAL, t, at + "FRI layer " + std::to_string(S.rep.layer) + ": the opened evaluation is not the folded one");
-                else reject(S, ZKM_VERIFY_FRI_MERKLE, t, at + "Invalid Merkle proof. (FRI layer " + std::to_string(S.rep.layer) + ")");
-            }
+            const query_finding found = decode_finding(f, ents[S.first_entry + t], who);
+            reject(S, found.code, t, found.text);
+            S.rep.query = found.query;
+            S.rep.tree = found.tree;
+            S.rep.layer = found.layer;
         }
         if (S.rep.code == ZKM_VERIFY_OK && !fixed) check_ctl_sums(cfg, in[s], ntables, ctls, sides, nctls, S);
     }
     if (fixed && segs[0].rep.code == ZKM_VERIFY_OK) *start = segs[0].ch;
 }
 
-int finish(const char* what, const std::vector<seg_state>& segs, zkm_verify_report* reports, char** err, bool name_segment) {
+int finish(const char* what, const std::vector<seg_state>& segs, zkm_verify_report* reports, char** err, const char* unit /* "segment", "proof" or null */) {
     if (reports)
         for (size_t s = 0; s < segs.size(); s++) reports[s] = segs[s].rep;
     for (size_t s = 0; s < segs.size(); s++)
         if (segs[s].rep.code != ZKM_VERIFY_OK) {
-            const std::string m = std::string(what) + ": " + (name_segment ? "segment " + std::to_string(s) + ": " : "") + segs[s].msg + " [" +
+            const std::string m = std::string(what) + ": " + (unit ? std::string(unit) + " " + std::to_string(s) + ": " : "") + segs[s].msg + " [" +
                                   CODE_NAMES[segs[s].rep.code] + "]";
             return zkm_fail(err, m.c_str());
         }
@@ -685,6 +763,187 @@ template <class F> int guarded(const char* what, zkm_ctx* c, zkm_verify_report* 
             reports[s].code = ZKM_VERIFY_FAILED;
         }
     return st ? st : 1;
+}
+
+// ------------------------------------------------------------------ zkm_fri_verify: verify_fri_proof for any instance
+struct fri_claim_in {
+    const uint64_t* proof;
+    size_t proof_words;
+    unsigned log_n;
+    const size_t* cols;
+    size_t noracles;
+    const uint64_t* const* caps;
+    const zkm_fri_batch* batches;
+    size_t nbatches;
+    const uint64_t* const* opened;
+    zkm_challenger* challenger;
+};
+// every SHAPE finding of one claim (include/zkm_hip.h), in the header's order; empty when the device may index the blob with y
+std::string fri_claim_shape(const zkm_stark_config* cfg, const fri_claim_in& in, const zkm_fri_part& y) {
+    if (in.proof_words < ZKM_FRI_BLOB_HEADER_WORDS) return "proof_words too short for the header";
+    if (in.proof[0] != ZKM_FRI_PROOF_MAGIC) return "no FRI proof header (magic)";
+    uint64_t want[ZKM_FRI_BLOB_HEADER_WORDS];
+    zkm_fri_blob_header_write(want, cfg, in.log_n, y);
+    for (int i = 1; i < ZKM_FRI_BLOB_HEADER_WORDS; i++)
+        if ((i <= 8 || i >= 16) && in.proof[i] != want[i]) return "header word " + std::to_string(i) + " does not match the configuration and the oracles";
+    const size_t total = y.total();
+    if (!y.round.fits() || y.round.L > ZKM_FRI_HEADER_LAYERS || y.round.lde_bits > 31 || total >= ((uint64_t)1 << 32)) return "unsupported FRI shape";
+    if (in.proof_words < total) return "proof_words too short";
+    for (size_t i = 1; i < total; i++)
+        if (in.proof[i] >= GL_P) return "word " + std::to_string(i) + " is not a canonical field element";
+    for (size_t k = 0; k < in.noracles; k++)
+        for (size_t i = 0; i < y.cap_words; i++)
+            if (in.caps[k][i] >= GL_P) return "word " + std::to_string(i) + " of the cap of oracle " + std::to_string(k) + " is not a canonical field element";
+    for (size_t b = 0; b < in.nbatches; b++) {
+        if (in.batches[b].point[0] >= GL_P || in.batches[b].point[1] >= GL_P) return "the point of batch " + std::to_string(b) + " is not a canonical field element";
+        for (size_t i = 0; i < 2 * in.batches[b].npolys; i++)
+            if (in.opened[b][i] >= GL_P) return "word " + std::to_string(i) + " of the opened values of batch " + std::to_string(b) + " is not a canonical field element";
+    }
+    return "";
+}
+
+void fri_verify_claims(zkm_ctx* c, const zkm_stark_config* cfg, size_t n, const fri_claim_in* in, std::vector<seg_state>& claims) {
+    if (!cfg) throw std::runtime_error("zkm_fri_verify: null configuration");
+    if (n == 0) throw std::runtime_error("zkm_fri_verify: nothing to verify");
+    if (n > 65535) throw std::runtime_error("zkm_fri_verify: at most 65535 proofs per call");
+    claims.assign(n, seg_state{});
+    std::vector<zkm_verify_chains> ents;
+    std::vector<fri_claim_dev> devs;
+    std::vector<uint32_t> polys, xs;
+    std::vector<size_t> launched;
+    std::vector<bool> pow_ok;
+    size_t words = 0, nverdicts = 0, nchains = 0;   // of the call's device block of field words: per launched claim its caps, then its blob
+    uint32_t most_chains = 0, most_q = 0;
+    for (size_t i = 0; i < n; i++) {
+        const fri_claim_in& a = in[i];
+        const std::string who = "zkm_fri_verify: proof " + std::to_string(i) + ": ";
+        // ---- what makes the call impossible (FAILED)
+        if (!a.proof || !a.cols || !a.caps || !a.batches || !a.opened || !a.challenger) throw std::runtime_error(who + "null argument");
+        if (a.noracles == 0 || a.noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error(who + "1..8 oracles");
+        if (a.nbatches == 0 || a.nbatches > FRI_CLAIM_BATCHES) throw std::runtime_error(who + "1..8 opening batches");
+        if (zkm_is_device_ptr(a.proof)) throw std::runtime_error(who + "the proof blob must be in host memory");
+        for (size_t k = 0; k < a.noracles; k++) {
+            if (!a.caps[k]) throw std::runtime_error(who + "null argument");
+            if (zkm_is_device_ptr(a.caps[k])) throw std::runtime_error(who + "the caps must be in host memory");
+        }
+        for (size_t b = 0; b < a.nbatches; b++) {
+            if (a.batches[b].npolys == 0 || !a.batches[b].polys) throw std::runtime_error(who + "empty batch");
+            if (!a.opened[b]) throw std::runtime_error(who + "null argument");
+            if (zkm_is_device_ptr(a.opened[b])) throw std::runtime_error(who + "the opened values must be in host memory");
+            for (size_t j = 0; j < a.batches[b].npolys; j++)
+                if (a.batches[b].polys[j].oracle >= a.noracles || a.batches[b].polys[j].poly >= a.cols[a.batches[b].polys[j].oracle])
+                    throw std::runtime_error(who + "polynomial index out of range");
+        }
+        const zkm_fri_part y = zkm_fri_blob_describe(cfg, a.log_n, a.cols, a.noracles);   // (throws on a configuration the library refuses)
+        // ---- what is wrong with the claim (SHAPE): it reaches no kernel
+        seg_state& S = claims[i];
+        const std::string shape = fri_claim_shape(cfg, a, y);
+        if (!shape.empty()) {
+            reject(S, ZKM_VERIFY_SHAPE, 0, "malformed proof: " + shape);
+            continue;
+        }
+        const zkm_query_round& R = y.round;
+        for (size_t b = 0; b < a.nbatches; b++) {   // plonky2 divides by x - point for every x of the coset g H
+            const gl_t z = a.batches[b].point[0];
+            if (a.batches[b].point[1] == 0 && gl_exp_pow2(gl_mul(z, gl_inv(GL_GENERATOR)), (unsigned)R.lde_bits) == 1)
+                throw std::runtime_error(who + "the point of batch " + std::to_string(b) + " lies on the LDE coset");
+        }
+        // ---- the transcript, from the blob alone: alpha; per layer the cap, then beta; the final polynomial; the witness; the indices
+        S.ch = *a.challenger;
+        zkm_verify_chains E{};
+        fri_claim_dev K{};
+        auto put = [](gl_t* dst, gl2_t v) { dst[0] = v.c0; dst[1] = v.c1; };
+        const gl2_t alpha = zkm_challenger_get_ext(&S.ch);
+        put(K.alpha, alpha);
+        for (unsigned l = 0; l < R.L; l++) put(K.betas[l], zkm_transcript_fri_beta(&S.ch, a.proof + y.o_cap(l), y.cap_words));
+        zkm_transcript_final_poly(&S.ch, a.proof + y.o_final(), y.F);
+        pow_ok.push_back(zkm_transcript_pow(&S.ch, a.proof[y.o_pow()], cfg->pow_bits));
+        E.xs = (uint32_t)xs.size();
+        zkm_transcript_query_indices(&S.ch, y.nq, (unsigned)R.lde_bits, std::back_inserter(xs));
+        // ---- the instance: reduced openings (PrecomputedReducedOpenings), alpha^npolys, the polynomials as offsets into a query round
+        K.nbatches = (uint32_t)a.nbatches;
+        for (size_t b = 0; b < a.nbatches; b++) {
+            const zkm_fri_batch& B = a.batches[b];
+            fri_claim_batch& o = K.b[b];
+            o.point[0] = B.point[0];
+            o.point[1] = B.point[1];
+            put(o.red_open, reduce_more(gl2_t{0, 0}, alpha, a.opened[b], B.npolys, 2));
+            put(o.shift, gl2_pow(alpha, B.npolys));
+            o.first = (uint32_t)polys.size();
+            o.npolys = (uint32_t)B.npolys;
+            for (size_t j = 0; j < B.npolys; j++) polys.push_back((uint32_t)(R.oracle_evals(B.polys[j].oracle) + B.polys[j].poly));
+        }
+        E.fri = y;
+        E.caps = words;
+        E.blob = words + a.noracles * y.cap_words;
+        E.verdicts = (uint32_t)nverdicts;
+        words = E.blob + y.total();
+        nverdicts += (size_t)y.nq * E.slots();
+        nchains += (size_t)y.nq * E.trees();
+        most_chains = std::max(most_chains, (uint32_t)(y.nq * E.trees()));
+        most_q = std::max(most_q, (uint32_t)y.nq);
+        S.launched = true;
+        S.first_entry = ents.size();
+        launched.push_back(i);
+        ents.push_back(E);
+        devs.push_back(K);
+    }
+    if (ents.empty()) return;   // (every claim was refused on the host: nothing is launched)
+    if (nverdicts >= ((uint64_t)1 << 32) || xs.size() >= ((uint64_t)1 << 32) || polys.size() >= ((uint64_t)1 << 32))
+        throw std::runtime_error("zkm_fri_verify: too many queries in one call");
+
+    const uint64_t waits_before = c->host_waits;
+    // ONE device block going up: [descriptions | claims | polynomial lists | query indices | per claim: caps, blob]; one word per claim
+    // coming down.  Nothing between the first copy and the download waits for the device.
+    const size_t nent = ents.size(), ent_bytes = nent * sizeof(zkm_verify_chains), dev_bytes = nent * sizeof(fri_claim_dev);
+    const size_t poly_bytes = (polys.size() * 4 + 15) & ~(size_t)15, xs_bytes = (xs.size() * 4 + 15) & ~(size_t)15;
+    const size_t param_bytes = (ent_bytes + dev_bytes + poly_bytes + xs_bytes + 15) & ~(size_t)15;
+    std::vector<char> params(param_bytes, 0);   // (alive until the download: the copy may read it after the call that queues it)
+    memcpy(params.data(), ents.data(), ent_bytes);
+    memcpy(params.data() + ent_bytes, devs.data(), dev_bytes);
+    memcpy(params.data() + ent_bytes + dev_bytes, polys.data(), polys.size() * 4);
+    memcpy(params.data() + ent_bytes + dev_bytes + poly_bytes, xs.data(), xs.size() * 4);
+    zkm_scratch up(c, param_bytes + words * 8), d_verdicts(c, nverdicts * 4), d_out(c, (nent * 4 + 15) & ~(size_t)15);
+    const zkm_verify_chains* d_ents = up.as<zkm_verify_chains>();
+    const fri_claim_dev* d_devs = (const fri_claim_dev*)(up.as<char>() + ent_bytes);
+    const uint32_t* d_polys = (const uint32_t*)(up.as<char>() + ent_bytes + dev_bytes);
+    const uint32_t* d_xs = (const uint32_t*)(up.as<char>() + ent_bytes + dev_bytes + poly_bytes);
+    gl_t* d_blobs = (gl_t*)(up.as<char>() + param_bytes);
+    ZKM_HIP_CHECK(hipMemcpyAsync(up.p, params.data(), params.size(), hipMemcpyHostToDevice, c->stream));
+    for (size_t k = 0; k < nent; k++) {
+        const fri_claim_in& a = in[launched[k]];
+        const zkm_verify_chains& E = ents[k];
+        for (size_t t = 0; t < a.noracles; t++)
+            ZKM_HIP_CHECK(hipMemcpyAsync(d_blobs + E.caps + t * E.fri.cap_words, a.caps[t], E.fri.cap_words * 8, hipMemcpyHostToDevice, c->stream));
+        ZKM_HIP_CHECK(hipMemcpyAsync(d_blobs + E.blob, a.proof, E.fri.total() * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    launch_chains(c, d_ents, nent, most_chains, nchains, d_blobs, d_xs, d_verdicts.as<uint32_t>());
+    {
+        zkm_prof_scope ps(c, "verify/fri_instance_queries");
+        hipLaunchKernelGGL(k_fri_verify_queries, dim3((most_q + 63) / 64, (unsigned)nent), dim3(64), 0, c->stream, d_ents, d_devs, d_polys, (const gl_t*)d_blobs,
+                           d_xs, d_verdicts.as<uint32_t>());
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+    launch_reduce(c, d_ents, nent, d_verdicts.as<uint32_t>(), d_out.as<uint32_t>());
+    std::vector<uint32_t> first(nent);
+    c->download(first.data(), d_out.p, nent * 4);   // the call's one host wait
+    const uint32_t waits = (uint32_t)(c->host_waits - waits_before);
+
+    for (size_t k = 0; k < nent; k++) {
+        seg_state& S = claims[launched[k]];
+        S.rep.host_waits = waits;
+        if (!pow_ok[k]) {
+            reject(S, ZKM_VERIFY_POW, 0, "Invalid proof of work witness.");
+        } else if (first[k] != ~0u) {
+            const query_finding found = decode_finding(first[k], ents[k], "");
+            reject(S, found.code, 0, found.text);
+            S.rep.query = found.query;
+            S.rep.tree = found.tree;
+            S.rep.layer = found.layer;
+        } else {
+            *in[launched[k]].challenger = S.ch;   // accepted: the state zkm_fri_prove leaves
+        }
+    }
 }
 
 }  // namespace
@@ -714,7 +973,7 @@ int zkm_verify_proofs(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_table_i
         const verify_input in{tables, pub, npub, proofs, proof_words, ctl_challenges};
         std::vector<seg_state> segs;
         verify_segments(c, cfg, 1, &in, ntables, ctls, sides, nctls, true, nullptr, nullptr, segs);
-        return finish("zkm_verify_proofs", segs, report, err, false);
+        return finish("zkm_verify_proofs", segs, report, err, nullptr);
     });
 }
 
@@ -736,7 +995,7 @@ int zkm_verify_segments(zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, co
         }
         std::vector<seg_state> segs;
         verify_segments(c, cfg, nseg, in.data(), ZKM_NUM_TABLES, ctls, sides, nctls, false, nullptr, nullptr, segs);
-        return finish("zkm_verify_segments", segs, reports, err, true);
+        return finish("zkm_verify_segments", segs, reports, err, "segment");
     });
 }
 
@@ -758,9 +1017,25 @@ int zkm_verify_single_table(zkm_ctx* c, int table_id, const zkm_stark_config* cf
         std::vector<seg_state> segs;
         zkm_challenger local = *challenger;
         verify_segments(c, cfg, 1, &in, 1, nullptr, nullptr, 0, false, &fixed, &local, segs);
-        const int rc = finish("zkm_verify_single_table", segs, report, err, false);
+        const int rc = finish("zkm_verify_single_table", segs, report, err, nullptr);
         if (!rc) *challenger = local;
         return rc;
+    });
+}
+
+int zkm_fri_verify(zkm_ctx* c, const zkm_stark_config* cfg, size_t nproofs, const uint64_t* const* proofs, const size_t* proof_words, const unsigned* log_n,
+                   const size_t* const* oracle_cols, const size_t* noracles, const uint64_t* const* const* oracle_caps, const zkm_fri_batch* const* batches,
+                   const size_t* nbatches, const uint64_t* const* const* opened, zkm_challenger* const* challengers, zkm_verify_report* reports, char** err) {
+    return guarded("zkm_fri_verify", c, reports, nproofs, err, [&] {
+        if (!cfg || !proofs || !proof_words || !log_n || !oracle_cols || !noracles || !oracle_caps || !batches || !nbatches || !opened || !challengers ||
+            nproofs == 0)
+            throw std::runtime_error("zkm_fri_verify: null argument");
+        std::vector<fri_claim_in> in(nproofs);
+        for (size_t i = 0; i < nproofs; i++)
+            in[i] = fri_claim_in{proofs[i], proof_words[i], log_n[i], oracle_cols[i], noracles[i], oracle_caps[i], batches[i], nbatches[i], opened[i], challengers[i]};
+        std::vector<seg_state> claims;
+        fri_verify_claims(c, cfg, nproofs, in.data(), claims);
+        return finish("zkm_fri_verify", claims, reports, err, "proof");
     });
 }
 

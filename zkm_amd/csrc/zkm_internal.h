@@ -700,6 +700,21 @@ void zkm_all_stark_table_inputs(zkm_table_input out[ZKM_NUM_TABLES]);   // ctl.h
 // description (proof_blob.h: every offset follows from it), and what the transcript replay gave.
 #define ZKM_VERIFY_LINE_POINTS 5      // constraints are evaluated on the rows v0 + t v1, t = 0 .. 4 (degree <= 3, one point to spare)
 #define ZKM_VERIFY_LINE_THREADS (4 * ZKM_VERIFY_LINE_POINTS)
+// What the Merkle chains and the reduction know of one entry of a verify call, a (segment, table) of zkm_verify_* or a claim of
+// zkm_fri_verify alike: where the blob and the caps of its initial trees lie in the call's device block, the blob's FRI part
+// (proof_blob.h: noracles initial trees and L layer trees, every offset follows from it) and the entry's query indices and verdicts.
+// A query has noracles + 2 L + 1 verdict words, in the order of the findings: the initial trees' Merkle paths, per layer the evaluation
+// check then the Merkle path, the final polynomial.  The STARK blob is the case of three initial trees whose caps lie in the blob.
+struct zkm_verify_chains {
+    uint64_t blob;                    // word offset of the blob
+    uint64_t caps;                    // word offset of initial tree 0's cap; tree k's lies k * fri.cap_words further
+    zkm_fri_part fri;
+    uint32_t xs, verdicts;            // first of its fri.nq query indices / of its fri.nq * slots() verdict words
+    GL_HD uint32_t trees() const { return (uint32_t)(fri.round.noracles + fri.round.L); }
+    GL_HD uint32_t slots() const { return (uint32_t)(fri.round.noracles + 2 * fri.round.L + 1); }
+    GL_HD uint32_t slot_layer_eval(uint32_t l) const { return (uint32_t)fri.round.noracles + 2 * l; }
+    GL_HD uint32_t slot_final() const { return slot_layer_eval((uint32_t)fri.round.L); }
+};
 struct zkm_verify_table {
     uint64_t blob;                    // word offset of the blob
     uint64_t rows;                    // word offset of its line rows: [t][column][local, next], trace columns then auxiliary columns
