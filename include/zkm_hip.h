@@ -225,6 +225,10 @@ int zkm_keccakf_batch(zkm_ctx* ctx, uint64_t* states, size_t k, char** err);
  *   FOLD                                   0                     n pairs (al, ah), both < 2^59 -> n words al + 2^32 ah
  *   FOLD_TY                                0                     n pairs (T, Y), T < 2^57, Y < 2^27 in the low half of its word -> n words T + 2^48 Y
  *   SBOX7, SBOX_DELTA, ADD_RC0             0                     n states -> n states, word by word: x^7;  x^7 - x;  x + constant of round 0
+ *   GROUP4                                 g = 0..4              n states -> n states: four-round group g of the one-lane permutation -- the linear layers
+ *                                                                of rounds 4g+3 .. 4g+6 with their constants and the word-0 s-boxes of rounds 4g+4 .. 4g+6
+ *   FOLD_WIDE                              0                     n triples (al, ah, carries), al and ah ANY uint64, carries = cl + 2 ch with cl, ch in {0, 1}
+ *                                                                -> n words (al + 2^64 cl) + 2^32 (ah + 2^64 ch): the fold of an M^4 row
  * (all mod p).  An unknown probe, an arg outside its column, n = 0 or n > 2^20 is an error: nothing is launched. */
 #define ZKM_POSEIDON_OUT_ALL 0
 #define ZKM_POSEIDON_OUT_CAPACITY 1
@@ -245,6 +249,8 @@ int zkm_keccakf_batch(zkm_ctx* ctx, uint64_t* states, size_t k, char** err);
 #define ZKM_POSEIDON_PROBE_SBOX7 13
 #define ZKM_POSEIDON_PROBE_SBOX_DELTA 14
 #define ZKM_POSEIDON_PROBE_ADD_RC0 15
+#define ZKM_POSEIDON_PROBE_GROUP4 17      /* (16 is not a probe) */
+#define ZKM_POSEIDON_PROBE_FOLD_WIDE 18
 int zkm_poseidon_selftest(zkm_ctx* ctx, uint32_t probe, uint32_t arg, const uint64_t* in, size_t n, uint64_t* out, char** err);
 
 /* Parity / debug: the constraint consumer of the quotient kernels (the alpha-accumulation of vanishing_poly.rs:30-45,

@@ -184,7 +184,7 @@ pub const ZKM_POSEIDON_PROBE_PERMUTE_WIDE: u32 = 3; pub const ZKM_POSEIDON_PROBE
 pub const ZKM_POSEIDON_PROBE_MDS_QUAD: u32 = 6; pub const ZKM_POSEIDON_PROBE_MDS_ROWS: u32 = 7; pub const ZKM_POSEIDON_PROBE_GROUP3: u32 = 8;
 pub const ZKM_POSEIDON_PROBE_GROUP3_QUAD: u32 = 9; pub const ZKM_POSEIDON_PROBE_GROUP2: u32 = 10; pub const ZKM_POSEIDON_PROBE_FOLD: u32 = 11;
 pub const ZKM_POSEIDON_PROBE_FOLD_TY: u32 = 12; pub const ZKM_POSEIDON_PROBE_SBOX7: u32 = 13; pub const ZKM_POSEIDON_PROBE_SBOX_DELTA: u32 = 14;
-pub const ZKM_POSEIDON_PROBE_ADD_RC0: u32 = 15;
+pub const ZKM_POSEIDON_PROBE_ADD_RC0: u32 = 15; pub const ZKM_POSEIDON_PROBE_GROUP4: u32 = 17; pub const ZKM_POSEIDON_PROBE_FOLD_WIDE: u32 = 18;
 pub const ZKM_TABLE_POSEIDON: c_int = 0; pub const ZKM_TABLE_LOGIC: c_int = 1; pub const ZKM_TABLE_KECCAK_SPONGE: c_int = 2;
 pub const ZKM_TABLE_KECCAK: c_int = 3; pub const ZKM_TABLE_MEMORY: c_int = 4; pub const ZKM_TABLE_POSEIDON_SPONGE: c_int = 5;
 pub const ZKM_TABLE_SHA_EXTEND: c_int = 6; pub const ZKM_TABLE_SHA_EXTEND_SPONGE: c_int = 7; pub const ZKM_TABLE_SHA_COMPRESS: c_int = 8;

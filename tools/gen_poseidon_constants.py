@@ -30,6 +30,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(os.environ.get("ZKM_REFERENCE_ROOT", "reference"), "prover/src/poseidon/constants.rs")   # ZKM_REFERENCE_ROOT: a checkout of the reference
 OUTS = [os.path.join(ROOT, "zkm_amd", "csrc", "poseidon_constants.inc"),
         os.path.join(ROOT, "oracle", "poseidon_constants.inc")]
+OUT_GROUP4 = os.path.join(ROOT, "zkm_amd", "csrc", "poseidon_group4.inc")   # the four-round groups' tables (product only)
 
 
 def parse_rust_arrays(text):
@@ -149,6 +150,53 @@ def derive_fused(rc, circ, diag):
     return M2, M3, c1, c2, c3
 
 
+GROUP4_SPLIT = [4, 4, 4, 4, 4, 3]   # the 23 linear layers (rounds 3 .. 25) as five groups of four and one of three
+GROUP4_LAST = WIDTH - 1             # the column of M^4 whose term closes a row's chain of multiply-adds
+
+
+def group4_bounds(M, M2, M3, M4):
+    """The three bounds poseidon_partial_group_t<4> relies on, per row, in exact integers: (a) the largest entry of M^4, (b) the
+    largest value a half-sum reaches BEFORE its last multiply-add, (c) the largest complete half-sum.  A half-sum is
+    c + d3 M[i][0] + d2 M^2[i][0] + d1 M^3[i][0] + sum_j x_j M^4[i][j] with c and every d, x a 32-bit half (<= 2^32 - 1)."""
+    top = (1 << 32) - 1
+    a = max(max(r) for r in M4)
+    weight = [sum(M4[i]) + M[i][0] + M2[i][0] + M3[i][0] for i in range(WIDTH)]
+    b = max(top * (weight[i] - M4[i][GROUP4_LAST]) + top for i in range(WIDTH))
+    c = max(top * weight[i] + top for i in range(WIDTH))
+    return a, b, c
+
+
+def derive_group4(rc, circ, diag):
+    """Tables of the four-round groups (poseidon_dev.h poseidon_partial_group_t<4>): M^4 in exact integers, the first columns of
+    M, M^2, M^3 (the coefficients of delta3, delta2, delta1 in the last layer), and per group the constants c1, c2, c3 added to word 0
+    after the first three layers and the vector c4 after the fourth -- for the split 4+4+4+4+4+3, whose last group is a three-round
+    group with constants of its own (tail: c1, c2, vector c3).  Everything is computed in exact integers from the round constants and
+    M and reduced mod p once, at the end."""
+    M = [[circ[(c - r) % WIDTH] + (diag[r] if r == c else 0) for c in range(WIDTH)] for r in range(WIDTH)]
+    imul = lambda a, b: [[sum(a[i][t] * b[t][j] for t in range(WIDTH)) for j in range(WIDTH)] for i in range(WIDTH)]
+    ivec = lambda a, v: [sum(a[i][j] * v[j] for j in range(WIDTH)) for i in range(WIDTH)]
+    powers = [None, M, imul(M, M)]
+    powers.append(imul(powers[2], M))
+    powers.append(imul(powers[3], M))
+    M2, M3, M4 = powers[2], powers[3], powers[4]
+    a, b, c = group4_bounds(M, M2, M3, M4)
+    assert a < 1 << 32, "(a) an entry of M^4 does not fit a 32-bit multiplier"
+    assert b < 1 << 64, "(b) a half-sum can wrap before its last multiply-add"
+    assert c < 1 << 65, "(c) a half-sum can carry more than once"
+    K = lambda r: rc[r * WIDTH:(r + 1) * WIDTH]
+    groups, rho = [], HALF_FULL - 1
+    for t in GROUP4_SPLIT:   # layers of rounds rho .. rho + t - 1; constants of rounds rho + 1 .. rho + t
+        acc, heads = [0] * WIDTH, []
+        for k in range(1, t + 1):
+            acc = [x + y for x, y in zip(ivec(M, acc), K(rho + k))]   # = sum_{m <= k} M^(k-m) K(rho + m), exact
+            heads.append(acc[0] % P)
+        groups.append((heads[:-1], [x % P for x in acc]))
+        rho += t
+    assert rho == HALF_FULL + N_PARTIAL
+    dcol = [[powers[e][i][0] for i in range(WIDTH)] for e in (1, 2, 3)]
+    return M4, dcol, groups
+
+
 def fmt32(name, rows):
     lines = ["ZKM_CONSTEXPR uint32_t %s[%d][%d] = {" % (name, len(rows), len(rows[0]))]
     for r in rows:
@@ -233,7 +281,50 @@ def main():
         os.makedirs(os.path.dirname(path), exist_ok=True)
         with open(path, "w") as f:
             f.write(text)
-    print("wrote", ", ".join(OUTS), "(cross-checked against reference)" if checked else "(reference absent: derivation not cross-checked)")
+    write_group4(rc, circ, diag)
+    print("wrote", ", ".join(OUTS + [OUT_GROUP4]), "(cross-checked against reference)" if checked else "(reference absent: derivation not cross-checked)")
+
+
+def write_group4(rc, circ, diag):
+    M4, dcol, groups = derive_group4(rc, circ, diag)
+    quads, tail = groups[:-1], groups[-1]
+    assert all(len(h) == 3 for h, _ in quads) and len(tail[0]) == 2
+    body = [
+        "/* Goldilocks Poseidon: tables of the four-round partial groups (poseidon_dev.h poseidon_partial_group_t<4>).",
+        " * GENERATED by tools/gen_poseidon_constants.py (derive_group4) -- do not edit.",
+        " * The 23 linear layers of rounds 3 .. 25 as 4+4+4+4+4+3: M^4 in exact integers (not reduced mod p), the first columns of M, M^2,",
+        " * M^3 (the coefficients of delta3, delta2, delta1 in a group's last layer), the constants c1, c2, c3 of word 0 and the vector c4 of",
+        " * each four-round group, and c1, c2 and the vector c3 of the three-round group that closes the section.  Included after",
+        " * poseidon_constants.inc, with the same ZKM_CONST / ZKM_CONSTEXPR storage qualifiers. */",
+        fmt32("ZKM_POSEIDON_M4", M4),
+        fmt32("ZKM_POSEIDON_G4_DCOL", dcol),
+        fmt("ZKM_POSEIDON_G4_C1", [len(quads)], [h[0] for h, _ in quads]),
+        fmt("ZKM_POSEIDON_G4_C2", [len(quads)], [h[1] for h, _ in quads]),
+        fmt("ZKM_POSEIDON_G4_C3", [len(quads)], [h[2] for h, _ in quads]),
+        fmt("ZKM_POSEIDON_G4_C4", [len(quads), WIDTH], [x for _, v in quads for x in v], 4),
+        fmt("ZKM_POSEIDON_G4_TAIL_C12", [2], tail[0]),
+        fmt("ZKM_POSEIDON_G4_TAIL_C3", [WIDTH], tail[1]),
+        "#ifdef __cplusplus",
+        "/* the bounds the device code relies on (the generator asserts the same in exact integers): with every input half, delta half and",
+        " * constant half <= 2^32 - 1, a half-sum of row i is at most (2^32 - 1) (w_i + 1), w_i = rowsum(M^4)_i + M[i][0] + M^2[i][0] + M^3[i][0] */",
+        "constexpr bool zkm_poseidon_group4_bounds() {",
+        "    for (int i = 0; i < %d; i++) {" % WIDTH,
+        "        uint64_t w = (uint64_t)ZKM_POSEIDON_G4_DCOL[0][i] + ZKM_POSEIDON_G4_DCOL[1][i] + ZKM_POSEIDON_G4_DCOL[2][i];",
+        "        for (int j = 0; j < %d; j++) w += ZKM_POSEIDON_M4[i][j];   /* (a) the table's type: every entry < 2^32 */" % WIDTH,
+        "        /* (b) before the last multiply-add (column %d): (2^32 - 1) (w - m_last + 1) < 2^64  <=  w - m_last + 1 <= 2^32 */" % GROUP4_LAST,
+        "        if (w - ZKM_POSEIDON_M4[i][%d] + 1 > (1ULL << 32)) return false;" % GROUP4_LAST,
+        "        /* (c) the complete sum: (2^32 - 1) (w + 1) < 2^65  <=  w + 1 <= 2^33 */",
+        "        if (w + 1 > (1ULL << 33)) return false;",
+        "    }",
+        "    return true;",
+        "}",
+        "static_assert(sizeof(ZKM_POSEIDON_M4[0][0]) == 4, \"(a) an entry of M^4 fits a 32-bit multiplier\");",
+        "static_assert(zkm_poseidon_group4_bounds(), \"(b), (c): a half-sum of an M^4 row is exact before its last multiply-add and carries at most once\");",
+        "#endif",
+        "",
+    ]
+    with open(OUT_GROUP4, "w") as f:
+        f.write("\n".join(body))
 
 
 if __name__ == "__main__":

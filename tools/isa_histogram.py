@@ -13,8 +13,10 @@ the 3 / 7 / 3 round loops of poseidon_permute and the 33 absorb steps of a 262-c
 The weighted VALU total is cross-checked by bench.py against rocprofv3's SQ_INSTS_VALU / SQ_WAVES of the same kernel.
 
 Usage:
-  python tools/isa_histogram.py zkm_amd/csrc/hash.hip k_merkle_leaves --trips 33,3,7,3,3,7,3,1 --only-loop 0 \
-      --out profiles/r02_isa_merkle_leaves.json
+  python tools/isa_histogram.py zkm_amd/csrc/hash.hip k_merkle_leaves_mfma --only-loop 0 --poseidon-regions \
+      --out profiles/r06_isa_merkle_leaves_mfma.json
+`--poseidon-regions` weighs the code behind the `; ZKM_REGION name` markers of poseidon_dev.h by how often one permutation runs it
+(POSEIDON_REGION_EXEC below; the same as spelling the counts out with --region-exec);
 `--trips` lists one trip count per loop in order of first appearance (run without it to see the loops);
 `--only-loop K` restricts the histogram to ONE iteration of the K-th loop (the steady state of the kernel).
 """
@@ -27,6 +29,12 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# Executions per permutation of the regions poseidon_permute_out_t marks (poseidon_dev.h): eight s-box layers; the partial-round section
+# hangs off round 3 as five four-round groups and one three-round group; six full-round linear layers, the seventh is the caller's rows.
+POSEIDON_REGION_EXEC = {"entry": 1, "full_sbox": 8, "partial_head": 1, "partial_group4": 5, "partial_tail": 1, "last_mds_rows": 1, "full_mds": 6,
+                        "exit": 1}
 
 
 def compile_asm(src, arch="gfx950"):
@@ -63,6 +71,7 @@ def parse(lines):
     out-of-line blocks), and parent[header] = enclosing loop's header or None."""
     blocks, parent = [], {}
     cur = {"label": None, "ops": [], "loop": None, "name": None}
+    in_cold = False   # from a ZKM_COLD marker to the s_branch that returns to the hot path: the blocks an inner branch splits the cold code into
 
     def annotate(block, note, own_label):
         m = re.search(r"in Loop: Header=(BB\w+)", note)
@@ -84,7 +93,7 @@ def parse(lines):
             while k < len(lines) and lines[k].lstrip().startswith(";") and not re.match(r"^\s*;\s*%bb\.\d+:", lines[k]):
                 note += lines[k]
                 k += 1
-            cur = {"label": lab.group(1) if lab else None, "ops": [], "loop": None,
+            cur = {"label": lab.group(1) if lab else None, "ops": [], "loop": None, "cold": in_cold,
                    "name": lab.group(1) if lab else re.search(r"%bb\.\d+", l).group(0)}
             annotate(cur, note, cur["label"])
             continue
@@ -96,7 +105,7 @@ def parse(lines):
                 cur = {"label": None, "ops": [], "loop": cur["loop"], "name": cur.get("name"), "cold": cur.get("cold", False)}
             cur["region"] = mreg.group(1)
         if "ZKM_COLD" in l:
-            cur["cold"] = True   # source-level marker (gl_dev.h): a block behind a never-taken branch
+            cur["cold"] = in_cold = True   # source-level marker (gl_dev.h): a block behind a never-taken branch
         if not s or s.startswith("."):
             continue
         op = s.split()[0]
@@ -104,7 +113,8 @@ def parse(lines):
         if op.startswith("s_cbranch") or op == "s_branch":
             blocks.append(cur)
             # a fall-through block without its own annotation stays in the loop of the block it follows
-            cur = {"label": None, "ops": [], "loop": cur["loop"], "name": cur.get("name")}
+            in_cold = in_cold and op != "s_branch"
+            cur = {"label": None, "ops": [], "loop": cur["loop"], "name": cur.get("name"), "cold": in_cold}
     if cur["ops"] or cur["label"]:
         blocks.append(cur)
     return blocks, parent
@@ -146,6 +156,7 @@ def main():
                     "per iteration of the --only-loop loop, for code under a condition the trip counts cannot express")
     ap.add_argument("--region-exec", default="", help="REGION=count,...: executions per iteration of the --only-loop loop of the code that "
                     "follows a `; ZKM_REGION name` marker (source-level markers, e.g. poseidon_dev.h) up to the next marker, in layout order")
+    ap.add_argument("--poseidon-regions", action="store_true", help="--region-exec with the counts of one Poseidon permutation (POSEIDON_REGION_EXEC)")
     ap.add_argument("--cost", default=os.path.join(ROOT, "profiles", "r02_ubench_issue_cost.json"))
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -179,7 +190,8 @@ def main():
     for i, b in enumerate(blocks):   # cold blocks, and the fall-through pieces a branch splits them into, do not execute
         if b.get("cold"):
             weight[i] = 0
-    rexec = dict((kv.split("=")[0], float(kv.split("=")[1])) for kv in args.region_exec.split(",") if kv)
+    rexec = dict(POSEIDON_REGION_EXEC) if args.poseidon_regions else {}
+    rexec.update((kv.split("=")[0], float(kv.split("=")[1])) for kv in args.region_exec.split(",") if kv)
     region = None
     for i, b in enumerate(blocks):
         region = b.get("region", region)

@@ -1112,14 +1112,15 @@ class Context:
 
     def poseidon_selftest(self, probe, arg, words):
         """One piece of the device's Poseidon permutation on chosen words (zkm_poseidon_selftest; probe: POSEIDON_PROBE[name] or its number).
-        `words`: n states of 12 words -- n pairs for FOLD / FOLD_TY -- of any uint64.  Returns the raw words the device produced:
-        an (n, 12) array, or n words for the folds."""
+        `words`: n states of 12 words -- n pairs for FOLD / FOLD_TY, n triples (al, ah, cl + 2 ch) for FOLD_WIDE -- of any uint64.  Returns
+        the raw words the device produced: an (n, 12) array, or n words for the folds."""
         probe = POSEIDON_PROBE[probe] if isinstance(probe, str) else int(probe)
         words = np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
-        pairs = probe in (POSEIDON_PROBE["FOLD"], POSEIDON_PROBE["FOLD_TY"])
-        per = 2 if pairs else 12
+        triples = probe == POSEIDON_PROBE["FOLD_WIDE"]
+        pairs = triples or probe in (POSEIDON_PROBE["FOLD"], POSEIDON_PROBE["FOLD_TY"])
+        per = 3 if triples else 2 if pairs else 12
         if words.size % per:
-            raise ValueError("poseidon_selftest: %d words are not a whole number of %s" % (words.size, "pairs" if pairs else "states"))
+            raise ValueError("poseidon_selftest: %d words are not a whole number of %s" % (words.size, "triples" if triples else "pairs" if pairs else "states"))
         n = words.size // per
         out = np.zeros(n if pairs else 12 * n, dtype=np.uint64)
         err = C.c_char_p()

@@ -305,8 +305,11 @@ __device__ __forceinline__ void merkle_leaves_body(Src src, size_t n, gl_t* __re
 }
 
 #define ZKM_LEAF_MFMA_ATTR __attribute__((amdgpu_waves_per_eu(ZKM_LEAF_MFMA_WAVES, ZKM_LEAF_MFMA_WAVES)))
+// The vector-ALU one-lane kernels: five waves per SIMD (<= 96 registers) for the leaves, six (<= 80) for the tree levels.  Without the
+// bound the register allocator, once a kernel does not fit 80, lets it grow past 96 (four waves).
+#define ZKM_LANE_WAVES_ATTR(n) __attribute__((amdgpu_waves_per_eu(n, n)))
 
-__global__ __launch_bounds__(256) void k_merkle_leaves(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride,
+__global__ __launch_bounds__(256) ZKM_LANE_WAVES_ATTR(5) void k_merkle_leaves(const gl_t* __restrict__ lde, size_t nrows, size_t ncols, size_t col_stride,
                                                        gl_t* __restrict__ digests, size_t lde_seg, size_t dig_seg) {
     merkle_leaves_body<sponge_lane_valu>(leaf_cols{lde, ncols, col_stride, lde_seg}, nrows, digests, dig_seg);
 }
@@ -336,7 +339,7 @@ __global__ __launch_bounds__(256) ZKM_LEAF_MFMA_ATTR void k_merkle_leaves_chunk_
     merkle_leaves_body<sponge_lane_mfma, leaf_cols, true>(leaf_cols{lde, nc, col_stride, 0}, nrows, digests, 0, state, first, last);
 }
 
-__global__ __launch_bounds__(256) void k_merkle_leaves_ext(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1,
+__global__ __launch_bounds__(256) ZKM_LANE_WAVES_ATTR(5) void k_merkle_leaves_ext(const gl_t* __restrict__ c0, const gl_t* __restrict__ c1,
                                                            size_t nleaves, unsigned arity, gl_t* __restrict__ digests, size_t val_seg, size_t dig_seg) {
     merkle_leaves_body<sponge_lane_valu>(leaf_f2{c0, c1, arity, val_seg}, nleaves, digests, dig_seg);
 }
@@ -427,7 +430,7 @@ struct merkle_fused_args {
     size_t dig_seg;         // blockIdx.z-th tree: every pointer + blockIdx.z * dig_seg
 };
 
-__global__ __launch_bounds__(256) void k_merkle_fused(merkle_fused_args p) {
+__global__ __launch_bounds__(256) ZKM_LANE_WAVES_ATTR(6) void k_merkle_fused(merkle_fused_args p) {
     __shared__ uint64_t sh[2][4][256];                    // [buffer][word][node]: parents of the level just made, word-major
     const unsigned tid = threadIdx.x;
     uint64_t s[12];
@@ -780,7 +783,8 @@ enum {
     PROBE_MDS_VALU = ZKM_POSEIDON_PROBE_MDS_VALU, PROBE_MDS_MFMA = ZKM_POSEIDON_PROBE_MDS_MFMA, PROBE_MDS_QUAD = ZKM_POSEIDON_PROBE_MDS_QUAD,
     PROBE_MDS_ROWS = ZKM_POSEIDON_PROBE_MDS_ROWS, PROBE_GROUP3 = ZKM_POSEIDON_PROBE_GROUP3, PROBE_GROUP3_QUAD = ZKM_POSEIDON_PROBE_GROUP3_QUAD,
     PROBE_GROUP2 = ZKM_POSEIDON_PROBE_GROUP2, PROBE_FOLD = ZKM_POSEIDON_PROBE_FOLD, PROBE_FOLD_TY = ZKM_POSEIDON_PROBE_FOLD_TY,
-    PROBE_SBOX7 = ZKM_POSEIDON_PROBE_SBOX7, PROBE_SBOX_DELTA = ZKM_POSEIDON_PROBE_SBOX_DELTA, PROBE_ADD_RC0 = ZKM_POSEIDON_PROBE_ADD_RC0
+    PROBE_SBOX7 = ZKM_POSEIDON_PROBE_SBOX7, PROBE_SBOX_DELTA = ZKM_POSEIDON_PROBE_SBOX_DELTA, PROBE_ADD_RC0 = ZKM_POSEIDON_PROBE_ADD_RC0,
+    PROBE_GROUP4 = ZKM_POSEIDON_PROBE_GROUP4, PROBE_FOLD_WIDE = ZKM_POSEIDON_PROBE_FOLD_WIDE
 };
 static_assert(POSEIDON_OUT_ALL == ZKM_POSEIDON_OUT_ALL && POSEIDON_OUT_CAPACITY == ZKM_POSEIDON_OUT_CAPACITY && POSEIDON_OUT_DIGEST == ZKM_POSEIDON_OUT_DIGEST,
               "include/zkm_hip.h names the output modes of poseidon_dev.h");
@@ -802,6 +806,8 @@ __device__ __forceinline__ void poseidon_probe_lane_body(const uint64_t* __restr
         else poseidon_mds_add<false, 8, 12>(s, nullptr);
     } else if constexpr (PROBE == PROBE_GROUP3) {
         poseidon_partial_group<3>(s, PC::ZKM_POSEIDON_FUSED_C1[arg], PC::ZKM_POSEIDON_FUSED_C2[arg], PC::ZKM_POSEIDON_FUSED_C3[arg]);
+    } else if constexpr (PROBE == PROBE_GROUP4) {
+        poseidon_partial_group4(s, PC::ZKM_POSEIDON_G4_C1[arg], PC::ZKM_POSEIDON_G4_C2[arg], &PC::ZKM_POSEIDON_G4_C3[arg], PC::ZKM_POSEIDON_G4_C4[arg]);
     } else {
         static_assert(PROBE == PROBE_GROUP2, "not a one-lane probe");
         poseidon_partial_group<2>(s, PC::ZKM_POSEIDON_FUSED_C1[7], 0, PC::ZKM_POSEIDON_FUSED_C3[7]);
@@ -852,13 +858,22 @@ __global__ __launch_bounds__(256) void k_poseidon_probe_wide(const uint64_t* __r
     if (f.live && f.idx < 12) out[item * 12 + f.idx] = s[0];
 }
 
-// word-wise probes: n pairs -> n words (the folds), n states -> n states (s-box, s-box delta, the first constant add)
+// word-wise probes: n pairs -> n words (the folds; the wide fold: n triples), n states -> n states (s-box, s-box delta, the first constant add)
 template <int PROBE>
 __global__ __launch_bounds__(256) void k_poseidon_probe_words(const uint64_t* __restrict__ in, size_t n, uint64_t* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     if constexpr (PROBE == PROBE_FOLD) {
         out[i] = poseidon_fold(in[2 * i], in[2 * i + 1]);
+    } else if constexpr (PROBE == PROBE_FOLD_WIDE) {
+        // the carries reach the fold the way a row's last multiply-adds deliver them: as the wave's lane masks
+        const uint64_t carries = in[3 * i + 2];
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint64_t cl = __ballot((int)(carries & 1)), ch = __ballot((int)((carries >> 1) & 1));
+#else
+        const uint64_t cl = carries & 1, ch = (carries >> 1) & 1;
+#endif
+        out[i] = poseidon_fold_wide(in[3 * i], in[3 * i + 1], cl, ch);
     } else if constexpr (PROBE == PROBE_FOLD_TY) {
 #if defined(__HIP_DEVICE_COMPILE__)      // (the matrix-core layer's fold has no host form)
         out[i] = poseidon_fold_ty(in[2 * i], (uint32_t)in[2 * i + 1]);
@@ -893,14 +908,15 @@ extern "C" int zkm_poseidon_selftest(zkm_ctx* c, uint32_t probe, uint32_t arg, c
             case PROBE_GROUP3: kernel = k_poseidon_probe_lane<PROBE_GROUP3>; arg_ok = arg < 7; break;
             case PROBE_GROUP3_QUAD: kernel = k_poseidon_probe_quad<PROBE_GROUP3_QUAD>; arg_ok = arg < 7; lanes = 4; break;
             case PROBE_GROUP2: kernel = k_poseidon_probe_lane<PROBE_GROUP2>; break;
-            case PROBE_FOLD: case PROBE_FOLD_TY: case PROBE_SBOX7: case PROBE_SBOX_DELTA: case PROBE_ADD_RC0: break;
+            case PROBE_GROUP4: kernel = k_poseidon_probe_lane<PROBE_GROUP4>; arg_ok = arg < 5; break;
+            case PROBE_FOLD_WIDE: case PROBE_FOLD: case PROBE_FOLD_TY: case PROBE_SBOX7: case PROBE_SBOX_DELTA: case PROBE_ADD_RC0: break;
             default: throw std::runtime_error("zkm_poseidon_selftest: unknown probe");
         }
         if (!arg_ok) throw std::runtime_error("zkm_poseidon_selftest: bad arg for this probe");
         if (!in || !out) throw std::runtime_error("zkm_poseidon_selftest: null argument");
         if (n == 0 || n > ((size_t)1 << 20)) throw std::runtime_error("zkm_poseidon_selftest: n must be 1 .. 2^20");
-        const bool pairs = probe == PROBE_FOLD || probe == PROBE_FOLD_TY;
-        const size_t in_words = pairs ? 2 * n : 12 * n, out_words = pairs ? n : 12 * n;
+        const bool pairs = probe == PROBE_FOLD || probe == PROBE_FOLD_TY, triples = probe == PROBE_FOLD_WIDE;
+        const size_t in_words = triples ? 3 * n : pairs ? 2 * n : 12 * n, out_words = pairs || triples ? n : 12 * n;
         zkm_scratch din(c, in_words * 8), dout(c, out_words * 8);
         ZKM_HIP_CHECK(hipMemcpyAsync(din.p, in, in_words * 8, hipMemcpyHostToDevice, c->stream));
         // (rows / words a probe leaves unspecified read as zero, not as what the block held before)
@@ -911,6 +927,7 @@ extern "C" int zkm_poseidon_selftest(zkm_ctx* c, uint32_t probe, uint32_t arg, c
         } else {
             void (*words)(const uint64_t*, size_t, uint64_t*) =
                 probe == PROBE_FOLD ? k_poseidon_probe_words<PROBE_FOLD> : probe == PROBE_FOLD_TY ? k_poseidon_probe_words<PROBE_FOLD_TY> :
+                probe == PROBE_FOLD_WIDE ? k_poseidon_probe_words<PROBE_FOLD_WIDE> :
                 probe == PROBE_SBOX7 ? k_poseidon_probe_words<PROBE_SBOX7> : probe == PROBE_SBOX_DELTA ? k_poseidon_probe_words<PROBE_SBOX_DELTA> :
                                                                                                         k_poseidon_probe_words<PROBE_ADD_RC0>;
             hipLaunchKernelGGL(words, grid, block, 0, c->stream, din.as<uint64_t>(), n, dout.as<uint64_t>());

@@ -15,16 +15,25 @@
 // folded into the MDS accumulators before the single reduction.  Algebraically identical, so outputs are
 // bit-exact (pinned by the plonky2 test vectors and by naive == fast in the oracle).
 //
-// Partial rounds, fused three at a time.  Between two lane-0 s-boxes the state only goes through linear maps, and the
-// integer powers of the MDS matrix stay small: the entries of M^3 are < 2^21 and its row sums < 2^25, so a row of M^3
-// applied to 32-bit halves still fits the same pair of 64-bit accumulators (24 multiply-adds) as a row of M.  With
+// Partial rounds, fused.  Between two lane-0 s-boxes the state only goes through linear maps, and the integer powers of
+// the MDS matrix stay small: the entries of M^3 are < 2^21 and its row sums < 2^25, so a row of M^3 applied to 32-bit
+// halves still fits the same pair of 64-bit accumulators (24 multiply-adds) as a row of M.  With
 // delta_k = sbox(a_k[0]) - a_k[0] the three rounds
 //     a1 = M x + K1,   a2 = M (a1 + e0 delta1) + K2,   a3 = M (a2 + e0 delta2) + K3
 // become  a1[0] = M[0,:] x + c1,   a2[0] = M^2[0,:] x + M[0,0] delta1 + c2,
 //         a3 = M^3 x + M^2[:,0] delta1 + M[:,0] delta2 + c3          (c1, c2, c3 precomputed from the round constants)
-// i.e. two single-row products and ONE dense product instead of three dense products: 23 linear layers (round 3's
-// MDS and the 22 partial rounds) cost 8 dense products.  Tables: tools/gen_poseidon_constants.py derive_fused (which
-// also asserts the no-overflow bound).  Algebraically identical to the reference's rounds, so outputs are bit-exact.
+// i.e. two single-row products and ONE dense product instead of three dense products (poseidon_partial_group_t<3>; tables:
+// tools/gen_poseidon_constants.py derive_fused, which also asserts the no-overflow bound).
+//
+// Four rounds per dense product (poseidon_partial_group_t<4>, what the one-lane permutation runs).  What limits the depth is the
+// 32-bit multiplier of a multiply-add, not the accumulator: the entries of M^4 are 29-bit numbers (357,057,728 .. 381,558,488), so a
+// row of M^4 is still 24 multiply-adds with scalar multipliers; the entries of M^5 have 37 bits and are not.  The row sums of M^4 are
+// 2^32 * 1.04, so a half-sum of a row can pass 2^64 -- by less than 2^60, and only in its LAST multiply-add (bounds (a)-(c) of
+// poseidon_group4.inc, asserted by the generator and by static_assert there).  That multiply-add's carry-out is the instruction's
+// own scalar result, and the row is folded by poseidon_fold_wide, which takes al, ah < 2^64 and the two carries.
+//     a4 = M^4 x + M^3[:,0] delta1 + M^2[:,0] delta2 + M[:,0] delta3 + c4,   a3[0] = M^3[0,:] x + M^2[0,0] delta1 + M[0,0] delta2 + c3
+// The 23 linear layers (round 3's MDS and the 22 partial rounds) are five four-round groups and one three-round group: 6 dense
+// products and 17 single rows (tables: derive_group4).  Algebraically identical to the reference's rounds, so outputs are bit-exact.
 //
 // The state is kept "loose" (any uint64 representing its residue) between rounds and canonicalised once
 // on exit -- see gl_dev.h for the overflow arguments of every loose primitive.
@@ -37,6 +46,7 @@ namespace pc_host {
 #undef ZKM_CONST
 #define ZKM_CONST static const
 #include "poseidon_constants.inc"
+#include "poseidon_group4.inc"
 ZKM_CONST uint64_t ZKM_POSEIDON_ZERO12[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // "constants" after the last round
 }  // namespace pc_host
 #if defined(__HIPCC__)
@@ -44,6 +54,7 @@ namespace pc_dev {
 #undef ZKM_CONST
 #define ZKM_CONST static __device__ __constant__ const
 #include "poseidon_constants.inc"
+#include "poseidon_group4.inc"
 ZKM_CONST uint64_t ZKM_POSEIDON_ZERO12[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 }  // namespace pc_dev
 #endif
@@ -54,7 +65,7 @@ ZKM_CONST uint64_t ZKM_POSEIDON_ZERO12[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0
 #define PC pc_dev
 #define POSEIDON_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 // region markers for tools/isa_histogram.py (comments in the assembly; no instructions): the permutation's control flow has parts
-// that run 8, 7 and 1 times per permutation, which loop trip counts alone cannot express
+// that run 8, 5 and 1 times per permutation, which loop trip counts alone cannot express
 #define POSEIDON_REGION(name) asm volatile("; ZKM_REGION " name)
 #else
 #define PC pc_host
@@ -106,6 +117,68 @@ GL_HD uint64_t poseidon_fold(uint64_t al, uint64_t ah) {
     uint64_t hs = (uint64_t)(uint32_t)ah + (s1 >> 32);
     uint64_t base = (hs << 32) | (uint32_t)s1;
     return (uint64_t)(uint32_t)(hs >> 32) * 0xFFFFFFFFu + base;
+}
+
+// x * m + c (mod 2^64) with the multiplier in a scalar register, and the carry-out of the 64-bit add: the instruction's own scalar
+// result, no compare.  Device: `carry` is the wave's lane mask (bit l = lane l carried); host: 0 or 1.
+GL_HD uint64_t gl_mad_s_co(uint32_t x, uint32_t m, uint64_t c, uint64_t& carry) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t r;
+    asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(r), "=s"(carry) : "v"(x), "s"(m), "v"(c));
+    return r;
+#else
+    const uint64_t r = (uint64_t)x * m + c;
+    carry = r < c;
+    return r;
+#endif
+}
+
+// (al + 2^64 cl) + 2^32 (ah + 2^64 ch) -> loose, for ANY al, ah < 2^64 and any carries cl, ch (device: lane masks, host: 0 / 1).
+// The fold of an M^4 row, whose half-sums can pass 2^64 once.  2^64 == EPS and 2^96 == -1, so the value is
+//     al + 2^32 ah_lo + EPS ah_hi  +  EPS cl - ch.
+//   t  = al + EPS ah_hi <= (2^64 - 1) + (2^32 - 1)^2 < 2^65: one multiply-add whose carry-out w1 again weighs EPS.  If w1 = 1 the
+//        wrapped t is <= 2^64 - 2^33, so t' = t + EPS w1 <= 2^64 - 2^32 - 1 does not wrap.
+//   hs = t'_hi + ah_lo is a 33-bit number whose top bit w2 weighs 2^64 == EPS.  If w2 = 1 then hs_lo32 <= 2^32 - 2, so
+//        r = (hs_lo32 : t'_lo) + EPS w2 <= 2^64 - 2 does not wrap.            r == al + 2^32 ah for every al, ah.
+//   cl, ch: a half-sum carries about once in 10^8 rows of uniformly distributed words (its mean is 0.52 * 2^64, its deviation
+//        0.09 * 2^64) and at the all-ones state on every row; the two corrections sit behind one wave-uniform branch on the masks.
+//        r + EPS cl is loose + canonical (gl_add_lc: after a wrap the sum is < EPS, and EPS more cannot wrap); r - ch borrows only at
+//        r = 0, where the result is p - 1.
+//        Correct whether or not the branch is rare.
+GL_HD uint64_t poseidon_fold_wide(uint64_t al, uint64_t ah, uint64_t cl, uint64_t ch) {
+    uint64_t r;
+#if defined(__HIP_DEVICE_COMPILE__)
+    // (the carries travel in vcc from each instruction to the next: written out, so that no 64-bit add needs a zero-extended pair)
+    uint64_t t;
+    uint32_t e, rlo, rhi;
+    asm("v_mad_u64_u32 %0, vcc, %2, -1, %3\n\tv_cndmask_b32 %1, 0, -1, vcc" : "=&v"(t), "=&v"(e) : "v"((uint32_t)(ah >> 32)), "v"(al) : "vcc");
+    asm("v_add_co_u32 %0, vcc, %3, %2\n\t"            // t' = t + EPS w1
+        "v_addc_co_u32 %1, vcc, 0, %4, vcc\n\t"
+        "v_add_co_u32 %1, vcc, %1, %5\n\t"            // hs = t'_hi + ah_lo, w2 in vcc
+        "v_cndmask_b32 %2, 0, -1, vcc\n\t"
+        "v_add_co_u32 %0, vcc, %0, %2\n\t"            // r = (hs_lo32 : t'_lo) + EPS w2
+        "v_addc_co_u32 %1, vcc, 0, %1, vcc"
+        : "=&v"(rlo), "=&v"(rhi), "+&v"(e)
+        : "v"((uint32_t)t), "v"((uint32_t)(t >> 32)), "v"((uint32_t)ah)
+        : "vcc");
+    r = ((uint64_t)rhi << 32) | rlo;
+    if (__builtin_expect((cl | ch) != 0, 0)) {          // the wave's carry masks: a scalar branch
+        asm volatile("; ZKM_COLD");
+        const unsigned lane = __lane_id() & 63;
+        if ((cl >> lane) & 1) r = gl_add_lc(r, GL_EPS);
+        if ((ch >> lane) & 1) r = r ? r - 1 : GL_P - 1;
+    }
+#else
+    const uint64_t p1 = (uint64_t)(uint32_t)(ah >> 32) * 0xFFFFFFFFu;
+    uint64_t t = p1 + al;
+    if (t < al) t += GL_EPS;
+    const uint64_t hs = (t >> 32) + (uint32_t)ah;
+    r = (hs << 32) | (uint32_t)t;
+    if (hs >> 32) r += GL_EPS;
+    if (cl) r = gl_add_lc(r, GL_EPS);
+    if (ch) r = r ? r - 1 : GL_P - 1;
+#endif
+    return r;
 }
 
 // Circulant MDS (first row CIRC = {17,15,41,16,2,28,13,13,39,18,34,20}, plus 8 on the (0,0) entry):
@@ -191,15 +264,45 @@ GL_HD void poseidon_group_rows(uint64_t s[12], const uint32_t lo[12], const uint
     }
 }
 
-// T linear layers (T = 3 or 2) with the T - 1 lane-0 s-boxes between them; c3 = constants after the last layer.
-// delta(k, a) = what lane 0 gains at s-box k = 0, 1 of the group on its input a: sbox(a) - a in the permutation; the constraint
+// Rows I .. 11 of the M^4 layer that closes a four-round group.  The constant c4[i] opens both half-sums as the addend of the term with
+// the inline multiplier M[i][0] (delta3's); each half-sum ends on the M^4 term of column 11, whose carry-out goes to the fold: every
+// partial sum before it is exact (bound (b) of poseidon_group4.inc) and the complete sum carries at most once (bound (c)).
+template <int I>
+GL_HD void poseidon_group4_rows(uint64_t s[12], const uint32_t lo[12], const uint32_t hi[12], uint32_t d1l, uint32_t d1h, uint32_t d2l, uint32_t d2h,
+                                uint32_t d3l, uint32_t d3h, const uint64_t* c4) {
+    if constexpr (I < 12) {
+        static_assert(PC::ZKM_POSEIDON_G4_DCOL[0][I] == poseidon_m1(I, 0) && PC::ZKM_POSEIDON_G4_DCOL[1][I] == PC::ZKM_POSEIDON_M2[I][0] &&
+                      PC::ZKM_POSEIDON_G4_DCOL[2][I] == PC::ZKM_POSEIDON_M3[I][0], "first columns of M, M^2, M^3");
+        uint64_t al = gl_mad_imm_sc<poseidon_m1(I, 0)>(d3l, (uint64_t)(uint32_t)c4[I]), ah = gl_mad_imm_sc<poseidon_m1(I, 0)>(d3h, c4[I] >> 32);
+        al = gl_mad_s(d2l, PC::ZKM_POSEIDON_G4_DCOL[1][I], al);
+        ah = gl_mad_s(d2h, PC::ZKM_POSEIDON_G4_DCOL[1][I], ah);
+        al = gl_mad_s(d1l, PC::ZKM_POSEIDON_G4_DCOL[2][I], al);
+        ah = gl_mad_s(d1h, PC::ZKM_POSEIDON_G4_DCOL[2][I], ah);
+#pragma unroll
+        for (int j = 0; j < 11; j++) {
+            al = gl_mad_s(lo[j], PC::ZKM_POSEIDON_M4[I][j], al);
+            ah = gl_mad_s(hi[j], PC::ZKM_POSEIDON_M4[I][j], ah);
+        }
+        uint64_t cl, ch;
+        al = gl_mad_s_co(lo[11], PC::ZKM_POSEIDON_M4[I][11], al, cl);
+        ah = gl_mad_s_co(hi[11], PC::ZKM_POSEIDON_M4[I][11], ah, ch);
+        s[I] = poseidon_fold_wide(al, ah, cl, ch);
+        if ((I & 1) == 1) POSEIDON_SCHED_FENCE();
+        poseidon_group4_rows<I + 1>(s, lo, hi, d1l, d1h, d2l, d2h, d3l, d3h, c4);
+    }
+}
+
+// T linear layers (T = 4, 3 or 2) with the T - 1 lane-0 s-boxes between them; c3 = constants after the last layer (T = 4: of word 0
+// after the third layer, with c4 = constants after the last).
+// delta(k, a) = what lane 0 gains at s-box k = 0, 1 (T = 4: and 2) of the group on its input a: sbox(a) - a in the permutation; the constraint
 // evaluator (constraints_dev.h) takes the s-box output from a witness cell instead.
 // c1, c2, c3[] are wave-uniform on the device: their halves are the scalar addends of each sum's first multiply-add (gl_mad_imm_sc).
 // ROW0_ASM: the first single row (M, inline multipliers) written out term by term (poseidon_m_row0).  The sponge kernels want it: left to
 // the compiler the row's shifts and shared multipliers need zero-extended register pairs, and with those gone it keeps ONE zeroed
 // scratch pair for the whole kernel.  The constraint evaluator does not: k_quotient<POSEIDON, 1> needs 93 registers with it, 69 without.
 template <int T, bool ROW0_ASM = true, class DELTA>
-GL_HD void poseidon_partial_group_t(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3, DELTA&& delta) {
+GL_HD void poseidon_partial_group_t(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3, DELTA&& delta, const uint64_t* c4 = nullptr) {
+    static_assert(T == 2 || T == 3 || T == 4, "groups of two, three or four layers");
     uint32_t lo[12], hi[12];
 #pragma unroll
     for (int i = 0; i < 12; i++) {
@@ -220,7 +323,7 @@ GL_HD void poseidon_partial_group_t(uint64_t s[12], uint64_t c1, uint64_t c2, co
     const uint32_t d1l = (uint32_t)d1, d1h = (uint32_t)(d1 >> 32);
     uint32_t d2l = 0, d2h = 0;
     POSEIDON_SCHED_FENCE();
-    if (T == 3) {
+    if (T >= 3) {
         al = gl_mad_imm_sc<poseidon_m1(0, 0)>(d1l, (uint64_t)(uint32_t)c2);
         ah = gl_mad_imm_sc<poseidon_m1(0, 0)>(d1h, c2 >> 32);
 #pragma unroll
@@ -233,7 +336,25 @@ GL_HD void poseidon_partial_group_t(uint64_t s[12], uint64_t c1, uint64_t c2, co
         d2h = (uint32_t)(d2 >> 32);
         POSEIDON_SCHED_FENCE();
     }
-    poseidon_group_rows<T, 0>(s, lo, hi, d1l, d1h, d2l, d2h, c3);
+    if constexpr (T == 4) {
+        // word 0 after the third layer: row 0 of the three-round group's dense layer, c3[0] its constant
+        al = gl_mad_s(d1l, PC::ZKM_POSEIDON_M2[0][0], gl_mad_imm_sc<poseidon_m1(0, 0)>(d2l, (uint64_t)(uint32_t)c3[0]));
+        ah = gl_mad_s(d1h, PC::ZKM_POSEIDON_M2[0][0], gl_mad_imm_sc<poseidon_m1(0, 0)>(d2h, c3[0] >> 32));
+#pragma unroll
+        for (int j = 0; j < 12; j++) {
+            al = gl_mad_s(lo[j], PC::ZKM_POSEIDON_M3[0][j], al);
+            ah = gl_mad_s(hi[j], PC::ZKM_POSEIDON_M3[0][j], ah);
+        }
+        const uint64_t d3 = delta(2, poseidon_fold(al, ah));
+        POSEIDON_SCHED_FENCE();
+        poseidon_group4_rows<0>(s, lo, hi, d1l, d1h, d2l, d2h, (uint32_t)d3, (uint32_t)(d3 >> 32), c4);
+    } else {
+        poseidon_group_rows<T, 0>(s, lo, hi, d1l, d1h, d2l, d2h, c3);
+    }
+}
+// one four-round group: c3 = &(constant of word 0 after the third layer), c4 = constants after the fourth
+GL_HD void poseidon_partial_group4(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3, const uint64_t* c4) {
+    poseidon_partial_group_t<4>(s, c1, c2, c3, [](int, uint64_t a) { return poseidon_sbox_delta(a); }, c4);
 }
 template <int T>
 GL_HD void poseidon_partial_group(uint64_t s[12], uint64_t c1, uint64_t c2, const uint64_t* c3) {
@@ -280,17 +401,17 @@ GL_HD void poseidon_permute_out_t(uint64_t s[12], int out, const MDS& mds) {
             POSEIDON_REGION("partial_head");
             // round 3's MDS opens the first fused group; the groups cover the MDS of rounds 3 .. 25 and the s-boxes of rounds 4 .. 25
 #pragma unroll 1
-            for (int g = 0; g < 7; g++) {  // MDS of rounds 3g+3 .. 3g+5 and the s-boxes of rounds 3g+4, 3g+5; then round 3g+6's
-                POSEIDON_REGION("partial_group");
-                poseidon_partial_group<3>(s, PC::ZKM_POSEIDON_FUSED_C1[g], PC::ZKM_POSEIDON_FUSED_C2[g], PC::ZKM_POSEIDON_FUSED_C3[g]);
+            for (int g = 0; g < 5; g++) {  // MDS of rounds 4g+3 .. 4g+6 and the s-boxes of rounds 4g+4 .. 4g+6; then round 4g+7's
+                POSEIDON_REGION("partial_group4");
+                poseidon_partial_group4(s, PC::ZKM_POSEIDON_G4_C1[g], PC::ZKM_POSEIDON_G4_C2[g], &PC::ZKM_POSEIDON_G4_C3[g], PC::ZKM_POSEIDON_G4_C4[g]);
                 s[0] = poseidon_sbox7(s[0]);
             }
             POSEIDON_REGION("partial_tail");
-            const uint64_t* fc1 = PC::ZKM_POSEIDON_FUSED_C1;
-            const uint64_t* fc3 = PC::ZKM_POSEIDON_FUSED_C3[7];
-            POSEIDON_OPAQUE_PTR(fc1);
-            POSEIDON_OPAQUE_PTR(fc3);
-            poseidon_partial_group<2>(s, fc1[7], 0, fc3);  // MDS of rounds 24, 25
+            const uint64_t* tc12 = PC::ZKM_POSEIDON_G4_TAIL_C12;
+            const uint64_t* tc3 = PC::ZKM_POSEIDON_G4_TAIL_C3;
+            POSEIDON_OPAQUE_PTR(tc12);
+            POSEIDON_OPAQUE_PTR(tc3);
+            poseidon_partial_group<3>(s, tc12[0], tc12[1], tc3);  // MDS of rounds 23, 24, 25 and the s-boxes of rounds 24, 25
         } else if (r == 7 && out != POSEIDON_OUT_ALL) {
             POSEIDON_REGION("last_mds_rows");
             if (out == POSEIDON_OUT_CAPACITY) poseidon_mds_add<false, 8, 12>(s, nullptr);
