@@ -115,6 +115,43 @@ def test_three_segments_in_one_call_one_wait_one_launch_a_kind(ctx, zkm):
     assert rec["io_calls/rows"][0] == 1 and not any(s in rec for s in SCOPES if s != "io_calls/rows"), rec
 
 
+DEVICE_LISTS = ("extend_w16", "compress_hx", "compress_w", "keccak_inputs", "keccak_digest_addrs", "io_data")
+
+
+def test_a_segment_with_its_lists_in_device_memory_between_two_with_host_lists(ctx, zkm):
+    """Which lists go up differs between the segments of one launch, and where the last segment's lists lie in the scratch block depends
+    on it.  THREE's middle segment has no calls, so the middle one here is "all" -- the segment with a call of every kind that takes
+    lists in device memory -- with every such list there (whole: the byte lists are indexed by absolute offsets in device memory);
+    "io-long" in front and "four" behind keep their lists on the host."""
+    from zkm_amd import _as_words
+    names = (THREE[0], "all", THREE[2])
+    pairs = [wanted(ctx, zkm, name) for name in names]
+    calls = [zkm.SegmentCalls(**kw) for kw, _ in pairs]
+    assert all(name in calls[1].lists for name in DEVICE_LISTS) and all(calls[1].lists[name].size for name in DEVICE_LISTS)
+    assert any(name in calls[0].lists for name in DEVICE_LISTS) and sum(name in calls[2].lists for name in DEVICE_LISTS) >= 5
+    bufs = []
+    try:
+        for name in DEVICE_LISTS:
+            a = calls[1].lists[name]
+            bufs.append(ctx.alloc((a.nbytes + 7) // 8).upload(_as_words(a)))
+            calls[1].lists[name] = bufs[-1]
+        ctx.profile(True)
+        ctx.profile_reset()
+        try:
+            x = ctx.segments_calls_expand(calls)
+            rec = ctx.profile_records()
+        finally:
+            ctx.profile(False)
+            ctx.profile_reset()
+        with x:
+            assert [rec[s][0] for s in SCOPES] == [1, 1, 1, 1], rec
+            for s, (_, want) in enumerate(pairs):
+                assert_expansions_equal(x.download(s), want, "segment %d (%s)" % (s, names[s]))
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def composed(ctx, zkm, kws):
     pairs = [ctx.calls_expand(**kw) for kw in kws]
     return [s for s, _ in pairs], [o for _, o in pairs]

@@ -6,20 +6,18 @@
 // The host half (zkm_segment_calls_steps) is built from the four zkm_*_steps / zkm_*_counts entry points and restates none of them.  The
 // device half is a stage in FRONT of the builder (segment_ops.hip is not touched): per group of up to ZKM_MAX_SEG segments one scratch
 // block for every list the host holds and the kernels' descriptors, one launch per kind through the kinds' own K-segment launchers
-// (zkm_internal.h "the calls' expansions"), one host wait.  A segment's rows and lists live in ONE block of the context's allocator, each
-// list in a run of its own (256-byte aligned): own items in front, the generated ones behind in the order SHA, Keccak, I/O, instructions.
-#include <functional>
-
-#include "zkm_internal.h"
+// (zkm_internal.h "the calls' expansions": each an instantiation of the one launcher in calls_launch.h), one host wait.  A segment's rows
+// and lists live in ONE block of the context's allocator, each list in a run of its own (256-byte aligned): own items in front, the
+// generated ones behind in the order SHA, Keccak, I/O, instructions.
+#include "calls_launch.h"
 
 namespace {
 
+using namespace zkm_calls;
 constexpr size_t CPU_W = ZKM_CPU_COLS;
-std::string dec(uint64_t v) { return std::to_string(v); }
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // a pure entry point of the library, its failure as an exception with its message
-void must(const std::function<int(char**)>& call) {
+template <class F> void must(F&& call) {
     char* e = nullptr;
     if (call(&e) == 0) return;
     const std::string m = e ? e : "error";

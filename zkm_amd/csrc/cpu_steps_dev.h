@@ -22,6 +22,8 @@ namespace zkm_step {
 // column map (cpu/columns/mod.rs:62-96, ops.rs, general.rs)
 constexpr unsigned C_IS_BOOT = 0, C_IS_EXIT = 1, C_CONTEXT = 2, C_PC = 4, C_NEXT_PC = 5, C_KERNEL = 6, C_OP = 7, C_BR = 40, C_BITS = 50, C_GEN = 86,
                    C_MEMIO = 188, C_CLOCK = 204, C_CH0 = 205, NUM_GP_CHANNELS = 8;
+constexpr unsigned C_IS_KECCAK_SPONGE = 83, C_IS_SHA_EXTEND_SPONGE = 84, C_IS_SHA_COMPRESS_SPONGE = 85;   // the sponge flags behind the bit fields
+static_assert(C_CLOCK + 1 == C_CH0, "a row's clock and its 48 channel cells are 49 contiguous words");
 constexpr uint32_t SEG_CODE = 0, SEG_SHIFT = 3, SEG_REG = 4;
 // op flags, in the order of cpu/columns/ops.rs
 enum : unsigned {
@@ -39,6 +41,18 @@ enum : uint32_t { A_ADD = 0, A_ADDU = 1, A_ADDI = 2, A_ADDIU = 3, A_SUB = 4, A_S
 
 GL_HD uint32_t sext(uint32_t v, unsigned n) { return (v >> (n - 1)) & 1 ? v | (0xFFFFFFFFu << n) : v & ((n < 32 ? 1u << n : 0u) - 1u); }
 GL_HD uint32_t low_mask(unsigned n) { return n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u; }   // n low bits
+
+#ifdef __HIPCC__
+// what the kernels that write a row's channels cell by cell compute (sha_calls.hip, keccak_calls.hip):
+// the cell `f` of a used channel (cpu/columns/mod.rs MemoryChannelView: used, is_read, addr_context, addr_segment, addr_virtual, value)
+__device__ __forceinline__ uint64_t chan_cell(unsigned f, bool is_read, uint64_t ctx, uint64_t seg, uint64_t virt, uint32_t value) {
+    return f == 0 ? 1 : f == 1 ? (uint64_t)is_read : f == 2 ? ctx : f == 3 ? seg : f == 4 ? virt : (uint64_t)value;
+}
+// the word `f` of a memory read of the sponge (zkm_memory_trace's six words)
+__device__ __forceinline__ uint64_t read_word(unsigned f, uint64_t ctx, uint64_t seg, uint64_t virt, uint64_t ts, uint32_t value) {
+    return f == 0 ? ctx : f == 1 ? seg : f == 2 ? virt : f == 3 ? ts : f == 4 ? 1 : (uint64_t)value;
+}
+#endif
 
 // what a walk returns
 enum : int { OK = 0, BAD_KIND = 1, BAD_ENCODING = 2, BAD_OPERANDS = 3 };

@@ -16,11 +16,8 @@
 // ballot over the lanes in front) and build their row in LDS through expand; then all lanes stream the block out word by word, adjacent
 // lanes on adjacent words with 8-byte stores.  Every word is written exactly once, so no zero-fill pass comes in front; the kernel's
 // floor is the 2,072 bytes a row it has to write.
-#include <array>
-#include <vector>
-
+#include "calls_launch.h"
 #include "cpu_steps_dev.h"
-#include "zkm_internal.h"
 
 namespace zkm_insn {
 
@@ -174,6 +171,7 @@ struct shape {
 namespace {
 
 using namespace zkm_insn;
+using namespace zkm_calls;
 constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256, ROWS_PER_WG = 16;
 static_assert(ROWS_PER_WG <= 64, "the rows' lanes are one wave: the arithmetic slots come from a ballot");
 static_assert(ROWS_PER_WG * CPU_W * 8 <= 48 * 1024, "the workgroup's rows fit in LDS");
@@ -240,15 +238,7 @@ __global__ __launch_bounds__(THREADS) void k_insn_rows(const insn_rows_args* __r
 }
 
 // ---- the host walk: every refusal, naming the record; the counts, the masks, the workgroups' bases
-constexpr uint64_t LIM = (uint64_t)1 << 32;
 const char* const KIND_NAME[NKINDS] = {"LUI", "MUL", "MULT", "MULTU", "DIV", "DIVU", "MFHI", "MTHI", "MFLO", "MTLO", "SDC1", "SYNC", "PREF"};
-std::string dec(uint64_t v) { return std::to_string(v); }
-std::string hex8(uint32_t v) {
-    char buf[16];
-    snprintf(buf, sizeof buf, "0x%08x", v);
-    return buf;
-}
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct totals { uint64_t mem = 0, arith = 0; };
 
@@ -289,19 +279,23 @@ void check_clocks(const uint64_t* clocks, size_t n) {
         if (clocks[k] >= LIM) throw std::runtime_error("record " + dec(k) + ": clock " + dec(clocks[k]) + " does not fit in 32 bits");
 }
 
-size_t wgs(size_t n) { return (n + ROWS_PER_WG - 1) / ROWS_PER_WG; }
-// where a job's three uploads lie behind the K descriptors
-size_t layout(const zkm_insn_job* j, size_t nseg, std::array<size_t, 3>* at) {
-    size_t total = up256(nseg * sizeof(insn_rows_args));
-    for (size_t s = 0; s < nseg; s++) {
-        const size_t bytes[3] = {j[s].n * sizeof(zkm_cpu_step), j[s].n * 8, wgs(j[s].n) * 4};
-        for (int i = 0; i < 3; i++) {
-            if (at) at[s][i] = total;
-            total += up256(bytes[i]);
-        }
+// what the K-segment launcher takes of this kind (calls_launch.h)
+struct insn_kind {
+    using job = zkm_insn_job;
+    using args = insn_rows_args;
+    static constexpr const char *name = "zkm_insn_rows_launch", *scope = "insn_rows/rows";
+    static constexpr auto kernel = k_insn_rows;
+    static constexpr unsigned threads = THREADS;
+    // a job's three lists: the records, the clocks, the workgroups' bases; the host holds them all
+    static std::array<zkm_calls_list, 3> lists(const job& j) {
+        return {{{j.insns, j.n * sizeof(zkm_cpu_step), true}, {j.clocks, j.n * 8, true}, {j.base.data(), j.base.size() * 4, true}}};
     }
-    return total;
-}
+    static args make(const job& j, const void* const* dev) {
+        return {(const zkm_cpu_step*)dev[0], (const uint64_t*)dev[1], (const uint32_t*)dev[2], j.rows, j.narith ? j.arith : nullptr, j.n, (uint32_t)extent(j)};
+    }
+    static size_t extent(const job& j) { return (j.n + ROWS_PER_WG - 1) / ROWS_PER_WG; }   // a workgroup for ROWS_PER_WG records
+    static size_t sparse_rows(const job&) { return 0; }   // (the kernel writes every word)
+};
 
 }  // namespace
 
@@ -312,27 +306,9 @@ void zkm_insn_rows_check(zkm_insn_job& j) {
     j.nmem = sum.mem;
     j.narith = sum.arith;
 }
-size_t zkm_insn_rows_scratch(const zkm_insn_job* j, size_t nseg) { return layout(j, nseg, nullptr); }
+size_t zkm_insn_rows_scratch(const zkm_insn_job* j, size_t nseg) { return zkm_calls_layout<insn_kind>(j, nseg, nullptr); }
 void zkm_insn_rows_launch(zkm_ctx* c, const zkm_insn_job* j, size_t nseg, char* sb, zkm_calls_hold& hold) {
-    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_insn_rows_launch: segment count out of range");
-    std::vector<std::array<size_t, 3>> at(nseg);
-    layout(j, nseg, at.data());
-    insn_rows_args* d = hold.make<insn_rows_args>(nseg);
-    size_t grid = 0;
-    for (size_t s = 0; s < nseg; s++) {
-        const void* in[3] = {j[s].insns, j[s].clocks, j[s].base.data()};
-        const size_t bytes[3] = {j[s].n * sizeof(zkm_cpu_step), j[s].n * 8, j[s].base.size() * 4};
-        for (int i = 0; i < 3; i++)
-            if (bytes[i]) ZKM_HIP_CHECK(hipMemcpyAsync(sb + at[s][i], in[i], bytes[i], hipMemcpyHostToDevice, c->stream));
-        d[s] = insn_rows_args{(const zkm_cpu_step*)(sb + at[s][0]), (const uint64_t*)(sb + at[s][1]), (const uint32_t*)(sb + at[s][2]), j[s].rows,
-                              j[s].narith ? j[s].arith : nullptr, j[s].n, (uint32_t)wgs(j[s].n)};
-        grid = std::max(grid, wgs(j[s].n));
-    }
-    if (!grid) return;
-    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(insn_rows_args), hipMemcpyHostToDevice, c->stream));
-    zkm_prof_scope ps(c, "insn_rows/rows");
-    hipLaunchKernelGGL(k_insn_rows, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(THREADS), 0, c->stream, (const insn_rows_args*)sb);
-    ZKM_HIP_CHECK(hipGetLastError());
+    zkm_calls_queue<insn_kind>(c, j, nseg, sb, hold, false);
 }
 
 extern "C" {
@@ -361,13 +337,7 @@ int zkm_insn_rows_steps(const zkm_cpu_step* insns, size_t ninsns, size_t raw_bas
         }
         if (ninsns && !steps_out) refuse("steps_out: NULL with " + dec(ninsns) + " records to write");
         if (raw_base >= LIM || raw_base + ninsns > LIM) refuse("raw_base " + dec(raw_base) + ": a RAW index does not fit in 32 bits");
-        for (size_t k = 0; k < ninsns; k++) {
-            zkm_cpu_step s{};
-            s.kind = ZKM_STEP_RAW;
-            s.reads[0] = (uint32_t)(raw_base + k);
-            s.reads[1] = masks[k];
-            steps_out[k] = s;
-        }
+        for (size_t k = 0; k < ninsns; k++) steps_out[k] = raw_step(raw_base + k, masks[k]);
     });
 }
 
@@ -379,9 +349,7 @@ int zkm_insn_rows_witness(zkm_ctx* c, const zkm_cpu_step* insns, const uint64_t*
         zkm_insn_job j;
         j.insns = insns, j.clocks = clocks, j.n = ninsns, j.rows = raw_rows_out_dev, j.arith = arithmetic_ops_out_dev;
         try {
-            const totals sum = check_insns(insns, ninsns, nullptr, &j.base);
-            check_clocks(clocks, ninsns);
-            j.nmem = sum.mem, j.narith = sum.arith;
+            zkm_insn_rows_check(j);
         } catch (const std::exception& e) {
             refuse(e.what());
         }
@@ -393,14 +361,9 @@ int zkm_insn_rows_witness(zkm_ctx* c, const zkm_cpu_step* insns, const uint64_t*
         if ((uintptr_t)raw_rows_out_dev & 7) refuse("raw_rows_out_dev is not aligned to its words (8 bytes)");
         if (j.narith && !arithmetic_ops_out_dev) refuse("arithmetic_ops_out_dev: NULL with " + dec(j.narith) + " operations to write");
         if ((uintptr_t)arithmetic_ops_out_dev & 3) refuse("arithmetic_ops_out_dev is not aligned to its words (4 bytes)");
-        if (ninsns > LIM) refuse(dec(ninsns) + " rows: a RAW index does not fit in 32 bits");
         if (!c) refuse("null argument");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        // the K = 1 case of the segments' launch: the descriptor, the records, the clocks and the workgroups' bases go up in one block
-        zkm_calls_hold hold;   // (declared first: it outlives the block's wait for the stream when an exception unwinds)
-        zkm_scratch block(c, zkm_insn_rows_scratch(&j, 1));
-        zkm_insn_rows_launch(c, &j, 1, block.as<char>(), hold);
-        c->sync();   // (the block, the job and the caller's lists are in use until here)
+        zkm_calls_one<insn_kind>(c, j);
     });
 }
 

@@ -15,16 +15,14 @@
 // row-major block word by word, adjacent lanes on adjacent words with 8-byte stores: zeros, the clock, and the channel cells computed in
 // place.  Every word is written, so no zero-fill pass comes in front; the kernel is write-only but for the calls' bytes, and its floor is
 // the 2,072 bytes a row it has to write.
-#include <array>
-#include <vector>
-
+#include "calls_launch.h"
 #include "cpu_steps_dev.h"
-#include "zkm_internal.h"
 
 namespace {
 
 using zkm_step::C_CH0;
 using zkm_step::C_CLOCK;
+using namespace zkm_calls;
 constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256, ROWS_PER_WG = 8;
 static_assert(C_CLOCK + 1 == C_CH0 && C_CH0 + 48 <= CPU_W, "a row's clock and its 48 channel cells are 49 contiguous words");
 
@@ -156,13 +154,6 @@ __global__ __launch_bounds__(THREADS) void k_io_calls(const io_calls_args* __res
 }
 
 // ---- the host's refusals, naming the list and the call's position (they throw the bare message)
-std::string dec(uint64_t v) { return std::to_string(v); }
-std::string hex(uint64_t v) {
-    char buf[24];
-    snprintf(buf, sizeof buf, "0x%llx", (unsigned long long)v);
-    return buf;
-}
-constexpr uint64_t LIM = (uint64_t)1 << 32;
 const char* const KIND_NAME[place::NKINDS] = {"hint read", "commit", "verify", "preimage"};
 
 struct totals { uint64_t rows, mem; };
@@ -212,37 +203,37 @@ void check_meta(const uint32_t* kinds, const uint64_t* off, const uint64_t* meta
     }
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-size_t wgs(size_t rows) { return (rows + ROWS_PER_WG - 1) / ROWS_PER_WG; }
-// a job's five lists: the kinds, the bytes, the offsets, the meta, the row offsets; which of them go up, and where behind the K descriptors
-struct list { const void* p; size_t bytes; bool up; };
-std::array<list, 5> lists(const zkm_io_job& j) {
-    const size_t n = j.n, first = n ? j.off[0] : 0, nbytes = n ? j.off[n] - first : 0;
-    const bool data_up = !zkm_is_device_ptr(j.data);
-    return {{{j.kinds, 4 * n, true},
-             {data_up && j.data ? j.data + first : j.data, nbytes, data_up},
-             {j.off_up.data(), n ? 8 * (n + 1) : 0, true},
-             {j.meta, 32 * n, !zkm_is_device_ptr(j.meta)},
-             {j.row_off.data(), n ? 8 * (n + 1) : 0, true}}};
-}
 // the bytes go up from the first call's offset on, so the offsets that go up count from there
 void rebase_offsets(zkm_io_job& j) {
     j.off_up.assign(j.off, j.off + j.n + 1);
     if (!zkm_is_device_ptr(j.data))
         for (uint64_t& o : j.off_up) o -= j.off[0];
 }
-size_t layout(const zkm_io_job* j, size_t nseg, std::array<size_t, 5>* at) {
-    size_t total = up256(nseg * sizeof(io_calls_args));
-    for (size_t s = 0; s < nseg; s++) {
-        const auto in = lists(j[s]);
-        for (int i = 0; i < 5; i++) {
-            if (at) at[s][i] = total;
-            if (in[i].up) total += up256(in[i].bytes);
-        }
+
+// what the K-segment launcher takes of this kind (calls_launch.h)
+struct io_kind {
+    using job = zkm_io_job;
+    using args = io_calls_args;
+    static constexpr const char *name = "zkm_io_calls_launch", *scope = "io_calls/rows";
+    static constexpr auto kernel = k_io_calls;
+    static constexpr unsigned threads = THREADS;
+    // a job's five lists: the kinds, the bytes, the offsets, the meta, the row offsets; which of them go up
+    static std::array<zkm_calls_list, 5> lists(const job& j) {
+        const size_t n = j.n, first = n ? j.off[0] : 0, nbytes = n ? j.off[n] - first : 0;
+        const bool data_up = !zkm_is_device_ptr(j.data);
+        return {{{j.kinds, 4 * n, true},
+                 {data_up && j.data ? j.data + first : j.data, nbytes, data_up},
+                 {j.off_up.data(), n ? 8 * (n + 1) : 0, true},
+                 {j.meta, 32 * n, !zkm_is_device_ptr(j.meta)},
+                 {j.row_off.data(), n ? 8 * (n + 1) : 0, true}}};
     }
-    return total;
-}
+    static args make(const job& j, const void* const* dev) {
+        return {(const uint32_t*)dev[0], (const uint8_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const uint64_t*)dev[4],
+                j.rows, j.nrows, (uint32_t)j.n, (uint32_t)extent(j)};
+    }
+    static size_t extent(const job& j) { return (j.nrows + ROWS_PER_WG - 1) / ROWS_PER_WG; }   // a workgroup for ROWS_PER_WG rows
+    static size_t sparse_rows(const job&) { return 0; }   // (the kernel writes every word)
+};
 
 }  // namespace
 
@@ -258,32 +249,9 @@ void zkm_io_calls_check(zkm_io_job& j) {
     if (j.n > 0x7FFFFFFF) throw std::runtime_error("2^31 or more calls");
     rebase_offsets(j);
 }
-size_t zkm_io_calls_scratch(const zkm_io_job* j, size_t nseg) { return layout(j, nseg, nullptr); }
+size_t zkm_io_calls_scratch(const zkm_io_job* j, size_t nseg) { return zkm_calls_layout<io_kind>(j, nseg, nullptr); }
 void zkm_io_calls_launch(zkm_ctx* c, const zkm_io_job* j, size_t nseg, char* sb, zkm_calls_hold& hold) {
-    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_io_calls_launch: segment count out of range");
-    std::vector<std::array<size_t, 5>> at(nseg);
-    layout(j, nseg, at.data());
-    io_calls_args* d = hold.make<io_calls_args>(nseg);
-    size_t grid = 0;
-    for (size_t s = 0; s < nseg; s++) {
-        const auto in = lists(j[s]);
-        const void* dev[5];
-        for (int i = 0; i < 5; i++) {
-            dev[i] = in[i].p;
-            if (in[i].up) {
-                dev[i] = sb + at[s][i];
-                if (in[i].bytes) ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-        d[s] = io_calls_args{(const uint32_t*)dev[0], (const uint8_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const uint64_t*)dev[4],
-                             j[s].rows, j[s].nrows, (uint32_t)j[s].n, (uint32_t)wgs(j[s].nrows)};
-        grid = std::max(grid, wgs(j[s].nrows));
-    }
-    if (!grid) return;
-    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(io_calls_args), hipMemcpyHostToDevice, c->stream));
-    zkm_prof_scope ps(c, "io_calls/rows");
-    hipLaunchKernelGGL(k_io_calls, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(THREADS), 0, c->stream, (const io_calls_args*)sb);
-    ZKM_HIP_CHECK(hipGetLastError());
+    zkm_calls_queue<io_kind>(c, j, nseg, sb, hold, false);
 }
 
 extern "C" {
@@ -319,11 +287,7 @@ int zkm_io_calls_steps(const uint32_t* kinds, const uint64_t* data_off, const ui
         for (size_t k = 0; k < ncalls; k++) {
             const uint64_t L = data_off[k + 1] - data_off[k];
             for (size_t j = 0; j < place::rows(kinds[k], L); j++) {
-                zkm_cpu_step s{};
-                s.kind = ZKM_STEP_RAW;
-                s.reads[0] = (uint32_t)(raw_base + row_off[k] + j);
-                s.reads[1] = place::row_mask(kinds[k], L, j);
-                steps_out[row_off[k] + j] = s;
+                steps_out[row_off[k] + j] = raw_step(raw_base + row_off[k] + j, place::row_mask(kinds[k], L, j));
                 clocks_out[row_off[k] + j] = place::row_clock(meta[4 * k + 3], j);
             }
         }
@@ -338,9 +302,7 @@ int zkm_io_calls_witness(zkm_ctx* c, const uint32_t* kinds, const uint8_t* data,
         zkm_io_job j;
         j.kinds = kinds, j.data = data, j.off = data_off, j.meta = meta, j.n = ncalls, j.rows = raw_rows_out_dev;
         try {
-            const totals sum = check_calls(kinds, data_off, ncalls, &j.row_off);
-            check_meta(kinds, data_off, meta, ncalls);
-            j.nrows = sum.rows, j.nmem = sum.mem;
+            zkm_io_calls_check(j);
         } catch (const std::exception& e) {
             refuse(e.what());
         }
@@ -348,20 +310,11 @@ int zkm_io_calls_witness(zkm_ctx* c, const uint32_t* kinds, const uint8_t* data,
             if (!c) refuse("null argument");
             return;
         }
-        const size_t first = data_off[0], nbytes = data_off[ncalls] - first;
-        if (nbytes && !data) refuse("data: NULL with " + dec(nbytes) + " bytes to read");
         if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(j.nrows) + " rows to write");
         if ((uintptr_t)raw_rows_out_dev & 7) refuse("raw_rows_out_dev is not aligned to its words (8 bytes)");
-        if (j.nrows > LIM) refuse(dec(j.nrows) + " rows: a RAW index does not fit in 32 bits");
-        if (ncalls > 0x7FFFFFFF) refuse("2^31 or more calls");
         if (!c) refuse("null argument");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        rebase_offsets(j);
-        // the K = 1 case of the segments' launch: the descriptor and the lists the host holds go up in one block, with the row offsets
-        zkm_calls_hold hold;   // (declared first: it outlives the block's wait for the stream when an exception unwinds)
-        zkm_scratch block(c, zkm_io_calls_scratch(&j, 1));
-        zkm_io_calls_launch(c, &j, 1, block.as<char>(), hold);
-        c->sync();   // (the block, the job and the caller's lists are in use until here)
+        zkm_calls_one<io_kind>(c, j);
     });
 }
 

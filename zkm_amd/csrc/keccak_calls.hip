@@ -14,23 +14,22 @@
 // digest goes into LDS.  After the barrier all lanes write: the 49 contiguous clock and channel cells of a row by adjacent lanes, every
 // list by adjacent lanes on adjacent words; an XOR's lhs is the stored state word ^ the block word.  The row block is zeroed by one
 // memset before the launch, so only the cells a row sets are stored.
-#include <array>
-#include <vector>
-
+#include "calls_launch.h"
 #include "cpu_steps_dev.h"
 #include "hash_constants_dev.h"
-#include "zkm_internal.h"
 
 namespace {
 
 using zkm_step::C_CH0;
 using zkm_step::C_CLOCK;
 using zkm_step::C_GEN;
+using zkm_step::C_IS_KECCAK_SPONGE;
+using zkm_step::chan_cell;
+using zkm_step::read_word;
+using namespace zkm_calls;
 constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256;
-constexpr unsigned C_IS_KECCAK_SPONGE = 83;   // cpu/columns/mod.rs: the sponge flags behind the bit fields
-constexpr uint32_t OP_XOR = 2;                // zkm_logic_trace's code
+constexpr uint32_t OP_XOR = 2;   // zkm_logic_trace's code
 constexpr uint64_t FLAG = ZKM_SPONGE_BYTE_ADDRESSED;
-static_assert(C_CLOCK + 1 == C_CH0, "a row's clock and its 48 channel cells are 49 contiguous words");
 
 // ---- the one statement of where things go, for a call of L input bytes (a positive multiple of 4)
 namespace place {
@@ -67,14 +66,6 @@ struct keccak_calls_args {
     uint32_t ncalls;             // the segment's own extent of the grid
 };
 
-// the cell `f` of a used channel (cpu/columns/mod.rs MemoryChannelView: used, is_read, addr_context, addr_segment, addr_virtual, value)
-__device__ __forceinline__ uint64_t chan_cell(unsigned f, bool is_read, uint64_t ctx, uint64_t seg, uint64_t virt, uint32_t value) {
-    return f == 0 ? 1 : f == 1 ? (uint64_t)is_read : f == 2 ? ctx : f == 3 ? seg : f == 4 ? virt : (uint64_t)value;
-}
-// the word `f` of a memory read of the sponge (zkm_memory_trace's six words)
-__device__ __forceinline__ uint64_t read_word(unsigned f, uint64_t ctx, uint64_t seg, uint64_t virt, uint64_t ts, uint32_t value) {
-    return f == 0 ? ctx : f == 1 ? seg : f == 2 ? virt : f == 3 ? ts : f == 4 ? 1 : (uint64_t)value;
-}
 // byte `pos` of the padded message: the input, then pad10*1 up to the end of the last block
 __device__ __forceinline__ uint32_t padded_byte(const uint8_t* __restrict__ msg, size_t L, size_t pos) {
     if (pos < L) return msg[pos];
@@ -180,14 +171,6 @@ __global__ __launch_bounds__(THREADS) void k_keccak_calls(const keccak_calls_arg
 }
 
 // ---- the host's refusals, naming the list and the call's position (they throw the bare message)
-std::string dec(uint64_t v) { return std::to_string(v); }
-std::string hex(uint64_t v) {
-    char buf[24];
-    snprintf(buf, sizeof buf, "0x%llx", (unsigned long long)v);
-    return buf;
-}
-constexpr uint64_t LIM = (uint64_t)1 << 32;
-
 // the offsets: host memory, increasing, every length a positive multiple of 4.  Returns the totals, and the sums a call if asked.
 call_base check_offsets(const uint64_t* off, size_t n, std::vector<call_base>* bases) {
     call_base sum{0, 0, 0, 0};
@@ -233,36 +216,37 @@ void check_digest_addrs(const uint64_t* addrs, size_t n) {
             throw std::runtime_error("digest_addrs: call " + dec(k) + ": address " + hex(addrs[k]) + ": the digest's eighth word does not fit in 32 bits");
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// a job's five lists: the bytes, the offsets, the meta, the digest addresses, the sums a call; which of them go up
-struct list { const void* p; size_t bytes; bool up; };
-std::array<list, 5> lists(const zkm_keccak_job& j) {
-    const size_t n = j.n, first = n ? j.off[0] : 0, nbytes = n ? j.off[n] - first : 0;
-    const bool inputs_up = !zkm_is_device_ptr(j.inputs);
-    return {{{inputs_up && j.inputs ? j.inputs + first : j.inputs, nbytes, inputs_up},
-             {j.off_up.data(), n ? 8 * (n + 1) : 0, true},
-             {j.meta, 32 * n, !zkm_is_device_ptr(j.meta)},
-             {j.digest_addrs, 8 * n, !zkm_is_device_ptr(j.digest_addrs)},
-             {j.bases.data(), sizeof(call_base) * n, true}}};
-}
 // the input bytes go up from the first call's offset on, so the offsets that go up count from there
 void rebase_offsets(zkm_keccak_job& j) {
     j.off_up.assign(j.off, j.off + j.n + 1);
     if (!zkm_is_device_ptr(j.inputs))
         for (uint64_t& o : j.off_up) o -= j.off[0];
 }
-size_t layout(const zkm_keccak_job* j, size_t nseg, std::array<size_t, 5>* at) {
-    size_t total = up256(nseg * sizeof(keccak_calls_args));
-    for (size_t s = 0; s < nseg; s++) {
-        const auto in = lists(j[s]);
-        for (int i = 0; i < 5; i++) {
-            if (at) at[s][i] = total;
-            if (in[i].up) total += up256(in[i].bytes);
-        }
+
+// what the K-segment launcher takes of this kind (calls_launch.h)
+struct keccak_kind {
+    using job = zkm_keccak_job;
+    using args = keccak_calls_args;
+    static constexpr const char *name = "zkm_keccak_calls_launch", *scope = "keccak_calls/rows_lists";
+    static constexpr auto kernel = k_keccak_calls;
+    static constexpr unsigned threads = THREADS;
+    // a job's five lists: the bytes, the offsets, the meta, the digest addresses, the sums a call; which of them go up
+    static std::array<zkm_calls_list, 5> lists(const job& j) {
+        const size_t n = j.n, first = n ? j.off[0] : 0, nbytes = n ? j.off[n] - first : 0;
+        const bool inputs_up = !zkm_is_device_ptr(j.inputs);
+        return {{{inputs_up && j.inputs ? j.inputs + first : j.inputs, nbytes, inputs_up},
+                 {j.off_up.data(), n ? 8 * (n + 1) : 0, true},
+                 {j.meta, 32 * n, !zkm_is_device_ptr(j.meta)},
+                 {j.digest_addrs, 8 * n, !zkm_is_device_ptr(j.digest_addrs)},
+                 {j.bases.data(), sizeof(call_base) * n, true}}};
     }
-    return total;
-}
+    static args make(const job& j, const void* const* dev) {
+        return {(const uint8_t*)dev[0], (const uint64_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const call_base*)dev[4],
+                j.rows, j.mem, j.perm_in, j.perm_ts, j.logic, (uint32_t)j.n};
+    }
+    static size_t extent(const job& j) { return j.n; }   // a workgroup a call
+    static size_t sparse_rows(const job& j) { return j.nrows; }
+};
 
 }  // namespace
 
@@ -276,33 +260,9 @@ void zkm_keccak_calls_check(zkm_keccak_job& j) {
     j.off_up.clear();
     if (j.n) rebase_offsets(j);
 }
-size_t zkm_keccak_calls_scratch(const zkm_keccak_job* j, size_t nseg) { return layout(j, nseg, nullptr); }
+size_t zkm_keccak_calls_scratch(const zkm_keccak_job* j, size_t nseg) { return zkm_calls_layout<keccak_kind>(j, nseg, nullptr); }
 void zkm_keccak_calls_launch(zkm_ctx* c, const zkm_keccak_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows) {
-    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_keccak_calls_launch: segment count out of range");
-    std::vector<std::array<size_t, 5>> at(nseg);
-    layout(j, nseg, at.data());
-    keccak_calls_args* d = hold.make<keccak_calls_args>(nseg);
-    size_t grid = 0;
-    for (size_t s = 0; s < nseg; s++) {
-        const auto in = lists(j[s]);
-        const void* dev[5];
-        for (int i = 0; i < 5; i++) {
-            dev[i] = in[i].p;
-            if (in[i].up) {
-                dev[i] = sb + at[s][i];
-                if (in[i].bytes) ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-        if (zero_rows && j[s].nrows) ZKM_HIP_CHECK(hipMemsetAsync(j[s].rows, 0, j[s].nrows * CPU_W * sizeof(uint64_t), c->stream));
-        d[s] = keccak_calls_args{(const uint8_t*)dev[0], (const uint64_t*)dev[1], (const uint64_t*)dev[2], (const uint64_t*)dev[3], (const call_base*)dev[4],
-                                 j[s].rows, j[s].mem, j[s].perm_in, j[s].perm_ts, j[s].logic, (uint32_t)j[s].n};
-        grid = std::max(grid, j[s].n);
-    }
-    if (!grid) return;
-    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(keccak_calls_args), hipMemcpyHostToDevice, c->stream));
-    zkm_prof_scope ps(c, "keccak_calls/rows_lists");
-    hipLaunchKernelGGL(k_keccak_calls, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(THREADS), 0, c->stream, (const keccak_calls_args*)sb);
-    ZKM_HIP_CHECK(hipGetLastError());
+    zkm_calls_queue<keccak_kind>(c, j, nseg, sb, hold, zero_rows);
 }
 
 extern "C" {
@@ -341,11 +301,7 @@ int zkm_keccak_calls_steps(const uint64_t* input_off, const uint64_t* meta, size
         for (size_t k = 0; k < ncalls; k++) {
             const uint64_t L = input_off[k + 1] - input_off[k], S = meta[4 * k + 3] / 10;
             for (size_t j = 0; j < place::rows(L); j++) {
-                zkm_cpu_step s{};
-                s.kind = ZKM_STEP_RAW;
-                s.reads[0] = (uint32_t)(raw_base + bases[k].row + j);
-                s.reads[1] = place::row_mask(L, j);
-                steps_out[bases[k].row + j] = s;
+                steps_out[bases[k].row + j] = raw_step(raw_base + bases[k].row + j, place::row_mask(L, j));
                 clocks_out[bases[k].row + j] = place::row_clock(S, L, j);
             }
         }
@@ -361,37 +317,26 @@ int zkm_keccak_calls_witness(zkm_ctx* c, const uint8_t* inputs, const uint64_t* 
         zkm_keccak_job j;
         j.inputs = inputs, j.off = input_off, j.meta = meta, j.digest_addrs = digest_addrs, j.n = ncalls;
         j.rows = raw_rows_out_dev, j.mem = memory_ops_out_dev, j.logic = logic_ops_out_dev, j.perm_in = keccak_inputs_out_dev, j.perm_ts = keccak_timestamps_out_dev;
-        call_base sum;
         try {
-            sum = check_offsets(input_off, ncalls, &j.bases);
-            check_meta(input_off, meta, ncalls);
-            check_digest_addrs(digest_addrs, ncalls);
+            zkm_keccak_calls_check(j);
         } catch (const std::exception& e) {
             refuse(e.what());
         }
-        j.nrows = sum.row, j.nmem = sum.mem, j.nlogic = sum.logic, j.nperm = sum.perm;
-        if (ncalls && !inputs) refuse("inputs: NULL with a count of " + dec(ncalls));
         if (ncalls == 0) {
             if (!c) refuse("null argument");
             return;
         }
-        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(sum.row) + " rows to write");
-        if (!memory_ops_out_dev) refuse("memory_ops_out_dev: NULL with " + dec(sum.mem) + " operations to write");
-        if (!logic_ops_out_dev) refuse("logic_ops_out_dev: NULL with " + dec(sum.logic) + " operations to write");
-        if (!keccak_inputs_out_dev) refuse("keccak_inputs_out_dev: NULL with " + dec(sum.perm) + " permutations to write");
-        if (!keccak_timestamps_out_dev) refuse("keccak_timestamps_out_dev: NULL with " + dec(sum.perm) + " permutations to write");
+        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(j.nrows) + " rows to write");
+        if (!memory_ops_out_dev) refuse("memory_ops_out_dev: NULL with " + dec(j.nmem) + " operations to write");
+        if (!logic_ops_out_dev) refuse("logic_ops_out_dev: NULL with " + dec(j.nlogic) + " operations to write");
+        if (!keccak_inputs_out_dev) refuse("keccak_inputs_out_dev: NULL with " + dec(j.nperm) + " permutations to write");
+        if (!keccak_timestamps_out_dev) refuse("keccak_timestamps_out_dev: NULL with " + dec(j.nperm) + " permutations to write");
         if (((uintptr_t)raw_rows_out_dev | (uintptr_t)memory_ops_out_dev | (uintptr_t)keccak_inputs_out_dev | (uintptr_t)keccak_timestamps_out_dev) & 7 ||
             (uintptr_t)logic_ops_out_dev & 3)
             refuse("an output is not aligned to its words (8 bytes; 4 for the logic operations)");
         if (!c) refuse("null argument");
-        if (ncalls > 0x7FFFFFFF) refuse("2^31 or more calls");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        rebase_offsets(j);
-        // the K = 1 case of the segments' launch: the descriptor and the lists the host holds go up in one block, with the sums a call
-        zkm_calls_hold hold;   // (declared first: it outlives the block's wait for the stream when an exception unwinds)
-        zkm_scratch block(c, zkm_keccak_calls_scratch(&j, 1));
-        zkm_keccak_calls_launch(c, &j, 1, block.as<char>(), hold, true);
-        c->sync();   // (the block, the job and the caller's lists are in use until here)
+        zkm_calls_one<keccak_kind>(c, j);
     });
 }
 

@@ -14,22 +14,22 @@
 // run once by one lane into LDS; after the barrier all lanes write from LDS: the 49 contiguous clock and channel cells of a row by
 // adjacent lanes, every list by adjacent lanes on adjacent words. The row block is zeroed by one memset before the launch, so only the
 // cells a row sets are stored.
-#include <array>
-#include <vector>
-
+#include "calls_launch.h"
 #include "cpu_steps_dev.h"
 #include "hash_constants_dev.h"
-#include "zkm_internal.h"
 
 namespace {
 
 using zkm_step::C_CH0;
 using zkm_step::C_CLOCK;
 using zkm_step::C_GEN;
+using zkm_step::C_IS_SHA_COMPRESS_SPONGE;
+using zkm_step::C_IS_SHA_EXTEND_SPONGE;
+using zkm_step::chan_cell;
+using zkm_step::read_word;
+using namespace zkm_calls;
 constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256;
-constexpr unsigned C_IS_SHA_EXTEND_SPONGE = 84, C_IS_SHA_COMPRESS_SPONGE = 85;   // cpu/columns/mod.rs: the sponge flags behind the bit fields
-constexpr uint32_t OP_AND = 0, OP_XOR = 2;                                       // zkm_logic_trace's codes
-static_assert(C_CLOCK + 1 == C_CH0, "a row's clock and its 48 channel cells are 49 contiguous words");
+constexpr uint32_t OP_AND = 0, OP_XOR = 2;   // zkm_logic_trace's codes
 
 // ---- the one statement of where things go.  E extend calls, then C compress calls, in every list.
 namespace place {
@@ -60,15 +60,6 @@ struct sha_calls_args {
 };
 
 __device__ __forceinline__ uint32_t ror(uint32_t x, unsigned r) { return (x >> r) | (x << (32 - r)); }
-
-// the cell `f` of a used channel (cpu/columns/mod.rs MemoryChannelView: used, is_read, addr_context, addr_segment, addr_virtual, value)
-__device__ __forceinline__ uint64_t chan_cell(unsigned f, bool is_read, uint64_t ctx, uint64_t seg, uint64_t virt, uint32_t value) {
-    return f == 0 ? 1 : f == 1 ? (uint64_t)is_read : f == 2 ? ctx : f == 3 ? seg : f == 4 ? virt : (uint64_t)value;
-}
-// the word `f` of a memory read of the sponge (zkm_memory_trace's six words)
-__device__ __forceinline__ uint64_t read_word(unsigned f, uint64_t ctx, uint64_t seg, uint64_t virt, uint64_t ts, uint32_t value) {
-    return f == 0 ? ctx : f == 1 ? seg : f == 2 ? virt : f == 3 ? ts : f == 4 ? 1 : (uint64_t)value;
-}
 
 // schedule word indices a round i reads, in the generator's order: w[i-15], w[i-2], w[i-16], w[i-7]
 __device__ __forceinline__ unsigned ext_src(unsigned i, unsigned q) { return i - (q == 0 ? 15 : q == 1 ? 2 : q == 2 ? 16 : 7); }
@@ -202,15 +193,8 @@ __global__ __launch_bounds__(THREADS) void k_sha_calls(const sha_calls_args* __r
 }
 
 // ---- the host's refusals: one walk over the two meta lists, naming the list and the call's position (throws the bare message)
-std::string dec(uint64_t v) { return std::to_string(v); }
-std::string hex(uint64_t v) {
-    char buf[24];
-    snprintf(buf, sizeof buf, "0x%llx", (unsigned long long)v);
-    return buf;
-}
 
 void check_meta(const uint64_t* emeta, size_t E, const uint64_t* cmeta, size_t C) {
-    constexpr uint64_t LIM = (uint64_t)1 << 32;
     if (E >= LIM / place::EXT_MEM || C >= LIM / place::CMP_LOGIC) throw std::runtime_error("2^32 or more operations");
     auto timestamp = [](const std::string& at, uint64_t ts, uint64_t before, const char* first) {
         if (ts % 10) throw std::runtime_error(at + "timestamp " + dec(ts) + " is not a multiple of 10 (NUM_CHANNELS)");
@@ -246,24 +230,25 @@ void check_meta(const uint64_t* emeta, size_t E, const uint64_t* cmeta, size_t C
     }
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// a job's five lists: which of them go up (the ones the host holds), and where behind the K descriptors
-struct list { const void* p; size_t bytes; };
-std::array<list, 5> lists(const zkm_sha_job& j) {
-    return {{{j.w16, 64 * j.E}, {j.emeta, 32 * j.E}, {j.hx, 32 * j.C}, {j.w, 256 * j.C}, {j.cmeta, 64 * j.C}}};
-}
-size_t layout(const zkm_sha_job* j, size_t nseg, std::array<size_t, 5>* at) {
-    size_t total = up256(nseg * sizeof(sha_calls_args));
-    for (size_t s = 0; s < nseg; s++) {
-        const auto in = lists(j[s]);
-        for (int i = 0; i < 5; i++) {
-            if (at) at[s][i] = total;
-            if (in[i].bytes && !zkm_is_device_ptr(in[i].p)) total += up256(in[i].bytes);
-        }
+// what the K-segment launcher takes of this kind (calls_launch.h)
+struct sha_kind {
+    using job = zkm_sha_job;
+    using args = sha_calls_args;
+    static constexpr const char *name = "zkm_sha_calls_launch", *scope = "sha_calls/rows_lists";
+    static constexpr auto kernel = k_sha_calls;
+    static constexpr unsigned threads = THREADS;
+    // a job's five lists: the ones the host holds go up
+    static std::array<zkm_calls_list, 5> lists(const job& j) {
+        auto list = [](const void* p, size_t bytes) { return zkm_calls_list{p, bytes, bytes && !zkm_is_device_ptr(p)}; };
+        return {{list(j.w16, 64 * j.E), list(j.emeta, 32 * j.E), list(j.hx, 32 * j.C), list(j.w, 256 * j.C), list(j.cmeta, 64 * j.C)}};
     }
-    return total;
-}
+    static args make(const job& j, const void* const* dev) {
+        return {(const uint32_t*)dev[0], (const uint64_t*)dev[1], (const uint32_t*)dev[2], (const uint32_t*)dev[3], (const uint64_t*)dev[4],
+                j.E, j.C, j.rows, j.mem, j.ext_ts, j.logic, j.ext_in};
+    }
+    static size_t extent(const job& j) { return j.E + j.C; }   // a workgroup a call
+    static size_t sparse_rows(const job& j) { return place::cmp_row(j.E, j.C, 0); }
+};
 
 }  // namespace
 
@@ -276,34 +261,9 @@ void zkm_sha_calls_check(zkm_sha_job& j) {
     j.nrows = place::cmp_row(j.E, j.C, 0), j.nmem = place::mem_base(j.E, j.C, true), j.nlogic = place::logic_base(j.E, j.C, true);
     j.next = place::EXT_ROUNDS * j.E;
 }
-size_t zkm_sha_calls_scratch(const zkm_sha_job* j, size_t nseg) { return layout(j, nseg, nullptr); }
+size_t zkm_sha_calls_scratch(const zkm_sha_job* j, size_t nseg) { return zkm_calls_layout<sha_kind>(j, nseg, nullptr); }
 void zkm_sha_calls_launch(zkm_ctx* c, const zkm_sha_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows) {
-    if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_sha_calls_launch: segment count out of range");
-    std::vector<std::array<size_t, 5>> at(nseg);
-    layout(j, nseg, at.data());
-    sha_calls_args* d = hold.make<sha_calls_args>(nseg);
-    size_t grid = 0;
-    for (size_t s = 0; s < nseg; s++) {
-        const auto in = lists(j[s]);
-        const void* dev[5];
-        for (int i = 0; i < 5; i++) {
-            dev[i] = in[i].p;
-            if (in[i].bytes && !zkm_is_device_ptr(in[i].p)) {
-                dev[i] = sb + at[s][i];
-                ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-        const size_t E = j[s].E, C = j[s].C;
-        if (zero_rows && E + C) ZKM_HIP_CHECK(hipMemsetAsync(j[s].rows, 0, place::cmp_row(E, C, 0) * CPU_W * sizeof(uint64_t), c->stream));
-        d[s] = sha_calls_args{(const uint32_t*)dev[0], (const uint64_t*)dev[1], (const uint32_t*)dev[2], (const uint32_t*)dev[3], (const uint64_t*)dev[4],
-                              E, C, j[s].rows, j[s].mem, j[s].ext_ts, j[s].logic, j[s].ext_in};
-        grid = std::max(grid, E + C);
-    }
-    if (!grid) return;
-    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(sha_calls_args), hipMemcpyHostToDevice, c->stream));
-    zkm_prof_scope ps(c, "sha_calls/rows_lists");
-    hipLaunchKernelGGL(k_sha_calls, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(THREADS), 0, c->stream, (const sha_calls_args*)sb);
-    ZKM_HIP_CHECK(hipGetLastError());
+    zkm_calls_queue<sha_kind>(c, j, nseg, sb, hold, zero_rows);
 }
 
 extern "C" {
@@ -327,13 +287,9 @@ int zkm_sha_calls_steps(const uint64_t* extend_meta, size_t nextend, const uint6
         if ((nextend && zkm_is_device_ptr(extend_meta)) || (ncompress && zkm_is_device_ptr(compress_meta))) refuse("the meta lists must be host memory");
         const size_t rows = place::cmp_row(nextend, ncompress, 0);
         if (rows && (!steps_out || !clocks_out)) refuse("null argument");
-        if (raw_base >= ((uint64_t)1 << 32) || raw_base + rows > ((uint64_t)1 << 32)) refuse("raw_base " + dec(raw_base) + ": a RAW index does not fit in 32 bits");
+        if (raw_base >= LIM || raw_base + rows > LIM) refuse("raw_base " + dec(raw_base) + ": a RAW index does not fit in 32 bits");
         auto put = [&](size_t j, uint32_t mask, uint64_t clock) {
-            zkm_cpu_step s{};
-            s.kind = ZKM_STEP_RAW;
-            s.reads[0] = (uint32_t)(raw_base + j);
-            s.reads[1] = mask;
-            steps_out[j] = s;
+            steps_out[j] = raw_step(raw_base + j, mask);
             clocks_out[j] = clock;
         };
         for (size_t e = 0; e < nextend; e++) {
@@ -357,39 +313,30 @@ int zkm_sha_calls_witness(zkm_ctx* c, const uint32_t* extend_w16, const uint64_t
     return zkm_api("zkm_sha_calls_witness", err, [&] {
         auto refuse = [](const std::string& m) { throw std::runtime_error("zkm_sha_calls_witness: " + m); };
         // every refusal first, on the host: the lists, the outputs, then the context
+        zkm_sha_job j;
+        j.w16 = extend_w16, j.emeta = extend_meta, j.E = nextend, j.hx = compress_hx, j.w = compress_w, j.cmeta = compress_meta, j.C = ncompress;
+        j.rows = raw_rows_out_dev, j.mem = memory_ops_out_dev, j.ext_ts = sha_extend_timestamps_out_dev, j.logic = logic_ops_out_dev;
+        j.ext_in = (uint32_t*)sha_extend_inputs_out_dev;
         try {
-            check_meta(extend_meta, nextend, compress_meta, ncompress);
+            zkm_sha_calls_check(j);
         } catch (const std::exception& e) {
             refuse(e.what());
         }
-        if (nextend && !extend_w16) refuse("extend_w16: NULL with a count of " + dec(nextend));
-        if (ncompress && !compress_hx) refuse("compress_hx: NULL with a count of " + dec(ncompress));
-        if (ncompress && !compress_w) refuse("compress_w: NULL with a count of " + dec(ncompress));
-        const size_t E = nextend, C = ncompress;
-        if (E + C == 0) {
+        if (j.E + j.C == 0) {
             if (!c) refuse("null argument");
             return;
         }
-        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(place::cmp_row(E, C, 0)) + " rows to write");
-        if (!memory_ops_out_dev) refuse("memory_ops_out_dev: NULL with " + dec(place::mem_base(E, C, true)) + " operations to write");
-        if (!logic_ops_out_dev) refuse("logic_ops_out_dev: NULL with " + dec(place::logic_base(E, C, true)) + " operations to write");
-        if (E && !sha_extend_inputs_out_dev) refuse("sha_extend_inputs_out_dev: NULL with " + dec(place::EXT_ROUNDS * E) + " rows to write");
-        if (E && !sha_extend_timestamps_out_dev) refuse("sha_extend_timestamps_out_dev: NULL with " + dec(place::EXT_ROUNDS * E) + " rows to write");
+        if (!raw_rows_out_dev) refuse("raw_rows_out_dev: NULL with " + dec(j.nrows) + " rows to write");
+        if (!memory_ops_out_dev) refuse("memory_ops_out_dev: NULL with " + dec(j.nmem) + " operations to write");
+        if (!logic_ops_out_dev) refuse("logic_ops_out_dev: NULL with " + dec(j.nlogic) + " operations to write");
+        if (j.E && !sha_extend_inputs_out_dev) refuse("sha_extend_inputs_out_dev: NULL with " + dec(j.next) + " rows to write");
+        if (j.E && !sha_extend_timestamps_out_dev) refuse("sha_extend_timestamps_out_dev: NULL with " + dec(j.next) + " rows to write");
         if (((uintptr_t)raw_rows_out_dev | (uintptr_t)memory_ops_out_dev | (uintptr_t)sha_extend_timestamps_out_dev) & 7 ||
             ((uintptr_t)logic_ops_out_dev | (uintptr_t)sha_extend_inputs_out_dev) & 3)
             refuse("an output is not aligned to its words (8 bytes; 4 for the logic operations and the ShaExtend inputs)");
         if (!c) refuse("null argument");
-        if (E + C > 0x7FFFFFFF) refuse("2^31 or more calls");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        // the K = 1 case of the segments' launch: the descriptor and the lists the host holds go up in one block
-        zkm_sha_job j;
-        j.w16 = extend_w16, j.emeta = extend_meta, j.E = E, j.hx = compress_hx, j.w = compress_w, j.cmeta = compress_meta, j.C = C;
-        j.rows = raw_rows_out_dev, j.mem = memory_ops_out_dev, j.ext_ts = sha_extend_timestamps_out_dev, j.logic = logic_ops_out_dev;
-        j.ext_in = (uint32_t*)sha_extend_inputs_out_dev;
-        zkm_calls_hold hold;   // (declared first: it outlives the block's wait for the stream when an exception unwinds)
-        zkm_scratch block(c, zkm_sha_calls_scratch(&j, 1));
-        zkm_sha_calls_launch(c, &j, 1, block.as<char>(), hold, true);
-        c->sync();   // (the block and the caller's lists are in use until here)
+        zkm_calls_one<sha_kind>(c, j);
     });
 }
 

@@ -578,22 +578,16 @@ void zkm_cpu_steps_launch(zkm_ctx* c, const zkm_steps_seg* segs, size_t nseg, bo
 
 // ---- the calls' expansions (sha_calls.hip, keccak_calls.hip, io_calls.hip, insn_rows.hip): K segments served by ONE launch a kind.
 // A job is one segment's calls of one kind: the caller's lists (host or device memory as the kind's entry point says), where the
-// outputs go (device) and what the host walk found.  The K descriptors travel in device memory, uploaded with the lists in the one
-// scratch block, as the bootstrap's do (d_desc): the kernel-argument block is one pointer.
-//   check    every refusal that concerns the lists (throws the bare message), the counts and the host walk's vectors
-//   scratch  the bytes a launch of these jobs puts up: the K descriptors and the lists the host holds
-//   launch   queues the uploads into `scratch` and ONE launch for nseg <= ZKM_MAX_SEG checked jobs (none when no job has a call).  The
-//            SHA and Keccak kernels store only the cells a row sets: zero_rows queues a memset of each job's rows in front (false: the
-//            caller has zeroed them).  The jobs, `hold` (the descriptors' host copy) and the caller's lists are in use until the
-//            stream has been waited for.
-// The per-kind entry points are the nseg = 1 case.
-struct zkm_calls_hold {
-    std::vector<std::unique_ptr<char[]>> blocks;
-    template <class T> T* make(size_t n) {
-        blocks.emplace_back(new char[n * sizeof(T) + 1]());
-        return (T*)blocks.back().get();
-    }
-};
+// outputs go (device) and what the host walk found.
+//   check    the ONE statement of the kind's refusals about its lists (throws the bare message; the kind's own entry point and
+//            calls_entry.hip both call it), the counts and the host walk's vectors
+//   scratch  the bytes a launch of these jobs puts up: the K descriptors and the lists the host holds (zkm_calls_layout)
+//   launch   queues the uploads into `scratch` and ONE launch for nseg <= ZKM_MAX_SEG checked jobs (zkm_calls_queue).  The SHA and
+//            Keccak kernels store only the cells a row sets: zero_rows queues a memset of each job's rows in front (false: the caller
+//            has zeroed them).
+// scratch and launch are the kinds' instantiations of the one launcher in calls_launch.h, where the block's layout and what is in use
+// until the stream has been waited for are stated.  The per-kind entry points are the nseg = 1 case (zkm_calls_one).
+struct zkm_calls_hold;   // the descriptors' host copy (calls_launch.h)
 struct zkm_sha_job {
     const uint32_t* w16 = nullptr; const uint64_t* emeta = nullptr; size_t E = 0;
     const uint32_t *hx = nullptr, *w = nullptr; const uint64_t* cmeta = nullptr; size_t C = 0;
