@@ -845,12 +845,14 @@ int zkm_boot_witness(zkm_ctx* ctx, const zkm_boot_image* image, uint64_t* cpu_ro
  *   PAD   the padding row of simulate_cpu (generation/mod.rs:170-185): clock, context, pc, next_pc and is_exit_kernel = 1
  *   RAW   reads[0] indexes a ready-made row in raw_rows (nraw x ZKM_CPU_COLS words row-major, any representative mod p, host or device
  *         memory); reads[1] has bit k set for each of the eight channels k whose `used` cell is 1 -- the counts and the operations
- *         follow this mask.  Rows in host memory are held to it on the walk (a mismatch is refused); for rows in device memory a
- *         mismatch is NOT detected: a used channel the mask leaves out pushes nothing.  The row is copied canonical and the masked
+ *         follow this mask.  Rows in host memory are held to it on the walk (a mismatch is refused), and so is every row, in host or
+ *         device memory, on the device walk (zkm_cpu_steps_scan, zkm_cpu_steps_stage, below); only the host walk of an unstaged
+ *         call leaves rows in device memory unread: there a mismatch is not detected, and a used channel the mask leaves out
+ *         pushes nothing.  The row is copied canonical and the masked
  *         channels become memory operations in ascending channel order, timestamped from the row's OWN clock cell (every other
  *         kind: first_clock + position); no logic or arithmetic operation.  The escape for everything the kinds do not cover: keccak_general and the precompile rows, a bootstrap row
  *         handed over by the caller, a register written outside an instruction.
- * `steps` is host memory (pageable or pinned); the library walks it once on the host, and every refusal -- an unknown kind, an encoding
+ * `steps` is host memory (pageable or pinned), or what zkm_staged_steps_get hands out; the library walks host memory once on the host, and every refusal -- an unknown kind, an encoding
  * the kind does not take, a RAW index >= nraw, a RAW mask that is not its host row's, a NULL pointer with a nonzero count -- is made
  * on that walk, before any device work, and names the step's index.  The counts of a step are a function of its record alone
  * (csrc/cpu_steps_dev.h, one __host__ __device__ function for the walk and the kernels).
@@ -867,7 +869,7 @@ int zkm_boot_witness(zkm_ctx* ctx, const zkm_boot_image* image, uint64_t* cpu_ro
  *                          into_tables on the joined lists; "check_ctls", "verify", waves, memory budget and sizing mode as in the
  *                          calls without steps, and so are the three host waits whatever K: the step path adds none.  Every table,
  *                          blob and challenge is word for word what the calls without steps give for the expanded rows and lists.
- * Steps are not staged (zkm_segment_ops_stage takes none), the pool takes none, kinds outside the list go RAW (the thirteen other
+ * Steps are staged by zkm_cpu_steps_stage (below; zkm_segment_ops_stage takes none), the pool takes none, kinds outside the list go RAW (the thirteen other
  * encodings decode() accepts as rows expanded on the device: zkm_insn_rows_* below), and there is no exit
  * kernel.  Profile scopes cpu_steps/lists and cpu_steps/rows (zkm_cpu_witness: cpu_steps/rows_lists). */
 #define ZKM_STEP_BINARY_OP 0
@@ -921,6 +923,50 @@ int zkm_segments_tables_steps(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t 
 int zkm_prove_segments_ops_steps(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images, const zkm_cpu_steps* steps,
                                  const zkm_segment_ops* ops, const uint64_t* const* public_values, const size_t* npublic,
                                  uint64_t* const* proofs_out, size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
+
+/* Staged steps: the NEXT call's step logs behind the CURRENT proofs, walked on the device.  The walk of an unstaged call runs on the
+ * calling thread before any device work; here it is two kernels behind the upload (csrc/cpu_steps_walk.hip): a thread per step takes
+ * the same counts from the same function, finds the step's first refusal in the host walk's order -- a RAW index >= nraw, an unknown
+ * kind, operands or an encoding the kind does not take, a RAW mask that is not the `used` cells of its row -- and a scan over the
+ * workgroups' sums gives the three list lengths and the base triples, word for word the host walk's.  The rows of RAW steps are in
+ * device memory by then whichever memory the caller had them in, so the mask check covers them all.  Of a refused segment the device
+ * keeps the lowest refused step, its record and the mask found, and the message is the host walk's, character for character.
+ *   zkm_cpu_steps_scan     the walk alone (tests and tools), for nseg segments in one set of launches: steps[s].steps and raw_rows may be
+ *                          host or device memory; counts_out takes 3 words a segment (memory, logic, arithmetic); base_out, which may be
+ *                          NULL and whose entries may be NULL, takes segment s's 3 words per 256 steps into HOST memory.  One host
+ *                          wait.  A refusal reads "zkm_cpu_steps_scan: segment <s>: step <i>: ...", of the lowest such segment.
+ *   zkm_cpu_steps_stage    reads nothing of the lists on the host: one block of the context's allocator for all segments, and, on the
+ *                          context's two copy streams behind what the compute stream has queued, the records, the RAW rows that lie in
+ *                          host memory, the walk's kernels behind them and the download of the verdicts into pinned memory of the
+ *                          handle.  RETURNS AT ONCE, with no host wait.  RAW rows in device memory are referenced, not copied: they
+ *                          must live until the handle is freed.  The caller's host lists must stay as they are until
+ *                          zkm_staged_steps_ready returns 1.  *out is the handle, which the functions below take (an address to the
+ *                          bindings, as every handle is).
+ *   zkm_staged_steps_ready 1: uploads, walk and download have ended -- the caller's lists may be reused; 0: in flight; -1: a runtime
+ *                          error.  wait != 0 blocks until they have.
+ *   zkm_staged_steps_get   waits on the host for the handle's events (long fired when the stage ran behind the previous call; one host
+ *                          wait a handle at most), then, for a segment that passed: steps_out with `steps` and `raw_rows` in device
+ *                          memory, and the three list lengths (each pointer may be NULL); the compute stream is ordered behind the
+ *                          events with a device-side wait, once per handle.  For a refused segment it fails with
+ *                          "zkm_staged_steps_get: segment <s>: step <i>: ..."; the other segments of the handle stay usable.
+ *   zkm_staged_steps_free  waits for the events, then releases the block (NULL is allowed); after the calls that consumed the handle
+ *                          have returned.
+ * zkm_segments_tables_steps and zkm_prove_segments_ops_steps ON THE SAME CONTEXT take steps_out as steps[s]: for such a segment the
+ * builder does not walk, uploads neither records nor bases and orders its compute stream behind the handle's events itself, and
+ * everything else is as for an unstaged segment -- the three host waits, waves, "check_ctls", "check_witness", "verify", and every
+ * table, blob and challenge word for word.  Staged and unstaged segments, images and the lists of zkm_staged_ops_get mix in one call.
+ * steps_out is taken as it was handed out (a changed count or raw_rows is refused), a handle of another context is refused, and so is
+ * a `steps` pointer in device memory that no handle owns.  Refused on the host before any device work, here and in zkm_cpu_steps_scan:
+ * NULL with a nonzero count, nseg = 0, nsteps above 2^28 (the builder's own limit: 8 memory operations a step stay below 2^32), a
+ * NULL argument.  A refusal leaves the context usable, its live memory as it was and no handle behind.
+ * The pool still takes no steps; images and calls (zkm_segments_calls_expand) are still not staged.  Profile scope cpu_steps/walk
+ * (zkm_cpu_steps_scan only: the staged walk runs on a copy stream). */
+int zkm_cpu_steps_scan(zkm_ctx* ctx, size_t nseg, const zkm_cpu_steps* steps, size_t* counts_out, uint32_t* const* base_out, char** err);
+int zkm_cpu_steps_stage(zkm_ctx* ctx, size_t nseg, const zkm_cpu_steps* steps, void** out, char** err);
+int zkm_staged_steps_ready(void* staged, int wait);
+int zkm_staged_steps_get(void* staged, size_t segment, zkm_cpu_steps* steps_out, size_t* memory_ops, size_t* logic_ops, size_t* arithmetic_ops,
+                         char** err);
+void zkm_staged_steps_free(void* staged);
 
 /* ------------------------------------------------------------------ SHA-256 precompile calls from their inputs
  * What generate_sha_extend and generate_sha_compress (witness/operation.rs:1183-1285, :1298-1458) and their helpers sha_extend_sponge_log

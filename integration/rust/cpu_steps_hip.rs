@@ -13,7 +13,8 @@
 //!     the precompiles of operation.rs:1101-1458, get / set context -- it fills the row as today and calls `step_log.push_raw(&row)`;
 //!   * the padding loop of `simulate_cpu` (generation/mod.rs:170-185) calls `step_log.pad(..)` instead of pushing rows.
 //! What the steps cover leaves `Traces::cpu`, and the memory / logic / arithmetic operations of those rows leave `Traces` too: the
-//! library puts them in front of the lists that remain (the precompiles' own operations).  Steps are not staged and the pool takes none.
+//! library puts them in front of the lists that remain (the precompiles' own operations).  `StagedSteps` stages the next call's steps
+//! behind the current proofs (the walk runs on the device); the pool takes none.
 //!
 //! Goes into the zkm-prover crate as `prover/src/cpu_steps_hip.rs`, beside `segment_hip.rs`.  The reference items used here are checked
 //! by tests/test_rust_cpu_steps_names.py.  NOT COMPILED in the build image (no cargo / rustc there).
@@ -174,4 +175,61 @@ pub fn segments_tables_steps_raw(ctx: *mut zkm_ctx, images: &[zkm_boot_image], s
     };
     check(rc, err)?;
     Ok((handles, log_n))
+}
+
+/// K segments' step logs on their way into HBM behind the context's current work, walked on the device behind the upload
+/// (zkm_cpu_steps_stage).  `stage` returns at once with no host wait; the lists it was given must stay as they are until `ready`
+/// answers true.  `get` is what the `*_steps` calls of the SAME context take for a segment; drop the handle after those calls.
+pub struct StagedSteps {
+    handle: *mut std::ffi::c_void,
+    nseg: usize,
+}
+
+impl StagedSteps {
+    pub fn stage(ctx: *mut zkm_ctx, steps: &[zkm_cpu_steps]) -> Result<Self> {
+        let (mut handle, mut err) = (std::ptr::null_mut(), std::ptr::null_mut());
+        let rc = unsafe { zkm_cpu_steps_stage(ctx, steps.len(), steps.as_ptr(), &mut handle, &mut err) };
+        check(rc, err)?;
+        Ok(StagedSteps { handle, nseg: steps.len() })
+    }
+
+    /// True once the uploads, the walk and the download of its verdicts have ended; `wait` blocks until they have.
+    pub fn ready(&self, wait: bool) -> Result<bool> {
+        let r = unsafe { zkm_staged_steps_ready(self.handle, wait as std::ffi::c_int) };
+        ensure!(r >= 0, "zkm_staged_steps_ready: runtime error");
+        Ok(r == 1)
+    }
+
+    /// Segment `segment` with device pointers and the lengths of the Memory, Logic and Arithmetic lists its steps push; a segment the
+    /// walk refused fails with the host walk's message.  One host wait a handle at most.
+    pub fn get(&self, segment: usize) -> Result<(zkm_cpu_steps, (usize, usize, usize))> {
+        let (mut m, mut l, mut a, mut err) = (0usize, 0usize, 0usize, std::ptr::null_mut());
+        let mut steps = zkm_cpu_steps { steps: std::ptr::null(), nsteps: 0, raw_rows: std::ptr::null(), nraw: 0 };
+        let rc = unsafe { zkm_staged_steps_get(self.handle, segment, &mut steps, &mut m, &mut l, &mut a, &mut err) };
+        check(rc, err)?;
+        Ok((steps, (m, l, a)))
+    }
+
+    /// Every segment of the handle, for the `*_steps` calls.
+    pub fn lists(&self) -> Result<Vec<zkm_cpu_steps>> {
+        (0..self.nseg).map(|s| self.get(s).map(|(steps, _)| steps)).collect()
+    }
+}
+
+impl Drop for StagedSteps {
+    fn drop(&mut self) {
+        unsafe { zkm_staged_steps_free(self.handle) }
+    }
+}
+
+/// `prove_segments_ops_steps_raw` on steps staged ahead of the call: no walk on the calling thread, no upload of records or bases.
+pub fn prove_segments_ops_steps_staged(ctx: *mut zkm_ctx, images: &[zkm_boot_image], staged: &StagedSteps, segments: &[zkm_segment_ops],
+                                       config: &zkm_stark_config, public_values: &[&[u64]]) -> Result<SegmentProofs> {
+    prove_segments_ops_steps_raw(ctx, images, &staged.lists()?, segments, config, public_values)
+}
+
+/// `segments_tables_steps_raw` on steps staged ahead of the call.
+pub fn segments_tables_steps_staged(ctx: *mut zkm_ctx, images: &[zkm_boot_image], staged: &StagedSteps, segments: &[zkm_segment_ops],
+                                    config: &zkm_stark_config) -> Result<(Vec<*mut zkm_staged>, Vec<u32>)> {
+    segments_tables_steps_raw(ctx, images, &staged.lists()?, segments, config)
 }

@@ -358,6 +358,14 @@ extern "C" {
                                         steps: *const zkm_cpu_steps, ops: *const zkm_segment_ops, public_values: *const *const u64,
                                         npublic: *const usize, proofs_out: *const *mut u64, proof_offsets_out: *mut usize,
                                         ctl_challenges_out: *const *mut u64, err: *mut *mut c_char) -> c_int;
+    // steps staged ahead of a call and walked on the device (the handle is an address, as the header passes it)
+    pub fn zkm_cpu_steps_scan(ctx: *mut zkm_ctx, nseg: usize, steps: *const zkm_cpu_steps, counts_out: *mut usize, base_out: *const *mut u32,
+                              err: *mut *mut c_char) -> c_int;
+    pub fn zkm_cpu_steps_stage(ctx: *mut zkm_ctx, nseg: usize, steps: *const zkm_cpu_steps, out: *mut *mut c_void, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_staged_steps_ready(staged: *mut c_void, wait: c_int) -> c_int;
+    pub fn zkm_staged_steps_get(staged: *mut c_void, segment: usize, steps_out: *mut zkm_cpu_steps, memory_ops: *mut usize, logic_ops: *mut usize,
+                                arithmetic_ops: *mut usize, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_staged_steps_free(staged: *mut c_void);
     // SHA-256 precompile calls expanded on the device from the sponge tables' lists: counts, the RAW records with their clocks, the kernel
     pub fn zkm_sha_calls_counts(nextend: usize, ncompress: usize, cpu_rows: *mut usize, memory_ops: *mut usize, logic_ops: *mut usize,
                                 sha_extend_rows: *mut usize);

@@ -781,6 +781,69 @@ class StagedOps:
                 self.ctx.L.zkm_staged_ops_free(h)
 
 
+class _StagedStepsSegment:
+    """A segment's staged step log as StagedSteps.get hands it out: device pointers the handle owns, and the three list lengths."""
+
+    def __init__(self, st, counts, owner):
+        self._st, self._owner, self.counts_, self.nsteps, self.nraw = st, owner, counts, st.nsteps, st.nraw
+
+    def struct(self):
+        return self._st
+
+    def counts(self):
+        return self.counts_
+
+
+class StagedSteps:
+    """The handle of zkm_cpu_steps_stage: K segments' step logs on their way into HBM behind the context's current work, walked on the
+    device behind the upload (include/zkm_hip.h "Staged steps").  get(s) is what segments_tables_steps / prove_segments_ops_steps of
+    the SAME context take for segment s; free() after those calls have returned.  The CpuSteps it was staged from are kept alive by
+    the handle, and their arrays must stay as they are until ready() is true.  Freed when dropped, at the end of a `with` block or by
+    Context.close()."""
+
+    def __init__(self, ctx, handle, steps_list):
+        self.ctx, self.h, self.steps_list = ctx, handle, list(steps_list)
+        ctx._staged.add(self)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return len(self.steps_list)
+
+    def get(self, s):
+        """zkm_staged_steps_get: segment s with device pointers (waits on the host for the walk the first time, one wait a handle at
+        most); a segment the walk refused raises ZkmError with the host walk's message."""
+        if not self.h:
+            raise ZkmError("zkm_staged_steps_get: freed handle")
+        st, n, err = CpuStepsStruct(), [C.c_size_t() for _ in range(3)], C.c_char_p()
+        _check(self.ctx.L.zkm_staged_steps_get(self.h, s, C.byref(st), *[C.byref(x) for x in n], C.byref(err)), err)
+        return _StagedStepsSegment(st, tuple(int(x.value) for x in n), self)
+
+    def ready(self, wait=False):
+        r = self.ctx.L.zkm_staged_steps_ready(self.h, 1 if wait else 0)
+        if r < 0:
+            raise ZkmError("zkm_staged_steps_ready: runtime error")
+        return bool(r)
+
+    def free(self):
+        """Waits for the uploads and the walk and returns the block."""
+        if self.h:
+            h, self.h = self.h, None
+            self.ctx._staged.discard(self)
+            if self.ctx.h:
+                self.ctx.L.zkm_staged_steps_free(h)
+
+
 class _ExpandedSteps:
     """A segment's patched step list as ExpandedCalls hands it out: .steps a numpy copy, raw_rows on the device (the handle's)."""
 
@@ -1544,6 +1607,31 @@ class Context:
     def cpu_steps_counts(self, steps):
         """zkm_cpu_steps_counts (module-level cpu_steps_counts: no GPU is involved)."""
         return cpu_steps_counts(steps)
+
+    def cpu_steps_scan(self, steps_list, bases=False):
+        """zkm_cpu_steps_scan: the walk over K step logs on the device, alone.  Returns [(memory_ops, logic_ops, arithmetic_ops)] per
+        segment; bases=True: ([counts], [the base triples of segment s, an (n, 3) uint32 array with one row per 256 steps]); bases may
+        also be the arrays to fill, one per segment (C-contiguous uint32 of at least that size, or None to skip a segment).  A refusal
+        raises ZkmError with the host walk's message behind "zkm_cpu_steps_scan: segment <s>: "."""
+        K = len(steps_list)
+        sl = (CpuStepsStruct * max(K, 1))(*[x.struct() for x in steps_list])
+        counts, err = (C.c_size_t * (3 * max(K, 1)))(), C.c_char_p()
+        base = [np.zeros(((sl[s].nsteps + 255) // 256, 3), dtype=np.uint32) for s in range(K)] if bases is True else list(bases or [])
+        assert not base or (len(base) == K and all(b is None or (b.dtype == np.uint32 and b.flags["C_CONTIGUOUS"] and
+                                                                 b.size >= 3 * ((sl[s].nsteps + 255) // 256)) for s, b in enumerate(base)))
+        ptrs = (C.c_void_p * max(K, 1))(*[None if b is None else b.ctypes.data for b in base]) if base else None
+        _check(self.L.zkm_cpu_steps_scan(self.h, K, sl, counts, ptrs, C.byref(err)), err)
+        out = [tuple(int(x) for x in counts[3 * s:3 * s + 3]) for s in range(K)]
+        return (out, base) if bases else out
+
+    def cpu_steps_stage(self, steps_list):
+        """zkm_cpu_steps_stage: queue the upload and the device walk of K step logs behind the context's current work and return a
+        StagedSteps at once (no host wait)."""
+        K = len(steps_list)
+        sl = (CpuStepsStruct * max(K, 1))(*[x.struct() for x in steps_list])
+        h, err = C.c_void_p(), C.c_char_p()
+        _check(self.L.zkm_cpu_steps_stage(self.h, K, sl, C.byref(h), C.byref(err)), err)
+        return StagedSteps(self, h, steps_list)
 
     def segments_tables_steps(self, steps_list, ops_list, images=None, cfg=None, sizing=False):
         """zkm_segments_tables_steps: segments_tables[_boot] with each segment's CPU rows built from its CpuSteps; the SegmentOps carry no

@@ -1,9 +1,11 @@
 // cpu_steps.hip -- a segment's CPU rows, and the memory, logic and arithmetic operations they push, built on the device from the compact
 // step log (include/zkm_hip.h zkm_cpu_step; what a step produces: cpu_steps_dev.h).
 //
-// The host walks the steps once (zkm_cpu_steps_walk): every refusal is made there, and since a step's counts are a function of its
-// record, the walk also knows the three list lengths and where each workgroup of ZKM_CPU_STEPS_BLOCK steps starts in the lists -- one
-// base triple per workgroup goes up with the steps, and the kernel scans inside the workgroup.  No host wait.
+// The steps are walked once before k_cpu_steps runs: every refusal is made on that walk, and since a step's counts are a function of
+// its record, the walk also knows the three list lengths and where each workgroup of ZKM_CPU_STEPS_BLOCK steps starts in the lists --
+// one base triple per workgroup, and the kernel scans inside the workgroup.  An unstaged call walks on the host (zkm_cpu_steps_walk:
+// the bases go up with the steps, no host wait); steps staged ahead of the call are walked on the device (cpu_steps_walk.hip), word
+// for word the same bases.
 //
 // k_cpu_steps: one thread per step, the segment is blockIdx.z.  The record comes in as three 16-byte loads; adjacent lanes are adjacent
 // rows, so a column's stores are coalesced with no LDS staging.  The row is never held: the table is zeroed by one memset before the
@@ -136,41 +138,49 @@ size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
+// The message of a step's refusal, without the entry point's prefix: the one statement of these texts, for the host walk below and for
+// the verdict records of the device walk (cpu_steps_walk.hip).  `used`: the channels a RAW step's row uses (BAD_MASK only).
+std::string zkm_cpu_step_refusal(size_t i, const zkm_cpu_step& t, size_t nraw, int code, uint32_t used) {
+    const std::string at = "step " + std::to_string(i) + ": ";
+    if (t.kind > ZKM_STEP_RAW) code = BAD_KIND;   // (no name to print: what count() says of such a record anyway)
+    switch (code) {
+    case BAD_INDEX: return at + "RAW index " + std::to_string(t.reads[0]) + ", raw_rows holds " + std::to_string(nraw);
+    case BAD_KIND: return at + "unknown kind " + std::to_string(t.kind);
+    case BAD_OPERANDS: return at + KIND_NAMES[t.kind] + " does not take these operands (TEQ of equal values traps)";
+    case BAD_MASK:
+        return at + "RAW row " + std::to_string(t.reads[0]) + " uses the channels " + hex8(used) + ", the step's mask is " + hex8(t.reads[1]);
+    default:
+        return at + KIND_NAMES[t.kind] + " does not take the encoding " + hex8(t.insn) +
+               (t.kind == ZKM_STEP_SYSCALL ? " with flags " + hex8(t.flags)
+                : t.kind == ZKM_STEP_RAW   ? " with the channel mask " + hex8(t.reads[1])
+                                           : std::string());
+    }
+}
+
 void zkm_cpu_steps_walk(const zkm_cpu_steps* st, zkm_steps_counts_t* n, std::vector<uint32_t>* base) {
     if (!st) throw std::runtime_error("null argument");
     if ((st->nsteps && !st->steps) || (st->nraw && !st->raw_rows)) throw std::runtime_error("null pointer with a nonzero count");
+    // (the records are read here, on the host: the device pointers a staged handle hands out go to the builder, which does not walk them)
+    if (st->nsteps && zkm_is_device_ptr(st->steps)) throw std::runtime_error("steps in device memory: this walk reads them on the host");
     *n = zkm_steps_counts_t{};
     // ready-made rows the host can read are held to their records: a RAW step's mask must name exactly the row's used channels
     const bool raw_host = st->nraw && !zkm_is_device_ptr(st->raw_rows);
     if (base) base->assign(3 * ((st->nsteps + BLOCK - 1) / BLOCK), 0);
     for (size_t i = 0; i < st->nsteps; i++) {
         const zkm_cpu_step& t = st->steps[i];
-        const std::string at = "step " + std::to_string(i) + ": ";
-        if (n->mem >= ((uint64_t)1 << 32) - 16) throw std::runtime_error(at + "2^32 or more memory operations");
+        if (n->mem >= ((uint64_t)1 << 32) - 16) throw std::runtime_error("step " + std::to_string(i) + ": 2^32 or more memory operations");
         if (base && i % BLOCK == 0) {
             uint32_t* b = base->data() + 3 * (i / BLOCK);
             b[0] = (uint32_t)n->mem; b[1] = (uint32_t)n->logic; b[2] = (uint32_t)n->arith;
         }
-        if (t.kind == ZKM_STEP_RAW && t.reads[0] >= st->nraw)
-            throw std::runtime_error(at + "RAW index " + std::to_string(t.reads[0]) + ", raw_rows holds " + std::to_string(st->nraw));
+        if (t.kind == ZKM_STEP_RAW && t.reads[0] >= st->nraw) throw std::runtime_error(zkm_cpu_step_refusal(i, t, st->nraw, BAD_INDEX, 0));
         counts k;
-        switch (count(t, k)) {
-        case OK: break;
-        case BAD_KIND: throw std::runtime_error(at + "unknown kind " + std::to_string(t.kind));
-        case BAD_OPERANDS: throw std::runtime_error(at + KIND_NAMES[t.kind] + " does not take these operands (TEQ of equal values traps)");
-        default:
-            throw std::runtime_error(at + KIND_NAMES[t.kind] + " does not take the encoding " + hex8(t.insn) +
-                                     (t.kind == ZKM_STEP_SYSCALL ? " with flags " + hex8(t.flags)
-                                      : t.kind == ZKM_STEP_RAW   ? " with the channel mask " + hex8(t.reads[1])
-                                                                 : std::string()));
-        }
+        if (const int code = count(t, k); code != OK) throw std::runtime_error(zkm_cpu_step_refusal(i, t, st->nraw, code, 0));
         if (t.kind == ZKM_STEP_RAW && raw_host) {
             const uint64_t* ch = st->raw_rows + (size_t)t.reads[0] * CPU_W + C_CH0;
             uint32_t used = 0;
             for (unsigned c = 0; c < NUM_GP_CHANNELS; c++) used |= (uint32_t)(gl_canon(ch[6 * c]) != 0) << c;
-            if (used != t.reads[1])
-                throw std::runtime_error(at + "RAW row " + std::to_string(t.reads[0]) + " uses the channels " + hex8(used) + ", the step's mask is " +
-                                         hex8(t.reads[1]));
+            if (used != t.reads[1]) throw std::runtime_error(zkm_cpu_step_refusal(i, t, st->nraw, BAD_MASK, used));
         }
         n->mem += k.nmem;
         n->logic += k.nlogic;

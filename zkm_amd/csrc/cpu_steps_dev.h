@@ -54,8 +54,8 @@ __device__ __forceinline__ uint64_t read_word(unsigned f, uint64_t ctx, uint64_t
 }
 #endif
 
-// what a walk returns
-enum : int { OK = 0, BAD_KIND = 1, BAD_ENCODING = 2, BAD_OPERANDS = 3 };
+// what a walk returns, and the two refusals of a RAW step that need more than its record: its index against nraw, its mask against its row
+enum : int { OK = 0, BAD_KIND = 1, BAD_ENCODING = 2, BAD_OPERANDS = 3, BAD_INDEX = 4, BAD_MASK = 5 };
 
 template <class S> GL_HD void reg_read(S& s, unsigned i, uint32_t reg, uint32_t v) { s.chan(i, 1, 1, 0, SEG_REG, reg, v); }
 // a write to register 0 fills the channel with used = 0 and pushes nothing (witness/util.rs:198-204)

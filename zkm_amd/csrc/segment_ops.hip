@@ -207,6 +207,7 @@ struct builder {
     zkm_steps_counts_t sn{};      // ... and what it adds to the Memory, Logic and Arithmetic lists, behind the bootstrap's part
     std::vector<uint32_t> step_base;   // ... where each workgroup of steps starts in them (cpu_steps.hip)
     const void *d_steps = nullptr, *d_step_base = nullptr, *d_raw = nullptr;   // device copies of the steps, the bases and the RAW rows
+    zkm_staged_steps_ref staged;  // steps a zkm_cpu_steps_stage handle owns (staged.ctx != null): walked on the device, nothing of them goes up
     zkm_segment_ops d{};          // ... and where the device reads them: the caller's device pointers, or places in the staging block
     unsigned lg[NTAB] = {};
     std::vector<uint64_t> ps_row, ks_row;   // first row of each sponge operation
@@ -278,10 +279,21 @@ struct builder {
         }
         if (st) {
             if (o.cpu_rows || o.ncpu_rows) refuse(CPU, "cpu_rows must be NULL with ncpu_rows 0: the steps take their place");
-            try {
-                zkm_cpu_steps_walk(st, &sn, &step_base);
-            } catch (const std::exception& e) {
-                refuse(CPU, e.what());
+            if (st->nsteps && zkm_staged_steps_find(st->steps, &staged)) {
+                // staged steps: the device has walked them; the handle knows the counts, the bases and the verdict
+                if (staged.ctx != c) refuse(CPU, "the steps were staged on another context");
+                if (st->nsteps != staged.dev.nsteps || st->raw_rows != staged.dev.raw_rows || st->nraw != staged.dev.nraw)
+                    refuse(CPU, "staged steps are taken as zkm_staged_steps_get hands them out");
+                if (!staged.refusal.empty()) refuse(CPU, staged.refusal);
+                sn = staged.n;
+            } else {
+                staged = zkm_staged_steps_ref{};
+                if (st->nsteps && st->steps && zkm_is_device_ptr(st->steps)) refuse(CPU, "steps in device memory that no staged handle owns");
+                try {
+                    zkm_cpu_steps_walk(st, &sn, &step_base);
+                } catch (const std::exception& e) {
+                    refuse(CPU, e.what());
+                }
             }
         }
         const size_t rows = ncpu_rows();
@@ -338,7 +350,11 @@ struct builder {
             if (skip || !zkm_is_device_ptr(l.get())) add(l, l.get(), skip);
         }
         // the steps, their workgroups' bases and the RAW rows that lie in host memory: read by the launch that sizes Memory and Arithmetic
-        if (st) {
+        if (st && staged.ctx) {
+            d_steps = st->steps;
+            d_step_base = staged.base;
+            d_raw = st->raw_rows;
+        } else if (st) {
             add(list_ref{&d_steps, st->nsteps * sizeof(zkm_cpu_step), true}, st->steps);
             add(list_ref{&d_step_base, step_base.size() * 4, true}, step_base.data());
             d_raw = st->raw_rows;
@@ -414,6 +430,11 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     char* sb = stage.as<char>();
     uint64_t* d_sync = (uint64_t*)sb;
     std::vector<uint64_t> sync(K * SYNC_WORDS);
+    // staged steps: the compute stream goes behind their uploads and their walk before anything of this wave is queued (every other stream
+    // of the call starts behind the compute stream; zkm_staged_steps_get has queued the same waits, as a rule)
+    for (size_t s = 0; s < K; s++)
+        for (const hipEvent_t e : b[s].staged.done)
+            if (b[s].staged.ctx) ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, e, 0));
     copy_join join;
     bool any_host_rows = false;
     for (size_t s = 0; s < K; s++) any_host_rows = any_host_rows || b[s].cpu_host;

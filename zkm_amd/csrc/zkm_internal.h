@@ -575,6 +575,22 @@ struct zkm_steps_seg {
 };
 // nseg <= ZKM_MAX_SEG segments of one context, ONE launch: the rows (over a zeroed table), the lists, or both
 void zkm_cpu_steps_launch(zkm_ctx* c, const zkm_steps_seg* segs, size_t nseg, bool rows, bool lists);
+// the text of a step's refusal ("step <i>: ..."): `code` is zkm_step's (cpu_steps_dev.h), `used` the channels a RAW row uses (BAD_MASK)
+std::string zkm_cpu_step_refusal(size_t i, const zkm_cpu_step& t, size_t nraw, int code, uint32_t used);
+
+// ---- cpu_steps_walk.hip: the same walk on the device, for steps staged ahead of a call (zkm_cpu_steps_stage).  What the builder
+// (segment_ops.hip) needs of a segment whose `steps` pointer a staged handle owns: the handle's context, what the segment was staged
+// with, the walk's counts and base triples, its refusal ("" when it passed) and the events every reader of the block is ordered behind.
+// zkm_staged_steps_find waits on the host for the handle's events the first time anyone asks (zkm_staged_steps_get has, as a rule).
+struct zkm_staged_steps_ref {
+    zkm_ctx* ctx = nullptr;
+    zkm_cpu_steps dev{};           // steps and raw_rows in device memory, as zkm_staged_steps_get hands them out
+    zkm_steps_counts_t n;
+    const uint32_t* base = nullptr;   // device
+    std::string refusal;
+    hipEvent_t done[2] = {nullptr, nullptr};
+};
+bool zkm_staged_steps_find(const void* d_steps, zkm_staged_steps_ref* out);
 
 // ---- the calls' expansions (sha_calls.hip, keccak_calls.hip, io_calls.hip, insn_rows.hip): K segments served by ONE launch a kind.
 // A job is one segment's calls of one kind: the caller's lists (host or device memory as the kind's entry point says), where the
