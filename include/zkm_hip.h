@@ -959,7 +959,8 @@ int zkm_prove_segments_ops_steps(zkm_ctx* ctx, const zkm_stark_config* cfg, size
  * a `steps` pointer in device memory that no handle owns.  Refused on the host before any device work, here and in zkm_cpu_steps_scan:
  * NULL with a nonzero count, nseg = 0, nsteps above 2^28 (the builder's own limit: 8 memory operations a step stay below 2^32), a
  * NULL argument.  A refusal leaves the context usable, its live memory as it was and no handle behind.
- * The pool still takes no steps; images and calls (zkm_segments_calls_expand) are still not staged.  Profile scope cpu_steps/walk
+ * The pool still takes no steps; images and calls (zkm_segments_calls_expand) are still not staged by THESE entry points:
+ * zkm_segments_calls_stage ("Staged calls", below) stages both, on top of this walk.  Profile scope cpu_steps/walk
  * (zkm_cpu_steps_scan only: the staged walk runs on a copy stream). */
 int zkm_cpu_steps_scan(zkm_ctx* ctx, size_t nseg, const zkm_cpu_steps* steps, size_t* counts_out, uint32_t* const* base_out, char** err);
 int zkm_cpu_steps_stage(zkm_ctx* ctx, size_t nseg, const zkm_cpu_steps* steps, void** out, char** err);
@@ -1237,8 +1238,9 @@ int zkm_insn_rows_witness(zkm_ctx* ctx, const zkm_cpu_step* insns, const uint64_
  * unknown I/O kind, an instruction record outside the thirteen, ...); a meta, offset, kind, record or clock list in device memory; a
  * call row whose clock lies outside the step list; two records on one clock; a group of `own` that the calls own; own.cpu_rows; raw_rows
  * in device memory; nseg = 0 or NULL calls.  A refusal leaves the context usable, its live memory as it was, and no handle behind.
- * Out of scope: nothing is fused into the builder (its kernels and its three host waits are untouched), calls and steps are not staged,
- * the pool takes none, and the records are placed into the step list on the host (the builder walks it there).
+ * Out of scope: nothing is fused into the builder (its kernels and its three host waits are untouched), the pool takes none, and THESE
+ * entry points place the records into the step list on the host (the builder walks it there): zkm_segments_calls_stage, below, does
+ * both on the device, ahead of the call.
  * (The struct and the handle are tagged, not typedef'd: to the header-driven bindings a pointer to either is a plain address.) */
 #define ZKM_CALLS_COUNTS 11
 struct zkm_segment_calls {
@@ -1262,6 +1264,52 @@ int zkm_segments_tables_calls(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t 
 int zkm_prove_segments_ops_calls(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
                                  const struct zkm_segment_calls* calls, const uint64_t* const* public_values, const size_t* npublic,
                                  uint64_t* const* proofs_out, size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
+
+/* Staged calls: the NEXT call's zkm_segment_calls behind the CURRENT proofs -- the form the emulator records, staged as steps, tables
+ * and operations are.  zkm_segments_calls_expand builds one record and one clock per generated ROW on the calling thread, checks and
+ * patches the step list there, and waits on the host once per 32 segments; the builder then walks the patched list on the host again.
+ * zkm_segments_calls_stage reads the lists on the host per CALL only -- the counts, and every refusal of zkm_segments_calls_expand that
+ * needs no row's clock, word for word under this function's name, before any device work and leaving no handle -- and queues the rest
+ * on the context's two copy streams, behind what the compute stream has queued (as zkm_cpu_steps_stage orders them): the segment's own
+ * step records, ready-made rows and lists, every payload and meta list of the calls, the images' addrs / values where they lie in host
+ * memory, the four expansion launches, a placement kernel (a thread per generated row: the row's record -- the same statement
+ * zkm_*_calls_steps write on the host -- stored at clock - first_clock of the device's step list), the walk of zkm_cpu_steps_stage
+ * over the patched list, whose mask check therefore covers the generated rows too, and the download of both sets of verdicts into
+ * pinned memory of the handle.  It RETURNS AT ONCE, with no host wait; more than 32 segments queue consecutive sets of launches in the
+ * same call.  images may be NULL (no segment stands behind a bootstrap); otherwise nseg images, as the builder's `images`.
+ * The two refusals that need a row's clock are found by the placement kernel: a row whose clock lies outside the step list (it touches
+ * nothing), and two records on one clock; the row named is the one zkm_segments_calls_expand names.
+ *   zkm_staged_calls_ready   1: uploads, expansions, placement, walk and downloads have ended -- every list of the caller may be reused;
+ *                            0: in flight (wait = 0 only); -1: a runtime error.  NULL: 1.
+ *   zkm_staged_calls_get     waits on the host for the handle's events the first time it is called (at most one host wait a handle),
+ *                            and orders the compute stream behind them once.  steps_out: the patched list and all ready-made rows --
+ *                            own, SHA, Keccak, I/O, instructions -- in device memory, staged steps to the builder (counts and bases
+ *                            from the handle, nothing uploaded; pass it as it is handed out).  ops_out: as zkm_expanded_calls_get's,
+ *                            with every list the builder accepts in device memory pointing into the handle's blocks -- the joined
+ *                            lists, and the calls' groups (sha_extend_sponge_*, sha_compress_*, sha_compress_sponge_*,
+ *                            keccak_sponge_inputs / _meta) at the copies the expansions read; keccak_sponge_off, which the builder
+ *                            reads on the host, points at the handle's own copy.  A payload list the caller had in device memory is
+ *                            referenced, not copied, and stays the caller's until the handle is freed, as do own.poseidon_* and
+ *                            own.poseidon_sponge_* (passed on untouched; poseidon_sponge_off is read on the host), and
+ *                            own.arithmetic_ops of a segment without instruction records.  image_out (may be NULL): the segment's
+ *                            image with addrs / values in device memory (zeroed when the stage had no images).
+ *                            A refused segment fails with "zkm_staged_calls_get: segment <s>: " and the placement's refusal in
+ *                            zkm_segments_calls_expand's words ("instruction record row 7 (clock 96): two records on one clock"), else
+ *                            the walk's in the host walk's ("step <i>: ..."); the other segments of the handle stay usable.
+ *   zkm_staged_calls_free    waits for the events, then releases everything (NULL is allowed); after the calls that consumed the
+ *                            handle have returned.
+ * zkm_segments_tables_steps / zkm_prove_segments_ops_steps, with `images`, take these outputs ON THE SAME CONTEXT and keep their three
+ * host waits; tables, blobs and challenges are word for word those of zkm_segments_tables_calls / zkm_prove_segments_ops_calls on the
+ * same input.  They refuse the outputs of a handle of another context, and steps whose nsteps, raw_rows or nraw were changed on the way.
+ * Refused by the stage, beside the lists' refusals: NULL `out`, NULL calls or nseg = 0, a segment of more than 2^28 steps, an image
+ * whose addrs or values is NULL with a nonzero nwords, a NULL context (last).  A refusal leaves the context usable and its live memory as it was.  The pool takes none.
+ * (The handle is passed as an address, as zkm_cpu_steps_stage's is.) */
+int zkm_segments_calls_stage(zkm_ctx* ctx, size_t nseg, const struct zkm_segment_calls* calls, const zkm_boot_image* images, void** out,
+                             char** err);
+int zkm_staged_calls_ready(void* staged, int wait);
+int zkm_staged_calls_get(void* staged, size_t segment, zkm_cpu_steps* steps_out, zkm_segment_ops* ops_out, zkm_boot_image* image_out,
+                         char** err);
+void zkm_staged_calls_free(void* staged);
 
 /* ------------------------------------------------------------------ a memory image's hash pages, root and image id
  * What the emulator does at every segment split -- Memory::update_page_hash and Memory::compute_image_id (emulator/src/memory.rs:388-471,

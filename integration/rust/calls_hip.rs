@@ -14,6 +14,9 @@
 //!   * K of them go to `prove_segments_ops_calls_raw`, in place of K x four `finish` calls and `prove_segments_ops_steps_raw`: per 32
 //!     segments the expansion takes one scratch block, at most one launch per kind and one host wait.
 //! `segment_calls_steps` is the host half alone (the patched step list and the counts), for a caller that sizes its tables first.
+//!   * a caller that records segment k + 1 while segment k is proven stages it instead: `StagedCalls::stage` queues the uploads, the
+//!     expansions, the placement of the records and the walk behind the proofs in flight and returns at once;
+//!     `prove_segments_ops_calls_staged` then proves from device memory with nothing read per row on the calling thread.
 //!
 //! Goes into the zkm-prover crate as `prover/src/calls_hip.rs`, beside `cpu_steps_hip.rs`.  NOT COMPILED in the build image (no cargo /
 //! rustc there).
@@ -131,4 +134,65 @@ impl Drop for ExpandedCalls<'_> {
     fn drop(&mut self) {
         unsafe { zkm_expanded_calls_free(self.handle) }
     }
+}
+
+/// K segments' calls on their way into HBM behind the context's current work (zkm_segments_calls_stage): expanded, their records placed
+/// into the step list and the list walked on the device.  `stage` returns at once with no host wait; the logs (and the images' words)
+/// must stay as they are until `ready` answers true.  `get` is what the `*_steps` calls of the SAME context take for a segment; drop
+/// the handle after those calls.
+pub struct StagedCalls<'a> {
+    handle: *mut c_void,
+    nseg: usize,
+    with_images: bool,
+    logs: PhantomData<&'a StepLog>,
+}
+
+impl<'a> StagedCalls<'a> {
+    pub fn stage(ctx: *mut zkm_ctx, images: &[zkm_boot_image], segments: &[SegmentCalls<'a>]) -> Result<Self> {
+        ensure!(images.is_empty() || images.len() == segments.len(), "{} images for {} segments", images.len(), segments.len());
+        let images_ptr = if images.is_empty() { std::ptr::null() } else { images.as_ptr() };
+        let raw = raw_array(segments);
+        let (mut handle, mut err) = (std::ptr::null_mut(), std::ptr::null_mut());
+        check(unsafe { zkm_segments_calls_stage(ctx, raw.len(), raw.as_ptr() as *const c_void, images_ptr, &mut handle, &mut err) }, err)?;
+        Ok(StagedCalls { handle, nseg: raw.len(), with_images: !images.is_empty(), logs: PhantomData })
+    }
+
+    /// True once the uploads, the expansions, the placement, the walk and the downloads have ended; `wait` blocks until they have.
+    pub fn ready(&self, wait: bool) -> Result<bool> {
+        let r = unsafe { zkm_staged_calls_ready(self.handle, wait as std::os::raw::c_int) };
+        ensure!(r >= 0, "zkm_staged_calls_ready: runtime error");
+        Ok(r == 1)
+    }
+
+    /// Segment `segment` with device pointers; a refused segment fails with the refusal's text.  One host wait a handle at most.
+    pub fn get(&self, segment: usize) -> Result<(zkm_cpu_steps, zkm_segment_ops, zkm_boot_image)> {
+        let (mut steps, mut ops, mut image) =
+            unsafe { (std::mem::zeroed::<zkm_cpu_steps>(), std::mem::zeroed::<zkm_segment_ops>(), std::mem::zeroed::<zkm_boot_image>()) };
+        let mut err = std::ptr::null_mut();
+        check(unsafe { zkm_staged_calls_get(self.handle, segment, &mut steps, &mut ops, &mut image, &mut err) }, err)?;
+        Ok((steps, ops, image))
+    }
+}
+
+impl Drop for StagedCalls<'_> {
+    fn drop(&mut self) {
+        unsafe { zkm_staged_calls_free(self.handle) }
+    }
+}
+
+/// `prove_segments_ops_calls_raw` on calls staged ahead of the call: zkm_prove_segments_ops_steps on the handle's outputs, word for
+/// word the same proofs, with its three host waits and nothing of the calls read on the calling thread.
+pub fn prove_segments_ops_calls_staged(ctx: *mut zkm_ctx, staged: &StagedCalls, config: &zkm_stark_config, public_values: &[&[u64]])
+                                       -> Result<SegmentProofs> {
+    let (mut lists, mut ops, mut images) = (Vec::new(), Vec::new(), Vec::new());
+    for s in 0..staged.nseg {
+        let (st, o, im) = staged.get(s)?;
+        lists.push(st);
+        ops.push(o);
+        images.push(im);
+    }
+    let images_ptr = if staged.with_images { images.as_ptr() } else { std::ptr::null() };
+    size_then_prove(staged.nseg, public_values, config.num_challenges as usize, |pv, npv, proofs, offs, chal, err| unsafe {
+        zkm_prove_segments_ops_steps(ctx, config, staged.nseg, images_ptr, lists.as_ptr(), ops.as_ptr(), pv, npv, proofs, offs, chal, err)
+    })
 }

@@ -409,6 +409,13 @@ extern "C" {
                                         calls: *const c_void, public_values: *const *const u64, npublic: *const usize,
                                         proofs_out: *const *mut u64, proof_offsets_out: *mut usize, ctl_challenges_out: *const *mut u64,
                                         err: *mut *mut c_char) -> c_int;
+    // the same calls staged behind the current proofs: expanded, placed and walked on the device (staged / *out: an address)
+    pub fn zkm_segments_calls_stage(ctx: *mut zkm_ctx, nseg: usize, calls: *const c_void, images: *const zkm_boot_image, out: *mut *mut c_void,
+                                    err: *mut *mut c_char) -> c_int;
+    pub fn zkm_staged_calls_ready(staged: *mut c_void, wait: c_int) -> c_int;
+    pub fn zkm_staged_calls_get(staged: *mut c_void, segment: usize, steps_out: *mut zkm_cpu_steps, ops_out: *mut zkm_segment_ops,
+                                image_out: *mut zkm_boot_image, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_staged_calls_free(staged: *mut c_void);
     // what the emulator hashes between two segments: hash pages, root and image id of a memory image
     pub fn zkm_image_hash_plan(dirty_index: *const u32, ndirty: usize, hash_index_out: *mut u32, capacity: usize) -> usize;
     pub fn zkm_image_hash(ctx: *mut zkm_ctx, r#in: *const zkm_image_pages, hash_words_out: *mut u32, page_hash_root_out: *mut u8,

@@ -898,7 +898,9 @@ class ExpandedCalls:
         """Segment s's outputs as numpy arrays, for comparisons: steps, nraw, raw_rows (nraw x 259) and every list of the operations that
         lies in device memory, under its zkm_segment_ops name; "counts": every count of the operations."""
         st, o = self.structs(s)
+        return self._download(st, o, s)
 
+    def _download(self, st, o, s):
         def down(ptr, n, dtype, shape):
             out = np.zeros(n, dtype=dtype)
             if n:
@@ -921,6 +923,73 @@ class ExpandedCalls:
             self.ctx._staged.discard(self)
             if self.ctx.h:
                 self.ctx.L.zkm_expanded_calls_free(h)
+
+
+class _StagedImage:
+    """A segment's boot image as StagedCalls.get hands it out: addrs / values in device memory (the handle's)."""
+
+    def __init__(self, st, owner):
+        self._st, self._owner, self.nwords = st, owner, st.nwords
+
+    def struct(self):
+        return self._st
+
+
+class StagedCalls(ExpandedCalls):
+    """The handle of zkm_segments_calls_stage: K segments' calls on their way into HBM behind the context's current work -- expanded,
+    their records placed into the step list and the list walked on the device (include/zkm_hip.h "Staged calls").  get(s) is what
+    segments_tables_steps / prove_segments_ops_steps of the SAME context take for segment s; free() after those calls have returned.
+    The SegmentCalls (and BootImages) it was staged from are kept alive by the handle, and their arrays must stay as they are until
+    ready() is true.  Freed when dropped, at the end of a `with` block or by Context.close()."""
+
+    def __init__(self, ctx, handle, calls, images=None):
+        ExpandedCalls.__init__(self, ctx, handle, calls)
+        self.images = None if images is None else list(images)
+
+    def structs(self, s, image=False):
+        """(CpuStepsStruct, SegmentOpsStruct[, BootImageStruct]) of segment s, as zkm_staged_calls_get fills them (waits on the host for
+        the handle's events the first time, one wait a handle at most); a refused segment raises ZkmError with the refusal's text."""
+        if not self.h:
+            raise ZkmError("zkm_staged_calls_get: freed handle")
+        st, ops, im, err = CpuStepsStruct(), SegmentOpsStruct(), BootImageStruct(), C.c_char_p()
+        _check(self.ctx.L.zkm_staged_calls_get(self.h, s, C.byref(st), C.byref(ops), C.byref(im), C.byref(err)), err)
+        return (st, ops, im) if image else (st, ops)
+
+    def get(self, s):
+        """(steps, ops, image) of segment s for segments_tables_steps / prove_segments_ops_steps: device pointers the handle owns; image is
+        None when the calls were staged without images."""
+        st, o, im = self.structs(s, image=True)
+        ops = SegmentOps.__new__(SegmentOps)
+        ops.lists, ops.counts, ops._staged_struct, ops._owner = {}, {}, o, self
+        n = _StagedStepsSegment(st, None, self)
+        return n, ops, (None if self.images is None else _StagedImage(im, self))
+
+    def segment(self, s):
+        return self.get(s)[:2]
+
+    def download(self, s):
+        """As ExpandedCalls.download, the patched steps from device memory too."""
+        st, o = self.structs(s)
+        steps = np.zeros(st.nsteps, dtype=CPU_STEP_DT)
+        if st.nsteps:
+            err = C.c_char_p()
+            _check(self.ctx.L.zkm_dev_download(self.ctx.h, steps.ctypes.data, st.steps, steps.nbytes, C.byref(err)), err)
+        host = CpuStepsStruct(steps.ctypes.data, st.nsteps, st.raw_rows, st.nraw)
+        return self._download(host, o, s)
+
+    def ready(self, wait=False):
+        r = self.ctx.L.zkm_staged_calls_ready(self.h, 1 if wait else 0)
+        if r < 0:
+            raise ZkmError("zkm_staged_calls_ready: runtime error")
+        return bool(r)
+
+    def free(self):
+        """Waits for the uploads, the expansions, the placement and the walk, and returns the blocks."""
+        if self.h:
+            h, self.h = self.h, None
+            self.ctx._staged.discard(self)
+            if self.ctx.h:
+                self.ctx.L.zkm_staged_calls_free(h)
 
 
 class _marshal_ops:
@@ -1880,6 +1949,16 @@ class Context:
         arr, h, err = self._calls_array(calls_list), C.c_void_p(), C.c_char_p()
         _check(self.L.zkm_segments_calls_expand(self.h, len(calls_list), C.addressof(arr), C.byref(h), C.byref(err)), err)
         return ExpandedCalls(self, h, calls_list)
+
+    def segments_calls_stage(self, calls_list, images=None):
+        """zkm_segments_calls_stage: queue the uploads, the expansions, the placement of the records and the device walk of K segments'
+        calls (and the upload of their BootImages) behind the context's current work and return a StagedCalls at once (no host wait)."""
+        K = len(calls_list)
+        assert images is None or len(images) == K, "one image per segment"
+        im = (BootImageStruct * max(K, 1))(*[i.struct() for i in images]) if images is not None else None
+        arr, h, err = self._calls_array(calls_list), C.c_void_p(), C.c_char_p()
+        _check(self.L.zkm_segments_calls_stage(self.h, K, C.addressof(arr), im, C.byref(h), C.byref(err)), err)
+        return StagedCalls(self, h, calls_list, images)
 
     def segments_tables_calls(self, calls_list, images=None, cfg=None, sizing=False):
         """zkm_segments_tables_calls: segments_calls_expand, segments_tables_steps on its outputs, the free.  Returns as

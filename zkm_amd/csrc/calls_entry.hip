@@ -25,18 +25,16 @@ template <class F> void must(F&& call) {
     throw std::runtime_error(m);
 }
 
-// counts_out of zkm_segment_calls_steps
-enum { N_SHA_ROWS, N_KECCAK_ROWS, N_IO_ROWS, N_INSN_ROWS, N_RAW, N_MEM, N_LOGIC, N_ARITH, N_EXT, N_PERMS, N_ROW_MEM };
-static_assert(N_ROW_MEM + 1 == ZKM_CALLS_COUNTS, "counts_out as the header lists it");
-
 void host_list(const void* p, size_t n, const char* name) {
     if (n && !p) throw std::runtime_error(std::string(name) + ": NULL with a count of " + dec(n));
     if (n && zkm_is_device_ptr(p)) throw std::runtime_error(std::string(name) + ": device memory (the list is read on the host)");
 }
 
-// The host half for one segment: every refusal that concerns the step list and `own` (throws the bare message; the per-kind entry
-// points' messages as they are), the counts, and the patched list into `out` (nsteps records) unless it is null.
-void calls_steps(const zkm_segment_calls& q, zkm_cpu_step* out, size_t counts[ZKM_CALLS_COUNTS]) {
+}  // namespace
+
+// The host half for one segment that reads the lists PER CALL and never per row: every refusal that concerns where the lists lie and
+// `own` (throws the bare message; the per-kind entry points' messages as they are), and the counts.
+void zkm_calls_counts(const zkm_segment_calls& q, size_t n[ZKM_CALLS_COUNTS]) {
     const zkm_cpu_steps& st = q.steps;
     host_list(st.steps, st.nsteps, "steps.steps");
     if (st.nraw && !st.raw_rows) throw std::runtime_error("steps.raw_rows: NULL with a count of " + dec(st.nraw));
@@ -58,7 +56,8 @@ void calls_steps(const zkm_segment_calls& q, zkm_cpu_step* out, size_t counts[ZK
     host_list(q.insn_clocks, q.ninsns, "insn_clocks");
 
     // the counts, from the kinds' own entry points
-    size_t n[ZKM_CALLS_COUNTS] = {}, mem[4] = {}, logic[2] = {};
+    size_t mem[4] = {}, logic[2] = {};
+    std::fill(n, n + ZKM_CALLS_COUNTS, 0);
     zkm_sha_calls_counts(q.nextend, q.ncompress, &n[N_SHA_ROWS], &mem[0], &logic[0], &n[N_EXT]);
     must([&](char** e) { return zkm_keccak_calls_counts(q.keccak_input_off, q.nkeccak, &n[N_KECCAK_ROWS], &mem[1], &logic[1], &n[N_PERMS], e); });
     must([&](char** e) { return zkm_io_calls_counts(q.io_kinds, q.io_data_off, q.nio, &n[N_IO_ROWS], &mem[2], e); });
@@ -69,6 +68,33 @@ void calls_steps(const zkm_segment_calls& q, zkm_cpu_step* out, size_t counts[ZK
     n[N_MEM] = mem[0] + mem[1];
     n[N_LOGIC] = logic[0] + logic[1];
     n[N_ROW_MEM] = mem[2] + mem[3];
+}
+
+// a generated row as a refusal names it: its kind, its position among the kind's rows, its clock
+static std::string zkm_calls_describe_row(const size_t n[ZKM_CALLS_COUNTS], size_t j, uint64_t clock) {
+    const size_t kind_end[4] = {n[N_SHA_ROWS], n[N_SHA_ROWS] + n[N_KECCAK_ROWS], n[N_SHA_ROWS] + n[N_KECCAK_ROWS] + n[N_IO_ROWS], (size_t)-1};
+    const char* const kind_name[4] = {"SHA call", "Keccak call", "I/O call", "instruction record"};
+    int k = 0;
+    while (j >= kind_end[k]) k++;
+    return std::string(kind_name[k]) + " row " + dec(j - (k ? kind_end[k - 1] : 0)) + " (clock " + dec(clock) + ")";
+}
+// the two refusals that need a row's clock, in one wording for the host loop below and the device's verdicts (calls_stage.hip)
+std::string zkm_calls_row_refusal(const zkm_segment_calls& q, const size_t n[ZKM_CALLS_COUNTS], size_t j, uint64_t clock) {
+    const std::string row = zkm_calls_describe_row(n, j, clock);
+    if (clock < q.first_clock || clock - q.first_clock >= q.steps.nsteps)
+        return row + " lies outside the step list (first_clock " + dec(q.first_clock) + ", " + dec(q.steps.nsteps) + " steps)";
+    return row + ": two records on one clock";
+}
+
+namespace {
+
+// The whole host half for one segment: zkm_calls_counts, then PER ROW the records, their clocks and the two refusals that need them,
+// and the patched list into `out` (nsteps records) unless it is null.
+void calls_steps(const zkm_segment_calls& q, zkm_cpu_step* out, size_t counts[ZKM_CALLS_COUNTS]) {
+    const zkm_cpu_steps& st = q.steps;
+    size_t n[ZKM_CALLS_COUNTS];
+    zkm_calls_counts(q, n);
+    const size_t rows = n[N_SHA_ROWS] + n[N_KECCAK_ROWS] + n[N_IO_ROWS] + n[N_INSN_ROWS];
 
     // the records and their clocks, kind by kind with the running raw_base
     std::vector<zkm_cpu_step> rec(rows);
@@ -86,20 +112,11 @@ void calls_steps(const zkm_segment_calls& q, zkm_cpu_step* out, size_t counts[ZK
     std::copy(q.insn_clocks, q.insn_clocks + q.ninsns, clk.begin() + at);
 
     // where each record goes: clock - first_clock, inside the list, one record a clock
-    const size_t kind_end[4] = {n[N_SHA_ROWS], n[N_SHA_ROWS] + n[N_KECCAK_ROWS], rows - n[N_INSN_ROWS], rows};
-    const char* const kind_name[4] = {"SHA call", "Keccak call", "I/O call", "instruction record"};
-    auto describe = [&](size_t j) {
-        int k = 0;
-        while (j >= kind_end[k]) k++;
-        return std::string(kind_name[k]) + " row " + dec(j - (k ? kind_end[k - 1] : 0)) + " (clock " + dec(clk[j]) + ")";
-    };
     std::vector<bool> taken(st.nsteps, false);
     for (size_t j = 0; j < rows; j++) {
-        if (clk[j] < q.first_clock || clk[j] - q.first_clock >= st.nsteps)
-            throw std::runtime_error(describe(j) + " lies outside the step list (first_clock " + dec(q.first_clock) + ", " + dec(st.nsteps) + " steps)");
-        const size_t p = clk[j] - q.first_clock;
-        if (taken[p]) throw std::runtime_error(describe(j) + ": two records on one clock");
-        taken[p] = true;
+        const bool outside = clk[j] < q.first_clock || clk[j] - q.first_clock >= st.nsteps;
+        if (outside || taken[clk[j] - q.first_clock]) throw std::runtime_error(zkm_calls_row_refusal(q, n, j, clk[j]));
+        taken[clk[j] - q.first_clock] = true;
     }
     if (out) {
         std::copy(st.steps, st.steps + st.nsteps, out);
@@ -108,17 +125,7 @@ void calls_steps(const zkm_segment_calls& q, zkm_cpu_step* out, size_t counts[ZK
     if (counts) std::copy(n, n + ZKM_CALLS_COUNTS, counts);
 }
 
-// one segment of the device half
-struct seg_plan {
-    size_t n[ZKM_CALLS_COUNTS] = {};
-    zkm_sha_job sha;
-    zkm_keccak_job keccak;
-    zkm_io_job io;
-    zkm_insn_job insn;
-    // the eight lists of the segment's block: rows, memory, logic, ShaExtend inputs and timestamps, Keccak inputs and timestamps, arithmetic
-    size_t own_bytes[8] = {}, bytes[8] = {}, at[8] = {}, total = 0;
-    const void* own_src[8] = {};
-};
+using seg_plan = zkm_calls_plan;
 
 void own_list(const void* p, size_t n, const char* name) {
     if (n && !p) throw std::runtime_error(std::string("own.") + name + ": NULL with a count of " + dec(n));
@@ -126,28 +133,9 @@ void own_list(const void* p, size_t n, const char* name) {
 
 }  // namespace
 
-struct zkm_expanded_calls {
-    zkm_ctx* c = nullptr;
-    struct seg {
-        std::vector<zkm_cpu_step> steps;
-        zkm_cpu_steps st{};
-        zkm_segment_ops ops{};
-    };
-    std::vector<seg> segs;
-    std::vector<void*> blocks;
-    zkm_expanded_calls() = default;
-    zkm_expanded_calls(const zkm_expanded_calls&) = delete;
-    ~zkm_expanded_calls() {
-        for (void* p : blocks) c->release(p);
-    }
-};
-
-namespace {
-
-// every refusal of one segment, on the host; fills the patched list, the jobs (without outputs) and the block's layout
-void plan_segment(const zkm_segment_calls& q, zkm_expanded_calls::seg& out, seg_plan& P) {
-    out.steps.resize(q.steps.nsteps);
-    calls_steps(q, out.steps.data(), P.n);
+// The rest of a segment's refusals (P.n is zkm_calls_counts'): the `own` lists, the four kinds' checks of their calls -- which fill the
+// jobs, without outputs -- and the layout of the segment's block.
+void zkm_calls_plan_lists(const zkm_segment_calls& q, zkm_calls_plan& P) {
     own_list(q.own.memory_ops, q.own.nmemory, "memory_ops");
     own_list(q.own.logic_ops, q.own.nlogic, "logic_ops");
     own_list(q.own.arithmetic_ops, q.own.narithmetic, "arithmetic_ops");
@@ -171,11 +159,72 @@ void plan_segment(const zkm_segment_calls& q, zkm_expanded_calls::seg& out, seg_
                              q.ninsns ? n[N_ARITH] * 12 : 0};
     const void* src[8] = {q.steps.raw_rows, q.own.memory_ops, q.own.logic_ops, nullptr, nullptr, q.own.keccak_inputs, q.own.keccak_timestamps,
                           q.own.arithmetic_ops};
+    P.total = 0;
     for (int i = 0; i < 8; i++) {
         P.own_bytes[i] = own_b[i], P.bytes[i] = own_b[i] + gen_b[i], P.own_src[i] = src[i];
         P.at[i] = P.total;
         P.total += up256(P.bytes[i]);
     }
+}
+
+// The planned segment's block at `b` (P.total bytes; null when that is 0): where the jobs write, and what the builder takes -- `own`
+// with the joined lists and the calls' groups, the latter pointing at the CALLER's call lists.  list[i]: where list i starts (null when
+// it is empty); the segment's own part of it, P.own_bytes[i] from P.own_src[i], is the caller's to copy there.
+void zkm_calls_bind(const zkm_segment_calls& q, zkm_calls_plan& p, char* b, char* list[8], zkm_segment_ops& o) {
+    for (int i = 0; i < 8; i++) list[i] = p.bytes[i] ? b + p.at[i] : nullptr;
+    const size_t* n = p.n;
+    // the rows behind the segment's own: the SHA calls', the Keccak calls', the I/O calls', the instructions'
+    uint64_t* rows = (uint64_t*)list[0] + q.steps.nraw * CPU_W;
+    p.sha.rows = rows;
+    p.keccak.rows = rows + n[N_SHA_ROWS] * CPU_W;
+    p.io.rows = p.keccak.rows + n[N_KECCAK_ROWS] * CPU_W;
+    p.insn.rows = p.io.rows + n[N_IO_ROWS] * CPU_W;
+    // the lists behind the segment's own: the SHA calls' items, then the Keccak calls'
+    p.sha.mem = (uint64_t*)list[1] + 6 * q.own.nmemory;
+    p.keccak.mem = p.sha.mem + 6 * p.sha.nmem;
+    p.sha.logic = (uint32_t*)list[2] + 3 * q.own.nlogic;
+    p.keccak.logic = p.sha.logic + 3 * p.sha.nlogic;
+    p.sha.ext_in = (uint32_t*)list[3], p.sha.ext_ts = (uint64_t*)list[4];
+    p.keccak.perm_in = (uint64_t*)list[5] + 25 * q.own.nkeccak, p.keccak.perm_ts = (uint64_t*)list[6] + q.own.nkeccak;
+    p.insn.arith = list[7] ? (uint32_t*)list[7] + 3 * q.own.narithmetic : nullptr;
+    o = q.own;
+    o.memory_ops = (const uint64_t*)list[1], o.nmemory = q.own.nmemory + n[N_MEM];
+    o.logic_ops = (const uint32_t*)list[2], o.nlogic = q.own.nlogic + n[N_LOGIC];
+    if (q.ninsns) o.arithmetic_ops = (const uint32_t*)list[7], o.narithmetic = q.own.narithmetic + n[N_ARITH];
+    o.keccak_inputs = (const uint64_t*)list[5], o.keccak_timestamps = (const uint64_t*)list[6], o.nkeccak = q.own.nkeccak + n[N_PERMS];
+    o.sha_extend_inputs = (const uint8_t*)list[3], o.sha_extend_timestamps = (const uint64_t*)list[4], o.nsha_extend = n[N_EXT];
+    o.sha_extend_sponge_w16 = q.extend_w16, o.sha_extend_sponge_meta = q.extend_meta, o.nsha_extend_sponge = q.nextend;
+    o.sha_compress_hx = o.sha_compress_sponge_hx = q.compress_hx;
+    o.sha_compress_w = o.sha_compress_sponge_w = q.compress_w;
+    o.sha_compress_meta = o.sha_compress_sponge_meta = q.compress_meta;
+    o.nsha_compress = o.nsha_compress_sponge = q.ncompress;
+    o.keccak_sponge_inputs = q.keccak_inputs, o.keccak_sponge_off = q.keccak_input_off, o.keccak_sponge_meta = q.keccak_meta;
+    o.nkeccak_sponge = q.nkeccak;
+}
+
+struct zkm_expanded_calls {
+    zkm_ctx* c = nullptr;
+    struct seg {
+        std::vector<zkm_cpu_step> steps;
+        zkm_cpu_steps st{};
+        zkm_segment_ops ops{};
+    };
+    std::vector<seg> segs;
+    std::vector<void*> blocks;
+    zkm_expanded_calls() = default;
+    zkm_expanded_calls(const zkm_expanded_calls&) = delete;
+    ~zkm_expanded_calls() {
+        for (void* p : blocks) c->release(p);
+    }
+};
+
+namespace {
+
+// every refusal of one segment, on the host; fills the patched list, the jobs (without outputs) and the block's layout
+void plan_segment(const zkm_segment_calls& q, zkm_expanded_calls::seg& out, seg_plan& P) {
+    out.steps.resize(q.steps.nsteps);
+    calls_steps(q, out.steps.data(), P.n);
+    zkm_calls_plan_lists(q, P);
 }
 
 // the device half for one group of <= ZKM_MAX_SEG planned segments: blocks, uploads, one launch a kind, one host wait
@@ -194,48 +243,19 @@ void expand_group(zkm_ctx* c, const zkm_segment_calls* calls, zkm_expanded_calls
             h->blocks.push_back(b = (char*)c->alloc(p.total));
         }
         char* list[8];
-        for (int i = 0; i < 8; i++) {
-            list[i] = p.bytes[i] ? b + p.at[i] : nullptr;
+        zkm_calls_bind(q, p, b, list, out.ops);
+        for (int i = 0; i < 8; i++)
             if (p.own_bytes[i]) ZKM_HIP_CHECK(hipMemcpyAsync(list[i], p.own_src[i], p.own_bytes[i], hipMemcpyDefault, c->stream));
-        }
         const size_t* n = p.n;
-        // the rows behind the segment's own: the SHA calls', the Keccak calls', the I/O calls', the instructions'
-        uint64_t* rows = (uint64_t*)list[0] + q.steps.nraw * CPU_W;
-        p.sha.rows = rows;
-        p.keccak.rows = rows + n[N_SHA_ROWS] * CPU_W;
-        p.io.rows = p.keccak.rows + n[N_KECCAK_ROWS] * CPU_W;
-        p.insn.rows = p.io.rows + n[N_IO_ROWS] * CPU_W;
         // the SHA and Keccak kernels store only the cells a row sets: their rows, adjacent, are zeroed by one memset a segment
         if (n[N_SHA_ROWS] + n[N_KECCAK_ROWS])
-            ZKM_HIP_CHECK(hipMemsetAsync(rows, 0, (n[N_SHA_ROWS] + n[N_KECCAK_ROWS]) * CPU_W * 8, c->stream));
-        // the lists behind the segment's own: the SHA calls' items, then the Keccak calls'
-        p.sha.mem = (uint64_t*)list[1] + 6 * q.own.nmemory;
-        p.keccak.mem = p.sha.mem + 6 * p.sha.nmem;
-        p.sha.logic = (uint32_t*)list[2] + 3 * q.own.nlogic;
-        p.keccak.logic = p.sha.logic + 3 * p.sha.nlogic;
-        p.sha.ext_in = (uint32_t*)list[3], p.sha.ext_ts = (uint64_t*)list[4];
-        p.keccak.perm_in = (uint64_t*)list[5] + 25 * q.own.nkeccak, p.keccak.perm_ts = (uint64_t*)list[6] + q.own.nkeccak;
-        p.insn.arith = list[7] ? (uint32_t*)list[7] + 3 * q.own.narithmetic : nullptr;
+            ZKM_HIP_CHECK(hipMemsetAsync(p.sha.rows, 0, (n[N_SHA_ROWS] + n[N_KECCAK_ROWS]) * CPU_W * 8, c->stream));
         sha[s] = p.sha;
         keccak[s] = std::move(p.keccak);
         io[s] = std::move(p.io);
         insn[s] = std::move(p.insn);
-        // what the builder takes: the patched list with the rows on the device; `own` with the joined lists and the calls' groups
+        // what the builder takes: the patched list with the rows on the device, and the operations
         out.st = zkm_cpu_steps{out.steps.data(), out.steps.size(), (const uint64_t*)list[0], n[N_RAW]};
-        zkm_segment_ops& o = out.ops;
-        o = q.own;
-        o.memory_ops = (const uint64_t*)list[1], o.nmemory = q.own.nmemory + n[N_MEM];
-        o.logic_ops = (const uint32_t*)list[2], o.nlogic = q.own.nlogic + n[N_LOGIC];
-        if (q.ninsns) o.arithmetic_ops = (const uint32_t*)list[7], o.narithmetic = q.own.narithmetic + n[N_ARITH];
-        o.keccak_inputs = (const uint64_t*)list[5], o.keccak_timestamps = (const uint64_t*)list[6], o.nkeccak = q.own.nkeccak + n[N_PERMS];
-        o.sha_extend_inputs = (const uint8_t*)list[3], o.sha_extend_timestamps = (const uint64_t*)list[4], o.nsha_extend = n[N_EXT];
-        o.sha_extend_sponge_w16 = q.extend_w16, o.sha_extend_sponge_meta = q.extend_meta, o.nsha_extend_sponge = q.nextend;
-        o.sha_compress_hx = o.sha_compress_sponge_hx = q.compress_hx;
-        o.sha_compress_w = o.sha_compress_sponge_w = q.compress_w;
-        o.sha_compress_meta = o.sha_compress_sponge_meta = q.compress_meta;
-        o.nsha_compress = o.nsha_compress_sponge = q.ncompress;
-        o.keccak_sponge_inputs = q.keccak_inputs, o.keccak_sponge_off = q.keccak_input_off, o.keccak_sponge_meta = q.keccak_meta;
-        o.nkeccak_sponge = q.nkeccak;
     }
     // ONE scratch block for every list the host holds, of every kind and segment, and the four sets of descriptors
     const size_t part[4] = {zkm_sha_calls_scratch(sha.data(), nseg), zkm_keccak_calls_scratch(keccak.data(), nseg),

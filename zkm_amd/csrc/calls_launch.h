@@ -38,7 +38,7 @@ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 constexpr uint64_t LIM = (uint64_t)1 << 32;   // what a 32-bit cell, address or RAW index stays below
 
 // the record of a ready-made row for the step log: RAW row `index` with the used channels `mask`
-inline zkm_cpu_step raw_step(size_t index, uint32_t mask) {
+GL_HD zkm_cpu_step raw_step(size_t index, uint32_t mask) {
     zkm_cpu_step s{};
     s.kind = ZKM_STEP_RAW;
     s.reads[0] = (uint32_t)index;
@@ -46,7 +46,30 @@ inline zkm_cpu_step raw_step(size_t index, uint32_t mask) {
     return s;
 }
 
+// counts_out of zkm_segment_calls_steps
+enum { N_SHA_ROWS, N_KECCAK_ROWS, N_IO_ROWS, N_INSN_ROWS, N_RAW, N_MEM, N_LOGIC, N_ARITH, N_EXT, N_PERMS, N_ROW_MEM };
+static_assert(N_ROW_MEM + 1 == ZKM_CALLS_COUNTS, "counts_out as the header lists it");
+
 }  // namespace zkm_calls
+
+// ---- one segment of the calls' composition (calls_entry.hip; calls_stage.hip queues the same plan on the copy streams)
+struct zkm_calls_plan {
+    size_t n[ZKM_CALLS_COUNTS] = {};
+    zkm_sha_job sha;
+    zkm_keccak_job keccak;
+    zkm_io_job io;
+    zkm_insn_job insn;
+    // the eight lists of the segment's block: rows, memory, logic, ShaExtend inputs and timestamps, Keccak inputs and timestamps, arithmetic
+    size_t own_bytes[8] = {}, bytes[8] = {}, at[8] = {}, total = 0;
+    const void* own_src[8] = {};
+};
+// calls_entry.hip, each throwing the bare message: the refusals and counts that read the lists per call and never per row; the rest of
+// the host's refusals, the jobs and the block's layout; the block bound to the jobs' outputs and to what the builder takes; and the
+// text of the two refusals that need a row's clock, for the host's loop and the device's verdict alike
+void zkm_calls_counts(const zkm_segment_calls& q, size_t n[ZKM_CALLS_COUNTS]);
+void zkm_calls_plan_lists(const zkm_segment_calls& q, zkm_calls_plan& P);
+void zkm_calls_bind(const zkm_segment_calls& q, zkm_calls_plan& p, char* b, char* list[8], zkm_segment_ops& o);
+std::string zkm_calls_row_refusal(const zkm_segment_calls& q, const size_t n[ZKM_CALLS_COUNTS], size_t j, uint64_t clock);
 
 // the host copies of the descriptors that uploads queued on a stream read: in use until the stream has been waited for
 struct zkm_calls_hold {
@@ -73,8 +96,11 @@ template <class K> size_t zkm_calls_layout(const typename K::job* j, size_t nseg
 
 // Queues the uploads into `sb` (zkm_calls_layout bytes) and ONE launch for nseg <= ZKM_MAX_SEG checked jobs; no launch when no job has
 // an item.  zero_rows queues a memset of each job's sparse rows in front (false: the caller has zeroed them).  The jobs, `hold` and
-// the caller's lists are in use until the stream has been waited for.
-template <class K> void zkm_calls_queue(zkm_ctx* c, const typename K::job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows) {
+// the caller's lists are in use until the stream has been waited for.  `st`: the stream everything is queued on -- the context's
+// compute stream for the kinds' entry points and zkm_segments_calls_expand, a copy stream for a staged call (calls_stage.hip; the
+// profiling scope is a pair of events on the compute stream, so only a launch there has one).
+template <class K>
+void zkm_calls_queue(zkm_ctx* c, hipStream_t st, const typename K::job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows) {
     using Args = typename K::args;
     constexpr size_t NL = std::tuple_size<decltype(K::lists(*j))>::value;
     if (nseg == 0 || nseg > ZKM_MAX_SEG) throw std::runtime_error(std::string(K::name) + ": segment count out of range");
@@ -89,17 +115,18 @@ template <class K> void zkm_calls_queue(zkm_ctx* c, const typename K::job* j, si
             dev[i] = in[i].p;
             if (!in[i].up) continue;
             dev[i] = sb + at[s * NL + i];
-            if (in[i].bytes) ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, c->stream));
+            if (in[i].bytes) ZKM_HIP_CHECK(hipMemcpyAsync((void*)dev[i], in[i].p, in[i].bytes, hipMemcpyHostToDevice, st));
         }
         if (zero_rows && K::sparse_rows(j[s]))
-            ZKM_HIP_CHECK(hipMemsetAsync(j[s].rows, 0, K::sparse_rows(j[s]) * ZKM_CPU_COLS * sizeof(uint64_t), c->stream));
+            ZKM_HIP_CHECK(hipMemsetAsync(j[s].rows, 0, K::sparse_rows(j[s]) * ZKM_CPU_COLS * sizeof(uint64_t), st));
         d[s] = K::make(j[s], dev);
         grid = std::max(grid, K::extent(j[s]));
     }
     if (!grid) return;
-    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(Args), hipMemcpyHostToDevice, c->stream));
-    zkm_prof_scope ps(c, K::scope);
-    hipLaunchKernelGGL(K::kernel, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(K::threads), 0, c->stream, (const Args*)sb);
+    ZKM_HIP_CHECK(hipMemcpyAsync(sb, d, nseg * sizeof(Args), hipMemcpyHostToDevice, st));
+    std::unique_ptr<zkm_prof_scope> ps;
+    if (st == c->stream) ps.reset(new zkm_prof_scope(c, K::scope));
+    hipLaunchKernelGGL(K::kernel, dim3((unsigned)grid, 1, (unsigned)nseg), dim3(K::threads), 0, st, (const Args*)sb);
     ZKM_HIP_CHECK(hipGetLastError());
 }
 
@@ -109,6 +136,6 @@ template <class K> void zkm_calls_one(zkm_ctx* c, const typename K::job& j) {
     // the block, and the uploads queued there still read the descriptors' host copy
     zkm_calls_hold hold;
     zkm_scratch block(c, zkm_calls_layout<K>(&j, 1, nullptr));
-    zkm_calls_queue<K>(c, &j, 1, block.as<char>(), hold, true);
+    zkm_calls_queue<K>(c, c->stream, &j, 1, block.as<char>(), hold, true);
     c->sync();   // (the block, the job and the caller's lists are in use until here)
 }

@@ -284,6 +284,11 @@ bool zkm_staged_steps_find(const void* d_steps, zkm_staged_steps_ref* out) {
         h = it->second.first;
         s = it->second.second;
     }
+    zkm_staged_steps_at(h, s, out);
+    return true;
+}
+
+void zkm_staged_steps_at(zkm_staged_steps* h, size_t s, zkm_staged_steps_ref* out) {
     resolve(h);
     out->ctx = h->ctx;
     out->dev = h->segs[s].dev;
@@ -292,7 +297,6 @@ bool zkm_staged_steps_find(const void* d_steps, zkm_staged_steps_ref* out) {
     out->refusal = h->segs[s].refusal;
     out->done[0] = h->done[0].e;
     out->done[1] = h->done[1].e;
-    return true;
 }
 
 extern "C" {
@@ -328,44 +332,52 @@ int zkm_cpu_steps_stage(zkm_ctx* c, size_t nseg, const zkm_cpu_steps* steps, voi
         check_lists(what, nseg, steps);
         if (!out || !c) throw std::runtime_error(what + ": null argument");
         ZKM_HIP_CHECK(hipSetDevice(c->device));
-        std::unique_ptr<zkm_staged_steps> h(new zkm_staged_steps());
-        h->ctx = c;
-        const walk_plan P(nseg, steps, true);
-        ZKM_HIP_CHECK(hipHostMalloc((void**)&h->verdicts, nseg * sizeof(steps_verdict), hipHostMallocDefault));
-        h->block = zkm_scratch(c, P.bytes);
-        char* sb = h->block.as<char>();
-        h->segs.resize(nseg);
-        for (size_t s = 0; s < nseg; s++) {
-            const walk_seg w = P.seg(sb, steps[s], s);
-            h->segs[s].dev = zkm_cpu_steps{steps[s].nsteps ? w.steps : nullptr, w.nsteps, w.nraw ? w.raw : nullptr, w.nraw};
-            h->segs[s].base = w.base;
-        }
-        // the copy streams start behind what the compute stream has queued (the block may be one that a finished call released)
-        c->ensure_copy_stream(0);
-        c->ensure_copy_stream(1);
-        {
-            const zkm_event e(c);
-            e.record(c->stream);
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
-        }
-        copy_join join;
-        join.c = c;
-        queue_walk(c, c->copy_stream, c->copy_stream2, P, sb, steps, nseg);
-        ZKM_HIP_CHECK(hipMemcpyAsync(h->verdicts, sb, nseg * sizeof(steps_verdict), hipMemcpyDeviceToHost, c->copy_stream));
-        h->done[0] = zkm_event(c);
-        h->done[1] = zkm_event(c);
-        h->done[0].record(c->copy_stream);
-        h->done[1].record(c->copy_stream2);
-        join.c = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(g_steps_mu);
-            for (size_t s = 0; s < nseg; s++)
-                if (h->segs[s].dev.steps) g_staged_steps[h->segs[s].dev.steps] = {h.get(), s};
-        }
-        *out = h.release();
+        *out = zkm_steps_stage_queue(c, nseg, steps, true);
     });
 }
+
+}  // extern "C"
+
+zkm_staged_steps* zkm_steps_stage_queue(zkm_ctx* c, size_t nseg, const zkm_cpu_steps* steps, bool own_steps) {
+    std::unique_ptr<zkm_staged_steps> h(new zkm_staged_steps());
+    h->ctx = c;
+    const walk_plan P(nseg, steps, own_steps);
+    ZKM_HIP_CHECK(hipHostMalloc((void**)&h->verdicts, nseg * sizeof(steps_verdict), hipHostMallocDefault));
+    h->block = zkm_scratch(c, P.bytes);
+    char* sb = h->block.as<char>();
+    h->segs.resize(nseg);
+    for (size_t s = 0; s < nseg; s++) {
+        const walk_seg w = P.seg(sb, steps[s], s);
+        h->segs[s].dev = zkm_cpu_steps{steps[s].nsteps ? w.steps : nullptr, w.nsteps, w.nraw ? w.raw : nullptr, w.nraw};
+        h->segs[s].base = w.base;
+    }
+    // the copy streams start behind what the compute stream has queued (the block may be one that a finished call released)
+    c->ensure_copy_stream(0);
+    c->ensure_copy_stream(1);
+    {
+        const zkm_event e(c);
+        e.record(c->stream);
+        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
+        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
+    }
+    copy_join join;
+    join.c = c;
+    queue_walk(c, c->copy_stream, c->copy_stream2, P, sb, steps, nseg);
+    ZKM_HIP_CHECK(hipMemcpyAsync(h->verdicts, sb, nseg * sizeof(steps_verdict), hipMemcpyDeviceToHost, c->copy_stream));
+    h->done[0] = zkm_event(c);
+    h->done[1] = zkm_event(c);
+    h->done[0].record(c->copy_stream);
+    h->done[1].record(c->copy_stream2);
+    join.c = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_steps_mu);
+        for (size_t s = 0; s < nseg; s++)
+            if (h->segs[s].dev.steps) g_staged_steps[h->segs[s].dev.steps] = {h.get(), s};
+    }
+    return h.release();
+}
+
+extern "C" {
 
 int zkm_staged_steps_ready(void* staged, int wait) {
     zkm_staged_steps* h = (zkm_staged_steps*)staged;

@@ -17,156 +17,7 @@
 // lanes on adjacent words with 8-byte stores.  Every word is written exactly once, so no zero-fill pass comes in front; the kernel's
 // floor is the 2,072 bytes a row it has to write.
 #include "calls_launch.h"
-#include "cpu_steps_dev.h"
-
-namespace zkm_insn {
-
-using zkm_step::bits32;
-using zkm_step::reg_read;
-using zkm_step::reg_write;
-using zkm_step::sext;
-using zkm_step::C_BITS;
-using zkm_step::C_CH0;
-using zkm_step::C_CLOCK;
-using zkm_step::C_CONTEXT;
-using zkm_step::C_GEN;
-using zkm_step::C_KERNEL;
-using zkm_step::C_MEMIO;
-using zkm_step::C_NEXT_PC;
-using zkm_step::C_PC;
-using zkm_step::F_BINARY;
-using zkm_step::F_BINARY_IMM;
-using zkm_step::F_NOP;
-using zkm_step::F_STORE;
-using zkm_step::IO_AUX;
-using zkm_step::IO_SDC1;
-using zkm_step::SEG_CODE;
-constexpr uint32_t NKINDS = 13;
-// row filters of the arithmetic operators the step kinds leave out (arithmetic/mod.rs:135-164)
-enum : uint32_t { A_MULT = 6, A_MULTU = 7, A_MUL = 8, A_DIV = 9, A_DIVU = 10, A_LUI = 21, A_MFHI = 22, A_MTHI = 23, A_MFLO = 24, A_MTLO = 25 };
-constexpr uint32_t REG_LO = 32, REG_HI = 33;
-// what expand returns
-enum : int { OK = 0, BAD_KIND, BAD_ENCODING, DIV_BY_ZERO, DIV_OVERFLOW, R0_NOT_ZERO };
-
-// does `kind` take this instruction word?  Exactly the (opcode, func) pair decode matches for it; the other fields are free.
-GL_HD bool takes(uint32_t kind, uint32_t insn) {
-    const uint32_t op = insn >> 26, fn = insn & 63;
-    switch (kind) {
-    case ZKM_INSN_LUI: return op == 0x0F;
-    case ZKM_INSN_MUL: return op == 0x1C && fn == 0x02;
-    case ZKM_INSN_MULT: return op == 0 && fn == 0x18;
-    case ZKM_INSN_MULTU: return op == 0 && fn == 0x19;
-    case ZKM_INSN_DIV: return op == 0 && fn == 0x1A;
-    case ZKM_INSN_DIVU: return op == 0 && fn == 0x1B;
-    case ZKM_INSN_MFHI: return op == 0 && fn == 0x10;
-    case ZKM_INSN_MTHI: return op == 0 && fn == 0x11;
-    case ZKM_INSN_MFLO: return op == 0 && fn == 0x12;
-    case ZKM_INSN_MTLO: return op == 0 && fn == 0x13;
-    case ZKM_INSN_SDC1: return op == 0x3D;
-    case ZKM_INSN_SYNC: return op == 0 && fn == 0x0F;
-    case ZKM_INSN_PREF: return op == 0x33;
-    default: return false;
-    }
-}
-
-// One record: the whole CpuColumnsView row (through s.cell / s.chan), and the arithmetic operation it pushes (s.arith).  Results are
-// BinaryOperator::result's (arithmetic/mod.rs:48-133).  Nothing is driven unless the verdict is OK.
-template <class S> GL_HD int expand(const zkm_cpu_step& t, uint64_t clock, S& s) {
-    if (t.kind >= NKINDS) return BAD_KIND;
-    if (!takes(t.kind, t.insn)) return BAD_ENCODING;
-    const uint32_t w = t.insn, rs = (w >> 21) & 31, rt = (w >> 16) & 31, rd = (w >> 11) & 31, imm = w & 0xFFFF;
-    const uint32_t a = t.reads[0], b = t.reads[1];
-    const bool div = t.kind == ZKM_INSN_DIV || t.kind == ZKM_INSN_DIVU;
-    const bool move = t.kind >= ZKM_INSN_MFHI && t.kind <= ZKM_INSN_MTLO;
-    if (div && b == 0) return DIV_BY_ZERO;
-    if (t.kind == ZKM_INSN_DIV && a == 0x80000000u && b == 0xFFFFFFFFu) return DIV_OVERFLOW;
-    if (move && b != 0) return R0_NOT_ZERO;
-    // the fixed part: clock, context, pc, next_pc, the kernel flag and the six bit fields in column order, each from its low bit
-    s.cell(C_CLOCK, clock);
-    if (t.context) s.cell(C_CONTEXT, t.context);
-    if (t.pc) s.cell(C_PC, t.pc);
-    if (t.next_pc) s.cell(C_NEXT_PC, t.next_pc);
-    if (t.flags & ZKM_STEP_FLAG_KERNEL) s.cell(C_KERNEL, 1);
-    bits32(s, C_BITS, (w >> 26) | (rs << 6) | (rt << 11) | (rd << 16) | (((w >> 6) & 31) << 21) | ((w & 63) << 26));
-    switch (t.kind) {
-    case ZKM_INSN_LUI: {   // channel 0 writes sext(imm) to rs, channel 1 writes 1 << 16 to rt, channel 2 the result to rt
-        const uint32_t in0 = sext(imm, 16), in1 = 1u << 16;
-        s.cell(F_BINARY_IMM, 1);
-        reg_write(s, 0, rs, in0);
-        reg_write(s, 1, rt, in1);
-        reg_write(s, 2, rt, in0 << 16);
-        s.arith(A_LUI, in0, in1);
-        return OK;
-    }
-    case ZKM_INSN_MUL:
-    case ZKM_INSN_MFHI:
-    case ZKM_INSN_MTHI:
-    case ZKM_INSN_MFLO:
-    case ZKM_INSN_MTLO: {   // channels 0 and 1 read, channel 2 writes; decode's operands: MFHI (33, 0, rd), MTHI (rs, 0, 33), MFLO (32, 0, rd), MTLO (rs, 0, 32)
-        const bool mul = t.kind == ZKM_INSN_MUL, from = t.kind == ZKM_INSN_MFHI || t.kind == ZKM_INSN_MFLO;
-        const bool hi = t.kind == ZKM_INSN_MFHI || t.kind == ZKM_INSN_MTHI;
-        const uint32_t r0 = mul ? rs : from ? (hi ? REG_HI : REG_LO) : rs, r1 = mul ? rt : 0, dest = mul || from ? rd : hi ? REG_HI : REG_LO;
-        const uint32_t f = mul ? A_MUL : t.kind == ZKM_INSN_MFHI ? A_MFHI : t.kind == ZKM_INSN_MTHI ? A_MTHI : t.kind == ZKM_INSN_MFLO ? A_MFLO : A_MTLO;
-        s.cell(F_BINARY, 1);
-        reg_read(s, 0, r0, a);
-        reg_read(s, 1, r1, b);
-        reg_write(s, 2, dest, mul ? a * b : a);
-        s.arith(f, a, b);
-        return OK;
-    }
-    case ZKM_INSN_MULT:
-    case ZKM_INSN_MULTU:
-    case ZKM_INSN_DIV:
-    case ZKM_INSN_DIVU: {   // channels 0 and 1 read rs and rt, channel 2 writes lo to register 32, channel 3 hi to register 33
-        uint32_t lo, hi, f;
-        if (t.kind == ZKM_INSN_MULT) {
-            const uint64_t p = (uint64_t)((int64_t)(int32_t)a * (int64_t)(int32_t)b);
-            f = A_MULT; lo = (uint32_t)p; hi = (uint32_t)(p >> 32);
-        } else if (t.kind == ZKM_INSN_MULTU) {
-            const uint64_t p = (uint64_t)a * b;
-            f = A_MULTU; lo = (uint32_t)p; hi = (uint32_t)(p >> 32);
-        } else if (t.kind == ZKM_INSN_DIV) {
-            f = A_DIV; lo = (uint32_t)((int32_t)a / (int32_t)b); hi = (uint32_t)((int32_t)a % (int32_t)b);
-        } else {
-            f = A_DIVU; lo = a / b; hi = a % b;
-        }
-        s.cell(F_BINARY, 1);
-        reg_read(s, 0, rs, a);
-        reg_read(s, 1, rt, b);
-        reg_write(s, 2, REG_LO, lo);
-        reg_write(s, 3, REG_HI, hi);
-        s.arith(f, a, b);
-        return OK;
-    }
-    case ZKM_INSN_SDC1: {   // channels 0 and 1 read base and rt, channel 2 reads the word, channel 3 stores 0; aux_rs0_mul_rs1 stays 0
-        const uint32_t m = t.reads[2], raw = a + sext(imm, 16), virt = raw & ~3u;
-        s.cell(F_STORE, 1);
-        s.cell(C_MEMIO + IO_SDC1, 1);
-        s.cell(C_MEMIO + IO_AUX, 1);   // aux_filter = m_op_store * opcode_bits[5]: 0x3D has the bit
-        reg_read(s, 0, rs, a);
-        reg_read(s, 1, rt, b);
-        s.chan(2, 1, 1, t.context, SEG_CODE, virt, m);
-        s.chan(3, 1, 0, t.context, SEG_CODE, virt, 0);
-        bits32(s, C_GEN, raw);
-        bits32(s, C_GEN + 32, b);
-        bits32(s, C_GEN + 64, m);
-        return OK;
-    }
-    default:   // SYNC, PREF: decode makes them Nop
-        s.cell(F_NOP, 1);
-        return OK;
-    }
-}
-
-// the counting sink: the mask of used channels and whether an operation is pushed
-struct shape {
-    uint32_t mask = 0, narith = 0;
-    GL_HD void cell(unsigned, uint64_t) {}
-    GL_HD void chan(unsigned i, bool used, bool, uint32_t, uint32_t, uint32_t, uint32_t) { mask |= (uint32_t)used << i; }
-    GL_HD void arith(uint32_t, uint32_t, uint32_t) { narith++; }
-};
-
-}  // namespace zkm_insn
+#include "calls_place_dev.h"   // zkm_insn: one record as a whole row (expand), and the record the step list gets for it
 
 namespace {
 
@@ -286,9 +137,10 @@ struct insn_kind {
     static constexpr const char *name = "zkm_insn_rows_launch", *scope = "insn_rows/rows";
     static constexpr auto kernel = k_insn_rows;
     static constexpr unsigned threads = THREADS;
-    // a job's three lists: the records, the clocks, the workgroups' bases; the host holds them all
+    // a job's three lists: the records, the clocks, the workgroups' bases; the records and clocks go up unless a staged call has them up already
     static std::array<zkm_calls_list, 3> lists(const job& j) {
-        return {{{j.insns, j.n * sizeof(zkm_cpu_step), true}, {j.clocks, j.n * 8, true}, {j.base.data(), j.base.size() * 4, true}}};
+        return {{{j.insns, j.n * sizeof(zkm_cpu_step), !zkm_is_device_ptr(j.insns)}, {j.clocks, j.n * 8, !zkm_is_device_ptr(j.clocks)},
+                 {j.base.data(), j.base.size() * 4, true}}};
     }
     static args make(const job& j, const void* const* dev) {
         return {(const zkm_cpu_step*)dev[0], (const uint64_t*)dev[1], (const uint32_t*)dev[2], j.rows, j.narith ? j.arith : nullptr, j.n, (uint32_t)extent(j)};
@@ -307,8 +159,8 @@ void zkm_insn_rows_check(zkm_insn_job& j) {
     j.narith = sum.arith;
 }
 size_t zkm_insn_rows_scratch(const zkm_insn_job* j, size_t nseg) { return zkm_calls_layout<insn_kind>(j, nseg, nullptr); }
-void zkm_insn_rows_launch(zkm_ctx* c, const zkm_insn_job* j, size_t nseg, char* sb, zkm_calls_hold& hold) {
-    zkm_calls_queue<insn_kind>(c, j, nseg, sb, hold, false);
+void zkm_insn_rows_launch(zkm_ctx* c, const zkm_insn_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, hipStream_t stream) {
+    zkm_calls_queue<insn_kind>(c, stream ? stream : c->stream, j, nseg, sb, hold, false);
 }
 
 extern "C" {

@@ -16,7 +16,7 @@
 // place.  Every word is written, so no zero-fill pass comes in front; the kernel is write-only but for the calls' bytes, and its floor is
 // the 2,072 bytes a row it has to write.
 #include "calls_launch.h"
-#include "cpu_steps_dev.h"
+#include "calls_place_dev.h"
 
 namespace {
 
@@ -27,37 +27,7 @@ constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256, ROWS_PER_WG = 8;
 static_assert(C_CLOCK + 1 == C_CH0 && C_CH0 + 48 <= CPU_W, "a row's clock and its 48 channel cells are 49 contiguous words");
 
 // ---- the one statement of where things go, for a call of kind `kind` with L bytes (the host has refused the lengths a kind does not take)
-namespace place {
-constexpr uint32_t NKINDS = 4;
-constexpr uint64_t PREIMAGE_HASH = 0x30001000, PREIMAGE_MAP = 0x31000000;   // load_preimage's two addresses
-constexpr unsigned POSEIDON_RATE_BYTES = 32;
-GL_HD size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
-// the words a call moves through channels beyond its first row's fixed part: hint read / commit W, verify 8, preimage Q = 1 + ceil(C / 4)
-GL_HD size_t words(uint32_t kind, size_t L) {
-    return kind == ZKM_IO_HINT_READ ? ceil_div(L, 4) : kind == ZKM_IO_COMMIT ? L / 4 : kind == ZKM_IO_VERIFY ? 8 : 1 + ceil_div(L - 32, 4);
-}
-// a preimage call's hash row stands in front of its write rows
-GL_HD size_t lead_rows(uint32_t kind) { return kind == ZKM_IO_PREIMAGE ? 1 : 0; }
-// what a call adds: rows (a hint read or commit of no word still pushes one row) and used channels
-GL_HD size_t rows(uint32_t kind, size_t L) {
-    const size_t r = ceil_div(words(kind, L), 8);
-    return lead_rows(kind) + (r ? r : 1);
-}
-GL_HD size_t mem(uint32_t kind, size_t L) { return 8 * lead_rows(kind) + words(kind, L); }
-GL_HD uint64_t row_clock(uint64_t timestamp, size_t j) { return timestamp / 10 + j; }
-// the used channels of a call's row j: always the low ones
-GL_HD unsigned channels(uint32_t kind, size_t L, size_t j) {
-    if (j < lead_rows(kind)) return 8;
-    const size_t left = words(kind, L) - 8 * (j - lead_rows(kind));
-    return left < 8 ? (unsigned)left : 8;
-}
-GL_HD uint32_t row_mask(uint32_t kind, size_t L, size_t j) { return (1u << channels(kind, L, j)) - 1; }
-// the address of the last word a call touches, given its meta's address (the hash row's are constants)
-GL_HD uint64_t last_address(uint32_t kind, size_t L, uint64_t address) {
-    const size_t w = words(kind, L);
-    return address + 4 * (w ? w - 1 : 0);
-}
-}  // namespace place
+namespace place = zkm_io_place;   // (calls_place_dev.h)
 
 struct io_calls_args {
     const uint32_t* kinds;      // ncalls
@@ -221,7 +191,7 @@ struct io_kind {
     static std::array<zkm_calls_list, 5> lists(const job& j) {
         const size_t n = j.n, first = n ? j.off[0] : 0, nbytes = n ? j.off[n] - first : 0;
         const bool data_up = !zkm_is_device_ptr(j.data);
-        return {{{j.kinds, 4 * n, true},
+        return {{{j.kinds, 4 * n, !zkm_is_device_ptr(j.kinds)},
                  {data_up && j.data ? j.data + first : j.data, nbytes, data_up},
                  {j.off_up.data(), n ? 8 * (n + 1) : 0, true},
                  {j.meta, 32 * n, !zkm_is_device_ptr(j.meta)},
@@ -250,8 +220,8 @@ void zkm_io_calls_check(zkm_io_job& j) {
     rebase_offsets(j);
 }
 size_t zkm_io_calls_scratch(const zkm_io_job* j, size_t nseg) { return zkm_calls_layout<io_kind>(j, nseg, nullptr); }
-void zkm_io_calls_launch(zkm_ctx* c, const zkm_io_job* j, size_t nseg, char* sb, zkm_calls_hold& hold) {
-    zkm_calls_queue<io_kind>(c, j, nseg, sb, hold, false);
+void zkm_io_calls_launch(zkm_ctx* c, const zkm_io_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, hipStream_t stream) {
+    zkm_calls_queue<io_kind>(c, stream ? stream : c->stream, j, nseg, sb, hold, false);
 }
 
 extern "C" {
@@ -287,8 +257,9 @@ int zkm_io_calls_steps(const uint32_t* kinds, const uint64_t* data_off, const ui
         for (size_t k = 0; k < ncalls; k++) {
             const uint64_t L = data_off[k + 1] - data_off[k];
             for (size_t j = 0; j < place::rows(kinds[k], L); j++) {
-                steps_out[row_off[k] + j] = raw_step(raw_base + row_off[k] + j, place::row_mask(kinds[k], L, j));
-                clocks_out[row_off[k] + j] = place::row_clock(meta[4 * k + 3], j);
+                const zkm_row_rec r = place::row_rec(kinds, data_off, meta, k, j);
+                steps_out[row_off[k] + j] = raw_step(raw_base + row_off[k] + j, r.mask);
+                clocks_out[row_off[k] + j] = r.clock;
             }
         }
     });

@@ -15,7 +15,7 @@
 // list by adjacent lanes on adjacent words; an XOR's lhs is the stored state word ^ the block word.  The row block is zeroed by one
 // memset before the launch, so only the cells a row sets are stored.
 #include "calls_launch.h"
-#include "cpu_steps_dev.h"
+#include "calls_place_dev.h"
 #include "hash_constants_dev.h"
 
 namespace {
@@ -32,26 +32,7 @@ constexpr uint32_t OP_XOR = 2;   // zkm_logic_trace's code
 constexpr uint64_t FLAG = ZKM_SPONGE_BYTE_ADDRESSED;
 
 // ---- the one statement of where things go, for a call of L input bytes (a positive multiple of 4)
-namespace place {
-constexpr unsigned RATE = 136, RATE_U32 = 34, STATE = 25;                         // KECCAK_RATE_BYTES, KECCAK_RATE_U32S, the state's u64 words
-constexpr uint32_t MASK_SPONGE = 0, MASK_WRITE = 0xFF;
-GL_HD size_t words(size_t L) { return L / 4; }
-GL_HD size_t read_rows(size_t L) { return (words(L) + 7) / 8; }                   // R: eight words a row
-GL_HD size_t blocks(size_t L) { return L / RATE + 1; }                            // B: the last one carries pad10*1 (it may hold nothing else)
-// what a call adds to each list
-GL_HD size_t rows(size_t L) { return read_rows(L) + 2; }
-GL_HD size_t mem(size_t L) { return L; }
-GL_HD size_t logic(size_t L) { return RATE_U32 * blocks(L); }
-// a call's rows: read rows 0 .. R - 1, the sponge row, the write row
-GL_HD size_t sponge_row(size_t L) { return read_rows(L); }
-GL_HD size_t write_row(size_t L) { return read_rows(L) + 1; }
-// clocks, counted from the sponge row's S = timestamp / NUM_CHANNELS: read row j at S - R + j, the write row at S + 1
-GL_HD uint64_t row_clock(uint64_t S, size_t L, size_t j) { return S - read_rows(L) + j; }
-GL_HD unsigned read_channels(size_t L, size_t j) { return words(L) - 8 * j < 8 ? (unsigned)(words(L) - 8 * j) : 8; }
-GL_HD uint32_t row_mask(size_t L, size_t j) { return j < read_rows(L) ? (1u << read_channels(L, j)) - 1 : j == sponge_row(L) ? MASK_SPONGE : MASK_WRITE; }
-// the word whose address the sponge row carries: the first of the final block (0 where the input ends before it)
-GL_HD size_t final_word(size_t L) { return L / RATE * RATE_U32; }
-}  // namespace place
+namespace place = zkm_keccak_place;   // (calls_place_dev.h)
 
 using call_base = zkm_keccak_base;   // where a call starts in each list: the sums of the earlier calls' counts
 
@@ -261,8 +242,8 @@ void zkm_keccak_calls_check(zkm_keccak_job& j) {
     if (j.n) rebase_offsets(j);
 }
 size_t zkm_keccak_calls_scratch(const zkm_keccak_job* j, size_t nseg) { return zkm_calls_layout<keccak_kind>(j, nseg, nullptr); }
-void zkm_keccak_calls_launch(zkm_ctx* c, const zkm_keccak_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows) {
-    zkm_calls_queue<keccak_kind>(c, j, nseg, sb, hold, zero_rows);
+void zkm_keccak_calls_launch(zkm_ctx* c, const zkm_keccak_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows, hipStream_t stream) {
+    zkm_calls_queue<keccak_kind>(c, stream ? stream : c->stream, j, nseg, sb, hold, zero_rows);
 }
 
 extern "C" {
@@ -299,10 +280,11 @@ int zkm_keccak_calls_steps(const uint64_t* input_off, const uint64_t* meta, size
         if (sum.row && (!steps_out || !clocks_out)) refuse("null argument");
         if (raw_base >= LIM || raw_base + sum.row > LIM) refuse("raw_base " + dec(raw_base) + ": a RAW index does not fit in 32 bits");
         for (size_t k = 0; k < ncalls; k++) {
-            const uint64_t L = input_off[k + 1] - input_off[k], S = meta[4 * k + 3] / 10;
+            const uint64_t L = input_off[k + 1] - input_off[k];
             for (size_t j = 0; j < place::rows(L); j++) {
-                steps_out[bases[k].row + j] = raw_step(raw_base + bases[k].row + j, place::row_mask(L, j));
-                clocks_out[bases[k].row + j] = place::row_clock(S, L, j);
+                const zkm_row_rec r = place::row_rec(input_off, meta, k, j);
+                steps_out[bases[k].row + j] = raw_step(raw_base + bases[k].row + j, r.mask);
+                clocks_out[bases[k].row + j] = r.clock;
             }
         }
     });

@@ -15,7 +15,7 @@
 // adjacent lanes, every list by adjacent lanes on adjacent words. The row block is zeroed by one memset before the launch, so only the
 // cells a row sets are stored.
 #include "calls_launch.h"
-#include "cpu_steps_dev.h"
+#include "calls_place_dev.h"
 #include "hash_constants_dev.h"
 
 namespace {
@@ -32,22 +32,7 @@ constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256;
 constexpr uint32_t OP_AND = 0, OP_XOR = 2;   // zkm_logic_trace's codes
 
 // ---- the one statement of where things go.  E extend calls, then C compress calls, in every list.
-namespace place {
-constexpr unsigned EXT_ROUNDS = 48, EXT_ROWS = 2 * EXT_ROUNDS, EXT_MEM = 16 * EXT_ROUNDS, EXT_LOGIC = 4 * EXT_ROUNDS;
-constexpr unsigned CMP_ROWS = 11, CMP_MEM = 4 * 8 + 4 * 64, CMP_LOGIC = 12 * 64;
-constexpr unsigned CMP_HX = 0, CMP_W0 = 1, CMP_SPONGE = 9, CMP_WRITE = 10;       // a compress call's rows
-constexpr uint32_t MASK_EXT_READ = 0x1F, MASK_CMP = 0xFF, MASK_SPONGE = 0;       // the channels a row uses
-// rows: extend call e owns 96 e + 2 r (read row of round r) and 96 e + 2 r + 1 (its sponge row); compress call c owns 96 E + 11 c + 0..10
-GL_HD size_t ext_row(size_t e, unsigned r, unsigned sponge) { return EXT_ROWS * e + 2 * r + sponge; }
-GL_HD size_t cmp_row(size_t E, size_t c, unsigned k) { return EXT_ROWS * E + CMP_ROWS * c + k; }
-// clocks, counted from the sponge row's S = timestamp / NUM_CHANNELS: an extend round's read row is one clock before its sponge row at
-// S + 2 r; a compress call's hx row is at S - 9, w row k at S - 8 + k, the sponge row at S, the write row at S + 1
-GL_HD uint64_t ext_clock(uint64_t S, unsigned r, unsigned sponge) { return S + 2 * r - 1 + sponge; }
-GL_HD uint64_t cmp_clock(uint64_t S, unsigned k) { return S - 9 + k; }
-GL_HD uint32_t cmp_mask(unsigned k) { return k == CMP_SPONGE ? MASK_SPONGE : MASK_CMP; }
-GL_HD size_t mem_base(size_t E, size_t e_or_c, bool compress) { return compress ? EXT_MEM * E + CMP_MEM * e_or_c : EXT_MEM * e_or_c; }
-GL_HD size_t logic_base(size_t E, size_t e_or_c, bool compress) { return compress ? EXT_LOGIC * E + CMP_LOGIC * e_or_c : EXT_LOGIC * e_or_c; }
-}  // namespace place
+namespace place = zkm_sha_place;   // (calls_place_dev.h)
 
 struct sha_calls_args {
     const uint32_t* w16;     // E x 16
@@ -262,8 +247,8 @@ void zkm_sha_calls_check(zkm_sha_job& j) {
     j.next = place::EXT_ROUNDS * j.E;
 }
 size_t zkm_sha_calls_scratch(const zkm_sha_job* j, size_t nseg) { return zkm_calls_layout<sha_kind>(j, nseg, nullptr); }
-void zkm_sha_calls_launch(zkm_ctx* c, const zkm_sha_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows) {
-    zkm_calls_queue<sha_kind>(c, j, nseg, sb, hold, zero_rows);
+void zkm_sha_calls_launch(zkm_ctx* c, const zkm_sha_job* j, size_t nseg, char* sb, zkm_calls_hold& hold, bool zero_rows, hipStream_t stream) {
+    zkm_calls_queue<sha_kind>(c, stream ? stream : c->stream, j, nseg, sb, hold, zero_rows);
 }
 
 extern "C" {
@@ -288,20 +273,10 @@ int zkm_sha_calls_steps(const uint64_t* extend_meta, size_t nextend, const uint6
         const size_t rows = place::cmp_row(nextend, ncompress, 0);
         if (rows && (!steps_out || !clocks_out)) refuse("null argument");
         if (raw_base >= LIM || raw_base + rows > LIM) refuse("raw_base " + dec(raw_base) + ": a RAW index does not fit in 32 bits");
-        auto put = [&](size_t j, uint32_t mask, uint64_t clock) {
-            steps_out[j] = raw_step(raw_base + j, mask);
-            clocks_out[j] = clock;
-        };
-        for (size_t e = 0; e < nextend; e++) {
-            const uint64_t S = extend_meta[4 * e + 3] / 10;
-            for (unsigned r = 0; r < place::EXT_ROUNDS; r++) {
-                put(place::ext_row(e, r, 0), place::MASK_EXT_READ, place::ext_clock(S, r, 0));
-                put(place::ext_row(e, r, 1), place::MASK_SPONGE, place::ext_clock(S, r, 1));
-            }
-        }
-        for (size_t c = 0; c < ncompress; c++) {
-            const uint64_t S = compress_meta[8 * c + 3] / 10;
-            for (unsigned k = 0; k < place::CMP_ROWS; k++) put(place::cmp_row(nextend, c, k), place::cmp_mask(k), place::cmp_clock(S, k));
+        for (size_t j = 0; j < rows; j++) {
+            const zkm_row_rec r = place::row_rec(extend_meta, nextend, compress_meta, j);
+            steps_out[j] = raw_step(raw_base + j, r.mask);
+            clocks_out[j] = r.clock;
         }
     });
 }

@@ -591,6 +591,14 @@ struct zkm_staged_steps_ref {
     hipEvent_t done[2] = {nullptr, nullptr};
 };
 bool zkm_staged_steps_find(const void* d_steps, zkm_staged_steps_ref* out);
+// The body of zkm_cpu_steps_stage behind its refusals (throws): the copies, the walk and the verdicts' download queued on the two copy
+// streams, the handle registered.  own_steps: the records are copied into the handle's block wherever they lie; false: records in device
+// memory are walked IN PLACE and handed out as they came (calls_stage.hip: the list it has patched on the device, queued on the first
+// copy stream in front of this call -- the caller keeps that list alive for as long as the handle).  zkm_staged_steps_at: what
+// zkm_staged_steps_find gives, for segment s of a handle the caller holds (a segment without steps is in no registry).
+struct zkm_staged_steps;
+zkm_staged_steps* zkm_steps_stage_queue(zkm_ctx* c, size_t nseg, const zkm_cpu_steps* steps, bool own_steps);
+void zkm_staged_steps_at(zkm_staged_steps* h, size_t s, zkm_staged_steps_ref* out);
 
 // ---- the calls' expansions (sha_calls.hip, keccak_calls.hip, io_calls.hip, insn_rows.hip): K segments served by ONE launch a kind.
 // A job is one segment's calls of one kind: the caller's lists (host or device memory as the kind's entry point says), where the
@@ -600,7 +608,8 @@ bool zkm_staged_steps_find(const void* d_steps, zkm_staged_steps_ref* out);
 //   scratch  the bytes a launch of these jobs puts up: the K descriptors and the lists the host holds (zkm_calls_layout)
 //   launch   queues the uploads into `scratch` and ONE launch for nseg <= ZKM_MAX_SEG checked jobs (zkm_calls_queue).  The SHA and
 //            Keccak kernels store only the cells a row sets: zero_rows queues a memset of each job's rows in front (false: the caller
-//            has zeroed them).
+//            has zeroed them).  `stream`: where everything is queued; null is the context's compute stream (a staged call passes a copy
+//            stream: calls_stage.hip).
 // scratch and launch are the kinds' instantiations of the one launcher in calls_launch.h, where the block's layout and what is in use
 // until the stream has been waited for are stated.  The per-kind entry points are the nseg = 1 case (zkm_calls_one).
 struct zkm_calls_hold;   // the descriptors' host copy (calls_launch.h)
@@ -613,7 +622,7 @@ struct zkm_sha_job {
 };
 void zkm_sha_calls_check(zkm_sha_job& j);
 size_t zkm_sha_calls_scratch(const zkm_sha_job* j, size_t nseg);
-void zkm_sha_calls_launch(zkm_ctx* c, const zkm_sha_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold, bool zero_rows);
+void zkm_sha_calls_launch(zkm_ctx* c, const zkm_sha_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold, bool zero_rows, hipStream_t stream = nullptr);
 struct zkm_keccak_base { uint64_t row, mem, logic, perm; };   // where a call starts in each list: the sums of the earlier calls' counts
 struct zkm_keccak_job {
     const uint8_t* inputs = nullptr; const uint64_t *off = nullptr, *meta = nullptr, *digest_addrs = nullptr; size_t n = 0;
@@ -625,7 +634,7 @@ struct zkm_keccak_job {
 };
 void zkm_keccak_calls_check(zkm_keccak_job& j);
 size_t zkm_keccak_calls_scratch(const zkm_keccak_job* j, size_t nseg);
-void zkm_keccak_calls_launch(zkm_ctx* c, const zkm_keccak_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold, bool zero_rows);
+void zkm_keccak_calls_launch(zkm_ctx* c, const zkm_keccak_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold, bool zero_rows, hipStream_t stream = nullptr);
 struct zkm_io_job {
     const uint32_t* kinds = nullptr; const uint8_t* data = nullptr; const uint64_t *off = nullptr, *meta = nullptr; size_t n = 0;
     uint64_t* rows = nullptr;
@@ -634,7 +643,7 @@ struct zkm_io_job {
 };
 void zkm_io_calls_check(zkm_io_job& j);
 size_t zkm_io_calls_scratch(const zkm_io_job* j, size_t nseg);
-void zkm_io_calls_launch(zkm_ctx* c, const zkm_io_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold);
+void zkm_io_calls_launch(zkm_ctx* c, const zkm_io_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold, hipStream_t stream = nullptr);
 struct zkm_insn_job {
     const zkm_cpu_step* insns = nullptr; const uint64_t* clocks = nullptr; size_t n = 0;
     uint64_t* rows = nullptr;
@@ -644,7 +653,7 @@ struct zkm_insn_job {
 };
 void zkm_insn_rows_check(zkm_insn_job& j);
 size_t zkm_insn_rows_scratch(const zkm_insn_job* j, size_t nseg);
-void zkm_insn_rows_launch(zkm_ctx* c, const zkm_insn_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold);
+void zkm_insn_rows_launch(zkm_ctx* c, const zkm_insn_job* j, size_t nseg, char* scratch, zkm_calls_hold& hold, hipStream_t stream = nullptr);
 
 // ---- the three witness checks (witness_check.hip, lookup_check.hip, ctl_check.hip), each in two parts so that segment_check.hip can put
 // them behind ONE pair of host waits: a part that QUEUES its launches on the context's stream into result words the caller names, and a
