@@ -125,6 +125,12 @@ void zkm_ctx_trim(zkm_ctx* ctx);
  *                               the quad form above -- the crossover tools/image_hash_time.py measured on an MI355X (a level of 8192
  *                               chains: 2.12 ms against 2.32; of 10240: 2.70 against 2.35; profiles/image_hash_time.json).  The words are
  *                               the same in every form
+ *   "pool_stage_ahead"          zkm_pool_prove_segments_calls, read by each worker from its own context (zkm_pool_set_tuning sets all): 1
+ *                               (default) the worker keeps ONE group staged ahead -- it stages the group it claims
+ *                               (zkm_segments_calls_stage), claims and stages its next group before it proves the current one
+ *                               (zkm_prove_segments_ops_steps on the handle's outputs), so the next group's uploads, expansions, placement
+ *                               and walk run behind the current proofs; at most two handles a worker.  0: every group is one expanding
+ *                               call, as zkm_prove_segments_ops_calls.  Proofs, offsets and challenges are the same words either way
  *   "debug_verify_flip"         TEST HOOK, accepted only when the process environment holds ZKM_ENABLE_TEST_HOOKS=1 (an unknown key otherwise):
  *                               under "verify", word `value` (0: off) of the blobs of segment 1 of the call (segment 0 of a call of one) is
  *                               increased by one mod p between proving and verifying (tests/test_gpu_verify.py)
@@ -792,7 +798,7 @@ void zkm_boot_counts(const zkm_boot_image* image, size_t* cpu_rows, size_t* memo
  *   ops   what simulate_cpu pushed only; its CPU rows carry clocks from R + P + 3 on and are transposed behind the bootstrap's rows, its
  *         Poseidon inputs, sponge operations and memory operations follow the bootstrap's.  (R + P + 3) + ops->ncpu_rows must be a power
  *         of two; nmemory may be 0.  The device pointers of zkm_staged_ops_get are accepted as ops; images themselves are not staged,
- *         and the pool takes none.
+ *         and the pool takes them beside a segment's steps and calls (zkm_pool_prove_segments_calls).
  * Heights are those of into_tables on the joined lists; "check_ctls", "verify", waves, memory budget and sizing mode as in the calls
  * without an image, and so are the three host waits whatever K: the sponge chains run on a second stream beside the Memory, Arithmetic
  * and Logic tables, and the digest checks ride on the third wait (sizing mode therefore makes the first two kinds of refusal only).
@@ -869,7 +875,8 @@ int zkm_boot_witness(zkm_ctx* ctx, const zkm_boot_image* image, uint64_t* cpu_ro
  *                          into_tables on the joined lists; "check_ctls", "verify", waves, memory budget and sizing mode as in the
  *                          calls without steps, and so are the three host waits whatever K: the step path adds none.  Every table,
  *                          blob and challenge is word for word what the calls without steps give for the expanded rows and lists.
- * Steps are staged by zkm_cpu_steps_stage (below; zkm_segment_ops_stage takes none), the pool takes none, kinds outside the list go RAW (the thirteen other
+ * Steps are staged by zkm_cpu_steps_stage (below; zkm_segment_ops_stage takes none), the pool takes them as
+ * zkm_segment_calls without calls (zkm_pool_prove_segments_calls), kinds outside the list go RAW (the thirteen other
  * encodings decode() accepts as rows expanded on the device: zkm_insn_rows_* below), and there is no exit
  * kernel.  Profile scopes cpu_steps/lists and cpu_steps/rows (zkm_cpu_witness: cpu_steps/rows_lists). */
 #define ZKM_STEP_BINARY_OP 0
@@ -959,8 +966,10 @@ int zkm_prove_segments_ops_steps(zkm_ctx* ctx, const zkm_stark_config* cfg, size
  * a `steps` pointer in device memory that no handle owns.  Refused on the host before any device work, here and in zkm_cpu_steps_scan:
  * NULL with a nonzero count, nseg = 0, nsteps above 2^28 (the builder's own limit: 8 memory operations a step stay below 2^32), a
  * NULL argument.  A refusal leaves the context usable, its live memory as it was and no handle behind.
- * The pool still takes no steps; images and calls (zkm_segments_calls_expand) are still not staged by THESE entry points:
- * zkm_segments_calls_stage ("Staged calls", below) stages both, on top of this walk.  Profile scope cpu_steps/walk
+ * The pool still takes no steps; images and calls (zkm_segments_calls_expand) are still not staged -- in THIS form and by THESE entry
+ * points, that is: a pool call takes neither a zkm_cpu_steps list nor a handle of zkm_cpu_steps_stage (a handle is its context's).
+ * zkm_segments_calls_stage ("Staged calls", below) stages images and calls, on top of this walk, and the pool takes a step log as a
+ * zkm_segment_calls without calls, which its workers stage themselves (zkm_pool_prove_segments_calls).  Profile scope cpu_steps/walk
  * (zkm_cpu_steps_scan only: the staged walk runs on a copy stream). */
 int zkm_cpu_steps_scan(zkm_ctx* ctx, size_t nseg, const zkm_cpu_steps* steps, size_t* counts_out, uint32_t* const* base_out, char** err);
 int zkm_cpu_steps_stage(zkm_ctx* ctx, size_t nseg, const zkm_cpu_steps* steps, void** out, char** err);
@@ -1012,7 +1021,8 @@ void zkm_staged_steps_free(void* staged);
  * and so not held to these rules: its words go into the rows and lists as they are (no store's address depends on them).
  * Out of scope: the Keccak calls have their own expansion (the next section), and the Poseidon sponge has no syscall in the reference (only
  * the bootstrap produces such operations); the SYSCALL row in front of a
- * call stays whatever the caller logs today; nothing is staged, the pool takes none, and nothing is fused into the segment builder -- the
+ * call stays whatever the caller logs today; nothing is staged by THIS entry point (zkm_segments_calls_stage does, and the pool takes
+ * calls: zkm_pool_prove_segments_calls), and nothing is fused into the segment builder -- the
  * expansion is a call of its own with its own host wait, and its outputs go into zkm_cpu_steps.raw_rows and the lists of zkm_segment_ops,
  * all of which may be device memory. */
 void zkm_sha_calls_counts(size_t nextend, size_t ncompress, size_t* cpu_rows, size_t* memory_ops, size_t* logic_ops, size_t* sha_extend_rows);
@@ -1116,7 +1126,8 @@ int zkm_keccak_calls_witness(zkm_ctx* ctx, const uint8_t* inputs, const uint64_t
  * misaligned output.  A refusal leaves the context usable.  A meta in DEVICE memory is not read by the host and so not held to these
  * rules (no store's address depends on it).
  * Out of scope: the SYSCALL row in front of a call stays whatever the caller logs today; commit and verify READ memory, so the caller
- * supplies the words; nothing is staged, the pool takes none, and nothing is fused into the segment builder. */
+ * supplies the words; nothing is staged by THIS entry point (zkm_segments_calls_stage does, and the pool takes calls:
+ * zkm_pool_prove_segments_calls), and nothing is fused into the segment builder. */
 #define ZKM_IO_HINT_READ 0
 #define ZKM_IO_COMMIT 1
 #define ZKM_IO_VERIFY 2
@@ -1171,7 +1182,8 @@ int zkm_io_calls_witness(zkm_ctx* ctx, const uint32_t* kinds, const uint8_t* dat
  * (result() panics on all three); MFHI, MFLO, MTHI or MTLO whose reads[1] is not 0; a clock of 2^32 or more; raw_base + ninsns that does
  * not fit in 32 bits; a NULL list or output with a nonzero count; records or clocks in device memory; a misaligned output.  A refusal
  * leaves the context usable and its live memory as it was.
- * Out of scope: new step kinds; the records are not staged and the pool takes none; nothing is fused into the segment builder;
+ * Out of scope: new step kinds; the records are not staged by THIS entry point (zkm_segments_calls_stage does, and the pool
+ * takes them: zkm_pool_prove_segments_calls); nothing is fused into the segment builder;
  * keccak_general, Pc and GetContext / SetContext (decode never produces them); the exit kernel. */
 #define ZKM_INSN_LUI 0
 #define ZKM_INSN_MUL 1
@@ -1238,7 +1250,8 @@ int zkm_insn_rows_witness(zkm_ctx* ctx, const zkm_cpu_step* insns, const uint64_
  * unknown I/O kind, an instruction record outside the thirteen, ...); a meta, offset, kind, record or clock list in device memory; a
  * call row whose clock lies outside the step list; two records on one clock; a group of `own` that the calls own; own.cpu_rows; raw_rows
  * in device memory; nseg = 0 or NULL calls.  A refusal leaves the context usable, its live memory as it was, and no handle behind.
- * Out of scope: nothing is fused into the builder (its kernels and its three host waits are untouched), the pool takes none, and THESE
+ * Out of scope: nothing is fused into the builder (its kernels and its three host waits are untouched); the pool takes the same lists
+ * (zkm_pool_prove_segments_calls); THESE
  * entry points place the records into the step list on the host (the builder walks it there): zkm_segments_calls_stage, below, does
  * both on the device, ahead of the call.
  * (The struct and the handle are tagged, not typedef'd: to the header-driven bindings a pointer to either is a plain address.) */
@@ -1302,7 +1315,9 @@ int zkm_prove_segments_ops_calls(zkm_ctx* ctx, const zkm_stark_config* cfg, size
  * host waits; tables, blobs and challenges are word for word those of zkm_segments_tables_calls / zkm_prove_segments_ops_calls on the
  * same input.  They refuse the outputs of a handle of another context, and steps whose nsteps, raw_rows or nraw were changed on the way.
  * Refused by the stage, beside the lists' refusals: NULL `out`, NULL calls or nseg = 0, a segment of more than 2^28 steps, an image
- * whose addrs or values is NULL with a nonzero nwords, a NULL context (last).  A refusal leaves the context usable and its live memory as it was.  The pool takes none.
+ * whose addrs or values is NULL with a nonzero nwords, a NULL context (last).  A refusal leaves the context usable and its live memory as it was.
+ * A handle is its context's, so of a caller's handles the pool takes none: its workers stage their own groups this way
+ * (zkm_pool_prove_segments_calls, "pool_stage_ahead").
  * (The handle is passed as an address, as zkm_cpu_steps_stage's is.) */
 int zkm_segments_calls_stage(zkm_ctx* ctx, size_t nseg, const struct zkm_segment_calls* calls, const zkm_boot_image* images, void** out,
                              char** err);
@@ -1387,6 +1402,22 @@ int zkm_pool_prove_segments_columns(zkm_pool* pool, const zkm_stark_config* cfg,
 int zkm_pool_prove_segments_ops(zkm_pool* pool, const zkm_stark_config* cfg, size_t nseg, size_t max_stack, const zkm_segment_ops* ops,
                                 const uint64_t* const* public_values, const size_t* npublic, uint64_t* const* proofs_out,
                                 size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
+/* The pool takes segments as the emulator records them: the same groups, each a list of zkm_segment_calls -- a step log, the SHA /
+ * Keccak / I/O calls and the instruction records ("Calls", above), behind a boot image where `images` is not NULL (then nseg of them).
+ * A zkm_segment_calls without calls is a plain step log: this is also how the pool takes steps.  Every blob, offset and challenge is
+ * word for word what zkm_prove_segments_ops_calls gives on one context for the same list, whatever the worker count, max_stack or
+ * "pool_stage_ahead" (zkm_ctx_set_tuning), which chooses how a worker serves its groups: staged one group ahead (default), or one
+ * expanding call a group.  proofs_out = NULL sizes (proof_offsets_out as zkm_pool_prove_segments_ops; the groups are served in the
+ * same way, so a refusal reads the same in both calls).  Every list must be host memory unless the pool has one device.
+ * Refused on the host, in this order: a NULL pool, cfg or calls (or proofs_out without ctl_challenges_out, or neither proofs_out nor
+ * proof_offsets_out), nseg = 0, max_stack beyond 32.  A failing group's message names the worker, the device and the group's
+ * segments, then what zkm_prove_segments_ops_calls (one call a group; under this entry point's name) or zkm_segments_calls_stage /
+ * zkm_staged_calls_get (staged ahead) say, with the segment's position in THIS call.  A failure frees every handle a worker holds --
+ * the group staged ahead and never proven too, whose segments stay unassigned -- and leaves every worker context's live memory as it
+ * was and the pool usable.  zkm_pool_last_assignment works after it.  Measured: profiles/pool_calls_time.json. */
+int zkm_pool_prove_segments_calls(zkm_pool* pool, const zkm_stark_config* cfg, size_t nseg, size_t max_stack, const zkm_boot_image* images,
+                                  const struct zkm_segment_calls* calls, const uint64_t* const* public_values, const size_t* npublic,
+                                  uint64_t* const* proofs_out, size_t* proof_offsets_out, uint64_t* const* ctl_challenges_out, char** err);
 /* The groups a pool call of nseg segments is cut into for `workers` workers (a pure function: no pool, no GPU): returns their number and
  * writes the first min(capacity, number) sizes, in segment order.  20 segments, 2 workers, max_stack 4 -> 4, 4, 3, 3, 3, 3. */
 size_t zkm_pool_plan(size_t nseg, size_t workers, size_t max_stack, size_t* group_sizes_out, size_t capacity);

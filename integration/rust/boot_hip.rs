@@ -2,7 +2,8 @@
 //! (the zkm_*_boot calls, include/zkm_hip.h) instead of on the host: `generate_traces` (generation/mod.rs:25-76) then pushes only what
 //! `simulate_cpu` does, with clocks from the bootstrap's row count on (zkm_boot_counts), and the library puts the bootstrap's CPU rows,
 //! memory operations, Poseidon inputs and sponge rows in front.  Bootstrap only: `generate_exit_kernel` has no caller in the reference
-//! (generation/mod.rs:168).  Images are not staged and the pool takes none.
+//! (generation/mod.rs:168).  Images are staged, and taken by the pool, beside a segment's calls
+//! (`calls_hip.rs` `StagedCalls`, `prove_segments_calls_pool_hip`).
 //!
 //! Goes into the zkm-prover crate as `prover/src/boot_hip.rs`, beside `segment_hip.rs`.  The reference items used here are checked by
 //! tests/test_rust_boot_names.py.  NOT COMPILED in the build image (no cargo / rustc there).

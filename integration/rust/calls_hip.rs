@@ -16,7 +16,8 @@
 //! `segment_calls_steps` is the host half alone (the patched step list and the counts), for a caller that sizes its tables first.
 //!   * a caller that records segment k + 1 while segment k is proven stages it instead: `StagedCalls::stage` queues the uploads, the
 //!     expansions, the placement of the records and the walk behind the proofs in flight and returns at once;
-//!     `prove_segments_ops_calls_staged` then proves from device memory with nothing read per row on the calling thread.
+//!     `prove_segments_ops_calls_staged` then proves from device memory with nothing read per row on the calling thread;
+//!   * a caller with several GPUs hands all segments to `prove_segments_calls_pool_hip`: the pool's workers do that staging themselves.
 //!
 //! Goes into the zkm-prover crate as `prover/src/calls_hip.rs`, beside `cpu_steps_hip.rs`.  NOT COMPILED in the build image (no cargo /
 //! rustc there).
@@ -87,6 +88,21 @@ pub fn prove_segments_ops_calls_raw(ctx: *mut zkm_ctx, images: &[zkm_boot_image]
     let raw = raw_array(segments);
     size_then_prove(segments.len(), public_values, config.num_challenges as usize, |pv, npv, proofs, offs, chal, err| unsafe {
         zkm_prove_segments_ops_calls(ctx, config, raw.len(), images_ptr, raw.as_ptr() as *const c_void, pv, npv, proofs, offs, chal, err)
+    })
+}
+
+/// All segments of a program over the pool's contexts, as the recorders logged them: the groups of `prove_segments_multi_hip`
+/// (prove_hip.rs), each proven on its worker's context -- staged one group ahead of the proofs, or expanded in its call
+/// (`zkm_pool_set_tuning(pool, "pool_stage_ahead", ..)`).  `pool` is the `*mut zkm_pool` of a `HipPool`; `images` may be empty.  A step
+/// log without calls is a `SegmentCalls` over empty logs.  Results word for word those of `prove_segments_ops_calls_raw` on one context.
+/// The logs must be host memory unless the pool has one device.
+pub fn prove_segments_calls_pool_hip(pool: *mut zkm_pool, images: &[zkm_boot_image], segments: &[SegmentCalls], config: &zkm_stark_config,
+                                     max_stack: usize, public_values: &[&[u64]]) -> Result<SegmentProofs> {
+    ensure!(images.is_empty() || images.len() == segments.len(), "{} images for {} segments", images.len(), segments.len());
+    let images_ptr = if images.is_empty() { std::ptr::null() } else { images.as_ptr() };
+    let raw = raw_array(segments);
+    size_then_prove(segments.len(), public_values, config.num_challenges as usize, |pv, npv, proofs, offs, chal, err| unsafe {
+        zkm_pool_prove_segments_calls(pool, config, raw.len(), max_stack, images_ptr, raw.as_ptr() as *const c_void, pv, npv, proofs, offs, chal, err)
     })
 }
 

@@ -14,7 +14,8 @@
 //!   * the padding loop of `simulate_cpu` (generation/mod.rs:170-185) calls `step_log.pad(..)` instead of pushing rows.
 //! What the steps cover leaves `Traces::cpu`, and the memory / logic / arithmetic operations of those rows leave `Traces` too: the
 //! library puts them in front of the lists that remain (the precompiles' own operations).  `StagedSteps` stages the next call's steps
-//! behind the current proofs (the walk runs on the device); the pool takes none.
+//! behind the current proofs (the walk runs on the device); the pool takes a step log as a `SegmentCalls` without
+//! calls (`calls_hip.rs` `prove_segments_calls_pool_hip`).
 //!
 //! Goes into the zkm-prover crate as `prover/src/cpu_steps_hip.rs`, beside `segment_hip.rs`.  The reference items used here are checked
 //! by tests/test_rust_cpu_steps_names.py.  NOT COMPILED in the build image (no cargo / rustc there).

@@ -447,6 +447,10 @@ extern "C" {
                                        ops: *const zkm_segment_ops, public_values: *const *const u64, npublic: *const usize,
                                        proofs_out: *const *mut u64, proof_offsets_out: *mut usize, ctl_challenges_out: *const *mut u64,
                                        err: *mut *mut c_char) -> c_int;
+    pub fn zkm_pool_prove_segments_calls(pool: *mut zkm_pool, cfg: *const zkm_stark_config, nseg: usize, max_stack: usize,
+                                         images: *const zkm_boot_image, calls: *const c_void, public_values: *const *const u64,
+                                         npublic: *const usize, proofs_out: *const *mut u64, proof_offsets_out: *mut usize,
+                                         ctl_challenges_out: *const *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_pool_plan(nseg: usize, workers: usize, max_stack: usize, group_sizes_out: *mut usize, capacity: usize) -> usize;
     pub fn zkm_pool_last_assignment(pool: *const zkm_pool, segment: usize, worker_out: *mut usize, group_out: *mut usize) -> c_int;
     pub fn zkm_prove_single_tables(ctx: *mut zkm_ctx, table_id: c_int, cfg: *const zkm_stark_config, nproofs: usize, traces: *const *const u64,

@@ -1139,6 +1139,33 @@ class Pool:
         _check(self.L.zkm_pool_prove_segments_ops(self.h, C.byref(cfg), m.K, max_stack, m.st, m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
         return m.results()
 
+    def prove_segments_calls(self, calls_list, images=None, public_values=None, max_stack=0, cfg=None, sizing=False):
+        """zkm_pool_prove_segments_calls: one SegmentCalls per segment as Context.prove_segments_ops_calls takes them (HOST lists unless the
+        pool has one device), behind one BootImage each where images is given.  Each worker keeps its next group staged behind the current
+        proofs ("pool_stage_ahead", the default) or expands each group in its call.  Returns (proofs, ctl_challenges, offsets) per segment;
+        sizing: the sizing call alone, the offsets per segment."""
+        cfg = cfg or self.standard_config()
+        m, err = _marshal_ops([q.own for q in calls_list], public_values, cfg, images), C.c_char_p()
+        im = m.im if images is not None else None
+        arr = Context._calls_array(calls_list)
+        fn = self.L.zkm_pool_prove_segments_calls
+        _check(fn(self.h, C.byref(cfg), m.K, max_stack, im, C.addressof(arr), m.pv, m.npv, None, m.offs, None, C.byref(err)), err)
+        m.alloc()
+        if sizing:
+            return m.sizes
+        _check(fn(self.h, C.byref(cfg), m.K, max_stack, im, C.addressof(arr), m.pv, m.npv, m.po, m.offs, m.co, C.byref(err)), err)
+        return m.results()
+
+    def memory(self, worker):
+        """(live bytes, cached bytes) of worker w's context (zkm_pool_context, zkm_ctx_memory)."""
+        live, cached = C.c_size_t(), C.c_size_t()
+        self.L.zkm_ctx_memory(self.L.zkm_pool_context(self.h, worker), C.byref(live), C.byref(cached))
+        return live.value, cached.value
+
+    def resident_bytes(self, worker):
+        """Bytes of the tables worker w's context keeps for reuse (zkm_ctx_resident_bytes): part of its live bytes."""
+        return self.L.zkm_ctx_resident_bytes(self.L.zkm_pool_context(self.h, worker))
+
     def last_assignment(self, segment):
         """(worker, group) that proved `segment` in the last call."""
         w, g = C.c_size_t(), C.c_size_t()

@@ -271,7 +271,8 @@ void expand_group(zkm_ctx* c, const zkm_segment_calls* calls, zkm_expanded_calls
 }
 
 // the body of zkm_segments_calls_expand (throws; `what` names the entry point in a refusal)
-std::unique_ptr<zkm_expanded_calls> expand(const char* what, zkm_ctx* c, size_t nseg, const zkm_segment_calls* calls) {
+// seg_base: position of segment 0 in the caller's larger call (the pool's groups; refusals only)
+std::unique_ptr<zkm_expanded_calls> expand(const char* what, zkm_ctx* c, size_t nseg, const zkm_segment_calls* calls, size_t seg_base = 0) {
     if (nseg == 0 || !calls) throw std::runtime_error(std::string(what) + ": null argument or no segment");
     std::unique_ptr<zkm_expanded_calls> h(new zkm_expanded_calls);
     h->c = c;
@@ -282,7 +283,7 @@ std::unique_ptr<zkm_expanded_calls> expand(const char* what, zkm_ctx* c, size_t 
         try {
             plan_segment(calls[s], h->segs[s], P[s]);
         } catch (const std::exception& e) {
-            throw std::runtime_error(std::string(what) + ": segment " + dec(s) + ": " + e.what());
+            throw std::runtime_error(std::string(what) + ": segment " + dec(seg_base + s) + ": " + e.what());
         }
     }
     if (!c) throw std::runtime_error(std::string(what) + ": null argument");
@@ -361,3 +362,17 @@ int zkm_prove_segments_ops_calls(zkm_ctx* c, const zkm_stark_config* cfg, size_t
 }
 
 }  // extern "C"
+
+// (zkm_internal.h: a group of the pool's, expanded in the call -- the same three steps, every refusal under `what` and at seg_base + s)
+int zkm_prove_segments_ops_calls_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
+                                       const zkm_segment_calls* calls, const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs,
+                                       size_t* offsets_out, uint64_t* const* challenges, char** err, size_t seg_base) {
+    return zkm_api(what, err, [&] {
+        const std::unique_ptr<zkm_expanded_calls> h = expand(what, c, nseg, calls, seg_base);
+        std::vector<zkm_cpu_steps> steps;
+        std::vector<zkm_segment_ops> ops;
+        outputs(*h, &steps, &ops);
+        return zkm_prove_segments_ops_steps_entry(what, c, cfg, nseg, images, steps.data(), ops.data(), pub, npub, proofs, offsets_out, challenges, err,
+                                                  seg_base);
+    });
+}

@@ -219,7 +219,9 @@ void resolve(zkm_staged_calls* h) {
     h->resolved = true;
 }
 
-std::unique_ptr<zkm_staged_calls> stage(const std::string& what, zkm_ctx* c, size_t nseg, const zkm_segment_calls* calls, const zkm_boot_image* images) {
+// seg_base: position of segment 0 in the caller's larger call (the pool's groups; refusals only)
+std::unique_ptr<zkm_staged_calls> stage(const std::string& what, zkm_ctx* c, size_t nseg, const zkm_segment_calls* calls, const zkm_boot_image* images,
+                                        size_t seg_base = 0) {
     if (nseg == 0 || !calls) throw std::runtime_error(what + ": null argument or no segment");
     std::unique_ptr<zkm_staged_calls> h(new zkm_staged_calls);
     h->ctx = c;
@@ -237,7 +239,7 @@ std::unique_ptr<zkm_staged_calls> stage(const std::string& what, zkm_ctx* c, siz
             if (images && images[s].nwords && (!images[s].addrs || !images[s].values))
                 throw std::runtime_error("image: NULL addrs or values with a count of " + dec(images[s].nwords));
         } catch (const std::exception& e) {
-            throw std::runtime_error(what + ": segment " + dec(s) + ": " + e.what());
+            throw std::runtime_error(what + ": segment " + dec(seg_base + s) + ": " + e.what());
         }
     }
     if (!c) throw std::runtime_error(what + ": null argument");
@@ -419,11 +421,7 @@ std::unique_ptr<zkm_staged_calls> stage(const std::string& what, zkm_ctx* c, siz
 extern "C" {
 
 int zkm_segments_calls_stage(zkm_ctx* c, size_t nseg, const zkm_segment_calls* calls, const zkm_boot_image* images, void** out, char** err) {
-    return zkm_api("zkm_segments_calls_stage", err, [&] {
-        if (!out) throw std::runtime_error("zkm_segments_calls_stage: null argument");
-        *out = nullptr;
-        *out = stage("zkm_segments_calls_stage", c, nseg, calls, images).release();
-    });
+    return zkm_segments_calls_stage_entry(c, nseg, calls, images, out, err, 0);
 }
 
 int zkm_staged_calls_ready(void* staged, int wait) {
@@ -431,28 +429,45 @@ int zkm_staged_calls_ready(void* staged, int wait) {
     return h ? zkm_staged_steps_ready(h->steps, wait) : 1;
 }
 
+// the body of zkm_staged_calls_get (throws); a refusal names segment seg_base + segment
+static void staged_get(void* staged, size_t segment, zkm_cpu_steps* steps_out, zkm_segment_ops* ops_out, zkm_boot_image* image_out, size_t seg_base) {
+    const std::string what = "zkm_staged_calls_get";
+    zkm_staged_calls* h = (zkm_staged_calls*)staged;
+    if (!h || !steps_out || !ops_out) throw std::runtime_error(what + ": null argument");
+    if (segment >= h->segs.size()) throw std::runtime_error(what + ": no segment " + dec(segment) + ": the handle holds " + dec(h->segs.size()));
+    ZKM_HIP_CHECK(hipSetDevice(h->ctx->device));
+    resolve(h);
+    const zkm_staged_calls::seg& g = h->segs[segment];
+    if (!g.refusal.empty()) throw std::runtime_error(what + ": segment " + dec(seg_base + segment) + ": " + g.refusal);
+    if (!h->joined) {
+        zkm_staged_steps_ref ref;
+        zkm_staged_steps_at(h->steps, segment, &ref);
+        for (const hipEvent_t e : ref.done) ZKM_HIP_CHECK(hipStreamWaitEvent(h->ctx->stream, e, 0));
+        h->joined = true;
+    }
+    *steps_out = g.st;
+    *ops_out = g.ops;
+    if (image_out) *image_out = g.image;
+}
+
 int zkm_staged_calls_get(void* staged, size_t segment, zkm_cpu_steps* steps_out, zkm_segment_ops* ops_out, zkm_boot_image* image_out, char** err) {
-    return zkm_api("zkm_staged_calls_get", err, [&] {
-        const std::string what = "zkm_staged_calls_get";
-        zkm_staged_calls* h = (zkm_staged_calls*)staged;
-        if (!h || !steps_out || !ops_out) throw std::runtime_error(what + ": null argument");
-        if (segment >= h->segs.size()) throw std::runtime_error(what + ": no segment " + dec(segment) + ": the handle holds " + dec(h->segs.size()));
-        ZKM_HIP_CHECK(hipSetDevice(h->ctx->device));
-        resolve(h);
-        const zkm_staged_calls::seg& g = h->segs[segment];
-        if (!g.refusal.empty()) throw std::runtime_error(what + ": segment " + dec(segment) + ": " + g.refusal);
-        if (!h->joined) {
-            zkm_staged_steps_ref ref;
-            zkm_staged_steps_at(h->steps, segment, &ref);
-            for (const hipEvent_t e : ref.done) ZKM_HIP_CHECK(hipStreamWaitEvent(h->ctx->stream, e, 0));
-            h->joined = true;
-        }
-        *steps_out = g.st;
-        *ops_out = g.ops;
-        if (image_out) *image_out = g.image;
-    });
+    return zkm_staged_calls_get_entry(staged, segment, steps_out, ops_out, image_out, err, 0);
 }
 
 void zkm_staged_calls_free(void* staged) { delete (zkm_staged_calls*)staged; }
 
 }  // extern "C"
+
+// (zkm_internal.h: the pool's workers stage their groups under these entry points' own names)
+int zkm_segments_calls_stage_entry(zkm_ctx* c, size_t nseg, const zkm_segment_calls* calls, const zkm_boot_image* images, void** out, char** err,
+                                   size_t seg_base) {
+    return zkm_api("zkm_segments_calls_stage", err, [&] {
+        if (!out) throw std::runtime_error("zkm_segments_calls_stage: null argument");
+        *out = nullptr;
+        *out = stage("zkm_segments_calls_stage", c, nseg, calls, images, seg_base).release();
+    });
+}
+int zkm_staged_calls_get_entry(void* staged, size_t segment, zkm_cpu_steps* steps_out, zkm_segment_ops* ops_out, zkm_boot_image* image_out, char** err,
+                               size_t seg_base) {
+    return zkm_api("zkm_staged_calls_get", err, [&] { staged_get(staged, segment, steps_out, ops_out, image_out, seg_base); });
+}

@@ -557,6 +557,7 @@ int zkm_ctx_set_tuning(zkm_ctx* c, const char* key, uint64_t value, char** err) 
             else if (k == "verify") x->verify = value ? 1 : 0;
             else if (k == "boot_chain_quad") x->boot_chain_quad = value ? 1 : 0;
             else if (k == "image_hash_form") x->image_hash_form = value > 2 ? 0 : (int)value;
+            else if (k == "pool_stage_ahead") x->pool_stage_ahead = value ? 1 : 0;
             else if (k == "debug_verify_flip") {
                 // test hook, as debug_fail_allocs below
                 const char* hooks = getenv("ZKM_ENABLE_TEST_HOOKS");

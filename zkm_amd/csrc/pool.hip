@@ -7,6 +7,8 @@
 // each device: every entry point of the library selects its context's device itself (hipSetDevice(c->device), core.hip), so the
 // workers need nothing but their own context.  bench.py's process-per-GPU harness (zkm_amd/dist.py) stays what the scaling bench
 // launches; this is what a Rust caller binds (integration/rust/prove_hip.rs prove_segments_multi_hip).
+// A group is finished tables, raw operations, or segments as the emulator records them (zkm_pool_prove_segments_calls, at the end: the
+// one entry whose workers keep their next group staged behind the current proofs).
 //
 // Host only: no kernel lives here.
 #include <exception>
@@ -40,46 +42,55 @@ static std::vector<std::pair<size_t, size_t>> pool_groups(size_t nseg, size_t wo
     return g;
 }
 
-// (throws: the entry points below run it inside the error boundary)
-// run_group(context, first segment, count, err): ONE call of the entry point that proves the group on that worker's context
-template <class G>
-static void pool_run(const char* what, zkm_pool* p, size_t nseg, size_t max_stack, G&& run_group) {
-    if (max_stack == 0) max_stack = 8;
-    if (max_stack > ZKM_MAX_SEG) throw std::runtime_error(std::string(what) + ": max_stack beyond " + std::to_string(ZKM_MAX_SEG));
-    const size_t W = p->ctxs.size();
-    const auto groups = pool_groups(nseg, W, max_stack);
-    p->last_worker.assign(nseg, ~(size_t)0);
-    p->last_group.assign(nseg, ~(size_t)0);
-    if (groups.empty()) return;
+// The queue of one call: the groups, who takes the next one, the first failure (which stops the queue) and the record of who proved what.
+struct pool_queue {
+    zkm_pool* p;
+    const std::vector<std::pair<size_t, size_t>> groups;
     std::mutex mu;
     size_t next = 0;
     std::string first_error;
     bool failed = false;
-    auto worker = [&](size_t w) {
-        for (;;) {
-            size_t g;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (failed || next >= groups.size()) return;
-                g = next++;
-            }
-            const size_t s0 = groups[g].first, k = groups[g].second;
-            char* e = nullptr;   // (the entry point is noexcept: nothing unwinds out of a worker thread)
-            const int rc = run_group(p->ctxs[w], s0, k, &e);
-            std::lock_guard<std::mutex> lk(mu);
-            if (rc != 0) {
-                if (!failed)
-                    first_error = "worker " + std::to_string(w) + " (device " + std::to_string(p->devices[w]) + "), segments " + std::to_string(s0) + ".." +
-                                  std::to_string(s0 + k - 1) + ": " + (e ? e : "unknown error");
-                failed = true;
-            } else {
-                for (size_t s = s0; s < s0 + k; s++) { p->last_worker[s] = w; p->last_group[s] = g; }
-            }
-            free(e);
+    pool_queue(zkm_pool* pool, std::vector<std::pair<size_t, size_t>> g) : p(pool), groups(std::move(g)) {}
+    bool claim(size_t* g) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (failed || next >= groups.size()) return false;
+        *g = next++;
+        return true;
+    }
+    bool stopped() {
+        std::lock_guard<std::mutex> lk(mu);
+        return failed;
+    }
+    // worker w is through with group g: proven (rc == 0) or refused with the entry point's message e, which is freed here
+    void done(size_t w, size_t g, int rc, char* e) {
+        const size_t s0 = groups[g].first, k = groups[g].second;
+        std::lock_guard<std::mutex> lk(mu);
+        if (rc != 0) {
+            if (!failed)
+                first_error = "worker " + std::to_string(w) + " (device " + std::to_string(p->devices[w]) + "), segments " + std::to_string(s0) + ".." +
+                              std::to_string(s0 + k - 1) + ": " + (e ? e : "unknown error");
+            failed = true;
+        } else {
+            for (size_t s = s0; s < s0 + k; s++) { p->last_worker[s] = w; p->last_group[s] = g; }
         }
-    };
+        free(e);
+    }
+};
+
+// (throws: the entry points below run it inside the error boundary)
+// serve(worker, queue): what one worker thread does until the queue is empty or stopped; nothing unwinds out of it
+template <class S>
+static void pool_serve(const char* what, zkm_pool* p, size_t nseg, size_t max_stack, S&& serve) {
+    if (max_stack == 0) max_stack = 8;
+    if (max_stack > ZKM_MAX_SEG) throw std::runtime_error(std::string(what) + ": max_stack beyond " + std::to_string(ZKM_MAX_SEG));
+    const size_t W = p->ctxs.size();
+    pool_queue q(p, pool_groups(nseg, W, max_stack));
+    p->last_worker.assign(nseg, ~(size_t)0);
+    p->last_group.assign(nseg, ~(size_t)0);
+    if (q.groups.empty()) return;
+    auto worker = [&](size_t w) { serve(w, q); };
     // one thread per context that has work (a thread start is ~50 us; a group is milliseconds to seconds).  The calling thread is worker 0.
-    const size_t nthreads = std::min(W, groups.size());
+    const size_t nthreads = std::min(W, q.groups.size());
     std::vector<std::thread> th;
     try {
         for (size_t w = 1; w < nthreads; w++) th.emplace_back(worker, w);
@@ -88,7 +99,19 @@ static void pool_run(const char* what, zkm_pool* p, size_t nseg, size_t max_stac
     }
     worker(0);
     for (auto& t : th) t.join();
-    if (failed) throw std::runtime_error(first_error);
+    if (q.failed) throw std::runtime_error(q.first_error);
+}
+
+// run_group(context, first segment, count, err): ONE call of the entry point that proves the group on that worker's context
+template <class G>
+static void pool_run(const char* what, zkm_pool* p, size_t nseg, size_t max_stack, G&& run_group) {
+    pool_serve(what, p, nseg, max_stack, [&](size_t w, pool_queue& q) {
+        for (size_t g; q.claim(&g);) {
+            char* e = nullptr;   // (the entry point is noexcept: nothing unwinds out of a worker thread)
+            const int rc = run_group(p->ctxs[w], q.groups[g].first, q.groups[g].second, &e);
+            q.done(w, g, rc, e);
+        }
+    });
 }
 
 static void pool_prove(const char* what, zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack,
@@ -178,6 +201,77 @@ int zkm_pool_prove_segments_ops(zkm_pool* p, const zkm_stark_config* cfg, size_t
             return zkm_prove_segments_ops_entry(what, c, cfg, k, ops + s0, pub ? pub + s0 : nullptr, npub ? npub + s0 : nullptr,
                                                 proofs ? proofs + s0 : nullptr, offsets_out ? offsets_out + (ZKM_NUM_TABLES + 1) * s0 : nullptr,
                                                 challenges ? challenges + s0 : nullptr, e, s0);
+        });
+    });
+}
+
+// The groups as above, each a segment list as the emulator records it.  A worker whose context has "pool_stage_ahead" (the default) keeps
+// ONE group staged ahead: it stages the group it claims (zkm_segments_calls_stage on its own context), claims and stages its next group
+// BEFORE it proves the current one -- so the next group's uploads, expansions, placement and walk run on the copy streams behind the
+// current proofs -- proves on the handle's outputs (zkm_prove_segments_ops_steps), frees the handle and moves on: two handles at most.
+// Otherwise a group is ONE expanding call (the body of zkm_prove_segments_ops_calls).  The sizing mode serves its groups the same way, so
+// a refusal reads the same in the sizing call and in the proving call.
+int zkm_pool_prove_segments_calls(zkm_pool* p, const zkm_stark_config* cfg, size_t nseg, size_t max_stack, const zkm_boot_image* images,
+                                  const zkm_segment_calls* calls, const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs,
+                                  size_t* offsets_out, uint64_t* const* challenges, char** err) {
+    const char* what = "zkm_pool_prove_segments_calls";
+    return zkm_api(what, err, [&] {
+        if (!p || !cfg || !calls || (proofs ? !challenges : !offsets_out)) throw std::runtime_error(std::string(what) + ": null argument");
+        if (nseg == 0) throw std::runtime_error(std::string(what) + ": no segments");
+        struct staged_group {
+            size_t g = 0;
+            std::unique_ptr<void, void (*)(void*)> h{nullptr, zkm_staged_calls_free};
+        };
+        pool_serve(what, p, nseg, max_stack, [&](size_t w, pool_queue& q) {
+            zkm_ctx* c = p->ctxs[w];
+            auto at = [&](size_t s0) { return offsets_out ? offsets_out + (ZKM_NUM_TABLES + 1) * s0 : nullptr; };
+            if (!c->pool_stage_ahead) {
+                for (size_t g; q.claim(&g);) {
+                    const size_t s0 = q.groups[g].first, k = q.groups[g].second;
+                    char* e = nullptr;
+                    const int rc = zkm_prove_segments_ops_calls_entry(what, c, cfg, k, images ? images + s0 : nullptr, calls + s0, pub ? pub + s0 : nullptr,
+                                                                      npub ? npub + s0 : nullptr, proofs ? proofs + s0 : nullptr, at(s0),
+                                                                      challenges ? challenges + s0 : nullptr, &e, s0);
+                    q.done(w, g, rc, e);
+                }
+                return;
+            }
+            // claim the next group and queue its staging; false when the queue is empty or stopped, or the stage refuses (reported)
+            auto stage_next = [&](staged_group& out) {
+                if (!q.claim(&out.g)) return false;
+                const size_t s0 = q.groups[out.g].first, k = q.groups[out.g].second;
+                char* e = nullptr;
+                void* h = nullptr;
+                const int rc = zkm_segments_calls_stage_entry(c, k, calls + s0, images ? images + s0 : nullptr, &h, &e, s0);
+                out.h.reset(h);
+                if (rc != 0) q.done(w, out.g, rc, e);
+                return rc == 0;
+            };
+            // the handle's outputs, proven: steps, operations and images all come from the handle
+            auto prove = [&](const staged_group& cur, char** e) {
+                const size_t s0 = q.groups[cur.g].first, k = q.groups[cur.g].second;
+                std::vector<zkm_cpu_steps> st(k);
+                std::vector<zkm_segment_ops> ops(k);
+                std::vector<zkm_boot_image> im(images ? k : 0);
+                for (size_t s = 0; s < k; s++)
+                    if (const int rc = zkm_staged_calls_get_entry(cur.h.get(), s, &st[s], &ops[s], images ? &im[s] : nullptr, e, s0)) return rc;
+                return zkm_prove_segments_ops_steps_entry(what, c, cfg, k, images ? im.data() : nullptr, st.data(), ops.data(), pub ? pub + s0 : nullptr,
+                                                          npub ? npub + s0 : nullptr, proofs ? proofs + s0 : nullptr, at(s0),
+                                                          challenges ? challenges + s0 : nullptr, e, s0);
+            };
+            // (the handles are freed on every path out of here: a group staged ahead and never proven stays unassigned)
+            staged_group cur, ahead;
+            for (bool have = stage_next(cur); have;) {
+                const bool more = stage_next(ahead);
+                if (q.stopped()) return;
+                char* e = nullptr;
+                const int rc = zkm_api(what, &e, [&] { return prove(cur, &e); });   // (the vectors may throw: nothing unwinds out of a worker thread)
+                cur.h.reset();   // (waits for the handle's events; the proofs that read its blocks have ended)
+                q.done(w, cur.g, rc, e);
+                if (rc != 0) return;
+                std::swap(cur, ahead);
+                have = more;
+            }
         });
     });
 }

@@ -801,6 +801,14 @@ int zkm_prove_segments_ops_steps(zkm_ctx* c, const zkm_stark_config* cfg, size_t
     if (!c) return steps_without_context("zkm_prove_segments_ops_steps", cfg, nseg, images, steps, ops, err);
     return prove_segments_ops("zkm_prove_segments_ops_steps", c, cfg, nseg, images, ops, pub, npub, proofs, offsets_out, challenges, err, 0, steps);
 }
+// (zkm_internal.h: the pool's workers, on the outputs of a staged or expanded group)
+extern "C++" int zkm_prove_segments_ops_steps_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
+                                                    const zkm_cpu_steps* steps, const zkm_segment_ops* ops, const uint64_t* const* pub,
+                                                    const size_t* npub, uint64_t* const* proofs, size_t* offsets_out, uint64_t* const* challenges,
+                                                    char** err, size_t seg_base) {
+    if (!steps) return zkm_fail(err, what, ": null argument");
+    return prove_segments_ops(what, c, cfg, nseg, images, ops, pub, npub, proofs, offsets_out, challenges, err, seg_base, steps);
+}
 
 // the body of zkm_segment_tables[_boot] (image: or null)
 static int segment_tables(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, const zkm_boot_image* image, const zkm_segment_ops* ops,

@@ -97,7 +97,8 @@ struct zkm_ctx {
     int aux_pipeline = 1;               // segments of short tables: lanes build later tables' auxiliary commitments behind the proofs      } zkm_ctx_set_tuning
     size_t commit_lanes = ZKM_COMMIT_LANES;   // trace / auxiliary commitments of one segment in flight (this context + lanes)   } zkm_ctx_set_tuning
     size_t segments_memory_budget = 0;  // bytes one wave of a zkm_prove_segments call may hold (0: 80 % of cached + free HBM, shared out over the contexts of the process that are inside such a call)   } zkm_ctx_set_tuning
-    size_t last_stack = 0;              // segments of the previous prove_with_traces call of this context (0: none yet)
+    int pool_stage_ahead = 1;           // a pool worker of zkm_pool_prove_segments_calls keeps its next group staged behind the current proofs (0: each group one expanding call)   } zkm_ctx_set_tuning
+    size_t last_stack = 0;             // segments of the previous prove_with_traces call of this context (0: none yet)
     size_t prev_stack = 0;              // ... and the other height whose blocks may still be cached (two heights are kept: ctl.hip prove_segments_impl)
     size_t max_stack = ZKM_MAX_SEG;     // segments of one lock-step group (zkm_prove_segments): 1 .. ZKM_MAX_SEG               } zkm_ctx_set_tuning
     int leaf_mfma = ZKM_LEAF_MFMA_DEFAULT;   // one-lane-per-leaf hashing: MDS layers of the full rounds on the matrix core (poseidon_mfma_dev.h)   } zkm_ctx_set_tuning
@@ -765,3 +766,19 @@ double zkm_segment_footprint(const zkm_stark_config* cfg, const unsigned log_n[Z
 extern "C" int zkm_prove_segments_ops_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_segment_ops* ops,
                                             const uint64_t* const* pub, const size_t* npub, uint64_t* const* proofs, size_t* offsets_out,
                                             uint64_t* const* challenges, char** err, size_t seg_base);
+// The pool's workers for a segment as the emulator records it (zkm_pool_prove_segments_calls), seg_base as above.  C++ linkage: these
+// are no part of the library's exported names.
+// segment_ops.hip: the body of zkm_prove_segments_ops_steps with a context (images: or null)
+int zkm_prove_segments_ops_steps_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
+                                       const zkm_cpu_steps* steps, const zkm_segment_ops* ops, const uint64_t* const* pub, const size_t* npub,
+                                       uint64_t* const* proofs, size_t* offsets_out, uint64_t* const* challenges, char** err, size_t seg_base);
+// calls_entry.hip: the body of zkm_prove_segments_ops_calls
+int zkm_prove_segments_ops_calls_entry(const char* what, zkm_ctx* c, const zkm_stark_config* cfg, size_t nseg, const zkm_boot_image* images,
+                                       const struct zkm_segment_calls* calls, const uint64_t* const* pub, const size_t* npub,
+                                       uint64_t* const* proofs, size_t* offsets_out, uint64_t* const* challenges, char** err, size_t seg_base);
+// calls_stage.hip: the bodies of zkm_segments_calls_stage and zkm_staged_calls_get, under their own names; a refusal names segment
+// seg_base + s
+int zkm_segments_calls_stage_entry(zkm_ctx* c, size_t nseg, const struct zkm_segment_calls* calls, const zkm_boot_image* images, void** out,
+                                   char** err, size_t seg_base);
+int zkm_staged_calls_get_entry(void* staged, size_t segment, zkm_cpu_steps* steps_out, zkm_segment_ops* ops_out, zkm_boot_image* image_out,
+                               char** err, size_t seg_base);
