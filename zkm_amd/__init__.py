@@ -528,13 +528,14 @@ class DeviceBuffer:
             self.ptr = None
 
 
-class StagedTrace:
-    """zkm_staged: a host matrix on its way into HBM behind the context's current work (include/zkm_hip.h "staged traces").  Pass it
-    wherever a prove call of the SAME context takes a trace; free() after that call has returned.  A handle that is dropped, leaves a
-    `with` block or outlives Context.close() is freed then (free() after close() is a no-op: the context freed it)."""
+class _StagedHandle:
+    """The lifetime every handle of input put into HBM shares (StagedTrace, StagedOps, StagedSteps, ExpandedCalls, StagedCalls): the
+    context keeps track of it (Context.close() frees what is outstanding), and it is freed when dropped, at the end of a `with` block
+    or by free(), once.  A subclass names the C function that frees the handle: _free."""
+    _free = None
 
-    def __init__(self, ctx, handle, words):
-        self.ctx, self.h, self.words = ctx, handle, words
+    def __init__(self, ctx, handle):
+        self.ctx, self.h = ctx, handle
         ctx._staged.add(self)
 
     def __enter__(self):
@@ -549,6 +550,39 @@ class StagedTrace:
         except Exception:
             pass
 
+    def free(self):
+        """Waits for the queued work and returns the handle's blocks (see include/zkm_hip.h); the host source may go after this.  A no-op on
+        a handle that has been freed, by the caller or by Context.close()."""
+        if self.h:
+            h, self.h = self.h, None
+            self.ctx._staged.discard(self)
+            if self.ctx.h:
+                getattr(self.ctx.L, self._free)(h)
+
+
+class _InFlightHandle(_StagedHandle):
+    """... of a handle whose work may still be in flight when the call that made it returns: ready() asks the C function _ready."""
+    _ready = None
+
+    def ready(self, wait=False):
+        """Has the queued work ended?  wait=True blocks until it has."""
+        r = getattr(self.ctx.L, self._ready)(self.h, 1 if wait else 0)
+        if r < 0:
+            raise ZkmError("%s: runtime error" % self._ready)
+        return bool(r)
+
+
+class StagedTrace(_InFlightHandle):
+    """zkm_staged: a host matrix on its way into HBM behind the context's current work (include/zkm_hip.h "staged traces").  Pass it
+    wherever a prove call of the SAME context takes a trace; free() after that call has returned.  A handle that is dropped, leaves a
+    `with` block or outlives Context.close() is freed then (free() after close() is a no-op: the context freed it)."""
+
+    _free, _ready = "zkm_staged_free", "zkm_staged_ready"
+
+    def __init__(self, ctx, handle, words):
+        _StagedHandle.__init__(self, ctx, handle)
+        self.words = words
+
     @property
     def ptr(self):
         p = self.ctx.L.zkm_staged_ptr(self.h)
@@ -562,20 +596,6 @@ class StagedTrace:
         if self.ctx.L.zkm_staged_segment_ptrs(self.h, out) != 0:
             raise ZkmError("zkm_staged_segment_ptrs: not a staged segment, or the upload could not be ordered before the compute stream")
         return [int(out[t]) for t in range(12)]
-
-    def ready(self, wait=False):
-        r = self.ctx.L.zkm_staged_ready(self.h, 1 if wait else 0)
-        if r < 0:
-            raise ZkmError("zkm_staged_ready: runtime error")
-        return bool(r)
-
-    def free(self):
-        """Waits for the upload and returns the block (see include/zkm_hip.h); the host matrix may go after this."""
-        if self.h:
-            h, self.h = self.h, None
-            self.ctx._staged.discard(self)
-            if self.ctx.h:
-                self.ctx.L.zkm_staged_free(h)
 
 
 def _data_ptr(x):
@@ -736,26 +756,12 @@ def boot_image_from_pages(dirty, plan, hash_pages, root, image_id, entry, check=
     return BootImage(addrs.reshape(-1), words.reshape(-1), root, image_id, entry, check=check)
 
 
-class StagedOps:
+class StagedOps(_InFlightHandle):
     """zkm_staged_ops: a segment's raw operations on their way into HBM behind the context's current work (include/zkm_hip.h "Staged
     operations").  ops() is the same segment with device pointers, for segment[s]_tables / prove_segment[s]_ops of the SAME context;
     free() after that call has returned.  Freed like a StagedTrace when dropped, at the end of a `with` block or by Context.close()."""
 
-    def __init__(self, ctx, handle):
-        self.ctx, self.h = ctx, handle
-        ctx._staged.add(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    _free, _ready = "zkm_staged_ops_free", "zkm_staged_ops_ready"
 
     def ops(self):
         """A SegmentOps of device pointers, ordered behind the upload on the device (no host wait)."""
@@ -765,20 +771,6 @@ class StagedOps:
         out = SegmentOps.__new__(SegmentOps)
         out.lists, out.counts, out._staged_struct, out._owner = {}, {}, st, self
         return out
-
-    def ready(self, wait=False):
-        r = self.ctx.L.zkm_staged_ops_ready(self.h, 1 if wait else 0)
-        if r < 0:
-            raise ZkmError("zkm_staged_ops_ready: runtime error")
-        return bool(r)
-
-    def free(self):
-        """Waits for the upload and returns the block."""
-        if self.h:
-            h, self.h = self.h, None
-            self.ctx._staged.discard(self)
-            if self.ctx.h:
-                self.ctx.L.zkm_staged_ops_free(h)
 
 
 class _StagedStepsSegment:
@@ -794,28 +786,18 @@ class _StagedStepsSegment:
         return self.counts_
 
 
-class StagedSteps:
+class StagedSteps(_InFlightHandle):
     """The handle of zkm_cpu_steps_stage: K segments' step logs on their way into HBM behind the context's current work, walked on the
     device behind the upload (include/zkm_hip.h "Staged steps").  get(s) is what segments_tables_steps / prove_segments_ops_steps of
     the SAME context take for segment s; free() after those calls have returned.  The CpuSteps it was staged from are kept alive by
     the handle, and their arrays must stay as they are until ready() is true.  Freed when dropped, at the end of a `with` block or by
     Context.close()."""
 
+    _free, _ready = "zkm_staged_steps_free", "zkm_staged_steps_ready"
+
     def __init__(self, ctx, handle, steps_list):
-        self.ctx, self.h, self.steps_list = ctx, handle, list(steps_list)
-        ctx._staged.add(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        _StagedHandle.__init__(self, ctx, handle)
+        self.steps_list = list(steps_list)
 
     def __len__(self):
         return len(self.steps_list)
@@ -828,20 +810,6 @@ class StagedSteps:
         st, n, err = CpuStepsStruct(), [C.c_size_t() for _ in range(3)], C.c_char_p()
         _check(self.ctx.L.zkm_staged_steps_get(self.h, s, C.byref(st), *[C.byref(x) for x in n], C.byref(err)), err)
         return _StagedStepsSegment(st, tuple(int(x.value) for x in n), self)
-
-    def ready(self, wait=False):
-        r = self.ctx.L.zkm_staged_steps_ready(self.h, 1 if wait else 0)
-        if r < 0:
-            raise ZkmError("zkm_staged_steps_ready: runtime error")
-        return bool(r)
-
-    def free(self):
-        """Waits for the uploads and the walk and returns the block."""
-        if self.h:
-            h, self.h = self.h, None
-            self.ctx._staged.discard(self)
-            if self.ctx.h:
-                self.ctx.L.zkm_staged_steps_free(h)
 
 
 class _ExpandedSteps:
@@ -856,26 +824,16 @@ class _ExpandedSteps:
         return self._st
 
 
-class ExpandedCalls:
+class ExpandedCalls(_StagedHandle):
     """struct zkm_expanded_calls: the expanded calls of K segments (Context.segments_calls_expand).  segment(s) gives what
     segments_tables_steps / prove_segments_ops_steps take for segment s; the SegmentCalls' lists must stay as they are until free().
     Freed like a StagedTrace when dropped, at the end of a `with` block or by Context.close()."""
 
+    _free = "zkm_expanded_calls_free"
+
     def __init__(self, ctx, handle, calls):
-        self.ctx, self.h, self.calls = ctx, handle, list(calls)
-        ctx._staged.add(self)
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        _StagedHandle.__init__(self, ctx, handle)
+        self.calls = list(calls)
 
     def __len__(self):
         return len(self.calls)
@@ -917,13 +875,6 @@ class ExpandedCalls:
             got["arithmetic_ops"] = down(o.arithmetic_ops, o.narithmetic * 3, np.uint32, (-1, 3))
         return got
 
-    def free(self):
-        if self.h:
-            h, self.h = self.h, None
-            self.ctx._staged.discard(self)
-            if self.ctx.h:
-                self.ctx.L.zkm_expanded_calls_free(h)
-
 
 class _StagedImage:
     """A segment's boot image as StagedCalls.get hands it out: addrs / values in device memory (the handle's)."""
@@ -935,12 +886,14 @@ class _StagedImage:
         return self._st
 
 
-class StagedCalls(ExpandedCalls):
+class StagedCalls(ExpandedCalls, _InFlightHandle):
     """The handle of zkm_segments_calls_stage: K segments' calls on their way into HBM behind the context's current work -- expanded,
     their records placed into the step list and the list walked on the device (include/zkm_hip.h "Staged calls").  get(s) is what
     segments_tables_steps / prove_segments_ops_steps of the SAME context take for segment s; free() after those calls have returned.
     The SegmentCalls (and BootImages) it was staged from are kept alive by the handle, and their arrays must stay as they are until
     ready() is true.  Freed when dropped, at the end of a `with` block or by Context.close()."""
+
+    _free, _ready = "zkm_staged_calls_free", "zkm_staged_calls_ready"
 
     def __init__(self, ctx, handle, calls, images=None):
         ExpandedCalls.__init__(self, ctx, handle, calls)
@@ -976,20 +929,6 @@ class StagedCalls(ExpandedCalls):
             _check(self.ctx.L.zkm_dev_download(self.ctx.h, steps.ctypes.data, st.steps, steps.nbytes, C.byref(err)), err)
         host = CpuStepsStruct(steps.ctypes.data, st.nsteps, st.raw_rows, st.nraw)
         return self._download(host, o, s)
-
-    def ready(self, wait=False):
-        r = self.ctx.L.zkm_staged_calls_ready(self.h, 1 if wait else 0)
-        if r < 0:
-            raise ZkmError("zkm_staged_calls_ready: runtime error")
-        return bool(r)
-
-    def free(self):
-        """Waits for the uploads, the expansions, the placement and the walk, and returns the blocks."""
-        if self.h:
-            h, self.h = self.h, None
-            self.ctx._staged.discard(self)
-            if self.ctx.h:
-                self.ctx.L.zkm_staged_calls_free(h)
 
 
 class _marshal_ops:

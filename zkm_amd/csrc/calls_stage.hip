@@ -140,16 +140,6 @@ struct slot {
     const void* dev(const char* sb) const { return up ? sb + at : src; }
 };
 
-// copies still in flight on the copy streams when a stage fails: they land before the block goes back to the allocator
-struct copy_join {
-    zkm_ctx* c = nullptr;
-    ~copy_join() {
-        if (!c) return;
-        (void)hipStreamSynchronize(c->copy_stream);
-        (void)hipStreamSynchronize(c->copy_stream2);
-    }
-};
-
 // A profiling scope on a copy stream (zkm_prof_scope's pair of events is recorded on the compute stream): calls_stage/expand,
 // calls_stage/place and calls_stage/walk are read once the handle is ready.
 struct copy_scope {
@@ -195,13 +185,10 @@ struct zkm_staged_calls {
     std::vector<zkm_insn_job> insn;
     std::vector<place_seg> desc;
     zkm_calls_hold hold;
-    place_verdict* verdicts = nullptr;   // pinned
-    zkm_staged_steps* steps = nullptr;   // owns the walk's block and the two events
-    bool resolved = false, joined = false;
-    ~zkm_staged_calls() {
-        zkm_staged_steps_free(steps);    // (waits for the events: everything queued on the copy streams has ended)
-        if (verdicts) (void)hipHostFree(verdicts);
-    }
+    zkm_pinned<place_verdict> verdicts;
+    zkm_staged_steps* steps = nullptr;   // owns the walk's block and the fence that stands for everything this handle has queued
+    bool resolved = false;
+    ~zkm_staged_calls() { zkm_staged_steps_free(steps); }   // (waits for that fence before the members above go)
 };
 
 namespace {
@@ -213,7 +200,7 @@ void resolve(zkm_staged_calls* h) {
         zkm_staged_calls::seg& g = h->segs[s];
         zkm_staged_steps_ref ref;
         zkm_staged_steps_at(h->steps, s, &ref);
-        const place_verdict& v = h->verdicts[s];
+        const place_verdict& v = h->verdicts.p[s];
         g.refusal = v.first_bad != NONE ? zkm_calls_row_refusal(g.q, g.n, v.first_bad, v.clock) : ref.refusal;
     }
     h->resolved = true;
@@ -295,7 +282,7 @@ std::unique_ptr<zkm_staged_calls> stage(const std::string& what, zkm_ctx* c, siz
     const size_t desc_at = take(nseg * sizeof(place_seg)), verdict_at = take(nseg * sizeof(place_verdict));
 
     // ---- the block, the jobs bound to it, what the builder takes
-    ZKM_HIP_CHECK(hipHostMalloc((void**)&h->verdicts, nseg * sizeof(place_verdict), hipHostMallocDefault));
+    h->verdicts.alloc(nseg);
     h->block = zkm_scratch(c, at);
     char* sb = h->block.as<char>();
     std::vector<zkm_cpu_steps> st(nseg);
@@ -354,16 +341,11 @@ std::unique_ptr<zkm_staged_calls> stage(const std::string& what, zkm_ctx* c, siz
     }
     h->scratch = zkm_scratch(c, scratch_bytes ? scratch_bytes : 256);
 
-    // ---- the queue.  The copy streams start behind what the compute stream has queued (the blocks may be ones a finished call released)
-    const hipStream_t up = c->ensure_copy_stream(0), up2 = c->ensure_copy_stream(1);
-    {
-        const zkm_event e(c);
-        e.record(c->stream);
-        ZKM_HIP_CHECK(hipStreamWaitEvent(up, e.e, 0));
-        ZKM_HIP_CHECK(hipStreamWaitEvent(up2, e.e, 0));
-    }
-    copy_join join;
-    join.c = c;
+    // ---- the queue.  Of the fence the start and the guard (a failure from here on: what is in flight lands before `h` goes); the events
+    // are the staged steps', recorded behind everything queued here
+    zkm_copy_fence queued;
+    queued.begin(c);
+    const hipStream_t up = c->copy_stream, up2 = c->copy_stream2;
     ZKM_HIP_CHECK(hipMemsetAsync(sb + verdict_at, 0xFF, nseg * sizeof(place_verdict), up));
     ZKM_HIP_CHECK(hipMemcpyAsync(sb + desc_at, h->desc.data(), nseg * sizeof(place_seg), hipMemcpyHostToDevice, up));
     for (size_t s = 0; s < nseg; s++) {
@@ -400,7 +382,7 @@ std::unique_ptr<zkm_staged_calls> stage(const std::string& what, zkm_ctx* c, siz
         hipLaunchKernelGGL(k_calls_verdict, dim3(1, 1, (unsigned)k), dim3(64), 0, up, d);
         ZKM_HIP_CHECK(hipGetLastError());
     }
-    ZKM_HIP_CHECK(hipMemcpyAsync(h->verdicts, sb + verdict_at, nseg * sizeof(place_verdict), hipMemcpyDeviceToHost, up));
+    ZKM_HIP_CHECK(hipMemcpyAsync(h->verdicts.p, sb + verdict_at, nseg * sizeof(place_verdict), hipMemcpyDeviceToHost, up));
     // the walk reads every ready-made row, the segment's own too: stream 1 goes behind stream 2's copies
     {
         const zkm_event e(c);
@@ -412,7 +394,7 @@ std::unique_ptr<zkm_staged_calls> stage(const std::string& what, zkm_ctx* c, siz
         const copy_scope ps(c, up, "calls_stage/walk");
         h->steps = zkm_steps_stage_queue(c, nseg, st.data(), false);
     }
-    join.c = nullptr;
+    queued.disarm();
     return h;
 }
 
@@ -439,12 +421,7 @@ static void staged_get(void* staged, size_t segment, zkm_cpu_steps* steps_out, z
     resolve(h);
     const zkm_staged_calls::seg& g = h->segs[segment];
     if (!g.refusal.empty()) throw std::runtime_error(what + ": segment " + dec(seg_base + segment) + ": " + g.refusal);
-    if (!h->joined) {
-        zkm_staged_steps_ref ref;
-        zkm_staged_steps_at(h->steps, segment, &ref);
-        for (const hipEvent_t e : ref.done) ZKM_HIP_CHECK(hipStreamWaitEvent(h->ctx->stream, e, 0));
-        h->joined = true;
-    }
+    zkm_staged_steps_join(h->steps);
     *steps_out = g.st;
     *ops_out = g.ops;
     if (image_out) *image_out = g.image;

@@ -662,63 +662,40 @@ int zkm_dev_download(zkm_ctx* c, void* dst, const void* src, size_t bytes, char*
 // PREVIOUS PROOF instead: zkm_trace_stage queues it on the context's two copy streams (alternate pieces of >= 64 MB)
 // and returns; the proof that consumes it runs the device-resident path at full speed.
 struct zkm_staged {
-    zkm_ctx* ctx;
-    gl_t* dev;
-    size_t words;
-    hipEvent_t done[2];
-    bool joined, canonical;
-    size_t off[ZKM_NUM_TABLES + 1];     // a staged SEGMENT: word offset of table t (Table::all() order) in the block, the last = words; one matrix: unused
-    bool segment;
-    bool counted;       // an upload counted in g_staged_live (a segment built on the device by zkm_segment_tables is not)
+    // an upload counted in g_staged_live (a segment built on the device by zkm_segment_tables is not).  The first member: it goes last,
+    // once the handle's block is back with the allocator
+    struct live_count {
+        bool on = false;
+        void count() { on = true; g_staged_live.fetch_add(1, std::memory_order_relaxed); }
+        ~live_count() { if (on) g_staged_live.fetch_sub(1, std::memory_order_relaxed); }
+    } counted;
+    zkm_ctx* ctx = nullptr;
+    zkm_scratch block;
+    size_t words = 0;
+    bool canonical = false;             // the words are canonical: vouched for by the caller, or canonicalised behind the first join
+    size_t off[ZKM_NUM_TABLES + 1] = {};   // a staged SEGMENT: word offset of table t (Table::all() order) in the block, the last = words; one matrix: unused
+    bool segment = false;
+    zkm_copy_fence fence;               // (behind the block: it has waited for the uploads when the block goes back)
+    gl_t* dev() const { return block.as<gl_t>(); }
 };
 
-static zkm_staged* stage_begin(zkm_ctx* c, size_t words, int canonical) {
+// a staged upload under way: the block, and the fence armed (zkm_copy_fence: a call that fails before the handle is handed out lets the
+// copies in flight land first)
+static std::unique_ptr<zkm_staged> stage_begin(zkm_ctx* c, size_t words, int canonical) {
     ZKM_HIP_CHECK(hipSetDevice(c->device));
-    c->ensure_copy_stream(0);
-    c->ensure_copy_stream(1);
-    zkm_scratch dev(c, words * sizeof(gl_t));
-    {
-        // the block may be one a finished call of this context released: whatever the compute stream still has queued on it comes first
-        const zkm_event e(c);
-        e.record(c->stream);
-        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
-        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
-    }
-    zkm_staged* s = new zkm_staged();
-    s->ctx = c; s->words = words; s->joined = false; s->canonical = canonical != 0;
-    s->done[0] = s->done[1] = nullptr;
-    s->segment = false;
-    s->counted = true;
-    for (size_t& o : s->off) o = 0;
-    s->dev = (gl_t*)dev.take();
-    g_staged_live.fetch_add(1, std::memory_order_relaxed);
+    std::unique_ptr<zkm_staged> s(new zkm_staged());
+    s->ctx = c; s->words = words; s->canonical = canonical != 0;
+    s->block = zkm_scratch(c, words * sizeof(gl_t));
+    s->fence.begin(c);
+    s->counted.count();
     return s;
 }
-static void stage_end(zkm_staged* s) {
-    zkm_ctx* c = s->ctx;
-    s->done[0] = c->get_event();
-    s->done[1] = c->get_event();
-    ZKM_HIP_CHECK(hipEventRecord(s->done[0], c->copy_stream));
-    ZKM_HIP_CHECK(hipEventRecord(s->done[1], c->copy_stream2));
-}
-static void stage_abort(zkm_staged* s) {
-    g_staged_live.fetch_sub(1, std::memory_order_relaxed);
-    (void)hipStreamSynchronize(s->ctx->copy_stream);
-    (void)hipStreamSynchronize(s->ctx->copy_stream2);
-    s->ctx->release(s->dev);
-    for (hipEvent_t e : s->done)
-        if (e) s->ctx->event_pool.push_back(e);
-    delete s;
-}
-
-// a staged upload under way: stage_abort releases it if the call fails before the handle is handed out
-using staged_owner = std::unique_ptr<zkm_staged, void (*)(zkm_staged*)>;
 
 int zkm_trace_stage(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, int canonical, zkm_staged** out, char** err) {
     return zkm_api("zkm_trace_stage", c, err, [&] {
         if (!values || !out || !ncols || log_n > 30) throw std::runtime_error("zkm_trace_stage: bad argument");
         const size_t n = (size_t)1 << log_n;
-        staged_owner s(stage_begin(c, ncols * n, canonical), stage_abort);
+        std::unique_ptr<zkm_staged> s = stage_begin(c, ncols * n, canonical);
         // pieces of >= 64 MB (8 columns at 2^20 rows; a short table is ONE copy): the two streams take alternate pieces; small pieces let
         // the other contexts' copies interleave (4 contexts at 2^20 rows: 16.3 proofs/s against 15.6 with 268 MB pieces), tiny ones are
         // all call overhead (a 2431-column table of 2^10 rows in 8-column pieces was 304 copies of 64 KB)
@@ -726,9 +703,9 @@ int zkm_trace_stage(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned l
         if (const char* e = getenv("ZKM_STAGE_PIECE_COLS")) piece = std::max<size_t>(1, (size_t)atoi(e));   // (measurement aid)
         for (size_t c0 = 0, k = 0; c0 < ncols; c0 += piece, k++) {
             const size_t nc = std::min(piece, ncols - c0);
-            ZKM_HIP_CHECK(hipMemcpyAsync(s->dev + c0 * n, values + c0 * n, nc * n * sizeof(gl_t), hipMemcpyHostToDevice, (k & 1) ? c->copy_stream2 : c->copy_stream));
+            ZKM_HIP_CHECK(hipMemcpyAsync(s->dev() + c0 * n, values + c0 * n, nc * n * sizeof(gl_t), hipMemcpyHostToDevice, (k & 1) ? c->copy_stream2 : c->copy_stream));
         }
-        stage_end(s.get());
+        s->fence.end();
         *out = s.release();
     });
 }
@@ -738,10 +715,10 @@ int zkm_trace_stage_columns(zkm_ctx* c, const uint64_t* const* columns, size_t n
         for (size_t i = 0; i < ncols; i++)
             if (!columns[i]) throw std::runtime_error("zkm_trace_stage_columns: null column pointer");
         const size_t n = (size_t)1 << log_n;
-        staged_owner s(stage_begin(c, ncols * n, canonical), stage_abort);
+        std::unique_ptr<zkm_staged> s = stage_begin(c, ncols * n, canonical);
         for (size_t i = 0; i < ncols; i++)
-            ZKM_HIP_CHECK(hipMemcpyAsync(s->dev + i * n, columns[i], n * sizeof(gl_t), hipMemcpyHostToDevice, ((i / 8) & 1) ? c->copy_stream2 : c->copy_stream));
-        stage_end(s.get());
+            ZKM_HIP_CHECK(hipMemcpyAsync(s->dev() + i * n, columns[i], n * sizeof(gl_t), hipMemcpyHostToDevice, ((i / 8) & 1) ? c->copy_stream2 : c->copy_stream));
+        s->fence.end();
         *out = s.release();
     });
 }
@@ -760,7 +737,7 @@ static int stage_segment(const char* what, zkm_ctx* c, const uint64_t* const* tr
             W[t] = zkm_table_at(t)->width;
             off[t + 1] = off[t] + (W[t] << log_n[t]);
         }
-        staged_owner s(stage_begin(c, off[NT], canonical), stage_abort);
+        std::unique_ptr<zkm_staged> s = stage_begin(c, off[NT], canonical);
         s->segment = true;
         for (int t = 0; t <= NT; t++) s->off[t] = off[t];
         size_t k = 0, bytes_on[2] = {0, 0};
@@ -772,11 +749,11 @@ static int stage_segment(const char* what, zkm_ctx* c, const uint64_t* const* tr
                 if (!columns || c0 % piece == 0) k = bytes_on[0] <= bytes_on[1] ? 0 : 1;     // the less loaded stream takes the next piece
                 if (columns && !columns[t][c0]) throw std::runtime_error(std::string(what) + ": null column pointer");
                 const void* src = columns ? (const void*)columns[t][c0] : (const void*)(traces[t] + c0 * n);
-                ZKM_HIP_CHECK(hipMemcpyAsync(s->dev + off[t] + c0 * n, src, nc * n * sizeof(gl_t), hipMemcpyHostToDevice, k ? c->copy_stream2 : c->copy_stream));
+                ZKM_HIP_CHECK(hipMemcpyAsync(s->dev() + off[t] + c0 * n, src, nc * n * sizeof(gl_t), hipMemcpyHostToDevice, k ? c->copy_stream2 : c->copy_stream));
                 bytes_on[k] += nc * n * sizeof(gl_t);
             }
         }
-        stage_end(s.get());
+        s->fence.end();
         *out = s.release();
     });
 }
@@ -800,59 +777,32 @@ int zkm_staged_segment_ptrs(zkm_staged* s, const uint64_t** ptrs_out) {
 const uint64_t* zkm_staged_ptr(zkm_staged* s) {
     if (!s) return nullptr;
     zkm_ctx* c = s->ctx;
-    if (!s->joined && zkm_api("zkm_staged_ptr", c, nullptr, [&] {
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, s->done[0], 0));
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, s->done[1], 0));
-            if (!s->canonical) zkm_launch_canon(c, s->dev, s->words);
-            s->joined = true;
+    if ((!s->fence.is_joined() || !s->canonical) && zkm_api("zkm_staged_ptr", c, nullptr, [&] {
+            s->fence.join();
+            if (!s->canonical) zkm_launch_canon(c, s->dev(), s->words);
+            s->canonical = true;
         }))
         return nullptr;
-    return s->dev;
+    return s->dev();
 }
 // host-side: has the upload finished (1), is it still in flight (0)?  `wait` != 0 blocks until it has.
-int zkm_staged_ready(zkm_staged* s, int wait) {
-    if (!s) return 1;
-    (void)hipSetDevice(s->ctx->device);
-    for (hipEvent_t e : s->done) {
-        if (wait) {
-            if (hipEventSynchronize(e) != hipSuccess) return -1;
-        } else {
-            const hipError_t q = hipEventQuery(e);
-            if (q == hipErrorNotReady) return 0;
-            if (q != hipSuccess) return -1;
-        }
-    }
-    return 1;
-}
-void zkm_staged_free(zkm_staged* s) {
-    if (!s) return;
-    zkm_ctx* c = s->ctx;
-    (void)hipSetDevice(c->device);
-    // the host source may go away after this returns, and the block goes back to an allocator whose blocks are reused by later work of
-    // the COMPUTE stream only: the uploads must have landed
-    (void)hipEventSynchronize(s->done[0]);
-    (void)hipEventSynchronize(s->done[1]);
-    c->release(s->dev);
-    (void)zkm_api("zkm_staged_free", nullptr, [&] { c->event_pool.insert(c->event_pool.end(), s->done, s->done + 2); });
-    const bool counted = s->counted;
-    delete s;
-    if (counted) g_staged_live.fetch_sub(1, std::memory_order_relaxed);
-}
+int zkm_staged_ready(zkm_staged* s, int wait) { return s ? s->fence.ready(wait != 0) : 1; }
+// The fence waits for the uploads: the host source may go away after this returns, and the block goes back to an allocator whose blocks
+// are reused by later work of the COMPUTE stream only.
+void zkm_staged_free(zkm_staged* s) { const std::unique_ptr<zkm_staged> gone(s); }
 
 // A segment whose tables were WRITTEN on the device by work already queued on the context's compute stream (segment_ops.hip): the block
 // becomes a segment-shaped handle that zkm_staged_segment_ptrs / _ready / _free take as they take an upload.  Both events are recorded
-// on the compute stream; the block is canonical and needs no join.  Not an upload, so not counted in g_staged_live.
+// on the compute stream; the block is canonical and needs no join.  Not an upload, so not counted in g_staged_live.  The handle takes
+// the block last: a call that fails leaves it with the caller.
 zkm_staged* zkm_staged_from_segment(zkm_ctx* c, void* block, const size_t off[ZKM_NUM_TABLES + 1]) {
-    zkm_event e0(c), e1(c);
-    e0.record(c->stream);
-    e1.record(c->stream);
-    zkm_staged* s = new zkm_staged();
-    s->ctx = c; s->dev = (gl_t*)block; s->words = off[ZKM_NUM_TABLES]; s->joined = true; s->canonical = true;
-    s->segment = true; s->counted = false;
+    std::unique_ptr<zkm_staged> s(new zkm_staged());
+    s->ctx = c; s->words = off[ZKM_NUM_TABLES]; s->canonical = true; s->segment = true;
     for (int t = 0; t <= ZKM_NUM_TABLES; t++) s->off[t] = off[t];
-    s->done[0] = e0.e; s->done[1] = e1.e;
-    e0.e = e1.e = nullptr;
-    return s;
+    s->fence.end_on_compute(c);
+    s->block.c = c;
+    s->block.p = block;
+    return s.release();
 }
 
 // ------------------------------------------------------------------ profiling

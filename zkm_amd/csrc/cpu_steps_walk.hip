@@ -214,19 +214,9 @@ std::string read_verdict(const steps_verdict& v, const zkm_cpu_steps& st, zkm_st
     return std::string();
 }
 
-// copies still in flight on the copy streams when a stage fails: they land before the block goes back to the allocator
-struct copy_join {
-    zkm_ctx* c = nullptr;
-    ~copy_join() {
-        if (!c) return;
-        (void)hipStreamSynchronize(c->copy_stream);
-        (void)hipStreamSynchronize(c->copy_stream2);
-    }
-};
-
 }  // namespace
 
-// ---- steps staged ahead of a call.  The handle owns the block, the pinned words the verdicts come down into and the two events; the
+// ---- steps staged ahead of a call.  The handle owns the block, the pinned words the verdicts come down into and the fence; the
 // registry maps each segment's device `steps` pointer to its handle, which is how the builder knows a staged segment.
 struct zkm_staged_steps {
     zkm_ctx* ctx = nullptr;
@@ -238,10 +228,9 @@ struct zkm_staged_steps {
         std::string refusal;
     };
     std::vector<seg> segs;
-    steps_verdict* verdicts = nullptr;   // pinned
-    zkm_event done[2];                   // the end of the work on the two copy streams
-    bool resolved = false;               // the host has waited for both and read the verdicts
-    bool joined = false;                 // the compute stream waits for both (first zkm_staged_steps_get of a good segment)
+    zkm_pinned<steps_verdict> verdicts;
+    zkm_copy_fence fence;                // the work on the two copy streams (behind the block and the pinned words: it has waited when they go)
+    bool resolved = false;               // the host has waited for the fence and read the verdicts
     ~zkm_staged_steps();
 };
 
@@ -253,25 +242,20 @@ std::map<const void*, std::pair<zkm_staged_steps*, size_t>> g_staged_steps;   //
 // the host's one wait for a handle
 void resolve(zkm_staged_steps* h) {
     if (h->resolved) return;
-    ZKM_HIP_CHECK(hipSetDevice(h->ctx->device));
     h->ctx->host_waits++;
-    ZKM_HIP_CHECK(hipEventSynchronize(h->done[0].e));
-    ZKM_HIP_CHECK(hipEventSynchronize(h->done[1].e));
-    for (size_t s = 0; s < h->segs.size(); s++) h->segs[s].refusal = read_verdict(h->verdicts[s], h->segs[s].dev, &h->segs[s].n);
+    if (h->fence.ready(true) < 0) throw std::runtime_error("zkm_staged_steps: the wait for the staged walk failed");
+    for (size_t s = 0; s < h->segs.size(); s++) h->segs[s].refusal = read_verdict(h->verdicts.p[s], h->segs[s].dev, &h->segs[s].n);
     h->resolved = true;
 }
 
 }  // namespace
 
 zkm_staged_steps::~zkm_staged_steps() {
-    {
-        std::lock_guard<std::mutex> lk(g_steps_mu);
-        for (const seg& s : segs) {
-            const auto it = g_staged_steps.find(s.dev.steps);
-            if (it != g_staged_steps.end() && it->second.first == this) g_staged_steps.erase(it);
-        }
+    std::lock_guard<std::mutex> lk(g_steps_mu);
+    for (const seg& s : segs) {
+        const auto it = g_staged_steps.find(s.dev.steps);
+        if (it != g_staged_steps.end() && it->second.first == this) g_staged_steps.erase(it);
     }
-    if (verdicts) (void)hipHostFree(verdicts);
 }
 
 bool zkm_staged_steps_find(const void* d_steps, zkm_staged_steps_ref* out) {
@@ -295,9 +279,11 @@ void zkm_staged_steps_at(zkm_staged_steps* h, size_t s, zkm_staged_steps_ref* ou
     out->n = h->segs[s].n;
     out->base = h->segs[s].base;
     out->refusal = h->segs[s].refusal;
-    out->done[0] = h->done[0].e;
-    out->done[1] = h->done[1].e;
+    out->done[0] = h->fence.event(0);
+    out->done[1] = h->fence.event(1);
 }
+
+void zkm_staged_steps_join(zkm_staged_steps* h) { h->fence.join(); }
 
 extern "C" {
 
@@ -342,7 +328,7 @@ zkm_staged_steps* zkm_steps_stage_queue(zkm_ctx* c, size_t nseg, const zkm_cpu_s
     std::unique_ptr<zkm_staged_steps> h(new zkm_staged_steps());
     h->ctx = c;
     const walk_plan P(nseg, steps, own_steps);
-    ZKM_HIP_CHECK(hipHostMalloc((void**)&h->verdicts, nseg * sizeof(steps_verdict), hipHostMallocDefault));
+    h->verdicts.alloc(nseg);
     h->block = zkm_scratch(c, P.bytes);
     char* sb = h->block.as<char>();
     h->segs.resize(nseg);
@@ -351,24 +337,10 @@ zkm_staged_steps* zkm_steps_stage_queue(zkm_ctx* c, size_t nseg, const zkm_cpu_s
         h->segs[s].dev = zkm_cpu_steps{steps[s].nsteps ? w.steps : nullptr, w.nsteps, w.nraw ? w.raw : nullptr, w.nraw};
         h->segs[s].base = w.base;
     }
-    // the copy streams start behind what the compute stream has queued (the block may be one that a finished call released)
-    c->ensure_copy_stream(0);
-    c->ensure_copy_stream(1);
-    {
-        const zkm_event e(c);
-        e.record(c->stream);
-        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
-        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
-    }
-    copy_join join;
-    join.c = c;
+    h->fence.begin(c);
     queue_walk(c, c->copy_stream, c->copy_stream2, P, sb, steps, nseg);
-    ZKM_HIP_CHECK(hipMemcpyAsync(h->verdicts, sb, nseg * sizeof(steps_verdict), hipMemcpyDeviceToHost, c->copy_stream));
-    h->done[0] = zkm_event(c);
-    h->done[1] = zkm_event(c);
-    h->done[0].record(c->copy_stream);
-    h->done[1].record(c->copy_stream2);
-    join.c = nullptr;
+    ZKM_HIP_CHECK(hipMemcpyAsync(h->verdicts.p, sb, nseg * sizeof(steps_verdict), hipMemcpyDeviceToHost, c->copy_stream));
+    h->fence.end();
     {
         std::lock_guard<std::mutex> lk(g_steps_mu);
         for (size_t s = 0; s < nseg; s++)
@@ -380,19 +352,8 @@ zkm_staged_steps* zkm_steps_stage_queue(zkm_ctx* c, size_t nseg, const zkm_cpu_s
 extern "C" {
 
 int zkm_staged_steps_ready(void* staged, int wait) {
-    zkm_staged_steps* h = (zkm_staged_steps*)staged;
-    if (!h) return 1;
-    (void)hipSetDevice(h->ctx->device);
-    for (const zkm_event& e : h->done) {
-        if (wait) {
-            if (hipEventSynchronize(e.e) != hipSuccess) return -1;
-        } else {
-            const hipError_t q = hipEventQuery(e.e);
-            if (q == hipErrorNotReady) return 0;
-            if (q != hipSuccess) return -1;
-        }
-    }
-    return 1;
+    const zkm_staged_steps* h = (const zkm_staged_steps*)staged;
+    return h ? h->fence.ready(wait != 0) : 1;
 }
 
 int zkm_staged_steps_get(void* staged, size_t segment, zkm_cpu_steps* steps_out, size_t* memory_ops, size_t* logic_ops, size_t* arithmetic_ops,
@@ -406,11 +367,7 @@ int zkm_staged_steps_get(void* staged, size_t segment, zkm_cpu_steps* steps_out,
         resolve(h);
         const zkm_staged_steps::seg& g = h->segs[segment];
         if (!g.refusal.empty()) throw std::runtime_error(what + ": segment " + std::to_string(segment) + ": " + g.refusal);
-        if (!h->joined) {
-            ZKM_HIP_CHECK(hipStreamWaitEvent(h->ctx->stream, h->done[0].e, 0));
-            ZKM_HIP_CHECK(hipStreamWaitEvent(h->ctx->stream, h->done[1].e, 0));
-            h->joined = true;
-        }
+        h->fence.join();
         *steps_out = g.dev;
         if (memory_ops) *memory_ops = g.n.mem;
         if (logic_ops) *logic_ops = g.n.logic;
@@ -419,13 +376,7 @@ int zkm_staged_steps_get(void* staged, size_t segment, zkm_cpu_steps* steps_out,
 }
 
 void zkm_staged_steps_free(void* staged) {
-    zkm_staged_steps* h = (zkm_staged_steps*)staged;
-    if (!h) return;
-    (void)hipSetDevice(h->ctx->device);
-    // the block goes back to an allocator whose blocks are reused by later work of the compute stream only: the walk must have ended
-    (void)hipEventSynchronize(h->done[0].e);
-    (void)hipEventSynchronize(h->done[1].e);
-    delete h;
+    delete (zkm_staged_steps*)staged;   // (the fence waits for the walk before the block goes back)
 }
 
 }  // extern "C"

@@ -112,16 +112,6 @@ static_assert(NTAB == ZKM_NUM_TABLES && zkm_table_at(ME)->id == ZKM_TABLE_MEMORY
 unsigned log2_of(size_t pow2) { return pow2 ? 63 - __builtin_clzll(pow2) : 0; }
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
-// after a failure the copy streams may still be writing into the staging block: wait for them before it goes back to the allocator
-struct copy_join {
-    zkm_ctx* c = nullptr;
-    ~copy_join() {
-        if (!c) return;
-        (void)hipStreamSynchronize(c->copy_stream);
-        (void)hipStreamSynchronize(c->copy_stream2);
-    }
-};
-
 // the output of one build: the block (empty in sizing mode), the word offset of each table in it, and the heights
 struct segment_block {
     zkm_scratch block;
@@ -376,11 +366,11 @@ struct builder {
         d.cpu_rows = (const uint64_t*)(sb + cpu_off);
         piece_rows = std::min<size_t>(o.ncpu_rows, std::max<size_t>(8192, o.ncpu_rows / 16));
         for (size_t r0 = 0; r0 < o.ncpu_rows; r0 += piece_rows, turn++) {
-            hipStream_t st = (turn & 1) ? c->copy_stream2 : c->copy_stream;
+            const hipStream_t up = (turn & 1) ? c->copy_stream2 : c->copy_stream;
             const size_t here = std::min(piece_rows, o.ncpu_rows - r0);   // (behind a bootstrap the caller's rows are no power of two)
-            ZKM_HIP_CHECK(hipMemcpyAsync((void*)(d.cpu_rows + r0 * CPU_W), o.cpu_rows + r0 * CPU_W, here * CPU_W * 8, hipMemcpyHostToDevice, st));
+            ZKM_HIP_CHECK(hipMemcpyAsync((void*)(d.cpu_rows + r0 * CPU_W), o.cpu_rows + r0 * CPU_W, here * CPU_W * 8, hipMemcpyHostToDevice, up));
             piece_done.emplace_back(c);
-            piece_done.back().record(st);
+            piece_done.back().record(up);
         }
     }
     // ---- phase: the uploads of the lists on the compute stream (sizing: the two that the heights need; then the others)
@@ -435,19 +425,13 @@ std::vector<segment_block> build_wave(zkm_ctx* c, builder* b, size_t K, bool wri
     for (size_t s = 0; s < K; s++)
         for (const hipEvent_t e : b[s].staged.done)
             if (b[s].staged.ctx) ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, e, 0));
-    copy_join join;
+    // host rows go up on the copy streams, each piece with an event of its own: of the fence only the start and the guard, which stays
+    // armed -- the copy streams are waited for before the staging block goes back, however the wave ends.  A wave of device-resident
+    // rows leaves the copy streams alone
+    zkm_copy_fence copies;
     bool any_host_rows = false;
     for (size_t s = 0; s < K; s++) any_host_rows = any_host_rows || b[s].cpu_host;
-    if (any_host_rows) {
-        // the copy streams start behind what the compute stream has queued (the block may be one that a finished call released)
-        c->ensure_copy_stream(0);
-        c->ensure_copy_stream(1);
-        const zkm_event e(c);
-        e.record(c->stream);
-        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
-        ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
-        join.c = c;
-    }
+    if (any_host_rows) copies.begin(c);
     size_t turn = 0;
     for (size_t s = 0; s < K; s++) b[s].copy_cpu_rows(sb, turn);
     ZKM_HIP_CHECK(hipMemsetAsync(d_sync, 0, K * SYNC_WORDS * 8, c->stream));
@@ -665,8 +649,7 @@ struct zkm_staged_ops {
     zkm_scratch block;                   // the CPU rows and every list
     zkm_segment_ops dev{};               // the segment with device pointers; the two offset arrays point at the copies below
     std::vector<uint64_t> ps_off, ks_off;
-    zkm_event done[2];                   // the end of the uploads on the two copy streams
-    bool joined = false;                 // the compute stream waits for both (first zkm_staged_ops_get)
+    zkm_copy_fence fence;                // the uploads on the two copy streams (behind the block: it has waited when the block goes back)
     ~zkm_staged_ops() {
         if (!block.p) return;
         std::lock_guard<std::mutex> lk(g_staged_mu);
@@ -875,16 +858,7 @@ int zkm_segment_ops_stage(zkm_ctx* c, const zkm_segment_ops* ops, zkm_staged_ops
         for (const list_ref& l : lists) bytes += align_up(l.bytes);
         h->block = zkm_scratch(c, bytes);
         char* base = h->block.as<char>();
-        c->ensure_copy_stream(0);
-        c->ensure_copy_stream(1);
-        {
-            const zkm_event e(c);
-            e.record(c->stream);
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, e.e, 0));
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream2, e.e, 0));
-        }
-        copy_join join;   // (a copy that fails to queue: the ones before it land before the block goes back)
-        join.c = c;
+        h->fence.begin(c);   // (a copy that fails to queue: the ones before it land before the block goes back)
         // alternate streams: the CPU rows in pieces of >= 16 MB, every other list in one copy (device-resident lists are copied too: the
         // handle owns all it hands out)
         size_t turn = 0, at = 0;
@@ -901,11 +875,7 @@ int zkm_segment_ops_stage(zkm_ctx* c, const zkm_segment_ops* ops, zkm_staged_ops
             l.set(base + at);
             at += align_up(l.bytes);
         }
-        h->done[0] = zkm_event(c);
-        h->done[1] = zkm_event(c);
-        h->done[0].record(c->copy_stream);
-        h->done[1].record(c->copy_stream2);
-        join.c = nullptr;
+        h->fence.end();
         {
             std::lock_guard<std::mutex> lk(g_staged_mu);
             g_staged_ops[h->block.p] = c;
@@ -917,38 +887,13 @@ int zkm_segment_ops_stage(zkm_ctx* c, const zkm_segment_ops* ops, zkm_staged_ops
 int zkm_staged_ops_get(zkm_staged_ops* h, zkm_segment_ops* ops_out) {
     if (!h || !ops_out) return 1;
     zkm_ctx* c = h->ctx;
-    if (!h->joined && zkm_api("zkm_staged_ops_get", c, nullptr, [&] {
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, h->done[0].e, 0));
-            ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, h->done[1].e, 0));
-            h->joined = true;
-        }))
-        return 1;
+    if (!h->fence.is_joined() && zkm_api("zkm_staged_ops_get", c, nullptr, [&] { h->fence.join(); })) return 1;
     *ops_out = h->dev;
     return 0;
 }
 
-int zkm_staged_ops_ready(zkm_staged_ops* h, int wait) {
-    if (!h) return 1;
-    (void)hipSetDevice(h->ctx->device);
-    for (const zkm_event& e : h->done) {
-        if (wait) {
-            if (hipEventSynchronize(e.e) != hipSuccess) return -1;
-        } else {
-            const hipError_t q = hipEventQuery(e.e);
-            if (q == hipErrorNotReady) return 0;
-            if (q != hipSuccess) return -1;
-        }
-    }
-    return 1;
-}
+int zkm_staged_ops_ready(zkm_staged_ops* h, int wait) { return h ? h->fence.ready(wait != 0) : 1; }
 
-void zkm_staged_ops_free(zkm_staged_ops* h) {
-    if (!h) return;
-    (void)hipSetDevice(h->ctx->device);
-    // the block goes back to an allocator whose blocks are reused by later work of the compute stream only: the uploads must have landed
-    (void)hipEventSynchronize(h->done[0].e);
-    (void)hipEventSynchronize(h->done[1].e);
-    delete h;
-}
+void zkm_staged_ops_free(zkm_staged_ops* h) { delete h; }   // (the fence waits for the uploads before the block goes back)
 
 }  // extern "C"

@@ -293,6 +293,103 @@ struct zkm_event {
     void record(hipStream_t st) const { ZKM_HIP_CHECK(hipEventRecord(e, st)); }
 };
 
+// Owner of pinned host words that a queued copy writes (a staged handle's verdicts).
+template <class T> struct zkm_pinned {
+    T* p = nullptr;
+    zkm_pinned() = default;
+    zkm_pinned(const zkm_pinned&) = delete;
+    zkm_pinned& operator=(const zkm_pinned&) = delete;
+    ~zkm_pinned() {
+        if (p) (void)hipHostFree(p);
+    }
+    void alloc(size_t n) { ZKM_HIP_CHECK(hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault)); }
+};
+
+// The ONE statement of how input is put into HBM behind the context's current work (the staged traces, operations, steps and calls;
+// DESIGN.md 3, "Input staged behind the current work").  The work goes onto the context's two copy streams, and the fence sees to the
+// orderings that make that safe:
+//   begin   the copy streams go behind what the compute stream has queued -- the block being filled may be one a finished call of
+//           this context released -- and the fence is ARMED: destroyed now (an exception unwinds the stage), it waits on the host for
+//           both copy streams, so that what is in flight lands before the block and the host memory it reads go away
+//   end     one event behind the work on each copy stream; the fence is ENDED and stands for that work from here on: ready / wait
+//           look at the events from the host, join puts the compute stream behind them (once, a device-side wait), and the
+//           destructor waits for them before the handle's block goes back to an allocator whose blocks later work of the compute
+//           stream reuses
+// A handle declares its fence BEHIND the blocks and the host memory that the queued work uses: members go in reverse order, so the fence
+// has waited by the time they do.  The events are pooled ones: a fence is destroyed on the thread that drives its context (zkm_event).
+struct zkm_copy_fence {
+    zkm_copy_fence() = default;
+    zkm_copy_fence(const zkm_copy_fence&) = delete;
+    zkm_copy_fence& operator=(const zkm_copy_fence&) = delete;
+    ~zkm_copy_fence() {
+        if (armed) {
+            (void)hipSetDevice(c->device);
+            (void)hipStreamSynchronize(c->copy_stream);
+            (void)hipStreamSynchronize(c->copy_stream2);
+        } else if (done[0].e) {
+            wait();
+        }
+    }
+    void begin(zkm_ctx* ctx) {
+        c = ctx;
+        const hipStream_t up[2] = {c->ensure_copy_stream(0), c->ensure_copy_stream(1)};
+        const zkm_event e(c);
+        e.record(c->stream);
+        for (const hipStream_t st : up) ZKM_HIP_CHECK(hipStreamWaitEvent(st, e.e, 0));
+        armed = true;
+    }
+    void end() { record(c->copy_stream, c->copy_stream2); }
+    // ... without a begin, for a block that work already queued on the compute stream fills (zkm_staged_from_segment): both events on
+    // that stream, and nothing left to join
+    void end_on_compute(zkm_ctx* ctx) {
+        c = ctx;
+        record(c->stream, c->stream);
+        joined = true;
+    }
+    void disarm() { armed = false; }   // a stage that records no events of its own (calls_stage.hip: its staged steps' stand for it)
+    // 1: the work has ended, 0: it is in flight (wait: block until it has ended instead), -1: the runtime reports an error.  (A fence
+    // that never began stands for no work: ready, and nothing to wait for)
+    int ready(bool wait) const {
+        if (!c) return 1;
+        (void)hipSetDevice(c->device);
+        for (const zkm_event& e : done) {
+            if (wait) {
+                if (hipEventSynchronize(e.e) != hipSuccess) return -1;
+            } else {
+                const hipError_t q = hipEventQuery(e.e);
+                if (q == hipErrorNotReady) return 0;
+                if (q != hipSuccess) return -1;
+            }
+        }
+        return 1;
+    }
+    void wait() const noexcept {
+        if (!c) return;
+        (void)hipSetDevice(c->device);
+        (void)hipEventSynchronize(done[0].e);
+        (void)hipEventSynchronize(done[1].e);
+    }
+    void join() {
+        if (joined) return;
+        for (const zkm_event& e : done) ZKM_HIP_CHECK(hipStreamWaitEvent(c->stream, e.e, 0));
+        joined = true;
+    }
+    bool is_joined() const { return joined; }
+    hipEvent_t event(int k) const { return done[k].e; }
+
+private:
+    zkm_ctx* c = nullptr;
+    zkm_event done[2];
+    bool armed = false, joined = false;
+    void record(hipStream_t s0, hipStream_t s1) {
+        done[0] = zkm_event(c);
+        done[1] = zkm_event(c);
+        done[0].record(s0);
+        done[1].record(s1);
+        armed = false;
+    }
+};
+
 // hipFuncSetAttribute is per device: `done` remembers the devices on which `kernel`'s dynamic-LDS limit has been raised (one bit per
 // device; a process may hold contexts on several GPUs, and several host threads may get here at once -- setting it twice is harmless).
 // The limit goes to a fixed maximum, never to what the current launch needs: a later, larger launch finds it raised.  Returns the
@@ -597,9 +694,11 @@ bool zkm_staged_steps_find(const void* d_steps, zkm_staged_steps_ref* out);
 // memory are walked IN PLACE and handed out as they came (calls_stage.hip: the list it has patched on the device, queued on the first
 // copy stream in front of this call -- the caller keeps that list alive for as long as the handle).  zkm_staged_steps_at: what
 // zkm_staged_steps_find gives, for segment s of a handle the caller holds (a segment without steps is in no registry).
+// zkm_staged_steps_join: the compute stream behind the handle's fence, once (what zkm_staged_steps_get does for a good segment).
 struct zkm_staged_steps;
 zkm_staged_steps* zkm_steps_stage_queue(zkm_ctx* c, size_t nseg, const zkm_cpu_steps* steps, bool own_steps);
 void zkm_staged_steps_at(zkm_staged_steps* h, size_t s, zkm_staged_steps_ref* out);
+void zkm_staged_steps_join(zkm_staged_steps* h);
 
 // ---- the calls' expansions (sha_calls.hip, keccak_calls.hip, io_calls.hip, insn_rows.hip): K segments served by ONE launch a kind.
 // A job is one segment's calls of one kind: the caller's lists (host or device memory as the kind's entry point says), where the
