@@ -299,10 +299,13 @@ int zkm_poseidon_sponge_trace(zkm_ctx* ctx, const uint8_t* inputs, const uint64_
  *                 virt_base + i (contiguous base addresses), or, with ZKM_SPONGE_BYTE_ADDRESSED set in virt_base, at
  *                 (virt_base & ~ZKM_SPONGE_BYTE_ADDRESSED) + 4 i: the addresses generate_keccak hands to keccak_sponge_log
  *                 (witness/operation.rs:1118-1134), one memory word every 4 bytes.  The flag is per operation and changes
- *                 nothing else of a row; zkm_poseidon_sponge_trace reads it the same way.
+ *                 nothing else of a row; zkm_poseidon_sponge_trace reads it the same way.  ZKM_SPONGE_PADDED_TAIL, a second
+ *                 flag bit of virt_base, is masked off and changes nothing of a row: it speaks to the SYSKECCAK calls'
+ *                 expansion (below), which hands its metas on unchanged.
  * Output: 470 x 2^log_n column-major, device pointer.  Fails if the operations need more than 2^log_n rows or if an
  * operation is empty (the reference indexes base_address[0]). */
 #define ZKM_SPONGE_BYTE_ADDRESSED 0x8000000000000000ULL
+#define ZKM_SPONGE_PADDED_TAIL 0x4000000000000000ULL
 #define ZKM_KECCAK_SPONGE_COLS 470
 int zkm_keccak_sponge_trace(zkm_ctx* ctx, const uint8_t* inputs, const uint64_t* input_off, const uint64_t* meta, size_t nops,
                             unsigned log_n, uint64_t* out_dev, size_t* rows_used_out, char** err);
@@ -1038,10 +1041,11 @@ int zkm_sha_calls_witness(zkm_ctx* ctx, const uint32_t* extend_w16, const uint64
  * :724-741) turn one SYSKECCAK call into, on the device, from the lists the caller hands over for the KeccakSponge table anyway:
  * keccak_sponge_inputs / _off / _meta of zkm_segment_ops, in the layout of zkm_keccak_sponge_trace, with ZKM_SPONGE_BYTE_ADDRESSED set in
  * every meta's virt_base (a call reads one memory word every 4 bytes), and one more word a call: digest_addrs, the address the digest is
- * written to (a2).  For a call of L = 4 W input bytes, with R = ceil(W / 8) and B = L / 136 + 1:
+ * written to (a2).  For a call of L input bytes in W = ceil(L / 4) memory words, with R = ceil(W / 8) and B = L / 136 + 1:
  *   cpu_rows      R + 2    ready-made CpuColumnsView rows for RAW steps: read row j (channels 0 .. min(8, W - 8 j) - 1 read word 8 j + i at
- *                          base + 4 (8 j + i), the value the big-endian reading of the word's four input bytes; mask = that many low
- *                          bits), the sponge row (mask 0: is_keccak_sponge; the values of channels 0-3 with used = 0 are context, segment,
+ *                          base + 4 (8 j + i), the value the big-endian reading of the word's four bytes in the padded message -- the
+ *                          input bytes, and in the last word of a length that is no multiple of 4 the padding behind them, see
+ *                          ZKM_SPONGE_PADDED_TAIL below; mask = that many low bits), the sponge row (mask 0: is_keccak_sponge; the values of channels 0-3 with used = 0 are context, segment,
  *                          the address of word (L / 136) * 34 -- 0 if the input has no such word -- and L; general.khash.value[i] the
  *                          big-endian reading of digest bytes 4 (7 - i) ..), the write row (mask 0xFF: channel i writes the big-endian
  *                          reading of digest bytes 4 i .. to digest_addr + 4 i).  Every other cell is 0
@@ -1054,7 +1058,11 @@ int zkm_sha_calls_witness(zkm_ctx* ctx, const uint32_t* extend_w16, const uint64
  * Every list holds the calls in list order; call k's items start at the sum of the earlier calls' counts.  Context and segment come from
  * the meta (the reference hard-codes 0 and Segment::Code: for its callers the rows are identical).  Clocks follow from the meta's
  * timestamp, the sponge row's: S = timestamp / 10 (NUM_CHANNELS); read row j at S - R + j, the sponge row at S, the write row at S + 1.
- *   zkm_keccak_calls_counts   the four totals (any out pointer may be NULL); pure: no context, no GPU
+ *   zkm_keccak_calls_counts   the four totals (any out pointer may be NULL); pure: no context, no GPU.  Without metas it takes lengths that
+ *                             are multiples of 4 only
+ *   zkm_keccak_calls_counts_meta   the same totals for calls of any length: meta as below (host memory; a list in device memory is
+ *                             not read) says which calls carry ZKM_SPONGE_PADDED_TAIL.  With meta NULL it is zkm_keccak_calls_counts,
+ *                             and its refusals are that function's, under that function's name.  Pure
  *   zkm_keccak_calls_steps    pure.  The cpu_rows RAW records (reads[0] = raw_base + j, reads[1] = the row's channel mask, every other field
  *                             0) into steps_out and the clock each belongs at into clocks_out, as zkm_sha_calls_steps does.  THE statement
  *                             of masks and positions: the binding, the Rust recorder and the kernel's indexing follow it.  meta is host
@@ -1067,16 +1075,29 @@ int zkm_sha_calls_witness(zkm_ctx* ctx, const uint32_t* extend_w16, const uint64
  *                             the outputs are complete: one host wait.  Profile scope keccak_calls/rows_lists.
  * Refused, on the host before any device work and before a missing context is reported, the message naming the list (input_off, meta,
  * digest_addrs, inputs, or the output) and the call's position: a NULL list or output with a nonzero count; input_off in device memory;
- * offsets that do not increase; a length that is 0 or not a multiple of 4; a meta without ZKM_SPONGE_BYTE_ADDRESSED; a timestamp that is
+ * offsets that do not increase; a length that is 0, or not a multiple of 4 in a call without ZKM_SPONGE_PADDED_TAIL; a meta without
+ * ZKM_SPONGE_BYTE_ADDRESSED; a timestamp that is
  * not a multiple of 10 or too small for the first read row's clock to be >= 0; base + 4 (W - 1) or digest_addr + 28 that does not fit in
  * 32 bits; a context or segment of 2^32 or more; raw_base + cpu_rows that does not fit in 32 bits; an output that is not aligned to its
  * words.  A refusal leaves the context usable.  meta or digest_addrs in DEVICE memory is not read by the host and so not held to these
- * rules (no store's address depends on them).
- * Lengths that are not a multiple of 4: the reference's sponge read of the last word then carries the padding byte (rem_data,
- * util.rs:515-535) and the other bytes of that memory word follow from no list, so such a call is refused here.  It can still travel as
- * RAW rows and the caller's own lists beside a flagged sponge operation: zkm_keccak_sponge_trace takes any length. */
+ * rules (no store's address depends on them); such a list takes lengths that are multiples of 4 only.
+ * Lengths that are not a multiple of 4: the last memory word then holds more than input bytes, and only one value of it can be proven.
+ * The guest runtime writes it as the remaining 1-3 input bytes, 0x01, then zeros, with 0x80 in its fourth byte when the word is the last
+ * of a 136-byte block (runtime/precompiles/src/io.rs:128-144); the sponge's reads of the remainder carry exactly that word (rem_data,
+ * witness/util.rs:513-535), the KeccakSponge table looks the final block's bytes up in memory with the padding in them
+ * (keccak_sponge_stark.rs:88-124, :319-347), and the Memory table makes every read of one address agree -- so the word is the padded
+ * message's, a function of the input bytes and L (0x81 in the fourth byte when L % 136 == 135).  The caller that has seen the call read
+ * that word sets ZKM_SPONGE_PADDED_TAIL in the meta's virt_base, beside ZKM_SPONGE_BYTE_ADDRESSED: the call is then expanded with the
+ * padded word in its last read channel and in the sponge's reads of the last 1-3 bytes, and nothing else of a call depends on L % 4.
+ * Without the flag (or with meta in device memory, which the host does not read) such a length is refused as before; the call can
+ * still travel as RAW rows and the caller's own lists beside a flagged sponge operation.  For a multiple of 4 the flag changes nothing.
+ * Every entry point that takes these lists with their metas -- zkm_keccak_calls_steps, zkm_keccak_calls_witness and the segment entry
+ * points built on them (zkm_segment_calls_steps, zkm_segments_calls_expand, zkm_segments_tables_calls, zkm_prove_segments_ops_calls,
+ * zkm_segments_calls_stage, zkm_pool_prove_segments_calls) -- takes flagged calls of any length. */
 int zkm_keccak_calls_counts(const uint64_t* input_off, size_t ncalls, size_t* cpu_rows, size_t* memory_ops, size_t* logic_ops,
                             size_t* keccak_perms, char** err);
+int zkm_keccak_calls_counts_meta(const uint64_t* input_off, const uint64_t* meta, size_t ncalls, size_t* cpu_rows, size_t* memory_ops,
+                                 size_t* logic_ops, size_t* keccak_perms, char** err);
 int zkm_keccak_calls_steps(const uint64_t* input_off, const uint64_t* meta, size_t ncalls, size_t raw_base, zkm_cpu_step* steps_out,
                            uint64_t* clocks_out, char** err);
 int zkm_keccak_calls_witness(zkm_ctx* ctx, const uint8_t* inputs, const uint64_t* input_off, const uint64_t* meta,

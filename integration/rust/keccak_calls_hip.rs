@@ -9,9 +9,13 @@
 //!   * `GenerationState` gets a `keccak_log: KeccakCallLog` beside its `step_log: StepLog`;
 //!   * `generate_keccak(state, addr, len, ptr)` reads the input words from memory and writes the digest as today and calls
 //!     `keccak_log.record_keccak(&mut step_log, clock, addr, &input, ptr)` in place of its row and trace pushes (clock: the clock of the
-//!     first row the call would have pushed; input: the `len` bytes, `keccak_value_byte_be`).  A call whose length is not a multiple of
-//!     4 is refused by the library: `record_keccak` returns false for it and the generator then pushes its rows and lists as today -- the
-//!     KeccakSponge operation it pushes is packed by segment_hip.rs with ZKM_SPONGE_BYTE_ADDRESSED;
+//!     first row the call would have pushed; input: the `len` bytes, `keccak_value_byte_be`).  For a length that is not a multiple of
+//!     4 it calls `record_keccak_tail` with one more argument, the last memory word its loop read: the only provable value of that word
+//!     is the padded message's (the remaining input bytes, 0x01, zeros, 0x80 in the fourth byte of a block's last word -- what the
+//!     guest runtime writes, runtime/precompiles/src/io.rs:128-144, and what the sponge's reads carry, witness/util.rs:513-535), and if
+//!     the word read is that one the call is recorded with ZKM_SPONGE_PADDED_TAIL.  Either function returns false for a call the
+//!     library would refuse (an empty input; a last word that is not the padded one): the generator then pushes its rows and lists
+//!     as today -- the KeccakSponge operation it pushes is packed by segment_hip.rs with ZKM_SPONGE_BYTE_ADDRESSED;
 //!   * at the end of the segment `finish` expands the calls into device memory and patches the reserved steps; the segment is then
 //!     proven with `prove_segments_ops_steps_raw`, its `zkm_cpu_steps.raw_rows` and the memory / logic / Keccak lists of its
 //!     `zkm_segment_ops` pointing at the device blocks `finish` returns, and `keccak_sponge_*` at the log's own three lists (with the
@@ -34,7 +38,7 @@ const CPU_COLS: usize = 259;
 pub struct KeccakCallLog {
     pub inputs: Vec<u8>,        // the calls' input bytes, concatenated
     pub input_off: Vec<u64>,    // ncalls + 1 offsets into `inputs`
-    pub meta: Vec<u64>,         // 4 words a call: context, segment, address of word 0 | ZKM_SPONGE_BYTE_ADDRESSED, the sponge row's timestamp
+    pub meta: Vec<u64>,         // 4 words a call: context, segment, address of word 0 | ZKM_SPONGE_BYTE_ADDRESSED (| ZKM_SPONGE_PADDED_TAIL), the sponge row's timestamp
     pub digest_addrs: Vec<u64>, // the address a call's digest is written to
     first_clock: Option<u64>,   // the clock of step 0 of the step list (the bootstrap's row count)
 }
@@ -58,29 +62,72 @@ pub struct KeccakCallBlocks {
     pub nkeccak: usize,
 }
 
+/// The last memory word of a call whose length is no multiple of 4, as the padded message has it: the input's last len % 4 bytes,
+/// 0x01, zeros, and 0x80 in the fourth byte when the word is the last of a 136-byte block (0x81 there when len % 136 == 135).
+pub fn padded_tail_word(input: &[u8]) -> u32 {
+    let rem = &input[input.len() / 4 * 4..];
+    let mut bytes = [0u8; 4];
+    bytes[..rem.len()].copy_from_slice(rem);
+    bytes[rem.len()] = 0x01;
+    if input.len() % 136 + 4 > 136 {
+        bytes[3] |= 0x80;
+    }
+    u32::from_be_bytes(bytes)
+}
+
+/// What a call of `len` input bytes costs the link host-expanded, in bytes: its CPU rows, the sponge's reads (48 a byte), the XORs and
+/// the Keccak-f inputs with their timestamps -- against `len` + 48 recorded (an offset, four meta words, the digest's address).
+pub fn call_bytes(len: usize) -> usize {
+    let (words, blocks) = ((len + 3) / 4, len / 136 + 1);
+    ((words + 7) / 8 + 2) * CPU_COLS * 8 + len * 48 + 34 * blocks * 12 + blocks * 208
+}
+
 impl KeccakCallLog {
     pub fn ncalls(&self) -> usize {
         self.digest_addrs.len()
     }
 
     /// A SYSKECCAK call: context 0, Segment::Code (0), `input` = the bytes read from `addr` on, the digest written to `ptr`.  `clock`:
-    /// state.traces.clock() at the call.  false (nothing recorded): the length is 0 or not a multiple of 4, the call stays on the host.
+    /// state.traces.clock() at the call.  false (nothing recorded): the length is 0 or not a multiple of 4 (such a call is recorded
+    /// with `record_keccak_tail`), the call stays on the host.
     pub fn record_keccak(&mut self, steps: &mut StepLog, clock: u64, addr: usize, input: &[u8], ptr: usize) -> bool {
-        if input.is_empty() || input.len() % 4 != 0 {
+        input.len() % 4 == 0 && self.record(steps, clock, addr, input, ptr, 0)
+    }
+
+    /// The same for a call of any length: `last_word` is the memory word generate_keccak read last (the one that holds the input's last
+    /// byte).  For a length that is no multiple of 4 the call is recorded, flagged, iff that word is the padded message's; for a
+    /// multiple of 4 the word is all input and nothing is asked of it.
+    pub fn record_keccak_tail(&mut self, steps: &mut StepLog, clock: u64, addr: usize, input: &[u8], ptr: usize, last_word: u32) -> bool {
+        if input.len() % 4 == 0 {
+            return self.record(steps, clock, addr, input, ptr, 0);
+        }
+        last_word == padded_tail_word(input) && self.record(steps, clock, addr, input, ptr, ZKM_SPONGE_PADDED_TAIL)
+    }
+
+    fn record(&mut self, steps: &mut StepLog, clock: u64, addr: usize, input: &[u8], ptr: usize, tail: u64) -> bool {
+        if input.is_empty() {
             return false;
         }
         // how many read rows stand in front of the sponge row is the library's statement: ask it for this call's clocks
         let off = [0u64, input.len() as u64];
+        let flags = [0u64, 0, tail, 0];
         let mut rows = 0usize;
         let mut err = std::ptr::null_mut();
-        let rc = unsafe { zkm_keccak_calls_counts(off.as_ptr(), 1, &mut rows, std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut(), &mut err) };
+        let null = std::ptr::null_mut();
+        let rc = unsafe {
+            if tail == 0 {
+                zkm_keccak_calls_counts(off.as_ptr(), 1, &mut rows, null, null, null, &mut err)
+            } else {
+                zkm_keccak_calls_counts_meta(off.as_ptr(), flags.as_ptr(), 1, &mut rows, null, null, null, &mut err)
+            }
+        };
         if check(rc, err).is_err() {
             return false;
         }
         let read_rows = (rows - 2) as u64;               // the sponge row and the write row close the call
         self.inputs.extend_from_slice(input);
         self.input_off.push(self.inputs.len() as u64);
-        self.meta.extend_from_slice(&[0, 0, addr as u64 | ZKM_SPONGE_BYTE_ADDRESSED, (clock + read_rows) * 10]);
+        self.meta.extend_from_slice(&[0, 0, addr as u64 | ZKM_SPONGE_BYTE_ADDRESSED | tail, (clock + read_rows) * 10]);
         self.digest_addrs.push(ptr as u64);
         // the step at position i of the list is the row of clock first_clock + i: the call's rows take the next `rows` positions
         let first = *self.first_clock.get_or_insert(clock - steps.steps.len() as u64);
@@ -97,7 +144,7 @@ impl KeccakCallLog {
         let n = self.ncalls();
         let (mut rows, mut mem, mut logic, mut perms) = (0usize, 0usize, 0usize, 0usize);
         let mut err = std::ptr::null_mut();
-        check(unsafe { zkm_keccak_calls_counts(self.input_off.as_ptr(), n, &mut rows, &mut mem, &mut logic, &mut perms, &mut err) }, err)?;
+        check(unsafe { zkm_keccak_calls_counts_meta(self.input_off.as_ptr(), self.meta.as_ptr(), n, &mut rows, &mut mem, &mut logic, &mut perms, &mut err) }, err)?;
         let own_raw = steps.raw_rows.len() / CPU_COLS;
         // the one statement of masks and positions: the records and the clock each belongs at
         let mut records = vec![zkm_cpu_step::default(); rows];

@@ -164,6 +164,8 @@ pub const ZKM_SYSCALL_READ: u32 = 5; pub const ZKM_SYSCALL_WRITE: u32 = 6; pub c
 pub const ZKM_SYSCALL_SET_THREAD_AREA: u32 = 8;
 // a sponge operation's meta word 2 (virt_base) with this bit set: word w of the input is read at (virt_base & !bit) + 4 w
 pub const ZKM_SPONGE_BYTE_ADDRESSED: u64 = 0x8000000000000000;
+// beside it, on a SYSKECCAK call whose length is no multiple of 4: the call's last memory word is the padded message's
+pub const ZKM_SPONGE_PADDED_TAIL: u64 = 0x4000000000000000;
 // the kinds of zkm_io_calls_*: the data-moving helper behind generate_syscall's row (load_input, commit, verify, load_preimage)
 pub const ZKM_IO_HINT_READ: u32 = 0; pub const ZKM_IO_COMMIT: u32 = 1; pub const ZKM_IO_VERIFY: u32 = 2; pub const ZKM_IO_PREIMAGE: u32 = 3;
 // the kinds of zkm_insn_rows_*: the thirteen encodings decode() accepts and no ZKM_STEP_* kind takes
@@ -378,6 +380,8 @@ extern "C" {
     // SYSKECCAK precompile calls expanded on the device from the KeccakSponge table's lists (meta flagged ZKM_SPONGE_BYTE_ADDRESSED)
     pub fn zkm_keccak_calls_counts(input_off: *const u64, ncalls: usize, cpu_rows: *mut usize, memory_ops: *mut usize, logic_ops: *mut usize,
                                    keccak_perms: *mut usize, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_keccak_calls_counts_meta(input_off: *const u64, meta: *const u64, ncalls: usize, cpu_rows: *mut usize, memory_ops: *mut usize,
+                                        logic_ops: *mut usize, keccak_perms: *mut usize, err: *mut *mut c_char) -> c_int;
     pub fn zkm_keccak_calls_steps(input_off: *const u64, meta: *const u64, ncalls: usize, raw_base: usize, steps_out: *mut zkm_cpu_step,
                                   clocks_out: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_keccak_calls_witness(ctx: *mut zkm_ctx, inputs: *const u8, input_off: *const u64, meta: *const u64, digest_addrs: *const u64,

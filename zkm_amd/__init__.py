@@ -206,13 +206,21 @@ def sha_calls_steps(extend_meta=None, compress_meta=None, raw_base=0):
     return steps, clocks
 
 
-def keccak_calls_counts(input_off):
+def keccak_calls_counts(input_off, meta=None):
     """zkm_keccak_calls_counts: (cpu_rows, memory_ops, logic_ops, keccak_perms) that the SYSKECCAK calls with these ncalls + 1 input
-    offsets expand into; needs no GPU.  A length that is 0 or not a multiple of 4 raises ZkmError naming the call."""
+    offsets expand into; needs no GPU.  A length that is 0 or not a multiple of 4 raises ZkmError naming the call.  With meta (ncalls x
+    4 uint64; anything but a numpy array or a list counts as device memory, which the host does not read) it is
+    zkm_keccak_calls_counts_meta: a call whose meta carries ZKM_SPONGE_PADDED_TAIL may have any positive length."""
     off = np.ascontiguousarray(input_off, dtype=np.uint64).reshape(-1)
     out, err = [C.c_size_t() for _ in range(4)], C.c_char_p()
-    _check(load().zkm_keccak_calls_counts(off.ctypes.data if off.size > 1 else None, max(off.size, 1) - 1, *[C.byref(x) for x in out],
-                                          C.byref(err)), err)
+    n = max(off.size, 1) - 1
+    if meta is None or not isinstance(meta, (np.ndarray, list, tuple)):
+        _check(load().zkm_keccak_calls_counts(off.ctypes.data if n else None, n, *[C.byref(x) for x in out], C.byref(err)), err)
+    else:
+        m = _sha_meta(meta, 4)
+        assert len(m) == n, "one meta per call"
+        _check(load().zkm_keccak_calls_counts_meta(off.ctypes.data if n else None, m.ctypes.data if n else None, n, *[C.byref(x) for x in out],
+                                                   C.byref(err)), err)
     return tuple(int(x.value) for x in out)
 
 
@@ -223,7 +231,7 @@ def keccak_calls_steps(input_off, meta, raw_base=0):
     off, m = np.ascontiguousarray(input_off, dtype=np.uint64).reshape(-1), _sha_meta(meta, 4)
     n = len(m)
     assert off.size == n + 1, "one offset more than calls"
-    rows = keccak_calls_counts(off)[0]
+    rows = keccak_calls_counts(off, m)[0]
     steps, clocks, err = np.zeros(rows, dtype=CPU_STEP_DT), np.zeros(rows, dtype=np.uint64), C.c_char_p()
     _check(load().zkm_keccak_calls_steps(off.ctypes.data if n else None, m.ctypes.data if n else None, n, raw_base,
                                          steps.ctypes.data if rows else None, clocks.ctypes.data if rows else None, C.byref(err)), err)
@@ -231,6 +239,7 @@ def keccak_calls_steps(input_off, meta, raw_base=0):
 
 
 SPONGE_BYTE_ADDRESSED = _H["SPONGE_BYTE_ADDRESSED"]
+SPONGE_PADDED_TAIL = _H["SPONGE_PADDED_TAIL"]           # beside it on a SYSKECCAK call: the last memory word is the padded message's
 # the kinds of the I/O calls (ZKM_IO_*): hint_read, commit, verify, preimage
 IO_KINDS = {n.lower(): v for n, v in abi.constants("ZKM_IO_").items()}
 
@@ -1767,7 +1776,7 @@ class Context:
         """zkm_keccak_calls_witness into buffers of its own.  Returns numpy (raw_rows n x 259 uint64, memory_ops n x 6 uint64, logic_ops
         n x 3 uint32, keccak_inputs n x 25 uint64, keccak_timestamps n uint64)."""
         k, n = self._keccak_lists((inputs, input_off, meta, digest_addrs))
-        rows, mem, logic, perms = keccak_calls_counts(k[1]) if n else (0, 0, 0, 0)
+        rows, mem, logic, perms = keccak_calls_counts(k[1], k[2]) if n else (0, 0, 0, 0)
         bufs = [self.alloc(max(w, 1)) for w in (rows * 259, mem * 6, (logic * 3 + 1) // 2, perms * 25, perms)]
         try:
             self.keccak_calls_witness_into(k, n, *[b.ptr for b in bufs])
@@ -1836,7 +1845,7 @@ class Context:
         i, ni = _io_lists(io)
         q, nq = _insn_lists(insns)
         rows, mem, logic, ext = sha_calls_counts(ne, nc)
-        krows, kmem, klogic, kperms = keccak_calls_counts(k[1]) if nk else (0, 0, 0, 0)
+        krows, kmem, klogic, kperms = keccak_calls_counts(k[1], k[2]) if nk else (0, 0, 0, 0)
         irows = io_calls_counts(i[0], i[2])[0] if ni else 0
         qarith = insn_rows_counts(q[0])[1] if nq else 0
         assert not isinstance(steps.raw_rows, DeviceBuffer) and not {"sha_extend", "keccak_sponge"} & set(groups)

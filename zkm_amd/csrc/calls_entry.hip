@@ -59,7 +59,7 @@ void zkm_calls_counts(const zkm_segment_calls& q, size_t n[ZKM_CALLS_COUNTS]) {
     size_t mem[4] = {}, logic[2] = {};
     std::fill(n, n + ZKM_CALLS_COUNTS, 0);
     zkm_sha_calls_counts(q.nextend, q.ncompress, &n[N_SHA_ROWS], &mem[0], &logic[0], &n[N_EXT]);
-    must([&](char** e) { return zkm_keccak_calls_counts(q.keccak_input_off, q.nkeccak, &n[N_KECCAK_ROWS], &mem[1], &logic[1], &n[N_PERMS], e); });
+    must([&](char** e) { return zkm_keccak_calls_counts_meta(q.keccak_input_off, q.keccak_meta, q.nkeccak, &n[N_KECCAK_ROWS], &mem[1], &logic[1], &n[N_PERMS], e); });
     must([&](char** e) { return zkm_io_calls_counts(q.io_kinds, q.io_data_off, q.nio, &n[N_IO_ROWS], &mem[2], e); });
     must([&](char** e) { return zkm_insn_rows_counts(q.insns, q.ninsns, &mem[3], &n[N_ARITH], e); });
     n[N_INSN_ROWS] = q.ninsns;

@@ -41,11 +41,12 @@ GL_HD zkm_row_rec row_rec(const uint64_t* emeta, size_t E, const uint64_t* cmeta
 }
 }  // namespace zkm_sha_place
 
-// ---- keccak_calls.hip: the one statement of where things go, for a call of L input bytes (a positive multiple of 4)
+// ---- keccak_calls.hip: the one statement of where things go, for a call of L >= 1 input bytes (the host has refused a length that is
+// no multiple of 4 in a call without ZKM_SPONGE_PADDED_TAIL)
 namespace zkm_keccak_place {
 constexpr unsigned RATE = 136, RATE_U32 = 34, STATE = 25;                         // KECCAK_RATE_BYTES, KECCAK_RATE_U32S, the state's u64 words
 constexpr uint32_t MASK_SPONGE = 0, MASK_WRITE = 0xFF;
-GL_HD size_t words(size_t L) { return L / 4; }
+GL_HD size_t words(size_t L) { return (L + 3) / 4; }                              // W: the memory words read, the last one maybe in part
 GL_HD size_t read_rows(size_t L) { return (words(L) + 7) / 8; }                   // R: eight words a row
 GL_HD size_t blocks(size_t L) { return L / RATE + 1; }                            // B: the last one carries pad10*1 (it may hold nothing else)
 // what a call adds to each list

@@ -29,9 +29,9 @@ using zkm_step::read_word;
 using namespace zkm_calls;
 constexpr unsigned CPU_W = ZKM_CPU_COLS, THREADS = 256;
 constexpr uint32_t OP_XOR = 2;   // zkm_logic_trace's code
-constexpr uint64_t FLAG = ZKM_SPONGE_BYTE_ADDRESSED;
+constexpr uint64_t FLAG = ZKM_SPONGE_BYTE_ADDRESSED, TAIL = ZKM_SPONGE_PADDED_TAIL;
 
-// ---- the one statement of where things go, for a call of L input bytes (a positive multiple of 4)
+// ---- the one statement of where things go, for a call of L >= 1 input bytes
 namespace place = zkm_keccak_place;   // (calls_place_dev.h)
 
 using call_base = zkm_keccak_base;   // where a call starts in each list: the sums of the earlier calls' counts
@@ -39,7 +39,7 @@ using call_base = zkm_keccak_base;   // where a call starts in each list: the su
 struct keccak_calls_args {
     const uint8_t* inputs;
     const uint64_t* off;         // ncalls + 1
-    const uint64_t* meta;        // ncalls x 4 {context, segment, address of word 0 | FLAG, timestamp of the sponge row}
+    const uint64_t* meta;        // ncalls x 4 {context, segment, address of word 0 | FLAG (| TAIL), timestamp of the sponge row}
     const uint64_t* digest_addr; // ncalls
     const call_base* base;       // ncalls
     uint64_t *rows, *mem, *perm_in, *perm_ts;
@@ -52,9 +52,12 @@ __device__ __forceinline__ uint32_t padded_byte(const uint8_t* __restrict__ msg,
     if (pos < L) return msg[pos];
     return (pos == L ? 0x01u : 0u) | (pos == place::RATE * place::blocks(L) - 1 ? 0x80u : 0u);
 }
-// memory word w of the input as the CPU reads it: the big-endian reading of its four bytes
-__device__ __forceinline__ uint32_t be_word(const uint8_t* __restrict__ msg, size_t w) {
-    return (uint32_t)msg[4 * w] << 24 | (uint32_t)msg[4 * w + 1] << 16 | (uint32_t)msg[4 * w + 2] << 8 | msg[4 * w + 3];
+// memory word w < W of the call as the CPU reads it: the big-endian reading of its four bytes in the padded message.  A word that
+// lies inside the input is loaded as it is; the last word of a length that is no multiple of 4 goes byte by byte through padded_byte,
+// so no lane loads a byte at or beyond msg + L (the next call's bytes, or the end of the buffer, lie there)
+__device__ __forceinline__ uint32_t be_word(const uint8_t* __restrict__ msg, size_t L, size_t w) {
+    if (4 * w + 4 <= L) return (uint32_t)msg[4 * w] << 24 | (uint32_t)msg[4 * w + 1] << 16 | (uint32_t)msg[4 * w + 2] << 8 | msg[4 * w + 3];
+    return padded_byte(msg, L, 4 * w) << 24 | padded_byte(msg, L, 4 * w + 1) << 16 | padded_byte(msg, L, 4 * w + 2) << 8 | padded_byte(msg, L, 4 * w + 3);
 }
 __device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
 
@@ -68,7 +71,7 @@ __global__ __launch_bounds__(THREADS) void k_keccak_calls(const keccak_calls_arg
     const uint8_t* __restrict__ msg = A.inputs + A.off[k];
     const size_t L = A.off[k + 1] - A.off[k], W = place::words(L), R = place::read_rows(L), B = place::blocks(L);
     const call_base at = A.base[k];
-    const uint64_t ctx = A.meta[4 * k], seg = A.meta[4 * k + 1], addr = A.meta[4 * k + 2] & ~FLAG, ts = A.meta[4 * k + 3], S = ts / 10;
+    const uint64_t ctx = A.meta[4 * k], seg = A.meta[4 * k + 1], addr = A.meta[4 * k + 2] & ~(FLAG | TAIL), ts = A.meta[4 * k + 3], S = ts / 10;
     const uint64_t daddr = A.digest_addr[k];
     uint64_t* __restrict__ perm_in = A.perm_in + place::STATE * at.perm;
 
@@ -107,7 +110,7 @@ __global__ __launch_bounds__(THREADS) void k_keccak_calls(const keccak_calls_arg
             const unsigned ch = (cell - 1) / 6, f = (cell - 1) % 6;
             if (ch >= place::read_channels(L, r)) continue;
             const size_t w = 8 * r + ch;
-            v = chan_cell(f, true, ctx, seg, addr + 4 * w, be_word(msg, w));
+            v = chan_cell(f, true, ctx, seg, addr + 4 * w, be_word(msg, L, w));
         }
         A.rows[(at.row + r) * CPU_W + C_CLOCK + cell] = v;
     }
@@ -135,7 +138,7 @@ __global__ __launch_bounds__(THREADS) void k_keccak_calls(const keccak_calls_arg
     uint64_t* __restrict__ mem = A.mem + 6 * at.mem;
     for (size_t j = t; j < 6 * place::mem(L); j += THREADS) {
         const size_t w = j / 24;
-        mem[j] = read_word((unsigned)(j % 6), ctx, seg, addr + 4 * w, ts, be_word(msg, w));
+        mem[j] = read_word((unsigned)(j % 6), ctx, seg, addr + 4 * w, ts, be_word(msg, L, w));
     }
     // the 34 XORs of every absorption (xor_into_sponge), three words an operation: the state before = the stored state ^ the block
     uint32_t* __restrict__ logic = A.logic + 3 * at.logic;
@@ -152,17 +155,19 @@ __global__ __launch_bounds__(THREADS) void k_keccak_calls(const keccak_calls_arg
 }
 
 // ---- the host's refusals, naming the list and the call's position (they throw the bare message)
-// the offsets: host memory, increasing, every length a positive multiple of 4.  Returns the totals, and the sums a call if asked.
-call_base check_offsets(const uint64_t* off, size_t n, std::vector<call_base>* bases) {
+// the offsets: host memory, increasing, every length positive, and a multiple of 4 unless the call's meta carries TAIL (`meta`: the
+// metas if the host may read them, else null -- then no call is flagged).  Returns the totals, and the sums a call if asked.
+call_base check_offsets(const uint64_t* off, const uint64_t* meta, size_t n, std::vector<call_base>* bases) {
     call_base sum{0, 0, 0, 0};
     if (n && !off) throw std::runtime_error("input_off: NULL with a count of " + dec(n));
     if (n && zkm_is_device_ptr(off)) throw std::runtime_error("input_off: device memory (the offsets size the outputs: they must be host memory)");
+    if (n && meta && zkm_is_device_ptr(meta)) meta = nullptr;
     if (bases) bases->resize(n);
     for (size_t k = 0; k < n; k++) {
         const std::string at = "input_off: call " + dec(k) + ": ";
         if (off[k + 1] < off[k]) throw std::runtime_error(at + "the offsets do not increase (" + dec(off[k]) + " then " + dec(off[k + 1]) + ")");
         const uint64_t L = off[k + 1] - off[k];
-        if (L == 0 || L % 4)
+        if (L == 0 || (L % 4 && !(meta && meta[4 * k + 2] & TAIL)))
             throw std::runtime_error(at + "length " + dec(L) + " is not a positive multiple of 4 (the other bytes of the last memory word follow from no list: "
                                           "such a call travels as RAW rows beside a sponge operation with ZKM_SPONGE_BYTE_ADDRESSED)");
         if (bases) (*bases)[k] = sum;
@@ -179,12 +184,12 @@ void check_meta(const uint64_t* off, const uint64_t* meta, size_t n) {
     // (a list in device memory is not read by the host: see the header)
     for (size_t k = 0; k < n && !zkm_is_device_ptr(meta); k++) {
         const uint64_t* m = meta + 4 * k;
-        const uint64_t L = off[k + 1] - off[k], base = m[2] & ~FLAG;
+        const uint64_t L = off[k + 1] - off[k], W = place::words(L), base = m[2] & ~(FLAG | TAIL);
         const std::string at = "meta: call " + dec(k) + ": ";
         if (m[0] >= LIM) throw std::runtime_error(at + "context " + dec(m[0]) + " does not fit in 32 bits");
         if (m[1] >= LIM) throw std::runtime_error(at + "segment " + dec(m[1]) + " does not fit in 32 bits");
         if (!(m[2] & FLAG)) throw std::runtime_error(at + "virt_base " + hex(m[2]) + " lacks ZKM_SPONGE_BYTE_ADDRESSED (a call reads one memory word every 4 bytes)");
-        if (base >= LIM || base + (L - 4) >= LIM) throw std::runtime_error(at + "address of word 0 " + hex(base) + ": word " + dec(L / 4 - 1) + " does not fit in 32 bits");
+        if (base >= LIM || base + 4 * (W - 1) >= LIM) throw std::runtime_error(at + "address of word 0 " + hex(base) + ": word " + dec(W - 1) + " does not fit in 32 bits");
         if (m[3] % 10) throw std::runtime_error(at + "timestamp " + dec(m[3]) + " is not a multiple of 10 (NUM_CHANNELS)");
         if (m[3] / 10 < place::read_rows(L)) throw std::runtime_error(at + "timestamp " + dec(m[3]) + " puts the first read row before clock 0");
     }
@@ -229,10 +234,25 @@ struct keccak_kind {
     static size_t sparse_rows(const job& j) { return j.nrows; }
 };
 
+// the four totals, for zkm_keccak_calls_counts (no metas) and zkm_keccak_calls_counts_meta: one set of refusals under the first's name,
+// which the segment entry points pass on as it is
+void counts(const uint64_t* off, const uint64_t* meta, size_t n, size_t* cpu_rows, size_t* memory_ops, size_t* logic_ops, size_t* keccak_perms) {
+    call_base sum;
+    try {
+        sum = check_offsets(off, meta, n, nullptr);
+    } catch (const std::exception& e) {
+        throw std::runtime_error(std::string("zkm_keccak_calls_counts: ") + e.what());
+    }
+    if (cpu_rows) *cpu_rows = sum.row;
+    if (memory_ops) *memory_ops = sum.mem;
+    if (logic_ops) *logic_ops = sum.logic;
+    if (keccak_perms) *keccak_perms = sum.perm;
+}
+
 }  // namespace
 
 void zkm_keccak_calls_check(zkm_keccak_job& j) {
-    const call_base sum = check_offsets(j.off, j.n, &j.bases);
+    const call_base sum = check_offsets(j.off, j.meta, j.n, &j.bases);
     check_meta(j.off, j.meta, j.n);
     check_digest_addrs(j.digest_addrs, j.n);
     if (j.n && !j.inputs) throw std::runtime_error("inputs: NULL with a count of " + dec(j.n));
@@ -250,18 +270,12 @@ extern "C" {
 
 int zkm_keccak_calls_counts(const uint64_t* input_off, size_t ncalls, size_t* cpu_rows, size_t* memory_ops, size_t* logic_ops,
                             size_t* keccak_perms, char** err) {
-    return zkm_api("zkm_keccak_calls_counts", err, [&] {
-        call_base sum;
-        try {
-            sum = check_offsets(input_off, ncalls, nullptr);
-        } catch (const std::exception& e) {
-            throw std::runtime_error(std::string("zkm_keccak_calls_counts: ") + e.what());
-        }
-        if (cpu_rows) *cpu_rows = sum.row;
-        if (memory_ops) *memory_ops = sum.mem;
-        if (logic_ops) *logic_ops = sum.logic;
-        if (keccak_perms) *keccak_perms = sum.perm;
-    });
+    return zkm_api("zkm_keccak_calls_counts", err, [&] { counts(input_off, nullptr, ncalls, cpu_rows, memory_ops, logic_ops, keccak_perms); });
+}
+
+int zkm_keccak_calls_counts_meta(const uint64_t* input_off, const uint64_t* meta, size_t ncalls, size_t* cpu_rows, size_t* memory_ops,
+                                 size_t* logic_ops, size_t* keccak_perms, char** err) {
+    return zkm_api("zkm_keccak_calls_counts_meta", err, [&] { counts(input_off, meta, ncalls, cpu_rows, memory_ops, logic_ops, keccak_perms); });
 }
 
 int zkm_keccak_calls_steps(const uint64_t* input_off, const uint64_t* meta, size_t ncalls, size_t raw_base, zkm_cpu_step* steps_out,
@@ -271,7 +285,7 @@ int zkm_keccak_calls_steps(const uint64_t* input_off, const uint64_t* meta, size
         std::vector<call_base> bases;
         call_base sum;
         try {
-            sum = check_offsets(input_off, ncalls, &bases);
+            sum = check_offsets(input_off, meta, ncalls, &bases);
             check_meta(input_off, meta, ncalls);
         } catch (const std::exception& e) {
             refuse(e.what());

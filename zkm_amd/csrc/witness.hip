@@ -23,11 +23,12 @@
 //       and the table needs no zero-fill.  (The one-lane-per-operation form stored only the non-zero cells of a zero-filled table,
 //       4.6 rows apart per lane: 8-byte partial-line writes, 14 GB of HBM traffic for a 3.9 GB table -- profiles/r03_a_*.)
 // where word w of a sponge operation's input is read (both sponges): the meta's virt_base + w, or with ZKM_SPONGE_BYTE_ADDRESSED set in
-// it, one memory word every 4 bytes (include/zkm_hip.h, zkm_keccak_sponge_trace)
+// it, one memory word every 4 bytes (include/zkm_hip.h, zkm_keccak_sponge_trace).  ZKM_SPONGE_PADDED_TAIL speaks to the calls'
+// expansion (keccak_calls.hip) and changes nothing here.
 struct sponge_virt {
     uint64_t base, step;
     __device__ explicit sponge_virt(uint64_t meta_word)
-        : base(meta_word & ~ZKM_SPONGE_BYTE_ADDRESSED), step(meta_word & ZKM_SPONGE_BYTE_ADDRESSED ? 4 : 1) {}
+        : base(meta_word & ~(ZKM_SPONGE_BYTE_ADDRESSED | ZKM_SPONGE_PADDED_TAIL)), step(meta_word & ZKM_SPONGE_BYTE_ADDRESSED ? 4 : 1) {}
     __device__ uint64_t of(size_t w) const { return base + step * w; }
 };
 
