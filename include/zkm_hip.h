@@ -203,6 +203,27 @@ int zkm_batch_merkle_path(const zkm_batch* b, size_t leaf_index, uint64_t* sibli
 /* digest layer `level` (0 = leaf digests), (4n >> level) x 4 words, host out -- parity/debug */
 int zkm_batch_digest_layer(const zkm_batch* b, unsigned level, uint64_t* out);
 
+/* ------------------------------------------------------------------ stacked commitments
+ * A STACK is nstack same-shaped commitments built in one set of launches and held in one handle: what a caller that commits the same
+ * oracle once per segment (a PLONK prover proving one circuit K times) hands to zkm_eval_openings_stack / zkm_fri_prove_stack.
+ * values[k] / coeffs[k] -> ncols x 2^log_n words of member k, host or device.  Member k is, word for word, what zkm_batch_commit_values /
+ * _coeffs gives for the same words: cap, polynomials, leaves and Merkle paths.
+ * Refused on the host, before the context: a NULL values or out; nstack outside 1..32; ncols = 0 or nstack x ncols > 65535;
+ * log_n + rate_bits > 30; cap_height > log_n + rate_bits; a NULL member pointer (the message names the member).
+ * The single-member accessors above do not know members; the ones below take the member.  zkm_batch_free frees a stack. */
+int zkm_batch_commit_values_stack(zkm_ctx* ctx, const uint64_t* const* values, size_t nstack, size_t ncols, unsigned log_n, unsigned rate_bits,
+                                  unsigned cap_height, zkm_batch** out, char** err);
+int zkm_batch_commit_coeffs_stack(zkm_ctx* ctx, const uint64_t* const* coeffs, size_t nstack, size_t ncols, unsigned log_n, unsigned rate_bits,
+                                  unsigned cap_height, zkm_batch** out, char** err);
+/* members of the handle: 1 for every batch of the constructors above the stack's, 0 for NULL */
+size_t zkm_batch_stack_size(const zkm_batch* b);
+/* member k's cap as zkm_batch_cap, its polynomials as zkm_batch_coeffs (natural order; out host or device), and
+ * merkle_tree.leaves[leaf_index] (ncols words) with merkle_tree.prove(leaf_index) ((lde_bits - cap_height) x 4 words) of its tree, host
+ * out, either may be NULL.  Status 1: a NULL batch, k or leaf_index out of range, a failed copy. */
+int zkm_batch_stack_cap(const zkm_batch* b, size_t k, uint64_t* out);
+int zkm_batch_stack_coeffs(const zkm_batch* b, size_t k, uint64_t* out);
+int zkm_batch_stack_merkle_path(const zkm_batch* b, size_t k, size_t leaf_index, uint64_t* leaf_out, uint64_t* siblings_out);
+
 /* ------------------------------------------------------------------ hash primitives
  * a13: Poseidon permutation (prover/src/poseidon/poseidon_stark.rs:51-95; == plonky2 PoseidonHash's
  * permutation); k states of 12 words, in place.  K15: Keccak-f[1600] (cpu/kernel/keccak_util.rs:6-31,
@@ -1471,6 +1492,22 @@ typedef struct { uint64_t point[2]; const zkm_fri_poly* polys; size_t npolys; } 
 size_t zkm_fri_proof_words(const zkm_stark_config* cfg, unsigned log_n, const size_t* oracle_cols, size_t noracles);
 int zkm_fri_prove(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles, const zkm_fri_batch* batches,
                   size_t nbatches, zkm_challenger* challenger, uint64_t* proof_out, char** err);
+/* K opening proofs of ONE instance in lock-step: every oracle is a stack of the same size K (zkm_batch_commit_values_stack /
+ * _coeffs_stack; K = zkm_batch_stack_size), the batches' polynomial lists are shared by the K claims, and
+ *   points          K x nbatches x 2 words: claim k's point of batch b (the `point` fields inside `batches` are ignored)
+ *   challengers[k]  in/out as zkm_fri_prove's        proofs_out[k]   zkm_fri_proof_words words, host
+ * Claim k is zkm_fri_prove on member k of every oracle: every blob and every challenger state equals that call's on single
+ * commitments of the same data, word for word, so zkm_fri_verify takes the K blobs as K claims.  The K proofs share every launch --
+ * one combination launch for all batches and claims, then the division, the commit phase, the proof of work and the query gather of
+ * the lock-step STARK proofs -- and every transcript round trip: the call waits for the device as often as ONE zkm_fri_prove does.
+ * Refused on the host before any device work, leaving every challenger, the context and its live memory as they were: a NULL
+ * argument; more than 8 oracles or batches; oracles whose stack sizes, degree, rate, cap height or coefficient layout differ (or
+ * differ from cfg); a stack of more than 32; an empty batch; a polynomial index out of range; a NULL challenger or blob, or a point
+ * word >= p, of a claim ("zkm_fri_prove_stack: claim 2: non-canonical opening point").  A call that fails later leaves the challengers
+ * untouched too.  Out of scope: claims of different shapes in one call (group them, as segments are grouped by height); the pool.
+ * Measured: profiles/fri_stack_time.json. */
+int zkm_fri_prove_stack(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles, const zkm_fri_batch* batches,
+                        size_t nbatches, const uint64_t* points, zkm_challenger* const* challengers, uint64_t* const* proofs_out, char** err);
 
 /* ------------------------------------------------------------------ stage entry points (parity / reuse)
  * a6: compute_quotient_polys (prover.rs:645-789): nalphas polys of 2n coefficients, natural order;
@@ -1739,6 +1776,9 @@ int zkm_fri_verify(zkm_ctx* ctx, const zkm_stark_config* cfg, size_t nproofs, co
 /* a9: StarkOpeningSet::new building block (proof.rs:299-334): p(zeta) in F2 for every polynomial of the
  * batch; out = ncols x 2 words, host. */
 int zkm_eval_openings(zkm_ctx* ctx, const zkm_batch* b, const uint64_t zeta[2], uint64_t* out, char** err);
+/* ... of a stack (zkm_batch_commit_values_stack), each member at its own point: zetas = nstack x 2 words, out = nstack x ncols x 2 words,
+ * host; member k's words are zkm_eval_openings' on member k's single commitment.  One set of launches, one host wait. */
+int zkm_eval_openings_stack(zkm_ctx* ctx, const zkm_batch* b, const uint64_t* zetas, uint64_t* out, char** err);
 
 /* ------------------------------------------------------------------ profiling (HIP events on the ctx stream) */
 void zkm_profile_enable(zkm_ctx* ctx, int on);

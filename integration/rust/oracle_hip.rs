@@ -414,3 +414,158 @@ where
     challenger.set_from_zkm(&ch);
     Ok(())
 }
+
+/// K same-shaped `PolynomialBatch`es in one handle, built in one set of launches (`zkm_batch_commit_values_stack` /
+/// `_coeffs_stack`): what a prover that proves one circuit once per segment holds per oracle.  Member k is, word for word, the
+/// `HipPolynomialBatch` of member k's polynomials; `prove_openings_stack` proves the K opening instances in lock-step.
+pub struct HipPolynomialBatchStack<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize> {
+    batch: *mut zkm_batch,
+    ctx: *mut zkm_ctx,
+    pub degree_log: usize,
+    pub rate_bits: usize,
+    num_polys: usize,
+    cap_height: usize,
+    _phantom: PhantomData<(F, C)>,
+}
+
+impl<F: RichField + Extendable<D>, C: GenericConfig<D, F = F>, const D: usize> Drop for HipPolynomialBatchStack<F, C, D> {
+    fn drop(&mut self) {
+        unsafe { zkm_batch_free(self.batch) };
+    }
+}
+
+impl<F, C, const D: usize> HipPolynomialBatchStack<F, C, D>
+where
+    F: RichField + Extendable<D>,
+    C: GenericConfig<D, F = F, Hasher = PoseidonHash>,
+{
+    /// `members[k]` = member k's polynomials as ONE slice of `num_polys * n` words, polynomial after polynomial (values over the
+    /// subgroup, natural order).
+    pub fn from_values(ctx: *mut zkm_ctx, members: &[&[F]], num_polys: usize, rate_bits: usize, cap_height: usize) -> Self {
+        Self::commit(ctx, members, num_polys, true, rate_bits, cap_height)
+    }
+
+    /// ... as coefficients (the quotient oracle of a PLONK proof).
+    pub fn from_coeffs(ctx: *mut zkm_ctx, members: &[&[F]], num_polys: usize, rate_bits: usize, cap_height: usize) -> Self {
+        Self::commit(ctx, members, num_polys, false, rate_bits, cap_height)
+    }
+
+    fn commit(ctx: *mut zkm_ctx, members: &[&[F]], num_polys: usize, are_values: bool, rate_bits: usize, cap_height: usize) -> Self {
+        const { assert!(core::mem::size_of::<F>() == 8) };
+        let words = members.first().map_or(0, |m| m.len());
+        assert!(num_polys > 0 && words % num_polys == 0 && (words / num_polys).is_power_of_two(), "num_polys polynomials of one power-of-two length");
+        assert!(members.iter().all(|m| m.len() == words), "members of one shape");
+        let log_n = (words / num_polys).trailing_zeros();
+        let ptrs: Vec<*const u64> = members.iter().map(|m| m.as_ptr() as *const u64).collect();
+        let mut batch = std::ptr::null_mut();
+        let mut err = std::ptr::null_mut();
+        let rc = unsafe {
+            if are_values {
+                zkm_batch_commit_values_stack(ctx, ptrs.as_ptr(), ptrs.len(), num_polys, log_n, rate_bits as u32, cap_height as u32, &mut batch, &mut err)
+            } else {
+                zkm_batch_commit_coeffs_stack(ctx, ptrs.as_ptr(), ptrs.len(), num_polys, log_n, rate_bits as u32, cap_height as u32, &mut batch, &mut err)
+            }
+        };
+        check(rc, err).expect("libzkmhip: zkm_batch_commit_*_stack");
+        Self { batch, ctx, degree_log: log_n as usize, rate_bits, num_polys, cap_height, _phantom: PhantomData }
+    }
+
+    pub fn hip_batch(&self) -> *const zkm_batch {
+        self.batch
+    }
+
+    /// Members of the stack.
+    pub fn len(&self) -> usize {
+        unsafe { zkm_batch_stack_size(self.batch) }
+    }
+
+    /// Member k's `.merkle_tree.cap`.
+    pub fn cap(&self, k: usize) -> MerkleCap<F, C::Hasher> {
+        let mut w = vec![0u64; 4 << self.cap_height];
+        assert_eq!(unsafe { zkm_batch_stack_cap(self.batch, k, w.as_mut_ptr()) }, 0, "zkm_batch_stack_cap");
+        MerkleCap(w.chunks_exact(4).map(|d| HashOut { elements: core::array::from_fn(|i| F::from_canonical_u64(d[i])) }).collect())
+    }
+
+    /// Member k's `.polynomials`, downloaded.
+    pub fn polynomials(&self, k: usize) -> Vec<PolynomialCoeffs<F>> {
+        let n = 1usize << self.degree_log;
+        let mut w = vec![0u64; self.num_polys * n];
+        assert_eq!(unsafe { zkm_batch_stack_coeffs(self.batch, k, w.as_mut_ptr()) }, 0, "zkm_batch_stack_coeffs");
+        w.chunks_exact(n).map(|c| PolynomialCoeffs::new(c.iter().map(|&x| F::from_canonical_u64(x)).collect())).collect()
+    }
+
+    /// Every member's polynomials at the member's own point: `zkm_eval_openings_stack`, one set of launches and one wait for all.
+    pub fn eval_openings(&self, zetas: &[F::Extension]) -> Vec<Vec<F::Extension>> {
+        assert_eq!(zetas.len(), self.len());
+        let z: Vec<u64> = zetas
+            .iter()
+            .flat_map(|v| {
+                let c: [F; D] = v.to_basefield_array();
+                c.into_iter().map(|e| e.to_canonical_u64())
+            })
+            .collect();
+        let mut w = vec![0u64; zetas.len() * self.num_polys * D];
+        let mut err = std::ptr::null_mut();
+        check(unsafe { zkm_eval_openings_stack(self.ctx, self.batch, z.as_ptr(), w.as_mut_ptr(), &mut err) }, err).expect("libzkmhip: zkm_eval_openings_stack");
+        w.chunks_exact(self.num_polys * D)
+            .map(|m| m.chunks_exact(D).map(|c| <F::Extension as FieldExtension<D>>::from_basefield_array(core::array::from_fn(|i| F::from_canonical_u64(c[i])))).collect())
+            .collect()
+    }
+
+    /// `PolynomialBatch::prove_openings` for K instances of one shape in lock-step: `oracles` are stacks of the same size K,
+    /// `instances[k]` is claim k's `FriInstanceInfo` -- the polynomial lists must be the same in all of them, the points are each
+    /// claim's own -- and `challengers[k]` its transcript.  One `zkm_fri_prove_stack` call; proof k is what `prove_openings` gives on
+    /// member k of every oracle.
+    pub fn prove_openings_stack(
+        instances: &[&FriInstanceInfo<F, D>],
+        oracles: &[&Self],
+        challengers: &mut [Challenger<F, C::Hasher>],
+        fri_params: &FriParams,
+    ) -> Vec<FriProof<F, C::Hasher, D>> {
+        assert!(D == 2, "libzkmhip implements the quadratic extension of Goldilocks");
+        let k = oracles[0].len();
+        assert!(instances.len() == k && challengers.len() == k, "one instance and one challenger per member");
+        let cfg = fri_config_words(fri_params);
+        let list = |b: &FriBatchInfo<F, D>| -> Vec<zkm_fri_poly> {
+            b.polynomials.iter().map(|p| zkm_fri_poly { oracle: p.oracle_index as u32, poly: p.polynomial_index as u32 }).collect()
+        };
+        let polys: Vec<Vec<zkm_fri_poly>> = instances[0].batches.iter().map(list).collect();
+        for inst in instances {
+            assert_eq!(inst.oracles.len(), oracles.len());
+            assert!(inst.batches.len() == polys.len(), "instances of one shape");
+            for (b, ps) in inst.batches.iter().zip(&polys) {
+                assert!(list(b).iter().zip(ps).all(|(x, y)| x.oracle == y.oracle && x.poly == y.poly) && b.polynomials.len() == ps.len(), "instances of one shape");
+            }
+        }
+        let batches: Vec<zkm_fri_batch> = polys.iter().map(|ps| zkm_fri_batch { point: [0, 0], polys: ps.as_ptr(), npolys: ps.len() }).collect();
+        let points: Vec<u64> = instances
+            .iter()
+            .flat_map(|inst| inst.batches.iter())
+            .flat_map(|b| {
+                let c: [F; D] = b.point.to_basefield_array();
+                c.into_iter().map(|e| e.to_canonical_u64())
+            })
+            .collect();
+        let handles: Vec<*const zkm_batch> = oracles.iter().map(|o| o.hip_batch()).collect();
+        let cols: Vec<usize> = oracles.iter().map(|o| o.num_polys).collect();
+        let words = unsafe { zkm_fri_proof_words(&cfg, oracles[0].degree_log as u32, cols.as_ptr(), cols.len()) };
+        assert!(words != 0, "libzkmhip: unsupported FriParams");
+        let mut blobs: Vec<Vec<u64>> = (0..k).map(|_| vec![0u64; words]).collect();
+        let mut chs: Vec<zkm_challenger> = challengers.iter().map(|c| c.to_zkm()).collect();
+        let ch_ptrs: Vec<*mut zkm_challenger> = chs.iter_mut().map(|c| c as *mut zkm_challenger).collect();
+        let blob_ptrs: Vec<*mut u64> = blobs.iter_mut().map(|b| b.as_mut_ptr()).collect();
+        let mut err = std::ptr::null_mut();
+        check(
+            unsafe {
+                zkm_fri_prove_stack(oracles[0].ctx, &cfg, handles.as_ptr(), handles.len(), batches.as_ptr(), batches.len(), points.as_ptr(),
+                                    ch_ptrs.as_ptr(), blob_ptrs.as_ptr(), &mut err)
+            },
+            err,
+        )
+        .expect("libzkmhip: zkm_fri_prove_stack");
+        for (c, z) in challengers.iter_mut().zip(&chs) {
+            c.set_from_zkm(z);
+        }
+        blobs.iter().map(|b| fri_proof_from_blob::<F, C, D>(b)).collect()
+    }
+}

@@ -231,6 +231,15 @@ extern "C" {
     pub fn zkm_batch_leaf(b: *const zkm_batch, leaf_index: usize, out: *mut u64) -> c_int;
     pub fn zkm_batch_merkle_path(b: *const zkm_batch, leaf_index: usize, siblings_out: *mut u64) -> c_int;
     pub fn zkm_batch_digest_layer(b: *const zkm_batch, level: c_uint, out: *mut u64) -> c_int;
+    // stacked commitments: nstack same-shaped members in one handle (zkm_eval_openings_stack, zkm_fri_prove_stack)
+    pub fn zkm_batch_commit_values_stack(ctx: *mut zkm_ctx, values: *const *const u64, nstack: usize, ncols: usize, log_n: c_uint,
+                                         rate_bits: c_uint, cap_height: c_uint, out: *mut *mut zkm_batch, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_batch_commit_coeffs_stack(ctx: *mut zkm_ctx, coeffs: *const *const u64, nstack: usize, ncols: usize, log_n: c_uint,
+                                         rate_bits: c_uint, cap_height: c_uint, out: *mut *mut zkm_batch, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_batch_stack_size(b: *const zkm_batch) -> usize;
+    pub fn zkm_batch_stack_cap(b: *const zkm_batch, k: usize, out: *mut u64) -> c_int;
+    pub fn zkm_batch_stack_coeffs(b: *const zkm_batch, k: usize, out: *mut u64) -> c_int;
+    pub fn zkm_batch_stack_merkle_path(b: *const zkm_batch, k: usize, leaf_index: usize, leaf_out: *mut u64, siblings_out: *mut u64) -> c_int;
     pub fn zkm_field_selftest(ctx: *mut zkm_ctx, a: *const u64, b: *const u64, n: usize, out: *mut u64, err: *mut *mut c_char) -> c_int;
     // hash primitives, witness kernels
     pub fn zkm_poseidon_permute_batch(ctx: *mut zkm_ctx, states: *mut u64, k: usize, err: *mut *mut c_char) -> c_int;
@@ -464,6 +473,9 @@ extern "C" {
     pub fn zkm_fri_prove(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, oracles: *const *const zkm_batch, noracles: usize,
                          batches: *const zkm_fri_batch, nbatches: usize, challenger: *mut zkm_challenger, proof_out: *mut u64,
                          err: *mut *mut c_char) -> c_int;
+    pub fn zkm_fri_prove_stack(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, oracles: *const *const zkm_batch, noracles: usize,
+                               batches: *const zkm_fri_batch, nbatches: usize, points: *const u64, challengers: *const *mut zkm_challenger,
+                               proofs_out: *const *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_prove_openings(ctx: *mut zkm_ctx, cfg: *const zkm_stark_config, trace_batch: *const zkm_batch, aux_batch: *const zkm_batch,
                               quot_batch: *const zkm_batch, nctl_zs: usize, challenger: *mut zkm_challenger, proof_out: *mut u64,
                               err: *mut *mut c_char) -> c_int;
@@ -477,6 +489,7 @@ extern "C" {
     pub fn zkm_quotient(ctx: *mut zkm_ctx, table_id: c_int, trace: *const zkm_batch, aux: *const zkm_batch, num_helpers: *const u32, nctl_zs: usize,
                         alphas: *const u64, nalphas: usize, out_coeffs: *mut u64, err: *mut *mut c_char) -> c_int;
     pub fn zkm_eval_openings(ctx: *mut zkm_ctx, b: *const zkm_batch, zeta: *const u64, out: *mut u64, err: *mut *mut c_char) -> c_int;
+    pub fn zkm_eval_openings_stack(ctx: *mut zkm_ctx, b: *const zkm_batch, zetas: *const u64, out: *mut u64, err: *mut *mut c_char) -> c_int;
     // check_constraints (prover.rs:793-910): debugging aid, rc != 0 + "Constraint failed in <Stark>" and the first failing row
     // check_ctls (cross_table_lookup.rs:1486-1581) on the device: every lookup's looking multiset against its looked multiset
     pub fn zkm_check_ctls(ctx: *mut zkm_ctx, tables: *const zkm_table_input, ntables: usize, ctls: *const zkm_cross_table_lookup,

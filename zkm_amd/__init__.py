@@ -2423,6 +2423,34 @@ class Context:
                                     C.byref(challenger), out.ctypes.data_as(u64p), C.byref(err)), err)
         return out
 
+    def fri_prove_stack(self, oracles, batches, points, challengers, cfg=None):
+        """zkm_fri_prove_stack: K opening proofs of one instance in lock-step.  oracles = list of PolynomialBatchStack of one size K;
+        batches = the polynomial lists [[(oracle_index, polynomial_index), ...], ...] the K claims share; points[k][b] = claim k's
+        (c0, c1) of batch b; challengers = K Challenger, in/out.  Returns the K FRI proof blobs: blob k is fri_prove's on member k of
+        every oracle."""
+        cfg = cfg or self.standard_config()
+        K = len(challengers)
+        orc = (C.c_void_p * len(oracles))(*[o.h.value for o in oracles])
+        cols = (C.c_size_t * len(oracles))(*[o.ncols for o in oracles])
+        words = self.L.zkm_fri_proof_words(C.byref(cfg), oracles[0].log_n, cols, len(oracles))
+        if not words:
+            raise ZkmError("zkm_fri_proof_words: unsupported configuration")
+        keep, arr = [], (FriBatch * len(batches))()
+        for i, polys in enumerate(batches):
+            a = np.array(polys, dtype=np.uint32).reshape(-1, 2)
+            keep.append(a)
+            arr[i] = FriBatch((C.c_uint64 * 2)(0, 0), a.ctypes.data, len(a))
+        pts = np.ascontiguousarray([[int(w) for w in pt] for claim in points for pt in claim], dtype=np.uint64).reshape(-1)
+        if pts.size != K * len(batches) * 2:
+            raise ZkmError("fri_prove_stack: points must be K x nbatches x 2 words")
+        out = np.zeros((K, words), dtype=np.uint64)
+        chs = (C.c_void_p * K)(*[C.addressof(ch) for ch in challengers])
+        outs = (C.c_void_p * K)(*[out[k].ctypes.data for k in range(K)])
+        err = C.c_char_p()
+        _check(self.L.zkm_fri_prove_stack(self.h, C.byref(cfg), C.cast(orc, C.POINTER(C.c_void_p)), len(oracles), C.cast(arr, C.c_void_p),
+                                          len(batches), pts.ctypes.data, chs, outs, C.byref(err)), err)
+        return list(out)
+
     def fri_verify(self, claims, cfg=None):
         """zkm_fri_verify: plonky2's verify_fri_proof for any FriInstanceInfo, on all claims in one set of launches.  claims = list of
         FriClaim.  Returns one VerifyReport per claim (the first rejected one carries .message); a call that could not be made raises
@@ -2486,6 +2514,16 @@ class Context:
         out = np.zeros(2 * batch.ncols, dtype=np.uint64)
         err = C.c_char_p()
         _check(self.L.zkm_eval_openings(self.h, batch.h, z.ctypes.data_as(u64p), out.ctypes.data_as(u64p), C.byref(err)), err)
+        return out
+
+    def eval_openings_stack(self, stack, zetas):
+        """zkm_eval_openings_stack: member k's polynomials at zetas[k] = (c0, c1); returns nstack x (2 ncols) words"""
+        z = np.ascontiguousarray([[int(w) for w in zeta] for zeta in zetas], dtype=np.uint64).reshape(-1)
+        if z.size != 2 * stack.nstack:
+            raise ZkmError("eval_openings_stack: one point per member")
+        out = np.zeros((stack.nstack, 2 * stack.ncols), dtype=np.uint64)
+        err = C.c_char_p()
+        _check(self.L.zkm_eval_openings_stack(self.h, stack.h, z.ctypes.data, out.ctypes.data, C.byref(err)), err)
         return out
 
 
@@ -2575,6 +2613,76 @@ class PolynomialBatch:
         out = np.zeros(4 << (self.lde_bits - level), dtype=np.uint64)
         assert self.ctx.L.zkm_batch_digest_layer(self.h, level, out.ctypes.data_as(u64p)) == 0
         return out
+
+
+class PolynomialBatchStack:
+    """nstack same-shaped PolynomialBatch in one handle, built in one set of launches (zkm_batch_commit_values_stack / _coeffs_stack):
+    the oracles of Context.fri_prove_stack and eval_openings_stack.  Member k is the single PolynomialBatch of the same words."""
+
+    def __init__(self, ctx, h, nstack, ncols, log_n, rate_bits, cap_height):
+        self.ctx, self.h, self.nstack, self.ncols, self.log_n, self.rate_bits, self.cap_height = ctx, h, nstack, ncols, log_n, rate_bits, cap_height
+
+    @classmethod
+    def _commit(cls, fn, ctx, members, ncols, log_n, rate_bits, cap_height):
+        keep = [np.ascontiguousarray(m, dtype=np.uint64) if isinstance(m, (np.ndarray, list, tuple)) else m for m in members]
+        ptrs = (C.c_void_p * len(keep))(*[None if m is None else _data_ptr(m).value for m in keep])
+        h = C.c_void_p()
+        err = C.c_char_p()
+        _check(fn(ctx.h, ptrs, len(keep), ncols, log_n, rate_bits, cap_height, C.byref(h), C.byref(err)), err)
+        return cls(ctx, h, len(keep), ncols, log_n, rate_bits, cap_height)
+
+    @classmethod
+    def from_values(cls, ctx, values, ncols, log_n, rate_bits=2, cap_height=4):
+        """values = one array (or DeviceBuffer) of ncols << log_n words per member"""
+        return cls._commit(ctx.L.zkm_batch_commit_values_stack, ctx, values, ncols, log_n, rate_bits, cap_height)
+
+    @classmethod
+    def from_coeffs(cls, ctx, coeffs, ncols, log_n, rate_bits=2, cap_height=4):
+        return cls._commit(ctx.L.zkm_batch_commit_coeffs_stack, ctx, coeffs, ncols, log_n, rate_bits, cap_height)
+
+    def free(self):
+        if self.h:
+            self.ctx.L.zkm_batch_free(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+
+    def __del__(self):
+        try:
+            if self.ctx.h:
+                self.free()
+        except Exception:
+            pass
+
+    @property
+    def lde_bits(self):
+        return self.log_n + self.rate_bits
+
+    def __len__(self):
+        return int(self.ctx.L.zkm_batch_stack_size(self.h))
+
+    def cap(self, k):
+        out = np.zeros(4 << self.cap_height, dtype=np.uint64)
+        if self.ctx.L.zkm_batch_stack_cap(self.h, k, out.ctypes.data) != 0:
+            raise ZkmError("zkm_batch_stack_cap failed")
+        return out
+
+    def coeffs(self, k):
+        out = np.zeros(self.ncols << self.log_n, dtype=np.uint64)
+        if self.ctx.L.zkm_batch_stack_coeffs(self.h, k, _np_ptr(out)) != 0:
+            raise ZkmError("zkm_batch_stack_coeffs failed")
+        return out
+
+    def merkle_path(self, k, i):
+        """(leaf i of member k's tree, its Merkle path)"""
+        leaf, sib = np.zeros(self.ncols, dtype=np.uint64), np.zeros(4 * (self.lde_bits - self.cap_height), dtype=np.uint64)
+        if self.ctx.L.zkm_batch_stack_merkle_path(self.h, k, i, leaf.ctypes.data, sib.ctypes.data) != 0:
+            raise ZkmError("zkm_batch_stack_merkle_path failed")
+        return leaf, sib
 
 
 def challenger_new():

@@ -1112,6 +1112,73 @@ int zkm_batch_commit_coeffs(zkm_ctx* c, const uint64_t* coeffs, size_t ncols, un
         *out = b.release();
     });
 }
+// ---- a STACK of same-shaped commitments as a public object: member k is what the single constructor gives for sources[k] (the stacked
+// zkm_batch of zkm_internal.h, built in one set of launches).  Everything refused here is refused on the host, before the context.
+static int commit_stack(const char* what, zkm_ctx* c, const uint64_t* const* sources, size_t nstack, size_t ncols, unsigned log_n, unsigned rate_bits,
+                        unsigned cap_height, bool are_values, zkm_batch** out, char** err) {
+    return zkm_api(what, err, [&] {
+        const std::string w(what);
+        if (!sources || !out) throw std::runtime_error(w + ": null argument");
+        if (nstack == 0 || nstack > ZKM_MAX_SEG) throw std::runtime_error(w + ": 1..32 members");
+        if (ncols == 0) throw std::runtime_error(w + ": empty polynomial batch");
+        if (ncols > 65535 / nstack) throw std::runtime_error(w + ": too many stacked columns (members x columns <= 65535)");
+        if (log_n > 30 || rate_bits > 30 || log_n + rate_bits > 30) throw std::runtime_error(w + ": polynomial batch too large");
+        if (cap_height > log_n + rate_bits) throw std::runtime_error(w + ": cap_height exceeds LDE size");
+        for (size_t k = 0; k < nstack; k++)
+            if (!sources[k]) throw std::runtime_error(w + ": member " + std::to_string(k) + ": null pointer");
+        return zkm_api(what, c, err, [&] {
+            zkm_batch_ptr b = zkm_batch_new(c, ncols, nstack, log_n, rate_bits, cap_height);
+            if (nstack == 1) zkm_batch_build(b.get(), sources[0], are_values);
+            else zkm_batch_build(b.get(), nullptr, are_values, nullptr, nullptr, sources);
+            *out = b.release();
+        });
+    });
+}
+int zkm_batch_commit_values_stack(zkm_ctx* c, const uint64_t* const* values, size_t nstack, size_t ncols, unsigned log_n, unsigned rate_bits,
+                                  unsigned cap_height, zkm_batch** out, char** err) {
+    return commit_stack("zkm_batch_commit_values_stack", c, values, nstack, ncols, log_n, rate_bits, cap_height, true, out, err);
+}
+int zkm_batch_commit_coeffs_stack(zkm_ctx* c, const uint64_t* const* coeffs, size_t nstack, size_t ncols, unsigned log_n, unsigned rate_bits,
+                                  unsigned cap_height, zkm_batch** out, char** err) {
+    return commit_stack("zkm_batch_commit_coeffs_stack", c, coeffs, nstack, ncols, log_n, rate_bits, cap_height, false, out, err);
+}
+size_t zkm_batch_stack_size(const zkm_batch* b) { return b ? b->nseg : 0; }
+int zkm_batch_stack_cap(const zkm_batch* b, size_t k, uint64_t* out) {
+    if (!b || !out || k >= b->nseg) return 1;
+    const size_t capw = (size_t)4 << b->cap_height;
+    memcpy(out, b->cap.data() + k * capw, capw * sizeof(uint64_t));
+    return 0;
+}
+int zkm_batch_stack_coeffs(const zkm_batch* b, size_t k, uint64_t* out) {
+    if (!b || !out || k >= b->nseg) return 1;
+    zkm_ctx* c = b->ctx;
+    return zkm_api("zkm_batch_stack_coeffs", c, nullptr, [&] {
+        const gl_t* src = b->coeffs + k * b->coeff_seg();
+        const size_t bytes = b->coeff_seg() * sizeof(gl_t);
+        const bool dev = zkm_is_device_ptr(out);
+        zkm_scratch nat(c, b->coeff_s1 && !dev ? bytes : 8);
+        if (!b->coeff_s1) {
+            ZKM_HIP_CHECK(hipMemcpyAsync(out, src, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+        } else {
+            gl_t* d = dev ? out : nat.as<gl_t>();
+            zkm_coeff_layout_convert(c, src, b->n(), d, b->n(), b->ncols, b->log_n, /*to_natural=*/true);
+            if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, c->stream));
+        }
+        c->sync();   // (before the scratch goes back)
+    });
+}
+int zkm_batch_stack_merkle_path(const zkm_batch* b, size_t k, size_t leaf, uint64_t* leaf_out, uint64_t* sib) {
+    if (!b || k >= b->nseg || leaf >= b->N()) return 1;
+    const hipStream_t st = b->ctx->stream;
+    // the leaf: one strided gather, ncols words at stride N; the path: one digest a level from member k's tree
+    if (leaf_out && hipMemcpy2DAsync(leaf_out, sizeof(gl_t), b->lde + k * b->lde_seg() + leaf, b->N() * sizeof(gl_t), sizeof(gl_t), b->ncols,
+                                     hipMemcpyDeviceToHost, st) != hipSuccess)
+        return 1;
+    for (unsigned l = 0; sib && l < b->top(); l++)
+        if (hipMemcpyAsync(sib + 4 * l, b->digests + k * b->dig_words + b->level_off[l] + 4 * ((leaf >> l) ^ 1), 32, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return 1;
+    return hipStreamSynchronize(st) == hipSuccess ? 0 : 1;
+}
 void zkm_batch_free(zkm_batch* b) {
     if (!b) return;
     (void)hipStreamSynchronize(b->ctx->stream);
