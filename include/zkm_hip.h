@@ -188,7 +188,9 @@ int zkm_batch_commit_coeffs(zkm_ctx* ctx, const uint64_t* coeffs, size_t ncols, 
 int zkm_batch_commit_columns(zkm_ctx* ctx, const uint64_t* const* columns, size_t ncols, unsigned log_n, int columns_are_values,
                              unsigned rate_bits, unsigned cap_height, zkm_batch** out, char** err);
 void zkm_batch_free(zkm_batch* b);
-/* .merkle_tree.cap (prover.rs:180, 524, 588): 2^cap_height digests x 4 words, host out */
+/* The accessors from here to zkm_batch_digest_layer take no member: given a STACK (below) every one of them reads member 0 and
+ * writes what it writes for a single commitment -- zkm_batch_cap 4 << cap_height words, whatever the stack's size.
+ * .merkle_tree.cap (prover.rs:180, 524, 588): 2^cap_height digests x 4 words, host out */
 int zkm_batch_cap(const zkm_batch* b, uint64_t* out);
 /* .polynomials (proof.rs:311): ncols x n coefficients, natural order; out may be host or device */
 int zkm_batch_coeffs(const zkm_batch* b, uint64_t* out);
@@ -210,7 +212,8 @@ int zkm_batch_digest_layer(const zkm_batch* b, unsigned level, uint64_t* out);
  * _coeffs gives for the same words: cap, polynomials, leaves and Merkle paths.
  * Refused on the host, before the context: a NULL values or out; nstack outside 1..32; ncols = 0 or nstack x ncols > 65535;
  * log_n + rate_bits > 30; cap_height > log_n + rate_bits; a NULL member pointer (the message names the member).
- * The single-member accessors above do not know members; the ones below take the member.  zkm_batch_free frees a stack. */
+ * The accessors above read member 0 of a stack (a single commitment is a stack of one: they are the ones below at k = 0); the ones
+ * below take the member.  zkm_batch_free frees a stack. */
 int zkm_batch_commit_values_stack(zkm_ctx* ctx, const uint64_t* const* values, size_t nstack, size_t ncols, unsigned log_n, unsigned rate_bits,
                                   unsigned cap_height, zkm_batch** out, char** err);
 int zkm_batch_commit_coeffs_stack(zkm_ctx* ctx, const uint64_t* const* coeffs, size_t nstack, size_t ncols, unsigned log_n, unsigned rate_bits,
@@ -1481,6 +1484,9 @@ int zkm_prove_openings(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_batc
  * STARK oracles and the three batches of stark.rs:91-148 the output equals the FRI part of zkm_prove_openings' blob.
  * cfg->rate_bits may be 2 or 3 here and in zkm_fri_verify (3: plonky2's standard_recursion_config; the oracles are committed at the
  * same rate); the STARK entry points take 2 only.
+ * The call is zkm_fri_prove_stack (below) at ONE claim -- one body, one combination launch for all batches -- on single commitments:
+ * it refuses a stack ("zkm_fri_prove: stacked batches are internal"), takes the claim's points from the batches, and every refusal
+ * leaves the challenger, the context and its live memory as they were.
  * FRI proof blob: [0] magic "ZKMFRIPF" [1] degree_bits [2] noracles [3] cap_height [4] L fri layers [5] F final_poly_len
  *   [6] num_queries [7] rate_bits [8] arity_bits [9..15] 0 [16..23] columns of each oracle
  *   commit_phase_merkle_caps[L][C*4]  final_poly[2F]  pow_witness[1]
@@ -1496,8 +1502,9 @@ int zkm_fri_prove(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_batch* co
  * _coeffs_stack; K = zkm_batch_stack_size), the batches' polynomial lists are shared by the K claims, and
  *   points          K x nbatches x 2 words: claim k's point of batch b (the `point` fields inside `batches` are ignored)
  *   challengers[k]  in/out as zkm_fri_prove's        proofs_out[k]   zkm_fri_proof_words words, host
- * Claim k is zkm_fri_prove on member k of every oracle: every blob and every challenger state equals that call's on single
- * commitments of the same data, word for word, so zkm_fri_verify takes the K blobs as K claims.  The K proofs share every launch --
+ * Claim k is zkm_fri_prove on member k of every oracle -- the two entry points are one body, zkm_fri_prove its case K = 1 -- so every
+ * blob and every challenger state equals that call's on single commitments of the same data, word for word, and zkm_fri_verify takes
+ * the K blobs as K claims.  The K proofs share every launch --
  * one combination launch for all batches and claims, then the division, the commit phase, the proof of work and the query gather of
  * the lock-step STARK proofs -- and every transcript round trip: the call waits for the device as often as ONE zkm_fri_prove does.
  * Refused on the host before any device work, leaving every challenger, the context and its live memory as they were: a NULL
@@ -1505,7 +1512,7 @@ int zkm_fri_prove(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_batch* co
  * differ from cfg); a stack of more than 32; an empty batch; a polynomial index out of range; a NULL challenger or blob, or a point
  * word >= p, of a claim ("zkm_fri_prove_stack: claim 2: non-canonical opening point").  A call that fails later leaves the challengers
  * untouched too.  Out of scope: claims of different shapes in one call (group them, as segments are grouped by height); the pool.
- * Measured: profiles/fri_stack_time.json. */
+ * Measured: profiles/fri_stack_time.json; the single call before and after it became this body: profiles/fri_single_path_time.json. */
 int zkm_fri_prove_stack(zkm_ctx* ctx, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles, const zkm_fri_batch* batches,
                         size_t nbatches, const uint64_t* points, zkm_challenger* const* challengers, uint64_t* const* proofs_out, char** err);
 

@@ -193,22 +193,7 @@ where
         assert!(D == 2, "libzkmhip implements the quadratic extension of Goldilocks");
         assert_eq!(instance.oracles.len(), oracles.len());
         let cfg = fri_config_words(fri_params);
-        let polys: Vec<Vec<zkm_fri_poly>> = instance
-            .batches
-            .iter()
-            .map(|b: &FriBatchInfo<F, D>| {
-                b.polynomials.iter().map(|p| zkm_fri_poly { oracle: p.oracle_index as u32, poly: p.polynomial_index as u32 }).collect()
-            })
-            .collect();
-        let batches: Vec<zkm_fri_batch> = instance
-            .batches
-            .iter()
-            .zip(&polys)
-            .map(|(b, ps)| {
-                let c: [F; D] = b.point.to_basefield_array();
-                zkm_fri_batch { point: [c[0].to_canonical_u64(), c[1].to_canonical_u64()], polys: ps.as_ptr(), npolys: ps.len() }
-            })
-            .collect();
+        let (_polys, batches) = fri_instance(instance);
         let handles: Vec<*const zkm_batch> = oracles.iter().map(|o| o.hip_batch()).collect();
         let cols: Vec<usize> = oracles.iter().map(|o| o.num_polys).collect();
         let log_n = oracles[0].degree_log as u32;
@@ -343,6 +328,26 @@ where
     blob
 }
 
+/// What the FRI entry points take of a `FriInstanceInfo`: the polynomial lists as (oracle, polynomial) words, and one `zkm_fri_batch`
+/// an opening batch -- its point, and a pointer INTO the lists, which the caller keeps for as long as it uses the batches.
+fn fri_instance<F: RichField + Extendable<D>, const D: usize>(instance: &FriInstanceInfo<F, D>) -> (Vec<Vec<zkm_fri_poly>>, Vec<zkm_fri_batch>) {
+    let polys: Vec<Vec<zkm_fri_poly>> = instance
+        .batches
+        .iter()
+        .map(|b: &FriBatchInfo<F, D>| b.polynomials.iter().map(|p| zkm_fri_poly { oracle: p.oracle_index as u32, poly: p.polynomial_index as u32 }).collect())
+        .collect();
+    let batches = instance
+        .batches
+        .iter()
+        .zip(&polys)
+        .map(|(b, ps)| {
+            let c: [F; D] = b.point.to_basefield_array();
+            zkm_fri_batch { point: [c[0].to_canonical_u64(), c[1].to_canonical_u64()], polys: ps.as_ptr(), npolys: ps.len() }
+        })
+        .collect();
+    (polys, batches)
+}
+
 /// plonky2's `verify_fri_proof` (fri/verifier.rs; call site verifier.rs:276-289) on the GPU: one `zkm_fri_verify` call with one claim.
 /// Takes what `verify_fri_proof` takes -- instance, openings, the initial oracles' caps, the proof, the parameters -- and the
 /// challenger in place of the precomputed `FriChallenges`: it must stand where `prove_openings` was entered (openings observed), and
@@ -369,20 +374,7 @@ where
     let blob = fri_proof_to_blob::<F, C, D>(proof, &cfg, log_n, &oracle_cols);
     let caps: Vec<Vec<u64>> = initial_merkle_caps.iter().map(|c| c.0.iter().flat_map(|h| h.elements.iter().map(|e| e.to_canonical_u64())).collect()).collect();
     let cap_ptrs: Vec<*const u64> = caps.iter().map(|c| c.as_ptr()).collect();
-    let polys: Vec<Vec<zkm_fri_poly>> = instance
-        .batches
-        .iter()
-        .map(|b: &FriBatchInfo<F, D>| b.polynomials.iter().map(|p| zkm_fri_poly { oracle: p.oracle_index as u32, poly: p.polynomial_index as u32 }).collect())
-        .collect();
-    let batches: Vec<zkm_fri_batch> = instance
-        .batches
-        .iter()
-        .zip(&polys)
-        .map(|(b, ps)| {
-            let c: [F; D] = b.point.to_basefield_array();
-            zkm_fri_batch { point: [c[0].to_canonical_u64(), c[1].to_canonical_u64()], polys: ps.as_ptr(), npolys: ps.len() }
-        })
-        .collect();
+    let (_polys, batches) = fri_instance(instance);
     let opened: Vec<Vec<u64>> = openings
         .batches
         .iter()
@@ -526,18 +518,15 @@ where
         let k = oracles[0].len();
         assert!(instances.len() == k && challengers.len() == k, "one instance and one challenger per member");
         let cfg = fri_config_words(fri_params);
-        let list = |b: &FriBatchInfo<F, D>| -> Vec<zkm_fri_poly> {
-            b.polynomials.iter().map(|p| zkm_fri_poly { oracle: p.oracle_index as u32, poly: p.polynomial_index as u32 }).collect()
-        };
-        let polys: Vec<Vec<zkm_fri_poly>> = instances[0].batches.iter().map(list).collect();
+        let (polys, batches) = fri_instance(instances[0]);   // (the lists all claims share; a claim's points travel in `points`)
         for inst in instances {
             assert_eq!(inst.oracles.len(), oracles.len());
             assert!(inst.batches.len() == polys.len(), "instances of one shape");
             for (b, ps) in inst.batches.iter().zip(&polys) {
-                assert!(list(b).iter().zip(ps).all(|(x, y)| x.oracle == y.oracle && x.poly == y.poly) && b.polynomials.len() == ps.len(), "instances of one shape");
+                let same = b.polynomials.iter().zip(ps).all(|(p, y)| p.oracle_index as u32 == y.oracle && p.polynomial_index as u32 == y.poly);
+                assert!(same && b.polynomials.len() == ps.len(), "instances of one shape");
             }
         }
-        let batches: Vec<zkm_fri_batch> = polys.iter().map(|ps| zkm_fri_batch { point: [0, 0], polys: ps.as_ptr(), npolys: ps.len() }).collect();
         let points: Vec<u64> = instances
             .iter()
             .flat_map(|inst| inst.batches.iter())

@@ -1,5 +1,8 @@
 """GPU suite: stacked commitments (PolynomialBatchStack), their openings (Context.eval_openings_stack) and K opening proofs in lock-step
-(Context.fri_prove_stack, zkm_fri_prove_stack).  The judge of every case is the single call on single commitments of the same words:
+(Context.fri_prove_stack, zkm_fri_prove_stack).  The single and the stacked entry points are one body (the single call: one claim), so
+"the stack equals the single calls" holds that body at K members against itself at one -- member strides, per-claim indexing; what
+judges the body itself is the Python model here and the oracle's blobs in tests/test_gpu_prove.py and tests/test_gpu_lde_rates.py.
+The judge of every case is the single call on single commitments of the same words:
 member k of a stack is PolynomialBatch of member k's words, claim k of a stacked proof is fri_prove on those -- caps, polynomials,
 Merkle paths, openings, blobs and final challenger states word for word.  The stacked blobs then go through fri_verify as K claims of one
 call, and one claim a shape through the Python model (tests/fri_verify_model.py).  Six queries, random polynomials; shapes, `prove` and
@@ -109,6 +112,31 @@ def test_single_constructors_make_stacks_of_one(ctx, zkm):
     b.free()
 
 
+def test_single_accessors_on_a_stack_read_member_0_and_nothing_more(ctx, zkm):
+    """the accessors that take no member, called through the C ABI on a stack of 3: each writes what it writes for the single commitment
+    of member 0's words -- zkm_batch_cap 4 << cap_height words, not the three caps -- and leaves the words behind them alone.  Every
+    buffer is (members + 1) times what one member needs, so neither answer leaves it."""
+    log_n, ncols, rate_bits, cap_height, K = 5, 3, 2, 4, 3
+    rng = np.random.default_rng(9000)
+    words = [rng.integers(0, P, ncols << log_n, dtype=np.uint64) for _ in range(K)]
+    leaf = (1 << (log_n + rate_bits)) // 2 + 1
+    one = zkm.PolynomialBatch.from_values(ctx, words[0], ncols, log_n, rate_bits, cap_height)
+    want = {"cap": one.cap(), "coeffs": one.coeffs(), "leaf": one.leaf(leaf), "merkle_path": one.merkle_path(leaf), "digest_layer": one.digest_layer(0)}
+    one.free()
+    assert want["cap"].size == 4 << cap_height
+    sentinel = np.uint64(0xA5A55A5AC3C33C3C)
+    with zkm.PolynomialBatchStack.from_values(ctx, words, ncols, log_n, rate_bits, cap_height) as s:
+        L = ctx.L
+        for name, call in (("cap", lambda out: L.zkm_batch_cap(s.h, out)), ("coeffs", lambda out: L.zkm_batch_coeffs(s.h, out)),
+                           ("leaf", lambda out: L.zkm_batch_leaf(s.h, leaf, out)), ("merkle_path", lambda out: L.zkm_batch_merkle_path(s.h, leaf, out)),
+                           ("digest_layer", lambda out: L.zkm_batch_digest_layer(s.h, 0, out))):
+            size = want[name].size
+            buf = np.full((K + 1) * size, sentinel, dtype=np.uint64)
+            assert call(buf.ctypes.data) == 0, name
+            assert np.array_equal(buf[:size], want[name]), "%s: not member 0's" % name
+            assert (buf[size:] == sentinel).all(), "%s: words behind the answer were written" % name
+
+
 # ---------------------------------------------------------------- 2. openings
 @pytest.mark.parametrize("log_n,ncols,K,rate_bits", [(7, 9, 5, 3), (18, 2, 2, 2)])
 def test_openings_of_a_stack(ctx, zkm, log_n, ncols, K, rate_bits):
@@ -138,7 +166,8 @@ def test_stacked_proofs_are_the_single_calls(ctx, zkm, name, K):
     reordered polynomials: own seed, own points and own starting challenger a claim"""
     cfg, log_n, cols, batches = SHAPES[name](ctx)
     seeds = [8000 + 100 * list(SHAPES).index(name) + 10 * K + k for k in range(K)]
-    check_against_single_calls(ctx, zkm, cfg, log_n, cols, batches, seeds, model=K == 2)      # (the model: one claim a shape)
+    check_against_single_calls(ctx, zkm, cfg, log_n, cols, batches, seeds, model=K in (1, 2))   # (the model: one claim at K = 1 -- the single
+                                                                                                # entry's own blob -- and one at K = 2, a shape)
 
 
 def test_a_full_stack_of_32(ctx, zkm):
@@ -194,7 +223,45 @@ def test_a_stacked_call_waits_as_often_as_one_single_call(ctx, zkm):
     assert got == W1, (got, W1)
 
 
+# the waits of one fri_prove call at the plonk7 shape, by seed, measured on the parent commit 791000c ("Lock-step FRI for any instance"),
+# where the single entry had its own body
+WAITS_OF_A_SINGLE_CALL_AT_791000C = {8800: 4, 8801: 4, 8802: 4}
+
+
+def test_a_single_call_waits_no_more_often_than_it_did(ctx, zkm):
+    cfg, log_n, cols, batches = SHAPES["plonk7"](ctx)
+    for seed, parent in WAITS_OF_A_SINGLE_CALL_AT_791000C.items():
+        oracles = [zkm.PolynomialBatch.from_values(ctx, v, k, log_n, cfg.rate_bits, cfg.cap_height) for v, k in zip(member_values(seed, cols, log_n), cols)]
+        w0 = ctx.host_waits()
+        ctx.fri_prove(oracles, claim_batches(batches, 0), start_challenger(zkm, seed), cfg)
+        got = ctx.host_waits() - w0
+        for b in oracles:
+            b.free()
+        assert got <= parent, (seed, got, parent)
+
+
 # ---------------------------------------------------------------- 6. refusals and atomicity
+def test_the_single_entries_refuse_a_stack(ctx, zkm):
+    """zkm_fri_prove and zkm_eval_openings given stacks of 2: refused in their own words, the challenger bit for bit and the context's
+    memory as they were"""
+    cfg, log_n, cols = config(ctx), 5, [3, 2]
+    rng = np.random.default_rng(9100)
+    words = [[rng.integers(0, P, c << log_n, dtype=np.uint64) for c in cols] for _ in range(2)]
+    stacks = commit_stacks(ctx, zkm, cfg, log_n, cols, words)
+    batches = [((5, 6), [(0, 0), (1, 1), (0, 2)]), ((7, 8), [(1, 0)])]
+    for call, want in ((lambda ch: ctx.fri_prove(stacks, batches, ch, cfg), "zkm_fri_prove: stacked batches are internal"),
+                       (lambda ch: ctx.eval_openings(stacks[0], (5, 6)), "zkm_eval_openings: stacked batches are internal")):
+        ch = start_challenger(zkm, 9100)
+        before, memory = bytes(ch), ctx.memory()
+        with pytest.raises(zkm.ZkmError) as e:
+            call(ch)
+        assert want in str(e.value), (want, str(e.value))
+        assert bytes(ch) == before
+        assert ctx.memory() == memory
+    for s in stacks:
+        s.free()
+
+
 def test_refusals_leave_challengers_memory_and_context_as_they_were(ctx, zkm):
     """a stack of 33 (refused where a stack is made: the claims of a call ARE its oracles' members), oracles of different stack sizes, a
     polynomial index out of range, a non-canonical point in claim 2; after each the callers' challengers and the context's live bytes are

@@ -10,7 +10,9 @@ tests, and 28 (standard_recursion_config) beside them.  K = 8 claims, each with 
 The two sides of a comparison run in the same process, alternating (the order swaps every round), REPS (default 20) timed rounds after a
 warm-up round; a figure is the median with min and max.  Host waits are zkm_ctx_host_waits around the call(s); launch scopes are the
 records of zkm_profile_* in one extra round with the profiler on (a scope is one launch or a small group of launches), outside the timed
-rounds.  Writes profiles/fri_stack_time.json (or OUT)."""
+rounds.  Writes profiles/fri_stack_time.json (or OUT).  LOG_N (default 12) is the height; ZKM_HIP_LIB, as everywhere, the library: the
+"single" arms of runs on two builds are how profiles/fri_single_path_time.json compares the single call before and after it became
+the stacked body at one claim (tools/fri_single_path_compare.py)."""
 import json
 import os
 import sys
@@ -23,7 +25,7 @@ sys.path.insert(0, ROOT)
 import zkm_amd  # noqa: E402
 
 P = zkm_amd.P
-K, LOG_N, COLS = 8, 12, [7, 9, 5, 4]
+K, LOG_N, COLS = 8, int(os.environ.get("LOG_N", "12")), [7, 9, 5, 4]
 LISTS = [[(o, c) for o in range(4) for c in range(COLS[o])], [(2, 0), (2, 1)]]
 
 

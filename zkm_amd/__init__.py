@@ -2402,25 +2402,30 @@ class Context:
                                               C.byref(total), offs, chal.ctypes.data_as(u64p), C.byref(err)), err)
         return proofs, chal, list(offs)
 
-    def fri_prove(self, oracles, batches, challenger, cfg=None):
-        """PolynomialBatch::prove_openings for an arbitrary FriInstanceInfo: oracles = list of PolynomialBatch, batches = list of
-        ((point_c0, point_c1), [(oracle_index, polynomial_index), ...]).  Returns the FRI proof blob (layout in zkm_hip.h)."""
-        cfg = cfg or self.standard_config()
+    def _fri_instance(self, oracles, batches, cfg):
+        """what zkm_fri_prove and zkm_fri_prove_stack take of a FRI instance: (oracle handles, number of proof words, FriBatch array, the
+        arrays it points into); batches = [((c0, c1), polynomial list), ...]"""
         orc = (C.c_void_p * len(oracles))(*[o.h.value for o in oracles])
         cols = (C.c_size_t * len(oracles))(*[o.ncols for o in oracles])
         words = self.L.zkm_fri_proof_words(C.byref(cfg), oracles[0].log_n, cols, len(oracles))
         if not words:
             raise ZkmError("zkm_fri_proof_words: unsupported configuration")
-
         keep, arr = [], (FriBatch * len(batches))()
         for i, (pt, polys) in enumerate(batches):
             a = np.array(polys, dtype=np.uint32).reshape(-1, 2)
             keep.append(a)
             arr[i] = FriBatch((C.c_uint64 * 2)(int(pt[0]), int(pt[1])), a.ctypes.data, len(a))
+        return C.cast(orc, C.POINTER(C.c_void_p)), words, C.cast(arr, C.c_void_p), (orc, arr, keep)
+
+    def fri_prove(self, oracles, batches, challenger, cfg=None):
+        """PolynomialBatch::prove_openings for an arbitrary FriInstanceInfo: oracles = list of PolynomialBatch, batches = list of
+        ((point_c0, point_c1), [(oracle_index, polynomial_index), ...]).  Returns the FRI proof blob (layout in zkm_hip.h)."""
+        cfg = cfg or self.standard_config()
+        orc, words, arr, keep = self._fri_instance(oracles, batches, cfg)
         out = np.zeros(words, dtype=np.uint64)
         err = C.c_char_p()
-        _check(self.L.zkm_fri_prove(self.h, C.byref(cfg), C.cast(orc, C.POINTER(C.c_void_p)), len(oracles), C.cast(arr, C.c_void_p), len(batches),
-                                    C.byref(challenger), out.ctypes.data_as(u64p), C.byref(err)), err)
+        _check(self.L.zkm_fri_prove(self.h, C.byref(cfg), orc, len(oracles), arr, len(batches), C.byref(challenger), out.ctypes.data_as(u64p),
+                                    C.byref(err)), err)
         return out
 
     def fri_prove_stack(self, oracles, batches, points, challengers, cfg=None):
@@ -2430,16 +2435,7 @@ class Context:
         every oracle."""
         cfg = cfg or self.standard_config()
         K = len(challengers)
-        orc = (C.c_void_p * len(oracles))(*[o.h.value for o in oracles])
-        cols = (C.c_size_t * len(oracles))(*[o.ncols for o in oracles])
-        words = self.L.zkm_fri_proof_words(C.byref(cfg), oracles[0].log_n, cols, len(oracles))
-        if not words:
-            raise ZkmError("zkm_fri_proof_words: unsupported configuration")
-        keep, arr = [], (FriBatch * len(batches))()
-        for i, polys in enumerate(batches):
-            a = np.array(polys, dtype=np.uint32).reshape(-1, 2)
-            keep.append(a)
-            arr[i] = FriBatch((C.c_uint64 * 2)(0, 0), a.ctypes.data, len(a))
+        orc, words, arr, keep = self._fri_instance(oracles, [((0, 0), polys) for polys in batches], cfg)
         pts = np.ascontiguousarray([[int(w) for w in pt] for claim in points for pt in claim], dtype=np.uint64).reshape(-1)
         if pts.size != K * len(batches) * 2:
             raise ZkmError("fri_prove_stack: points must be K x nbatches x 2 words")
@@ -2447,8 +2443,8 @@ class Context:
         chs = (C.c_void_p * K)(*[C.addressof(ch) for ch in challengers])
         outs = (C.c_void_p * K)(*[out[k].ctypes.data for k in range(K)])
         err = C.c_char_p()
-        _check(self.L.zkm_fri_prove_stack(self.h, C.byref(cfg), C.cast(orc, C.POINTER(C.c_void_p)), len(oracles), C.cast(arr, C.c_void_p),
-                                          len(batches), pts.ctypes.data, chs, outs, C.byref(err)), err)
+        _check(self.L.zkm_fri_prove_stack(self.h, C.byref(cfg), orc, len(oracles), arr, len(batches), pts.ctypes.data, chs, outs,
+                                          C.byref(err)), err)
         return list(out)
 
     def fri_verify(self, claims, cfg=None):
@@ -2527,44 +2523,29 @@ class Context:
         return out
 
 
-class PolynomialBatch:
-    """== plonky2 PolynomialBatch<F, PoseidonGoldilocksConfig, 2> living in HBM."""
+class _BatchHandle:
+    """owner of one zkm_batch handle -- a single commitment or a stack of them"""
 
     def __init__(self, ctx, h, ncols, log_n, rate_bits, cap_height):
         self.ctx, self.h, self.ncols, self.log_n, self.rate_bits, self.cap_height = ctx, h, ncols, log_n, rate_bits, cap_height
 
-    @classmethod
-    def from_values(cls, ctx, values, ncols, log_n, rate_bits=2, cap_height=4):
-        h = C.c_void_p()
-        err = C.c_char_p()
-        _check(ctx.L.zkm_batch_commit_values(ctx.h, _data_ptr(values), ncols, log_n, rate_bits, cap_height, C.byref(h),
-                                             C.byref(err)), err)
-        return cls(ctx, h, ncols, log_n, rate_bits, cap_height)
-
-    @classmethod
-    def from_columns(cls, ctx, columns, log_n, values=True, rate_bits=2, cap_height=4):
-        """from_values / from_coeffs from one array per column (zkm_batch_commit_columns): the shape of the reference's
-        Vec<PolynomialValues<F>> -- nothing is flattened on the host."""
-        keep = [c if isinstance(c, (DeviceBuffer, StagedTrace)) else np.ascontiguousarray(c, dtype=np.uint64) for c in columns]
-        ptrs = (C.c_void_p * len(keep))(*[_data_ptr(c).value for c in keep])
-        h = C.c_void_p()
-        err = C.c_char_p()
-        _check(ctx.L.zkm_batch_commit_columns(ctx.h, ptrs, len(keep), log_n, int(bool(values)), rate_bits, cap_height, C.byref(h),
-                                              C.byref(err)), err)
-        return cls(ctx, h, len(keep), log_n, rate_bits, cap_height)
-
-    @classmethod
-    def from_coeffs(cls, ctx, coeffs, ncols, log_n, rate_bits=2, cap_height=4):
-        h = C.c_void_p()
-        err = C.c_char_p()
-        _check(ctx.L.zkm_batch_commit_coeffs(ctx.h, _data_ptr(coeffs), ncols, log_n, rate_bits, cap_height, C.byref(h),
-                                             C.byref(err)), err)
-        return cls(ctx, h, ncols, log_n, rate_bits, cap_height)
+    @staticmethod
+    def _commit(call):
+        """the handle one zkm_batch_commit_* entry makes: call(&handle, &err) -> status"""
+        h, err = C.c_void_p(), C.c_char_p()
+        _check(call(C.byref(h), C.byref(err)), err)
+        return h
 
     def free(self):
         if self.h:
             self.ctx.L.zkm_batch_free(self.h)
             self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
 
     def __del__(self):
         try:
@@ -2576,6 +2557,29 @@ class PolynomialBatch:
     @property
     def lde_bits(self):
         return self.log_n + self.rate_bits
+
+
+class PolynomialBatch(_BatchHandle):
+    """== plonky2 PolynomialBatch<F, PoseidonGoldilocksConfig, 2> living in HBM."""
+
+    @classmethod
+    def from_values(cls, ctx, values, ncols, log_n, rate_bits=2, cap_height=4):
+        h = cls._commit(lambda h, err: ctx.L.zkm_batch_commit_values(ctx.h, _data_ptr(values), ncols, log_n, rate_bits, cap_height, h, err))
+        return cls(ctx, h, ncols, log_n, rate_bits, cap_height)
+
+    @classmethod
+    def from_columns(cls, ctx, columns, log_n, values=True, rate_bits=2, cap_height=4):
+        """from_values / from_coeffs from one array per column (zkm_batch_commit_columns): the shape of the reference's
+        Vec<PolynomialValues<F>> -- nothing is flattened on the host."""
+        keep = [c if isinstance(c, (DeviceBuffer, StagedTrace)) else np.ascontiguousarray(c, dtype=np.uint64) for c in columns]
+        ptrs = (C.c_void_p * len(keep))(*[_data_ptr(c).value for c in keep])
+        h = cls._commit(lambda h, err: ctx.L.zkm_batch_commit_columns(ctx.h, ptrs, len(keep), log_n, int(bool(values)), rate_bits, cap_height, h, err))
+        return cls(ctx, h, len(keep), log_n, rate_bits, cap_height)
+
+    @classmethod
+    def from_coeffs(cls, ctx, coeffs, ncols, log_n, rate_bits=2, cap_height=4):
+        h = cls._commit(lambda h, err: ctx.L.zkm_batch_commit_coeffs(ctx.h, _data_ptr(coeffs), ncols, log_n, rate_bits, cap_height, h, err))
+        return cls(ctx, h, ncols, log_n, rate_bits, cap_height)
 
     def cap(self):
         out = np.zeros(4 << self.cap_height, dtype=np.uint64)
@@ -2615,52 +2619,29 @@ class PolynomialBatch:
         return out
 
 
-class PolynomialBatchStack:
+class PolynomialBatchStack(_BatchHandle):
     """nstack same-shaped PolynomialBatch in one handle, built in one set of launches (zkm_batch_commit_values_stack / _coeffs_stack):
     the oracles of Context.fri_prove_stack and eval_openings_stack.  Member k is the single PolynomialBatch of the same words."""
 
     def __init__(self, ctx, h, nstack, ncols, log_n, rate_bits, cap_height):
-        self.ctx, self.h, self.nstack, self.ncols, self.log_n, self.rate_bits, self.cap_height = ctx, h, nstack, ncols, log_n, rate_bits, cap_height
+        super().__init__(ctx, h, ncols, log_n, rate_bits, cap_height)
+        self.nstack = nstack
 
     @classmethod
-    def _commit(cls, fn, ctx, members, ncols, log_n, rate_bits, cap_height):
+    def _commit_members(cls, fn, ctx, members, ncols, log_n, rate_bits, cap_height):
         keep = [np.ascontiguousarray(m, dtype=np.uint64) if isinstance(m, (np.ndarray, list, tuple)) else m for m in members]
         ptrs = (C.c_void_p * len(keep))(*[None if m is None else _data_ptr(m).value for m in keep])
-        h = C.c_void_p()
-        err = C.c_char_p()
-        _check(fn(ctx.h, ptrs, len(keep), ncols, log_n, rate_bits, cap_height, C.byref(h), C.byref(err)), err)
+        h = cls._commit(lambda h, err: fn(ctx.h, ptrs, len(keep), ncols, log_n, rate_bits, cap_height, h, err))
         return cls(ctx, h, len(keep), ncols, log_n, rate_bits, cap_height)
 
     @classmethod
     def from_values(cls, ctx, values, ncols, log_n, rate_bits=2, cap_height=4):
         """values = one array (or DeviceBuffer) of ncols << log_n words per member"""
-        return cls._commit(ctx.L.zkm_batch_commit_values_stack, ctx, values, ncols, log_n, rate_bits, cap_height)
+        return cls._commit_members(ctx.L.zkm_batch_commit_values_stack, ctx, values, ncols, log_n, rate_bits, cap_height)
 
     @classmethod
     def from_coeffs(cls, ctx, coeffs, ncols, log_n, rate_bits=2, cap_height=4):
-        return cls._commit(ctx.L.zkm_batch_commit_coeffs_stack, ctx, coeffs, ncols, log_n, rate_bits, cap_height)
-
-    def free(self):
-        if self.h:
-            self.ctx.L.zkm_batch_free(self.h)
-            self.h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.free()
-
-    def __del__(self):
-        try:
-            if self.ctx.h:
-                self.free()
-        except Exception:
-            pass
-
-    @property
-    def lde_bits(self):
-        return self.log_n + self.rate_bits
+        return cls._commit_members(ctx.L.zkm_batch_commit_coeffs_stack, ctx, coeffs, ncols, log_n, rate_bits, cap_height)
 
     def __len__(self):
         return int(self.ctx.L.zkm_batch_stack_size(self.h))

@@ -1077,6 +1077,16 @@ zkm_batch_ptr zkm_batch_new(zkm_ctx* c, size_t ncols, size_t nseg, unsigned log_
     return b;
 }
 
+// a new batch committed to srcs[0 .. nseg): one matrix goes through zkm_batch_build's single form (the pipelined ingest is one of its paths),
+// a stack through the per-member sources
+zkm_batch_ptr zkm_batch_commit(zkm_ctx* c, const uint64_t* const* srcs, size_t nseg, size_t ncols, unsigned log_n, unsigned rate_bits,
+                               unsigned cap_height, bool are_values) {
+    zkm_batch_ptr b = zkm_batch_new(c, ncols, nseg, log_n, rate_bits, cap_height);
+    if (nseg == 1) zkm_batch_build(b.get(), srcs[0], are_values);
+    else zkm_batch_build(b.get(), nullptr, are_values, nullptr, nullptr, srcs);
+    return b;
+}
+
 // from_values keeping the uploaded values in dev_values (see zkm_batch_build); throws
 zkm_batch* zkm_batch_commit_values_keep(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, unsigned rate_bits,
                                         unsigned cap_height, gl_t* dev_values, const uint64_t* const* columns) {
@@ -1089,11 +1099,7 @@ extern "C" {
 
 int zkm_batch_commit_values(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, unsigned rate_bits,
                             unsigned cap_height, zkm_batch** out, char** err) {
-    return zkm_api("zkm_batch_commit_values", c, err, [&] {
-        zkm_batch_ptr b = zkm_batch_new(c, ncols, 1, log_n, rate_bits, cap_height);
-        zkm_batch_build(b.get(), values, true);
-        *out = b.release();
-    });
+    return zkm_api("zkm_batch_commit_values", c, err, [&] { *out = zkm_batch_commit(c, &values, 1, ncols, log_n, rate_bits, cap_height, true).release(); });
 }
 int zkm_batch_commit_columns(zkm_ctx* c, const uint64_t* const* columns, size_t ncols, unsigned log_n, int columns_are_values,
                              unsigned rate_bits, unsigned cap_height, zkm_batch** out, char** err) {
@@ -1106,11 +1112,7 @@ int zkm_batch_commit_columns(zkm_ctx* c, const uint64_t* const* columns, size_t 
 }
 int zkm_batch_commit_coeffs(zkm_ctx* c, const uint64_t* coeffs, size_t ncols, unsigned log_n, unsigned rate_bits,
                             unsigned cap_height, zkm_batch** out, char** err) {
-    return zkm_api("zkm_batch_commit_coeffs", c, err, [&] {
-        zkm_batch_ptr b = zkm_batch_new(c, ncols, 1, log_n, rate_bits, cap_height);
-        zkm_batch_build(b.get(), coeffs, false);
-        *out = b.release();
-    });
+    return zkm_api("zkm_batch_commit_coeffs", c, err, [&] { *out = zkm_batch_commit(c, &coeffs, 1, ncols, log_n, rate_bits, cap_height, false).release(); });
 }
 // ---- a STACK of same-shaped commitments as a public object: member k is what the single constructor gives for sources[k] (the stacked
 // zkm_batch of zkm_internal.h, built in one set of launches).  Everything refused here is refused on the host, before the context.
@@ -1126,12 +1128,7 @@ static int commit_stack(const char* what, zkm_ctx* c, const uint64_t* const* sou
         if (cap_height > log_n + rate_bits) throw std::runtime_error(w + ": cap_height exceeds LDE size");
         for (size_t k = 0; k < nstack; k++)
             if (!sources[k]) throw std::runtime_error(w + ": member " + std::to_string(k) + ": null pointer");
-        return zkm_api(what, c, err, [&] {
-            zkm_batch_ptr b = zkm_batch_new(c, ncols, nstack, log_n, rate_bits, cap_height);
-            if (nstack == 1) zkm_batch_build(b.get(), sources[0], are_values);
-            else zkm_batch_build(b.get(), nullptr, are_values, nullptr, nullptr, sources);
-            *out = b.release();
-        });
+        return zkm_api(what, c, err, [&] { *out = zkm_batch_commit(c, sources, nstack, ncols, log_n, rate_bits, cap_height, are_values).release(); });
     });
 }
 int zkm_batch_commit_values_stack(zkm_ctx* c, const uint64_t* const* values, size_t nstack, size_t ncols, unsigned log_n, unsigned rate_bits,
@@ -1152,6 +1149,7 @@ int zkm_batch_stack_cap(const zkm_batch* b, size_t k, uint64_t* out) {
 int zkm_batch_stack_coeffs(const zkm_batch* b, size_t k, uint64_t* out) {
     if (!b || !out || k >= b->nseg) return 1;
     zkm_ctx* c = b->ctx;
+    // .polynomials in NATURAL order, whatever layout the batch keeps them in
     return zkm_api("zkm_batch_stack_coeffs", c, nullptr, [&] {
         const gl_t* src = b->coeffs + k * b->coeff_seg();
         const size_t bytes = b->coeff_seg() * sizeof(gl_t);
@@ -1188,30 +1186,10 @@ void zkm_batch_free(zkm_batch* b) {
     b->ctx->release(b->digests);
     delete b;
 }
-// (the accessors have no message: a null batch, an index out of range or a failed copy is status 1)
-int zkm_batch_cap(const zkm_batch* b, uint64_t* out) {
-    if (!b) return 1;
-    memcpy(out, b->cap.data(), b->cap.size() * sizeof(uint64_t));
-    return 0;
-}
-int zkm_batch_coeffs(const zkm_batch* b, uint64_t* out) {
-    // .polynomials in NATURAL order, whatever layout the batch keeps them in
-    zkm_ctx* c = b ? b->ctx : nullptr;
-    return zkm_api("zkm_batch_coeffs", c, nullptr, [&] {
-        const size_t bytes = b->ncols * b->n() * sizeof(gl_t);
-        const bool dev = zkm_is_device_ptr(out);
-        if (!b->coeff_s1) {
-            ZKM_HIP_CHECK(hipMemcpyAsync(out, b->coeffs, bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-        } else {
-            zkm_scratch nat(c, dev ? 8 : bytes);
-            gl_t* d = dev ? out : nat.as<gl_t>();
-            zkm_coeff_layout_convert(c, b->coeffs, b->n(), d, b->n(), b->ncols, b->log_n, /*to_natural=*/true);
-            if (!dev) ZKM_HIP_CHECK(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, c->stream));
-            c->sync();   // (the scratch goes back to the allocator on return)
-        }
-        c->sync();
-    });
-}
+// (the accessors have no message: a null batch, an index out of range or a failed copy is status 1.)  The single accessors read member 0
+// of whatever they are given: a single commitment is a stack of one
+int zkm_batch_cap(const zkm_batch* b, uint64_t* out) { return zkm_batch_stack_cap(b, 0, out); }
+int zkm_batch_coeffs(const zkm_batch* b, uint64_t* out) { return zkm_batch_stack_coeffs(b, 0, out); }
 int zkm_batch_leaf(const zkm_batch* b, size_t leaf, uint64_t* out) {
     if (!b || leaf >= b->N()) return 1;
     // one strided gather: ncols words at stride N
@@ -1245,14 +1223,7 @@ int zkm_batch_lde_rows(const zkm_batch* b, size_t index_start, size_t step, size
         c->sync();
     });
 }
-int zkm_batch_merkle_path(const zkm_batch* b, size_t leaf, uint64_t* sib) {
-    if (!b || leaf >= b->N()) return 1;
-    for (unsigned l = 0; l < b->top(); l++)
-        if (hipMemcpyAsync(sib + 4 * l, b->digests + b->level_off[l] + 4 * ((leaf >> l) ^ 1), 32, hipMemcpyDeviceToHost,
-                           b->ctx->stream) != hipSuccess)
-            return 1;
-    return hipStreamSynchronize(b->ctx->stream) == hipSuccess ? 0 : 1;
-}
+int zkm_batch_merkle_path(const zkm_batch* b, size_t leaf, uint64_t* sib) { return zkm_batch_stack_merkle_path(b, 0, leaf, nullptr, sib); }
 int zkm_batch_digest_layer(const zkm_batch* b, unsigned level, uint64_t* out) {
     if (!b || level > b->top()) return 1;
     size_t words = (size_t)4 << (b->lde_bits() - level);

@@ -1450,11 +1450,8 @@ static void begin_blobs(table_proof& p) {
 // where they lie)
 static zkm_batch_ptr commit_values(zkm_ctx* c, const zkm_stark_config* cfg, const char* stage, size_t ncols, unsigned log_n, const uint64_t* const* srcs,
                                    size_t nseg) {
-    zkm_batch_ptr b = zkm_batch_new(c, ncols, nseg, log_n, cfg->rate_bits, cfg->cap_height);
     zkm_prof_scope st(c, stage);
-    if (nseg == 1) zkm_batch_build(b.get(), srcs[0], true);
-    else zkm_batch_build(b.get(), nullptr, true, nullptr, nullptr, srcs);
-    return b;
+    return zkm_batch_commit(c, srcs, nseg, ncols, log_n, cfg->rate_bits, cfg->cap_height, true);
 }
 
 // ---- stage: the trace commitment from values (prover.rs:146-163, done by the caller in the reference)
@@ -1610,35 +1607,21 @@ void zkm_prove_table_from_commitments(zkm_ctx* c, int table_id, const zkm_stark_
 // zkm_transcripts, zkm_internal.h)
 
 // ---- PolynomialBatch::prove_openings for an arbitrary FriInstanceInfo (plonky2 fri/oracle.rs; instance of the STARKs: stark.rs:91-148)
-// composite of one batch: sum_j alpha^j p_j, polynomials named by pointer (any oracle, any column)
-__global__ __launch_bounds__(256) void k_fri_combine_generic(const gl_t* const* __restrict__ polys, size_t npolys, const gl_t* __restrict__ apow,
-                                                             size_t n, gl_t* __restrict__ c0, gl_t* __restrict__ c1) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    gl_t a0 = 0, a1 = 0;
-    for (size_t j = 0; j < npolys; j++) {
-        gl_t v = polys[j][i];
-        a0 = gl_add(a0, gl_mul(v, apow[2 * j]));
-        a1 = gl_add(a1, gl_mul(v, apow[2 * j + 1]));
-    }
-    c0[i] = a0;
-    c1[i] = a1;
-}
-
-// ... of every batch of every claim of a stack, in ONE launch (zkm_fri_prove_stack): blockIdx.y = batch, blockIdx.z = claim.  The K claims
+// composite of one batch: sum_j alpha^j p_j, polynomials named by (oracle, column) -- any oracle, any column -- for every batch of every
+// claim in ONE launch (zkm_fri_prove: one claim; zkm_fri_prove_stack: one a member): blockIdx.y = batch, blockIdx.z = claim.  The claims
 // share the instance, so the (oracle, polynomial) lists lie once in device memory, batch after batch; an oracle is a base pointer and the
 // words from one member's polynomials to the next one's, as in gather_args -- no pointer table per claim.  A workgroup's lanes share
 // claim, batch and list: the list entries and the claim's alpha powers are read through the constant address space (written before the
 // launch, read-only in it: scalar loads, as zkm_seg_desc's), the oracle's base and stride come from the kernel argument by a uniform
-// index, and the only per-lane traffic is the coefficient itself -- adjacent lanes, adjacent coefficients.  The products are
-// k_fri_combine_generic's, in its order: the composites are the single call's word for word.
+// index, and the only per-lane traffic is the coefficient itself -- adjacent lanes, adjacent coefficients.  The products run down the
+// list in its order, whatever the number of claims: claim k's composites are those of a call with that claim alone, word for word.
 static_assert(sizeof(zkm_fri_poly) == 8, "a list entry is read as one 64-bit word");
-struct fri_stack_args {
+struct fri_list_args {
     const gl_t* base[ZKM_FRI_MAX_ORACLES];   // oracle o: member 0's coefficients
     size_t member[ZKM_FRI_MAX_ORACLES];      // ... and the words to the next member's (ncols x n)
     uint32_t first[FRI_MAX_BATCHES + 1];     // batch b's list: polys[first[b] .. first[b + 1])
 };
-__global__ __launch_bounds__(256) void k_fri_combine_stack(fri_stack_args A, const zkm_fri_poly* __restrict__ polys,
+__global__ __launch_bounds__(256) void k_fri_combine_lists(fri_list_args A, const zkm_fri_poly* __restrict__ polys,
                                                            const gl_t* __restrict__ apow /* [claim][apow_seg]: alpha^j as (c0, c1) */, size_t apow_seg,
                                                            size_t n, gl_t* __restrict__ comp /* [claim][batch][2][n] */) {
     typedef const __attribute__((address_space(4))) uint64_t* list_ptr;   // (an entry is one 64-bit word: oracle below, polynomial above)
@@ -1759,136 +1742,108 @@ size_t zkm_fri_proof_words(const zkm_stark_config* cfg, unsigned log_n, const si
     return zkm_api("zkm_fri_proof_words", nullptr, [&] { y = zkm_fri_blob_describe(cfg, log_n, oracle_cols, noracles); }) ? 0 : y.total();
 }
 
+// K opening proofs of one instance in LOCK-STEP, the body of zkm_fri_prove (K = 1 on single commitments) and zkm_fri_prove_stack: the
+// oracles are stacks of K members, claim k opens member k of every oracle at points[(k * nbatches + b) * 2 ..] on challengers[k] into
+// proofs_out[k].  One combination launch for all batches and claims, then fri_finish on a proof_stack of K.  `who` starts every
+// refusal; `name_claims`: a refusal of one claim's arguments says which.  Everything is refused before a blob is written, and the
+// callers' challengers move only when every proof exists.
+static void fri_prove_claims(const char* who_, bool name_claims, zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles,
+                             const zkm_fri_batch* batches, size_t nbatches, size_t K, const uint64_t* points, zkm_challenger* const* challengers,
+                             uint64_t* const* proofs_out) {
+    const std::string who(who_);
+    if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error(who + ": 1..8 oracles");
+    if (nbatches > FRI_MAX_BATCHES) throw std::runtime_error(who + ": 1..8 opening batches");
+    for (size_t o = 0; o < noracles; o++)
+        if (!oracles[o]) throw std::runtime_error(who + ": null argument");
+    if (K == 0 || K > ZKM_MAX_SEG) throw std::runtime_error(who + ": 1..32 claims");
+    const unsigned log_n = oracles[0]->log_n;
+    size_t cols[ZKM_FRI_MAX_ORACLES];
+    for (size_t o = 0; o < noracles; o++) {
+        if (oracles[o]->nseg != K) throw std::runtime_error(who + ": oracles must be stacks of one size");
+        if (oracles[o]->log_n != log_n || oracles[o]->rate_bits != cfg->rate_bits || oracles[o]->cap_height != cfg->cap_height ||
+            oracles[o]->coeff_s1 != oracles[0]->coeff_s1)
+            throw std::runtime_error(who + ": oracles must share degree, rate and cap height with the config");
+        cols[o] = oracles[o]->ncols;
+    }
+    const zkm_fri_part y = zkm_fri_blob_describe(cfg, log_n, cols, noracles);
+    const size_t n = (size_t)1 << log_n;
+    fri_list_args A{};
+    std::vector<zkm_fri_poly> list;
+    size_t maxp = 0;
+    for (size_t b = 0; b < nbatches; b++) {
+        if (batches[b].npolys == 0 || !batches[b].polys) throw std::runtime_error(who + ": empty batch");
+        for (size_t j = 0; j < batches[b].npolys; j++)
+            if (batches[b].polys[j].oracle >= noracles || batches[b].polys[j].poly >= cols[batches[b].polys[j].oracle])
+                throw std::runtime_error(who + ": polynomial index out of range");
+        list.insert(list.end(), batches[b].polys, batches[b].polys + batches[b].npolys);
+        if (list.size() > UINT32_MAX) throw std::runtime_error(who + ": too many polynomials");
+        A.first[b + 1] = (uint32_t)list.size();
+        maxp = std::max(maxp, batches[b].npolys);
+    }
+    for (size_t k = 0; k < K; k++) {
+        const std::string claim = name_claims ? who + ": claim " + std::to_string(k) : who;
+        if (!challengers[k] || !proofs_out[k]) throw std::runtime_error(claim + ": null argument");
+        for (size_t w = 0; w < 2 * nbatches; w++)
+            if (points[k * 2 * nbatches + w] >= GL_P) throw std::runtime_error(claim + ": non-canonical opening point");
+    }
+    for (size_t o = 0; o < noracles; o++) { A.base[o] = oracles[o]->coeffs; A.member[o] = oracles[o]->coeff_seg(); }
+    for (size_t k = 0; k < K; k++) {
+        memset(proofs_out[k], 0, y.total() * sizeof(uint64_t));
+        zkm_fri_blob_header_write(proofs_out[k], cfg, log_n, y);
+    }
+
+    zkm_transcripts tr(challengers, K);
+    const std::vector<uint64_t*> blobs(proofs_out, proofs_out + K);
+    proof_stack f{c, cfg, log_n, tr.chs, blobs};
+    const size_t apow_seg = 2 * (maxp + 1);
+    std::vector<gl_t> apow(K * apow_seg);
+    for (size_t k = 0; k < K; k++) alpha_powers(zkm_challenger_get_ext(tr.chs[k]), maxp, apow.data() + k * apow_seg);
+    // (zkm_ctx::upload is done with its source when it returns: no wait for the stream before the host vectors go)
+    gl_t* d_apow = f.scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
+    c->upload(d_apow, apow.data(), apow.size() * sizeof(gl_t));
+    zkm_fri_poly* d_list = f.scratch.alloc<zkm_fri_poly>(list.size() * sizeof(zkm_fri_poly));
+    c->upload(d_list, list.data(), list.size() * sizeof(zkm_fri_poly));
+    gl_t* d_comp = f.scratch.alloc<gl_t>(K * 2 * nbatches * n * sizeof(gl_t));
+    {
+        zkm_prof_scope ps(c, "fri_combine");
+        hipLaunchKernelGGL(k_fri_combine_lists, dim3((unsigned)((n + 255) / 256), (unsigned)nbatches, (unsigned)K), dim3(256), 0, c->stream, A, d_list,
+                           d_apow, apow_seg, n, d_comp);
+        ZKM_HIP_CHECK(hipGetLastError());
+    }
+    std::vector<std::vector<fri_composite>> comps(K);
+    for (size_t k = 0; k < K; k++)
+        for (size_t b = 0; b < nbatches; b++) {
+            const uint64_t* pt = points + (k * nbatches + b) * 2;
+            const gl_t* shift = apow.data() + k * apow_seg + 2 * batches[b].npolys;
+            comps[k].push_back({nullptr, nullptr, gl2_t{pt[0], pt[1]}, gl2_t{shift[0], shift[1]}});
+        }
+    fri_finish(f, y, oracles[0]->coeff_s1, d_comp, std::move(comps), oracles, noracles);
+    tr.commit();
+}
+
+// one claim on single commitments: the points are the batches' own
 int zkm_fri_prove(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles, const zkm_fri_batch* batches,
                   size_t nbatches, zkm_challenger* ch_io, uint64_t* proof, char** err) {
     return zkm_api("zkm_fri_prove", c, err, [&] {
         if (!cfg || !oracles || !batches || !nbatches || !ch_io || !proof) throw std::runtime_error("zkm_fri_prove: null argument");
-        if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error("zkm_fri_prove: 1..8 oracles");
-        const unsigned log_n = oracles[0]->log_n;
-        size_t cols[ZKM_FRI_MAX_ORACLES];
-        for (size_t k = 0; k < noracles; k++) {
-            if (!oracles[k] || oracles[k]->log_n != log_n || oracles[k]->rate_bits != cfg->rate_bits || oracles[k]->cap_height != cfg->cap_height ||
-                oracles[k]->coeff_s1 != oracles[0]->coeff_s1)
-                throw std::runtime_error("zkm_fri_prove: oracles must share degree, rate and cap height with the config");
-            if (oracles[k]->nseg != 1) throw std::runtime_error("zkm_fri_prove: stacked batches are internal");
-            cols[k] = oracles[k]->ncols;
+        if (nbatches > FRI_MAX_BATCHES) throw std::runtime_error("FRI: 1..8 opening batches");   // (this entry's words for it: divide_accumulate_all's)
+        for (size_t o = 0; o < noracles; o++) {
+            if (!oracles[o]) throw std::runtime_error("zkm_fri_prove: oracles must share degree, rate and cap height with the config");
+            if (oracles[o]->nseg != 1) throw std::runtime_error("zkm_fri_prove: stacked batches are internal");
         }
-        const zkm_fri_part y = zkm_fri_blob_describe(cfg, log_n, cols, noracles);
-        const size_t n = (size_t)1 << log_n;
-        size_t maxp = 0;
-        for (size_t b = 0; b < nbatches; b++) {
-            if (batches[b].npolys == 0 || !batches[b].polys) throw std::runtime_error("zkm_fri_prove: empty batch");
-            if (batches[b].point[0] >= GL_P || batches[b].point[1] >= GL_P) throw std::runtime_error("zkm_fri_prove: non-canonical opening point");
-            for (size_t j = 0; j < batches[b].npolys; j++)
-                if (batches[b].polys[j].oracle >= noracles || batches[b].polys[j].poly >= cols[batches[b].polys[j].oracle])
-                    throw std::runtime_error("zkm_fri_prove: polynomial index out of range");
-            maxp = std::max(maxp, batches[b].npolys);
-        }
-        memset(proof, 0, y.total() * sizeof(uint64_t));
-        zkm_fri_blob_header_write(proof, cfg, log_n, y);
-
-        zkm_transcripts tr(ch_io);
-        const std::vector<uint64_t*> blobs{proof};
-        proof_stack f{c, cfg, log_n, tr.chs, blobs};
-        std::vector<gl_t> apow(2 * (maxp + 1));
-        alpha_powers(zkm_challenger_get_ext(tr.chs[0]), maxp, apow.data());
-        gl_t* d_apow = f.scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
-        c->upload(d_apow, apow.data(), apow.size() * sizeof(gl_t));
-        gl_t* d_comp = f.scratch.alloc<gl_t>(2 * nbatches * n * sizeof(gl_t));
-        std::vector<const gl_t*> ptrs;
-        for (size_t b = 0; b < nbatches; b++)
-            for (size_t j = 0; j < batches[b].npolys; j++) ptrs.push_back(oracles[batches[b].polys[j].oracle]->coeffs + (size_t)batches[b].polys[j].poly * n);
-        const gl_t** d_ptrs = f.scratch.alloc<const gl_t*>(ptrs.size() * sizeof(gl_t*));
-        c->upload((void*)d_ptrs, ptrs.data(), ptrs.size() * sizeof(gl_t*));
-        std::vector<std::vector<fri_composite>> comps(1);
-        for (size_t b = 0, first = 0; b < nbatches; first += batches[b++].npolys) {
-            zkm_prof_scope ps(c, "fri_combine");
-            hipLaunchKernelGGL(k_fri_combine_generic, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_ptrs + first, batches[b].npolys, d_apow, n,
-                               d_comp + 2 * b * n, d_comp + (2 * b + 1) * n);
-            ZKM_HIP_CHECK(hipGetLastError());
-            const size_t np = batches[b].npolys;
-            comps[0].push_back({nullptr, nullptr, gl2_t{batches[b].point[0], batches[b].point[1]}, gl2_t{apow[2 * np], apow[2 * np + 1]}});
-        }
-        ZKM_HIP_CHECK(hipStreamSynchronize(c->stream));  // host vectors (ptrs, apow) are consumed
-        fri_finish(f, y, oracles[0]->coeff_s1, d_comp, std::move(comps), oracles, noracles);
-        tr.commit();
+        uint64_t points[2 * FRI_MAX_BATCHES];
+        for (size_t b = 0; b < nbatches; b++) { points[2 * b] = batches[b].point[0]; points[2 * b + 1] = batches[b].point[1]; }
+        fri_prove_claims("zkm_fri_prove", false, c, cfg, oracles, noracles, batches, nbatches, 1, points, &ch_io, &proof);
     });
 }
 
-// K opening proofs of one instance in LOCK-STEP: the oracles are stacks of K members (zkm_batch_commit_*_stack), claim k is zkm_fri_prove
-// on member k of every oracle at points[k].  One combination launch for all batches and claims, then fri_finish on a proof_stack of K.
+// one claim a member of the oracles' stacks (zkm_batch_commit_*_stack), at points of its own
 int zkm_fri_prove_stack(zkm_ctx* c, const zkm_stark_config* cfg, const zkm_batch* const* oracles, size_t noracles, const zkm_fri_batch* batches,
                         size_t nbatches, const uint64_t* points, zkm_challenger* const* challengers, uint64_t* const* proofs_out, char** err) {
     return zkm_api("zkm_fri_prove_stack", c, err, [&] {
         if (!cfg || !oracles || !batches || !nbatches || !points || !challengers || !proofs_out) throw std::runtime_error("zkm_fri_prove_stack: null argument");
-        if (noracles == 0 || noracles > ZKM_FRI_MAX_ORACLES) throw std::runtime_error("zkm_fri_prove_stack: 1..8 oracles");
-        if (nbatches > FRI_MAX_BATCHES) throw std::runtime_error("zkm_fri_prove_stack: 1..8 opening batches");
-        for (size_t o = 0; o < noracles; o++)
-            if (!oracles[o]) throw std::runtime_error("zkm_fri_prove_stack: null argument");
-        const size_t K = oracles[0]->nseg;
-        if (K == 0 || K > ZKM_MAX_SEG) throw std::runtime_error("zkm_fri_prove_stack: 1..32 claims");
-        const unsigned log_n = oracles[0]->log_n;
-        size_t cols[ZKM_FRI_MAX_ORACLES];
-        for (size_t o = 0; o < noracles; o++) {
-            if (oracles[o]->nseg != K) throw std::runtime_error("zkm_fri_prove_stack: oracles must be stacks of one size");
-            if (oracles[o]->log_n != log_n || oracles[o]->rate_bits != cfg->rate_bits || oracles[o]->cap_height != cfg->cap_height ||
-                oracles[o]->coeff_s1 != oracles[0]->coeff_s1)
-                throw std::runtime_error("zkm_fri_prove_stack: oracles must share degree, rate and cap height with the config");
-            cols[o] = oracles[o]->ncols;
-        }
-        const zkm_fri_part y = zkm_fri_blob_describe(cfg, log_n, cols, noracles);
-        const size_t n = (size_t)1 << log_n;
-        fri_stack_args A{};
-        std::vector<zkm_fri_poly> list;
-        size_t maxp = 0;
-        for (size_t b = 0; b < nbatches; b++) {
-            if (batches[b].npolys == 0 || !batches[b].polys) throw std::runtime_error("zkm_fri_prove_stack: empty batch");
-            for (size_t j = 0; j < batches[b].npolys; j++)
-                if (batches[b].polys[j].oracle >= noracles || batches[b].polys[j].poly >= cols[batches[b].polys[j].oracle])
-                    throw std::runtime_error("zkm_fri_prove_stack: polynomial index out of range");
-            list.insert(list.end(), batches[b].polys, batches[b].polys + batches[b].npolys);
-            if (list.size() > UINT32_MAX) throw std::runtime_error("zkm_fri_prove_stack: too many polynomials");
-            A.first[b + 1] = (uint32_t)list.size();
-            maxp = std::max(maxp, batches[b].npolys);
-        }
-        for (size_t k = 0; k < K; k++) {
-            const std::string claim = "zkm_fri_prove_stack: claim " + std::to_string(k);
-            if (!challengers[k] || !proofs_out[k]) throw std::runtime_error(claim + ": null argument");
-            for (size_t w = 0; w < 2 * nbatches; w++)
-                if (points[k * 2 * nbatches + w] >= GL_P) throw std::runtime_error(claim + ": non-canonical opening point");
-        }
-        for (size_t o = 0; o < noracles; o++) { A.base[o] = oracles[o]->coeffs; A.member[o] = oracles[o]->coeff_seg(); }
-        for (size_t k = 0; k < K; k++) {
-            memset(proofs_out[k], 0, y.total() * sizeof(uint64_t));
-            zkm_fri_blob_header_write(proofs_out[k], cfg, log_n, y);
-        }
-
-        zkm_transcripts tr(challengers, K);
-        const std::vector<uint64_t*> blobs(proofs_out, proofs_out + K);
-        proof_stack f{c, cfg, log_n, tr.chs, blobs};
-        const size_t apow_seg = 2 * (maxp + 1);
-        std::vector<gl_t> apow(K * apow_seg);
-        for (size_t k = 0; k < K; k++) alpha_powers(zkm_challenger_get_ext(tr.chs[k]), maxp, apow.data() + k * apow_seg);
-        gl_t* d_apow = f.scratch.alloc<gl_t>(apow.size() * sizeof(gl_t));
-        c->upload(d_apow, apow.data(), apow.size() * sizeof(gl_t));
-        zkm_fri_poly* d_list = f.scratch.alloc<zkm_fri_poly>(list.size() * sizeof(zkm_fri_poly));
-        c->upload(d_list, list.data(), list.size() * sizeof(zkm_fri_poly));
-        gl_t* d_comp = f.scratch.alloc<gl_t>(K * 2 * nbatches * n * sizeof(gl_t));
-        {
-            zkm_prof_scope ps(c, "fri_combine");
-            hipLaunchKernelGGL(k_fri_combine_stack, dim3((unsigned)((n + 255) / 256), (unsigned)nbatches, (unsigned)K), dim3(256), 0, c->stream, A, d_list,
-                               d_apow, apow_seg, n, d_comp);
-            ZKM_HIP_CHECK(hipGetLastError());
-        }
-        std::vector<std::vector<fri_composite>> comps(K);
-        for (size_t k = 0; k < K; k++)
-            for (size_t b = 0; b < nbatches; b++) {
-                const uint64_t* pt = points + (k * nbatches + b) * 2;
-                const gl_t* shift = apow.data() + k * apow_seg + 2 * batches[b].npolys;
-                comps[k].push_back({nullptr, nullptr, gl2_t{pt[0], pt[1]}, gl2_t{shift[0], shift[1]}});
-            }
-        fri_finish(f, y, oracles[0]->coeff_s1, d_comp, std::move(comps), oracles, noracles);
-        tr.commit();
+        const size_t K = noracles && oracles[0] ? oracles[0]->nseg : 0;   // (no oracle, a null one: refused in the body before K is looked at)
+        fri_prove_claims("zkm_fri_prove_stack", true, c, cfg, oracles, noracles, batches, nbatches, K, points, challengers, proofs_out);
     });
 }
 
@@ -2065,29 +2020,30 @@ int zkm_check_constraints(zkm_ctx* c, int table_id, const zkm_stark_config* cfg,
     });
 }
 
+// every member of a stack (a single commitment: of one) at the member's own point: the member is the grid's z in k_open_powers /
+// k_open_partials, one download
+static void eval_openings_members(zkm_ctx* c, const zkm_batch* b, const uint64_t* zetas, uint64_t* out) {
+    std::vector<gl2_t> z(b->nseg);
+    for (size_t k = 0; k < b->nseg; k++) z[k] = gl2_t{zetas[2 * k], zetas[2 * k + 1]};
+    const auto v = eval_batches(c, {b}, z.data(), z.data());
+    for (size_t k = 0; k < b->nseg; k++)
+        for (size_t i = 0; i < b->ncols; i++) {
+            out[2 * (k * b->ncols + i)] = v[k][0][i].at_z0.c0;
+            out[2 * (k * b->ncols + i) + 1] = v[k][0][i].at_z0.c1;
+        }
+}
 int zkm_eval_openings(zkm_ctx* c, const zkm_batch* b, const uint64_t zeta[2], uint64_t* out, char** err) {
     return zkm_api("zkm_eval_openings", c, err, [&] {
         if (!b || !zeta || !out) throw std::runtime_error("zkm_eval_openings: null argument");
-        gl2_t z{zeta[0], zeta[1]};
         if (b->nseg != 1) throw std::runtime_error("zkm_eval_openings: stacked batches are internal");
-        auto v = eval_batches(c, {b}, &z, &z)[0][0];
-        for (size_t i = 0; i < b->ncols; i++) { out[2 * i] = v[i].at_z0.c0; out[2 * i + 1] = v[i].at_z0.c1; }
+        eval_openings_members(c, b, zeta, out);
     });
 }
-
-// ... of every member of a stack at the member's own point: the member is the grid's z in k_open_powers / k_open_partials, one download
 int zkm_eval_openings_stack(zkm_ctx* c, const zkm_batch* b, const uint64_t* zetas, uint64_t* out, char** err) {
     return zkm_api("zkm_eval_openings_stack", c, err, [&] {
         if (!b || !zetas || !out) throw std::runtime_error("zkm_eval_openings_stack: null argument");
         if (b->nseg == 0 || b->nseg > ZKM_MAX_SEG) throw std::runtime_error("zkm_eval_openings_stack: 1..32 members");
-        std::vector<gl2_t> z(b->nseg);
-        for (size_t k = 0; k < b->nseg; k++) z[k] = gl2_t{zetas[2 * k], zetas[2 * k + 1]};
-        const auto v = eval_batches(c, {b}, z.data(), z.data());
-        for (size_t k = 0; k < b->nseg; k++)
-            for (size_t i = 0; i < b->ncols; i++) {
-                out[2 * (k * b->ncols + i)] = v[k][0][i].at_z0.c0;
-                out[2 * (k * b->ncols + i) + 1] = v[k][0][i].at_z0.c1;
-            }
+        eval_openings_members(c, b, zetas, out);
     });
 }
 

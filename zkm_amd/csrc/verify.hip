@@ -270,7 +270,7 @@ struct fri_claim_dev {
 
 // plonky2 fri_verifier_query_round without the Merkle proofs, for any instance: one thread per (claim, query).  fri_combine_initial
 // (fri/verifier.rs): per batch in instance order the alpha-reduction of its polynomials' values at x, minus the batch's reduced opening,
-// over (x - point); ReducingFactor::shift chains the batches by alpha^npolys -- what k_fri_combine_generic and shift_poly do in
+// over (x - point); ReducingFactor::shift chains the batches by alpha^npolys -- what k_fri_combine_lists and shift_poly do in
 // zkm_fri_prove.  Everything the lanes of a claim share -- the description, the challenges, the batches and their polynomial lists -- is
 // uniform over the workgroup and went up before the launch: it is read through the constant address space (scalar loads), as the calls'
 // expansions read their descriptors (zkm_seg_desc).  A base-field point on the LDE coset is refused on the host: x - point is never 0.

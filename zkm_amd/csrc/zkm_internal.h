@@ -553,6 +553,10 @@ int zkm_live_contexts();   // contexts of this process that exist right now (zkm
 // src_cols (optional, instead of src): one pointer per column (each n words, host or device).
 void zkm_batch_build(zkm_batch* b, const uint64_t* src, bool src_is_values, gl_t* dev_values = nullptr,
                      const uint64_t* const* src_cols = nullptr, const uint64_t* const* seg_srcs = nullptr);
+// a new batch of nseg members committed to srcs[0 .. nseg) (values, or coefficients in natural order; host or device): the one place that
+// chooses between zkm_batch_build's single form (nseg == 1: srcs[0]) and its per-member sources (throws)
+zkm_batch_ptr zkm_batch_commit(zkm_ctx* c, const uint64_t* const* srcs, size_t nseg, size_t ncols, unsigned log_n, unsigned rate_bits,
+                               unsigned cap_height, bool are_values);
 zkm_batch* zkm_batch_commit_values_keep(zkm_ctx* c, const uint64_t* values, size_t ncols, unsigned log_n, unsigned rate_bits,
                                         unsigned cap_height, gl_t* dev_values, const uint64_t* const* columns = nullptr);
 // stark.hip: prove_single_table from existing (stacked) trace and auxiliary commitments, for chs.size() proofs in lock-step (throws)
